@@ -5,20 +5,26 @@ Headline workload (BASELINE.json configs[1], "C2"): 10 M x 150 bp synthetic shor
 (seed 1002), gap-affine 0/4/6/2, end-to-end, scope=score.  One "step" = one pass of the alignment kernels
 over the whole batch, with the 2-bit packed sequences already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU (the driver launches torch.distributed.run; `python bench.py --gpus N` without a
 WORLD_SIZE spawns it itself); every rank aligns its own P pairs (weak scaling, pairs are independent: no
 collective on the data path); barrier + device sync on both sides of the timed region, MAX over ranks, rank 0
 prints ONE JSON line.
 
-The LAST stdout line is one compact strict-JSON record (about 5 KB; tests/test_bench_line.py): the contract keys, `config` (workload + one
-scalar triple per extra configuration), `roofline`, `cpu_baseline`, `end_to_end` as scalars.  The fat record described below goes to
-bench_detail.json (and gpurun_out/bench_detail.json); a failed configuration, a parity mismatch or an invalid transcript ends the run non-zero.
-N > 1: every rank also times a C3 leg (10 kb, wf-adaptive, full CIGAR; `config.c3_alignments_per_s`).  --multi: only the C5 leg through ONE
-process's wfa_hip_multi_align_batch over every visible device.
+A plain run does only what the headline needs: generate the batch, warm up, time exactly K steps, write the outputs of the last
+step if --dump-outputs is given, print the line (the contract keys, `config` with the workload, `roofline` of the timed steps).
+--dump-outputs DIR: the last timed step's per-pair `score` and `status` (what a caller of the path receives) as DIR/<name>.npy in
+float64; where the whole would exceed 64 MB, a fixed seeded sample of the pairs (dump_outputs).
 
-Besides the contract keys the detail record carries (rank 0, N = 1):
+--full adds everything else the benchmark measures and checks, described below.  The LAST stdout line is then one compact strict-JSON
+record (about 5 KB; tests/test_bench_line.py): the contract keys, `config` (workload + one scalar triple per extra configuration),
+`roofline`, `cpu_baseline`, `end_to_end` as scalars.  The fat record goes to a side file, bench_detail.json; a failed configuration, a
+parity mismatch or an invalid transcript ends the run non-zero.  N > 1 with --full: every rank also times a C3 leg (10 kb, wf-adaptive,
+full CIGAR; `config.c3_alignments_per_s`).  --multi: only the C5 leg through ONE process's wfa_hip_multi_align_batch over every visible
+device.
+
+Besides the contract keys the --full detail record carries (rank 0, N = 1):
   roofline      HBM roofline of the C2 step (HIP events on the launch stream), + "secondary": the on-chip bound
                 from the committed counter passes (profiles/), + "traffic" with its provenance
   end_to_end    the PCIe-inclusive rate of the same batch: host ASCII in -> host results out (wfa_hip_align_batch)
@@ -145,6 +151,27 @@ def run_resident(al, batch, steps, warmup, want_cigar, barrier=None, min_seconds
            "fallback": rb.fallback_pairs(), "io_bytes": rb.algorithmic_bytes(), "steps": steps}
     rb.close()
     return out
+
+
+DUMP_LIMIT = 64_000_000   # bytes of .npy files one --dump-outputs run writes at most, over all ranks
+DUMP_SEED = 20251016      # the seed of the sample of pairs written where the whole would exceed DUMP_LIMIT
+
+
+def dump_outputs(d, arrays, rank=0, world=1):
+    """--dump-outputs: `arrays` (name -> one value per pair, all of one length) as d/<name>.npy in float64, exact for int32 results.
+    Where they would exceed this rank's share of DUMP_LIMIT, every array is written at the same pairs: a fixed sample drawn with
+    DUMP_SEED, in pair order.  N > 1: every rank writes its own shard as d/<name>_rank<r>.npy."""
+    n = len(next(iter(arrays.values())))
+    cap = (DUMP_LIMIT // world - 4096) // (8 * len(arrays))   # (4 KB for the .npy headers)
+    idx = None
+    if n > cap:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert len(a) == n, name
+        np.save(os.path.join(d, name + (f"_rank{rank}" if world > 1 else "") + ".npy"),
+                (a if idx is None else a[idx]).astype(np.float64))
 
 
 def counter_file(name, src_hash):
@@ -534,6 +561,98 @@ def multi_leg(pairs_per_device, length=100000, calls=2):
     return out
 
 
+def end_to_end_legs(al, cfg, batch, args, score, status, rank, n_gpus, local_rank, dist, backend):
+    """--full: the PCIe-inclusive rate of the C2 batch through `al` (closed on the way) and its variants.  Returns the scalars that
+    go into `config` and the `end_to_end` record."""
+    from pywfa_amd import _native, datagen
+    # PCIe-inclusive rate (host ASCII in -> host results out): eight calls, the first (it pins and sizes the staging) left out; the line
+    # carries the MEDIAN as the figure, with the minimum and every call's time beside it (VERDICT r05: a best-of-five hid a 2x spread)
+    # (results into caller-owned arrays, as a C caller has them: fresh 2 x 40 MB NumPy arrays per call cost ~10 ms of page faults)
+    def time_e2e(a, calls, what=None):
+        what = batch if what is None else what
+        ts = []
+        outs = (np.zeros(args.pairs, np.int32), np.zeros(args.pairs, np.int32))
+        for _ in range(calls + 1):
+            t0 = time.perf_counter()
+            s2, st2, _ = a.align_batch(what, False, out=outs)
+            ts.append(time.perf_counter() - t0)
+        assert np.array_equal(s2, score) and np.array_equal(st2, status)
+        ts = ts[1:]
+        return {"median": float(np.median(ts)), "min": float(min(ts)), "max": float(max(ts)), "calls": [round(x, 5) for x in ts]}
+    dist_barrier(dist, backend)
+    e2e_stats = time_e2e(al, 7)
+    upload_info = al.upload_info()
+    t_e2e = dist_max(dist, backend, e2e_stats["median"])   # (N > 1: every rank's call at once, the host cores shared: the slowest rank counts)
+    # a caller that holds 2-bit reads already (wfa_hip_align_batch_packed2bits): no host packing, a quarter of the bytes
+    # (N > 1 too, every rank at once, the slowest counted: with ASCII input eight ranks read 8 x 300 B per pair from host memory — the
+    # 2-bit entry and the resident rate are the figures that can scale with the devices, DESIGN §6.3)
+    pk = datagen.to_packed2bits(batch)
+    dist_barrier(dist, backend)
+    e2e_2bit_stats = time_e2e(al, 5, pk)
+    t_e2e_2bit = dist_max(dist, backend, e2e_2bit_stats["median"])
+    del pk
+    al.close()
+    # the same call with the upload workers bound to the GPU's NUMA node (WFA_HIP_NUMA=1, round 5's behaviour): the A/B leg VERDICT r05 asked
+    # for — the default leaves the scheduler alone (csrc/wfa_hip.hip: numa_lookup has the measurements)
+    e2e_bound_stats = None
+    if rank == 0 and n_gpus == 1 and args.pairs >= 262144 and upload_info["gpu_node_cpus"] > 0:
+        os.environ["WFA_HIP_NUMA"] = "1"
+        alb = _native.Aligner(cfg, device=local_rank)
+        e2e_bound_stats = time_e2e(alb, 5)
+        e2e_bound_stats["upload_info"] = alb.upload_info()
+        alb.close()
+        del os.environ["WFA_HIP_NUMA"]
+    # the same call with the host packer off (ASCII over PCIe + device pack kernel), for the record
+    t_e2e_ascii = None
+    if rank == 0 and n_gpus == 1 and args.pairs >= 262144:
+        os.environ["WFA_HIP_HOST_PACK"] = "0"
+        al0 = _native.Aligner(cfg, device=local_rank)   # (the knobs are read when the aligner is created)
+        del os.environ["WFA_HIP_HOST_PACK"]
+        t_e2e_ascii = time_e2e(al0, 2)["median"]
+        al0.close()
+
+    e2e_rate = args.pairs / t_e2e
+    ascii_bytes = float(batch["p_len"].sum() + batch["t_len"].sum()) / args.pairs + 8
+    host_packed = args.pairs >= 262144   # (csrc/wfa_hip.hip batch_build: the large-batch form)
+    words = float((((batch["p_len"].astype(np.int64) + 15) >> 4) + ((batch["t_len"].astype(np.int64) + 15) >> 4)).sum()) / args.pairs
+    # host-packed: the 2-bit words + 4 B of 16-bit lengths per pair up (round 6: the 16 B metadata records are rebuilt on the device),
+    # 8 B of results down; small batches: the ASCII bytes + 16 B metadata + 16 B byte offsets
+    sent_bytes = (4 * words + 4 + 8) if host_packed else (ascii_bytes + 32)
+    config = {
+        # (wfa_hip_align_batch pays the pilot that chooses the first stage's width on every call: these figures include it)
+        "end_to_end_includes_pilot": True,
+        # `value` is the HBM-resident rate; the PCIe-inclusive rate of the same batch (host ASCII in -> host results out, every
+        # rank's call at once, the slowest rank counted) is never `value` but belongs beside it (full detail: "end_to_end")
+        "end_to_end_alignments_per_s": e2e_rate * n_gpus, "end_to_end_seconds_per_batch": t_e2e,
+        "end_to_end_pcie_frac": e2e_rate * sent_bytes / 1e9 / PCIE_PEAK_GBS,
+        "end_to_end_2bit_input_alignments_per_s": None if t_e2e_2bit is None else args.pairs * n_gpus / t_e2e_2bit}
+    record = {"value": e2e_rate * n_gpus, "unit": "alignments/s", "seconds_per_batch": t_e2e,
+              "what": "wfa_hip_align_batch: host ASCII in -> host scores/status out (host threads pack to 2 bits into the pinned "
+                      "upload ring, DMA, align, download); results into caller-owned arrays",
+              "statistic": "median of 7 calls after one warm-up call", "seconds_min": e2e_stats["min"], "seconds_max": e2e_stats["max"],
+              "seconds_calls": e2e_stats["calls"], "value_best_call": args.pairs / e2e_stats["min"] * n_gpus,
+              "host": upload_info,
+              "workers_bound_to_gpu_numa_node": None if e2e_bound_stats is None else {
+                  "value": args.pairs / e2e_bound_stats["median"], "seconds_per_batch": e2e_bound_stats["median"],
+                  "seconds_min": e2e_bound_stats["min"], "seconds_calls": e2e_bound_stats["calls"], "host": e2e_bound_stats["upload_info"],
+                  "what": "WFA_HIP_NUMA=1: the spawned upload workers bound to the CPUs of the GPU's NUMA node (round 5's default)"},
+              "includes_pilot": True, "ascii_bytes_per_pair": ascii_bytes, "ascii_gb_s_consumed": e2e_rate * ascii_bytes / 1e9,
+              "pcie_bytes_per_pair": sent_bytes, "pcie_gb_s": e2e_rate * sent_bytes / 1e9,
+              "pcie_frac": e2e_rate * sent_bytes / 1e9 / PCIE_PEAK_GBS,
+              "packed2bits_input": None if t_e2e_2bit is None else {
+                  "value": args.pairs * n_gpus / t_e2e_2bit, "seconds_per_batch": t_e2e_2bit, "seconds_min": e2e_2bit_stats["min"],
+                  "seconds_calls": e2e_2bit_stats["calls"],
+                  "what": "wfa_hip_align_batch_packed2bits: the caller holds 2-bit reads (4 bases per byte); the upload workers re-base them "
+                          "to whole words on their way into the pinned ring (round 6): the same bytes cross PCIe as for ASCII input",
+                  "pcie_bytes_per_pair": sent_bytes},
+              "ascii_upload": None if t_e2e_ascii is None else {
+                  "value": args.pairs / t_e2e_ascii, "seconds_per_batch": t_e2e_ascii,
+                  "what": "WFA_HIP_HOST_PACK=0: the ASCII blob crosses PCIe, the device packs it",
+                  "pcie_gb_s": args.pairs / t_e2e_ascii * (ascii_bytes + 32) / 1e9,
+                  "pcie_frac": args.pairs / t_e2e_ascii * (ascii_bytes + 32) / 1e9 / PCIE_PEAK_GBS}}
+    return config, record
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -550,6 +669,12 @@ def main():
                     help="only the C5 leg: one process, wfa_hip_multi_align_batch over every visible device")
     ap.add_argument("--multi-pairs", type=int, default=8192, help="100 kb pairs per device of the C5 leg (at most 16 384 pairs in all; "
                     "BASELINE's C5 is 12 500 per device; 4 096 pairs leave the first stage's launches half empty: 23 k against 36 k aln/s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: end-to-end rates, work counts, the CPU reference baseline "
+                         "and its parity check, the extra configurations, the Python and C5 multi-device legs, the C3 leg of N > 1 runs, "
+                         "the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's per-pair results (score, status) as DIR/<name>.npy in float64")
     args = ap.parse_args()
 
     if args.multi:
@@ -615,54 +740,14 @@ def main():
     elapsed = dist_max(dist, backend, r["elapsed"])
     c2_spread = rank_spread([args.pairs * args.steps / t for t in dist_all(dist, backend, r["elapsed"])])
     kernel_ms, score, status = r["kernel_ms"], r["score"], r["status"]
-    # PCIe-inclusive rate (host ASCII in -> host results out): eight calls, the first (it pins and sizes the staging) left out; the line
-    # carries the MEDIAN as the figure, with the minimum and every call's time beside it (a best-of-five hid a 2x spread)
-    # (results into caller-owned arrays, as a C caller has them: fresh 2 x 40 MB NumPy arrays per call cost ~10 ms of page faults)
-    def time_e2e(a, calls, what=None):
-        what = batch if what is None else what
-        ts = []
-        outs = (np.zeros(args.pairs, np.int32), np.zeros(args.pairs, np.int32))
-        for _ in range(calls + 1):
-            t0 = time.perf_counter()
-            s2, st2, _ = a.align_batch(what, False, out=outs)
-            ts.append(time.perf_counter() - t0)
-        assert np.array_equal(s2, score) and np.array_equal(st2, status)
-        ts = ts[1:]
-        return {"median": float(np.median(ts)), "min": float(min(ts)), "max": float(max(ts)), "calls": [round(x, 5) for x in ts]}
-    dist_barrier(dist, backend)
-    e2e_stats = time_e2e(al, 7)
-    upload_info = al.upload_info()
-    t_e2e = dist_max(dist, backend, e2e_stats["median"])   # (N > 1: every rank's call at once, the host cores shared: the slowest rank counts)
-    # a caller that holds 2-bit reads already (wfa_hip_align_batch_packed2bits): no host packing, a quarter of the bytes
-    # (N > 1 too, every rank at once, the slowest counted: with ASCII input eight ranks read 8 x 300 B per pair from host memory — the
-    # 2-bit entry and the resident rate are the figures that can scale with the devices)
-    pk = datagen.to_packed2bits(batch)
-    dist_barrier(dist, backend)
-    e2e_2bit_stats = time_e2e(al, 5, pk)
-    t_e2e_2bit = dist_max(dist, backend, e2e_2bit_stats["median"])
-    del pk
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"score": score, "status": status}, rank, world)
+    if args.full:
+        e2e_config, e2e = end_to_end_legs(al, cfg, batch, args, score, status, rank, n_gpus, local_rank, dist, backend)
     al.close()
-    # the same call with the upload workers bound to the GPU's NUMA node (WFA_HIP_NUMA=1, round 5's behaviour): the A/B leg VERDICT r05 asked
-    # for — the default leaves the scheduler alone (csrc/wfa_hip.hip: numa_lookup has the measurements)
-    e2e_bound_stats = None
-    if rank == 0 and n_gpus == 1 and args.pairs >= 262144 and upload_info["gpu_node_cpus"] > 0:
-        os.environ["WFA_HIP_NUMA"] = "1"
-        alb = _native.Aligner(cfg, device=local_rank)
-        e2e_bound_stats = time_e2e(alb, 5)
-        e2e_bound_stats["upload_info"] = alb.upload_info()
-        alb.close()
-        del os.environ["WFA_HIP_NUMA"]
-    # the same call with the host packer off (ASCII over PCIe + device pack kernel), for the record
-    t_e2e_ascii = None
-    if rank == 0 and n_gpus == 1 and args.pairs >= 262144:
-        os.environ["WFA_HIP_HOST_PACK"] = "0"
-        al0 = _native.Aligner(cfg, device=local_rank)   # (the knobs are read when the aligner is created)
-        del os.environ["WFA_HIP_HOST_PACK"]
-        t_e2e_ascii = time_e2e(al0, 2)["median"]
-        al0.close()
 
     c3 = None
-    if args.c3_leg or (n_gpus > 1 and not args.no_extra_configs):
+    if args.c3_leg or (args.full and n_gpus > 1 and not args.no_extra_configs):
         c3 = c3_leg(rank, world, local_rank, args.c3_pairs, 3, dist, backend)
 
     if rank == 0:
@@ -689,14 +774,6 @@ def main():
         value = total_pairs / elapsed
         alg_bytes = r["io_bytes"]
         achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
-        wc = work_counts(batch, cfg_kw, 20000)
-        e2e_rate = args.pairs / t_e2e
-        ascii_bytes = float(batch["p_len"].sum() + batch["t_len"].sum()) / args.pairs + 8
-        host_packed = args.pairs >= 262144   # (csrc/wfa_hip.hip batch_build: the large-batch form)
-        words = float((((batch["p_len"].astype(np.int64) + 15) >> 4) + ((batch["t_len"].astype(np.int64) + 15) >> 4)).sum()) / args.pairs
-        # host-packed: the 2-bit words + 4 B of 16-bit lengths per pair up (round 6: the 16 B metadata records are rebuilt on the device),
-        # 8 B of results down; small batches: the ASCII bytes + 16 B metadata + 16 B byte offsets
-        sent_bytes = (4 * words + 4 + 8) if host_packed else (ascii_bytes + 32)
         out = {
             "metric": "pairwise alignments/sec",
             "value": value,
@@ -714,18 +791,12 @@ def main():
             "data": "synthetic",
             "config": {"workload": f"C2: {args.pairs} x {args.length}bp pairs/GPU, {args.error * 100:g}% error, gap-affine 0/4/6/2, "
                                    "end-to-end, scope=score, 2-bit reads resident in HBM",
-                       # (the first stage's width is chosen by a pilot on 8192 pairs once per resident batch, outside the timed steps;
-                       #  wfa_hip_align_batch pays it on every call: the end_to_end figures below include it)
-                       "pilot_in_timed_region": False, "end_to_end_includes_pilot": True,
+                       # (the first stage's width is chosen by a pilot on 8192 pairs once per resident batch, outside the timed steps)
+                       "pilot_in_timed_region": False,
                        "pairs_per_gpu": args.pairs, "read_length": args.length, "parallelism": f"pairs sharded over {n_gpus} GPU(s), no collective",
                        # per-rank rates of the timed steps (weak scaling: every rank the same work; `value` is all pairs over the slowest rank's time)
                        "rank_alignments_per_s_min": c2_spread["min"], "rank_alignments_per_s_max": c2_spread["max"],
-                       "rank_imbalance": c2_spread["imbalance"],
-                       # `value` is the HBM-resident rate; the PCIe-inclusive rate of the same batch (host ASCII in -> host results out, every
-                       # rank's call at once, the slowest rank counted) is never `value` but belongs beside it (full detail: "end_to_end")
-                       "end_to_end_alignments_per_s": e2e_rate * n_gpus, "end_to_end_seconds_per_batch": t_e2e,
-                       "end_to_end_pcie_frac": e2e_rate * sent_bytes / 1e9 / PCIE_PEAK_GBS,
-                       "end_to_end_2bit_input_alignments_per_s": None if t_e2e_2bit is None else args.pairs * n_gpus / t_e2e_2bit},
+                       "rank_imbalance": c2_spread["imbalance"]},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_provenance": provenance,
                          "secondary": secondary,
@@ -733,36 +804,17 @@ def main():
                          "secondary_frac": None if not secondary else secondary.get("frac"),
                          "algorithmic_bytes_per_launch": alg_bytes, "bytes_per_pair": alg_bytes / max(args.pairs, 1),
                          "kernel_ms": kernel_ms, "kernel": "wfa alignment kernels of one step (HIP events on the launch stream)"},
-            "offsets_per_s": value * wc["offsets_per_pair"],
-            "end_to_end": {"value": e2e_rate * n_gpus, "unit": "alignments/s", "seconds_per_batch": t_e2e,
-                           "what": "wfa_hip_align_batch: host ASCII in -> host scores/status out (host threads pack to 2 bits into the pinned "
-                                   "upload ring, DMA, align, download); results into caller-owned arrays",
-                           "statistic": "median of 7 calls after one warm-up call", "seconds_min": e2e_stats["min"], "seconds_max": e2e_stats["max"],
-                           "seconds_calls": e2e_stats["calls"], "value_best_call": args.pairs / e2e_stats["min"] * n_gpus,
-                           "host": upload_info,
-                           "workers_bound_to_gpu_numa_node": None if e2e_bound_stats is None else {
-                               "value": args.pairs / e2e_bound_stats["median"], "seconds_per_batch": e2e_bound_stats["median"],
-                               "seconds_min": e2e_bound_stats["min"], "seconds_calls": e2e_bound_stats["calls"], "host": e2e_bound_stats["upload_info"],
-                               "what": "WFA_HIP_NUMA=1: the spawned upload workers bound to the CPUs of the GPU's NUMA node (round 5's default)"},
-                           "includes_pilot": True, "ascii_bytes_per_pair": ascii_bytes, "ascii_gb_s_consumed": e2e_rate * ascii_bytes / 1e9,
-                           "pcie_bytes_per_pair": sent_bytes, "pcie_gb_s": e2e_rate * sent_bytes / 1e9,
-                           "pcie_frac": e2e_rate * sent_bytes / 1e9 / PCIE_PEAK_GBS,
-                           "packed2bits_input": None if t_e2e_2bit is None else {
-                               "value": args.pairs * n_gpus / t_e2e_2bit, "seconds_per_batch": t_e2e_2bit, "seconds_min": e2e_2bit_stats["min"],
-                               "seconds_calls": e2e_2bit_stats["calls"],
-                               "what": "wfa_hip_align_batch_packed2bits: the caller holds 2-bit reads (4 bases per byte); the upload workers re-base them "
-                                       "to whole words on their way into the pinned ring (round 6): the same bytes cross PCIe as for ASCII input",
-                               "pcie_bytes_per_pair": sent_bytes},
-                           "ascii_upload": None if t_e2e_ascii is None else {
-                               "value": args.pairs / t_e2e_ascii, "seconds_per_batch": t_e2e_ascii,
-                               "what": "WFA_HIP_HOST_PACK=0: the ASCII blob crosses PCIe, the device packs it",
-                               "pcie_gb_s": args.pairs / t_e2e_ascii * (ascii_bytes + 32) / 1e9,
-                               "pcie_frac": args.pairs / t_e2e_ascii * (ascii_bytes + 32) / 1e9 / PCIE_PEAK_GBS}},
             "extra": {"mean_score": float(score.mean()), "completed": int((status == 0).sum()),
                       "fallback_pairs": int(r["fallback"]), "datagen_s": t_gen, "upload_pack_s": r["upload_s"],
-                      "work_per_pair": wc, "kernel_source_hash": src_hash},
+                      "kernel_source_hash": src_hash},
         }
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full:
+            wc = work_counts(batch, cfg_kw, 20000)
+            out["config"].update(e2e_config)
+            out["offsets_per_s"] = value * wc["offsets_per_pair"]
+            out["end_to_end"] = e2e
+            out["extra"]["work_per_pair"] = wc
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             from oracle import loader
             cpu, n_cpu, res = cpu_reference(batch, cfg_kw, args.pairs, 12.0, False)
             cpu["parity_checked_pairs"] = n_cpu
@@ -797,7 +849,7 @@ def main():
                 except Exception as e:  # the single-thread figure above is the reported baseline
                     cpu["all_threads"] = {"error": str(e)}
             out["cpu_baseline"] = cpu
-        if n_gpus == 1 and not args.no_extra_configs:
+        if args.full and n_gpus == 1 and not args.no_extra_configs:
             C4 = dict(distance="affine2p", span="ends-free", pattern_begin_free=100, pattern_end_free=100, scope="full")
             xs = []
             plan = [
@@ -911,7 +963,8 @@ def main():
         if (cb.get("all_threads") or {}).get("parity_mismatches"):
             errors.append(f"C2 (all threads): {cb['all_threads']['parity_mismatches']} parity mismatches")
         out["errors"] = errors
-        out["detail_file"] = write_detail(out)
+        if args.full:
+            out["detail_file"] = write_detail(out)
         # the LAST stdout line: one strict-JSON object well under the driver's 8 KB (tests/test_bench_line.py)
         print(format_line(compact_record(out)), flush=True)
     failed = bool(rank == 0 and out["errors"])

@@ -120,3 +120,26 @@ def test_transcript_checker_accepts_the_oracle_and_rejects_damage():
     ops[cbeg[5] + 10] = ord("X") if ops[cbeg[5] + 10] == ord("M") else ord("M")   # M over unequal / X over equal bases
     clen[7] -= 1                                    # does not consume the whole pattern / text
     assert bench.transcripts_valid(batch, score, status, (ops, cbeg, clen), kw, sample=n) == 3
+
+
+def test_dump_outputs_whole_or_one_seeded_sample_under_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files equal to the int32 results; over the size limit every array is written at the same pairs,
+    a sample in pair order that is the same from run to run, and the files stay within the limit."""
+    n = 10_000
+    score = (-7 * np.arange(n)).astype(np.int32)
+    status = (np.arange(n) % 3).astype(np.int32)
+    bench.dump_outputs(str(tmp_path / "whole"), {"score": score, "status": status})
+    s = np.load(tmp_path / "whole" / "score.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, score)
+    assert np.array_equal(np.load(tmp_path / "whole" / "status.npy"), status)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096 + 2 * 8 * 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"score": score, "status": status})
+    sa, sb = np.load(tmp_path / "a" / "score.npy"), np.load(tmp_path / "b" / "score.npy")
+    assert len(sa) == 1000 and np.array_equal(sa, sb)
+    idx = -sa / 7
+    assert (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), idx % 3)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in ("score.npy", "status.npy")) <= bench.DUMP_LIMIT
+    bench.dump_outputs(str(tmp_path / "r"), {"score": score, "status": status}, rank=1, world=2)
+    assert sum(os.path.getsize(tmp_path / "r" / f) for f in ("score_rank1.npy", "status_rank1.npy")) <= bench.DUMP_LIMIT // 2
