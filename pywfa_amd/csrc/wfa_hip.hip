@@ -51,7 +51,7 @@ static thread_local std::string g_error;
   F(ARENA_KB) F(BAND_DEBUG) F(BAND_SLIM) F(BAND_LDS_MAX) F(BAND_NO_WIN) F(BAND_SPLIT_MIN) F(NO_TINY_INLINE) F(BILEVEL) F(BILEVEL_WIDE_LEVELS) F(BILEVEL_PER_CU) F(BILEVEL_I32) F(BILEVEL_QCAP) F(BILEVEL_LEVELS) F(BILEVEL_LDS) F(BILEVEL_NO_1024) F(BILEVEL_HUGE_MIN) F(BILEVEL_LDS_W) F(BILEVEL_NO_SEQL) F(LANE_DYN) F(LANE_DYN_WAVES) F(BAND_LEFTOVER_WAVES_PER_CU) F(BAND_NCH) F(BAND_NO_LDS) F(BAND_NO_SPLIT) F(BAND_PB) F(PIPE_TAIL) F(LEN16) F(MAILBOX) F(MAILBOX_IDLE_US) F(TILE32)     \
   F(BAND_RECORDS) F(BAND_SPLIT_ROUNDS) F(BAND_WAVES_PER_CU) F(NO_BAND) F(NO_FAST) F(NO_SEGFULL) F(SEGFULL_PAIRS)     \
   F(SEGFULL_STAGES) F(STAGE_TIMING) F(LANE_HEUR32) F(THREADS) F(TINY_BATCH) F(WAVES_PER_CU) F(FAST_WAVES_PER_CU) F(TIMING)          \
-  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS)
+  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT)
 enum WfaKnob {
 #define WFA_KNOB_ENUM(n) K_##n,
   WFA_KNOBS(WFA_KNOB_ENUM)
@@ -258,6 +258,8 @@ struct wfa_hip_batch {
   // waits for it (the host-packed upload returns with its DMAs still in flight)
   hipEvent_t upload_event = nullptr;
   int stage_pick = 0;  // first register-kernel stage chosen by the pilot of the first run (0 = not yet): 16, 32 or 64 lanes
+  int narrow_pick = 0; // stage_pick 16, score only: the 8-diagonal lane stage in front of the 16-diagonal one (1) or not (2), 0 undecided
+  int narrow_permille = -1;   // ... and the share of its pilot's sample it handed on (-1: no pilot), which sizes the slices of the stage behind it
   int segh_pick = 0;   // the same for the general form of the 32-lane segments (wfa_seg_kernel<.., HEUR>)
   int band_pick = 0;   // exact reads of 300 - 1 200 bases: the 256-diagonal register window first (1) or not (2: its pilot handed on most pairs), 0 undecided
   int laneh_pick = 0;  // general score-only form of the lane kernel first (wf-adaptive / free ends / step limit): 1 yes, 2 no (its pilot), 0 undecided
@@ -1333,8 +1335,8 @@ static int batch_build(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, const u
 // The narrowest band that keeps most pairs is the cheapest first stage of the short-read cascade; it depends on the divergence
 // of the batch (16 lanes up to ~3 %, 32 up to ~6 %, 64 up to ~10 %).  A pilot on 8192 pairs sampled at a fixed stride across
 // the batch (score-only kernels, one-round form: a name of its own in a profile) decides once per batch, when the batch is
-// created: b->stage_pick = 16 / 32 / 64, or 128 = none of them.  (Up to three small launches, each waited for: it runs where
-// the upload is waited for anyway, so that wfa_hip_batch_run only enqueues.)
+// created: b->stage_pick = 16 / 32 / 64, or 128 = none of them; score only with 16 first, also b->narrow_pick.  (Up to four small
+// launches, each waited for: it runs where the upload is waited for anyway, so that wfa_hip_batch_run only enqueues.)
 // score_mode (csrc/wfa_common.hpp): the kernels leave -s; completed pairs get the score of the original configuration
 __global__ void __launch_bounds__(256) wfa_score_translate_kernel(int32_t* __restrict__ score, const int32_t* __restrict__ status,
                                                                   const WfaPairMeta* __restrict__ meta, long long n, int mode, int sw_match) {
@@ -1403,6 +1405,23 @@ static int pilot_first_width(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t 
     const uint32_t pct = (w == 16) ? (uint32_t)knob(al, K_PILOT_PCT, full ? 15 : 8) : 40u;
     if (knob(al, K_STAGE_TIMING, 0)) fprintf(stderr, "[wfa_hip] pilot: %d diagonals hand on %u of %u\n", w, handed, np);
     if (handed * 100u <= np * pct) { b->stage_pick = w; break; }
+  }
+  // Score only, 16 diagonals first: the 8-diagonal lane form (wfa_lane.hpp, NRP = 4) in front of it pays while it proves most pairs —
+  // what it hands on starts over in the 16-diagonal form.  Its own pass over the same sample decides (b->narrow_pick).
+  int X, OE, E;
+  if (!full && b->stage_pick == 16 && wfa::seg_shape(b->dcfg, &X, &OE, &E) != WFA_SHAPE_RTC) {
+    HIP_TRY(al, hipMemsetAsync(pcount, 0, sizeof(uint32_t), stream));
+    if (wfa::launch_lane(wfa::seg_shape(b->dcfg, &X, &OE, &E), wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1), al->cu_count,
+                         knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, b->d_words, b->d_meta, psample, nullptr, np,
+                         b->d_score, b->d_status, plist, pcount, nullptr, 0, X, OE, E, 0, nullptr, 0, 4) != 0) return pilot_launch_failed(al, b, rtc_failures);
+    uint32_t handed = 0;
+    HIP_TRY(al, hipMemcpyAsync(&handed, pcount, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(al, hipStreamSynchronize(stream));
+    // (150 bp, 2 M - 10 M pairs: 1 % and 2 % divergence, where it hands on 5 % / 18 %, 2-23 % faster; 3 % slower by 9 %)
+    const uint32_t pct = (uint32_t)knob(al, K_PILOT_NARROW_PCT, 20);
+    if (knob(al, K_STAGE_TIMING, 0)) fprintf(stderr, "[wfa_hip] pilot: 8 diagonals (lane form) hand on %u of %u\n", handed, np);
+    b->narrow_pick = (handed * 100u <= np * pct) ? 1 : 2;
+    b->narrow_permille = (int)((uint64_t)handed * 1000u / np);
   }
   HIP_TRY(al, hipMemsetAsync(pcount, 0, sizeof(uint32_t), stream));
   return WFA_HIP_OK;
@@ -2475,26 +2494,27 @@ static int batch_run_once(wfa_hip_batch_t* b, void* stream_) {
     }
     if (use_fast) {
       // register-kernel stages, each taking what the one before handed on (WFA_HIP_FAST_STAGES, one digit per
-      // stage): 1 = the lane-per-pair kernel (64 pairs per wave, band of 16 diagonals, wfa_lane.hpp); 7/6/8/9 = segments
-      // of 8/16/32/64 lanes with the two-round (lazy) extension, 3/2/4/5 = the same widths extending every cell at once
+      // stage): 1 = the lane-per-pair kernel (64 pairs per wave, band of 16 diagonals, wfa_lane.hpp), 0 = its 8-diagonal form (built-in
+      // penalty shapes only); 7/6/8/9 = segments of 8/16/32/64 lanes with the two-round (lazy) extension, 3/2/4/5 = the same widths
+      // extending every cell at once
       const char* stages_env = al->knobs.fast_stages.empty() ? nullptr : al->knobs.fast_stages.c_str();
       const char* stages = stages_env ? stages_env : "189";
-      if (!stages_env && b->stage_pick != 0 && in_count == nullptr) {   // (the pilot of batch_build chose the first width)
-        stages = (b->stage_pick == 16) ? "189" : (b->stage_pick == 32) ? "89" : "9";  // (128: 64 lanes still take the pairs that fit)
+      if (!stages_env && b->stage_pick != 0 && in_count == nullptr) {   // (the pilots of batch_build chose the first width)
+        stages = (b->stage_pick == 16) ? (b->narrow_pick == 1 ? "0189" : "189") : (b->stage_pick == 32) ? "89" : "9";  // (128: 64 lanes still take the pairs that fit)
       }
       int variants[6] = {-1, -1, -1, -1, -1, -1};
       int nv = 0;
       for (const char* c = stages; *c && nv < 6; ++c) {
         const int v = *c - '0';
         if (v < 0 || v > 9) continue;
-        if (v < 1) continue;
-        if (v == 1) {   // (the lane kernel of a run-time shape: only while its rings fit the register file)
+        if (v <= 1) {   // (the lane kernel of a run-time shape: only while its rings fit the register file, and never the 8-diagonal form)
           int X_, OE_, E_;
-          if (wfa::seg_shape(b->dcfg, &X_, &OE_, &E_) == WFA_SHAPE_RTC && !wfa::rtc_lane_shape_ok(X_, OE_, E_)) continue;
+          if (wfa::seg_shape(b->dcfg, &X_, &OE_, &E_) == WFA_SHAPE_RTC && (v == 0 || !wfa::rtc_lane_shape_ok(X_, OE_, E_))) continue;
         }
         variants[nv++] = v;
       }
       if (nv == 0) variants[nv++] = 6;
+      int lane_passes = 0;   // lane stages launched so far: the first two take slices of their list at run time, each from a counter of its own
       for (int pass = 0; pass < nv; ++pass) {
         uint32_t* out_list = b->d_fb_list2[out_sel];
         uint32_t* out_count = next_count();
@@ -2502,18 +2522,32 @@ static int batch_run_once(wfa_hip_batch_t* b, void* stream_) {
         const bool stage_timing = knob(al, K_STAGE_TIMING, 0) != 0;
         if (stage_timing) { hipEventCreate(&se0); hipEventCreate(&se1); hipEventRecord(se0, stream); }
         int lrc;
-        if (variants[pass] == 1) {
+        if (variants[pass] <= 1) {
           int X, OE, E;
           const int shape = wfa::seg_shape(b->dcfg, &X, &OE, &E);
-          // (slices of the list taken at run time: as many waves as the chip holds at once — every wave goes on until the list is used up)
-          const uint32_t lane_dyn = (in_count == nullptr && in_n >= 65536u) ? (uint32_t)std::max(0, knob(al, K_LANE_DYN, 192)) : 0u;
+          const bool narrow = variants[pass] == 0;
+          const int lane_k = lane_passes++;
+          // (slices of the list taken at run time: as many waves as the chip holds at once — every wave goes on until the list is used up.
+          // A stage behind another reads the length of its list from the device (a.nwork_dev) and takes slices the same way: a grid sized
+          // for the chip, not for a count the host does not know)
+          uint32_t lane_dyn = (in_n >= 65536u && lane_k < 2) ? (uint32_t)std::max(0, knob(al, K_LANE_DYN, 192)) : 0u;
+          // (waves per CU: the 16-diagonal form holds 4 per SIMD, the 8-diagonal one 6)
+          const int dyn_waves = narrow ? knob(al, K_LANE_NARROW_WAVES, 24) : knob(al, K_LANE_DYN_WAVES, 16);
+          if (lane_dyn && in_count != nullptr) {
+            // behind another stage: slices sized for the pairs it is expected to receive (the first stage's pilot, else 64), so that
+            // every wave gets at least two — a wave with one slice of 192 runs as long as its slowest lane's three pairs (2 M pairs at
+            // 2 %, 350 k handed on: 1.02 ms for the cascade with slices of 192, 0.89 with 64; 10 M: 192 is right)
+            const int64_t expect = (b->narrow_permille >= 0 && variants[0] == 0) ? (int64_t)in_n * b->narrow_permille / 1000 : 0;
+            const int64_t per_wave = expect / std::max<int64_t>(1, (int64_t)al->cu_count * dyn_waves * 2);
+            lane_dyn = (uint32_t)std::max<int64_t>(64, std::min<int64_t>(lane_dyn, per_wave));
+          }
           lrc = wfa::launch_lane(shape, wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1), al->cu_count,
-                                 lane_dyn ? knob(al, K_LANE_DYN_WAVES, 16) : knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, b->d_words, b->d_meta,
+                                 lane_dyn ? dyn_waves : knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, b->d_words, b->d_meta,
                                  in_list, in_count, in_n, b->d_score, b->d_status, out_list, out_count,
                                  (knob(al, K_LANE_DEBUG, 0) && al->ws) ? al->ws : nullptr, knob(al, K_LANE_LDS_PAD_KB, 0), X, OE, E, knob(al, K_LANE_MIN_PAIRS, 0),
-                                 // (slices of the list taken at run time, 256 pairs at a time, from a counter zeroed with the run's others;
-                                 // a list whose length only the device knows keeps the fixed slices; WFA_HIP_LANE_DYN=0: fixed slices)
-                                 b->d_counters + 12, lane_dyn);
+                                 // (slices of the list taken at run time, 192 pairs at a time, from counters zeroed with the run's others: [12] for
+                                 // the first lane stage, [14] for the one behind it; WFA_HIP_LANE_DYN=0: fixed slices)
+                                 b->d_counters + (lane_k == 0 ? 12 : 14), lane_dyn, narrow ? 4 : 8);
           if (knob(al, K_LANE_DEBUG, 0) && al->ws) {  // development aid (build with -DWFA_LANE_DEBUG_COUNTERS=1)
             unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             hipStreamSynchronize(stream); hipMemcpy(c, al->ws, sizeof(c), hipMemcpyDeviceToHost); hipMemset(al->ws, 0, sizeof(c));

@@ -93,12 +93,24 @@ __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) {
   lane_s2 r = __builtin_bit_cast(lane_s2, a) + __builtin_bit_cast(lane_s2, b);
   return __builtin_bit_cast(uint32_t, r);
 }
-// per half: nm > lim ? NULL : nm   (only M is clamped, R/wavefront_compute_affine.c:80-84; negative values are dead anyway)
+// per half: nm > lim ? NULL : nm   (only M is clamped, R/wavefront_compute_affine.c:80-84; negative values are dead anyway).
+// Built-in shapes: three instructions per register — packed difference, its sign spread over each half, one bit-select.  Written in C
+// the compiler sees a compare-and-select per half and lowers it to seven half-rate instructions (sub, two compares, two cndmasks, shift,
+// perm): C2 2.73 -> 2.68 ms per step with the assembly.  The run-time instantiation keeps the C form: there the assembly measured slower
+// (150 bp at 2 %, mismatch 5 = shape 5/8/2: 1.68 -> 1.72 ms per 2 M pairs).
 __device__ __forceinline__ uint32_t pk_clamp(uint32_t nm, uint32_t lim) {
+#ifndef __HIPCC_RTC__
+  uint32_t d, m, r;
+  asm("v_pk_sub_i16 %0, %1, %2" : "=v"(d) : "v"(lim), "v"(nm));
+  asm("v_pk_ashrrev_i16 %0, 15, %1 op_sel_hi:[0,1]" : "=v"(m) : "v"(d));   // 0xffff where nm > lim (the shift count 15 in both halves)
+  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "s"(WFA_LANE_NULL2), "v"(nm));
+  return r;
+#else
   lane_s2 d = __builtin_bit_cast(lane_s2, lim) - __builtin_bit_cast(lane_s2, nm);
   d = d >> (short)15;  // 0xffff where nm > lim
   const uint32_t m = __builtin_bit_cast(uint32_t, d);
   return (nm & ~m) | (WFA_LANE_NULL2 & m);
+#endif
 }
 
 #ifndef WFA_LANE_WAVES_PER_EU
@@ -123,13 +135,18 @@ struct LaneFull { static constexpr int NREC = 2 * (OE - E) + E * 17 + 1; };
 // LIN = 2: indel — the same without the mismatch candidate (R/wavefront_compute_edit.c:44-100 with the indel metric).
 // NRP (round 6, HEUR only): packed registers per component — 8 (16 diagonals) or 16: a band of 32 diagonals for pairs whose whole
 // wavefront the 16 slots cannot hold (150 bp at 2 %: 45 % of the pairs pass score 20, where the hull reaches slots 0 / 15; 6 % pass 36).
+// NRP = 4 (plain score-only form only): a band of 8 diagonals, k in [c - 4, c + 4), as the first stage of the cascade for batches whose
+// pairs it mostly proves (150 bp at 2 %: 82 % of the pairs within its Bmin; 16 diagonals: 98 %).  The rings take half the registers
+// (4/6/2: 79 VGPRs, 6 waves per SIMD instead of 4) and the step half the probe blocks; what it cannot prove is handed on and starts
+// over in the 16-diagonal form (its state is exact only up to the narrow deadline).  Every use of NR / H below is generic in the width.
 template <int X, int OE, int E, bool FULL, bool HEUR = false, int LIN = 0, int NRP = 8>
 __global__ void __launch_bounds__(64) WFA_LANE_OCCUPANCY
 wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg) {
   static_assert(!(FULL && HEUR), "the general form is score only");
-  static_assert(NRP == 8 || (HEUR && NRP == 16), "the wider band exists in the general form only");
+  static_assert(NRP == 8 || (HEUR && NRP == 16) || (NRP == 4 && !FULL && !HEUR && LIN == 0),
+                "the wider band exists in the general form only, the narrow one in the plain score-only form only");
   const int refill_min = refill_arg & 0xff;
-  constexpr int NR = NRP, W = 2 * NR, H = NR;     // band of 16 diagonals = 8 packed registers (NRP = 16: 32 diagonals)
+  constexpr int NR = NRP, W = 2 * NR, H = NR;     // band of 16 diagonals = 8 packed registers (NRP = 16: 32 diagonals, NRP = 4: 8)
   constexpr int DM = (X > OE) ? X : OE;           // depth of the M ring
   constexpr int NEVER = 0x7fffffff;
   constexpr int NREC = LaneFull<OE, E>::NREC;     // FULL: steps a pair can take here (bounds the walk)
@@ -643,15 +660,17 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
 #ifndef __HIPCC_RTC__   // ---- host side (launch code) ----
 // per-shape entry points (csrc/k_lane.hip compiled once per shape index of WFA_SEG_SHAPES)
 #define WFA_LANE_DECL(i, x, oe, e) \
-  int launch_lane_s##i(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur);
+  int launch_lane_s##i(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur, int nrp);
 // (the shape list is wfa_seg.hpp's; declared here without including it)
 WFA_LANE_DECL(0, 2, 4, 1) WFA_LANE_DECL(1, 2, 3, 1) WFA_LANE_DECL(2, 4, 7, 1) WFA_LANE_DECL(3, 3, 5, 1)
 WFA_LANE_DECL(4, 6, 8, 3) WFA_LANE_DECL(5, 5, 3, 3) WFA_LANE_DECL(6, 1, 2, 1)
 #undef WFA_LANE_DECL
 
 template <int X, int OE, int E>
-inline int launch_lane_shape(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur) {
-  if (heur == 2) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, true, 0, 16>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
+inline int launch_lane_shape(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur, int nrp) {
+  if (nrp == 4 && (full || heur)) return -1;   // (the 8-diagonal band exists in the plain score-only form only)
+  if (nrp == 4) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, false, 0, 4>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
+  else if (heur == 2) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, true, 0, 16>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
   else if (heur) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, true>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
   else if (full) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, true>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
   else hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
@@ -694,12 +713,12 @@ inline void lane_full_geometry(uint32_t nwork, int cu_count, int per_cu, int min
 
 // full = the FULL form: a.hist = run-record slots (a.hist_stride ints each, slot = work item - a.work_begin), a.end_state per slot
 // (shape_idx WFA_SHAPE_RTC: no instantiation in the library — the kernel of (X, OE, E) is compiled at run time, csrc/wfa_rtc.cpp)
-inline int launch_lane_args(int shape_idx, int OE, int E, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, FastArgs a, bool full, int lds_pad_kb = 0, int min_pairs = 0, int heur = 0, int X = 0);   // heur: 0 no, 1 the general form (16 diagonals), 2 its 32-diagonal form
+inline int launch_lane_args(int shape_idx, int OE, int E, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, FastArgs a, bool full, int lds_pad_kb = 0, int min_pairs = 0, int heur = 0, int X = 0, int nrp = 8);   // heur: 0 no, 1 the general form (16 diagonals), 2 its 32-diagonal form; nrp: 8 (16 diagonals) or 4 (8 diagonals: plain score-only form, instantiated shapes only)
 
 inline int launch_lane(int shape_idx, int g, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, const uint32_t* words,
                        const WfaPairMeta* meta, const uint32_t* worklist, const uint32_t* nwork_dev, uint32_t nwork,
                        int32_t* score, int32_t* status, uint32_t* fb_list, uint32_t* fb_count, int32_t* debug_counters = nullptr, int lds_pad_kb = 0,
-                       int X = 0, int OE = 0, int E = 0, int min_pairs = 0, uint32_t* dyn_next = nullptr, uint32_t dyn_chunk = 0) {
+                       int X = 0, int OE = 0, int E = 0, int min_pairs = 0, uint32_t* dyn_next = nullptr, uint32_t dyn_chunk = 0, int nrp = 8) {
   FastArgs a = FastArgs();
   a.dyn_next = dyn_chunk ? dyn_next : nullptr; a.dyn_chunk = dyn_chunk;
   a.words = words; a.meta = meta; a.worklist = worklist; a.nwork_dev = nwork_dev; a.nwork = nwork;
@@ -707,10 +726,10 @@ inline int launch_lane(int shape_idx, int g, int cu_count, int per_cu, int refil
   a.g = g;
   a.hist = debug_counters; a.hist_stride = 0; a.end_state = nullptr; a.work_begin = 0;
   a.ef = a.pbf = a.pef = a.tbf = a.tef = 0; a.heur = 0; a.min_wf_len = a.max_dist_thr = a.steps_between = 0; a.max_steps = INT_MAX;
-  return launch_lane_args(shape_idx, OE, E, cu_count, per_cu, refill_min, max_len, stream, a, false, lds_pad_kb, min_pairs, 0, X);
+  return launch_lane_args(shape_idx, OE, E, cu_count, per_cu, refill_min, max_len, stream, a, false, lds_pad_kb, min_pairs, 0, X, nrp);
 }
 
-inline int launch_lane_args(int shape_idx, int OE, int E, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, FastArgs a, bool full, int lds_pad_kb, int min_pairs, int heur, int X) {
+inline int launch_lane_args(int shape_idx, int OE, int E, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, FastArgs a, bool full, int lds_pad_kb, int min_pairs, int heur, int X, int nrp) {
   const uint32_t nwork = a.nwork;
   const uint32_t* nwork_dev = a.nwork_dev;
   const int slot_words = lane_slot_words(std::min(max_len, WFA_FAST_MAX_LEN));
@@ -727,14 +746,16 @@ inline int launch_lane_args(int shape_idx, int OE, int E, int cu_count, int per_
   if (grid < 1) grid = 1;
   if (full && a.codes_cap <= 0) return -1;   // (the caller sizes the record lists with lane_full_geometry)
   if (a.lin) shape_idx = WFA_SHAPE_RTC;      // (the one-component form: instantiated at run time whatever the shape)
+  if (nrp != 8 && nrp != 4) return -1;
+  if (nrp == 4 && (shape_idx == WFA_SHAPE_RTC || full || heur)) return -1;   // (the 8-diagonal form: built-in shapes, plain score-only form)
   switch (shape_idx) {
-    case 0: return launch_lane_s0((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur);
-    case 1: return launch_lane_s1((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur);
-    case 2: return launch_lane_s2((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur);
-    case 3: return launch_lane_s3((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur);
-    case 4: return launch_lane_s4((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur);
-    case 5: return launch_lane_s5((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur);
-    case 6: return launch_lane_s6((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur);
+    case 0: return launch_lane_s0((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
+    case 1: return launch_lane_s1((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
+    case 2: return launch_lane_s2((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
+    case 3: return launch_lane_s3((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
+    case 4: return launch_lane_s4((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
+    case 5: return launch_lane_s5((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
+    case 6: return launch_lane_s6((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
     case WFA_SHAPE_RTC: {
       struct { FastArgs a; int slot_words; int refill_min; } args = {a, slot_words, refill_min};   // (the kernel's argument list)
       const std::string name = "wfa::wfa_lane_kernel<" + std::to_string(X) + ", " + std::to_string(OE) + ", " + std::to_string(E) + ", " +

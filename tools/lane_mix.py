@@ -2,7 +2,10 @@
 """Dynamic instruction mix of wfa_lane_kernel<2,4,1,false,false> (the C2 hot loop): which share of its vector instructions runs at
 the full issue rate (development aid).
 
-    python tools/lane_mix.py [counts-file]
+    python tools/lane_mix.py [--width 16|8 | --kernel SYMBOL] [--static] [counts-file]
+
+   --width 8 counts the 8-diagonal form (NRP = 4, the first stage of the score-only cascade), --kernel any instantiation of k_lane.hip's
+   shape 0 by its mangled name; --static prints the static counts per region and instruction and stops (no counts file needed).
 
 1. The kernel is compiled for gfx950 with region marks (-DWFA_LANE_REGION_MARKS=1: comments in the assembly around the refill,
    the first-probe block of a register, a round of a second run, the parked-run loop and its write-back, the hand-over block),
@@ -19,7 +22,9 @@ import json, os, re, subprocess, sys, collections
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 CSRC = os.path.join(ROOT, "pywfa_amd", "csrc")
 ASM = "/tmp/k_lane_marks.s"
-KERNEL = "_ZN3wfa15wfa_lane_kernelILi2ELi4ELi1ELb0ELb0ELi0ELi8EEEvNS_8FastArgsEii"   # (round 6: the LIN and NRP parameters)
+KERNELS = {16: "_ZN3wfa15wfa_lane_kernelILi2ELi4ELi1ELb0ELb0ELi0ELi8EEEvNS_8FastArgsEii",   # (round 6: the LIN and NRP parameters)
+           8: "_ZN3wfa15wfa_lane_kernelILi2ELi4ELi1ELb0ELb0ELi0ELi4EEEvNS_8FastArgsEii"}
+KERNEL = KERNELS[16]
 FULL_RATE = ("v_add_u32", "v_add_co_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_and_or_b32", "v_or3_b32", "v_not_b32")
 
 
@@ -77,10 +82,24 @@ def static_counts():
 
 
 def main():
+    global KERNEL
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, choices=sorted(KERNELS), default=16, help="diagonals of the band (the kernel's NRP x 2)")
+    ap.add_argument("--kernel", help="mangled kernel symbol (overrides --width)")
+    ap.add_argument("--static", action="store_true", help="print the static counts per region and stop")
+    ap.add_argument("counts_file", nargs="?")
+    args = ap.parse_args()
+    KERNEL = args.kernel or KERNELS[args.width]
     compile_marks()
     regions, copies = static_counts()
+    if args.static:
+        for name, cnt in sorted(regions.items()):
+            n_copies = max(copies.get(name, 1), 1)
+            print(f"{name} ({n_copies} copies): " + ", ".join(f"{k[4:]} {v}" for k, v in sorted(cnt.items()) if k.startswith("ops:")))
+        return
     TAG = os.environ.get("WFA_PROFILE_TAG", "r05")
-    counts_file = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", TAG + "_lane_regions.txt")
+    counts_file = args.counts_file or os.path.join(ROOT, "profiles", TAG + "_lane_regions.txt")
     txt = open(counts_file).read()
     m = re.search(r"(\d+) wave-steps, (\d+) refills, (\d+) parked runs, (\d+) parked rounds, (\d+) probe blocks, (\d+) second-run rounds, (\d+) hand-over blocks, (\d+) second runs", txt)
     steps, refills, parked, prounds, probes, now_rounds, bd, now_runs = [int(x) for x in m.groups()]
@@ -98,7 +117,7 @@ def main():
                 dyn[k] += e * v / n_copies
     # (the marks nest: probe contains now; parkfix contains parked — static counts are attributed to the innermost region)
     total = sum(dyn.values())
-    out = {"kernel": "wfa_lane_kernel<2,4,1,false>", "counts_file": os.path.relpath(counts_file, ROOT),
+    out = {"kernel": KERNEL, "counts_file": os.path.relpath(counts_file, ROOT),
            "region_executions": execs, "regions": per_region,
            "dynamic_valu_by_class": dict(dyn), "dynamic_valu_total": total,
            "full_rate_share": dyn["full"] / total, "mov_share": dyn["mov"] / total, "lane_share": dyn["lane"] / total,
@@ -121,7 +140,7 @@ def main():
             out["model_over_counter"] = total / out["sq_insts_valu_per_dispatch"]
     except OSError:
         pass
-    with open(os.path.join(ROOT, "profiles", TAG + "_lane_mix.json"), "w") as f:
+    with open(os.path.join(ROOT, "profiles", TAG + ("_lane_mix.json" if KERNEL == KERNELS[16] else "_lane%d_mix.json" % args.width)), "w") as f:
         json.dump(out, f, indent=1)
     print(json.dumps({k: v for k, v in out.items() if k != "regions"}, indent=1))
 
