@@ -334,6 +334,55 @@ int64_t wfa_hip_batch_fallback_pairs(const wfa_hip_batch_t* batch);
 int64_t wfa_hip_batch_rle_counts(wfa_hip_batch_t* batch, int32_t* run_count, int32_t* locations);
 int wfa_hip_batch_rle_runs(wfa_hip_batch_t* batch, uint8_t* run_code, int32_t* run_len);
 
+/* ---- score matrices: every sequence of one set against every sequence of another, or of itself ---------- */
+
+/*
+ * Semantics.  Cross mode: pattern set P (m sequences) and text set T (n sequences); score[i][j] / status[i][j] are exactly what
+ * wfa_hip_align_batch returns for the pair (P[i], T[j]) under the aligner's configuration at wfa_hip_cross_run with scope set to
+ * score (whatever scope the aligner has: no op strings).  All-vs-all mode (T = NULL): the dense result is the full n x n cross product
+ * of P with itself, diagonal included, every cell meaning the same.  Where the score is provably symmetric — no heuristic, and span
+ * end-to-end or ends-free with pattern_begin_free == text_begin_free and pattern_end_free == text_end_free — only the cells j >= i are
+ * aligned and mirrored; under wf-adaptive, X-drop or asymmetric free ends both orders are aligned.  Free ends larger than a sequence:
+ * WFA_HIP_EINVAL (as wfa_hip_align_batch).
+ *
+ * Completed pairs: the list of (i, j, score) of every cell with status 0, in row-major order of (i, j); all-vs-all: the cells i < j
+ * only.  Meant for runs under max_steps (clustering, de-duplication: the close pairs), it needs no m x n buffer on either side.
+ *
+ * Inside, the pair metadata of the cross product is generated on the device in bands of rows, each band aligned by the batch
+ * cascade over the sets' packed words (each sequence is uploaded and packed once: m + n sequences cross PCIe, not m x n pairs).
+ * WFA_HIP_CROSS_BAND (pairs per band, read when the aligner is created) caps the band size.
+ */
+typedef struct wfa_hip_seqset wfa_hip_seqset_t;  /* a set of sequences resident in HBM, 2-bit packed once */
+typedef struct wfa_hip_cross  wfa_hip_cross_t;   /* the results of one cross run, resident in HBM       */
+
+#define WFA_HIP_CROSS_DENSE      1   /* want: the m x n score / status matrices          */
+#define WFA_HIP_CROSS_COMPLETED  2   /* want: the list of completed pairs                */
+
+/* Upload n sequences (ASCII; sequence k = seqs[off[k] .. +len[k])) as the word table the kernels read, one word-aligned run per
+ * sequence.  The set keeps the lengths on the host, a flag per sequence holding letters outside ACGT (such a sequence also keeps its
+ * bytes, and its pairs are aligned on them, as in a batch), and the aligner's wildcard at this call: a cross run under another
+ * wildcard returns WFA_HIP_EINVAL.  The inputs are not read after the call returns.  Returns NULL on error (wfa_hip_last_error). */
+wfa_hip_seqset_t* wfa_hip_seqset_create(wfa_hip_aligner_t* aligner, int64_t n, const uint8_t* seqs, const int64_t* off, const int32_t* len);
+void wfa_hip_seqset_destroy(wfa_hip_seqset_t* set);
+
+/* Run the cross product of `patterns` x `texts` (texts = NULL: all-vs-all of `patterns`); synchronous.  want = WFA_HIP_CROSS_DENSE
+ * and / or WFA_HIP_CROSS_COMPLETED.  The sets must belong to `aligner`.  Returns NULL on error (wfa_hip_last_error). */
+wfa_hip_cross_t* wfa_hip_cross_run(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want);
+/* The dense results: m x n row-major int32 host arrays (needs WFA_HIP_CROSS_DENSE). */
+int wfa_hip_cross_dense(wfa_hip_cross_t* cross, int32_t* score, int32_t* status);
+/* The completed pairs: *count always; i / j / score (each *count entries) when not NULL (needs WFA_HIP_CROSS_COMPLETED). */
+int wfa_hip_cross_completed(wfa_hip_cross_t* cross, int64_t* count, int32_t* i, int32_t* j, int32_t* score);
+/* HIP-event time (ms) of the alignment kernels summed over the bands (the span wfa_hip_batch_last_kernel_ms times for a batch), and
+ * the pairs aligned. */
+int wfa_hip_cross_kernel_ms(wfa_hip_cross_t* cross, float* ms, int64_t* pairs);
+void wfa_hip_cross_destroy(wfa_hip_cross_t* cross);
+
+/* The band planner alone (host only, needs no GPU): bands of whole rows of the m x n rectangle (triangle = 0) or of the upper triangle
+ * of an n x n square, columns j >= i (triangle = 1, m ignored), each of at most max_pairs pairs (a row longer than that is a band of
+ * its own).  Writes the first row of every band and the end, row_begin[0 .. nbands], when row_begin is not NULL and cap >= nbands + 1.
+ * Returns nbands, or WFA_HIP_EINVAL. */
+int64_t wfa_hip_plan_cross_bands(int64_t m, int64_t n, int triangle, int64_t max_pairs, int64_t* row_begin, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

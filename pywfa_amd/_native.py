@@ -61,7 +61,11 @@ SYMBOLS = [
     "wfa_hip_multi_last_error", "wfa_hip_multi_align_batch", "wfa_hip_pack_2bit", "wfa_hip_batch_extent",
     "wfa_hip_align_batch_packed2bits", "wfa_hip_batch_create_packed2bits", "wfa_hip_cigar_sprint_pretty",
     "wfa_hip_batch_extent_packed2bits", "wfa_hip_align_pair", "wfa_hip_upload_info",
+    "wfa_hip_seqset_create", "wfa_hip_seqset_destroy", "wfa_hip_cross_run", "wfa_hip_cross_dense", "wfa_hip_cross_completed",
+    "wfa_hip_cross_kernel_ms", "wfa_hip_cross_destroy", "wfa_hip_plan_cross_bands",
 ]
+
+CROSS_DENSE, CROSS_COMPLETED = 1, 2
 
 
 def lib():
@@ -126,6 +130,19 @@ def lib():
     L.wfa_hip_multi_last_error.argtypes = [vp]
     L.wfa_hip_multi_last_error.restype = ctypes.c_char_p
     L.wfa_hip_multi_align_batch.argtypes = [vp, i64] + [vp] * 11
+    L.wfa_hip_seqset_create.argtypes = [vp, i64, vp, vp, vp]
+    L.wfa_hip_seqset_create.restype = vp
+    L.wfa_hip_seqset_destroy.argtypes = [vp]
+    L.wfa_hip_seqset_destroy.restype = None
+    L.wfa_hip_cross_run.argtypes = [vp, vp, vp, ctypes.c_int]
+    L.wfa_hip_cross_run.restype = vp
+    L.wfa_hip_cross_dense.argtypes = [vp, vp, vp]
+    L.wfa_hip_cross_completed.argtypes = [vp, ctypes.POINTER(i64), vp, vp, vp]
+    L.wfa_hip_cross_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
+    L.wfa_hip_cross_destroy.argtypes = [vp]
+    L.wfa_hip_cross_destroy.restype = None
+    L.wfa_hip_plan_cross_bands.argtypes = [i64, i64, ctypes.c_int, i64, vp, i64]
+    L.wfa_hip_plan_cross_bands.restype = i64
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -359,6 +376,13 @@ class Aligner:
     def batch(self, batch):
         return ResidentBatch(self, batch)
 
+    def seqset(self, seqs, off, length):
+        return SeqSet(self, seqs, off, length)
+
+    def cross(self, patterns, texts=None, want=CROSS_DENSE):
+        """wfa_hip_cross_run of two SeqSets (texts None: all-vs-all of ``patterns``)."""
+        return CrossRun(self, patterns, texts, want)
+
 
 def pack_2bit(seq, form=-1):
     """wfa_hip_pack_2bit (host only): the 2-bit words of an ASCII sequence and whether a letter outside ACGT was seen."""
@@ -389,6 +413,108 @@ def plan_shards(p_len, t_len, nshards):
     if rc != OK:
         raise ValueError("wfa_hip_plan_shards: invalid arguments")
     return out
+
+
+def plan_cross_bands(m, n, triangle, max_pairs):
+    """wfa_hip_plan_cross_bands: the first row of every band of a cross run and the end, int64[nbands + 1] (host only)."""
+    nb = lib().wfa_hip_plan_cross_bands(int(m), int(n), int(bool(triangle)), int(max_pairs), None, 0)
+    if nb < 0:
+        raise ValueError("wfa_hip_plan_cross_bands: invalid arguments")
+    out = np.zeros(nb + 1, np.int64)
+    lib().wfa_hip_plan_cross_bands(int(m), int(n), int(bool(triangle)), int(max_pairs), _ptr(out), nb + 1)
+    return out
+
+
+class SeqSet:
+    """A set of sequences resident in HBM, 2-bit packed once (wfa_hip_seqset_t).  ``seqs`` / ``off`` / ``len`` as a batch's blob:
+    sequence k = seqs[off[k] .. +len[k])."""
+
+    def __init__(self, aligner, seqs, off, length):
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        n = length.shape[0]
+        if off.shape[0] != n:
+            raise ValueError("sequence set arrays differ in length")
+        if n and (int(off.min()) < 0 or int(length.min()) < 0):
+            raise ValueError("negative length or offset")
+        if n and int((off + length).max()) > seqs.size:
+            raise ValueError("sequence offsets run past the blob")
+        self.aligner = aligner
+        self.n = n
+        self._h = lib().wfa_hip_seqset_create(aligner._h, n, _ptr(seqs) if seqs.size else None, _ptr(off), _ptr(length))
+        if not self._h:
+            msg = aligner.error()
+            if "failed:" in msg:
+                raise NativeError(f"wfa_hip_seqset_create: {msg}")
+            raise ValueError(f"wfa_hip_seqset_create: {msg}")
+        aligner._batches.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().wfa_hip_seqset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CrossRun:
+    """The results of one cross run, resident in HBM (wfa_hip_cross_t)."""
+
+    def __init__(self, aligner, patterns, texts=None, want=CROSS_DENSE):
+        self.aligner = aligner
+        self.m = patterns.n
+        self.n = patterns.n if texts is None else texts.n
+        self._h = lib().wfa_hip_cross_run(aligner._h, patterns._h, None if texts is None else texts._h, int(want))
+        if not self._h:
+            msg = aligner.error()
+            if "failed" in msg:
+                raise NativeError(f"wfa_hip_cross_run: {msg}")
+            raise ValueError(f"wfa_hip_cross_run: {msg}")
+        aligner._batches.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().wfa_hip_cross_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def dense(self):
+        score = np.zeros((self.m, self.n), np.int32)
+        status = np.zeros((self.m, self.n), np.int32)
+        rc = lib().wfa_hip_cross_dense(self._h, _ptr(score), _ptr(status))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_cross_dense")
+        return score, status
+
+    def completed(self):
+        count = ctypes.c_int64(0)
+        rc = lib().wfa_hip_cross_completed(self._h, ctypes.byref(count), None, None, None)
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_cross_completed")
+        out = {k: np.zeros(count.value, np.int32) for k in ("i", "j", "score")}
+        if count.value:
+            rc = lib().wfa_hip_cross_completed(self._h, ctypes.byref(count), _ptr(out["i"]), _ptr(out["j"]), _ptr(out["score"]))
+            if rc != OK:
+                self.aligner._raise(rc, "wfa_hip_cross_completed")
+        return out
+
+    def kernel_ms(self):
+        ms = ctypes.c_float(0)
+        pairs = ctypes.c_int64(0)
+        rc = lib().wfa_hip_cross_kernel_ms(self._h, ctypes.byref(ms), ctypes.byref(pairs))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_cross_kernel_ms")
+        return ms.value, pairs.value
 
 
 class MultiAligner:

@@ -530,6 +530,49 @@ class WavefrontAligner:
         """Upload + 2-bit pack a batch into HBM once; ``.run()`` it many times (bench.py)."""
         return self._native.batch(batch)
 
+    # ------------------------------------------------------------------ score matrices (additive API)
+    def _seqset(self, seqs):
+        """Upload one set of sequences (upper-cased and checked like ``wavefront_align_batch``), packed once on the device."""
+        seqs = seqs if type(seqs) is list else list(seqs)
+        host = _native.compiled_host()
+        # (the compiled host's batch blob with an empty shared pattern: the texts are the set; a fresh scratch dict, the set's upload
+        # is over when seqset() returns)
+        batch = host.from_strings(b"", seqs, {}) if host is not None else None
+        if batch is None:
+            batch = datagen.from_strings(b"", seqs, upper=True)
+        return self._native.seqset(batch["seqs"], batch["t_off"], batch["t_len"])
+
+    def _cross(self, patterns, texts, want):
+        if self._cfg.wildcard != self._bwildcard:
+            self._push()
+        sets = [self._seqset(patterns)]
+        if texts is not None:
+            sets.append(self._seqset(texts))
+        try:
+            run = self._native.cross(sets[0], sets[1] if texts is not None else None, want)
+            try:
+                return run.dense() if want == _native.CROSS_DENSE else run.completed()
+            finally:
+                run.close()
+        finally:
+            for s in sets:
+                s.close()
+
+    def score_matrix(self, patterns, texts=None):
+        """Score every pattern against every text on the GPU: returns ``(score, status)``, int32 arrays of shape (M, N).
+
+        Cell (i, j) is what ``wavefront_align_batch`` gives for the pair (patterns[i], texts[j]) with ``scope="score"`` (this
+        aligner's configuration otherwise; no CIGARs whatever its scope).  ``texts=None``: all-vs-all, the N x N matrix of
+        ``patterns`` against itself, diagonal included.  Each sequence is uploaded and packed once, the M x N pairs are generated on
+        the device.  With ``devices=[...]`` the run takes the first device only."""
+        return self._cross(patterns, texts, _native.CROSS_DENSE)
+
+    def completed_pairs(self, patterns, texts=None):
+        """The cells of ``score_matrix`` whose status is 0, without the M x N matrix on either side: ``dict(i=, j=, score=)`` of
+        int32 arrays in row-major order of (i, j).  ``texts=None``: all-vs-all, the pairs i < j only.  Meant for runs under
+        ``max_steps`` (the pairs within that score: clustering, de-duplication, nearest candidates)."""
+        return self._cross(patterns, texts, _native.CROSS_COMPLETED)
+
     # ------------------------------------------------------------------ results
     @property
     def status(self):

@@ -39,6 +39,7 @@
 #include "wfa_biwfa.hpp"
 #include "wfa_bilevel.hpp"
 #include "wfa_rle.hpp"
+#include "wfa_cross.hpp"
 
 #define WFA_HIP_ABI_VERSION 3
 
@@ -51,7 +52,7 @@ static thread_local std::string g_error;
   F(ARENA_KB) F(BAND_DEBUG) F(BAND_SLIM) F(BAND_LDS_MAX) F(BAND_NO_WIN) F(BAND_SPLIT_MIN) F(NO_TINY_INLINE) F(BILEVEL) F(BILEVEL_WIDE_LEVELS) F(BILEVEL_PER_CU) F(BILEVEL_I32) F(BILEVEL_QCAP) F(BILEVEL_LEVELS) F(BILEVEL_LDS) F(BILEVEL_NO_1024) F(BILEVEL_HUGE_MIN) F(BILEVEL_LDS_W) F(BILEVEL_NO_SEQL) F(LANE_DYN) F(LANE_DYN_WAVES) F(BAND_LEFTOVER_WAVES_PER_CU) F(BAND_NCH) F(BAND_NO_LDS) F(BAND_NO_SPLIT) F(BAND_PB) F(PIPE_TAIL) F(LEN16) F(MAILBOX) F(MAILBOX_IDLE_US) F(TILE32)     \
   F(BAND_RECORDS) F(BAND_SPLIT_ROUNDS) F(BAND_WAVES_PER_CU) F(NO_BAND) F(NO_FAST) F(NO_SEGFULL) F(SEGFULL_PAIRS)     \
   F(SEGFULL_STAGES) F(STAGE_TIMING) F(LANE_HEUR32) F(THREADS) F(TINY_BATCH) F(WAVES_PER_CU) F(FAST_WAVES_PER_CU) F(TIMING)          \
-  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT)
+  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT) F(CROSS_BAND)
 enum WfaKnob {
 #define WFA_KNOB_ENUM(n) K_##n,
   WFA_KNOBS(WFA_KNOB_ENUM)
@@ -3599,5 +3600,406 @@ extern "C" int wfa_hip_multi_align_batch(wfa_hip_multi_t* m, int64_t n, const ui
   for (auto& x : th) x.join();
   for (int d = 0; d < nd; ++d)
     if (rcs[(size_t)d] != WFA_HIP_OK) { m->err = "device " + std::to_string(m->al[(size_t)d]->device) + ": " + m->al[(size_t)d]->err; return rcs[(size_t)d]; }
+  return WFA_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// score matrices (include/wfa_hip.h: sequence sets packed once, cross products in bands of rows, csrc/wfa_cross.hpp)
+// ------------------------------------------------------------------------------------------------
+struct wfa_hip_seqset {
+  wfa_hip_aligner* al = nullptr;
+  int64_t n = 0;
+  int wildcard = -1;               // the aligner's wildcard when the set was packed
+  std::vector<int32_t> h_len;
+  std::vector<uint8_t> h_flag;     // 1: a letter outside ACGT (its pairs are aligned on their bytes)
+  uint64_t nwords = 0;             // words of the table, without the 4 zero words behind it
+  int64_t nbytes = 0;              // bytes of the ASCII blob
+  uint32_t* d_words = nullptr;     // one word-aligned run per sequence (wfa_hip_pack_2bit's layout)
+  uint8_t* d_bytes = nullptr;      // the sequences' bytes, back to back (a byte pair needs both of its sequences' bytes)
+  uint32_t* d_woff = nullptr; int32_t* d_len = nullptr; int64_t* d_boff = nullptr; uint8_t* d_flag = nullptr;
+};
+
+struct wfa_hip_cross {
+  wfa_hip_aligner* al = nullptr;
+  int64_t m = 0, n = 0;
+  int want = 0;
+  int32_t* d_score = nullptr; int32_t* d_status = nullptr;           // dense: m x n
+  int32_t* d_ci = nullptr; int32_t* d_cj = nullptr; int32_t* d_cs = nullptr;   // completed pairs
+  int64_t count = 0, cap = 0;
+  double ms = 0.0;
+  int64_t pairs = 0;
+};
+
+static void aligner_release_ref(wfa_hip_aligner* al) {
+  if (--al->live_batches == 0 && al->destroy_pending) aligner_free(al);
+}
+
+static bool wildcard_in_acgt(int wc) {
+  return wc == 'A' || wc == 'C' || wc == 'G' || wc == 'T' || wc == 'a' || wc == 'c' || wc == 'g' || wc == 't';
+}
+
+extern "C" void wfa_hip_seqset_destroy(wfa_hip_seqset_t* s) {
+  if (!s) return;
+  wfa_hip_aligner* al = s->al;
+  (void)hipSetDevice(al->device);
+  void* ptrs[] = {s->d_words, s->d_bytes, s->d_woff, s->d_len, s->d_boff, s->d_flag};
+  for (void* p : ptrs) pool_release(al, p);
+  delete s;
+  aligner_release_ref(al);
+}
+
+static int seqset_build(wfa_hip_aligner* al, wfa_hip_seqset* s, int64_t n, const uint8_t* seqs, const int64_t* off, const int32_t* len) {
+  s->n = n;
+  s->h_len.assign(len, len + n);
+  s->h_flag.assign((size_t)n, 0);
+  std::vector<uint32_t> woff((size_t)n);
+  std::vector<int64_t> boff((size_t)n);
+  uint64_t w = 0;
+  int64_t bb = 0;
+  for (int64_t k = 0; k < n; ++k) {
+    if (len[k] < 0 || off[k] < 0) { al->err = "negative length or offset"; return WFA_HIP_EINVAL; }
+    if (len[k] > INT_MAX / 4 - 8) { al->err = "sequence too long"; return WFA_HIP_EINVAL; }
+    woff[(size_t)k] = (uint32_t)w; w += (uint64_t)((len[k] + 15) >> 4);
+    boff[(size_t)k] = bb; bb += len[k];
+    if (w > 0x7FFFFFF0ull) { al->err = "sequence set too large: more than 2^31 packed words"; return WFA_HIP_EINVAL; }
+  }
+  s->nwords = w; s->nbytes = bb;
+  std::vector<uint32_t> words((size_t)w + 4, 0u);
+  std::vector<uint8_t> bytes((size_t)bb + 64, 0u);
+  // packed and copied on host threads: m + n sequences, once
+  const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, std::thread::hardware_concurrency()), (bb >> 20) + 1));
+  auto work = [&](int t) {
+    for (int64_t k = n * t / nthr, hi = n * (t + 1) / nthr; k < hi; ++k) {
+      s->h_flag[(size_t)k] = wfa::host_pack_seq(seqs + off[k], len[k], words.data() + woff[(size_t)k], -1) ? 1 : 0;
+      if (len[k] > 0) memcpy(bytes.data() + boff[(size_t)k], seqs + off[k], (size_t)len[k]);
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < nthr; ++t) th.emplace_back(work, t);
+  work(0);
+  for (auto& x : th) x.join();
+  const size_t nn = (size_t)std::max<int64_t>(n, 1);
+  HIP_TRY(al, pool_alloc(al, (void**)&s->d_words, words.size() * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&s->d_bytes, bytes.size()));
+  HIP_TRY(al, pool_alloc(al, (void**)&s->d_woff, nn * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&s->d_len, nn * sizeof(int32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&s->d_boff, nn * sizeof(int64_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&s->d_flag, nn));
+  HIP_TRY(al, hipMemcpy(s->d_words, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIP_TRY(al, hipMemcpy(s->d_bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+  if (n > 0) {
+    HIP_TRY(al, hipMemcpy(s->d_woff, woff.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(al, hipMemcpy(s->d_len, len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(al, hipMemcpy(s->d_boff, boff.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIP_TRY(al, hipMemcpy(s->d_flag, s->h_flag.data(), (size_t)n, hipMemcpyHostToDevice));
+  }
+  return WFA_HIP_OK;
+}
+
+extern "C" wfa_hip_seqset_t* wfa_hip_seqset_create(wfa_hip_aligner_t* al, int64_t n, const uint8_t* seqs, const int64_t* off, const int32_t* len) {
+  if (!al) { g_error = "null aligner"; return nullptr; }
+  if (n < 0 || n > 0x7FFFFFF0ll || (n > 0 && (!seqs || !off || !len))) { al->err = "invalid sequence set arguments"; g_error = al->err; return nullptr; }
+  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);   // (the resident one-pair kernel: sets take the device)
+  wfa_hip_seqset* s = new wfa_hip_seqset();
+  s->al = al;
+  s->wildcard = al->cfg.wildcard;
+  al->live_batches += 1;
+  if (seqset_build(al, s, n, seqs, off, len) != WFA_HIP_OK) { g_error = al->err; wfa_hip_seqset_destroy(s); return nullptr; }
+  return s;
+}
+
+extern "C" int64_t wfa_hip_plan_cross_bands(int64_t m, int64_t n, int triangle, int64_t max_pairs, int64_t* row_begin, int64_t cap) {
+  if (m < 0 || n < 0 || max_pairs < 1 || (triangle != 0 && triangle != 1)) return WFA_HIP_EINVAL;
+  const int64_t rows = (n == 0) ? 0 : (triangle ? n : m);
+  if (row_begin && cap >= 1) row_begin[0] = 0;
+  int64_t nb = 0, r = 0;
+  while (r < rows) {
+    int64_t acc = 0, r1 = r;
+    if (!triangle) r1 = std::min(rows, r + std::max<int64_t>(1, max_pairs / n));
+    else
+      while (r1 < rows) {
+        const int64_t wr = n - r1;
+        if (r1 > r && acc + wr > max_pairs) break;
+        acc += wr; ++r1;
+      }
+    r = r1; ++nb;
+    if (row_begin && nb < cap) row_begin[nb] = r;
+  }
+  return nb;
+}
+
+extern "C" void wfa_hip_cross_destroy(wfa_hip_cross_t* x) {
+  if (!x) return;
+  wfa_hip_aligner* al = x->al;
+  (void)hipSetDevice(al->device);
+  (void)hipStreamSynchronize(al->stream);
+  void* ptrs[] = {x->d_score, x->d_status, x->d_ci, x->d_cj, x->d_cs};
+  for (void* p : ptrs) pool_release(al, p);
+  delete x;
+  aligner_release_ref(al);
+}
+
+// the device blocks of one cross run besides the batch view's (released when the run returns)
+struct CrossScratch {
+  wfa_hip_aligner* al;
+  std::vector<void*> blocks;
+  uint32_t* h_cnt = nullptr;          // pinned: the completed pairs of the last two bands
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  template <class T> int alloc(T** p, size_t count) {
+    HIP_TRY(al, pool_alloc(al, (void**)p, std::max<size_t>(count, 1) * sizeof(T)));
+    blocks.push_back(*p);
+    return WFA_HIP_OK;
+  }
+  ~CrossScratch() {
+    (void)hipStreamSynchronize(al->stream);
+    for (void* p : blocks) pool_release(al, p);
+    if (h_cnt) (void)hipHostFree(h_cnt);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+
+static int cross_run_impl(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wfa_hip_seqset* T, int want, wfa_hip_cross* x) {
+  const bool ava = (T == nullptr);
+  if (ava) T = P;
+  if (!P || P->al != al || T->al != al) { al->err = "sequence set of another aligner"; return WFA_HIP_EINVAL; }
+  if (want <= 0 || (want & ~(WFA_HIP_CROSS_DENSE | WFA_HIP_CROSS_COMPLETED)) != 0) { al->err = "want: WFA_HIP_CROSS_DENSE and / or WFA_HIP_CROSS_COMPLETED"; return WFA_HIP_EINVAL; }
+  if (P->wildcard != al->cfg.wildcard || T->wildcard != al->cfg.wildcard) { al->err = "sequence set packed under another wildcard: create it again"; return WFA_HIP_EINVAL; }
+  wfa_hip_config_t c = al->cfg;
+  c.scope = WFA_SCOPE_SCORE;
+  const int64_t m = P->n, n = T->n;
+  x->m = m; x->n = n; x->want = want;
+  if (c.span == WFA_SPAN_ENDSFREE && m > 0 && n > 0) {   // (wavefront_align.c:86-102, as batch_build)
+    const int32_t minp = *std::min_element(P->h_len.begin(), P->h_len.end()), mint = *std::min_element(T->h_len.begin(), T->h_len.end());
+    if (c.pattern_begin_free > minp || c.pattern_end_free > minp || c.text_begin_free > mint || c.text_end_free > mint) {
+      al->err = "Ends-free parameters must be not larger than the sequences"; return WFA_HIP_EINVAL;
+    }
+  }
+  const bool dense = (want & WFA_HIP_CROSS_DENSE) != 0, completed = (want & WFA_HIP_CROSS_COMPLETED) != 0;
+  if (dense && m * n > 0) {
+    HIP_TRY(al, pool_alloc(al, (void**)&x->d_score, (size_t)(m * n) * sizeof(int32_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&x->d_status, (size_t)(m * n) * sizeof(int32_t)));
+  }
+  if (m == 0 || n == 0) return WFA_HIP_OK;
+  // the mirror rule: the score of (P[j], P[i]) is that of (P[i], P[j]) when nothing tells the pattern from the text — no heuristic (their
+  // cut-offs look at offsets, not at the alignment's symmetry) and the same free ends on both sides
+  const bool mirror = ava && c.heuristic == WFA_HEUR_NONE &&
+                      (c.span == WFA_SPAN_END2END || (c.pattern_begin_free == c.text_begin_free && c.pattern_end_free == c.text_end_free));
+  const int tri = mirror ? 1 : 0;
+  const int64_t rows = tri ? n : m;
+  const bool all_bytes = c.wildcard >= 0 && wildcard_in_acgt(c.wildcard);
+  // the 2-bit / byte split of every row, from the sets' flags (host prefix sums: no band reads anything back for it)
+  std::vector<int64_t> col_flag((size_t)n + 1, 0), row_bytes((size_t)rows + 1, 0);
+  for (int64_t j = 0; j < n; ++j) col_flag[(size_t)j + 1] = col_flag[(size_t)j] + ((all_bytes || T->h_flag[(size_t)j]) ? 1 : 0);
+  for (int64_t i = 0; i < rows; ++i) {
+    const bool pf = all_bytes || P->h_flag[(size_t)i];
+    const int64_t cnt = tri ? (pf ? n - i : col_flag[(size_t)n] - col_flag[(size_t)i]) : (pf ? n : col_flag[(size_t)n]);
+    row_bytes[(size_t)i + 1] = row_bytes[(size_t)i] + cnt;
+  }
+  const bool any_bytes = row_bytes[(size_t)rows] > 0;
+  // the longest text at or behind column j (a triangle row's columns)
+  std::vector<int32_t> suf_t((size_t)n + 1, 0);
+  for (int64_t j = n - 1; j >= 0; --j) suf_t[(size_t)j] = std::max(suf_t[(size_t)j + 1], T->h_len[(size_t)j]);
+  // band size: the knob, else what the lengths and the free memory allow (about 100 B of band arrays per pair; the workspace of the
+  // general kernel is sized from the reads, not from the band)
+  int slot_p = 0, slot_t = 0;   // words of the longest pattern / text of up to WFA_FAST_MAX_LEN bases (a pair's slot, below)
+  for (int32_t l : P->h_len) if (l <= WFA_FAST_MAX_LEN) slot_p = std::max(slot_p, (l + 15) >> 4);
+  for (int32_t l : T->h_len) if (l <= WFA_FAST_MAX_LEN) slot_t = std::max(slot_t, (l + 15) >> 4);
+  int64_t band_max = knob(al, K_CROSS_BAND, 0);
+  if (band_max <= 0) band_max = std::max<int64_t>(65536, std::min<int64_t>((int64_t)1 << 23, free_budget(al) / 4 / (112 + 4 * (slot_p + slot_t))));
+  band_max = std::min<int64_t>(band_max, (int64_t)1 << 30);
+  band_max = std::max<int64_t>(1, std::min<int64_t>(band_max, (int64_t)((0xFFFFFFF0ull - P->nwords - T->nwords - 64) / (uint64_t)std::max(1, slot_p + slot_t))));
+  const int64_t nbands = wfa_hip_plan_cross_bands(m, n, tri, band_max, nullptr, 0);
+  std::vector<int64_t> rb((size_t)nbands + 1);
+  wfa_hip_plan_cross_bands(m, n, tri, band_max, rb.data(), nbands + 1);
+  auto tri_before = [n](int64_t i) { return i * n - (i * (i - 1)) / 2; };
+  int64_t cap = 0;
+  for (int64_t k = 0; k < nbands; ++k) cap = std::max(cap, tri ? tri_before(rb[(size_t)k + 1]) - tri_before(rb[(size_t)k]) : (rb[(size_t)k + 1] - rb[(size_t)k]) * n);
+  CrossScratch sc{al};
+  // the batch view: one for every band, so that the pilots' picks of the first large band hold for the later ones
+  wfa_hip_batch* b = new wfa_hip_batch();
+  b->al = al;
+  al->live_batches += 1;
+  struct ViewGuard {   // (the result and list pointers of the last band are the matrix's or the scratch's: not the view's to release)
+    wfa_hip_batch* b;
+    ~ViewGuard() { b->d_score = b->d_status = nullptr; b->d_list_packed = b->d_list_bytes = nullptr; batch_free(b); }
+  } view_guard{b};
+  b->cfg = c;
+  derive_dev_config(c, &b->dcfg, &b->ncomp, &b->gcfg, &b->gncomp);
+  if (!al->dcfg.rtc) { b->dcfg.rtc = 0; b->gcfg.rtc = 0; }   // (the run-time path failed earlier on this aligner)
+  if (c.wildcard >= 0 && !all_bytes) { b->wild = c.wildcard; b->dcfg.wildcard = -1; b->gcfg.wildcard = -1; }   // (as batch_build)
+  // One word table per run: the pattern set's words, the text set's (cross mode), 64 zero words, then a slot per pair of a band for the
+  // pairs of up to WFA_FAST_MAX_LEN bases: the register stages (wfa_lane.hpp, wfa_seg.hpp) fetch a pair's pattern and text words in ONE
+  // load, the text's words right behind the pattern's, so the generator copies both sequences of such a pair into its slot.  Longer pairs
+  // point into the sets' words (every other stage reads pattern and text through their own offsets).
+  const uint32_t t_wshift = ava ? 0u : (uint32_t)P->nwords;
+  const int64_t t_bshift = ava ? 0 : P->nbytes;
+  const uint64_t table_words = P->nwords + (ava ? 0 : T->nwords) + 64;
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)(P->nbytes + (ava ? 0 : T->nbytes) + 64)));
+  HIP_TRY(al, hipMemcpyAsync(b->d_bytes, P->d_bytes, (size_t)P->nbytes + (ava ? 64 : 0), hipMemcpyDeviceToDevice, al->stream));
+  if (!ava) HIP_TRY(al, hipMemcpyAsync(b->d_bytes + P->nbytes, T->d_bytes, (size_t)T->nbytes + 64, hipMemcpyDeviceToDevice, al->stream));
+  const uint64_t slot_words = (uint64_t)slot_p + slot_t;
+  if (table_words + (uint64_t)cap * slot_words > 0xFFFFFFF0ull) { al->err = "sequence sets too large: more than 2^32 words of a band"; return WFA_HIP_EINVAL; }
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_words, (size_t)(table_words + (uint64_t)cap * slot_words) * sizeof(uint32_t)));
+  HIP_TRY(al, hipMemcpyAsync(b->d_words, P->d_words, (size_t)P->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
+  if (!ava) HIP_TRY(al, hipMemcpyAsync(b->d_words + P->nwords, T->d_words, (size_t)T->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
+  HIP_TRY(al, hipMemsetAsync(b->d_words + table_words - 64, 0, 64 * sizeof(uint32_t), al->stream));
+  const size_t ncap = (size_t)cap;
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_meta, ncap * sizeof(WfaPairMeta)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_flags, ncap));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_fb_list2[0], ncap * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_fb_list2[1], ncap * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_counters, WFA_COUNTER_WORDS * sizeof(uint32_t)));
+  HIP_TRY(al, hipMemsetAsync(b->d_counters, 0, WFA_COUNTER_WORDS * sizeof(uint32_t), al->stream));
+  uint32_t *list_packed = nullptr, *list_bytes = nullptr;
+  int64_t *d_row_bytes = nullptr, *d_col_flag = nullptr;
+  if (any_bytes) {
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_pboff, ncap * sizeof(int64_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_tboff, ncap * sizeof(int64_t)));
+    if (sc.alloc(&list_packed, ncap) || sc.alloc(&list_bytes, ncap) || sc.alloc(&d_row_bytes, row_bytes.size()) || sc.alloc(&d_col_flag, col_flag.size()))
+      return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpy(d_row_bytes, row_bytes.data(), row_bytes.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIP_TRY(al, hipMemcpy(d_col_flag, col_flag.data(), col_flag.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  }
+  // a band's own score / status: always, except rectangular bands of a dense run (those ARE the matrix's rows r0 .. r1)
+  int32_t *band_score = nullptr, *band_status = nullptr;
+  if (tri || !dense) {
+    if (sc.alloc(&band_score, ncap) || sc.alloc(&band_status, ncap)) return WFA_HIP_EDEVICE;
+  }
+  // completed pairs: each band compacts into one of two staging lists; the band before is appended to the handle's list once its
+  // count is known (read while the next band runs)
+  int32_t *st_i[2] = {nullptr, nullptr}, *st_j[2] = {nullptr, nullptr}, *st_s[2] = {nullptr, nullptr};
+  uint32_t *blk = nullptr, *d_cnt = nullptr;
+  if (completed) {
+    for (int h = 0; h < 2; ++h)
+      if (sc.alloc(&st_i[h], ncap) || sc.alloc(&st_j[h], ncap) || sc.alloc(&st_s[h], ncap)) return WFA_HIP_EDEVICE;
+    if (sc.alloc(&blk, (ncap + WFA_CROSS_CHUNK - 1) / WFA_CROSS_CHUNK) || sc.alloc(&d_cnt, 2)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipHostMalloc((void**)&sc.h_cnt, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    for (int h = 0; h < 2; ++h) HIP_TRY(al, hipEventCreateWithFlags(&sc.ev[h], hipEventDisableTiming));
+  }
+  auto drain = [&](int64_t k) -> int {   // append band k's completed pairs to the handle's list
+    const int h = (int)(k & 1);
+    HIP_TRY(al, hipEventSynchronize(sc.ev[h]));
+    const int64_t cnt = sc.h_cnt[h];
+    if (cnt == 0) return WFA_HIP_OK;
+    if (x->count + cnt > x->cap) {
+      const int64_t ncap2 = std::max<int64_t>(x->count + cnt, std::max<int64_t>(2 * x->cap, 4096));
+      int32_t* nb[3] = {nullptr, nullptr, nullptr};
+      int32_t** old[3] = {&x->d_ci, &x->d_cj, &x->d_cs};
+      for (int a = 0; a < 3; ++a) {
+        HIP_TRY(al, pool_alloc(al, (void**)&nb[a], (size_t)ncap2 * sizeof(int32_t)));
+        if (x->count) HIP_TRY(al, hipMemcpyAsync(nb[a], *old[a], (size_t)x->count * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
+        pool_release(al, *old[a]);   // (back to the pool; anything that takes it again is ordered behind this copy on the stream)
+        *old[a] = nb[a];
+      }
+      x->cap = ncap2;
+    }
+    HIP_TRY(al, hipMemcpyAsync(x->d_ci + x->count, st_i[h], (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
+    HIP_TRY(al, hipMemcpyAsync(x->d_cj + x->count, st_j[h], (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
+    HIP_TRY(al, hipMemcpyAsync(x->d_cs + x->count, st_s[h], (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
+    x->count += cnt;
+    return WFA_HIP_OK;
+  };
+  for (int64_t k = 0; k < nbands; ++k) {
+    const int64_t r0 = rb[(size_t)k], r1 = rb[(size_t)k + 1];
+    const int64_t tri0 = tri ? tri_before(r0) : 0;
+    const int64_t np = tri ? tri_before(r1) - tri0 : (r1 - r0) * n;
+    const int64_t nbytes = row_bytes[(size_t)r1] - row_bytes[(size_t)r0];
+    int maxp = 0, maxw = 0;
+    for (int64_t i = r0; i < r1; ++i) {
+      const int32_t pl = P->h_len[(size_t)i], tl = suf_t[tri ? (size_t)i : 0];
+      maxp = std::max(maxp, pl); maxw = std::max(maxw, pl + tl);
+    }
+    b->n = np;
+    b->n_bytes = (uint32_t)nbytes; b->n_packed = (uint32_t)(np - nbytes);
+    b->max_len = std::max(maxp, suf_t[tri ? (size_t)r0 : 0]);
+    b->max_width = maxw + 3;
+    b->d_list_packed = (nbytes > 0 && np > nbytes) ? list_packed : nullptr;
+    b->d_list_bytes = nbytes > 0 ? list_bytes : nullptr;
+    b->d_score = band_score ? band_score : x->d_score + r0 * n;
+    b->d_status = band_status ? band_status : x->d_status + r0 * n;
+    wfa::CrossGenArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.p_woff = P->d_woff; ga.p_len = P->d_len; ga.p_boff = P->d_boff; ga.p_flag = P->d_flag;
+    ga.t_woff = T->d_woff; ga.t_len = T->d_len; ga.t_boff = T->d_boff; ga.t_flag = T->d_flag;
+    ga.t_wshift = t_wshift; ga.t_bshift = t_bshift;
+    ga.words = b->d_words; ga.slot_base = (uint32_t)table_words; ga.slot_words = (uint32_t)slot_words;
+    ga.row_bytes = d_row_bytes; ga.col_flag = d_col_flag;
+    ga.n = n; ga.r0 = r0; ga.tri0 = tri0; ga.npairs = np; ga.tri = tri; ga.all_bytes = all_bytes ? 1 : 0; ga.lists = nbytes > 0 ? 1 : 0;
+    ga.meta = b->d_meta; ga.pboff = b->d_pboff; ga.tboff = b->d_tboff; ga.flags = b->d_flags;
+    ga.list_packed = list_packed; ga.list_bytes = list_bytes;
+    if (wfa::launch_cross_gen(ga, al->stream) != 0) { al->err = "cross band generator launch failed"; return WFA_HIP_EDEVICE; }
+    // the pilots: no-ops once the first band of >= 64 k pairs has picked (the picks live in the view)
+    { const int prc = pilot_first_width(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
+    { const int prc = pilot_lane_heur(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
+    { const int prc = pilot_band(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
+    int rc = wfa_hip_batch_run(b, nullptr);
+    if (rc != WFA_HIP_OK) return rc;
+    wfa::CrossResArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.score = b->d_score; ra.status = b->d_status;
+    ra.n = n; ra.r0 = r0; ra.tri0 = tri0; ra.npairs = np; ra.tri = tri; ra.upper = ava ? 1 : 0; ra.mirror = mirror ? 1 : 0;
+    ra.dense_score = x->d_score; ra.dense_status = x->d_status;
+    if (dense && tri && wfa::launch_cross_scatter(ra, al->stream) != 0) { al->err = "cross scatter launch failed"; return WFA_HIP_EDEVICE; }
+    if (completed) {
+      const int h = (int)(k & 1);
+      ra.blk_count = blk; ra.band_count = d_cnt + h; ra.out_i = st_i[h]; ra.out_j = st_j[h]; ra.out_score = st_s[h];
+      if (wfa::launch_cross_compact(ra, al->stream) != 0) { al->err = "cross compaction launch failed"; return WFA_HIP_EDEVICE; }
+      HIP_TRY(al, hipMemcpyAsync(sc.h_cnt + h, d_cnt + h, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
+      HIP_TRY(al, hipEventRecord(sc.ev[h], al->stream));
+      if (k > 0) { rc = drain(k - 1); if (rc != WFA_HIP_OK) return rc; }
+    }
+    x->pairs += np;
+  }
+  if (completed && nbands > 0) { const int rc = drain(nbands - 1); if (rc != WFA_HIP_OK) return rc; }
+  { const int rc = wfa_hip_batch_sync(b); if (rc != WFA_HIP_OK) return rc; }
+  x->ms = b->ms_sum;
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  return WFA_HIP_OK;
+}
+
+extern "C" wfa_hip_cross_t* wfa_hip_cross_run(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want) {
+  if (!al) { g_error = "null aligner"; return nullptr; }
+  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);
+  wfa_hip_cross* x = new wfa_hip_cross();
+  x->al = al;
+  al->live_batches += 1;
+  const int rc = cross_run_impl(al, patterns, texts, want, x);
+  if (rc != WFA_HIP_OK) { g_error = al->err; wfa_hip_cross_destroy(x); return nullptr; }
+  return x;
+}
+
+extern "C" int wfa_hip_cross_dense(wfa_hip_cross_t* x, int32_t* score, int32_t* status) {
+  if (!x) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = x->al;
+  if (!(x->want & WFA_HIP_CROSS_DENSE)) { al->err = "the run was made without WFA_HIP_CROSS_DENSE"; return WFA_HIP_EINVAL; }
+  const size_t cells = (size_t)(x->m * x->n);
+  if (cells == 0) return WFA_HIP_OK;
+  if (!score || !status) { al->err = "score/status outputs are required"; return WFA_HIP_EINVAL; }
+  HIP_TRY(al, hipSetDevice(al->device));
+  HIP_TRY(al, hipMemcpy(score, x->d_score, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(al, hipMemcpy(status, x->d_status, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_cross_completed(wfa_hip_cross_t* x, int64_t* count, int32_t* i, int32_t* j, int32_t* score) {
+  if (!x || !count) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = x->al;
+  if (!(x->want & WFA_HIP_CROSS_COMPLETED)) { al->err = "the run was made without WFA_HIP_CROSS_COMPLETED"; return WFA_HIP_EINVAL; }
+  *count = x->count;
+  if (x->count == 0) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  const size_t bytes = (size_t)x->count * sizeof(int32_t);
+  if (i) HIP_TRY(al, hipMemcpy(i, x->d_ci, bytes, hipMemcpyDeviceToHost));
+  if (j) HIP_TRY(al, hipMemcpy(j, x->d_cj, bytes, hipMemcpyDeviceToHost));
+  if (score) HIP_TRY(al, hipMemcpy(score, x->d_cs, bytes, hipMemcpyDeviceToHost));
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_cross_kernel_ms(wfa_hip_cross_t* x, float* ms, int64_t* pairs) {
+  if (!x) return WFA_HIP_EINVAL;
+  if (ms) *ms = (float)x->ms;
+  if (pairs) *pairs = x->pairs;
   return WFA_HIP_OK;
 }
