@@ -357,6 +357,8 @@ typedef struct wfa_hip_cross  wfa_hip_cross_t;   /* the results of one cross run
 
 #define WFA_HIP_CROSS_DENSE      1   /* want: the m x n score / status matrices          */
 #define WFA_HIP_CROSS_COMPLETED  2   /* want: the list of completed pairs                */
+#define WFA_HIP_CROSS_TOPK       4   /* want: the k best cells of every row (wfa_hip_cross_run_k only) */
+#define WFA_HIP_CROSS_MAX_K      64  /* the largest k of WFA_HIP_CROSS_TOPK              */
 
 /* Upload n sequences (ASCII; sequence k = seqs[off[k] .. +len[k])) as the word table the kernels read, one word-aligned run per
  * sequence.  The set keeps the lengths on the host, a flag per sequence holding letters outside ACGT (such a sequence also keeps its
@@ -368,6 +370,17 @@ void wfa_hip_seqset_destroy(wfa_hip_seqset_t* set);
 /* Run the cross product of `patterns` x `texts` (texts = NULL: all-vs-all of `patterns`); synchronous.  want = WFA_HIP_CROSS_DENSE
  * and / or WFA_HIP_CROSS_COMPLETED.  The sets must belong to `aligner`.  Returns NULL on error (wfa_hip_last_error). */
 wfa_hip_cross_t* wfa_hip_cross_run(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want);
+/* Top-k per row.  For every row i of the score matrix, the k best of its eligible cells, best first.  Eligible: status 0 (the cells
+ * the completed pairs list), and in all-vs-all mode every column j != i: the diagonal is excluded, and where the run mirrors (the rule
+ * above) the cells j < i of row i are the aligned cells (j, i).  Best: the larger score as the score matrix holds it (so also for
+ * match < 0, where scores are positive), ties to the smaller j; the result does not depend on band sizes or runs.  A row with fewer
+ * than k eligible cells is padded with j = -1, score = INT32_MIN.  Reduced on the device band by band (csrc/wfa_cross.hpp): no m x n
+ * buffer on either side unless WFA_HIP_CROSS_DENSE is also wanted.
+ * wfa_hip_cross_run_k: as wfa_hip_cross_run, want any non-empty combination of WFA_HIP_CROSS_DENSE, _COMPLETED and _TOPK; k (read
+ * only with WFA_HIP_CROSS_TOPK) in 1 .. WFA_HIP_CROSS_MAX_K, else WFA_HIP_EINVAL.  wfa_hip_cross_run refuses WFA_HIP_CROSS_TOPK. */
+wfa_hip_cross_t* wfa_hip_cross_run_k(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want, int k);
+/* The top-k: m x k row-major int32 host arrays of columns and scores (needs WFA_HIP_CROSS_TOPK, else WFA_HIP_EINVAL). */
+int wfa_hip_cross_topk(wfa_hip_cross_t* cross, int32_t* j, int32_t* score);
 /* The dense results: m x n row-major int32 host arrays (needs WFA_HIP_CROSS_DENSE). */
 int wfa_hip_cross_dense(wfa_hip_cross_t* cross, int32_t* score, int32_t* status);
 /* The completed pairs: *count always; i / j / score (each *count entries) when not NULL (needs WFA_HIP_CROSS_COMPLETED). */

@@ -62,10 +62,11 @@ SYMBOLS = [
     "wfa_hip_align_batch_packed2bits", "wfa_hip_batch_create_packed2bits", "wfa_hip_cigar_sprint_pretty",
     "wfa_hip_batch_extent_packed2bits", "wfa_hip_align_pair", "wfa_hip_upload_info",
     "wfa_hip_seqset_create", "wfa_hip_seqset_destroy", "wfa_hip_cross_run", "wfa_hip_cross_dense", "wfa_hip_cross_completed",
-    "wfa_hip_cross_kernel_ms", "wfa_hip_cross_destroy", "wfa_hip_plan_cross_bands",
+    "wfa_hip_cross_kernel_ms", "wfa_hip_cross_destroy", "wfa_hip_plan_cross_bands", "wfa_hip_cross_run_k", "wfa_hip_cross_topk",
 ]
 
-CROSS_DENSE, CROSS_COMPLETED = 1, 2
+CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
+CROSS_MAX_K = 64
 
 
 def lib():
@@ -136,6 +137,9 @@ def lib():
     L.wfa_hip_seqset_destroy.restype = None
     L.wfa_hip_cross_run.argtypes = [vp, vp, vp, ctypes.c_int]
     L.wfa_hip_cross_run.restype = vp
+    L.wfa_hip_cross_run_k.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int]
+    L.wfa_hip_cross_run_k.restype = vp
+    L.wfa_hip_cross_topk.argtypes = [vp, vp, vp]
     L.wfa_hip_cross_dense.argtypes = [vp, vp, vp]
     L.wfa_hip_cross_completed.argtypes = [vp, ctypes.POINTER(i64), vp, vp, vp]
     L.wfa_hip_cross_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
@@ -379,9 +383,9 @@ class Aligner:
     def seqset(self, seqs, off, length):
         return SeqSet(self, seqs, off, length)
 
-    def cross(self, patterns, texts=None, want=CROSS_DENSE):
-        """wfa_hip_cross_run of two SeqSets (texts None: all-vs-all of ``patterns``)."""
-        return CrossRun(self, patterns, texts, want)
+    def cross(self, patterns, texts=None, want=CROSS_DENSE, k=None):
+        """wfa_hip_cross_run of two SeqSets (texts None: all-vs-all of ``patterns``); wfa_hip_cross_run_k when ``k`` is given."""
+        return CrossRun(self, patterns, texts, want, k)
 
 
 def pack_2bit(seq, form=-1):
@@ -465,11 +469,16 @@ class SeqSet:
 class CrossRun:
     """The results of one cross run, resident in HBM (wfa_hip_cross_t)."""
 
-    def __init__(self, aligner, patterns, texts=None, want=CROSS_DENSE):
+    def __init__(self, aligner, patterns, texts=None, want=CROSS_DENSE, k=None):
         self.aligner = aligner
         self.m = patterns.n
         self.n = patterns.n if texts is None else texts.n
-        self._h = lib().wfa_hip_cross_run(aligner._h, patterns._h, None if texts is None else texts._h, int(want))
+        self.k = 0 if k is None else int(k)
+        th = None if texts is None else texts._h
+        if k is None:
+            self._h = lib().wfa_hip_cross_run(aligner._h, patterns._h, th, int(want))
+        else:
+            self._h = lib().wfa_hip_cross_run_k(aligner._h, patterns._h, th, int(want), self.k)
         if not self._h:
             msg = aligner.error()
             if "failed" in msg:
@@ -506,6 +515,14 @@ class CrossRun:
             rc = lib().wfa_hip_cross_completed(self._h, ctypes.byref(count), _ptr(out["i"]), _ptr(out["j"]), _ptr(out["score"]))
             if rc != OK:
                 self.aligner._raise(rc, "wfa_hip_cross_completed")
+        return out
+
+    def topk(self):
+        """wfa_hip_cross_topk: dict(j=, score=), int32 arrays of shape (m, k)."""
+        out = {key: np.zeros((self.m, self.k), np.int32) for key in ("j", "score")}
+        rc = lib().wfa_hip_cross_topk(self._h, _ptr(out["j"]), _ptr(out["score"]))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_cross_topk")
         return out
 
     def kernel_ms(self):

@@ -542,15 +542,17 @@ class WavefrontAligner:
             batch = datagen.from_strings(b"", seqs, upper=True)
         return self._native.seqset(batch["seqs"], batch["t_off"], batch["t_len"])
 
-    def _cross(self, patterns, texts, want):
+    def _cross(self, patterns, texts, want, k=None):
         if self._cfg.wildcard != self._bwildcard:
             self._push()
         sets = [self._seqset(patterns)]
         if texts is not None:
             sets.append(self._seqset(texts))
         try:
-            run = self._native.cross(sets[0], sets[1] if texts is not None else None, want)
+            run = self._native.cross(sets[0], sets[1] if texts is not None else None, want, k)
             try:
+                if want == _native.CROSS_TOPK:
+                    return run.topk()
                 return run.dense() if want == _native.CROSS_DENSE else run.completed()
             finally:
                 run.close()
@@ -572,6 +574,18 @@ class WavefrontAligner:
         int32 arrays in row-major order of (i, j).  ``texts=None``: all-vs-all, the pairs i < j only.  Meant for runs under
         ``max_steps`` (the pairs within that score: clustering, de-duplication, nearest candidates)."""
         return self._cross(patterns, texts, _native.CROSS_COMPLETED)
+
+    def nearest(self, patterns, texts=None, k=1):
+        """The ``k`` best cells of every row of ``score_matrix``, reduced on the GPU without the M x N matrix on either side:
+        ``dict(j=, score=)`` of int32 arrays of shape (M, k), best first.  Only cells whose status is 0 count (those of
+        ``completed_pairs``); best is the larger score, ties to the smaller j.  ``texts=None``: all-vs-all, row i takes every
+        j != i (the diagonal is excluded).  A row with fewer than ``k`` such cells is padded with ``j = -1``, ``score = INT32_MIN``.
+        ``k``: 1 .. 64.  Meant for runs under ``max_steps`` (the nearest candidates of every query, with a bounded output)."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"k must be an integer in 1 .. {_native.CROSS_MAX_K}, got {k!r}")
+        if not 1 <= int(k) <= _native.CROSS_MAX_K:
+            raise ValueError(f"k must be in 1 .. {_native.CROSS_MAX_K}, got {k}")
+        return self._cross(patterns, texts, _native.CROSS_TOPK, int(k))
 
     # ------------------------------------------------------------------ results
     @property

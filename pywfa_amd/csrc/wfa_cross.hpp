@@ -1,6 +1,6 @@
 // wfa_cross.hpp — all-vs-all and many-vs-many score matrices (wfa_hip_cross_run, csrc/wfa_hip.hip): the pair metadata of a band of
 // the cross product, generated on the device from two sequence sets packed once (wfa_hip_seqset_create), and what is done with the
-// band's results (scatter into the dense matrix, ordered compaction of the completed pairs).  Kernels in k_cross.hip.
+// band's results (scatter into the dense matrix, ordered compaction of the completed pairs, top-k per row).  Kernels in k_cross.hip.
 //
 // Layout.  A set is one word-aligned run of 2-bit words per sequence (the batch layout of wfa_pack.hpp).  A run joins the sets' words
 // in one table (the text set's offsets shifted behind the pattern set's) followed by one slot per band pair: the register stages
@@ -59,6 +59,34 @@ struct CrossResArgs {
 };
 
 #define WFA_CROSS_CHUNK 4096   // pairs per workgroup of the compaction (256 threads x 16 rounds)
+
+// Top-k per row (wfa_hip_cross_run_k, WFA_HIP_CROSS_TOPK).  A candidate is one 64-bit key, ((uint32)(score ^ 0x80000000) << 32) |
+// (uint32)~j: the k best cells of a row are its k largest keys (larger score first, then smaller j); key 0 is "empty" (it decodes to
+// j = -1, score = INT32_MIN) and no cell has it.  Every wave keeps a list of 64 keys sorted in descending order across its lanes (lane t:
+// rank t) and a wave-uniform bar, the list's k-th key: cells that beat it are compacted into 128 keys of LDS by ballot, and the list is
+// merged with them (bitonic, across lanes) only when 64 are waiting.  Per band, after the band's alignment, in two launches on the stream:
+//  * row pass (only where a band row is longer than `chunk`): one wave per (band row, chunk of `chunk` cells) writes its chunk's k best
+//    keys to part[(row - r0) * nch + chunk];
+//  * merge: one wave per target row reads the row's running list (k keys in HBM, sorted), merges the row's own cells (or its chunk
+//    lists) and, in a triangle band, the cells (i, row) of the band's rows i < row (the mirrored column: cell (i, j) of the upper
+//    triangle is also a candidate of row j), and writes the list back.  Each row is owned by one wave of one launch: no atomics, the
+//    result is the same whatever the band and chunk sizes.
+struct CrossTopkArgs {
+  const int32_t* score;     // the band's results (pair q)
+  const int32_t* status;
+  int64_t n, r0, r1, tri0;
+  int tri;                  // upper-triangle band: row i holds columns j >= i; the merge also takes the columns (rows r0 .. n)
+  int ava;                  // all-vs-all: the diagonal cell is no candidate
+  int k;                    // 1 .. WFA_CROSS_MAX_K
+  int64_t chunk;            // cells per chunk of the row pass (a multiple of 64)
+  int64_t nch;              // chunks per band row; 0: no row pass, the merge reads the rows' cells itself
+  uint64_t* part;           // row pass: k keys per (band row, chunk)
+  uint64_t* run;            // the running lists: k keys per target row, descending
+};
+
+#define WFA_CROSS_MAX_K 64
+
+int launch_cross_topk(const CrossTopkArgs& a, hipStream_t stream);
 
 int launch_cross_gen(const CrossGenArgs& a, hipStream_t stream);
 int launch_cross_scatter(const CrossResArgs& a, hipStream_t stream);

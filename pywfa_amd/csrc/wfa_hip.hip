@@ -52,7 +52,7 @@ static thread_local std::string g_error;
   F(ARENA_KB) F(BAND_DEBUG) F(BAND_SLIM) F(BAND_LDS_MAX) F(BAND_NO_WIN) F(BAND_SPLIT_MIN) F(NO_TINY_INLINE) F(BILEVEL) F(BILEVEL_WIDE_LEVELS) F(BILEVEL_PER_CU) F(BILEVEL_I32) F(BILEVEL_QCAP) F(BILEVEL_LEVELS) F(BILEVEL_LDS) F(BILEVEL_NO_1024) F(BILEVEL_HUGE_MIN) F(BILEVEL_LDS_W) F(BILEVEL_NO_SEQL) F(LANE_DYN) F(LANE_DYN_WAVES) F(BAND_LEFTOVER_WAVES_PER_CU) F(BAND_NCH) F(BAND_NO_LDS) F(BAND_NO_SPLIT) F(BAND_PB) F(PIPE_TAIL) F(LEN16) F(MAILBOX) F(MAILBOX_IDLE_US) F(TILE32)     \
   F(BAND_RECORDS) F(BAND_SPLIT_ROUNDS) F(BAND_WAVES_PER_CU) F(NO_BAND) F(NO_FAST) F(NO_SEGFULL) F(SEGFULL_PAIRS)     \
   F(SEGFULL_STAGES) F(STAGE_TIMING) F(LANE_HEUR32) F(THREADS) F(TINY_BATCH) F(WAVES_PER_CU) F(FAST_WAVES_PER_CU) F(TIMING)          \
-  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT) F(CROSS_BAND)
+  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT) F(CROSS_BAND) F(CROSS_TOPK_CHUNK)
 enum WfaKnob {
 #define WFA_KNOB_ENUM(n) K_##n,
   WFA_KNOBS(WFA_KNOB_ENUM)
@@ -3619,12 +3619,16 @@ struct wfa_hip_seqset {
   uint32_t* d_woff = nullptr; int32_t* d_len = nullptr; int64_t* d_boff = nullptr; uint8_t* d_flag = nullptr;
 };
 
+static_assert(WFA_CROSS_MAX_K == WFA_HIP_CROSS_MAX_K, "top-k bound of the kernels and of the ABI");
+
 struct wfa_hip_cross {
   wfa_hip_aligner* al = nullptr;
   int64_t m = 0, n = 0;
   int want = 0;
   int32_t* d_score = nullptr; int32_t* d_status = nullptr;           // dense: m x n
   int32_t* d_ci = nullptr; int32_t* d_cj = nullptr; int32_t* d_cs = nullptr;   // completed pairs
+  int k = 0;
+  uint64_t* d_topk = nullptr;                                          // top-k: m x k keys (wfa_cross.hpp), descending per row
   int64_t count = 0, cap = 0;
   double ms = 0.0;
   int64_t pairs = 0;
@@ -3734,7 +3738,7 @@ extern "C" void wfa_hip_cross_destroy(wfa_hip_cross_t* x) {
   wfa_hip_aligner* al = x->al;
   (void)hipSetDevice(al->device);
   (void)hipStreamSynchronize(al->stream);
-  void* ptrs[] = {x->d_score, x->d_status, x->d_ci, x->d_cj, x->d_cs};
+  void* ptrs[] = {x->d_score, x->d_status, x->d_ci, x->d_cj, x->d_cs, x->d_topk};
   for (void* p : ptrs) pool_release(al, p);
   delete x;
   aligner_release_ref(al);
@@ -3759,16 +3763,21 @@ struct CrossScratch {
   }
 };
 
-static int cross_run_impl(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wfa_hip_seqset* T, int want, wfa_hip_cross* x) {
+static int cross_run_impl(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wfa_hip_seqset* T, int want, int top_k, wfa_hip_cross* x) {
   const bool ava = (T == nullptr);
   if (ava) T = P;
   if (!P || P->al != al || T->al != al) { al->err = "sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (want <= 0 || (want & ~(WFA_HIP_CROSS_DENSE | WFA_HIP_CROSS_COMPLETED)) != 0) { al->err = "want: WFA_HIP_CROSS_DENSE and / or WFA_HIP_CROSS_COMPLETED"; return WFA_HIP_EINVAL; }
+  if (want <= 0 || (want & ~(WFA_HIP_CROSS_DENSE | WFA_HIP_CROSS_COMPLETED | WFA_HIP_CROSS_TOPK)) != 0) {
+    al->err = "want: a combination of WFA_HIP_CROSS_DENSE, WFA_HIP_CROSS_COMPLETED and WFA_HIP_CROSS_TOPK"; return WFA_HIP_EINVAL;
+  }
+  if ((want & WFA_HIP_CROSS_TOPK) && (top_k < 1 || top_k > WFA_HIP_CROSS_MAX_K)) { al->err = "k: 1 .. WFA_HIP_CROSS_MAX_K (64)"; return WFA_HIP_EINVAL; }
   if (P->wildcard != al->cfg.wildcard || T->wildcard != al->cfg.wildcard) { al->err = "sequence set packed under another wildcard: create it again"; return WFA_HIP_EINVAL; }
   wfa_hip_config_t c = al->cfg;
   c.scope = WFA_SCOPE_SCORE;
   const int64_t m = P->n, n = T->n;
   x->m = m; x->n = n; x->want = want;
+  const bool topk = (want & WFA_HIP_CROSS_TOPK) != 0;
+  if (topk) x->k = top_k;
   if (c.span == WFA_SPAN_ENDSFREE && m > 0 && n > 0) {   // (wavefront_align.c:86-102, as batch_build)
     const int32_t minp = *std::min_element(P->h_len.begin(), P->h_len.end()), mint = *std::min_element(T->h_len.begin(), T->h_len.end());
     if (c.pattern_begin_free > minp || c.pattern_end_free > minp || c.text_begin_free > mint || c.text_end_free > mint) {
@@ -3780,7 +3789,7 @@ static int cross_run_impl(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wf
     HIP_TRY(al, pool_alloc(al, (void**)&x->d_score, (size_t)(m * n) * sizeof(int32_t)));
     HIP_TRY(al, pool_alloc(al, (void**)&x->d_status, (size_t)(m * n) * sizeof(int32_t)));
   }
-  if (m == 0 || n == 0) return WFA_HIP_OK;
+  if (m == 0 || n == 0) return WFA_HIP_OK;   // (top-k: all padding, written by wfa_hip_cross_topk)
   // the mirror rule: the score of (P[j], P[i]) is that of (P[i], P[j]) when nothing tells the pattern from the text — no heuristic (their
   // cut-offs look at offsets, not at the alignment's symmetry) and the same free ends on both sides
   const bool mirror = ava && c.heuristic == WFA_HEUR_NONE &&
@@ -3877,6 +3886,26 @@ static int cross_run_impl(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wf
     HIP_TRY(al, hipHostMalloc((void**)&sc.h_cnt, 2 * sizeof(uint32_t), hipHostMallocDefault));
     for (int h = 0; h < 2; ++h) HIP_TRY(al, hipEventCreateWithFlags(&sc.ev[h], hipEventDisableTiming));
   }
+  // top-k: the running lists (m x k keys, "empty") and the row pass's chunk lists.  A band row longer than one chunk is split into
+  // chunks of `chunk` cells, each reduced by a wave of its own (a band of a wide rectangle holds few rows); the chunk grows until the
+  // largest band's chunk lists fit a share of the free memory
+  int64_t chunk = 0;
+  uint64_t* part = nullptr;
+  auto band_chunks = [&](int64_t r0b) { const int64_t len = tri ? n - r0b : n; return len > chunk ? (len + chunk - 1) / chunk : (int64_t)0; };
+  if (topk) {
+    HIP_TRY(al, pool_alloc(al, (void**)&x->d_topk, (size_t)m * (size_t)top_k * sizeof(uint64_t)));
+    HIP_TRY(al, hipMemsetAsync(x->d_topk, 0, (size_t)m * (size_t)top_k * sizeof(uint64_t), al->stream));
+    chunk = std::max<int64_t>(64, ((int64_t)knob(al, K_CROSS_TOPK_CHUNK, 4096) + 63) / 64 * 64);
+    int64_t part_keys = 0;
+    for (;;) {
+      part_keys = 0;
+      for (int64_t kb = 0; kb < nbands; ++kb)
+        part_keys = std::max(part_keys, (rb[(size_t)kb + 1] - rb[(size_t)kb]) * band_chunks(rb[(size_t)kb]) * top_k);
+      if (part_keys * (int64_t)sizeof(uint64_t) <= std::max<int64_t>(free_budget(al) / 8, (int64_t)64 << 20) || chunk >= ((int64_t)1 << 30)) break;
+      chunk *= 2;
+    }
+    if (part_keys > 0 && sc.alloc(&part, (size_t)part_keys)) return WFA_HIP_EDEVICE;
+  }
   auto drain = [&](int64_t k) -> int {   // append band k's completed pairs to the handle's list
     const int h = (int)(k & 1);
     HIP_TRY(al, hipEventSynchronize(sc.ev[h]));
@@ -3949,6 +3978,14 @@ static int cross_run_impl(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wf
       HIP_TRY(al, hipEventRecord(sc.ev[h], al->stream));
       if (k > 0) { rc = drain(k - 1); if (rc != WFA_HIP_OK) return rc; }
     }
+    if (topk) {
+      wfa::CrossTopkArgs ta;
+      memset(&ta, 0, sizeof(ta));
+      ta.score = b->d_score; ta.status = b->d_status;
+      ta.n = n; ta.r0 = r0; ta.r1 = r1; ta.tri0 = tri0; ta.tri = tri; ta.ava = ava ? 1 : 0;
+      ta.k = x->k; ta.chunk = chunk; ta.nch = band_chunks(r0); ta.part = part; ta.run = x->d_topk;
+      if (wfa::launch_cross_topk(ta, al->stream) != 0) { al->err = "cross top-k launch failed"; return WFA_HIP_EDEVICE; }
+    }
     x->pairs += np;
   }
   if (completed && nbands > 0) { const int rc = drain(nbands - 1); if (rc != WFA_HIP_OK) return rc; }
@@ -3958,16 +3995,42 @@ static int cross_run_impl(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wf
   return WFA_HIP_OK;
 }
 
-extern "C" wfa_hip_cross_t* wfa_hip_cross_run(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want) {
+extern "C" wfa_hip_cross_t* wfa_hip_cross_run_k(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want, int k) {
   if (!al) { g_error = "null aligner"; return nullptr; }
   if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
   if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);
   wfa_hip_cross* x = new wfa_hip_cross();
   x->al = al;
   al->live_batches += 1;
-  const int rc = cross_run_impl(al, patterns, texts, want, x);
+  const int rc = cross_run_impl(al, patterns, texts, want, k, x);
   if (rc != WFA_HIP_OK) { g_error = al->err; wfa_hip_cross_destroy(x); return nullptr; }
   return x;
+}
+
+extern "C" wfa_hip_cross_t* wfa_hip_cross_run(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want) {
+  if (al && (want & WFA_HIP_CROSS_TOPK)) {
+    al->err = "want: WFA_HIP_CROSS_DENSE and / or WFA_HIP_CROSS_COMPLETED (top-k: wfa_hip_cross_run_k)"; g_error = al->err; return nullptr;
+  }
+  return wfa_hip_cross_run_k(al, patterns, texts, want, 0);
+}
+
+extern "C" int wfa_hip_cross_topk(wfa_hip_cross_t* x, int32_t* j, int32_t* score) {
+  if (!x) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = x->al;
+  if (!(x->want & WFA_HIP_CROSS_TOPK)) { al->err = "the run was made without WFA_HIP_CROSS_TOPK"; return WFA_HIP_EINVAL; }
+  const size_t cells = (size_t)x->m * (size_t)x->k;
+  if (cells == 0) return WFA_HIP_OK;
+  if (!j || !score) { al->err = "j/score outputs are required"; return WFA_HIP_EINVAL; }
+  std::vector<uint64_t> keys(cells, 0ull);   // (no device list: no columns, every row is padding)
+  if (x->d_topk) {
+    HIP_TRY(al, hipSetDevice(al->device));
+    HIP_TRY(al, hipMemcpy(keys.data(), x->d_topk, cells * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  }
+  for (size_t c = 0; c < cells; ++c) {   // key 0 decodes to j = -1, score = INT32_MIN
+    j[c] = (int32_t)~(uint32_t)keys[c];
+    score[c] = (int32_t)((uint32_t)(keys[c] >> 32) ^ 0x80000000u);
+  }
+  return WFA_HIP_OK;
 }
 
 extern "C" int wfa_hip_cross_dense(wfa_hip_cross_t* x, int32_t* score, int32_t* status) {
