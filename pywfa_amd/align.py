@@ -399,10 +399,19 @@ class WavefrontAligner:
         self.pattern_len = len(self._bpattern)
 
     def _push(self):
-        self._cfg.wildcard = self._bwildcard
-        self._native.set_config(self._cfg)
+        # (the wildcard set through its setter goes with the push; _cfg records it only once the library took the configuration,
+        # so that a refused setter leaves the pending wildcard pending)
+        cfg = self._cfg.copy()
+        cfg.wildcard = self._bwildcard
+        self._native.set_config(cfg)
         if self._multi is not None:
-            self._multi.set_config(self._cfg)
+            self._multi.set_config(cfg)
+        self._cfg.wildcard = self._bwildcard
+
+    def _sync_wildcard(self):
+        """Push a wildcard set through the setter that the library does not have yet (every entry point calls this first)."""
+        if self._cfg.wildcard != self._bwildcard:
+            self._push()
 
     # ------------------------------------------------------------------ single pair
     def wavefront_align(self, text, pattern=None):
@@ -414,8 +423,7 @@ class WavefrontAligner:
         self.text_len = len(t)
         if self._bpattern is None:
             raise AttributeError("pattern has not been set")
-        if self._cfg.wildcard != self._bwildcard:
-            self._push()
+        self._sync_wildcard()
         # one pair per call: wfa_hip_align_pair (no arrays on the way; about 14 us per 150 bp call at the C ABI, 19 us with the op
         # string — the reference takes 1-2 us on a host core: loops of single calls work and are exact, throughput needs
         # wavefront_align_batch)
@@ -469,8 +477,7 @@ class WavefrontAligner:
             patterns = self._bpattern  # stored once in the batch: every pair points to it
         else:
             patterns = patterns if type(patterns) is list else list(patterns)
-        if self._cfg.wildcard != self._bwildcard:
-            self._push()
+        self._sync_wildcard()
         # the compiled host reads the objects' buffers in place and upper-cases on OpenMP threads (pywfa_amd/host/_host.pyx); objects
         # it does not take (non-ASCII text, other types) and builds without the extension go through datagen.from_strings, which
         # raises what the reference raises (align.pyx:432,435)
@@ -483,6 +490,7 @@ class WavefrontAligner:
 
     def align_batch(self, batch):
         """Align a prepared batch dict (see ``pywfa_amd.datagen``): ASCII blob + offsets + lengths."""
+        self._sync_wildcard()
         full = self._cfg.scope == 1
         if full and self._multi is None and len(batch["p_len"]) <= 1024:
             # a small batch: the single-call form of the library (one launch, results polled in a pinned block); the CIGAR
@@ -516,6 +524,7 @@ class WavefrontAligner:
         cigartuples / locations of every pair computed on the GPU (what ``__call__`` derives per pair)."""
         if self._cfg.scope != 1:
             raise ValueError("align_batch_results needs scope='full'")
+        self._sync_wildcard()
         rb = self._native.batch(batch)
         try:
             rb.run()
@@ -527,7 +536,9 @@ class WavefrontAligner:
         return BatchResults(batch, score, status, off, code, rlen, locs)
 
     def resident_batch(self, batch):
-        """Upload + 2-bit pack a batch into HBM once; ``.run()`` it many times (bench.py)."""
+        """Upload + 2-bit pack a batch into HBM once; ``.run()`` it many times (bench.py).  The batch keeps the configuration
+        (wildcard included) that is in force when it is created."""
+        self._sync_wildcard()
         return self._native.batch(batch)
 
     # ------------------------------------------------------------------ score matrices (additive API)
@@ -543,8 +554,7 @@ class WavefrontAligner:
         return self._native.seqset(batch["seqs"], batch["t_off"], batch["t_len"])
 
     def _cross(self, patterns, texts, want, k=None):
-        if self._cfg.wildcard != self._bwildcard:
-            self._push()
+        self._sync_wildcard()
         sets = [self._seqset(patterns)]
         if texts is not None:
             sets.append(self._seqset(texts))
@@ -707,8 +717,13 @@ class WavefrontAligner:
     @max_steps.setter
     def max_steps(self, steps):
         steps = int(steps)
+        old = self._cfg.max_steps
         self._cfg.max_steps = steps if 0 < steps < _INT_MAX else 0
-        self._push()
+        try:
+            self._push()
+        except Exception:
+            self._cfg.max_steps = old
+            raise
 
     def close(self):
         self._native.close()

@@ -413,9 +413,11 @@ static void map_to_gap_affine(const wfa_hip_config_t& c, WfaDevConfig* d, int* n
 }
 
 // gd / gncomp: the configuration the GENERAL kernel runs — the same, unless a one-component distance with CIGARs was mapped (d->lin)
+// d starts from zero: wfa_hip_set_config passes the aligner's live configuration, and nothing of the previous one may carry over (the
+// snapshots orig / orig1 below used to keep its score_mode / sw_match, which a LIN configuration's general kernel then reported with)
 static void derive_dev_config(const wfa_hip_config_t& c, WfaDevConfig* d, int* ncomp, WfaDevConfig* gd = nullptr, int* gncomp = nullptr) {
   const bool two = (c.distance == WFA_DIST_AFFINE2P);
-  d->lin = 0;
+  *d = WfaDevConfig{};
   d->metric = c.distance;
   if (c.distance <= WFA_DIST_LINEAR) {
     // single-component metrics: wavefront_penalties.c:39-94, wavefront_components.c:43-74
