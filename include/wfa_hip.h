@@ -396,6 +396,23 @@ void wfa_hip_cross_destroy(wfa_hip_cross_t* cross);
  * Returns nbands, or WFA_HIP_EINVAL. */
 int64_t wfa_hip_plan_cross_bands(int64_t m, int64_t n, int triangle, int64_t max_pairs, int64_t* row_begin, int64_t cap);
 
+/* ---- indexed batches: a list of (i, j) index pairs over resident sequence sets ----------------------------- */
+
+/* A resident batch whose pair q is (patterns[i[q]], texts[j[q]]); texts = NULL: both indices into `patterns`.  The result is an
+ * ordinary batch: run / sync / results / rle_counts / rle_runs / last_kernel_ms / algorithmic_bytes / fallback_pairs / destroy work on
+ * it unchanged, and pair q's score, status and op string are exactly what wfa_hip_align_batch returns for that pair under the
+ * aligner's configuration at this call, scope included (scope full: op strings, in regions of plen + tlen bytes in list order, as a
+ * batch's).  Results are in list order; duplicates, i == j and empty sequences are legal; npairs = 0 is a valid empty batch.  Eight
+ * bytes per pair cross PCIe: the pair metadata and the pairs' words are laid out on the device from the sets' tables
+ * (csrc/wfa_cross.hpp).
+ * WFA_HIP_EINVAL (NULL, wfa_hip_last_error; nothing is launched): an index outside its set (the message names the first such
+ * position), a set of another aligner or packed under another wildcard, free ends larger than a LISTED sequence (checked per listed
+ * pair: a short sequence no pair names is harmless), more than 2^32 words of sets and slots ("split the list").
+ * The index arrays are not read after the call returns, and the batch stays valid after either set is destroyed (it copies what it
+ * needs of them on the device).  A set serves any number of indexed batches and cross runs, in any order. */
+wfa_hip_batch_t* wfa_hip_batch_create_indexed(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts,
+                                              int64_t npairs, const int32_t* i, const int32_t* j);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,7 @@ SYMBOLS = [
     "wfa_hip_batch_extent_packed2bits", "wfa_hip_align_pair", "wfa_hip_upload_info",
     "wfa_hip_seqset_create", "wfa_hip_seqset_destroy", "wfa_hip_cross_run", "wfa_hip_cross_dense", "wfa_hip_cross_completed",
     "wfa_hip_cross_kernel_ms", "wfa_hip_cross_destroy", "wfa_hip_plan_cross_bands", "wfa_hip_cross_run_k", "wfa_hip_cross_topk",
+    "wfa_hip_batch_create_indexed",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
@@ -147,6 +148,8 @@ def lib():
     L.wfa_hip_cross_destroy.restype = None
     L.wfa_hip_plan_cross_bands.argtypes = [i64, i64, ctypes.c_int, i64, vp, i64]
     L.wfa_hip_plan_cross_bands.restype = i64
+    L.wfa_hip_batch_create_indexed.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.wfa_hip_batch_create_indexed.restype = vp
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -383,6 +386,11 @@ class Aligner:
     def seqset(self, seqs, off, length):
         return SeqSet(self, seqs, off, length)
 
+    def batch_indexed(self, patterns, texts, i, j):
+        """wfa_hip_batch_create_indexed: the ResidentBatch whose pair q is (patterns[i[q]], texts[j[q]]) of two SeqSets (texts None:
+        both indices into ``patterns``)."""
+        return ResidentBatch.indexed(self, patterns, texts, i, j)
+
     def cross(self, patterns, texts=None, want=CROSS_DENSE, k=None):
         """wfa_hip_cross_run of two SeqSets (texts None: all-vs-all of ``patterns``); wfa_hip_cross_run_k when ``k`` is given."""
         return CrossRun(self, patterns, texts, want, k)
@@ -446,6 +454,7 @@ class SeqSet:
             raise ValueError("sequence offsets run past the blob")
         self.aligner = aligner
         self.n = n
+        self.length = length.copy()   # (an indexed batch sizes its op buffers from the lengths)
         self._h = lib().wfa_hip_seqset_create(aligner._h, n, _ptr(seqs) if seqs.size else None, _ptr(off), _ptr(length))
         if not self._h:
             msg = aligner.error()
@@ -613,6 +622,43 @@ class ResidentBatch:
                 raise NativeError(f"wfa_hip_batch_create: {msg}")
             raise ValueError(f"wfa_hip_batch_create: {msg}")
         aligner._batches.add(self)
+
+    @classmethod
+    def indexed(cls, aligner, patterns, texts, i, j):
+        """wfa_hip_batch_create_indexed over two SeqSets (texts None: both indices into ``patterns``).  ``i`` / ``j``: integer arrays
+        of equal length, every value inside its set (the library checks them again and raises ValueError)."""
+        for a in (np.asarray(i), np.asarray(j)):
+            if a.size and (a.dtype.kind not in "iu" or
+                           (a.dtype != np.int32 and (int(a.min()) < -2**31 or int(a.max()) >= 2**31))):
+                raise ValueError("index arrays must hold integers that fit 32 bits")
+        i = np.ascontiguousarray(i, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        if i.ndim != 1 or i.shape != j.shape:
+            raise ValueError("index arrays differ in length")
+        tset = patterns if texts is None else texts
+        if not patterns._h or not tset._h:
+            raise ValueError("sequence set is closed")
+        self = cls.__new__(cls)
+        self.aligner = aligner
+        self.n = n = i.shape[0]
+        # (the pairs' lengths, which size the op buffers of results(True), are looked up when first asked for: the library has
+        # checked the indices by then)
+        self._lens = (patterns.length, tset.length, i, j)
+        self._h = lib().wfa_hip_batch_create_indexed(aligner._h, patterns._h, texts._h if texts is not None else None, n, _ptr(i), _ptr(j))
+        if not self._h:
+            msg = aligner.error()
+            if "failed:" in msg:
+                raise NativeError(f"wfa_hip_batch_create_indexed: {msg}")
+            raise ValueError(f"wfa_hip_batch_create_indexed: {msg}")
+        aligner._batches.add(self)
+        return self
+
+    def __getattr__(self, name):
+        if name in ("_p_len", "_t_len") and "_lens" in self.__dict__:   # an indexed batch: the listed pairs' lengths, on first use
+            pl, tl, i, j = self._lens
+            self._p_len, self._t_len = pl[i], tl[j]
+            return self.__dict__[name]
+        raise AttributeError(name)
 
     def close(self):
         if getattr(self, "_h", None):

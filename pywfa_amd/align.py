@@ -17,6 +17,7 @@ Deliberate deviations from the reference (DESIGN.md §"Deviations"):
   * property setters re-derive the whole native configuration (the reference pokes single C fields
     and leaves derived state stale).
 """
+import os
 import sys
 
 import numpy as np
@@ -324,6 +325,33 @@ class BatchResults:
                                int(self.status[i]))
 
 
+class SequenceSet:
+    """Sequences kept on the GPU, uploaded and packed once (``WavefrontAligner.sequence_set``): pass it wherever ``score_matrix``,
+    ``completed_pairs``, ``nearest`` and ``align_pairs`` take a list of sequences.  ``len()`` is the number of sequences; ``close()``
+    (or leaving the ``with`` block) releases the device memory.  Results already returned stay valid."""
+
+    def __init__(self, aligner, native_set):
+        self._aligner = aligner
+        self._set = native_set
+
+    def __len__(self):
+        if self._set is None:
+            raise ValueError("sequence set is closed")
+        return self._set.n
+
+    def close(self):
+        if self._set is not None:
+            self._set.close()
+            self._set = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class WavefrontAligner:
     """Drop-in for ``pywfa.WavefrontAligner`` on the GPU. If a pattern is supplied it is cached.
 
@@ -553,11 +581,36 @@ class WavefrontAligner:
             batch = datagen.from_strings(b"", seqs, upper=True)
         return self._native.seqset(batch["seqs"], batch["t_off"], batch["t_len"])
 
+    def sequence_set(self, seqs):
+        """Upload a list of sequences once and keep them on the GPU: a ``SequenceSet`` (``len()``, ``close()``, context manager) that
+        ``score_matrix``, ``completed_pairs``, ``nearest`` and ``align_pairs`` accept wherever they accept a list of ``str``.  The set
+        is packed under the wildcard in force now; after ``wildcard`` changes, make a new one."""
+        self._sync_wildcard()
+        return SequenceSet(self, self._seqset(seqs))
+
+    def _open_sets(self, patterns, texts):
+        """The native sets of ``patterns`` / ``texts`` (None: one set) and those of them this call uploaded (its to close)."""
+        sets, mine = [], []
+        try:
+            for x in ((patterns,) if texts is None else (patterns, texts)):
+                if isinstance(x, SequenceSet):
+                    if x._aligner is not self:
+                        raise ValueError("sequence set of another aligner")
+                    if x._set is None or not x._set._h:
+                        raise ValueError("sequence set is closed")
+                    sets.append(x._set)
+                else:
+                    sets.append(self._seqset(x))
+                    mine.append(sets[-1])
+        except BaseException:
+            for s in mine:
+                s.close()
+            raise
+        return sets, mine
+
     def _cross(self, patterns, texts, want, k=None):
         self._sync_wildcard()
-        sets = [self._seqset(patterns)]
-        if texts is not None:
-            sets.append(self._seqset(texts))
+        sets, mine = self._open_sets(patterns, texts)
         try:
             run = self._native.cross(sets[0], sets[1] if texts is not None else None, want, k)
             try:
@@ -567,8 +620,111 @@ class WavefrontAligner:
             finally:
                 run.close()
         finally:
-            for s in sets:
+            for s in mine:
                 s.close()
+
+    # ------------------------------------------------------------------ index pairs over resident sets (additive API)
+    @staticmethod
+    def _check_pair_indices(i, j, m, n):
+        """The index arrays of ``align_pairs`` as int32, or ValueError: before anything is uploaded."""
+        out = []
+        for name, a, size in (("i", i, m), ("j", j, n)):
+            if a is None:
+                raise ValueError(f"align_pairs needs the index arrays i= and j= ({name} is missing)")
+            a = np.asarray(a)
+            if a.ndim != 1:
+                raise ValueError(f"{name} must be a one-dimensional array of indices")
+            if a.size == 0:
+                a = a.astype(np.int32)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"{name} must hold integers, got dtype {a.dtype}")
+            if a.size:
+                if int(a.min()) < 0:
+                    raise ValueError(f"{name}[{int(np.flatnonzero(a < 0)[0])}] is negative: filter such rows out first "
+                                     "(nearest() pads its rows with j = -1)")
+                if int(a.max()) >= size:
+                    q = int(np.flatnonzero(a >= size)[0])
+                    raise ValueError(f"{name}[{q}] = {int(a[q])} is out of range for a set of {size} sequences")
+            out.append(np.ascontiguousarray(a, dtype=np.int32))
+        if out[0].shape[0] != out[1].shape[0]:
+            raise ValueError(f"i and j differ in length: {out[0].shape[0]} and {out[1].shape[0]}")
+        return out
+
+    def align_pairs(self, patterns, texts=None, *, i=None, j=None):
+        """Align the listed pairs (patterns[i[q]], texts[j[q]]) on the GPU, each sequence uploaded once however many pairs name it;
+        ``texts=None``: both indices into ``patterns``.  ``patterns`` / ``texts``: lists of ``str`` (uploaded and released inside
+        the call) or ``SequenceSet`` handles of ``sequence_set`` (left open).  ``i`` / ``j``: integer arrays of equal length, every
+        value inside its set (ValueError before anything is uploaded otherwise: rows of ``nearest`` padded with ``j = -1`` must be
+        filtered out first).  Duplicates, ``i == j`` and empty sequences are fine.
+
+        Returns what ``wavefront_align_batch`` returns for those pairs under this aligner's configuration, in list order:
+        dict(score=, status=) and, with scope full, cigarstrings= / cigar_ops=.  With ``devices=[...]`` the first device runs it."""
+        if not isinstance(patterns, (SequenceSet, list)):
+            patterns = list(patterns)
+        if texts is not None and not isinstance(texts, (SequenceSet, list)):
+            texts = list(texts)
+        m = len(patterns)
+        n = m if texts is None else len(texts)
+        i, j = self._check_pair_indices(i, j, m, n)
+        self._sync_wildcard()
+        full = self._cfg.scope == 1
+        npairs = i.shape[0]
+        sets, mine = self._open_sets(patterns, texts)
+        try:
+            pset, tset = sets[0], sets[-1]
+            # lists too long for one batch run in consecutive chunks: a pair budget (WFA_HIP_PAIRS_BAND pairs, as WFA_HIP_CROSS_BAND caps
+            # a band of a cross run) and the library's bound on the words of one batch (2^32; half of it here)
+            budget = max(1, int(os.environ.get("WFA_HIP_PAIRS_BAND", "0") or 0) or (1 << 24))
+            longest = ((int(pset.length.max()) + 15) >> 4) + ((int(tset.length.max()) + 15) >> 4) if npairs else 0
+            cuts = [0]
+            if npairs <= budget and npairs * longest < (1 << 31):
+                cuts.append(npairs)   # (one batch whatever the pairs: no need to sum their words)
+            words = None
+            while cuts[-1] < npairs:
+                if words is None:
+                    words = np.cumsum(((pset.length[i].astype(np.int64) + 15) >> 4) + ((tset.length[j].astype(np.int64) + 15) >> 4))
+                lo = cuts[-1]
+                before = int(words[lo - 1]) if lo else 0
+                hi = min(lo + budget, int(np.searchsorted(words, before + (1 << 31), side="right")))
+                cuts.append(max(hi, lo + 1))
+            score = np.zeros(npairs, np.int32)
+            status = np.zeros(npairs, np.int32)
+            small = full and npairs <= 1024 and len(cuts) <= 2
+            ops_res, runs = None, []
+            for lo, hi in zip(cuts[:-1], cuts[1:]):
+                rb = self._native.batch_indexed(pset, tset if texts is not None else None, i[lo:hi], j[lo:hi])
+                try:
+                    rb.run()
+                    rb.sync()
+                    sc, st, cig = rb.results(small)
+                    score[lo:hi] = sc
+                    status[lo:hi] = st
+                    if small:
+                        ops_res = cig
+                    elif full:
+                        runs.append(rb.rle()[:3])
+                finally:
+                    rb.close()
+        finally:
+            for s in mine:
+                s.close()
+        out = {"score": score, "status": status}
+        if small or (full and npairs == 0):
+            ops, cbeg, clen = ops_res if ops_res is not None else (np.zeros(1, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.int32))
+            out["cigar_ops"] = _OpsSequence(ops, cbeg, clen, "ops")
+            out["cigarstrings"] = _OpsSequence(ops, cbeg, clen, "str")
+        elif full:
+            # the op strings stayed on the GPU, their run-length encoding came back (as align_batch); chunks joined end to end
+            off = np.zeros(npairs + 1, np.int64)
+            base = 0
+            for (o, _c, _l), lo, hi in zip(runs, cuts[:-1], cuts[1:]):
+                off[lo + 1:hi + 1] = o[1:] + base
+                base += int(o[-1])
+            code = np.concatenate([r[1] for r in runs])
+            rlen = np.concatenate([r[2] for r in runs])
+            out["cigar_ops"] = _RunSequence(off, code, rlen, "ops")
+            out["cigarstrings"] = _RunSequence(off, code, rlen, "str")
+        return out
 
     def score_matrix(self, patterns, texts=None):
         """Score every pattern against every text on the GPU: returns ``(score, status)``, int32 arrays of shape (M, N).

@@ -86,6 +86,34 @@ struct CrossTopkArgs {
 
 #define WFA_CROSS_MAX_K 64
 
+// Indexed batches (wfa_hip_batch_create_indexed): pair q of a list is (patterns[i[q]], texts[j[q]]).  The layout is the explicit batch's
+// (wfa_hip.hip batch_build): the slots of the pairs of up to WFA_FAST_MAX_LEN bases stand back to back in list order, each as long as
+// its pair needs (pattern words, text words right behind); a longer pair points into the batch's copy of the sets' words.  The host
+// knows every slot's place from the sets' lengths; it sends one word offset per WFA_PAIRS_CHUNK pairs (chunk_base), and the chunk's
+// workgroup finds its pairs' slots with a prefix sum over their word counts.  Kernel in k_pairs.hip.
+#define WFA_PAIRS_CHUNK 256   // pairs per workgroup round (256 threads: one pair each for the metadata, then groups of lanes over words)
+
+struct PairsGenArgs {
+  const uint32_t* p_words; const uint32_t* p_woff; const int32_t* p_len; const int64_t* p_boff; const uint8_t* p_flag;   // the pattern set
+  const uint32_t* t_words; const uint32_t* t_woff; const int32_t* t_len; const int64_t* t_boff; const uint8_t* t_flag;   // the text set
+  const int32_t* i;         // [npairs] index into the pattern set
+  const int32_t* j;         // [npairs] index into the text set
+  const uint32_t* chunk_base;   // [chunks]: the first slot word of pair chunk * WFA_PAIRS_CHUNK in `words`
+  uint32_t* words;          // the batch's word table: (the sets' words when a listed pair is longer than a slot may be,) then the slots
+  uint32_t t_wshift;        // the text set's first word in the table (long pairs)
+  int64_t t_bshift;         // the text set's first byte in the batch's byte blob
+  int64_t npairs;
+  int log2g;                // lanes per pair of the copy: 1 << log2g (the longest slot's words rounded up to a power of two, at most 64)
+  int all_bytes;            // 1: every pair on its bytes (the wildcard is one of ACGT)
+  int lists;                // 1: the list holds byte pairs: write pboff / tboff / flags
+  WfaPairMeta* meta;
+  int64_t* pboff;
+  int64_t* tboff;
+  uint8_t* flags;
+};
+
+int launch_pairs_gen(const PairsGenArgs& a, int cu_count, hipStream_t stream);
+
 int launch_cross_topk(const CrossTopkArgs& a, hipStream_t stream);
 
 int launch_cross_gen(const CrossGenArgs& a, hipStream_t stream);

@@ -4068,3 +4068,198 @@ extern "C" int wfa_hip_cross_kernel_ms(wfa_hip_cross_t* x, float* ms, int64_t* p
   if (pairs) *pairs = x->pairs;
   return WFA_HIP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// indexed batches (include/wfa_hip.h: a list of (i, j) index pairs over resident sequence sets; csrc/wfa_cross.hpp, k_pairs.hip)
+// ------------------------------------------------------------------------------------------------
+// What batch_build does for an explicit batch, from the sets' host tables instead of the caller's arrays: one pass over the list checks
+// and sums (on threads for long lists; the parts start on chunk boundaries of the generator), a second writes what the host keeps (the
+// op-region prefix, the lengths, the work lists) and the generator's chunk bases.  The generator then writes the metadata and the slots
+// on the device.  The batch owns all it reads afterwards: the slots, and copies (device to device) of the sets' words when a listed pair
+// is too long for a slot, of their bytes when a listed pair is aligned on its bytes — so it outlives the sets.
+static int batch_build_indexed(wfa_hip_aligner* al, wfa_hip_batch* b, const wfa_hip_seqset* P, const wfa_hip_seqset* T, bool same,
+                               int64_t n, const int32_t* ii, const int32_t* jj) {
+  b->cfg = al->cfg; b->dcfg = al->dcfg; b->ncomp = al->ncomp; b->gcfg = al->gcfg; b->gncomp = al->gncomp;
+  const wfa_hip_config_t& c = b->cfg;
+  const bool all_bytes = c.wildcard >= 0 && wildcard_in_acgt(c.wildcard);
+  if (c.wildcard >= 0 && !all_bytes) { b->wild = c.wildcard; b->dcfg.wildcard = -1; b->gcfg.wildcard = -1; }   // (as batch_build)
+  b->al = al;
+  b->n = n;
+  const bool full = (c.scope == WFA_SCOPE_FULL);
+  const bool ef = (c.span == WFA_SPAN_ENDSFREE);
+  const int64_t np_set = P->n, nt_set = T->n;
+  const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, std::thread::hardware_concurrency()), n / 65536));
+  auto part_lo = [&](int t) -> int64_t { return t >= nthr ? n : (n * t / nthr) & ~(int64_t)(WFA_PAIRS_CHUNK - 1); };
+  struct Part { uint64_t words = 0; int64_t packed = 0, ops = 0, nbytes = 0, bad = -1; int max_width = 0, max_len = 0, max_slot = 0, err = 0; bool any_long = false; };
+  std::vector<Part> parts((size_t)nthr);
+  auto pass1 = [&](int t) {
+    Part& pt = parts[(size_t)t];
+    for (int64_t q = part_lo(t), hi = part_lo(t + 1); q < hi; ++q) {
+      const int64_t a = ii[q], bq = jj[q];
+      if (a < 0 || a >= np_set || bq < 0 || bq >= nt_set) { pt.err = 1; pt.bad = q; return; }
+      const int pl = P->h_len[(size_t)a], tl = T->h_len[(size_t)bq];
+      // wavefront_align.c:86-102, per listed pair as batch_build
+      if (ef && (c.pattern_begin_free > pl || c.pattern_end_free > pl || c.text_begin_free > tl || c.text_end_free > tl)) { pt.err = 3; pt.bad = q; return; }
+      if (pl <= WFA_FAST_MAX_LEN && tl <= WFA_FAST_MAX_LEN) {
+        const int nw = ((pl + 15) >> 4) + ((tl + 15) >> 4);
+        pt.words += (uint64_t)nw; pt.max_slot = std::max(pt.max_slot, nw);
+      } else pt.any_long = true;
+      pt.max_width = std::max(pt.max_width, pl + tl + 3);
+      pt.max_len = std::max(pt.max_len, std::max(pl, tl));
+      pt.packed += (int64_t)((pl + 3) >> 2) + ((tl + 3) >> 2);
+      pt.ops += (int64_t)pl + tl;
+      pt.nbytes += (all_bytes || P->h_flag[(size_t)a] || T->h_flag[(size_t)bq]) ? 1 : 0;
+    }
+  };
+  auto run_threads = [&](auto&& fn) {
+    std::vector<std::thread> th;
+    for (int t = 1; t < nthr; ++t) th.emplace_back(fn, t);
+    fn(0);
+    for (auto& x : th) x.join();
+  };
+  run_threads(pass1);
+  uint64_t slot_words = 0;
+  int64_t nbytes = 0;
+  int max_slot = 0;
+  bool any_long = false;
+  std::vector<uint64_t> wbase((size_t)nthr);
+  std::vector<int64_t> obase((size_t)nthr), bbase((size_t)nthr);
+  for (int t = 0; t < nthr; ++t) {
+    const Part& pt = parts[(size_t)t];
+    if (pt.err == 1) {
+      char buf[160];
+      snprintf(buf, sizeof(buf), "index out of range at position %lld of the pair list: (%d, %d) over sets of %lld and %lld sequences",
+               (long long)pt.bad, (int)ii[pt.bad], (int)jj[pt.bad], (long long)np_set, (long long)nt_set);
+      al->err = buf; return WFA_HIP_EINVAL;
+    }
+    if (pt.err == 3) { al->err = "Ends-free parameters must be not larger than the sequences"; return WFA_HIP_EINVAL; }
+    wbase[(size_t)t] = slot_words; obase[(size_t)t] = b->ops_bytes; bbase[(size_t)t] = nbytes;
+    slot_words += pt.words; nbytes += pt.nbytes;
+    max_slot = std::max(max_slot, pt.max_slot); any_long |= pt.any_long;
+    b->max_width = std::max(b->max_width, pt.max_width); b->max_len = std::max(b->max_len, pt.max_len);
+    b->packed_bytes += pt.packed; b->ops_bytes += pt.ops;
+  }
+  // the word table: the sets' words and 64 zero words (only when a listed pair points into them), the slots, 64 zero words
+  const uint32_t t_wshift = same ? 0u : (uint32_t)P->nwords;
+  const int64_t t_bshift = same ? 0 : P->nbytes;
+  const uint64_t table_words = any_long ? P->nwords + (same ? 0 : T->nwords) + 64 : 0;
+  if (table_words + slot_words + 64 > 0xFFFFFFF0ull) {
+    al->err = "indexed batch too large: more than 2^32 words of sets and slots (split the list)"; return WFA_HIP_EINVAL;
+  }
+  const bool lists = nbytes > 0;
+  const int64_t chunks = (n + WFA_PAIRS_CHUNK - 1) / WFA_PAIRS_CHUNK;
+  std::vector<uint32_t> chunk_base((size_t)std::max<int64_t>(chunks, 1), (uint32_t)table_words);
+  std::vector<uint32_t> lp(lists ? (size_t)(n - nbytes) : 0), lb(lists ? (size_t)nbytes : 0);
+  if (full) {   // needed later to lay out the op-string regions
+    b->h_plen.resize((size_t)n); b->h_tlen.resize((size_t)n);
+    b->h_coff.assign((size_t)n + 1, 0);
+  }
+  auto pass2 = [&](int t) {
+    uint64_t w = table_words + wbase[(size_t)t];
+    int64_t o = obase[(size_t)t], nb = bbase[(size_t)t];
+    const int64_t lo = part_lo(t), hi = part_lo(t + 1);
+    int64_t npk = lo - nb;   // 2-bit pairs before this part
+    for (int64_t q = lo; q < hi; ++q) {
+      const size_t a = (size_t)ii[q], bq = (size_t)jj[q];
+      const int pl = P->h_len[a], tl = T->h_len[bq];
+      if ((q & (WFA_PAIRS_CHUNK - 1)) == 0) chunk_base[(size_t)(q / WFA_PAIRS_CHUNK)] = (uint32_t)w;
+      if (pl <= WFA_FAST_MAX_LEN && tl <= WFA_FAST_MAX_LEN) w += (uint64_t)(((pl + 15) >> 4) + ((tl + 15) >> 4));
+      if (full) { b->h_plen[(size_t)q] = pl; b->h_tlen[(size_t)q] = tl; o += (int64_t)pl + tl; b->h_coff[(size_t)q + 1] = o; }
+      if (lists) {
+        if (all_bytes || P->h_flag[a] || T->h_flag[bq]) lb[(size_t)nb++] = (uint32_t)q;
+        else lp[(size_t)npk++] = (uint32_t)q;
+      }
+    }
+  };
+  run_threads(pass2);
+  int32_t *d_i = nullptr, *d_j = nullptr;
+  uint32_t* d_chunk = nullptr;
+  CrossScratch sc{al};   // (declared behind the host tables above: it waits for the stream before they go)
+  const size_t nn = (size_t)std::max<int64_t>(n, 1);
+  const uint64_t total_words = table_words + slot_words + 64;
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_meta, nn * sizeof(WfaPairMeta)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_words, (size_t)total_words * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_flags, nn));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_score, nn * sizeof(int32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_status, nn * sizeof(int32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_fb_list2[0], nn * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_fb_list2[1], nn * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_counters, WFA_COUNTER_WORDS * sizeof(uint32_t)));
+  HIP_TRY(al, hipMemsetAsync(b->d_counters, 0, WFA_COUNTER_WORDS * sizeof(uint32_t), al->stream));
+  HIP_TRY(al, hipMemsetAsync(b->d_flags, 0, nn, al->stream));
+  HIP_TRY(al, hipMemsetAsync(b->d_words + (total_words - 64), 0, 64 * sizeof(uint32_t), al->stream));
+  if (any_long) {
+    HIP_TRY(al, hipMemcpyAsync(b->d_words, P->d_words, (size_t)P->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
+    if (!same) HIP_TRY(al, hipMemcpyAsync(b->d_words + P->nwords, T->d_words, (size_t)T->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
+    HIP_TRY(al, hipMemsetAsync(b->d_words + (table_words - 64), 0, 64 * sizeof(uint32_t), al->stream));
+  }
+  if (full) {
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_ops, (size_t)std::max<int64_t>(b->ops_bytes, 1)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_cigar_off, ((size_t)n + 1) * sizeof(int64_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_cigar_begin, nn * sizeof(int64_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_cigar_len, nn * sizeof(int32_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_ovf_list[0], nn * sizeof(uint32_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_ovf_list[1], nn * sizeof(uint32_t)));
+    HIP_TRY(al, hipMemcpyAsync(b->d_cigar_off, b->h_coff.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
+  }
+  b->n_bytes = (uint32_t)nbytes;
+  b->n_packed = (uint32_t)(n - nbytes);
+  if (n > 0) {
+    if (lists) {   // (byte pairs: the sets' bytes, the text set's behind the pattern set's; the two work lists, ascending)
+      HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)(P->nbytes + (same ? 0 : T->nbytes) + 64)));
+      HIP_TRY(al, hipMemcpyAsync(b->d_bytes, P->d_bytes, (size_t)P->nbytes + (same ? 64 : 0), hipMemcpyDeviceToDevice, al->stream));
+      if (!same) HIP_TRY(al, hipMemcpyAsync(b->d_bytes + P->nbytes, T->d_bytes, (size_t)T->nbytes + 64, hipMemcpyDeviceToDevice, al->stream));
+      HIP_TRY(al, pool_alloc(al, (void**)&b->d_pboff, nn * sizeof(int64_t)));
+      HIP_TRY(al, pool_alloc(al, (void**)&b->d_tboff, nn * sizeof(int64_t)));
+      HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_bytes, lb.size() * sizeof(uint32_t)));
+      HIP_TRY(al, hipMemcpyAsync(b->d_list_bytes, lb.data(), lb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
+      if (!lp.empty()) {
+        HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_packed, lp.size() * sizeof(uint32_t)));
+        HIP_TRY(al, hipMemcpyAsync(b->d_list_packed, lp.data(), lp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
+      }
+    }
+    if (sc.alloc(&d_i, nn) || sc.alloc(&d_j, nn) || sc.alloc(&d_chunk, chunk_base.size())) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpyAsync(d_i, ii, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    HIP_TRY(al, hipMemcpyAsync(d_j, jj, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    HIP_TRY(al, hipMemcpyAsync(d_chunk, chunk_base.data(), chunk_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
+    wfa::PairsGenArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.p_words = P->d_words; ga.p_woff = P->d_woff; ga.p_len = P->d_len; ga.p_boff = P->d_boff; ga.p_flag = P->d_flag;
+    ga.t_words = T->d_words; ga.t_woff = T->d_woff; ga.t_len = T->d_len; ga.t_boff = T->d_boff; ga.t_flag = T->d_flag;
+    ga.i = d_i; ga.j = d_j; ga.chunk_base = d_chunk;
+    ga.words = b->d_words; ga.t_wshift = t_wshift; ga.t_bshift = t_bshift; ga.npairs = n;
+    ga.log2g = 2;   // lanes per pair: the words of the longest slot, rounded up to a power of two (at most a whole wave)
+    while (ga.log2g < 6 && (1 << ga.log2g) < max_slot) ++ga.log2g;
+    ga.all_bytes = all_bytes ? 1 : 0; ga.lists = lists ? 1 : 0;
+    ga.meta = b->d_meta; ga.pboff = b->d_pboff; ga.tboff = b->d_tboff; ga.flags = b->d_flags;
+    if (wfa::launch_pairs_gen(ga, al->cu_count, al->stream) != 0) { al->err = "indexed batch generator launch failed"; return WFA_HIP_EDEVICE; }
+  }
+  { const int prc = pilot_first_width(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
+  { const int prc = pilot_lane_heur(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
+  { const int prc = pilot_band(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
+  HIP_TRY(al, hipEventCreateWithFlags(&b->upload_event, hipEventDisableTiming));
+  HIP_TRY(al, hipEventRecord(b->upload_event, al->stream));
+  // the caller's index arrays, the host tables above and the sets are read by what is enqueued: over before this returns
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  return WFA_HIP_OK;
+}
+
+extern "C" wfa_hip_batch_t* wfa_hip_batch_create_indexed(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts,
+                                                         int64_t npairs, const int32_t* i, const int32_t* j) {
+  if (!al) { g_error = "null aligner"; return nullptr; }
+  const bool same = (texts == nullptr);
+  if (same) texts = patterns;
+  if (!patterns || patterns->al != al || texts->al != al) { al->err = "sequence set of another aligner"; g_error = al->err; return nullptr; }
+  if (patterns->wildcard != al->cfg.wildcard || texts->wildcard != al->cfg.wildcard) {
+    al->err = "sequence set packed under another wildcard: create it again"; g_error = al->err; return nullptr;
+  }
+  if (npairs < 0 || npairs > 0x7FFFFFF0ll || (npairs > 0 && (!i || !j))) { al->err = "invalid pair list arguments"; g_error = al->err; return nullptr; }
+  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);   // (the resident one-pair kernel: batches take the device)
+  wfa_hip_batch* b = new wfa_hip_batch();
+  b->al = al;
+  al->live_batches += 1;
+  const int rc = batch_build_indexed(al, b, patterns, texts, same, npairs, i, j);
+  if (rc != WFA_HIP_OK) { g_error = al->err; batch_free(b); return nullptr; }
+  return b;
+}
