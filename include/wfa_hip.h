@@ -362,7 +362,7 @@ typedef struct wfa_hip_cross  wfa_hip_cross_t;   /* the results of one cross run
 
 /* Upload n sequences (ASCII; sequence k = seqs[off[k] .. +len[k])) as the word table the kernels read, one word-aligned run per
  * sequence.  The set keeps the lengths on the host, a flag per sequence holding letters outside ACGT (such a sequence also keeps its
- * bytes, and its pairs are aligned on them, as in a batch), and the aligner's wildcard at this call: a cross run under another
+ * bytes, and its pairs are aligned on them, as in a batch; the host also keeps where those letters are, for windowed batches), and the aligner's wildcard at this call: a cross run under another
  * wildcard returns WFA_HIP_EINVAL.  The inputs are not read after the call returns.  Returns NULL on error (wfa_hip_last_error). */
 wfa_hip_seqset_t* wfa_hip_seqset_create(wfa_hip_aligner_t* aligner, int64_t n, const uint8_t* seqs, const int64_t* off, const int32_t* len);
 void wfa_hip_seqset_destroy(wfa_hip_seqset_t* set);
@@ -412,6 +412,39 @@ int64_t wfa_hip_plan_cross_bands(int64_t m, int64_t n, int triangle, int64_t max
  * needs of them on the device).  A set serves any number of indexed batches and cross runs, in any order. */
 wfa_hip_batch_t* wfa_hip_batch_create_indexed(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts,
                                               int64_t npairs, const int32_t* i, const int32_t* j);
+
+/* ---- windowed batches: windows of resident sequences, either strand, by index ------------------------------ */
+
+/* A resident batch whose pair q is a window of patterns[i[q]] against a window of texts[j[q]] (texts = NULL: both indices into
+ * `patterns`).  Pattern: bases [p_start[q], p_start[q] + p_len[q]) of patterns[i[q]], and where reverse[q] != 0 the reverse complement
+ * of that window; text: bases [t_start[q], t_start[q] + t_len[q]) of texts[j[q]], never reversed.  A NULL start array means 0 for every
+ * pair, a NULL length array "to the end of the sequence from the start", a NULL `reverse` every pair forward.  The complement on bytes
+ * is A<->T, C<->G, a<->t, c<->g and every other byte unchanged (N stays N, a wildcard byte stays itself).
+ * The result is an ordinary batch (run / sync / results / rle_counts / rle_runs / last_kernel_ms / algorithmic_bytes / fallback_pairs /
+ * destroy work on it unchanged): pair q's score, status and op string are exactly what wfa_hip_align_batch returns for the two
+ * materialised byte strings under the aligner's configuration at this call, scope included; op-string regions are p_len[q] + t_len[q]
+ * bytes in list order, coordinates are relative to the windows (the caller adds the starts).  Duplicates, overlapping windows, empty
+ * windows (length 0) and i == j are legal; npairs = 0 is a valid empty batch.  Up to 25 bytes per pair cross PCIe (8 with every
+ * optional array NULL): the slots are gathered on the device from the sets' words (csrc/wfa_cross.hpp, k_windows.hip).
+ * A pair is aligned on its bytes exactly when the wildcard is one of ACGT or one of its two WINDOWS holds a letter outside ACGT: the
+ * windows of a reference with a few N runs that avoid the Ns take the 2-bit kernels (wfa_hip_batch_last_kernel_ms reports the count).
+ * WFA_HIP_EINVAL (NULL, wfa_hip_last_error; nothing is launched): an index outside its set, a negative start or length, a window that
+ * ends behind its sequence (the message names the first offending list position and its values), a set of another aligner or packed
+ * under another wildcard, free ends larger than a LISTED WINDOW, more than 2^32 words of slots ("split the list").
+ * The arrays are not read after the call returns.  The batch owns the slots of the listed windows and nothing else (no copy of a set,
+ * whatever the sequences' lengths), and stays valid after either set is destroyed. */
+wfa_hip_batch_t* wfa_hip_batch_create_windows(wfa_hip_aligner_t* aligner,
+    const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int64_t npairs,
+    const int32_t* i, const int32_t* j,
+    const int32_t* p_start, const int32_t* p_len,     /* nullable */
+    const int32_t* t_start, const int32_t* t_len,     /* nullable */
+    const uint8_t* reverse);                          /* nullable */
+
+/* Host only, needs no GPU: the (len + 15) / 16 words of the window [start, start + len) of a sequence in wfa_hip_pack_2bit's layout,
+ * re-based to bit 0, reverse-complemented when reverse != 0 (a reversal of the 2-bit groups and code ^ 2), zero beyond `len` — what
+ * the device gather stores in a slot, and wfa_hip_pack_2bit of the materialised ACGT string.  Only the words that hold a base of the
+ * window are read.  Returns WFA_HIP_OK, or WFA_HIP_EINVAL on a negative start or length (or a NULL pointer with len > 0). */
+int wfa_hip_window_2bit(const uint32_t* words, int64_t start, int32_t len, int reverse, uint32_t* out);
 
 #ifdef __cplusplus
 }

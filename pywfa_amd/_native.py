@@ -13,7 +13,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WFA_HIP_LIB") or os.path.join(_HERE, "libwfa_hip.so")  # (WFA_HIP_LIB: development builds)
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 OK, EINVAL, ENOTSUP, EDEVICE = 0, -1, -2, -3
 
@@ -63,7 +63,7 @@ SYMBOLS = [
     "wfa_hip_batch_extent_packed2bits", "wfa_hip_align_pair", "wfa_hip_upload_info",
     "wfa_hip_seqset_create", "wfa_hip_seqset_destroy", "wfa_hip_cross_run", "wfa_hip_cross_dense", "wfa_hip_cross_completed",
     "wfa_hip_cross_kernel_ms", "wfa_hip_cross_destroy", "wfa_hip_plan_cross_bands", "wfa_hip_cross_run_k", "wfa_hip_cross_topk",
-    "wfa_hip_batch_create_indexed",
+    "wfa_hip_batch_create_indexed", "wfa_hip_batch_create_windows", "wfa_hip_window_2bit",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
@@ -150,6 +150,9 @@ def lib():
     L.wfa_hip_plan_cross_bands.restype = i64
     L.wfa_hip_batch_create_indexed.argtypes = [vp, vp, vp, i64, vp, vp]
     L.wfa_hip_batch_create_indexed.restype = vp
+    L.wfa_hip_batch_create_windows.argtypes = [vp, vp, vp, i64] + [vp] * 7
+    L.wfa_hip_batch_create_windows.restype = vp
+    L.wfa_hip_window_2bit.argtypes = [vp, i64, i32, ctypes.c_int, vp]
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -391,6 +394,11 @@ class Aligner:
         both indices into ``patterns``)."""
         return ResidentBatch.indexed(self, patterns, texts, i, j)
 
+    def batch_windows(self, patterns, texts, i, j, p_start=None, p_len=None, t_start=None, t_len=None, reverse=None):
+        """wfa_hip_batch_create_windows: the ResidentBatch whose pair q is the window [p_start[q], + p_len[q]) of patterns[i[q]]
+        (reverse-complemented where reverse[q]) against the window [t_start[q], + t_len[q]) of texts[j[q]]."""
+        return ResidentBatch.windows(self, patterns, texts, i, j, p_start, p_len, t_start, t_len, reverse)
+
     def cross(self, patterns, texts=None, want=CROSS_DENSE, k=None):
         """wfa_hip_cross_run of two SeqSets (texts None: all-vs-all of ``patterns``); wfa_hip_cross_run_k when ``k`` is given."""
         return CrossRun(self, patterns, texts, want, k)
@@ -404,6 +412,20 @@ def pack_2bit(seq, form=-1):
     if rc < 0:
         raise ValueError("wfa_hip_pack_2bit: invalid arguments")
     return words[:(len(a) + 15) // 16], bool(rc)
+
+
+def window_2bit(words, start, len, reverse=False):
+    """wfa_hip_window_2bit (host only): the words of the window [start, start + len) of a sequence packed by ``pack_2bit``, re-based
+    to bit 0 and reverse-complemented when ``reverse``."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    start, n = int(start), int(len)
+    if start >= 0 and n > 0 and start + n > 16 * words.shape[0]:
+        raise ValueError("wfa_hip_window_2bit: the window ends behind the words")
+    out = np.zeros(max((n + 15) // 16, 1), np.uint32)
+    rc = lib().wfa_hip_window_2bit(_ptr(words), start, n, int(bool(reverse)), _ptr(out))
+    if rc != OK:
+        raise ValueError("wfa_hip_window_2bit: negative start or length")
+    return out[:(n + 15) // 16]
 
 
 def plan_host_threads(sharers, hw_threads=None):
@@ -653,7 +675,54 @@ class ResidentBatch:
         aligner._batches.add(self)
         return self
 
+    @classmethod
+    def windows(cls, aligner, patterns, texts, i, j, p_start=None, p_len=None, t_start=None, t_len=None, reverse=None):
+        """wfa_hip_batch_create_windows over two SeqSets (texts None: both indices into ``patterns``).  ``i`` / ``j`` and the optional
+        start / length arrays: integers that fit 32 bits, one per pair; ``reverse``: 0 / 1 per pair.  None = the C entry's NULL.  A
+        list the library refuses raises NativeError carrying its message."""
+        given = {"i": i, "j": j, "p_start": p_start, "p_len": p_len, "t_start": t_start, "t_len": t_len}
+        arr = {}
+        for name, a in given.items():
+            if a is None:
+                if name in ("i", "j"):
+                    raise ValueError("index arrays are missing")
+                arr[name] = None
+                continue
+            a = np.asarray(a)
+            if a.size and (a.dtype.kind not in "iu" or
+                           (a.dtype != np.int32 and (int(a.min()) < -2**31 or int(a.max()) >= 2**31))):
+                raise ValueError(f"{name} must hold integers that fit 32 bits")
+            arr[name] = np.ascontiguousarray(a, dtype=np.int32)
+        if reverse is not None:
+            arr["reverse"] = np.ascontiguousarray(np.asarray(reverse) != 0, dtype=np.uint8)
+        else:
+            arr["reverse"] = None
+        n = arr["i"].shape[0]
+        for name, a in arr.items():
+            if a is not None and (a.ndim != 1 or a.shape[0] != n):
+                raise ValueError(f"window arrays differ in length ({name})")
+        tset = patterns if texts is None else texts
+        if not patterns._h or not tset._h:
+            raise ValueError("sequence set is closed")
+        self = cls.__new__(cls)
+        self.aligner = aligner
+        self.n = n
+        self._wins = (patterns.length, tset.length, arr)   # (the windows' lengths size the op buffers of results(True): on first use)
+        self._h = lib().wfa_hip_batch_create_windows(aligner._h, patterns._h, texts._h if texts is not None else None, n,
+                                                     *[_ptr(arr[k]) for k in ("i", "j", "p_start", "p_len", "t_start", "t_len", "reverse")])
+        if not self._h:
+            raise NativeError(f"wfa_hip_batch_create_windows: {aligner.error()}")
+        aligner._batches.add(self)
+        return self
+
     def __getattr__(self, name):
+        if name in ("_p_len", "_t_len") and "_wins" in self.__dict__:   # a windowed batch: the listed windows' lengths, on first use
+            pl, tl, a = self._wins
+            ps = a["p_start"] if a["p_start"] is not None else 0
+            ts = a["t_start"] if a["t_start"] is not None else 0
+            self._p_len = a["p_len"] if a["p_len"] is not None else (pl[a["i"]] - ps).astype(np.int32)
+            self._t_len = a["t_len"] if a["t_len"] is not None else (tl[a["j"]] - ts).astype(np.int32)
+            return self.__dict__[name]
         if name in ("_p_len", "_t_len") and "_lens" in self.__dict__:   # an indexed batch: the listed pairs' lengths, on first use
             pl, tl, i, j = self._lens
             self._p_len, self._t_len = pl[i], tl[j]

@@ -687,27 +687,33 @@ class WavefrontAligner:
                 before = int(words[lo - 1]) if lo else 0
                 hi = min(lo + budget, int(np.searchsorted(words, before + (1 << 31), side="right")))
                 cuts.append(max(hi, lo + 1))
-            score = np.zeros(npairs, np.int32)
-            status = np.zeros(npairs, np.int32)
-            small = full and npairs <= 1024 and len(cuts) <= 2
-            ops_res, runs = None, []
-            for lo, hi in zip(cuts[:-1], cuts[1:]):
-                rb = self._native.batch_indexed(pset, tset if texts is not None else None, i[lo:hi], j[lo:hi])
-                try:
-                    rb.run()
-                    rb.sync()
-                    sc, st, cig = rb.results(small)
-                    score[lo:hi] = sc
-                    status[lo:hi] = st
-                    if small:
-                        ops_res = cig
-                    elif full:
-                        runs.append(rb.rle()[:3])
-                finally:
-                    rb.close()
+            return self._run_lists(npairs, cuts, lambda lo, hi: self._native.batch_indexed(
+                pset, tset if texts is not None else None, i[lo:hi], j[lo:hi]))
         finally:
             for s in mine:
                 s.close()
+
+    def _run_lists(self, npairs, cuts, make):
+        """Run the resident batches ``make(lo, hi)`` of the consecutive chunks ``cuts`` of a pair list and join their results."""
+        full = self._cfg.scope == 1
+        score = np.zeros(npairs, np.int32)
+        status = np.zeros(npairs, np.int32)
+        small = full and npairs <= 1024 and len(cuts) <= 2
+        ops_res, runs = None, []
+        for lo, hi in zip(cuts[:-1], cuts[1:]):
+            rb = make(lo, hi)
+            try:
+                rb.run()
+                rb.sync()
+                sc, st, cig = rb.results(small)
+                score[lo:hi] = sc
+                status[lo:hi] = st
+                if small:
+                    ops_res = cig
+                elif full:
+                    runs.append(rb.rle()[:3])
+            finally:
+                rb.close()
         out = {"score": score, "status": status}
         if small or (full and npairs == 0):
             ops, cbeg, clen = ops_res if ops_res is not None else (np.zeros(1, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.int32))
@@ -725,6 +731,108 @@ class WavefrontAligner:
             out["cigar_ops"] = _RunSequence(off, code, rlen, "ops")
             out["cigarstrings"] = _RunSequence(off, code, rlen, "str")
         return out
+
+    # ------------------------------------------------------------------ windows of resident sequences (additive API)
+    @staticmethod
+    def _window_array(name, a, npairs, boolean=False):
+        """One optional per-pair array of ``align_windows``, checked, or ValueError naming the array and the position."""
+        if a is None:
+            return None
+        a = np.asarray(a)
+        if a.ndim != 1:
+            raise ValueError(f"{name} must be a one-dimensional array")
+        if a.size == 0:
+            a = a.astype(np.uint8 if boolean else np.int32)
+        if a.dtype.kind not in ("biu" if boolean else "iu"):
+            raise ValueError(f"{name} must hold {'booleans or 0 / 1' if boolean else 'integers'}, got dtype {a.dtype}")
+        if a.shape[0] != npairs:
+            raise ValueError(f"{name} and i differ in length: {a.shape[0]} and {npairs}")
+        if boolean:
+            if a.dtype.kind != "b" and a.size and ((a != 0) & (a != 1)).any():
+                q = int(np.flatnonzero((a != 0) & (a != 1))[0])
+                raise ValueError(f"{name}[{q}] = {int(a[q])} is neither 0 nor 1")
+            return np.ascontiguousarray(a != 0, dtype=np.uint8)
+        if a.size and int(a.min()) < 0:
+            q = int(np.flatnonzero(a < 0)[0])
+            raise ValueError(f"{name}[{q}] = {int(a[q])} is negative")
+        if a.size and int(a.max()) >= 2**31:
+            q = int(np.flatnonzero(a >= 2**31)[0])
+            raise ValueError(f"{name}[{q}] = {int(a[q])} does not fit 32 bits")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def align_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None,
+                      text_start=None, text_len=None, reverse=None):
+        """Align windows of resident sequences on the GPU: pair q is bases [pattern_start[q], + pattern_len[q]) of patterns[i[q]],
+        reverse-complemented where ``reverse[q]``, against bases [text_start[q], + text_len[q]) of texts[j[q]] (never reversed);
+        ``texts=None``: both indices into ``patterns``.  A start left out is 0 for every pair, a length left out runs to the end of
+        the sequence, ``reverse`` left out means forward.  The complement is A<->T, C<->G (either case), any other letter stays.
+        ``patterns`` / ``texts``: lists of ``str`` or ``SequenceSet`` handles, as for ``align_pairs``; the windows are cut, reversed
+        and complemented on the device, only the index and window arrays are uploaded.
+
+        Returns what ``wavefront_align_batch`` returns for the materialised strings under this aligner's configuration, in list
+        order, as ``align_pairs`` does: dict(score=, status=) and, with scope full, cigarstrings= / cigar_ops= (coordinates relative
+        to the windows: add the starts).  ValueError, before anything is uploaded, for arrays that are not one-dimensional integer
+        arrays of one length, negative values, a window that ends behind its sequence, or a ``reverse`` that is not boolean / 0-1."""
+        if not isinstance(patterns, (SequenceSet, list)):
+            patterns = list(patterns)
+        if texts is not None and not isinstance(texts, (SequenceSet, list)):
+            texts = list(texts)
+        m = len(patterns)
+        n = m if texts is None else len(texts)
+        i, j = self._check_pair_indices(i, j, m, n)
+        npairs = i.shape[0]
+        ps = self._window_array("pattern_start", pattern_start, npairs)
+        pl = self._window_array("pattern_len", pattern_len, npairs)
+        ts = self._window_array("text_start", text_start, npairs)
+        tl = self._window_array("text_len", text_len, npairs)
+        rev = self._window_array("reverse", reverse, npairs, boolean=True)
+
+        def lengths(x):
+            if isinstance(x, SequenceSet):
+                if x._aligner is not self:
+                    raise ValueError("sequence set of another aligner")
+                if x._set is None or not x._set._h:
+                    raise ValueError("sequence set is closed")
+                return x._set.length
+            return np.fromiter((len(s) for s in x), np.int32, len(x))
+
+        plen_seq = lengths(patterns)
+        tlen_seq = plen_seq if texts is None else lengths(texts)
+        wlen = []
+        for what, seq_len, idx, start, length in (("pattern", plen_seq, i, ps, pl), ("text", tlen_seq, j, ts, tl)):
+            have = seq_len[idx].astype(np.int64) if npairs else np.zeros(0, np.int64)
+            s0 = start.astype(np.int64) if start is not None else 0
+            ln = length.astype(np.int64) if length is not None else have - s0
+            over = np.flatnonzero((s0 + ln > have) | (ln < 0))
+            if len(over):
+                q = int(over[0])
+                raise ValueError(f"{what}_start[{q}] + {what}_len[{q}] = {int(s0[q]) if start is not None else 0} + "
+                                 f"{int(ln[q]) if length is not None else 'the rest'} runs past the end of {what} sequence "
+                                 f"{int(idx[q])} ({int(have[q])} bases)")
+            wlen.append(ln)
+        self._sync_wildcard()
+        sets, mine = self._open_sets(patterns, texts)
+        try:
+            pset, tset = sets[0], sets[-1]
+            # chunks as align_pairs cuts them, by the words of the WINDOWS
+            budget = max(1, int(os.environ.get("WFA_HIP_PAIRS_BAND", "0") or 0) or (1 << 24))
+            words = np.cumsum(((wlen[0] + 15) >> 4) + ((wlen[1] + 15) >> 4)) if npairs else np.zeros(0, np.int64)
+            cuts = [0]
+            while cuts[-1] < npairs:
+                lo = cuts[-1]
+                before = int(words[lo - 1]) if lo else 0
+                hi = min(lo + budget, int(np.searchsorted(words, before + (1 << 31), side="right")))
+                cuts.append(max(hi, lo + 1))
+
+            def cut(a, lo, hi):
+                return None if a is None else a[lo:hi]
+
+            return self._run_lists(npairs, cuts, lambda lo, hi: self._native.batch_windows(
+                pset, tset if texts is not None else None, i[lo:hi], j[lo:hi], cut(ps, lo, hi), cut(pl, lo, hi),
+                cut(ts, lo, hi), cut(tl, lo, hi), cut(rev, lo, hi)))
+        finally:
+            for s in mine:
+                s.close()
 
     def score_matrix(self, patterns, texts=None):
         """Score every pattern against every text on the GPU: returns ``(score, status)``, int32 arrays of shape (M, N).

@@ -114,6 +114,69 @@ struct PairsGenArgs {
 
 int launch_pairs_gen(const PairsGenArgs& a, int cu_count, hipStream_t stream);
 
+// Windowed batches (wfa_hip_batch_create_windows): pair q of a list is a window of patterns[i[q]], on either strand, against a window
+// of texts[j[q]].  A window starts at any base, so nothing of a set can be used in place: EVERY pair gets a word slot, whatever its
+// length (the explicit batch's layout: pattern words, text words right behind, slots back to back in list order), re-based to bit 0 of
+// its first word, and a pair aligned on its bytes also gets a byte slot holding the two materialised windows (each rounded up to whole
+// 32-bit words, zero behind the window).  The batch owns the slots and nothing else of the sets.  The host sends one word offset and
+// one byte offset per WFA_PAIRS_CHUNK pairs; the chunk's workgroup places its pairs' slots with two prefix sums.  Kernel in
+// k_windows.hip; wfa_window_word below is the gather of one slot word, shared with the host statement of it (wfa_hip_window_2bit).
+#define WFA_WIN_REVERSE 1   // opt[q]: the pattern window is reverse-complemented
+#define WFA_WIN_BYTES 2     // opt[q]: a window of the pair holds a letter outside ACGT (the host looked it up in the sets' runs)
+
+struct WindowsGenArgs {
+  const uint32_t* p_words; const uint32_t* p_woff; const int32_t* p_len; const int64_t* p_boff; const uint8_t* p_bytes;   // the pattern set
+  const uint32_t* t_words; const uint32_t* t_woff; const int32_t* t_len; const int64_t* t_boff; const uint8_t* t_bytes;   // the text set
+  const int32_t* i;         // [npairs] index into the pattern set
+  const int32_t* j;         // [npairs] index into the text set
+  const int32_t* p_start;   // [npairs] or nullptr: 0
+  const int32_t* p_wlen;    // [npairs] or nullptr: to the end of the sequence
+  const int32_t* t_start;
+  const int32_t* t_wlen;
+  const uint8_t* opt;       // [npairs] WFA_WIN_* or nullptr: forward, no byte pairs but under all_bytes
+  const uint32_t* chunk_base;    // [chunks]: the first slot word of pair chunk * WFA_PAIRS_CHUNK in `words`
+  const int64_t* chunk_bbase;    // [chunks]: its first slot byte in `bytes` (lists only)
+  uint32_t* words;          // the batch's word table: the slots
+  uint8_t* bytes;           // the batch's byte blob: the byte slots
+  int64_t npairs;
+  int log2g;                // lanes per pair of the gather: 1 << log2g
+  int all_bytes;            // 1: every pair on its bytes (the wildcard is one of ACGT)
+  int lists;                // 1: the list holds byte pairs: write pboff / tboff / flags and the byte slots
+  WfaPairMeta* meta;
+  int64_t* pboff;
+  int64_t* tboff;
+  uint8_t* flags;
+};
+
+int launch_windows_gen(const WindowsGenArgs& a, int cu_count, hipStream_t stream);
+
+// Word w of a window of `len` bases from base `start` of a packed sequence, re-based to bit 0, zero beyond `len`.  `lo` / `hi` are the
+// source words wfa_window_src(...) and the one after it (0 where the sequence has none).  Forward: the funnel shift of the two by the
+// start's residue.  Reverse: the same funnel shift ending at base start + len - 1 - 16 w, then the 2-bit groups reversed (a bit
+// reversal and a swap of each group's two bits) and complemented (code ^ 2).
+__host__ __device__ inline int64_t wfa_window_first(int64_t start, int32_t len, uint32_t w, bool rev) {   // first source base of word w (may be < start)
+  return rev ? start + len - 16 - 16 * (int64_t)w : start + 16 * (int64_t)w;
+}
+__host__ __device__ inline uint32_t wfa_window_word(uint32_t lo, uint32_t hi, int64_t first, int32_t len, uint32_t w, bool rev) {
+  const uint32_t sh = 2u * (uint32_t)(first & 15);
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t v = __builtin_amdgcn_alignbit(hi, lo, sh);
+  if (rev) v = __builtin_bitreverse32(v);
+#else
+  uint32_t v = sh ? (lo >> sh) | (hi << (32u - sh)) : lo;
+  if (rev) {
+    v = ((v >> 16) | (v << 16));
+    v = ((v >> 8) & 0x00FF00FFu) | ((v & 0x00FF00FFu) << 8);
+    v = ((v >> 4) & 0x0F0F0F0Fu) | ((v & 0x0F0F0F0Fu) << 4);
+    v = ((v >> 2) & 0x33333333u) | ((v & 0x33333333u) << 2);
+    v = ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
+  }
+#endif
+  if (rev) v = (((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1)) ^ 0xAAAAAAAAu;
+  const int32_t cnt = len - 16 * (int32_t)w;
+  return cnt >= 16 ? v : v & ((1u << (2 * cnt)) - 1u);
+}
+
 int launch_cross_topk(const CrossTopkArgs& a, hipStream_t stream);
 
 int launch_cross_gen(const CrossGenArgs& a, hipStream_t stream);

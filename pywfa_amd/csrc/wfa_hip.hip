@@ -41,7 +41,7 @@
 #include "wfa_rle.hpp"
 #include "wfa_cross.hpp"
 
-#define WFA_HIP_ABI_VERSION 3
+#define WFA_HIP_ABI_VERSION 4
 
 static thread_local std::string g_error;
 
@@ -1989,7 +1989,7 @@ static int batch_run_once(wfa_hip_batch_t* b, void* stream_) {
         if (rc != WFA_HIP_OK) return rc;
       }
     }
-    b->last_kernel_pairs = b->n;
+    b->last_kernel_pairs = b->n_packed > 0 ? b->n_packed : b->n_bytes;   // (the first launch's pairs, as the cascade below reports them)
     HIP_TRY(al, hipEventRecord(ev1, stream));
     HIP_TRY(al, hipEventRecord(al->ws_event, stream));
     al->ws_event_recorded = true; al->ws_last_stream = stream;
@@ -3614,6 +3614,7 @@ struct wfa_hip_seqset {
   int wildcard = -1;               // the aligner's wildcard when the set was packed
   std::vector<int32_t> h_len;
   std::vector<uint8_t> h_flag;     // 1: a letter outside ACGT (its pairs are aligned on their bytes)
+  std::vector<std::vector<int32_t>> h_runs;   // flagged sequences only: the runs of such letters as (start, end) pairs, ascending (windowed batches)
   uint64_t nwords = 0;             // words of the table, without the 4 zero words behind it
   int64_t nbytes = 0;              // bytes of the ASCII blob
   uint32_t* d_words = nullptr;     // one word-aligned run per sequence (wfa_hip_pack_2bit's layout)
@@ -3654,10 +3655,23 @@ extern "C" void wfa_hip_seqset_destroy(wfa_hip_seqset_t* s) {
   aligner_release_ref(al);
 }
 
+// the runs of letters host_pack_seq flags (anything but upper-case ACGT) in one sequence
+static void flagged_runs(const uint8_t* seq, int32_t len, std::vector<int32_t>& runs) {
+  for (int32_t p = 0; p < len;) {
+    const uint8_t ch = seq[p];
+    if (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T') { ++p; continue; }
+    int32_t e = p + 1;
+    while (e < len && !(seq[e] == 'A' || seq[e] == 'C' || seq[e] == 'G' || seq[e] == 'T')) ++e;
+    runs.push_back(p); runs.push_back(e);
+    p = e;
+  }
+}
+
 static int seqset_build(wfa_hip_aligner* al, wfa_hip_seqset* s, int64_t n, const uint8_t* seqs, const int64_t* off, const int32_t* len) {
   s->n = n;
   s->h_len.assign(len, len + n);
   s->h_flag.assign((size_t)n, 0);
+  s->h_runs.assign((size_t)n, std::vector<int32_t>());
   std::vector<uint32_t> woff((size_t)n);
   std::vector<int64_t> boff((size_t)n);
   uint64_t w = 0;
@@ -3677,6 +3691,7 @@ static int seqset_build(wfa_hip_aligner* al, wfa_hip_seqset* s, int64_t n, const
   auto work = [&](int t) {
     for (int64_t k = n * t / nthr, hi = n * (t + 1) / nthr; k < hi; ++k) {
       s->h_flag[(size_t)k] = wfa::host_pack_seq(seqs + off[k], len[k], words.data() + woff[(size_t)k], -1) ? 1 : 0;
+      if (s->h_flag[(size_t)k]) flagged_runs(seqs + off[k], len[k], s->h_runs[(size_t)k]);
       if (len[k] > 0) memcpy(bytes.data() + boff[(size_t)k], seqs + off[k], (size_t)len[k]);
     }
   };
@@ -4260,6 +4275,262 @@ extern "C" wfa_hip_batch_t* wfa_hip_batch_create_indexed(wfa_hip_aligner_t* al, 
   b->al = al;
   al->live_batches += 1;
   const int rc = batch_build_indexed(al, b, patterns, texts, same, npairs, i, j);
+  if (rc != WFA_HIP_OK) { g_error = al->err; batch_free(b); return nullptr; }
+  return b;
+}
+
+// ------------------------------------------------------------------------------------------------
+// windowed batches (include/wfa_hip.h: windows of resident sequences, either strand, by index; csrc/wfa_cross.hpp, k_windows.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int wfa_hip_window_2bit(const uint32_t* words, int64_t start, int32_t len, int reverse, uint32_t* out) {
+  if (start < 0 || len < 0 || (len > 0 && (!words || !out))) return WFA_HIP_EINVAL;
+  if (len == 0) return WFA_HIP_OK;
+  const int64_t w_lo = start >> 4, w_hi = (start + len - 1) >> 4;   // the source words that hold a base of the window: nothing else is read
+  const uint32_t n = (uint32_t)(len + 15) >> 4;
+  for (uint32_t w = 0; w < n; ++w) {
+    const int64_t first = wfa::wfa_window_first(start, len, w, reverse != 0), si = first >> 4;
+    const uint32_t lo = (si >= w_lo && si <= w_hi) ? words[si] : 0u, hi = (si + 1 >= w_lo && si + 1 <= w_hi) ? words[si + 1] : 0u;
+    out[w] = wfa::wfa_window_word(lo, hi, first, len, w, reverse != 0);
+  }
+  return WFA_HIP_OK;
+}
+
+// does [start, start + len) of sequence k of the set touch a run of flagged letters?
+static inline bool window_flagged(const wfa_hip_seqset* S, size_t k, int32_t start, int32_t len) {
+  if (!S->h_flag[k] || len <= 0) return false;
+  const std::vector<int32_t>& r = S->h_runs[k];
+  size_t lo = 0, hi = r.size() / 2;   // the first run that ends behind `start`
+  while (lo < hi) { const size_t mid = (lo + hi) / 2; if (r[2 * mid + 1] > start) hi = mid; else lo = mid + 1; }
+  return lo < r.size() / 2 && r[2 * lo] < start + len;
+}
+
+struct WindowList {
+  const int32_t *i, *j, *p_start, *p_len, *t_start, *t_len;
+  const uint8_t* reverse;
+};
+
+// batch_build_indexed for windows: the same two host passes over the list (the first checks and sums, the second writes what the host
+// keeps and the generator's chunk bases), but every pair has a word slot, a byte pair a byte slot, and whether a pair is a byte pair
+// is looked up per window in the sets' runs of flagged letters.  One byte of options per pair (strand, byte pair) goes to the device
+// when the list has a reversed or a byte pair; the batch owns its slots and nothing of the sets.
+static int batch_build_windows(wfa_hip_aligner* al, wfa_hip_batch* b, const wfa_hip_seqset* P, const wfa_hip_seqset* T, int64_t n, const WindowList& L) {
+  b->cfg = al->cfg; b->dcfg = al->dcfg; b->ncomp = al->ncomp; b->gcfg = al->gcfg; b->gncomp = al->gncomp;
+  const wfa_hip_config_t& c = b->cfg;
+  const bool all_bytes = c.wildcard >= 0 && wildcard_in_acgt(c.wildcard);
+  if (c.wildcard >= 0 && !all_bytes) { b->wild = c.wildcard; b->dcfg.wildcard = -1; b->gcfg.wildcard = -1; }   // (as batch_build)
+  b->al = al;
+  b->n = n;
+  const bool full = (c.scope == WFA_SCOPE_FULL);
+  const bool ef = (c.span == WFA_SPAN_ENDSFREE);
+  const int64_t np_set = P->n, nt_set = T->n;
+  const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, std::thread::hardware_concurrency()), n / 65536));
+  auto part_lo = [&](int t) -> int64_t { return t >= nthr ? n : (n * t / nthr) & ~(int64_t)(WFA_PAIRS_CHUNK - 1); };
+  struct Part { uint64_t words = 0; int64_t packed = 0, ops = 0, nbytes = 0, slot_bytes = 0, bad = -1; int max_width = 0, max_len = 0, max_seq = 0, err = 0; bool any_opt = false; };
+  std::vector<Part> parts((size_t)nthr);
+  std::vector<uint8_t> opt((size_t)n, 0);
+  struct Win { int64_t ps, pl, ts, tl; };
+  auto window = [&](int64_t q, int64_t pseq, int64_t tseq) -> Win {
+    Win w;
+    w.ps = L.p_start ? L.p_start[q] : 0; w.ts = L.t_start ? L.t_start[q] : 0;
+    w.pl = L.p_len ? L.p_len[q] : pseq - w.ps; w.tl = L.t_len ? L.t_len[q] : tseq - w.ts;
+    return w;
+  };
+  auto pass1 = [&](int t) {
+    Part& pt = parts[(size_t)t];
+    for (int64_t q = part_lo(t), hi = part_lo(t + 1); q < hi; ++q) {
+      const int64_t a = L.i[q], bq = L.j[q];
+      if (a < 0 || a >= np_set || bq < 0 || bq >= nt_set) { pt.err = 1; pt.bad = q; return; }
+      const int64_t pseq = P->h_len[(size_t)a], tseq = T->h_len[(size_t)bq];
+      const Win w = window(q, pseq, tseq);
+      if (w.ps < 0 || w.ts < 0 || (L.p_len && w.pl < 0) || (L.t_len && w.tl < 0)) { pt.err = 2; pt.bad = q; return; }
+      if (w.ps + w.pl > pseq || w.ts + w.tl > tseq || w.pl < 0 || w.tl < 0) { pt.err = 4; pt.bad = q; return; }
+      const int pl = (int)w.pl, tl = (int)w.tl;
+      // wavefront_align.c:86-102, per listed pair as batch_build: against the WINDOWS
+      if (ef && (c.pattern_begin_free > pl || c.pattern_end_free > pl || c.text_begin_free > tl || c.text_end_free > tl)) { pt.err = 3; pt.bad = q; return; }
+      pt.words += (uint64_t)(((pl + 15) >> 4) + ((tl + 15) >> 4));
+      pt.max_seq = std::max(pt.max_seq, std::max((pl + 15) >> 4, (tl + 15) >> 4));
+      pt.max_width = std::max(pt.max_width, pl + tl + 3);
+      pt.max_len = std::max(pt.max_len, std::max(pl, tl));
+      pt.packed += (int64_t)((pl + 3) >> 2) + ((tl + 3) >> 2);
+      pt.ops += (int64_t)pl + tl;
+      const bool rev = L.reverse && L.reverse[q] != 0;
+      const bool byt = all_bytes || window_flagged(P, (size_t)a, (int32_t)w.ps, pl) || window_flagged(T, (size_t)bq, (int32_t)w.ts, tl);
+      if (byt) { pt.nbytes += 1; pt.slot_bytes += (((int64_t)pl + 3) & ~(int64_t)3) + (((int64_t)tl + 3) & ~(int64_t)3); }
+      opt[(size_t)q] = (uint8_t)((rev ? WFA_WIN_REVERSE : 0) | (byt ? WFA_WIN_BYTES : 0));
+      pt.any_opt |= rev || byt;
+    }
+  };
+  auto run_threads = [&](auto&& fn) {
+    std::vector<std::thread> th;
+    for (int t = 1; t < nthr; ++t) th.emplace_back(fn, t);
+    fn(0);
+    for (auto& x : th) x.join();
+  };
+  run_threads(pass1);
+  uint64_t slot_words = 0;
+  int64_t nbytes = 0, slot_bytes = 0;
+  int max_seq = 0;
+  bool any_opt = false;
+  std::vector<uint64_t> wbase((size_t)nthr);
+  std::vector<int64_t> obase((size_t)nthr), bbase((size_t)nthr), sbase((size_t)nthr);
+  for (int t = 0; t < nthr; ++t) {
+    const Part& pt = parts[(size_t)t];
+    if (pt.err == 1) {
+      char buf[200];
+      snprintf(buf, sizeof(buf), "index out of range at position %lld of the pair list: (%d, %d) over sets of %lld and %lld sequences",
+               (long long)pt.bad, (int)L.i[pt.bad], (int)L.j[pt.bad], (long long)np_set, (long long)nt_set);
+      al->err = buf; return WFA_HIP_EINVAL;
+    }
+    if (pt.err == 2 || pt.err == 4) {
+      const int64_t q = pt.bad;
+      const int64_t pseq = P->h_len[(size_t)L.i[q]], tseq = T->h_len[(size_t)L.j[q]];
+      const Win w = window(q, pseq, tseq);
+      char buf[320];
+      snprintf(buf, sizeof(buf), "%s at position %lld of the pair list: pattern window [%lld, %lld + %lld) of sequence %d (%lld bases), "
+               "text window [%lld, %lld + %lld) of sequence %d (%lld bases)", pt.err == 2 ? "negative start or length" : "window out of range",
+               (long long)q, (long long)w.ps, (long long)w.ps, (long long)w.pl, (int)L.i[q], (long long)pseq,
+               (long long)w.ts, (long long)w.ts, (long long)w.tl, (int)L.j[q], (long long)tseq);
+      al->err = buf; return WFA_HIP_EINVAL;
+    }
+    if (pt.err == 3) { al->err = "Ends-free parameters must be not larger than the sequences"; return WFA_HIP_EINVAL; }
+    wbase[(size_t)t] = slot_words; obase[(size_t)t] = b->ops_bytes; bbase[(size_t)t] = nbytes; sbase[(size_t)t] = slot_bytes;
+    slot_words += pt.words; nbytes += pt.nbytes; slot_bytes += pt.slot_bytes;
+    max_seq = std::max(max_seq, pt.max_seq); any_opt |= pt.any_opt;
+    b->max_width = std::max(b->max_width, pt.max_width); b->max_len = std::max(b->max_len, pt.max_len);
+    b->packed_bytes += pt.packed; b->ops_bytes += pt.ops;
+  }
+  if (slot_words + 64 > 0xFFFFFFF0ull) {
+    al->err = "windowed batch too large: more than 2^32 words of slots (split the list)"; return WFA_HIP_EINVAL;
+  }
+  const bool lists = nbytes > 0;
+  const int64_t chunks = (n + WFA_PAIRS_CHUNK - 1) / WFA_PAIRS_CHUNK;
+  std::vector<uint32_t> chunk_base((size_t)std::max<int64_t>(chunks, 1), 0u);
+  std::vector<int64_t> chunk_bbase(lists ? (size_t)std::max<int64_t>(chunks, 1) : 0, 0);
+  std::vector<uint32_t> lp(lists ? (size_t)(n - nbytes) : 0), lb(lists ? (size_t)nbytes : 0);
+  if (full) {   // needed later to lay out the op-string regions
+    b->h_plen.resize((size_t)n); b->h_tlen.resize((size_t)n);
+    b->h_coff.assign((size_t)n + 1, 0);
+  }
+  auto pass2 = [&](int t) {
+    uint64_t w = wbase[(size_t)t];
+    int64_t o = obase[(size_t)t], nb = bbase[(size_t)t], sb = sbase[(size_t)t];
+    const int64_t lo = part_lo(t), hi = part_lo(t + 1);
+    int64_t npk = lo - nb;   // 2-bit pairs before this part
+    for (int64_t q = lo; q < hi; ++q) {
+      const Win wn = window(q, P->h_len[(size_t)L.i[q]], T->h_len[(size_t)L.j[q]]);
+      const int pl = (int)wn.pl, tl = (int)wn.tl;
+      if ((q & (WFA_PAIRS_CHUNK - 1)) == 0) {
+        chunk_base[(size_t)(q / WFA_PAIRS_CHUNK)] = (uint32_t)w;
+        if (lists) chunk_bbase[(size_t)(q / WFA_PAIRS_CHUNK)] = sb;
+      }
+      w += (uint64_t)(((pl + 15) >> 4) + ((tl + 15) >> 4));
+      if (full) { b->h_plen[(size_t)q] = pl; b->h_tlen[(size_t)q] = tl; o += (int64_t)pl + tl; b->h_coff[(size_t)q + 1] = o; }
+      if (lists) {
+        if (opt[(size_t)q] & WFA_WIN_BYTES) {
+          lb[(size_t)nb++] = (uint32_t)q;
+          sb += (((int64_t)pl + 3) & ~(int64_t)3) + (((int64_t)tl + 3) & ~(int64_t)3);
+        } else lp[(size_t)npk++] = (uint32_t)q;
+      }
+    }
+  };
+  run_threads(pass2);
+  int32_t* d_arr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  uint8_t* d_opt = nullptr;
+  uint32_t* d_chunk = nullptr;
+  int64_t* d_bchunk = nullptr;
+  CrossScratch sc{al};   // (declared behind the host tables above: it waits for the stream before they go)
+  const size_t nn = (size_t)std::max<int64_t>(n, 1);
+  const uint64_t total_words = slot_words + 64;
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_meta, nn * sizeof(WfaPairMeta)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_words, (size_t)total_words * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_flags, nn));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_score, nn * sizeof(int32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_status, nn * sizeof(int32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_fb_list2[0], nn * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_fb_list2[1], nn * sizeof(uint32_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_counters, WFA_COUNTER_WORDS * sizeof(uint32_t)));
+  HIP_TRY(al, hipMemsetAsync(b->d_counters, 0, WFA_COUNTER_WORDS * sizeof(uint32_t), al->stream));
+  HIP_TRY(al, hipMemsetAsync(b->d_flags, 0, nn, al->stream));
+  HIP_TRY(al, hipMemsetAsync(b->d_words + (total_words - 64), 0, 64 * sizeof(uint32_t), al->stream));
+  if (full) {
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_ops, (size_t)std::max<int64_t>(b->ops_bytes, 1)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_cigar_off, ((size_t)n + 1) * sizeof(int64_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_cigar_begin, nn * sizeof(int64_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_cigar_len, nn * sizeof(int32_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_ovf_list[0], nn * sizeof(uint32_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_ovf_list[1], nn * sizeof(uint32_t)));
+    HIP_TRY(al, hipMemcpyAsync(b->d_cigar_off, b->h_coff.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
+  }
+  b->n_bytes = (uint32_t)nbytes;
+  b->n_packed = (uint32_t)(n - nbytes);
+  if (n > 0) {
+    if (lists) {   // (byte pairs: their byte slots and 64 zero bytes; the two work lists, ascending)
+      HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)slot_bytes + 64));
+      HIP_TRY(al, hipMemsetAsync(b->d_bytes + slot_bytes, 0, 64, al->stream));
+      HIP_TRY(al, pool_alloc(al, (void**)&b->d_pboff, nn * sizeof(int64_t)));
+      HIP_TRY(al, pool_alloc(al, (void**)&b->d_tboff, nn * sizeof(int64_t)));
+      HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_bytes, lb.size() * sizeof(uint32_t)));
+      HIP_TRY(al, hipMemcpyAsync(b->d_list_bytes, lb.data(), lb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
+      if (!lp.empty()) {
+        HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_packed, lp.size() * sizeof(uint32_t)));
+        HIP_TRY(al, hipMemcpyAsync(b->d_list_packed, lp.data(), lp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
+      }
+      if (sc.alloc(&d_bchunk, chunk_bbase.size())) return WFA_HIP_EDEVICE;
+      HIP_TRY(al, hipMemcpyAsync(d_bchunk, chunk_bbase.data(), chunk_bbase.size() * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
+    }
+    const int32_t* h_arr[6] = {L.i, L.j, L.p_start, L.p_len, L.t_start, L.t_len};
+    for (int k = 0; k < 6; ++k) {
+      if (!h_arr[k]) continue;
+      if (sc.alloc(&d_arr[k], nn)) return WFA_HIP_EDEVICE;
+      HIP_TRY(al, hipMemcpyAsync(d_arr[k], h_arr[k], (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    }
+    if (any_opt) {
+      if (sc.alloc(&d_opt, nn)) return WFA_HIP_EDEVICE;
+      HIP_TRY(al, hipMemcpyAsync(d_opt, opt.data(), (size_t)n, hipMemcpyHostToDevice, al->stream));
+    }
+    if (sc.alloc(&d_chunk, chunk_base.size())) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpyAsync(d_chunk, chunk_base.data(), chunk_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
+    wfa::WindowsGenArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.p_words = P->d_words; ga.p_woff = P->d_woff; ga.p_len = P->d_len; ga.p_boff = P->d_boff; ga.p_bytes = P->d_bytes;
+    ga.t_words = T->d_words; ga.t_woff = T->d_woff; ga.t_len = T->d_len; ga.t_boff = T->d_boff; ga.t_bytes = T->d_bytes;
+    ga.i = d_arr[0]; ga.j = d_arr[1]; ga.p_start = d_arr[2]; ga.p_wlen = d_arr[3]; ga.t_start = d_arr[4]; ga.t_wlen = d_arr[5];
+    ga.opt = d_opt; ga.chunk_base = d_chunk; ga.chunk_bbase = d_bchunk;
+    ga.words = b->d_words; ga.bytes = b->d_bytes; ga.npairs = n;
+    ga.log2g = 2;   // lanes per pair: the words of the longest window, rounded up to a power of two (at most a whole wave)
+    while (ga.log2g < 6 && (1 << ga.log2g) < max_seq) ++ga.log2g;
+    ga.all_bytes = all_bytes ? 1 : 0; ga.lists = lists ? 1 : 0;
+    ga.meta = b->d_meta; ga.pboff = b->d_pboff; ga.tboff = b->d_tboff; ga.flags = b->d_flags;
+    if (wfa::launch_windows_gen(ga, al->cu_count, al->stream) != 0) { al->err = "windowed batch generator launch failed"; return WFA_HIP_EDEVICE; }
+  }
+  { const int prc = pilot_first_width(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
+  { const int prc = pilot_lane_heur(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
+  { const int prc = pilot_band(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
+  HIP_TRY(al, hipEventCreateWithFlags(&b->upload_event, hipEventDisableTiming));
+  HIP_TRY(al, hipEventRecord(b->upload_event, al->stream));
+  // the caller's arrays, the host tables above and the sets are read by what is enqueued: over before this returns
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  return WFA_HIP_OK;
+}
+
+extern "C" wfa_hip_batch_t* wfa_hip_batch_create_windows(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts,
+                                                         int64_t npairs, const int32_t* i, const int32_t* j,
+                                                         const int32_t* p_start, const int32_t* p_len, const int32_t* t_start, const int32_t* t_len,
+                                                         const uint8_t* reverse) {
+  if (!al) { g_error = "null aligner"; return nullptr; }
+  if (!texts) texts = patterns;
+  if (!patterns || patterns->al != al || texts->al != al) { al->err = "sequence set of another aligner"; g_error = al->err; return nullptr; }
+  if (patterns->wildcard != al->cfg.wildcard || texts->wildcard != al->cfg.wildcard) {
+    al->err = "sequence set packed under another wildcard: create it again"; g_error = al->err; return nullptr;
+  }
+  if (npairs < 0 || npairs > 0x7FFFFFF0ll || (npairs > 0 && (!i || !j))) { al->err = "invalid pair list arguments"; g_error = al->err; return nullptr; }
+  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);   // (the resident one-pair kernel: batches take the device)
+  wfa_hip_batch* b = new wfa_hip_batch();
+  b->al = al;
+  al->live_batches += 1;
+  const WindowList L{i, j, p_start, p_len, t_start, t_len, reverse};
+  const int rc = batch_build_windows(al, b, patterns, texts, npairs, L);
   if (rc != WFA_HIP_OK) { g_error = al->err; batch_free(b); return nullptr; }
   return b;
 }
