@@ -446,6 +446,76 @@ wfa_hip_batch_t* wfa_hip_batch_create_windows(wfa_hip_aligner_t* aligner,
  * window are read.  Returns WFA_HIP_OK, or WFA_HIP_EINVAL on a negative start or length (or a NULL pointer with len > 0). */
 int wfa_hip_window_2bit(const uint32_t* words, int64_t start, int32_t len, int reverse, uint32_t* out);
 
+/* ---- reductions of the op strings on the device: per pair, and per text position --------------------------- */
+
+/* Op letters are the library's: M and X consume one pattern base and one text base, D a pattern base only, I a text base only.  The
+ * ALIGNED CORE of an op string is the span from its first M to its last M, inclusive (the ops outside it are the ends `locations`
+ * strips, align.pyx:797-831 with a threshold of 1); an op string without an M has an empty core. */
+
+/* Per-pair summary of the last scope=full run, for any resident batch (plain, packed2bits, indexed, windows): `summary` receives n
+ * rows of WFA_HIP_SUMMARY_COLS int32, row-major.  Over the whole op string [cigar_begin, + cigar_len) of the pair:
+ *   0..3  the numbers of M, X, I and D ops
+ *   4, 5  the numbers of maximal runs of I, and of D
+ *   6..9  pattern_start, pattern_end, text_start, text_end: exactly what wfa_hip_batch_rle_counts writes to `locations` for the pair
+ *         (all zero for an empty pair or an empty op string)
+ * A pair with an empty op string (heuristically dropped, step limit) has zeros in columns 0..5 too.  Waits for the last run like
+ * wfa_hip_batch_rle_counts; one kernel (csrc/wfa_summary.hpp) and one download of 40 bytes per pair: no op string and no run-length
+ * encoding crosses PCIe.  n = 0 is fine.  WFA_HIP_EINVAL: a batch of scope score or without a run ("... needs scope=full" / "... needs
+ * a finished run"), a NULL `summary` with n > 0. */
+#define WFA_HIP_SUMMARY_COLS 10
+int wfa_hip_batch_summary(wfa_hip_batch_t* batch, int32_t* summary);
+
+/* Host only, needs no GPU: the row wfa_hip_batch_summary writes for ONE pair, from its op string ops[0 .. ops_len) and its lengths.
+ * Returns WFA_HIP_OK, or WFA_HIP_EINVAL on a negative length or a missing pointer. */
+int wfa_hip_ops_summary(const uint8_t* ops, int64_t ops_len, int32_t plen, int32_t tlen, int32_t* out10);
+
+/*
+ * Pileup over a text set: the pairs of full-scope batches taken as READS (the pattern) aligned against windows of REFERENCES (the
+ * texts of a resident set), counted per text base.  Per base WFA_HIP_PILEUP_COLS int32 counters:
+ *   0..4  reads whose aligned base here is A, C, G, T, or anything else (N, a wildcard byte, lower case)
+ *   5     reads that delete this base (op I: a text base the read lacks)
+ *   6     reads that insert bases in front of this base (op D: read bases the text lacks; one count per maximal D run)
+ *   7     reads that mismatch here (op X; also counted in 0..4 under the read's letter)
+ * so the sum of columns 0..5 is the number of contributing reads whose aligned core covers the base.
+ *
+ * wfa_hip_pileup_create allocates the zeroed table for every base of `texts` in HBM: 32 BYTES PER TEXT BASE (a failed allocation:
+ * NULL, WFA_HIP_EDEVICE, the message names the byte count).  COUNTERS ARE int32 AND NOT CHECKED FOR OVERFLOW.  The pileup copies the
+ * set's lengths and prefix offsets: it stays valid after the set is destroyed.  A set of another aligner is refused (NULL).
+ *
+ * wfa_hip_pileup_add waits for the batch's last run, then adds its pairs: pair q is taken to be a read aligned against the text bases
+ * [t_start[q], t_start[q] + tlen[q]) of texts[j[q]], tlen[q] being the batch's own text length of the pair (the caller guarantees that
+ * the batch's text really was that window; the arrays given to wfa_hip_batch_create_windows are exactly this).  t_start NULL: 0 for
+ * every pair.  Pair q contributes iff its status is 0 and (keep == NULL or keep[q] != 0).  Its op string is walked with a pattern
+ * position v and a text position h, both from 0; only the ops of the aligned core add, to row g = t_start[q] + h:
+ *   M  +1 to the column of pattern letter v                          then v, h advance
+ *   X  +1 to the column of pattern letter v, +1 to column 7          then v, h advance
+ *   I  +1 to column 5                                                then h advances
+ *   D  +1 to column 6, once per maximal D run (at the g where the run starts: the text base behind the inserted read bases);  v advances
+ * The pattern letter is the batch's: of a reverse-strand window the reverse complement, i.e. on the text's strand.  Any number of adds
+ * accumulate into one table; integer adds make the result independent of their order and of how a list is split.  One kernel
+ * (csrc/wfa_pileup.hpp, k_pileup.hip: a wave per pair, int32 atomics), 9 bytes per pair uploaded, nothing downloaded.
+ * WFA_HIP_EINVAL, nothing launched (wfa_hip_last_error names the first offending list position and its values): a batch of another
+ * aligner, of scope score or without a finished run; j[q] outside the set; a negative t_start[q]; t_start[q] + tlen[q] behind the end
+ * of texts[j[q]].
+ *
+ * wfa_hip_pileup_read copies the rows [start, start + len) of sequence `seq` into counts (len x WFA_HIP_PILEUP_COLS, row-major);
+ * WFA_HIP_EINVAL when the range leaves the sequence.  wfa_hip_pileup_clear zeroes the table.
+ */
+#define WFA_HIP_PILEUP_COLS 8   /* A, C, G, T, other, deleted, insertion-before, mismatch */
+typedef struct wfa_hip_pileup wfa_hip_pileup_t;
+wfa_hip_pileup_t* wfa_hip_pileup_create(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* texts);
+int  wfa_hip_pileup_add(wfa_hip_pileup_t* pileup, wfa_hip_batch_t* batch,
+                        const int32_t* j, const int32_t* t_start /* nullable: 0 */, const uint8_t* keep /* nullable: all */);
+int  wfa_hip_pileup_read(wfa_hip_pileup_t* pileup, int32_t seq, int64_t start, int64_t len, int32_t* counts /* len x 8 */);
+int  wfa_hip_pileup_clear(wfa_hip_pileup_t* pileup);
+void wfa_hip_pileup_destroy(wfa_hip_pileup_t* pileup);
+
+/* Host only, needs no GPU: ONE pair's contribution by the rule above, from its op string and its ASCII pattern bytes, added to the
+ * window-relative rows rows[0 .. tlen) (tlen x WFA_HIP_PILEUP_COLS, row-major; not cleared).  Returns WFA_HIP_OK, or WFA_HIP_EINVAL on
+ * a negative length, a missing pointer, or an op string that consumes more than plen pattern or tlen text bases (nothing is added). */
+int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen,
+                       int32_t* rows /* tlen x 8, added to */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,10 +64,15 @@ SYMBOLS = [
     "wfa_hip_seqset_create", "wfa_hip_seqset_destroy", "wfa_hip_cross_run", "wfa_hip_cross_dense", "wfa_hip_cross_completed",
     "wfa_hip_cross_kernel_ms", "wfa_hip_cross_destroy", "wfa_hip_plan_cross_bands", "wfa_hip_cross_run_k", "wfa_hip_cross_topk",
     "wfa_hip_batch_create_indexed", "wfa_hip_batch_create_windows", "wfa_hip_window_2bit",
+    "wfa_hip_batch_summary", "wfa_hip_ops_summary", "wfa_hip_pileup_create", "wfa_hip_pileup_add", "wfa_hip_pileup_read",
+    "wfa_hip_pileup_clear", "wfa_hip_pileup_destroy", "wfa_hip_ops_pileup",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
 CROSS_MAX_K = 64
+SUMMARY_COLS = 10   # M, X, I, D, I runs, D runs, pattern_start, pattern_end, text_start, text_end
+PILEUP_COLS = 8
+PILEUP_COLUMNS = ("A", "C", "G", "T", "other", "del", "ins", "mismatch")
 
 
 def lib():
@@ -153,6 +158,16 @@ def lib():
     L.wfa_hip_batch_create_windows.argtypes = [vp, vp, vp, i64] + [vp] * 7
     L.wfa_hip_batch_create_windows.restype = vp
     L.wfa_hip_window_2bit.argtypes = [vp, i64, i32, ctypes.c_int, vp]
+    L.wfa_hip_batch_summary.argtypes = [vp, vp]
+    L.wfa_hip_ops_summary.argtypes = [vp, i64, i32, i32, vp]
+    L.wfa_hip_pileup_create.argtypes = [vp, vp]
+    L.wfa_hip_pileup_create.restype = vp
+    L.wfa_hip_pileup_add.argtypes = [vp, vp, vp, vp, vp]
+    L.wfa_hip_pileup_read.argtypes = [vp, i32, i64, i64, vp]
+    L.wfa_hip_pileup_clear.argtypes = [vp]
+    L.wfa_hip_pileup_destroy.argtypes = [vp]
+    L.wfa_hip_pileup_destroy.restype = None
+    L.wfa_hip_ops_pileup.argtypes = [vp, i64, vp, i32, i32, vp]
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -399,6 +414,10 @@ class Aligner:
         (reverse-complemented where reverse[q]) against the window [t_start[q], + t_len[q]) of texts[j[q]]."""
         return ResidentBatch.windows(self, patterns, texts, i, j, p_start, p_len, t_start, t_len, reverse)
 
+    def pileup(self, texts):
+        """wfa_hip_pileup_create: a zeroed Pileup over the bases of a SeqSet."""
+        return Pileup(self, texts)
+
     def cross(self, patterns, texts=None, want=CROSS_DENSE, k=None):
         """wfa_hip_cross_run of two SeqSets (texts None: all-vs-all of ``patterns``); wfa_hip_cross_run_k when ``k`` is given."""
         return CrossRun(self, patterns, texts, want, k)
@@ -426,6 +445,34 @@ def window_2bit(words, start, len, reverse=False):
     if rc != OK:
         raise ValueError("wfa_hip_window_2bit: negative start or length")
     return out[:(n + 15) // 16]
+
+
+def ops_summary(ops, plen, tlen):
+    """wfa_hip_ops_summary (host only): the row ``ResidentBatch.summary()`` holds for one pair, from its op string (bytes or a uint8
+    array of M / X / I / D) and its lengths: int32[10]."""
+    ops = np.frombuffer(bytes(ops), dtype=np.uint8) if not isinstance(ops, np.ndarray) else np.ascontiguousarray(ops, dtype=np.uint8)
+    out = np.zeros(SUMMARY_COLS, np.int32)
+    rc = lib().wfa_hip_ops_summary(_ptr(ops) if ops.size else None, ops.size, int(plen), int(tlen), _ptr(out))
+    if rc != OK:
+        raise ValueError("wfa_hip_ops_summary: invalid arguments")
+    return out
+
+
+def ops_pileup(ops, pattern, tlen, rows=None):
+    """wfa_hip_ops_pileup (host only): one pair's contribution to a pileup, from its op string and its ASCII pattern, added to the
+    window-relative ``rows`` (int32, shape (tlen, 8); a fresh zeroed array when None), which is returned."""
+    ops = np.frombuffer(bytes(ops), dtype=np.uint8) if not isinstance(ops, np.ndarray) else np.ascontiguousarray(ops, dtype=np.uint8)
+    pattern = np.frombuffer(bytes(pattern), dtype=np.uint8) if not isinstance(pattern, np.ndarray) else np.ascontiguousarray(pattern, dtype=np.uint8)
+    tlen = int(tlen)
+    if rows is None:
+        rows = np.zeros((max(tlen, 0), PILEUP_COLS), np.int32)
+    if not (isinstance(rows, np.ndarray) and rows.dtype == np.int32 and rows.shape == (tlen, PILEUP_COLS) and rows.flags.c_contiguous):
+        raise ValueError("rows: a contiguous int32 array of shape (tlen, 8)")
+    rc = lib().wfa_hip_ops_pileup(_ptr(ops) if ops.size else None, ops.size, _ptr(pattern) if pattern.size else None, pattern.size, tlen,
+                                  _ptr(rows) if rows.size else None)
+    if rc != OK:
+        raise ValueError("wfa_hip_ops_pileup: invalid arguments (an op string that outruns its pair?)")
+    return rows
 
 
 def plan_host_threads(sharers, hw_threads=None):
@@ -563,6 +610,67 @@ class CrossRun:
         if rc != OK:
             self.aligner._raise(rc, "wfa_hip_cross_kernel_ms")
         return ms.value, pairs.value
+
+
+class Pileup:
+    """Per-base counters over a text SeqSet, resident in HBM (wfa_hip_pileup_t): 32 bytes per text base, int32 counters without an
+    overflow check.  Stays valid after the set is closed."""
+
+    def __init__(self, aligner, texts):
+        if not texts._h:
+            raise ValueError("sequence set is closed")
+        self.aligner = aligner
+        self.n = texts.n
+        self.length = texts.length
+        self._h = lib().wfa_hip_pileup_create(aligner._h, texts._h)
+        if not self._h:
+            msg = aligner.error()
+            if "failed" in msg:
+                raise NativeError(f"wfa_hip_pileup_create: {msg}")
+            raise ValueError(f"wfa_hip_pileup_create: {msg}")
+        aligner._batches.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().wfa_hip_pileup_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, batch, j, t_start=None, keep=None):
+        """wfa_hip_pileup_add: the pairs of a ResidentBatch after its full-scope run, pair q against texts[j[q]] from t_start[q]."""
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        t_start = None if t_start is None else np.ascontiguousarray(t_start, dtype=np.int32)
+        keep = None if keep is None else np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        for name, a in (("j", j), ("t_start", t_start), ("keep", keep)):
+            if a is not None and a.shape != (batch.n,):
+                raise ValueError(f"{name}: one value per pair of the batch ({batch.n})")
+        rc = lib().wfa_hip_pileup_add(self._h, batch._h, _ptr(j), _ptr(t_start), _ptr(keep))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_pileup_add")
+
+    def read(self, seq, start=0, length=None):
+        """wfa_hip_pileup_read: int32[length, 8], the rows [start, start + length) of one sequence (to its end when None)."""
+        seq, start = int(seq), int(start)
+        if length is None:
+            if not 0 <= seq < self.n:
+                raise ValueError(f"sequence {seq} is out of range for a set of {self.n}")
+            length = int(self.length[seq]) - start
+        length = int(length)
+        out = np.zeros((max(length, 0), PILEUP_COLS), np.int32)
+        rc = lib().wfa_hip_pileup_read(self._h, seq, start, length, _ptr(out) if out.size else None)
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_pileup_read")
+        return out
+
+    def clear(self):
+        rc = lib().wfa_hip_pileup_clear(self._h)
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_pileup_clear")
 
 
 class MultiAligner:
@@ -794,6 +902,15 @@ class ResidentBatch:
         off = np.zeros(n + 1, np.int64)
         np.cumsum(cnt, out=off[1:])
         return off, code[:total], rlen[:total], locs
+
+    def summary(self):
+        """wfa_hip_batch_summary: int32[n, 10] of the last scope=full run, reduced on the GPU — per pair the numbers of M, X, I and D
+        ops, of I runs and of D runs, and the four ``locations``."""
+        out = np.zeros((self.n, SUMMARY_COLS), np.int32)
+        rc = lib().wfa_hip_batch_summary(self._h, _ptr(out) if self.n else None)
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_batch_summary")
+        return out
 
     def algorithmic_bytes(self):
         return int(lib().wfa_hip_batch_algorithmic_bytes(self._h))

@@ -28,7 +28,7 @@ from . import datagen
 _NO_OPS = np.zeros(0, np.uint8)   # (the op string of a call without a backtrace: one read-only array for every such call)
 _NO_OPS.flags.writeable = False
 
-__all__ = ["WavefrontAligner", "AlignmentResult", "BatchResults", "clip_cigartuples", "cigartuples_to_str",
+__all__ = ["WavefrontAligner", "AlignmentResult", "BatchResults", "Pileup", "clip_cigartuples", "cigartuples_to_str",
            "elide_mismatches_from_cigar"]
 
 # CIGAR tuple codes (align.pyx:11-14, README.rst:61-86): M I D N S H P = X B
@@ -325,6 +325,69 @@ class BatchResults:
                                int(self.status[i]))
 
 
+def _summary_dict(rows):
+    """The (n, 10) rows of ``ResidentBatch.summary()`` as the dict the ``summary=True`` forms return."""
+    out = {name: np.ascontiguousarray(rows[:, k]) for k, name in enumerate(("M", "X", "I", "D", "I_runs", "D_runs"))}
+    out["locations"] = np.ascontiguousarray(rows[:, 6:10])
+    return out
+
+
+def _need_full_for_summary(cfg):
+    if cfg.scope != 1:
+        raise ValueError("summary=True needs scope='full'")
+
+
+class Pileup:
+    """Per-base counts over the text sequences, kept on the GPU (``WavefrontAligner.pileup``).  ``score`` / ``status``: the listed
+    pairs' results, in list order.  ``counts(j)``: int32 rows of the columns ``COLUMNS`` for text ``j`` — reads whose aligned base is
+    A, C, G, T or another letter, reads that delete the base, reads that insert in front of it, reads that mismatch (these are also
+    under their letter).  ``depth(j)``: the reads whose aligned core covers each base.  Counters are int32 and not checked for
+    overflow; the table takes 32 bytes per text base until ``close()`` (or the end of the ``with`` block)."""
+
+    COLUMNS = _native.PILEUP_COLUMNS
+
+    def __init__(self, native_pileup, score, status):
+        self._pileup = native_pileup
+        self.score = score
+        self.status = status
+
+    def _open(self):
+        if self._pileup is None or not self._pileup._h:
+            raise ValueError("pileup is closed")
+        return self._pileup
+
+    def __len__(self):
+        return self._open().n
+
+    def counts(self, j, start=0, stop=None):
+        """int32 array of shape (stop - start, 8): the rows [start, stop) of text ``j`` (to its end when ``stop`` is None)."""
+        p = self._open()
+        if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= int(j) < p.n:
+            raise ValueError(f"j = {j!r} is out of range for {p.n} text sequences")
+        have = int(p.length[int(j)])
+        start = int(start)
+        stop = have if stop is None else int(stop)
+        if not 0 <= start <= stop <= have:
+            raise ValueError(f"rows [{start}, {stop}) are out of range for text sequence {int(j)} ({have} bases)")
+        return p.read(int(j), start, stop - start)
+
+    def depth(self, j, start=0, stop=None):
+        """The sum of the columns A, C, G, T, other and del: the contributing reads whose aligned core covers each base."""
+        return self.counts(j, start, stop)[:, :6].sum(axis=1, dtype=np.int32)
+
+    def close(self):
+        if self._pileup is not None:
+            self._pileup.close()
+            self._pileup = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class SequenceSet:
     """Sequences kept on the GPU, uploaded and packed once (``WavefrontAligner.sequence_set``): pass it wherever ``score_matrix``,
     ``completed_pairs``, ``nearest`` and ``align_pairs`` take a list of sequences.  ``len()`` is the number of sequences; ``close()``
@@ -493,11 +556,13 @@ class WavefrontAligner:
         return res
 
     # ------------------------------------------------------------------ batches (additive API)
-    def wavefront_align_batch(self, texts, patterns=None):
+    def wavefront_align_batch(self, texts, patterns=None, *, summary=False):
         """Align many pairs on the GPU. ``patterns`` None = the cached pattern for every text.
 
         Returns dict(score=int32[n], status=int32[n], cigarstrings=sequence of str, cigar_ops=sequence of uint8 arrays
-        (scope full; built from the GPU's run-length encoding when an item is read))."""
+        (scope full; built from the GPU's run-length encoding when an item is read)).  ``summary=True``: see ``align_batch``."""
+        if summary:
+            _need_full_for_summary(self._cfg)
         texts = texts if type(texts) is list else list(texts)
         if patterns is None:
             if self._bpattern is None:
@@ -514,10 +579,27 @@ class WavefrontAligner:
         batch = host.from_strings(patterns, texts, self._host_scratch) if host is not None else None
         if batch is None:
             batch = datagen.from_strings(patterns, texts, upper=True)
-        return self.align_batch(batch)
+        return self.align_batch(batch, summary=True) if summary else self.align_batch(batch)
 
-    def align_batch(self, batch):
-        """Align a prepared batch dict (see ``pywfa_amd.datagen``): ASCII blob + offsets + lengths."""
+    def align_batch(self, batch, *, summary=False):
+        """Align a prepared batch dict (see ``pywfa_amd.datagen``): ASCII blob + offsets + lengths.
+
+        ``summary=True`` (scope full only, else ValueError): no op string leaves the GPU; returns dict(score=, status=, summary=),
+        ``summary`` a dict of int32 arrays ``M``, ``X``, ``I``, ``D`` (ops of each kind per pair), ``I_runs``, ``D_runs`` (maximal
+        runs) and ``locations`` of shape (n, 4) (pattern_start, pattern_end, text_start, text_end), reduced on the device
+        (csrc/wfa_summary.hpp).  Always one resident batch on this aligner's device."""
+        if summary:
+            _need_full_for_summary(self._cfg)
+            self._sync_wildcard()
+            rb = self._native.batch(batch)
+            try:
+                rb.run()
+                rb.sync()
+                score, status, _ = rb.results(False)
+                rows = rb.summary()
+            finally:
+                rb.close()
+            return {"score": score, "status": status, "summary": _summary_dict(rows)}
         self._sync_wildcard()
         full = self._cfg.scope == 1
         if full and self._multi is None and len(batch["p_len"]) <= 1024:
@@ -650,7 +732,7 @@ class WavefrontAligner:
             raise ValueError(f"i and j differ in length: {out[0].shape[0]} and {out[1].shape[0]}")
         return out
 
-    def align_pairs(self, patterns, texts=None, *, i=None, j=None):
+    def align_pairs(self, patterns, texts=None, *, i=None, j=None, summary=False):
         """Align the listed pairs (patterns[i[q]], texts[j[q]]) on the GPU, each sequence uploaded once however many pairs name it;
         ``texts=None``: both indices into ``patterns``.  ``patterns`` / ``texts``: lists of ``str`` (uploaded and released inside
         the call) or ``SequenceSet`` handles of ``sequence_set`` (left open).  ``i`` / ``j``: integer arrays of equal length, every
@@ -658,7 +740,10 @@ class WavefrontAligner:
         filtered out first).  Duplicates, ``i == j`` and empty sequences are fine.
 
         Returns what ``wavefront_align_batch`` returns for those pairs under this aligner's configuration, in list order:
-        dict(score=, status=) and, with scope full, cigarstrings= / cigar_ops=.  With ``devices=[...]`` the first device runs it."""
+        dict(score=, status=) and, with scope full, cigarstrings= / cigar_ops=.  With ``devices=[...]`` the first device runs it.
+        ``summary=True`` (scope full only): dict(score=, status=, summary=) as ``align_batch`` describes, no op strings."""
+        if summary:
+            _need_full_for_summary(self._cfg)
         if not isinstance(patterns, (SequenceSet, list)):
             patterns = list(patterns)
         if texts is not None and not isinstance(texts, (SequenceSet, list)):
@@ -688,16 +773,38 @@ class WavefrontAligner:
                 hi = min(lo + budget, int(np.searchsorted(words, before + (1 << 31), side="right")))
                 cuts.append(max(hi, lo + 1))
             return self._run_lists(npairs, cuts, lambda lo, hi: self._native.batch_indexed(
-                pset, tset if texts is not None else None, i[lo:hi], j[lo:hi]))
+                pset, tset if texts is not None else None, i[lo:hi], j[lo:hi]), summary=summary)
         finally:
             for s in mine:
                 s.close()
 
-    def _run_lists(self, npairs, cuts, make):
-        """Run the resident batches ``make(lo, hi)`` of the consecutive chunks ``cuts`` of a pair list and join their results."""
+    def _run_lists(self, npairs, cuts, make, summary=False, each=None):
+        """Run the resident batches ``make(lo, hi)`` of the consecutive chunks ``cuts`` of a pair list and join their results.
+        ``summary``: the per-pair summary rows instead of op strings.  ``each(rb, lo, hi, score, status)``: called on every chunk's
+        batch after its run instead of fetching op strings (``pileup``)."""
         full = self._cfg.scope == 1
         score = np.zeros(npairs, np.int32)
         status = np.zeros(npairs, np.int32)
+        if summary or each is not None:
+            rows = np.zeros((npairs, _native.SUMMARY_COLS), np.int32) if summary else None
+            for lo, hi in zip(cuts[:-1], cuts[1:]):
+                rb = make(lo, hi)
+                try:
+                    rb.run()
+                    rb.sync()
+                    sc, st, _ = rb.results(False)
+                    score[lo:hi] = sc
+                    status[lo:hi] = st
+                    if summary:
+                        rows[lo:hi] = rb.summary()
+                    else:
+                        each(rb, lo, hi, sc, st)
+                finally:
+                    rb.close()
+            out = {"score": score, "status": status}
+            if summary:
+                out["summary"] = _summary_dict(rows)
+            return out
         small = full and npairs <= 1024 and len(cuts) <= 2
         ops_res, runs = None, []
         for lo, hi in zip(cuts[:-1], cuts[1:]):
@@ -760,19 +867,9 @@ class WavefrontAligner:
             raise ValueError(f"{name}[{q}] = {int(a[q])} does not fit 32 bits")
         return np.ascontiguousarray(a, dtype=np.int32)
 
-    def align_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None,
-                      text_start=None, text_len=None, reverse=None):
-        """Align windows of resident sequences on the GPU: pair q is bases [pattern_start[q], + pattern_len[q]) of patterns[i[q]],
-        reverse-complemented where ``reverse[q]``, against bases [text_start[q], + text_len[q]) of texts[j[q]] (never reversed);
-        ``texts=None``: both indices into ``patterns``.  A start left out is 0 for every pair, a length left out runs to the end of
-        the sequence, ``reverse`` left out means forward.  The complement is A<->T, C<->G (either case), any other letter stays.
-        ``patterns`` / ``texts``: lists of ``str`` or ``SequenceSet`` handles, as for ``align_pairs``; the windows are cut, reversed
-        and complemented on the device, only the index and window arrays are uploaded.
-
-        Returns what ``wavefront_align_batch`` returns for the materialised strings under this aligner's configuration, in list
-        order, as ``align_pairs`` does: dict(score=, status=) and, with scope full, cigarstrings= / cigar_ops= (coordinates relative
-        to the windows: add the starts).  ValueError, before anything is uploaded, for arrays that are not one-dimensional integer
-        arrays of one length, negative values, a window that ends behind its sequence, or a ``reverse`` that is not boolean / 0-1."""
+    def _window_lists(self, patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse):
+        """The arguments of ``align_windows`` / ``pileup`` checked (ValueError before anything is uploaded): the sequences (lists or
+        handles), the int32 index arrays, the optional window arrays, and the windows' lengths (int64) of patterns and texts."""
         if not isinstance(patterns, (SequenceSet, list)):
             patterns = list(patterns)
         if texts is not None and not isinstance(texts, (SequenceSet, list)):
@@ -810,27 +907,87 @@ class WavefrontAligner:
                                  f"{int(ln[q]) if length is not None else 'the rest'} runs past the end of {what} sequence "
                                  f"{int(idx[q])} ({int(have[q])} bases)")
             wlen.append(ln)
+        return patterns, texts, (i, j, ps, pl, ts, tl, rev), wlen
+
+    def _run_windows(self, pset, tset, arrays, wlen, **how):
+        """The windowed batches of a checked list over two native sets (``tset`` None: one set), in chunks as ``align_pairs`` cuts
+        them, by the words of the WINDOWS; ``how`` goes to ``_run_lists``."""
+        i, j, ps, pl, ts, tl, rev = arrays
+        npairs = i.shape[0]
+        budget = max(1, int(os.environ.get("WFA_HIP_PAIRS_BAND", "0") or 0) or (1 << 24))
+        words = np.cumsum(((wlen[0] + 15) >> 4) + ((wlen[1] + 15) >> 4)) if npairs else np.zeros(0, np.int64)
+        cuts = [0]
+        while cuts[-1] < npairs:
+            lo = cuts[-1]
+            before = int(words[lo - 1]) if lo else 0
+            hi = min(lo + budget, int(np.searchsorted(words, before + (1 << 31), side="right")))
+            cuts.append(max(hi, lo + 1))
+
+        def cut(a, lo, hi):
+            return None if a is None else a[lo:hi]
+
+        return self._run_lists(npairs, cuts, lambda lo, hi: self._native.batch_windows(
+            pset, tset, i[lo:hi], j[lo:hi], cut(ps, lo, hi), cut(pl, lo, hi),
+            cut(ts, lo, hi), cut(tl, lo, hi), cut(rev, lo, hi)), **how)
+
+    def align_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None,
+                      text_start=None, text_len=None, reverse=None, summary=False):
+        """Align windows of resident sequences on the GPU: pair q is bases [pattern_start[q], + pattern_len[q]) of patterns[i[q]],
+        reverse-complemented where ``reverse[q]``, against bases [text_start[q], + text_len[q]) of texts[j[q]] (never reversed);
+        ``texts=None``: both indices into ``patterns``.  A start left out is 0 for every pair, a length left out runs to the end of
+        the sequence, ``reverse`` left out means forward.  The complement is A<->T, C<->G (either case), any other letter stays.
+        ``patterns`` / ``texts``: lists of ``str`` or ``SequenceSet`` handles, as for ``align_pairs``; the windows are cut, reversed
+        and complemented on the device, only the index and window arrays are uploaded.
+
+        Returns what ``wavefront_align_batch`` returns for the materialised strings under this aligner's configuration, in list
+        order, as ``align_pairs`` does: dict(score=, status=) and, with scope full, cigarstrings= / cigar_ops= (coordinates relative
+        to the windows: add the starts).  ValueError, before anything is uploaded, for arrays that are not one-dimensional integer
+        arrays of one length, negative values, a window that ends behind its sequence, or a ``reverse`` that is not boolean / 0-1.
+        ``summary=True`` (scope full only): dict(score=, status=, summary=) as ``align_batch`` describes, no op strings."""
+        if summary:
+            _need_full_for_summary(self._cfg)
+        patterns, texts, arrays, wlen = self._window_lists(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
         self._sync_wildcard()
         sets, mine = self._open_sets(patterns, texts)
         try:
-            pset, tset = sets[0], sets[-1]
-            # chunks as align_pairs cuts them, by the words of the WINDOWS
-            budget = max(1, int(os.environ.get("WFA_HIP_PAIRS_BAND", "0") or 0) or (1 << 24))
-            words = np.cumsum(((wlen[0] + 15) >> 4) + ((wlen[1] + 15) >> 4)) if npairs else np.zeros(0, np.int64)
-            cuts = [0]
-            while cuts[-1] < npairs:
-                lo = cuts[-1]
-                before = int(words[lo - 1]) if lo else 0
-                hi = min(lo + budget, int(np.searchsorted(words, before + (1 << 31), side="right")))
-                cuts.append(max(hi, lo + 1))
-
-            def cut(a, lo, hi):
-                return None if a is None else a[lo:hi]
-
-            return self._run_lists(npairs, cuts, lambda lo, hi: self._native.batch_windows(
-                pset, tset if texts is not None else None, i[lo:hi], j[lo:hi], cut(ps, lo, hi), cut(pl, lo, hi),
-                cut(ts, lo, hi), cut(tl, lo, hi), cut(rev, lo, hi)))
+            return self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, summary=summary)
         finally:
+            for s in mine:
+                s.close()
+
+    def pileup(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
+               text_len=None, reverse=None, min_score=None):
+        """Align the listed windows as ``align_windows`` does (same arguments, same checks; scope must be "full") and pile the
+        alignments up over the TEXT sequences on the GPU: the patterns are reads, the texts references.  Every pair whose status is
+        0 (and whose score is at least ``min_score``, when given) adds the ops of its aligned core — first M to last M — to the
+        text bases they cover; neither op strings nor their run-length encoding leave the device (csrc/wfa_pileup.hpp).
+        ``texts=None`` piles up over ``patterns``.
+
+        Returns a ``Pileup`` (``score``, ``status``, ``counts(j)``, ``depth(j)``, ``close()``; a context manager), which stays
+        valid after the sets are closed.  With ``devices=[...]`` the first device runs it."""
+        if self._cfg.scope != 1:
+            raise ValueError("pileup needs scope='full'")
+        if min_score is not None and (isinstance(min_score, bool) or not isinstance(min_score, (int, np.integer))):
+            raise ValueError(f"min_score must be an integer or None, got {min_score!r}")
+        patterns, texts, arrays, wlen = self._window_lists(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
+        jj, ts = arrays[1], arrays[4]
+        self._sync_wildcard()
+        sets, mine = self._open_sets(patterns, texts)
+        table = None
+        try:
+            table = self._native.pileup(sets[-1])
+
+            def add(rb, lo, hi, score, status):
+                keep = None if min_score is None else (score >= int(min_score))
+                table.add(rb, jj[lo:hi], None if ts is None else ts[lo:hi], keep)
+
+            out = self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, each=add)
+            res = Pileup(table, out["score"], out["status"])
+            table = None
+            return res
+        finally:
+            if table is not None:
+                table.close()
             for s in mine:
                 s.close()
 

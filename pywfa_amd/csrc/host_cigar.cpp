@@ -63,3 +63,71 @@ extern "C" int64_t wfa_hip_cigar_sprint_pretty(const uint8_t* ops, int64_t ops_l
   }
   return (int64_t)s.size();
 }
+
+// ---- the two reductions of an op string, stated for one pair in plain C (the kernels: wfa_summary.hpp, k_pileup.hip) ----------------
+
+namespace {
+// the aligned core [first M, last M] of ops[0..len); false: no M
+bool aligned_core(const uint8_t* ops, int64_t len, int64_t* first, int64_t* last) {
+  int64_t f = 0, l = len - 1;
+  while (f < len && ops[f] != 'M') ++f;
+  if (f >= len) return false;
+  while (ops[l] != 'M') --l;
+  *first = f; *last = l;
+  return true;
+}
+}  // namespace
+
+extern "C" int wfa_hip_ops_summary(const uint8_t* ops, int64_t ops_len, int32_t plen, int32_t tlen, int32_t* out10) {
+  if (ops_len < 0 || plen < 0 || tlen < 0 || (ops_len > 0 && !ops) || !out10) return WFA_HIP_EINVAL;
+  for (int k = 0; k < WFA_HIP_SUMMARY_COLS; ++k) out10[k] = 0;
+  for (int64_t i = 0; i < ops_len; ++i) {
+    const uint8_t c = ops[i];
+    const bool run_start = i == 0 || ops[i - 1] != c;
+    if (c == 'M') out10[0] += 1;
+    else if (c == 'X') out10[1] += 1;
+    else if (c == 'I') { out10[2] += 1; out10[4] += run_start; }
+    else if (c == 'D') { out10[3] += 1; out10[5] += run_start; }
+  }
+  if (ops_len == 0 || plen == 0 || tlen == 0) return WFA_HIP_OK;
+  // locations (align.pyx:797-831 with a threshold of 1): the ops in front of the first and behind the last M stripped; without an
+  // M both scans run through the whole string
+  int64_t first = ops_len, last = -1;
+  (void)aligned_core(ops, ops_len, &first, &last);
+  int32_t ps = 0, ts = 0, pe = plen, te = tlen;
+  for (int64_t i = 0; i < first; ++i) { const uint8_t c = ops[i]; ps += (c == 'D' || c == 'X'); ts += (c == 'I' || c == 'X'); }
+  for (int64_t i = ops_len - 1; i > last; --i) { const uint8_t c = ops[i]; pe -= (c == 'D' || c == 'X'); te -= (c == 'I' || c == 'X'); }
+  out10[6] = ps; out10[7] = pe; out10[8] = ts; out10[9] = te;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen, int32_t* rows) {
+  if (ops_len < 0 || plen < 0 || tlen < 0 || (ops_len > 0 && !ops) || (plen > 0 && !pattern) || (tlen > 0 && !rows)) return WFA_HIP_EINVAL;
+  // an op string that outruns its pair is refused before anything is added
+  int64_t nv = 0, nh = 0;
+  for (int64_t i = 0; i < ops_len; ++i) { const uint8_t c = ops[i]; nv += (c == 'M' || c == 'X' || c == 'D'); nh += (c == 'M' || c == 'X' || c == 'I'); }
+  if (nv > plen || nh > tlen) return WFA_HIP_EINVAL;
+  int64_t first = 0, last = -1;
+  if (!aligned_core(ops, ops_len, &first, &last)) return WFA_HIP_OK;
+  int32_t v = 0, h = 0;
+  for (int64_t i = 0; i <= last; ++i) {
+    const uint8_t c = ops[i];
+    const bool in = i >= first;
+    int32_t* row = rows + (int64_t)WFA_HIP_PILEUP_COLS * h;
+    if (c == 'M' || c == 'X') {
+      if (in) {
+        const uint8_t l = pattern[v];
+        row[l == 'A' ? 0 : l == 'C' ? 1 : l == 'G' ? 2 : l == 'T' ? 3 : 4] += 1;
+        if (c == 'X') row[7] += 1;
+      }
+      ++v; ++h;
+    } else if (c == 'I') {
+      if (in) row[5] += 1;
+      ++h;
+    } else if (c == 'D') {
+      if (in && ops[i - 1] != 'D') row[6] += 1;   // (inside the core a D has an op in front of it)
+      ++v;
+    }
+  }
+  return WFA_HIP_OK;
+}

@@ -39,6 +39,8 @@
 #include "wfa_biwfa.hpp"
 #include "wfa_bilevel.hpp"
 #include "wfa_rle.hpp"
+#include "wfa_summary.hpp"
+#include "wfa_pileup.hpp"
 #include "wfa_cross.hpp"
 
 #define WFA_HIP_ABI_VERSION 4
@@ -52,7 +54,7 @@ static thread_local std::string g_error;
   F(ARENA_KB) F(BAND_DEBUG) F(BAND_SLIM) F(BAND_LDS_MAX) F(BAND_NO_WIN) F(BAND_SPLIT_MIN) F(NO_TINY_INLINE) F(BILEVEL) F(BILEVEL_WIDE_LEVELS) F(BILEVEL_PER_CU) F(BILEVEL_I32) F(BILEVEL_QCAP) F(BILEVEL_LEVELS) F(BILEVEL_LDS) F(BILEVEL_NO_1024) F(BILEVEL_HUGE_MIN) F(BILEVEL_LDS_W) F(BILEVEL_NO_SEQL) F(LANE_DYN) F(LANE_DYN_WAVES) F(BAND_LEFTOVER_WAVES_PER_CU) F(BAND_NCH) F(BAND_NO_LDS) F(BAND_NO_SPLIT) F(BAND_PB) F(PIPE_TAIL) F(LEN16) F(MAILBOX) F(MAILBOX_IDLE_US) F(TILE32)     \
   F(BAND_RECORDS) F(BAND_SPLIT_ROUNDS) F(BAND_WAVES_PER_CU) F(NO_BAND) F(NO_FAST) F(NO_SEGFULL) F(SEGFULL_PAIRS)     \
   F(SEGFULL_STAGES) F(STAGE_TIMING) F(LANE_HEUR32) F(THREADS) F(TINY_BATCH) F(WAVES_PER_CU) F(FAST_WAVES_PER_CU) F(TIMING)          \
-  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT) F(CROSS_BAND) F(CROSS_TOPK_CHUNK)
+  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT) F(CROSS_BAND) F(CROSS_TOPK_CHUNK) F(REDUCE_TIMING)
 enum WfaKnob {
 #define WFA_KNOB_ENUM(n) K_##n,
   WFA_KNOBS(WFA_KNOB_ENUM)
@@ -3091,6 +3093,55 @@ extern "C" int wfa_hip_batch_rle_runs(wfa_hip_batch_t* b, uint8_t* run_code, int
 
 extern "C" int64_t wfa_hip_batch_fallback_pairs(const wfa_hip_batch_t* b) { return b ? b->last_fallback : 0; }
 
+// ---- device-side per-pair summary (csrc/wfa_summary.hpp) ------------------------------------------------
+// WFA_HIP_REDUCE_TIMING=1 (a development knob): the summary and pileup kernels are bracketed by two events and their HIP-event time
+// goes to stderr, one line per call (tools/probes/pileup_index.py reads it).
+struct ReduceTimer {
+  wfa_hip_aligner* al; const char* what; int64_t n;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ReduceTimer(wfa_hip_aligner* al_, const char* what_, int64_t n_) : al(al_), what(what_), n(n_) {
+    if (knob(al, K_REDUCE_TIMING, 0) && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess) (void)hipEventRecord(ev[0], al->stream);
+  }
+  void stop() { if (ev[1]) (void)hipEventRecord(ev[1], al->stream); }
+  ~ReduceTimer() {   // (after the caller's stream synchronisation)
+    float ms = 0.f;
+    if (ev[1] && hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+      fprintf(stderr, "[wfa_hip] %s kernel %.4f ms (%lld pairs)\n", what, ms, (long long)n);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+
+extern "C" int wfa_hip_batch_summary(wfa_hip_batch_t* b, int32_t* summary) {
+  if (!b) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = b->al;
+  if (b->cfg.scope != WFA_SCOPE_FULL) { al->err = "per-pair summary needs scope=full"; return WFA_HIP_EINVAL; }
+  if (!b->ran) { al->err = "per-pair summary needs a finished run of the batch"; return WFA_HIP_EINVAL; }
+  const int64_t n = b->n;
+  if (n > 0 && !summary) { al->err = "per-pair summary: null output"; return WFA_HIP_EINVAL; }
+  const int rc = wfa_hip_batch_sync(b);
+  if (rc != WFA_HIP_OK) return rc;
+  if (n == 0) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  const size_t bytes = (size_t)n * WFA_SUMMARY_COLS * sizeof(int32_t);
+  int32_t* d_out = nullptr;
+  HIP_TRY(al, pool_alloc(al, (void**)&d_out, bytes));
+  const int grid = (int)std::min<int64_t>((n + 3) / 4, (int64_t)al->cu_count * 16);
+  hipError_t e;
+  {
+    ReduceTimer timer(al, "summary", n);
+    hipLaunchKernelGGL(wfa::wfa_summary_kernel, dim3(grid), dim3(256), 0, al->stream, b->d_ops, b->d_cigar_begin, b->d_cigar_len,
+                       (const WfaPairMeta*)b->d_meta, n, d_out);
+    e = hipGetLastError();
+    timer.stop();
+    if (e == hipSuccess) e = hipMemcpyAsync(summary, d_out, bytes, hipMemcpyDeviceToHost, al->stream);
+    const hipError_t e2 = hipStreamSynchronize(al->stream);
+    if (e == hipSuccess) e = e2;
+  }
+  pool_release(al, d_out);
+  HIP_TRY(al, e);
+  return WFA_HIP_OK;
+}
+
 // ---- the single-call path --------------------------------------------------------
 // pywfa's usual loop calls the aligner with ONE pair at a time (align.pyx:421-443).  For a handful of pairs the batch
 // machinery above (a dozen device arrays, uploads, the pack kernel, several result copies) is most of the call, so such
@@ -4533,4 +4584,161 @@ extern "C" wfa_hip_batch_t* wfa_hip_batch_create_windows(wfa_hip_aligner_t* al, 
   const int rc = batch_build_windows(al, b, patterns, texts, npairs, L);
   if (rc != WFA_HIP_OK) { g_error = al->err; batch_free(b); return nullptr; }
   return b;
+}
+
+// ------------------------------------------------------------------------------------------------
+// pileup over a text set (include/wfa_hip.h; csrc/wfa_pileup.hpp, k_pileup.hip)
+// ------------------------------------------------------------------------------------------------
+static_assert(WFA_SUMMARY_COLS == WFA_HIP_SUMMARY_COLS && WFA_PILEUP_COLS == WFA_HIP_PILEUP_COLS, "columns of the kernels and of the ABI");
+
+struct wfa_hip_pileup {
+  wfa_hip_aligner* al = nullptr;
+  int64_t nseq = 0, total = 0;         // sequences, and bases of all of them (the stride of a plane)
+  std::vector<int32_t> h_len;
+  std::vector<int64_t> h_off;          // first base of a sequence in a plane
+  int32_t* d_table = nullptr;          // WFA_PILEUP_COLS planes of `total` counters (its own allocation: up to 32 bytes x every text base)
+  int64_t* d_off = nullptr; int32_t* d_len = nullptr;
+};
+
+extern "C" void wfa_hip_pileup_destroy(wfa_hip_pileup_t* p) {
+  if (!p) return;
+  wfa_hip_aligner* al = p->al;
+  (void)hipSetDevice(al->device);
+  if (p->d_table) (void)hipFree(p->d_table);
+  pool_release(al, p->d_off); pool_release(al, p->d_len);
+  delete p;
+  aligner_release_ref(al);
+}
+
+static int pileup_build(wfa_hip_aligner* al, wfa_hip_pileup* p, const wfa_hip_seqset_t* T) {
+  p->nseq = T->n;
+  p->h_len = T->h_len;
+  p->h_off.assign((size_t)T->n + 1, 0);
+  for (int64_t k = 0; k < T->n; ++k) p->h_off[(size_t)k + 1] = p->h_off[(size_t)k] + T->h_len[(size_t)k];
+  p->total = p->h_off[(size_t)T->n];
+  const size_t bytes = (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t);
+  if (hipMalloc((void**)&p->d_table, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    p->d_table = nullptr;
+    char buf[160];
+    snprintf(buf, sizeof(buf), "pileup table: hipMalloc of %zu bytes failed (32 bytes per text base, %lld bases)", bytes, (long long)p->total);
+    al->err = buf;
+    return WFA_HIP_EDEVICE;
+  }
+  const size_t nn = (size_t)std::max<int64_t>(T->n, 1);
+  HIP_TRY(al, pool_alloc(al, (void**)&p->d_off, nn * sizeof(int64_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&p->d_len, nn * sizeof(int32_t)));
+  HIP_TRY(al, hipMemsetAsync(p->d_table, 0, bytes, al->stream));
+  if (T->n > 0) {
+    HIP_TRY(al, hipMemcpyAsync(p->d_off, p->h_off.data(), (size_t)T->n * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
+    HIP_TRY(al, hipMemcpyAsync(p->d_len, p->h_len.data(), (size_t)T->n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+  }
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  return WFA_HIP_OK;
+}
+
+extern "C" wfa_hip_pileup_t* wfa_hip_pileup_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts) {
+  if (!al) { g_error = "null aligner"; return nullptr; }
+  if (!texts || texts->al != al) { al->err = "sequence set of another aligner"; g_error = al->err; return nullptr; }
+  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  wfa_hip_pileup* p = new wfa_hip_pileup();
+  p->al = al;
+  al->live_batches += 1;
+  if (pileup_build(al, p, texts) != WFA_HIP_OK) { g_error = al->err; wfa_hip_pileup_destroy(p); return nullptr; }
+  return p;
+}
+
+extern "C" int wfa_hip_pileup_clear(wfa_hip_pileup_t* p) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  HIP_TRY(al, hipSetDevice(al->device));
+  HIP_TRY(al, hipMemsetAsync(p->d_table, 0, (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t), al->stream));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (!b) { al->err = "pileup: null batch"; return WFA_HIP_EINVAL; }
+  if (b->al != al) { al->err = "pileup: batch of another aligner"; return WFA_HIP_EINVAL; }
+  if (b->cfg.scope != WFA_SCOPE_FULL) { al->err = "pileup needs scope=full"; return WFA_HIP_EINVAL; }
+  if (!b->ran) { al->err = "pileup needs a finished run of the batch"; return WFA_HIP_EINVAL; }
+  const int64_t n = b->n;
+  if (n > 0 && !j) { al->err = "pileup: the text indices are missing"; return WFA_HIP_EINVAL; }
+  for (int64_t q = 0; q < n; ++q) {
+    char buf[240];
+    if (j[q] < 0 || j[q] >= p->nseq) {
+      snprintf(buf, sizeof(buf), "pileup: text index out of range at position %lld of the pair list: j = %d over a set of %lld sequences",
+               (long long)q, (int)j[q], (long long)p->nseq);
+      al->err = buf; return WFA_HIP_EINVAL;
+    }
+    const int64_t ts = t_start ? t_start[q] : 0, tl = b->h_tlen[(size_t)q], have = p->h_len[(size_t)j[q]];
+    if (ts < 0) {
+      snprintf(buf, sizeof(buf), "pileup: negative text start at position %lld of the pair list: t_start = %lld", (long long)q, (long long)ts);
+      al->err = buf; return WFA_HIP_EINVAL;
+    }
+    if (ts + tl > have) {
+      snprintf(buf, sizeof(buf), "pileup: text window out of range at position %lld of the pair list: [%lld, %lld + %lld) of sequence %d (%lld bases)",
+               (long long)q, (long long)ts, (long long)ts, (long long)tl, (int)j[q], (long long)have);
+      al->err = buf; return WFA_HIP_EINVAL;
+    }
+  }
+  const int rc = wfa_hip_batch_sync(b);
+  if (rc != WFA_HIP_OK) return rc;
+  if (n == 0) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  CrossScratch sc{al};   // (waits for the stream before the blocks go back)
+  int32_t *d_j = nullptr, *d_ts = nullptr;
+  uint8_t* d_keep = nullptr;
+  if (sc.alloc(&d_j, (size_t)n)) return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipMemcpyAsync(d_j, j, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+  if (t_start) {
+    if (sc.alloc(&d_ts, (size_t)n)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpyAsync(d_ts, t_start, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+  }
+  if (keep) {
+    if (sc.alloc(&d_keep, (size_t)n)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpyAsync(d_keep, keep, (size_t)n, hipMemcpyHostToDevice, al->stream));
+  }
+  wfa::PileupArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ops = b->d_ops; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len; a.status = b->d_status;
+  a.meta = b->d_meta; a.words = b->d_words; a.bytes = b->d_bytes; a.pboff = b->d_pboff; a.flags = b->d_flags;
+  a.npairs = n; a.j = d_j; a.t_start = d_ts; a.keep = d_keep;
+  a.seq_off = p->d_off; a.seq_len = p->d_len; a.nseq = p->nseq; a.total = p->total; a.table = p->d_table;
+  {
+    ReduceTimer timer(al, "pileup", n);
+    const int lrc = wfa::launch_pileup(a, al->cu_count, al->stream);
+    timer.stop();
+    const hipError_t e = hipStreamSynchronize(al->stream);   // (the caller's arrays are read by the copies above)
+    if (lrc != 0) { al->err = "pileup kernel launch failed"; return WFA_HIP_EDEVICE; }
+    HIP_TRY(al, e);
+  }
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int32_t* counts) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (seq < 0 || seq >= p->nseq || start < 0 || len < 0 || start + len > p->h_len[(size_t)seq]) {
+    char buf[200];
+    snprintf(buf, sizeof(buf), "pileup: rows [%lld, %lld + %lld) of sequence %d are out of range (%lld sequences; sequence length %lld)", (long long)start,
+             (long long)start, (long long)len, (int)seq, (long long)p->nseq, (long long)((seq >= 0 && seq < p->nseq) ? p->h_len[(size_t)seq] : -1));
+    al->err = buf; return WFA_HIP_EINVAL;
+  }
+  if (len == 0) return WFA_HIP_OK;
+  if (!counts) { al->err = "pileup: null output"; return WFA_HIP_EINVAL; }
+  HIP_TRY(al, hipSetDevice(al->device));
+  // the table is a plane per column: one copy per plane, interleaved into rows on the host
+  std::vector<int32_t> plane((size_t)len * WFA_PILEUP_COLS);
+  for (int c = 0; c < WFA_PILEUP_COLS; ++c)
+    HIP_TRY(al, hipMemcpyAsync(plane.data() + (size_t)c * (size_t)len, p->d_table + (int64_t)c * p->total + p->h_off[(size_t)seq] + start,
+                               (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  for (int c = 0; c < WFA_PILEUP_COLS; ++c) {
+    const int32_t* src = plane.data() + (size_t)c * (size_t)len;
+    for (int64_t r = 0; r < len; ++r) counts[r * WFA_PILEUP_COLS + c] = src[r];
+  }
+  return WFA_HIP_OK;
 }

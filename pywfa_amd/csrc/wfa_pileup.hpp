@@ -1,0 +1,62 @@
+// wfa_pileup.hpp — device-side result surface, per reference position (wfa_hip_pileup_*): the pairs of a full-scope batch taken as
+// reads (patterns) aligned against windows of a resident text set, reduced into per-base counters where the op strings lie.
+//
+// Rule (include/wfa_hip.h; wfa_hip_ops_pileup in host_cigar.cpp is its plain statement for one pair, needing no GPU): walk the op
+// string with pattern position v and text position h from 0; only the ops of the aligned core, first M .. last M, add, to row
+// g = t_start + h of the pair's text:
+//   M  +1 to the column of pattern letter v                        v, h advance
+//   X  +1 to the column of pattern letter v, +1 to `mismatch`      v, h advance
+//   I  +1 to `deleted` (a text base the read lacks)                h advances
+//   D  +1 to `insertion-before`, once per maximal D run            v advances
+// Columns: A C G T other | deleted | insertion-before | mismatch (WFA_PILEUP_COLS).
+//
+// Table layout on the device: one PLANE per column, plane c = table[c * total .. + total), a text base's place in a plane its
+// sequence's prefix offset plus its position.  The lanes of a wave hold neighbouring ops of one pair, hence neighbouring rows g: in
+// this layout the atomics of a wave's M ops on one letter fall into one or two 256-byte stretches of that letter's plane, where a
+// row-major table (8 counters per base) would spread them over 64 rows of 32 bytes each (the one-lane-per-row shape).
+//
+// Kernel (k_pileup.hip): one wave per pair, grid-stride; a first pass finds the first and the last M with ballots (as the location
+// pass of wfa_rle.hpp), a second pass takes 64 ops per round: v and h of a lane are the running bases plus the popcounts of the
+// pattern- / text-consuming ballots below the lane; at most two no-return int32 atomicAdds per op.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "wfa_common.hpp"
+
+namespace wfa {
+
+#define WFA_PILEUP_COLS 8
+#define WFA_PILEUP_DEL 5
+#define WFA_PILEUP_INS 6
+#define WFA_PILEUP_MISMATCH 7
+
+// column of an ASCII pattern letter / of a 2-bit code (A 0, C 1, T 2, G 3: wfa_hip_pack_2bit)
+__host__ __device__ inline int wfa_pileup_letter_col(uint32_t c) {
+  return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4;
+}
+__host__ __device__ inline int wfa_pileup_code_col(uint32_t code) { return (int)((code ^ (code >> 1)) & 3u); }
+
+struct PileupArgs {
+  // the batch (after its run)
+  const uint8_t* ops; const int64_t* cigar_begin; const int32_t* cigar_len; const int32_t* status;
+  const WfaPairMeta* meta;
+  const uint32_t* words;     // the pairs' 2-bit patterns (meta[q].p_woff)
+  const uint8_t* bytes;      // the bytes of the flagged pairs (pboff[q]); nullptr: no pair is flagged
+  const int64_t* pboff;
+  const uint8_t* flags;
+  int64_t npairs;
+  // the list
+  const int32_t* j;          // [npairs] text sequence of pair q
+  const int32_t* t_start;    // [npairs] or nullptr: 0
+  const uint8_t* keep;       // [npairs] or nullptr: every pair
+  // the table
+  const int64_t* seq_off;    // [nseq] first base of a sequence in a plane
+  const int32_t* seq_len;    // [nseq]
+  int64_t nseq;
+  int64_t total;             // bases of the set = the plane stride
+  int32_t* table;            // WFA_PILEUP_COLS planes
+};
+
+int launch_pileup(const PileupArgs& a, int cu_count, hipStream_t stream);
+
+}  // namespace wfa
