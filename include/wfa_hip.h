@@ -516,6 +516,62 @@ void wfa_hip_pileup_destroy(wfa_hip_pileup_t* pileup);
 int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen,
                        int32_t* rows /* tlen x 8, added to */);
 
+/* ---- seed finder: an exact-match k-mer index over a text set, candidate windows for every read ------------ */
+
+/*
+ * The first stage of read mapping on resident sets: from `texts` (references) an index of their k-mers, built on the device; from
+ * `patterns` (reads) the best candidate windows of every read on both strands, in the shape wfa_hip_batch_create_windows and
+ * wfa_hip_pileup_add take (i = the read, j, t_start = text_start, t_len = text_len, reverse).
+ *
+ * Valid k-mers.  The k-mer at position p of a sequence is valid when p + k <= len and none of its k letters is outside ACGT (the
+ * letters wfa_hip_seqset_create flags; a set is upper-cased by nothing in this ABI: lower case is outside ACGT).  Matching is exact, on
+ * the 2-bit codes; the aligner's wildcard plays no part.
+ * Index (k in 8 .. 15, stride >= 1, max_occ >= 1).  Position (j, t) is indexed when t % stride == 0 and the k-mer at t of texts[j] is
+ * valid.  occ(x) is the number of indexed positions of k-mer x over the whole set; a k-mer with occ(x) > max_occ yields no hits (the
+ * repeat mask).
+ * Hits of read i (length L).  R_0 is the read, R_1 its reverse complement.  Every valid k-mer of R_s at position r, for every indexed
+ * position (j, t) of the same k-mer, is one hit (s, j, d = t - r).  H is the number of hits over both strands; H > max_hits: the read
+ * gets overflow = 1 and no seeds.  A read shorter than k has no hits.
+ * Clusters.  The read's hits sorted by (s, j, d); a cluster is a maximal run of consecutive hits of one (s, j) whose neighbouring d
+ * differ by at most `gap`, with hits = its size c, d_lo and d_hi.  (A definition on the sorted multiset: no bucket or thread order
+ * enters.)  The clusters with c >= min_hits, ranked by c descending, then s, j, d_lo ascending; the first n are the read's seeds.
+ * Window of a cluster.  text_start = max(0, d_lo - pad), text_end = min(len(texts[j]), d_hi + L + pad), text_len = text_end -
+ * text_start (always positive).
+ * Result.  Five M x n int32 row-major arrays j, reverse, text_start, text_len, hits, rows padded with j = -1 and zeros elsewhere (as
+ * wfa_hip_cross_topk pads), and overflow, M bytes.
+ *
+ * wfa_hip_seed_index_create builds the index in HBM (csrc/wfa_seed.hpp, k_seed.hip: a direct-addressed counting sort): A TABLE OF
+ * 4^k * 4 BYTES (k = 13: 256 MiB; k = 15: 4 GiB) PLUS 8 BYTES PER INDEXED POSITION; a failed allocation: NULL, WFA_HIP_EDEVICE, the
+ * message names the byte count.  The index copies what it needs of the set (lengths; the query reads no text base) and stays valid
+ * after the set is destroyed.  WFA_HIP_EINVAL (NULL, wfa_hip_last_error names the parameter and its value; nothing is launched): k,
+ * stride or max_occ out of range, a set of another aligner, an empty set (no sequence), a set of 2^31 bases or more.
+ * wfa_hip_seed_index_query: synchronous, writes the host arrays above for the M sequences of `patterns` (n in 1 ..
+ * WFA_HIP_SEED_MAX_N, min_hits >= 1, gap >= 0, pad >= 0, max_hits in 1 .. WFA_HIP_SEED_MAX_HITS).  One kernel, a workgroup per read;
+ * the reads' words are read in place, 20 n + 1 bytes per read come back.  WFA_HIP_EINVAL, nothing launched: a parameter out of range
+ * (named, with its value), a set of another aligner, a missing array with M > 0.  M = 0 is fine.
+ * wfa_hip_seed_index_stats (any pointer may be NULL): the indexed positions, the k-mers over max_occ, the bytes of table and
+ * records, and the HIP-event milliseconds of the last build and of the last query's kernel (0 before the first query).
+ */
+#define WFA_HIP_SEED_MAX_N    16
+#define WFA_HIP_SEED_MAX_HITS 4096
+typedef struct wfa_hip_seed_index wfa_hip_seed_index_t;
+wfa_hip_seed_index_t* wfa_hip_seed_index_create(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* texts, int k, int stride, int max_occ);
+void wfa_hip_seed_index_destroy(wfa_hip_seed_index_t* index);
+int wfa_hip_seed_index_query(wfa_hip_seed_index_t* index, const wfa_hip_seqset_t* patterns, int n, int min_hits, int gap, int pad,
+                             int max_hits, int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits,
+                             uint8_t* overflow);
+int wfa_hip_seed_index_stats(const wfa_hip_seed_index_t* index, int64_t* positions, int64_t* masked_kmers, int64_t* table_bytes,
+                             float* build_ms, float* query_ms);
+
+/* Host only, needs no GPU: the row wfa_hip_seed_index_query writes for ONE read, by the definitions above, from the ASCII read and the
+ * ASCII text set (text q = texts[t_off[q] .. + t_len[q])): j, reverse, text_start, text_len, hits receive n values each, *overflow one
+ * byte.  Returns WFA_HIP_OK, or WFA_HIP_EINVAL for a parameter out of range (msg, when not NULL, receives up to msg_cap bytes naming
+ * the parameter and its value, exactly as the device entries' wfa_hip_last_error), a negative length or a missing array. */
+int wfa_hip_seeds_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                       const int32_t* t_len, int k, int stride, int max_occ, int n, int min_hits, int gap, int pad, int max_hits,
+                       int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow,
+                       char* msg, size_t msg_cap);
+
 #ifdef __cplusplus
 }
 #endif

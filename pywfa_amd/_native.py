@@ -66,6 +66,8 @@ SYMBOLS = [
     "wfa_hip_batch_create_indexed", "wfa_hip_batch_create_windows", "wfa_hip_window_2bit",
     "wfa_hip_batch_summary", "wfa_hip_ops_summary", "wfa_hip_pileup_create", "wfa_hip_pileup_add", "wfa_hip_pileup_read",
     "wfa_hip_pileup_clear", "wfa_hip_pileup_destroy", "wfa_hip_ops_pileup",
+    "wfa_hip_seed_index_create", "wfa_hip_seed_index_destroy", "wfa_hip_seed_index_query", "wfa_hip_seed_index_stats",
+    "wfa_hip_seeds_host",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
@@ -73,6 +75,8 @@ CROSS_MAX_K = 64
 SUMMARY_COLS = 10   # M, X, I, D, I runs, D runs, pattern_start, pattern_end, text_start, text_end
 PILEUP_COLS = 8
 PILEUP_COLUMNS = ("A", "C", "G", "T", "other", "del", "ins", "mismatch")
+SEED_MAX_N, SEED_MAX_HITS = 16, 4096
+SEED_KEYS = ("j", "reverse", "text_start", "text_len", "hits")   # the int32 arrays of a seed query, and overflow (uint8)
 
 
 def lib():
@@ -168,6 +172,14 @@ def lib():
     L.wfa_hip_pileup_destroy.argtypes = [vp]
     L.wfa_hip_pileup_destroy.restype = None
     L.wfa_hip_ops_pileup.argtypes = [vp, i64, vp, i32, i32, vp]
+    L.wfa_hip_seed_index_create.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.wfa_hip_seed_index_create.restype = vp
+    L.wfa_hip_seed_index_destroy.argtypes = [vp]
+    L.wfa_hip_seed_index_destroy.restype = None
+    L.wfa_hip_seed_index_query.argtypes = [vp, vp] + [ctypes.c_int] * 5 + [vp] * 6
+    L.wfa_hip_seed_index_stats.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                           ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.wfa_hip_seeds_host.argtypes = [vp, i32, i64, vp, vp, vp] + [ctypes.c_int] * 8 + [vp] * 6 + [ctypes.c_char_p, ctypes.c_size_t]
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -418,6 +430,10 @@ class Aligner:
         """wfa_hip_pileup_create: a zeroed Pileup over the bases of a SeqSet."""
         return Pileup(self, texts)
 
+    def seed_index(self, texts, k=13, stride=1, max_occ=64):
+        """wfa_hip_seed_index_create: the k-mer index of a SeqSet (4^k * 4 bytes + 8 bytes per indexed position in HBM)."""
+        return SeedIndex(self, texts, k, stride, max_occ)
+
     def cross(self, patterns, texts=None, want=CROSS_DENSE, k=None):
         """wfa_hip_cross_run of two SeqSets (texts None: all-vs-all of ``patterns``); wfa_hip_cross_run_k when ``k`` is given."""
         return CrossRun(self, patterns, texts, want, k)
@@ -473,6 +489,37 @@ def ops_pileup(ops, pattern, tlen, rows=None):
     if rc != OK:
         raise ValueError("wfa_hip_ops_pileup: invalid arguments (an op string that outruns its pair?)")
     return rows
+
+
+def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16, pad=16, max_hits=2048):
+    """wfa_hip_seeds_host (host only): the row ``SeedIndex.query`` holds for ONE read (bytes) against the texts (a list of bytes, or a
+    blob dict(seqs=, off=, len=) made once for many reads): dict of int32[n] ``j`` / ``reverse`` / ``text_start`` / ``text_len`` /
+    ``hits`` and ``overflow`` (0 or 1).  ValueError (naming the parameter) for a parameter out of range."""
+    read = np.frombuffer(bytes(read), dtype=np.uint8) if not isinstance(read, np.ndarray) else np.ascontiguousarray(read, dtype=np.uint8)
+    if not isinstance(texts, dict):
+        texts = seeds_host_texts(texts)
+    rows = max(int(n), 1) if isinstance(n, (int, np.integer)) else 1
+    out = {key: np.zeros(rows, np.int32) for key in SEED_KEYS}
+    over = np.zeros(1, np.uint8)
+    msg = ctypes.create_string_buffer(256)
+    rc = lib().wfa_hip_seeds_host(_ptr(read) if read.size else None, read.size, texts["len"].shape[0], _ptr(texts["seqs"]),
+                                  _ptr(texts["off"]), _ptr(texts["len"]), k, stride, max_occ, n, min_hits, gap, pad, max_hits,
+                                  *[_ptr(out[key]) for key in SEED_KEYS], _ptr(over), msg, len(msg))
+    if rc != OK:
+        raise ValueError(f"wfa_hip_seeds_host: {msg.value.decode()}")
+    out["overflow"] = int(over[0])
+    return out
+
+
+def seeds_host_texts(texts):
+    """The text set of ``seeds_host`` as one blob: dict(seqs= uint8, off= int64, len= int32)."""
+    texts = [bytes(t) for t in texts]
+    length = np.fromiter((len(t) for t in texts), np.int32, len(texts))
+    off = np.zeros(len(texts), np.int64)
+    if len(texts) > 1:
+        off[1:] = np.cumsum(length[:-1], dtype=np.int64)
+    seqs = np.frombuffer(b"".join(texts) + b"\0", dtype=np.uint8)
+    return dict(seqs=seqs, off=off, len=length)
 
 
 def plan_host_threads(sharers, hw_threads=None):
@@ -671,6 +718,63 @@ class Pileup:
         rc = lib().wfa_hip_pileup_clear(self._h)
         if rc != OK:
             self.aligner._raise(rc, "wfa_hip_pileup_clear")
+
+
+class SeedIndex:
+    """An exact-match k-mer index over a text SeqSet, resident in HBM (wfa_hip_seed_index_t): 4^k * 4 bytes of table plus 8 bytes per
+    indexed position.  Stays valid after the set is closed."""
+
+    def __init__(self, aligner, texts, k=13, stride=1, max_occ=64):
+        if not texts._h:
+            raise ValueError("sequence set is closed")
+        self.aligner = aligner
+        self.n = texts.n
+        self._h = lib().wfa_hip_seed_index_create(aligner._h, texts._h, k, stride, max_occ)
+        if not self._h:
+            msg = aligner.error()
+            if "failed" in msg:
+                raise NativeError(f"wfa_hip_seed_index_create: {msg}")
+            raise ValueError(f"wfa_hip_seed_index_create: {msg}")
+        aligner._batches.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().wfa_hip_seed_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def query(self, patterns, n=4, min_hits=2, gap=16, pad=16, max_hits=2048):
+        """wfa_hip_seed_index_query: dict of int32[M, n] ``j`` / ``reverse`` / ``text_start`` / ``text_len`` / ``hits`` and uint8[M]
+        ``overflow`` for the M sequences of a SeqSet."""
+        if not self._h:
+            raise ValueError("seed index is closed")
+        if not patterns._h:
+            raise ValueError("sequence set is closed")
+        cols = n if 1 <= n <= SEED_MAX_N else 1   # (out of range: the library refuses before it writes)
+        out = {key: np.zeros((patterns.n, cols), np.int32) for key in SEED_KEYS}
+        out["overflow"] = np.zeros(patterns.n, np.uint8)
+        rc = lib().wfa_hip_seed_index_query(self._h, patterns._h, n, min_hits, gap, pad, max_hits, *[_ptr(out[key]) for key in SEED_KEYS],
+                                            _ptr(out["overflow"]))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_seed_index_query")
+        return out
+
+    def stats(self):
+        """wfa_hip_seed_index_stats: dict(positions=, masked_kmers=, table_bytes=, build_ms=, query_ms=)."""
+        if not self._h:
+            raise ValueError("seed index is closed")
+        pos, masked, nbytes = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        bms, qms = ctypes.c_float(0), ctypes.c_float(0)
+        rc = lib().wfa_hip_seed_index_stats(self._h, ctypes.byref(pos), ctypes.byref(masked), ctypes.byref(nbytes), ctypes.byref(bms),
+                                            ctypes.byref(qms))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_seed_index_stats")
+        return dict(positions=pos.value, masked_kmers=masked.value, table_bytes=nbytes.value, build_ms=bms.value, query_ms=qms.value)
 
 
 class MultiAligner:

@@ -415,6 +415,78 @@ class SequenceSet:
         return False
 
 
+def _seed_param(name, value, lo, hi=None):
+    """An integer parameter of the seed finder inside its range, or ValueError naming it and its value."""
+    want = f"{lo} .. {hi}" if hi is not None else f"at least {lo}"
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer ({want}), got {value!r}")
+    if value < lo or (hi is not None and value > hi):
+        raise ValueError(f"{name} = {value} is out of range ({want})")
+    return int(value)
+
+
+class SeedIndex:
+    """An exact-match k-mer index over text sequences, kept on the GPU (``WavefrontAligner.seed_index``): ``seeds(patterns)`` finds
+    every read's best candidate windows on both strands, in the shape ``align_windows`` and ``pileup`` take.  ``stats()``:
+    dict(positions=, masked_kmers=, table_bytes=, build_ms=, query_ms=).  The index takes 4^k * 4 bytes plus 8 bytes per indexed
+    position until ``close()`` (or the end of the ``with`` block) and stays valid after the texts' set is closed."""
+
+    def __init__(self, aligner, native_index):
+        self._aligner = aligner
+        self._index = native_index
+
+    def _open(self):
+        if self._index is None or not self._index._h:
+            raise ValueError("seed index is closed")
+        return self._index
+
+    def __len__(self):
+        return self._open().n
+
+    def seeds(self, patterns, n=4, min_hits=2, gap=16, pad=16, max_hits=2048):
+        """The ``n`` best clusters of exact k-mer hits of every read: dict of int32 arrays of shape (M, n) ``j`` (the text),
+        ``reverse`` (1: the read's reverse complement matches), ``text_start`` / ``text_len`` (the window) and ``hits``, best
+        first, rows padded with ``j = -1`` (as ``nearest`` pads), and ``overflow`` (uint8, M): 1 for a read with more than
+        ``max_hits`` hits, which gets no seeds.  A cluster is a run of hits on one strand of one text whose diagonals
+        (text position - read position) lie within ``gap`` of their neighbours; clusters below ``min_hits`` are dropped; the window
+        spans the cluster's diagonals plus the read's length and ``pad`` on both sides, cut to the text.  ``patterns``: a list of
+        ``str`` or a ``SequenceSet``.  ``n``: 1 .. 16, ``max_hits``: 1 .. 4096."""
+        index = self._open()
+        n = _seed_param("n", n, 1, _native.SEED_MAX_N)
+        min_hits = _seed_param("min_hits", min_hits, 1)
+        gap = _seed_param("gap", gap, 0)
+        pad = _seed_param("pad", pad, 0)
+        max_hits = _seed_param("max_hits", max_hits, 1, _native.SEED_MAX_HITS)
+        for name, v in (("min_hits", min_hits), ("gap", gap), ("pad", pad)):
+            if v >= 2**31:
+                raise ValueError(f"{name} = {v} does not fit 32 bits")
+        a = self._aligner
+        if not isinstance(patterns, (SequenceSet, list)):
+            patterns = list(patterns)
+        a._sync_wildcard()
+        sets, mine = a._open_sets(patterns, None)
+        try:
+            return index.query(sets[0], n, min_hits, gap, pad, max_hits)
+        finally:
+            for s in mine:
+                s.close()
+
+    def stats(self):
+        return self._open().stats()
+
+    def close(self):
+        if self._index is not None:
+            self._index.close()
+            self._index = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class WavefrontAligner:
     """Drop-in for ``pywfa.WavefrontAligner`` on the GPU. If a pattern is supplied it is cached.
 
@@ -669,6 +741,30 @@ class WavefrontAligner:
         is packed under the wildcard in force now; after ``wildcard`` changes, make a new one."""
         self._sync_wildcard()
         return SequenceSet(self, self._seqset(seqs))
+
+    def seed_index(self, texts, k=13, stride=1, max_occ=64):
+        """Index the k-mers of ``texts`` (a list of ``str`` or a ``SequenceSet``) on the GPU: a ``SeedIndex`` (``seeds()``,
+        ``stats()``, ``close()``, context manager), the seed source of ``align_windows`` / ``pileup`` for reads without an index of
+        your own.  Every position ``t`` with ``t % stride == 0`` whose ``k`` letters are all of ACGT is indexed; a k-mer that occurs
+        more than ``max_occ`` times in the texts yields no hits (the repeat mask).  ``k``: 8 .. 15; the table takes 4^k * 4 bytes of
+        HBM (k = 13: 256 MiB, k = 15: 4 GiB) plus 8 bytes per indexed position.  With ``devices=[...]`` the first device holds it."""
+        k = _seed_param("k", k, 8, 15)
+        stride = _seed_param("stride", stride, 1)
+        max_occ = _seed_param("max_occ", max_occ, 1)
+        for name, v in (("stride", stride), ("max_occ", max_occ)):
+            if v >= 2**31:
+                raise ValueError(f"{name} = {v} does not fit 32 bits")
+        if not isinstance(texts, (SequenceSet, list)):
+            texts = list(texts)
+        if len(texts) == 0:
+            raise ValueError("texts = a set of 0 sequences is out of range (at least 1)")
+        self._sync_wildcard()
+        sets, mine = self._open_sets(texts, None)
+        try:
+            return SeedIndex(self, self._native.seed_index(sets[0], k, stride, max_occ))
+        finally:
+            for s in mine:
+                s.close()
 
     def _open_sets(self, patterns, texts):
         """The native sets of ``patterns`` / ``texts`` (None: one set) and those of them this call uploaded (its to close)."""

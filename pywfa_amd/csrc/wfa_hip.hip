@@ -41,6 +41,7 @@
 #include "wfa_rle.hpp"
 #include "wfa_summary.hpp"
 #include "wfa_pileup.hpp"
+#include "wfa_seed.hpp"
 #include "wfa_cross.hpp"
 
 #define WFA_HIP_ABI_VERSION 4
@@ -3671,6 +3672,7 @@ struct wfa_hip_seqset {
   uint32_t* d_words = nullptr;     // one word-aligned run per sequence (wfa_hip_pack_2bit's layout)
   uint8_t* d_bytes = nullptr;      // the sequences' bytes, back to back (a byte pair needs both of its sequences' bytes)
   uint32_t* d_woff = nullptr; int32_t* d_len = nullptr; int64_t* d_boff = nullptr; uint8_t* d_flag = nullptr;
+  mutable uint16_t* d_mask = nullptr;   // the seed finder's view of h_runs: one bit per base, 16 per word (seqset_mask: built on first use)
 };
 
 static_assert(WFA_CROSS_MAX_K == WFA_HIP_CROSS_MAX_K, "top-k bound of the kernels and of the ABI");
@@ -3700,7 +3702,7 @@ extern "C" void wfa_hip_seqset_destroy(wfa_hip_seqset_t* s) {
   if (!s) return;
   wfa_hip_aligner* al = s->al;
   (void)hipSetDevice(al->device);
-  void* ptrs[] = {s->d_words, s->d_bytes, s->d_woff, s->d_len, s->d_boff, s->d_flag};
+  void* ptrs[] = {s->d_words, s->d_bytes, s->d_woff, s->d_len, s->d_boff, s->d_flag, s->d_mask};
   for (void* p : ptrs) pool_release(al, p);
   delete s;
   aligner_release_ref(al);
@@ -4740,5 +4742,193 @@ extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t sta
     const int32_t* src = plane.data() + (size_t)c * (size_t)len;
     for (int64_t r = 0; r < len; ++r) counts[r * WFA_PILEUP_COLS + c] = src[r];
   }
+  return WFA_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// seed finder: a k-mer index over a text set, candidate windows per read (include/wfa_hip.h; csrc/wfa_seed.hpp, k_seed.hip)
+// ------------------------------------------------------------------------------------------------
+static_assert(WFA_SEED_MAX_N == WFA_HIP_SEED_MAX_N && WFA_SEED_MAX_HITS == WFA_HIP_SEED_MAX_HITS, "bounds of the kernels and of the ABI");
+
+namespace wfa {   // host_seed.cpp: the parameter checks shared with wfa_hip_seeds_host
+int seed_check_index(int k, int stride, int max_occ, char* msg, size_t cap);
+int seed_check_query(int n, int min_hits, int gap, int pad, int max_hits, char* msg, size_t cap);
+}
+
+struct wfa_hip_seed_index {
+  wfa_hip_aligner* al = nullptr;
+  int k = 0, stride = 0, max_occ = 0;
+  int64_t nseq = 0;
+  uint32_t* d_table = nullptr;        // 4^k + 1 bucket starts (its own allocation: 4^k * 4 bytes)
+  wfa::SeedRec* d_recs = nullptr;     // {j, t} per indexed position, in bucket order (its own allocation)
+  int32_t* d_len = nullptr;           // the texts' lengths
+  int64_t positions = 0, masked = 0, table_bytes = 0;
+  float build_ms = 0.f, query_ms = 0.f;
+};
+
+// The letters outside ACGT of a set as the seed kernels read them: bit b of mask[w] = base 16 (w - woff) + b of the word's sequence,
+// from the runs the set keeps on the host; uploaded on the first call, nullptr when no sequence of the set is flagged.
+static int seqset_mask(wfa_hip_aligner* al, const wfa_hip_seqset* S, const uint16_t** out) {
+  *out = S->d_mask;
+  if (S->d_mask || std::find(S->h_flag.begin(), S->h_flag.end(), (uint8_t)1) == S->h_flag.end()) return WFA_HIP_OK;
+  std::vector<uint16_t> mask((size_t)S->nwords + 4, 0);
+  uint64_t w = 0;
+  for (int64_t q = 0; q < S->n; ++q) {
+    const std::vector<int32_t>& r = S->h_runs[(size_t)q];
+    for (size_t x = 0; x + 1 < r.size(); x += 2)
+      for (int32_t p = r[x]; p < r[x + 1]; ++p) mask[(size_t)w + ((size_t)p >> 4)] |= (uint16_t)(1u << (p & 15));
+    w += (uint64_t)((S->h_len[(size_t)q] + 15) >> 4);
+  }
+  uint16_t* d = nullptr;
+  HIP_TRY(al, pool_alloc(al, (void**)&d, mask.size() * sizeof(uint16_t)));
+  const hipError_t e = hipMemcpy(d, mask.data(), mask.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { pool_release(al, d); HIP_TRY(al, e); }
+  S->d_mask = d;
+  *out = d;
+  return WFA_HIP_OK;
+}
+
+static wfa::SeedSetView seed_view(const wfa_hip_seqset* S, const uint16_t* mask) {
+  wfa::SeedSetView v;
+  v.words = S->d_words; v.mask = mask; v.woff = S->d_woff; v.len = S->d_len; v.nseq = S->n; v.nwords = S->nwords;
+  return v;
+}
+
+extern "C" void wfa_hip_seed_index_destroy(wfa_hip_seed_index_t* x) {
+  if (!x) return;
+  wfa_hip_aligner* al = x->al;
+  (void)hipSetDevice(al->device);
+  if (x->d_table) (void)hipFree(x->d_table);
+  if (x->d_recs) (void)hipFree(x->d_recs);
+  pool_release(al, x->d_len);
+  delete x;
+  aligner_release_ref(al);
+}
+
+static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wfa_hip_seqset* T) {
+  x->nseq = T->n;
+  uint64_t cap = 0;   // the positions the stride takes of sequences without a flagged letter: at least the indexed ones
+  for (int32_t len : T->h_len)
+    if (len >= x->k) cap += (uint64_t)((len - x->k) / x->stride + 1);
+  const uint64_t buckets = 1ull << (2 * x->k);
+  const size_t table_bytes = (size_t)(buckets + 1) * sizeof(uint32_t), rec_bytes = (size_t)std::max<uint64_t>(cap, 1) * sizeof(wfa::SeedRec);
+  char buf[240];
+  if (hipMalloc((void**)&x->d_table, table_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    x->d_table = nullptr;
+    snprintf(buf, sizeof(buf), "seed index table: hipMalloc of %zu bytes failed (4 bytes per k-mer of k = %d: 4^k buckets)", table_bytes, x->k);
+    al->err = buf;
+    return WFA_HIP_EDEVICE;
+  }
+  if (hipMalloc((void**)&x->d_recs, rec_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    x->d_recs = nullptr;
+    snprintf(buf, sizeof(buf), "seed index records: hipMalloc of %zu bytes failed (8 bytes per indexed position, %llu positions)", rec_bytes,
+             (unsigned long long)cap);
+    al->err = buf;
+    return WFA_HIP_EDEVICE;
+  }
+  x->table_bytes = (int64_t)(table_bytes + rec_bytes);
+  const uint16_t* mask = nullptr;
+  if (seqset_mask(al, T, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
+  CrossScratch sc{al};
+  uint32_t *d_bsum = nullptr, *d_masked = nullptr;
+  if (sc.alloc(&d_bsum, (size_t)((buckets + 1 + WFA_SEED_SCAN_CHUNK - 1) / WFA_SEED_SCAN_CHUNK)) || sc.alloc(&d_masked, 1)) return WFA_HIP_EDEVICE;
+  HIP_TRY(al, pool_alloc(al, (void**)&x->d_len, (size_t)T->n * sizeof(int32_t)));
+  HIP_TRY(al, hipMemcpyAsync(x->d_len, T->d_len, (size_t)T->n * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
+  HIP_TRY(al, hipEventCreate(&sc.ev[0]));
+  HIP_TRY(al, hipEventCreate(&sc.ev[1]));
+  wfa::SeedBuildArgs a;
+  memset(&a, 0, sizeof(a));
+  a.t = seed_view(T, mask);
+  a.k = x->k; a.stride = x->stride; a.max_occ = (uint32_t)x->max_occ;
+  a.table = x->d_table; a.recs = x->d_recs; a.bsum = d_bsum; a.masked = d_masked;
+  HIP_TRY(al, hipEventRecord(sc.ev[0], al->stream));
+  HIP_TRY(al, hipMemsetAsync(x->d_table, 0, table_bytes, al->stream));
+  HIP_TRY(al, hipMemsetAsync(d_masked, 0, sizeof(uint32_t), al->stream));
+  const int lrc = wfa::launch_seed_count(a, al->stream) | wfa::launch_seed_scan(a, al->stream) |
+                  wfa::launch_seed_fill(a, (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull), al->stream);
+  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
+  uint32_t total = 0, masked = 0;
+  HIP_TRY(al, hipMemcpyAsync(&total, x->d_table + buckets, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
+  HIP_TRY(al, hipMemcpyAsync(&masked, d_masked, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
+  const hipError_t e = hipStreamSynchronize(al->stream);
+  if (lrc != 0) { al->err = "seed index kernel launch failed"; return WFA_HIP_EDEVICE; }
+  HIP_TRY(al, e);
+  HIP_TRY(al, hipEventElapsedTime(&x->build_ms, sc.ev[0], sc.ev[1]));
+  x->positions = total; x->masked = masked;
+  return WFA_HIP_OK;
+}
+
+extern "C" wfa_hip_seed_index_t* wfa_hip_seed_index_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int stride, int max_occ) {
+  if (!al) { g_error = "null aligner"; return nullptr; }
+  char buf[200];
+  if (!texts || texts->al != al) { al->err = "seed index: sequence set of another aligner"; g_error = al->err; return nullptr; }
+  if (wfa::seed_check_index(k, stride, max_occ, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; g_error = al->err; return nullptr; }
+  if (texts->n == 0) { al->err = "seed index: texts = a set of 0 sequences is out of range (at least 1)"; g_error = al->err; return nullptr; }
+  if (texts->nbytes >= (1ll << 31)) {
+    snprintf(buf, sizeof(buf), "seed index: texts = a set of %lld bases is out of range (below 2^31: split the set)", (long long)texts->nbytes);
+    al->err = buf; g_error = al->err; return nullptr;
+  }
+  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);   // (the resident one-pair kernel: the build takes the device)
+  wfa_hip_seed_index* x = new wfa_hip_seed_index();
+  x->al = al; x->k = k; x->stride = stride; x->max_occ = max_occ;
+  al->live_batches += 1;
+  if (seed_index_build(al, x, texts) != WFA_HIP_OK) { g_error = al->err; wfa_hip_seed_index_destroy(x); return nullptr; }
+  return x;
+}
+
+extern "C" int wfa_hip_seed_index_query(wfa_hip_seed_index_t* x, const wfa_hip_seqset_t* P, int n, int min_hits, int gap, int pad, int max_hits,
+                                        int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow) {
+  if (!x) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = x->al;
+  char buf[200];
+  if (!P || P->al != al) { al->err = "seed query: sequence set of another aligner"; return WFA_HIP_EINVAL; }
+  if (wfa::seed_check_query(n, min_hits, gap, pad, max_hits, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  const int64_t m = P->n;
+  if (m == 0) return WFA_HIP_OK;
+  if (!j || !reverse || !text_start || !text_len || !hits || !overflow) { al->err = "seed query: a result array is missing"; return WFA_HIP_EINVAL; }
+  HIP_TRY(al, hipSetDevice(al->device));
+  if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);
+  const uint16_t* mask = nullptr;
+  if (seqset_mask(al, P, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
+  CrossScratch sc{al};
+  const size_t cells = (size_t)m * (size_t)n;
+  int32_t* d_rows = nullptr;
+  uint8_t* d_over = nullptr;
+  if (sc.alloc(&d_rows, 5 * cells) || sc.alloc(&d_over, (size_t)m)) return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipEventCreate(&sc.ev[0]));
+  HIP_TRY(al, hipEventCreate(&sc.ev[1]));
+  wfa::SeedQueryArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = seed_view(P, mask);
+  a.table = x->d_table; a.recs = x->d_recs; a.t_len = x->d_len; a.t_nseq = x->nseq;
+  a.k = x->k; a.max_occ = (uint32_t)x->max_occ;
+  a.n = n; a.min_hits = min_hits; a.max_hits = max_hits; a.gap = (uint32_t)gap; a.pad = pad;
+  a.j = d_rows; a.reverse = d_rows + cells; a.text_start = d_rows + 2 * cells; a.text_len = d_rows + 3 * cells; a.hits = d_rows + 4 * cells;
+  a.overflow = d_over;
+  HIP_TRY(al, hipEventRecord(sc.ev[0], al->stream));
+  const int lrc = wfa::launch_seed_query(a, m, al->cu_count, al->stream);
+  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
+  int32_t* host[5] = {j, reverse, text_start, text_len, hits};
+  for (int c = 0; c < 5; ++c)
+    HIP_TRY(al, hipMemcpyAsync(host[c], d_rows + (size_t)c * cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+  HIP_TRY(al, hipMemcpyAsync(overflow, d_over, (size_t)m, hipMemcpyDeviceToHost, al->stream));
+  const hipError_t e = hipStreamSynchronize(al->stream);
+  if (lrc != 0) { al->err = "seed query kernel launch failed"; return WFA_HIP_EDEVICE; }
+  HIP_TRY(al, e);
+  HIP_TRY(al, hipEventElapsedTime(&x->query_ms, sc.ev[0], sc.ev[1]));
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_seed_index_stats(const wfa_hip_seed_index_t* x, int64_t* positions, int64_t* masked_kmers, int64_t* table_bytes,
+                                        float* build_ms, float* query_ms) {
+  if (!x) return WFA_HIP_EINVAL;
+  if (positions) *positions = x->positions;
+  if (masked_kmers) *masked_kmers = x->masked;
+  if (table_bytes) *table_bytes = x->table_bytes;
+  if (build_ms) *build_ms = x->build_ms;
+  if (query_ms) *query_ms = x->query_ms;
   return WFA_HIP_OK;
 }

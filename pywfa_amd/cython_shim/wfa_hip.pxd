@@ -25,3 +25,19 @@ cdef extern from "wfa_hip.h" nogil:
                             const int64_t* cigar_off, int64_t* cigar_begin, int32_t* cigar_len)
     int64_t wfa_hip_cigar_sprint_pretty(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen,
                             const uint8_t* text, int32_t tlen, char* out, int64_t cap)
+    # the seed finder over resident sequence sets (include/wfa_hip.h: "seed finder")
+    ctypedef struct wfa_hip_seqset_t
+    ctypedef struct wfa_hip_seed_index_t
+    wfa_hip_seqset_t* wfa_hip_seqset_create(wfa_hip_aligner_t* aligner, int64_t n, const uint8_t* seqs, const int64_t* off, const int32_t* len)
+    void wfa_hip_seqset_destroy(wfa_hip_seqset_t* set)
+    wfa_hip_seed_index_t* wfa_hip_seed_index_create(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* texts, int k, int stride, int max_occ)
+    void wfa_hip_seed_index_destroy(wfa_hip_seed_index_t* index)
+    int wfa_hip_seed_index_query(wfa_hip_seed_index_t* index, const wfa_hip_seqset_t* patterns, int n, int min_hits, int gap, int pad,
+                            int max_hits, int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits,
+                            uint8_t* overflow)
+    int wfa_hip_seed_index_stats(const wfa_hip_seed_index_t* index, int64_t* positions, int64_t* masked_kmers, int64_t* table_bytes,
+                            float* build_ms, float* query_ms)
+    int wfa_hip_seeds_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                            const int32_t* t_len, int k, int stride, int max_occ, int n, int min_hits, int gap, int pad, int max_hits,
+                            int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow,
+                            char* msg, size_t msg_cap)
