@@ -572,6 +572,60 @@ int wfa_hip_seeds_host(const uint8_t* read, int32_t read_len, int64_t ntexts, co
                        int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow,
                        char* msg, size_t msg_cap);
 
+/* ---- chains: co-linear chaining of a read's anchors on the seed index, candidate windows for long reads --- */
+
+/*
+ * A second query on the same index, for reads whose hits neither fit the seed query's max_hits nor stay within `gap` of one diagonal:
+ * the read's anchors are chained along the read, and the best chains become windows.  Integers only, and a definition on a sorted
+ * multiset: no bucket order or thread order enters.  The index semantics (valid k-mers, stride, max_occ, R_0 the read and R_1 its
+ * reverse complement) are exactly those of the seed finder above.
+ *
+ * Anchors of read i (length L).  Every valid k-mer of R_s at position r, for every indexed position (j, t) of the same k-mer with
+ * occ <= max_occ, is one anchor (s, r, j, t) with diagonal d = t - r.  N is the number of anchors over both strands; N > max_anchors:
+ * the read gets overflow = 1 and a padded row.
+ * Order.  The anchors sorted by (s, r, j, t): the order in which a scan along the read meets them, made canonical inside a bucket.
+ * Chaining.  In that order; an anchor starts with f = k, cnt = 1, d_lo = d_hi = d, r_first = r.  The candidate predecessors of anchor a
+ * are the up to `lookback` anchors immediately before a in the order.  Candidate b is eligible when it has the same s and j as a,
+ * dr = r_a - r_b > 0 and dt = t_a - t_b > 0, dr <= max_dist and dt <= max_dist, and g = |dt - dr| <= band.  Its value is
+ * f(b) + min(dr, dt, k) - cost(g), with cost(0) = 0 and cost(g) = ((g * k) >> 6) + (floor(log2 g) >> 1) for g >= 1.  Anchor a adopts
+ * the eligible candidate of largest value, on a tie the nearest one (the largest index), but only when that value is strictly greater
+ * than k; it then takes f = that value, cnt = cnt(b) + 1, d_lo = min(d_lo(b), d), d_hi = max(d_hi(b), d), r_first = r_first(b).
+ * Selection.  n rounds.  Of the anchors with cnt >= min_hits and f >= min_score that are not yet covered, the one of largest f, on a tie
+ * the smallest index in the order, is taken; its window is text_start = max(0, d_lo - pad), text_end = min(len(texts[j]), d_hi + L +
+ * pad) (the shape of a seed cluster's window); every anchor of the same (s, j) with text_start <= t and t + k <= text_end becomes
+ * covered (the chosen anchor always does).  The rounds stop when no anchor qualifies.
+ * Result.  Eight M x n int32 row-major arrays: j, reverse (= s), text_start, text_len, hits (= cnt), score (= f), and pattern_start,
+ * pattern_len: the chain's span [r_first, r_a + k) of R_s in the coordinates of the stored read, as wfa_hip_batch_create_windows takes
+ * them (s = 0: pattern_start = r_first; s = 1: pattern_start = L - (r_a + k)).  Rows padded with j = -1 and zeros elsewhere, and
+ * overflow, M bytes.
+ * Ranges (outside: WFA_HIP_EINVAL, the parameter named with its value, nothing launched): n in 1 .. WFA_HIP_SEED_MAX_N, min_hits >= 1,
+ * min_score >= 0, lookback in 1 .. WFA_HIP_CHAIN_MAX_LOOKBACK, max_dist in 1 .. 2^20, band in 0 .. 2^16, pad >= 0, max_anchors in 1 ..
+ * WFA_HIP_CHAIN_MAX_ANCHORS.  Within them every value above fits 32 bits.
+ *
+ * wfa_hip_seed_index_chain: synchronous, writes the host arrays above for the M sequences of `patterns`; also refused: a set of another
+ * aligner, a missing array with M > 0.  M = 0 is fine.  One kernel, a workgroup per read (csrc/wfa_chain.hpp, k_chain.hip); the anchors
+ * and their chain state live in a workspace in HBM of 32 BYTES x max_anchors PER RESIDENT WORKGROUP, its own allocation, kept on the
+ * index and grown on demand (freed with the index); a failed allocation: WFA_HIP_EDEVICE, the message names the byte count.
+ * wfa_hip_seed_index_chain_stats (either pointer may be NULL): the HIP-event milliseconds of the last chain kernel (0 before the first)
+ * and the bytes of the workspace now held.
+ */
+#define WFA_HIP_CHAIN_MAX_LOOKBACK 64
+#define WFA_HIP_CHAIN_MAX_ANCHORS  65536
+int wfa_hip_seed_index_chain(wfa_hip_seed_index_t* index, const wfa_hip_seqset_t* patterns, int n, int min_hits, int min_score, int lookback,
+                             int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
+                             int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
+                             uint8_t* overflow);
+int wfa_hip_seed_index_chain_stats(const wfa_hip_seed_index_t* index, float* kernel_ms, int64_t* workspace_bytes);
+
+/* Host only, needs no GPU: the row wfa_hip_seed_index_chain writes for ONE read, by the definitions above, from the ASCII read and the
+ * ASCII text set (as wfa_hip_seeds_host takes them): the eight arrays receive n values each, *overflow one byte.  Returns WFA_HIP_OK,
+ * or WFA_HIP_EINVAL with the device entry's message for a parameter out of range, a negative length or a missing array. */
+int wfa_hip_chains_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                        const int32_t* t_len, int k, int stride, int max_occ, int n, int min_hits, int min_score, int lookback,
+                        int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
+                        int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
+                        uint8_t* overflow, char* msg, size_t msg_cap);
+
 #ifdef __cplusplus
 }
 #endif

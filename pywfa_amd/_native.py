@@ -68,6 +68,7 @@ SYMBOLS = [
     "wfa_hip_pileup_clear", "wfa_hip_pileup_destroy", "wfa_hip_ops_pileup",
     "wfa_hip_seed_index_create", "wfa_hip_seed_index_destroy", "wfa_hip_seed_index_query", "wfa_hip_seed_index_stats",
     "wfa_hip_seeds_host",
+    "wfa_hip_seed_index_chain", "wfa_hip_seed_index_chain_stats", "wfa_hip_chains_host",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
@@ -77,6 +78,9 @@ PILEUP_COLS = 8
 PILEUP_COLUMNS = ("A", "C", "G", "T", "other", "del", "ins", "mismatch")
 SEED_MAX_N, SEED_MAX_HITS = 16, 4096
 SEED_KEYS = ("j", "reverse", "text_start", "text_len", "hits")   # the int32 arrays of a seed query, and overflow (uint8)
+CHAIN_MAX_LOOKBACK, CHAIN_MAX_ANCHORS = 64, 65536
+# the int32 arrays of a chain query, and overflow (uint8)
+CHAIN_KEYS = ("j", "reverse", "text_start", "text_len", "hits", "score", "pattern_start", "pattern_len")
 
 
 def lib():
@@ -180,6 +184,9 @@ def lib():
     L.wfa_hip_seed_index_stats.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64),
                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.wfa_hip_seeds_host.argtypes = [vp, i32, i64, vp, vp, vp] + [ctypes.c_int] * 8 + [vp] * 6 + [ctypes.c_char_p, ctypes.c_size_t]
+    L.wfa_hip_seed_index_chain.argtypes = [vp, vp] + [ctypes.c_int] * 8 + [vp] * 9
+    L.wfa_hip_seed_index_chain_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
+    L.wfa_hip_chains_host.argtypes = [vp, i32, i64, vp, vp, vp] + [ctypes.c_int] * 11 + [vp] * 9 + [ctypes.c_char_p, ctypes.c_size_t]
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -511,6 +518,27 @@ def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16,
     return out
 
 
+def chains_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=3, min_score=40, lookback=32, max_dist=5000, band=500, pad=64,
+                max_anchors=16384):
+    """wfa_hip_chains_host (host only): the row ``SeedIndex.chain`` holds for ONE read (bytes) against the texts (a list of bytes, or
+    the blob of ``seeds_host_texts``): dict of int32[n] per key of ``CHAIN_KEYS`` and ``overflow`` (0 or 1).  ValueError (naming the
+    parameter) for a parameter out of range."""
+    read = np.frombuffer(bytes(read), dtype=np.uint8) if not isinstance(read, np.ndarray) else np.ascontiguousarray(read, dtype=np.uint8)
+    if not isinstance(texts, dict):
+        texts = seeds_host_texts(texts)
+    rows = max(int(n), 1) if isinstance(n, (int, np.integer)) else 1
+    out = {key: np.zeros(rows, np.int32) for key in CHAIN_KEYS}
+    over = np.zeros(1, np.uint8)
+    msg = ctypes.create_string_buffer(256)
+    rc = lib().wfa_hip_chains_host(_ptr(read) if read.size else None, read.size, texts["len"].shape[0], _ptr(texts["seqs"]),
+                                   _ptr(texts["off"]), _ptr(texts["len"]), k, stride, max_occ, n, min_hits, min_score, lookback, max_dist,
+                                   band, pad, max_anchors, *[_ptr(out[key]) for key in CHAIN_KEYS], _ptr(over), msg, len(msg))
+    if rc != OK:
+        raise ValueError(f"wfa_hip_chains_host: {msg.value.decode()}")
+    out["overflow"] = int(over[0])
+    return out
+
+
 def seeds_host_texts(texts):
     """The text set of ``seeds_host`` as one blob: dict(seqs= uint8, off= int64, len= int32)."""
     texts = [bytes(t) for t in texts]
@@ -763,6 +791,32 @@ class SeedIndex:
         if rc != OK:
             self.aligner._raise(rc, "wfa_hip_seed_index_query")
         return out
+
+    def chain(self, patterns, n=4, min_hits=3, min_score=40, lookback=32, max_dist=5000, band=500, pad=64, max_anchors=16384):
+        """wfa_hip_seed_index_chain: dict of int32[M, n] per key of ``CHAIN_KEYS`` and uint8[M] ``overflow`` for the M sequences of a
+        SeqSet."""
+        if not self._h:
+            raise ValueError("seed index is closed")
+        if not patterns._h:
+            raise ValueError("sequence set is closed")
+        cols = n if 1 <= n <= SEED_MAX_N else 1   # (out of range: the library refuses before it writes)
+        out = {key: np.zeros((patterns.n, cols), np.int32) for key in CHAIN_KEYS}
+        out["overflow"] = np.zeros(patterns.n, np.uint8)
+        rc = lib().wfa_hip_seed_index_chain(self._h, patterns._h, n, min_hits, min_score, lookback, max_dist, band, pad, max_anchors,
+                                            *[_ptr(out[key]) for key in CHAIN_KEYS], _ptr(out["overflow"]))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_seed_index_chain")
+        return out
+
+    def chain_stats(self):
+        """wfa_hip_seed_index_chain_stats: dict(kernel_ms=, workspace_bytes=)."""
+        if not self._h:
+            raise ValueError("seed index is closed")
+        ms, nbytes = ctypes.c_float(0), ctypes.c_int64(0)
+        rc = lib().wfa_hip_seed_index_chain_stats(self._h, ctypes.byref(ms), ctypes.byref(nbytes))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_seed_index_chain_stats")
+        return dict(kernel_ms=ms.value, workspace_bytes=nbytes.value)
 
     def stats(self):
         """wfa_hip_seed_index_stats: dict(positions=, masked_kmers=, table_bytes=, build_ms=, query_ms=)."""

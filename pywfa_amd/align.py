@@ -471,8 +471,48 @@ class SeedIndex:
             for s in mine:
                 s.close()
 
+    def chains(self, patterns, n=4, min_hits=3, min_score=40, lookback=32, max_dist=5000, band=500, pad=64, max_anchors=16384):
+        """The ``n`` best co-linear chains of exact k-mer anchors of every read, for reads too long or too divergent for ``seeds``:
+        dict of int32 arrays of shape (M, n) ``j``, ``reverse``, ``text_start`` / ``text_len`` (the text window, of the shape of a
+        seed's), ``hits`` (the chain's anchors), ``score`` and ``pattern_start`` / ``pattern_len`` (the part of the stored read the
+        chain spans), best first, rows padded with ``j = -1``, and ``overflow`` (uint8, M): 1 for a read with more than
+        ``max_anchors`` anchors, which gets no chains.  All of it goes into ``align_windows`` / ``pileup`` as it is.  An anchor is an
+        exact k-mer match of read position r and text position t; along the read an anchor joins the best of the ``lookback``
+        anchors before it that lies on the same strand and text, at most ``max_dist`` behind it on both sequences and at most
+        ``band`` off its diagonal; chains below ``min_hits`` anchors or ``min_score`` are dropped, and a chain inside the window of a
+        better one is not reported again (the rule: include/wfa_hip.h, "chains").  ``patterns``: a list of ``str`` or a
+        ``SequenceSet``.  ``n``: 1 .. 16, ``lookback``: 1 .. 64, ``max_dist``: 1 .. 2^20, ``band``: 0 .. 2^16, ``max_anchors``:
+        1 .. 65536; the anchors take 32 bytes x ``max_anchors`` per resident workgroup of GPU memory, kept on the index."""
+        index = self._open()
+        n = _seed_param("n", n, 1, _native.SEED_MAX_N)
+        min_hits = _seed_param("min_hits", min_hits, 1)
+        min_score = _seed_param("min_score", min_score, 0)
+        lookback = _seed_param("lookback", lookback, 1, _native.CHAIN_MAX_LOOKBACK)
+        max_dist = _seed_param("max_dist", max_dist, 1, 1 << 20)
+        band = _seed_param("band", band, 0, 1 << 16)
+        pad = _seed_param("pad", pad, 0)
+        max_anchors = _seed_param("max_anchors", max_anchors, 1, _native.CHAIN_MAX_ANCHORS)
+        for name, v in (("min_hits", min_hits), ("min_score", min_score), ("pad", pad)):
+            if v >= 2**31:
+                raise ValueError(f"{name} = {v} does not fit 32 bits")
+        a = self._aligner
+        if not isinstance(patterns, (SequenceSet, list)):
+            patterns = list(patterns)
+        a._sync_wildcard()
+        sets, mine = a._open_sets(patterns, None)
+        try:
+            return index.chain(sets[0], n, min_hits, min_score, lookback, max_dist, band, pad, max_anchors)
+        finally:
+            for s in mine:
+                s.close()
+
     def stats(self):
-        return self._open().stats()
+        """dict(positions=, masked_kmers=, table_bytes=, build_ms=, query_ms=) and, of the last ``chains()``, chain_ms= and
+        chain_workspace_bytes=."""
+        index = self._open()
+        st, ch = index.stats(), index.chain_stats()
+        st.update(chain_ms=ch["kernel_ms"], chain_workspace_bytes=ch["workspace_bytes"])
+        return st
 
     def close(self):
         if self._index is not None:

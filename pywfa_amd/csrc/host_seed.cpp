@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "wfa_hip.h"
+#include "host_kmer.hpp"
 
 namespace wfa {
 
@@ -35,32 +36,7 @@ int seed_check_query(int n, int min_hits, int gap, int pad, int max_hits, char* 
 
 namespace {
 
-// the 2-bit code of a letter of ACGT (wfa_hip_pack_2bit: (c >> 1) & 3), -1 for every other byte
-struct CodeTable {
-  int8_t v[256];
-  CodeTable() { for (int c = 0; c < 256; ++c) v[c] = (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? (int8_t)((c >> 1) & 3) : (int8_t)-1; }
-};
-const CodeTable code_table;
-inline int code_of(uint8_t c) { return code_table.v[c]; }
-
-inline uint8_t complement(uint8_t c) {
-  switch (c) { case 'A': return 'T'; case 'T': return 'A'; case 'C': return 'G'; case 'G': return 'C'; default: return c; }
-}
-
-// calls f(p, code) for every valid k-mer of seq[0 .. len): p + k <= len and k letters of ACGT; base p + i in bits 2 i .. 2 i + 1
-template <class F>
-void each_kmer(const uint8_t* seq, int64_t len, int k, F f) {
-  uint32_t code = 0;
-  int run = 0;   // letters of ACGT that end at the current base
-  for (int64_t e = 0; e < len; ++e) {
-    const int c = code_of(seq[e]);
-    if (c < 0) { run = 0; code = 0; continue; }
-    code = (code >> 2) | ((uint32_t)c << (2 * (k - 1)));
-    if (++run >= k) f(e - k + 1, code);
-  }
-}
-
-struct ReadKmer { uint32_t code; int32_t s, r; };
+using namespace wfa::hostk;
 struct Hit { int32_t s, j, d; };
 
 }  // namespace
@@ -86,38 +62,13 @@ extern "C" int wfa_hip_seeds_host(const uint8_t* read, int32_t read_len, int64_t
   for (int q = 0; q < n; ++q) { j[q] = -1; reverse[q] = 0; text_start[q] = 0; text_len[q] = 0; hits[q] = 0; }
   *overflow = 0;
   const int32_t L = read_len;
-  // the valid k-mers of both strands of the read, by code
+  // the valid k-mers of both strands of the read by code, the indexed positions that carry one of them, and the hits: every match of
+  // a k-mer that is not masked, once per entry of the read with that code
   std::vector<ReadKmer> rk;
-  std::vector<uint8_t> rc_read((size_t)L);
-  for (int32_t p = 0; p < L; ++p) rc_read[(size_t)p] = complement(read[L - 1 - p]);
-  each_kmer(read, L, k, [&](int64_t r, uint32_t code) { rk.push_back({code, 0, (int32_t)r}); });
-  each_kmer(rc_read.data(), L, k, [&](int64_t r, uint32_t code) { rk.push_back({code, 1, (int32_t)r}); });
-  if (rk.empty()) return WFA_HIP_OK;
-  std::sort(rk.begin(), rk.end(), [](const ReadKmer& a, const ReadKmer& b) { return a.code < b.code; });
-  std::vector<uint64_t> seen(1024, 0);   // the low 16 bits of the read's codes: most text positions stop here
-  for (const ReadKmer& x : rk) seen[(x.code & 0xFFFFu) >> 6] |= 1ull << (x.code & 63u);
-  // the indexed positions that carry one of the read's codes, and occ() of those codes over the whole set
-  struct Match { uint32_t first; int32_t j, t; };   // first: the first entry of rk with the code
+  std::vector<int64_t> occ;           // at the first entry of a code
   std::vector<Match> matches;
-  std::vector<int64_t> occ(rk.size(), 0);           // at the first entry of a code
-  const uint64_t* const seen_bits = seen.data();
-  for (int64_t jt = 0; jt < ntexts; ++jt)
-    each_kmer(texts + t_off[jt], t_len[jt], k, [&, seen_bits](int64_t t, uint32_t code) {
-      if (!((seen_bits[(code & 0xFFFFu) >> 6] >> (code & 63u)) & 1ull) || t % stride != 0) return;
-      const auto it = std::lower_bound(rk.begin(), rk.end(), code, [](const ReadKmer& a, uint32_t c) { return a.code < c; });
-      if (it == rk.end() || it->code != code) return;
-      const uint32_t first = (uint32_t)(it - rk.begin());
-      occ[first] += 1;
-      if (occ[first] <= max_occ) matches.push_back({first, (int32_t)jt, (int32_t)t});
-    });
-  // the hits: every match of a k-mer that is not masked, once per entry of the read with that code
-  int64_t H = 0;
-  for (size_t f = 0; f < rk.size(); ++f) {
-    if (occ[f] == 0 || occ[f] > max_occ) continue;
-    size_t e = f;
-    while (e < rk.size() && rk[e].code == rk[f].code) ++e;
-    H += occ[f] * (int64_t)(e - f);
-  }
+  const int64_t H = read_matches(read, L, ntexts, texts, t_off, t_len, k, stride, max_occ, rk, occ, matches);
+  if (rk.empty()) return WFA_HIP_OK;
   if (H > max_hits) { *overflow = 1; return WFA_HIP_OK; }
   std::vector<Hit> hit;
   for (const Match& m : matches) {

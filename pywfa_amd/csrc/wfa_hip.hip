@@ -42,6 +42,7 @@
 #include "wfa_summary.hpp"
 #include "wfa_pileup.hpp"
 #include "wfa_seed.hpp"
+#include "wfa_chain.hpp"
 #include "wfa_cross.hpp"
 
 #define WFA_HIP_ABI_VERSION 4
@@ -4749,10 +4750,13 @@ extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t sta
 // seed finder: a k-mer index over a text set, candidate windows per read (include/wfa_hip.h; csrc/wfa_seed.hpp, k_seed.hip)
 // ------------------------------------------------------------------------------------------------
 static_assert(WFA_SEED_MAX_N == WFA_HIP_SEED_MAX_N && WFA_SEED_MAX_HITS == WFA_HIP_SEED_MAX_HITS, "bounds of the kernels and of the ABI");
+static_assert(WFA_CHAIN_MAX_LOOKBACK == WFA_HIP_CHAIN_MAX_LOOKBACK && WFA_CHAIN_MAX_ANCHORS == WFA_HIP_CHAIN_MAX_ANCHORS, "bounds of the chain kernel and of the ABI");
 
 namespace wfa {   // host_seed.cpp: the parameter checks shared with wfa_hip_seeds_host
 int seed_check_index(int k, int stride, int max_occ, char* msg, size_t cap);
 int seed_check_query(int n, int min_hits, int gap, int pad, int max_hits, char* msg, size_t cap);
+// host_chain.cpp: the check shared with wfa_hip_chains_host
+int seed_check_chain(int n, int min_hits, int min_score, int lookback, int max_dist, int band, int pad, int max_anchors, char* msg, size_t cap);
 }
 
 struct wfa_hip_seed_index {
@@ -4764,6 +4768,9 @@ struct wfa_hip_seed_index {
   int32_t* d_len = nullptr;           // the texts' lengths
   int64_t positions = 0, masked = 0, table_bytes = 0;
   float build_ms = 0.f, query_ms = 0.f;
+  int32_t* d_chain_ws = nullptr;      // the chaining workspace: a slab per workgroup of the last launch (its own allocation, grown on demand)
+  size_t chain_ws_bytes = 0;
+  float chain_ms = 0.f;
 };
 
 // The letters outside ACGT of a set as the seed kernels read them: bit b of mask[w] = base 16 (w - woff) + b of the word's sequence,
@@ -4800,6 +4807,7 @@ extern "C" void wfa_hip_seed_index_destroy(wfa_hip_seed_index_t* x) {
   (void)hipSetDevice(al->device);
   if (x->d_table) (void)hipFree(x->d_table);
   if (x->d_recs) (void)hipFree(x->d_recs);
+  if (x->d_chain_ws) (void)hipFree(x->d_chain_ws);
   pool_release(al, x->d_len);
   delete x;
   aligner_release_ref(al);
@@ -4930,5 +4938,85 @@ extern "C" int wfa_hip_seed_index_stats(const wfa_hip_seed_index_t* x, int64_t* 
   if (table_bytes) *table_bytes = x->table_bytes;
   if (build_ms) *build_ms = x->build_ms;
   if (query_ms) *query_ms = x->query_ms;
+  return WFA_HIP_OK;
+}
+
+// chains: the anchors of every read chained along the read, the best chains as windows (include/wfa_hip.h "chains"; csrc/wfa_chain.hpp)
+extern "C" int wfa_hip_seed_index_chain(wfa_hip_seed_index_t* x, const wfa_hip_seqset_t* P, int n, int min_hits, int min_score, int lookback,
+                                        int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
+                                        int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
+                                        uint8_t* overflow) {
+  if (!x) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = x->al;
+  char buf[240];
+  if (!P || P->al != al) { al->err = "seed chain: sequence set of another aligner"; return WFA_HIP_EINVAL; }
+  if (wfa::seed_check_chain(n, min_hits, min_score, lookback, max_dist, band, pad, max_anchors, buf, sizeof(buf)) != WFA_HIP_OK) {
+    al->err = buf;
+    return WFA_HIP_EINVAL;
+  }
+  const int64_t m = P->n;
+  if (m == 0) return WFA_HIP_OK;
+  if (!j || !reverse || !text_start || !text_len || !hits || !score || !pattern_start || !pattern_len || !overflow) {
+    al->err = "seed chain: a result array is missing";
+    return WFA_HIP_EINVAL;
+  }
+  HIP_TRY(al, hipSetDevice(al->device));
+  if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);
+  const uint16_t* mask = nullptr;
+  if (seqset_mask(al, P, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
+  // the workspace: a slab of WFA_CHAIN_PLANES x max_anchors int32 per workgroup of this launch
+  const unsigned grid = wfa::chain_grid(m, al->cu_count);
+  const size_t ws_bytes = (size_t)grid * WFA_CHAIN_PLANES * (size_t)max_anchors * sizeof(int32_t);
+  if (ws_bytes > x->chain_ws_bytes) {
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    if (x->d_chain_ws) (void)hipFree(x->d_chain_ws);
+    x->d_chain_ws = nullptr;
+    x->chain_ws_bytes = 0;
+    if (hipMalloc((void**)&x->d_chain_ws, ws_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      x->d_chain_ws = nullptr;
+      snprintf(buf, sizeof(buf), "seed chain workspace: hipMalloc of %zu bytes failed (32 bytes x max_anchors = %d per workgroup, %u workgroups)",
+               ws_bytes, max_anchors, grid);
+      al->err = buf;
+      return WFA_HIP_EDEVICE;
+    }
+    x->chain_ws_bytes = ws_bytes;
+  }
+  CrossScratch sc{al};
+  const size_t cells = (size_t)m * (size_t)n;
+  int32_t* d_rows = nullptr;
+  uint8_t* d_over = nullptr;
+  if (sc.alloc(&d_rows, 8 * cells) || sc.alloc(&d_over, (size_t)m)) return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipEventCreate(&sc.ev[0]));
+  HIP_TRY(al, hipEventCreate(&sc.ev[1]));
+  wfa::ChainArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = seed_view(P, mask);
+  a.table = x->d_table; a.recs = x->d_recs; a.t_len = x->d_len; a.t_nseq = x->nseq;
+  a.k = x->k; a.max_occ = (uint32_t)x->max_occ;
+  a.n = n; a.min_hits = min_hits; a.min_score = min_score; a.lookback = lookback; a.max_dist = max_dist; a.band = band; a.pad = pad;
+  a.max_anchors = (uint32_t)max_anchors;
+  a.slab = x->d_chain_ws;
+  a.j = d_rows; a.reverse = d_rows + cells; a.text_start = d_rows + 2 * cells; a.text_len = d_rows + 3 * cells; a.hits = d_rows + 4 * cells;
+  a.score = d_rows + 5 * cells; a.pattern_start = d_rows + 6 * cells; a.pattern_len = d_rows + 7 * cells;
+  a.overflow = d_over;
+  HIP_TRY(al, hipEventRecord(sc.ev[0], al->stream));
+  const int lrc = wfa::launch_chain(a, m, grid, al->stream);
+  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
+  int32_t* host[8] = {j, reverse, text_start, text_len, hits, score, pattern_start, pattern_len};
+  for (int c = 0; c < 8; ++c)
+    HIP_TRY(al, hipMemcpyAsync(host[c], d_rows + (size_t)c * cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+  HIP_TRY(al, hipMemcpyAsync(overflow, d_over, (size_t)m, hipMemcpyDeviceToHost, al->stream));
+  const hipError_t e = hipStreamSynchronize(al->stream);
+  if (lrc != 0) { al->err = "seed chain kernel launch failed"; return WFA_HIP_EDEVICE; }
+  HIP_TRY(al, e);
+  HIP_TRY(al, hipEventElapsedTime(&x->chain_ms, sc.ev[0], sc.ev[1]));
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_seed_index_chain_stats(const wfa_hip_seed_index_t* x, float* kernel_ms, int64_t* workspace_bytes) {
+  if (!x) return WFA_HIP_EINVAL;
+  if (kernel_ms) *kernel_ms = x->chain_ms;
+  if (workspace_bytes) *workspace_bytes = (int64_t)x->chain_ws_bytes;
   return WFA_HIP_OK;
 }

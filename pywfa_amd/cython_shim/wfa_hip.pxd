@@ -41,3 +41,13 @@ cdef extern from "wfa_hip.h" nogil:
                             const int32_t* t_len, int k, int stride, int max_occ, int n, int min_hits, int gap, int pad, int max_hits,
                             int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow,
                             char* msg, size_t msg_cap)
+    int wfa_hip_seed_index_chain(wfa_hip_seed_index_t* index, const wfa_hip_seqset_t* patterns, int n, int min_hits, int min_score,
+                            int lookback, int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse,
+                            int32_t* text_start, int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start,
+                            int32_t* pattern_len, uint8_t* overflow)
+    int wfa_hip_seed_index_chain_stats(const wfa_hip_seed_index_t* index, float* kernel_ms, int64_t* workspace_bytes)
+    int wfa_hip_chains_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                            const int32_t* t_len, int k, int stride, int max_occ, int n, int min_hits, int min_score, int lookback,
+                            int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
+                            int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
+                            uint8_t* overflow, char* msg, size_t msg_cap)
