@@ -626,6 +626,57 @@ int wfa_hip_chains_host(const uint8_t* read, int32_t read_len, int64_t ntexts, c
                         int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
                         uint8_t* overflow, char* msg, size_t msg_cap);
 
+/* ---- minimizers: (w,k) sampling of the seed index, for seeds and chains alike ----------------------------- */
+
+/*
+ * A second way of thinning the index, beside `stride`: the text and the read are sampled by the same content-defined rule, so the read
+ * looks up only its own minimizers, the index holds about 2 / (w + 1) of the valid positions, and any exact match of at least
+ * w + k - 1 bases shares a sampled position on both sides.  Valid k-mers, the 2-bit codes, occ, max_occ, R_0 and R_1 are those of the
+ * seed finder above.
+ *
+ * Key of a position.  For a sequence of length len, key(p) = +inf when p < 0 or p + k > len, or when the k-mer at p is not valid.
+ * Otherwise key(p) = mix32(min(code, rc(code))): code the 2-bit code of the k-mer at p (base p + i in bits 2 i .. 2 i + 1), rc(code) the
+ * code of its reverse complement, and, on uint32_t,
+ *     mix32(h):  h ^= h >> 16;  h *= 0x85ebca6b;  h ^= h >> 13;  h *= 0xc2b2ae35;  h ^= h >> 16.
+ * mix32 is a bijection: two positions tie only when their canonical k-mers are equal.
+ * Selection.  p is a minimizer iff key(p) is finite and the maximal run of positions around p whose keys are >= key(p) (+inf counts as
+ * >=) is at least w long.  In counts: l = the number of consecutive positions p - 1, p - 2, ... with key >= key(p), r likewise for
+ * p + 1, p + 2, ..., each capped at w - 1; p is selected iff l + r + 1 >= w.  So every position that is a minimum of some window of w
+ * consecutive k-mer starts is selected, and every tie with it; windows that hang over a sequence end or over a letter outside ACGT
+ * count too (a short sequence still has minimizers); w = 1 selects every valid k-mer; and the rule is its own mirror image: the
+ * minimizers of the reverse complement are the mirrored positions len - k - p.
+ * Index (k in 8 .. 15, w in 1 .. WFA_HIP_MINIMIZER_MAX_W, max_occ >= 1).  Position (j, t) is indexed iff t is a minimizer of texts[j];
+ * it goes into the bucket of its forward code.  occ and the repeat mask are as above, counted over the indexed positions.
+ * Hits and anchors of a read.  As in the two sections above, but only from the read positions r of R_s that are minimizers of R_s.
+ * Everything behind that (sorting, clusters, chaining, selection, windows, overflow) is unchanged, for the seeds and for the chains.
+ *
+ * wfa_hip_seed_index_create_minimizer: as wfa_hip_seed_index_create, with w in place of stride (w out of range: NULL, WFA_HIP_EINVAL, w
+ * named with its value, nothing launched); the records take 8 BYTES PER INDEXED POSITION, allocated after the counting pass.  The
+ * index remembers w: wfa_hip_seed_index_query and wfa_hip_seed_index_chain apply the selection to the reads of such an index, and do
+ * exactly what they do for an index of wfa_hip_seed_index_create otherwise.
+ * wfa_hip_seed_index_params (any pointer may be NULL): k, and stride with w = 0 for a stride index, stride = 1 with w for a minimizer
+ * index.
+ */
+#define WFA_HIP_MINIMIZER_MAX_W 32
+wfa_hip_seed_index_t* wfa_hip_seed_index_create_minimizer(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* texts, int k, int w,
+                                                          int max_occ);
+int wfa_hip_seed_index_params(const wfa_hip_seed_index_t* index, int* k, int* stride, int* w);
+
+/* Host only, needs no GPU.  wfa_hip_minimizers_host: selected[p] = 1 for the minimizers of ONE ASCII sequence, 0 elsewhere (len bytes).
+ * wfa_hip_seeds_host_minimizer / wfa_hip_chains_host_minimizer: the rows of wfa_hip_seeds_host / wfa_hip_chains_host for a minimizer
+ * index, w in place of stride (one body each; only the predicate on text and read positions differs).  WFA_HIP_EINVAL as there, w named
+ * with its value. */
+int wfa_hip_minimizers_host(const uint8_t* seq, int64_t len, int k, int w, uint8_t* selected /* len bytes */, char* msg, size_t msg_cap);
+int wfa_hip_seeds_host_minimizer(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                                 const int32_t* t_len, int k, int w, int max_occ, int n, int min_hits, int gap, int pad, int max_hits,
+                                 int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow,
+                                 char* msg, size_t msg_cap);
+int wfa_hip_chains_host_minimizer(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                                  const int32_t* t_len, int k, int w, int max_occ, int n, int min_hits, int min_score, int lookback,
+                                  int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
+                                  int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
+                                  uint8_t* overflow, char* msg, size_t msg_cap);
+
 #ifdef __cplusplus
 }
 #endif

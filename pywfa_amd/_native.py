@@ -69,6 +69,8 @@ SYMBOLS = [
     "wfa_hip_seed_index_create", "wfa_hip_seed_index_destroy", "wfa_hip_seed_index_query", "wfa_hip_seed_index_stats",
     "wfa_hip_seeds_host",
     "wfa_hip_seed_index_chain", "wfa_hip_seed_index_chain_stats", "wfa_hip_chains_host",
+    "wfa_hip_seed_index_create_minimizer", "wfa_hip_seed_index_params", "wfa_hip_minimizers_host", "wfa_hip_seeds_host_minimizer",
+    "wfa_hip_chains_host_minimizer",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
@@ -79,6 +81,7 @@ PILEUP_COLUMNS = ("A", "C", "G", "T", "other", "del", "ins", "mismatch")
 SEED_MAX_N, SEED_MAX_HITS = 16, 4096
 SEED_KEYS = ("j", "reverse", "text_start", "text_len", "hits")   # the int32 arrays of a seed query, and overflow (uint8)
 CHAIN_MAX_LOOKBACK, CHAIN_MAX_ANCHORS = 64, 65536
+MINIMIZER_MAX_W = 32
 # the int32 arrays of a chain query, and overflow (uint8)
 CHAIN_KEYS = ("j", "reverse", "text_start", "text_len", "hits", "score", "pattern_start", "pattern_len")
 
@@ -187,6 +190,12 @@ def lib():
     L.wfa_hip_seed_index_chain.argtypes = [vp, vp] + [ctypes.c_int] * 8 + [vp] * 9
     L.wfa_hip_seed_index_chain_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
     L.wfa_hip_chains_host.argtypes = [vp, i32, i64, vp, vp, vp] + [ctypes.c_int] * 11 + [vp] * 9 + [ctypes.c_char_p, ctypes.c_size_t]
+    L.wfa_hip_seed_index_create_minimizer.argtypes = L.wfa_hip_seed_index_create.argtypes
+    L.wfa_hip_seed_index_create_minimizer.restype = vp
+    L.wfa_hip_seed_index_params.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int)] * 3
+    L.wfa_hip_minimizers_host.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_size_t]
+    L.wfa_hip_seeds_host_minimizer.argtypes = L.wfa_hip_seeds_host.argtypes
+    L.wfa_hip_chains_host_minimizer.argtypes = L.wfa_hip_chains_host.argtypes
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -437,9 +446,10 @@ class Aligner:
         """wfa_hip_pileup_create: a zeroed Pileup over the bases of a SeqSet."""
         return Pileup(self, texts)
 
-    def seed_index(self, texts, k=13, stride=1, max_occ=64):
-        """wfa_hip_seed_index_create: the k-mer index of a SeqSet (4^k * 4 bytes + 8 bytes per indexed position in HBM)."""
-        return SeedIndex(self, texts, k, stride, max_occ)
+    def seed_index(self, texts, k=13, stride=1, max_occ=64, w=None):
+        """wfa_hip_seed_index_create: the k-mer index of a SeqSet (4^k * 4 bytes + 8 bytes per indexed position in HBM).  ``w``:
+        wfa_hip_seed_index_create_minimizer instead, the (w,k)-minimizers of the texts (``stride`` plays no part)."""
+        return SeedIndex(self, texts, k, stride, max_occ, w)
 
     def cross(self, patterns, texts=None, want=CROSS_DENSE, k=None):
         """wfa_hip_cross_run of two SeqSets (texts None: all-vs-all of ``patterns``); wfa_hip_cross_run_k when ``k`` is given."""
@@ -498,10 +508,11 @@ def ops_pileup(ops, pattern, tlen, rows=None):
     return rows
 
 
-def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16, pad=16, max_hits=2048):
+def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16, pad=16, max_hits=2048, w=None):
     """wfa_hip_seeds_host (host only): the row ``SeedIndex.query`` holds for ONE read (bytes) against the texts (a list of bytes, or a
     blob dict(seqs=, off=, len=) made once for many reads): dict of int32[n] ``j`` / ``reverse`` / ``text_start`` / ``text_len`` /
-    ``hits`` and ``overflow`` (0 or 1).  ValueError (naming the parameter) for a parameter out of range."""
+    ``hits`` and ``overflow`` (0 or 1).  ``w``: wfa_hip_seeds_host_minimizer, the row under a minimizer index (``stride`` plays no
+    part).  ValueError (naming the parameter) for a parameter out of range."""
     read = np.frombuffer(bytes(read), dtype=np.uint8) if not isinstance(read, np.ndarray) else np.ascontiguousarray(read, dtype=np.uint8)
     if not isinstance(texts, dict):
         texts = seeds_host_texts(texts)
@@ -509,20 +520,22 @@ def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16,
     out = {key: np.zeros(rows, np.int32) for key in SEED_KEYS}
     over = np.zeros(1, np.uint8)
     msg = ctypes.create_string_buffer(256)
-    rc = lib().wfa_hip_seeds_host(_ptr(read) if read.size else None, read.size, texts["len"].shape[0], _ptr(texts["seqs"]),
-                                  _ptr(texts["off"]), _ptr(texts["len"]), k, stride, max_occ, n, min_hits, gap, pad, max_hits,
-                                  *[_ptr(out[key]) for key in SEED_KEYS], _ptr(over), msg, len(msg))
+    entry = lib().wfa_hip_seeds_host if w is None else lib().wfa_hip_seeds_host_minimizer
+    rc = entry(_ptr(read) if read.size else None, read.size, texts["len"].shape[0], _ptr(texts["seqs"]), _ptr(texts["off"]),
+               _ptr(texts["len"]), k, stride if w is None else w, max_occ, n, min_hits, gap, pad, max_hits,
+               *[_ptr(out[key]) for key in SEED_KEYS], _ptr(over), msg, len(msg))
     if rc != OK:
-        raise ValueError(f"wfa_hip_seeds_host: {msg.value.decode()}")
+        raise ValueError(f"{'wfa_hip_seeds_host' if w is None else 'wfa_hip_seeds_host_minimizer'}: {msg.value.decode()}")
     out["overflow"] = int(over[0])
     return out
 
 
 def chains_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=3, min_score=40, lookback=32, max_dist=5000, band=500, pad=64,
-                max_anchors=16384):
+                max_anchors=16384, w=None):
     """wfa_hip_chains_host (host only): the row ``SeedIndex.chain`` holds for ONE read (bytes) against the texts (a list of bytes, or
-    the blob of ``seeds_host_texts``): dict of int32[n] per key of ``CHAIN_KEYS`` and ``overflow`` (0 or 1).  ValueError (naming the
-    parameter) for a parameter out of range."""
+    the blob of ``seeds_host_texts``): dict of int32[n] per key of ``CHAIN_KEYS`` and ``overflow`` (0 or 1).  ``w``:
+    wfa_hip_chains_host_minimizer, the row under a minimizer index (``stride`` plays no part).  ValueError (naming the parameter) for
+    a parameter out of range."""
     read = np.frombuffer(bytes(read), dtype=np.uint8) if not isinstance(read, np.ndarray) else np.ascontiguousarray(read, dtype=np.uint8)
     if not isinstance(texts, dict):
         texts = seeds_host_texts(texts)
@@ -530,13 +543,26 @@ def chains_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=3, min_sc
     out = {key: np.zeros(rows, np.int32) for key in CHAIN_KEYS}
     over = np.zeros(1, np.uint8)
     msg = ctypes.create_string_buffer(256)
-    rc = lib().wfa_hip_chains_host(_ptr(read) if read.size else None, read.size, texts["len"].shape[0], _ptr(texts["seqs"]),
-                                   _ptr(texts["off"]), _ptr(texts["len"]), k, stride, max_occ, n, min_hits, min_score, lookback, max_dist,
-                                   band, pad, max_anchors, *[_ptr(out[key]) for key in CHAIN_KEYS], _ptr(over), msg, len(msg))
+    entry = lib().wfa_hip_chains_host if w is None else lib().wfa_hip_chains_host_minimizer
+    rc = entry(_ptr(read) if read.size else None, read.size, texts["len"].shape[0], _ptr(texts["seqs"]), _ptr(texts["off"]),
+               _ptr(texts["len"]), k, stride if w is None else w, max_occ, n, min_hits, min_score, lookback, max_dist, band, pad,
+               max_anchors, *[_ptr(out[key]) for key in CHAIN_KEYS], _ptr(over), msg, len(msg))
     if rc != OK:
-        raise ValueError(f"wfa_hip_chains_host: {msg.value.decode()}")
+        raise ValueError(f"{'wfa_hip_chains_host' if w is None else 'wfa_hip_chains_host_minimizer'}: {msg.value.decode()}")
     out["overflow"] = int(over[0])
     return out
+
+
+def minimizers_host(seq, k, w):
+    """wfa_hip_minimizers_host (host only): bool[len(seq)], True at the (w,k)-minimizers of ONE sequence (bytes).  ValueError (naming
+    the parameter) for ``k`` or ``w`` out of range."""
+    seq = np.frombuffer(bytes(seq), dtype=np.uint8) if not isinstance(seq, np.ndarray) else np.ascontiguousarray(seq, dtype=np.uint8)
+    flags = np.zeros(seq.size, np.uint8)
+    msg = ctypes.create_string_buffer(256)
+    rc = lib().wfa_hip_minimizers_host(_ptr(seq) if seq.size else None, seq.size, k, w, _ptr(flags) if seq.size else None, msg, len(msg))
+    if rc != OK:
+        raise ValueError(f"wfa_hip_minimizers_host: {msg.value.decode()}")
+    return flags.astype(bool)
 
 
 def seeds_host_texts(texts):
@@ -752,18 +778,33 @@ class SeedIndex:
     """An exact-match k-mer index over a text SeqSet, resident in HBM (wfa_hip_seed_index_t): 4^k * 4 bytes of table plus 8 bytes per
     indexed position.  Stays valid after the set is closed."""
 
-    def __init__(self, aligner, texts, k=13, stride=1, max_occ=64):
+    def __init__(self, aligner, texts, k=13, stride=1, max_occ=64, w=None):
         if not texts._h:
             raise ValueError("sequence set is closed")
         self.aligner = aligner
         self.n = texts.n
-        self._h = lib().wfa_hip_seed_index_create(aligner._h, texts._h, k, stride, max_occ)
+        if w is None:
+            name = "wfa_hip_seed_index_create"
+            self._h = lib().wfa_hip_seed_index_create(aligner._h, texts._h, k, stride, max_occ)
+        else:
+            name = "wfa_hip_seed_index_create_minimizer"
+            self._h = lib().wfa_hip_seed_index_create_minimizer(aligner._h, texts._h, k, w, max_occ)
         if not self._h:
             msg = aligner.error()
             if "failed" in msg:
-                raise NativeError(f"wfa_hip_seed_index_create: {msg}")
-            raise ValueError(f"wfa_hip_seed_index_create: {msg}")
+                raise NativeError(f"{name}: {msg}")
+            raise ValueError(f"{name}: {msg}")
         aligner._batches.add(self)
+
+    def params(self):
+        """wfa_hip_seed_index_params: dict(k=, stride=, w=); w = 0 for a stride index, stride = 1 for a minimizer index."""
+        if not self._h:
+            raise ValueError("seed index is closed")
+        k, stride, w = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        rc = lib().wfa_hip_seed_index_params(self._h, ctypes.byref(k), ctypes.byref(stride), ctypes.byref(w))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_seed_index_params")
+        return dict(k=k.value, stride=stride.value, w=w.value)
 
     def close(self):
         if getattr(self, "_h", None):

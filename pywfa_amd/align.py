@@ -443,6 +443,21 @@ class SeedIndex:
     def __len__(self):
         return self._open().n
 
+    @property
+    def k(self):
+        """The k-mer length of the index."""
+        return self._open().params()["k"]
+
+    @property
+    def w(self):
+        """The minimizer window of the index, ``None`` for a stride index."""
+        return self._open().params()["w"] or None
+
+    @property
+    def stride(self):
+        """The stride of the index (1 for a minimizer index)."""
+        return self._open().params()["stride"]
+
     def seeds(self, patterns, n=4, min_hits=2, gap=16, pad=16, max_hits=2048):
         """The ``n`` best clusters of exact k-mer hits of every read: dict of int32 arrays of shape (M, n) ``j`` (the text),
         ``reverse`` (1: the read's reverse complement matches), ``text_start`` / ``text_len`` (the window) and ``hits``, best
@@ -450,7 +465,9 @@ class SeedIndex:
         ``max_hits`` hits, which gets no seeds.  A cluster is a run of hits on one strand of one text whose diagonals
         (text position - read position) lie within ``gap`` of their neighbours; clusters below ``min_hits`` are dropped; the window
         spans the cluster's diagonals plus the read's length and ``pad`` on both sides, cut to the text.  ``patterns``: a list of
-        ``str`` or a ``SequenceSet``.  ``n``: 1 .. 16, ``max_hits``: 1 .. 4096."""
+        ``str`` or a ``SequenceSet``.  ``n``: 1 .. 16, ``max_hits``: 1 .. 4096.  Under a minimizer index (``seed_index(w=...)``) only
+        the read's own minimizers are looked up, so ``hits`` counts minimizers, about 2 / (w + 1) of what a dense index gives:
+        ``min_hits`` wants a lower value than for a dense index."""
         index = self._open()
         n = _seed_param("n", n, 1, _native.SEED_MAX_N)
         min_hits = _seed_param("min_hits", min_hits, 1)
@@ -482,7 +499,9 @@ class SeedIndex:
         ``band`` off its diagonal; chains below ``min_hits`` anchors or ``min_score`` are dropped, and a chain inside the window of a
         better one is not reported again (the rule: include/wfa_hip.h, "chains").  ``patterns``: a list of ``str`` or a
         ``SequenceSet``.  ``n``: 1 .. 16, ``lookback``: 1 .. 64, ``max_dist``: 1 .. 2^20, ``band``: 0 .. 2^16, ``max_anchors``:
-        1 .. 65536; the anchors take 32 bytes x ``max_anchors`` per resident workgroup of GPU memory, kept on the index."""
+        1 .. 65536; the anchors take 32 bytes x ``max_anchors`` per resident workgroup of GPU memory, kept on the index.  Under a
+        minimizer index (``seed_index(w=...)``) the anchors are minimizer matches, so ``hits`` and ``score`` count minimizers, about
+        2 / (w + 1) of a dense index's anchors: ``min_hits`` and ``min_score`` want lower values than for a dense index."""
         index = self._open()
         n = _seed_param("n", n, 1, _native.SEED_MAX_N)
         min_hits = _seed_param("min_hits", min_hits, 1)
@@ -782,15 +801,23 @@ class WavefrontAligner:
         self._sync_wildcard()
         return SequenceSet(self, self._seqset(seqs))
 
-    def seed_index(self, texts, k=13, stride=1, max_occ=64):
+    def seed_index(self, texts, k=13, stride=1, max_occ=64, w=None):
         """Index the k-mers of ``texts`` (a list of ``str`` or a ``SequenceSet``) on the GPU: a ``SeedIndex`` (``seeds()``,
         ``stats()``, ``close()``, context manager), the seed source of ``align_windows`` / ``pileup`` for reads without an index of
         your own.  Every position ``t`` with ``t % stride == 0`` whose ``k`` letters are all of ACGT is indexed; a k-mer that occurs
         more than ``max_occ`` times in the texts yields no hits (the repeat mask).  ``k``: 8 .. 15; the table takes 4^k * 4 bytes of
-        HBM (k = 13: 256 MiB, k = 15: 4 GiB) plus 8 bytes per indexed position.  With ``devices=[...]`` the first device holds it."""
+        HBM (k = 13: 256 MiB, k = 15: 4 GiB) plus 8 bytes per indexed position.  With ``devices=[...]`` the first device holds it.
+        ``w`` (1 .. 32; not together with a ``stride`` other than 1): a minimizer index instead.  The texts and the reads are sampled
+        by one rule, the (w,k)-minimizers under a hash of the canonical k-mer (include/wfa_hip.h, "minimizers"): about 2 / (w + 1) of
+        the positions are indexed, a read looks up only its own minimizers, and an exact match of w + k - 1 bases always shares one.
+        ``SeedIndex.k`` / ``.w`` / ``.stride`` tell which index it is."""
         k = _seed_param("k", k, 8, 15)
         stride = _seed_param("stride", stride, 1)
         max_occ = _seed_param("max_occ", max_occ, 1)
+        if w is not None:
+            w = _seed_param("w", w, 1, _native.MINIMIZER_MAX_W)
+            if stride != 1:
+                raise ValueError(f"w = {w} goes with stride = 1 only (a minimizer index has no stride), got stride = {stride}")
         for name, v in (("stride", stride), ("max_occ", max_occ)):
             if v >= 2**31:
                 raise ValueError(f"{name} = {v} does not fit 32 bits")
@@ -801,7 +828,7 @@ class WavefrontAligner:
         self._sync_wildcard()
         sets, mine = self._open_sets(texts, None)
         try:
-            return SeedIndex(self, self._native.seed_index(sets[0], k, stride, max_occ))
+            return SeedIndex(self, self._native.seed_index(sets[0], k, stride, max_occ, w))
         finally:
             for s in mine:
                 s.close()

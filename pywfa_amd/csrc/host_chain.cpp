@@ -11,6 +11,7 @@
 namespace wfa {
 
 int seed_check_index(int k, int stride, int max_occ, char* msg, size_t cap);   // host_seed.cpp
+int seed_check_minimizer(int k, int w, int max_occ, char* msg, size_t cap);
 
 static int refuse_chain(char* msg, size_t cap, const char* what, long long value, const char* want) {
   if (msg && cap) snprintf(msg, cap, "seed chain: %s = %lld is out of range (%s)", what, value, want);
@@ -46,15 +47,13 @@ inline int32_t gap_cost(int32_t g, int k) {
   return ((g * k) >> 6) + ((31 - __builtin_clz((uint32_t)g)) >> 1);
 }
 
-}  // namespace
-
-extern "C" int wfa_hip_chains_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
-                                   const int32_t* t_len, int k, int stride, int max_occ, int n, int min_hits, int min_score, int lookback,
-                                   int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
-                                   int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
-                                   uint8_t* overflow, char* msg, size_t msg_cap) {
+// the one body of wfa_hip_chains_host (w = 0: the stride index) and wfa_hip_chains_host_minimizer (w >= 1: stride plays no part)
+int chains_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off, const int32_t* t_len,
+                int k, int stride, int w, int max_occ, int n, int min_hits, int min_score, int lookback, int max_dist, int band, int pad,
+                int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, int32_t* score,
+                int32_t* pattern_start, int32_t* pattern_len, uint8_t* overflow, char* msg, size_t msg_cap) {
   if (msg && msg_cap) msg[0] = '\0';
-  int rc = wfa::seed_check_index(k, stride, max_occ, msg, msg_cap);
+  int rc = w ? wfa::seed_check_minimizer(k, w, max_occ, msg, msg_cap) : wfa::seed_check_index(k, stride, max_occ, msg, msg_cap);
   if (rc == WFA_HIP_OK) rc = wfa::seed_check_chain(n, min_hits, min_score, lookback, max_dist, band, pad, max_anchors, msg, msg_cap);
   if (rc != WFA_HIP_OK) return rc;
   if (read_len < 0 || ntexts < 0 || (read_len > 0 && !read) || (ntexts > 0 && (!t_off || !t_len)) || !j || !reverse || !text_start ||
@@ -75,7 +74,7 @@ extern "C" int wfa_hip_chains_host(const uint8_t* read, int32_t read_len, int64_
   std::vector<ReadKmer> rk;
   std::vector<int64_t> occ;
   std::vector<Match> matches;
-  const int64_t N = read_matches(read, L, ntexts, texts, t_off, t_len, k, stride, max_occ, rk, occ, matches);
+  const int64_t N = read_matches(read, L, ntexts, texts, t_off, t_len, k, stride, w, max_occ, rk, occ, matches);
   if (N > max_anchors) { *overflow = 1; return WFA_HIP_OK; }
   if (N == 0) return WFA_HIP_OK;
   // the anchors, in the order of a scan along the read: (s, r, j, t)
@@ -129,4 +128,27 @@ extern "C" int wfa_hip_chains_host(const uint8_t* read, int32_t read_len, int64_
       if (x.s == c.s && x.j == c.j && ts <= x.t && (int64_t)x.t + k <= te) x.covered = true;
   }
   return WFA_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int wfa_hip_chains_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                                   const int32_t* t_len, int k, int stride, int max_occ, int n, int min_hits, int min_score, int lookback,
+                                   int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
+                                   int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
+                                   uint8_t* overflow, char* msg, size_t msg_cap) {
+  return chains_host(read, read_len, ntexts, texts, t_off, t_len, k, stride, 0, max_occ, n, min_hits, min_score, lookback, max_dist, band,
+                     pad, max_anchors, j, reverse, text_start, text_len, hits, score, pattern_start, pattern_len, overflow, msg, msg_cap);
+}
+
+extern "C" int wfa_hip_chains_host_minimizer(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts,
+                                             const int64_t* t_off, const int32_t* t_len, int k, int w, int max_occ, int n, int min_hits,
+                                             int min_score, int lookback, int max_dist, int band, int pad, int max_anchors, int32_t* j,
+                                             int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, int32_t* score,
+                                             int32_t* pattern_start, int32_t* pattern_len, uint8_t* overflow, char* msg, size_t msg_cap) {
+  if (msg && msg_cap) msg[0] = '\0';
+  const int rc = wfa::seed_check_minimizer(k, w, max_occ, msg, msg_cap);   // (w = 0 is the body's word for the stride index: refused here)
+  if (rc != WFA_HIP_OK) return rc;
+  return chains_host(read, read_len, ntexts, texts, t_off, t_len, k, 1, w, max_occ, n, min_hits, min_score, lookback, max_dist, band, pad,
+                     max_anchors, j, reverse, text_start, text_len, hits, score, pattern_start, pattern_len, overflow, msg, msg_cap);
 }

@@ -23,6 +23,13 @@ int seed_check_index(int k, int stride, int max_occ, char* msg, size_t cap) {
   return WFA_HIP_OK;
 }
 
+int seed_check_minimizer(int k, int w, int max_occ, char* msg, size_t cap) {
+  if (k < 8 || k > 15) return refuse(msg, cap, "k", k, "8 .. 15");
+  if (w < 1 || w > WFA_HIP_MINIMIZER_MAX_W) return refuse(msg, cap, "w", w, "1 .. 32");
+  if (max_occ < 1) return refuse(msg, cap, "max_occ", max_occ, "at least 1");
+  return WFA_HIP_OK;
+}
+
 int seed_check_query(int n, int min_hits, int gap, int pad, int max_hits, char* msg, size_t cap) {
   if (n < 1 || n > WFA_HIP_SEED_MAX_N) return refuse(msg, cap, "n", n, "1 .. 16");
   if (min_hits < 1) return refuse(msg, cap, "min_hits", min_hits, "at least 1");
@@ -39,14 +46,12 @@ namespace {
 using namespace wfa::hostk;
 struct Hit { int32_t s, j, d; };
 
-}  // namespace
-
-extern "C" int wfa_hip_seeds_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
-                                  const int32_t* t_len, int k, int stride, int max_occ, int n, int min_hits, int gap, int pad,
-                                  int max_hits, int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits,
-                                  uint8_t* overflow, char* msg, size_t msg_cap) {
+// the one body of wfa_hip_seeds_host (w = 0: the stride index) and wfa_hip_seeds_host_minimizer (w >= 1: stride plays no part)
+int seeds_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off, const int32_t* t_len,
+               int k, int stride, int w, int max_occ, int n, int min_hits, int gap, int pad, int max_hits, int32_t* j, int32_t* reverse,
+               int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow, char* msg, size_t msg_cap) {
   if (msg && msg_cap) msg[0] = '\0';
-  int rc = wfa::seed_check_index(k, stride, max_occ, msg, msg_cap);
+  int rc = w ? wfa::seed_check_minimizer(k, w, max_occ, msg, msg_cap) : wfa::seed_check_index(k, stride, max_occ, msg, msg_cap);
   if (rc == WFA_HIP_OK) rc = wfa::seed_check_query(n, min_hits, gap, pad, max_hits, msg, msg_cap);
   if (rc != WFA_HIP_OK) return rc;
   if (read_len < 0 || ntexts < 0 || (read_len > 0 && !read) || (ntexts > 0 && (!t_off || !t_len)) || !j || !reverse || !text_start ||
@@ -67,7 +72,7 @@ extern "C" int wfa_hip_seeds_host(const uint8_t* read, int32_t read_len, int64_t
   std::vector<ReadKmer> rk;
   std::vector<int64_t> occ;           // at the first entry of a code
   std::vector<Match> matches;
-  const int64_t H = read_matches(read, L, ntexts, texts, t_off, t_len, k, stride, max_occ, rk, occ, matches);
+  const int64_t H = read_matches(read, L, ntexts, texts, t_off, t_len, k, stride, w, max_occ, rk, occ, matches);
   if (rk.empty()) return WFA_HIP_OK;
   if (H > max_hits) { *overflow = 1; return WFA_HIP_OK; }
   std::vector<Hit> hit;
@@ -93,5 +98,38 @@ extern "C" int wfa_hip_seeds_host(const uint8_t* read, int32_t read_len, int64_t
     const int64_t ts = std::max<int64_t>(0, (int64_t)c.d_lo - pad), te = std::min<int64_t>(t_len[c.j], (int64_t)c.d_hi + L + pad);
     j[q] = c.j; reverse[q] = c.s; text_start[q] = (int32_t)ts; text_len[q] = (int32_t)(te - ts); hits[q] = c.c;
   }
+  return WFA_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int wfa_hip_seeds_host(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                                  const int32_t* t_len, int k, int stride, int max_occ, int n, int min_hits, int gap, int pad,
+                                  int max_hits, int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits,
+                                  uint8_t* overflow, char* msg, size_t msg_cap) {
+  return seeds_host(read, read_len, ntexts, texts, t_off, t_len, k, stride, 0, max_occ, n, min_hits, gap, pad, max_hits, j, reverse,
+                    text_start, text_len, hits, overflow, msg, msg_cap);
+}
+
+extern "C" int wfa_hip_seeds_host_minimizer(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                                            const int32_t* t_len, int k, int w, int max_occ, int n, int min_hits, int gap, int pad,
+                                            int max_hits, int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len,
+                                            int32_t* hits, uint8_t* overflow, char* msg, size_t msg_cap) {
+  if (msg && msg_cap) msg[0] = '\0';
+  const int rc = wfa::seed_check_minimizer(k, w, max_occ, msg, msg_cap);   // (w = 0 is the body's word for the stride index: refused here)
+  if (rc != WFA_HIP_OK) return rc;
+  return seeds_host(read, read_len, ntexts, texts, t_off, t_len, k, 1, w, max_occ, n, min_hits, gap, pad, max_hits, j, reverse,
+                    text_start, text_len, hits, overflow, msg, msg_cap);
+}
+
+extern "C" int wfa_hip_minimizers_host(const uint8_t* seq, int64_t len, int k, int w, uint8_t* selected, char* msg, size_t msg_cap) {
+  if (msg && msg_cap) msg[0] = '\0';
+  const int rc = wfa::seed_check_minimizer(k, w, 1, msg, msg_cap);
+  if (rc != WFA_HIP_OK) return rc;
+  if (len < 0 || (len > 0 && (!seq || !selected))) {
+    if (msg && msg_cap) snprintf(msg, msg_cap, "minimizers: a negative length or a missing array");
+    return WFA_HIP_EINVAL;
+  }
+  minimizer_flags(seq, len, k, w, selected);
   return WFA_HIP_OK;
 }

@@ -58,6 +58,7 @@ __device__ inline void chain_place(const SeedRec* recs, uint32_t first, uint32_t
   }
 }
 
+template <bool MINI>   // MINI: the index is a minimizer index (a.w >= 1), only the read's minimizers give anchors
 __global__ void __launch_bounds__(256) wfa_chain_kernel(ChainArgs a, int64_t npat) {
   __shared__ uint32_t s_red[4];
   __shared__ uint64_t s_red64[4];
@@ -78,7 +79,7 @@ __global__ void __launch_bounds__(256) wfa_chain_kernel(ChainArgs a, int64_t npa
     uint32_t c0 = 0, c1 = 0;
     for (int32_t q = q0; q < q1; ++q) {
       uint32_t code, first;
-      if (!seed_kmer(a.p, w0, q, k, &code)) continue;
+      if (!seed_read_kmer<MINI>(a.p, w0, L, q, k, a.w, &code)) continue;
       c0 = min(c0 + min(chain_occ(a, code, &first), WFA_CHAIN_SAT), WFA_CHAIN_SAT);
       c1 = min(c1 + min(chain_occ(a, seed_rc(code, k), &first), WFA_CHAIN_SAT), WFA_CHAIN_SAT);
     }
@@ -90,18 +91,19 @@ __global__ void __launch_bounds__(256) wfa_chain_kernel(ChainArgs a, int64_t npa
     if (t == 0) a.overflow[i] = overflow ? 1 : 0;
     int slot = 0;
     if (!overflow && N > 0) {
-      // 2. gather: strand 0 up the range; strand 1 down it (r = L - k - q), its place counted from the far end of the read
+      // 2. gather: strand 0 up the range; strand 1 down it (r = L - k - q), its place counted from the far end of the read (under
+      // a minimizer index from the same positions q: the minimizers of the reverse complement are the mirrored positions)
       uint32_t p0 = e0, p1 = N0 + (N1 - (e1 + c1));
       for (int32_t q = q0; q < q1; ++q) {
         uint32_t code, first;
-        if (!seed_kmer(a.p, w0, q, k, &code)) continue;
+        if (!seed_read_kmer<MINI>(a.p, w0, L, q, k, a.w, &code)) continue;
         const uint32_t cnt = chain_occ(a, code, &first);
         chain_place(a.recs, first, cnt, p0, q, cap, aj, at, ar);
         p0 += cnt;
       }
       for (int32_t q = q1 - 1; q >= q0; --q) {
         uint32_t code, first;
-        if (!seed_kmer(a.p, w0, q, k, &code)) continue;
+        if (!seed_read_kmer<MINI>(a.p, w0, L, q, k, a.w, &code)) continue;
         const uint32_t cnt = chain_occ(a, seed_rc(code, k), &first);
         chain_place(a.recs, first, cnt, p1, L - k - q, cap, aj, at, ar);
         p1 += cnt;
@@ -184,9 +186,10 @@ unsigned chain_grid(int64_t npat, int cu_count) {
 int launch_chain(const ChainArgs& a, int64_t npat, unsigned grid, hipStream_t stream) {
   if (npat <= 0) return 0;
   if (a.k < WFA_SEED_MIN_K || a.k > WFA_SEED_MAX_K || a.n < 1 || a.n > WFA_SEED_MAX_N || a.lookback < 1 || a.lookback > WFA_CHAIN_MAX_LOOKBACK ||
-      a.max_anchors < 1 || a.max_anchors > WFA_CHAIN_MAX_ANCHORS || !a.slab || grid < 1)
+      a.max_anchors < 1 || a.max_anchors > WFA_CHAIN_MAX_ANCHORS || !a.slab || grid < 1 || a.w < 0 || a.w > WFA_SEED_MAX_W)
     return -1;
-  hipLaunchKernelGGL(wfa_chain_kernel, dim3(grid), dim3(256), 0, stream, a, npat);
+  if (a.w >= 1) hipLaunchKernelGGL(wfa_chain_kernel<true>, dim3(grid), dim3(256), 0, stream, a, npat);
+  else hipLaunchKernelGGL(wfa_chain_kernel<false>, dim3(grid), dim3(256), 0, stream, a, npat);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -43,6 +43,33 @@ __global__ void __launch_bounds__(256) wfa_seed_positions_kernel(SeedBuildArgs a
   }
 }
 
+// the minimizer form: the same thread per word, the same stores; a position is taken when it is a minimizer of ITS sequence (keys and
+// neighbours from the owner's first word and length: beyond its last k-mer start the neighbours are +inf, whatever word follows).
+// Count and fill run the one predicate on the same words, so they select identically.
+template <bool FILL>
+__global__ void __launch_bounds__(256) wfa_seed_minimizer_positions_kernel(SeedBuildArgs a, uint32_t cap) {
+  const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < a.t.nwords; g += nthreads) {
+    const int64_t j = seed_owner(a.t, (uint32_t)g);
+    if (j < 0) continue;
+    const uint32_t w0 = a.t.woff[j];
+    const int32_t len = a.t.len[j], p0 = 16 * (int32_t)((uint32_t)g - w0);
+    for (int u = 0; u < 16; ++u) {
+      const int32_t p = p0 + u;
+      if (p + a.k > len) break;
+      uint32_t code;
+      const uint64_t kp = seed_key(a.t, w0, len, p, a.k, &code);
+      if (kp == WFA_SEED_KEY_INF || !seed_selected(a.t, w0, len, p, a.k, a.w, kp)) continue;
+      if (!FILL) {
+        atomicAdd(&a.table[code], 1u);
+      } else {
+        const uint32_t slot = atomicSub(&a.table[code], 1u) - 1u;
+        if (slot < cap) { SeedRec r; r.j = (int32_t)j; r.t = p; a.recs[slot] = r; }
+      }
+    }
+  }
+}
+
 // chunk sums of the table's counters, and the k-mers over max_occ
 __global__ void __launch_bounds__(256) wfa_seed_scan_reduce_kernel(SeedBuildArgs a, uint64_t count) {
   __shared__ uint32_t s_red[4];
@@ -96,7 +123,8 @@ static unsigned positions_grid(uint64_t nwords) { return (unsigned)std::max<uint
 
 int launch_seed_count(const SeedBuildArgs& a, hipStream_t stream) {
   if (a.t.nwords == 0) return 0;
-  hipLaunchKernelGGL(wfa_seed_positions_kernel<false>, dim3(positions_grid(a.t.nwords)), dim3(256), 0, stream, a, 0u);
+  if (a.w >= 1) hipLaunchKernelGGL(wfa_seed_minimizer_positions_kernel<false>, dim3(positions_grid(a.t.nwords)), dim3(256), 0, stream, a, 0u);
+  else hipLaunchKernelGGL(wfa_seed_positions_kernel<false>, dim3(positions_grid(a.t.nwords)), dim3(256), 0, stream, a, 0u);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -111,7 +139,8 @@ int launch_seed_scan(const SeedBuildArgs& a, hipStream_t stream) {
 
 int launch_seed_fill(const SeedBuildArgs& a, uint32_t cap, hipStream_t stream) {
   if (a.t.nwords == 0 || cap == 0) return 0;
-  hipLaunchKernelGGL(wfa_seed_positions_kernel<true>, dim3(positions_grid(a.t.nwords)), dim3(256), 0, stream, a, cap);
+  if (a.w >= 1) hipLaunchKernelGGL(wfa_seed_minimizer_positions_kernel<true>, dim3(positions_grid(a.t.nwords)), dim3(256), 0, stream, a, cap);
+  else hipLaunchKernelGGL(wfa_seed_positions_kernel<true>, dim3(positions_grid(a.t.nwords)), dim3(256), 0, stream, a, cap);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -125,6 +154,7 @@ __device__ inline uint32_t seed_occ(const SeedQueryArgs& a, uint32_t code, uint3
   return cnt > a.max_occ ? 0u : cnt;
 }
 
+template <bool MINI>   // MINI: the index is a minimizer index (a.w >= 1), only the read's minimizers are looked up
 __global__ void __launch_bounds__(256) wfa_seed_query_kernel(SeedQueryArgs a, int64_t npat) {
   __shared__ uint64_t s_key[WFA_SEED_MAX_HITS];
   __shared__ uint16_t s_seg[2][WFA_SEED_MAX_HITS];
@@ -139,7 +169,7 @@ __global__ void __launch_bounds__(256) wfa_seed_query_kernel(SeedQueryArgs a, in
     uint32_t mine = 0;
     for (int32_t q = t; q < npos; q += 256) {
       uint32_t code, first;
-      if (!seed_kmer(a.p, w0, q, k, &code)) continue;
+      if (!seed_read_kmer<MINI>(a.p, w0, L, q, k, a.w, &code)) continue;
       mine = min(mine + min(seed_occ(a, code, &first), WFA_SEED_SAT), WFA_SEED_SAT);
       mine = min(mine + min(seed_occ(a, seed_rc(code, k), &first), WFA_SEED_SAT), WFA_SEED_SAT);
     }
@@ -152,7 +182,7 @@ __global__ void __launch_bounds__(256) wfa_seed_query_kernel(SeedQueryArgs a, in
       // 2. the hits as keys: strand | text | d biased to unsigned, so that the keys' order is the order of (s, j, d)
       for (int32_t q = t; q < npos; q += 256) {
         uint32_t code;
-        if (!seed_kmer(a.p, w0, q, k, &code)) continue;
+        if (!seed_read_kmer<MINI>(a.p, w0, L, q, k, a.w, &code)) continue;
         for (int s = 0; s < 2; ++s) {
           uint32_t first;
           const uint32_t cnt = seed_occ(a, s ? seed_rc(code, k) : code, &first);
@@ -238,9 +268,12 @@ __global__ void __launch_bounds__(256) wfa_seed_query_kernel(SeedQueryArgs a, in
 
 int launch_seed_query(const SeedQueryArgs& a, int64_t npat, int cu_count, hipStream_t stream) {
   if (npat <= 0) return 0;
-  if (a.k < WFA_SEED_MIN_K || a.k > WFA_SEED_MAX_K || a.n < 1 || a.n > WFA_SEED_MAX_N || a.max_hits < 1 || a.max_hits > WFA_SEED_MAX_HITS) return -1;
+  if (a.k < WFA_SEED_MIN_K || a.k > WFA_SEED_MAX_K || a.n < 1 || a.n > WFA_SEED_MAX_N || a.max_hits < 1 || a.max_hits > WFA_SEED_MAX_HITS || a.w < 0 ||
+      a.w > WFA_SEED_MAX_W)
+    return -1;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(npat, (int64_t)cu_count * 12));
-  hipLaunchKernelGGL(wfa_seed_query_kernel, dim3(grid), dim3(256), 0, stream, a, npat);
+  if (a.w >= 1) hipLaunchKernelGGL(wfa_seed_query_kernel<true>, dim3(grid), dim3(256), 0, stream, a, npat);
+  else hipLaunchKernelGGL(wfa_seed_query_kernel<false>, dim3(grid), dim3(256), 0, stream, a, npat);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

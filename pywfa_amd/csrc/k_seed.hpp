@@ -22,6 +22,41 @@ __device__ inline bool seed_kmer(const SeedSetView& s, uint32_t w0, int32_t p, i
   return (m & ((1u << k) - 1u)) == 0u;
 }
 
+// ---- minimizers (include/wfa_hip.h, "minimizers"; the choice of recomputing keys: wfa_seed.hpp) ----------------------------------------
+
+#define WFA_SEED_KEY_INF (~0ull)   // above every mix32 value
+
+__device__ inline uint32_t seed_mix32(uint32_t h) {
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  return h;
+}
+
+// key(p) of the sequence of length len whose first word is w0: mix32 of the canonical code, +inf outside the sequence (p < 0 or
+// p + k > len: no word is read) or over a masked letter; *code: the forward code of a finite key
+__device__ inline uint64_t seed_key(const SeedSetView& s, uint32_t w0, int32_t len, int32_t p, int k, uint32_t* code) {
+  if (p < 0 || p + k > len || !seed_kmer(s, w0, p, k, code)) return WFA_SEED_KEY_INF;
+  return seed_mix32(min(*code, seed_rc(*code, k)));
+}
+
+// whether position p with the finite key kp is a (w,k)-minimizer of its sequence: l / r neighbours with key >= kp on either side,
+// each capped at w - 1, l + r + 1 >= w.  The neighbours' keys are recomputed from the sequence's own words; the walk to the right
+// stops as soon as the sum is reached.
+__device__ inline bool seed_selected(const SeedSetView& s, uint32_t w0, int32_t len, int32_t p, int k, int w, uint64_t kp) {
+  uint32_t c;
+  int run = 1;   // l + r + 1
+  for (int l = 1; l < w && seed_key(s, w0, len, p - l, k, &c) >= kp; ++l) ++run;
+  for (int r = 1; r < w && run < w && seed_key(s, w0, len, p + r, k, &c) >= kp; ++r) ++run;
+  return run >= w;
+}
+
+// the k-mer at p as the query kernels take it: valid and, under a minimizer index (w >= 1), a minimizer of the read
+template <bool MINI>
+__device__ inline bool seed_read_kmer(const SeedSetView& s, uint32_t w0, int32_t len, int32_t p, int k, int w, uint32_t* code) {
+  if (!MINI) return seed_kmer(s, w0, p, k, code);
+  const uint64_t kp = seed_key(s, w0, len, p, k, code);
+  return kp != WFA_SEED_KEY_INF && seed_selected(s, w0, len, p, k, w, kp);
+}
+
 __device__ inline uint32_t seed_wave_sum(uint32_t v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);

@@ -39,6 +39,7 @@ struct ChainArgs {
   SeedSetView p;
   const uint32_t* table; const SeedRec* recs; const int32_t* t_len; int64_t t_nseq;
   int k;
+  int w;                    // of the index: 0, or the minimizer window (wfa_seed.hpp)
   uint32_t max_occ;
   int n, min_hits, min_score, lookback, max_dist, band;
   int32_t pad;

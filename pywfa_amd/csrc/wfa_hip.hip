@@ -4750,10 +4750,12 @@ extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t sta
 // seed finder: a k-mer index over a text set, candidate windows per read (include/wfa_hip.h; csrc/wfa_seed.hpp, k_seed.hip)
 // ------------------------------------------------------------------------------------------------
 static_assert(WFA_SEED_MAX_N == WFA_HIP_SEED_MAX_N && WFA_SEED_MAX_HITS == WFA_HIP_SEED_MAX_HITS, "bounds of the kernels and of the ABI");
+static_assert(WFA_SEED_MAX_W == WFA_HIP_MINIMIZER_MAX_W, "bounds of the minimizer kernels and of the ABI");
 static_assert(WFA_CHAIN_MAX_LOOKBACK == WFA_HIP_CHAIN_MAX_LOOKBACK && WFA_CHAIN_MAX_ANCHORS == WFA_HIP_CHAIN_MAX_ANCHORS, "bounds of the chain kernel and of the ABI");
 
 namespace wfa {   // host_seed.cpp: the parameter checks shared with wfa_hip_seeds_host
 int seed_check_index(int k, int stride, int max_occ, char* msg, size_t cap);
+int seed_check_minimizer(int k, int w, int max_occ, char* msg, size_t cap);
 int seed_check_query(int n, int min_hits, int gap, int pad, int max_hits, char* msg, size_t cap);
 // host_chain.cpp: the check shared with wfa_hip_chains_host
 int seed_check_chain(int n, int min_hits, int min_score, int lookback, int max_dist, int band, int pad, int max_anchors, char* msg, size_t cap);
@@ -4762,6 +4764,7 @@ int seed_check_chain(int n, int min_hits, int min_score, int lookback, int max_d
 struct wfa_hip_seed_index {
   wfa_hip_aligner* al = nullptr;
   int k = 0, stride = 0, max_occ = 0;
+  int w = 0;                          // 0: a stride index; 1 .. 32: a minimizer index (stride = 1)
   int64_t nseq = 0;
   uint32_t* d_table = nullptr;        // 4^k + 1 bucket starts (its own allocation: 4^k * 4 bytes)
   wfa::SeedRec* d_recs = nullptr;     // {j, t} per indexed position, in bucket order (its own allocation)
@@ -4828,14 +4831,16 @@ static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wf
     al->err = buf;
     return WFA_HIP_EDEVICE;
   }
-  if (hipMalloc((void**)&x->d_recs, rec_bytes) != hipSuccess) {
+  const auto alloc_recs = [&](size_t bytes, uint64_t positions) {
+    if (hipMalloc((void**)&x->d_recs, bytes) == hipSuccess) return true;
     (void)hipGetLastError();
     x->d_recs = nullptr;
-    snprintf(buf, sizeof(buf), "seed index records: hipMalloc of %zu bytes failed (8 bytes per indexed position, %llu positions)", rec_bytes,
-             (unsigned long long)cap);
+    snprintf(buf, sizeof(buf), "seed index records: hipMalloc of %zu bytes failed (8 bytes per indexed position, %llu positions)", bytes,
+             (unsigned long long)positions);
     al->err = buf;
-    return WFA_HIP_EDEVICE;
-  }
+    return false;
+  };
+  if (x->w == 0 && !alloc_recs(rec_bytes, cap)) return WFA_HIP_EDEVICE;   // (a minimizer index: after the counting pass, by its total)
   x->table_bytes = (int64_t)(table_bytes + rec_bytes);
   const uint16_t* mask = nullptr;
   if (seqset_mask(al, T, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
@@ -4849,15 +4854,25 @@ static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wf
   wfa::SeedBuildArgs a;
   memset(&a, 0, sizeof(a));
   a.t = seed_view(T, mask);
-  a.k = x->k; a.stride = x->stride; a.max_occ = (uint32_t)x->max_occ;
+  a.k = x->k; a.stride = x->stride; a.w = x->w; a.max_occ = (uint32_t)x->max_occ;
   a.table = x->d_table; a.recs = x->d_recs; a.bsum = d_bsum; a.masked = d_masked;
   HIP_TRY(al, hipEventRecord(sc.ev[0], al->stream));
   HIP_TRY(al, hipMemsetAsync(x->d_table, 0, table_bytes, al->stream));
   HIP_TRY(al, hipMemsetAsync(d_masked, 0, sizeof(uint32_t), al->stream));
-  const int lrc = wfa::launch_seed_count(a, al->stream) | wfa::launch_seed_scan(a, al->stream) |
-                  wfa::launch_seed_fill(a, (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull), al->stream);
-  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
+  int lrc = wfa::launch_seed_count(a, al->stream) | wfa::launch_seed_scan(a, al->stream);
   uint32_t total = 0, masked = 0;
+  if (x->w >= 1 && lrc == 0) {
+    // the records by the count: the scan has left the total behind the last bucket
+    HIP_TRY(al, hipMemcpyAsync(&total, x->d_table + buckets, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    cap = total;
+    const size_t bytes = (size_t)std::max<uint64_t>(cap, 1) * sizeof(wfa::SeedRec);
+    if (!alloc_recs(bytes, cap)) return WFA_HIP_EDEVICE;
+    x->table_bytes = (int64_t)(table_bytes + bytes);
+    a.recs = x->d_recs;
+  }
+  lrc |= wfa::launch_seed_fill(a, (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull), al->stream);
+  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
   HIP_TRY(al, hipMemcpyAsync(&total, x->d_table + buckets, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
   HIP_TRY(al, hipMemcpyAsync(&masked, d_masked, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
   const hipError_t e = hipStreamSynchronize(al->stream);
@@ -4868,11 +4883,13 @@ static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wf
   return WFA_HIP_OK;
 }
 
-extern "C" wfa_hip_seed_index_t* wfa_hip_seed_index_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int stride, int max_occ) {
+// the one body of both creates; minimizer: w is the window and stride plays no part, otherwise w = 0
+static wfa_hip_seed_index_t* seed_index_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int stride, int w, int max_occ, bool minimizer) {
   if (!al) { g_error = "null aligner"; return nullptr; }
   char buf[200];
   if (!texts || texts->al != al) { al->err = "seed index: sequence set of another aligner"; g_error = al->err; return nullptr; }
-  if (wfa::seed_check_index(k, stride, max_occ, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; g_error = al->err; return nullptr; }
+  const int crc = minimizer ? wfa::seed_check_minimizer(k, w, max_occ, buf, sizeof(buf)) : wfa::seed_check_index(k, stride, max_occ, buf, sizeof(buf));
+  if (crc != WFA_HIP_OK) { al->err = buf; g_error = al->err; return nullptr; }
   if (texts->n == 0) { al->err = "seed index: texts = a set of 0 sequences is out of range (at least 1)"; g_error = al->err; return nullptr; }
   if (texts->nbytes >= (1ll << 31)) {
     snprintf(buf, sizeof(buf), "seed index: texts = a set of %lld bases is out of range (below 2^31: split the set)", (long long)texts->nbytes);
@@ -4881,10 +4898,26 @@ extern "C" wfa_hip_seed_index_t* wfa_hip_seed_index_create(wfa_hip_aligner_t* al
   if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
   if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);   // (the resident one-pair kernel: the build takes the device)
   wfa_hip_seed_index* x = new wfa_hip_seed_index();
-  x->al = al; x->k = k; x->stride = stride; x->max_occ = max_occ;
+  x->al = al; x->k = k; x->stride = stride; x->w = w; x->max_occ = max_occ;
   al->live_batches += 1;
   if (seed_index_build(al, x, texts) != WFA_HIP_OK) { g_error = al->err; wfa_hip_seed_index_destroy(x); return nullptr; }
   return x;
+}
+
+extern "C" wfa_hip_seed_index_t* wfa_hip_seed_index_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int stride, int max_occ) {
+  return seed_index_create(al, texts, k, stride, 0, max_occ, false);
+}
+
+extern "C" wfa_hip_seed_index_t* wfa_hip_seed_index_create_minimizer(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int w, int max_occ) {
+  return seed_index_create(al, texts, k, 1, w, max_occ, true);
+}
+
+extern "C" int wfa_hip_seed_index_params(const wfa_hip_seed_index_t* x, int* k, int* stride, int* w) {
+  if (!x) return WFA_HIP_EINVAL;
+  if (k) *k = x->k;
+  if (stride) *stride = x->stride;
+  if (w) *w = x->w;
+  return WFA_HIP_OK;
 }
 
 extern "C" int wfa_hip_seed_index_query(wfa_hip_seed_index_t* x, const wfa_hip_seqset_t* P, int n, int min_hits, int gap, int pad, int max_hits,
@@ -4912,7 +4945,7 @@ extern "C" int wfa_hip_seed_index_query(wfa_hip_seed_index_t* x, const wfa_hip_s
   memset(&a, 0, sizeof(a));
   a.p = seed_view(P, mask);
   a.table = x->d_table; a.recs = x->d_recs; a.t_len = x->d_len; a.t_nseq = x->nseq;
-  a.k = x->k; a.max_occ = (uint32_t)x->max_occ;
+  a.k = x->k; a.w = x->w; a.max_occ = (uint32_t)x->max_occ;
   a.n = n; a.min_hits = min_hits; a.max_hits = max_hits; a.gap = (uint32_t)gap; a.pad = pad;
   a.j = d_rows; a.reverse = d_rows + cells; a.text_start = d_rows + 2 * cells; a.text_len = d_rows + 3 * cells; a.hits = d_rows + 4 * cells;
   a.overflow = d_over;
@@ -4993,7 +5026,7 @@ extern "C" int wfa_hip_seed_index_chain(wfa_hip_seed_index_t* x, const wfa_hip_s
   memset(&a, 0, sizeof(a));
   a.p = seed_view(P, mask);
   a.table = x->d_table; a.recs = x->d_recs; a.t_len = x->d_len; a.t_nseq = x->nseq;
-  a.k = x->k; a.max_occ = (uint32_t)x->max_occ;
+  a.k = x->k; a.w = x->w; a.max_occ = (uint32_t)x->max_occ;
   a.n = n; a.min_hits = min_hits; a.min_score = min_score; a.lookback = lookback; a.max_dist = max_dist; a.band = band; a.pad = pad;
   a.max_anchors = (uint32_t)max_anchors;
   a.slab = x->d_chain_ws;

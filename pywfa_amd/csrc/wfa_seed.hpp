@@ -31,6 +31,20 @@
 //       bitonic sort of the next power of two, cluster starts carried to every hit by a max-scan in LDS (two uint16 planes), and up
 //       to n rounds of a workgroup-wide minimum over the cluster ends' rank keys.  LDS: 32 KB of keys + 16 KB of scan planes.
 //       Every store goes to row i of the M x n result arrays or to overflow[i]; the gather checks its LDS slot against the capacity.
+//
+// Minimizers (include/wfa_hip.h, "minimizers"; w >= 1 in the argument blocks below, w = 0: the stride index, whose kernels and code
+// paths are the ones above, untouched).  The table, the scan and the records are the same; only WHICH positions enter differs:
+//   wfa_seed_minimizer_positions_kernel<FILL>      the sibling of the positions kernel, a thread per word of the text set again: of
+//       its 16 positions it takes those that are minimizers of the owning sequence.
+//   wfa_seed_query_kernel<true>, wfa_chain_kernel<true>   the same kernels with the read's positions filtered the same way (<false>
+//       is the code as it was).
+// The selection RECOMPUTES the neighbours' keys from the sequence's own words (k_seed.hpp: seed_key, seed_selected) in all three
+// kernels, instead of staging a tile of keys in LDS: a key is two cached word reads, a funnel shift, a bit reversal and five
+// multiply/xor steps; the walk stops at the first smaller key, which for hashed keys comes after about ln w steps on either side (at
+// most 2 (w - 1) keys for a position inside a run of ties or beside a sequence end); and a neighbour is addressed by (first word,
+// length) of ITS sequence, so a workgroup's tile edge, a short sequence inside a tile and the counting pass versus the gather pass are
+// not cases: every pass evaluates one predicate on the same words.  The query kernel keeps its 48 KB of LDS as they were and no
+// kernel gains an array, so none needs scratch (the resource figures: DESIGN.md §6.4).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +53,7 @@ namespace wfa {
 
 #define WFA_SEED_MIN_K 8
 #define WFA_SEED_MAX_K 15
+#define WFA_SEED_MAX_W 32
 #define WFA_SEED_MAX_N 16
 #define WFA_SEED_MAX_HITS 4096      // the LDS key array of the query kernel
 #define WFA_SEED_SCAN_CHUNK 4096    // counters per workgroup of the table scan (256 threads x 16)
@@ -58,6 +73,7 @@ struct SeedSetView {
 struct SeedBuildArgs {
   SeedSetView t;
   int k, stride;
+  int w;                    // 0: the stride index; 1 .. WFA_SEED_MAX_W: the minimizer index (stride plays no part)
   uint32_t max_occ;
   uint32_t* table;          // [4^k + 1]
   SeedRec* recs;            // [total]
@@ -69,6 +85,7 @@ struct SeedQueryArgs {
   SeedSetView p;
   const uint32_t* table; const SeedRec* recs; const int32_t* t_len; int64_t t_nseq;
   int k;
+  int w;                    // of the index: 0, or the minimizer window
   uint32_t max_occ;
   int n, min_hits, max_hits;
   uint32_t gap;

@@ -51,3 +51,17 @@ cdef extern from "wfa_hip.h" nogil:
                             int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
                             int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
                             uint8_t* overflow, char* msg, size_t msg_cap)
+    # minimizers (include/wfa_hip.h: "minimizers")
+    wfa_hip_seed_index_t* wfa_hip_seed_index_create_minimizer(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* texts, int k, int w,
+                            int max_occ)
+    int wfa_hip_seed_index_params(const wfa_hip_seed_index_t* index, int* k, int* stride, int* w)
+    int wfa_hip_minimizers_host(const uint8_t* seq, int64_t len, int k, int w, uint8_t* selected, char* msg, size_t msg_cap)
+    int wfa_hip_seeds_host_minimizer(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                            const int32_t* t_len, int k, int w, int max_occ, int n, int min_hits, int gap, int pad, int max_hits,
+                            int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow,
+                            char* msg, size_t msg_cap)
+    int wfa_hip_chains_host_minimizer(const uint8_t* read, int32_t read_len, int64_t ntexts, const uint8_t* texts, const int64_t* t_off,
+                            const int32_t* t_len, int k, int w, int max_occ, int n, int min_hits, int min_score, int lookback,
+                            int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
+                            int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
+                            uint8_t* overflow, char* msg, size_t msg_cap)
