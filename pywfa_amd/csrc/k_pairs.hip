@@ -1,4 +1,4 @@
-// k_pairs.hip — the generator of an indexed batch (wfa_cross.hpp: PairsGenArgs; wfa_hip_batch_create_indexed in wfa_hip.hip).
+// k_pairs.hip — the generator of an indexed batch (wfa_cross.hpp: PairsGenArgs, filled by IndexedPairs::generate for batch_build_list in wfa_hip.hip).
 // A workgroup takes WFA_PAIRS_CHUNK listed pairs per round, in two steps:
 //  1. thread t = pair t of the chunk: its indices, the sets' tables (lengths, word / byte offsets, flags), the words its slot needs; an
 //     exclusive prefix sum of those over the chunk (wave shuffles, the four wave totals through LDS) on top of the chunk's base gives

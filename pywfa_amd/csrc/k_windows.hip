@@ -1,4 +1,4 @@
-// k_windows.hip — the generator of a windowed batch (wfa_cross.hpp: WindowsGenArgs; wfa_hip_batch_create_windows in wfa_hip.hip).
+// k_windows.hip — the generator of a windowed batch (wfa_cross.hpp: WindowsGenArgs, filled by WindowPairs::generate for batch_build_list in wfa_hip.hip).
 // The shape of k_pairs.hip: a workgroup takes WFA_PAIRS_CHUNK listed pairs per round, in two steps:
 //  1. thread t = pair t of the chunk: its indices, windows and strand, the words and (a byte pair) the bytes its slots need; two
 //     exclusive prefix sums over the chunk (wave shuffles, the four wave totals through LDS) on top of the chunk's bases place the word

@@ -89,7 +89,7 @@ struct CrossTopkArgs {
 // Indexed batches (wfa_hip_batch_create_indexed): pair q of a list is (patterns[i[q]], texts[j[q]]).  The layout is the explicit batch's
 // (wfa_hip.hip batch_build): the slots of the pairs of up to WFA_FAST_MAX_LEN bases stand back to back in list order, each as long as
 // its pair needs (pattern words, text words right behind); a longer pair points into the batch's copy of the sets' words.  The host
-// knows every slot's place from the sets' lengths; it sends one word offset per WFA_PAIRS_CHUNK pairs (chunk_base), and the chunk's
+// (wfa_hip.hip: batch_build_list over IndexedPairs) knows every slot's place from the sets' lengths; it sends one word offset per WFA_PAIRS_CHUNK pairs (chunk_base), and the chunk's
 // workgroup finds its pairs' slots with a prefix sum over their word counts.  Kernel in k_pairs.hip.
 #define WFA_PAIRS_CHUNK 256   // pairs per workgroup round (256 threads: one pair each for the metadata, then groups of lanes over words)
 
@@ -118,7 +118,7 @@ int launch_pairs_gen(const PairsGenArgs& a, int cu_count, hipStream_t stream);
 // of texts[j[q]].  A window starts at any base, so nothing of a set can be used in place: EVERY pair gets a word slot, whatever its
 // length (the explicit batch's layout: pattern words, text words right behind, slots back to back in list order), re-based to bit 0 of
 // its first word, and a pair aligned on its bytes also gets a byte slot holding the two materialised windows (each rounded up to whole
-// 32-bit words, zero behind the window).  The batch owns the slots and nothing else of the sets.  The host sends one word offset and
+// 32-bit words, zero behind the window).  The batch owns the slots and nothing else of the sets.  The host (wfa_hip.hip: batch_build_list over WindowPairs) sends one word offset and
 // one byte offset per WFA_PAIRS_CHUNK pairs; the chunk's workgroup places its pairs' slots with two prefix sums.  Kernel in
 // k_windows.hip; wfa_window_word below is the gather of one slot word, shared with the host statement of it (wfa_hip_window_2bit).
 #define WFA_WIN_REVERSE 1   // opt[q]: the pattern window is reverse-complemented

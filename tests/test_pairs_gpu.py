@@ -257,6 +257,76 @@ def test_size(gpu):
         al.close()
 
 
+def multipart_list():
+    """A list long enough for two host parts of the list planner (it splits a list over host threads once every part gets 65536
+    pairs, and the parts meet on a multiple of 256, the generator's chunk): 2 * 65536 + 300 pairs, the 300 leaving a partial last
+    chunk, over 300 reads of 32-64 bases in families of five.  Two reads of 600-700 bases are too long for a word slot: listed in
+    both parts, they put the sets' words in front of the slots.  Two reads hold an N: about 1 % of the pairs are byte pairs, and
+    one sits at the part boundary, on either side of it and at the end of the list.  Returns the reads, the list and the boundary."""
+    n = 2 * 65536 + 300
+    edge = (n // 2) & ~255
+    short, _ = family_reads(61, 60, 5, 32, 64)
+    longs, _ = family_reads(62, 1, 2, 600, 700, div=0.02)
+    wild = [short[0][:20] + "N" + short[0][20:], short[1][:9] + "N" + short[1][10:]]
+    reads = short + longs + wild
+    m, lg, wd = len(short), len(short), len(short) + 2
+    rng = np.random.default_rng(63)
+    i = rng.integers(0, m, n)
+    j = np.where(rng.random(n) < 0.85, i // 5 * 5 + rng.integers(0, 5, n), rng.integers(0, m, n))
+    for q in np.flatnonzero(rng.random(n) < 0.01):          # a byte pair: an N-holding read on either side, or on both
+        kind = q % 3
+        i[q], j[q] = (wd + q % 2, j[q]) if kind == 0 else (i[q], wd + q % 2) if kind == 1 else (wd, wd + 1)
+    for base in (0, edge):                                   # the long reads, in each part
+        for k, (a, b) in enumerate(((lg, lg + 1), (lg + 1, lg), (lg, 3), (4, lg + 1), (lg + 1, lg + 1))):
+            i[base + 40 + 9001 * k], j[base + 40 + 9001 * k] = a, b
+    for q, (a, b) in zip((edge - 1, edge, edge + 1, n - 1), ((wd, wd + 1), (wd + 1, wd), (0, wd), (wd + 1, 6))):
+        i[q], j[q] = a, b
+    return reads, i.astype(np.int64), j.astype(np.int32), edge
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scope", ["score", "full"])
+def test_multipart_list(gpu, scope):
+    """Two host parts: what each part writes from its own base (the op-region prefix, the two work lists, the chunk bases behind
+    the sets' words) against the oracle, pair for pair."""
+    reads, i, j, edge = multipart_list()
+    n = len(i)
+    assert n == 2 * 65536 + 300 and n // 65536 >= 2 and edge % 256 == 0 and n % 256 != 0
+    length = np.array([len(s) for s in reads])
+    dirty = np.array(["N" in s for s in reads])
+    too_long = (length[i] > 512) | (length[j] > 512)         # (512: the longest sequence that still gets a word slot)
+    byte_pair = dirty[i] | dirty[j]
+    assert (length > 512).sum() == 2 and 600 <= length[length > 512].min() and length.max() <= 700
+    assert 3 <= too_long[:edge].sum() <= 10 and 3 <= too_long[edge:].sum() <= 10
+    assert 0.005 * n < byte_pair.sum() < 0.02 * n and byte_pair[:edge].any() and byte_pair[edge:].any()
+    assert all(byte_pair[q] for q in (edge - 1, edge, edge + 1, n - 1))
+    kw = dict(span="end-to-end", scope=scope)
+    o, batch = oracle_pairs(kw, reads, None, i, j)
+    # through the C ABI binding: first the two pairs that go wrong when a part's base is off, by name, then every pair
+    full = scope == "full"
+    _, nc = configs_pair(**kw)
+    al = _native.Aligner(nc)
+    try:
+        ps = native_set(al, reads)
+        rb = al.batch_indexed(ps, None, i, j)
+        rb.run()
+        rb.sync()
+        score, status, cig = rb.results(full)
+        routed = rb.last_kernel()[1]
+        rb.close()
+        ps.close()
+    finally:
+        al.close()
+    for q, what in ((edge - 1, "last pair of the first part"), (edge, "first pair of the second part"), (n - 1, "last pair of the list")):
+        assert (score[q], status[q]) == (o["score"][q], o["status"][q]), (what, q)
+        if full:
+            ops, cbeg, clen = cig
+            assert rle(ops[cbeg[q]:cbeg[q] + clen[q]].tobytes()) == rle(o["cigars"][q]), (what, q)
+    assert_same(o, score, status, cigars_of(cig, n) if full else None, batch, ("two parts", scope, "C ABI"))
+    assert routed == n - byte_pair.sum(), ("two parts", "2-bit pairs", routed)
+    check_both(kw, reads, None, i, j, ("two parts", scope))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("scope", ["score", "full"])
 def test_lifetime_and_reuse(gpu, scope):

@@ -446,6 +446,80 @@ def test_lifetime_and_reuse(gpu, scope):
         wa.align_windows(R, G, i=[0], j=[0])
 
 
+def multipart_list():
+    """A list long enough for two host parts of the list planner (it splits a list over host threads once every part gets 65536
+    pairs, and the parts meet on a multiple of 256, the generator's chunk): 2 * 65536 + 300 windows of 20-40 bases, the 300 leaving
+    a partial last chunk.  Texts are three references of a few thousand bases, the last with five single Ns; patterns are copies
+    of them with 3 % substitutions (same coordinates) and the reverse complements of those copies, so that a reversed pair is as
+    related as a forward one.  About 1 % of the pairs are reversed, about 1 % are byte pairs (their text window covers an N), and a
+    pair that is both sits at the part boundary, on either side of it and at the end of the list.
+    Returns the pattern set, the text set, the list and the boundary position."""
+    n = 2 * 65536 + 300
+    edge = (n // 2) & ~255
+    rng = np.random.default_rng(21)
+    bases = [rng.integers(0, 4, m) for m in (3000, 4100, 5003)]
+    lens = np.array([len(b) for b in bases])
+    n_at = (700, 1733, 2500, 3301, 4250)
+    texts = [LETTERS[b] for b in bases]
+    texts[2][list(n_at)] = "N"
+    texts = ["".join(t) for t in texts]
+    copies = ["".join(LETTERS[np.where(rng.random(len(b)) < 0.03, rng.integers(0, 4, len(b)), b)]) for b in bases]
+    pats = copies + [revcomp(s) for s in copies]
+    r = rng.integers(0, 3, n)
+    pl, tl = rng.integers(20, 41, n), rng.integers(20, 41, n)
+    ts = 3 + (rng.random(n) * (lens[r] - 46)).astype(np.int64)
+    ps = ts + rng.integers(-3, 4, n)
+    rev = rng.random(n) < 0.01
+    for k, q in enumerate((edge - 1, edge, edge + 1, n - 1)):
+        r[q], ts[q], tl[q], ps[q], pl[q], rev[q] = 2, n_at[k] - 10 - k, 30 + k, n_at[k] - 9, 27 + k, True
+    W = dict(i=np.where(rev, 3 + r, r).astype(np.int64), j=r.astype(np.int32),
+             p_start=np.where(rev, lens[r] - (ps + pl), ps).astype(np.int32), p_len=pl.astype(np.int64),
+             t_start=ts.astype(np.int64), t_len=tl.astype(np.int32), reverse=rev.astype(np.uint8))
+    return pats, texts, W, edge
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scope", ["score", "full"])
+def test_multipart_list(gpu, scope):
+    """Two host parts: what each part writes from its own base (the op-region prefix, the two work lists, the chunk bases of the
+    word and byte slots) against the oracle, pair for pair."""
+    pats, texts, W, edge = multipart_list()
+    n = len(W["i"])
+    assert n == 2 * 65536 + 300 and n // 65536 >= 2 and edge % 256 == 0 and n % 256 != 0
+    kw = dict(span="end-to-end", scope=scope)
+    o, batch, clean = oracle_windows(kw, pats, texts, W)
+    dirty = np.array(["N" in texts[W["j"][q]][W["t_start"][q]:W["t_start"][q] + W["t_len"][q]] for q in range(n)])
+    assert n - clean == dirty.sum() and 0.005 * n < dirty.sum() < 0.02 * n and 0.005 * n < W["reverse"].sum() < 0.02 * n
+    assert ((W["j"] == 2) & ~dirty).sum() > 10000, "windows of the N-holding reference that avoid the Ns"
+    spots = (edge - 1, edge, edge + 1, n - 1)
+    assert all(dirty[q] and W["reverse"][q] for q in spots)
+    assert dirty[:edge].any() and not dirty[:edge].all() and (W["reverse"][:edge] == 1).any() and (W["reverse"][edge:] == 1).any()
+    # through the C ABI binding: first the two pairs that go wrong when a part's base is off, by name, then every pair
+    full = scope == "full"
+    _, nc = configs_pair(**kw)
+    al = _native.Aligner(nc)
+    try:
+        ps, ts = native_set(al, pats), native_set(al, texts)
+        rb = native_windows(al, ps, ts, W)
+        rb.run()
+        rb.sync()
+        score, status, cig = rb.results(full)
+        routed = rb.last_kernel()[1]
+        rb.close()
+        ps.close()
+        ts.close()
+    finally:
+        al.close()
+    for q, what in ((edge - 1, "last pair of the first part"), (edge, "first pair of the second part"), (n - 1, "last pair of the list")):
+        assert (score[q], status[q]) == (o["score"][q], o["status"][q]), (what, q)
+        if full:
+            ops, cbeg, clen = cig
+            assert rle(ops[cbeg[q]:cbeg[q] + clen[q]].tobytes()) == rle(o["cigars"][q]), (what, q)
+    assert_same(o, score, status, cigars_of(cig, n) if full else None, batch, ("two parts", scope, "C ABI"))
+    assert routed == clean, ("two parts", "2-bit pairs", routed, clean)
+    check_python(kw, pats, texts, W, o, batch, ("two parts", scope))
+
+
 @pytest.mark.gpu
 def test_refusals(gpu):
     kw = dict(span="end-to-end", scope="full")
