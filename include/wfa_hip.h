@@ -516,6 +516,59 @@ void wfa_hip_pileup_destroy(wfa_hip_pileup_t* pileup);
 int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen,
                        int32_t* rows /* tlen x 8, added to */);
 
+/* ---- calls and sites: two reductions of a pileup against its reference set -------------------------------- */
+
+/*
+ * What a caller wants from a pileup is rarely the table: it is one byte per base (the consensus call) or the few rows where the reads
+ * disagree with the reference.  Both are computed on the device from the table and the reference letters; 1 byte per base, or 32 bytes
+ * per SITE, cross PCIe instead of 32 bytes per base.  Integers only.
+ *
+ * For base g of text j take the counters c0..c7 (the columns of WFA_HIP_PILEUP_COLS) and the reference byte b of that base:
+ *   r     = col(b): 'A' 0, 'C' 1, 'G' 2, 'T' 3, every other byte 4 (lower case, N, a wildcard byte) — the mapping the pileup applies to
+ *           read letters
+ *   depth = c0 + ... + c5, summed in 64 bits (the site row holds its low 32 bits: counters are not checked for overflow)
+ *
+ * CALL (one byte per base), parameter min_depth >= 1.
+ *   low 3 bits: 6 ("no call") when depth < min_depth; otherwise the column x in 0..5 with the greatest c[x]; among equal greatest
+ *               columns r if it is one of them, else the smallest x.  So 0..3 are a base, 4 another letter, 5 "deleted here".
+ *   bit 3 (8):  set when depth >= min_depth and 2 * c6 > depth: most covering reads insert in front of this base.
+ *
+ * SITE, parameters min_depth >= 1 and min_permille in 1..1000.  A base is considered only when depth >= min_depth.
+ *   alt  = the column in 0..5 other than r with the greatest count, the smallest on a tie; A = c[alt]
+ *   snv  = A >= 1 && 1000 * A >= min_permille * depth            (64-bit products)
+ *   ins  = c6 >= 1 && 1000 * c6 >= min_permille * depth
+ * The base is a site iff snv || ins.  Its row is WFA_HIP_SITE_COLS int32:
+ *   j, pos, ref = r, alt (-1 when !snv), depth, ref_count = c[r], alt_count (A; 0 when !snv), ins_count = c6
+ * Sites come out in ascending (j, pos), always: the order does not depend on scheduling, two calls give identical rows.
+ *
+ * Out of scope: the pileup does not record WHICH bases were inserted, so a site says that, and how often, reads insert in front of a
+ * base, not what they insert (align those few reads with CIGARs); quality values, strand bias, genotypes and multi-base events.
+ *
+ * The pileup keeps no reference letters and outlives its set, so both device calls take the set: the one the pileup was made over, or
+ * one made again from the same sequences.  wfa_hip_pileup_calls writes out[0 .. len) for the rows [start, start + len) of sequence
+ * seq.  wfa_hip_pileup_sites sets *count to the number of sites in the range (always the full number) and writes the first
+ * min(*count, cap) rows (cap x 8 int32, row-major; rows behind them are not touched); cap = 0 with rows = NULL is the counting call;
+ * seq = -1 takes every sequence, with start = 0 and len = -1.  Both wait for the aligner's stream, as wfa_hip_pileup_read does; len = 0
+ * is fine.  Kernels: csrc/wfa_calls.hpp, k_calls.hip (calls: a thread per base; sites: count per chunk of bases, exclusive scan of
+ * the chunk counts, scatter — no atomics; the chunk is WFA_HIP_CALLS_CHUNK bases, read per call).
+ * WFA_HIP_EINVAL, nothing launched, nothing written (wfa_hip_last_error names the values): a set of another aligner; a set whose
+ * number of sequences or any length differs from the pileup's (the first differing sequence and both lengths are named); a range that
+ * leaves its sequence; min_depth < 1; min_permille outside 1..1000; cap < 0; a NULL `out` with len > 0, a NULL `count`, NULL `rows`
+ * with cap > 0; seq = -1 with another start or len.
+ */
+#define WFA_HIP_SITE_COLS 8   /* j, pos, ref, alt, depth, ref_count, alt_count, ins_count */
+int wfa_hip_pileup_calls(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                         int32_t min_depth, uint8_t* out /* len */);
+int wfa_hip_pileup_sites(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                         int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows /* cap x 8, nullable */);
+
+/* Host only, needs no GPU: the same two rules on `len` rows as wfa_hip_pileup_read returns them (counts: len x 8, row-major) and the
+ * reference bytes ref[0 .. len) of those rows.  wfa_hip_sites_host numbers its rows j = seq, pos = start + row.  Returns WFA_HIP_OK,
+ * or WFA_HIP_EINVAL (nothing written) on a negative len, a parameter out of range (as above) or a missing pointer. */
+int wfa_hip_calls_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t min_depth, uint8_t* out);
+int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t seq, int64_t start,
+                       int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows);
+
 /* ---- seed finder: an exact-match k-mer index over a text set, candidate windows for every read ------------ */
 
 /*

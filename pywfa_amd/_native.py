@@ -71,6 +71,7 @@ SYMBOLS = [
     "wfa_hip_seed_index_chain", "wfa_hip_seed_index_chain_stats", "wfa_hip_chains_host",
     "wfa_hip_seed_index_create_minimizer", "wfa_hip_seed_index_params", "wfa_hip_minimizers_host", "wfa_hip_seeds_host_minimizer",
     "wfa_hip_chains_host_minimizer",
+    "wfa_hip_pileup_calls", "wfa_hip_pileup_sites", "wfa_hip_calls_host", "wfa_hip_sites_host",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
@@ -78,6 +79,10 @@ CROSS_MAX_K = 64
 SUMMARY_COLS = 10   # M, X, I, D, I runs, D runs, pattern_start, pattern_end, text_start, text_end
 PILEUP_COLS = 8
 PILEUP_COLUMNS = ("A", "C", "G", "T", "other", "del", "ins", "mismatch")
+CALL_CODES = ("A", "C", "G", "T", "other", "del", "no call")   # the low 3 bits of a call byte; CALL_INS: its insertion flag
+CALL_NONE, CALL_INS = 6, 8
+SITE_COLS = 8
+SITE_COLUMNS = ("j", "pos", "ref", "alt", "depth", "ref_count", "alt_count", "ins_count")
 SEED_MAX_N, SEED_MAX_HITS = 16, 4096
 SEED_KEYS = ("j", "reverse", "text_start", "text_len", "hits")   # the int32 arrays of a seed query, and overflow (uint8)
 CHAIN_MAX_LOOKBACK, CHAIN_MAX_ANCHORS = 64, 65536
@@ -196,6 +201,10 @@ def lib():
     L.wfa_hip_minimizers_host.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_size_t]
     L.wfa_hip_seeds_host_minimizer.argtypes = L.wfa_hip_seeds_host.argtypes
     L.wfa_hip_chains_host_minimizer.argtypes = L.wfa_hip_chains_host.argtypes
+    L.wfa_hip_pileup_calls.argtypes = [vp, vp, i32, i64, i64, i32, vp]
+    L.wfa_hip_pileup_sites.argtypes = [vp, vp, i32, i64, i64, i32, i32, i64, ctypes.POINTER(i64), vp]
+    L.wfa_hip_calls_host.argtypes = [vp, vp, i64, i32, vp]
+    L.wfa_hip_sites_host.argtypes = [vp, vp, i64, i32, i64, i32, i32, i64, ctypes.POINTER(i64), vp]
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -508,6 +517,43 @@ def ops_pileup(ops, pattern, tlen, rows=None):
     return rows
 
 
+def _calls_rows(counts, ref):
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    ref = np.frombuffer(bytes(ref), dtype=np.uint8) if not isinstance(ref, np.ndarray) else np.ascontiguousarray(ref, dtype=np.uint8)
+    if counts.ndim != 2 or counts.shape[1] != PILEUP_COLS or ref.shape != (counts.shape[0],):
+        raise ValueError("counts: int32 of shape (len, 8); ref: one byte per row")
+    return counts, ref
+
+
+def calls_host(counts, ref, min_depth=1):
+    """wfa_hip_calls_host (host only): the call bytes ``Pileup.calls`` gives for the rows ``counts`` (int32, shape (len, 8), as
+    ``Pileup.read`` returns them) over the reference bytes ``ref``: uint8[len]."""
+    counts, ref = _calls_rows(counts, ref)
+    out = np.zeros(counts.shape[0], np.uint8)
+    rc = lib().wfa_hip_calls_host(_ptr(counts) if counts.size else None, _ptr(ref) if ref.size else None, counts.shape[0], int(min_depth),
+                                  _ptr(out) if out.size else None)
+    if rc != OK:
+        raise ValueError(f"wfa_hip_calls_host: invalid arguments (min_depth = {min_depth})")
+    return out
+
+
+def sites_host(counts, ref, seq=0, start=0, min_depth=1, min_permille=500, cap=None):
+    """wfa_hip_sites_host (host only): ``(count, rows)`` of the sites among the rows ``counts`` over the reference bytes ``ref``, numbered
+    j = seq, pos = start + row; rows: int32 of shape (min(count, cap), 8), every site when ``cap`` is None (a counting call first)."""
+    counts, ref = _calls_rows(counts, ref)
+    n = counts.shape[0]
+    args = (_ptr(counts) if counts.size else None, _ptr(ref) if ref.size else None, n, int(seq), int(start), int(min_depth), int(min_permille))
+    count = ctypes.c_int64(0)
+    if cap is None:
+        if lib().wfa_hip_sites_host(*args, 0, ctypes.byref(count), None) != OK:
+            raise ValueError(f"wfa_hip_sites_host: invalid arguments (min_depth = {min_depth}, min_permille = {min_permille})")
+        cap = count.value
+    rows = np.zeros((max(int(cap), 0), SITE_COLS), np.int32)
+    if lib().wfa_hip_sites_host(*args, int(cap), ctypes.byref(count), _ptr(rows) if rows.size else None) != OK:
+        raise ValueError(f"wfa_hip_sites_host: invalid arguments (min_depth = {min_depth}, min_permille = {min_permille}, cap = {cap})")
+    return count.value, rows[:min(count.value, rows.shape[0])]
+
+
 def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16, pad=16, max_hits=2048, w=None):
     """wfa_hip_seeds_host (host only): the row ``SeedIndex.query`` holds for ONE read (bytes) against the texts (a list of bytes, or a
     blob dict(seqs=, off=, len=) made once for many reads): dict of int32[n] ``j`` / ``reverse`` / ``text_start`` / ``text_len`` /
@@ -767,6 +813,38 @@ class Pileup:
         if rc != OK:
             self.aligner._raise(rc, "wfa_hip_pileup_read")
         return out
+
+    def calls(self, texts, seq, start=0, length=None, min_depth=1):
+        """wfa_hip_pileup_calls: uint8[length], the call bytes of the rows [start, start + length) of one sequence (to its end when
+        None) against the letters of the SeqSet ``texts``."""
+        seq, start = int(seq), int(start)
+        if length is None:
+            if not 0 <= seq < self.n:
+                raise ValueError(f"sequence {seq} is out of range for a set of {self.n}")
+            length = int(self.length[seq]) - start
+        length = int(length)
+        out = np.zeros(max(length, 0), np.uint8)
+        rc = lib().wfa_hip_pileup_calls(self._h, texts._h, seq, start, length, int(min_depth), _ptr(out) if out.size else None)
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_pileup_calls")
+        return out
+
+    def sites(self, texts, seq=-1, start=0, length=-1, min_depth=1, min_permille=500, cap=None):
+        """wfa_hip_pileup_sites: ``(count, rows)``, rows int32 of shape (min(count, cap), 8) in ascending (j, pos); ``cap`` None: a
+        counting call, then one with the exact capacity.  seq = -1: every sequence."""
+        args = (self._h, texts._h, int(seq), int(start), int(length), int(min_depth), int(min_permille))
+        count = ctypes.c_int64(0)
+        if cap is None:
+            rc = lib().wfa_hip_pileup_sites(*args, 0, ctypes.byref(count), None)
+            if rc != OK:
+                self.aligner._raise(rc, "wfa_hip_pileup_sites")
+            cap = count.value
+        rows = np.zeros((max(int(cap), 0), SITE_COLS), np.int32)
+        if cap != 0:
+            rc = lib().wfa_hip_pileup_sites(*args, int(cap), ctypes.byref(count), _ptr(rows) if rows.size else None)
+            if rc != OK:
+                self.aligner._raise(rc, "wfa_hip_pileup_sites")
+        return count.value, rows[:min(count.value, rows.shape[0])]
 
     def clear(self):
         rc = lib().wfa_hip_pileup_clear(self._h)

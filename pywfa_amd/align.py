@@ -337,19 +337,26 @@ def _need_full_for_summary(cfg):
         raise ValueError("summary=True needs scope='full'")
 
 
+_CALL_LETTERS = np.frombuffer(b"ACGTN-N", np.uint8)   # (CALL_CODES as letters; deleted bases are dropped before the lookup)
+
+
 class Pileup:
     """Per-base counts over the text sequences, kept on the GPU (``WavefrontAligner.pileup``).  ``score`` / ``status``: the listed
     pairs' results, in list order.  ``counts(j)``: int32 rows of the columns ``COLUMNS`` for text ``j`` — reads whose aligned base is
     A, C, G, T or another letter, reads that delete the base, reads that insert in front of it, reads that mismatch (these are also
     under their letter).  ``depth(j)``: the reads whose aligned core covers each base.  Counters are int32 and not checked for
-    overflow; the table takes 32 bytes per text base until ``close()`` (or the end of the ``with`` block)."""
+    overflow; the table takes 32 bytes per text base until ``close()`` (or the end of the ``with`` block).  ``calls`` / ``consensus`` /
+    ``sites`` reduce the table on the GPU against the reference letters: a byte per base or a row per variant site comes back."""
 
     COLUMNS = _native.PILEUP_COLUMNS
+    CALL_CODES = _native.CALL_CODES
+    SITE_COLUMNS = _native.SITE_COLUMNS
 
-    def __init__(self, native_pileup, score, status):
+    def __init__(self, native_pileup, score, status, aligner=None):
         self._pileup = native_pileup
         self.score = score
         self.status = status
+        self._aligner = aligner
 
     def _open(self):
         if self._pileup is None or not self._pileup._h:
@@ -374,6 +381,79 @@ class Pileup:
     def depth(self, j, start=0, stop=None):
         """The sum of the columns A, C, G, T, other and del: the contributing reads whose aligned core covers each base."""
         return self.counts(j, start, stop)[:, :6].sum(axis=1, dtype=np.int32)
+
+    def _range(self, p, j, start, stop):
+        """The checked rows [start, stop) of text ``j`` (the wording of ``counts``)."""
+        if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= int(j) < p.n:
+            raise ValueError(f"j = {j!r} is out of range for {p.n} text sequences")
+        have = int(p.length[int(j)])
+        start = int(start)
+        stop = have if stop is None else int(stop)
+        if not 0 <= start <= stop <= have:
+            raise ValueError(f"rows [{start}, {stop}) are out of range for text sequence {int(j)} ({have} bases)")
+        return int(j), start, stop
+
+    def _with_texts(self, p, texts, min_depth, run):
+        """``run(native set)`` on the reference letters: a ``SequenceSet`` as it is, a list of ``str`` uploaded for this call."""
+        if isinstance(min_depth, bool) or not isinstance(min_depth, (int, np.integer)) or not 1 <= int(min_depth) < 2**31:
+            raise ValueError(f"min_depth = {min_depth!r} is out of range (an integer, at least 1)")
+        al = self._aligner
+        if al is None:
+            raise ValueError("this Pileup was made without its aligner: calls and sites need it")
+        if not isinstance(texts, (SequenceSet, list)):
+            texts = list(texts)
+        if len(texts) != p.n:
+            raise ValueError(f"texts holds {len(texts)} sequences, the pileup was made over {p.n}")
+        if isinstance(texts, list):
+            for k, t in enumerate(texts):
+                if len(t) != int(p.length[k]):
+                    raise ValueError(f"texts[{k}] has {len(t)} bases, the pileup was made over {int(p.length[k])}")
+        al._sync_wildcard()
+        sets, mine = al._open_sets(texts, None)
+        try:
+            return run(sets[0])
+        finally:
+            for s in mine:
+                s.close()
+
+    def calls(self, texts, j, start=0, stop=None, min_depth=1):
+        """The consensus call of the rows [start, stop) of text ``j``, made on the GPU (one byte per base comes back):
+        dict(code=uint8 array, ins=bool array).  ``code`` indexes ``CALL_CODES``: the column among A, C, G, T, other, del with the most
+        reads (among equals the reference's own letter, else the first), or 6, "no call", below ``min_depth`` covering reads; ``ins``:
+        more than half of the covering reads insert in front of the base.  ``texts``: the ``SequenceSet`` or the list of ``str`` the
+        pileup was made over (its letters are not kept by the pileup; a list is uploaded for the call)."""
+        p = self._open()
+        j, start, stop = self._range(p, j, start, stop)
+        raw = self._with_texts(p, texts, min_depth, lambda t: p.calls(t, j, start, stop - start, int(min_depth)))
+        return dict(code=raw & 7, ins=(raw & _native.CALL_INS) != 0)
+
+    def consensus(self, texts, j, start=0, stop=None, min_depth=1):
+        """The called sequence of the rows [start, stop) of text ``j`` as a ``str``: A, C, G, T; N for another letter and for no call;
+        deleted bases are left out.  The insertion flag of ``calls`` is ignored: the pileup does not record which bases were inserted."""
+        code = self.calls(texts, j, start, stop, min_depth)["code"]
+        return _CALL_LETTERS[code[code != 5]].tobytes().decode()
+
+    def sites(self, texts, j=None, start=0, stop=None, min_depth=1, min_frac=0.5):
+        """The bases where the reads disagree with the reference, found on the GPU (only their rows come back): a dict of int32 arrays
+        ``SITE_COLUMNS`` in ascending (j, pos).  Among bases covered by at least ``min_depth`` reads, a site is one whose strongest
+        column other than the reference's letter holds at least ``min_frac`` of the covering reads (``alt`` its column in
+        ``CALL_CODES``, 5 = deleted; ``alt_count``), or where at least ``min_frac`` of them insert in front of the base (``ins_count``;
+        ``alt`` = -1 and ``alt_count`` = 0 when only this holds).  ``min_frac`` is rounded to permille.  ``j=None``: every text (then
+        ``start`` / ``stop`` must be left alone); otherwise the rows [start, stop) of text ``j``.  What was inserted, qualities, strands
+        and genotypes are out of scope: align the few reads of a site with CIGARs."""
+        p = self._open()
+        if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
+            raise ValueError(f"min_frac = {min_frac!r} is out of range (0.001 .. 1)")
+        permille = int(round(float(min_frac) * 1000))
+        if j is None:
+            if start != 0 or stop is not None:
+                raise ValueError("j = None takes every text: start and stop go with one text")
+            seq, start, length = -1, 0, -1
+        else:
+            seq, start, stop = self._range(p, j, start, stop)
+            length = stop - start
+        _, rows = self._with_texts(p, texts, min_depth, lambda t: p.sites(t, seq, start, length, int(min_depth), permille))
+        return {name: np.ascontiguousarray(rows[:, k]) for k, name in enumerate(self.SITE_COLUMNS)}
 
     def close(self):
         if self._pileup is not None:
@@ -1126,7 +1206,8 @@ class WavefrontAligner:
         text bases they cover; neither op strings nor their run-length encoding leave the device (csrc/wfa_pileup.hpp).
         ``texts=None`` piles up over ``patterns``.
 
-        Returns a ``Pileup`` (``score``, ``status``, ``counts(j)``, ``depth(j)``, ``close()``; a context manager), which stays
+        Returns a ``Pileup`` (``score``, ``status``, ``counts(j)``, ``depth(j)``, ``calls()``, ``consensus()``, ``sites()``,
+        ``close()``; a context manager), which stays
         valid after the sets are closed.  With ``devices=[...]`` the first device runs it."""
         if self._cfg.scope != 1:
             raise ValueError("pileup needs scope='full'")
@@ -1145,7 +1226,7 @@ class WavefrontAligner:
                 table.add(rb, jj[lo:hi], None if ts is None else ts[lo:hi], keep)
 
             out = self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, each=add)
-            res = Pileup(table, out["score"], out["status"])
+            res = Pileup(table, out["score"], out["status"], self)
             table = None
             return res
         finally:

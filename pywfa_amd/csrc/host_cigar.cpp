@@ -131,3 +131,57 @@ extern "C" int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uin
   }
   return WFA_HIP_OK;
 }
+
+// ---- calls and sites: the two reductions of pileup rows against their reference bytes (the kernels: wfa_calls.hpp, k_calls.hip) ----
+
+namespace {
+int ref_col(uint8_t b) { return b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : 4; }
+int64_t depth_of(const int32_t* c) {
+  int64_t d = 0;
+  for (int x = 0; x < 6; ++x) d += c[x];
+  return d;
+}
+}  // namespace
+
+extern "C" int wfa_hip_calls_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t min_depth, uint8_t* out) {
+  if (len < 0 || min_depth < 1 || (len > 0 && (!counts || !ref || !out))) return WFA_HIP_EINVAL;
+  for (int64_t g = 0; g < len; ++g) {
+    const int32_t* c = counts + g * WFA_HIP_PILEUP_COLS;
+    const int64_t depth = depth_of(c);
+    if (depth < min_depth) { out[g] = 6; continue; }
+    const int r = ref_col(ref[g]);
+    int best = 0;
+    for (int x = 1; x < 6; ++x) if (c[x] > c[best]) best = x;   // the smallest of the greatest
+    if (c[r] == c[best]) best = r;
+    out[g] = (uint8_t)(best | (2 * (int64_t)c[6] > depth ? 8 : 0));
+  }
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t seq, int64_t start, int32_t min_depth,
+                                  int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows) {
+  if (len < 0 || min_depth < 1 || min_permille < 1 || min_permille > 1000 || cap < 0 || !count || (len > 0 && (!counts || !ref)) ||
+      (cap > 0 && !rows))
+    return WFA_HIP_EINVAL;
+  int64_t n = 0;
+  for (int64_t g = 0; g < len; ++g) {
+    const int32_t* c = counts + g * WFA_HIP_PILEUP_COLS;
+    const int64_t depth = depth_of(c);
+    if (depth < min_depth) continue;
+    const int r = ref_col(ref[g]);
+    int alt = -1;
+    for (int x = 0; x < 6; ++x) if (x != r && (alt < 0 || c[x] > c[alt])) alt = x;
+    const int64_t A = c[alt], ins = c[6];
+    const bool snv = A >= 1 && 1000 * A >= (int64_t)min_permille * depth;
+    const bool has_ins = ins >= 1 && 1000 * ins >= (int64_t)min_permille * depth;
+    if (!snv && !has_ins) continue;
+    if (n < cap) {
+      int32_t* row = rows + n * WFA_HIP_SITE_COLS;
+      row[0] = seq; row[1] = (int32_t)(start + g); row[2] = r; row[3] = snv ? alt : -1; row[4] = (int32_t)depth;
+      row[5] = c[r]; row[6] = snv ? c[alt] : 0; row[7] = c[6];
+    }
+    ++n;
+  }
+  *count = n;
+  return WFA_HIP_OK;
+}

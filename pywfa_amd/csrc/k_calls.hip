@@ -1,0 +1,113 @@
+// k_calls.hip — calls and sites of a pileup (wfa_calls.hpp: rule, layout and the kernels' outline; wfa_hip_pileup_calls / _sites in
+// wfa_hip.hip).  Stores: the calls kernel writes out[i] for i < n; the count kernel chunk_count[ch] for ch < chunks; the scan
+// chunk_off[i] for i <= chunks; the scatter kernel row `rank` only where rank < cap.  The host has checked that [g0, g0 + n) lies
+// inside the table and the byte blob.
+#include <algorithm>
+#include "k_seed.hpp"   // (the workgroup sum and exclusive scan of the seed kernels)
+#include "wfa_calls.hpp"
+
+namespace wfa {
+
+__global__ void __launch_bounds__(256) wfa_calls_kernel(CallsArgs a) {
+  const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += nthreads)
+    a.out[i] = calls_code(calls_load(a, a.g0 + i), a.min_depth);
+}
+
+// whether base i of the run is a site (false behind the run's end)
+__device__ inline bool sites_flag(const CallsArgs& a, int64_t i, CallsBase* b, int* alt, bool* snv) {
+  if (i >= a.n) return false;
+  *b = calls_load(a, a.g0 + i);
+  return calls_site(*b, a.min_depth, a.min_permille, alt, snv);
+}
+
+__global__ void __launch_bounds__(256) wfa_sites_count_kernel(CallsArgs a) {
+  __shared__ uint32_t s_red[4];
+  for (int64_t ch = blockIdx.x; ch < a.chunks; ch += gridDim.x) {
+    const int64_t i0 = ch * a.chunk;
+    uint32_t mine = 0;   // the sites of this wave's rounds (the same in every lane)
+    for (int64_t t = threadIdx.x; t < a.chunk; t += 256) {
+      CallsBase b; int alt; bool snv;
+      mine += (uint32_t)__builtin_popcountll(__ballot(sites_flag(a, i0 + t, &b, &alt, &snv)));
+    }
+    const uint32_t sum = seed_block_sum((threadIdx.x & 63) == 0 ? mine : 0u, s_red);
+    if (threadIdx.x == 0) a.chunk_count[ch] = sum;
+  }
+}
+
+// the chunk counts to their exclusive prefix in 64 bits, chunk_off[chunks] the total: one workgroup, 256 counts per round
+__global__ void __launch_bounds__(256) wfa_sites_scan_kernel(CallsArgs a) {
+  __shared__ uint32_t s_red[4];
+  uint64_t carry = 0;
+  for (int64_t b0 = 0; b0 < a.chunks; b0 += 256) {
+    const int64_t i = b0 + threadIdx.x;
+    const uint32_t v = i < a.chunks ? a.chunk_count[i] : 0u;
+    uint32_t total;   // (256 chunks of at most 2^20 bases: below 2^32)
+    const uint32_t ex = seed_block_exclusive(v, s_red, &total);
+    if (i < a.chunks) a.chunk_off[i] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) a.chunk_off[a.chunks] = carry;
+}
+
+__global__ void __launch_bounds__(256) wfa_sites_scatter_kernel(CallsArgs a) {
+  __shared__ uint32_t s_red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long lower = (1ull << lane) - 1ull;
+  for (int64_t ch = blockIdx.x; ch < a.chunks; ch += gridDim.x) {
+    uint64_t run = a.chunk_off[ch];
+    if (run >= (uint64_t)a.cap || a.chunk_off[ch + 1] == run) continue;   // (uniform over the workgroup)
+    const int64_t i0 = ch * a.chunk;
+    for (int64_t t0 = 0; t0 < a.chunk; t0 += 256) {
+      const int64_t i = i0 + t0 + threadIdx.x;
+      CallsBase b; int alt; bool snv;
+      const bool site = t0 + threadIdx.x < a.chunk && sites_flag(a, i, &b, &alt, &snv);
+      const unsigned long long m = __ballot(site);
+      if (lane == 0) s_red[wave] = (uint32_t)__builtin_popcountll(m);
+      __syncthreads();
+      uint32_t before = 0;
+      for (int w = 0; w < wave; ++w) before += s_red[w];
+      const uint32_t total = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+      __syncthreads();
+      const uint64_t rank = run + before + (uint32_t)__builtin_popcountll(m & lower);
+      run += total;
+      if (!site || rank >= (uint64_t)a.cap) continue;
+      const int64_t g = a.g0 + i;
+      int64_t lo = 0, hi = a.nseq;   // the first sequence that starts behind g; its predecessor owns g
+      while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.seq_off[mid] > g) hi = mid; else lo = mid + 1; }
+      const int64_t j = lo - 1;
+      int32_t ref_count = b.c[0];
+#pragma unroll
+      for (int x = 1; x < 5; ++x) if (x == b.r) ref_count = b.c[x];
+      int32_t alt_count = 0;
+#pragma unroll
+      for (int x = 0; x < 6; ++x) if (x == alt) alt_count = b.c[x];
+      int4* row = reinterpret_cast<int4*>(a.rows + rank * WFA_SITE_COLS);
+      row[0] = make_int4((int32_t)j, (int32_t)(g - a.seq_off[j]), b.r, snv ? alt : -1);
+      row[1] = make_int4((int32_t)b.depth, ref_count, snv ? alt_count : 0, b.c[6]);
+    }
+  }
+}
+
+int launch_calls(const CallsArgs& a, int cu_count, hipStream_t stream) {
+  if (a.n <= 0) return 0;
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.n + 255) / 256, (int64_t)cu_count * 32));
+  hipLaunchKernelGGL(wfa_calls_kernel, dim3(grid), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+static unsigned chunk_grid(int64_t chunks) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(chunks, 1 << 16)); }
+
+int launch_sites_count(const CallsArgs& a, hipStream_t stream) {
+  if (a.chunks > 0) hipLaunchKernelGGL(wfa_sites_count_kernel, dim3(chunk_grid(a.chunks)), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(wfa_sites_scan_kernel, dim3(1), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_sites_scatter(const CallsArgs& a, hipStream_t stream) {
+  if (a.chunks <= 0 || a.cap <= 0) return 0;
+  hipLaunchKernelGGL(wfa_sites_scatter_kernel, dim3(chunk_grid(a.chunks)), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace wfa

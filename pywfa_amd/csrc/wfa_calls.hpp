@@ -1,0 +1,92 @@
+// wfa_calls.hpp — two reductions of a pileup table against its reference letters (wfa_hip_pileup_calls / _sites): one call byte per
+// base, and the ordered rows of the bases where the reads disagree with the reference.
+//
+// Rule (include/wfa_hip.h, "calls and sites"; wfa_hip_calls_host / wfa_hip_sites_host in host_cigar.cpp are its plain statement,
+// needing no GPU): per base the counters c0..c7 of the table, the reference column r of its byte, depth = c0 + .. + c5 in 64 bits.
+//   call  6 below min_depth, else the greatest of c0..c5 (r among equals, else the smallest) | 8 when 2 * c6 > depth
+//   site  depth >= min_depth and (the greatest non-reference column A has A >= 1, 1000 A >= permille * depth, or the same for c6)
+//
+// Layout: the table is a plane per column (wfa_pileup.hpp), a base's place in a plane its GLOBAL index seq_off[j] + pos; the set's
+// byte blob holds the sequences back to back, so the reference byte of a base sits at the same global index.  A range of one
+// sequence, and every sequence (seq = -1), are both one run [g0, g0 + n) of global indices, and ascending global index is ascending
+// (j, pos).  Neighbouring lanes take neighbouring bases: seven coalesced int32 reads and one byte per base, 29 bytes.
+//
+// Kernels (k_calls.hip):
+//   calls    a thread per base, grid-stride; one byte stored per base.
+//   sites    three passes over chunks of `chunk` bases (a multiple of 64; WFA_HIP_CALLS_CHUNK), no atomics, no waiting on other
+//            workgroups:
+//     count    a workgroup per chunk: the predicate per base, ballot + popcount per wave, a workgroup sum -> chunk_count[chunk]
+//     scan     one workgroup: the exclusive prefix of the chunk counts (64-bit) -> chunk_off[0 .. chunks], the last one the total
+//     scatter  a workgroup per chunk: the predicate again, a site's rank = chunk_off[chunk] + the sites of the rounds and waves in
+//              front of it + the popcount of the ballot below its lane; rows of rank < cap are written.  The sequence of a site is
+//              the last one that starts at or before its global index (a binary search in seq_off, as the seed positions kernel's).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "wfa_pileup.hpp"
+
+namespace wfa {
+
+#define WFA_SITE_COLS 8
+
+struct CallsArgs {
+  const int32_t* table;      // WFA_PILEUP_COLS planes of `total` counters
+  int64_t total;
+  const uint8_t* ref;        // the set's byte blob: the reference byte of global base g is ref[g]
+  int64_t g0, n;             // the run of global base indices [g0, g0 + n)
+  int32_t min_depth, min_permille;
+  // calls
+  uint8_t* out;              // [n]
+  // sites
+  int64_t chunk, chunks;     // bases per chunk (a multiple of 64), chunks = ceil(n / chunk)
+  uint32_t* chunk_count;     // [chunks]
+  uint64_t* chunk_off;       // [chunks + 1]
+  const int64_t* seq_off;    // [nseq] first global index of a sequence
+  int64_t nseq;
+  int64_t cap;               // rows of `rows`
+  int32_t* rows;             // [cap x WFA_SITE_COLS]
+};
+
+struct CallsBase { int32_t c[7]; int r; int64_t depth; };
+
+__device__ inline CallsBase calls_load(const CallsArgs& a, int64_t g) {
+  CallsBase b;
+#pragma unroll
+  for (int x = 0; x < 7; ++x) b.c[x] = a.table[(int64_t)x * a.total + g];
+  b.r = wfa_pileup_letter_col(a.ref[g]);
+  b.depth = 0;
+#pragma unroll
+  for (int x = 0; x < 6; ++x) b.depth += b.c[x];
+  return b;
+}
+
+__host__ __device__ inline uint8_t calls_code(const CallsBase& b, int32_t min_depth) {
+  if (b.depth < min_depth) return 6;
+  int best = 0, cb = b.c[0], cr = b.c[0];
+#pragma unroll
+  for (int x = 1; x < 6; ++x) {
+    if (b.c[x] > cb) { cb = b.c[x]; best = x; }
+    if (x == b.r) cr = b.c[x];
+  }
+  if (cr == cb) best = b.r;
+  return (uint8_t)(best | (2 * (int64_t)b.c[6] > b.depth ? 8 : 0));
+}
+
+// whether the base is a site; *alt, *snv: its greatest non-reference column and whether that one qualifies
+__host__ __device__ inline bool calls_site(const CallsBase& b, int32_t min_depth, int32_t min_permille, int* alt, bool* snv) {
+  int best = -1, cb = 0;
+#pragma unroll
+  for (int x = 0; x < 6; ++x)
+    if (x != b.r && (best < 0 || b.c[x] > cb)) { cb = b.c[x]; best = x; }
+  const int64_t bar = (int64_t)min_permille * b.depth;
+  *alt = best;
+  *snv = cb >= 1 && 1000 * (int64_t)cb >= bar;
+  const bool ins = b.c[6] >= 1 && 1000 * (int64_t)b.c[6] >= bar;
+  return b.depth >= min_depth && (*snv || ins);
+}
+
+int launch_calls(const CallsArgs& a, int cu_count, hipStream_t stream);
+int launch_sites_count(const CallsArgs& a, hipStream_t stream);     // count + scan: chunk_off[chunks] is the number of sites
+int launch_sites_scatter(const CallsArgs& a, hipStream_t stream);
+
+}  // namespace wfa

@@ -41,6 +41,7 @@
 #include "wfa_rle.hpp"
 #include "wfa_summary.hpp"
 #include "wfa_pileup.hpp"
+#include "wfa_calls.hpp"
 #include "wfa_seed.hpp"
 #include "wfa_chain.hpp"
 #include "wfa_cross.hpp"
@@ -3118,19 +3119,20 @@ extern "C" int wfa_hip_batch_rle_runs(wfa_hip_batch_t* b, uint8_t* run_code, int
 extern "C" int64_t wfa_hip_batch_fallback_pairs(const wfa_hip_batch_t* b) { return b ? b->last_fallback : 0; }
 
 // ---- device-side per-pair summary (csrc/wfa_summary.hpp) ------------------------------------------------
-// WFA_HIP_REDUCE_TIMING=1 (a development knob): the summary and pileup kernels are bracketed by two events and their HIP-event time
-// goes to stderr, one line per call (tools/probes/pileup_index.py reads it).
+// WFA_HIP_REDUCE_TIMING=1 (a development knob): the summary, pileup, calls and sites kernels are bracketed by two events and their
+// HIP-event time goes to stderr, one line per call (tools/probes/pileup_index.py and pileup_calls.py read it).
 struct ReduceTimer {
   wfa_hip_aligner* al; const char* what; int64_t n;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  ReduceTimer(wfa_hip_aligner* al_, const char* what_, int64_t n_) : al(al_), what(what_), n(n_) {
+  const char* unit;
+  ReduceTimer(wfa_hip_aligner* al_, const char* what_, int64_t n_, const char* unit_ = "pairs") : al(al_), what(what_), n(n_), unit(unit_) {
     if (knob(al, K_REDUCE_TIMING, 0) && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess) (void)hipEventRecord(ev[0], al->stream);
   }
   void stop() { if (ev[1]) (void)hipEventRecord(ev[1], al->stream); }
   ~ReduceTimer() {   // (after the caller's stream synchronisation)
     float ms = 0.f;
     if (ev[1] && hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-      fprintf(stderr, "[wfa_hip] %s kernel %.4f ms (%lld pairs)\n", what, ms, (long long)n);
+      fprintf(stderr, "[wfa_hip] %s kernel %.4f ms (%lld %s)\n", what, ms, (long long)n, unit);
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
   }
 };
@@ -4688,6 +4690,134 @@ extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t sta
   for (int c = 0; c < WFA_PILEUP_COLS; ++c) {
     const int32_t* src = plane.data() + (size_t)c * (size_t)len;
     for (int64_t r = 0; r < len; ++r) counts[r * WFA_PILEUP_COLS + c] = src[r];
+  }
+  return WFA_HIP_OK;
+}
+
+// ---- calls and sites of a pileup against its reference set (include/wfa_hip.h; csrc/wfa_calls.hpp, k_calls.hip) ----------------------
+static_assert(WFA_SITE_COLS == WFA_HIP_SITE_COLS, "columns of the kernels and of the ABI");
+
+// the checks the two calls share: the set is the pileup's (same aligner, same lengths), the parameters, the range.  On success
+// *g0 / *n are the run of global base indices (seq = -1, sites only: every base).
+static int calls_check(wfa_hip_pileup* p, const wfa_hip_seqset_t* T, bool sites, int32_t seq, int64_t start, int64_t len, int32_t min_depth,
+                       int32_t min_permille, int64_t cap, int64_t* g0, int64_t* n) {
+  wfa_hip_aligner* al = p->al;
+  char buf[240];
+  if (!T || T->al != al) { al->err = "sequence set of another aligner"; return WFA_HIP_EINVAL; }
+  if (T->n != p->nseq) {
+    snprintf(buf, sizeof(buf), "pileup: the set holds %lld sequences, the pileup was made over %lld", (long long)T->n, (long long)p->nseq);
+    al->err = buf; return WFA_HIP_EINVAL;
+  }
+  for (int64_t k = 0; k < p->nseq; ++k)
+    if (T->h_len[(size_t)k] != p->h_len[(size_t)k]) {
+      snprintf(buf, sizeof(buf), "pileup: sequence %lld of the set has %lld bases, the pileup was made over %lld", (long long)k,
+               (long long)T->h_len[(size_t)k], (long long)p->h_len[(size_t)k]);
+      al->err = buf; return WFA_HIP_EINVAL;
+    }
+  if (min_depth < 1) {
+    snprintf(buf, sizeof(buf), "pileup: min_depth = %d is out of range (at least 1)", (int)min_depth);
+    al->err = buf; return WFA_HIP_EINVAL;
+  }
+  if (sites && (min_permille < 1 || min_permille > 1000)) {
+    snprintf(buf, sizeof(buf), "pileup: min_permille = %d is out of range (1 .. 1000)", (int)min_permille);
+    al->err = buf; return WFA_HIP_EINVAL;
+  }
+  if (sites && cap < 0) {
+    snprintf(buf, sizeof(buf), "pileup: cap = %lld is negative", (long long)cap);
+    al->err = buf; return WFA_HIP_EINVAL;
+  }
+  if (sites && seq == -1) {
+    if (start != 0 || len != -1) {
+      snprintf(buf, sizeof(buf), "pileup: seq = -1 (every sequence) goes with start = 0 and len = -1, got start = %lld, len = %lld",
+               (long long)start, (long long)len);
+      al->err = buf; return WFA_HIP_EINVAL;
+    }
+    *g0 = 0; *n = p->total;
+    return WFA_HIP_OK;
+  }
+  if (seq < 0 || seq >= p->nseq || start < 0 || len < 0 || start + len > p->h_len[(size_t)seq]) {
+    snprintf(buf, sizeof(buf), "pileup: rows [%lld, %lld + %lld) of sequence %d are out of range (%lld sequences; sequence length %lld)", (long long)start,
+             (long long)start, (long long)len, (int)seq, (long long)p->nseq, (long long)((seq >= 0 && seq < p->nseq) ? p->h_len[(size_t)seq] : -1));
+    al->err = buf; return WFA_HIP_EINVAL;
+  }
+  *g0 = p->h_off[(size_t)seq] + start; *n = len;
+  return WFA_HIP_OK;
+}
+
+static wfa::CallsArgs calls_args(const wfa_hip_pileup* p, const wfa_hip_seqset_t* T, int64_t g0, int64_t n, int32_t min_depth, int32_t min_permille) {
+  wfa::CallsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.table = p->d_table; a.total = p->total; a.ref = T->d_bytes; a.g0 = g0; a.n = n; a.min_depth = min_depth; a.min_permille = min_permille;
+  a.seq_off = p->d_off; a.nseq = p->nseq;
+  return a;
+}
+
+extern "C" int wfa_hip_pileup_calls(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                    int32_t min_depth, uint8_t* out) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  int64_t g0 = 0, n = 0;
+  const int rc = calls_check(p, texts, false, seq, start, len, min_depth, 1, 0, &g0, &n);
+  if (rc != WFA_HIP_OK) return rc;
+  if (n > 0 && !out) { al->err = "pileup: null output"; return WFA_HIP_EINVAL; }
+  HIP_TRY(al, hipSetDevice(al->device));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  if (n == 0) return WFA_HIP_OK;
+  CrossScratch sc{al};
+  wfa::CallsArgs a = calls_args(p, texts, g0, n, min_depth, 1);
+  if (sc.alloc(&a.out, (size_t)n)) return WFA_HIP_EDEVICE;
+  {
+    ReduceTimer timer(al, "calls", n, "bases");
+    const int lrc = wfa::launch_calls(a, al->cu_count, al->stream);
+    timer.stop();
+    if (lrc != 0) { al->err = "calls kernel launch failed"; return WFA_HIP_EDEVICE; }
+    HIP_TRY(al, hipMemcpyAsync(out, a.out, (size_t)n, hipMemcpyDeviceToHost, al->stream));
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+  }
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                    int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  int64_t g0 = 0, n = 0;
+  const int rc = calls_check(p, texts, true, seq, start, len, min_depth, min_permille, cap, &g0, &n);
+  if (rc != WFA_HIP_OK) return rc;
+  if (!count) { al->err = "pileup: null count"; return WFA_HIP_EINVAL; }
+  if (cap > 0 && !rows) { al->err = "pileup: null rows with cap > 0"; return WFA_HIP_EINVAL; }
+  HIP_TRY(al, hipSetDevice(al->device));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  *count = 0;
+  if (n == 0) return WFA_HIP_OK;
+  // bases per chunk: read per call, a multiple of 64 in 64 .. 2^20
+  const char* env = getenv("WFA_HIP_CALLS_CHUNK");
+  const int64_t asked = env && *env ? atoll(env) : 4096;
+  CrossScratch sc{al};
+  wfa::CallsArgs a = calls_args(p, texts, g0, n, min_depth, min_permille);
+  a.chunk = std::min<int64_t>(1 << 20, std::max<int64_t>(64, (std::min<int64_t>(asked, 1 << 20) + 63) / 64 * 64));
+  a.chunks = (n + a.chunk - 1) / a.chunk;
+  if (sc.alloc(&a.chunk_count, (size_t)a.chunks) || sc.alloc(&a.chunk_off, (size_t)a.chunks + 1)) return WFA_HIP_EDEVICE;
+  uint64_t total = 0;
+  {
+    ReduceTimer timer(al, "sites count", n, "bases");
+    const int lrc = wfa::launch_sites_count(a, al->stream);
+    timer.stop();
+    if (lrc != 0) { al->err = "sites count kernel launch failed"; return WFA_HIP_EDEVICE; }
+    HIP_TRY(al, hipMemcpyAsync(&total, a.chunk_off + a.chunks, sizeof(total), hipMemcpyDeviceToHost, al->stream));
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+  }
+  *count = (int64_t)total;
+  a.cap = std::min<int64_t>((int64_t)total, cap);
+  if (a.cap == 0) return WFA_HIP_OK;
+  if (sc.alloc(&a.rows, (size_t)a.cap * WFA_SITE_COLS)) return WFA_HIP_EDEVICE;
+  {
+    ReduceTimer timer(al, "sites scatter", n, "bases");
+    const int lrc = wfa::launch_sites_scatter(a, al->stream);
+    timer.stop();
+    if (lrc != 0) { al->err = "sites scatter kernel launch failed"; return WFA_HIP_EDEVICE; }
+    HIP_TRY(al, hipMemcpyAsync(rows, a.rows, (size_t)a.cap * WFA_SITE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
   }
   return WFA_HIP_OK;
 }

@@ -65,3 +65,12 @@ cdef extern from "wfa_hip.h" nogil:
                             int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
                             int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
                             uint8_t* overflow, char* msg, size_t msg_cap)
+    # calls and sites of a pileup (include/wfa_hip.h: "calls and sites")
+    ctypedef struct wfa_hip_pileup_t
+    int wfa_hip_pileup_calls(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                            int32_t min_depth, uint8_t* out)
+    int wfa_hip_pileup_sites(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                            int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows)
+    int wfa_hip_calls_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t min_depth, uint8_t* out)
+    int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t seq, int64_t start, int32_t min_depth,
+                            int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows)
