@@ -2579,10 +2579,10 @@ static int batch_run_once(wfa_hip_batch_t* b, void* stream_) {
                                  // the first lane stage, [14] for the one behind it; WFA_HIP_LANE_DYN=0: fixed slices)
                                  b->d_counters + (lane_k == 0 ? 12 : 14), lane_dyn, narrow ? 4 : 8);
           if (knob(al, K_LANE_DEBUG, 0) && al->ws) {  // development aid (build with -DWFA_LANE_DEBUG_COUNTERS=1)
-            unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            unsigned long long c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             hipStreamSynchronize(stream); hipMemcpy(c, al->ws, sizeof(c), hipMemcpyDeviceToHost); hipMemset(al->ws, 0, sizeof(c));
             fprintf(stderr, "[wfa_hip] lane kernel: %llu wave-steps, %llu refills, %llu parked runs, %llu parked rounds, %llu probe blocks, %llu second-run rounds, "
-                            "%llu hand-over blocks, %llu second runs\n", c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);
+                            "%llu hand-over blocks, %llu second runs, %llu entries, %llu entry rounds\n", c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]);
           }
         } else {
           lrc = wfa::launch_seg(b->dcfg, al->cu_count, knob(al, K_FAST_WAVES_PER_CU, 256), stream, b->d_words, b->d_meta, in_list, in_count,

@@ -42,6 +42,29 @@
 // wfa_seg_kernel<.., FULL>, so that every candidate the reference's backtrace compares lies inside the band with its true value.
 // (First form of this round: records in LDS and the walk inside this kernel at every refill — 12 of 64 lanes busy in the walk,
 // 2.25 waves per SIMD: 0.80 ms per million pairs against 0.30 for the score alone; dropped.)
+//
+// ENTRY (plain score-only form: !FULL, !HEUR, LIN = 0; both widths, built-in and run-time shapes): a pair enters the loop at score
+// K = OE instead of score 0.  Below OE no gap can have been opened (I_s, D_s read M at s - OE < 0), so the only cells are those of
+// diagonal 0 at the multiples of X: chain[0] = extend(0), chain[i] = extend(chain[i - 1] + 1) for i < NCH = ceil(OE / X) — and with
+// X >= OE just chain[0].  OE is the first score at which a cell off diagonal 0 exists (I_OE on k = 1, D_OE on k = -1), which is what K
+// has to be for any shape.  A lock-step pass per unit of score for one cell (and none at all at the other scores) is what the
+// refill now does on its own: the lanes that take a pair follow diagonal 0 together, 32 bases per round, bounded by lim of slot j0 =
+// min(tlen, plen); a run that stops is the next cell of the chain, the one behind it starts a base further on, and if that lies beyond
+// lim the clamp of compute-next would have made it (and with it every later cell) NULL.  A pair with tlen == plen whose cell i
+// reaches tlen is finished there, as termination would have found at step i X: score -(i X) g, status 0, the lane idle again.
+// The state at step K, before its extension, is then written down as the loop would hold it:
+//   Mh[d] = M at score K - 1 - d = chain[(K - 1 - d) / X] in slot j0 where that score is a multiple of X in [0, K), else NULL;
+//   Ih[0] = I_K = M_0 + 1 in slot j0 + 1, Dh[0] = D_K = M_0 in slot j0 - 1 (a slot outside the band: nothing, as the NULL
+//   shifted in by alignbit); deeper I / D: NULL (scores below OE);
+//   cur = clamp(max(I_K, D_K, chain[NCH - 1] + 1 in slot j0 if X divides K), lim); s0 = gstep - K, the deadline counted from s0.
+// Invariant: for every pair these registers equal, cell for cell, what the loop entered at score 0 holds after K steps — up to the
+// value of dead cells: the loop lets NULL drift (NULL + 1 per mismatch or insertion step, at most one per step), here they are NULL
+// itself.  No test tells two negative values apart (a cell lives if its offset is >= 0, termination compares with tlen >= 0, the
+// clamp keeps a negative value negative, max prefers any live value), and the drift of either stays far below 0 for the steps a pair
+// can take, so from step K on both forms compute the same live cells, the same scores and the same hand-overs.
+// Nothing else can happen before K: a pair ends below K only on diagonal 0 (handled above), and it is handed on only past its
+// deadline, which lies at Bmin / g >= 2 (OE - E) + 2 E H = K + (OE - 2 E) + 2 E H > K steps after its score 0 for every H >= 1.
+// (A pair the stage cannot take keeps its expired deadline and an all-NULL state, and leaves at once as before.)
 #pragma once
 #include "wfa_rtc_compat.hpp"
 #include "wfa_common.hpp"
@@ -58,8 +81,9 @@ typedef unsigned short lane_u2 __attribute__((ext_vector_type(2)));
 #define WFA_LANE_NULL16 (-16384)
 #define WFA_LANE_NULL2 0xC000C000u
 #ifndef WFA_LANE_DEBUG_COUNTERS
-#define WFA_LANE_DEBUG_COUNTERS 0  // 1: a.hist (if set) receives eight uint64: {wave-steps, refills, parked runs, parked 32-base rounds,
-#endif                             //    first-probe blocks, rounds of second runs, hand-over blocks, second runs} (score-only form)
+#define WFA_LANE_DEBUG_COUNTERS 0  // 1: a.hist (if set) receives ten uint64: {wave-steps, refills, parked runs, parked 32-base rounds,
+#endif                             //    first-probe blocks, rounds of second runs, hand-over blocks, second runs, entries (refills that
+                                   //    ran the entry chain), 32-base rounds of the entry chain} (score-only form)
 // Analysis builds (tools/lane_mix.py): region marks as comments in the assembly, so that the instructions of each region of the
 // step can be counted by class and weighted with the counters above (the dynamic instruction mix of the kernel)
 #ifndef WFA_LANE_REGION_MARKS
@@ -149,6 +173,9 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
   constexpr int NR = NRP, W = 2 * NR, H = NR;     // band of 16 diagonals = 8 packed registers (NRP = 16: 32 diagonals, NRP = 4: 8)
   constexpr int DM = (X > OE) ? X : OE;           // depth of the M ring
   constexpr int NEVER = 0x7fffffff;
+  // the entry at score K (header comment): the plain score-only form only.  NCH cells of diagonal 0 precede score K: scores 0, X, .. < OE
+  constexpr bool ENTRY = !FULL && !HEUR && LIN == 0;
+  constexpr int K = ENTRY ? OE : 0, NCH = (OE + X - 1) / X;
   constexpr int NREC = LaneFull<OE, E>::NREC;     // FULL: steps a pair can take here (bounds the walk)
   extern __shared__ uint32_t lds[];               // [4 guard words][64 slots x slot_words][4 guard words]
   const int slot_words = slot_words_seq;
@@ -288,7 +315,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
       if (take) {
         const int c = bad ? 0 : (HEUR ? ((dlo + dhi + 1) >> 1) : ((ak + 1) >> 1));      // band centre: k in [c - H, c + H)
         const int k0 = c - H;                         // diagonal of slot 0
-        mypid = n_pid; s0 = gstep;
+        mypid = n_pid; s0 = gstep - K;                // (ENTRY: the pair enters the loop at its score K)
         if (FULL) myslot = next_i + rank;   // (slot = index of the work item in this launch)
         kb0 = pbase - k0; tb = pbase + nwp * 16;
         jt = bad ? 0 : ak - k0;
@@ -296,7 +323,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
         // Bmin / g in units of g (o / g = OE - E, e / g = E), see wfa_seg.hpp
         deadline = bad ? gstep - 1
                        : HEUR ? gstep + 4 * (pl + tl) + 64   // (no bound to prove: only a cap on the steps a pair may take here)
-                       : gstep + min(2 * (OE - E) + E * (2 * c + 2 * H - ak), 2 * (OE - E) + E * (2 * H + 2 - 2 * c + ak))
+                       : s0 + min(2 * (OE - E) + E * (2 * c + 2 * H - ak), 2 * (OE - E) + E * (2 * H + 2 - 2 * c + ak))
                                - (FULL ? 1 : 0);   // FULL: S' < Bmin strictly, so that no co-optimal alignment leaves the band
         const int j0 = -k0;                           // slot of diagonal 0: the cell (score 0, offset 0)
         // lim of slot j = min(tlen, plen + k0 + j), two per register (a pair this stage cannot take: NULL, nothing lives)
@@ -308,7 +335,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
           lim[r] = bad ? WFA_LANE_NULL2 : pk_min(tl2, pk_add(lb2, (uint32_t)(2 * r) * 0x00010001u));
-          cur[r] = (j0r == r) ? c0 : WFA_LANE_NULL2;
+          cur[r] = (!ENTRY && j0r == r) ? c0 : WFA_LANE_NULL2;   // (ENTRY: built below, once the words are in LDS)
           if (HEUR) {
             // wavefront 0 over the free begins (offset max(k, 0) on diagonals -pbf .. tbf) and the thresholds that end the alignment:
             // end-to-end: offset tlen on the end diagonal; ends-free: h >= tlen with plen - v <= pef, or v >= plen with tlen - h <= tef,
@@ -342,6 +369,79 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
       if (next_i - wbase >= 64u) {           // window 0 used up: window 1 moves down, the one after is requested
         pid0 = pid1; pw0 = pw1; ln0 = ln1; wbase += 64u;
         load_window(wbase + 64u, pid1, pw1, ln1);
+      }
+      if constexpr (ENTRY) {
+        // ---- entry at score K (header comment): diagonal 0 through its NCH cells, all taking lanes together, then the state of step K
+        const bool go = take && !bad;
+        if (__any(go)) {
+          WFA_LANE_MARK("entry_begin");
+          WFA_LANE_COUNT(8);
+          int ch[NCH];
+#pragma unroll
+          for (int i = 0; i < NCH; ++i) ch[i] = WFA_LANE_NULL16;
+          const int etb = go ? tb : pbase;             // (other lanes read along, inside their own slot, and advance by 0)
+          int ci = 0, ex = 0, lf = go ? min(pl, tl) : 0, fin_i = -1;   // lf: what is left up to lim of slot j0 = min(tlen, plen)
+          bool act = go;
+          do {
+            WFA_LANE_MARK("entryround_begin");
+            WFA_LANE_COUNT(9);
+            const int v = ex + pbase, h = ex + etb;    // (slot j0 is diagonal 0: kb0 - j0 = pbase)
+            const uint32_t pa = ((uint32_t)v >> 2) & ~3u, ta = ((uint32_t)h >> 2) & ~3u;
+            const uint32_t* pp = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds) + pa);
+            const uint32_t* tp = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds) + ta);
+            const uint32_t p0 = pp[0], p1 = pp[1], p2 = pp[2], t0 = tp[0], t1 = tp[1], t2 = tp[2];
+            const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, (uint32_t)v << 1) ^ __builtin_amdgcn_alignbit(t1, t0, (uint32_t)h << 1);
+            const uint32_t xh = __builtin_amdgcn_alignbit(p2, p1, (uint32_t)v << 1) ^ __builtin_amdgcn_alignbit(t2, t1, (uint32_t)h << 1);
+            const uint32_t fb = min(lane_ffbl(xl), lane_ffbl(xh) | 32u);
+            const int m = min((int)(fb >> 1), min(32, lf));
+            ex += m; lf -= m;
+            // a run that stops is cell ci of the chain; the next one starts one base on (a mismatch), if that is still within lim —
+            // beyond it the clamp makes that cell and every later one NULL.  (A cell AT lim takes one more round, which advances by 0.)
+            const bool stop = act && !((m == 32) && (lf > 0));
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) ch[i] = (stop && ci == i) ? ex : ch[i];
+            fin_i = (stop && ak == 0 && ex == tl) ? ci : fin_i;   // the end cell: the pair's score is ci * X (then lf == 0: the chain ends)
+            ci += stop ? 1 : 0;
+            const bool on = stop && ci < NCH && lf > 0;
+            act = stop ? on : act;
+            ex += on ? 1 : 0; lf -= on ? 1 : 0;
+            WFA_LANE_MARK("entryround_end");
+          } while (__any(act));
+          const bool fin = fin_i >= 0;                 // (set by lanes with `go` only)
+          if (fin) {
+            a.score[mypid] = -__mul24(fin_i * X, a.g);
+            a.status[mypid] = 0;
+          }
+          idle |= __ballot(fin);                       // finished before the loop: the lane is idle again
+          if (go) {
+            // one value in slot `slot` of a ring register set, NULL elsewhere (a slot outside the band, or a finished pair: all NULL)
+            auto place = [&](uint32_t (&dst)[NR], int slot, int val) {
+              const int rr = fin ? -1 : (slot >> 1);   // (-1 and NR match no register)
+              const uint32_t w = (slot & 1) ? (((uint32_t)WFA_LANE_NULL16 & 0xffffu) | ((uint32_t)val << 16))
+                                            : ((WFA_LANE_NULL2 & 0xffff0000u) | ((uint32_t)val & 0xffffu));
+#pragma unroll
+              for (int r = 0; r < NR; ++r) dst[r] = (rr == r) ? w : WFA_LANE_NULL2;
+            };
+            const int j0 = H - ((ak + 1) >> 1);
+#pragma unroll
+            for (int d = 0; d < DM; ++d) {
+              const int sc = K - 1 - d;                // Mh[d] = M at score K - 1 - d: a cell of the chain, or nothing
+              if (sc >= 0 && sc % X == 0) place(Mh[d], j0, ch[sc / X]);
+            }
+            place(Ih[0], j0 + 1, ch[0] + 1);           // I_K = M_0(k - 1) + 1
+            place(Dh[0], j0 - 1, ch[0]);               // D_K = M_0(k + 1)
+            uint32_t mm[NR];
+            if (K % X == 0) place(mm, j0, ch[NCH - 1] + 1);   // the mismatch candidate M_(K - X) + 1 (dead if that cell is)
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+              const uint32_t gap = pk_max(Ih[0][r], Dh[0][r]);
+              cur[r] = pk_clamp((K % X == 0) ? pk_max(gap, mm[r]) : gap, lim[r]);   // (not extended: the loop does that)
+              if (fin) lim[r] = WFA_LANE_NULL2;
+            }
+            if (fin) { deadline = NEVER; jt = 0; tend = 0xffffu; }
+          }
+          WFA_LANE_MARK("entry_end");
+        }
       }
       WFA_LANE_MARK("refill_end");
     } else if (idle == ~0ull && exhausted) {
