@@ -569,6 +569,76 @@ int wfa_hip_calls_host(const int32_t* counts, const uint8_t* ref, int64_t len, i
 int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t seq, int64_t start,
                        int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows);
 
+/* ---- placement: one row per read from the hits of any number of batches ---------------------------------- */
+
+/*
+ * The seed and chain queries give up to n candidate windows per read and a windowed batch aligns them all; what a mapper wants next is
+ * where each read GOES: its best hit, how far the runner-up at another place is behind, and which hits are merely the same place found
+ * twice.  The hits are recorded on the device where the batches lie, grouped by read and reduced there; 32 bytes per read and 1 byte
+ * per hit cross PCIe.  Integers only.
+ *
+ * HIT.  One aligned pair: its read i and text j, its strand `reverse` (0 or 1), score and status, a text interval [ts, te) in
+ * coordinates of text j, and its HIT NUMBER: its position in the order of the adds (the first add first, list order within an add).
+ * ELIGIBLE.  status == 0 && score >= min_score.  min_score = INT32_MIN keeps every hit of status 0.
+ * PRIMARY of a read: its eligible hit of greatest score; on a tie the smallest hit number.
+ * SAME LOCUS.  Eligible hit h is at the locus of the primary p iff h != p, j_h == j_p, reverse_h == reverse_p, and
+ *     ov = min(te_h, te_p) - max(ts_h, ts_p)   has   ov > 0 && 2 * ov >= min(te_h - ts_h, te_p - ts_p)        (64-bit)
+ * so a hit with an empty interval (te <= ts) is never at the same locus, and neither is p at one's.
+ * RUNNER-UP.  `second` is the greatest score among the eligible hits that are neither p nor at p's locus; `ties` the number of those
+ * whose score equals p's.
+ * MAPPING QUALITY.  60 when there is no runner-up; otherwise min(60, 60 * (score_p - second) / full_gap), the product and the floor
+ * division in 64 bits, full_gap >= 1: a tie gives 0, a runner-up full_gap or more behind gives 60.  It is a documented confidence, not a
+ * calibrated probability; score, second and ties are returned so that a caller can apply a rule of their own.
+ *
+ * PER READ WFA_HIP_PLACE_COLS int32: hit (the primary's hit number), score, second (INT32_MIN without a runner-up), mapq, hits (the
+ * read's eligible hits), ties, text_start, text_end (the primary's [ts, te)).  A read without an eligible hit gets
+ * -1, INT32_MIN, INT32_MIN, 0, 0, 0, 0, 0.
+ * PER HIT one byte: 0 not eligible, 1 eligible at another locus, 2 at the locus of the primary, 3 the primary.
+ *
+ * INTERVAL OF A BATCH'S PAIR q, with t0 = t_start[q] (0 when t_start is NULL).  Scope full: [t0 + loc_ts, t0 + loc_te), loc_ts and
+ * loc_te being exactly columns 8 and 9 of wfa_hip_batch_summary for the pair: the aligned core; for an op string without an M
+ * loc_te <= loc_ts, an empty interval.  Scope score: the whole window [t0, t0 + tlen[q]), tlen[q] the batch's own text length.
+ *
+ * wfa_hip_placer_create: a placer over reads 0 .. nreads - 1 (nreads >= 0), without hits.  37 BYTES PER HIT AND 36 PER READ in HBM
+ * (csrc/wfa_place.hpp), the records grown by doubling; a failed allocation: WFA_HIP_EDEVICE, the message names the byte count.
+ * wfa_hip_placer_add waits for the batch's last run, as wfa_hip_pileup_add does, and appends its pairs as hits: pair q is a hit of
+ * read i[q] on text j[q] from t_start[q], on the strand reverse[q] != 0 (the arrays given to wfa_hip_batch_create_windows are exactly
+ * these; reverse NULL: forward).  One kernel; 13 bytes per pair uploaded, nothing downloaded.  The batch may be destroyed afterwards:
+ * a list too long for one batch is added chunk by chunk.
+ * wfa_hip_placer_add_hits appends n hits from host arrays (reverse nullable), for hits aligned elsewhere.
+ * wfa_hip_placer_run groups and reduces ALL hits added so far: rows receives nreads x WFA_HIP_PLACE_COLS int32, row-major; flags,
+ * when not NULL, wfa_hip_placer_count bytes.  It may be called again with other parameters (the grouping is kept), and adds after a
+ * run are legal: the next run sees every hit.  Rows and flags depend on the hits alone, never on scheduling: two runs give identical
+ * bytes.  Kernels: csrc/wfa_place.hpp, k_place.hip (count per read, exclusive scan, scatter; then a wave per read).  A READ WITH A VERY
+ * LARGE GROUP OF HITS IS SERVED BY ONE WAVE; that is the design, not a defect: groups come from n <= WFA_HIP_SEED_MAX_N candidates.
+ * wfa_hip_placer_count: the hits so far.  wfa_hip_placer_clear drops them (the capacity stays).  wfa_hip_placer_kernel_ms: the
+ * HIP-event time of the last run's kernels (0 before the first).
+ * WFA_HIP_EINVAL, nothing launched, nothing appended (wfa_hip_last_error names the first offending position and its values): a batch
+ * of another aligner or without a finished run; i[q] outside [0, nreads); a negative j[q], t_start[q] or text_start[q];
+ * text_end[q] < text_start[q]; full_gap < 1; more than 2^31 - 1 hits in all; a NULL pointer where an array is needed.
+ */
+#define WFA_HIP_PLACE_COLS 8   /* hit, score, second, mapq, hits, ties, text_start, text_end */
+typedef struct wfa_hip_placer wfa_hip_placer_t;
+wfa_hip_placer_t* wfa_hip_placer_create(wfa_hip_aligner_t* aligner, int64_t nreads);
+int  wfa_hip_placer_add(wfa_hip_placer_t* placer, wfa_hip_batch_t* batch, const int32_t* i, const int32_t* j,
+                        const int32_t* t_start /* nullable: 0 */, const uint8_t* reverse /* nullable: forward */);
+int  wfa_hip_placer_add_hits(wfa_hip_placer_t* placer, int64_t n, const int32_t* i, const int32_t* j, const uint8_t* reverse /* nullable */,
+                             const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end);
+int  wfa_hip_placer_run(wfa_hip_placer_t* placer, int32_t min_score, int32_t full_gap, int32_t* rows /* nreads x 8 */,
+                        uint8_t* flags /* nhits, nullable */);
+int64_t wfa_hip_placer_count(const wfa_hip_placer_t* placer);
+int  wfa_hip_placer_clear(wfa_hip_placer_t* placer);
+int  wfa_hip_placer_kernel_ms(const wfa_hip_placer_t* placer, float* ms);
+void wfa_hip_placer_destroy(wfa_hip_placer_t* placer);
+
+/* Host only, needs no GPU: the rule above in plain C++ over arrays of nhits hits in hit-number order (reverse nullable: forward):
+ * what wfa_hip_placer_add_hits + wfa_hip_placer_run give.  Returns WFA_HIP_OK, or WFA_HIP_EINVAL (nothing written; msg, when not NULL,
+ * receives up to msg_cap bytes: the device entries' message) for a negative count, a hit the device entries refuse, full_gap < 1 or
+ * a missing array. */
+int wfa_hip_place_host(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse, const int32_t* score,
+                       const int32_t* status, const int32_t* text_start, const int32_t* text_end, int32_t min_score, int32_t full_gap,
+                       int32_t* rows /* nreads x 8 */, uint8_t* flags /* nhits, nullable */, char* msg, size_t msg_cap);
+
 /* ---- seed finder: an exact-match k-mer index over a text set, candidate windows for every read ------------ */
 
 /*

@@ -72,6 +72,8 @@ SYMBOLS = [
     "wfa_hip_seed_index_create_minimizer", "wfa_hip_seed_index_params", "wfa_hip_minimizers_host", "wfa_hip_seeds_host_minimizer",
     "wfa_hip_chains_host_minimizer",
     "wfa_hip_pileup_calls", "wfa_hip_pileup_sites", "wfa_hip_calls_host", "wfa_hip_sites_host",
+    "wfa_hip_placer_create", "wfa_hip_placer_add", "wfa_hip_placer_add_hits", "wfa_hip_placer_run", "wfa_hip_placer_count",
+    "wfa_hip_placer_clear", "wfa_hip_placer_kernel_ms", "wfa_hip_placer_destroy", "wfa_hip_place_host",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
@@ -83,6 +85,10 @@ CALL_CODES = ("A", "C", "G", "T", "other", "del", "no call")   # the low 3 bits 
 CALL_NONE, CALL_INS = 6, 8
 SITE_COLS = 8
 SITE_COLUMNS = ("j", "pos", "ref", "alt", "depth", "ref_count", "alt_count", "ins_count")
+PLACE_COLS = 8
+PLACE_COLUMNS = ("hit", "score", "second", "mapq", "hits", "ties", "text_start", "text_end")
+PLACE_NOT_ELIGIBLE, PLACE_OTHER_LOCUS, PLACE_SAME_LOCUS, PLACE_PRIMARY = 0, 1, 2, 3   # the flag byte of a hit
+INT32_MIN = -2**31
 SEED_MAX_N, SEED_MAX_HITS = 16, 4096
 SEED_KEYS = ("j", "reverse", "text_start", "text_len", "hits")   # the int32 arrays of a seed query, and overflow (uint8)
 CHAIN_MAX_LOOKBACK, CHAIN_MAX_ANCHORS = 64, 65536
@@ -205,6 +211,18 @@ def lib():
     L.wfa_hip_pileup_sites.argtypes = [vp, vp, i32, i64, i64, i32, i32, i64, ctypes.POINTER(i64), vp]
     L.wfa_hip_calls_host.argtypes = [vp, vp, i64, i32, vp]
     L.wfa_hip_sites_host.argtypes = [vp, vp, i64, i32, i64, i32, i32, i64, ctypes.POINTER(i64), vp]
+    L.wfa_hip_placer_create.argtypes = [vp, i64]
+    L.wfa_hip_placer_create.restype = vp
+    L.wfa_hip_placer_add.argtypes = [vp] * 6
+    L.wfa_hip_placer_add_hits.argtypes = [vp, i64] + [vp] * 7
+    L.wfa_hip_placer_run.argtypes = [vp, i32, i32, vp, vp]
+    L.wfa_hip_placer_count.argtypes = [vp]
+    L.wfa_hip_placer_count.restype = i64
+    L.wfa_hip_placer_clear.argtypes = [vp]
+    L.wfa_hip_placer_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    L.wfa_hip_placer_destroy.argtypes = [vp]
+    L.wfa_hip_placer_destroy.restype = None
+    L.wfa_hip_place_host.argtypes = [i64, i64] + [vp] * 7 + [i32, i32, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -455,6 +473,10 @@ class Aligner:
         """wfa_hip_pileup_create: a zeroed Pileup over the bases of a SeqSet."""
         return Pileup(self, texts)
 
+    def placer(self, nreads):
+        """wfa_hip_placer_create: a Placer over reads 0 .. nreads - 1, without hits."""
+        return Placer(self, nreads)
+
     def seed_index(self, texts, k=13, stride=1, max_occ=64, w=None):
         """wfa_hip_seed_index_create: the k-mer index of a SeqSet (4^k * 4 bytes + 8 bytes per indexed position in HBM).  ``w``:
         wfa_hip_seed_index_create_minimizer instead, the (w,k)-minimizers of the texts (``stride`` plays no part)."""
@@ -552,6 +574,34 @@ def sites_host(counts, ref, seq=0, start=0, min_depth=1, min_permille=500, cap=N
     if lib().wfa_hip_sites_host(*args, int(cap), ctypes.byref(count), _ptr(rows) if rows.size else None) != OK:
         raise ValueError(f"wfa_hip_sites_host: invalid arguments (min_depth = {min_depth}, min_permille = {min_permille}, cap = {cap})")
     return count.value, rows[:min(count.value, rows.shape[0])]
+
+
+def _hit_arrays(i, j, reverse, score, status, text_start, text_end):
+    """The arrays of a hit list as the C entries take them: int32 each, ``reverse`` uint8 0 / 1 or None; one length."""
+    a = {k: np.ascontiguousarray(v, dtype=np.int32) for k, v in
+         (("i", i), ("j", j), ("score", score), ("status", status), ("text_start", text_start), ("text_end", text_end))}
+    a["reverse"] = None if reverse is None else np.ascontiguousarray(np.asarray(reverse) != 0, dtype=np.uint8)
+    n = a["i"].shape[0]
+    for k, v in a.items():
+        if v is not None and v.shape != (n,):
+            raise ValueError(f"{k}: one value per hit ({n})")
+    return a, n
+
+
+def place_host(nreads, i, j, reverse, score, status, text_start, text_end, min_score=INT32_MIN, full_gap=1):
+    """wfa_hip_place_host (host only): ``(rows, flags)`` of the placement rule over a list of hits in hit-number order — rows int32 of
+    shape (nreads, 8) in the columns PLACE_COLUMNS, flags uint8 per hit; what ``Placer.add_hits`` + ``Placer.run`` give."""
+    a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
+    nreads = int(nreads)
+    rows = np.zeros((max(nreads, 0), PLACE_COLS), np.int32)
+    flags = np.zeros(n, np.uint8)
+    msg = ctypes.create_string_buffer(256)
+    p = lambda v: _ptr(v) if v is not None and v.size else None   # noqa: E731
+    rc = lib().wfa_hip_place_host(nreads, n, p(a["i"]), p(a["j"]), p(a["reverse"]), p(a["score"]), p(a["status"]), p(a["text_start"]),
+                                  p(a["text_end"]), int(min_score), int(full_gap), p(rows), p(flags), msg, 256)
+    if rc != OK:
+        raise ValueError(f"wfa_hip_place_host: {msg.value.decode()}")
+    return rows, flags
 
 
 def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16, pad=16, max_hits=2048, w=None):
@@ -850,6 +900,78 @@ class Pileup:
         rc = lib().wfa_hip_pileup_clear(self._h)
         if rc != OK:
             self.aligner._raise(rc, "wfa_hip_pileup_clear")
+
+
+class Placer:
+    """The hits of any number of batches, recorded and grouped by read in HBM (wfa_hip_placer_t); ``run`` reduces every read to one
+    row.  Stays valid after the batches are closed."""
+
+    def __init__(self, aligner, nreads):
+        self.aligner = aligner
+        self.nreads = int(nreads)
+        self._h = lib().wfa_hip_placer_create(aligner._h, self.nreads)
+        if not self._h:
+            msg = aligner.error()
+            if "failed" in msg:
+                raise NativeError(f"wfa_hip_placer_create: {msg}")
+            raise ValueError(f"wfa_hip_placer_create: {msg}")
+        aligner._batches.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().wfa_hip_placer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(lib().wfa_hip_placer_count(self._h))
+
+    def add(self, batch, i, j, t_start=None, reverse=None):
+        """wfa_hip_placer_add: the pairs of a ResidentBatch after its run, pair q a hit of read i[q] on texts[j[q]] from t_start[q]."""
+        i = np.ascontiguousarray(i, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        t_start = None if t_start is None else np.ascontiguousarray(t_start, dtype=np.int32)
+        reverse = None if reverse is None else np.ascontiguousarray(np.asarray(reverse) != 0, dtype=np.uint8)
+        for name, a in (("i", i), ("j", j), ("t_start", t_start), ("reverse", reverse)):
+            if a is not None and a.shape != (batch.n,):
+                raise ValueError(f"{name}: one value per pair of the batch ({batch.n})")
+        rc = lib().wfa_hip_placer_add(self._h, batch._h, _ptr(i), _ptr(j), _ptr(t_start), _ptr(reverse))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_placer_add")
+
+    def add_hits(self, i, j, reverse, score, status, text_start, text_end):
+        """wfa_hip_placer_add_hits: hits from host arrays, in list order."""
+        a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
+        rc = lib().wfa_hip_placer_add_hits(self._h, n, *[_ptr(a[k]) for k in ("i", "j", "reverse", "score", "status", "text_start", "text_end")])
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_placer_add_hits")
+
+    def run(self, min_score=INT32_MIN, full_gap=1, flags=True):
+        """wfa_hip_placer_run over every hit added so far: ``(rows, flags)``, rows int32 of shape (nreads, 8) in the columns
+        PLACE_COLUMNS, flags uint8 per hit (None when ``flags`` is False)."""
+        rows = np.zeros((self.nreads, PLACE_COLS), np.int32)
+        fl = np.zeros(len(self), np.uint8) if flags else None
+        rc = lib().wfa_hip_placer_run(self._h, int(min_score), int(full_gap), _ptr(rows) if rows.size else None, _ptr(fl))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_placer_run")
+        return rows, fl
+
+    def kernel_ms(self):
+        ms = ctypes.c_float(0)
+        rc = lib().wfa_hip_placer_kernel_ms(self._h, ctypes.byref(ms))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_placer_kernel_ms")
+        return ms.value
+
+    def clear(self):
+        rc = lib().wfa_hip_placer_clear(self._h)
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_placer_clear")
 
 
 class SeedIndex:

@@ -1235,6 +1235,55 @@ class WavefrontAligner:
             for s in mine:
                 s.close()
 
+    def place_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
+                      text_len=None, reverse=None, min_score=None, full_gap=None):
+        """Align the listed windows as ``align_windows`` does (same arguments, same checks; either scope) and decide on the GPU where
+        every PATTERN sequence goes: the patterns are reads, each window one candidate hit of read ``i[q]``.  The rule is that of
+        include/wfa_hip.h ("placement"), integers only.  A hit is eligible when its status is 0 and its score at least ``min_score``
+        (None: every hit of status 0); a read's primary is its eligible hit of greatest score, the first in list order on a tie; an
+        eligible hit on the same text and strand whose text interval overlaps the primary's by at least half of the shorter of the
+        two is the same locus found again; the runner-up is the best eligible hit elsewhere.  The interval is the aligned core
+        (first M to last M) under scope full, the whole text window under scope score.  ``mapq`` is 60 without a runner-up, else
+        min(60, 60 * (score - second) // full_gap): a documented confidence, not a calibrated probability.  ``full_gap=None``: six
+        times the mismatch penalty (6 for edit / indel), a runner-up six mismatches behind.
+
+        Returns dict(score=, status=, flag=, reads=): the first three per hit in list order, ``flag`` uint8 (0 not eligible, 1
+        eligible at another locus, 2 at the primary's locus, 3 the primary); ``reads`` a dict of int32 arrays of length
+        ``len(patterns)``: hit (the primary's list position, -1 for a read without an eligible hit), score, second (-2**31 without
+        a runner-up), mapq, hits (eligible), ties (runner-ups that equal the primary's score), text_start, text_end (the primary's
+        interval on its text).  Neither scores nor locations are grouped on the host: 32 bytes per read and a byte per hit come
+        back (csrc/wfa_place.hpp).  With ``devices=[...]`` the first device runs it."""
+        for name, v in (("min_score", min_score), ("full_gap", full_gap)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise ValueError(f"{name} must be an integer or None, got {v!r}")
+        if min_score is not None and not -2**31 <= int(min_score) < 2**31:
+            raise ValueError(f"min_score = {min_score} does not fit 32 bits")
+        if full_gap is None:
+            full_gap = 6 * int(self._cfg.mismatch) if self._cfg.distance >= 2 else 6
+        if not 1 <= int(full_gap) < 2**31:
+            raise ValueError(f"full_gap = {full_gap} is out of range (at least 1)")
+        patterns, texts, arrays, wlen = self._window_lists(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
+        ii, jj, ts, rev = arrays[0], arrays[1], arrays[4], arrays[6]
+        self._sync_wildcard()
+        sets, mine = self._open_sets(patterns, texts)
+        placer = None
+        try:
+            placer = self._native.placer(len(patterns))
+
+            def add(rb, lo, hi, score, status):
+                placer.add(rb, ii[lo:hi], jj[lo:hi], None if ts is None else ts[lo:hi], None if rev is None else rev[lo:hi])
+
+            out = self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, each=add)
+            rows, flags = placer.run(_native.INT32_MIN if min_score is None else int(min_score), int(full_gap))
+            out["flag"] = flags
+            out["reads"] = {name: np.ascontiguousarray(rows[:, c]) for c, name in enumerate(_native.PLACE_COLUMNS)}
+            return out
+        finally:
+            if placer is not None:
+                placer.close()
+            for s in mine:
+                s.close()
+
     def score_matrix(self, patterns, texts=None):
         """Score every pattern against every text on the GPU: returns ``(score, status)``, int32 arrays of shape (M, N).
 

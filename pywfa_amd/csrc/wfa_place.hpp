@@ -1,0 +1,70 @@
+// wfa_place.hpp — device-side result surface, per READ (wfa_hip_placer_*): the hits of any number of batches recorded where they lie,
+// grouped by read, and every read reduced to one row — its primary hit, the runner-up at another locus, a mapping quality, counts —
+// with one flag byte per hit.  32 bytes per read and 1 byte per hit cross PCIe.
+//
+// Rule (include/wfa_hip.h, "placement"; wfa_hip_place_host in host_place.cpp is its plain statement, needing no GPU).  A hit is
+// eligible iff status == 0 && score >= min_score.  The primary p of a read is its eligible hit of greatest score, the smallest hit
+// number on a tie.  Eligible h is at p's locus iff h != p, same j, same strand, and ov = min(te) - max(ts) has ov > 0 and
+// 2 ov >= min(te_h - ts_h, te_p - ts_p).  second / ties are over the eligible hits that are neither p nor at its locus; mapq is 60
+// without one, else min(60, 60 (score_p - second) / full_gap).
+//
+// Layout on the device, 37 bytes per hit: a 32-byte record (PlaceHit: two 16-byte loads), its 4-byte slot in the grouped order, its
+// flag byte; per read a 4-byte counter and the 32-byte row.  The records are appended in hit-number order and never move: a hit's
+// number is its index.
+//
+// Kernels (k_place.hip):
+//   record   per pair of a batch after its run, one PlaceHit.  Scope full: a wave per pair, the walk of wfa_summary.hpp
+//            (summary_scan: 64 ops per round, ballots) for the text bases in front of the first and behind the last M, so that the
+//            interval is columns 8 and 9 of the summary.  Scope score: a thread per pair, the whole window.
+//   group    count (a thread per hit, one atomicAdd on its read's counter), an inclusive scan of the nreads + 1 counters in the
+//            three passes of the seed index's table (chunk sums, their prefix in one workgroup, apply: a counter becomes the END of
+//            its group), scatter (a thread per hit: atomicSub on the counter gives its slot, the counter ends as the group's BEGIN,
+//            counter[nreads] stays the number of hits).  The order inside a group depends on scheduling; nothing below does.
+//   place    one wave per read, grid-stride; the lanes stride the group.  Pass 1: the wave-wide maximum of the 64-bit key
+//            (score ^ 0x80000000) << 32 | ~hit number — greatest score, then smallest number; eligible keys are never 0.  Pass 2: the
+//            same-locus test against p's record, the flags, and wave reductions for second (a maximum), ties, hits and the number
+//            of runner-up candidates.  Groups longer than 64 loop; lanes 0 .. 7 store the row.  No LDS.
+//            A READ WITH A VERY LARGE GROUP IS SERVED BY ONE WAVE (two passes of group / 64 rounds).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "wfa_common.hpp"
+
+namespace wfa {
+
+#define WFA_PLACE_COLS 8
+#define WFA_PLACE_SCAN_CHUNK 4096   // counters per workgroup of the scan: 256 threads x 16
+
+struct alignas(16) PlaceHit {
+  int32_t i, j, reverse, status;   // read, text, strand (0 / 1), the pair's status
+  int32_t score, ts, te, spare;    // its score, the text interval [ts, te) in coordinates of text j; spare: 0
+};
+
+struct PlaceRecordArgs {
+  // the batch (after its run)
+  const int32_t* score; const int32_t* status; const WfaPairMeta* meta;
+  const uint8_t* ops; const int64_t* cigar_begin; const int32_t* cigar_len;   // scope full only
+  int64_t npairs;
+  // the list
+  const int32_t* i; const int32_t* j;
+  const int32_t* t_start;    // [npairs] or nullptr: 0
+  const uint8_t* reverse;    // [npairs] or nullptr: forward
+  PlaceHit* out;             // [npairs]: the placer's records from its first free one
+};
+
+struct PlaceArgs {
+  const PlaceHit* hits; int64_t nhits;
+  int64_t nreads;
+  uint32_t* count;           // [nreads + 1]: zero before the count pass; ends after the scan; begins (and [nreads] = nhits) after the scatter
+  uint32_t* bsum;            // [ceil((nreads + 1) / WFA_PLACE_SCAN_CHUNK)]
+  uint32_t* order;           // [nhits] hit numbers, group by group
+  int32_t min_score, full_gap;
+  int32_t* rows;             // [nreads x WFA_PLACE_COLS]
+  uint8_t* flags;            // [nhits]
+};
+
+int launch_place_record(const PlaceRecordArgs& a, bool full, int cu_count, hipStream_t stream);
+int launch_place_group(const PlaceArgs& a, hipStream_t stream);   // count, scan, scatter (a.count zeroed by the caller)
+int launch_place(const PlaceArgs& a, int cu_count, hipStream_t stream);
+
+}  // namespace wfa

@@ -74,3 +74,19 @@ cdef extern from "wfa_hip.h" nogil:
     int wfa_hip_calls_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t min_depth, uint8_t* out)
     int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t seq, int64_t start, int32_t min_depth,
                             int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows)
+    # placement: one row per read from the hits of any number of batches (include/wfa_hip.h: "placement")
+    ctypedef struct wfa_hip_batch_t
+    ctypedef struct wfa_hip_placer_t
+    wfa_hip_placer_t* wfa_hip_placer_create(wfa_hip_aligner_t* aligner, int64_t nreads)
+    int wfa_hip_placer_add(wfa_hip_placer_t* placer, wfa_hip_batch_t* batch, const int32_t* i, const int32_t* j, const int32_t* t_start,
+                            const uint8_t* reverse)
+    int wfa_hip_placer_add_hits(wfa_hip_placer_t* placer, int64_t n, const int32_t* i, const int32_t* j, const uint8_t* reverse,
+                            const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end)
+    int wfa_hip_placer_run(wfa_hip_placer_t* placer, int32_t min_score, int32_t full_gap, int32_t* rows, uint8_t* flags)
+    int64_t wfa_hip_placer_count(const wfa_hip_placer_t* placer)
+    int wfa_hip_placer_clear(wfa_hip_placer_t* placer)
+    int wfa_hip_placer_kernel_ms(const wfa_hip_placer_t* placer, float* ms)
+    void wfa_hip_placer_destroy(wfa_hip_placer_t* placer)
+    int wfa_hip_place_host(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse, const int32_t* score,
+                            const int32_t* status, const int32_t* text_start, const int32_t* text_end, int32_t min_score,
+                            int32_t full_gap, int32_t* rows, uint8_t* flags, char* msg, size_t msg_cap)
