@@ -1682,12 +1682,10 @@ static int ensure_ws(wfa_hip_aligner* al, size_t bytes) {
   return WFA_HIP_OK;
 }
 
-// memory_mode medium / low: the general kernel keeps the piggy-back history (one byte of origin codes per cell) instead of the
-// explicit arena (full scope, gap-affine / gap-affine-2p; WFA_HIP_GENERAL_PB = 0 / 1 overrides)
-// history of the general kernel: one byte of origin codes per cell (PB) instead of the offsets — memory modes medium / low, and, like
-// the banded kernel's split stage, reads over 20 kb in every mode (round 3: the explicit arena of a 100 kb pair overflows and is re-run 8x
-// larger, with a host round trip each time: C5-shaped wf-adaptive 10.8 k -> 16 k aln/s); WFA_HIP_BAND_PB=0 / WFA_HIP_GENERAL_PB=0 keep
-// the explicit offsets
+// history of the general kernel: the piggy-back form — one byte of origin codes per cell instead of the explicit arena of offsets (full
+// scope, gap-affine / gap-affine-2p) — in memory modes medium / low, and, like the banded kernel's split stage, for reads over 20 kb in
+// every mode (round 3: the explicit arena of a 100 kb pair overflows and is re-run 8x larger, with a host round trip each time: C5-shaped
+// wf-adaptive 10.8 k -> 16 k aln/s); WFA_HIP_GENERAL_PB = 0 / 1 overrides, WFA_HIP_BAND_PB=0 / WFA_HIP_GENERAL_PB=0 keep the explicit offsets
 static bool general_pb(const wfa_hip_aligner* al, const wfa_hip_config_t& c, int ncomp, int max_len) {
   if (c.scope != WFA_SCOPE_FULL || ncomp < 3) return false;
   const int e = knob(al, K_GENERAL_PB, -1);
@@ -1797,6 +1795,1217 @@ extern "C" int wfa_hip_batch_run(wfa_hip_batch_t* b, void* stream_) {
   return rc;
 }
 
+// ---- words of wfa_hip_batch::d_counters as a run uses them ------------------------------------------
+enum CounterWord {
+  CNT_OVF = 1,             // [1], [2]: overflow counts A / B (retry_overflows alternates between them)
+  CNT_BIWFA_FB = 4,        // [4 + kind]: what the BiWFA kernel hands to the general kernel (the pilots of batch_build use [4..5] before a run)
+  CNT_LANEFULL_LIST = 8,   // pairs the walks of the lane-full stage hand on (short reads)
+  CNT_DEBUG = 8,           // [8..15]: counting builds of the band / tile kernels under stage timing (long reads)
+  CNT_DEBUG_WORDS = 8,
+  CNT_LANE_DYN0 = 12,      // run-time slices: the first lane stage,
+  CNT_LANEH_DYN = 13,      // the heuristic lane stage,
+  CNT_LANE_DYN1 = 14,      // the lane stage behind the first
+  CNT_STAGE = 16,          // [16 + i]: hand-over count of the run's i-th stage
+  CNT_STAGE_MAX = 48,      // (a run has at most 1 + 3 + 6 + 1 + 1 + 3 + 1 + 1 + 3 = 20 stages)
+  CNT_SNAP_A = 64,         // [64 + j]: the split stage's hand-over count before its launch j (the pipelined tail)
+  CNT_SNAP_B = 160,        // [160 + j]: the same for the stage behind it
+  CNT_SNAP_LAUNCHES = 90   // launches a pipelined split stage may have: words [j] .. [j + 1] are used, j < 90
+};
+static_assert(CNT_DEBUG + CNT_DEBUG_WORDS <= CNT_STAGE && CNT_LANE_DYN1 < CNT_STAGE, "the fixed counters end before the stage counts");
+static_assert(CNT_STAGE + CNT_STAGE_MAX <= CNT_SNAP_A, "stage counts run into the snapshots");
+static_assert(CNT_SNAP_A + CNT_SNAP_LAUNCHES + 1 <= CNT_SNAP_B, "the two snapshot ranges overlap");
+static_assert(CNT_SNAP_B + CNT_SNAP_LAUNCHES + 1 <= WFA_COUNTER_WORDS, "snapshots beyond the counters of a batch");
+
+// ---- run state of the cascade ---------------------------------------------------------------------------
+// The list a stage reads and where it leaves what it hands on: leftovers go to d_fb_list2[out_sel]; their count: a word of its own
+// per stage (zeroed with all the counters at the start of the run: round 4 — a fill per stage was 9 x 4.5 us of a 3.2 ms C2 step)
+struct Chain {
+  const uint32_t* in_list;             // nullptr = identity
+  const uint32_t* in_count = nullptr;  // nullptr = host count
+  uint32_t in_n;
+  int out_sel = 0;
+  int stage_counts = 0;
+  bool first_stage = true;
+  uint32_t* out_list(const wfa_hip_batch* b) const { return b->d_fb_list2[out_sel]; }
+  uint32_t* next_count(const wfa_hip_batch* b) {
+    uint32_t* c = b->d_counters + CNT_STAGE + stage_counts;
+    if (stage_counts < CNT_STAGE_MAX - 1) ++stage_counts;
+    return c;
+  }
+  // the next stage reads what this one handed on; the selector stays (the pipelined tail: it used both lists)
+  void hand_on(wfa_hip_batch* b, const uint32_t* list, const uint32_t* count) {
+    if (first_stage) b->last_kernel_pairs = in_n;
+    in_list = list; in_count = count; first_stage = false;
+  }
+  void advance(wfa_hip_batch* b, const uint32_t* list, const uint32_t* count) { hand_on(b, list, count); out_sel ^= 1; }
+};
+
+// WFA_HIP_STAGE_TIMING, a development aid: the time of a stage between two events, and what it handed on.  It synchronises.
+struct StageTimer {
+  hipStream_t stream; bool on; hipEvent_t e0 = nullptr, e1 = nullptr;
+  StageTimer(const wfa_hip_aligner* al, hipStream_t s) : stream(s), on(knob(al, K_STAGE_TIMING, 0) != 0) {
+    if (on) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, stream); }
+  }
+  float stop(const uint32_t* out_count, uint32_t* handed) {
+    (void)hipEventRecord(e1, stream); (void)hipEventSynchronize(e1);
+    float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipMemcpy(handed, out_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return ms;
+  }
+};
+
+// ---- fields that every stage's arguments share (FastArgs / BandArgs / TileArgs / WideArgs / WfaKernelArgs) ----
+template <class Args> static void fill_cigar_out(Args& a, const wfa_hip_batch* b) {
+  a.cigar_ops = b->d_ops; a.cigar_off = b->d_cigar_off; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len;
+}
+// (need_free_len: the register and banded kernels take the ends-free path only when an end is free at all; the tile and wide kernels
+// whenever the span is ends-free)
+template <class Args> static void fill_ends_free(Args& a, const WfaDevConfig& d, bool need_free_len) {
+  a.ef = (d.endsfree && (!need_free_len || (d.pbf | d.pef | d.tbf | d.tef))) ? 1 : 0;
+  a.pbf = d.pbf; a.pef = d.pef; a.tbf = d.tbf; a.tef = d.tef;
+}
+template <class Args> static void fill_heuristic(Args& a, const WfaDevConfig& d) {
+  a.heur = d.heuristic; a.min_wf_len = d.min_wf_len; a.max_dist_thr = d.max_dist_thr;
+  a.steps_between = d.steps_between; a.max_steps = d.max_steps;
+}
+static int affine_gcd(const WfaDevConfig& d) { return wfa::gcd_int(wfa::gcd_int(d.x, d.o1 + d.e1), d.e1); }
+
+// ---- the plan of the cascade ------------------------------------------------------------------------------
+struct WideStage { wfa::WideArgs a; int grid = 0, threads = 0; size_t smem = 0, hist_off = 0; bool grows = false, w32 = false; };
+struct TileStage { wfa::TileArgs a; int grid = 0, threads = 0; size_t smem = 0, hist_off = 0; bool on = false, w32 = false; };
+
+// What plan_cascade decides and the launchers read: which stages run, their grids, and every offset into the one workspace.  A plain
+// value on the stack, built again for every run (wfa_hip_batch_run may run a batch twice, the second time without run-time kernels).
+struct CascadePlan {
+  bool tiny = false, lin = false, adapt = false;
+  bool use_fast = false, use_segfull = false, use_laneh = false, use_segh = false, use_lanefull = false;
+  int laneh_form = 1;                       // (2: 32 diagonals per pair)
+  int shape = -1, sh_x = 0, sh_oe = 0, sh_e = 0;   // wfa::seg_shape of the run's penalties, and the penalties over their gcd
+  bool lane_shape_fits = false;             // a built-in shape, or a run-time one whose rings fit the lane kernel's registers
+  int64_t budget = 0;                       // free_budget at the top of the plan (nothing in it allocates)
+  bool wide_adapt = false, wide_ok = false, wide32 = false, wide_two = false;
+  // band stages
+  int n_stages = 0;
+  int band_nch[3] = {0, 0, 0};
+  long long band_grid[3] = {0, 0, 0};
+  int64_t band_stride[3] = {0, 0, 0};
+  bool pb_mode = false;
+  int64_t pb_code_ints = 0, pb_event_ints = 0, pb_stride = 0;
+  size_t split_region = 0, later_need = 0;   // bytes of the split stage's slots; largest history of the band stages behind it
+  size_t later_off = 0, gen_off = 0;
+  int gen_grid = 0;
+  int64_t gen_stride = 0;
+  bool want_pipe_tail = false;
+  // tile and wide stages
+  wfa::WideArgs w0;                          // what the tile and wide stages share: penalties over their gcd, sequence words
+  int full_range = 0;                        // the whole diagonal range of the longest pair
+  TileStage tile_stage;
+  WideStage wide_stage[3];
+  int n_wide = 0;
+  // full CIGARs of short reads
+  int n_segfull = 0;
+  int segfull_w[3] = {16, 32, 64};
+  int64_t segfull_slot_ints[3] = {0, 0, 0}, segfull_cap[3] = {0, 0, 0};
+  int64_t lanefull_slot_bytes = 0, lanefull_cap = 0;
+  long long lanefull_grid = 0;
+  int lanefull_recs = 0, lf_min_pairs = 256;
+  size_t lanefull_off = 0, lanefull_codes_off = 0, lanefull_codes_bytes = 0, lanefull_list_off = 0;
+  int lanefull_split = 1;   // > 1: every launch has slots and code lists of its own
+  Geometry g;               // the general kernel at the end
+  size_t need = 0;          // bytes of workspace the run asks for
+};
+
+// which band windows (in chunks of 64 diagonals) the banded stages run, in order
+static void plan_band_windows(const wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePlan& p) {
+  if (!p.lin && !p.tiny && wfa::band_supported(b->dcfg, b->ncomp) && (b->ncomp != 5 || b->max_len < 32000) && knob(al, K_NO_BAND, 0) == 0) {
+    if (b->ncomp == 5) {
+      // gap-affine-2p wavefronts are wide (C4: 99 % need more than 108 diagonals, 2.6 % more than 172)
+      if (b->band_pick != 2) { p.band_nch[p.n_stages++] = 3; p.band_nch[p.n_stages++] = 4; }   // (2: the pilot of batch_build saw most pairs outgrow 256 diagonals)
+    } else if (p.adapt) {
+      // (the wavefront a cut-off keeps grows with the read: at 10 kb 3 % of the pairs outgrow the 128-diagonal window, at 100 kb 46 % —
+      // and a second stage of few, lone waves runs at its pairs' latency: reads over 20 kb start in the 256-diagonal window.
+      // 8 192 x 100 kb wf-adaptive: 509 -> 359 ms)
+      if (b->max_len <= 300) { p.band_nch[p.n_stages++] = 1; }
+      if (b->max_len <= 20000) p.band_nch[p.n_stages++] = 2;
+      p.band_nch[p.n_stages++] = 4;
+    } else if (b->max_len <= 300) {
+      if (!p.use_fast && !p.use_segfull) p.band_nch[p.n_stages++] = 1;
+      p.band_nch[p.n_stages++] = 2; p.band_nch[p.n_stages++] = 4;
+    } else if (b->max_len <= 1200) {
+      if (b->band_pick != 2) p.band_nch[p.n_stages++] = 4;   // (2: the pilot of batch_build saw most pairs outgrow the window)
+    }
+    const int only = knob(al, K_BAND_NCH, 0);
+    if (only) { p.n_stages = 1; p.band_nch[0] = only; }
+  }
+}
+
+// history and workspace regions of the band stages: grids, strides, the split stage's slots, the regions behind them
+static void plan_band_stages(wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePlan& p) {
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  const uint32_t in_n = b->n_packed;
+  // band history: fixed-stride records per score step, one slice per wave
+  // The split stage (long reads) keeps the piggy-back history (the reference's R/wavefront_backtrace_offload.c scheme): one
+  // byte of origin codes per (step, diagonal) instead of the offsets, the matches re-extended afterwards.  In EVERY
+  // memory mode: the op strings are the same and it is the faster form (C3 91 vs 97 ms per 100 k pairs, C4 adaptive 57 vs
+  // 77 ms per 10 k: 8-16x less history, so more pairs per launch); WFA_HIP_BAND_PB=0 keeps the explicit offsets.
+  const int pb_env = knob(al, K_BAND_PB, -1);
+  p.pb_mode = full && (pb_env >= 0 ? pb_env != 0 : true);
+  // Round 6, the pipelined tail (16 % of a C4-adaptive run was a latency tail — the 256-diagonal stage 22.7 ms
+  // and the general kernel 17.4 ms for ONE pair, both after the last launch of the split stage).  What launch j of the split stage
+  // hands on is aligned by the stage behind it — and what THAT hands on by the general kernel — on a third stream beside launch
+  // j + 1: [snapshot of the hand-over count before, after) is the launch's part of the list (BandArgs::wbeg_dev).  Only the last
+  // launch's leftovers remain exposed.  Needs a region of its own for each of the two (behind the split stage's slots), two band
+  // stages, long reads with CIGARs (the split form), no tile / wide stage in the chain.  WFA_HIP_PIPE_TAIL=0: off
+  p.want_pipe_tail = full && p.n_stages == 2 && b->max_len > 1000 && knob(al, K_PIPE_TAIL, 1) != 0 && knob(al, K_NO_DUAL, 0) == 0 &&
+                     knob(al, K_STAGE_TIMING, 0) == 0 && !al->knobs.set[K_BAND_LEFTOVER_WAVES_PER_CU];
+  for (int i = 0; i < p.n_stages; ++i) {
+    // 4x more waves than a CU holds at once: waves retire one after the other (oldest-first issue) and the
+    // dispatcher refills the CU, instead of a tail of lone waves (C1 +20 %, C3 +13 %)
+    long long grid = (long long)al->cu_count * knob(al, K_BAND_WAVES_PER_CU, 128);
+    grid = std::min<long long>(grid, in_n);
+    if (i > 0 || p.use_fast || p.use_laneh || p.use_segh || p.use_segfull) grid = std::min<long long>(grid, (long long)al->cu_count * knob(al, K_BAND_LEFTOVER_WAVES_PER_CU, 64));
+    if (i > 0 && p.want_pipe_tail) grid = std::min<long long>(grid, (long long)al->cu_count * 8);   // (one launch's leftovers at a time: a few hundred pairs; the history slices are tens of megabytes each)
+    if (full) {
+      const bool h16 = b->max_len < 32000;
+      const int rec = ((h16 && b->ncomp != 5) ? 2 : 4) * (p.band_nch[i] == 3 ? 256 : 64 * p.band_nch[i]);  // ints per record (2p: 16-byte entries)
+      // steps of an alignment = score / g; sized for scores up to 0.9 x the read length (about 15 % divergence)
+      long long records = std::max<long long>(256, (long long)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / wfa::band_gcd(b->dcfg, b->ncomp == 5) + 64);
+      records = knob(al, K_BAND_RECORDS, (int)records);
+      p.band_stride[i] = ((int64_t)records * rec + 63) & ~63ll;
+      const int64_t budget = p.budget;
+      while (grid > 1 && grid * p.band_stride[i] * 4 > budget) grid = (grid + 1) / 2;
+      p.need = std::max(p.need, (size_t)grid * p.band_stride[i] * 4);
+      if (i == 0 && !p.use_fast && !p.use_segfull && b->max_len > knob(al, K_BAND_SPLIT_MIN, 100) && knob(al, K_BAND_NO_SPLIT, 0) == 0) {
+        // split backtrace: one history slot per pair of a launch; take up to 4x the wave count (or all pairs)
+        if (p.pb_mode) {
+          p.pb_code_ints = ((int64_t)records * ((p.band_nch[i] == 3 ? 256 : 64 * p.band_nch[i]) / 4) + 63) & ~63ll;  // one byte per window position and step
+          p.pb_event_ints = (((int64_t)records + 3) / 4 + 63) & ~63ll;                 // one byte per edit event (<= one per step)
+          p.pb_stride = p.pb_code_ints + p.pb_event_ints + ((2 * (int64_t)records + 8 + 63) & ~63ll);  // + run records
+        }
+        const int64_t slot_bytes = (p.pb_mode ? p.pb_stride : p.band_stride[i]) * 4 + 16;
+        // slots for every pair of the batch when they fit half of the free memory (the compact piggy-back history: C3 0.3 MB
+        // per pair), otherwise for as many pairs as do (explicit history: up to 4 x the resident waves)
+        int64_t pairs = in_n;
+        if (pairs * slot_bytes > budget / 2) {
+          // (round 6: gap-affine-2p 8 — its kernel holds 12 waves per CU, so a launch of cu_count x 64 pairs was 1.17 rounds of resident
+          // waves with most of the chip idle in the second one; with twice the slots a launch is 2.7 rounds: C4-adaptive 214 -> 204 ms)
+          pairs = std::min<int64_t>(in_n, (int64_t)al->cu_count * 32 * knob(al, K_BAND_SPLIT_ROUNDS, b->ncomp == 5 ? 8 : 4));
+          while (pairs > 1 && pairs * slot_bytes > budget) pairs = (pairs + 1) / 2;
+        }
+        p.split_region = ((size_t)(pairs * slot_bytes) + 255) & ~(size_t)255;
+        p.need = std::max(p.need, p.split_region);
+      } else if (i > 0) {
+        p.later_need = std::max(p.later_need, (size_t)grid * p.band_stride[i] * 4);
+      }
+    }
+    p.band_grid[i] = grid;
+  }
+  // the band stages behind a split stage get a region of their own behind its slots when both fit: the walks of the split
+  // stage's last launch then run under them
+  p.gen_stride = p.g.ws_stride;
+  if (p.split_region && p.later_need && (int64_t)(p.split_region + p.later_need) <= p.budget) {
+    p.later_off = p.split_region;
+    p.need = std::max(p.need, p.split_region + p.later_need);
+    if (p.want_pipe_tail) {   // ... and the general kernel behind them a few slices of its own
+      // (a pair that reaches it has outgrown 256 diagonals: the arena of the first attempt would overflow and the pair be re-run with
+      // an 8 x larger one after a host round trip — 62 ms for ONE pair of a C4-adaptive run; these few slices start that large)
+      p.gen_grid = std::max(1, std::min(p.g.grid, 16));
+      const size_t at = (p.split_region + p.later_need + 255) & ~(size_t)255;
+      if (full) p.gen_stride = ((b->arena_fixed + 8 * b->arena_ints) + 63) & ~63ll;
+      size_t gen_need = (size_t)p.gen_grid * (size_t)p.gen_stride * 4;
+      if ((int64_t)(at + gen_need) > p.budget) { p.gen_stride = p.g.ws_stride; gen_need = (size_t)p.gen_grid * (size_t)p.gen_stride * 4; }
+      if ((int64_t)(at + gen_need) <= p.budget) { p.gen_off = at; p.need = std::max(p.need, at + gen_need); }
+    }
+  }
+}
+
+// Round 4: the temporally blocked form (wfa_tile.hpp) goes first for exact alignments with int16 rows: a wave advances a
+// block of diagonals by T steps inside an LDS tile, the rows in the workspace are read and written once per T steps.  What it
+// hands on (pairs where the reference's per-step trimming would change a value, a history that does not fit) goes to the
+// step-by-step forms below.  WFA_HIP_TILE=0: off; WFA_HIP_TILE_T / _WT / _THREADS / _PER_CU: geometry
+// (round 6: reads of up to 32 000 bases on int16 rows — their NULL is -32768.  Longer ones: wfa_tile_kernel<.., W32> — int32 cells,
+// the sequences read from global memory (50 KB of them per workgroup in LDS left one workgroup per CU), eight waves per pair.  One
+// workgroup per pair needs pairs to fill the chip: exact 100 kb score, 512 / 1 024 pairs 345 / 351 aln/s against 275 / 192 on the
+// step-by-step forms below, but 256 pairs 238 against 290 and 64 pairs 62 against 104 — so from two pairs per CU on.
+// WFA_HIP_TILE32 = 0 never, 1 always)
+static void plan_tile_stage(const wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePlan& p) {
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  const uint32_t in_n = b->n_packed;
+  const wfa::WideArgs& w0 = p.w0;
+  const int64_t budget = p.budget;
+  const bool tile32 = b->max_len > WFA_TILE_MAX_LEN;
+  const int tile_cb = tile32 ? 4 : 2;
+  const int tile32_knob = knob(al, K_TILE32, -1);
+  const bool tile32_on = tile32_knob >= 0 ? tile32_knob != 0 : (int64_t)in_n >= 2 * (int64_t)al->cu_count;
+  if (b->dcfg.heuristic == WFA_HEUR_NONE && (!tile32 || (tile32_on && 2 * (int64_t)b->max_len < ((int64_t)1 << 29))) && knob(al, K_TILE, 1) != 0) {
+    wfa::TileArgs& ta = p.tile_stage.a;
+    memset(&ta, 0, sizeof(ta));
+    wfa::TileGeom& tg = ta.g;
+    tg.X = w0.X; tg.OE = w0.OE; tg.E = w0.E; tg.OE2 = w0.OE2; tg.E2 = w0.E2;
+    tg.DM = std::max(std::max(tg.X, tg.OE), tg.OE2);
+    // geometry by read length (round 5): reads of up to 8 kb have wavefronts of a few hundred diagonals and scores of a few hundred
+    // steps — tiles of 128 diagonals advanced 8 steps by two waves per alignment keep more alignments in flight and waste less of
+    // a tile on halo (1 kb at 5 %: 4.3 -> 6.6 M aln/s, 2 kb at 1 %: 6.8 -> 15.1 M, 600 bp at 10 %: 3.9 -> 5.9 M; 4 kb at 5 %: equal)
+    const bool small_geom = !p.wide_two && b->max_len <= 8000;   // (3 / 5 / 7 kb at 5 %: equal / +10 % / +2 % score, 5 kb full +35 %; 10 kb: -20 %)
+    p.tile_stage.w32 = tile32;
+    tg.T = knob(al, K_TILE_T, (p.wide_two || small_geom) ? 8 : 16) & ~1;
+    tg.Wt = tile32 ? (p.wide_two ? 128 : 256) : knob(al, K_TILE_WT, (p.wide_two || small_geom) ? 128 : 256);   // (int32 cells: the two widths that exist)
+    const int bw = tg.Wt - 2 * tg.T;
+    // (gap-affine-2p reads of up to 1.2 kb: one wave per alignment — 300 / 600 / 1 000 bp at 8 %: +28 / +51 / +29 % over four;
+    // round 6: gap-affine reads over 16 kb eight waves — 30 kb, 512 pairs: 128 / 256 / 512 threads 4.6 / 8.7 / 11.7 k aln/s; 10 kb keeps 256)
+    const int tthreads = std::max(64, std::min(512, knob(al, K_TILE_THREADS, (tile32 || (!p.wide_two && b->max_len > 16000)) ? 512 : small_geom ? 128 : (p.wide_two && b->max_len <= 1200) ? 64 : 256) & ~63));
+    if (tg.T >= 2 && tg.T <= WFA_TILE_MAX_T && tg.Wt >= 64 && tg.Wt % 64 == 0 && tg.Wt <= 256 && bw >= 16 &&
+        wfa::tile_cand_count(tg) <= WFA_TILE_MAX_ROWS) {
+      ta.gs = w0.g; ta.seq_words = tile32 ? 0 : w0.seq_words;   // (int32 form: the sequences stay in global memory)
+      const int nbmax = (2 * b->max_len + 1 + bw - 1) / bw;
+      ta.rwh = (nbmax * bw + 2 * tg.T + 1) & ~1;
+      ta.rows_stride = ((int64_t)wfa::tile_hbm_rows(tg) * ta.rwh + 63) & ~63ll;
+      p.tile_stage.threads = tthreads;
+      p.tile_stage.smem = wfa::tile_smem_bytes(tg, ta.seq_words, tthreads / 64, tile_cb);
+      if (p.tile_stage.smem <= (size_t)160 * 1024) {
+        int per_cu = wfa::tile_occupancy(full, p.wide_two, tg.Wt / 64, tthreads, p.tile_stage.smem, tile32);
+        per_cu = std::max(1, std::min(per_cu, knob(al, K_TILE_PER_CU, 16)));
+        p.tile_stage.grid = (int)std::min<int64_t>((int64_t)al->cu_count * per_cu, in_n);
+        int64_t hist_bytes = 0;
+        if (full) hist_bytes = (int64_t)p.full_range * ((int64_t)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / w0.g + 64 + tg.T) / 2 + (1 << 20);
+        while (p.tile_stage.grid > 1 && (int64_t)p.tile_stage.grid * (ta.rows_stride * tile_cb + hist_bytes) > budget) p.tile_stage.grid = (p.tile_stage.grid + 1) / 2;
+        if ((int64_t)p.tile_stage.grid * (ta.rows_stride * tile_cb + hist_bytes) <= budget) {
+          ta.hist_stride = (hist_bytes / 4) & ~15ll;
+          p.tile_stage.hist_off = ((size_t)p.tile_stage.grid * (size_t)ta.rows_stride * tile_cb + 255) & ~(size_t)255;
+          p.need = std::max(p.need, p.tile_stage.hist_off + (size_t)p.tile_stage.grid * (size_t)ta.hist_stride * 4);
+          p.tile_stage.on = true;
+        }
+      }
+    }
+  }
+}
+
+// Wide-wavefront stage (wfa_wide.hpp): exact gap-affine pairs the register windows cannot hold (or never try: reads
+// over 1.2 kb without a heuristic) — one alignment per workgroup, the wavefront rows in LDS; what it hands on goes to
+// the general kernel.  Rows as wide as LDS allows, at most the whole diagonal range of the longest pair.
+// Up to two such stages: rows in LDS (gap-affine: the faster form, 23.3 vs 21.7 k aln/s at 10 kb, but ~7 900 diagonals at
+// most), then rows in the workgroup's slice of the HBM workspace (as wide as the whole diagonal range of the longest pair: no
+// pair outgrows them; gap-affine-2p has only this form: its M ring alone is o2 + e2 + 1 rows).
+static void plan_wide_stages(const wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePlan& p) {
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  const uint32_t in_n = b->n_packed;
+  const wfa::WideArgs& w0 = p.w0;
+  const int64_t budget = p.budget;
+  const int nrows = wfa::wide_rows(w0.X, w0.OE, w0.E, w0.OE2, w0.E2);
+  bool lds_covers_all = false;
+  // Round 3: the pass of a step is a short dependent chain (row reads -> recurrences -> sequence reads -> stores -> barrier),
+  // so a CU is kept busy by MANY pairs in flight, not by many threads on one pair: with rows in the workspace (L2) a workgroup
+  // needs only its sequences in LDS, and 8 workgroups of 256 threads per CU align 10 kb reads 1.6x faster than one workgroup
+  // of 1 024 threads with its rows in LDS (36.8 k vs 23.3 k aln/s; gap-affine-2p: 4 x 512 threads, +25 %).  The LDS form
+  // (north_star's layout) remains what a small batch gets: all of a CU's threads on one pair is the shortest latency.
+  // WFA_HIP_WIDE_GROWS: 1 = workspace rows always, 0 = LDS rows first always
+  const int grows_knob = knob(al, K_WIDE_GROWS, -1);
+  const bool many_pairs = (int64_t)in_n >= (int64_t)al->cu_count * 2;
+  const bool prefer_ws = grows_knob >= 0 ? grows_knob != 0 : many_pairs;
+  // threads per workgroup of the workspace form: 256 (gap-affine-2p: 512) once the batch has a pair for every CU's four
+  // workgroup slots of that size — measured on 2 000 x 10 kb: 128 threads 35.1 k, 256: 36.8 k, 384: 31.0 k, 512: 32.6 k, 1 024: 21.6 k aln/s
+  // (8 192 x 10 kb: 128 threads 200 / 231 ms score / full, 256: 207 / 241; C4 as written, 4 096 pairs: 256 threads 705 ms, 512: 740,
+  // 384: 925, 128: 719; the 2p form compiled for six waves per SIMD — three 512-thread workgroups per CU instead of two — 1 047 ms:
+  // more workgroups in flight than the rows' L2 footprint allows cost more than the latency they hide)
+  int ws_threads = 1024;
+  if (!p.wide_two && (int64_t)in_n >= (int64_t)al->cu_count * 16) ws_threads = 128;
+  else if ((int64_t)in_n >= (int64_t)al->cu_count * 8) ws_threads = 256;
+  else if ((int64_t)in_n >= (int64_t)al->cu_count * 4) ws_threads = p.wide_two ? 512 : 256;
+  else if ((int64_t)in_n >= (int64_t)al->cu_count * 2) ws_threads = 512;
+  if (!p.wide_two && !p.wide32 && !prefer_ws && !p.wide_adapt) {
+    WideStage& st = p.wide_stage[p.n_wide];
+    st.a = w0;
+    const size_t lds_max = (size_t)std::min(160, std::max(16, knob(al, K_WIDE_LDS_KB, 160))) * 1024;
+    const size_t fixed = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, 0, 0, 0, w0.seq_words, true);
+    if (fixed + (size_t)nrows * 2 * 512 <= lds_max) {
+      int wcap = (int)((lds_max - fixed) / ((size_t)nrows * 2)) - 4;
+      wcap = std::min(wcap, p.full_range) & ~1;
+      lds_covers_all = wcap >= p.full_range;
+      st.a.wcap = wcap;
+      st.smem = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, 0, 0, wcap, w0.seq_words, true);
+      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, ((size_t)160 * 1024) / st.smem));
+      st.threads = knob(al, K_WIDE_THREADS, per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024));
+      st.grid = (int)std::min<int64_t>((int64_t)al->cu_count * per_cu, in_n);
+      if (full) {
+        // history: one byte per cell up to the step where a wavefront would outgrow the rows, + directory + events
+        const int64_t tmax = (int64_t)wcap * w0.E / 2 + 64;
+        int64_t bytes = (int64_t)wcap * wcap * w0.E / 4 + 16 * tmax + (1 << 16);
+        while (st.grid > 1 && (int64_t)st.grid * bytes > budget) st.grid = (st.grid + 1) / 2;
+        bytes = std::min<int64_t>(bytes, budget / std::max(st.grid, 1));
+        st.a.hist_stride = (bytes / 4) & ~15ll;
+        p.need = std::max(p.need, (size_t)st.grid * (size_t)st.a.hist_stride * 4);
+      }
+      ++p.n_wide;
+    }
+  }
+  // Round 4: what the banded stages hand on under wf-adaptive (47 of 8 192 pairs of 100 kb: a wavefront beyond their 256 diagonals)
+  // is a few hundred diagonals wide and a handful of pairs — one alignment's latency is all that counts.  Rows in LDS (int32 beyond
+  // 16 kb), as many diagonals as fit beside the sequences, one workgroup per CU: a step costs LDS round trips instead of L2 ones
+  // (100 kb: 5.2 us per step there).  A wavefront that leaves the rows goes on to the workspace form below.
+  if (p.wide_adapt && knob(al, K_WIDE_ADAPT_LDS, 1) != 0) {
+    WideStage& st = p.wide_stage[p.n_wide];
+    st.a = w0; st.grows = false; st.w32 = p.wide32;
+    const int ob = p.wide32 ? 4 : 2;
+    const size_t lds_max = (size_t)std::min(160, std::max(16, knob(al, K_WIDE_LDS_KB, 160))) * 1024;
+    const size_t fixed = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, w0.OE2, w0.E2, 0, w0.seq_words, true, ob);
+    if (fixed + (size_t)nrows * ob * 516 <= lds_max) {
+      int wcap = (int)((lds_max - fixed) / ((size_t)nrows * ob)) - 4;
+      wcap = std::min(std::min(wcap, 4096), p.full_range) & ~1;
+      if (knob(al, K_WIDE_ADAPT_LDS, 1) > 1) wcap = std::min(wcap, knob(al, K_WIDE_ADAPT_LDS, 1) & ~1);   // (tests: rows so narrow that pairs go on to the workspace form)
+      st.a.wcap = wcap;
+      st.smem = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, w0.OE2, w0.E2, wcap, w0.seq_words, true, ob);
+      st.threads = knob(al, K_WIDE_THREADS, 512);
+      st.grid = (int)std::min<int64_t>((int64_t)al->cu_count, in_n);
+      bool fits = true;
+      if (full) {
+        int64_t hist_bytes = std::min<int64_t>((int64_t)p.full_range * ((int64_t)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / w0.g + 64) / 2 + (1 << 20),
+                                               ((int64_t)(b->max_len * 1.2) / w0.g + 64) * 2048 + (1 << 20));
+        while (st.grid > 1 && (int64_t)st.grid * hist_bytes > budget) st.grid = (st.grid + 1) / 2;
+        fits = (int64_t)st.grid * hist_bytes <= budget;
+        st.a.hist_stride = (hist_bytes / 4) & ~15ll;
+        if (fits) p.need = std::max(p.need, (size_t)st.grid * (size_t)st.a.hist_stride * 4);
+      }
+      if (fits) ++p.n_wide;
+    }
+  }
+  if (!lds_covers_all) {
+    WideStage& st = p.wide_stage[p.n_wide];
+    st.a = w0; st.grows = true; st.w32 = p.wide32;
+    st.a.wcap = p.full_range;
+    st.a.rows_stride = (int64_t)((nrows * wfa::wide_row_halfs(p.full_range) + 63) & ~(size_t)63);
+    const int64_t row_bytes = p.wide32 ? 4 : 2;   // bytes per offset
+    st.smem = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, w0.OE2, w0.E2, p.full_range, w0.seq_words, false);
+    const bool seqs_fit_lds = st.smem <= (size_t)160 * 1024;   // (both packed sequences are staged in LDS: reads up to ~300 kb)
+    st.threads = knob(al, K_WIDE_THREADS, p.wide_adapt ? 512 : ws_threads);   // (wf-adaptive: a cut wavefront is a few hundred diagonals: one cell per thread)
+    st.grid = (int)std::min<int64_t>((int64_t)al->cu_count * std::max<int64_t>(1, std::min<int64_t>(2048 / st.threads, (160 * 1024) / std::max<size_t>(st.smem, 1))), in_n);
+    if (p.wide_adapt) st.grid = std::min(st.grid, al->cu_count);   // (leftovers: one workgroup per CU is plenty)
+    int64_t hist_bytes = 0;
+    if (full) hist_bytes = (int64_t)p.full_range * ((int64_t)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / w0.g + 64) / 2 + (1 << 20);   // one byte per cell, + directory + events
+    // (wf-adaptive: the cut-off keeps the wavefronts narrow: ~2 KB of codes per step; a pair that needs more is handed on)
+    if (full && p.wide_adapt) hist_bytes = std::min<int64_t>(hist_bytes, ((int64_t)(b->max_len * 1.2) / w0.g + 64) * 2048 + (1 << 20));
+    while (st.grid > 1 && (int64_t)st.grid * (st.a.rows_stride * row_bytes + hist_bytes) > budget) st.grid = (st.grid + 1) / 2;
+    if (seqs_fit_lds && (int64_t)st.grid * (st.a.rows_stride * row_bytes + hist_bytes) <= budget) {
+      st.a.hist_stride = (hist_bytes / 4) & ~15ll;
+      st.hist_off = ((size_t)st.grid * (size_t)st.a.rows_stride * (size_t)row_bytes + 255) & ~(size_t)255;
+      p.need = std::max(p.need, st.hist_off + (size_t)st.grid * (size_t)st.a.hist_stride * 4);
+      ++p.n_wide;
+    }
+  }
+}
+
+// full CIGARs of short reads: 16-lane segments over the whole batch (history slot per pair, several launches), then
+// 32- and 64-lane segments over what was handed on (device-side counts: slots for 1/8 resp. 1/32 of the batch)
+static void plan_segfull(const wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePlan& p) {
+  const uint32_t in_n = b->n_packed;
+  p.n_segfull = p.use_segfull ? 3 : 0;
+  if (p.use_segfull && b->stage_pick != 0 && !al->knobs.set[K_SEGFULL_STAGES]) {   // (the pilot of batch_build chose the first width)
+    p.n_segfull = 0;
+    for (int w = 16; w <= 64; w *= 2) if (w >= b->stage_pick) p.segfull_w[p.n_segfull++] = w;
+  } else if (p.use_segfull) {
+    p.n_segfull = std::max(0, std::min(3, knob(al, K_SEGFULL_STAGES, 3)));
+  }
+  // Round 3: the 16-diagonal stage of that cascade is the lane-per-pair kernel with origin codes (wfa_lane_kernel<.., FULL>):
+  // it walks in-kernel and leaves only run records in HBM (WFA_LANE_RUN_SLOT ints + an end state per pair), so the whole batch
+  // is one launch; WFA_HIP_LANE_FULL=0 keeps the 16-lane segments (round 4: with piggy-back code records) as the first stage
+  p.use_lanefull = p.use_segfull && p.n_segfull >= 1 && p.segfull_w[0] == 16 && knob(al, K_LANE_FULL, 1) != 0 && p.lane_shape_fits;
+  // (behind it one segment stage, 32 lanes, then the banded kernel: the 64-lane stage cost more in launches than its ~300 pairs per
+  // million are worth)
+  if (p.use_lanefull) { for (int i = 1; i < p.n_segfull; ++i) p.segfull_w[i - 1] = p.segfull_w[i]; --p.n_segfull; if (!al->knobs.set[K_SEGFULL_STAGES]) p.n_segfull = std::min(p.n_segfull, 1); }
+  if (p.use_segfull) {
+    for (int i = 0; i < p.n_segfull; ++i) {
+      const int rank = i + (p.use_lanefull ? 1 : 0);   // position in the cascade: 0 = takes the whole batch
+      { long long ci, ei, si; wfa::seg_full_slot(b->dcfg, p.segfull_w[i], b->max_len, &ci, &ei, &si); p.segfull_slot_ints[i] = si; }   // code records of w bytes, events, runs
+      const int64_t slot_bytes = p.segfull_slot_ints[i] * 4 + (int64_t)sizeof(int4);
+      int64_t want = (rank == 0) ? std::min<int64_t>((int64_t)knob(al, K_SEGFULL_PAIRS, 2000000), std::max<int64_t>(1, ((int64_t)8 << 30) / slot_bytes))
+                                 : std::max<int64_t>(4096, (int64_t)in_n / (rank == 1 ? 8 : 32));
+      // (the stage that takes the whole batch runs it as two balanced launches at least, once each still fills the chip: the walks and
+      // the expand of a launch — a third of the stage's time at 10 % divergence — run under the alignment kernel of the next)
+      if (rank == 0 && (int64_t)in_n >= 262144 && !al->knobs.set[K_SEGFULL_PAIRS] && knob(al, K_NO_DUAL, 0) == 0)
+        want = std::min<int64_t>(want, (((int64_t)in_n + 1) / 2 + 63) & ~63ll);
+      p.segfull_cap[i] = std::max<int64_t>(1, std::min<int64_t>(in_n, std::min<int64_t>(want, p.budget / slot_bytes)));
+      // (several launches: two slot arrays, the walks of a launch run under the alignment kernel of the next)
+      p.need = std::max(p.need, (size_t)(p.segfull_cap[i] * slot_bytes) * ((rank == 0 && p.segfull_cap[i] < (int64_t)in_n) ? 2 : 1));
+    }
+  }
+}
+
+// the lane-full stage's region lies BEHIND everything the later stages use (its expand runs on the side stream under them)
+static void plan_lanefull(const wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePlan& p) {
+  const uint32_t in_n = b->n_packed;
+  p.lanefull_slot_bytes = (int64_t)WFA_LANE_RUN_SLOT * 4 + (int64_t)sizeof(int4);
+  if (p.use_lanefull) {
+    p.lanefull_off = (p.need + 255) & ~(size_t)255;
+    // per launch: run records + end state per pair, and the waves' record lists of comparison bits (512 bytes per wave-step)
+    const int64_t lf_budget = std::max<int64_t>((int64_t)p.budget - (int64_t)p.lanefull_off, (int64_t)1 << 20);
+    p.lanefull_cap = std::max<int64_t>(1, std::min<int64_t>(in_n, lf_budget / (p.lanefull_slot_bytes + 256)));
+    if (al->knobs.set[K_SEGFULL_PAIRS]) p.lanefull_cap = std::min<int64_t>(p.lanefull_cap, std::max<int64_t>(64, knob(al, K_SEGFULL_PAIRS, 2000000)));   // (tests: several launches over one region)
+    // When the whole batch fits (the usual case) it is cut into balanced launches with code lists of their own: walk + expand of a
+    // launch (latency- and memory-bound) run on the side stream under the lane kernel (issue-bound) of the next
+    if (p.lanefull_cap >= (int64_t)in_n) {
+      p.lanefull_split = std::max(1, std::min(8, knob(al, K_LANE_FULL_SPLIT, (int64_t)in_n >= 524288 ? 2 : 1)));
+      p.lanefull_cap = ((((int64_t)in_n + p.lanefull_split - 1) / p.lanefull_split) + 63) & ~63ll;
+    }
+    // pairs per wave: 256 for launches that fill the chip; a launch of up to 256 k pairs is cut into lane-fulls of 64 (a run is as long as
+    // a wave's life: 65 536 pairs with CIGAR 397 -> 289 us; 1 M pairs in two launches: 1.07 ms with 256, 1.15 with 64).  One value for the
+    // geometry and every launch of the stage: a shorter last launch must not have more waves than the record lists were sized for
+    p.lf_min_pairs = knob(al, K_LANE_MIN_PAIRS, p.lanefull_cap <= 262144 ? 64 : 256);
+    wfa::lane_full_geometry((uint32_t)p.lanefull_cap, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), p.lf_min_pairs, p.sh_oe, p.sh_e,
+                            &p.lanefull_grid, &p.lanefull_recs);
+    p.lanefull_codes_off = p.lanefull_off + (((size_t)(p.lanefull_cap * p.lanefull_split * p.lanefull_slot_bytes) + 255) & ~(size_t)255);
+    p.lanefull_codes_bytes = ((size_t)p.lanefull_grid * (size_t)p.lanefull_recs * 512 + 255) & ~(size_t)255;
+    p.lanefull_list_off = p.lanefull_codes_off + p.lanefull_codes_bytes * (size_t)p.lanefull_split;
+    p.need = std::max(p.need, p.lanefull_list_off + (size_t)in_n * sizeof(uint32_t));
+  }
+}
+
+// The plan of the 2-bit cascade, in the order the workspace is laid out: every planner raises p.need, and the lane-full region is
+// placed behind p.need as it stands after all the others.  No HIP call but the memory query of free_budget.
+static void plan_cascade(wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePlan& p) {
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  const uint32_t in_n = b->n_packed;
+  p.budget = free_budget(al);
+  p.shape = wfa::seg_shape(b->dcfg, &p.sh_x, &p.sh_oe, &p.sh_e);
+  p.lane_shape_fits = p.shape != WFA_SHAPE_RTC || wfa::rtc_lane_shape_ok(p.sh_x, p.sh_oe, p.sh_e);
+  p.adapt = (b->dcfg.heuristic != WFA_HEUR_NONE);  // the heuristic instantiations of the banded kernel (wf-adaptive / X-drop)
+  // a handful of short pairs: one launch of the general kernel beats six nearly empty stages (single-pair calls of a
+  // pywfa-style loop).  Long reads take the stages whatever the count: an alignment of milliseconds dwarfs the launches, and
+  // the banded / wide kernels are several times faster per pair (8 pairs of C4 as written: 57 ms instead of 436 ms; 8 x 10 kb
+  // wf-adaptive with full CIGAR: 3.9 instead of 15.7 ms)
+  p.tiny = in_n <= (uint32_t)knob(al, K_TINY_BATCH, 128) && b->max_len <= 1000;
+  p.use_fast = !p.tiny && !full && wfa::seg_supported(b->dcfg, b->ncomp, full) && b->max_len <= WFA_FAST_MAX_LEN &&
+               knob(al, K_NO_FAST, 0) == 0;
+  // full CIGARs of short reads: the segmented kernel with a history slot per pair, then the thread-per-alignment walk
+  // (round 6: a one-component distance with CIGARs, mapped — b->dcfg.lin: the register stages' LIN form exists as a run-time instantiation
+  // only; without hipRTC, and for what those stages hand on, the general kernel under the original configuration)
+  p.lin = b->dcfg.lin != 0;
+  const bool lin_regs = p.lin && b->dcfg.rtc != 0 && wfa::rtc_available();
+  p.use_segfull = (!p.lin || lin_regs) && !p.tiny && full && wfa::seg_supported(b->dcfg, b->ncomp, false) && b->max_len <= WFA_FAST_MAX_LEN &&
+                  knob(al, K_NO_FAST, 0) == 0 && knob(al, K_NO_SEGFULL, 0) == 0;
+  // Round 3: score-only short reads with wf-adaptive, free ends or a step limit — what the bound of the register kernels cannot
+  // prove — start in the general form of the lane kernel (wfa_lane_kernel<.., HEUR>: the pair is handed on the moment its
+  // wavefront touches the band's outermost slots); the banded stages take what it hands on
+  p.use_laneh = !p.tiny && !full && !p.use_fast && wfa::lane_heur_config(b->dcfg, b->ncomp) && p.shape >= 0 &&
+                p.lane_shape_fits &&
+                b->max_len <= WFA_FAST_MAX_LEN && knob(al, K_NO_FAST, 0) == 0 &&
+                (b->laneh_pick == 1 || b->laneh_pick == 3 || (b->laneh_pick == 0 && knob(al, K_LANE_HEUR, 0) != 0));   // (the pilot of batch_build, or WFA_HIP_LANE_HEUR=1 / 2)
+  p.laneh_form = (b->laneh_pick == 3 || (b->laneh_pick == 0 && knob(al, K_LANE_HEUR, 0) == 2)) ? 2 : 1;   // (2: 32 diagonals per pair)
+  // ... and then (or first, when the lane form's pilot said no) the same form of the 32-lane segments: two pairs per wave, a band twice
+  // as wide (WFA_HIP_SEG_HEUR=0: off)
+  p.use_segh = !p.tiny && !full && !p.use_fast && wfa::seg_heur_config(b->dcfg, b->ncomp) && b->max_len <= WFA_FAST_MAX_LEN &&
+               knob(al, K_NO_FAST, 0) == 0 && !wfa::seg_supported(b->dcfg, b->ncomp, false) &&
+               (b->segh_pick == 1 || (b->segh_pick == 0 && knob(al, K_SEG_HEUR, 0) != 0)) &&   // (the pilot of batch_build, or WFA_HIP_SEG_HEUR=1)
+               // (behind the 32-slot lane form the segments would see the same 32 diagonals again: what it hands on — 2 % of 150 bp
+               // pairs at 2 % — goes straight to the banded stages, 2.22 -> 2.02 ms per 2 M pairs; WFA_HIP_SEG_HEUR=1 keeps the stage)
+               !(p.use_laneh && p.laneh_form == 2 && knob(al, K_SEG_HEUR, -1) < 0);
+  plan_band_windows(al, b, p);
+  // (round 3) wf-adaptive: the wide kernel takes what the banded stages hand on — the few pairs whose wavefront outgrows 256 diagonals
+  // (47 of 8 192 at 100 kb) — instead of the general kernel: rows in the workspace, its cut-off in-kernel (WFA_HIP_WIDE_ADAPT=0: off)
+  // (reads over 20 kb: at 10 kb the general kernel is as quick for the odd pair, and the 2p rows of the wide kernel are slower)
+  const int wide_adapt_knob = knob(al, K_WIDE_ADAPT, 1);
+  p.wide_adapt = b->dcfg.heuristic == WFA_HEUR_ADAPTIVE && b->max_len > 1000 &&
+                 (wide_adapt_knob == 2 || (p.n_stages > 0 && wide_adapt_knob != 0 && b->max_len > 20000));   // (2: any length, also without banded stages in front: tests)
+  p.wide_ok = !p.lin && !p.tiny && ((b->ncomp == 3 && b->dcfg.metric == 3) || (b->ncomp == 5 && b->dcfg.metric == 4 && b->dcfg.e2 >= 1)) &&
+              (b->dcfg.heuristic == WFA_HEUR_NONE || p.wide_adapt) && b->dcfg.match == 0 &&
+              b->max_len > 64 && 2 * (int64_t)b->max_len <= 0x3fffff00ll && b->dcfg.e1 >= 1 && b->dcfg.x >= 1 && knob(al, K_NO_WIDE, 0) == 0;
+  // reads beyond 16 kb (plen + tlen > 32 000 does not fit int16 offsets): the workspace-row form with int32 rows (round 3)
+  p.wide32 = 2 * (int64_t)b->max_len > 32000;
+  const bool any_pre = p.use_fast || p.use_laneh || p.use_segh || p.use_segfull || p.n_stages > 0 || p.wide_ok;
+  // the general kernel's geometry is fixed first so that one workspace allocation serves every stage
+  p.g = plan_general(al, b, any_pre ? std::min<uint32_t>(in_n, (uint32_t)al->cu_count * 16) : in_n, b->arena_fixed + b->arena_ints);
+  p.need = (size_t)p.g.grid * p.g.ws_stride * 4;
+  plan_band_stages(al, b, p);
+  p.wide_two = (b->ncomp == 5);
+  if (p.wide_ok) {
+    wfa::WideArgs& w0 = p.w0;
+    memset(&w0, 0, sizeof(w0));
+    w0.g = p.wide_two ? wfa::band_gcd(b->dcfg, true) : affine_gcd(b->dcfg);
+    w0.X = b->dcfg.x / w0.g; w0.OE = (b->dcfg.o1 + b->dcfg.e1) / w0.g; w0.E = b->dcfg.e1 / w0.g;
+    if (p.wide_two) { w0.OE2 = (b->dcfg.o2 + b->dcfg.e2) / w0.g; w0.E2 = b->dcfg.e2 / w0.g; }
+    w0.seq_words = ((b->max_len + 15) >> 4) + 4;
+    p.full_range = (2 * b->max_len + 8 + b->dcfg.pbf + b->dcfg.tbf) & ~1;
+    plan_tile_stage(al, b, p);
+    plan_wide_stages(al, b, p);
+  }
+  plan_segfull(al, b, p);
+  plan_lanefull(al, b, p);
+}
+
+// BiWFA: one wave per alignment; a workgroup's slice of the workspace = forward ring + reverse ring + base-case history.
+// (scope=score with a step limit: the top-level breakpoint search alone, no base-case history)
+struct BilevelPlan {
+  wfa::BiwfaArgs ba; wfa::BlArgs la;   // the sizes; run_biwfa adds the pointers
+  bool bilevel = false, bl_i16 = false;
+  int bl_grid = 0, bl_levels = 0;
+  int64_t grid = 0, stride = 0, dfs_off = 0;   // the depth-first kernel: workgroups, ints per slice, where its slices begin
+  Geometry g;                                  // the general kernel behind it (full scope)
+};
+
+static BilevelPlan plan_bilevel(wfa_hip_aligner* al, const wfa_hip_batch* b, bool biwfa_score) {
+  BilevelPlan bp;
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  memset(&bp.ba, 0, sizeof(bp.ba));
+  bp.ba.score_only = biwfa_score ? 1 : 0;
+  bp.ba.ring_stride = b->max_width;
+  bp.ba.ring_ints = ((int64_t)b->dcfg.scope * b->ncomp * bp.ba.ring_stride + 63) & ~63ll;
+  bp.ba.base_stride = wfa::biwfa_base_stride(b->max_width);
+  bp.ba.base_ints = biwfa_score ? 0 : ((wfa::biwfa_base_ints(b->ncomp, bp.ba.base_stride) + 63) & ~63ll);
+  bp.stride = 2 * bp.ba.ring_ints + bp.ba.base_ints;
+  bp.grid = std::min<int64_t>((int64_t)al->cu_count * knob(al, K_WAVES_PER_CU, 32), std::max<int64_t>(b->n, 1));
+  const int64_t budget = free_budget(al);
+  while (bp.grid > 1 && bp.grid * bp.stride * 4 > budget) bp.grid = (bp.grid + 1) / 2;
+  bp.g = plan_general(al, b, (uint32_t)std::min<int64_t>(b->n, (int64_t)al->cu_count * 16), b->arena_fixed + b->arena_ints);
+  // Round 5: full CIGARs go level by level (csrc/wfa_bilevel.hpp: every window of a recursion level is a work item of one launch);
+  // the depth-first kernel keeps the score-only form and what the level queues could not hold (redo list).
+  //   workspace: [ring / base-history slices][window queues, leaves, per-pair words, counters][slices of the depth-first kernel]
+  memset(&bp.la, 0, sizeof(bp.la));
+  bp.bilevel = full && knob(al, K_BILEVEL, 1) != 0;
+  bp.bl_i16 = b->max_len <= 32000 && knob(al, K_BILEVEL_I32, 0) == 0;
+  size_t bl_bytes = 0;
+  if (bp.bilevel) {
+    const int64_t esz = bp.bl_i16 ? 2 : 4;
+    bp.la.ring_stride = (b->max_width + 1) & ~1;
+    bp.la.ring_elems = ((int64_t)b->dcfg.scope * b->ncomp * bp.la.ring_stride + 63) & ~63ll;
+    bp.la.base_stride = bp.ba.base_stride; bp.la.base_ints = bp.ba.base_ints;
+    bp.la.slice_bytes = (std::max<int64_t>(2 * bp.la.ring_elems * esz, bp.ba.base_ints * 4) + 255) & ~255ll;
+    bp.bl_grid = al->cu_count * std::max(1, knob(al, K_BILEVEL_PER_CU, 32));
+    // (a slice is megabytes: no more of them than the batch can keep busy — a few windows per pair are in flight at the deep levels)
+    bp.bl_grid = (int)std::min<int64_t>(bp.bl_grid, std::max<int64_t>(64, 8 * (int64_t)std::max<int64_t>(b->n_packed, b->n_bytes)));
+    // windows a pair can be in at once: about two per 250 of score; queues sized from the longest pair, what overflows is redone
+    const int64_t per_pair = std::min<int64_t>(1024, std::max<int64_t>(4, b->max_width / 96));
+    const int64_t nmax = std::max<int64_t>(b->n_packed, b->n_bytes);
+    int64_t qcap = knob(al, K_BILEVEL_QCAP, 0) > 0 ? knob(al, K_BILEVEL_QCAP, 0) : std::min<int64_t>(nmax * per_pair + 1024, (int64_t)1 << 28);   // (the knob: tests of the redo path)
+    const int64_t pair_bytes = (int64_t)b->n * (4 + 4 + 4 + 8 + 4) + WFA_BL_COUNTER_WORDS * 4 + 4096;
+    // the depth-first kernel behind it: a few slices (its int32 rings are the large ones)
+    bp.grid = std::min<int64_t>(std::min<int64_t>(bp.grid, al->cu_count), std::max<int64_t>(1, nmax));   // (the redo list holds pairs of this batch)
+    // the queues must leave room for one ring slice per CU and one slice of the depth-first kernel — a large batch of
+    // short reads (10 M pairs: 6.4 GB of queues) would otherwise ask for more than the device has.  Queue overflow is a speed matter
+    // only (the redo list), so the capacity is clamped to half of what remains
+    if (knob(al, K_BILEVEL_QCAP, 0) <= 0) {
+      const int64_t room = budget - (int64_t)al->cu_count * bp.la.slice_bytes - pair_bytes - bp.stride * 4;
+      qcap = std::max<int64_t>(1024, std::min<int64_t>(qcap, room / 2 / 160));
+    }
+    const int64_t meta_bytes = qcap * 32 * 5 + pair_bytes;
+    while (bp.bl_grid > al->cu_count && (int64_t)bp.bl_grid * bp.la.slice_bytes + meta_bytes + bp.grid * bp.stride * 4 > budget) bp.bl_grid /= 2;
+    while (bp.grid > 1 && (int64_t)bp.bl_grid * bp.la.slice_bytes + meta_bytes + bp.grid * bp.stride * 4 > budget) bp.grid = (bp.grid + 1) / 2;
+    bp.la.qcap = bp.la.qbcap = bp.la.leafcap = bp.la.qwcap = (uint32_t)qcap;
+    bl_bytes = (size_t)((int64_t)bp.bl_grid * bp.la.slice_bytes + meta_bytes);
+    bp.dfs_off = (int64_t)((bl_bytes + 255) & ~(size_t)255);
+    // levels: a window's score halves per level (to within the ring's scope) until it is <= 250
+    const int64_t pmax = std::max<int64_t>(1, std::max<int64_t>(b->dcfg.x, std::max<int64_t>(b->dcfg.o1 + b->dcfg.e1, b->dcfg.o2 + b->dcfg.e2)));
+    int64_t smax = pmax * (int64_t)b->max_width;
+    bp.bl_levels = 3;
+    while (smax > 250 && bp.bl_levels < WFA_BL_MAX_LEVELS - 1) { smax /= 2; ++bp.bl_levels; }
+    if (knob(al, K_BILEVEL_LEVELS, 0) > 0) bp.bl_levels = std::min(knob(al, K_BILEVEL_LEVELS, 0), WFA_BL_MAX_LEVELS - 1);
+  }
+  return bp;
+}
+
+static int run_biwfa(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, bool biwfa_score) {
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  // the general kernel behind it (full scope): pairs whose top-level base case outgrew the BiWFA kernel's history
+  // (reads of <= 100 bases under large penalties) are aligned by the ordinary algorithm, which is what that base case is
+  b->dcfg.biwfa_top = full ? 1 : 0;
+  b->gcfg.biwfa_top = b->dcfg.biwfa_top;   // (the general kernel's copy of the configuration)
+  BilevelPlan bp = plan_bilevel(al, b, biwfa_score);
+  int rc = ensure_ws(al, std::max((size_t)bp.dfs_off + (size_t)bp.grid * bp.stride * 4, full ? (size_t)bp.g.grid * bp.g.ws_stride * 4 : (size_t)0));
+  if (rc != WFA_HIP_OK) return rc;
+  WfaKernelArgs& a = bp.ba.k;
+  a.words = b->d_words; a.bytes = b->d_bytes; a.meta = b->d_meta; a.p_boff = b->d_pboff; a.t_boff = b->d_tboff;
+  a.score = b->d_score; a.status = b->d_status;
+  fill_cigar_out(a, b);
+  a.ws = reinterpret_cast<int*>(reinterpret_cast<char*>(al->ws) + bp.dfs_off); a.ws_stride = bp.stride; a.cfg = b->dcfg;
+  if (bp.bilevel) {
+    char* p = reinterpret_cast<char*>(al->ws);
+    bp.la.rings = p; p += (int64_t)bp.bl_grid * bp.la.slice_bytes;
+    bp.la.q[0] = reinterpret_cast<wfa::BlWindow*>(p); p += (int64_t)bp.la.qcap * 32;
+    bp.la.q[1] = reinterpret_cast<wfa::BlWindow*>(p); p += (int64_t)bp.la.qcap * 32;
+    bp.la.qb = reinterpret_cast<wfa::BlWindow*>(p); p += (int64_t)bp.la.qcap * 32;
+    bp.la.qw = reinterpret_cast<wfa::BlWindow*>(p); p += (int64_t)bp.la.qcap * 32;
+    bp.la.leaves = reinterpret_cast<wfa::BlLeaf*>(p); p += (int64_t)bp.la.qcap * 32;
+    bp.la.failkey = reinterpret_cast<unsigned long long*>(p); p += (int64_t)b->n * 8;
+    bp.la.head = reinterpret_cast<int*>(p); p += (int64_t)b->n * 4;
+    bp.la.flags = reinterpret_cast<int*>(p); p += (int64_t)b->n * 4;
+    bp.la.top = reinterpret_cast<int*>(p); p += (int64_t)b->n * 4;
+    bp.la.redo_list = reinterpret_cast<uint32_t*>(p); p += (int64_t)b->n * 4;
+    bp.la.cnt = reinterpret_cast<uint32_t*>(p);
+  }
+  for (int kind = 0; kind < 2; ++kind) {   // 2-bit pairs, then the pairs aligned on their bytes
+    const uint32_t cnt = kind ? b->n_bytes : b->n_packed;
+    if (cnt == 0) continue;
+    a.worklist = kind ? b->d_list_bytes : b->d_list_packed; a.nwork_dev = nullptr; a.nwork = cnt;
+    a.fb_list = full ? b->d_fb_list2[kind] : nullptr; a.fb_count = b->d_counters + CNT_BIWFA_FB + kind;
+    a.cfg.wildcard = (kind && b->wild >= 0) ? b->wild : b->dcfg.wildcard;   // (the 8-bit pairs keep the wildcard rule)
+    int64_t dfs_grid = std::min<int64_t>(bp.grid, cnt);
+    if (bp.bilevel) {
+      bp.la.k = a;
+      HIP_TRY(al, hipMemsetAsync(bp.la.cnt, 0, WFA_BL_COUNTER_WORDS * sizeof(uint32_t), stream));
+      const bool stage_timing = knob(al, K_STAGE_TIMING, 0) != 0;   // development aid: synchronises
+      std::vector<hipEvent_t> tev;
+      auto mark = [&]() { if (stage_timing) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, stream); tev.push_back(e); } };
+      mark();
+      bool ok = wfa::launch_bl_seed(bp.la, stream) == 0;
+      // four waves per window while the wavefronts are expected to span several chunks (about max_len / 8 diagonals at the top
+      // level for reads at 8 - 10 %, half of it per level)
+      int wide_auto = 0;
+      while (wide_auto < 8 && ((b->max_len / 8) >> wide_auto) >= 512) ++wide_auto;   // (10 kb: two levels, measured best of 0 / 2 / 3)
+      const int wide_levels = knob(al, K_BILEVEL_WIDE_LEVELS, wide_auto);
+      // Per level: the LDS form first where it pays (2-bit pairs, int16 offsets, gap-affine and the one-component metrics): both
+      // aligners' rows and the window's sub-sequences in LDS, W diagonals per row — W halves per level as the windows' scores do;
+      // used where at least two windows fit a CU (W <= 1024 for gap-affine 4/6/2).  A window whose wavefront outgrows W (or whose
+      // sub-sequences outgrow the buffers) moves to the level's second launch, the workspace form: rows in HBM / L2, the pair's
+      // sequences in LDS when they fit, four chunks of loads in flight per thread.
+      const bool lds_form = kind == 0 && bp.bl_i16 && b->ncomp <= 3 && knob(al, K_BILEVEL_LDS, 0) != 0;   // (off: measured slower than the workspace form at every level of 1 kb and 10 kb reads — per-step overheads, not the rows' latency, are what a narrow window pays)
+      const int gsc = std::max(1, wfa::band_gcd(b->dcfg, false));
+      bp.la.lds_slots = (b->dcfg.scope - 1) / gsc + 1;
+      const int full_seq_words = (b->max_len + 15) / 16 + 4;
+      const bool seql = kind == 0 && (size_t)2 * full_seq_words * 4 <= (size_t)48 * 1024 && knob(al, K_BILEVEL_NO_SEQL, 0) == 0;
+      const int lds_w_max = knob(al, K_BILEVEL_LDS_W, 1024);
+      for (int lv = 0; lv < bp.bl_levels && ok; ++lv) {
+        bp.la.level = lv;
+        bp.la.from_wide = 0;
+        // expected width of a level's wavefronts: a quarter of the window's length at 8 - 10 % error; rows of 1.3 x that, a power of two
+        int w = 128;
+        while (w < 8192 && w < (int)((((int64_t)b->max_len * 13 / 40) >> lv))) w *= 2;
+        if (lds_form && w <= lds_w_max) {
+          bp.la.lds_seq_words = std::min(full_seq_words, (int)(((int64_t)b->max_len * 3 / 2) >> lv) / 16 + 12);
+          const int lthreads = (w >= 2048) ? 1024 : (w >= 512) ? 256 : 64;
+          const size_t lsm = wfa::bl_split_lds_smem(b->ncomp, b->dcfg.scope, lthreads, w, bp.la.lds_slots, bp.la.lds_seq_words);
+          if (lsm <= (size_t)156 * 1024) {
+            bp.la.lds_w = w;
+            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)160 * 1024 / (lsm + 512), (size_t)(2048 / lthreads)));
+            const int64_t lgrid = (int64_t)al->cu_count * per_cu;
+            ok = wfa::launch_bl_split_lds_any(b->ncomp, lthreads, bp.la, (int)std::min<int64_t>(lgrid, lv == 0 ? (int64_t)cnt : lgrid), stream) == 0;
+            bp.la.from_wide = 1;
+          }
+        }
+        // (expected width of a level's wavefronts: a quarter of the read length at the top, half of it per level; sixteen waves per
+        // window from 8 192 diagonals on (measured at 20 / 40 / 100 kb: 1 024 / 2 048 / 4 096 / 8 192): 100 kb reads' top levels — a step is then 6 passes over the wavefront instead of 24)
+        const int64_t w_est = ((int64_t)b->max_len / 4) >> lv;
+        const bool few_windows = ((int64_t)cnt << std::min(lv, 20)) <= 2 * (int64_t)al->cu_count;   // (every window of the level resident at sixteen waves each)
+        const bool huge = kind == 0 && knob(al, K_BILEVEL_NO_1024, 0) == 0 &&
+                          (w_est >= knob(al, K_BILEVEL_HUGE_MIN, 8192) || (few_windows && w_est >= 2048));   // (small batches: 64 / 256 x 10 kb +20 %)
+        const int threads = huge ? 1024 : (lv < wide_levels) ? 256 : 64;
+        const int lgrid = huge ? std::min(bp.bl_grid, 2 * al->cu_count)
+                               : (threads == 256) ? std::min(bp.bl_grid, std::max(al->cu_count, bp.bl_grid / 2)) : bp.bl_grid;   // (a slice of the workspace per workgroup: never more than bl_grid)
+        bp.la.lds_seq_words = full_seq_words;
+        ok = ok && wfa::launch_bl_split_any(b->ncomp, kind == 0, bp.bl_i16, threads, seql, bp.la, (int)std::min<int64_t>(lgrid, lv == 0 ? (int64_t)cnt : (int64_t)lgrid), stream) == 0;
+        bp.la.from_wide = 0;
+        mark();
+      }
+      ok = ok && wfa::launch_bl_base_any(b->ncomp, kind == 0, bp.la, bp.bl_grid, stream) == 0;
+      mark();
+      ok = ok && wfa::launch_bl_finish(bp.la, (int)std::min<int64_t>((int64_t)al->cu_count * 16, cnt), stream) == 0;
+      mark();
+      if (!ok) { al->err = "BiWFA level kernel launch failed"; return WFA_HIP_EDEVICE; }
+      a.worklist = bp.la.redo_list; a.nwork_dev = bp.la.cnt + WFA_BL_MAX_LEVELS + 2; a.nwork = cnt;
+      dfs_grid = bp.grid;
+      if (wfa::launch_biwfa_any(b->ncomp, kind == 0, bp.ba, (int)dfs_grid, stream) != 0) { al->err = "BiWFA kernel launch failed"; return WFA_HIP_EDEVICE; }
+      mark();
+      if (stage_timing) {
+        (void)hipStreamSynchronize(stream);
+        uint32_t hc[WFA_BL_COUNTER_WORDS];
+        (void)hipMemcpy(hc, bp.la.cnt, sizeof(hc), hipMemcpyDeviceToHost);
+        fprintf(stderr, "[wfa_hip] biwfa levels (%s, %d pairs, grid %d, slice %.2f MB, %s rings):", kind ? "bytes" : "2-bit", (int)cnt, bp.bl_grid, bp.la.slice_bytes / 1048576.0, bp.bl_i16 ? "int16" : "int32");
+        for (int lv = 0; lv < bp.bl_levels; ++lv) { float ms = 0; (void)hipEventElapsedTime(&ms, tev[lv], tev[lv + 1]); fprintf(stderr, " L%d %u windows (%u past the LDS form) %.3f ms;", lv, hc[lv], hc[128 + lv], ms); }
+        float mb = 0, mf = 0, md = 0;
+        (void)hipEventElapsedTime(&mb, tev[bp.bl_levels], tev[bp.bl_levels + 1]); (void)hipEventElapsedTime(&mf, tev[bp.bl_levels + 1], tev[bp.bl_levels + 2]); (void)hipEventElapsedTime(&md, tev[bp.bl_levels + 2], tev[bp.bl_levels + 3]);
+        fprintf(stderr, " base %u windows %.3f ms; finish %.3f ms (%u leaves); redo %u pairs %.3f ms\n", hc[WFA_BL_MAX_LEVELS], mb, mf, hc[WFA_BL_MAX_LEVELS + 1], hc[WFA_BL_MAX_LEVELS + 2], md);
+        for (hipEvent_t e : tev) (void)hipEventDestroy(e);
+      }
+      continue;
+    }
+    if (wfa::launch_biwfa_any(b->ncomp, kind == 0, bp.ba, (int)dfs_grid, stream) != 0) { al->err = "BiWFA kernel launch failed"; return WFA_HIP_EDEVICE; }
+  }
+  if (full) {
+    for (int kind = 0; kind < 2; ++kind) {
+      if ((kind ? b->n_bytes : b->n_packed) == 0) continue;
+      rc = launch_general_dyn(al, b, stream, kind == 0, b->d_fb_list2[kind], b->d_counters + CNT_BIWFA_FB + kind, 0u, bp.g.ws_stride, bp.g.grid, bp.g.threads,
+                              b->d_ovf_list[0], b->d_counters + CNT_OVF);
+      if (rc != WFA_HIP_OK) return rc;
+    }
+  }
+  b->last_kernel_pairs = b->n_packed > 0 ? b->n_packed : b->n_bytes;   // (the first launch's pairs, as the cascade below reports them)
+  return WFA_HIP_OK;
+}
+
+// ---- one launcher per stage of the cascade -----------------------------------------------------------
+static int run_lanefull_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, const CascadePlan& p, Chain& c, DualStream& lane_expands) {
+  uint32_t* out_list = c.out_list(b);
+  uint32_t* out_count = c.next_count(b);
+  wfa::FastArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.lin = b->dcfg.lin;
+  fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = c.in_list; fa.nwork_dev = nullptr;
+  fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
+  fa.g = affine_gcd(b->dcfg);
+  const int64_t lf_slots = p.lanefull_cap * p.lanefull_split;   // slots in the region (split: slot = work item; otherwise one launch's worth, reused)
+  int32_t* const lf_runs = al->ws + p.lanefull_off / 4;
+  int4* const lf_ends = reinterpret_cast<int4*>(reinterpret_cast<char*>(al->ws) + p.lanefull_off + (size_t)lf_slots * WFA_LANE_RUN_SLOT * 4);
+  fa.hist = lf_runs; fa.hist_stride = WFA_LANE_RUN_SLOT; fa.end_state = lf_ends;
+  fa.codes = reinterpret_cast<uint2*>(reinterpret_cast<char*>(al->ws) + p.lanefull_codes_off); fa.codes_cap = p.lanefull_recs;
+  wfa::BandArgs ba;
+  memset(&ba, 0, sizeof(ba));
+  ba.meta = b->d_meta; ba.worklist = c.in_list; ba.words = b->d_words;
+  fill_cigar_out(ba, b);
+  ba.hist = fa.hist; ba.hist_stride = fa.hist_stride; ba.end_state = fa.end_state;
+  // (the walk hands a pair with more runs than its slot holds to a list of its own, taken by the general kernel after the join:
+  // walk and expand both run beside the later stages)
+  uint32_t* const walk_list = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(al->ws) + p.lanefull_list_off);
+  ba.lane_codes = fa.codes; ba.status = b->d_status; ba.fb_list = walk_list; ba.fb_count = b->d_counters + CNT_LANEFULL_LIST;
+  ba.g = fa.g; ba.x = b->dcfg.x; ba.oe = b->dcfg.o1 + b->dcfg.e1; ba.e = b->dcfg.e1;
+  // one launch (the usual case): the op bytes are written on the side stream while the main stream goes on with what was handed on
+  { const int drc = lane_expands.begin(lf_slots >= (int64_t)c.in_n); if (drc != WFA_HIP_OK) return drc; }
+  int64_t launch = 0;
+  for (int64_t w0 = 0; w0 < (int64_t)c.in_n; w0 += p.lanefull_cap, ++launch) {
+    const uint32_t cnt = (uint32_t)std::min<int64_t>(p.lanefull_cap, (int64_t)c.in_n - w0);
+    fa.work_begin = (uint32_t)w0; fa.nwork = cnt;
+    if (lf_slots >= (int64_t)c.in_n) {   // slots and code lists of this launch
+      fa.hist = lf_runs + w0 * WFA_LANE_RUN_SLOT; fa.end_state = lf_ends + w0;
+      fa.codes = reinterpret_cast<uint2*>(reinterpret_cast<char*>(al->ws) + p.lanefull_codes_off + (size_t)launch * p.lanefull_codes_bytes);
+      ba.hist = fa.hist; ba.end_state = fa.end_state; ba.lane_codes = fa.codes;
+    }
+    // (a shorter last launch has fewer waves and needs fewer records than the lists were sized for)
+    if (wfa::launch_lane_args(p.shape, p.sh_oe, p.sh_e, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, fa, true, 0, p.lf_min_pairs, false, p.sh_x) != 0) {
+      al->err = "lane kernel launch failed"; return WFA_HIP_EDEVICE;
+    }
+    ba.work_begin = (uint32_t)w0; ba.nwork = cnt;
+    hipStream_t es_ = stream;
+    { const int drc = lane_expands.walk_stream(launch, &es_); if (drc != WFA_HIP_OK) return drc; }
+    if (wfa::launch_lane_expand(ba, es_, es_) != 0) { al->err = "walk / expand launch failed"; return WFA_HIP_EDEVICE; }
+    { const int drc = lane_expands.after_walk(launch); if (drc != WFA_HIP_OK) return drc; }
+  }
+  c.advance(b, out_list, out_count);
+  return WFA_HIP_OK;
+}
+
+static int run_segfull_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, const CascadePlan& p, Chain& c, int sf) {
+  uint32_t* out_list = c.out_list(b);
+  uint32_t* out_count = c.next_count(b);
+  wfa::FastArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.lin = b->dcfg.lin;
+  fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = c.in_list; fa.nwork_dev = c.in_count;
+  fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
+  fa.hist = al->ws; fa.hist_stride = p.segfull_slot_ints[sf];
+  fa.end_state = reinterpret_cast<int4*>(reinterpret_cast<char*>(al->ws) + (size_t)p.segfull_cap[sf] * p.segfull_slot_ints[sf] * 4);
+  wfa::BandArgs ba;
+  memset(&ba, 0, sizeof(ba));
+  ba.meta = b->d_meta; ba.worklist = c.in_list; ba.words = b->d_words;
+  fill_cigar_out(ba, b);
+  ba.g = affine_gcd(b->dcfg);
+  ba.x = b->dcfg.x; ba.oe = b->dcfg.o1 + b->dcfg.e1; ba.e = b->dcfg.e1;
+  ba.hist = al->ws; ba.hist_stride = p.segfull_slot_ints[sf]; ba.end_state = fa.end_state;
+  ba.split = 1; ba.h16 = 1; ba.seg_w = p.segfull_w[sf];
+  { long long ci, ei, si; wfa::seg_full_slot(b->dcfg, p.segfull_w[sf], b->max_len, &ci, &ei, &si); ba.pb = 1; ba.pb_code_ints = ci; ba.pb_event_ints = ei; }
+  // (first stage: the host knows the count and walks it in launches of `cap` pairs; later stages: one launch over
+  // the device-side list, slots for `cap` of its pairs)
+  const int64_t total = (c.in_count == nullptr) ? (int64_t)c.in_n : p.segfull_cap[sf];
+  const size_t half_bytes = ((size_t)p.segfull_cap[sf] * (size_t)(p.segfull_slot_ints[sf] * 4 + (int64_t)sizeof(int4)) + 255) & ~(size_t)255;
+  DualStream dual{al, stream};
+  { const int drc = dual.begin(sf == 0 && c.in_count == nullptr && total > p.segfull_cap[sf] && al->ws_bytes >= 2 * half_bytes); if (drc != WFA_HIP_OK) return drc; }
+  int64_t launch = 0;
+  for (int64_t w0 = 0; w0 < total; w0 += p.segfull_cap[sf], ++launch) {
+    const uint32_t cnt = (uint32_t)std::min<int64_t>(p.segfull_cap[sf], total - w0);
+    char* base = reinterpret_cast<char*>(al->ws) + ((dual.on && (launch & 1)) ? half_bytes : 0);
+    fa.hist = reinterpret_cast<int32_t*>(base);
+    fa.end_state = reinterpret_cast<int4*>(base + (size_t)p.segfull_cap[sf] * p.segfull_slot_ints[sf] * 4);
+    ba.hist = fa.hist; ba.end_state = fa.end_state;
+    fa.work_begin = (uint32_t)w0; fa.nwork = cnt;
+    { const int drc = dual.before_align(launch); if (drc != WFA_HIP_OK) return drc; }
+    if (c.in_count != nullptr) HIP_TRY(al, hipMemsetAsync(fa.end_state, 0, (size_t)cnt * sizeof(int4), stream));
+    if (wfa::launch_seg_full(b->dcfg, al->cu_count, knob(al, K_FAST_WAVES_PER_CU, 256), stream, fa, p.segfull_w[sf]) != 0) { al->err = "segmented kernel launch failed"; return WFA_HIP_EDEVICE; }
+    ba.work_begin = (uint32_t)w0; ba.nwork = cnt;
+    hipStream_t ws_ = stream;
+    { const int drc = dual.walk_stream(launch, &ws_); if (drc != WFA_HIP_OK) return drc; }
+    if (wfa::launch_band_bt(ba, 1, ws_) != 0) { al->err = "backtrace launch failed"; return WFA_HIP_EDEVICE; }
+    { const int drc = dual.after_walk(launch); if (drc != WFA_HIP_OK) return drc; }
+  }
+  { const int drc = dual.end(); if (drc != WFA_HIP_OK) return drc; }
+  c.advance(b, out_list, out_count);
+  return WFA_HIP_OK;
+}
+
+static int run_fast_stages(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, const CascadePlan& p, Chain& c) {
+  // register-kernel stages, each taking what the one before handed on (WFA_HIP_FAST_STAGES, one digit per
+  // stage): 1 = the lane-per-pair kernel (64 pairs per wave, band of 16 diagonals, wfa_lane.hpp), 0 = its 8-diagonal form (built-in
+  // penalty shapes only); 7/6/8/9 = segments of 8/16/32/64 lanes with the two-round (lazy) extension, 3/2/4/5 = the same widths
+  // extending every cell at once
+  const char* stages_env = al->knobs.fast_stages.empty() ? nullptr : al->knobs.fast_stages.c_str();
+  const char* stages = stages_env ? stages_env : "189";
+  if (!stages_env && b->stage_pick != 0 && c.in_count == nullptr) {   // (the pilots of batch_build chose the first width)
+    stages = (b->stage_pick == 16) ? (b->narrow_pick == 1 ? "0189" : "189") : (b->stage_pick == 32) ? "89" : "9";  // (128: 64 lanes still take the pairs that fit)
+  }
+  int variants[6] = {-1, -1, -1, -1, -1, -1};
+  int nv = 0;
+  for (const char* c = stages; *c && nv < 6; ++c) {
+    const int v = *c - '0';
+    if (v < 0 || v > 9) continue;
+    if (v <= 1) {   // (the lane kernel of a run-time shape: only while its rings fit the register file, and never the 8-diagonal form)
+      if (p.shape == WFA_SHAPE_RTC && (v == 0 || !p.lane_shape_fits)) continue;
+    }
+    variants[nv++] = v;
+  }
+  if (nv == 0) variants[nv++] = 6;
+  int lane_passes = 0;   // lane stages launched so far: the first two take slices of their list at run time, each from a counter of its own
+  for (int pass = 0; pass < nv; ++pass) {
+    uint32_t* out_list = c.out_list(b);
+    uint32_t* out_count = c.next_count(b);
+    StageTimer timer(al, stream);
+    int lrc;
+    if (variants[pass] <= 1) {
+      const bool narrow = variants[pass] == 0;
+      const int lane_k = lane_passes++;
+      // (slices of the list taken at run time: as many waves as the chip holds at once — every wave goes on until the list is used up.
+      // A stage behind another reads the length of its list from the device (a.nwork_dev) and takes slices the same way: a grid sized
+      // for the chip, not for a count the host does not know)
+      uint32_t lane_dyn = (c.in_n >= 65536u && lane_k < 2) ? (uint32_t)std::max(0, knob(al, K_LANE_DYN, 192)) : 0u;
+      // (waves per CU: the 16-diagonal form holds 4 per SIMD, the 8-diagonal one 6)
+      const int dyn_waves = narrow ? knob(al, K_LANE_NARROW_WAVES, 24) : knob(al, K_LANE_DYN_WAVES, 16);
+      if (lane_dyn && c.in_count != nullptr) {
+        // behind another stage: slices sized for the pairs it is expected to receive (the first stage's pilot, else 64), so that
+        // every wave gets at least two — a wave with one slice of 192 runs as long as its slowest lane's three pairs (2 M pairs at
+        // 2 %, 350 k handed on: 1.02 ms for the cascade with slices of 192, 0.89 with 64; 10 M: 192 is right)
+        const int64_t expect = (b->narrow_permille >= 0 && variants[0] == 0) ? (int64_t)c.in_n * b->narrow_permille / 1000 : 0;
+        const int64_t per_wave = expect / std::max<int64_t>(1, (int64_t)al->cu_count * dyn_waves * 2);
+        lane_dyn = (uint32_t)std::max<int64_t>(64, std::min<int64_t>(lane_dyn, per_wave));
+      }
+      lrc = wfa::launch_lane(p.shape, affine_gcd(b->dcfg), al->cu_count,
+                             lane_dyn ? dyn_waves : knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, b->d_words, b->d_meta,
+                             c.in_list, c.in_count, c.in_n, b->d_score, b->d_status, out_list, out_count,
+                             (knob(al, K_LANE_DEBUG, 0) && al->ws) ? al->ws : nullptr, knob(al, K_LANE_LDS_PAD_KB, 0), p.sh_x, p.sh_oe, p.sh_e, knob(al, K_LANE_MIN_PAIRS, 0),
+                             // (slices of the list taken at run time, 192 pairs at a time, from counters zeroed with the run's others: [12] for
+                             // the first lane stage, [14] for the one behind it; WFA_HIP_LANE_DYN=0: fixed slices)
+                             b->d_counters + (lane_k == 0 ? CNT_LANE_DYN0 : CNT_LANE_DYN1), lane_dyn, narrow ? 4 : 8);
+      if (knob(al, K_LANE_DEBUG, 0) && al->ws) {  // development aid (build with -DWFA_LANE_DEBUG_COUNTERS=1)
+        unsigned long long c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        hipStreamSynchronize(stream); hipMemcpy(c, al->ws, sizeof(c), hipMemcpyDeviceToHost); hipMemset(al->ws, 0, sizeof(c));
+        fprintf(stderr, "[wfa_hip] lane kernel: %llu wave-steps, %llu refills, %llu parked runs, %llu parked rounds, %llu probe blocks, %llu second-run rounds, "
+                        "%llu hand-over blocks, %llu second runs, %llu entries, %llu entry rounds\n", c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]);
+      }
+    } else {
+      lrc = wfa::launch_seg(b->dcfg, al->cu_count, knob(al, K_FAST_WAVES_PER_CU, 256), stream, b->d_words, b->d_meta, c.in_list, c.in_count,
+                            c.in_n, b->d_score, b->d_status, out_list, out_count, variants[pass]);
+    }
+    if (lrc != 0) { al->err = "fast kernel launch failed"; return WFA_HIP_EDEVICE; }
+    if (timer.on) {  // development aid: synchronises after every stage
+      uint32_t handed = 0;
+      const float ms = timer.stop(out_count, &handed);
+      fprintf(stderr, "[wfa_hip] stage %d (variant %d): %.3f ms, handed on %u pairs\n", pass, variants[pass], ms, handed);
+    }
+    c.advance(b, out_list, out_count);
+  }
+  return WFA_HIP_OK;
+}
+
+static int run_laneh_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, const CascadePlan& p, Chain& c) {
+  uint32_t* out_list = c.out_list(b);
+  uint32_t* out_count = c.next_count(b);
+  wfa::FastArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = c.in_list; fa.nwork_dev = c.in_count; fa.nwork = c.in_n;
+  fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
+  fa.g = affine_gcd(b->dcfg);
+  fill_ends_free(fa, b->dcfg, true);
+  fill_heuristic(fa, b->dcfg);
+  // (slices of the list taken at run time, as the plain score-only form)
+  const uint32_t laneh_dyn = (c.in_count == nullptr && c.in_n >= 65536u) ? (uint32_t)std::max(0, knob(al, K_LANE_DYN, 192)) : 0u;
+  if (laneh_dyn) { fa.dyn_next = b->d_counters + CNT_LANEH_DYN; fa.dyn_chunk = laneh_dyn; }
+  if (wfa::launch_lane_args(p.shape, p.sh_oe, p.sh_e, al->cu_count, laneh_dyn ? knob(al, K_LANE_DYN_WAVES, 16) : knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, fa, false, 0, knob(al, K_LANE_MIN_PAIRS, 0), p.laneh_form, p.sh_x) != 0) {   // (pairs per wave by the size of the batch, as the plain form)
+    al->err = "lane kernel launch failed"; return WFA_HIP_EDEVICE;
+  }
+  c.advance(b, out_list, out_count);
+  return WFA_HIP_OK;
+}
+
+static int run_segh_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, const CascadePlan& p, Chain& c) {
+  uint32_t* out_list = c.out_list(b);
+  uint32_t* out_count = c.next_count(b);
+  wfa::FastArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = c.in_list; fa.nwork_dev = c.in_count; fa.nwork = c.in_n;
+  fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
+  fill_ends_free(fa, b->dcfg, true);
+  fill_heuristic(fa, b->dcfg);
+  fa.xdrop = b->dcfg.xdrop; fa.scope = b->dcfg.scope;
+  if (wfa::launch_seg_heur(b->dcfg, al->cu_count, knob(al, K_FAST_WAVES_PER_CU, 256), stream, fa) != 0) {
+    al->err = "segmented kernel launch failed"; return WFA_HIP_EDEVICE;
+  }
+  c.advance(b, out_list, out_count);
+  return WFA_HIP_OK;
+}
+
+// the split form of a band stage (long reads with CIGARs, the first stage of the run): history slot per pair, the walks in a kernel of
+// their own, and, where the plan allows it, the pipelined tail beside it
+static int run_band_split(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, const CascadePlan& p, Chain& c, int i, wfa::BandArgs& ba, bool seqlds, bool try_win, uint32_t* out_list, uint32_t* out_count, DualStream& pending_walks, bool* pipe_tail) {
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  // history slot per PAIR: as many pairs per launch as the workspace holds; the walks of a launch run
+  // afterwards in a thread-per-alignment kernel
+  const int64_t slot_ints = (p.pb_mode && p.pb_stride) ? p.pb_stride : p.band_stride[i];
+  if (p.pb_mode && p.pb_stride) { ba.pb = 1; ba.hist_stride = p.pb_stride; ba.pb_code_ints = p.pb_code_ints; ba.pb_event_ints = p.pb_event_ints; }
+  const int64_t slot_bytes = slot_ints * 4 + (int64_t)sizeof(int4);
+  // Slots: `cap` pairs fit the stage's region.  The launches are balanced (no small last launch) and their walks run on
+  // the side stream under the next alignment kernel: every launch has slots of its own when the whole batch fits
+  // (two launches at least, if each still fills the chip a few times over), otherwise the launches alternate between
+  // two halves of the region (only while a half still fills the chip: gap-affine-2p with explicit history at 10 kb
+  // runs 2 waves per SIMD and its launches are small already — halving them measured -35 %).
+  const size_t region = p.later_off ? p.later_off : al->ws_bytes;
+  const int64_t cap = std::min<int64_t>((int64_t)(region / (size_t)slot_bytes), c.in_n);
+  if (cap < 1) { al->err = "band history does not fit"; return WFA_HIP_EDEVICE; }
+  const int64_t chip = (int64_t)al->cu_count * 32;
+  const bool dual_ok = knob(al, K_NO_DUAL, 0) == 0;
+  const bool all_fit = cap >= (int64_t)c.in_n;
+  int64_t nl, per_launch;
+  bool halves = false;
+  if (all_fit) {
+    nl = (dual_ok && (int64_t)c.in_n >= 4 * chip) ? 2 : 1;
+    per_launch = ((int64_t)c.in_n + nl - 1) / nl;
+  } else {
+    halves = dual_ok && cap / 2 >= chip;
+    const int64_t lmax = halves ? cap / 2 : cap;
+    nl = ((int64_t)c.in_n + lmax - 1) / lmax;
+    per_launch = std::min<int64_t>(lmax, (((int64_t)c.in_n + nl - 1) / nl + 63) & ~63ll);
+  }
+  // the pipelined tail (see want_pipe_tail): this stage's launches and, beside each, the later stages on its leftovers
+  const bool tail = p.want_pipe_tail && i == 0 && p.gen_off != 0 && nl >= 2 && nl <= CNT_SNAP_LAUNCHES && !p.tile_stage.on && p.n_wide == 0 && (all_fit || halves);
+  uint32_t* const snap_a = b->d_counters + CNT_SNAP_A;    // [j] = this stage's hand-over count before launch j
+  uint32_t* const snap_b = b->d_counters + CNT_SNAP_B;   // the same for the stage behind it
+  uint32_t* tail_list = nullptr; uint32_t* tail_count = nullptr;
+  wfa::BandArgs tb = ba;   // the stage behind: everything but lists, history region and window width is this stage's
+  if (tail) {
+    if (!al->tail_join) {
+      for (int q = 0; q < 2; ++q) HIP_TRY(al, hipEventCreateWithFlags(&al->tail_fork[q], hipEventDisableTiming));
+      HIP_TRY(al, hipEventCreateWithFlags(&al->tail_join, hipEventDisableTiming));
+    }
+    tail_list = b->d_fb_list2[c.out_sel ^ 1]; tail_count = c.next_count(b);
+    tb.worklist = out_list; tb.fb_list = tail_list; tb.fb_count = tail_count;
+    tb.hist = al->ws + p.later_off / 4; tb.hist_stride = p.band_stride[1];
+    tb.pb = 0; tb.pb_code_ints = 0; tb.pb_event_ints = 0; tb.pb_raw = 0; tb.split = 0;   // (unsplit: explicit history, walked in-kernel)
+    // (the tail stream's first kernel must see the counters zeroed and the previous run's use of the regions over)
+    HIP_TRY(al, hipEventRecord(al->tail_fork[0], stream));
+    HIP_TRY(al, hipStreamWaitEvent(al->tail_stream, al->tail_fork[0], 0));
+  }
+  ba.split = 1;
+  char* const es_base = reinterpret_cast<char*>(al->ws) + (size_t)cap * slot_ints * 4;   // end states behind the slots
+  DualStream dual{al, stream};
+  // (one launch: its walks go to the side stream only if a band stage with a region of its own follows)
+  const bool side = (nl > 1 && (all_fit || halves)) || (nl == 1 && p.later_off != 0 && i + 1 < p.n_stages);
+  { const int drc = dual.begin(side); if (drc != WFA_HIP_OK) return drc; }
+  int64_t launch = 0;
+  for (int64_t w0 = 0; w0 < c.in_n; w0 += per_launch, ++launch) {
+    const uint32_t cnt = (uint32_t)std::min<int64_t>(per_launch, c.in_n - w0);
+    const int64_t slot0 = all_fit ? w0 : ((halves && (launch & 1)) ? per_launch : 0);
+    ba.hist = al->ws + slot0 * slot_ints;
+    ba.end_state = reinterpret_cast<int4*>(es_base) + slot0;
+    ba.work_begin = (uint32_t)w0; ba.nwork = cnt;
+    const long long grid = std::min<long long>((long long)al->cu_count * knob(al, K_BAND_WAVES_PER_CU, 128), cnt);
+    if (!all_fit) { const int drc = dual.before_align(launch); if (drc != WFA_HIP_OK) return drc; }
+    if (try_win && !ba.win) {   // (decided once per stage: the launches of a stage share everything slim_takes looks at)
+      wfa::BandArgs t = ba; t.win = 1; t.lds_words = 643;
+      if (wfa::slim_launches(t, p.band_nch[i], full, p.adapt, true)) { ba.win = 1; ba.lds_words = 643; seqlds = true; }
+    }
+    ba.pb_raw = wfa::slim_launches(ba, p.band_nch[i], full, p.adapt, seqlds) ? 1 : 0;   // (wfa_slim_kernel writes comparison bits; the walk below decodes them)
+    if (wfa::launch_band(ba, p.band_nch[i], full, p.adapt, seqlds, grid, stream) != 0) { al->err = "band kernel launch failed"; return WFA_HIP_EDEVICE; }
+    if (tail) {
+      // [snap_a[launch], snap_a[launch + 1]) = what this launch handed on (snap_a[0] = 0: the counters are zeroed per run)
+      hipLaunchKernelGGL(wfa_snapshot_kernel, dim3(1), dim3(1), 0, stream, out_count, snap_a + launch + 1);
+      HIP_TRY(al, hipEventRecord(al->tail_fork[launch & 1], stream));
+      HIP_TRY(al, hipStreamWaitEvent(al->tail_stream, al->tail_fork[launch & 1], 0));
+      tb.wbeg_dev = snap_a + launch; tb.nwork_dev = snap_a + launch + 1; tb.nwork = c.in_n;
+      if (wfa::launch_band(tb, p.band_nch[1], full, p.adapt, seqlds, p.band_grid[1], al->tail_stream) != 0) { al->err = "band kernel launch failed"; return WFA_HIP_EDEVICE; }
+      hipLaunchKernelGGL(wfa_snapshot_kernel, dim3(1), dim3(1), 0, al->tail_stream, tail_count, snap_b + launch + 1);
+      const int grc = launch_general_dyn(al, b, al->tail_stream, true, tail_list, snap_b + launch + 1, c.in_n, p.gen_stride, p.gen_grid, p.g.threads,
+                                         b->d_ovf_list[0], b->d_counters + CNT_OVF, reinterpret_cast<int32_t*>(reinterpret_cast<char*>(al->ws) + p.gen_off), snap_b + launch);
+      if (grc != WFA_HIP_OK) return grc;
+    }
+    hipStream_t ws_ = stream;
+    { const int drc = dual.walk_stream(launch, &ws_); if (drc != WFA_HIP_OK) return drc; }
+    if (wfa::launch_band_bt(ba, p.band_nch[i], ws_) != 0) { al->err = "band backtrace launch failed"; return WFA_HIP_EDEVICE; }
+    { const int drc = dual.after_walk(launch); if (drc != WFA_HIP_OK) return drc; }
+  }
+  // the walks still running are joined before anything reuses their slots: at once, unless the next band stage has
+  // its own region
+  if (p.later_off && i + 1 < p.n_stages && dual.on) pending_walks = dual;
+  else { const int drc = dual.end(); if (drc != WFA_HIP_OK) return drc; }
+  if (tail) {
+    // everything behind this stage has been enqueued beside it: the main stream joins the tail stream, the stage behind is
+    // skipped below and so is the last launch of the general kernel; the lists move on as if the stages had run here
+    HIP_TRY(al, hipEventRecord(al->tail_join, al->tail_stream));
+    HIP_TRY(al, hipStreamWaitEvent(stream, al->tail_join, 0));
+    c.hand_on(b, tail_list, tail_count);   // (out_sel: two lists were used, the selector is where it was)
+    *pipe_tail = true;
+  }
+  return WFA_HIP_OK;
+}
+
+static int run_band_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, const CascadePlan& p, Chain& c, int i, DualStream& pending_walks, bool* pipe_tail, std::chrono::steady_clock::time_point& band_prev) {
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  wfa::BandArgs ba;
+  memset(&ba, 0, sizeof(ba));
+  ba.words = b->d_words; ba.meta = b->d_meta; ba.worklist = c.in_list; ba.nwork_dev = c.in_count; ba.nwork = c.in_n;
+  ba.score = b->d_score; ba.status = b->d_status;
+  fill_cigar_out(ba, b);
+  uint32_t* out_list = c.out_list(b);
+  uint32_t* out_count = c.next_count(b);
+  ba.fb_list = out_list; ba.fb_count = out_count;
+  ba.g = wfa::band_gcd(b->dcfg, b->ncomp == 5);
+  ba.x = b->dcfg.x; ba.oe = b->dcfg.o1 + b->dcfg.e1; ba.e = b->dcfg.e1;
+  if (b->ncomp == 5) { ba.oe2 = b->dcfg.o2 + b->dcfg.e2; ba.e2 = b->dcfg.e2; }
+  fill_heuristic(ba, b->dcfg);
+  ba.xdrop = b->dcfg.xdrop; ba.scope = b->dcfg.scope;
+  const int words = ((b->max_len + 15) >> 4) + 4;
+  // (round 5: up to 13 KB per wave — reads of up to 26 kb: the 128-diagonal slim kernel then runs four waves per SIMD instead of
+  // seven and is still twice as fast as wfa_band_kernel on HBM-resident sequences (15 kb: 3.1 -> 5.9 M aln/s score); beyond, the
+  // waves a CU can hold are too few)
+  bool seqlds = ((size_t)words * 8 <= (size_t)knob(al, K_BAND_LDS_MAX, 13312)) && knob(al, K_BAND_NO_LDS, 0) == 0;
+  ba.lds_words = seqlds ? words : 0;
+  // longer reads, wf-adaptive or no heuristic, gap-affine: wfa_slim_kernel on WINDOWS of the sequences (10 k bases of each in LDS,
+  // moved along as the alignment advances) — launches it does not take (slim_takes) read the sequences from HBM as before
+  const bool try_win = !seqlds && b->ncomp == 3 && b->dcfg.heuristic != WFA_HEUR_XDROP && knob(al, K_BAND_NO_LDS, 0) == 0 && knob(al, K_BAND_NO_WIN, 0) == 0;
+  ba.debug = knob(al, K_BAND_DEBUG, 0);
+  ba.slim = knob(al, K_BAND_SLIM, 1);   // (0: wfa_band_kernel also where wfa_slim_kernel would take the launch)
+  ba.pb_raw = 0;
+  if (knob(al, K_STAGE_TIMING, 0) != 0 && b->max_len > WFA_FAST_MAX_LEN) {   // (counting builds; [8..15] belong to the short-read stages otherwise)
+    ba.dbg = b->d_counters + CNT_DEBUG;
+    (void)hipMemsetAsync(b->d_counters + CNT_DEBUG, 0, CNT_DEBUG_WORDS * sizeof(uint32_t), stream);
+  }
+  ba.h16 = (b->max_len < 32000) ? 1 : 0;
+  fill_ends_free(ba, b->dcfg, true);
+  ba.hist = (i > 0 && p.later_off) ? al->ws + p.later_off / 4 : al->ws; ba.hist_stride = p.band_stride[i];
+  const bool split = full && c.in_count == nullptr && b->max_len > knob(al, K_BAND_SPLIT_MIN, 100) && knob(al, K_BAND_NO_SPLIT, 0) == 0;
+  if (split) {
+    const int rc = run_band_split(al, b, stream, p, c, i, ba, seqlds, try_win, out_list, out_count, pending_walks, pipe_tail);
+    if (rc != WFA_HIP_OK || *pipe_tail) return rc;   // (the pipelined tail has moved the lists on itself)
+  } else {
+    if (try_win) {
+      wfa::BandArgs t = ba; t.win = 1; t.lds_words = 643;
+      if (wfa::slim_launches(t, p.band_nch[i], full, p.adapt, true)) { ba.win = 1; ba.lds_words = 643; seqlds = true; }
+    }
+    if (wfa::launch_band(ba, p.band_nch[i], full, p.adapt, seqlds, p.band_grid[i], stream) != 0) { al->err = "band kernel launch failed"; return WFA_HIP_EDEVICE; }
+  }
+  if (knob(al, K_STAGE_TIMING, 0) != 0) {  // development aid: synchronises (the time of the stage is the gap between these lines' events)
+    (void)hipStreamSynchronize(stream);
+    uint32_t handed = 0, took = c.in_n; (void)hipMemcpy(&handed, out_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (c.in_count) (void)hipMemcpy(&took, c.in_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    const auto t_now = std::chrono::steady_clock::now();
+    fprintf(stderr, "[wfa_hip] band stage %d (%d diagonals): took %u pairs, handed on %u; %.3f ms\n", i, 64 * p.band_nch[i], took, handed,
+            std::chrono::duration<double, std::milli>(t_now - band_prev).count());
+    if (ba.dbg) {
+      uint32_t dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0}; (void)hipMemcpy(dbg, ba.dbg, sizeof(dbg), hipMemcpyDeviceToHost);
+      if (dbg[0] | dbg[1]) fprintf(stderr, "[wfa_hip]   slim counters: steps of 64 diagonals %u, of 128 %u, extension rounds %u, cut-offs that cut %u, window shifts %u, end trims %u, live diagonals / 64 %u\n",
+                                   dbg[0], dbg[1], dbg[2], dbg[3], dbg[4], dbg[5], dbg[6]);
+    }
+    band_prev = std::chrono::steady_clock::now();
+  }
+  c.advance(b, out_list, out_count);
+  return WFA_HIP_OK;
+}
+
+static int run_tile_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, const CascadePlan& p, Chain& c) {
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  wfa::TileArgs ta = p.tile_stage.a;
+  uint32_t* out_list = c.out_list(b);
+  uint32_t* out_count = c.next_count(b);
+  ta.words = b->d_words; ta.meta = b->d_meta; ta.worklist = c.in_list; ta.nwork_dev = c.in_count; ta.nwork = c.in_n;
+  ta.score = b->d_score; ta.status = b->d_status; ta.fb_list = out_list; ta.fb_count = out_count;
+  fill_cigar_out(ta, b);
+  ta.rows = reinterpret_cast<short*>(al->ws);
+  ta.hist = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(al->ws) + p.tile_stage.hist_off);
+  fill_ends_free(ta, b->dcfg, false);
+  ta.max_steps = b->dcfg.max_steps;
+  StageTimer timer(al, stream);
+  ta.dbg = timer.on ? b->d_counters + CNT_DEBUG : nullptr;   // ([8] is the lane-full stage's list count: short reads only)
+  if (timer.on) (void)hipMemsetAsync(b->d_counters + CNT_DEBUG, 0, CNT_DEBUG_WORDS * sizeof(uint32_t), stream);
+  if (wfa::launch_tile(full, p.wide_two, ta, p.tile_stage.grid, p.tile_stage.threads, p.tile_stage.smem, stream, p.tile_stage.w32) != 0) { al->err = "tile kernel launch failed"; return WFA_HIP_EDEVICE; }
+  if (timer.on) {  // development aid: synchronises
+    uint32_t handed = 0;
+    const float ms = timer.stop(out_count, &handed);
+    uint32_t dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0}; (void)hipMemcpy(dbg, b->d_counters + CNT_DEBUG, sizeof(dbg), hipMemcpyDeviceToHost);
+    if (dbg[3] | dbg[4]) fprintf(stderr, "[wfa_hip] tile profile (k-cycles of s_memtime, summed over waves): load %u, steps %u, write-back %u; steps that entered the end test %u, the long-match loop %u\n", dbg[3], dbg[4], dbg[5], dbg[6], dbg[7]);
+    fprintf(stderr, "[wfa_hip] tile stage (T %d, Wt %d, %d x %d threads, %zu B LDS): %.3f ms, handed on %u pairs; %u super-steps, %u repeated with statistics, %u tiles\n",
+            ta.g.T, ta.g.Wt, p.tile_stage.grid, p.tile_stage.threads, p.tile_stage.smem, ms, handed, dbg[0], dbg[1], dbg[2]);
+  }
+  c.advance(b, out_list, out_count);
+  return WFA_HIP_OK;
+}
+
+static int run_wide_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, const CascadePlan& p, Chain& c, int ws_i) {
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  const WideStage& st = p.wide_stage[ws_i];
+  wfa::WideArgs wa = st.a;
+  uint32_t* out_list = c.out_list(b);
+  uint32_t* out_count = c.next_count(b);
+  wa.words = b->d_words; wa.meta = b->d_meta; wa.worklist = c.in_list; wa.nwork_dev = c.in_count; wa.nwork = c.in_n;
+  wa.score = b->d_score; wa.status = b->d_status; wa.fb_list = out_list; wa.fb_count = out_count;
+  fill_cigar_out(wa, b);
+  wa.rows = st.grows ? reinterpret_cast<short*>(al->ws) : nullptr;
+  wa.hist = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(al->ws) + st.hist_off);
+  fill_ends_free(wa, b->dcfg, false);
+  fill_heuristic(wa, b->dcfg);
+  wa.heur = (b->dcfg.heuristic == WFA_HEUR_ADAPTIVE) ? 1 : 0;   // (the one cut-off the wide kernel has)
+  StageTimer timer(al, stream);
+  if (wfa::launch_wide(full, p.wide_two, st.grows, wa, st.grid, st.threads, st.smem, stream, st.w32) != 0) { al->err = "wide kernel launch failed"; return WFA_HIP_EDEVICE; }
+  if (timer.on) {  // development aid: synchronises
+    uint32_t handed = 0;
+    const float ms = timer.stop(out_count, &handed);
+    fprintf(stderr, "[wfa_hip] wide stage %d (%d x %d threads): %.3f ms, handed on %u pairs\n", ws_i, st.grid, st.threads, ms, handed);
+  }
+  c.advance(b, out_list, out_count);
+  return WFA_HIP_OK;
+}
+
+// A cascade of kernels over the 2-bit pairs: each stage aligns what fits it and appends the rest to
+// a leftover list (pair ids + a device-side count) that the next stage consumes on the same stream;
+// the general kernel at the end takes everything.  All stages compute the same wavefronts, so which
+// stage finishes a pair does not change its result.
+static int run_cascade(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream) {
+  CascadePlan p;
+  plan_cascade(al, b, p);
+  int rc = ensure_ws(al, p.need);
+  if (rc != WFA_HIP_OK) return rc;
+  Chain c;
+  c.in_list = b->d_list_packed; c.in_n = b->n_packed;
+
+  DualStream lane_expands{al, stream, 2};   // the expand of the lane-full stage, left running under the stages behind it
+  if (p.use_lanefull && (rc = run_lanefull_stage(al, b, stream, p, c, lane_expands)) != WFA_HIP_OK) return rc;
+  for (int sf = 0; sf < p.n_segfull; ++sf)
+    if ((rc = run_segfull_stage(al, b, stream, p, c, sf)) != WFA_HIP_OK) return rc;
+  if (p.use_fast && (rc = run_fast_stages(al, b, stream, p, c)) != WFA_HIP_OK) return rc;
+  if (p.use_laneh && (rc = run_laneh_stage(al, b, stream, p, c)) != WFA_HIP_OK) return rc;
+  if (p.use_segh && (rc = run_segh_stage(al, b, stream, p, c)) != WFA_HIP_OK) return rc;
+  DualStream pending_walks{al, stream};   // walks of a split stage left running under the band stages behind it
+  bool pipe_tail = false;                 // the stages behind the split stage ran beside it, the general kernel included
+  std::chrono::steady_clock::time_point band_prev;
+  if (knob(al, K_STAGE_TIMING, 0) != 0) { (void)hipStreamSynchronize(stream); band_prev = std::chrono::steady_clock::now(); }
+  for (int i = 0; i < p.n_stages; ++i) {
+    if ((rc = run_band_stage(al, b, stream, p, c, i, pending_walks, &pipe_tail, band_prev)) != WFA_HIP_OK) return rc;
+    if (pipe_tail) break;   // (the stage behind the split stage has run beside it)
+  }
+  { const int drc = pending_walks.end(); if (drc != WFA_HIP_OK) return drc; }   // (the stages below use the workspace from its start)
+  if (p.tile_stage.on && (rc = run_tile_stage(al, b, stream, p, c)) != WFA_HIP_OK) return rc;
+  for (int ws_i = 0; ws_i < p.n_wide; ++ws_i)
+    if ((rc = run_wide_stage(al, b, stream, p, c, ws_i)) != WFA_HIP_OK) return rc;
+  b->leftover_count = c.in_count;
+  // (lin: what the register stages finished carries raw scores, what the general kernel finishes below — under the original
+  // configuration — final ones: the translation comes here, before it; a pair still to be aligned carries a non-zero status)
+  if (p.lin && b->dcfg.score_mode != 0)
+    hipLaunchKernelGGL(wfa_score_translate_kernel, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, stream, b->d_score, b->d_status, b->d_meta,
+                       (long long)b->n, b->dcfg.score_mode, b->dcfg.sw_match);
+  if (!pipe_tail) {   // (the pipelined tail has run the general kernel on every launch's leftovers already)
+    rc = launch_general_dyn(al, b, stream, true, c.in_list, c.in_count, c.in_n, p.g.ws_stride, p.g.grid, p.g.threads,
+                            b->d_ovf_list[0], b->d_counters + CNT_OVF);
+    if (rc != WFA_HIP_OK) return rc;
+  }
+  if (c.first_stage) b->last_kernel_pairs = c.in_n;
+  { const int drc = lane_expands.end(); if (drc != WFA_HIP_OK) return drc; }
+  if (p.use_lanefull) {   // what the walks of the lane-full stage handed on (nothing, as a rule)
+    rc = launch_general_dyn(al, b, stream, true, reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(al->ws) + p.lanefull_list_off), b->d_counters + CNT_LANEFULL_LIST,
+                            (uint32_t)b->n_packed, p.g.ws_stride, p.g.grid, p.g.threads, b->d_ovf_list[0], b->d_counters + CNT_OVF);
+    if (rc != WFA_HIP_OK) return rc;
+  }
+  return WFA_HIP_OK;
+}
+
 static int batch_run_once(wfa_hip_batch_t* b, void* stream_) {
   wfa_hip_aligner* al = b->al;
   HIP_TRY(al, hipSetDevice(al->device));
@@ -1826,1077 +3035,38 @@ static int batch_run_once(wfa_hip_batch_t* b, void* stream_) {
   b->arena_ints = full ? initial_arena_ints(al, b) : 0;
   b->arena_fixed = general_pb(al, b->cfg, b->gncomp, b->max_len) ? (((int64_t)b->dcfg.scope * b->ncomp * b->max_width + 64 + 63) & ~63ll) : 0;
 
-  // A cascade of kernels over the 2-bit pairs: each stage aligns what fits it and appends the rest to
-  // a leftover list (pair ids + a device-side count) that the next stage consumes on the same stream;
-  // the general kernel at the end takes everything.  All stages compute the same wavefronts, so which
-  // stage finishes a pair does not change its result.
   while (b->ev.size() < b->ev_used + 2) { hipEvent_t e; HIP_TRY(al, hipEventCreate(&e)); b->ev.push_back(e); }
   hipEvent_t ev0 = b->ev[b->ev_used], ev1 = b->ev[b->ev_used + 1];
   b->ev_used += 2; b->runs_pending += 1;
   HIP_TRY(al, hipEventRecord(ev0, stream));
   const bool biwfa_score = !full && b->cfg.memory_mode == WFA_MEM_BIWFA && (b->cfg.max_steps > 0 || b->cfg.heuristic != WFA_HEUR_NONE);
   if ((full && b->cfg.memory_mode == WFA_MEM_BIWFA) || biwfa_score) {
-    // BiWFA: one wave per alignment; a workgroup's slice of the workspace = forward ring + reverse ring + base-case history.
-    // (scope=score with a step limit: the top-level breakpoint search alone, no base-case history)
-    wfa::BiwfaArgs ba;
-    memset(&ba, 0, sizeof(ba));
-    ba.score_only = biwfa_score ? 1 : 0;
-    ba.ring_stride = b->max_width;
-    ba.ring_ints = ((int64_t)b->dcfg.scope * b->ncomp * ba.ring_stride + 63) & ~63ll;
-    ba.base_stride = wfa::biwfa_base_stride(b->max_width);
-    ba.base_ints = biwfa_score ? 0 : ((wfa::biwfa_base_ints(b->ncomp, ba.base_stride) + 63) & ~63ll);
-    const int64_t stride = 2 * ba.ring_ints + ba.base_ints;
-    int64_t grid = std::min<int64_t>((int64_t)al->cu_count * knob(al, K_WAVES_PER_CU, 32), std::max<int64_t>(b->n, 1));
-    const int64_t budget = free_budget(al);
-    while (grid > 1 && grid * stride * 4 > budget) grid = (grid + 1) / 2;
-    // the general kernel behind it (full scope): pairs whose top-level base case outgrew the BiWFA kernel's history
-    // (reads of <= 100 bases under large penalties) are aligned by the ordinary algorithm, which is what that base case is
-    b->dcfg.biwfa_top = full ? 1 : 0;
-    b->gcfg.biwfa_top = b->dcfg.biwfa_top;   // (the general kernel's copy of the configuration)
-    Geometry g = plan_general(al, b, (uint32_t)std::min<int64_t>(b->n, (int64_t)al->cu_count * 16), b->arena_fixed + b->arena_ints);
-    // Round 5: full CIGARs go level by level (csrc/wfa_bilevel.hpp: every window of a recursion level is a work item of one launch);
-    // the depth-first kernel keeps the score-only form and what the level queues could not hold (redo list).
-    //   workspace: [ring / base-history slices][window queues, leaves, per-pair words, counters][slices of the depth-first kernel]
-    wfa::BlArgs la;
-    memset(&la, 0, sizeof(la));
-    const bool bilevel = full && knob(al, K_BILEVEL, 1) != 0;
-    const bool bl_i16 = b->max_len <= 32000 && knob(al, K_BILEVEL_I32, 0) == 0;
-    int bl_grid = 0, bl_levels = 0;
-    int64_t dfs_off = 0;
-    size_t bl_bytes = 0;
-    if (bilevel) {
-      const int64_t esz = bl_i16 ? 2 : 4;
-      la.ring_stride = (b->max_width + 1) & ~1;
-      la.ring_elems = ((int64_t)b->dcfg.scope * b->ncomp * la.ring_stride + 63) & ~63ll;
-      la.base_stride = ba.base_stride; la.base_ints = ba.base_ints;
-      la.slice_bytes = (std::max<int64_t>(2 * la.ring_elems * esz, ba.base_ints * 4) + 255) & ~255ll;
-      bl_grid = al->cu_count * std::max(1, knob(al, K_BILEVEL_PER_CU, 32));
-      // (a slice is megabytes: no more of them than the batch can keep busy — a few windows per pair are in flight at the deep levels)
-      bl_grid = (int)std::min<int64_t>(bl_grid, std::max<int64_t>(64, 8 * (int64_t)std::max<int64_t>(b->n_packed, b->n_bytes)));
-      // windows a pair can be in at once: about two per 250 of score; queues sized from the longest pair, what overflows is redone
-      const int64_t per_pair = std::min<int64_t>(1024, std::max<int64_t>(4, b->max_width / 96));
-      const int64_t nmax = std::max<int64_t>(b->n_packed, b->n_bytes);
-      int64_t qcap = knob(al, K_BILEVEL_QCAP, 0) > 0 ? knob(al, K_BILEVEL_QCAP, 0) : std::min<int64_t>(nmax * per_pair + 1024, (int64_t)1 << 28);   // (the knob: tests of the redo path)
-      const int64_t pair_bytes = (int64_t)b->n * (4 + 4 + 4 + 8 + 4) + WFA_BL_COUNTER_WORDS * 4 + 4096;
-      // the depth-first kernel behind it: a few slices (its int32 rings are the large ones)
-      grid = std::min<int64_t>(std::min<int64_t>(grid, al->cu_count), std::max<int64_t>(1, nmax));   // (the redo list holds pairs of this batch)
-      // the queues must leave room for one ring slice per CU and one slice of the depth-first kernel — a large batch of
-      // short reads (10 M pairs: 6.4 GB of queues) would otherwise ask for more than the device has.  Queue overflow is a speed matter
-      // only (the redo list), so the capacity is clamped to half of what remains
-      if (knob(al, K_BILEVEL_QCAP, 0) <= 0) {
-        const int64_t room = budget - (int64_t)al->cu_count * la.slice_bytes - pair_bytes - stride * 4;
-        qcap = std::max<int64_t>(1024, std::min<int64_t>(qcap, room / 2 / 160));
-      }
-      const int64_t meta_bytes = qcap * 32 * 5 + pair_bytes;
-      while (bl_grid > al->cu_count && (int64_t)bl_grid * la.slice_bytes + meta_bytes + grid * stride * 4 > budget) bl_grid /= 2;
-      while (grid > 1 && (int64_t)bl_grid * la.slice_bytes + meta_bytes + grid * stride * 4 > budget) grid = (grid + 1) / 2;
-      la.qcap = la.qbcap = la.leafcap = la.qwcap = (uint32_t)qcap;
-      bl_bytes = (size_t)((int64_t)bl_grid * la.slice_bytes + meta_bytes);
-      dfs_off = (int64_t)((bl_bytes + 255) & ~(size_t)255);
-      // levels: a window's score halves per level (to within the ring's scope) until it is <= 250
-      const int64_t pmax = std::max<int64_t>(1, std::max<int64_t>(b->dcfg.x, std::max<int64_t>(b->dcfg.o1 + b->dcfg.e1, b->dcfg.o2 + b->dcfg.e2)));
-      int64_t smax = pmax * (int64_t)b->max_width;
-      bl_levels = 3;
-      while (smax > 250 && bl_levels < WFA_BL_MAX_LEVELS - 1) { smax /= 2; ++bl_levels; }
-      if (knob(al, K_BILEVEL_LEVELS, 0) > 0) bl_levels = std::min(knob(al, K_BILEVEL_LEVELS, 0), WFA_BL_MAX_LEVELS - 1);
-    }
-    int rc = ensure_ws(al, std::max((size_t)dfs_off + (size_t)grid * stride * 4, full ? (size_t)g.grid * g.ws_stride * 4 : (size_t)0));
+    const int rc = run_biwfa(al, b, stream, biwfa_score);
     if (rc != WFA_HIP_OK) return rc;
-    WfaKernelArgs& a = ba.k;
-    a.words = b->d_words; a.bytes = b->d_bytes; a.meta = b->d_meta; a.p_boff = b->d_pboff; a.t_boff = b->d_tboff;
-    a.score = b->d_score; a.status = b->d_status;
-    a.cigar_ops = b->d_ops; a.cigar_off = b->d_cigar_off; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len;
-    a.ws = reinterpret_cast<int*>(reinterpret_cast<char*>(al->ws) + dfs_off); a.ws_stride = stride; a.cfg = b->dcfg;
-    if (bilevel) {
-      char* p = reinterpret_cast<char*>(al->ws);
-      la.rings = p; p += (int64_t)bl_grid * la.slice_bytes;
-      la.q[0] = reinterpret_cast<wfa::BlWindow*>(p); p += (int64_t)la.qcap * 32;
-      la.q[1] = reinterpret_cast<wfa::BlWindow*>(p); p += (int64_t)la.qcap * 32;
-      la.qb = reinterpret_cast<wfa::BlWindow*>(p); p += (int64_t)la.qcap * 32;
-      la.qw = reinterpret_cast<wfa::BlWindow*>(p); p += (int64_t)la.qcap * 32;
-      la.leaves = reinterpret_cast<wfa::BlLeaf*>(p); p += (int64_t)la.qcap * 32;
-      la.failkey = reinterpret_cast<unsigned long long*>(p); p += (int64_t)b->n * 8;
-      la.head = reinterpret_cast<int*>(p); p += (int64_t)b->n * 4;
-      la.flags = reinterpret_cast<int*>(p); p += (int64_t)b->n * 4;
-      la.top = reinterpret_cast<int*>(p); p += (int64_t)b->n * 4;
-      la.redo_list = reinterpret_cast<uint32_t*>(p); p += (int64_t)b->n * 4;
-      la.cnt = reinterpret_cast<uint32_t*>(p);
-    }
-    for (int kind = 0; kind < 2; ++kind) {   // 2-bit pairs, then the pairs aligned on their bytes
-      const uint32_t cnt = kind ? b->n_bytes : b->n_packed;
-      if (cnt == 0) continue;
-      a.worklist = kind ? b->d_list_bytes : b->d_list_packed; a.nwork_dev = nullptr; a.nwork = cnt;
-      a.fb_list = full ? b->d_fb_list2[kind] : nullptr; a.fb_count = b->d_counters + 4 + kind;
-      a.cfg.wildcard = (kind && b->wild >= 0) ? b->wild : b->dcfg.wildcard;   // (the 8-bit pairs keep the wildcard rule)
-      int64_t dfs_grid = std::min<int64_t>(grid, cnt);
-      if (bilevel) {
-        la.k = a;
-        HIP_TRY(al, hipMemsetAsync(la.cnt, 0, WFA_BL_COUNTER_WORDS * sizeof(uint32_t), stream));
-        const bool stage_timing = knob(al, K_STAGE_TIMING, 0) != 0;   // development aid: synchronises
-        std::vector<hipEvent_t> tev;
-        auto mark = [&]() { if (stage_timing) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, stream); tev.push_back(e); } };
-        mark();
-        bool ok = wfa::launch_bl_seed(la, stream) == 0;
-        // four waves per window while the wavefronts are expected to span several chunks (about max_len / 8 diagonals at the top
-        // level for reads at 8 - 10 %, half of it per level)
-        int wide_auto = 0;
-        while (wide_auto < 8 && ((b->max_len / 8) >> wide_auto) >= 512) ++wide_auto;   // (10 kb: two levels, measured best of 0 / 2 / 3)
-        const int wide_levels = knob(al, K_BILEVEL_WIDE_LEVELS, wide_auto);
-        // Per level: the LDS form first where it pays (2-bit pairs, int16 offsets, gap-affine and the one-component metrics): both
-        // aligners' rows and the window's sub-sequences in LDS, W diagonals per row — W halves per level as the windows' scores do;
-        // used where at least two windows fit a CU (W <= 1024 for gap-affine 4/6/2).  A window whose wavefront outgrows W (or whose
-        // sub-sequences outgrow the buffers) moves to the level's second launch, the workspace form: rows in HBM / L2, the pair's
-        // sequences in LDS when they fit, four chunks of loads in flight per thread.
-        const bool lds_form = kind == 0 && bl_i16 && b->ncomp <= 3 && knob(al, K_BILEVEL_LDS, 0) != 0;   // (off: measured slower than the workspace form at every level of 1 kb and 10 kb reads — per-step overheads, not the rows' latency, are what a narrow window pays)
-        const int gsc = std::max(1, wfa::band_gcd(b->dcfg, false));
-        la.lds_slots = (b->dcfg.scope - 1) / gsc + 1;
-        const int full_seq_words = (b->max_len + 15) / 16 + 4;
-        const bool seql = kind == 0 && (size_t)2 * full_seq_words * 4 <= (size_t)48 * 1024 && knob(al, K_BILEVEL_NO_SEQL, 0) == 0;
-        const int lds_w_max = knob(al, K_BILEVEL_LDS_W, 1024);
-        for (int lv = 0; lv < bl_levels && ok; ++lv) {
-          la.level = lv;
-          la.from_wide = 0;
-          // expected width of a level's wavefronts: a quarter of the window's length at 8 - 10 % error; rows of 1.3 x that, a power of two
-          int w = 128;
-          while (w < 8192 && w < (int)((((int64_t)b->max_len * 13 / 40) >> lv))) w *= 2;
-          if (lds_form && w <= lds_w_max) {
-            la.lds_seq_words = std::min(full_seq_words, (int)(((int64_t)b->max_len * 3 / 2) >> lv) / 16 + 12);
-            const int lthreads = (w >= 2048) ? 1024 : (w >= 512) ? 256 : 64;
-            const size_t lsm = wfa::bl_split_lds_smem(b->ncomp, b->dcfg.scope, lthreads, w, la.lds_slots, la.lds_seq_words);
-            if (lsm <= (size_t)156 * 1024) {
-              la.lds_w = w;
-              const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)160 * 1024 / (lsm + 512), (size_t)(2048 / lthreads)));
-              const int64_t lgrid = (int64_t)al->cu_count * per_cu;
-              ok = wfa::launch_bl_split_lds_any(b->ncomp, lthreads, la, (int)std::min<int64_t>(lgrid, lv == 0 ? (int64_t)cnt : lgrid), stream) == 0;
-              la.from_wide = 1;
-            }
-          }
-          // (expected width of a level's wavefronts: a quarter of the read length at the top, half of it per level; sixteen waves per
-          // window from 8 192 diagonals on (measured at 20 / 40 / 100 kb: 1 024 / 2 048 / 4 096 / 8 192): 100 kb reads' top levels — a step is then 6 passes over the wavefront instead of 24)
-          const int64_t w_est = ((int64_t)b->max_len / 4) >> lv;
-          const bool few_windows = ((int64_t)cnt << std::min(lv, 20)) <= 2 * (int64_t)al->cu_count;   // (every window of the level resident at sixteen waves each)
-          const bool huge = kind == 0 && knob(al, K_BILEVEL_NO_1024, 0) == 0 &&
-                            (w_est >= knob(al, K_BILEVEL_HUGE_MIN, 8192) || (few_windows && w_est >= 2048));   // (small batches: 64 / 256 x 10 kb +20 %)
-          const int threads = huge ? 1024 : (lv < wide_levels) ? 256 : 64;
-          const int lgrid = huge ? std::min(bl_grid, 2 * al->cu_count)
-                                 : (threads == 256) ? std::min(bl_grid, std::max(al->cu_count, bl_grid / 2)) : bl_grid;   // (a slice of the workspace per workgroup: never more than bl_grid)
-          la.lds_seq_words = full_seq_words;
-          ok = ok && wfa::launch_bl_split_any(b->ncomp, kind == 0, bl_i16, threads, seql, la, (int)std::min<int64_t>(lgrid, lv == 0 ? (int64_t)cnt : (int64_t)lgrid), stream) == 0;
-          la.from_wide = 0;
-          mark();
-        }
-        ok = ok && wfa::launch_bl_base_any(b->ncomp, kind == 0, la, bl_grid, stream) == 0;
-        mark();
-        ok = ok && wfa::launch_bl_finish(la, (int)std::min<int64_t>((int64_t)al->cu_count * 16, cnt), stream) == 0;
-        mark();
-        if (!ok) { al->err = "BiWFA level kernel launch failed"; return WFA_HIP_EDEVICE; }
-        a.worklist = la.redo_list; a.nwork_dev = la.cnt + WFA_BL_MAX_LEVELS + 2; a.nwork = cnt;
-        dfs_grid = grid;
-        if (wfa::launch_biwfa_any(b->ncomp, kind == 0, ba, (int)dfs_grid, stream) != 0) { al->err = "BiWFA kernel launch failed"; return WFA_HIP_EDEVICE; }
-        mark();
-        if (stage_timing) {
-          (void)hipStreamSynchronize(stream);
-          uint32_t hc[WFA_BL_COUNTER_WORDS];
-          (void)hipMemcpy(hc, la.cnt, sizeof(hc), hipMemcpyDeviceToHost);
-          fprintf(stderr, "[wfa_hip] biwfa levels (%s, %d pairs, grid %d, slice %.2f MB, %s rings):", kind ? "bytes" : "2-bit", (int)cnt, bl_grid, la.slice_bytes / 1048576.0, bl_i16 ? "int16" : "int32");
-          for (int lv = 0; lv < bl_levels; ++lv) { float ms = 0; (void)hipEventElapsedTime(&ms, tev[lv], tev[lv + 1]); fprintf(stderr, " L%d %u windows (%u past the LDS form) %.3f ms;", lv, hc[lv], hc[128 + lv], ms); }
-          float mb = 0, mf = 0, md = 0;
-          (void)hipEventElapsedTime(&mb, tev[bl_levels], tev[bl_levels + 1]); (void)hipEventElapsedTime(&mf, tev[bl_levels + 1], tev[bl_levels + 2]); (void)hipEventElapsedTime(&md, tev[bl_levels + 2], tev[bl_levels + 3]);
-          fprintf(stderr, " base %u windows %.3f ms; finish %.3f ms (%u leaves); redo %u pairs %.3f ms\n", hc[WFA_BL_MAX_LEVELS], mb, mf, hc[WFA_BL_MAX_LEVELS + 1], hc[WFA_BL_MAX_LEVELS + 2], md);
-          for (hipEvent_t e : tev) (void)hipEventDestroy(e);
-        }
-        continue;
-      }
-      if (wfa::launch_biwfa_any(b->ncomp, kind == 0, ba, (int)dfs_grid, stream) != 0) { al->err = "BiWFA kernel launch failed"; return WFA_HIP_EDEVICE; }
-    }
-    if (full) {
-      for (int kind = 0; kind < 2; ++kind) {
-        if ((kind ? b->n_bytes : b->n_packed) == 0) continue;
-        rc = launch_general_dyn(al, b, stream, kind == 0, b->d_fb_list2[kind], b->d_counters + 4 + kind, 0u, g.ws_stride, g.grid, g.threads,
-                                b->d_ovf_list[0], b->d_counters + 1);
-        if (rc != WFA_HIP_OK) return rc;
-      }
-    }
-    b->last_kernel_pairs = b->n_packed > 0 ? b->n_packed : b->n_bytes;   // (the first launch's pairs, as the cascade below reports them)
     HIP_TRY(al, hipEventRecord(ev1, stream));
-    HIP_TRY(al, hipEventRecord(al->ws_event, stream));
-    al->ws_event_recorded = true; al->ws_last_stream = stream;
-    side_guard.ok = true;
-    return WFA_HIP_OK;
-  }
-  if (b->n_packed > 0) {
-    const uint32_t* in_list = b->d_list_packed;   // nullptr = identity
-    const uint32_t* in_count = nullptr;            // nullptr = host count
-    uint32_t in_n = b->n_packed;
-    int out_sel = 0;                               // leftovers go to d_fb_list[out_sel]; their count: a word of its own per stage
-    int stage_counts = 0;                          // (zeroed with all the counters at the start of the run: round 4 — a fill per stage was 9 x 4.5 us of a 3.2 ms C2 step)
-    auto next_count = [&]() -> uint32_t* { uint32_t* c = b->d_counters + 16 + stage_counts; if (stage_counts < WFA_COUNTER_WORDS - 17) ++stage_counts; return c; };
-    bool first_stage = true;
-    const bool adapt = (b->dcfg.heuristic != WFA_HEUR_NONE);  // the heuristic instantiations of the banded kernel (wf-adaptive / X-drop)
-    // the general kernel's geometry is fixed first so that one workspace allocation serves every stage
-    int n_stages = 0;
-    int band_nch[3] = {0, 0, 0};
-    // a handful of short pairs: one launch of the general kernel beats six nearly empty stages (single-pair calls of a
-    // pywfa-style loop).  Long reads take the stages whatever the count: an alignment of milliseconds dwarfs the launches, and
-    // the banded / wide kernels are several times faster per pair (8 pairs of C4 as written: 57 ms instead of 436 ms; 8 x 10 kb
-    // wf-adaptive with full CIGAR: 3.9 instead of 15.7 ms)
-    const bool tiny = in_n <= (uint32_t)knob(al, K_TINY_BATCH, 128) && b->max_len <= 1000;
-    const bool use_fast = !tiny && !full && wfa::seg_supported(b->dcfg, b->ncomp, full) && b->max_len <= WFA_FAST_MAX_LEN &&
-                          knob(al, K_NO_FAST, 0) == 0;
-    // full CIGARs of short reads: the segmented kernel with a history slot per pair, then the thread-per-alignment walk
-    // (round 6: a one-component distance with CIGARs, mapped — b->dcfg.lin: the register stages' LIN form exists as a run-time instantiation
-    // only; without hipRTC, and for what those stages hand on, the general kernel under the original configuration)
-    const bool lin = b->dcfg.lin != 0;
-    const bool lin_regs = lin && b->dcfg.rtc != 0 && wfa::rtc_available();
-    const bool use_segfull = (!lin || lin_regs) && !tiny && full && wfa::seg_supported(b->dcfg, b->ncomp, false) && b->max_len <= WFA_FAST_MAX_LEN &&
-                             knob(al, K_NO_FAST, 0) == 0 && knob(al, K_NO_SEGFULL, 0) == 0;
-    // Round 3: score-only short reads with wf-adaptive, free ends or a step limit — what the bound of the register kernels cannot
-    // prove — start in the general form of the lane kernel (wfa_lane_kernel<.., HEUR>: the pair is handed on the moment its
-    // wavefront touches the band's outermost slots); the banded stages take what it hands on
-    int lh_x, lh_oe, lh_e;
-    const bool use_laneh = !tiny && !full && !use_fast && wfa::lane_heur_config(b->dcfg, b->ncomp) && wfa::seg_shape(b->dcfg, &lh_x, &lh_oe, &lh_e) >= 0 &&
-                           (wfa::seg_shape(b->dcfg, &lh_x, &lh_oe, &lh_e) != WFA_SHAPE_RTC || wfa::rtc_lane_shape_ok(lh_x, lh_oe, lh_e)) &&
-                           b->max_len <= WFA_FAST_MAX_LEN && knob(al, K_NO_FAST, 0) == 0 &&
-                           (b->laneh_pick == 1 || b->laneh_pick == 3 || (b->laneh_pick == 0 && knob(al, K_LANE_HEUR, 0) != 0));   // (the pilot of batch_build, or WFA_HIP_LANE_HEUR=1 / 2)
-    const int laneh_form = (b->laneh_pick == 3 || (b->laneh_pick == 0 && knob(al, K_LANE_HEUR, 0) == 2)) ? 2 : 1;   // (2: 32 diagonals per pair)
-    // ... and then (or first, when the lane form's pilot said no) the same form of the 32-lane segments: two pairs per wave, a band twice
-    // as wide (WFA_HIP_SEG_HEUR=0: off)
-    const bool use_segh = !tiny && !full && !use_fast && wfa::seg_heur_config(b->dcfg, b->ncomp) && b->max_len <= WFA_FAST_MAX_LEN &&
-                          knob(al, K_NO_FAST, 0) == 0 && !wfa::seg_supported(b->dcfg, b->ncomp, false) &&
-                          (b->segh_pick == 1 || (b->segh_pick == 0 && knob(al, K_SEG_HEUR, 0) != 0)) &&   // (the pilot of batch_build, or WFA_HIP_SEG_HEUR=1)
-                          // (behind the 32-slot lane form the segments would see the same 32 diagonals again: what it hands on — 2 % of 150 bp
-                          // pairs at 2 % — goes straight to the banded stages, 2.22 -> 2.02 ms per 2 M pairs; WFA_HIP_SEG_HEUR=1 keeps the stage)
-                          !(use_laneh && laneh_form == 2 && knob(al, K_SEG_HEUR, -1) < 0);
-    if (!lin && !tiny && wfa::band_supported(b->dcfg, b->ncomp) && (b->ncomp != 5 || b->max_len < 32000) && knob(al, K_NO_BAND, 0) == 0) {
-      if (b->ncomp == 5) {
-        // gap-affine-2p wavefronts are wide (C4: 99 % need more than 108 diagonals, 2.6 % more than 172)
-        if (b->band_pick != 2) { band_nch[n_stages++] = 3; band_nch[n_stages++] = 4; }   // (2: the pilot of batch_build saw most pairs outgrow 256 diagonals)
-      } else if (adapt) {
-        // (the wavefront a cut-off keeps grows with the read: at 10 kb 3 % of the pairs outgrow the 128-diagonal window, at 100 kb 46 % —
-        // and a second stage of few, lone waves runs at its pairs' latency: reads over 20 kb start in the 256-diagonal window.
-        // 8 192 x 100 kb wf-adaptive: 509 -> 359 ms)
-        if (b->max_len <= 300) { band_nch[n_stages++] = 1; }
-        if (b->max_len <= 20000) band_nch[n_stages++] = 2;
-        band_nch[n_stages++] = 4;
-      } else if (b->max_len <= 300) {
-        if (!use_fast && !use_segfull) band_nch[n_stages++] = 1;
-        band_nch[n_stages++] = 2; band_nch[n_stages++] = 4;
-      } else if (b->max_len <= 1200) {
-        if (b->band_pick != 2) band_nch[n_stages++] = 4;   // (2: the pilot of batch_build saw most pairs outgrow the window)
-      }
-      const int only = knob(al, K_BAND_NCH, 0);
-      if (only) { n_stages = 1; band_nch[0] = only; }
+  } else {
+    if (b->n_packed > 0) {
+      const int rc = run_cascade(al, b, stream);
+      if (rc != WFA_HIP_OK) return rc;
     }
-    // (round 3) wf-adaptive: the wide kernel takes what the banded stages hand on — the few pairs whose wavefront outgrows 256 diagonals
-    // (47 of 8 192 at 100 kb) — instead of the general kernel: rows in the workspace, its cut-off in-kernel (WFA_HIP_WIDE_ADAPT=0: off)
-    // (reads over 20 kb: at 10 kb the general kernel is as quick for the odd pair, and the 2p rows of the wide kernel are slower)
-    const int wide_adapt_knob = knob(al, K_WIDE_ADAPT, 1);
-    const bool wide_adapt = b->dcfg.heuristic == WFA_HEUR_ADAPTIVE && b->max_len > 1000 &&
-                            (wide_adapt_knob == 2 || (n_stages > 0 && wide_adapt_knob != 0 && b->max_len > 20000));   // (2: any length, also without banded stages in front: tests)
-    const bool wide_ok = !lin && !tiny && ((b->ncomp == 3 && b->dcfg.metric == 3) || (b->ncomp == 5 && b->dcfg.metric == 4 && b->dcfg.e2 >= 1)) &&
-                         (b->dcfg.heuristic == WFA_HEUR_NONE || wide_adapt) && b->dcfg.match == 0 &&
-                         b->max_len > 64 && 2 * (int64_t)b->max_len <= 0x3fffff00ll && b->dcfg.e1 >= 1 && b->dcfg.x >= 1 && knob(al, K_NO_WIDE, 0) == 0;
-    // reads beyond 16 kb (plen + tlen > 32 000 does not fit int16 offsets): the workspace-row form with int32 rows (round 3)
-    const bool wide32 = 2 * (int64_t)b->max_len > 32000;
-    const bool any_pre = use_fast || use_laneh || use_segh || use_segfull || n_stages > 0 || wide_ok;
-    Geometry g = plan_general(al, b, any_pre ? std::min<uint32_t>(in_n, (uint32_t)al->cu_count * 16) : in_n, b->arena_fixed + b->arena_ints);
-    size_t need = (size_t)g.grid * g.ws_stride * 4;
-    // band history: fixed-stride records per score step, one slice per wave
-    long long band_grid[3] = {0, 0, 0};
-    int64_t band_stride[3] = {0, 0, 0};
-    size_t split_region = 0, later_need = 0;   // bytes of the split stage's slots; largest history of the band stages behind it
-    // The split stage (long reads) keeps the piggy-back history (the reference's R/wavefront_backtrace_offload.c scheme): one
-    // byte of origin codes per (step, diagonal) instead of the offsets, the matches re-extended afterwards.  In EVERY
-    // memory mode: the op strings are the same and it is the faster form (C3 91 vs 97 ms per 100 k pairs, C4 adaptive 57 vs
-    // 77 ms per 10 k: 8-16x less history, so more pairs per launch); WFA_HIP_BAND_PB=0 keeps the explicit offsets.
-    const int pb_env = knob(al, K_BAND_PB, -1);
-    const bool pb_mode = full && (pb_env >= 0 ? pb_env != 0 : true);
-    int64_t pb_code_ints = 0, pb_event_ints = 0, pb_stride = 0;
-    // Round 6, the pipelined tail (16 % of a C4-adaptive run was a latency tail — the 256-diagonal stage 22.7 ms
-    // and the general kernel 17.4 ms for ONE pair, both after the last launch of the split stage).  What launch j of the split stage
-    // hands on is aligned by the stage behind it — and what THAT hands on by the general kernel — on a third stream beside launch
-    // j + 1: [snapshot of the hand-over count before, after) is the launch's part of the list (BandArgs::wbeg_dev).  Only the last
-    // launch's leftovers remain exposed.  Needs a region of its own for each of the two (behind the split stage's slots), two band
-    // stages, long reads with CIGARs (the split form), no tile / wide stage in the chain.  WFA_HIP_PIPE_TAIL=0: off
-    const bool want_pipe_tail = full && n_stages == 2 && b->max_len > 1000 && knob(al, K_PIPE_TAIL, 1) != 0 && knob(al, K_NO_DUAL, 0) == 0 &&
-                                knob(al, K_STAGE_TIMING, 0) == 0 && !al->knobs.set[K_BAND_LEFTOVER_WAVES_PER_CU];
-    for (int i = 0; i < n_stages; ++i) {
-      // 4x more waves than a CU holds at once: waves retire one after the other (oldest-first issue) and the
-      // dispatcher refills the CU, instead of a tail of lone waves (C1 +20 %, C3 +13 %)
-      long long grid = (long long)al->cu_count * knob(al, K_BAND_WAVES_PER_CU, 128);
-      grid = std::min<long long>(grid, in_n);
-      if (i > 0 || use_fast || use_laneh || use_segh || use_segfull) grid = std::min<long long>(grid, (long long)al->cu_count * knob(al, K_BAND_LEFTOVER_WAVES_PER_CU, 64));
-      if (i > 0 && want_pipe_tail) grid = std::min<long long>(grid, (long long)al->cu_count * 8);   // (one launch's leftovers at a time: a few hundred pairs; the history slices are tens of megabytes each)
-      if (full) {
-        const bool h16 = b->max_len < 32000;
-        const int rec = ((h16 && b->ncomp != 5) ? 2 : 4) * (band_nch[i] == 3 ? 256 : 64 * band_nch[i]);  // ints per record (2p: 16-byte entries)
-        // steps of an alignment = score / g; sized for scores up to 0.9 x the read length (about 15 % divergence)
-        long long records = std::max<long long>(256, (long long)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / wfa::band_gcd(b->dcfg, b->ncomp == 5) + 64);
-        records = knob(al, K_BAND_RECORDS, (int)records);
-        band_stride[i] = ((int64_t)records * rec + 63) & ~63ll;
-        const int64_t budget = free_budget(al);
-        while (grid > 1 && grid * band_stride[i] * 4 > budget) grid = (grid + 1) / 2;
-        need = std::max(need, (size_t)grid * band_stride[i] * 4);
-        if (i == 0 && !use_fast && !use_segfull && b->max_len > knob(al, K_BAND_SPLIT_MIN, 100) && knob(al, K_BAND_NO_SPLIT, 0) == 0) {
-          // split backtrace: one history slot per pair of a launch; take up to 4x the wave count (or all pairs)
-          if (pb_mode) {
-            pb_code_ints = ((int64_t)records * ((band_nch[i] == 3 ? 256 : 64 * band_nch[i]) / 4) + 63) & ~63ll;  // one byte per window position and step
-            pb_event_ints = (((int64_t)records + 3) / 4 + 63) & ~63ll;                 // one byte per edit event (<= one per step)
-            pb_stride = pb_code_ints + pb_event_ints + ((2 * (int64_t)records + 8 + 63) & ~63ll);  // + run records
-          }
-          const int64_t slot_bytes = (pb_mode ? pb_stride : band_stride[i]) * 4 + 16;
-          // slots for every pair of the batch when they fit half of the free memory (the compact piggy-back history: C3 0.3 MB
-          // per pair), otherwise for as many pairs as do (explicit history: up to 4 x the resident waves)
-          int64_t pairs = in_n;
-          if (pairs * slot_bytes > budget / 2) {
-            // (round 6: gap-affine-2p 8 — its kernel holds 12 waves per CU, so a launch of cu_count x 64 pairs was 1.17 rounds of resident
-            // waves with most of the chip idle in the second one; with twice the slots a launch is 2.7 rounds: C4-adaptive 214 -> 204 ms)
-            pairs = std::min<int64_t>(in_n, (int64_t)al->cu_count * 32 * knob(al, K_BAND_SPLIT_ROUNDS, b->ncomp == 5 ? 8 : 4));
-            while (pairs > 1 && pairs * slot_bytes > budget) pairs = (pairs + 1) / 2;
-          }
-          split_region = ((size_t)(pairs * slot_bytes) + 255) & ~(size_t)255;
-          need = std::max(need, split_region);
-        } else if (i > 0) {
-          later_need = std::max(later_need, (size_t)grid * band_stride[i] * 4);
-        }
-      }
-      band_grid[i] = grid;
+    HIP_TRY(al, hipEventRecord(ev1, stream));
+    // 3) 8-bit pairs (non-ACGT letters, wildcard matching)
+    if (b->n_bytes > 0) {
+      Geometry g = plan_general(al, b, b->n_bytes, b->arena_fixed + b->arena_ints);
+      int rc = ensure_ws(al, (size_t)g.grid * g.ws_stride * 4);
+      if (rc != WFA_HIP_OK) return rc;
+      rc = launch_general_dyn(al, b, stream, false, b->d_list_bytes, nullptr, b->n_bytes, g.ws_stride, g.grid, g.threads,
+                              b->d_ovf_list[0], b->d_counters + CNT_OVF);
+      if (rc != WFA_HIP_OK) return rc;
     }
-    // the band stages behind a split stage get a region of their own behind its slots when both fit: the walks of the split
-    // stage's last launch then run under them
-    size_t later_off = 0, gen_off = 0;
-    int gen_grid = 0;
-    int64_t gen_stride = g.ws_stride;
-    if (split_region && later_need && (int64_t)(split_region + later_need) <= free_budget(al)) {
-      later_off = split_region;
-      need = std::max(need, split_region + later_need);
-      if (want_pipe_tail) {   // ... and the general kernel behind them a few slices of its own
-        // (a pair that reaches it has outgrown 256 diagonals: the arena of the first attempt would overflow and the pair be re-run with
-        // an 8 x larger one after a host round trip — 62 ms for ONE pair of a C4-adaptive run; these few slices start that large)
-        gen_grid = std::max(1, std::min(g.grid, 16));
-        const size_t at = (split_region + later_need + 255) & ~(size_t)255;
-        if (full) gen_stride = ((b->arena_fixed + 8 * b->arena_ints) + 63) & ~63ll;
-        size_t gen_need = (size_t)gen_grid * (size_t)gen_stride * 4;
-        if ((int64_t)(at + gen_need) > free_budget(al)) { gen_stride = g.ws_stride; gen_need = (size_t)gen_grid * (size_t)gen_stride * 4; }
-        if ((int64_t)(at + gen_need) <= free_budget(al)) { gen_off = at; need = std::max(need, at + gen_need); }
-      }
-    }
-    // Wide-wavefront stage (wfa_wide.hpp): exact gap-affine pairs the register windows cannot hold (or never try: reads
-    // over 1.2 kb without a heuristic) — one alignment per workgroup, the wavefront rows in LDS; what it hands on goes to
-    // the general kernel.  Rows as wide as LDS allows, at most the whole diagonal range of the longest pair.
-    // Up to two such stages: rows in LDS (gap-affine: the faster form, 23.3 vs 21.7 k aln/s at 10 kb, but ~7 900 diagonals at
-    // most), then rows in the workgroup's slice of the HBM workspace (as wide as the whole diagonal range of the longest pair: no
-    // pair outgrows them; gap-affine-2p has only this form: its M ring alone is o2 + e2 + 1 rows).
-    struct WideStage { wfa::WideArgs a; int grid = 0, threads = 0; size_t smem = 0, hist_off = 0; bool grows = false, w32 = false; };
-    WideStage wide_stage[3];
-    int n_wide = 0;
-    struct TileStage { wfa::TileArgs a; int grid = 0, threads = 0; size_t smem = 0, hist_off = 0; bool on = false, w32 = false; } tile_stage;
-    const bool wide_two = (b->ncomp == 5);
-    if (wide_ok) {
-      wfa::WideArgs w0;
-      memset(&w0, 0, sizeof(w0));
-      w0.g = wide_two ? wfa::band_gcd(b->dcfg, true) : wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1);
-      w0.X = b->dcfg.x / w0.g; w0.OE = (b->dcfg.o1 + b->dcfg.e1) / w0.g; w0.E = b->dcfg.e1 / w0.g;
-      if (wide_two) { w0.OE2 = (b->dcfg.o2 + b->dcfg.e2) / w0.g; w0.E2 = b->dcfg.e2 / w0.g; }
-      w0.seq_words = ((b->max_len + 15) >> 4) + 4;
-      const int nrows = wfa::wide_rows(w0.X, w0.OE, w0.E, w0.OE2, w0.E2);
-      const int64_t budget = free_budget(al);
-      const int full_range = (2 * b->max_len + 8 + b->dcfg.pbf + b->dcfg.tbf) & ~1;
-      bool lds_covers_all = false;
-      // Round 3: the pass of a step is a short dependent chain (row reads -> recurrences -> sequence reads -> stores -> barrier),
-      // so a CU is kept busy by MANY pairs in flight, not by many threads on one pair: with rows in the workspace (L2) a workgroup
-      // needs only its sequences in LDS, and 8 workgroups of 256 threads per CU align 10 kb reads 1.6x faster than one workgroup
-      // of 1 024 threads with its rows in LDS (36.8 k vs 23.3 k aln/s; gap-affine-2p: 4 x 512 threads, +25 %).  The LDS form
-      // (north_star's layout) remains what a small batch gets: all of a CU's threads on one pair is the shortest latency.
-      // WFA_HIP_WIDE_GROWS: 1 = workspace rows always, 0 = LDS rows first always
-      const int grows_knob = knob(al, K_WIDE_GROWS, -1);
-      const bool many_pairs = (int64_t)in_n >= (int64_t)al->cu_count * 2;
-      const bool prefer_ws = grows_knob >= 0 ? grows_knob != 0 : many_pairs;
-      // threads per workgroup of the workspace form: 256 (gap-affine-2p: 512) once the batch has a pair for every CU's four
-      // workgroup slots of that size — measured on 2 000 x 10 kb: 128 threads 35.1 k, 256: 36.8 k, 384: 31.0 k, 512: 32.6 k, 1 024: 21.6 k aln/s
-      // (8 192 x 10 kb: 128 threads 200 / 231 ms score / full, 256: 207 / 241; C4 as written, 4 096 pairs: 256 threads 705 ms, 512: 740,
-      // 384: 925, 128: 719; the 2p form compiled for six waves per SIMD — three 512-thread workgroups per CU instead of two — 1 047 ms:
-      // more workgroups in flight than the rows' L2 footprint allows cost more than the latency they hide)
-      int ws_threads = 1024;
-      if (!wide_two && (int64_t)in_n >= (int64_t)al->cu_count * 16) ws_threads = 128;
-      else if ((int64_t)in_n >= (int64_t)al->cu_count * 8) ws_threads = 256;
-      else if ((int64_t)in_n >= (int64_t)al->cu_count * 4) ws_threads = wide_two ? 512 : 256;
-      else if ((int64_t)in_n >= (int64_t)al->cu_count * 2) ws_threads = 512;
-      // Round 4: the temporally blocked form (wfa_tile.hpp) goes first for exact alignments with int16 rows: a wave advances a
-      // block of diagonals by T steps inside an LDS tile, the rows in the workspace are read and written once per T steps.  What it
-      // hands on (pairs where the reference's per-step trimming would change a value, a history that does not fit) goes to the
-      // step-by-step forms below.  WFA_HIP_TILE=0: off; WFA_HIP_TILE_T / _WT / _THREADS / _PER_CU: geometry
-      // (round 6: reads of up to 32 000 bases on int16 rows — their NULL is -32768.  Longer ones: wfa_tile_kernel<.., W32> — int32 cells,
-      // the sequences read from global memory (50 KB of them per workgroup in LDS left one workgroup per CU), eight waves per pair.  One
-      // workgroup per pair needs pairs to fill the chip: exact 100 kb score, 512 / 1 024 pairs 345 / 351 aln/s against 275 / 192 on the
-      // step-by-step forms below, but 256 pairs 238 against 290 and 64 pairs 62 against 104 — so from two pairs per CU on.
-      // WFA_HIP_TILE32 = 0 never, 1 always)
-      const bool tile32 = b->max_len > WFA_TILE_MAX_LEN;
-      const int tile_cb = tile32 ? 4 : 2;
-      const int tile32_knob = knob(al, K_TILE32, -1);
-      const bool tile32_on = tile32_knob >= 0 ? tile32_knob != 0 : (int64_t)in_n >= 2 * (int64_t)al->cu_count;
-      if (b->dcfg.heuristic == WFA_HEUR_NONE && (!tile32 || (tile32_on && 2 * (int64_t)b->max_len < ((int64_t)1 << 29))) && knob(al, K_TILE, 1) != 0) {
-        wfa::TileArgs& ta = tile_stage.a;
-        memset(&ta, 0, sizeof(ta));
-        wfa::TileGeom& tg = ta.g;
-        tg.X = w0.X; tg.OE = w0.OE; tg.E = w0.E; tg.OE2 = w0.OE2; tg.E2 = w0.E2;
-        tg.DM = std::max(std::max(tg.X, tg.OE), tg.OE2);
-        // geometry by read length (round 5): reads of up to 8 kb have wavefronts of a few hundred diagonals and scores of a few hundred
-        // steps — tiles of 128 diagonals advanced 8 steps by two waves per alignment keep more alignments in flight and waste less of
-        // a tile on halo (1 kb at 5 %: 4.3 -> 6.6 M aln/s, 2 kb at 1 %: 6.8 -> 15.1 M, 600 bp at 10 %: 3.9 -> 5.9 M; 4 kb at 5 %: equal)
-        const bool small_geom = !wide_two && b->max_len <= 8000;   // (3 / 5 / 7 kb at 5 %: equal / +10 % / +2 % score, 5 kb full +35 %; 10 kb: -20 %)
-        tile_stage.w32 = tile32;
-        tg.T = knob(al, K_TILE_T, (wide_two || small_geom) ? 8 : 16) & ~1;
-        tg.Wt = tile32 ? (wide_two ? 128 : 256) : knob(al, K_TILE_WT, (wide_two || small_geom) ? 128 : 256);   // (int32 cells: the two widths that exist)
-        const int bw = tg.Wt - 2 * tg.T;
-        // (gap-affine-2p reads of up to 1.2 kb: one wave per alignment — 300 / 600 / 1 000 bp at 8 %: +28 / +51 / +29 % over four;
-        // round 6: gap-affine reads over 16 kb eight waves — 30 kb, 512 pairs: 128 / 256 / 512 threads 4.6 / 8.7 / 11.7 k aln/s; 10 kb keeps 256)
-        const int tthreads = std::max(64, std::min(512, knob(al, K_TILE_THREADS, (tile32 || (!wide_two && b->max_len > 16000)) ? 512 : small_geom ? 128 : (wide_two && b->max_len <= 1200) ? 64 : 256) & ~63));
-        if (tg.T >= 2 && tg.T <= WFA_TILE_MAX_T && tg.Wt >= 64 && tg.Wt % 64 == 0 && tg.Wt <= 256 && bw >= 16 &&
-            wfa::tile_cand_count(tg) <= WFA_TILE_MAX_ROWS) {
-          ta.gs = w0.g; ta.seq_words = tile32 ? 0 : w0.seq_words;   // (int32 form: the sequences stay in global memory)
-          const int nbmax = (2 * b->max_len + 1 + bw - 1) / bw;
-          ta.rwh = (nbmax * bw + 2 * tg.T + 1) & ~1;
-          ta.rows_stride = ((int64_t)wfa::tile_hbm_rows(tg) * ta.rwh + 63) & ~63ll;
-          tile_stage.threads = tthreads;
-          tile_stage.smem = wfa::tile_smem_bytes(tg, ta.seq_words, tthreads / 64, tile_cb);
-          if (tile_stage.smem <= (size_t)160 * 1024) {
-            int per_cu = wfa::tile_occupancy(full, wide_two, tg.Wt / 64, tthreads, tile_stage.smem, tile32);
-            per_cu = std::max(1, std::min(per_cu, knob(al, K_TILE_PER_CU, 16)));
-            tile_stage.grid = (int)std::min<int64_t>((int64_t)al->cu_count * per_cu, in_n);
-            int64_t hist_bytes = 0;
-            if (full) hist_bytes = (int64_t)full_range * ((int64_t)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / w0.g + 64 + tg.T) / 2 + (1 << 20);
-            while (tile_stage.grid > 1 && (int64_t)tile_stage.grid * (ta.rows_stride * tile_cb + hist_bytes) > budget) tile_stage.grid = (tile_stage.grid + 1) / 2;
-            if ((int64_t)tile_stage.grid * (ta.rows_stride * tile_cb + hist_bytes) <= budget) {
-              ta.hist_stride = (hist_bytes / 4) & ~15ll;
-              tile_stage.hist_off = ((size_t)tile_stage.grid * (size_t)ta.rows_stride * tile_cb + 255) & ~(size_t)255;
-              need = std::max(need, tile_stage.hist_off + (size_t)tile_stage.grid * (size_t)ta.hist_stride * 4);
-              tile_stage.on = true;
-            }
-          }
-        }
-      }
-      if (!wide_two && !wide32 && !prefer_ws && !wide_adapt) {
-        WideStage& st = wide_stage[n_wide];
-        st.a = w0;
-        const size_t lds_max = (size_t)std::min(160, std::max(16, knob(al, K_WIDE_LDS_KB, 160))) * 1024;
-        const size_t fixed = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, 0, 0, 0, w0.seq_words, true);
-        if (fixed + (size_t)nrows * 2 * 512 <= lds_max) {
-          int wcap = (int)((lds_max - fixed) / ((size_t)nrows * 2)) - 4;
-          wcap = std::min(wcap, full_range) & ~1;
-          lds_covers_all = wcap >= full_range;
-          st.a.wcap = wcap;
-          st.smem = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, 0, 0, wcap, w0.seq_words, true);
-          const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, ((size_t)160 * 1024) / st.smem));
-          st.threads = knob(al, K_WIDE_THREADS, per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024));
-          st.grid = (int)std::min<int64_t>((int64_t)al->cu_count * per_cu, in_n);
-          if (full) {
-            // history: one byte per cell up to the step where a wavefront would outgrow the rows, + directory + events
-            const int64_t tmax = (int64_t)wcap * w0.E / 2 + 64;
-            int64_t bytes = (int64_t)wcap * wcap * w0.E / 4 + 16 * tmax + (1 << 16);
-            while (st.grid > 1 && (int64_t)st.grid * bytes > budget) st.grid = (st.grid + 1) / 2;
-            bytes = std::min<int64_t>(bytes, budget / std::max(st.grid, 1));
-            st.a.hist_stride = (bytes / 4) & ~15ll;
-            need = std::max(need, (size_t)st.grid * (size_t)st.a.hist_stride * 4);
-          }
-          ++n_wide;
-        }
-      }
-      // Round 4: what the banded stages hand on under wf-adaptive (47 of 8 192 pairs of 100 kb: a wavefront beyond their 256 diagonals)
-      // is a few hundred diagonals wide and a handful of pairs — one alignment's latency is all that counts.  Rows in LDS (int32 beyond
-      // 16 kb), as many diagonals as fit beside the sequences, one workgroup per CU: a step costs LDS round trips instead of L2 ones
-      // (100 kb: 5.2 us per step there).  A wavefront that leaves the rows goes on to the workspace form below.
-      if (wide_adapt && knob(al, K_WIDE_ADAPT_LDS, 1) != 0) {
-        WideStage& st = wide_stage[n_wide];
-        st.a = w0; st.grows = false; st.w32 = wide32;
-        const int ob = wide32 ? 4 : 2;
-        const size_t lds_max = (size_t)std::min(160, std::max(16, knob(al, K_WIDE_LDS_KB, 160))) * 1024;
-        const size_t fixed = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, w0.OE2, w0.E2, 0, w0.seq_words, true, ob);
-        if (fixed + (size_t)nrows * ob * 516 <= lds_max) {
-          int wcap = (int)((lds_max - fixed) / ((size_t)nrows * ob)) - 4;
-          wcap = std::min(std::min(wcap, 4096), full_range) & ~1;
-          if (knob(al, K_WIDE_ADAPT_LDS, 1) > 1) wcap = std::min(wcap, knob(al, K_WIDE_ADAPT_LDS, 1) & ~1);   // (tests: rows so narrow that pairs go on to the workspace form)
-          st.a.wcap = wcap;
-          st.smem = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, w0.OE2, w0.E2, wcap, w0.seq_words, true, ob);
-          st.threads = knob(al, K_WIDE_THREADS, 512);
-          st.grid = (int)std::min<int64_t>((int64_t)al->cu_count, in_n);
-          bool fits = true;
-          if (full) {
-            int64_t hist_bytes = std::min<int64_t>((int64_t)full_range * ((int64_t)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / w0.g + 64) / 2 + (1 << 20),
-                                                   ((int64_t)(b->max_len * 1.2) / w0.g + 64) * 2048 + (1 << 20));
-            while (st.grid > 1 && (int64_t)st.grid * hist_bytes > budget) st.grid = (st.grid + 1) / 2;
-            fits = (int64_t)st.grid * hist_bytes <= budget;
-            st.a.hist_stride = (hist_bytes / 4) & ~15ll;
-            if (fits) need = std::max(need, (size_t)st.grid * (size_t)st.a.hist_stride * 4);
-          }
-          if (fits) ++n_wide;
-        }
-      }
-      if (!lds_covers_all) {
-        WideStage& st = wide_stage[n_wide];
-        st.a = w0; st.grows = true; st.w32 = wide32;
-        st.a.wcap = full_range;
-        st.a.rows_stride = (int64_t)((nrows * wfa::wide_row_halfs(full_range) + 63) & ~(size_t)63);
-        const int64_t row_bytes = wide32 ? 4 : 2;   // bytes per offset
-        st.smem = wfa::wide_smem_bytes(w0.X, w0.OE, w0.E, w0.OE2, w0.E2, full_range, w0.seq_words, false);
-        const bool seqs_fit_lds = st.smem <= (size_t)160 * 1024;   // (both packed sequences are staged in LDS: reads up to ~300 kb)
-        st.threads = knob(al, K_WIDE_THREADS, wide_adapt ? 512 : ws_threads);   // (wf-adaptive: a cut wavefront is a few hundred diagonals: one cell per thread)
-        st.grid = (int)std::min<int64_t>((int64_t)al->cu_count * std::max<int64_t>(1, std::min<int64_t>(2048 / st.threads, (160 * 1024) / std::max<size_t>(st.smem, 1))), in_n);
-        if (wide_adapt) st.grid = std::min(st.grid, al->cu_count);   // (leftovers: one workgroup per CU is plenty)
-        int64_t hist_bytes = 0;
-        if (full) hist_bytes = (int64_t)full_range * ((int64_t)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / w0.g + 64) / 2 + (1 << 20);   // one byte per cell, + directory + events
-        // (wf-adaptive: the cut-off keeps the wavefronts narrow: ~2 KB of codes per step; a pair that needs more is handed on)
-        if (full && wide_adapt) hist_bytes = std::min<int64_t>(hist_bytes, ((int64_t)(b->max_len * 1.2) / w0.g + 64) * 2048 + (1 << 20));
-        while (st.grid > 1 && (int64_t)st.grid * (st.a.rows_stride * row_bytes + hist_bytes) > budget) st.grid = (st.grid + 1) / 2;
-        if (seqs_fit_lds && (int64_t)st.grid * (st.a.rows_stride * row_bytes + hist_bytes) <= budget) {
-          st.a.hist_stride = (hist_bytes / 4) & ~15ll;
-          st.hist_off = ((size_t)st.grid * (size_t)st.a.rows_stride * (size_t)row_bytes + 255) & ~(size_t)255;
-          need = std::max(need, st.hist_off + (size_t)st.grid * (size_t)st.a.hist_stride * 4);
-          ++n_wide;
-        }
-      }
-    }
-    // full CIGARs of short reads: 16-lane segments over the whole batch (history slot per pair, several launches), then
-    // 32- and 64-lane segments over what was handed on (device-side counts: slots for 1/8 resp. 1/32 of the batch)
-    int64_t segfull_slot_ints[3] = {0, 0, 0}, segfull_cap[3] = {0, 0, 0};
-    int segfull_w[3] = {16, 32, 64};
-    int n_segfull = use_segfull ? 3 : 0;
-    if (use_segfull && b->stage_pick != 0 && !al->knobs.set[K_SEGFULL_STAGES]) {   // (the pilot of batch_build chose the first width)
-      n_segfull = 0;
-      for (int w = 16; w <= 64; w *= 2) if (w >= b->stage_pick) segfull_w[n_segfull++] = w;
-    } else if (use_segfull) {
-      n_segfull = std::max(0, std::min(3, knob(al, K_SEGFULL_STAGES, 3)));
-    }
-    // Round 3: the 16-diagonal stage of that cascade is the lane-per-pair kernel with origin codes (wfa_lane_kernel<.., FULL>):
-    // it walks in-kernel and leaves only run records in HBM (WFA_LANE_RUN_SLOT ints + an end state per pair), so the whole batch
-    // is one launch; WFA_HIP_LANE_FULL=0 keeps the 16-lane segments (round 4: with piggy-back code records) as the first stage
-    int lfs_x = 0, lfs_oe = 0, lfs_e = 0;
-    const bool lane_shape_fits = wfa::seg_shape(b->dcfg, &lfs_x, &lfs_oe, &lfs_e) != WFA_SHAPE_RTC || wfa::rtc_lane_shape_ok(lfs_x, lfs_oe, lfs_e);
-    const bool use_lanefull = use_segfull && n_segfull >= 1 && segfull_w[0] == 16 && knob(al, K_LANE_FULL, 1) != 0 && lane_shape_fits;
-    // (behind it one segment stage, 32 lanes, then the banded kernel: the 64-lane stage cost more in launches than its ~300 pairs per
-    // million are worth)
-    if (use_lanefull) { for (int i = 1; i < n_segfull; ++i) segfull_w[i - 1] = segfull_w[i]; --n_segfull; if (!al->knobs.set[K_SEGFULL_STAGES]) n_segfull = std::min(n_segfull, 1); }
-    if (use_segfull) {
-      for (int i = 0; i < n_segfull; ++i) {
-        const int rank = i + (use_lanefull ? 1 : 0);   // position in the cascade: 0 = takes the whole batch
-        { long long ci, ei, si; wfa::seg_full_slot(b->dcfg, segfull_w[i], b->max_len, &ci, &ei, &si); segfull_slot_ints[i] = si; }   // code records of w bytes, events, runs
-        const int64_t slot_bytes = segfull_slot_ints[i] * 4 + (int64_t)sizeof(int4);
-        int64_t want = (rank == 0) ? std::min<int64_t>((int64_t)knob(al, K_SEGFULL_PAIRS, 2000000), std::max<int64_t>(1, ((int64_t)8 << 30) / slot_bytes))
-                                   : std::max<int64_t>(4096, (int64_t)in_n / (rank == 1 ? 8 : 32));
-        // (the stage that takes the whole batch runs it as two balanced launches at least, once each still fills the chip: the walks and
-        // the expand of a launch — a third of the stage's time at 10 % divergence — run under the alignment kernel of the next)
-        if (rank == 0 && in_count == nullptr && (int64_t)in_n >= 262144 && !al->knobs.set[K_SEGFULL_PAIRS] && knob(al, K_NO_DUAL, 0) == 0)
-          want = std::min<int64_t>(want, (((int64_t)in_n + 1) / 2 + 63) & ~63ll);
-        segfull_cap[i] = std::max<int64_t>(1, std::min<int64_t>(in_n, std::min<int64_t>(want, free_budget(al) / slot_bytes)));
-        // (several launches: two slot arrays, the walks of a launch run under the alignment kernel of the next)
-        need = std::max(need, (size_t)(segfull_cap[i] * slot_bytes) * ((rank == 0 && segfull_cap[i] < (int64_t)in_n) ? 2 : 1));
-      }
-    }
-    // the lane-full stage's region lies BEHIND everything the later stages use (its expand runs on the side stream under them)
-    const int64_t lanefull_slot_bytes = (int64_t)WFA_LANE_RUN_SLOT * 4 + (int64_t)sizeof(int4);
-    int64_t lanefull_cap = 0;
-    long long lanefull_grid = 0;
-    int lanefull_recs = 0, lf_x = 0, lf_oe = 0, lf_e = 0, lf_min_pairs = 256;
-    size_t lanefull_off = 0, lanefull_codes_off = 0, lanefull_codes_bytes = 0, lanefull_list_off = 0;
-    int lanefull_split = 1;   // > 1: every launch has slots and code lists of its own
-    if (use_lanefull) {
-      (void)wfa::seg_shape(b->dcfg, &lf_x, &lf_oe, &lf_e);
-      lanefull_off = (need + 255) & ~(size_t)255;
-      // per launch: run records + end state per pair, and the waves' record lists of comparison bits (512 bytes per wave-step)
-      const int64_t lf_budget = std::max<int64_t>((int64_t)free_budget(al) - (int64_t)lanefull_off, (int64_t)1 << 20);
-      lanefull_cap = std::max<int64_t>(1, std::min<int64_t>(in_n, lf_budget / (lanefull_slot_bytes + 256)));
-      if (al->knobs.set[K_SEGFULL_PAIRS]) lanefull_cap = std::min<int64_t>(lanefull_cap, std::max<int64_t>(64, knob(al, K_SEGFULL_PAIRS, 2000000)));   // (tests: several launches over one region)
-      // When the whole batch fits (the usual case) it is cut into balanced launches with code lists of their own: walk + expand of a
-      // launch (latency- and memory-bound) run on the side stream under the lane kernel (issue-bound) of the next
-      if (lanefull_cap >= (int64_t)in_n) {
-        lanefull_split = std::max(1, std::min(8, knob(al, K_LANE_FULL_SPLIT, (int64_t)in_n >= 524288 ? 2 : 1)));
-        lanefull_cap = ((((int64_t)in_n + lanefull_split - 1) / lanefull_split) + 63) & ~63ll;
-      }
-      // pairs per wave: 256 for launches that fill the chip; a launch of up to 256 k pairs is cut into lane-fulls of 64 (a run is as long as
-      // a wave's life: 65 536 pairs with CIGAR 397 -> 289 us; 1 M pairs in two launches: 1.07 ms with 256, 1.15 with 64).  One value for the
-      // geometry and every launch of the stage: a shorter last launch must not have more waves than the record lists were sized for
-      lf_min_pairs = knob(al, K_LANE_MIN_PAIRS, lanefull_cap <= 262144 ? 64 : 256);
-      wfa::lane_full_geometry((uint32_t)lanefull_cap, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), lf_min_pairs, lf_oe, lf_e,
-                              &lanefull_grid, &lanefull_recs);
-      lanefull_codes_off = lanefull_off + (((size_t)(lanefull_cap * lanefull_split * lanefull_slot_bytes) + 255) & ~(size_t)255);
-      lanefull_codes_bytes = ((size_t)lanefull_grid * (size_t)lanefull_recs * 512 + 255) & ~(size_t)255;
-      lanefull_list_off = lanefull_codes_off + lanefull_codes_bytes * (size_t)lanefull_split;
-      need = std::max(need, lanefull_list_off + (size_t)in_n * sizeof(uint32_t));
-    }
-    int rc = ensure_ws(al, need);
-    if (rc != WFA_HIP_OK) return rc;
-
-    DualStream lane_expands{al, stream, 2};   // the expand of the lane-full stage, left running under the stages behind it
-    if (use_lanefull) {
-      uint32_t* out_list = b->d_fb_list2[out_sel];
-      uint32_t* out_count = next_count();
-      int X, OE, E;
-      const int shape = wfa::seg_shape(b->dcfg, &X, &OE, &E);
-      wfa::FastArgs fa;
-      memset(&fa, 0, sizeof(fa));
-      fa.lin = b->dcfg.lin;
-      fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = in_list; fa.nwork_dev = nullptr;
-      fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
-      fa.g = wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1);
-      const int64_t lf_slots = lanefull_cap * lanefull_split;   // slots in the region (split: slot = work item; otherwise one launch's worth, reused)
-      int32_t* const lf_runs = al->ws + lanefull_off / 4;
-      int4* const lf_ends = reinterpret_cast<int4*>(reinterpret_cast<char*>(al->ws) + lanefull_off + (size_t)lf_slots * WFA_LANE_RUN_SLOT * 4);
-      fa.hist = lf_runs; fa.hist_stride = WFA_LANE_RUN_SLOT; fa.end_state = lf_ends;
-      fa.codes = reinterpret_cast<uint2*>(reinterpret_cast<char*>(al->ws) + lanefull_codes_off); fa.codes_cap = lanefull_recs;
-      wfa::BandArgs ba;
-      memset(&ba, 0, sizeof(ba));
-      ba.meta = b->d_meta; ba.worklist = in_list; ba.words = b->d_words;
-      ba.cigar_ops = b->d_ops; ba.cigar_off = b->d_cigar_off; ba.cigar_begin = b->d_cigar_begin; ba.cigar_len = b->d_cigar_len;
-      ba.hist = fa.hist; ba.hist_stride = fa.hist_stride; ba.end_state = fa.end_state;
-      // (the walk hands a pair with more runs than its slot holds to a list of its own, taken by the general kernel after the join:
-      // walk and expand both run beside the later stages)
-      uint32_t* const walk_list = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(al->ws) + lanefull_list_off);
-      ba.lane_codes = fa.codes; ba.status = b->d_status; ba.fb_list = walk_list; ba.fb_count = b->d_counters + 8;
-      ba.g = fa.g; ba.x = b->dcfg.x; ba.oe = b->dcfg.o1 + b->dcfg.e1; ba.e = b->dcfg.e1;
-      // one launch (the usual case): the op bytes are written on the side stream while the main stream goes on with what was handed on
-      { const int drc = lane_expands.begin(lf_slots >= (int64_t)in_n); if (drc != WFA_HIP_OK) return drc; }
-      int64_t launch = 0;
-      for (int64_t w0 = 0; w0 < (int64_t)in_n; w0 += lanefull_cap, ++launch) {
-        const uint32_t cnt = (uint32_t)std::min<int64_t>(lanefull_cap, (int64_t)in_n - w0);
-        fa.work_begin = (uint32_t)w0; fa.nwork = cnt;
-        if (lf_slots >= (int64_t)in_n) {   // slots and code lists of this launch
-          fa.hist = lf_runs + w0 * WFA_LANE_RUN_SLOT; fa.end_state = lf_ends + w0;
-          fa.codes = reinterpret_cast<uint2*>(reinterpret_cast<char*>(al->ws) + lanefull_codes_off + (size_t)launch * lanefull_codes_bytes);
-          ba.hist = fa.hist; ba.end_state = fa.end_state; ba.lane_codes = fa.codes;
-        }
-        // (a shorter last launch has fewer waves and needs fewer records than the lists were sized for)
-        if (wfa::launch_lane_args(shape, OE, E, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, fa, true, 0, lf_min_pairs, false, X) != 0) {
-          al->err = "lane kernel launch failed"; return WFA_HIP_EDEVICE;
-        }
-        ba.work_begin = (uint32_t)w0; ba.nwork = cnt;
-        hipStream_t es_ = stream;
-        { const int drc = lane_expands.walk_stream(launch, &es_); if (drc != WFA_HIP_OK) return drc; }
-        if (wfa::launch_lane_expand(ba, es_, es_) != 0) { al->err = "walk / expand launch failed"; return WFA_HIP_EDEVICE; }
-        { const int drc = lane_expands.after_walk(launch); if (drc != WFA_HIP_OK) return drc; }
-      }
-      if (first_stage) b->last_kernel_pairs = in_n;
-      in_list = out_list; in_count = out_count; out_sel ^= 1; first_stage = false;
-    }
-    for (int sf = 0; sf < n_segfull; ++sf) {
-      uint32_t* out_list = b->d_fb_list2[out_sel];
-      uint32_t* out_count = next_count();
-      wfa::FastArgs fa;
-      memset(&fa, 0, sizeof(fa));
-      fa.lin = b->dcfg.lin;
-      fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = in_list; fa.nwork_dev = in_count;
-      fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
-      fa.hist = al->ws; fa.hist_stride = segfull_slot_ints[sf];
-      fa.end_state = reinterpret_cast<int4*>(reinterpret_cast<char*>(al->ws) + (size_t)segfull_cap[sf] * segfull_slot_ints[sf] * 4);
-      wfa::BandArgs ba;
-      memset(&ba, 0, sizeof(ba));
-      ba.meta = b->d_meta; ba.worklist = in_list; ba.words = b->d_words;
-      ba.cigar_ops = b->d_ops; ba.cigar_off = b->d_cigar_off; ba.cigar_begin = b->d_cigar_begin; ba.cigar_len = b->d_cigar_len;
-      ba.g = wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1);
-      ba.x = b->dcfg.x; ba.oe = b->dcfg.o1 + b->dcfg.e1; ba.e = b->dcfg.e1;
-      ba.hist = al->ws; ba.hist_stride = segfull_slot_ints[sf]; ba.end_state = fa.end_state;
-      ba.split = 1; ba.h16 = 1; ba.seg_w = segfull_w[sf];
-      { long long ci, ei, si; wfa::seg_full_slot(b->dcfg, segfull_w[sf], b->max_len, &ci, &ei, &si); ba.pb = 1; ba.pb_code_ints = ci; ba.pb_event_ints = ei; }
-      // (first stage: the host knows the count and walks it in launches of `cap` pairs; later stages: one launch over
-      // the device-side list, slots for `cap` of its pairs)
-      const int64_t total = (in_count == nullptr) ? (int64_t)in_n : segfull_cap[sf];
-      const size_t half_bytes = ((size_t)segfull_cap[sf] * (size_t)(segfull_slot_ints[sf] * 4 + (int64_t)sizeof(int4)) + 255) & ~(size_t)255;
-      DualStream dual{al, stream};
-      { const int drc = dual.begin(sf == 0 && in_count == nullptr && total > segfull_cap[sf] && al->ws_bytes >= 2 * half_bytes); if (drc != WFA_HIP_OK) return drc; }
-      int64_t launch = 0;
-      for (int64_t w0 = 0; w0 < total; w0 += segfull_cap[sf], ++launch) {
-        const uint32_t cnt = (uint32_t)std::min<int64_t>(segfull_cap[sf], total - w0);
-        char* base = reinterpret_cast<char*>(al->ws) + ((dual.on && (launch & 1)) ? half_bytes : 0);
-        fa.hist = reinterpret_cast<int32_t*>(base);
-        fa.end_state = reinterpret_cast<int4*>(base + (size_t)segfull_cap[sf] * segfull_slot_ints[sf] * 4);
-        ba.hist = fa.hist; ba.end_state = fa.end_state;
-        fa.work_begin = (uint32_t)w0; fa.nwork = cnt;
-        { const int drc = dual.before_align(launch); if (drc != WFA_HIP_OK) return drc; }
-        if (in_count != nullptr) HIP_TRY(al, hipMemsetAsync(fa.end_state, 0, (size_t)cnt * sizeof(int4), stream));
-        if (wfa::launch_seg_full(b->dcfg, al->cu_count, knob(al, K_FAST_WAVES_PER_CU, 256), stream, fa, segfull_w[sf]) != 0) { al->err = "segmented kernel launch failed"; return WFA_HIP_EDEVICE; }
-        ba.work_begin = (uint32_t)w0; ba.nwork = cnt;
-        hipStream_t ws_ = stream;
-        { const int drc = dual.walk_stream(launch, &ws_); if (drc != WFA_HIP_OK) return drc; }
-        if (wfa::launch_band_bt(ba, 1, ws_) != 0) { al->err = "backtrace launch failed"; return WFA_HIP_EDEVICE; }
-        { const int drc = dual.after_walk(launch); if (drc != WFA_HIP_OK) return drc; }
-      }
-      { const int drc = dual.end(); if (drc != WFA_HIP_OK) return drc; }
-      if (first_stage) b->last_kernel_pairs = in_n;
-      in_list = out_list; in_count = out_count; out_sel ^= 1; first_stage = false;
-    }
-    if (use_fast) {
-      // register-kernel stages, each taking what the one before handed on (WFA_HIP_FAST_STAGES, one digit per
-      // stage): 1 = the lane-per-pair kernel (64 pairs per wave, band of 16 diagonals, wfa_lane.hpp), 0 = its 8-diagonal form (built-in
-      // penalty shapes only); 7/6/8/9 = segments of 8/16/32/64 lanes with the two-round (lazy) extension, 3/2/4/5 = the same widths
-      // extending every cell at once
-      const char* stages_env = al->knobs.fast_stages.empty() ? nullptr : al->knobs.fast_stages.c_str();
-      const char* stages = stages_env ? stages_env : "189";
-      if (!stages_env && b->stage_pick != 0 && in_count == nullptr) {   // (the pilots of batch_build chose the first width)
-        stages = (b->stage_pick == 16) ? (b->narrow_pick == 1 ? "0189" : "189") : (b->stage_pick == 32) ? "89" : "9";  // (128: 64 lanes still take the pairs that fit)
-      }
-      int variants[6] = {-1, -1, -1, -1, -1, -1};
-      int nv = 0;
-      for (const char* c = stages; *c && nv < 6; ++c) {
-        const int v = *c - '0';
-        if (v < 0 || v > 9) continue;
-        if (v <= 1) {   // (the lane kernel of a run-time shape: only while its rings fit the register file, and never the 8-diagonal form)
-          int X_, OE_, E_;
-          if (wfa::seg_shape(b->dcfg, &X_, &OE_, &E_) == WFA_SHAPE_RTC && (v == 0 || !wfa::rtc_lane_shape_ok(X_, OE_, E_))) continue;
-        }
-        variants[nv++] = v;
-      }
-      if (nv == 0) variants[nv++] = 6;
-      int lane_passes = 0;   // lane stages launched so far: the first two take slices of their list at run time, each from a counter of its own
-      for (int pass = 0; pass < nv; ++pass) {
-        uint32_t* out_list = b->d_fb_list2[out_sel];
-        uint32_t* out_count = next_count();
-        hipEvent_t se0 = nullptr, se1 = nullptr;
-        const bool stage_timing = knob(al, K_STAGE_TIMING, 0) != 0;
-        if (stage_timing) { hipEventCreate(&se0); hipEventCreate(&se1); hipEventRecord(se0, stream); }
-        int lrc;
-        if (variants[pass] <= 1) {
-          int X, OE, E;
-          const int shape = wfa::seg_shape(b->dcfg, &X, &OE, &E);
-          const bool narrow = variants[pass] == 0;
-          const int lane_k = lane_passes++;
-          // (slices of the list taken at run time: as many waves as the chip holds at once — every wave goes on until the list is used up.
-          // A stage behind another reads the length of its list from the device (a.nwork_dev) and takes slices the same way: a grid sized
-          // for the chip, not for a count the host does not know)
-          uint32_t lane_dyn = (in_n >= 65536u && lane_k < 2) ? (uint32_t)std::max(0, knob(al, K_LANE_DYN, 192)) : 0u;
-          // (waves per CU: the 16-diagonal form holds 4 per SIMD, the 8-diagonal one 6)
-          const int dyn_waves = narrow ? knob(al, K_LANE_NARROW_WAVES, 24) : knob(al, K_LANE_DYN_WAVES, 16);
-          if (lane_dyn && in_count != nullptr) {
-            // behind another stage: slices sized for the pairs it is expected to receive (the first stage's pilot, else 64), so that
-            // every wave gets at least two — a wave with one slice of 192 runs as long as its slowest lane's three pairs (2 M pairs at
-            // 2 %, 350 k handed on: 1.02 ms for the cascade with slices of 192, 0.89 with 64; 10 M: 192 is right)
-            const int64_t expect = (b->narrow_permille >= 0 && variants[0] == 0) ? (int64_t)in_n * b->narrow_permille / 1000 : 0;
-            const int64_t per_wave = expect / std::max<int64_t>(1, (int64_t)al->cu_count * dyn_waves * 2);
-            lane_dyn = (uint32_t)std::max<int64_t>(64, std::min<int64_t>(lane_dyn, per_wave));
-          }
-          lrc = wfa::launch_lane(shape, wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1), al->cu_count,
-                                 lane_dyn ? dyn_waves : knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, b->d_words, b->d_meta,
-                                 in_list, in_count, in_n, b->d_score, b->d_status, out_list, out_count,
-                                 (knob(al, K_LANE_DEBUG, 0) && al->ws) ? al->ws : nullptr, knob(al, K_LANE_LDS_PAD_KB, 0), X, OE, E, knob(al, K_LANE_MIN_PAIRS, 0),
-                                 // (slices of the list taken at run time, 192 pairs at a time, from counters zeroed with the run's others: [12] for
-                                 // the first lane stage, [14] for the one behind it; WFA_HIP_LANE_DYN=0: fixed slices)
-                                 b->d_counters + (lane_k == 0 ? 12 : 14), lane_dyn, narrow ? 4 : 8);
-          if (knob(al, K_LANE_DEBUG, 0) && al->ws) {  // development aid (build with -DWFA_LANE_DEBUG_COUNTERS=1)
-            unsigned long long c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            hipStreamSynchronize(stream); hipMemcpy(c, al->ws, sizeof(c), hipMemcpyDeviceToHost); hipMemset(al->ws, 0, sizeof(c));
-            fprintf(stderr, "[wfa_hip] lane kernel: %llu wave-steps, %llu refills, %llu parked runs, %llu parked rounds, %llu probe blocks, %llu second-run rounds, "
-                            "%llu hand-over blocks, %llu second runs, %llu entries, %llu entry rounds\n", c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]);
-          }
-        } else {
-          lrc = wfa::launch_seg(b->dcfg, al->cu_count, knob(al, K_FAST_WAVES_PER_CU, 256), stream, b->d_words, b->d_meta, in_list, in_count,
-                                in_n, b->d_score, b->d_status, out_list, out_count, variants[pass]);
-        }
-        if (lrc != 0) { al->err = "fast kernel launch failed"; return WFA_HIP_EDEVICE; }
-        if (stage_timing) {  // development aid: synchronises after every stage
-          hipEventRecord(se1, stream); hipEventSynchronize(se1);
-          float ms = 0.f; hipEventElapsedTime(&ms, se0, se1);
-          uint32_t handed = 0; hipMemcpy(&handed, out_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
-          fprintf(stderr, "[wfa_hip] stage %d (variant %d): %.3f ms, handed on %u pairs\n", pass, variants[pass], ms, handed);
-          hipEventDestroy(se0); hipEventDestroy(se1);
-        }
-        if (first_stage) b->last_kernel_pairs = in_n;
-        in_list = out_list; in_count = out_count; out_sel ^= 1; first_stage = false;
-      }
-    }
-    if (use_laneh) {
-      uint32_t* out_list = b->d_fb_list2[out_sel];
-      uint32_t* out_count = next_count();
-      wfa::FastArgs fa;
-      memset(&fa, 0, sizeof(fa));
-      fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = in_list; fa.nwork_dev = in_count; fa.nwork = in_n;
-      fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
-      fa.g = wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1);
-      fa.ef = (b->dcfg.endsfree && (b->dcfg.pbf | b->dcfg.pef | b->dcfg.tbf | b->dcfg.tef)) ? 1 : 0;
-      fa.pbf = b->dcfg.pbf; fa.pef = b->dcfg.pef; fa.tbf = b->dcfg.tbf; fa.tef = b->dcfg.tef;
-      fa.heur = b->dcfg.heuristic; fa.min_wf_len = b->dcfg.min_wf_len; fa.max_dist_thr = b->dcfg.max_dist_thr;
-      fa.steps_between = b->dcfg.steps_between; fa.max_steps = b->dcfg.max_steps;
-      const int shape = wfa::seg_shape(b->dcfg, &lh_x, &lh_oe, &lh_e);
-      // (slices of the list taken at run time, as the plain score-only form)
-      const uint32_t laneh_dyn = (in_count == nullptr && in_n >= 65536u) ? (uint32_t)std::max(0, knob(al, K_LANE_DYN, 192)) : 0u;
-      if (laneh_dyn) { fa.dyn_next = b->d_counters + 13; fa.dyn_chunk = laneh_dyn; }
-      if (wfa::launch_lane_args(shape, lh_oe, lh_e, al->cu_count, laneh_dyn ? knob(al, K_LANE_DYN_WAVES, 16) : knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, fa, false, 0, knob(al, K_LANE_MIN_PAIRS, 0), laneh_form, lh_x) != 0) {   // (pairs per wave by the size of the batch, as the plain form)
-        al->err = "lane kernel launch failed"; return WFA_HIP_EDEVICE;
-      }
-      if (first_stage) b->last_kernel_pairs = in_n;
-      in_list = out_list; in_count = out_count; out_sel ^= 1; first_stage = false;
-    }
-    if (use_segh) {
-      uint32_t* out_list = b->d_fb_list2[out_sel];
-      uint32_t* out_count = next_count();
-      wfa::FastArgs fa;
-      memset(&fa, 0, sizeof(fa));
-      fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = in_list; fa.nwork_dev = in_count; fa.nwork = in_n;
-      fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
-      fa.ef = (b->dcfg.endsfree && (b->dcfg.pbf | b->dcfg.pef | b->dcfg.tbf | b->dcfg.tef)) ? 1 : 0;
-      fa.pbf = b->dcfg.pbf; fa.pef = b->dcfg.pef; fa.tbf = b->dcfg.tbf; fa.tef = b->dcfg.tef;
-      fa.heur = b->dcfg.heuristic; fa.min_wf_len = b->dcfg.min_wf_len; fa.max_dist_thr = b->dcfg.max_dist_thr;
-      fa.steps_between = b->dcfg.steps_between; fa.max_steps = b->dcfg.max_steps; fa.xdrop = b->dcfg.xdrop; fa.scope = b->dcfg.scope;
-      if (wfa::launch_seg_heur(b->dcfg, al->cu_count, knob(al, K_FAST_WAVES_PER_CU, 256), stream, fa) != 0) {
-        al->err = "segmented kernel launch failed"; return WFA_HIP_EDEVICE;
-      }
-      if (first_stage) b->last_kernel_pairs = in_n;
-      in_list = out_list; in_count = out_count; out_sel ^= 1; first_stage = false;
-    }
-    DualStream pending_walks{al, stream};   // walks of a split stage left running under the band stages behind it
-    bool pipe_tail = false;                 // the stages behind the split stage ran beside it, the general kernel included
-    std::chrono::steady_clock::time_point band_prev;
-    if (knob(al, K_STAGE_TIMING, 0) != 0) { (void)hipStreamSynchronize(stream); band_prev = std::chrono::steady_clock::now(); }
-    for (int i = 0; i < n_stages; ++i) {
-      wfa::BandArgs ba;
-      memset(&ba, 0, sizeof(ba));
-      ba.words = b->d_words; ba.meta = b->d_meta; ba.worklist = in_list; ba.nwork_dev = in_count; ba.nwork = in_n;
-      ba.score = b->d_score; ba.status = b->d_status;
-      ba.cigar_ops = b->d_ops; ba.cigar_off = b->d_cigar_off; ba.cigar_begin = b->d_cigar_begin; ba.cigar_len = b->d_cigar_len;
-      uint32_t* out_list = b->d_fb_list2[out_sel];
-      uint32_t* out_count = next_count();
-      ba.fb_list = out_list; ba.fb_count = out_count;
-      ba.g = wfa::band_gcd(b->dcfg, b->ncomp == 5);
-      ba.x = b->dcfg.x; ba.oe = b->dcfg.o1 + b->dcfg.e1; ba.e = b->dcfg.e1;
-      if (b->ncomp == 5) { ba.oe2 = b->dcfg.o2 + b->dcfg.e2; ba.e2 = b->dcfg.e2; }
-      ba.min_wf_len = b->dcfg.min_wf_len; ba.max_dist_thr = b->dcfg.max_dist_thr; ba.steps_between = b->dcfg.steps_between;
-      ba.heur = b->dcfg.heuristic; ba.xdrop = b->dcfg.xdrop; ba.max_steps = b->dcfg.max_steps; ba.scope = b->dcfg.scope;
-      const int words = ((b->max_len + 15) >> 4) + 4;
-      // (round 5: up to 13 KB per wave — reads of up to 26 kb: the 128-diagonal slim kernel then runs four waves per SIMD instead of
-      // seven and is still twice as fast as wfa_band_kernel on HBM-resident sequences (15 kb: 3.1 -> 5.9 M aln/s score); beyond, the
-      // waves a CU can hold are too few)
-      bool seqlds = ((size_t)words * 8 <= (size_t)knob(al, K_BAND_LDS_MAX, 13312)) && knob(al, K_BAND_NO_LDS, 0) == 0;
-      ba.lds_words = seqlds ? words : 0;
-      // longer reads, wf-adaptive or no heuristic, gap-affine: wfa_slim_kernel on WINDOWS of the sequences (10 k bases of each in LDS,
-      // moved along as the alignment advances) — launches it does not take (slim_takes) read the sequences from HBM as before
-      const bool try_win = !seqlds && b->ncomp == 3 && b->dcfg.heuristic != WFA_HEUR_XDROP && knob(al, K_BAND_NO_LDS, 0) == 0 && knob(al, K_BAND_NO_WIN, 0) == 0;
-      ba.debug = knob(al, K_BAND_DEBUG, 0);
-      ba.slim = knob(al, K_BAND_SLIM, 1);   // (0: wfa_band_kernel also where wfa_slim_kernel would take the launch)
-      ba.pb_raw = 0;
-      if (knob(al, K_STAGE_TIMING, 0) != 0 && b->max_len > WFA_FAST_MAX_LEN) {   // (counting builds; [8..15] belong to the short-read stages otherwise)
-        ba.dbg = b->d_counters + 8;
-        (void)hipMemsetAsync(b->d_counters + 8, 0, 8 * sizeof(uint32_t), stream);
-      }
-      ba.h16 = (b->max_len < 32000) ? 1 : 0;
-      ba.ef = (b->dcfg.endsfree && (b->dcfg.pbf | b->dcfg.pef | b->dcfg.tbf | b->dcfg.tef)) ? 1 : 0;
-      ba.pbf = b->dcfg.pbf; ba.pef = b->dcfg.pef; ba.tbf = b->dcfg.tbf; ba.tef = b->dcfg.tef;
-      ba.hist = (i > 0 && later_off) ? al->ws + later_off / 4 : al->ws; ba.hist_stride = band_stride[i];
-      const bool split = full && in_count == nullptr && b->max_len > knob(al, K_BAND_SPLIT_MIN, 100) && knob(al, K_BAND_NO_SPLIT, 0) == 0;
-      if (split) {
-        // history slot per PAIR: as many pairs per launch as the workspace holds; the walks of a launch run
-        // afterwards in a thread-per-alignment kernel
-        const int64_t slot_ints = (pb_mode && pb_stride) ? pb_stride : band_stride[i];
-        if (pb_mode && pb_stride) { ba.pb = 1; ba.hist_stride = pb_stride; ba.pb_code_ints = pb_code_ints; ba.pb_event_ints = pb_event_ints; }
-        const int64_t slot_bytes = slot_ints * 4 + (int64_t)sizeof(int4);
-        // Slots: `cap` pairs fit the stage's region.  The launches are balanced (no small last launch) and their walks run on
-        // the side stream under the next alignment kernel: every launch has slots of its own when the whole batch fits
-        // (two launches at least, if each still fills the chip a few times over), otherwise the launches alternate between
-        // two halves of the region (only while a half still fills the chip: gap-affine-2p with explicit history at 10 kb
-        // runs 2 waves per SIMD and its launches are small already — halving them measured -35 %).
-        const size_t region = later_off ? later_off : al->ws_bytes;
-        const int64_t cap = std::min<int64_t>((int64_t)(region / (size_t)slot_bytes), in_n);
-        if (cap < 1) { al->err = "band history does not fit"; return WFA_HIP_EDEVICE; }
-        const int64_t chip = (int64_t)al->cu_count * 32;
-        const bool dual_ok = knob(al, K_NO_DUAL, 0) == 0;
-        const bool all_fit = cap >= (int64_t)in_n;
-        int64_t nl, per_launch;
-        bool halves = false;
-        if (all_fit) {
-          nl = (dual_ok && (int64_t)in_n >= 4 * chip) ? 2 : 1;
-          per_launch = ((int64_t)in_n + nl - 1) / nl;
-        } else {
-          halves = dual_ok && cap / 2 >= chip;
-          const int64_t lmax = halves ? cap / 2 : cap;
-          nl = ((int64_t)in_n + lmax - 1) / lmax;
-          per_launch = std::min<int64_t>(lmax, (((int64_t)in_n + nl - 1) / nl + 63) & ~63ll);
-        }
-        // the pipelined tail (see want_pipe_tail): this stage's launches and, beside each, the later stages on its leftovers
-        pipe_tail = want_pipe_tail && i == 0 && gen_off != 0 && nl >= 2 && nl <= 90 && !tile_stage.on && n_wide == 0 && (all_fit || halves);
-        uint32_t* const snap_a = b->d_counters + 64;    // [j] = this stage's hand-over count before launch j
-        uint32_t* const snap_b = b->d_counters + 160;   // the same for the stage behind it
-        uint32_t* tail_list = nullptr; uint32_t* tail_count = nullptr;
-        wfa::BandArgs tb = ba;   // the stage behind: everything but lists, history region and window width is this stage's
-        if (pipe_tail) {
-          if (!al->tail_join) {
-            for (int q = 0; q < 2; ++q) HIP_TRY(al, hipEventCreateWithFlags(&al->tail_fork[q], hipEventDisableTiming));
-            HIP_TRY(al, hipEventCreateWithFlags(&al->tail_join, hipEventDisableTiming));
-          }
-          tail_list = b->d_fb_list2[out_sel ^ 1]; tail_count = next_count();
-          tb.worklist = out_list; tb.fb_list = tail_list; tb.fb_count = tail_count;
-          tb.hist = al->ws + later_off / 4; tb.hist_stride = band_stride[1];
-          tb.pb = 0; tb.pb_code_ints = 0; tb.pb_event_ints = 0; tb.pb_raw = 0; tb.split = 0;   // (unsplit: explicit history, walked in-kernel)
-          // (the tail stream's first kernel must see the counters zeroed and the previous run's use of the regions over)
-          HIP_TRY(al, hipEventRecord(al->tail_fork[0], stream));
-          HIP_TRY(al, hipStreamWaitEvent(al->tail_stream, al->tail_fork[0], 0));
-        }
-        ba.split = 1;
-        char* const es_base = reinterpret_cast<char*>(al->ws) + (size_t)cap * slot_ints * 4;   // end states behind the slots
-        DualStream dual{al, stream};
-        // (one launch: its walks go to the side stream only if a band stage with a region of its own follows)
-        const bool side = (nl > 1 && (all_fit || halves)) || (nl == 1 && later_off != 0 && i + 1 < n_stages);
-        { const int drc = dual.begin(side); if (drc != WFA_HIP_OK) return drc; }
-        int64_t launch = 0;
-        for (int64_t w0 = 0; w0 < in_n; w0 += per_launch, ++launch) {
-          const uint32_t cnt = (uint32_t)std::min<int64_t>(per_launch, in_n - w0);
-          const int64_t slot0 = all_fit ? w0 : ((halves && (launch & 1)) ? per_launch : 0);
-          ba.hist = al->ws + slot0 * slot_ints;
-          ba.end_state = reinterpret_cast<int4*>(es_base) + slot0;
-          ba.work_begin = (uint32_t)w0; ba.nwork = cnt;
-          const long long grid = std::min<long long>((long long)al->cu_count * knob(al, K_BAND_WAVES_PER_CU, 128), cnt);
-          if (!all_fit) { const int drc = dual.before_align(launch); if (drc != WFA_HIP_OK) return drc; }
-          if (try_win && !ba.win) {   // (decided once per stage: the launches of a stage share everything slim_takes looks at)
-            wfa::BandArgs t = ba; t.win = 1; t.lds_words = 643;
-            if (wfa::slim_launches(t, band_nch[i], full, adapt, true)) { ba.win = 1; ba.lds_words = 643; seqlds = true; }
-          }
-          ba.pb_raw = wfa::slim_launches(ba, band_nch[i], full, adapt, seqlds) ? 1 : 0;   // (wfa_slim_kernel writes comparison bits; the walk below decodes them)
-          if (wfa::launch_band(ba, band_nch[i], full, adapt, seqlds, grid, stream) != 0) { al->err = "band kernel launch failed"; return WFA_HIP_EDEVICE; }
-          if (pipe_tail) {
-            // [snap_a[launch], snap_a[launch + 1]) = what this launch handed on (snap_a[0] = 0: the counters are zeroed per run)
-            hipLaunchKernelGGL(wfa_snapshot_kernel, dim3(1), dim3(1), 0, stream, out_count, snap_a + launch + 1);
-            HIP_TRY(al, hipEventRecord(al->tail_fork[launch & 1], stream));
-            HIP_TRY(al, hipStreamWaitEvent(al->tail_stream, al->tail_fork[launch & 1], 0));
-            tb.wbeg_dev = snap_a + launch; tb.nwork_dev = snap_a + launch + 1; tb.nwork = in_n;
-            if (wfa::launch_band(tb, band_nch[1], full, adapt, seqlds, band_grid[1], al->tail_stream) != 0) { al->err = "band kernel launch failed"; return WFA_HIP_EDEVICE; }
-            hipLaunchKernelGGL(wfa_snapshot_kernel, dim3(1), dim3(1), 0, al->tail_stream, tail_count, snap_b + launch + 1);
-            const int grc = launch_general_dyn(al, b, al->tail_stream, true, tail_list, snap_b + launch + 1, in_n, gen_stride, gen_grid, g.threads,
-                                               b->d_ovf_list[0], b->d_counters + 1, reinterpret_cast<int32_t*>(reinterpret_cast<char*>(al->ws) + gen_off), snap_b + launch);
-            if (grc != WFA_HIP_OK) return grc;
-          }
-          hipStream_t ws_ = stream;
-          { const int drc = dual.walk_stream(launch, &ws_); if (drc != WFA_HIP_OK) return drc; }
-          if (wfa::launch_band_bt(ba, band_nch[i], ws_) != 0) { al->err = "band backtrace launch failed"; return WFA_HIP_EDEVICE; }
-          { const int drc = dual.after_walk(launch); if (drc != WFA_HIP_OK) return drc; }
-        }
-        // the walks still running are joined before anything reuses their slots: at once, unless the next band stage has
-        // its own region
-        if (later_off && i + 1 < n_stages && dual.on) pending_walks = dual;
-        else { const int drc = dual.end(); if (drc != WFA_HIP_OK) return drc; }
-        if (pipe_tail) {
-          // everything behind this stage has been enqueued beside it: the main stream joins the tail stream, the stage behind is
-          // skipped below and so is the last launch of the general kernel; the lists move on as if the stages had run here
-          HIP_TRY(al, hipEventRecord(al->tail_join, al->tail_stream));
-          HIP_TRY(al, hipStreamWaitEvent(stream, al->tail_join, 0));
-          if (first_stage) b->last_kernel_pairs = in_n;
-          in_list = tail_list; in_count = tail_count; first_stage = false;   // (out_sel: two lists were used, the selector is where it was)
-          break;
-        }
-      } else {
-        if (try_win) {
-          wfa::BandArgs t = ba; t.win = 1; t.lds_words = 643;
-          if (wfa::slim_launches(t, band_nch[i], full, adapt, true)) { ba.win = 1; ba.lds_words = 643; seqlds = true; }
-        }
-        if (wfa::launch_band(ba, band_nch[i], full, adapt, seqlds, band_grid[i], stream) != 0) { al->err = "band kernel launch failed"; return WFA_HIP_EDEVICE; }
-      }
-      if (knob(al, K_STAGE_TIMING, 0) != 0) {  // development aid: synchronises (the time of the stage is the gap between these lines' events)
-        (void)hipStreamSynchronize(stream);
-        uint32_t handed = 0, took = in_n; (void)hipMemcpy(&handed, out_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (in_count) (void)hipMemcpy(&took, in_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
-        const auto t_now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[wfa_hip] band stage %d (%d diagonals): took %u pairs, handed on %u; %.3f ms\n", i, 64 * band_nch[i], took, handed,
-                std::chrono::duration<double, std::milli>(t_now - band_prev).count());
-        if (ba.dbg) {
-          uint32_t dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0}; (void)hipMemcpy(dbg, ba.dbg, sizeof(dbg), hipMemcpyDeviceToHost);
-          if (dbg[0] | dbg[1]) fprintf(stderr, "[wfa_hip]   slim counters: steps of 64 diagonals %u, of 128 %u, extension rounds %u, cut-offs that cut %u, window shifts %u, end trims %u, live diagonals / 64 %u\n",
-                                       dbg[0], dbg[1], dbg[2], dbg[3], dbg[4], dbg[5], dbg[6]);
-        }
-        band_prev = std::chrono::steady_clock::now();
-      }
-      if (first_stage) b->last_kernel_pairs = in_n;
-      in_list = out_list; in_count = out_count; out_sel ^= 1; first_stage = false;
-    }
-    { const int drc = pending_walks.end(); if (drc != WFA_HIP_OK) return drc; }   // (the stages below use the workspace from its start)
-    if (tile_stage.on) {
-      wfa::TileArgs& ta = tile_stage.a;
-      uint32_t* out_list = b->d_fb_list2[out_sel];
-      uint32_t* out_count = next_count();
-      ta.words = b->d_words; ta.meta = b->d_meta; ta.worklist = in_list; ta.nwork_dev = in_count; ta.nwork = in_n;
-      ta.score = b->d_score; ta.status = b->d_status; ta.fb_list = out_list; ta.fb_count = out_count;
-      ta.cigar_ops = b->d_ops; ta.cigar_off = b->d_cigar_off; ta.cigar_begin = b->d_cigar_begin; ta.cigar_len = b->d_cigar_len;
-      ta.rows = reinterpret_cast<short*>(al->ws);
-      ta.hist = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(al->ws) + tile_stage.hist_off);
-      ta.ef = b->dcfg.endsfree ? 1 : 0;
-      ta.pbf = b->dcfg.pbf; ta.pef = b->dcfg.pef; ta.tbf = b->dcfg.tbf; ta.tef = b->dcfg.tef;
-      ta.max_steps = b->dcfg.max_steps;
-      hipEvent_t se0 = nullptr, se1 = nullptr;
-      const bool stage_timing = knob(al, K_STAGE_TIMING, 0) != 0;
-      if (stage_timing) { (void)hipEventCreate(&se0); (void)hipEventCreate(&se1); (void)hipEventRecord(se0, stream); }
-      ta.dbg = stage_timing ? b->d_counters + 8 : nullptr;   // ([8] is the lane-full stage's list count: short reads only)
-      if (stage_timing) (void)hipMemsetAsync(b->d_counters + 8, 0, 8 * sizeof(uint32_t), stream);
-      if (wfa::launch_tile(full, wide_two, ta, tile_stage.grid, tile_stage.threads, tile_stage.smem, stream, tile_stage.w32) != 0) { al->err = "tile kernel launch failed"; return WFA_HIP_EDEVICE; }
-      if (stage_timing) {  // development aid: synchronises
-        (void)hipEventRecord(se1, stream); (void)hipEventSynchronize(se1);
-        float ms = 0.f; (void)hipEventElapsedTime(&ms, se0, se1);
-        uint32_t handed = 0; (void)hipMemcpy(&handed, out_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
-        uint32_t dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0}; (void)hipMemcpy(dbg, b->d_counters + 8, sizeof(dbg), hipMemcpyDeviceToHost);
-        if (dbg[3] | dbg[4]) fprintf(stderr, "[wfa_hip] tile profile (k-cycles of s_memtime, summed over waves): load %u, steps %u, write-back %u; steps that entered the end test %u, the long-match loop %u\n", dbg[3], dbg[4], dbg[5], dbg[6], dbg[7]);
-        fprintf(stderr, "[wfa_hip] tile stage (T %d, Wt %d, %d x %d threads, %zu B LDS): %.3f ms, handed on %u pairs; %u super-steps, %u repeated with statistics, %u tiles\n",
-                ta.g.T, ta.g.Wt, tile_stage.grid, tile_stage.threads, tile_stage.smem, ms, handed, dbg[0], dbg[1], dbg[2]);
-        (void)hipEventDestroy(se0); (void)hipEventDestroy(se1);
-      }
-      if (first_stage) b->last_kernel_pairs = in_n;
-      in_list = out_list; in_count = out_count; out_sel ^= 1; first_stage = false;
-    }
-    for (int ws_i = 0; ws_i < n_wide; ++ws_i) {
-      WideStage& st = wide_stage[ws_i];
-      wfa::WideArgs& wa = st.a;
-      uint32_t* out_list = b->d_fb_list2[out_sel];
-      uint32_t* out_count = next_count();
-      wa.words = b->d_words; wa.meta = b->d_meta; wa.worklist = in_list; wa.nwork_dev = in_count; wa.nwork = in_n;
-      wa.score = b->d_score; wa.status = b->d_status; wa.fb_list = out_list; wa.fb_count = out_count;
-      wa.cigar_ops = b->d_ops; wa.cigar_off = b->d_cigar_off; wa.cigar_begin = b->d_cigar_begin; wa.cigar_len = b->d_cigar_len;
-      wa.rows = st.grows ? reinterpret_cast<short*>(al->ws) : nullptr;
-      wa.hist = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(al->ws) + st.hist_off);
-      wa.ef = b->dcfg.endsfree ? 1 : 0;
-      wa.pbf = b->dcfg.pbf; wa.pef = b->dcfg.pef; wa.tbf = b->dcfg.tbf; wa.tef = b->dcfg.tef;
-      wa.max_steps = b->dcfg.max_steps;
-      wa.heur = (b->dcfg.heuristic == WFA_HEUR_ADAPTIVE) ? 1 : 0; wa.min_wf_len = b->dcfg.min_wf_len; wa.max_dist_thr = b->dcfg.max_dist_thr;
-      wa.steps_between = b->dcfg.steps_between;
-      hipEvent_t se0 = nullptr, se1 = nullptr;
-      const bool stage_timing = knob(al, K_STAGE_TIMING, 0) != 0;
-      if (stage_timing) { (void)hipEventCreate(&se0); (void)hipEventCreate(&se1); (void)hipEventRecord(se0, stream); }
-      if (wfa::launch_wide(full, wide_two, st.grows, wa, st.grid, st.threads, st.smem, stream, st.w32) != 0) { al->err = "wide kernel launch failed"; return WFA_HIP_EDEVICE; }
-      if (stage_timing) {  // development aid: synchronises
-        (void)hipEventRecord(se1, stream); (void)hipEventSynchronize(se1);
-        float ms = 0.f; (void)hipEventElapsedTime(&ms, se0, se1);
-        uint32_t handed = 0; (void)hipMemcpy(&handed, out_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[wfa_hip] wide stage %d (%d x %d threads): %.3f ms, handed on %u pairs\n", ws_i, st.grid, st.threads, ms, handed);
-        (void)hipEventDestroy(se0); (void)hipEventDestroy(se1);
-      }
-      if (first_stage) b->last_kernel_pairs = in_n;
-      in_list = out_list; in_count = out_count; out_sel ^= 1; first_stage = false;
-    }
-    b->leftover_count = in_count;
-    // (lin: what the register stages finished carries raw scores, what the general kernel finishes below — under the original
-    // configuration — final ones: the translation comes here, before it; a pair still to be aligned carries a non-zero status)
-    if (lin && b->dcfg.score_mode != 0)
+    // scores of a configuration that was mapped onto another (match < 0, the one-component distances): translated in-stream, in every
+    // scope (round 6: full scope used to wait for wfa_hip_batch_sync — an extra launch and a second synchronisation; now only the pairs an
+    // arena overflow re-runs are translated there: a pair that is still to be re-run carries a non-zero status and is skipped here)
+    if (b->dcfg.score_mode != 0 && !b->dcfg.lin)
       hipLaunchKernelGGL(wfa_score_translate_kernel, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, stream, b->d_score, b->d_status, b->d_meta,
                          (long long)b->n, b->dcfg.score_mode, b->dcfg.sw_match);
-    if (!pipe_tail) {   // (the pipelined tail has run the general kernel on every launch's leftovers already)
-      rc = launch_general_dyn(al, b, stream, true, in_list, in_count, in_n, g.ws_stride, g.grid, g.threads,
-                              b->d_ovf_list[0], b->d_counters + 1);
-      if (rc != WFA_HIP_OK) return rc;
-    }
-    if (first_stage) b->last_kernel_pairs = in_n;
-    { const int drc = lane_expands.end(); if (drc != WFA_HIP_OK) return drc; }
-    if (use_lanefull) {   // what the walks of the lane-full stage handed on (nothing, as a rule)
-      rc = launch_general_dyn(al, b, stream, true, reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(al->ws) + lanefull_list_off), b->d_counters + 8,
-                              (uint32_t)b->n_packed, g.ws_stride, g.grid, g.threads, b->d_ovf_list[0], b->d_counters + 1);
-      if (rc != WFA_HIP_OK) return rc;
-    }
   }
-  HIP_TRY(al, hipEventRecord(ev1, stream));
-  // 3) 8-bit pairs (non-ACGT letters, wildcard matching)
-  if (b->n_bytes > 0) {
-    Geometry g = plan_general(al, b, b->n_bytes, b->arena_fixed + b->arena_ints);
-    int rc = ensure_ws(al, (size_t)g.grid * g.ws_stride * 4);
-    if (rc != WFA_HIP_OK) return rc;
-    rc = launch_general_dyn(al, b, stream, false, b->d_list_bytes, nullptr, b->n_bytes, g.ws_stride, g.grid, g.threads,
-                            b->d_ovf_list[0], b->d_counters + 1);
-    if (rc != WFA_HIP_OK) return rc;
-  }
-  // scores of a configuration that was mapped onto another (match < 0, the one-component distances): translated in-stream, in every
-  // scope (round 6: full scope used to wait for wfa_hip_batch_sync — an extra launch and a second synchronisation; now only the pairs an
-  // arena overflow re-runs are translated there: a pair that is still to be re-run carries a non-zero status and is skipped here)
-  if (b->dcfg.score_mode != 0 && !b->dcfg.lin)
-    hipLaunchKernelGGL(wfa_score_translate_kernel, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, stream, b->d_score, b->d_status, b->d_meta,
-                       (long long)b->n, b->dcfg.score_mode, b->dcfg.sw_match);
+  // the shared ending: this run's use of the workspace is over at this point of the stream
   HIP_TRY(al, hipEventRecord(al->ws_event, stream));
   al->ws_event_recorded = true; al->ws_last_stream = stream;
   side_guard.ok = true;
