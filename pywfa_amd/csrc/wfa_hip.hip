@@ -959,6 +959,28 @@ static int staged_pack_upload(wfa_hip_aligner* al, wfa_hip_batch* b, const std::
   return WFA_HIP_OK;
 }
 
+// ---- fields that every stage's arguments share (FastArgs / BandArgs / TileArgs / WideArgs / WfaKernelArgs) ----
+template <class Args> static void fill_cigar_out(Args& a, const wfa_hip_batch* b) {
+  a.cigar_ops = b->d_ops; a.cigar_off = b->d_cigar_off; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len;
+}
+// (need_free_len: the register and banded kernels take the ends-free path only when an end is free at all; the tile and wide kernels
+// whenever the span is ends-free)
+template <class Args> static void fill_ends_free(Args& a, const WfaDevConfig& d, bool need_free_len) {
+  a.ef = (d.endsfree && (!need_free_len || (d.pbf | d.pef | d.tbf | d.tef))) ? 1 : 0;
+  a.pbf = d.pbf; a.pef = d.pef; a.tbf = d.tbf; a.tef = d.tef;
+}
+template <class Args> static void fill_heuristic(Args& a, const WfaDevConfig& d) {
+  a.heur = d.heuristic; a.min_wf_len = d.min_wf_len; a.max_dist_thr = d.max_dist_thr;
+  a.steps_between = d.steps_between; a.max_steps = d.max_steps;
+}
+static int affine_gcd(const WfaDevConfig& d) { return wfa::gcd_int(wfa::gcd_int(d.x, d.o1 + d.e1), d.e1); }
+// (BandArgs: the penalties, and the gcd the kernels divide scores by; two: gap-affine-2p)
+static void fill_band_penalties(wfa::BandArgs& a, const WfaDevConfig& d, bool two) {
+  a.g = wfa::band_gcd(d, two);
+  a.x = d.x; a.oe = d.o1 + d.e1; a.e = d.e1;
+  if (two) { a.oe2 = d.o2 + d.e2; a.e2 = d.e2; }
+}
+
 static int pilot_first_width(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream);
 static int pilot_lane_heur(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream);
 static int pilot_band(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream);
@@ -1012,194 +1034,431 @@ static int batch_alloc_common(wfa_hip_aligner* al, wfa_hip_batch* b, uint64_t to
   return WFA_HIP_OK;
 }
 
-// in2bit: `seqs` holds 2-bit reads in the reference's packed form (wavefront_sequences.c:102-139: four bases per byte, base j
-// of a byte in bits 2j..2j+1, A 0 / C 1 / G 2 / T 3), a sequence of len bases = (len + 3) / 4 bytes at its BYTE offset
-static int batch_build(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, const uint8_t* seqs,
-                       const int64_t* p_off, const int32_t* p_len, const int64_t* t_off, const int32_t* t_len, bool in2bit = false) {
-  mailbox_release(al);   // (the resident one-pair kernel: batches take the device)
+// ---- building an explicit batch: adopt the configuration, scan the lengths, allocate, upload by form ---------------------------------
+
+// the configuration a batch is laid out and run under, taken from the aligner when the batch is built (batch_build, batch_build_list)
+static void batch_adopt_config(wfa_hip_aligner* al, wfa_hip_batch* b) {
   b->cfg = al->cfg; b->dcfg = al->dcfg; b->ncomp = al->ncomp; b->gcfg = al->gcfg; b->gncomp = al->gncomp;
   // Round 5: a wildcard letter outside ACGT cannot occur in a pair whose letters are all ACGT — such pairs take the 2-bit kernels as if
   // no wildcard were set (same result: nothing in them matches by wildcard), only the pairs holding other letters are aligned on their
   // bytes with the wildcard rule (150 bp, clean reads: 44 M -> the 2-bit rates).  A wildcard that IS one of ACGT keeps every pair on bytes.
   if (b->cfg.wildcard >= 0 && !wildcard_in_acgt(b->cfg.wildcard)) { b->wild = b->cfg.wildcard; b->dcfg.wildcard = -1; b->gcfg.wildcard = -1; }
-  const wfa_hip_config_t& c = b->cfg;
-  const bool timing = al->knobs.set[K_TIMING];
-  double t0 = now_ms();
-  b->al = al;
-  b->n = n;
-  if (c.scope == WFA_SCOPE_FULL) {  // needed later to lay out the op-string regions
-    b->h_plen.assign(p_len, p_len + n);
-    b->h_tlen.assign(t_len, t_len + n);
+}
+
+// the two work lists of a batch that has byte pairs (ascending; `lp` may be empty: every pair on its bytes).  async: copies on al->stream,
+// the caller keeps the vectors alive until it has waited for the stream; otherwise blocking copies
+static int upload_work_lists(wfa_hip_aligner* al, wfa_hip_batch* b, const std::vector<uint32_t>& lp, const std::vector<uint32_t>& lb, bool async) {
+  if (lb.empty()) return WFA_HIP_OK;
+  auto put = [&](uint32_t** dst, const std::vector<uint32_t>& l) -> int {
+    HIP_TRY(al, pool_alloc(al, (void**)dst, l.size() * sizeof(uint32_t)));
+    if (async) HIP_TRY(al, hipMemcpyAsync(*dst, l.data(), l.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
+    else HIP_TRY(al, hipMemcpy(*dst, l.data(), l.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return WFA_HIP_OK;
+  };
+  { const int rc = put(&b->d_list_bytes, lb); if (rc != WFA_HIP_OK) return rc; }
+  return lp.empty() ? WFA_HIP_OK : put(&b->d_list_packed, lp);
+}
+
+// parts 0 .. nparts - 1 of a pass over a batch on at most `team` host threads, the caller's among them (the parts are claimed from a counter)
+template <class Fn> static void run_parts(int nparts, int team, Fn&& fn) {
+  if (nparts == 1) { fn(0); return; }
+  std::atomic<int> nextp(0);
+  auto loop = [&]() { for (int t = nextp.fetch_add(1); t < nparts; t = nextp.fetch_add(1)) fn(t); };
+  std::vector<std::thread> th;
+  for (int t = 1; t < std::min(team, nparts); ++t) th.emplace_back(loop);
+  loop();
+  for (auto& x : th) x.join();
+}
+
+// why a part of a batch was refused (PART_OVER_LIGHT is no refusal: scan_lengths leaves the host-packed form on it)
+enum PartError { PART_OK = 0, PART_NEGATIVE = 1, PART_TOO_LONG = 2, PART_ENDS_FREE = 3, PART_OVER_LIGHT = 4 };
+static const char* part_error_message(int err) {
+  return err == PART_NEGATIVE ? "negative length or offset" : err == PART_TOO_LONG ? "sequence too long"
+       : err == PART_ENDS_FREE ? "Ends-free parameters must be not larger than the sequences" : "";
+}
+// wavefront_align.c:86-102: the reference exit(1)s here
+static inline bool free_ends_exceed(const wfa_hip_config_t& c, int pl, int tl) {
+  return c.span == WFA_SPAN_ENDSFREE && (c.pattern_begin_free > pl || c.pattern_end_free > pl || c.text_begin_free > tl || c.text_end_free > tl);
+}
+
+// the caller's arrays.  in2bit: `seqs` holds 2-bit reads in the reference's packed form (wavefront_sequences.c:102-139: four bases per
+// byte, base j of a byte in bits 2j..2j+1, A 0 / C 1 / G 2 / T 3), a sequence of len bases = (len + 3) / 4 bytes at its BYTE offset
+struct BatchInput {
+  int64_t n; const uint8_t* seqs; const int64_t* p_off; const int32_t* p_len; const int64_t* t_off; const int32_t* t_len; bool in2bit;
+  int64_t seq_bytes(int len) const { return in2bit ? (len + 3) >> 2 : len; }
+};
+
+// How the sequences and the metadata reach the device.  HostPacked(16): host threads pack to 2 bits into the pinned ring (staged_pack_upload;
+// 16: the metadata crosses as 4 B per pair); AsciiRing: the caller's bytes through the pinned ring; PlainCopies: hipMemcpyAsync from the
+// caller's arrays.  The two ASCII forms are followed by the device pack kernel (or, 2-bit input, the re-pack kernel).
+enum class UploadForm { HostPacked16, HostPacked, AsciiRing, PlainCopies };
+
+// What the passes over the lengths leave (scan_lengths): the sums, the upload form, and the parts the host threads worked in
+struct BuildScan {
+  UploadForm form = UploadForm::PlainCopies;
+  bool pipelined = false;           // through the pinned ring: fixed before the first pass (the parts below depend on it), whatever `form` becomes
+  int64_t n = 0;
+  size_t slot = 0;                  // bytes of a slot of the pinned ring
+  int nthr = 1, sub = 1;            // parts; pipelined: a piece of the metadata upload = `sub` parts, so that a large team shares pass 1 evenly
+  int team = 1;                     // host threads that share the parts
+  int64_t part_pairs = 0;           // pipelined: pairs per part (a multiple of 64: the slot size is whole megabytes)
+  uint64_t total_words = 0;
+  int64_t blob_end = 0, packed_bytes = 0, ops_bytes = 0;   // blob_end: the ASCII forms only
+  int max_len = 0, max_width = 0;
+  std::vector<uint64_t> wbase;      // first packed word of each part
+  std::vector<uint32_t> blk_words;  // host-packed: the words of every block of 64 pairs (the parts start on block boundaries)
+  bool host_packed() const { return form == UploadForm::HostPacked16 || form == UploadForm::HostPacked; }
+  int64_t part_lo(int t) const { return pipelined ? std::min<int64_t>(n, (int64_t)t * part_pairs) : n * t / nthr; }
+};
+
+struct ScanPart { uint64_t words = 0; int64_t packed = 0, ops = 0, blob_end = 0; int max_width = 0, max_len = 0, err = PART_OK; };
+
+// pass 1 over pairs [lo, hi): checks and sums (with_offsets: also the byte offsets and the end of the caller's blob)
+static ScanPart scan_part(const BatchInput& in, const wfa_hip_config_t& c, int64_t lo, int64_t hi, bool with_offsets) {
+  ScanPart pt;
+  for (int64_t i = lo; i < hi; ++i) {
+    const int pl = in.p_len[i], tl = in.t_len[i];
+    if (pl < 0 || tl < 0 || (with_offsets && (in.p_off[i] < 0 || in.t_off[i] < 0))) { pt.err = PART_NEGATIVE; return pt; }
+    if ((int64_t)pl + tl > (int64_t)INT_MAX / 2 - 8) { pt.err = PART_TOO_LONG; return pt; }
+    if (free_ends_exceed(c, pl, tl)) { pt.err = PART_ENDS_FREE; return pt; }
+    pt.words += (uint64_t)((pl + 15) >> 4) + (uint64_t)((tl + 15) >> 4);
+    pt.max_width = std::max(pt.max_width, pl + tl + 3);
+    pt.max_len = std::max(pt.max_len, std::max(pl, tl));
+    pt.packed += (int64_t)((pl + 3) >> 2) + ((tl + 3) >> 2);
+    pt.ops += (int64_t)pl + tl;
+    if (with_offsets) pt.blob_end = std::max(pt.blob_end, std::max(in.p_off[i] + in.seq_bytes(pl), in.t_off[i] + in.seq_bytes(tl)));
   }
-  // per-pair metadata on several host threads: pass 1 validates and sums each slice of the batch, pass 2 writes the word
-  // offsets from the slice prefix.  Large batches (pipelined upload): the slices are the pieces of the upload ring and pass 2
-  // writes each piece straight into its pinned slot — no host copy of the metadata exists
-  // (round 4: also few pairs of long reads — C5's 100 kb reads are 200 KB of ASCII per pair: a plain copy from pageable memory moved
-  // them at 3.6 GB/s, the pinned ring with host-side packing at the link's rate)
+  return pt;
+}
+
+// pass 1 of the host-packed form (the offsets are first read, and checked, by the pack workers): lengths only, no early exits — a loop
+// the compiler vectorises (10 M pairs: 3.3 -> ~0.5 ms on 32 threads); negative lengths / free ends larger than a sequence are found
+// from the OR / minima afterwards.  Also writes the words of every block of 64 pairs (lo is a block boundary).
+static ScanPart scan_part_light(const BatchInput& in, const wfa_hip_config_t& c, int64_t lo, int64_t hi, uint32_t* blk_words) {
+  ScanPart pt;
+  int32_t neg = 0, minp = INT_MAX, mint = INT_MAX, mxl = 0;
+  uint32_t mxw = 0;
+  uint64_t words = 0, packed = 0, ops = 0;
+  for (int64_t b0 = lo; b0 < hi; b0 += 64) {
+    const int64_t b1 = std::min<int64_t>(hi, b0 + 64);
+    uint32_t bw = 0, bp = 0, bo = 0;
+    for (int64_t i = b0; i < b1; ++i) {
+      const int32_t pl = in.p_len[i], tl = in.t_len[i];
+      neg |= pl | tl;
+      minp = std::min(minp, pl); mint = std::min(mint, tl);
+      mxl = std::max(mxl, std::max(pl, tl));
+      mxw = std::max(mxw, (uint32_t)pl + (uint32_t)tl);
+      bw += ((uint32_t)(pl + 15) >> 4) + ((uint32_t)(tl + 15) >> 4);
+      bp += ((uint32_t)(pl + 3) >> 2) + ((uint32_t)(tl + 3) >> 2);
+      bo += (uint32_t)pl + (uint32_t)tl;
+    }
+    // (64 pairs: the 32-bit sums cannot overflow before the length check below fails)
+    blk_words[(size_t)(b0 >> 6)] = bw;
+    words += bw; packed += bp; ops += bo;
+  }
+  if (neg < 0) { pt.err = PART_NEGATIVE; return pt; }
+  if (mxw > (uint32_t)(INT_MAX / 2 - 8)) { pt.err = PART_TOO_LONG; return pt; }
+  if (mxl > (1 << 24)) { pt.err = PART_OVER_LIGHT; return pt; }   // (sequences this long: the ASCII form and its 64-bit sums)
+  if (hi > lo && c.span == WFA_SPAN_ENDSFREE &&
+      (std::max(c.pattern_begin_free, c.pattern_end_free) > minp || std::max(c.text_begin_free, c.text_end_free) > mint)) { pt.err = PART_ENDS_FREE; return pt; }
+  pt.words = words; pt.packed = (int64_t)packed; pt.ops = (int64_t)ops;
+  pt.max_width = (int)mxw + 3; pt.max_len = mxl;
+  return pt;
+}
+
+// what a pass without the offsets left out, for a batch that leaves the host-packed form (a part refused already keeps its reason)
+static void scan_part_offsets(const BatchInput& in, int64_t lo, int64_t hi, ScanPart* pt) {
+  if (pt->err != PART_OK) return;
+  for (int64_t i = lo; i < hi; ++i) {
+    if (in.p_off[i] < 0 || in.t_off[i] < 0) { pt->err = PART_NEGATIVE; return; }
+    pt->blob_end = std::max(pt->blob_end, std::max(in.p_off[i] + in.seq_bytes(in.p_len[i]), in.t_off[i] + in.seq_bytes(in.t_len[i])));
+  }
+}
+
+// a block of 64 pairs is the unit the host-packed pieces are cut from: its words and full-size metadata must fit one slot
+static bool blocks_fit_slot(const std::vector<uint32_t>& blk_words, size_t slot) {
+  for (const uint32_t bw : blk_words) if ((size_t)bw * 4 + 16 + 64 * sizeof(WfaPairMeta) > slot) return false;
+  return true;
+}
+
+// Per-pair checks and sums on several host threads, and the choice of the upload form.  Large batches (>= 256 k pairs; round 4: also few
+// pairs of long reads — C5's 100 kb reads are 200 KB of ASCII per pair: a plain copy from pageable memory moved them at 3.6 GB/s, the
+// pinned ring with host-side packing at the link's rate) go through the pinned ring, in parts that are the pieces of the metadata upload;
+// without a wildcard (a wildcard aligns every pair on its bytes) the host packs them (round 6: 2-bit input too — its bytes are re-based
+// to whole words and re-coded by the same workers: wfa::host_repack2_seq).
+static int scan_lengths(wfa_hip_aligner* al, const wfa_hip_config_t& c, const BatchInput& in, BuildScan* s) {
+  const int64_t n = in.n;
   bool many_bases = false;
   if (n < 262144 && n >= 64) {
     int64_t bases = 0;
-    for (int64_t i = 0; i < n; ++i) bases += (int64_t)std::max(p_len[i], 0) + std::max(t_len[i], 0);
+    for (int64_t i = 0; i < n; ++i) bases += (int64_t)std::max(in.p_len[i], 0) + std::max(in.t_len[i], 0);
     many_bases = bases >= ((int64_t)32 << 20);
   }
   const bool pipelined = (n >= 262144 || many_bases) && knob(al, K_NO_PIPE, 0) == 0;
-  const int64_t piece_pairs = (int64_t)(staged_slot_bytes(al) / sizeof(WfaPairMeta));
-  // (pipelined: a piece of the metadata upload = `sub` parts of pass 1, so that a large team shares pass 1 evenly)
-  const int sub = pipelined ? 8 : 1;
-  const int64_t part_pairs = piece_pairs / sub;   // (a multiple of 64: the slot size is whole megabytes)
-  const int nthr = pipelined ? (int)((n + part_pairs - 1) / part_pairs)
-                             : (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, std::thread::hardware_concurrency()), n / 65536));
-  auto part_lo = [&](int t) -> int64_t { return pipelined ? std::min<int64_t>(n, (int64_t)t * part_pairs) : n * t / nthr; };
-  std::unique_ptr<WfaPairMeta[]> meta(pipelined ? nullptr : new WfaPairMeta[(size_t)std::max<int64_t>(n, 1)]);  // not zero-filled: first touched in parallel below
-  struct Part { uint64_t words = 0; int64_t packed = 0, ops = 0, blob_end = 0; int max_width = 0, max_len = 0, err = 0; };
-  std::vector<Part> parts((size_t)nthr);
-  // host-packed upload: large batches without a wildcard (a wildcard aligns every pair on its bytes).  Pass 1 then also
-  // sums the words of every block of 64 pairs (the parts start on block boundaries), the pieces of the upload are cut
-  // from those below
-  // (round 6: 2-bit input too — its bytes are re-based to whole words and re-coded by the same workers: wfa::host_repack2_seq)
-  bool host_pack = pipelined && c.wildcard < 0 && knob(al, K_HOST_PACK, 1) != 0;
-  const bool light = host_pack;   // (pass 1 reads the lengths only; see pass1_light)
-  std::vector<uint32_t> blk_words(host_pack ? (size_t)((n + 63) >> 6) : 0, 0u);
-  auto pass1 = [&](int t) {
-    Part& pt = parts[(size_t)t];
-    const int64_t lo = part_lo(t), hi = part_lo(t + 1);
-    for (int64_t i = lo; i < hi; ++i) {
-      const int pl = p_len[i], tl = t_len[i];
-      // (host-packed upload: the offsets are first read, and checked, by the pack workers; pass 1 reads the lengths only)
-      if (pl < 0 || tl < 0 || (!light && (p_off[i] < 0 || t_off[i] < 0))) { pt.err = 1; return; }
-      if ((int64_t)pl + tl > (int64_t)INT_MAX / 2 - 8) { pt.err = 2; return; }
-      // wavefront_align.c:86-102: the reference exit(1)s here
-      if (c.span == WFA_SPAN_ENDSFREE &&
-          (c.pattern_begin_free > pl || c.pattern_end_free > pl || c.text_begin_free > tl || c.text_end_free > tl)) { pt.err = 3; return; }
-      pt.words += (uint64_t)((pl + 15) >> 4) + (uint64_t)((tl + 15) >> 4);
-      if (host_pack) blk_words[(size_t)(i >> 6)] += (uint32_t)((pl + 15) >> 4) + (uint32_t)((tl + 15) >> 4);
-      pt.max_width = std::max(pt.max_width, pl + tl + 3);
-      pt.max_len = std::max(pt.max_len, std::max(pl, tl));
-      pt.packed += (int64_t)((pl + 3) >> 2) + ((tl + 3) >> 2);
-      pt.ops += (int64_t)pl + tl;
-      if (!light) pt.blob_end = in2bit ? std::max(pt.blob_end, std::max(p_off[i] + ((pl + 3) >> 2), t_off[i] + ((tl + 3) >> 2)))
-                                       : std::max(pt.blob_end, std::max(p_off[i] + pl, t_off[i] + tl));
-    }
+  s->form = !pipelined ? UploadForm::PlainCopies : (c.wildcard < 0 && knob(al, K_HOST_PACK, 1) != 0) ? UploadForm::HostPacked : UploadForm::AsciiRing;
+  s->pipelined = pipelined;
+  s->n = n;
+  s->slot = staged_slot_bytes(al);
+  const int hc = (int)std::thread::hardware_concurrency();
+  s->team = std::max(1, pipelined ? std::min(32, hc / 2) : std::min(16, hc));
+  s->sub = pipelined ? 8 : 1;
+  s->part_pairs = (int64_t)(s->slot / sizeof(WfaPairMeta)) / s->sub;
+  s->nthr = pipelined ? (int)((n + s->part_pairs - 1) / s->part_pairs)
+                      : (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, std::thread::hardware_concurrency()), n / 65536));
+  std::vector<ScanPart> parts((size_t)s->nthr);
+  auto full_pass = [&](bool with_offsets) {
+    run_parts(s->nthr, s->team, [&](int t) { parts[(size_t)t] = scan_part(in, c, s->part_lo(t), s->part_lo(t + 1), with_offsets); });
   };
-  // pass 1 of the host-packed form: lengths only, no early exits — a loop the compiler vectorises (10 M pairs: 3.3 -> ~0.5 ms
-  // on 32 threads); negative lengths / free ends larger than a sequence are found from the OR / minima afterwards
-  auto pass1_light = [&](int t) {
-    Part& pt = parts[(size_t)t];
-    const int64_t lo = part_lo(t), hi = part_lo(t + 1);
-    int32_t neg = 0, minp = INT_MAX, mint = INT_MAX, mxl = 0;
-    uint32_t mxw = 0;
-    uint64_t words = 0, packed = 0, ops = 0;
-    for (int64_t b0 = lo; b0 < hi; b0 += 64) {
-      const int64_t b1 = std::min<int64_t>(hi, b0 + 64);
-      uint32_t bw = 0, bp = 0, bo = 0;
-      for (int64_t i = b0; i < b1; ++i) {
-        const int32_t pl = p_len[i], tl = t_len[i];
-        neg |= pl | tl;
-        minp = std::min(minp, pl); mint = std::min(mint, tl);
-        mxl = std::max(mxl, std::max(pl, tl));
-        mxw = std::max(mxw, (uint32_t)pl + (uint32_t)tl);
-        bw += ((uint32_t)(pl + 15) >> 4) + ((uint32_t)(tl + 15) >> 4);
-        bp += ((uint32_t)(pl + 3) >> 2) + ((uint32_t)(tl + 3) >> 2);
-        bo += (uint32_t)pl + (uint32_t)tl;
-      }
-      // (64 pairs: the 32-bit sums cannot overflow before the length check below fails)
-      blk_words[(size_t)(b0 >> 6)] = bw;
-      words += bw; packed += bp; ops += bo;
+  if (s->host_packed()) {
+    s->blk_words.assign((size_t)((n + 63) >> 6), 0u);
+    run_parts(s->nthr, s->team, [&](int t) { parts[(size_t)t] = scan_part_light(in, c, s->part_lo(t), s->part_lo(t + 1), s->blk_words.data()); });
+    bool over_light = false;
+    for (const ScanPart& pt : parts) over_light |= (pt.err == PART_OVER_LIGHT);
+    // The one place a batch leaves the host-packed form: a sequence of more than 2^24 bases (the light pass's 32-bit sums: pass 1 again),
+    // or very long reads of which 64 pairs do not fit a slot.  Nothing has looked at the offsets so far: the offsets pass runs here, once,
+    // and its refusal is reported by the one reduction below, in part order with the others and before the 2^32-word bound.
+    if (over_light || !blocks_fit_slot(s->blk_words, s->slot)) {
+      s->form = UploadForm::AsciiRing;
+      if (over_light) full_pass(false);
+      run_parts(s->nthr, s->team, [&](int t) { scan_part_offsets(in, s->part_lo(t), s->part_lo(t + 1), &parts[(size_t)t]); });
     }
-    if (neg < 0) { pt.err = 1; return; }
-    if (mxw > (uint32_t)(INT_MAX / 2 - 8)) { pt.err = 2; return; }
-    if (mxl > (1 << 24)) { pt.err = 4; return; }   // (sequences this long: the plain form and its 64-bit sums)
-    if (hi > lo && c.span == WFA_SPAN_ENDSFREE &&
-        (std::max(c.pattern_begin_free, c.pattern_end_free) > minp || std::max(c.text_begin_free, c.text_end_free) > mint)) { pt.err = 3; return; }
-    pt.words = words; pt.packed = (int64_t)packed; pt.ops = (int64_t)ops;
-    pt.max_width = (int)mxw + 3; pt.max_len = mxl;
-  };
-  auto pass_offsets = [&](int t) {   // what a light pass 1 left out (the host-packed form turned out not to fit)
-    Part& pt = parts[(size_t)t];
-    for (int64_t i = part_lo(t), hi = part_lo(t + 1); i < hi; ++i) {
-      if (p_off[i] < 0 || t_off[i] < 0) { pt.err = 1; return; }
-      pt.blob_end = std::max(pt.blob_end, std::max(p_off[i] + (int64_t)p_len[i], t_off[i] + (int64_t)t_len[i]));
-    }
-  };
-  auto run_threads = [&](auto&& fn) {
-    if (nthr == 1) { fn(0); return; }
-    // (a bounded team: the parts are claimed from a counter)
-    const int team = std::min(nthr, std::max(1, std::min(pipelined ? 32 : 16, (int)std::thread::hardware_concurrency() / (pipelined ? 2 : 1))));
-    std::atomic<int> nextp(0);
-    auto loop = [&]() { for (int t = nextp.fetch_add(1); t < nthr; t = nextp.fetch_add(1)) fn(t); };
-    std::vector<std::thread> th;
-    for (int t = 1; t < team; ++t) th.emplace_back(loop);
-    loop();
-    for (auto& x : th) x.join();
-  };
-  if (light) {
-    run_threads(pass1_light);
-    bool too_long = false;
-    for (const Part& pt : parts) too_long |= (pt.err == 4);
-    if (too_long) {
-      host_pack = false;
-      for (Part& pt : parts) pt = Part();
-      run_threads(pass1);
-      run_threads(pass_offsets);
-    }
-  } else run_threads(pass1);
-  uint64_t woff = 0;
-  int64_t blob_end = 0;
-  std::vector<uint64_t> wbase((size_t)nthr);
-  for (int t = 0; t < nthr; ++t) {
-    const Part& pt = parts[(size_t)t];
-    if (pt.err == 1) { al->err = "negative length or offset"; return WFA_HIP_EINVAL; }
-    if (pt.err == 2) { al->err = "sequence too long"; return WFA_HIP_EINVAL; }
-    if (pt.err == 3) { al->err = "Ends-free parameters must be not larger than the sequences"; return WFA_HIP_EINVAL; }
-    wbase[(size_t)t] = woff; woff += pt.words;
-    b->max_width = std::max(b->max_width, pt.max_width); b->max_len = std::max(b->max_len, pt.max_len);
-    b->packed_bytes += pt.packed; b->ops_bytes += pt.ops; blob_end = std::max(blob_end, pt.blob_end);
+  } else {
+    full_pass(true);
   }
-  if (woff > 0xFFFFFFF0ull) { al->err = "batch too large: more than 2^32 packed words (split the batch)"; return WFA_HIP_EINVAL; }
-  std::vector<PackPiece> pack_pieces;
+  s->wbase.resize((size_t)s->nthr);
+  for (int t = 0; t < s->nthr; ++t) {
+    const ScanPart& pt = parts[(size_t)t];
+    if (pt.err != PART_OK) { al->err = part_error_message(pt.err); return WFA_HIP_EINVAL; }
+    s->wbase[(size_t)t] = s->total_words; s->total_words += pt.words;
+    s->max_width = std::max(s->max_width, pt.max_width); s->max_len = std::max(s->max_len, pt.max_len);
+    s->packed_bytes += pt.packed; s->ops_bytes += pt.ops; s->blob_end = std::max(s->blob_end, pt.blob_end);
+  }
+  if (s->total_words > 0xFFFFFFF0ull) { al->err = "batch too large: more than 2^32 packed words (split the batch)"; return WFA_HIP_EINVAL; }
   // the metadata of a host-packed upload as 4 B per pair (16-bit lengths; the word offsets are rebuilt on the device) when no sequence
   // is longer than 65 535 bases (WFA_HIP_LEN16=0: the 16 B records)
-  const bool len16 = host_pack && b->max_len < 65536 && knob(al, K_LEN16, 1) != 0;
-  const size_t meta_wire = len16 ? sizeof(uint32_t) : sizeof(WfaPairMeta);
-  if (host_pack) {
-    const size_t slot = staged_slot_bytes(al);
-    PackPiece cur{0, 0, 0, 0};
-    const int64_t nblk = (n + 63) >> 6;
-    for (int64_t bi = 0; bi < nblk && host_pack; ++bi) {
-      const int64_t blo = bi << 6, bhi = std::min<int64_t>(n, blo + 64);
-      const uint64_t bw = blk_words[(size_t)bi];
-      if ((size_t)bw * 4 + 16 + 64 * sizeof(WfaPairMeta) > slot) host_pack = false;   // (very long reads: the plain form)
-      if (cur.hi > cur.lo && (size_t)(cur.nwords + bw) * 4 + 16 + (size_t)(bhi - cur.lo) * meta_wire > slot) {
-        pack_pieces.push_back(cur);
-        cur = PackPiece{blo, blo, cur.wlo + cur.nwords, 0};
-      }
-      cur.hi = bhi; cur.nwords += bw;
+  if (s->form == UploadForm::HostPacked && s->max_len < 65536 && knob(al, K_LEN16, 1) != 0) s->form = UploadForm::HostPacked16;
+  return WFA_HIP_OK;
+}
+
+// the pieces of a host-packed upload: runs of whole 64-pair blocks whose words and metadata fit one slot (every block fits: scan_lengths)
+static std::vector<PackPiece> plan_pack_pieces(const BuildScan& s) {
+  const size_t meta_wire = s.form == UploadForm::HostPacked16 ? sizeof(uint32_t) : sizeof(WfaPairMeta);
+  std::vector<PackPiece> pieces;
+  PackPiece cur{0, 0, 0, 0};
+  const int64_t nblk = (s.n + 63) >> 6;
+  for (int64_t bi = 0; bi < nblk; ++bi) {
+    const int64_t blo = bi << 6, bhi = std::min<int64_t>(s.n, blo + 64);
+    const uint64_t bw = s.blk_words[(size_t)bi];
+    if (cur.hi > cur.lo && (size_t)(cur.nwords + bw) * 4 + 16 + (size_t)(bhi - cur.lo) * meta_wire > s.slot) {
+      pieces.push_back(cur);
+      cur = PackPiece{blo, blo, cur.wlo + cur.nwords, 0};
     }
-    if (cur.hi > cur.lo) pack_pieces.push_back(cur);
-    if (!host_pack) {
-      run_threads(pass_offsets);
-      for (int t = 0; t < nthr; ++t) {
-        if (parts[(size_t)t].err == 1) { al->err = "negative length or offset"; return WFA_HIP_EINVAL; }
-        blob_end = std::max(blob_end, parts[(size_t)t].blob_end);
-      }
+    cur.hi = bhi; cur.nwords += bw;
+  }
+  if (cur.hi > cur.lo) pieces.push_back(cur);
+  return pieces;
+}
+
+// pass 2: the metadata records of parts t .. t + nparts - 1 (out[0] = pair part_lo(t)), the word offsets from the part's prefix
+static void write_meta_parts(const BatchInput& in, const BuildScan& s, int t, WfaPairMeta* out, int nparts) {
+  uint64_t w = s.wbase[(size_t)t];
+  const int64_t lo = s.part_lo(t), hi = s.part_lo(std::min(t + nparts, s.nthr));
+  for (int64_t i = lo; i < hi; ++i) {
+    const int pl = in.p_len[i], tl = in.t_len[i];
+    WfaPairMeta& m = out[i - lo];
+    m.p_woff = (uint32_t)w; w += (uint64_t)((pl + 15) >> 4);
+    m.t_woff = (uint32_t)w; w += (uint64_t)((tl + 15) >> 4);
+    m.plen = pl; m.tlen = tl;
+  }
+}
+
+// the timing lines of a build (WFA_HIP_TIMING): each reports the time since the one before
+struct LapTimer {
+  bool on; double t0;
+  double lap() { const double t = now_ms(), d = t - t0; t0 = t; return d; }
+};
+
+// the few pairs of a host-packed batch with letters outside ACGT (`flagged`, ascending): their bytes in a compact blob, byte offsets and
+// flags scattered to their slots, and the two work lists
+static int upload_flagged_pairs(wfa_hip_aligner* al, wfa_hip_batch* b, const BatchInput& in, const std::vector<uint32_t>& flagged) {
+  const size_t nb = flagged.size();
+  std::vector<int64_t> fpo(nb), fto(nb);
+  size_t blob = 0;
+  for (size_t j = 0; j < nb; ++j) { fpo[j] = (int64_t)blob; blob += (size_t)in.p_len[flagged[j]]; fto[j] = (int64_t)blob; blob += (size_t)in.t_len[flagged[j]]; }
+  std::vector<uint8_t> hb(blob + 1);
+  for (size_t j = 0; j < nb; ++j) {
+    memcpy(hb.data() + fpo[j], in.seqs + in.p_off[flagged[j]], (size_t)in.p_len[flagged[j]]);
+    memcpy(hb.data() + fto[j], in.seqs + in.t_off[flagged[j]], (size_t)in.t_len[flagged[j]]);
+  }
+  // the list of the 2-bit pairs = all pairs but the flagged ones (ascending)
+  std::vector<uint32_t> lp;
+  lp.reserve((size_t)in.n - nb);
+  size_t fj = 0;
+  for (int64_t i = 0; i < in.n; ++i) { if (fj < nb && flagged[fj] == (uint32_t)i) { ++fj; continue; } lp.push_back((uint32_t)i); }
+  b->n_packed = (uint32_t)lp.size();
+  int64_t *d_fpo = nullptr, *d_fto = nullptr;
+  HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, blob + 64));
+  HIP_TRY(al, pool_alloc(al, (void**)&d_fpo, nb * sizeof(int64_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&d_fto, nb * sizeof(int64_t)));
+  HIP_TRY(al, hipMemcpyAsync(b->d_bytes, hb.data(), blob, hipMemcpyHostToDevice, al->stream));
+  HIP_TRY(al, hipMemcpyAsync(d_fpo, fpo.data(), nb * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
+  HIP_TRY(al, hipMemcpyAsync(d_fto, fto.data(), nb * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
+  { const int lrc = upload_work_lists(al, b, lp, flagged, true); if (lrc != WFA_HIP_OK) return lrc; }
+  hipLaunchKernelGGL(wfa::wfa_flag_scatter_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, al->stream,
+                     b->d_list_bytes, d_fpo, d_fto, (uint32_t)nb, b->d_pboff, b->d_tboff, b->d_flags);
+  HIP_TRY(al, hipGetLastError());
+  HIP_TRY(al, hipStreamSynchronize(al->stream));   // (host vectors above go out of scope)
+  pool_release(al, d_fpo); pool_release(al, d_fto);
+  return WFA_HIP_OK;
+}
+
+// host-packed form: host threads -> 2 bits per base in the pinned ring -> DMA (staged_pack_upload); HostPacked16: the 16 B metadata
+// records are rebuilt on the device from the 4 B ones; then the pairs the pack workers flagged
+static int upload_host_packed(wfa_hip_aligner* al, wfa_hip_batch* b, const BatchInput& in, const BuildScan& s,
+                              const std::vector<PackPiece>& pieces, LapTimer& lap) {
+  const bool use16 = s.form == UploadForm::HostPacked16;
+  std::vector<uint32_t> flagged;
+  if (use16) {
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_len16, (size_t)in.n * sizeof(uint32_t)));
+    HIP_TRY(al, pool_alloc(al, (void**)&b->d_pieces, pieces.size() * sizeof(wfa::WfaPieceDesc)));
+  }
+  const int urc = staged_pack_upload(al, b, pieces, in.seqs, in.p_off, in.p_len, in.t_off, in.t_len, al->stream, &flagged, in.in2bit, use16 ? b->d_len16 : nullptr);
+  if (urc != WFA_HIP_OK) return urc;
+  if (use16) {
+    b->h_pieces.resize(pieces.size());
+    for (size_t q = 0; q < pieces.size(); ++q) b->h_pieces[q] = wfa::WfaPieceDesc{(long long)pieces[q].lo, (long long)pieces[q].hi, (unsigned long long)pieces[q].wlo};
+    HIP_TRY(al, hipMemcpyAsync(b->d_pieces, b->h_pieces.data(), b->h_pieces.size() * sizeof(wfa::WfaPieceDesc), hipMemcpyHostToDevice, al->stream));
+    hipLaunchKernelGGL(wfa::wfa_meta_from_len16_kernel, dim3((unsigned)pieces.size()), dim3(256), 0, al->stream, b->d_pieces, b->d_len16, b->d_meta);
+    HIP_TRY(al, hipGetLastError());
+  }
+  if (lap.on) fprintf(stderr, "[wfa_hip] host pack + H2D enqueue %.3f ms (%.2f GB of ASCII, %.2f GB sent)\n", lap.lap(), b->ops_bytes / 1e9,
+                      (s.total_words * 4.0 + in.n * 16.0) / 1e9);
+  b->n_bytes = (uint32_t)flagged.size();
+  b->n_packed = (uint32_t)in.n;
+  return flagged.empty() ? WFA_HIP_OK : upload_flagged_pairs(al, b, in, flagged);
+}
+
+// ASCII forms: the caller's bytes, byte offsets and the metadata to the device, through the pinned ring (host threads -> pinned slots ->
+// DMA; the metadata pieces are computed into their slots, no host copy of them exists) or by plain copies (`meta`: written by pass 2)
+static int upload_ascii(wfa_hip_aligner* al, wfa_hip_batch* b, const BatchInput& in, const BuildScan& s, const WfaPairMeta* meta) {
+  const size_t n = (size_t)in.n;
+  if (s.form == UploadForm::AsciiRing) {
+    std::vector<UploadJob> jobs;
+    jobs.push_back({b->d_meta, nullptr, n * sizeof(WfaPairMeta),
+                    [&](uint8_t* out, size_t off, size_t) { write_meta_parts(in, s, (int)(off / s.slot) * s.sub, reinterpret_cast<WfaPairMeta*>(out), s.sub); }});
+    jobs.push_back({b->d_bytes, in.seqs, (size_t)s.blob_end, nullptr});
+    jobs.push_back({b->d_pboff, in.p_off, n * sizeof(int64_t), nullptr});
+    jobs.push_back({b->d_tboff, in.t_off, n * sizeof(int64_t), nullptr});
+    return staged_upload(al, jobs, al->stream);
+  }
+  HIP_TRY(al, hipMemcpyAsync(b->d_bytes, in.seqs, (size_t)s.blob_end, hipMemcpyHostToDevice, al->stream));
+  HIP_TRY(al, hipMemcpyAsync(b->d_pboff, in.p_off, n * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
+  HIP_TRY(al, hipMemcpyAsync(b->d_tboff, in.t_off, n * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
+  HIP_TRY(al, hipMemcpyAsync(b->d_meta, meta, n * sizeof(WfaPairMeta), hipMemcpyHostToDevice, al->stream));
+  return WFA_HIP_OK;
+}
+
+// 2-bit input behind an ASCII-form upload: re-based to whole words and re-coded by one small kernel; no letter can be outside ACGT
+static int repack_2bit_input(wfa_hip_aligner* al, wfa_hip_batch* b) {
+  const int64_t n = b->n;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)al->cu_count * 64));
+  hipLaunchKernelGGL(wfa::wfa_repack2_kernel, dim3(grid), dim3(256), 0, al->stream, b->d_bytes, b->d_pboff, b->d_tboff, b->d_meta, n, b->d_words);
+  HIP_TRY(al, hipGetLastError());
+  b->n_bytes = 0; b->n_packed = (uint32_t)n;
+  if (n <= 256) { b->uploads_pending = true; return WFA_HIP_OK; }
+  // (plain copies: the caller's arrays are still being read; either way nothing reads the 2-bit blob after the repack kernel —
+  // it used to stay in HBM for the batch's lifetime on the pipelined path)
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  pool_release(al, b->d_bytes); b->d_bytes = nullptr;
+  return WFA_HIP_OK;
+}
+
+// ASCII input behind an ASCII-form upload: the pack kernel (2 bits per base, a flag per pair with a letter outside ACGT), the flags
+// to the host, the split into the 2-bit and the 8-bit work lists (wildcard matching needs the bytes)
+static int pack_on_device(wfa_hip_aligner* al, wfa_hip_batch* b, const BatchInput& in, const BuildScan& s, LapTimer& lap) {
+  const int64_t n = in.n;
+  const wfa_hip_config_t& c = b->cfg;
+  const bool all_bytes = c.wildcard >= 0 && b->wild < 0;   // (a wildcard among ACGT: every pair on its bytes)
+  // lanes per pair: the words of the longest pair, rounded up to a power of two (at most a whole wave)
+  int log2slots = 1;
+  while (log2slots < 6 && (1 << log2slots) < 2 * ((b->max_len + 15) >> 4)) ++log2slots;
+  const int64_t group = 64 >> log2slots;
+  const int64_t want = ((n + group - 1) / group + 3) / 4;  // 4 waves per workgroup
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)al->cu_count * 64));
+  hipLaunchKernelGGL(wfa::wfa_pack_kernel, dim3(grid), dim3(256), 0, al->stream,
+                     b->d_bytes, b->d_pboff, b->d_tboff, b->d_meta, n, b->d_words, b->d_flags, log2slots, b->d_counters + 15);
+  HIP_TRY(al, hipGetLastError());
+  std::vector<uint8_t> flags;
+  if (n <= 256) {
+    flags.assign((size_t)n, 0);
+    // a handful of pairs: look for letters outside ACGT on the host, the round trip costs more than the scan
+    for (int64_t i = 0; i < n; ++i) {
+      uint8_t bad = 0;
+      const uint8_t* ps = in.seqs + in.p_off[i]; const uint8_t* ts = in.seqs + in.t_off[i];
+      for (int32_t j = 0; j < in.p_len[i]; ++j) { const uint8_t ch = ps[j]; bad |= !(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'); }
+      for (int32_t j = 0; j < in.t_len[i]; ++j) { const uint8_t ch = ts[j]; bad |= !(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'); }
+      flags[(size_t)i] = bad;
+    }
+    b->uploads_pending = true;  // the caller's arrays are still being read: see wfa_hip_batch_create
+  } else {
+    // one word first: the per-pair flags (n bytes) are fetched only if some pair holds a letter outside ACGT
+    uint32_t any_flag = 0;
+    HIP_TRY(al, hipMemcpyAsync(&any_flag, b->d_counters + 15, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    if (any_flag || all_bytes) {
+      flags.assign((size_t)n, 0);
+      HIP_TRY(al, hipMemcpy(flags.data(), b->d_flags, (size_t)n, hipMemcpyDeviceToHost));
     }
   }
-  auto pass2_part = [&](int t, WfaPairMeta* out /* element 0 = pair part_lo(t) */, int nparts = 1) {
-    uint64_t w = wbase[(size_t)t];
-    const int64_t lo = part_lo(t), hi = part_lo(std::min(t + nparts, nthr));
-    for (int64_t i = lo; i < hi; ++i) {
-      const int pl = p_len[i], tl = t_len[i];
-      WfaPairMeta& m = out[i - lo];
-      m.p_woff = (uint32_t)w; w += (uint64_t)((pl + 15) >> 4);
-      m.t_woff = (uint32_t)w; w += (uint64_t)((tl + 15) >> 4);
-      m.plen = pl; m.tlen = tl;
+  if (lap.on) fprintf(stderr, "[wfa_hip] H2D + pack + flags D2H %.3f ms (%.2f GB)\n", lap.lap(), s.blob_end / 1e9);
+  std::vector<uint32_t> lp, lb;
+  if (all_bytes) {
+    lb.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) lb[i] = (uint32_t)i;
+  } else {
+    int64_t nbad = 0;
+    for (size_t i = 0; i < flags.size(); ++i) nbad += flags[i];
+    if (nbad) {
+      lp.reserve((size_t)(n - nbad)); lb.reserve((size_t)nbad);
+      for (int64_t i = 0; i < n; ++i) (flags[i] ? lb : lp).push_back((uint32_t)i);
     }
-  };
-  if (!pipelined) run_threads([&](int t) { pass2_part(t, meta.get() + part_lo(t)); });
-  if (timing) { fprintf(stderr, "[wfa_hip] meta pass %.3f ms\n", now_ms() - t0); t0 = now_ms(); }
-  const bool full = (c.scope == WFA_SCOPE_FULL);
+  }
+  b->n_bytes = (uint32_t)lb.size();
+  b->n_packed = (uint32_t)(lb.empty() ? n : lp.size());
+  { const int lrc = upload_work_lists(al, b, lp, lb, false); if (lrc != WFA_HIP_OK) return lrc; }
+  // every pair is pure ACGT: the ASCII blob is no longer needed
+  if (lb.empty()) { pool_release(al, b->d_bytes); b->d_bytes = nullptr; }
+  if (lap.on) fprintf(stderr, "[wfa_hip] work lists + free %.3f ms\n", lap.lap());
+  return WFA_HIP_OK;
+}
+
+// An explicit batch from the caller's arrays (in2bit: see BatchInput).  Every form's uploads, memsets and kernels are enqueued on
+// al->stream; finish_batch_build is the one exit, so upload_event lies behind all of them.
+static int batch_build(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, const uint8_t* seqs,
+                       const int64_t* p_off, const int32_t* p_len, const int64_t* t_off, const int32_t* t_len, bool in2bit = false) {
+  mailbox_release(al);   // (the resident one-pair kernel: batches take the device)
+  batch_adopt_config(al, b);
+  const BatchInput in{n, seqs, p_off, p_len, t_off, t_len, in2bit};
+  const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
+  LapTimer lap{al->knobs.set[K_TIMING], now_ms()};
+  b->al = al;
+  b->n = n;
+  if (full) {  // needed later to lay out the op-string regions
+    b->h_plen.assign(p_len, p_len + n);
+    b->h_tlen.assign(t_len, t_len + n);
+  }
+  BuildScan scan;
+  { const int src = scan_lengths(al, b->cfg, in, &scan); if (src != WFA_HIP_OK) return src; }
+  b->max_width = scan.max_width; b->max_len = scan.max_len; b->packed_bytes = scan.packed_bytes; b->ops_bytes = scan.ops_bytes;
+  std::vector<PackPiece> pieces;
+  if (scan.host_packed()) pieces = plan_pack_pieces(scan);
+  // plain copies: the metadata in a host array (not zero-filled: first touched in parallel), kept by the batch — its copy may still be
+  // in flight when this returns
+  std::unique_ptr<WfaPairMeta[]> meta(scan.pipelined ? nullptr : new WfaPairMeta[(size_t)std::max<int64_t>(n, 1)]);
+  if (!scan.pipelined) run_parts(scan.nthr, scan.team, [&](int t) { write_meta_parts(in, scan, t, meta.get() + scan.part_lo(t), 1); });
+  if (lap.on) fprintf(stderr, "[wfa_hip] meta pass %.3f ms\n", lap.lap());
   const size_t nn = (size_t)std::max<int64_t>(n, 1);
-  if (!host_pack) HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)blob_end + 64));
+  if (!scan.host_packed()) HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)scan.blob_end + 64));
   HIP_TRY(al, pool_alloc(al, (void**)&b->d_pboff, nn * sizeof(int64_t)));
   HIP_TRY(al, pool_alloc(al, (void**)&b->d_tboff, nn * sizeof(int64_t)));
   if (full) {
@@ -1207,157 +1466,17 @@ static int batch_build(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, const u
     coff.assign((size_t)n + 1, 0);
     for (int64_t i = 0; i < n; ++i) coff[i + 1] = coff[i] + p_len[i] + t_len[i];
   }
-  { const int arc = batch_alloc_common(al, b, woff + 4, 4); if (arc != WFA_HIP_OK) return arc; }
+  { const int arc = batch_alloc_common(al, b, scan.total_words + 4, 4); if (arc != WFA_HIP_OK) return arc; }
   if (full) { if (n > 256) HIP_TRY(al, hipStreamSynchronize(al->stream)); else b->uploads_pending = true; }
-  if (timing) { fprintf(stderr, "[wfa_hip] mallocs %.3f ms\n", now_ms() - t0); t0 = now_ms(); }
-  if (n > 0 && host_pack) {
-    std::vector<uint32_t> flagged;
-    const bool use16 = len16 && host_pack;
-    if (use16) {
-      HIP_TRY(al, pool_alloc(al, (void**)&b->d_len16, nn * sizeof(uint32_t)));
-      HIP_TRY(al, pool_alloc(al, (void**)&b->d_pieces, pack_pieces.size() * sizeof(wfa::WfaPieceDesc)));
+  if (lap.on) fprintf(stderr, "[wfa_hip] mallocs %.3f ms\n", lap.lap());
+  if (n > 0) {
+    int urc;
+    if (scan.host_packed()) urc = upload_host_packed(al, b, in, scan, pieces, lap);
+    else {
+      urc = upload_ascii(al, b, in, scan, meta.get());
+      if (urc == WFA_HIP_OK) urc = in2bit ? repack_2bit_input(al, b) : pack_on_device(al, b, in, scan, lap);
     }
-    const int urc = staged_pack_upload(al, b, pack_pieces, seqs, p_off, p_len, t_off, t_len, al->stream, &flagged, in2bit, use16 ? b->d_len16 : nullptr);
     if (urc != WFA_HIP_OK) return urc;
-    if (use16) {
-      b->h_pieces.resize(pack_pieces.size());
-      for (size_t q = 0; q < pack_pieces.size(); ++q) b->h_pieces[q] = wfa::WfaPieceDesc{(long long)pack_pieces[q].lo, (long long)pack_pieces[q].hi, (unsigned long long)pack_pieces[q].wlo};
-      HIP_TRY(al, hipMemcpyAsync(b->d_pieces, b->h_pieces.data(), b->h_pieces.size() * sizeof(wfa::WfaPieceDesc), hipMemcpyHostToDevice, al->stream));
-      hipLaunchKernelGGL(wfa::wfa_meta_from_len16_kernel, dim3((unsigned)pack_pieces.size()), dim3(256), 0, al->stream, b->d_pieces, b->d_len16, b->d_meta);
-      HIP_TRY(al, hipGetLastError());
-    }
-    if (timing) { fprintf(stderr, "[wfa_hip] host pack + H2D enqueue %.3f ms (%.2f GB of ASCII, %.2f GB sent)\n", now_ms() - t0, b->ops_bytes / 1e9,
-                          (woff * 4.0 + n * 16.0) / 1e9); t0 = now_ms(); }
-    b->n_bytes = (uint32_t)flagged.size();
-    b->n_packed = (uint32_t)n;
-    if (!flagged.empty()) {
-      // the few pairs with other letters: their bytes in a compact blob, byte offsets and flags scattered to their slots
-      const size_t nb = flagged.size();
-      std::vector<int64_t> fpo(nb), fto(nb);
-      size_t blob = 0;
-      for (size_t j = 0; j < nb; ++j) { fpo[j] = (int64_t)blob; blob += (size_t)p_len[flagged[j]]; fto[j] = (int64_t)blob; blob += (size_t)t_len[flagged[j]]; }
-      std::vector<uint8_t> hb(blob + 1);
-      for (size_t j = 0; j < nb; ++j) {
-        memcpy(hb.data() + fpo[j], seqs + p_off[flagged[j]], (size_t)p_len[flagged[j]]);
-        memcpy(hb.data() + fto[j], seqs + t_off[flagged[j]], (size_t)t_len[flagged[j]]);
-      }
-      int64_t *d_fpo = nullptr, *d_fto = nullptr;
-      HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, blob + 64));
-      HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_bytes, nb * sizeof(uint32_t)));
-      HIP_TRY(al, pool_alloc(al, (void**)&d_fpo, nb * sizeof(int64_t)));
-      HIP_TRY(al, pool_alloc(al, (void**)&d_fto, nb * sizeof(int64_t)));
-      HIP_TRY(al, hipMemcpyAsync(b->d_bytes, hb.data(), blob, hipMemcpyHostToDevice, al->stream));
-      HIP_TRY(al, hipMemcpyAsync(b->d_list_bytes, flagged.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
-      HIP_TRY(al, hipMemcpyAsync(d_fpo, fpo.data(), nb * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
-      HIP_TRY(al, hipMemcpyAsync(d_fto, fto.data(), nb * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
-      hipLaunchKernelGGL(wfa::wfa_flag_scatter_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, al->stream,
-                         b->d_list_bytes, d_fpo, d_fto, (uint32_t)nb, b->d_pboff, b->d_tboff, b->d_flags);
-      HIP_TRY(al, hipGetLastError());
-      // the list of the 2-bit pairs = all pairs but the flagged ones (ascending)
-      std::vector<uint32_t> lp;
-      lp.reserve((size_t)n - nb);
-      size_t fj = 0;
-      for (int64_t i = 0; i < n; ++i) { if (fj < nb && flagged[fj] == (uint32_t)i) { ++fj; continue; } lp.push_back((uint32_t)i); }
-      b->n_packed = (uint32_t)lp.size();
-      if (!lp.empty()) {
-        HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_packed, lp.size() * sizeof(uint32_t)));
-        HIP_TRY(al, hipMemcpyAsync(b->d_list_packed, lp.data(), lp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
-      }
-      HIP_TRY(al, hipStreamSynchronize(al->stream));   // (host vectors above go out of scope)
-      pool_release(al, d_fpo); pool_release(al, d_fto);
-    }
-  } else if (n > 0) {
-    if (pipelined) {
-      // host threads -> pinned ring -> DMA; the metadata pieces are computed into their slots, the caller's arrays copied
-      std::vector<UploadJob> jobs;
-      jobs.push_back({b->d_meta, nullptr, (size_t)n * sizeof(WfaPairMeta),
-                      [&](uint8_t* out, size_t off, size_t) { pass2_part((int)(off / staged_slot_bytes(al)) * sub, reinterpret_cast<WfaPairMeta*>(out), sub); }});
-      jobs.push_back({b->d_bytes, seqs, (size_t)blob_end, nullptr});
-      jobs.push_back({b->d_pboff, p_off, (size_t)n * sizeof(int64_t), nullptr});
-      jobs.push_back({b->d_tboff, t_off, (size_t)n * sizeof(int64_t), nullptr});
-      const int urc = staged_upload(al, jobs, al->stream);
-      if (urc != WFA_HIP_OK) return urc;
-    } else {
-      HIP_TRY(al, hipMemcpyAsync(b->d_bytes, seqs, (size_t)blob_end, hipMemcpyHostToDevice, al->stream));
-      HIP_TRY(al, hipMemcpyAsync(b->d_pboff, p_off, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
-      HIP_TRY(al, hipMemcpyAsync(b->d_tboff, t_off, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
-      HIP_TRY(al, hipMemcpyAsync(b->d_meta, meta.get(), (size_t)n * sizeof(WfaPairMeta), hipMemcpyHostToDevice, al->stream));
-    }
-    if (in2bit) {
-      // 2-bit input: re-based to whole words and re-coded by one small kernel; no letter can be outside ACGT
-      const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)al->cu_count * 64));
-      hipLaunchKernelGGL(wfa::wfa_repack2_kernel, dim3(grid), dim3(256), 0, al->stream, b->d_bytes, b->d_pboff, b->d_tboff, b->d_meta, n, b->d_words);
-      HIP_TRY(al, hipGetLastError());
-      b->n_bytes = 0; b->n_packed = (uint32_t)n;
-      if (n <= 256) b->uploads_pending = true;
-      else {   // (plain copies: the caller's arrays are still being read; either way nothing reads the 2-bit blob after the repack kernel —
-               // it used to stay in HBM for the batch's lifetime on the pipelined path)
-        HIP_TRY(al, hipStreamSynchronize(al->stream));
-        pool_release(al, b->d_bytes); b->d_bytes = nullptr;
-      }
-      b->h_meta = std::move(meta);
-      return finish_batch_build(al, b);
-    }
-    const int threads = 256;
-    // lanes per pair: the words of the longest pair, rounded up to a power of two (at most a whole wave)
-    int log2slots = 1;
-    while (log2slots < 6 && (1 << log2slots) < 2 * ((b->max_len + 15) >> 4)) ++log2slots;
-    const int64_t group = 64 >> log2slots;
-    const int64_t want = ((n + group - 1) / group + 3) / 4;  // 4 waves per workgroup
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)al->cu_count * 64));
-    hipLaunchKernelGGL(wfa::wfa_pack_kernel, dim3(grid), dim3(threads), 0, al->stream,
-                       b->d_bytes, b->d_pboff, b->d_tboff, b->d_meta, n, b->d_words, b->d_flags, log2slots, b->d_counters + 15);
-    HIP_TRY(al, hipGetLastError());
-    std::vector<uint8_t> flags;
-    if (n <= 256) {
-      flags.assign((size_t)n, 0);
-      // a handful of pairs: look for letters outside ACGT on the host, the round trip costs more than the scan
-      for (int64_t i = 0; i < n; ++i) {
-        uint8_t bad = 0;
-        const uint8_t* ps = seqs + p_off[i]; const uint8_t* ts = seqs + t_off[i];
-        for (int32_t j = 0; j < p_len[i]; ++j) { const uint8_t ch = ps[j]; bad |= !(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'); }
-        for (int32_t j = 0; j < t_len[i]; ++j) { const uint8_t ch = ts[j]; bad |= !(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'); }
-        flags[(size_t)i] = bad;
-      }
-      b->uploads_pending = true;  // the caller's arrays are still being read: see wfa_hip_batch_create
-    } else {
-      // one word first: the per-pair flags (n bytes) are fetched only if some pair holds a letter outside ACGT
-      uint32_t any_flag = 0;
-      HIP_TRY(al, hipMemcpyAsync(&any_flag, b->d_counters + 15, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
-      HIP_TRY(al, hipStreamSynchronize(al->stream));
-      if (any_flag || (c.wildcard >= 0 && b->wild < 0)) {
-        flags.assign((size_t)n, 0);
-        HIP_TRY(al, hipMemcpy(flags.data(), b->d_flags, (size_t)n, hipMemcpyDeviceToHost));
-      }
-    }
-    if (timing) { fprintf(stderr, "[wfa_hip] H2D + pack + flags D2H %.3f ms (%.2f GB)\n", now_ms() - t0, blob_end / 1e9); t0 = now_ms(); }
-    // split into the 2-bit and the 8-bit work lists (wildcard matching needs the bytes)
-    std::vector<uint32_t> lp, lb;
-    if (c.wildcard >= 0 && b->wild < 0) {   // (a wildcard among ACGT: every pair on its bytes)
-      lb.resize((size_t)n);
-      for (int64_t i = 0; i < n; ++i) lb[i] = (uint32_t)i;
-    } else {
-      int64_t nbad = 0;
-      for (size_t i = 0; i < flags.size(); ++i) nbad += flags[i];
-      if (nbad) {
-        lp.reserve((size_t)(n - nbad)); lb.reserve((size_t)nbad);
-        for (int64_t i = 0; i < n; ++i) (flags[i] ? lb : lp).push_back((uint32_t)i);
-      }
-    }
-    b->n_bytes = (uint32_t)lb.size();
-    b->n_packed = (uint32_t)(lb.empty() ? n : lp.size());
-    if (!lb.empty()) {
-      HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_bytes, lb.size() * sizeof(uint32_t)));
-      HIP_TRY(al, hipMemcpy(b->d_list_bytes, lb.data(), lb.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      if (!lp.empty()) {
-        HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_packed, lp.size() * sizeof(uint32_t)));
-        HIP_TRY(al, hipMemcpy(b->d_list_packed, lp.data(), lp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      }
-    } else {
-      // every pair is pure ACGT: the ASCII blob is no longer needed
-      pool_release(al, b->d_bytes); b->d_bytes = nullptr;
-    }
-    if (timing) { fprintf(stderr, "[wfa_hip] work lists + free %.3f ms\n", now_ms() - t0); t0 = now_ms(); }
   }
   b->h_meta = std::move(meta);
   return finish_batch_build(al, b);
@@ -1478,17 +1597,14 @@ static int pilot_band(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream)
   memset(&ba, 0, sizeof(ba));
   ba.words = b->d_words; ba.meta = b->d_meta; ba.worklist = psample; ba.nwork = np;
   ba.score = b->d_score; ba.status = b->d_status; ba.fb_list = plist; ba.fb_count = pcount;
-  ba.g = wfa::band_gcd(b->dcfg, two);
-  ba.x = b->dcfg.x; ba.oe = b->dcfg.o1 + b->dcfg.e1; ba.e = b->dcfg.e1;
-  if (two) { ba.oe2 = b->dcfg.o2 + b->dcfg.e2; ba.e2 = b->dcfg.e2; }
-  ba.min_wf_len = b->dcfg.min_wf_len; ba.max_dist_thr = b->dcfg.max_dist_thr; ba.steps_between = b->dcfg.steps_between;
-  ba.heur = b->dcfg.heuristic; ba.xdrop = b->dcfg.xdrop; ba.max_steps = b->dcfg.max_steps; ba.scope = b->dcfg.scope;
+  fill_band_penalties(ba, b->dcfg, two);
+  fill_heuristic(ba, b->dcfg);
+  ba.xdrop = b->dcfg.xdrop; ba.scope = b->dcfg.scope;
   const int words = ((b->max_len + 15) >> 4) + 4;
   ba.lds_words = words;
   ba.slim = knob(al, K_BAND_SLIM, 1);
   ba.h16 = 1;
-  ba.ef = (b->dcfg.endsfree && (b->dcfg.pbf | b->dcfg.pef | b->dcfg.tbf | b->dcfg.tef)) ? 1 : 0;
-  ba.pbf = b->dcfg.pbf; ba.pef = b->dcfg.pef; ba.tbf = b->dcfg.tbf; ba.tef = b->dcfg.tef;
+  fill_ends_free(ba, b->dcfg, true);
   if (wfa::launch_band(ba, 4, false, false, true, (long long)np, stream) != 0) return pilot_launch_failed(al, b, rtc_failures);   // (the widest window: what it hands on, both stages hand on)
   uint32_t handed = 0;
   HIP_TRY(al, hipMemcpyAsync(&handed, pcount, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -1720,6 +1836,12 @@ static int launch_general_dyn(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t
 // Geometry of the general kernel: threads per alignment, workgroups in flight, workspace per workgroup.
 struct Geometry { int threads; int grid; int64_t ws_stride; };
 
+// every run of an aligner uses the one workspace (al->ws): order `stream` after the previous run when that was enqueued on another stream
+static int wait_for_workspace(wfa_hip_aligner* al, hipStream_t stream) {
+  if (al->ws_event_recorded && al->ws_last_stream != stream) HIP_TRY(al, hipStreamWaitEvent(stream, al->ws_event, 0));
+  return WFA_HIP_OK;
+}
+
 static int64_t free_budget(wfa_hip_aligner* al) {
   size_t fr = 0, tot = 0;
   if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = al->total_mem / 2;
@@ -1854,22 +1976,6 @@ struct StageTimer {
     return ms;
   }
 };
-
-// ---- fields that every stage's arguments share (FastArgs / BandArgs / TileArgs / WideArgs / WfaKernelArgs) ----
-template <class Args> static void fill_cigar_out(Args& a, const wfa_hip_batch* b) {
-  a.cigar_ops = b->d_ops; a.cigar_off = b->d_cigar_off; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len;
-}
-// (need_free_len: the register and banded kernels take the ends-free path only when an end is free at all; the tile and wide kernels
-// whenever the span is ends-free)
-template <class Args> static void fill_ends_free(Args& a, const WfaDevConfig& d, bool need_free_len) {
-  a.ef = (d.endsfree && (!need_free_len || (d.pbf | d.pef | d.tbf | d.tef))) ? 1 : 0;
-  a.pbf = d.pbf; a.pef = d.pef; a.tbf = d.tbf; a.tef = d.tef;
-}
-template <class Args> static void fill_heuristic(Args& a, const WfaDevConfig& d) {
-  a.heur = d.heuristic; a.min_wf_len = d.min_wf_len; a.max_dist_thr = d.max_dist_thr;
-  a.steps_between = d.steps_between; a.max_steps = d.max_steps;
-}
-static int affine_gcd(const WfaDevConfig& d) { return wfa::gcd_int(wfa::gcd_int(d.x, d.o1 + d.e1), d.e1); }
 
 // ---- the plan of the cascade ------------------------------------------------------------------------------
 struct WideStage { wfa::WideArgs a; int grid = 0, threads = 0; size_t smem = 0, hist_off = 0; bool grows = false, w32 = false; };
@@ -2593,8 +2699,7 @@ static int run_segfull_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t 
   memset(&ba, 0, sizeof(ba));
   ba.meta = b->d_meta; ba.worklist = c.in_list; ba.words = b->d_words;
   fill_cigar_out(ba, b);
-  ba.g = affine_gcd(b->dcfg);
-  ba.x = b->dcfg.x; ba.oe = b->dcfg.o1 + b->dcfg.e1; ba.e = b->dcfg.e1;
+  fill_band_penalties(ba, b->dcfg, false);
   ba.hist = al->ws; ba.hist_stride = p.segfull_slot_ints[sf]; ba.end_state = fa.end_state;
   ba.split = 1; ba.h16 = 1; ba.seg_w = p.segfull_w[sf];
   { long long ci, ei, si; wfa::seg_full_slot(b->dcfg, p.segfull_w[sf], b->max_len, &ci, &ei, &si); ba.pb = 1; ba.pb_code_ints = ci; ba.pb_event_ints = ei; }
@@ -2848,9 +2953,7 @@ static int run_band_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t str
   uint32_t* out_list = c.out_list(b);
   uint32_t* out_count = c.next_count(b);
   ba.fb_list = out_list; ba.fb_count = out_count;
-  ba.g = wfa::band_gcd(b->dcfg, b->ncomp == 5);
-  ba.x = b->dcfg.x; ba.oe = b->dcfg.o1 + b->dcfg.e1; ba.e = b->dcfg.e1;
-  if (b->ncomp == 5) { ba.oe2 = b->dcfg.o2 + b->dcfg.e2; ba.e2 = b->dcfg.e2; }
+  fill_band_penalties(ba, b->dcfg, b->ncomp == 5);
   fill_heuristic(ba, b->dcfg);
   ba.xdrop = b->dcfg.xdrop; ba.scope = b->dcfg.scope;
   const int words = ((b->max_len + 15) >> 4) + 4;
@@ -3011,9 +3114,7 @@ static int batch_run_once(wfa_hip_batch_t* b, void* stream_) {
   HIP_TRY(al, hipSetDevice(al->device));
   mailbox_release(al);
   hipStream_t stream = stream_ ? (hipStream_t)stream_ : al->stream;
-  // every run of this aligner uses the one workspace (al->ws): order this run after the previous one when it was
-  // enqueued on another stream
-  if (al->ws_event_recorded && al->ws_last_stream != stream) HIP_TRY(al, hipStreamWaitEvent(stream, al->ws_event, 0));
+  { const int wrc = wait_for_workspace(al, stream); if (wrc != WFA_HIP_OK) return wrc; }
   // the batch's uploads were enqueued on the aligner's stream (and may still be in flight): a run elsewhere waits for them
   if (stream != al->stream && b->upload_event) HIP_TRY(al, hipStreamWaitEvent(stream, b->upload_event, 0));
   // an early return (an error) must not leave walks / expands running on the side stream: they write blocks the caller may
@@ -3352,6 +3453,7 @@ static const int64_t TINY_MAX_PAIRS = 16;          // general-kernel form (a wor
 // 2 048 pairs 160 us (score) / 320 us (op strings) against 482 / 730 us, 4 096 pairs 319 / 589 against 534 / 1 001 us
 static const int64_t TINY_MAX_PAIRS_BAND = 4096;
 static const size_t TINY_IN_BYTES = (size_t)1 << 20, TINY_BLOCK_BYTES = (size_t)4 << 20;
+static const int TINY_BAND_NCH = 2;   // diagonals of the banded form: 64 x this
 
 __global__ void __launch_bounds__(256) wfa_tiny_copy_kernel(uint4* __restrict__ dst, const uint4* __restrict__ src, int n16) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) dst[i] = src[i];
@@ -3452,243 +3554,298 @@ static int mailbox_call(wfa_hip_aligner* al, const wfa::BandArgs& ba, bool full,
   }
 }
 
-static int align_tiny(wfa_hip_aligner* al, int64_t n, const uint8_t* seqs, const int64_t* p_off, const int32_t* p_len,
-                      const int64_t* t_off, const int32_t* t_len, int32_t* score, int32_t* status, uint8_t* cigar_ops,
-                      const int64_t* cigar_off, int64_t* cigar_begin, int32_t* cigar_len) {
-  const wfa_hip_config_t& c = al->cfg;
-  const bool full = c.scope == WFA_SCOPE_FULL;
-  if (n < 1 || n > TINY_MAX_PAIRS_BAND || knob(al, K_NO_TINY, 0)) return 0;
-  if (c.memory_mode == WFA_MEM_BIWFA && (full || c.max_steps > 0 || c.heuristic != WFA_HEUR_NONE)) return 0;   // (the BiWFA kernel: the batch path)
-  if (!score || !status || (full && cigar_ops && (!cigar_off || !cigar_begin || !cigar_len))) return 0;
+// what wfa_hip_align_batch was called with
+struct TinyCall {
+  int64_t n; const uint8_t* seqs; const int64_t* p_off; const int32_t* p_len; const int64_t* t_off; const int32_t* t_len;
+  int32_t* score; int32_t* status; uint8_t* cigar_ops; const int64_t* cigar_off; int64_t* cigar_begin; int32_t* cigar_len;
+  bool full;
+};
+// what a form of the tiny path answers (< 0: an error)
+enum { TINY_TO_BATCH = 0, TINY_SERVED = 1, TINY_TO_GENERAL = 2 };
+
+// Where everything lies in the pinned block.  Input region (the first TINY_IN_BYTES), general form: meta, byte offsets, op-region starts,
+// the bytes; band form: meta, op-region starts, completion flags, the packed words.  Output region, both forms: results and op bytes.
+struct TinyLayout {
   int64_t blob = 0, ops_total = 0;
   int max_len = 0, max_width = 0;
+  size_t o_meta = 0, o_pb = 0, o_tb = 0, o_co = 0, o_blob = 0, in_bytes = 0;
+  size_t b_meta = 0, b_co = 0, b_done = 0, b_words = 0;
+  size_t o_score = 0, o_status = 0, o_cb = 0, o_cl = 0, o_ops = 0;
+  bool general_fits = false, band_form = false;
+};
+
+// the argument checks and the layout: 1 = laid out, 0 = not for this path, < 0 = an error
+static int tiny_layout(wfa_hip_aligner* al, const TinyCall& k, TinyLayout* L) {
+  const wfa_hip_config_t& c = al->cfg;
+  const int64_t n = k.n;
+  if (n < 1 || n > TINY_MAX_PAIRS_BAND || knob(al, K_NO_TINY, 0)) return 0;
+  if (c.memory_mode == WFA_MEM_BIWFA && (k.full || c.max_steps > 0 || c.heuristic != WFA_HEUR_NONE)) return 0;   // (the BiWFA kernel: the batch path)
+  if (!k.score || !k.status || (k.full && k.cigar_ops && (!k.cigar_off || !k.cigar_begin || !k.cigar_len))) return 0;
   for (int64_t i = 0; i < n; ++i) {
-    const int pl = p_len[i], tl = t_len[i];
-    if (pl < 0 || tl < 0 || p_off[i] < 0 || t_off[i] < 0) { al->err = "negative length or offset"; return WFA_HIP_EINVAL; }
-    if (c.span == WFA_SPAN_ENDSFREE && (c.pattern_begin_free > pl || c.pattern_end_free > pl || c.text_begin_free > tl || c.text_end_free > tl)) {
-      al->err = "Ends-free parameters must be not larger than the sequences"; return WFA_HIP_EINVAL;
-    }
-    blob += (int64_t)((pl + 15) & ~15) + ((tl + 15) & ~15);
-    ops_total += (int64_t)pl + tl;
-    max_len = std::max(max_len, std::max(pl, tl)); max_width = std::max(max_width, pl + tl + 3);
+    const int pl = k.p_len[i], tl = k.t_len[i];
+    if (pl < 0 || tl < 0 || k.p_off[i] < 0 || k.t_off[i] < 0) { al->err = part_error_message(PART_NEGATIVE); return WFA_HIP_EINVAL; }
+    if (free_ends_exceed(c, pl, tl)) { al->err = part_error_message(PART_ENDS_FREE); return WFA_HIP_EINVAL; }
+    L->blob += (int64_t)((pl + 15) & ~15) + ((tl + 15) & ~15);
+    L->ops_total += (int64_t)pl + tl;
+    L->max_len = std::max(L->max_len, std::max(pl, tl)); L->max_width = std::max(L->max_width, pl + tl + 3);
   }
-  if (max_len > 1000) return 0;   // long reads: the staged path (banded / wide kernels) is several times faster than this one's general kernel
-  // input region: meta, byte offsets, op-region starts, the bytes; output region: results and op bytes
-  const size_t o_meta = 0, o_pb = o_meta + (size_t)n * sizeof(WfaPairMeta), o_tb = o_pb + (size_t)n * 8, o_co = o_tb + (size_t)n * 8,
-               o_blob = (o_co + (size_t)(n + 1) * 8 + 15) & ~(size_t)15, in_bytes = (o_blob + (size_t)blob + 15) & ~(size_t)15;
-  const size_t o_score = TINY_IN_BYTES, o_status = o_score + (size_t)n * 4, o_cb = (o_status + (size_t)n * 4 + 7) & ~(size_t)7, o_cl = o_cb + (size_t)n * 8,
-               o_ops = (o_cl + (size_t)n * 4 + 15) & ~(size_t)15;
-  if (full && o_ops + (size_t)ops_total + 16 > TINY_BLOCK_BYTES) return 0;
-  const bool general_fits = n <= TINY_MAX_PAIRS && in_bytes <= TINY_IN_BYTES;
-  const bool band_form = !al->dcfg.lin && wfa::band_supported(al->dcfg, al->ncomp) && c.wildcard < 0 && knob(al, K_NO_TINY_BAND, 0) == 0 && knob(al, K_NO_BAND, 0) == 0;   // (lin: the banded kernel has no one-component form)
-  if (!general_fits && !band_form) return 0;
-  HIP_TRY(al, hipSetDevice(al->device));
-  if (!al->tiny_h) {
-    HIP_TRY(al, hipHostMalloc((void**)&al->tiny_h, TINY_BLOCK_BYTES, hipHostMallocMapped));
-    HIP_TRY(al, hipMalloc((void**)&al->tiny_d, TINY_IN_BYTES));
-  }
-  uint8_t* h = al->tiny_h;
-  if (!al->tiny_hd) HIP_TRY(al, hipHostGetDevicePointer((void**)&al->tiny_hd, h, 0));
-  uint8_t* hd = al->tiny_hd;   // the pinned block as the device sees it
-  // ---- gap-affine / gap-affine-2p with an instantiated penalty shape, pure ACGT: ONE launch of the banded kernel (one wave per
-  // pair, 128 diagonals in registers).  The host packs the sequences to 2 bits into the pinned block; the kernel stages them
-  // in LDS straight from there (no copy kernel), aligns, walks back in-kernel and writes results and op bytes into the pinned
-  // block.  A pair the window cannot hold shows as status WFA_INTERNAL_FALLBACK and the call goes on to the general kernel below.
-  if (band_form) {
-    const size_t b_meta = 0, b_co = b_meta + (size_t)n * sizeof(WfaPairMeta), b_done = b_co + (size_t)(n + 1) * 8,
-                 b_words = (b_done + (size_t)n * 4 + 15) & ~(size_t)15;
-    WfaPairMeta* bm = reinterpret_cast<WfaPairMeta*>(h + b_meta);
-    int64_t* bco = reinterpret_cast<int64_t*>(h + b_co);
-    uint32_t* bw = reinterpret_cast<uint32_t*>(h + b_words);
-    uint32_t w = 0;
-    int64_t oo = 0;
-    bool bad = false;
-    size_t need_bytes = b_words;
-    for (int64_t i = 0; i < n; ++i) need_bytes += (size_t)(((p_len[i] + 15) >> 4) + ((t_len[i] + 15) >> 4)) * 4;
-    if (need_bytes + 64 <= TINY_IN_BYTES) {
-      for (int64_t i = 0; i < n && !bad; ++i) {
-        const int pl = p_len[i], tl = t_len[i];
-        bm[i].plen = pl; bm[i].tlen = tl;
-        bm[i].p_woff = w; bad |= wfa::host_pack_seq(seqs + p_off[i], pl, bw + w, -1); w += (uint32_t)((pl + 15) >> 4);
-        bm[i].t_woff = w; bad |= wfa::host_pack_seq(seqs + t_off[i], tl, bw + w, -1); w += (uint32_t)((tl + 15) >> 4);
-        bco[i] = oo; oo += (int64_t)pl + tl;
-      }
-      bco[n] = oo;
-      for (int j = 0; j < 4; ++j) bw[w + j] = 0;   // (the funnel shift reads one word ahead)
-    } else {
-      bad = true;
-    }
-    if (!bad) {
-      const int nch = 2;
-      wfa::BandArgs ba;
-      memset(&ba, 0, sizeof(ba));
-      ba.words = reinterpret_cast<const uint32_t*>(hd + b_words); ba.meta = reinterpret_cast<const WfaPairMeta*>(hd + b_meta);
-      ba.nwork = (uint32_t)n;
-      ba.score = reinterpret_cast<int32_t*>(hd + o_score); ba.status = reinterpret_cast<int32_t*>(hd + o_status);
-      ba.cigar_ops = hd + o_ops; ba.cigar_off = reinterpret_cast<const int64_t*>(hd + b_co);
-      ba.cigar_begin = reinterpret_cast<int64_t*>(hd + o_cb); ba.cigar_len = reinterpret_cast<int32_t*>(hd + o_cl);
-      ba.g = wfa::band_gcd(al->dcfg, al->ncomp == 5);
-      ba.x = al->dcfg.x; ba.oe = al->dcfg.o1 + al->dcfg.e1; ba.e = al->dcfg.e1;
-      if (al->ncomp == 5) { ba.oe2 = al->dcfg.o2 + al->dcfg.e2; ba.e2 = al->dcfg.e2; }
-      ba.min_wf_len = al->dcfg.min_wf_len; ba.max_dist_thr = al->dcfg.max_dist_thr; ba.steps_between = al->dcfg.steps_between;
-      ba.heur = al->dcfg.heuristic; ba.xdrop = al->dcfg.xdrop; ba.max_steps = al->dcfg.max_steps; ba.scope = al->dcfg.scope;
-      ba.lds_words = ((max_len + 15) >> 4) + 4;
-      // one pair, gap-affine: the resident kernel takes it from its mailbox when it can (mailbox_call) — its instance outlives the call,
-      // so everything in its arguments is sized for the longest pair of this path, not for this one
-      const bool try_mb = n == 1 && w + 4 <= 136 && al->ncomp == 3 && knob(al, K_BAND_SLIM, 1) != 0 && knob(al, K_NO_TINY_INLINE, 0) == 0 &&
-                          knob(al, K_MAILBOX, 1) != 0 && knob(al, K_NO_TINY_POLL, 0) == 0 && al->mb_failures < 3;
-      if (try_mb) ba.lds_words = ((1000 + 15) >> 4) + 5;
-      ba.h16 = 1;
-      ba.slim = knob(al, K_BAND_SLIM, 1);   // (wf-adaptive or no heuristic: wfa_slim_kernel — a third of the instructions per score step)
-      ba.ef = (al->dcfg.endsfree && (al->dcfg.pbf | al->dcfg.pef | al->dcfg.tbf | al->dcfg.tef)) ? 1 : 0;
-      ba.pbf = al->dcfg.pbf; ba.pef = al->dcfg.pef; ba.tbf = al->dcfg.tbf; ba.tef = al->dcfg.tef;
-      if (full) {
-        const int rec = ((al->ncomp != 5) ? 2 : 4) * 64 * nch;
-        const long long records = std::max<long long>(256, (long long)((try_mb ? 1000 : max_len) * 0.9 * penalty_scale(al->dcfg)) / ba.g + 64);
-        ba.hist_stride = ((int64_t)records * rec + 63) & ~63ll;
-        // (one history slice per pair — 256 KB for 150 bp gap-affine — stays allocated for the aligner's lifetime: calls
-        // whose slices exceed 256 MB or the free memory take the batch path, and so does a call whose workspace cannot be had)
-        const size_t hist_bytes = (size_t)n * (size_t)ba.hist_stride * 4;
-        if (hist_bytes > ((size_t)256 << 20) || (int64_t)hist_bytes > free_budget(al)) return 0;
-        if (ensure_ws(al, hist_bytes) != WFA_HIP_OK) return 0;
-        ba.hist = al->ws;
-      }
-      hipStream_t stream = al->stream;
-      if (al->ws_event_recorded && al->ws_last_stream != stream) HIP_TRY(al, hipStreamWaitEvent(stream, al->ws_event, 0));
-      // (a status that is none of the kernel's: a wave that wrote nothing would be seen)
-      int32_t* hst0 = reinterpret_cast<int32_t*>(h + o_status);
-      for (int64_t i = 0; i < n; ++i) hst0[i] = WFA_INTERNAL_FALLBACK;
-      // completion: a flag per pair in the pinned block, stored by the kernel at system scope after the pair's results;
-      // the host polls the flags (a few microseconds after the last store) and only then falls back on the stream wait
-      volatile int32_t* hdone = reinterpret_cast<volatile int32_t*>(h + b_done);
-      const bool poll = knob(al, K_NO_TINY_POLL, 0) == 0;
-      for (int64_t i = 0; i < n; ++i) hdone[i] = 0;
-      ba.done = poll ? reinterpret_cast<int32_t*>(hd + b_done) : nullptr;
-      // one pair: lengths, op-region offsets and packed words ride in the kernel arguments (wfa_slim_kernel_one)
-      uint32_t one[8 + 136];
-      if (n == 1 && w + 4 <= 136 && ba.slim && knob(al, K_NO_TINY_INLINE, 0) == 0) {
-        memcpy(one, &bm[0], 16); memcpy(one + 4, &bco[0], 16);
-        memcpy(one + 8, bw, (size_t)(w + 4) * 4);
-        ba.one = one;
-      }
-      bool seen = false;
-      if (try_mb && ba.one) {
-        // (a batch run still in flight may be using the workspace this pair's history goes to)
-        if (full && al->ws_event_recorded) HIP_TRY(al, hipEventSynchronize(al->ws_event));
-        wfa::BandArgs mba = ba;
-        mba.done = nullptr;
-        int32_t sr = 0, st = WFA_INTERNAL_FALLBACK;
-        seen = mailbox_call(al, mba, full, al->dcfg.heuristic != WFA_HEUR_NONE, one, (size_t)8 + w + 4, &sr, &st) == 1;
-        if (seen) {   // (the answer came in the mailbox's own word: the pinned block's score / status are what the launch path reads)
-          std::atomic_thread_fence(std::memory_order_acquire);
-          reinterpret_cast<int32_t*>(h + o_score)[0] = sr; hst0[0] = st;
-        }
-      }
-      const unsigned rtc_failures = wfa::rtc_failure_count();
-      if (!seen && wfa::launch_band(ba, nch, full, al->dcfg.heuristic != WFA_HEUR_NONE, true, (long long)n, stream) != 0) {
-        if (al->dcfg.rtc && wfa::rtc_failure_count() != rtc_failures) {
-          // a run-time shape that cannot be built: this aligner goes on without them (the batch path and the general kernel take the call)
-          (void)hipGetLastError();
-          al->dcfg.rtc = 0;
-          al->rtc_note = std::string("run-time kernels switched off for this aligner: ") + wfa::rtc_last_error();
-          return 0;
-        }
-        al->err = "band kernel launch failed"; return WFA_HIP_EDEVICE;
-      }
-      // (no event for the workspace: the call returns only after every pair's flag — stored behind its walk, the history's last
-      // reader — or after the stream has drained)
-      const bool served = seen;
-      if (poll && !served) {
-        const double t_poll = now_ms();
-        for (;;) {
-          int64_t got = 0;
-          for (int64_t i = 0; i < n; ++i) got += (hdone[i] != 0);
-          if (got == n) { seen = true; break; }
-          if (now_ms() - t_poll > 20.0) break;   // (something is wrong or slow: the stream wait below decides)
-          __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-      }
-      if (!seen) HIP_TRY(al, hipStreamSynchronize(stream));
-      const int32_t* hs = reinterpret_cast<const int32_t*>(h + o_score);
-      bool handed_on = false;
-      for (int64_t i = 0; i < n; ++i) handed_on |= (hst0[i] == WFA_INTERNAL_FALLBACK);
-      if (!handed_on) {
-        const int64_t* hcb = reinterpret_cast<const int64_t*>(h + o_cb); const int32_t* hcl = reinterpret_cast<const int32_t*>(h + o_cl);
-        for (int64_t i = 0; i < n; ++i) {
-          score[i] = tiny_score(al->dcfg, hs[i], hst0[i], p_len[i], t_len[i]); status[i] = hst0[i];
-          if (cigar_len) cigar_len[i] = full ? hcl[i] : 0;
-          if (cigar_begin) cigar_begin[i] = 0;
-          if (full && cigar_ops) {
-            const int64_t rel = hcb[i] - bco[i];
-            if (hcl[i] > 0) memcpy(cigar_ops + cigar_off[i] + rel, h + o_ops + hcb[i], (size_t)hcl[i]);
-            cigar_begin[i] = cigar_off[i] + rel;
-          }
-        }
-        return 1;
-      }
+  if (L->max_len > 1000) return 0;   // long reads: the staged path (banded / wide kernels) is several times faster than this one's general kernel
+  const size_t sn = (size_t)n;
+  L->o_meta = 0; L->o_pb = L->o_meta + sn * sizeof(WfaPairMeta); L->o_tb = L->o_pb + sn * 8; L->o_co = L->o_tb + sn * 8;
+  L->o_blob = (L->o_co + (sn + 1) * 8 + 15) & ~(size_t)15; L->in_bytes = (L->o_blob + (size_t)L->blob + 15) & ~(size_t)15;
+  L->b_meta = 0; L->b_co = L->b_meta + sn * sizeof(WfaPairMeta); L->b_done = L->b_co + (sn + 1) * 8;
+  L->b_words = (L->b_done + sn * 4 + 15) & ~(size_t)15;
+  L->o_score = TINY_IN_BYTES; L->o_status = L->o_score + sn * 4; L->o_cb = (L->o_status + sn * 4 + 7) & ~(size_t)7; L->o_cl = L->o_cb + sn * 8;
+  L->o_ops = (L->o_cl + sn * 4 + 15) & ~(size_t)15;
+  if (k.full && L->o_ops + (size_t)L->ops_total + 16 > TINY_BLOCK_BYTES) return 0;
+  L->general_fits = n <= TINY_MAX_PAIRS && L->in_bytes <= TINY_IN_BYTES;
+  L->band_form = !al->dcfg.lin && wfa::band_supported(al->dcfg, al->ncomp) && c.wildcard < 0 && knob(al, K_NO_TINY_BAND, 0) == 0 && knob(al, K_NO_BAND, 0) == 0;   // (lin: the banded kernel has no one-component form)
+  return (L->general_fits || L->band_form) ? 1 : 0;
+}
+
+// results and op bytes from the pinned block to the caller's arrays (`co`: the op-region starts the kernel was given)
+static void tiny_copy_out(const TinyCall& k, const TinyLayout& L, const uint8_t* h, const WfaDevConfig& d, const int64_t* co) {
+  const int32_t* hs = reinterpret_cast<const int32_t*>(h + L.o_score); const int32_t* hst = reinterpret_cast<const int32_t*>(h + L.o_status);
+  const int64_t* hcb = reinterpret_cast<const int64_t*>(h + L.o_cb); const int32_t* hcl = reinterpret_cast<const int32_t*>(h + L.o_cl);
+  for (int64_t i = 0; i < k.n; ++i) {
+    k.score[i] = tiny_score(d, hs[i], hst[i], k.p_len[i], k.t_len[i]); k.status[i] = hst[i];
+    if (k.cigar_len) k.cigar_len[i] = k.full ? hcl[i] : 0;
+    if (k.cigar_begin) k.cigar_begin[i] = 0;
+    if (k.full && k.cigar_ops) {
+      const int64_t rel = hcb[i] - co[i];
+      if (hcl[i] > 0) memcpy(k.cigar_ops + k.cigar_off[i] + rel, h + L.o_ops + hcb[i], (size_t)hcl[i]);
+      k.cigar_begin[i] = k.cigar_off[i] + rel;
     }
   }
-  if (!general_fits) return 0;   // (more pairs than the general-kernel form takes: the batch path)
-  WfaPairMeta* meta = reinterpret_cast<WfaPairMeta*>(h + o_meta);
-  int64_t* pb = reinterpret_cast<int64_t*>(h + o_pb); int64_t* tb = reinterpret_cast<int64_t*>(h + o_tb); int64_t* co = reinterpret_cast<int64_t*>(h + o_co);
+}
+
+// band form, input: metadata, op-region starts and the sequences packed to 2 bits into the pinned block; *words = the packed words.
+// false: a letter outside ACGT, or more words than the input region holds
+static bool tiny_band_pack(const TinyCall& k, const TinyLayout& L, uint8_t* h, uint32_t* words) {
+  WfaPairMeta* bm = reinterpret_cast<WfaPairMeta*>(h + L.b_meta);
+  int64_t* bco = reinterpret_cast<int64_t*>(h + L.b_co);
+  uint32_t* bw = reinterpret_cast<uint32_t*>(h + L.b_words);
+  size_t need_bytes = L.b_words;
+  for (int64_t i = 0; i < k.n; ++i) need_bytes += (size_t)(((k.p_len[i] + 15) >> 4) + ((k.t_len[i] + 15) >> 4)) * 4;
+  if (need_bytes + 64 > TINY_IN_BYTES) return false;
+  uint32_t w = 0;
+  int64_t oo = 0;
+  bool bad = false;
+  for (int64_t i = 0; i < k.n && !bad; ++i) {
+    const int pl = k.p_len[i], tl = k.t_len[i];
+    bm[i].plen = pl; bm[i].tlen = tl;
+    bm[i].p_woff = w; bad |= wfa::host_pack_seq(k.seqs + k.p_off[i], pl, bw + w, -1); w += (uint32_t)((pl + 15) >> 4);
+    bm[i].t_woff = w; bad |= wfa::host_pack_seq(k.seqs + k.t_off[i], tl, bw + w, -1); w += (uint32_t)((tl + 15) >> 4);
+    bco[i] = oo; oo += (int64_t)pl + tl;
+  }
+  if (bad) return false;
+  bco[k.n] = oo;
+  for (int j = 0; j < 4; ++j) bw[w + j] = 0;   // (the funnel shift reads one word ahead)
+  *words = w;
+  return true;
+}
+
+// band form, the kernel's arguments (for_mailbox: the resident kernel's instance outlives the call, so everything in its arguments is
+// sized for the longest pair of this path, not for this one).  1 = filled, 0 = the history does not fit: the batch path
+static int tiny_band_args(wfa_hip_aligner* al, const TinyCall& k, const TinyLayout& L, bool for_mailbox, wfa::BandArgs* out) {
+  uint8_t* const hd = al->tiny_hd;
+  wfa::BandArgs& ba = *out;
+  memset(&ba, 0, sizeof(ba));
+  ba.words = reinterpret_cast<const uint32_t*>(hd + L.b_words); ba.meta = reinterpret_cast<const WfaPairMeta*>(hd + L.b_meta);
+  ba.nwork = (uint32_t)k.n;
+  ba.score = reinterpret_cast<int32_t*>(hd + L.o_score); ba.status = reinterpret_cast<int32_t*>(hd + L.o_status);
+  ba.cigar_ops = hd + L.o_ops; ba.cigar_off = reinterpret_cast<const int64_t*>(hd + L.b_co);
+  ba.cigar_begin = reinterpret_cast<int64_t*>(hd + L.o_cb); ba.cigar_len = reinterpret_cast<int32_t*>(hd + L.o_cl);
+  fill_band_penalties(ba, al->dcfg, al->ncomp == 5);
+  fill_heuristic(ba, al->dcfg);
+  ba.xdrop = al->dcfg.xdrop; ba.scope = al->dcfg.scope;
+  ba.lds_words = for_mailbox ? ((1000 + 15) >> 4) + 5 : ((L.max_len + 15) >> 4) + 4;
+  ba.h16 = 1;
+  ba.slim = knob(al, K_BAND_SLIM, 1);   // (wf-adaptive or no heuristic: wfa_slim_kernel — a third of the instructions per score step)
+  fill_ends_free(ba, al->dcfg, true);
+  if (k.full) {
+    const int rec = ((al->ncomp != 5) ? 2 : 4) * 64 * TINY_BAND_NCH;
+    const long long records = std::max<long long>(256, (long long)((for_mailbox ? 1000 : L.max_len) * 0.9 * penalty_scale(al->dcfg)) / ba.g + 64);
+    ba.hist_stride = ((int64_t)records * rec + 63) & ~63ll;
+    // (one history slice per pair — 256 KB for 150 bp gap-affine — stays allocated for the aligner's lifetime: calls
+    // whose slices exceed 256 MB or the free memory take the batch path, and so does a call whose workspace cannot be had)
+    const size_t hist_bytes = (size_t)k.n * (size_t)ba.hist_stride * 4;
+    if (hist_bytes > ((size_t)256 << 20) || (int64_t)hist_bytes > free_budget(al)) return 0;
+    if (ensure_ws(al, hist_bytes) != WFA_HIP_OK) return 0;
+    ba.hist = al->ws;
+  }
+  return 1;
+}
+
+// band form, one pair through the resident kernel's mailbox: *seen = answered, score and status then stand in the pinned block where the
+// launch path's would
+static int tiny_band_mailbox(wfa_hip_aligner* al, const wfa::BandArgs& ba, const TinyCall& k, const TinyLayout& L, const uint32_t* one, size_t one_words, bool* seen) {
+  // (a batch run still in flight may be using the workspace this pair's history goes to)
+  if (k.full && al->ws_event_recorded) HIP_TRY(al, hipEventSynchronize(al->ws_event));
+  wfa::BandArgs mba = ba;
+  mba.done = nullptr;
+  int32_t sr = 0, st = WFA_INTERNAL_FALLBACK;
+  *seen = mailbox_call(al, mba, k.full, al->dcfg.heuristic != WFA_HEUR_NONE, one, one_words, &sr, &st) == 1;
+  if (*seen) {   // (the answer came in the mailbox's own word)
+    std::atomic_thread_fence(std::memory_order_acquire);
+    reinterpret_cast<int32_t*>(al->tiny_h + L.o_score)[0] = sr; reinterpret_cast<int32_t*>(al->tiny_h + L.o_status)[0] = st;
+  }
+  return WFA_HIP_OK;
+}
+
+// band form, ONE launch of the banded kernel.  1 = enqueued, 0 = a run-time shape that cannot be built: the batch path
+static int tiny_band_launch(wfa_hip_aligner* al, const wfa::BandArgs& ba, const TinyCall& k, hipStream_t stream) {
+  const unsigned rtc_failures = wfa::rtc_failure_count();
+  if (wfa::launch_band(ba, TINY_BAND_NCH, k.full, al->dcfg.heuristic != WFA_HEUR_NONE, true, (long long)k.n, stream) == 0) return 1;
+  if (al->dcfg.rtc && wfa::rtc_failure_count() != rtc_failures) {
+    // this aligner goes on without them (the batch path and the general kernel take the call)
+    (void)hipGetLastError();
+    al->dcfg.rtc = 0;
+    al->rtc_note = std::string("run-time kernels switched off for this aligner: ") + wfa::rtc_last_error();
+    return 0;
+  }
+  al->err = "band kernel launch failed"; return WFA_HIP_EDEVICE;
+}
+
+// band form, completion of a launch: a flag per pair in the pinned block, stored by the kernel at system scope after the pair's results;
+// the host polls the flags (a few microseconds after the last store) and only then falls back on the stream wait
+// (no event for the workspace: the call returns only after every pair's flag — stored behind its walk, the history's last reader — or
+// after the stream has drained)
+static int tiny_band_wait(wfa_hip_aligner* al, hipStream_t stream, const volatile int32_t* hdone, int64_t n, bool poll) {
+  bool seen = false;
+  if (poll) {
+    const double t_poll = now_ms();
+    for (;;) {
+      int64_t got = 0;
+      for (int64_t i = 0; i < n; ++i) got += (hdone[i] != 0);
+      if (got == n) { seen = true; break; }
+      if (now_ms() - t_poll > 20.0) break;   // (something is wrong or slow: the stream wait below decides)
+      __builtin_ia32_pause();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+  }
+  if (!seen) HIP_TRY(al, hipStreamSynchronize(stream));
+  return WFA_HIP_OK;
+}
+
+// Gap-affine / gap-affine-2p with an instantiated penalty shape, pure ACGT: ONE launch of the banded kernel (one wave per pair, 128
+// diagonals in registers).  The host packs the sequences to 2 bits into the pinned block; the kernel stages them in LDS straight from
+// there (no copy kernel), aligns, walks back in-kernel and writes results and op bytes into the pinned block.  A pair the window cannot
+// hold shows as status WFA_INTERNAL_FALLBACK and the call goes on to the general kernel.
+static int tiny_band(wfa_hip_aligner* al, const TinyCall& k, const TinyLayout& L) {
+  uint8_t* const h = al->tiny_h;
+  uint8_t* const hd = al->tiny_hd;
+  const int64_t n = k.n;
+  uint32_t w = 0;
+  if (!tiny_band_pack(k, L, h, &w)) return TINY_TO_GENERAL;
+  // one pair, gap-affine: the resident kernel takes it from its mailbox when it can (mailbox_call)
+  const bool try_mb = n == 1 && w + 4 <= 136 && al->ncomp == 3 && knob(al, K_BAND_SLIM, 1) != 0 && knob(al, K_NO_TINY_INLINE, 0) == 0 &&
+                      knob(al, K_MAILBOX, 1) != 0 && knob(al, K_NO_TINY_POLL, 0) == 0 && al->mb_failures < 3;
+  wfa::BandArgs ba;
+  if (tiny_band_args(al, k, L, try_mb, &ba) == 0) return TINY_TO_BATCH;
+  hipStream_t stream = al->stream;
+  { const int wrc = wait_for_workspace(al, stream); if (wrc != WFA_HIP_OK) return wrc; }
+  // (a status that is none of the kernel's: a wave that wrote nothing would be seen)
+  int32_t* hst = reinterpret_cast<int32_t*>(h + L.o_status);
+  for (int64_t i = 0; i < n; ++i) hst[i] = WFA_INTERNAL_FALLBACK;
+  volatile int32_t* hdone = reinterpret_cast<volatile int32_t*>(h + L.b_done);
+  const bool poll = knob(al, K_NO_TINY_POLL, 0) == 0;
+  for (int64_t i = 0; i < n; ++i) hdone[i] = 0;
+  ba.done = poll ? reinterpret_cast<int32_t*>(hd + L.b_done) : nullptr;
+  // one pair: lengths, op-region offsets and packed words ride in the kernel arguments (wfa_slim_kernel_one)
+  uint32_t one[8 + 136];
+  if (n == 1 && w + 4 <= 136 && ba.slim && knob(al, K_NO_TINY_INLINE, 0) == 0) {
+    memcpy(one, h + L.b_meta, 16); memcpy(one + 4, h + L.b_co, 16);
+    memcpy(one + 8, h + L.b_words, (size_t)(w + 4) * 4);
+    ba.one = one;
+  }
+  // the order of waits and fences: the workspace's event before a full-scope mailbox call; the acquire fence after the mailbox's answer
+  // and after polling; the stream wait only when nothing was seen
+  bool served = false;
+  if (try_mb && ba.one) { const int mrc = tiny_band_mailbox(al, ba, k, L, one, (size_t)8 + w + 4, &served); if (mrc != WFA_HIP_OK) return mrc; }
+  if (!served) {
+    { const int lrc = tiny_band_launch(al, ba, k, stream); if (lrc != 1) return lrc; }
+    { const int wrc = tiny_band_wait(al, stream, hdone, n, poll); if (wrc != WFA_HIP_OK) return wrc; }
+  }
+  for (int64_t i = 0; i < n; ++i) if (hst[i] == WFA_INTERNAL_FALLBACK) return TINY_TO_GENERAL;
+  tiny_copy_out(k, L, h, al->dcfg, reinterpret_cast<const int64_t*>(h + L.b_co));
+  return TINY_SERVED;
+}
+
+// The general kernel (raw bytes: any alphabet, every configuration) on the device copy of the input region, a workspace slice per pair.
+// TINY_TO_BATCH: an arena too small for a pair (the batch path grows it).
+static int tiny_general(wfa_hip_aligner* al, const TinyCall& k, const TinyLayout& L) {
+  const wfa_hip_config_t& c = al->cfg;
+  uint8_t* const h = al->tiny_h;
+  uint8_t* const hd = al->tiny_hd;
+  const int64_t n = k.n;
+  WfaPairMeta* meta = reinterpret_cast<WfaPairMeta*>(h + L.o_meta);
+  int64_t* pb = reinterpret_cast<int64_t*>(h + L.o_pb); int64_t* tb = reinterpret_cast<int64_t*>(h + L.o_tb); int64_t* co = reinterpret_cast<int64_t*>(h + L.o_co);
   int64_t bo = 0, oo = 0;
   for (int64_t i = 0; i < n; ++i) {
-    const int pl = p_len[i], tl = t_len[i];
+    const int pl = k.p_len[i], tl = k.t_len[i];
     meta[i].p_woff = 0; meta[i].t_woff = 0; meta[i].plen = pl; meta[i].tlen = tl;
-    pb[i] = bo; memcpy(h + o_blob + bo, seqs + p_off[i], (size_t)pl); bo += (pl + 15) & ~15;
-    tb[i] = bo; memcpy(h + o_blob + bo, seqs + t_off[i], (size_t)tl); bo += (tl + 15) & ~15;
+    pb[i] = bo; memcpy(h + L.o_blob + bo, k.seqs + k.p_off[i], (size_t)pl); bo += (pl + 15) & ~15;
+    tb[i] = bo; memcpy(h + L.o_blob + bo, k.seqs + k.t_off[i], (size_t)tl); bo += (tl + 15) & ~15;
     co[i] = oo; oo += (int64_t)pl + tl;
   }
   co[n] = oo;
   // geometry of the general kernel (plan_general / initial_arena_ints for these few pairs)
-  int threads = (max_len > 2000 && c.heuristic != WFA_HEUR_ADAPTIVE) ? 256 : 64;
+  int threads = (L.max_len > 2000 && c.heuristic != WFA_HEUR_ADAPTIVE) ? 256 : 64;
   threads = std::max(64, std::min(512, (knob(al, K_THREADS, threads) / 64) * 64));
   int64_t stride;
-  if (full) {
+  if (k.full) {
     const int mi = 2 * al->ncomp + 4;
-    stride = std::max<int64_t>((int64_t)max_len * (al->ncomp * 64 + mi) / 4 + (int64_t)max_width * al->ncomp * 4 + 4096 * mi, 1 << 14);
+    stride = std::max<int64_t>((int64_t)L.max_len * (al->ncomp * 64 + mi) / 4 + (int64_t)L.max_width * al->ncomp * 4 + 4096 * mi, 1 << 14);
   } else {
-    stride = (int64_t)al->dcfg.scope * al->ncomp * max_width;
+    stride = (int64_t)al->dcfg.scope * al->ncomp * L.max_width;
   }
   stride = (stride + 63) & ~63ll;
   int rc = ensure_ws(al, (size_t)n * stride * 4);
   if (rc != WFA_HIP_OK) return rc;
   hipStream_t stream = al->stream;
-  if (al->ws_event_recorded && al->ws_last_stream != stream) HIP_TRY(al, hipStreamWaitEvent(stream, al->ws_event, 0));
-  const int n16 = (int)(in_bytes / 16);
+  { const int wrc = wait_for_workspace(al, stream); if (wrc != WFA_HIP_OK) return wrc; }
+  const int n16 = (int)(L.in_bytes / 16);
   hipLaunchKernelGGL(wfa_tiny_copy_kernel, dim3(std::min(64, (n16 + 255) / 256)), dim3(256), 0, stream,
                      reinterpret_cast<uint4*>(al->tiny_d), reinterpret_cast<const uint4*>(hd), n16);
   WfaKernelArgs a;
   memset(&a, 0, sizeof(a));
-  a.bytes = al->tiny_d + o_blob; a.meta = reinterpret_cast<const WfaPairMeta*>(al->tiny_d + o_meta);
-  a.p_boff = reinterpret_cast<const int64_t*>(al->tiny_d + o_pb); a.t_boff = reinterpret_cast<const int64_t*>(al->tiny_d + o_tb);
-  a.cigar_off = reinterpret_cast<const int64_t*>(al->tiny_d + o_co);
+  a.bytes = al->tiny_d + L.o_blob; a.meta = reinterpret_cast<const WfaPairMeta*>(al->tiny_d + L.o_meta);
+  a.p_boff = reinterpret_cast<const int64_t*>(al->tiny_d + L.o_pb); a.t_boff = reinterpret_cast<const int64_t*>(al->tiny_d + L.o_tb);
+  a.cigar_off = reinterpret_cast<const int64_t*>(al->tiny_d + L.o_co);
   a.nwork = (uint32_t)n;
-  a.score = reinterpret_cast<int32_t*>(hd + o_score); a.status = reinterpret_cast<int32_t*>(hd + o_status);
-  a.cigar_begin = reinterpret_cast<int64_t*>(hd + o_cb); a.cigar_len = reinterpret_cast<int32_t*>(hd + o_cl); a.cigar_ops = hd + o_ops;
+  a.score = reinterpret_cast<int32_t*>(hd + L.o_score); a.status = reinterpret_cast<int32_t*>(hd + L.o_status);
+  a.cigar_begin = reinterpret_cast<int64_t*>(hd + L.o_cb); a.cigar_len = reinterpret_cast<int32_t*>(hd + L.o_cl); a.cigar_ops = hd + L.o_ops;
   a.ws = al->ws; a.ws_stride = stride; a.cfg = al->gcfg;
   // (no overflow list: an arena that is too small shows as status WFA_INTERNAL_OVERFLOW below and the call takes the batch path)
   static uint32_t* const no_list = nullptr;
   a.fb_list = no_list; a.fb_count = nullptr;
-  if (wfa::launch_general_any(al->gncomp, false, full, false, a, (int)n, threads, stream) != 0) { al->err = "general kernel launch failed"; return WFA_HIP_EDEVICE; }
+  if (wfa::launch_general_any(al->gncomp, false, k.full, false, a, (int)n, threads, stream) != 0) { al->err = "general kernel launch failed"; return WFA_HIP_EDEVICE; }
   HIP_TRY(al, hipEventRecord(al->ws_event, stream));
   al->ws_event_recorded = true; al->ws_last_stream = stream;
   HIP_TRY(al, hipStreamSynchronize(stream));
-  const int32_t* hs = reinterpret_cast<const int32_t*>(h + o_score); const int32_t* hst = reinterpret_cast<const int32_t*>(h + o_status);
-  for (int64_t i = 0; i < n; ++i) if (hst[i] == WFA_STATUS_OOM && full) return 0;   // arena too small for this pair: the batch path grows it
-  const int64_t* hcb = reinterpret_cast<const int64_t*>(h + o_cb); const int32_t* hcl = reinterpret_cast<const int32_t*>(h + o_cl);
-  for (int64_t i = 0; i < n; ++i) {
-    score[i] = tiny_score(al->gcfg, hs[i], hst[i], p_len[i], t_len[i]); status[i] = hst[i];
-    if (cigar_len) cigar_len[i] = full ? hcl[i] : 0;
-    if (cigar_begin) cigar_begin[i] = 0;
-    if (full && cigar_ops) {
-      const int64_t rel = hcb[i] - co[i];
-      if (hcl[i] > 0) memcpy(cigar_ops + cigar_off[i] + rel, h + o_ops + hcb[i], (size_t)hcl[i]);
-      cigar_begin[i] = cigar_off[i] + rel;
-    }
+  const int32_t* hst = reinterpret_cast<const int32_t*>(h + L.o_status);
+  for (int64_t i = 0; i < n; ++i) if (hst[i] == WFA_STATUS_OOM && k.full) return TINY_TO_BATCH;   // arena too small for this pair: the batch path grows it
+  tiny_copy_out(k, L, h, al->gcfg, co);
+  return TINY_SERVED;
+}
+
+// The single-call path: the band form where it applies, the general form for what it hands on or does not take.
+static int align_tiny(wfa_hip_aligner* al, int64_t n, const uint8_t* seqs, const int64_t* p_off, const int32_t* p_len,
+                      const int64_t* t_off, const int32_t* t_len, int32_t* score, int32_t* status, uint8_t* cigar_ops,
+                      const int64_t* cigar_off, int64_t* cigar_begin, int32_t* cigar_len) {
+  const TinyCall k{n, seqs, p_off, p_len, t_off, t_len, score, status, cigar_ops, cigar_off, cigar_begin, cigar_len, al->cfg.scope == WFA_SCOPE_FULL};
+  TinyLayout L;
+  { const int lrc = tiny_layout(al, k, &L); if (lrc != 1) return lrc; }
+  HIP_TRY(al, hipSetDevice(al->device));
+  if (!al->tiny_h) {
+    HIP_TRY(al, hipHostMalloc((void**)&al->tiny_h, TINY_BLOCK_BYTES, hipHostMallocMapped));
+    HIP_TRY(al, hipMalloc((void**)&al->tiny_d, TINY_IN_BYTES));
   }
-  return 1;
+  if (!al->tiny_hd) HIP_TRY(al, hipHostGetDevicePointer((void**)&al->tiny_hd, al->tiny_h, 0));   // the pinned block as the device sees it
+  if (L.band_form) { const int brc = tiny_band(al, k, L); if (brc != TINY_TO_GENERAL) return brc; }
+  if (!L.general_fits) return TINY_TO_BATCH;   // (more pairs than the general-kernel form takes: the batch path)
+  return tiny_general(al, k, L);
 }
 
 extern "C" int wfa_hip_align_batch(wfa_hip_aligner_t* al, int64_t n, const uint8_t* seqs,
@@ -4522,14 +4679,12 @@ struct WindowPairs {
 // itself are the descriptor's (IndexedPairs, WindowPairs); its per-pair calls inline into the two passes.
 template <class Desc>
 static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, Desc& D) {
-  b->cfg = al->cfg; b->dcfg = al->dcfg; b->ncomp = al->ncomp; b->gcfg = al->gcfg; b->gncomp = al->gncomp;
+  batch_adopt_config(al, b);
   const wfa_hip_config_t& c = b->cfg;
-  const bool all_bytes = c.wildcard >= 0 && wildcard_in_acgt(c.wildcard);
-  if (c.wildcard >= 0 && !all_bytes) { b->wild = c.wildcard; b->dcfg.wildcard = -1; b->gcfg.wildcard = -1; }   // (as batch_build)
+  const bool all_bytes = c.wildcard >= 0 && b->wild < 0;   // (a wildcard among ACGT: every pair on its bytes)
   b->al = al;
   b->n = n;
   const bool full = (c.scope == WFA_SCOPE_FULL);
-  const bool ef = (c.span == WFA_SPAN_ENDSFREE);
   const int64_t np_set = D.P->n, nt_set = D.T->n;
   const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, std::thread::hardware_concurrency()), n / 65536));
   auto part_lo = [&](int t) -> int64_t { return t >= nthr ? n : (n * t / nthr) & ~(int64_t)(WFA_PAIRS_CHUNK - 1); };
@@ -4547,7 +4702,7 @@ static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, De
       if (const int bad = D.check(q, all_bytes, &p)) { pt.err = bad; pt.bad = q; return; }
       const int pl = p.pl, tl = p.tl;
       // wavefront_align.c:86-102, per listed pair as batch_build: against what is aligned (the sequences, or the windows)
-      if (ef && (c.pattern_begin_free > pl || c.pattern_end_free > pl || c.text_begin_free > tl || c.text_end_free > tl)) { pt.err = 3; pt.bad = q; return; }
+      if (free_ends_exceed(c, pl, tl)) { pt.err = PART_ENDS_FREE; pt.bad = q; return; }
       if (p.slot) pt.words += (uint64_t)(((pl + 15) >> 4) + ((tl + 15) >> 4));
       else pt.any_long = true;
       pt.max_gen = std::max(pt.max_gen, p.gen_words);
@@ -4559,13 +4714,7 @@ static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, De
       pt.any_opt |= p.opt;
     }
   };
-  auto run_threads = [&](auto&& fn) {
-    std::vector<std::thread> th;
-    for (int t = 1; t < nthr; ++t) th.emplace_back(fn, t);
-    fn(0);
-    for (auto& x : th) x.join();
-  };
-  run_threads(pass1);
+  run_parts(nthr, nthr, pass1);   // (a thread per part)
   uint64_t slot_words = 0;
   int64_t nbytes = 0, slot_bytes = 0;
   int max_gen = 0;
@@ -4580,7 +4729,7 @@ static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, De
                (long long)pt.bad, (int)D.i[pt.bad], (int)D.j[pt.bad], (long long)np_set, (long long)nt_set);
       al->err = buf; return WFA_HIP_EINVAL;
     }
-    if (pt.err == 3) { al->err = "Ends-free parameters must be not larger than the sequences"; return WFA_HIP_EINVAL; }
+    if (pt.err == PART_ENDS_FREE) { al->err = part_error_message(pt.err); return WFA_HIP_EINVAL; }
     if (pt.err) { al->err = D.refusal(pt.err, pt.bad); return WFA_HIP_EINVAL; }
     wbase[(size_t)t] = slot_words; obase[(size_t)t] = b->ops_bytes; bbase[(size_t)t] = nbytes; sbase[(size_t)t] = slot_bytes;
     slot_words += pt.words; nbytes += pt.nbytes; slot_bytes += pt.slot_bytes;
@@ -4621,7 +4770,7 @@ static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, De
       }
     }
   };
-  run_threads(pass2);
+  run_parts(nthr, nthr, pass2);
   CrossScratch sc{al};   // (declared behind the host tables above: it waits for the stream before they go)
   const size_t nn = (size_t)std::max<int64_t>(n, 1);
   { const int arc = batch_alloc_common(al, b, table_words + slot_words + 64, 64); if (arc != WFA_HIP_OK) return arc; }
@@ -4634,12 +4783,7 @@ static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, De
       { const int src = D.byte_store(al, b, plan); if (src != WFA_HIP_OK) return src; }
       HIP_TRY(al, pool_alloc(al, (void**)&b->d_pboff, nn * sizeof(int64_t)));
       HIP_TRY(al, pool_alloc(al, (void**)&b->d_tboff, nn * sizeof(int64_t)));
-      HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_bytes, lb.size() * sizeof(uint32_t)));
-      HIP_TRY(al, hipMemcpyAsync(b->d_list_bytes, lb.data(), lb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
-      if (!lp.empty()) {
-        HIP_TRY(al, pool_alloc(al, (void**)&b->d_list_packed, lp.size() * sizeof(uint32_t)));
-        HIP_TRY(al, hipMemcpyAsync(b->d_list_packed, lp.data(), lp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
-      }
+      { const int lrc = upload_work_lists(al, b, lp, lb, true); if (lrc != WFA_HIP_OK) return lrc; }
     }
     { const int grc = D.generate(al, b, sc, plan); if (grc != WFA_HIP_OK) return grc; }
   }

@@ -459,3 +459,49 @@ def test_few_long_reads_take_the_pinned_host_packed_upload(gpu, monkeypatch):
     s, st, _ = ma.align_batch(batch, False)
     ma.close()
     assert np.array_equal(s, res["ring"][0]) and np.array_equal(st, res["ring"][1])
+
+
+def test_long_reads_whose_block_exceeds_a_ring_slot_leave_the_host_packed_upload(gpu, monkeypatch, capfd):
+    """A batch of many bases starts in the host-packed form; when 64 pairs do not fit one slot of the pinned ring the build
+    leaves it for the ASCII ring + device pack, and only then looks at the byte offsets.  64 pairs of 262 144 bases (32 Mi
+    bases: the threshold at the smallest pair count that takes the ring) with WFA_HIP_PIPE_CHUNK=1: a block is 8 MB of packed
+    words against 1 MB slots.  Every text is its pattern with one substitution, so a pair ends at the score of one mismatch.
+    The build's timing lines name the form that ran (the device pack's line, not the host pack's).  The same results without
+    the ring (WFA_HIP_NO_PIPE=1), the oracle's on 4 pairs, and a negative offset is refused by the build's late offsets pass
+    (wfa_hip_batch_create: wfa_hip_align_batch would refuse it in its check for the single-call path first)."""
+    n, length = 64, 262144
+    rng = np.random.default_rng(2621)
+    seqs = np.empty((n, 2, length), np.uint8)
+    seqs[:, 0] = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, (n, length), dtype=np.uint8)]
+    seqs[:, 1] = seqs[:, 0]
+    rows, pos = np.arange(n), (np.arange(n) * 4099 + 17) % length
+    seqs[rows, 1, pos] = np.frombuffer(b"CGTA", np.uint8)[np.searchsorted(np.frombuffer(b"ACGT", np.uint8), seqs[rows, 0, pos])]
+    p_off = rows.astype(np.int64) * 2 * length
+    batch = dict(seqs=seqs.reshape(-1), p_off=p_off, p_len=np.full(n, length, np.int32),
+                 t_off=p_off + length, t_len=np.full(n, length, np.int32))
+    assert int(batch["p_len"].sum() + batch["t_len"].sum()) >= (32 << 20)
+    oc, nc = common.configs_pair(span="end-to-end", scope="score")
+    monkeypatch.setenv("WFA_HIP_PIPE_CHUNK", "1")
+    monkeypatch.setenv("WFA_HIP_TIMING", "1")
+    al = _native.Aligner(nc)     # (the knobs are read when the aligner is created)
+    capfd.readouterr()
+    ring = al.align_batch(batch, False)
+    lines = capfd.readouterr().err
+    assert "[wfa_hip] H2D + pack + flags D2H" in lines and "[wfa_hip] host pack + H2D enqueue" not in lines, lines
+    # the late offset check, through the raw C ABI (the Python wrapper refuses such a batch before the call)
+    a_seqs, a_poff, a_plen, a_toff, a_tlen, _ = _native._check_batch(batch)
+    bad_off = a_poff.copy()
+    bad_off[37] = -1
+    b = _native.lib().wfa_hip_batch_create(al._h, n, _native._ptr(a_seqs), _native._ptr(bad_off), _native._ptr(a_plen), _native._ptr(a_toff),
+                                           _native._ptr(a_tlen))
+    assert not b and "negative length or offset" in al.error()
+    al.close()
+    monkeypatch.delenv("WFA_HIP_TIMING")
+    monkeypatch.setenv("WFA_HIP_NO_PIPE", "1")
+    al = _native.Aligner(nc)
+    plain = al.align_batch(batch, False)
+    al.close()
+    assert np.array_equal(ring[0], plain[0]) and np.array_equal(ring[1], plain[1])
+    sel = np.array([0, 21, 42, 63])
+    o = loader.run(loader.oracle(), oc, datagen.subset(batch, sel), want_cigar=False)
+    assert np.array_equal(ring[0][sel], o["score"]) and np.array_equal(ring[1][sel], o["status"])
