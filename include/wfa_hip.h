@@ -639,6 +639,77 @@ int wfa_hip_place_host(int64_t nreads, int64_t nhits, const int32_t* i, const in
                        const int32_t* status, const int32_t* text_start, const int32_t* text_end, int32_t min_score, int32_t full_gap,
                        int32_t* rows /* nreads x 8 */, uint8_t* flags /* nhits, nullable */, char* msg, size_t msg_cap);
 
+/* ---- pairing: one row per fragment of two reads from the hits of a placer ---------------------------------- */
+
+/*
+ * Short reads come in pairs, and the mate is the strongest placement evidence there is: a read inside an exact repeat has mapq 0 on
+ * its own, whichever copy its mate sits next to.  The join of the two mates' hits is made where the records lie, after the group and
+ * place passes of the same placer; 48 bytes per fragment and 1 byte per hit cross PCIe.  Integers only, nothing depends on scheduling.
+ *
+ * HIT, ELIGIBLE, PRIMARY, SAME LOCUS and the single-end row are those of "placement"; se(r) is read r's single-end row under the same
+ * min_score and full_gap, and a hit's single-end flag its byte there.
+ * FRAGMENT.  Fragment f is two distinct reads, mate1[f] and mate2[f]; with both arrays NULL, mate1[f] = 2 f and mate2[f] = 2 f + 1,
+ * and 2 * nfrag <= nreads.  A read belongs to at most one fragment.  Reads in no fragment are untouched by the pairing: their
+ * pair_flags equal their single-end flags.
+ * PAIRING.  (h, g), h an eligible hit of mate 1 and g an eligible hit of mate 2.  It is PROPER iff
+ *     j_h == j_g && reverse_h != reverse_g;
+ *     te_h > ts_h && te_g > ts_g (both intervals non-empty);
+ *     with F the one of reverse == 0 and R the other:  ts_F <= ts_R && te_F <= te_R  (the mates face each other, neither extends
+ *     past the other);
+ *     min_insert <= te_R - ts_F <= max_insert                                                                     (64-bit)
+ * with 0 <= min_insert <= max_insert.  `insert` of a pairing is te_R - ts_F; its PAIR SCORE is score_h + score_g in 64 bits, saturated
+ * to [INT32_MIN + 1, INT32_MAX] where it is returned as int32 (nowhere else).
+ * BEST.  The proper pairing of greatest pair score; on a tie the smallest hit number of h, then of g.
+ * PROPER FRAGMENT.  proper = 1 iff both mates have an eligible hit, a proper pairing exists and
+ *     pairscore(best) + unpaired >= se(mate1).score + se(mate2).score                                   (64-bit, unpaired >= 0)
+ * `unpaired` being the number of score points a mapper gives up to keep the mates together.  When proper, the CHOSEN hits are (h, g)
+ * of the best pairing; otherwise the single-end primaries, -1 where there is none.
+ * SAME PLACE.  A proper pairing (h', g') is at the place of the chosen (h, g) iff (h' == h or h' is at h's locus by the SAME LOCUS
+ * test with h in the role of p) and the same holds for g' and g.
+ * RUNNER-UP.  `second` is the greatest pair score among the proper pairings not at the chosen place, `ties` the number of those whose
+ * pair score equals the chosen one's (0 when proper = 0).  `pairings` is the number of proper pairings, the chosen one included; it is
+ * reported even when proper = 0.
+ * PAIR MAPQ.  60 without a runner-up; otherwise min(60, 60 * (pairscore - second) / full_gap), a 64-bit floor division on the
+ * unsaturated values; 0 when proper = 0.
+ * MATE MAPQ.  When proper, for mate m with chosen hit c: max(pair mapq, se(m).mapq) if c's single-end flag is 3 or 2 (c is that read's
+ * own primary or at its locus), else the pair mapq.  When not proper, se(m).mapq.
+ * OVERFLOW.  With E1, E2 the column `hits` of the two single-end rows: a fragment with E1 * E2 > WFA_HIP_PAIR_MAX_PAIRINGS is not
+ * joined and gets overflow = 1, proper = 0, pairings = 0.  The bound is why A FRAGMENT IS SERVED BY ONE WAVE can stay the design: at
+ * most WFA_HIP_PAIR_MAX_PAIRINGS / 64 rounds of eligible pairings a pass.
+ *
+ * PER FRAGMENT WFA_HIP_PAIR_COLS int32: hit1, hit2 (the chosen hits), proper, score, second, mapq, mapq1, mapq2, insert, pairings,
+ * ties, overflow.  score and second are INT32_MIN when proper = 0, second is INT32_MIN without a runner-up, insert is 0 when
+ * proper = 0.
+ * PER HIT one byte, pair_flags: the single-end flag relative to the CHOSEN hit c of its read: 3 = c, 2 = eligible at c's locus,
+ * 1 = eligible elsewhere, 0 = not eligible.
+ *
+ * wfa_hip_placer_run_pairs groups ALL hits added so far (the grouping is shared with wfa_hip_placer_run), reduces every read as
+ * wfa_hip_placer_run does and then joins every fragment: one wave per fragment over the slots of the two groups (csrc/wfa_place.hpp).
+ * rows (nreads x WFA_HIP_PLACE_COLS), flags and pair_flags (wfa_hip_placer_count bytes each) are nullable; pair_rows receives
+ * nfrag x WFA_HIP_PAIR_COLS int32.  8 bytes per fragment are uploaded (none for interleaved mates), 48 per fragment downloaded plus the
+ * nullable outputs asked for.  It may be called before, after or between calls of wfa_hip_placer_run and adds, under the same rules;
+ * wfa_hip_placer_kernel_ms then covers the pair kernel too.  Two runs give identical bytes.
+ * WFA_HIP_EINVAL, nothing launched, nothing written (wfa_hip_last_error names the first offending position and its values): what
+ * wfa_hip_placer_run refuses; nfrag < 0; min_insert < 0, max_insert < min_insert or unpaired < 0; a mate outside [0, nreads);
+ * mate1[f] == mate2[f]; a read named by two fragments; exactly one of mate1 / mate2 NULL; 2 * nfrag > nreads with both NULL; a NULL
+ * pair_rows with nfrag > 0.
+ */
+#define WFA_HIP_PAIR_COLS 12   /* hit1, hit2, proper, score, second, mapq, mapq1, mapq2, insert, pairings, ties, overflow */
+#define WFA_HIP_PAIR_MAX_PAIRINGS 65536
+int  wfa_hip_placer_run_pairs(wfa_hip_placer_t* placer, int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert,
+                              int32_t unpaired, int64_t nfrag, const int32_t* mate1 /* nullable */, const int32_t* mate2 /* nullable */,
+                              int32_t* rows /* nreads x 8, nullable */, uint8_t* flags /* nhits, nullable */,
+                              int32_t* pair_rows /* nfrag x 12 */, uint8_t* pair_flags /* nhits, nullable */);
+
+/* Host only, needs no GPU: the rule above in plain C++ over arrays of nhits hits in hit-number order (reverse nullable: forward): what
+ * wfa_hip_placer_add_hits + wfa_hip_placer_run_pairs give.  Returns WFA_HIP_OK, or WFA_HIP_EINVAL (nothing written; msg as for
+ * wfa_hip_place_host) for whatever wfa_hip_place_host refuses and for the refusals of wfa_hip_placer_run_pairs. */
+int wfa_hip_pair_host(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse, const int32_t* score,
+                      const int32_t* status, const int32_t* text_start, const int32_t* text_end, int32_t min_score, int32_t full_gap,
+                      int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1 /* nullable */,
+                      const int32_t* mate2 /* nullable */, int32_t* rows /* nreads x 8, nullable */, uint8_t* flags /* nhits, nullable */,
+                      int32_t* pair_rows /* nfrag x 12 */, uint8_t* pair_flags /* nhits, nullable */, char* msg, size_t msg_cap);
+
 /* ---- seed finder: an exact-match k-mer index over a text set, candidate windows for every read ------------ */
 
 /*

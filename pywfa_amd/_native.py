@@ -74,6 +74,7 @@ SYMBOLS = [
     "wfa_hip_pileup_calls", "wfa_hip_pileup_sites", "wfa_hip_calls_host", "wfa_hip_sites_host",
     "wfa_hip_placer_create", "wfa_hip_placer_add", "wfa_hip_placer_add_hits", "wfa_hip_placer_run", "wfa_hip_placer_count",
     "wfa_hip_placer_clear", "wfa_hip_placer_kernel_ms", "wfa_hip_placer_destroy", "wfa_hip_place_host",
+    "wfa_hip_placer_run_pairs", "wfa_hip_pair_host",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
@@ -88,6 +89,9 @@ SITE_COLUMNS = ("j", "pos", "ref", "alt", "depth", "ref_count", "alt_count", "in
 PLACE_COLS = 8
 PLACE_COLUMNS = ("hit", "score", "second", "mapq", "hits", "ties", "text_start", "text_end")
 PLACE_NOT_ELIGIBLE, PLACE_OTHER_LOCUS, PLACE_SAME_LOCUS, PLACE_PRIMARY = 0, 1, 2, 3   # the flag byte of a hit
+PAIR_COLS = 12
+PAIR_COLUMNS = ("hit1", "hit2", "proper", "score", "second", "mapq", "mapq1", "mapq2", "insert", "pairings", "ties", "overflow")
+PAIR_MAX_PAIRINGS = 65536
 INT32_MIN = -2**31
 SEED_MAX_N, SEED_MAX_HITS = 16, 4096
 SEED_KEYS = ("j", "reverse", "text_start", "text_len", "hits")   # the int32 arrays of a seed query, and overflow (uint8)
@@ -223,6 +227,8 @@ def lib():
     L.wfa_hip_placer_destroy.argtypes = [vp]
     L.wfa_hip_placer_destroy.restype = None
     L.wfa_hip_place_host.argtypes = [i64, i64] + [vp] * 7 + [i32, i32, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
+    L.wfa_hip_placer_run_pairs.argtypes = [vp] + [i32] * 5 + [i64] + [vp] * 6
+    L.wfa_hip_pair_host.argtypes = [i64, i64] + [vp] * 7 + [i32] * 5 + [i64] + [vp] * 6 + [ctypes.c_char_p, ctypes.c_size_t]
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -604,6 +610,43 @@ def place_host(nreads, i, j, reverse, score, status, text_start, text_end, min_s
     return rows, flags
 
 
+def _mate_arrays(mates):
+    """``(nfrag, mate1, mate2)`` of the ``mates`` argument of the pairing entries: an int (that many interleaved fragments, no arrays)
+    or an (F, 2) integer array of read indices (two contiguous int32 columns)."""
+    if isinstance(mates, (int, np.integer)) and not isinstance(mates, bool):
+        return int(mates), None, None
+    m = np.asarray(mates)
+    if m.ndim != 2 or m.shape[1] != 2 or (m.size and not np.issubdtype(m.dtype, np.integer)):
+        raise ValueError(f"mates: an integer array of shape (F, 2) or a number of interleaved fragments, got shape {m.shape} of {m.dtype}")
+    if m.size and (m.min() < -2**31 or m.max() >= 2**31):
+        raise ValueError("mates: an index does not fit 32 bits")
+    return m.shape[0], np.ascontiguousarray(m[:, 0], dtype=np.int32), np.ascontiguousarray(m[:, 1], dtype=np.int32)
+
+
+def pair_host(nreads, i, j, reverse, score, status, text_start, text_end, mates, min_score=INT32_MIN, full_gap=1, min_insert=0,
+              max_insert=1000, unpaired=0):
+    """wfa_hip_pair_host (host only): ``(rows, flags, pair_rows, pair_flags)`` of the pairing rule over a list of hits in hit-number
+    order — rows and flags as ``place_host`` gives them, pair_rows int32 of shape (F, 12) in the columns PAIR_COLUMNS, pair_flags uint8
+    per hit; what ``Placer.add_hits`` + ``Placer.run_pairs`` give.  ``mates``: an (F, 2) integer array of read indices, or an int F:
+    interleaved, fragment f being reads 2 f and 2 f + 1."""
+    a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
+    nfrag, m1, m2 = _mate_arrays(mates)
+    nreads = int(nreads)
+    rows = np.zeros((max(nreads, 0), PLACE_COLS), np.int32)
+    flags = np.zeros(n, np.uint8)
+    pair_rows = np.zeros((max(nfrag, 0), PAIR_COLS), np.int32)
+    pair_flags = np.zeros(n, np.uint8)
+    msg = ctypes.create_string_buffer(256)
+    p = lambda v: _ptr(v) if v is not None and v.size else None   # noqa: E731
+    mp = lambda v: None if v is None else _ptr(v)                 # noqa: E731  (an empty mate array is still "given")
+    rc = lib().wfa_hip_pair_host(nreads, n, p(a["i"]), p(a["j"]), p(a["reverse"]), p(a["score"]), p(a["status"]), p(a["text_start"]),
+                                 p(a["text_end"]), int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired), nfrag,
+                                 mp(m1), mp(m2), p(rows), p(flags), p(pair_rows), p(pair_flags), msg, 256)
+    if rc != OK:
+        raise ValueError(f"wfa_hip_pair_host: {msg.value.decode()}")
+    return rows, flags, pair_rows, pair_flags
+
+
 def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16, pad=16, max_hits=2048, w=None):
     """wfa_hip_seeds_host (host only): the row ``SeedIndex.query`` holds for ONE read (bytes) against the texts (a list of bytes, or a
     blob dict(seqs=, off=, len=) made once for many reads): dict of int32[n] ``j`` / ``reverse`` / ``text_start`` / ``text_len`` /
@@ -960,6 +1003,23 @@ class Placer:
         if rc != OK:
             self.aligner._raise(rc, "wfa_hip_placer_run")
         return rows, fl
+
+    def run_pairs(self, mates, min_score=INT32_MIN, full_gap=1, min_insert=0, max_insert=1000, unpaired=0, rows=True, flags=True,
+                  pair_flags=True):
+        """wfa_hip_placer_run_pairs over every hit added so far: ``(rows, flags, pair_rows, pair_flags)`` — rows and flags as ``run``
+        gives them, pair_rows int32 of shape (F, 12) in the columns PAIR_COLUMNS, pair_flags uint8 per hit; None for each of rows,
+        flags and pair_flags that is False.  ``mates``: an (F, 2) integer array of read indices, or an int F: interleaved."""
+        nfrag, m1, m2 = _mate_arrays(mates)
+        r = np.zeros((self.nreads, PLACE_COLS), np.int32) if rows else None
+        fl = np.zeros(len(self), np.uint8) if flags else None
+        pr = np.zeros((max(nfrag, 0), PAIR_COLS), np.int32)
+        pf = np.zeros(len(self), np.uint8) if pair_flags else None
+        p = lambda v: _ptr(v) if v is not None and v.size else None   # noqa: E731
+        rc = lib().wfa_hip_placer_run_pairs(self._h, int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired), nfrag,
+                                            None if m1 is None else _ptr(m1), None if m2 is None else _ptr(m2), p(r), p(fl), p(pr), p(pf))
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_placer_run_pairs")
+        return r, fl, pr, pf
 
     def kernel_ms(self):
         ms = ctypes.c_float(0)

@@ -1284,6 +1284,93 @@ class WavefrontAligner:
             for s in mine:
                 s.close()
 
+    def place_pairs(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
+                    text_len=None, reverse=None, mates=None, min_insert=0, max_insert=1000, unpaired=None, min_score=None,
+                    full_gap=None):
+        """``place_windows`` for paired-end reads (same arguments, same checks; either scope): the listed windows are aligned, every
+        read is placed on its own, and then the hits of the two mates of every fragment are joined on the GPU.  The rule is that of
+        include/wfa_hip.h ("pairing"), integers only.  ``mates``: an (F, 2) integer array of indices into ``patterns``, fragment f
+        being the reads ``mates[f, 0]`` (mate 1) and ``mates[f, 1]`` (mate 2), no read in two fragments; None: interleaved, reads
+        2 f and 2 f + 1, ``len(patterns)`` even.  A pairing of an eligible hit of each mate is proper when the two lie on one text
+        and on opposite strands, the forward one starts and ends no later than the reverse one (they face each other, neither
+        extends past the other) and ``min_insert <= insert <= max_insert``, ``insert`` running from the forward hit's start to the
+        reverse hit's end.  A fragment is proper when its best proper pairing is at most ``unpaired`` score points behind the two
+        single-end primaries taken together (None: ``full_gap``); its reads then go to that pairing, otherwise to their single-end
+        primaries.  ``mapq`` of a proper fragment is 60 without a proper pairing at another place, else
+        min(60, 60 * (score - second) // full_gap); a mate's own mapq is never below it.  A fragment with more than 65 536 pairings
+        of eligible hits is not joined (``overflow``).  The interval of a hit is the aligned core under scope full and the WHOLE
+        TEXT WINDOW under scope score: there ``insert`` and the order test are as coarse as the windows are, so windows that are
+        much longer than the reads call for wider insert bounds.
+
+        Returns what ``place_windows`` returns, plus ``pair_flag`` (uint8 per hit: the flag relative to the hit its read was
+        given, 3 that hit, 2 at its locus, 1 eligible elsewhere, 0 not eligible; the single-end flag for a read in no proper
+        fragment) and ``pairs``, a dict of int32 arrays of length F: hit1, hit2 (list positions, -1 without one), proper, score,
+        second (-2**31 when not proper or without a runner-up), mapq, mapq1, mapq2, insert, pairings (proper pairings), ties,
+        overflow.  48 bytes per fragment more come back than from ``place_windows``, and a byte per hit."""
+        for name, v in (("min_score", min_score), ("full_gap", full_gap), ("min_insert", min_insert), ("max_insert", max_insert),
+                        ("unpaired", unpaired)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise ValueError(f"{name} must be an integer{'' if name.endswith('insert') else ' or None'}, got {v!r}")
+        if min_score is not None and not -2**31 <= int(min_score) < 2**31:
+            raise ValueError(f"min_score = {min_score} does not fit 32 bits")
+        if full_gap is None:
+            full_gap = 6 * int(self._cfg.mismatch) if self._cfg.distance >= 2 else 6
+        if not 1 <= int(full_gap) < 2**31:
+            raise ValueError(f"full_gap = {full_gap} is out of range (at least 1)")
+        if min_insert is None or max_insert is None or not 0 <= int(min_insert) <= int(max_insert) < 2**31:
+            raise ValueError(f"min_insert = {min_insert}, max_insert = {max_insert} are out of range (0 <= min_insert <= max_insert)")
+        if unpaired is None:
+            unpaired = full_gap
+        if not 0 <= int(unpaired) < 2**31:
+            raise ValueError(f"unpaired = {unpaired} is out of range (at least 0)")
+        patterns, texts, arrays, wlen = self._window_lists(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
+        nreads = len(patterns)
+        if mates is None:
+            if nreads % 2:
+                raise ValueError(f"mates=None takes the reads as interleaved pairs: {nreads} reads are an odd number")
+            mates = nreads // 2
+        else:
+            mates = np.asarray(mates)
+            if mates.ndim != 2 or mates.shape[1] != 2 or (mates.size and not np.issubdtype(mates.dtype, np.integer)):
+                raise ValueError(f"mates must be an integer array of shape (F, 2), got shape {mates.shape} of {mates.dtype}")
+            m = mates.astype(np.int64).reshape(-1, 2)
+            bad = np.flatnonzero(((m < 0) | (m >= nreads)).any(axis=1))
+            if bad.size:
+                raise ValueError(f"mates[{bad[0]}] = ({m[bad[0], 0]}, {m[bad[0], 1]}) is out of range ({nreads} reads)")
+            bad = np.flatnonzero(m[:, 0] == m[:, 1])
+            if bad.size:
+                raise ValueError(f"mates[{bad[0]}] = ({m[bad[0], 0]}, {m[bad[0], 1]}): the two mates are one read")
+            flat = m.ravel()
+            order = np.argsort(flat, kind="stable")
+            again = order[1:][flat[order][1:] == flat[order][:-1]]
+            if again.size:
+                f = int(again.min()) // 2
+                raise ValueError(f"mates[{f}] = ({m[f, 0]}, {m[f, 1]}): read {flat[again.min()]} belongs to an earlier fragment")
+        ii, jj, ts, rev = arrays[0], arrays[1], arrays[4], arrays[6]
+        self._sync_wildcard()
+        sets, mine = self._open_sets(patterns, texts)
+        placer = None
+        try:
+            placer = self._native.placer(nreads)
+
+            def add(rb, lo, hi, score, status):
+                placer.add(rb, ii[lo:hi], jj[lo:hi], None if ts is None else ts[lo:hi], None if rev is None else rev[lo:hi])
+
+            out = self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, each=add)
+            rows, flags, pair_rows, pair_flags = placer.run_pairs(
+                mates, _native.INT32_MIN if min_score is None else int(min_score), int(full_gap), int(min_insert), int(max_insert),
+                int(unpaired))
+            out["flag"] = flags
+            out["reads"] = {name: np.ascontiguousarray(rows[:, c]) for c, name in enumerate(_native.PLACE_COLUMNS)}
+            out["pair_flag"] = pair_flags
+            out["pairs"] = {name: np.ascontiguousarray(pair_rows[:, c]) for c, name in enumerate(_native.PAIR_COLUMNS)}
+            return out
+        finally:
+            if placer is not None:
+                placer.close()
+            for s in mine:
+                s.close()
+
     def score_matrix(self, patterns, texts=None):
         """Score every pattern against every text on the GPU: returns ``(score, status)``, int32 arrays of shape (M, N).
 

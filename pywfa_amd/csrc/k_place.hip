@@ -2,7 +2,8 @@
 // Stores: the record kernels write out[q] for q < npairs (the host has grown the records to hold them); the count / scatter kernels
 // touch count[i] only for i < nreads and order[slot] only for slot < nhits (the host has checked every i; the guards are here so
 // that nothing a caller passes can move a store out of its array); the scan writes count[0 .. nreads] and bsum[chunk]; the place
-// kernel writes row r < nreads and flags[h] for h < nhits read from order[].
+// kernel writes row r < nreads and flags[h] for h < nhits read from order[]; the pair kernel writes row f < nfrag and pair_flags[h]
+// for h < nhits read from order[], and reads rows / count only for mates inside [0, nreads).
 #include <algorithm>
 #define WFA_SUMMARY_SCAN_ONLY
 #include "wfa_summary.hpp"   // (summary_scan: the walk that gives the summary's text_start / text_end)
@@ -198,6 +199,153 @@ __global__ void __launch_bounds__(256) wfa_place_kernel(PlaceArgs a) {
   }
 }
 
+
+// ---- pairing (wfa_place.hpp: "pair") ----
+
+// SAME LOCUS of x against p, for x != p (the caller's test)
+__device__ inline bool place_same_locus(const PlaceHit& x, const PlaceHit& p) {
+  const int64_t ov = (int64_t)min(x.te, p.te) - (int64_t)max(x.ts, p.ts);
+  const int64_t len_x = (int64_t)x.te - x.ts, len_p = (int64_t)p.te - p.ts;
+  return x.j == p.j && x.reverse == p.reverse && ov > 0 && 2 * ov >= (len_x < len_p ? len_x : len_p);
+}
+
+// PROPER of a pairing of two eligible hits; *insert = te_R - ts_F
+__device__ inline bool pair_proper(const PlaceHit& x, const PlaceHit& y, int32_t min_insert, int32_t max_insert, int64_t* insert) {
+  if (x.j != y.j || x.reverse == y.reverse || x.te <= x.ts || y.te <= y.ts) return false;
+  const PlaceHit& F = x.reverse ? y : x;
+  const PlaceHit& R = x.reverse ? x : y;
+  *insert = (int64_t)R.te - F.ts;
+  return F.ts <= R.ts && F.te <= R.te && *insert >= min_insert && *insert <= max_insert;
+}
+
+// the slot pair (p / n2, p % n2) of a lane's p = lane, lane + 64, ...: one division per fragment
+struct PairWalk {
+  uint32_t s1, s2, q64, r64, n2;
+  __device__ PairWalk(int lane, uint32_t n2_) : s1((uint32_t)lane / n2_), s2((uint32_t)lane % n2_), q64(64u / n2_), r64(64u % n2_), n2(n2_) {}
+  __device__ void next() {
+    s1 += q64; s2 += r64;
+    if (s2 >= n2) { s2 -= n2; s1 += 1; }
+  }
+};
+
+__device__ inline int32_t pair_saturate(int64_t v) {
+  return (int32_t)(v < (int64_t)INT32_MIN + 1 ? (int64_t)INT32_MIN + 1 : v > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : v);
+}
+
+#define WFA_PAIR_BIAS (1ll << 33)   // a pair score + the bias is positive: key 0 is "none"
+
+__global__ void __launch_bounds__(256) wfa_pair_kernel(PairArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const PlaceArgs& P = a.place;
+  const uint64_t nhits = (uint64_t)P.nhits;
+  const int32_t min_score = P.min_score;
+  for (int64_t f = wave; f < a.nfrag; f += nwaves) {
+    const int64_t r1 = a.mate1 ? (int64_t)a.mate1[f] : 2 * f, r2 = a.mate2 ? (int64_t)a.mate2[f] : 2 * f + 1;
+    if (r1 < 0 || r1 >= P.nreads || r2 < 0 || r2 >= P.nreads) continue;   // (wave-uniform; the host has checked the mates)
+    const int32_t* se1 = P.rows + WFA_PLACE_COLS * r1;
+    const int32_t* se2 = P.rows + WFA_PLACE_COLS * r2;
+    const int32_t hit1 = se1[0], sc1 = se1[1], mq1 = se1[3], e1 = se1[4];
+    const int32_t hit2 = se2[0], sc2 = se2[1], mq2 = se2[3], e2 = se2[4];
+    const uint64_t beg1 = P.count[r1], stop1 = P.count[r1 + 1], end1 = stop1 < nhits ? stop1 : nhits;
+    const uint64_t beg2 = P.count[r2], stop2 = P.count[r2 + 1], end2 = stop2 < nhits ? stop2 : nhits;
+    const uint32_t n1 = end1 > beg1 ? (uint32_t)(end1 - beg1) : 0u, n2 = end2 > beg2 ? (uint32_t)(end2 - beg2) : 0u;
+    const uint64_t total = (uint64_t)n1 * n2;
+    const bool overflow = (int64_t)e1 * e2 > (int64_t)WFA_PAIR_MAX_PAIRINGS;
+    const bool join = !overflow && e1 > 0 && e2 > 0 && total > 0;            // (wave-uniform)
+    uint32_t pairings = 0, ch = ~0u, cg = ~0u;
+    unsigned long long top = 0;
+    if (join) {
+      // pass 1: the proper pairings, and the best of them
+      unsigned long long key = 0;
+      uint32_t kh = ~0u, kg = ~0u;
+      PairWalk w(lane, n2);
+      for (uint64_t p = lane; p < total; p += 64) {
+        const uint32_t h = P.order[beg1 + w.s1], g = P.order[beg2 + w.s2];
+        w.next();
+        if (h >= nhits || g >= nhits) continue;
+        const PlaceHit x = place_load(P.hits + h);
+        if (x.status != 0 || x.score < min_score) continue;
+        const PlaceHit y = place_load(P.hits + g);
+        if (y.status != 0 || y.score < min_score) continue;
+        int64_t ins;
+        if (!pair_proper(x, y, a.min_insert, a.max_insert, &ins)) continue;
+        pairings += 1;
+        const unsigned long long k = (unsigned long long)((int64_t)x.score + y.score + WFA_PAIR_BIAS);
+        if (k > key || (k == key && (h < kh || (h == kh && g < kg)))) { key = k; kh = h; kg = g; }
+      }
+      pairings = seed_wave_sum(pairings);
+      top = place_wave_max64(key);
+      ch = seed_wave_min(top != 0 && key == top ? kh : ~0u);
+      cg = seed_wave_min(top != 0 && key == top && kh == ch ? kg : ~0u);
+    }
+    int decided = 0;
+    if (lane == 0 && top != 0) decided = (int64_t)top - WFA_PAIR_BIAS + a.unpaired >= (int64_t)sc1 + sc2 ? 1 : 0;
+    const bool proper = __shfl(decided, 0) != 0 && ch < nhits && cg < nhits;
+    int v;
+    if (!proper) {
+      switch (lane) {
+        case 0: v = hit1; break; case 1: v = hit2; break; case 3: case 4: v = INT32_MIN; break; case 6: v = mq1; break;
+        case 7: v = mq2; break; case 9: v = (int32_t)pairings; break; case 11: v = overflow ? 1 : 0; break; default: v = 0; break;
+      }
+    } else {
+      const PlaceHit hc = place_load(P.hits + ch), gc = place_load(P.hits + cg);
+      const int64_t best = (int64_t)top - WFA_PAIR_BIAS;
+      // pass 2: every proper pairing against the chosen place
+      uint32_t ties = 0, others = 0;
+      unsigned long long sec = 0;
+      PairWalk w(lane, n2);
+      for (uint64_t p = lane; p < total; p += 64) {
+        const uint32_t h = P.order[beg1 + w.s1], g = P.order[beg2 + w.s2];
+        w.next();
+        if (h >= nhits || g >= nhits) continue;
+        const PlaceHit x = place_load(P.hits + h);
+        if (x.status != 0 || x.score < min_score) continue;
+        const PlaceHit y = place_load(P.hits + g);
+        if (y.status != 0 || y.score < min_score) continue;
+        int64_t ins;
+        if (!pair_proper(x, y, a.min_insert, a.max_insert, &ins)) continue;
+        if ((h == ch || place_same_locus(x, hc)) && (g == cg || place_same_locus(y, gc))) continue;
+        const unsigned long long k = (unsigned long long)((int64_t)x.score + y.score + WFA_PAIR_BIAS);
+        others += 1; ties += k == top ? 1u : 0u;
+        sec = k > sec ? k : sec;
+      }
+      ties = seed_wave_sum(ties); others = seed_wave_sum(others);
+      sec = place_wave_max64(sec);
+      const int64_t second = (int64_t)sec - WFA_PAIR_BIAS;
+      int32_t mapq = 60;
+      if (others) {
+        const int64_t q = 60 * (best - second) / P.full_gap;   // (best >= second: a floor division)
+        mapq = (int32_t)(q < 60 ? q : 60);
+      }
+      const int32_t m1 = P.flags[ch] >= 2 ? max(mapq, mq1) : mapq, m2 = P.flags[cg] >= 2 ? max(mapq, mq2) : mapq;
+      const int64_t insert = hc.reverse ? (int64_t)hc.te - gc.ts : (int64_t)gc.te - hc.ts;
+      if (a.pair_flags) {
+        for (uint64_t t = beg1 + lane; t < end1; t += 64) {
+          const uint32_t h = P.order[t];
+          if (h >= nhits) continue;
+          const PlaceHit x = place_load(P.hits + h);
+          a.pair_flags[h] = (x.status != 0 || x.score < min_score) ? 0 : h == ch ? 3 : place_same_locus(x, hc) ? 2 : 1;
+        }
+        for (uint64_t t = beg2 + lane; t < end2; t += 64) {
+          const uint32_t g = P.order[t];
+          if (g >= nhits) continue;
+          const PlaceHit y = place_load(P.hits + g);
+          a.pair_flags[g] = (y.status != 0 || y.score < min_score) ? 0 : g == cg ? 3 : place_same_locus(y, gc) ? 2 : 1;
+        }
+      }
+      switch (lane) {
+        case 0: v = (int32_t)ch; break; case 1: v = (int32_t)cg; break; case 2: v = 1; break; case 3: v = pair_saturate(best); break;
+        case 4: v = others ? pair_saturate(second) : INT32_MIN; break; case 5: v = mapq; break; case 6: v = m1; break;
+        case 7: v = m2; break; case 8: v = (int32_t)insert; break; case 9: v = (int32_t)pairings; break;
+        case 10: v = (int32_t)ties; break; default: v = 0; break;
+      }
+    }
+    if (lane < WFA_PAIR_COLS) a.pair_rows[WFA_PAIR_COLS * f + lane] = v;
+  }
+}
+
 int launch_place_record(const PlaceRecordArgs& a, bool full, int cu_count, hipStream_t stream) {
   if (a.npairs <= 0) return 0;
   if (full) {
@@ -226,6 +374,13 @@ int launch_place(const PlaceArgs& a, int cu_count, hipStream_t stream) {
   if (a.nreads <= 0) return 0;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.nreads + 3) / 4, (int64_t)cu_count * 16));
   hipLaunchKernelGGL(wfa_place_kernel, dim3(grid), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_pair(const PairArgs& a, int cu_count, hipStream_t stream) {
+  if (a.nfrag <= 0) return 0;
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.nfrag + 3) / 4, (int64_t)cu_count * 16));
+  hipLaunchKernelGGL(wfa_pair_kernel, dim3(grid), dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -5146,7 +5146,11 @@ namespace wfa {   // host_place.cpp: the checks shared with wfa_hip_place_host
 int place_check_hits(int64_t nreads, int64_t base, int64_t n, const int32_t* i, const int32_t* j, const int32_t* text_start,
                      const int32_t* text_end, char* msg, size_t cap);
 int place_check_run(int32_t full_gap, char* msg, size_t cap);
+// host_pair.cpp: the check shared with wfa_hip_pair_host
+int pair_check(int64_t nreads, int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
+               const int32_t* mate2, char* msg, size_t cap);
 }
+static_assert(WFA_PAIR_COLS == WFA_HIP_PAIR_COLS && WFA_PAIR_MAX_PAIRINGS == WFA_HIP_PAIR_MAX_PAIRINGS, "pairing: the kernels and the ABI");
 
 struct wfa_hip_placer {
   wfa_hip_aligner* al = nullptr;
@@ -5351,6 +5355,71 @@ extern "C" int wfa_hip_placer_run(wfa_hip_placer_t* p, int32_t min_score, int32_
     p->grouped = p->nhits;
     HIP_TRY(al, hipMemcpyAsync(rows, a.rows, (size_t)p->nreads * WFA_PLACE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
     if (flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(flags, a.flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
+  }
+  return WFA_HIP_OK;
+}
+
+// group (when the hits changed), place, then the pair kernel: the single-end rows and flags stay on the device for the join
+extern "C" int wfa_hip_placer_run_pairs(wfa_hip_placer_t* p, int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert,
+                                        int32_t unpaired, int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int32_t* rows,
+                                        uint8_t* flags, int32_t* pair_rows, uint8_t* pair_flags) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  char buf[240];
+  if (wfa::place_check_run(full_gap, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (wfa::pair_check(p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (nfrag > 0 && !pair_rows) { al->err = "pairing: null pair_rows"; return WFA_HIP_EINVAL; }
+  if (p->nreads == 0) return WFA_HIP_OK;   // (no read: no fragment, no hit)
+  HIP_TRY(al, hipSetDevice(al->device));
+  if (p->nhits > p->order_cap) {
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
+    const int rc = placer_alloc(al, (void**)&p->d_order, (size_t)p->cap * sizeof(uint32_t), "4 bytes per hit");
+    if (rc != WFA_HIP_OK) return rc;
+    p->order_cap = p->cap;
+  }
+  CrossScratch sc{al};
+  wfa::PairArgs a;
+  memset(&a, 0, sizeof(a));
+  wfa::PlaceArgs& s = a.place;
+  s.hits = p->d_hits; s.nhits = p->nhits; s.nreads = p->nreads; s.count = p->d_count; s.bsum = p->d_bsum; s.order = p->d_order;
+  s.min_score = min_score; s.full_gap = full_gap;
+  a.min_insert = min_insert; a.max_insert = max_insert; a.unpaired = unpaired; a.nfrag = nfrag;
+  if (sc.alloc(&s.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
+  if (sc.alloc(&s.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  if (pair_flags && sc.alloc(&a.pair_flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  if (nfrag > 0 && sc.alloc(&a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS)) return WFA_HIP_EDEVICE;
+  if (mate1 && nfrag > 0) {
+    int32_t *d_m1 = nullptr, *d_m2 = nullptr;
+    if (sc.alloc(&d_m1, (size_t)nfrag) || sc.alloc(&d_m2, (size_t)nfrag)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpyAsync(d_m1, mate1, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    HIP_TRY(al, hipMemcpyAsync(d_m2, mate2, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    a.mate1 = d_m1; a.mate2 = d_m2;
+  }
+  {
+    ReduceTimer timer(al, "place pairs", p->nhits, "hits");
+    HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
+    int lrc = 0;
+    if (p->grouped != p->nhits) {
+      p->grouped = -1;
+      HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
+      lrc = wfa::launch_place_group(s, al->stream);
+    }
+    if (lrc == 0) lrc = wfa::launch_place(s, al->cu_count, al->stream);
+    // reads in no fragment, and fragments that are not proper, keep their single-end flags
+    if (lrc == 0 && a.pair_flags && p->nhits > 0)
+      HIP_TRY(al, hipMemcpyAsync(a.pair_flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToDevice, al->stream));
+    if (lrc == 0) lrc = wfa::launch_pair(a, al->cu_count, al->stream);
+    HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
+    timer.stop();
+    if (lrc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "pairing: kernel launch failed"; return WFA_HIP_EDEVICE; }
+    p->grouped = p->nhits;
+    if (rows) HIP_TRY(al, hipMemcpyAsync(rows, s.rows, (size_t)p->nreads * WFA_PLACE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+    if (flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
+    if (nfrag > 0) HIP_TRY(al, hipMemcpyAsync(pair_rows, a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+    if (pair_flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(pair_flags, a.pair_flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
     HIP_TRY(al, hipStreamSynchronize(al->stream));
     HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
   }

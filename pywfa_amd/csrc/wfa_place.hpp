@@ -25,6 +25,18 @@
 //            same-locus test against p's record, the flags, and wave reductions for second (a maximum), ties, hits and the number
 //            of runner-up candidates.  Groups longer than 64 loop; lanes 0 .. 7 store the row.  No LDS.
 //            A READ WITH A VERY LARGE GROUP IS SERVED BY ONE WAVE (two passes of group / 64 rounds).
+//   pair     (include/wfa_hip.h, "pairing"; wfa_hip_pair_host in host_pair.cpp is its plain statement.)  After group and place, so it
+//            reads count / order, the single-end rows and the single-end flags in HBM.  One wave per fragment, grid-stride.  With
+//            n1, n2 the sizes of the mates' groups, the lanes stride the n1 x n2 slot pairs p -> (p / n2, p % n2) — the slot pair
+//            is advanced by (64 / n2, 64 % n2) a round, no division in the loop — and load both records (two 16-byte loads each);
+//            a pair with an ineligible slot is skipped, not compacted, so the rounds of a pass are n1 n2 / 64 while the rule's
+//            bound E1 E2 <= WFA_PAIR_MAX_PAIRINGS is on the eligible ones (E from the single-end rows; over the bound: no join).
+//            Pass 1: the number of proper pairings and the best one by three wave-wide reductions: the maximum of the biased 64-bit
+//            pair score, the minimum h among the lanes that hold it, the minimum g among those.  Lane 0 decides `proper` against
+//            the single-end scores and broadcasts it.  Pass 2 (proper only): the same-place test against the two chosen records,
+//            wave reductions for second, ties and the number of runner-up candidates.  Then the lanes stride each mate's group
+//            once for pair_flags (which the host entry has filled with the single-end flags beforehand, a device copy: reads in
+//            no fragment and fragments that are not proper keep them); lanes 0 .. 11 store the row.  No LDS, no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,5 +78,20 @@ struct PlaceArgs {
 int launch_place_record(const PlaceRecordArgs& a, bool full, int cu_count, hipStream_t stream);
 int launch_place_group(const PlaceArgs& a, hipStream_t stream);   // count, scan, scatter (a.count zeroed by the caller)
 int launch_place(const PlaceArgs& a, int cu_count, hipStream_t stream);
+
+#define WFA_PAIR_COLS 12
+#define WFA_PAIR_MAX_PAIRINGS 65536
+
+struct PairArgs {
+  PlaceArgs place;           // after launch_place_group and launch_place: count / order, rows and flags (flags never nullptr here)
+  int32_t min_insert, max_insert, unpaired;
+  int64_t nfrag;
+  const int32_t* mate1;      // [nfrag], or both nullptr: fragment f is reads 2 f and 2 f + 1
+  const int32_t* mate2;
+  int32_t* pair_rows;        // [nfrag x WFA_PAIR_COLS]
+  uint8_t* pair_flags;       // [nhits] holding the single-end flags, or nullptr
+};
+
+int launch_pair(const PairArgs& a, int cu_count, hipStream_t stream);
 
 }  // namespace wfa

@@ -90,3 +90,12 @@ cdef extern from "wfa_hip.h" nogil:
     int wfa_hip_place_host(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse, const int32_t* score,
                             const int32_t* status, const int32_t* text_start, const int32_t* text_end, int32_t min_score,
                             int32_t full_gap, int32_t* rows, uint8_t* flags, char* msg, size_t msg_cap)
+    # pairing: one row per fragment of two reads (include/wfa_hip.h: "pairing")
+    int wfa_hip_placer_run_pairs(wfa_hip_placer_t* placer, int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert,
+                            int32_t unpaired, int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int32_t* rows, uint8_t* flags,
+                            int32_t* pair_rows, uint8_t* pair_flags)
+    int wfa_hip_pair_host(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse, const int32_t* score,
+                            const int32_t* status, const int32_t* text_start, const int32_t* text_end, int32_t min_score,
+                            int32_t full_gap, int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag,
+                            const int32_t* mate1, const int32_t* mate2, int32_t* rows, uint8_t* flags, int32_t* pair_rows,
+                            uint8_t* pair_flags, char* msg, size_t msg_cap)
