@@ -47,11 +47,19 @@
 // K = OE instead of score 0.  Below OE no gap can have been opened (I_s, D_s read M at s - OE < 0), so the only cells are those of
 // diagonal 0 at the multiples of X: chain[0] = extend(0), chain[i] = extend(chain[i - 1] + 1) for i < NCH = ceil(OE / X) — and with
 // X >= OE just chain[0].  OE is the first score at which a cell off diagonal 0 exists (I_OE on k = 1, D_OE on k = -1), which is what K
-// has to be for any shape.  A lock-step pass per unit of score for one cell (and none at all at the other scores) is what the
-// refill now does on its own: the lanes that take a pair follow diagonal 0 together, 32 bases per round, bounded by lim of slot j0 =
-// min(tlen, plen); a run that stops is the next cell of the chain, the one behind it starts a base further on, and if that lies beyond
-// lim the clamp of compute-next would have made it (and with it every later cell) NULL.  A pair with tlen == plen whose cell i
-// reaches tlen is finished there, as termination would have found at step i X: score -(i X) g, status 0, the lane idle again.
+// has to be for any shape.  A lock-step pass per unit of score for one cell (and none at all at the other scores) is replaced by a
+// walk along diagonal 0, bounded by lim of slot j0 = min(tlen, plen): a run that stops is the next cell of the chain, the one behind
+// it starts a base further on, and if that lies beyond lim the clamp of compute-next would have made it (and with it every later
+// cell) NULL.  A pair with tlen == plen whose cell i reaches tlen is finished in the refill, as termination would have found at
+// step i X: score -(i X) g, status 0, the lane idle again.
+// Where the walk runs (WINCH, shapes of up to two cells: every built-in shape): once per 64-pair metadata window, at the head of the
+// refill that may first draw from it — all 64 lanes hold a pair then, a refill only the 8 - 12 that take one, and the chain does not
+// depend on when a lane takes the pair.  Diagonal 0 needs no funnel shift (the text words follow the pattern words, both
+// word-aligned), so lane i XORs its pair's words straight from global memory, 32 bases per round, and the cells are the positions of
+// the first NCH differences below lim, then lim itself.  Cell 0 travels in the ten spare bits of the window's `ln`, cell 1 waits in LDS
+// (`wch`, int16 by window position: 256 B, so that a wave's LDS at 150 bp stays within five 1 280-byte granules) for the refill that
+// takes the pair, which only writes the state down.  Pairs the stage cannot take are not walked.  Shapes with more cells keep the
+// walk inside the refill, on the words in LDS, all taking lanes together.
 // The state at step K, before its extension, is then written down as the loop would hold it:
 //   Mh[d] = M at score K - 1 - d = chain[(K - 1 - d) / X] in slot j0 where that score is a multiple of X in [0, K), else NULL;
 //   Ih[0] = I_K = M_0 + 1 in slot j0 + 1, Dh[0] = D_K = M_0 in slot j0 - 1 (a slot outside the band: nothing, as the NULL
@@ -82,8 +90,8 @@ typedef unsigned short lane_u2 __attribute__((ext_vector_type(2)));
 #define WFA_LANE_NULL2 0xC000C000u
 #ifndef WFA_LANE_DEBUG_COUNTERS
 #define WFA_LANE_DEBUG_COUNTERS 0  // 1: a.hist (if set) receives ten uint64: {wave-steps, refills, parked runs, parked 32-base rounds,
-#endif                             //    first-probe blocks, rounds of second runs, hand-over blocks, second runs, entries (refills that
-                                   //    ran the entry chain), 32-base rounds of the entry chain} (score-only form)
+#endif                             //    first-probe blocks, rounds of second runs, hand-over blocks, second runs, entries (windows whose
+                                   //    entry chains were followed), 32-base rounds of the entry chain} (score-only form)
 // Analysis builds (tools/lane_mix.py): region marks as comments in the assembly, so that the instructions of each region of the
 // step can be counted by class and weighted with the counters above (the dynamic instruction mix of the kernel)
 #ifndef WFA_LANE_REGION_MARKS
@@ -143,7 +151,15 @@ __device__ __forceinline__ uint32_t pk_clamp(uint32_t nm, uint32_t lim) {
 #if WFA_LANE_WAVES_PER_EU > 0
 #define WFA_LANE_OCCUPANCY __attribute__((amdgpu_waves_per_eu(WFA_LANE_WAVES_PER_EU, WFA_LANE_WAVES_PER_EU)))
 #else
-#define WFA_LANE_OCCUPANCY
+// The 8-diagonal form is built for occupancy: 6 waves per SIMD (at most 80 VGPRs) for the 2/4/1 shape of C2.  Left to itself the allocator
+// ends a few registers above the step the form stood on — in the extension probes — once the window-time chain shares the loop with them, so
+// the form asks for the waves its rings allow (R = M depth + 2 E + cur and lim, four registers each): every built-in shape then compiles
+// to that many without scratch.  (1: no bound — every other form as it was.)
+constexpr int lane_narrow_waves(int X, int OE, int E) {
+  const int R = ((X > OE) ? X : OE) + 2 * E + 2;
+  return R <= 6 ? 7 : R <= 8 ? 6 : R <= 11 ? 5 : 4;
+}
+#define WFA_LANE_OCCUPANCY __attribute__((amdgpu_waves_per_eu((NRP == 4) ? lane_narrow_waves(X, OE, E) : 1)))
 #endif
 
 // records of origin codes a lane can need: steps 0 .. Bmin / g - 1 (wfa_seg.hpp: Bmin / g <= 2 (OE - E) + E (2 H + 1))
@@ -176,6 +192,11 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
   // the entry at score K (header comment): the plain score-only form only.  NCH cells of diagonal 0 precede score K: scores 0, X, .. < OE
   constexpr bool ENTRY = !FULL && !HEUR && LIN == 0;
   constexpr int K = ENTRY ? OE : 0, NCH = (OE + X - 1) / X;
+  // the chain of a pair is followed when its metadata window is loaded (all 64 lanes hold a pair then) and waits for the refill that
+  // takes the pair: cell 0 in the ten spare bits of the window's `ln` (bits 10-15 and 26-29), cell 1 as an int16 in LDS.  Shapes with
+  // more than two cells keep the chain inside the refill.
+  constexpr bool WINCH = ENTRY && NCH <= 2;
+  constexpr uint32_t LNM = WINCH ? 0x3ffu : 0xffffu;   // a length in its half of ln (WINCH: the bits above hold cell 0)
   constexpr int NREC = LaneFull<OE, E>::NREC;     // FULL: steps a pair can take here (bounds the walk)
   extern __shared__ uint32_t lds[];               // [4 guard words][64 slots x slot_words][4 guard words]
   const int slot_words = slot_words_seq;
@@ -206,6 +227,60 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
 
   // ---- two windows of 64 pairs' metadata: lane i holds pair wbase + i / wbase + 64 + i
   uint32_t pid0, pw0, ln0, pid1, pw1, ln1;        // ln = plen | tlen << 16 (0xffffffff: too long for this stage)
+  __shared__ short wch[(WINCH && NCH == 2) ? 128 : 1];   // WINCH: cell 1 of the chains of the two windows, by window position
+  // WINCH: the entry chain (header comment) of every pair of a window, lane i for the pair whose metadata it holds: the first NCH
+  // differences of pattern and text on diagonal 0 below L = min(plen, tlen), straight from global memory (text words follow the
+  // pattern words, both word-aligned: an XOR word by word, 32 bases per round).  Cell c is the c-th difference; the first cell
+  // without one is L itself (the run reaches lim: a live cell there), the cell behind it stays NULL.  Pairs the stage cannot
+  // take and lanes beyond the slice load nothing; no load leaves the first ceil(L / 16) words of either sequence.  Returns ln
+  // with cell 0 in its spare bits (a pair that is not walked: ln as it is — the refill does not read its cells).
+  auto window_chain = [&](uint32_t wb, uint32_t pw, uint32_t ln) -> uint32_t {
+    WFA_LANE_MARK("entry_begin");
+    WFA_LANE_COUNT(8);
+    const int pl = (int)(ln & 0xffffu), tl = (int)(ln >> 16);
+    const int nwp = (pl + 15) >> 4, ntot = nwp + ((tl + 15) >> 4), ak = tl - pl, L = min(pl, tl);
+    const bool elig = (unsigned long long)wb + lane < end &&
+                      !(ln == 0xffffffffu || ntot + 1 > slot_words_seq || ak < 1 - 2 * H || ak > 2 * H - 1);
+    bool act = elig;
+    const uint32_t* pp = a.words + pw;             // pattern word 2 r of round r; the text word lies nwp words on
+    int ch[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) ch[c] = WFA_LANE_NULL16;
+    int ci = 0;
+    const int imax = slot_words_seq >> 1;          // (a slot holds no longer sequence: the loop ends there whatever the data say)
+    int base = 0;                                  // first base of this round's words
+#pragma nounroll
+    for (int i = 0; i < imax && __any(act); i += 2) {
+      WFA_LANE_MARK("entryround_begin");
+      WFA_LANE_COUNT(9);
+      uint32_t x0 = 0u, x1 = 0u;
+      if (act && base < L) x0 = pp[0] ^ pp[nwp];
+      if (act && base + 16 < L) x1 = pp[1] ^ pp[nwp + 1];
+      // one bit per differing base (bit 2 b of its word)
+      unsigned long long d = (unsigned long long)((x0 | (x0 >> 1)) & 0x55555555u) | ((unsigned long long)((x1 | (x1 >> 1)) & 0x55555555u) << 32);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const int pos = d ? base + ((int)__builtin_ctzll(d) >> 1) : 0x7fff;
+        const bool hit = act && pos < L;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) ch[k] = (hit && ci == k) ? pos : ch[k];
+        ci += hit ? 1 : 0;
+        act = act && ci < NCH;
+        d &= d - 1ull;
+      }
+      // no further difference below L in these words, and they reach L: the run ends at L, and with it the chain
+      const bool endc = act && base + 32 >= L;
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) ch[k] = (endc && ci == k) ? L : ch[k];
+      act = act && !endc;
+      pp += 2; base += 32;
+      WFA_LANE_MARK("entryround_end");
+    }
+    if constexpr (NCH == 2) wch[64 + lane] = (short)ch[1];   // (always window 1: a window moves down with its cells)
+    WFA_LANE_MARK("entry_end");
+    const uint32_t c0 = (uint32_t)ch[0];           // 0 .. 512 in a pair that was walked
+    return elig ? (ln | ((c0 & 0x3fu) << 10) | ((c0 >> 6) << 26)) : ln;
+  };
   auto load_window = [&](uint32_t wb, uint32_t& pid, uint32_t& pw, uint32_t& ln) {
     const unsigned long long idx = (unsigned long long)wb + lane;
     pid = 0u; pw = 0u; ln = 0u;
@@ -217,8 +292,18 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
     }
   };
   uint32_t wbase = begin, next_i = begin;
-  load_window(wbase, pid0, pw0, ln0);
-  load_window(wbase + 64u, pid1, pw1, ln1);
+  // WINCH: the chains of a window are followed in ONE place, at the head of the refill that may first draw from it (the chain loop
+  // exists once, and its registers are not live across the prologue).  wneed: windows whose chains are due (2: a new slice, both
+  // windows); wmeta: the metadata of window 1 has been requested already (when window 1 moved down: its latency hides behind the
+  // steps up to the next refill)
+  uint32_t wneed = 2u;
+  bool wmeta = false;
+  if constexpr (!WINCH) {
+    load_window(wbase, pid0, pw0, ln0);
+    load_window(wbase + 64u, pid1, pw1, ln1);
+  } else {
+    pid0 = pw0 = ln0 = pid1 = pw1 = ln1 = 0u;
+  }
 
   // ---- per-lane state
   const int pbase = (4 + lane * slot_words) * 16;  // base coordinate (in bases) of my LDS slot
@@ -272,12 +357,29 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
     if (!exhausted && next_i >= end && (nidle >= refill_min || idle == ~0ull)) {
       // this slice is used up: the next chunk of the list, if any (its metadata windows replace the old ones: every pair of the old
       // slice has been taken)
-      if (grab(begin, end)) { wbase = begin; next_i = begin; load_window(wbase, pid0, pw0, ln0); load_window(wbase + 64u, pid1, pw1, ln1); }
-      else exhausted = true;
+      if (grab(begin, end)) {
+        wbase = begin; next_i = begin;
+        if constexpr (WINCH) { wneed = 2u; wmeta = false; }
+        else { load_window(wbase, pid0, pw0, ln0); load_window(wbase + 64u, pid1, pw1, ln1); }
+      } else exhausted = true;
     }
     if (next_i < end && (nidle >= refill_min || idle == ~0ull)) {
       WFA_LANE_MARK("refill_begin");
       WFA_LANE_COUNT(1);
+      if constexpr (WINCH) {
+        // the windows that are due, always through window 1: with two (a new slice) the first moves down before the second is fetched
+#pragma nounroll
+        for (; wneed; --wneed) {
+          const uint32_t wb = wneed == 2u ? wbase : wbase + 64u;
+          if (!wmeta) load_window(wb, pid1, pw1, ln1);
+          wmeta = false;
+          ln1 = window_chain(wb, pw1, ln1);
+          if (wneed == 2u) {
+            pid0 = pid1; pw0 = pw1; ln0 = ln1;
+            if constexpr (NCH == 2) wch[lane] = wch[64 + lane];
+          }
+        }
+      }
       const bool is_idle = __builtin_amdgcn_inverse_ballot_w64(idle);
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
       const uint32_t navail = end - next_i;
@@ -288,7 +390,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
       const uint32_t b_pid = __shfl(pid1, sl, 64), b_pw = __shfl(pw1, sl, 64), b_ln = __shfl(ln1, sl, 64);
       const bool hi_w = src >= 64u;
       const uint32_t n_pid = hi_w ? b_pid : a_pid, n_pw = hi_w ? b_pw : a_pw, n_ln = hi_w ? b_ln : a_ln;
-      const int pl = (int)(n_ln & 0xffffu), tl = (int)(n_ln >> 16);
+      const int pl = (int)(n_ln & LNM), tl = (int)((n_ln >> 16) & LNM);
       const int nwp = (pl + 15) >> 4, ntot = nwp + ((tl + 15) >> 4);
       const int ak = tl - pl;
       // a pair this stage cannot take (too long for the slot, |tlen - plen| outside the band) gets an expired deadline:
@@ -364,50 +466,59 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
       const uint32_t ntake = min((uint32_t)nidle, navail);
       next_i += ntake;
       idle &= ~tmask;
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the words are in LDS
-      asm volatile("" ::: "memory");
-      if (next_i - wbase >= 64u) {           // window 0 used up: window 1 moves down, the one after is requested
-        pid0 = pid1; pw0 = pw1; ln0 = ln1; wbase += 64u;
-        load_window(wbase + 64u, pid1, pw1, ln1);
+      if constexpr (!WINCH) {
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the words are in LDS
+        asm volatile("" ::: "memory");
       }
       if constexpr (ENTRY) {
-        // ---- entry at score K (header comment): diagonal 0 through its NCH cells, all taking lanes together, then the state of step K
+        // ---- entry at score K (header comment): the NCH cells of diagonal 0, then the state of step K
         const bool go = take && !bad;
         if (__any(go)) {
-          WFA_LANE_MARK("entry_begin");
-          WFA_LANE_COUNT(8);
           int ch[NCH];
+          int fin_i = -1;
+          if constexpr (WINCH) {
+            // the chain was followed before this refill: cell 0 comes with the pair's ln, cell 1 waits at its window position
+            ch[0] = (int)(((n_ln >> 10) & 0x3fu) | (((n_ln >> 26) & 0xfu) << 6));
+            if constexpr (NCH == 2) ch[1] = (int)wch[src];
 #pragma unroll
-          for (int i = 0; i < NCH; ++i) ch[i] = WFA_LANE_NULL16;
-          const int etb = go ? tb : pbase;             // (other lanes read along, inside their own slot, and advance by 0)
-          int ci = 0, ex = 0, lf = go ? min(pl, tl) : 0, fin_i = -1;   // lf: what is left up to lim of slot j0 = min(tlen, plen)
-          bool act = go;
-          do {
-            WFA_LANE_MARK("entryround_begin");
-            WFA_LANE_COUNT(9);
-            const int v = ex + pbase, h = ex + etb;    // (slot j0 is diagonal 0: kb0 - j0 = pbase)
-            const uint32_t pa = ((uint32_t)v >> 2) & ~3u, ta = ((uint32_t)h >> 2) & ~3u;
-            const uint32_t* pp = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds) + pa);
-            const uint32_t* tp = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds) + ta);
-            const uint32_t p0 = pp[0], p1 = pp[1], p2 = pp[2], t0 = tp[0], t1 = tp[1], t2 = tp[2];
-            const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, (uint32_t)v << 1) ^ __builtin_amdgcn_alignbit(t1, t0, (uint32_t)h << 1);
-            const uint32_t xh = __builtin_amdgcn_alignbit(p2, p1, (uint32_t)v << 1) ^ __builtin_amdgcn_alignbit(t2, t1, (uint32_t)h << 1);
-            const uint32_t fb = min(lane_ffbl(xl), lane_ffbl(xh) | 32u);
-            const int m = min((int)(fb >> 1), min(32, lf));
-            ex += m; lf -= m;
-            // a run that stops is cell ci of the chain; the next one starts one base on (a mismatch), if that is still within lim —
-            // beyond it the clamp makes that cell and every later one NULL.  (A cell AT lim takes one more round, which advances by 0.)
-            const bool stop = act && !((m == 32) && (lf > 0));
+            for (int i = 0; i < NCH; ++i) fin_i = (ak == 0 && ch[i] == tl) ? i : fin_i;   // the end cell: the pair's score is i * X
+          } else {
+            // (more cells than the windows hold: all taking lanes follow diagonal 0 together, here)
+            WFA_LANE_MARK("entry_begin");
+            WFA_LANE_COUNT(8);
 #pragma unroll
-            for (int i = 0; i < NCH; ++i) ch[i] = (stop && ci == i) ? ex : ch[i];
-            fin_i = (stop && ak == 0 && ex == tl) ? ci : fin_i;   // the end cell: the pair's score is ci * X (then lf == 0: the chain ends)
-            ci += stop ? 1 : 0;
-            const bool on = stop && ci < NCH && lf > 0;
-            act = stop ? on : act;
-            ex += on ? 1 : 0; lf -= on ? 1 : 0;
-            WFA_LANE_MARK("entryround_end");
-          } while (__any(act));
-          const bool fin = fin_i >= 0;                 // (set by lanes with `go` only)
+            for (int i = 0; i < NCH; ++i) ch[i] = WFA_LANE_NULL16;
+            const int etb = go ? tb : pbase;             // (other lanes read along, inside their own slot, and advance by 0)
+            int ci = 0, ex = 0, lf = go ? min(pl, tl) : 0;   // lf: what is left up to lim of slot j0 = min(tlen, plen)
+            bool act = go;
+            do {
+              WFA_LANE_MARK("entryround_begin");
+              WFA_LANE_COUNT(9);
+              const int v = ex + pbase, h = ex + etb;    // (slot j0 is diagonal 0: kb0 - j0 = pbase)
+              const uint32_t pa = ((uint32_t)v >> 2) & ~3u, ta = ((uint32_t)h >> 2) & ~3u;
+              const uint32_t* pp = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds) + pa);
+              const uint32_t* tp = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds) + ta);
+              const uint32_t p0 = pp[0], p1 = pp[1], p2 = pp[2], t0 = tp[0], t1 = tp[1], t2 = tp[2];
+              const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, (uint32_t)v << 1) ^ __builtin_amdgcn_alignbit(t1, t0, (uint32_t)h << 1);
+              const uint32_t xh = __builtin_amdgcn_alignbit(p2, p1, (uint32_t)v << 1) ^ __builtin_amdgcn_alignbit(t2, t1, (uint32_t)h << 1);
+              const uint32_t fb = min(lane_ffbl(xl), lane_ffbl(xh) | 32u);
+              const int m = min((int)(fb >> 1), min(32, lf));
+              ex += m; lf -= m;
+              // a run that stops is cell ci of the chain; the next one starts one base on (a mismatch), if that is still within lim —
+              // beyond it the clamp makes that cell and every later one NULL.  (A cell AT lim takes one more round, which advances by 0.)
+              const bool stop = act && !((m == 32) && (lf > 0));
+#pragma unroll
+              for (int i = 0; i < NCH; ++i) ch[i] = (stop && ci == i) ? ex : ch[i];
+              fin_i = (stop && ak == 0 && ex == tl) ? ci : fin_i;   // the end cell: the pair's score is ci * X (then lf == 0: the chain ends)
+              ci += stop ? 1 : 0;
+              const bool on = stop && ci < NCH && lf > 0;
+              act = stop ? on : act;
+              ex += on ? 1 : 0; lf -= on ? 1 : 0;
+              WFA_LANE_MARK("entryround_end");
+            } while (__any(act));
+            WFA_LANE_MARK("entry_end");
+          }
+          const bool fin = go && fin_i >= 0;
           if (fin) {
             a.score[mypid] = -__mul24(fin_i * X, a.g);
             a.status[mypid] = 0;
@@ -440,8 +551,19 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
             }
             if (fin) { deadline = NEVER; jt = 0; tend = 0xffffu; }
           }
-          WFA_LANE_MARK("entry_end");
         }
+      }
+      if constexpr (WINCH) {
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the words are in LDS
+        asm volatile("" ::: "memory");
+      }
+      if (next_i - wbase >= 64u) {           // window 0 used up: window 1 moves down (WINCH: with its chains), the one after is requested
+        pid0 = pid1; pw0 = pw1; ln0 = ln1; wbase += 64u;
+        if constexpr (WINCH) {
+          if constexpr (NCH == 2) wch[lane] = wch[64 + lane];
+          wneed = 1u; wmeta = true;
+        }
+        load_window(wbase + 64u, pid1, pw1, ln1);
       }
       WFA_LANE_MARK("refill_end");
     } else if (idle == ~0ull && exhausted) {

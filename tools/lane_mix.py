@@ -8,15 +8,17 @@ the full issue rate (development aid).
    shape 0 by its mangled name; --static prints the static counts per region and instruction and stops (no counts file needed).
 
 1. The kernel is compiled for gfx950 with region marks (-DWFA_LANE_REGION_MARKS=1: comments in the assembly around the refill,
-   the entry of new pairs at score K and a round of its chain, the first-probe block of a register, a round of a second run, the
+   the entry chains of a 64-pair window and a round of them (`entry` / `entryround`: inside `refill`, at its head, once per
+   window; the part of the refill that reads the cells and writes the state of step K down is priced under `refill`; shapes with
+   more than two cells below K run the chain in every refill that takes a pair instead), the first-probe block of a register, a round of a second run, the
    parked-run loop and its write-back, the hand-over block),
    and the vector instructions of every region are counted by class: "full rate" = v_add_u32 / v_and / v_or / v_xor (0.91-0.93 ns
    per wave64 instruction and SIMD, profiles/r02_issue_rate.txt), everything else "half rate" (min / max / alignbit / cndmask /
    shifts / sub / add3 / pk / dpp / ffbl / cmp / mov-with-dpp: 1.64-1.83 ns); v_mov_b32 and v_readlane etc. are listed apart.
 2. How often each region runs comes from the counting build of the same kernel on the C2 batch (-DWFA_LANE_DEBUG_COUNTERS=1,
    WFA_HIP_LANE_DEBUG=1; the line is kept in profiles/r03_lane_regions.txt): wave-steps, refills, probe blocks, second-run
-   rounds, parked runs and rounds, hand-over blocks, entries and entry rounds (a counts line without the last two, from a build
-   before the entry, reads as 0 for both).
+   rounds, parked runs and rounds, hand-over blocks, entries (windows whose chains were followed) and entry rounds (a counts line
+   without the last two, from a build before the entry, reads as 0 for both).
 3. Dynamic count of a class = sum over regions of executions x static count; what lies outside the marks inside the main loop is
    straight-line per-step code (tests, termination, compute-next).  The total is checked against SQ_INSTS_VALU of the counter pass.
 Writes profiles/<tag>_lane_mix.json (tag: WFA_PROFILE_TAG, default r05) (tools/make_traffic.py takes full_rate_share from it)."""
@@ -118,7 +120,7 @@ def main():
         for k, v in cnt.items():
             if not k.startswith("ops:"):
                 dyn[k] += e * v / n_copies
-    # (the marks nest: probe contains now; parkfix contains parked; refill contains entry, which contains entryround — static counts are attributed to the innermost region)
+    # (the marks nest: probe contains now; parkfix contains parked; refill contains entry (once per window, at its head), which contains entryround — static counts are attributed to the innermost region)
     total = sum(dyn.values())
     out = {"kernel": KERNEL, "counts_file": os.path.relpath(counts_file, ROOT),
            "region_executions": execs, "regions": per_region,
