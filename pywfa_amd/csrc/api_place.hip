@@ -1,0 +1,292 @@
+// api_place.hip — the placer of libwfa_hip.so (the C ABI declared in include/wfa_hip.h).
+#include "host_sets.hpp"
+#include "wfa_place.hpp"
+
+// ------------------------------------------------------------------------------------------------
+// placement: one row per read from the hits of any number of batches (include/wfa_hip.h; csrc/wfa_place.hpp, k_place.hip)
+// ------------------------------------------------------------------------------------------------
+static_assert(WFA_PLACE_COLS == WFA_HIP_PLACE_COLS, "columns of the kernels and of the ABI");
+
+namespace wfa {   // host_place.cpp: the checks shared with wfa_hip_place_host
+int place_check_hits(int64_t nreads, int64_t base, int64_t n, const int32_t* i, const int32_t* j, const int32_t* text_start,
+                     const int32_t* text_end, char* msg, size_t cap);
+int place_check_run(int32_t full_gap, char* msg, size_t cap);
+// host_pair.cpp: the check shared with wfa_hip_pair_host
+int pair_check(int64_t nreads, int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
+               const int32_t* mate2, char* msg, size_t cap);
+}
+static_assert(WFA_PAIR_COLS == WFA_HIP_PAIR_COLS && WFA_PAIR_MAX_PAIRINGS == WFA_HIP_PAIR_MAX_PAIRINGS, "pairing: the kernels and the ABI");
+
+struct wfa_hip_placer {
+  wfa_hip_aligner* al = nullptr;
+  int64_t nreads = 0;
+  int64_t nhits = 0, cap = 0;          // records in use, and allocated
+  wfa::PlaceHit* d_hits = nullptr;     // the records, in hit-number order
+  uint32_t* d_count = nullptr;         // [nreads + 1] (wfa_place.hpp: PlaceArgs::count)
+  uint32_t* d_bsum = nullptr;
+  uint32_t* d_order = nullptr;         // [order_cap] the grouped hit numbers
+  int64_t order_cap = 0;
+  int64_t grouped = -1;                // the number of hits d_count / d_order were made for (-1: none)
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  float last_ms = 0.f;
+};
+
+extern "C" void wfa_hip_placer_destroy(wfa_hip_placer_t* p) {
+  if (!p) return;
+  wfa_hip_aligner* al = p->al;
+  (void)hipSetDevice(al->device);
+  (void)hipStreamSynchronize(al->stream);
+  pool_release(al, p->d_hits); pool_release(al, p->d_count); pool_release(al, p->d_bsum); pool_release(al, p->d_order);
+  for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
+  delete p;
+  aligner_release_ref(al);
+}
+
+// a device block of `bytes`, or WFA_HIP_EDEVICE with the byte count in the message
+static int placer_alloc(wfa_hip_aligner* al, void** out, size_t bytes, const char* what) {
+  if (pool_alloc(al, out, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    *out = nullptr;
+    char buf[160];
+    snprintf(buf, sizeof(buf), "placement: the allocation of %zu bytes failed (%s)", bytes, what);
+    al->err = buf;
+    return WFA_HIP_EDEVICE;
+  }
+  return WFA_HIP_OK;
+}
+
+extern "C" wfa_hip_placer_t* wfa_hip_placer_create(wfa_hip_aligner_t* al, int64_t nreads) {
+  if (!al) { g_error = "null aligner"; return nullptr; }
+  if (nreads < 0 || nreads >= (int64_t)INT32_MAX) {
+    char buf[120];
+    snprintf(buf, sizeof(buf), "placement: nreads = %lld is out of range (0 .. 2^31 - 2)", (long long)nreads);
+    al->err = buf; g_error = al->err; return nullptr;
+  }
+  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  wfa_hip_placer* p = new wfa_hip_placer();
+  p->al = al;
+  p->nreads = nreads;
+  al->live_batches += 1;
+  const size_t chunks = (size_t)((nreads + 1 + WFA_PLACE_SCAN_CHUNK - 1) / WFA_PLACE_SCAN_CHUNK);
+  if (placer_alloc(al, (void**)&p->d_count, (size_t)(nreads + 1) * sizeof(uint32_t), "4 bytes per read") != WFA_HIP_OK ||
+      placer_alloc(al, (void**)&p->d_bsum, chunks * sizeof(uint32_t), "the scan's chunk sums") != WFA_HIP_OK) {
+    g_error = al->err; wfa_hip_placer_destroy(p); return nullptr;
+  }
+  if (hipEventCreate(&p->ev[0]) != hipSuccess || hipEventCreate(&p->ev[1]) != hipSuccess) {
+    al->err = "placement: hipEventCreate failed";
+    g_error = al->err; wfa_hip_placer_destroy(p); return nullptr;
+  }
+  return p;
+}
+
+extern "C" int64_t wfa_hip_placer_count(const wfa_hip_placer_t* p) { return p ? p->nhits : 0; }
+
+extern "C" int wfa_hip_placer_clear(wfa_hip_placer_t* p) {
+  if (!p) return WFA_HIP_EINVAL;
+  p->nhits = 0; p->grouped = -1;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_placer_kernel_ms(const wfa_hip_placer_t* p, float* ms) {
+  if (!p || !ms) return WFA_HIP_EINVAL;
+  *ms = p->last_ms;
+  return WFA_HIP_OK;
+}
+
+// room for `more` records behind the ones in use: doubling, the records copied on the aligner's stream
+static int placer_reserve(wfa_hip_placer* p, int64_t more) {
+  wfa_hip_aligner* al = p->al;
+  if (p->nhits + more <= p->cap) return WFA_HIP_OK;
+  const int64_t want = std::max<int64_t>(p->nhits + more, std::max<int64_t>(2 * p->cap, 1024));
+  wfa::PlaceHit* d_new = nullptr;
+  const int rc = placer_alloc(al, (void**)&d_new, (size_t)want * sizeof(wfa::PlaceHit), "32 bytes per hit");
+  if (rc != WFA_HIP_OK) return rc;
+  if (p->nhits > 0) {
+    const hipError_t e = hipMemcpyAsync(d_new, p->d_hits, (size_t)p->nhits * sizeof(wfa::PlaceHit), hipMemcpyDeviceToDevice, al->stream);
+    const hipError_t e2 = hipStreamSynchronize(al->stream);
+    if (e != hipSuccess || e2 != hipSuccess) { pool_release(al, d_new); HIP_TRY(al, e); HIP_TRY(al, e2); }
+  }
+  pool_release(al, p->d_hits);
+  p->d_hits = d_new; p->cap = want;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_placer_add(wfa_hip_placer_t* p, wfa_hip_batch_t* b, const int32_t* i, const int32_t* j, const int32_t* t_start,
+                                  const uint8_t* reverse) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (!b) { al->err = "placement: null batch"; return WFA_HIP_EINVAL; }
+  if (b->al != al) { al->err = "placement: batch of another aligner"; return WFA_HIP_EINVAL; }
+  if (!b->ran) { al->err = "placement needs a finished run of the batch"; return WFA_HIP_EINVAL; }
+  const int64_t n = b->n;
+  char buf[240];
+  if (wfa::place_check_hits(p->nreads, p->nhits, n, i, j, t_start, nullptr, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  int rc = wfa_hip_batch_sync(b);
+  if (rc != WFA_HIP_OK) return rc;
+  if (n == 0) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  rc = placer_reserve(p, n);
+  if (rc != WFA_HIP_OK) return rc;
+  CrossScratch sc{al};   // (waits for the stream before the blocks go back)
+  int32_t *d_i = nullptr, *d_j = nullptr, *d_ts = nullptr;
+  uint8_t* d_rev = nullptr;
+  if (sc.alloc(&d_i, (size_t)n) || sc.alloc(&d_j, (size_t)n)) return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipMemcpyAsync(d_i, i, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+  HIP_TRY(al, hipMemcpyAsync(d_j, j, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+  if (t_start) {
+    if (sc.alloc(&d_ts, (size_t)n)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpyAsync(d_ts, t_start, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+  }
+  if (reverse) {
+    if (sc.alloc(&d_rev, (size_t)n)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpyAsync(d_rev, reverse, (size_t)n, hipMemcpyHostToDevice, al->stream));
+  }
+  const bool full = b->cfg.scope == WFA_SCOPE_FULL;
+  wfa::PlaceRecordArgs a;
+  memset(&a, 0, sizeof(a));
+  a.score = b->d_score; a.status = b->d_status; a.meta = b->d_meta;
+  if (full) { a.ops = b->d_ops; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len; }
+  a.npairs = n; a.i = d_i; a.j = d_j; a.t_start = d_ts; a.reverse = d_rev; a.out = p->d_hits + p->nhits;
+  {
+    ReduceTimer timer(al, "place record", n);
+    const int lrc = wfa::launch_place_record(a, full, al->cu_count, al->stream);
+    timer.stop();
+    const hipError_t e = hipStreamSynchronize(al->stream);   // (the caller's arrays are read by the copies above)
+    if (lrc != 0) { al->err = "placement: record kernel launch failed"; return WFA_HIP_EDEVICE; }
+    HIP_TRY(al, e);
+  }
+  p->nhits += n; p->grouped = -1;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_placer_add_hits(wfa_hip_placer_t* p, int64_t n, const int32_t* i, const int32_t* j, const uint8_t* reverse,
+                                       const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (n > 0 && (!score || !status || !text_start || !text_end)) { al->err = "placement: a missing array"; return WFA_HIP_EINVAL; }
+  char buf[240];
+  if (wfa::place_check_hits(p->nreads, p->nhits, n, i, j, text_start, text_end, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (n == 0) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  const int rc = placer_reserve(p, n);
+  if (rc != WFA_HIP_OK) return rc;
+  std::vector<wfa::PlaceHit> rec((size_t)n);
+  for (int64_t q = 0; q < n; ++q) {
+    wfa::PlaceHit& h = rec[(size_t)q];
+    h.i = i[q]; h.j = j[q]; h.reverse = (reverse && reverse[q]) ? 1 : 0; h.status = status[q];
+    h.score = score[q]; h.ts = text_start[q]; h.te = text_end[q]; h.spare = 0;
+  }
+  HIP_TRY(al, hipMemcpyAsync(p->d_hits + p->nhits, rec.data(), (size_t)n * sizeof(wfa::PlaceHit), hipMemcpyHostToDevice, al->stream));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  p->nhits += n; p->grouped = -1;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_placer_run(wfa_hip_placer_t* p, int32_t min_score, int32_t full_gap, int32_t* rows, uint8_t* flags) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  char buf[160];
+  if (wfa::place_check_run(full_gap, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (p->nreads > 0 && !rows) { al->err = "placement: null rows"; return WFA_HIP_EINVAL; }
+  if (p->nreads == 0) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  if (p->nhits > p->order_cap) {
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
+    const int rc = placer_alloc(al, (void**)&p->d_order, (size_t)p->cap * sizeof(uint32_t), "4 bytes per hit");
+    if (rc != WFA_HIP_OK) return rc;
+    p->order_cap = p->cap;
+  }
+  CrossScratch sc{al};
+  wfa::PlaceArgs a;
+  memset(&a, 0, sizeof(a));
+  a.hits = p->d_hits; a.nhits = p->nhits; a.nreads = p->nreads; a.count = p->d_count; a.bsum = p->d_bsum; a.order = p->d_order;
+  a.min_score = min_score; a.full_gap = full_gap;
+  if (sc.alloc(&a.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
+  if (flags && sc.alloc(&a.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  {
+    ReduceTimer timer(al, "place", p->nhits, "hits");
+    HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
+    int lrc = 0;
+    if (p->grouped != p->nhits) {
+      p->grouped = -1;
+      HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
+      lrc = wfa::launch_place_group(a, al->stream);
+    }
+    if (lrc == 0) lrc = wfa::launch_place(a, al->cu_count, al->stream);
+    HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
+    timer.stop();
+    if (lrc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "placement: kernel launch failed"; return WFA_HIP_EDEVICE; }
+    p->grouped = p->nhits;
+    HIP_TRY(al, hipMemcpyAsync(rows, a.rows, (size_t)p->nreads * WFA_PLACE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+    if (flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(flags, a.flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
+  }
+  return WFA_HIP_OK;
+}
+
+// group (when the hits changed), place, then the pair kernel: the single-end rows and flags stay on the device for the join
+extern "C" int wfa_hip_placer_run_pairs(wfa_hip_placer_t* p, int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert,
+                                        int32_t unpaired, int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int32_t* rows,
+                                        uint8_t* flags, int32_t* pair_rows, uint8_t* pair_flags) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  char buf[240];
+  if (wfa::place_check_run(full_gap, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (wfa::pair_check(p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (nfrag > 0 && !pair_rows) { al->err = "pairing: null pair_rows"; return WFA_HIP_EINVAL; }
+  if (p->nreads == 0) return WFA_HIP_OK;   // (no read: no fragment, no hit)
+  HIP_TRY(al, hipSetDevice(al->device));
+  if (p->nhits > p->order_cap) {
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
+    const int rc = placer_alloc(al, (void**)&p->d_order, (size_t)p->cap * sizeof(uint32_t), "4 bytes per hit");
+    if (rc != WFA_HIP_OK) return rc;
+    p->order_cap = p->cap;
+  }
+  CrossScratch sc{al};
+  wfa::PairArgs a;
+  memset(&a, 0, sizeof(a));
+  wfa::PlaceArgs& s = a.place;
+  s.hits = p->d_hits; s.nhits = p->nhits; s.nreads = p->nreads; s.count = p->d_count; s.bsum = p->d_bsum; s.order = p->d_order;
+  s.min_score = min_score; s.full_gap = full_gap;
+  a.min_insert = min_insert; a.max_insert = max_insert; a.unpaired = unpaired; a.nfrag = nfrag;
+  if (sc.alloc(&s.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
+  if (sc.alloc(&s.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  if (pair_flags && sc.alloc(&a.pair_flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  if (nfrag > 0 && sc.alloc(&a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS)) return WFA_HIP_EDEVICE;
+  if (mate1 && nfrag > 0) {
+    int32_t *d_m1 = nullptr, *d_m2 = nullptr;
+    if (sc.alloc(&d_m1, (size_t)nfrag) || sc.alloc(&d_m2, (size_t)nfrag)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpyAsync(d_m1, mate1, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    HIP_TRY(al, hipMemcpyAsync(d_m2, mate2, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    a.mate1 = d_m1; a.mate2 = d_m2;
+  }
+  {
+    ReduceTimer timer(al, "place pairs", p->nhits, "hits");
+    HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
+    int lrc = 0;
+    if (p->grouped != p->nhits) {
+      p->grouped = -1;
+      HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
+      lrc = wfa::launch_place_group(s, al->stream);
+    }
+    if (lrc == 0) lrc = wfa::launch_place(s, al->cu_count, al->stream);
+    // reads in no fragment, and fragments that are not proper, keep their single-end flags
+    if (lrc == 0 && a.pair_flags && p->nhits > 0)
+      HIP_TRY(al, hipMemcpyAsync(a.pair_flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToDevice, al->stream));
+    if (lrc == 0) lrc = wfa::launch_pair(a, al->cu_count, al->stream);
+    HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
+    timer.stop();
+    if (lrc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "pairing: kernel launch failed"; return WFA_HIP_EDEVICE; }
+    p->grouped = p->nhits;
+    if (rows) HIP_TRY(al, hipMemcpyAsync(rows, s.rows, (size_t)p->nreads * WFA_PLACE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+    if (flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
+    if (nfrag > 0) HIP_TRY(al, hipMemcpyAsync(pair_rows, a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+    if (pair_flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(pair_flags, a.pair_flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
+  }
+  return WFA_HIP_OK;
+}

@@ -26,8 +26,7 @@
 #include <unistd.h>
 #include <sys/syscall.h>
 
-#include "wfa_hip.h"
-#include "wfa_common.hpp"
+#include "host_core.hpp"
 #include "wfa_pack.hpp"
 #include "wfa_general.hpp"
 #include "wfa_wide.hpp"
@@ -40,126 +39,10 @@
 #include "wfa_bilevel.hpp"
 #include "wfa_rle.hpp"
 #include "wfa_summary.hpp"
-#include "wfa_pileup.hpp"
-#include "wfa_calls.hpp"
-#include "wfa_place.hpp"
-#include "wfa_seed.hpp"
-#include "wfa_chain.hpp"
-#include "wfa_cross.hpp"
 
 #define WFA_HIP_ABI_VERSION 4
 
-static thread_local std::string g_error;
-
-// Development knobs, read from the environment ONCE per aligner in wfa_hip_create: the hot entry points
-// never call getenv.
-#define WFA_COUNTER_WORDS 256  // counters of a batch (wfa_hip_batch::d_counters)
-#define WFA_KNOBS(F)                                                                                              \
-  F(ARENA_KB) F(BAND_DEBUG) F(BAND_SLIM) F(BAND_LDS_MAX) F(BAND_NO_WIN) F(BAND_SPLIT_MIN) F(NO_TINY_INLINE) F(BILEVEL) F(BILEVEL_WIDE_LEVELS) F(BILEVEL_PER_CU) F(BILEVEL_I32) F(BILEVEL_QCAP) F(BILEVEL_LEVELS) F(BILEVEL_LDS) F(BILEVEL_NO_1024) F(BILEVEL_HUGE_MIN) F(BILEVEL_LDS_W) F(BILEVEL_NO_SEQL) F(LANE_DYN) F(LANE_DYN_WAVES) F(BAND_LEFTOVER_WAVES_PER_CU) F(BAND_NCH) F(BAND_NO_LDS) F(BAND_NO_SPLIT) F(BAND_PB) F(PIPE_TAIL) F(LEN16) F(MAILBOX) F(MAILBOX_IDLE_US) F(TILE32)     \
-  F(BAND_RECORDS) F(BAND_SPLIT_ROUNDS) F(BAND_WAVES_PER_CU) F(NO_BAND) F(NO_FAST) F(NO_SEGFULL) F(SEGFULL_PAIRS)     \
-  F(SEGFULL_STAGES) F(STAGE_TIMING) F(LANE_HEUR32) F(THREADS) F(TINY_BATCH) F(WAVES_PER_CU) F(FAST_WAVES_PER_CU) F(TIMING)          \
-  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT) F(CROSS_BAND) F(CROSS_TOPK_CHUNK) F(REDUCE_TIMING)
-enum WfaKnob {
-#define WFA_KNOB_ENUM(n) K_##n,
-  WFA_KNOBS(WFA_KNOB_ENUM)
-#undef WFA_KNOB_ENUM
-  K_COUNT
-};
-struct WfaKnobs {
-  int value[K_COUNT];
-  bool set[K_COUNT];
-  std::string fast_stages;  // WFA_HIP_FAST_STAGES (digits)
-  void load() {
-    static const char* const names[K_COUNT] = {
-#define WFA_KNOB_NAME(n) "WFA_HIP_" #n,
-        WFA_KNOBS(WFA_KNOB_NAME)
-#undef WFA_KNOB_NAME
-    };
-    for (int i = 0; i < K_COUNT; ++i) {
-      const char* v = getenv(names[i]);
-      set[i] = v && *v;
-      value[i] = set[i] ? atoi(v) : 0;
-    }
-    const char* fs = getenv("WFA_HIP_FAST_STAGES");
-    fast_stages = (fs && *fs) ? fs : "";
-  }
-};
-
-struct wfa_hip_aligner {
-  int numa_state = 0;     // 0 not looked up, 1 the device's node and its CPUs are known (`numa_cpus`), 2 no binding ever (no NUMA information, one node, too few CPUs, WFA_HIP_NUMA=0)
-  int numa_node = -1;     // NUMA node of the device's PCIe slot
-  cpu_set_t numa_cpus;    // that node's CPUs, as far as this process may run on them
-  int numa_mode = 0;      // WFA_HIP_NUMA: 0 never bind, 1 always bind the spawned upload workers to the device's node, 2 only when the caller's input lives there
-  cpu_set_t proc_cpus;    // the process's affinity mask when the aligner was created (before anything here bound a thread)
-  bool proc_cpus_valid = false;
-  int last_src_node = -1, last_bound = 0;   // the last pipelined upload: node of the caller's pages (-1 unknown), workers bound or not
-  int host_share = 1;     // aligners / processes feeding GPUs from this host (thread plan of the upload pipeline)
-  std::string rtc_note;   // why the run-time kernels were switched off (wfa_hip_batch_run), empty otherwise
-  int device = 0;
-  wfa_hip_config_t cfg;
-  WfaDevConfig dcfg;
-  int ncomp = 3;
-  WfaDevConfig gcfg;      // what the general kernel runs (= dcfg unless dcfg.lin)
-  int gncomp = 3;
-  WfaKnobs knobs;
-  hipStream_t stream = nullptr;
-  std::vector<uint8_t> pair_blob;   // wfa_hip_align_pair: the two sequences of the call, back to back
-  // lifetime: batches keep a pointer to their aligner; wfa_hip_destroy with batches still alive only marks the handle,
-  // the last batch to go frees it
-  int live_batches = 0;
-  bool destroy_pending = false;
-  // the workspace below is shared by every run of this aligner: a run enqueued on another stream than the previous
-  // one first waits for ws_event (recorded after each run), so runs are stream-ordered whatever streams callers pass
-  hipEvent_t ws_event = nullptr;
-  hipStream_t ws_last_stream = nullptr;
-  // the walks of a split stage's launch run on this stream, under the alignment kernel of the next launch (which writes
-  // the other half of the workspace); created on first use
-  hipStream_t side_stream = nullptr;
-  // round 6: what ONE launch of a split stage hands on is aligned by the stages behind it on this stream, beside the split stage's
-  // next launch (batch_run_once: "pipelined tail"); created on first use
-  hipStream_t tail_stream = nullptr;
-  hipEvent_t tail_fork[2] = {nullptr, nullptr}, tail_join = nullptr;
-  hipEvent_t band_event[4] = {nullptr, nullptr, nullptr, nullptr}, walk_event[4] = {nullptr, nullptr, nullptr, nullptr};   // [0..1] the band stages' walks, [2..3] the lane-full stage's expands
-  // second upload stream of the host-packed upload (every other slot's DMAs: two copy engines)
-  hipStream_t up_stream = nullptr;
-  hipEvent_t up_fork = nullptr, up_join = nullptr;
-  bool ws_event_recorded = false;
-  // pinned staging ring of the pipelined upload (batches of >= 256 k pairs): host threads copy pieces of the caller's
-  // pageable arrays into the slots, each slot goes to the device by DMA as soon as it is full
-  std::vector<uint8_t*> pin_slot;
-  std::vector<hipEvent_t> pin_ev;
-  std::vector<char> pin_ev_recorded;   // the slot's event was recorded: its DMA must be over before the slot is refilled
-  // single calls of a pywfa-style loop (a handful of pairs): one pinned, device-visible staging block + its device copy,
-  // allocated once; the call is then host writes -> copy kernel -> alignment kernel -> one stream sync -> host reads
-  uint8_t* tiny_h = nullptr;
-  uint8_t* tiny_hd = nullptr;
-  uint8_t* tiny_d = nullptr;
-  // the resident one-pair kernel (round 6; wfa_slim.hpp: wfa_slim_kernel_mailbox): its mailbox in pinned host memory, the stream its
-  // instances run on, the arguments the running instance was started with (another configuration / workspace: it is told to leave first)
-  wfa::SlimMailbox* mb_h = nullptr;
-  wfa::SlimMailbox* mb_d = nullptr;
-  hipStream_t mb_stream = nullptr;
-  wfa::BandArgs mb_args;
-  bool mb_args_valid = false;
-  uint32_t mb_seq = 0;
-  int mb_failures = 0;
-  size_t pin_slot_bytes = 0;
-  int cu_count = 256;
-  size_t total_mem = 0;
-  std::string err;
-  // persistent workspace for the general kernel (grown on demand)
-  int32_t* ws = nullptr;
-  size_t ws_bytes = 0;
-  // device blocks of finished batches kept for the next one (a batch takes ~20 arrays; for the small batches of
-  // a pywfa-style loop of single alignments hipMalloc / hipFree are most of the call)
-  std::multimap<size_t, void*> pool_free;
-  std::unordered_map<void*, size_t> pool_size;
-  size_t pool_cached = 0;
-};
-
-static inline int knob(const wfa_hip_aligner* al, WfaKnob k, int dflt) {
-  return al->knobs.set[k] ? al->knobs.value[k] : dflt;
-}
+thread_local std::string g_error;
 
 // Blocks of finished batches are kept for the next batch: small ones (a pywfa-style loop of single alignments) and the
 // large arrays of a big batch alike (a loop of wfa_hip_align_batch calls over equally shaped batches then allocates
@@ -172,7 +55,7 @@ static void pool_drain_cached(wfa_hip_aligner* al) {
   al->pool_free.clear(); al->pool_cached = 0;
 }
 
-static hipError_t pool_alloc(wfa_hip_aligner* al, void** p, size_t bytes) {
+hipError_t pool_alloc(wfa_hip_aligner* al, void** p, size_t bytes) {
   size_t want = 256;
   if (bytes > POOL_MAX_BLOCK) want = (bytes + 255) & ~(size_t)255;
   else while (want < bytes) want <<= 1;
@@ -194,7 +77,7 @@ static hipError_t pool_alloc(wfa_hip_aligner* al, void** p, size_t bytes) {
   return e;
 }
 
-static void pool_release(wfa_hip_aligner* al, void* p) {
+void pool_release(wfa_hip_aligner* al, void* p) {
   if (!p) return;
   auto it = al->pool_size.find(p);
   if (it == al->pool_size.end()) { (void)hipFree(p); return; }
@@ -208,86 +91,6 @@ static void pool_drain(wfa_hip_aligner* al) {
   for (auto& kv : al->pool_free) (void)hipFree(kv.second);
   al->pool_free.clear(); al->pool_size.clear(); al->pool_cached = 0;
 }
-
-struct wfa_hip_batch {
-  wfa_hip_aligner* al = nullptr;
-  // configuration in force when the batch was created: the layout of the batch (op regions, 8-bit work list, checked
-  // free ends) follows it, so run / sync / results use this snapshot, never the aligner's current configuration
-  wfa_hip_config_t cfg;
-  WfaDevConfig dcfg;
-  WfaDevConfig gcfg;       // the general kernel's configuration (= dcfg unless dcfg.lin: the original one-component distance)
-  int gncomp = 3;
-  int wild = -1;           // the wildcard letter of the 8-bit pairs when dcfg.wildcard was cleared for the 2-bit ones (round 5, below)
-  int ncomp = 3;
-  int64_t n = 0;
-  // host copies needed later
-  std::vector<int32_t> h_plen, h_tlen;
-  std::vector<int64_t> h_coff;
-  std::unique_ptr<WfaPairMeta[]> h_meta;  // kept until the batch dies: its upload may still be in flight when batch_build returns
-  std::vector<wfa::WfaPieceDesc> h_pieces;   // host-packed upload with 16-bit lengths: the pieces' first pair / first word (uploaded; kept like h_meta)
-  uint32_t* d_len16 = nullptr;               // ... the {plen, tlen} halves as uploaded, and the piece table on the device
-  wfa::WfaPieceDesc* d_pieces = nullptr;
-  int max_width = 0;       // max(plen+tlen)+3
-  int max_len = 0;         // max(plen, tlen)
-  int64_t packed_bytes = 0;  // sum of ceil(len/4) over all sequences (algorithmic 2-bit bytes)
-  int64_t ops_bytes = 0;     // sum(plen+tlen)
-  // device
-  uint8_t* d_bytes = nullptr;
-  int64_t* d_pboff = nullptr;
-  int64_t* d_tboff = nullptr;
-  WfaPairMeta* d_meta = nullptr;
-  uint32_t* d_words = nullptr;
-  uint8_t* d_flags = nullptr;
-  int32_t* d_score = nullptr;
-  int32_t* d_status = nullptr;
-  uint8_t* d_ops = nullptr;
-  int64_t* d_cigar_off = nullptr;
-  int64_t* d_cigar_begin = nullptr;
-  int32_t* d_cigar_len = nullptr;
-  uint32_t* d_list_packed = nullptr;  // worklists (nullptr = identity over all pairs)
-  uint32_t* d_list_bytes = nullptr;
-  uint32_t n_packed = 0, n_bytes = 0;
-  uint32_t* d_fb_list2[2] = {nullptr, nullptr};  // leftover lists handed from one kernel stage to the next (ping-pong)
-  const uint32_t* leftover_count = nullptr;       // device count of the pairs that reached the general kernel
-  uint32_t* d_ovf_list[2] = {nullptr, nullptr};  // pairs whose arena overflowed
-  uint32_t* d_counters = nullptr;  // [0] fallback count, [1] overflow count A, [2] overflow count B, [4..5] the pilots, [8..15] lane-full list / debug, [16..] one hand-over count per stage of a run
-  std::vector<hipEvent_t> ev;   // 2 events per run since the last sync (kernel timing)
-  size_t ev_used = 0;
-  int runs_pending = 0;
-  double ms_sum = 0.0; int ms_runs = 0;
-  bool ran = false, synced = true;
-  float last_ms = 0.f;
-  int64_t last_kernel_pairs = 0;
-  int64_t last_fallback = 0;
-  hipStream_t last_stream = nullptr;
-  bool uploads_pending = false;
-  // recorded on the aligner's stream after the last upload / memset / pack kernel of batch_build: a run on another stream
-  // waits for it (the host-packed upload returns with its DMAs still in flight)
-  hipEvent_t upload_event = nullptr;
-  int stage_pick = 0;  // first register-kernel stage chosen by the pilot of the first run (0 = not yet): 16, 32 or 64 lanes
-  int narrow_pick = 0; // stage_pick 16, score only: the 8-diagonal lane stage in front of the 16-diagonal one (1) or not (2), 0 undecided
-  int narrow_permille = -1;   // ... and the share of its pilot's sample it handed on (-1: no pilot), which sizes the slices of the stage behind it
-  int segh_pick = 0;   // the same for the general form of the 32-lane segments (wfa_seg_kernel<.., HEUR>)
-  int band_pick = 0;   // exact reads of 300 - 1 200 bases: the 256-diagonal register window first (1) or not (2: its pilot handed on most pairs), 0 undecided
-  int laneh_pick = 0;  // general score-only form of the lane kernel first (wf-adaptive / free ends / step limit): 1 yes, 2 no (its pilot), 0 undecided
-  int64_t arena_ints = 0;  // FULL: arena size used by the last launch (the part that grows 8x when a pair overflows it)
-  int64_t arena_fixed = 0; // FULL, piggy-back history of the general kernel: the score-only ring in front of the growing part
-  // device-side result surface (RLE)
-  int32_t* d_plen = nullptr; int32_t* d_tlen = nullptr; int32_t* d_run_count = nullptr; int32_t* d_locs = nullptr;
-  int64_t* d_run_off = nullptr; int64_t rle_total = -1;
-};
-
-#define HIP_TRY(al, expr)                                                                      \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) {                                                                    \
-      char buf_[512];                                                                          \
-      snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      if (al) (al)->err = buf_;                                                                \
-      g_error = buf_;                                                                          \
-      return WFA_HIP_EDEVICE;                                                                  \
-    }                                                                                          \
-  } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // configuration
@@ -421,7 +224,7 @@ static void map_to_gap_affine(const wfa_hip_config_t& c, WfaDevConfig* d, int* n
 // gd / gncomp: the configuration the GENERAL kernel runs — the same, unless a one-component distance with CIGARs was mapped (d->lin)
 // d starts from zero: wfa_hip_set_config passes the aligner's live configuration, and nothing of the previous one may carry over (the
 // snapshots orig / orig1 below used to keep its score_mode / sw_match, which a LIN configuration's general kernel then reported with)
-static void derive_dev_config(const wfa_hip_config_t& c, WfaDevConfig* d, int* ncomp, WfaDevConfig* gd = nullptr, int* gncomp = nullptr) {
+void derive_dev_config(const wfa_hip_config_t& c, WfaDevConfig* d, int* ncomp, WfaDevConfig* gd, int* gncomp) {
   const bool two = (c.distance == WFA_DIST_AFFINE2P);
   *d = WfaDevConfig{};
   d->metric = c.distance;
@@ -542,10 +345,10 @@ extern "C" wfa_hip_aligner_t* wfa_hip_create(const wfa_hip_config_t* cfg, int de
 
 static void mailbox_quit(wfa_hip_aligner* al);
 // whatever takes the device (a batch, a set, an index build) first tells a running instance of the resident one-pair kernel to leave
-static inline void mailbox_release(wfa_hip_aligner* al) {
+void mailbox_release(wfa_hip_aligner* al) {
   if (al->mb_h && __atomic_load_n(&al->mb_h->alive, __ATOMIC_ACQUIRE) != 0) mailbox_quit(al);
 }
-static void aligner_free(wfa_hip_aligner* al) {
+void aligner_free(wfa_hip_aligner* al) {
   (void)hipSetDevice(al->device);
   if (al->ws) (void)hipFree(al->ws);
   pool_drain(al);
@@ -597,7 +400,15 @@ extern "C" const char* wfa_hip_last_error(const wfa_hip_aligner_t* al) { return 
 // ------------------------------------------------------------------------------------------------
 // batches
 // ------------------------------------------------------------------------------------------------
-static void batch_free(wfa_hip_batch* b) {
+// a new batch, counted among the aligner's live ones (batch_free takes it off again)
+wfa_hip_batch* batch_new(wfa_hip_aligner* al) {
+  wfa_hip_batch* b = new wfa_hip_batch();
+  b->al = al;
+  al->live_batches += 1;
+  return b;
+}
+
+void batch_free(wfa_hip_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->al->device);
   void* ptrs[] = {b->d_bytes, b->d_pboff, b->d_tboff, b->d_meta, b->d_words, b->d_flags, b->d_score, b->d_status,
@@ -986,28 +797,28 @@ static int pilot_lane_heur(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t st
 static int pilot_band(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream);
 
 // the pilots of a freshly built batch (or of a band of a cross run: no-ops once a band has picked)
-static int run_pilots(wfa_hip_aligner* al, wfa_hip_batch* b) {
+int run_pilots(wfa_hip_aligner* al, wfa_hip_batch* b) {
   { const int prc = pilot_first_width(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
   { const int prc = pilot_lane_heur(al, b, al->stream); if (prc != WFA_HIP_OK) return prc; }
   return pilot_band(al, b, al->stream);
 }
 
 // the tail of every builder: the pilots, then the event behind the last upload / memset / generator of the build (wfa_hip_batch::upload_event)
-static int finish_batch_build(wfa_hip_aligner* al, wfa_hip_batch* b) {
+int finish_batch_build(wfa_hip_aligner* al, wfa_hip_batch* b) {
   { const int prc = run_pilots(al, b); if (prc != WFA_HIP_OK) return prc; }
   HIP_TRY(al, hipEventCreateWithFlags(&b->upload_event, hipEventDisableTiming));
   HIP_TRY(al, hipEventRecord(b->upload_event, al->stream));
   return WFA_HIP_OK;
 }
 
-static bool wildcard_in_acgt(int wc) {
+bool wildcard_in_acgt(int wc) {
   return wc == 'A' || wc == 'C' || wc == 'G' || wc == 'T' || wc == 'a' || wc == 'c' || wc == 'g' || wc == 't';
 }
 
 // What every batch has, allocated and cleared: the metadata, `total_words` packed words of which the last `zero_tail` are zero (reads
 // past the last sequence), flags, results, the fall-back lists and the counters; scope full: the op regions laid out by b->h_coff
 // (filled by the caller: b->n + 1 entries) and what goes with them.  b->n and b->ops_bytes are set.
-static int batch_alloc_common(wfa_hip_aligner* al, wfa_hip_batch* b, uint64_t total_words, int zero_tail) {
+int batch_alloc_common(wfa_hip_aligner* al, wfa_hip_batch* b, uint64_t total_words, int zero_tail) {
   const int64_t n = b->n;
   const size_t nn = (size_t)std::max<int64_t>(n, 1);
   HIP_TRY(al, pool_alloc(al, (void**)&b->d_meta, nn * sizeof(WfaPairMeta)));
@@ -1037,7 +848,7 @@ static int batch_alloc_common(wfa_hip_aligner* al, wfa_hip_batch* b, uint64_t to
 // ---- building an explicit batch: adopt the configuration, scan the lengths, allocate, upload by form ---------------------------------
 
 // the configuration a batch is laid out and run under, taken from the aligner when the batch is built (batch_build, batch_build_list)
-static void batch_adopt_config(wfa_hip_aligner* al, wfa_hip_batch* b) {
+void batch_adopt_config(wfa_hip_aligner* al, wfa_hip_batch* b) {
   b->cfg = al->cfg; b->dcfg = al->dcfg; b->ncomp = al->ncomp; b->gcfg = al->gcfg; b->gncomp = al->gncomp;
   // Round 5: a wildcard letter outside ACGT cannot occur in a pair whose letters are all ACGT — such pairs take the 2-bit kernels as if
   // no wildcard were set (same result: nothing in them matches by wildcard), only the pairs holding other letters are aligned on their
@@ -1047,7 +858,7 @@ static void batch_adopt_config(wfa_hip_aligner* al, wfa_hip_batch* b) {
 
 // the two work lists of a batch that has byte pairs (ascending; `lp` may be empty: every pair on its bytes).  async: copies on al->stream,
 // the caller keeps the vectors alive until it has waited for the stream; otherwise blocking copies
-static int upload_work_lists(wfa_hip_aligner* al, wfa_hip_batch* b, const std::vector<uint32_t>& lp, const std::vector<uint32_t>& lb, bool async) {
+int upload_work_lists(wfa_hip_aligner* al, wfa_hip_batch* b, const std::vector<uint32_t>& lp, const std::vector<uint32_t>& lb, bool async) {
   if (lb.empty()) return WFA_HIP_OK;
   auto put = [&](uint32_t** dst, const std::vector<uint32_t>& l) -> int {
     HIP_TRY(al, pool_alloc(al, (void**)dst, l.size() * sizeof(uint32_t)));
@@ -1059,28 +870,10 @@ static int upload_work_lists(wfa_hip_aligner* al, wfa_hip_batch* b, const std::v
   return lp.empty() ? WFA_HIP_OK : put(&b->d_list_packed, lp);
 }
 
-// parts 0 .. nparts - 1 of a pass over a batch on at most `team` host threads, the caller's among them (the parts are claimed from a counter)
-template <class Fn> static void run_parts(int nparts, int team, Fn&& fn) {
-  if (nparts == 1) { fn(0); return; }
-  std::atomic<int> nextp(0);
-  auto loop = [&]() { for (int t = nextp.fetch_add(1); t < nparts; t = nextp.fetch_add(1)) fn(t); };
-  std::vector<std::thread> th;
-  for (int t = 1; t < std::min(team, nparts); ++t) th.emplace_back(loop);
-  loop();
-  for (auto& x : th) x.join();
-}
-
-// why a part of a batch was refused (PART_OVER_LIGHT is no refusal: scan_lengths leaves the host-packed form on it)
-enum PartError { PART_OK = 0, PART_NEGATIVE = 1, PART_TOO_LONG = 2, PART_ENDS_FREE = 3, PART_OVER_LIGHT = 4 };
-static const char* part_error_message(int err) {
+const char* part_error_message(int err) {
   return err == PART_NEGATIVE ? "negative length or offset" : err == PART_TOO_LONG ? "sequence too long"
        : err == PART_ENDS_FREE ? "Ends-free parameters must be not larger than the sequences" : "";
 }
-// wavefront_align.c:86-102: the reference exit(1)s here
-static inline bool free_ends_exceed(const wfa_hip_config_t& c, int pl, int tl) {
-  return c.span == WFA_SPAN_ENDSFREE && (c.pattern_begin_free > pl || c.pattern_end_free > pl || c.text_begin_free > tl || c.text_end_free > tl);
-}
-
 // the caller's arrays.  in2bit: `seqs` holds 2-bit reads in the reference's packed form (wavefront_sequences.c:102-139: four bases per
 // byte, base j of a byte in bits 2j..2j+1, A 0 / C 1 / G 2 / T 3), a sequence of len bases = (len + 3) / 4 bytes at its BYTE offset
 struct BatchInput {
@@ -1690,9 +1483,7 @@ static wfa_hip_batch* batch_create_nosync(wfa_hip_aligner_t* al, int64_t n, cons
     al->err = "invalid batch arguments"; g_error = al->err; return nullptr;
   }
   if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
-  wfa_hip_batch* b = new wfa_hip_batch();
-  b->al = al;
-  al->live_batches += 1;
+  wfa_hip_batch* b = batch_new(al);
   if (in2bit && al->cfg.wildcard >= 0) { al->err = "2-bit reads cannot hold a wildcard letter"; g_error = al->err; batch_free(b); return nullptr; }
   const int rc = batch_build(al, b, n, seqs, p_off, p_len, t_off, t_len, in2bit);
   if (rc != WFA_HIP_OK) { g_error = al->err; batch_free(b); return nullptr; }
@@ -1842,7 +1633,7 @@ static int wait_for_workspace(wfa_hip_aligner* al, hipStream_t stream) {
   return WFA_HIP_OK;
 }
 
-static int64_t free_budget(wfa_hip_aligner* al) {
+int64_t free_budget(wfa_hip_aligner* al) {
   size_t fr = 0, tot = 0;
   if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = al->total_mem / 2;
   // what we already hold as workspace can be re-used, and so can the idle blocks of the pool (drained on demand)
@@ -3391,23 +3182,7 @@ extern "C" int wfa_hip_batch_rle_runs(wfa_hip_batch_t* b, uint8_t* run_code, int
 extern "C" int64_t wfa_hip_batch_fallback_pairs(const wfa_hip_batch_t* b) { return b ? b->last_fallback : 0; }
 
 // ---- device-side per-pair summary (csrc/wfa_summary.hpp) ------------------------------------------------
-// WFA_HIP_REDUCE_TIMING=1 (a development knob): the summary, pileup, calls, sites and placement kernels are bracketed by two events and their
-// HIP-event time goes to stderr, one line per call (tools/probes/pileup_index.py and pileup_calls.py read it).
-struct ReduceTimer {
-  wfa_hip_aligner* al; const char* what; int64_t n;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  const char* unit;
-  ReduceTimer(wfa_hip_aligner* al_, const char* what_, int64_t n_, const char* unit_ = "pairs") : al(al_), what(what_), n(n_), unit(unit_) {
-    if (knob(al, K_REDUCE_TIMING, 0) && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess) (void)hipEventRecord(ev[0], al->stream);
-  }
-  void stop() { if (ev[1]) (void)hipEventRecord(ev[1], al->stream); }
-  ~ReduceTimer() {   // (after the caller's stream synchronisation)
-    float ms = 0.f;
-    if (ev[1] && hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-      fprintf(stderr, "[wfa_hip] %s kernel %.4f ms (%lld %s)\n", what, ms, (long long)n, unit);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  }
-};
+static_assert(WFA_SUMMARY_COLS == WFA_HIP_SUMMARY_COLS, "columns of the kernels and of the ABI");
 
 extern "C" int wfa_hip_batch_summary(wfa_hip_batch_t* b, int32_t* summary) {
   if (!b) return WFA_HIP_EINVAL;
@@ -4007,1729 +3782,5 @@ extern "C" int wfa_hip_multi_align_batch(wfa_hip_multi_t* m, int64_t n, const ui
   for (auto& x : th) x.join();
   for (int d = 0; d < nd; ++d)
     if (rcs[(size_t)d] != WFA_HIP_OK) { m->err = "device " + std::to_string(m->al[(size_t)d]->device) + ": " + m->al[(size_t)d]->err; return rcs[(size_t)d]; }
-  return WFA_HIP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// score matrices (include/wfa_hip.h: sequence sets packed once, cross products in bands of rows, csrc/wfa_cross.hpp)
-// ------------------------------------------------------------------------------------------------
-struct wfa_hip_seqset {
-  wfa_hip_aligner* al = nullptr;
-  int64_t n = 0;
-  int wildcard = -1;               // the aligner's wildcard when the set was packed
-  std::vector<int32_t> h_len;
-  std::vector<uint8_t> h_flag;     // 1: a letter outside ACGT (its pairs are aligned on their bytes)
-  std::vector<std::vector<int32_t>> h_runs;   // flagged sequences only: the runs of such letters as (start, end) pairs, ascending (windowed batches)
-  uint64_t nwords = 0;             // words of the table, without the 4 zero words behind it
-  int64_t nbytes = 0;              // bytes of the ASCII blob
-  uint32_t* d_words = nullptr;     // one word-aligned run per sequence (wfa_hip_pack_2bit's layout)
-  uint8_t* d_bytes = nullptr;      // the sequences' bytes, back to back (a byte pair needs both of its sequences' bytes)
-  uint32_t* d_woff = nullptr; int32_t* d_len = nullptr; int64_t* d_boff = nullptr; uint8_t* d_flag = nullptr;
-  mutable uint16_t* d_mask = nullptr;   // the seed finder's view of h_runs: one bit per base, 16 per word (seqset_mask: built on first use)
-};
-
-static_assert(WFA_CROSS_MAX_K == WFA_HIP_CROSS_MAX_K, "top-k bound of the kernels and of the ABI");
-
-struct wfa_hip_cross {
-  wfa_hip_aligner* al = nullptr;
-  int64_t m = 0, n = 0;
-  int want = 0;
-  int32_t* d_score = nullptr; int32_t* d_status = nullptr;           // dense: m x n
-  int32_t* d_ci = nullptr; int32_t* d_cj = nullptr; int32_t* d_cs = nullptr;   // completed pairs
-  int k = 0;
-  uint64_t* d_topk = nullptr;                                          // top-k: m x k keys (wfa_cross.hpp), descending per row
-  int64_t count = 0, cap = 0;
-  double ms = 0.0;
-  int64_t pairs = 0;
-};
-
-static void aligner_release_ref(wfa_hip_aligner* al) {
-  if (--al->live_batches == 0 && al->destroy_pending) aligner_free(al);
-}
-
-extern "C" void wfa_hip_seqset_destroy(wfa_hip_seqset_t* s) {
-  if (!s) return;
-  wfa_hip_aligner* al = s->al;
-  (void)hipSetDevice(al->device);
-  void* ptrs[] = {s->d_words, s->d_bytes, s->d_woff, s->d_len, s->d_boff, s->d_flag, s->d_mask};
-  for (void* p : ptrs) pool_release(al, p);
-  delete s;
-  aligner_release_ref(al);
-}
-
-// the runs of letters host_pack_seq flags (anything but upper-case ACGT) in one sequence
-static void flagged_runs(const uint8_t* seq, int32_t len, std::vector<int32_t>& runs) {
-  for (int32_t p = 0; p < len;) {
-    const uint8_t ch = seq[p];
-    if (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T') { ++p; continue; }
-    int32_t e = p + 1;
-    while (e < len && !(seq[e] == 'A' || seq[e] == 'C' || seq[e] == 'G' || seq[e] == 'T')) ++e;
-    runs.push_back(p); runs.push_back(e);
-    p = e;
-  }
-}
-
-static int seqset_build(wfa_hip_aligner* al, wfa_hip_seqset* s, int64_t n, const uint8_t* seqs, const int64_t* off, const int32_t* len) {
-  s->n = n;
-  s->h_len.assign(len, len + n);
-  s->h_flag.assign((size_t)n, 0);
-  s->h_runs.assign((size_t)n, std::vector<int32_t>());
-  std::vector<uint32_t> woff((size_t)n);
-  std::vector<int64_t> boff((size_t)n);
-  uint64_t w = 0;
-  int64_t bb = 0;
-  for (int64_t k = 0; k < n; ++k) {
-    if (len[k] < 0 || off[k] < 0) { al->err = "negative length or offset"; return WFA_HIP_EINVAL; }
-    if (len[k] > INT_MAX / 4 - 8) { al->err = "sequence too long"; return WFA_HIP_EINVAL; }
-    woff[(size_t)k] = (uint32_t)w; w += (uint64_t)((len[k] + 15) >> 4);
-    boff[(size_t)k] = bb; bb += len[k];
-    if (w > 0x7FFFFFF0ull) { al->err = "sequence set too large: more than 2^31 packed words"; return WFA_HIP_EINVAL; }
-  }
-  s->nwords = w; s->nbytes = bb;
-  std::vector<uint32_t> words((size_t)w + 4, 0u);
-  std::vector<uint8_t> bytes((size_t)bb + 64, 0u);
-  // packed and copied on host threads: m + n sequences, once
-  const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, std::thread::hardware_concurrency()), (bb >> 20) + 1));
-  auto work = [&](int t) {
-    for (int64_t k = n * t / nthr, hi = n * (t + 1) / nthr; k < hi; ++k) {
-      s->h_flag[(size_t)k] = wfa::host_pack_seq(seqs + off[k], len[k], words.data() + woff[(size_t)k], -1) ? 1 : 0;
-      if (s->h_flag[(size_t)k]) flagged_runs(seqs + off[k], len[k], s->h_runs[(size_t)k]);
-      if (len[k] > 0) memcpy(bytes.data() + boff[(size_t)k], seqs + off[k], (size_t)len[k]);
-    }
-  };
-  std::vector<std::thread> th;
-  for (int t = 1; t < nthr; ++t) th.emplace_back(work, t);
-  work(0);
-  for (auto& x : th) x.join();
-  const size_t nn = (size_t)std::max<int64_t>(n, 1);
-  HIP_TRY(al, pool_alloc(al, (void**)&s->d_words, words.size() * sizeof(uint32_t)));
-  HIP_TRY(al, pool_alloc(al, (void**)&s->d_bytes, bytes.size()));
-  HIP_TRY(al, pool_alloc(al, (void**)&s->d_woff, nn * sizeof(uint32_t)));
-  HIP_TRY(al, pool_alloc(al, (void**)&s->d_len, nn * sizeof(int32_t)));
-  HIP_TRY(al, pool_alloc(al, (void**)&s->d_boff, nn * sizeof(int64_t)));
-  HIP_TRY(al, pool_alloc(al, (void**)&s->d_flag, nn));
-  HIP_TRY(al, hipMemcpy(s->d_words, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_TRY(al, hipMemcpy(s->d_bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
-  if (n > 0) {
-    HIP_TRY(al, hipMemcpy(s->d_woff, woff.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(al, hipMemcpy(s->d_len, len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(al, hipMemcpy(s->d_boff, boff.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-    HIP_TRY(al, hipMemcpy(s->d_flag, s->h_flag.data(), (size_t)n, hipMemcpyHostToDevice));
-  }
-  return WFA_HIP_OK;
-}
-
-extern "C" wfa_hip_seqset_t* wfa_hip_seqset_create(wfa_hip_aligner_t* al, int64_t n, const uint8_t* seqs, const int64_t* off, const int32_t* len) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  if (n < 0 || n > 0x7FFFFFF0ll || (n > 0 && (!seqs || !off || !len))) { al->err = "invalid sequence set arguments"; g_error = al->err; return nullptr; }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
-  mailbox_release(al);   // (the resident one-pair kernel: sets take the device)
-  wfa_hip_seqset* s = new wfa_hip_seqset();
-  s->al = al;
-  s->wildcard = al->cfg.wildcard;
-  al->live_batches += 1;
-  if (seqset_build(al, s, n, seqs, off, len) != WFA_HIP_OK) { g_error = al->err; wfa_hip_seqset_destroy(s); return nullptr; }
-  return s;
-}
-
-extern "C" int64_t wfa_hip_plan_cross_bands(int64_t m, int64_t n, int triangle, int64_t max_pairs, int64_t* row_begin, int64_t cap) {
-  if (m < 0 || n < 0 || max_pairs < 1 || (triangle != 0 && triangle != 1)) return WFA_HIP_EINVAL;
-  const int64_t rows = (n == 0) ? 0 : (triangle ? n : m);
-  if (row_begin && cap >= 1) row_begin[0] = 0;
-  int64_t nb = 0, r = 0;
-  while (r < rows) {
-    int64_t acc = 0, r1 = r;
-    if (!triangle) r1 = std::min(rows, r + std::max<int64_t>(1, max_pairs / n));
-    else
-      while (r1 < rows) {
-        const int64_t wr = n - r1;
-        if (r1 > r && acc + wr > max_pairs) break;
-        acc += wr; ++r1;
-      }
-    r = r1; ++nb;
-    if (row_begin && nb < cap) row_begin[nb] = r;
-  }
-  return nb;
-}
-
-extern "C" void wfa_hip_cross_destroy(wfa_hip_cross_t* x) {
-  if (!x) return;
-  wfa_hip_aligner* al = x->al;
-  (void)hipSetDevice(al->device);
-  (void)hipStreamSynchronize(al->stream);
-  void* ptrs[] = {x->d_score, x->d_status, x->d_ci, x->d_cj, x->d_cs, x->d_topk};
-  for (void* p : ptrs) pool_release(al, p);
-  delete x;
-  aligner_release_ref(al);
-}
-
-// the device blocks of one cross run besides the batch view's (released when the run returns)
-struct CrossScratch {
-  wfa_hip_aligner* al;
-  std::vector<void*> blocks;
-  uint32_t* h_cnt = nullptr;          // pinned: the completed pairs of the last two bands
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  template <class T> int alloc(T** p, size_t count) {
-    HIP_TRY(al, pool_alloc(al, (void**)p, std::max<size_t>(count, 1) * sizeof(T)));
-    blocks.push_back(*p);
-    return WFA_HIP_OK;
-  }
-  ~CrossScratch() {
-    (void)hipStreamSynchronize(al->stream);
-    for (void* p : blocks) pool_release(al, p);
-    if (h_cnt) (void)hipHostFree(h_cnt);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  }
-};
-
-static int cross_run_impl(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wfa_hip_seqset* T, int want, int top_k, wfa_hip_cross* x) {
-  const bool ava = (T == nullptr);
-  if (ava) T = P;
-  if (!P || P->al != al || T->al != al) { al->err = "sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (want <= 0 || (want & ~(WFA_HIP_CROSS_DENSE | WFA_HIP_CROSS_COMPLETED | WFA_HIP_CROSS_TOPK)) != 0) {
-    al->err = "want: a combination of WFA_HIP_CROSS_DENSE, WFA_HIP_CROSS_COMPLETED and WFA_HIP_CROSS_TOPK"; return WFA_HIP_EINVAL;
-  }
-  if ((want & WFA_HIP_CROSS_TOPK) && (top_k < 1 || top_k > WFA_HIP_CROSS_MAX_K)) { al->err = "k: 1 .. WFA_HIP_CROSS_MAX_K (64)"; return WFA_HIP_EINVAL; }
-  if (P->wildcard != al->cfg.wildcard || T->wildcard != al->cfg.wildcard) { al->err = "sequence set packed under another wildcard: create it again"; return WFA_HIP_EINVAL; }
-  wfa_hip_config_t c = al->cfg;
-  c.scope = WFA_SCOPE_SCORE;
-  const int64_t m = P->n, n = T->n;
-  x->m = m; x->n = n; x->want = want;
-  const bool topk = (want & WFA_HIP_CROSS_TOPK) != 0;
-  if (topk) x->k = top_k;
-  if (c.span == WFA_SPAN_ENDSFREE && m > 0 && n > 0) {   // (wavefront_align.c:86-102, as batch_build)
-    const int32_t minp = *std::min_element(P->h_len.begin(), P->h_len.end()), mint = *std::min_element(T->h_len.begin(), T->h_len.end());
-    if (c.pattern_begin_free > minp || c.pattern_end_free > minp || c.text_begin_free > mint || c.text_end_free > mint) {
-      al->err = "Ends-free parameters must be not larger than the sequences"; return WFA_HIP_EINVAL;
-    }
-  }
-  const bool dense = (want & WFA_HIP_CROSS_DENSE) != 0, completed = (want & WFA_HIP_CROSS_COMPLETED) != 0;
-  if (dense && m * n > 0) {
-    HIP_TRY(al, pool_alloc(al, (void**)&x->d_score, (size_t)(m * n) * sizeof(int32_t)));
-    HIP_TRY(al, pool_alloc(al, (void**)&x->d_status, (size_t)(m * n) * sizeof(int32_t)));
-  }
-  if (m == 0 || n == 0) return WFA_HIP_OK;   // (top-k: all padding, written by wfa_hip_cross_topk)
-  // the mirror rule: the score of (P[j], P[i]) is that of (P[i], P[j]) when nothing tells the pattern from the text — no heuristic (their
-  // cut-offs look at offsets, not at the alignment's symmetry) and the same free ends on both sides
-  const bool mirror = ava && c.heuristic == WFA_HEUR_NONE &&
-                      (c.span == WFA_SPAN_END2END || (c.pattern_begin_free == c.text_begin_free && c.pattern_end_free == c.text_end_free));
-  const int tri = mirror ? 1 : 0;
-  const int64_t rows = tri ? n : m;
-  const bool all_bytes = c.wildcard >= 0 && wildcard_in_acgt(c.wildcard);
-  // the 2-bit / byte split of every row, from the sets' flags (host prefix sums: no band reads anything back for it)
-  std::vector<int64_t> col_flag((size_t)n + 1, 0), row_bytes((size_t)rows + 1, 0);
-  for (int64_t j = 0; j < n; ++j) col_flag[(size_t)j + 1] = col_flag[(size_t)j] + ((all_bytes || T->h_flag[(size_t)j]) ? 1 : 0);
-  for (int64_t i = 0; i < rows; ++i) {
-    const bool pf = all_bytes || P->h_flag[(size_t)i];
-    const int64_t cnt = tri ? (pf ? n - i : col_flag[(size_t)n] - col_flag[(size_t)i]) : (pf ? n : col_flag[(size_t)n]);
-    row_bytes[(size_t)i + 1] = row_bytes[(size_t)i] + cnt;
-  }
-  const bool any_bytes = row_bytes[(size_t)rows] > 0;
-  // the longest text at or behind column j (a triangle row's columns)
-  std::vector<int32_t> suf_t((size_t)n + 1, 0);
-  for (int64_t j = n - 1; j >= 0; --j) suf_t[(size_t)j] = std::max(suf_t[(size_t)j + 1], T->h_len[(size_t)j]);
-  // band size: the knob, else what the lengths and the free memory allow (about 100 B of band arrays per pair; the workspace of the
-  // general kernel is sized from the reads, not from the band)
-  int slot_p = 0, slot_t = 0;   // words of the longest pattern / text of up to WFA_FAST_MAX_LEN bases (a pair's slot, below)
-  for (int32_t l : P->h_len) if (l <= WFA_FAST_MAX_LEN) slot_p = std::max(slot_p, (l + 15) >> 4);
-  for (int32_t l : T->h_len) if (l <= WFA_FAST_MAX_LEN) slot_t = std::max(slot_t, (l + 15) >> 4);
-  int64_t band_max = knob(al, K_CROSS_BAND, 0);
-  if (band_max <= 0) band_max = std::max<int64_t>(65536, std::min<int64_t>((int64_t)1 << 23, free_budget(al) / 4 / (112 + 4 * (slot_p + slot_t))));
-  band_max = std::min<int64_t>(band_max, (int64_t)1 << 30);
-  band_max = std::max<int64_t>(1, std::min<int64_t>(band_max, (int64_t)((0xFFFFFFF0ull - P->nwords - T->nwords - 64) / (uint64_t)std::max(1, slot_p + slot_t))));
-  const int64_t nbands = wfa_hip_plan_cross_bands(m, n, tri, band_max, nullptr, 0);
-  std::vector<int64_t> rb((size_t)nbands + 1);
-  wfa_hip_plan_cross_bands(m, n, tri, band_max, rb.data(), nbands + 1);
-  auto tri_before = [n](int64_t i) { return i * n - (i * (i - 1)) / 2; };
-  int64_t cap = 0;
-  for (int64_t k = 0; k < nbands; ++k) cap = std::max(cap, tri ? tri_before(rb[(size_t)k + 1]) - tri_before(rb[(size_t)k]) : (rb[(size_t)k + 1] - rb[(size_t)k]) * n);
-  CrossScratch sc{al};
-  // the batch view: one for every band, so that the pilots' picks of the first large band hold for the later ones
-  wfa_hip_batch* b = new wfa_hip_batch();
-  b->al = al;
-  al->live_batches += 1;
-  struct ViewGuard {   // (the result and list pointers of the last band are the matrix's or the scratch's: not the view's to release)
-    wfa_hip_batch* b;
-    ~ViewGuard() { b->d_score = b->d_status = nullptr; b->d_list_packed = b->d_list_bytes = nullptr; batch_free(b); }
-  } view_guard{b};
-  b->cfg = c;
-  derive_dev_config(c, &b->dcfg, &b->ncomp, &b->gcfg, &b->gncomp);
-  if (!al->dcfg.rtc) { b->dcfg.rtc = 0; b->gcfg.rtc = 0; }   // (the run-time path failed earlier on this aligner)
-  if (c.wildcard >= 0 && !all_bytes) { b->wild = c.wildcard; b->dcfg.wildcard = -1; b->gcfg.wildcard = -1; }   // (as batch_build)
-  // One word table per run: the pattern set's words, the text set's (cross mode), 64 zero words, then a slot per pair of a band for the
-  // pairs of up to WFA_FAST_MAX_LEN bases: the register stages (wfa_lane.hpp, wfa_seg.hpp) fetch a pair's pattern and text words in ONE
-  // load, the text's words right behind the pattern's, so the generator copies both sequences of such a pair into its slot.  Longer pairs
-  // point into the sets' words (every other stage reads pattern and text through their own offsets).
-  const uint32_t t_wshift = ava ? 0u : (uint32_t)P->nwords;
-  const int64_t t_bshift = ava ? 0 : P->nbytes;
-  const uint64_t table_words = P->nwords + (ava ? 0 : T->nwords) + 64;
-  HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)(P->nbytes + (ava ? 0 : T->nbytes) + 64)));
-  HIP_TRY(al, hipMemcpyAsync(b->d_bytes, P->d_bytes, (size_t)P->nbytes + (ava ? 64 : 0), hipMemcpyDeviceToDevice, al->stream));
-  if (!ava) HIP_TRY(al, hipMemcpyAsync(b->d_bytes + P->nbytes, T->d_bytes, (size_t)T->nbytes + 64, hipMemcpyDeviceToDevice, al->stream));
-  const uint64_t slot_words = (uint64_t)slot_p + slot_t;
-  if (table_words + (uint64_t)cap * slot_words > 0xFFFFFFF0ull) { al->err = "sequence sets too large: more than 2^32 words of a band"; return WFA_HIP_EINVAL; }
-  HIP_TRY(al, pool_alloc(al, (void**)&b->d_words, (size_t)(table_words + (uint64_t)cap * slot_words) * sizeof(uint32_t)));
-  HIP_TRY(al, hipMemcpyAsync(b->d_words, P->d_words, (size_t)P->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
-  if (!ava) HIP_TRY(al, hipMemcpyAsync(b->d_words + P->nwords, T->d_words, (size_t)T->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
-  HIP_TRY(al, hipMemsetAsync(b->d_words + table_words - 64, 0, 64 * sizeof(uint32_t), al->stream));
-  const size_t ncap = (size_t)cap;
-  HIP_TRY(al, pool_alloc(al, (void**)&b->d_meta, ncap * sizeof(WfaPairMeta)));
-  HIP_TRY(al, pool_alloc(al, (void**)&b->d_flags, ncap));
-  HIP_TRY(al, pool_alloc(al, (void**)&b->d_fb_list2[0], ncap * sizeof(uint32_t)));
-  HIP_TRY(al, pool_alloc(al, (void**)&b->d_fb_list2[1], ncap * sizeof(uint32_t)));
-  HIP_TRY(al, pool_alloc(al, (void**)&b->d_counters, WFA_COUNTER_WORDS * sizeof(uint32_t)));
-  HIP_TRY(al, hipMemsetAsync(b->d_counters, 0, WFA_COUNTER_WORDS * sizeof(uint32_t), al->stream));
-  uint32_t *list_packed = nullptr, *list_bytes = nullptr;
-  int64_t *d_row_bytes = nullptr, *d_col_flag = nullptr;
-  if (any_bytes) {
-    HIP_TRY(al, pool_alloc(al, (void**)&b->d_pboff, ncap * sizeof(int64_t)));
-    HIP_TRY(al, pool_alloc(al, (void**)&b->d_tboff, ncap * sizeof(int64_t)));
-    if (sc.alloc(&list_packed, ncap) || sc.alloc(&list_bytes, ncap) || sc.alloc(&d_row_bytes, row_bytes.size()) || sc.alloc(&d_col_flag, col_flag.size()))
-      return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpy(d_row_bytes, row_bytes.data(), row_bytes.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    HIP_TRY(al, hipMemcpy(d_col_flag, col_flag.data(), col_flag.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  }
-  // a band's own score / status: always, except rectangular bands of a dense run (those ARE the matrix's rows r0 .. r1)
-  int32_t *band_score = nullptr, *band_status = nullptr;
-  if (tri || !dense) {
-    if (sc.alloc(&band_score, ncap) || sc.alloc(&band_status, ncap)) return WFA_HIP_EDEVICE;
-  }
-  // completed pairs: each band compacts into one of two staging lists; the band before is appended to the handle's list once its
-  // count is known (read while the next band runs)
-  int32_t *st_i[2] = {nullptr, nullptr}, *st_j[2] = {nullptr, nullptr}, *st_s[2] = {nullptr, nullptr};
-  uint32_t *blk = nullptr, *d_cnt = nullptr;
-  if (completed) {
-    for (int h = 0; h < 2; ++h)
-      if (sc.alloc(&st_i[h], ncap) || sc.alloc(&st_j[h], ncap) || sc.alloc(&st_s[h], ncap)) return WFA_HIP_EDEVICE;
-    if (sc.alloc(&blk, (ncap + WFA_CROSS_CHUNK - 1) / WFA_CROSS_CHUNK) || sc.alloc(&d_cnt, 2)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipHostMalloc((void**)&sc.h_cnt, 2 * sizeof(uint32_t), hipHostMallocDefault));
-    for (int h = 0; h < 2; ++h) HIP_TRY(al, hipEventCreateWithFlags(&sc.ev[h], hipEventDisableTiming));
-  }
-  // top-k: the running lists (m x k keys, "empty") and the row pass's chunk lists.  A band row longer than one chunk is split into
-  // chunks of `chunk` cells, each reduced by a wave of its own (a band of a wide rectangle holds few rows); the chunk grows until the
-  // largest band's chunk lists fit a share of the free memory
-  int64_t chunk = 0;
-  uint64_t* part = nullptr;
-  auto band_chunks = [&](int64_t r0b) { const int64_t len = tri ? n - r0b : n; return len > chunk ? (len + chunk - 1) / chunk : (int64_t)0; };
-  if (topk) {
-    HIP_TRY(al, pool_alloc(al, (void**)&x->d_topk, (size_t)m * (size_t)top_k * sizeof(uint64_t)));
-    HIP_TRY(al, hipMemsetAsync(x->d_topk, 0, (size_t)m * (size_t)top_k * sizeof(uint64_t), al->stream));
-    chunk = std::max<int64_t>(64, ((int64_t)knob(al, K_CROSS_TOPK_CHUNK, 4096) + 63) / 64 * 64);
-    int64_t part_keys = 0;
-    for (;;) {
-      part_keys = 0;
-      for (int64_t kb = 0; kb < nbands; ++kb)
-        part_keys = std::max(part_keys, (rb[(size_t)kb + 1] - rb[(size_t)kb]) * band_chunks(rb[(size_t)kb]) * top_k);
-      if (part_keys * (int64_t)sizeof(uint64_t) <= std::max<int64_t>(free_budget(al) / 8, (int64_t)64 << 20) || chunk >= ((int64_t)1 << 30)) break;
-      chunk *= 2;
-    }
-    if (part_keys > 0 && sc.alloc(&part, (size_t)part_keys)) return WFA_HIP_EDEVICE;
-  }
-  auto drain = [&](int64_t k) -> int {   // append band k's completed pairs to the handle's list
-    const int h = (int)(k & 1);
-    HIP_TRY(al, hipEventSynchronize(sc.ev[h]));
-    const int64_t cnt = sc.h_cnt[h];
-    if (cnt == 0) return WFA_HIP_OK;
-    if (x->count + cnt > x->cap) {
-      const int64_t ncap2 = std::max<int64_t>(x->count + cnt, std::max<int64_t>(2 * x->cap, 4096));
-      int32_t* nb[3] = {nullptr, nullptr, nullptr};
-      int32_t** old[3] = {&x->d_ci, &x->d_cj, &x->d_cs};
-      for (int a = 0; a < 3; ++a) {
-        HIP_TRY(al, pool_alloc(al, (void**)&nb[a], (size_t)ncap2 * sizeof(int32_t)));
-        if (x->count) HIP_TRY(al, hipMemcpyAsync(nb[a], *old[a], (size_t)x->count * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
-        pool_release(al, *old[a]);   // (back to the pool; anything that takes it again is ordered behind this copy on the stream)
-        *old[a] = nb[a];
-      }
-      x->cap = ncap2;
-    }
-    HIP_TRY(al, hipMemcpyAsync(x->d_ci + x->count, st_i[h], (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(x->d_cj + x->count, st_j[h], (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(x->d_cs + x->count, st_s[h], (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
-    x->count += cnt;
-    return WFA_HIP_OK;
-  };
-  for (int64_t k = 0; k < nbands; ++k) {
-    const int64_t r0 = rb[(size_t)k], r1 = rb[(size_t)k + 1];
-    const int64_t tri0 = tri ? tri_before(r0) : 0;
-    const int64_t np = tri ? tri_before(r1) - tri0 : (r1 - r0) * n;
-    const int64_t nbytes = row_bytes[(size_t)r1] - row_bytes[(size_t)r0];
-    int maxp = 0, maxw = 0;
-    for (int64_t i = r0; i < r1; ++i) {
-      const int32_t pl = P->h_len[(size_t)i], tl = suf_t[tri ? (size_t)i : 0];
-      maxp = std::max(maxp, pl); maxw = std::max(maxw, pl + tl);
-    }
-    b->n = np;
-    b->n_bytes = (uint32_t)nbytes; b->n_packed = (uint32_t)(np - nbytes);
-    b->max_len = std::max(maxp, suf_t[tri ? (size_t)r0 : 0]);
-    b->max_width = maxw + 3;
-    b->d_list_packed = (nbytes > 0 && np > nbytes) ? list_packed : nullptr;
-    b->d_list_bytes = nbytes > 0 ? list_bytes : nullptr;
-    b->d_score = band_score ? band_score : x->d_score + r0 * n;
-    b->d_status = band_status ? band_status : x->d_status + r0 * n;
-    wfa::CrossGenArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.p_woff = P->d_woff; ga.p_len = P->d_len; ga.p_boff = P->d_boff; ga.p_flag = P->d_flag;
-    ga.t_woff = T->d_woff; ga.t_len = T->d_len; ga.t_boff = T->d_boff; ga.t_flag = T->d_flag;
-    ga.t_wshift = t_wshift; ga.t_bshift = t_bshift;
-    ga.words = b->d_words; ga.slot_base = (uint32_t)table_words; ga.slot_words = (uint32_t)slot_words;
-    ga.row_bytes = d_row_bytes; ga.col_flag = d_col_flag;
-    ga.n = n; ga.r0 = r0; ga.tri0 = tri0; ga.npairs = np; ga.tri = tri; ga.all_bytes = all_bytes ? 1 : 0; ga.lists = nbytes > 0 ? 1 : 0;
-    ga.meta = b->d_meta; ga.pboff = b->d_pboff; ga.tboff = b->d_tboff; ga.flags = b->d_flags;
-    ga.list_packed = list_packed; ga.list_bytes = list_bytes;
-    if (wfa::launch_cross_gen(ga, al->stream) != 0) { al->err = "cross band generator launch failed"; return WFA_HIP_EDEVICE; }
-    // the pilots: no-ops once the first band of >= 64 k pairs has picked (the picks live in the view)
-    { const int prc = run_pilots(al, b); if (prc != WFA_HIP_OK) return prc; }
-    int rc = wfa_hip_batch_run(b, nullptr);
-    if (rc != WFA_HIP_OK) return rc;
-    wfa::CrossResArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    ra.score = b->d_score; ra.status = b->d_status;
-    ra.n = n; ra.r0 = r0; ra.tri0 = tri0; ra.npairs = np; ra.tri = tri; ra.upper = ava ? 1 : 0; ra.mirror = mirror ? 1 : 0;
-    ra.dense_score = x->d_score; ra.dense_status = x->d_status;
-    if (dense && tri && wfa::launch_cross_scatter(ra, al->stream) != 0) { al->err = "cross scatter launch failed"; return WFA_HIP_EDEVICE; }
-    if (completed) {
-      const int h = (int)(k & 1);
-      ra.blk_count = blk; ra.band_count = d_cnt + h; ra.out_i = st_i[h]; ra.out_j = st_j[h]; ra.out_score = st_s[h];
-      if (wfa::launch_cross_compact(ra, al->stream) != 0) { al->err = "cross compaction launch failed"; return WFA_HIP_EDEVICE; }
-      HIP_TRY(al, hipMemcpyAsync(sc.h_cnt + h, d_cnt + h, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
-      HIP_TRY(al, hipEventRecord(sc.ev[h], al->stream));
-      if (k > 0) { rc = drain(k - 1); if (rc != WFA_HIP_OK) return rc; }
-    }
-    if (topk) {
-      wfa::CrossTopkArgs ta;
-      memset(&ta, 0, sizeof(ta));
-      ta.score = b->d_score; ta.status = b->d_status;
-      ta.n = n; ta.r0 = r0; ta.r1 = r1; ta.tri0 = tri0; ta.tri = tri; ta.ava = ava ? 1 : 0;
-      ta.k = x->k; ta.chunk = chunk; ta.nch = band_chunks(r0); ta.part = part; ta.run = x->d_topk;
-      if (wfa::launch_cross_topk(ta, al->stream) != 0) { al->err = "cross top-k launch failed"; return WFA_HIP_EDEVICE; }
-    }
-    x->pairs += np;
-  }
-  if (completed && nbands > 0) { const int rc = drain(nbands - 1); if (rc != WFA_HIP_OK) return rc; }
-  { const int rc = wfa_hip_batch_sync(b); if (rc != WFA_HIP_OK) return rc; }
-  x->ms = b->ms_sum;
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  return WFA_HIP_OK;
-}
-
-extern "C" wfa_hip_cross_t* wfa_hip_cross_run_k(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want, int k) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
-  mailbox_release(al);
-  wfa_hip_cross* x = new wfa_hip_cross();
-  x->al = al;
-  al->live_batches += 1;
-  const int rc = cross_run_impl(al, patterns, texts, want, k, x);
-  if (rc != WFA_HIP_OK) { g_error = al->err; wfa_hip_cross_destroy(x); return nullptr; }
-  return x;
-}
-
-extern "C" wfa_hip_cross_t* wfa_hip_cross_run(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want) {
-  if (al && (want & WFA_HIP_CROSS_TOPK)) {
-    al->err = "want: WFA_HIP_CROSS_DENSE and / or WFA_HIP_CROSS_COMPLETED (top-k: wfa_hip_cross_run_k)"; g_error = al->err; return nullptr;
-  }
-  return wfa_hip_cross_run_k(al, patterns, texts, want, 0);
-}
-
-extern "C" int wfa_hip_cross_topk(wfa_hip_cross_t* x, int32_t* j, int32_t* score) {
-  if (!x) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = x->al;
-  if (!(x->want & WFA_HIP_CROSS_TOPK)) { al->err = "the run was made without WFA_HIP_CROSS_TOPK"; return WFA_HIP_EINVAL; }
-  const size_t cells = (size_t)x->m * (size_t)x->k;
-  if (cells == 0) return WFA_HIP_OK;
-  if (!j || !score) { al->err = "j/score outputs are required"; return WFA_HIP_EINVAL; }
-  std::vector<uint64_t> keys(cells, 0ull);   // (no device list: no columns, every row is padding)
-  if (x->d_topk) {
-    HIP_TRY(al, hipSetDevice(al->device));
-    HIP_TRY(al, hipMemcpy(keys.data(), x->d_topk, cells * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  }
-  for (size_t c = 0; c < cells; ++c) {   // key 0 decodes to j = -1, score = INT32_MIN
-    j[c] = (int32_t)~(uint32_t)keys[c];
-    score[c] = (int32_t)((uint32_t)(keys[c] >> 32) ^ 0x80000000u);
-  }
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_cross_dense(wfa_hip_cross_t* x, int32_t* score, int32_t* status) {
-  if (!x) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = x->al;
-  if (!(x->want & WFA_HIP_CROSS_DENSE)) { al->err = "the run was made without WFA_HIP_CROSS_DENSE"; return WFA_HIP_EINVAL; }
-  const size_t cells = (size_t)(x->m * x->n);
-  if (cells == 0) return WFA_HIP_OK;
-  if (!score || !status) { al->err = "score/status outputs are required"; return WFA_HIP_EINVAL; }
-  HIP_TRY(al, hipSetDevice(al->device));
-  HIP_TRY(al, hipMemcpy(score, x->d_score, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIP_TRY(al, hipMemcpy(status, x->d_status, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_cross_completed(wfa_hip_cross_t* x, int64_t* count, int32_t* i, int32_t* j, int32_t* score) {
-  if (!x || !count) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = x->al;
-  if (!(x->want & WFA_HIP_CROSS_COMPLETED)) { al->err = "the run was made without WFA_HIP_CROSS_COMPLETED"; return WFA_HIP_EINVAL; }
-  *count = x->count;
-  if (x->count == 0) return WFA_HIP_OK;
-  HIP_TRY(al, hipSetDevice(al->device));
-  const size_t bytes = (size_t)x->count * sizeof(int32_t);
-  if (i) HIP_TRY(al, hipMemcpy(i, x->d_ci, bytes, hipMemcpyDeviceToHost));
-  if (j) HIP_TRY(al, hipMemcpy(j, x->d_cj, bytes, hipMemcpyDeviceToHost));
-  if (score) HIP_TRY(al, hipMemcpy(score, x->d_cs, bytes, hipMemcpyDeviceToHost));
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_cross_kernel_ms(wfa_hip_cross_t* x, float* ms, int64_t* pairs) {
-  if (!x) return WFA_HIP_EINVAL;
-  if (ms) *ms = (float)x->ms;
-  if (pairs) *pairs = x->pairs;
-  return WFA_HIP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// list-built batches (include/wfa_hip.h; csrc/wfa_cross.hpp): indexed batches, a list of (i, j) index pairs over resident sequence
-// sets (k_pairs.hip), and windowed batches, windows of resident sequences, either strand, by index (k_windows.hip)
-// ------------------------------------------------------------------------------------------------
-namespace {   // (the descriptors' members: internal, so that none of them is exported)
-
-// What a descriptor (IndexedPairs, WindowPairs below) tells batch_build_list about the pair at one list position
-struct ListPair {
-  int pl = 0, tl = 0;       // the lengths of what is aligned
-  int gen_words = 0;        // the words one lane group of the generator covers for it
-  bool slot = true;         // it has a word slot (otherwise it points into the sets' words, copied in front of the slots)
-  bool bytes = false;       // it is aligned on its bytes
-  bool opt = false;         // the descriptor recorded an option for it
-  int64_t byte_slot = 0;    // a byte pair's byte slot, where the descriptor has byte slots
-};
-
-// ... and what batch_build_list tells the descriptor, once the list is laid out and the batch's common blocks are allocated
-struct ListPlan {
-  bool all_bytes, lists, any_long, any_opt;
-  uint64_t table_words;     // words in front of the slots
-  int64_t slot_bytes;
-  int log2g;                // lanes per pair of the generator: the largest gen_words, rounded up to a power of two (at most a whole wave)
-  const std::vector<uint32_t>& chunk_base;
-  const std::vector<int64_t>& chunk_bbase;
-};
-
-// does [start, start + len) of sequence k of the set touch a run of flagged letters?
-static inline bool window_flagged(const wfa_hip_seqset* S, size_t k, int32_t start, int32_t len) {
-  if (!S->h_flag[k] || len <= 0) return false;
-  const std::vector<int32_t>& r = S->h_runs[k];
-  size_t lo = 0, hi = r.size() / 2;   // the first run that ends behind `start`
-  while (lo < hi) { const size_t mid = (lo + hi) / 2; if (r[2 * mid + 1] > start) hi = mid; else lo = mid + 1; }
-  return lo < r.size() / 2 && r[2 * lo] < start + len;
-}
-
-// Index pairs: whole sequences.  A pair of up to WFA_FAST_MAX_LEN bases gets a word slot, a longer one points into the sets' words; a
-// pair is a byte pair when one of its sequences is flagged.  The batch owns all it reads afterwards: the slots, and copies (device to
-// device) of the sets' words when a listed pair is too long for a slot, of their bytes when a listed pair is aligned on its bytes —
-// so it outlives the sets.
-struct IndexedPairs {
-  const wfa_hip_seqset *P, *T;
-  bool same;
-  const int32_t *i, *j;
-  static constexpr bool byte_slots = false;
-  static constexpr const char* too_large = "indexed batch too large: more than 2^32 words of sets and slots (split the list)";
-
-  __attribute__((always_inline)) void get(int64_t q, bool all_bytes, ListPair* p) const {
-    const size_t a = (size_t)i[q], bq = (size_t)j[q];
-    p->pl = P->h_len[a]; p->tl = T->h_len[bq];
-    p->slot = p->pl <= WFA_FAST_MAX_LEN && p->tl <= WFA_FAST_MAX_LEN;
-    p->gen_words = p->slot ? ((p->pl + 15) >> 4) + ((p->tl + 15) >> 4) : 0;   // (the longest slot)
-    p->bytes = all_bytes || P->h_flag[a] || T->h_flag[bq];
-  }
-  __attribute__((always_inline)) int check(int64_t q, bool all_bytes, ListPair* p) const { get(q, all_bytes, p); return 0; }   // (indices in range: nothing else to refuse)
-  std::string refusal(int, int64_t) const { return std::string(); }
-  // the sets' words and 64 zero words, only when a listed pair points into them
-  uint64_t table_words(bool any_long) const { return any_long ? P->nwords + (same ? 0 : T->nwords) + 64 : 0; }
-  // byte pairs: the sets' bytes, the text set's behind the pattern set's
-  int byte_store(wfa_hip_aligner* al, wfa_hip_batch* b, const ListPlan&) const {
-    HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)(P->nbytes + (same ? 0 : T->nbytes) + 64)));
-    HIP_TRY(al, hipMemcpyAsync(b->d_bytes, P->d_bytes, (size_t)P->nbytes + (same ? 64 : 0), hipMemcpyDeviceToDevice, al->stream));
-    if (!same) HIP_TRY(al, hipMemcpyAsync(b->d_bytes + P->nbytes, T->d_bytes, (size_t)T->nbytes + 64, hipMemcpyDeviceToDevice, al->stream));
-    return WFA_HIP_OK;
-  }
-  int generate(wfa_hip_aligner* al, wfa_hip_batch* b, CrossScratch& sc, const ListPlan& plan) const {
-    const int64_t n = b->n;
-    if (plan.any_long) {
-      HIP_TRY(al, hipMemcpyAsync(b->d_words, P->d_words, (size_t)P->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
-      if (!same) HIP_TRY(al, hipMemcpyAsync(b->d_words + P->nwords, T->d_words, (size_t)T->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
-      HIP_TRY(al, hipMemsetAsync(b->d_words + (plan.table_words - 64), 0, 64 * sizeof(uint32_t), al->stream));
-    }
-    int32_t *d_i = nullptr, *d_j = nullptr;
-    uint32_t* d_chunk = nullptr;
-    if (sc.alloc(&d_i, (size_t)n) || sc.alloc(&d_j, (size_t)n) || sc.alloc(&d_chunk, plan.chunk_base.size())) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_i, i, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(d_j, j, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(d_chunk, plan.chunk_base.data(), plan.chunk_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
-    wfa::PairsGenArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.p_words = P->d_words; ga.p_woff = P->d_woff; ga.p_len = P->d_len; ga.p_boff = P->d_boff; ga.p_flag = P->d_flag;
-    ga.t_words = T->d_words; ga.t_woff = T->d_woff; ga.t_len = T->d_len; ga.t_boff = T->d_boff; ga.t_flag = T->d_flag;
-    ga.i = d_i; ga.j = d_j; ga.chunk_base = d_chunk;
-    ga.words = b->d_words; ga.t_wshift = same ? 0u : (uint32_t)P->nwords; ga.t_bshift = same ? 0 : P->nbytes; ga.npairs = n;
-    ga.log2g = plan.log2g;
-    ga.all_bytes = plan.all_bytes ? 1 : 0; ga.lists = plan.lists ? 1 : 0;
-    ga.meta = b->d_meta; ga.pboff = b->d_pboff; ga.tboff = b->d_tboff; ga.flags = b->d_flags;
-    if (wfa::launch_pairs_gen(ga, al->cu_count, al->stream) != 0) { al->err = "indexed batch generator launch failed"; return WFA_HIP_EDEVICE; }
-    return WFA_HIP_OK;
-  }
-};
-
-// Windows: every pair has a word slot, a byte pair a byte slot, and whether a pair is a byte pair is looked up per window in the sets'
-// runs of flagged letters.  One byte of options per pair (strand, byte pair) goes to the device when the list has a reversed or a byte
-// pair; the batch owns its slots and nothing of the sets.
-struct WindowPairs {
-  const wfa_hip_seqset *P, *T;
-  const int32_t *i, *j, *p_start, *p_len, *t_start, *t_len;
-  const uint8_t* reverse;
-  std::vector<uint8_t> opt;   // per pair: written by check, read by get
-  static constexpr bool byte_slots = true;
-  static constexpr const char* too_large = "windowed batch too large: more than 2^32 words of slots (split the list)";
-
-  struct Win { int64_t ps, pl, ts, tl; };
-  Win window(int64_t q, int64_t pseq, int64_t tseq) const {
-    Win w;
-    w.ps = p_start ? p_start[q] : 0; w.ts = t_start ? t_start[q] : 0;
-    w.pl = p_len ? p_len[q] : pseq - w.ps; w.tl = t_len ? t_len[q] : tseq - w.ts;
-    return w;
-  }
-  static void fill(ListPair* p, int pl, int tl, bool byt) {
-    p->pl = pl; p->tl = tl; p->bytes = byt;
-    p->gen_words = std::max((pl + 15) >> 4, (tl + 15) >> 4);   // (the longest window)
-    p->byte_slot = byt ? (((int64_t)pl + 3) & ~(int64_t)3) + (((int64_t)tl + 3) & ~(int64_t)3) : 0;
-  }
-  __attribute__((always_inline)) int check(int64_t q, bool all_bytes, ListPair* p) {
-    const size_t a = (size_t)i[q], bq = (size_t)j[q];
-    const int64_t pseq = P->h_len[a], tseq = T->h_len[bq];
-    const Win w = window(q, pseq, tseq);
-    if (w.ps < 0 || w.ts < 0 || (p_len && w.pl < 0) || (t_len && w.tl < 0)) return 2;
-    if (w.ps + w.pl > pseq || w.ts + w.tl > tseq || w.pl < 0 || w.tl < 0) return 4;
-    const int pl = (int)w.pl, tl = (int)w.tl;
-    const bool rev = reverse && reverse[q] != 0;
-    const bool byt = all_bytes || window_flagged(P, a, (int32_t)w.ps, pl) || window_flagged(T, bq, (int32_t)w.ts, tl);
-    opt[(size_t)q] = (uint8_t)((rev ? WFA_WIN_REVERSE : 0) | (byt ? WFA_WIN_BYTES : 0));
-    fill(p, pl, tl, byt);
-    p->opt = rev || byt;
-    return 0;
-  }
-  __attribute__((always_inline)) void get(int64_t q, bool, ListPair* p) const {
-    const Win w = window(q, P->h_len[(size_t)i[q]], T->h_len[(size_t)j[q]]);
-    fill(p, (int)w.pl, (int)w.tl, (opt[(size_t)q] & WFA_WIN_BYTES) != 0);
-  }
-  std::string refusal(int err, int64_t q) const {
-    const int64_t pseq = P->h_len[(size_t)i[q]], tseq = T->h_len[(size_t)j[q]];
-    const Win w = window(q, pseq, tseq);
-    char buf[320];
-    snprintf(buf, sizeof(buf), "%s at position %lld of the pair list: pattern window [%lld, %lld + %lld) of sequence %d (%lld bases), "
-             "text window [%lld, %lld + %lld) of sequence %d (%lld bases)", err == 2 ? "negative start or length" : "window out of range",
-             (long long)q, (long long)w.ps, (long long)w.ps, (long long)w.pl, (int)i[q], (long long)pseq,
-             (long long)w.ts, (long long)w.ts, (long long)w.tl, (int)j[q], (long long)tseq);
-    return buf;
-  }
-  uint64_t table_words(bool) const { return 0; }
-  // byte pairs: their byte slots and 64 zero bytes
-  int byte_store(wfa_hip_aligner* al, wfa_hip_batch* b, const ListPlan& plan) const {
-    HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)plan.slot_bytes + 64));
-    HIP_TRY(al, hipMemsetAsync(b->d_bytes + plan.slot_bytes, 0, 64, al->stream));
-    return WFA_HIP_OK;
-  }
-  int generate(wfa_hip_aligner* al, wfa_hip_batch* b, CrossScratch& sc, const ListPlan& plan) const {
-    const int64_t n = b->n;
-    int32_t* d_arr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint8_t* d_opt = nullptr;
-    uint32_t* d_chunk = nullptr;
-    int64_t* d_bchunk = nullptr;
-    if (plan.lists) {
-      if (sc.alloc(&d_bchunk, plan.chunk_bbase.size())) return WFA_HIP_EDEVICE;
-      HIP_TRY(al, hipMemcpyAsync(d_bchunk, plan.chunk_bbase.data(), plan.chunk_bbase.size() * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
-    }
-    const int32_t* h_arr[6] = {i, j, p_start, p_len, t_start, t_len};
-    for (int k = 0; k < 6; ++k) {
-      if (!h_arr[k]) continue;
-      if (sc.alloc(&d_arr[k], (size_t)n)) return WFA_HIP_EDEVICE;
-      HIP_TRY(al, hipMemcpyAsync(d_arr[k], h_arr[k], (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    }
-    if (plan.any_opt) {
-      if (sc.alloc(&d_opt, (size_t)n)) return WFA_HIP_EDEVICE;
-      HIP_TRY(al, hipMemcpyAsync(d_opt, opt.data(), (size_t)n, hipMemcpyHostToDevice, al->stream));
-    }
-    if (sc.alloc(&d_chunk, plan.chunk_base.size())) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_chunk, plan.chunk_base.data(), plan.chunk_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
-    wfa::WindowsGenArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.p_words = P->d_words; ga.p_woff = P->d_woff; ga.p_len = P->d_len; ga.p_boff = P->d_boff; ga.p_bytes = P->d_bytes;
-    ga.t_words = T->d_words; ga.t_woff = T->d_woff; ga.t_len = T->d_len; ga.t_boff = T->d_boff; ga.t_bytes = T->d_bytes;
-    ga.i = d_arr[0]; ga.j = d_arr[1]; ga.p_start = d_arr[2]; ga.p_wlen = d_arr[3]; ga.t_start = d_arr[4]; ga.t_wlen = d_arr[5];
-    ga.opt = d_opt; ga.chunk_base = d_chunk; ga.chunk_bbase = d_bchunk;
-    ga.words = b->d_words; ga.bytes = b->d_bytes; ga.npairs = n;
-    ga.log2g = plan.log2g;
-    ga.all_bytes = plan.all_bytes ? 1 : 0; ga.lists = plan.lists ? 1 : 0;
-    ga.meta = b->d_meta; ga.pboff = b->d_pboff; ga.tboff = b->d_tboff; ga.flags = b->d_flags;
-    if (wfa::launch_windows_gen(ga, al->cu_count, al->stream) != 0) { al->err = "windowed batch generator launch failed"; return WFA_HIP_EDEVICE; }
-    return WFA_HIP_OK;
-  }
-};
-
-}  // namespace
-
-// What batch_build does for an explicit batch, from the sets' host tables instead of the caller's arrays: one pass over the list checks
-// and sums (on threads for long lists; the parts start on chunk boundaries of the generator), a second writes what the host keeps (the
-// op-region prefix, the lengths, the work lists) and the generator's chunk bases.  The generator then writes the metadata and the slots
-// on the device.  How a listed pair is described, what stands in front of the slots, where a byte pair's bytes are and the generator
-// itself are the descriptor's (IndexedPairs, WindowPairs); its per-pair calls inline into the two passes.
-template <class Desc>
-static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, Desc& D) {
-  batch_adopt_config(al, b);
-  const wfa_hip_config_t& c = b->cfg;
-  const bool all_bytes = c.wildcard >= 0 && b->wild < 0;   // (a wildcard among ACGT: every pair on its bytes)
-  b->al = al;
-  b->n = n;
-  const bool full = (c.scope == WFA_SCOPE_FULL);
-  const int64_t np_set = D.P->n, nt_set = D.T->n;
-  const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, std::thread::hardware_concurrency()), n / 65536));
-  auto part_lo = [&](int t) -> int64_t { return t >= nthr ? n : (n * t / nthr) & ~(int64_t)(WFA_PAIRS_CHUNK - 1); };
-  struct Part {
-    uint64_t words = 0; int64_t packed = 0, ops = 0, nbytes = 0, slot_bytes = 0, bad = -1;
-    int max_width = 0, max_len = 0, max_gen = 0, err = 0; bool any_long = false, any_opt = false;
-  };
-  std::vector<Part> parts((size_t)nthr);
-  auto pass1 = [&](int t) {
-    Part& pt = parts[(size_t)t];
-    for (int64_t q = part_lo(t), hi = part_lo(t + 1); q < hi; ++q) {
-      const int64_t a = D.i[q], bq = D.j[q];
-      if (a < 0 || a >= np_set || bq < 0 || bq >= nt_set) { pt.err = 1; pt.bad = q; return; }
-      ListPair p;
-      if (const int bad = D.check(q, all_bytes, &p)) { pt.err = bad; pt.bad = q; return; }
-      const int pl = p.pl, tl = p.tl;
-      // wavefront_align.c:86-102, per listed pair as batch_build: against what is aligned (the sequences, or the windows)
-      if (free_ends_exceed(c, pl, tl)) { pt.err = PART_ENDS_FREE; pt.bad = q; return; }
-      if (p.slot) pt.words += (uint64_t)(((pl + 15) >> 4) + ((tl + 15) >> 4));
-      else pt.any_long = true;
-      pt.max_gen = std::max(pt.max_gen, p.gen_words);
-      pt.max_width = std::max(pt.max_width, pl + tl + 3);
-      pt.max_len = std::max(pt.max_len, std::max(pl, tl));
-      pt.packed += (int64_t)((pl + 3) >> 2) + ((tl + 3) >> 2);
-      pt.ops += (int64_t)pl + tl;
-      if (p.bytes) { pt.nbytes += 1; pt.slot_bytes += p.byte_slot; }
-      pt.any_opt |= p.opt;
-    }
-  };
-  run_parts(nthr, nthr, pass1);   // (a thread per part)
-  uint64_t slot_words = 0;
-  int64_t nbytes = 0, slot_bytes = 0;
-  int max_gen = 0;
-  bool any_long = false, any_opt = false;
-  std::vector<uint64_t> wbase((size_t)nthr);
-  std::vector<int64_t> obase((size_t)nthr), bbase((size_t)nthr), sbase((size_t)nthr);
-  for (int t = 0; t < nthr; ++t) {
-    const Part& pt = parts[(size_t)t];
-    if (pt.err == 1) {
-      char buf[200];
-      snprintf(buf, sizeof(buf), "index out of range at position %lld of the pair list: (%d, %d) over sets of %lld and %lld sequences",
-               (long long)pt.bad, (int)D.i[pt.bad], (int)D.j[pt.bad], (long long)np_set, (long long)nt_set);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
-    if (pt.err == PART_ENDS_FREE) { al->err = part_error_message(pt.err); return WFA_HIP_EINVAL; }
-    if (pt.err) { al->err = D.refusal(pt.err, pt.bad); return WFA_HIP_EINVAL; }
-    wbase[(size_t)t] = slot_words; obase[(size_t)t] = b->ops_bytes; bbase[(size_t)t] = nbytes; sbase[(size_t)t] = slot_bytes;
-    slot_words += pt.words; nbytes += pt.nbytes; slot_bytes += pt.slot_bytes;
-    max_gen = std::max(max_gen, pt.max_gen); any_long |= pt.any_long; any_opt |= pt.any_opt;
-    b->max_width = std::max(b->max_width, pt.max_width); b->max_len = std::max(b->max_len, pt.max_len);
-    b->packed_bytes += pt.packed; b->ops_bytes += pt.ops;
-  }
-  // the word table: what the descriptor puts in front, the slots, 64 zero words
-  const uint64_t table_words = D.table_words(any_long);
-  if (table_words + slot_words + 64 > 0xFFFFFFF0ull) { al->err = Desc::too_large; return WFA_HIP_EINVAL; }
-  const bool lists = nbytes > 0;
-  const int64_t chunks = (n + WFA_PAIRS_CHUNK - 1) / WFA_PAIRS_CHUNK;
-  std::vector<uint32_t> chunk_base((size_t)std::max<int64_t>(chunks, 1), (uint32_t)table_words);
-  std::vector<int64_t> chunk_bbase(lists && Desc::byte_slots ? (size_t)std::max<int64_t>(chunks, 1) : 0, 0);
-  std::vector<uint32_t> lp(lists ? (size_t)(n - nbytes) : 0), lb(lists ? (size_t)nbytes : 0);
-  if (full) {   // needed later to lay out the op-string regions
-    b->h_plen.resize((size_t)n); b->h_tlen.resize((size_t)n);
-    b->h_coff.assign((size_t)n + 1, 0);
-  }
-  auto pass2 = [&](int t) {
-    uint64_t w = table_words + wbase[(size_t)t];
-    int64_t o = obase[(size_t)t], nb = bbase[(size_t)t], sb = sbase[(size_t)t];
-    const int64_t lo = part_lo(t), hi = part_lo(t + 1);
-    int64_t npk = lo - nb;   // 2-bit pairs before this part
-    for (int64_t q = lo; q < hi; ++q) {
-      ListPair p;
-      D.get(q, all_bytes, &p);
-      const int pl = p.pl, tl = p.tl;
-      if ((q & (WFA_PAIRS_CHUNK - 1)) == 0) {
-        chunk_base[(size_t)(q / WFA_PAIRS_CHUNK)] = (uint32_t)w;
-        if (!chunk_bbase.empty()) chunk_bbase[(size_t)(q / WFA_PAIRS_CHUNK)] = sb;
-      }
-      if (p.slot) w += (uint64_t)(((pl + 15) >> 4) + ((tl + 15) >> 4));
-      if (full) { b->h_plen[(size_t)q] = pl; b->h_tlen[(size_t)q] = tl; o += (int64_t)pl + tl; b->h_coff[(size_t)q + 1] = o; }
-      if (lists) {
-        if (p.bytes) { lb[(size_t)nb++] = (uint32_t)q; sb += p.byte_slot; }
-        else lp[(size_t)npk++] = (uint32_t)q;
-      }
-    }
-  };
-  run_parts(nthr, nthr, pass2);
-  CrossScratch sc{al};   // (declared behind the host tables above: it waits for the stream before they go)
-  const size_t nn = (size_t)std::max<int64_t>(n, 1);
-  { const int arc = batch_alloc_common(al, b, table_words + slot_words + 64, 64); if (arc != WFA_HIP_OK) return arc; }
-  b->n_bytes = (uint32_t)nbytes;
-  b->n_packed = (uint32_t)(n - nbytes);
-  if (n > 0) {
-    ListPlan plan{all_bytes, lists, any_long, any_opt, table_words, slot_bytes, 2, chunk_base, chunk_bbase};
-    while (plan.log2g < 6 && (1 << plan.log2g) < max_gen) ++plan.log2g;
-    if (lists) {   // (byte pairs: where their bytes are, the descriptor's; the two work lists, ascending)
-      { const int src = D.byte_store(al, b, plan); if (src != WFA_HIP_OK) return src; }
-      HIP_TRY(al, pool_alloc(al, (void**)&b->d_pboff, nn * sizeof(int64_t)));
-      HIP_TRY(al, pool_alloc(al, (void**)&b->d_tboff, nn * sizeof(int64_t)));
-      { const int lrc = upload_work_lists(al, b, lp, lb, true); if (lrc != WFA_HIP_OK) return lrc; }
-    }
-    { const int grc = D.generate(al, b, sc, plan); if (grc != WFA_HIP_OK) return grc; }
-  }
-  { const int frc = finish_batch_build(al, b); if (frc != WFA_HIP_OK) return frc; }
-  // the caller's arrays, the host tables above and the sets are read by what is enqueued: over before this returns
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  return WFA_HIP_OK;
-}
-
-// What both creators check before the build, in this order; the new batch, counted among the aligner's live ones, or nullptr with the
-// reason in al->err and g_error.  *texts == nullptr: one set against itself.
-static wfa_hip_batch* list_batch_new(wfa_hip_aligner* al, const wfa_hip_seqset* patterns, const wfa_hip_seqset** texts,
-                                     int64_t npairs, const int32_t* i, const int32_t* j) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  if (!*texts) *texts = patterns;
-  if (!patterns || patterns->al != al || (*texts)->al != al) { al->err = "sequence set of another aligner"; g_error = al->err; return nullptr; }
-  if (patterns->wildcard != al->cfg.wildcard || (*texts)->wildcard != al->cfg.wildcard) {
-    al->err = "sequence set packed under another wildcard: create it again"; g_error = al->err; return nullptr;
-  }
-  if (npairs < 0 || npairs > 0x7FFFFFF0ll || (npairs > 0 && (!i || !j))) { al->err = "invalid pair list arguments"; g_error = al->err; return nullptr; }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
-  mailbox_release(al);   // (the resident one-pair kernel: batches take the device)
-  wfa_hip_batch* b = new wfa_hip_batch();
-  b->al = al;
-  al->live_batches += 1;
-  return b;
-}
-
-// ... and what they do with the build's outcome
-static wfa_hip_batch* list_batch_done(wfa_hip_aligner* al, wfa_hip_batch* b, int rc) {
-  if (rc == WFA_HIP_OK) return b;
-  g_error = al->err;
-  batch_free(b);
-  return nullptr;
-}
-
-extern "C" wfa_hip_batch_t* wfa_hip_batch_create_indexed(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts,
-                                                         int64_t npairs, const int32_t* i, const int32_t* j) {
-  const bool same = (texts == nullptr);
-  wfa_hip_batch* b = list_batch_new(al, patterns, &texts, npairs, i, j);
-  if (!b) return nullptr;
-  IndexedPairs D{patterns, texts, same, i, j};
-  return list_batch_done(al, b, batch_build_list(al, b, npairs, D));
-}
-
-extern "C" int wfa_hip_window_2bit(const uint32_t* words, int64_t start, int32_t len, int reverse, uint32_t* out) {
-  if (start < 0 || len < 0 || (len > 0 && (!words || !out))) return WFA_HIP_EINVAL;
-  if (len == 0) return WFA_HIP_OK;
-  const int64_t w_lo = start >> 4, w_hi = (start + len - 1) >> 4;   // the source words that hold a base of the window: nothing else is read
-  const uint32_t n = (uint32_t)(len + 15) >> 4;
-  for (uint32_t w = 0; w < n; ++w) {
-    const int64_t first = wfa::wfa_window_first(start, len, w, reverse != 0), si = first >> 4;
-    const uint32_t lo = (si >= w_lo && si <= w_hi) ? words[si] : 0u, hi = (si + 1 >= w_lo && si + 1 <= w_hi) ? words[si + 1] : 0u;
-    out[w] = wfa::wfa_window_word(lo, hi, first, len, w, reverse != 0);
-  }
-  return WFA_HIP_OK;
-}
-
-extern "C" wfa_hip_batch_t* wfa_hip_batch_create_windows(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts,
-                                                         int64_t npairs, const int32_t* i, const int32_t* j,
-                                                         const int32_t* p_start, const int32_t* p_len, const int32_t* t_start, const int32_t* t_len,
-                                                         const uint8_t* reverse) {
-  wfa_hip_batch* b = list_batch_new(al, patterns, &texts, npairs, i, j);
-  if (!b) return nullptr;
-  WindowPairs D{patterns, texts, i, j, p_start, p_len, t_start, t_len, reverse, std::vector<uint8_t>((size_t)npairs, 0)};
-  return list_batch_done(al, b, batch_build_list(al, b, npairs, D));
-}
-
-// ------------------------------------------------------------------------------------------------
-// pileup over a text set (include/wfa_hip.h; csrc/wfa_pileup.hpp, k_pileup.hip)
-// ------------------------------------------------------------------------------------------------
-static_assert(WFA_SUMMARY_COLS == WFA_HIP_SUMMARY_COLS && WFA_PILEUP_COLS == WFA_HIP_PILEUP_COLS, "columns of the kernels and of the ABI");
-
-struct wfa_hip_pileup {
-  wfa_hip_aligner* al = nullptr;
-  int64_t nseq = 0, total = 0;         // sequences, and bases of all of them (the stride of a plane)
-  std::vector<int32_t> h_len;
-  std::vector<int64_t> h_off;          // first base of a sequence in a plane
-  int32_t* d_table = nullptr;          // WFA_PILEUP_COLS planes of `total` counters (its own allocation: up to 32 bytes x every text base)
-  int64_t* d_off = nullptr; int32_t* d_len = nullptr;
-};
-
-extern "C" void wfa_hip_pileup_destroy(wfa_hip_pileup_t* p) {
-  if (!p) return;
-  wfa_hip_aligner* al = p->al;
-  (void)hipSetDevice(al->device);
-  if (p->d_table) (void)hipFree(p->d_table);
-  pool_release(al, p->d_off); pool_release(al, p->d_len);
-  delete p;
-  aligner_release_ref(al);
-}
-
-static int pileup_build(wfa_hip_aligner* al, wfa_hip_pileup* p, const wfa_hip_seqset_t* T) {
-  p->nseq = T->n;
-  p->h_len = T->h_len;
-  p->h_off.assign((size_t)T->n + 1, 0);
-  for (int64_t k = 0; k < T->n; ++k) p->h_off[(size_t)k + 1] = p->h_off[(size_t)k] + T->h_len[(size_t)k];
-  p->total = p->h_off[(size_t)T->n];
-  const size_t bytes = (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t);
-  if (hipMalloc((void**)&p->d_table, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    p->d_table = nullptr;
-    char buf[160];
-    snprintf(buf, sizeof(buf), "pileup table: hipMalloc of %zu bytes failed (32 bytes per text base, %lld bases)", bytes, (long long)p->total);
-    al->err = buf;
-    return WFA_HIP_EDEVICE;
-  }
-  const size_t nn = (size_t)std::max<int64_t>(T->n, 1);
-  HIP_TRY(al, pool_alloc(al, (void**)&p->d_off, nn * sizeof(int64_t)));
-  HIP_TRY(al, pool_alloc(al, (void**)&p->d_len, nn * sizeof(int32_t)));
-  HIP_TRY(al, hipMemsetAsync(p->d_table, 0, bytes, al->stream));
-  if (T->n > 0) {
-    HIP_TRY(al, hipMemcpyAsync(p->d_off, p->h_off.data(), (size_t)T->n * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(p->d_len, p->h_len.data(), (size_t)T->n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  }
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  return WFA_HIP_OK;
-}
-
-extern "C" wfa_hip_pileup_t* wfa_hip_pileup_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  if (!texts || texts->al != al) { al->err = "sequence set of another aligner"; g_error = al->err; return nullptr; }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
-  wfa_hip_pileup* p = new wfa_hip_pileup();
-  p->al = al;
-  al->live_batches += 1;
-  if (pileup_build(al, p, texts) != WFA_HIP_OK) { g_error = al->err; wfa_hip_pileup_destroy(p); return nullptr; }
-  return p;
-}
-
-extern "C" int wfa_hip_pileup_clear(wfa_hip_pileup_t* p) {
-  if (!p) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = p->al;
-  HIP_TRY(al, hipSetDevice(al->device));
-  HIP_TRY(al, hipMemsetAsync(p->d_table, 0, (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t), al->stream));
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep) {
-  if (!p) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = p->al;
-  if (!b) { al->err = "pileup: null batch"; return WFA_HIP_EINVAL; }
-  if (b->al != al) { al->err = "pileup: batch of another aligner"; return WFA_HIP_EINVAL; }
-  if (b->cfg.scope != WFA_SCOPE_FULL) { al->err = "pileup needs scope=full"; return WFA_HIP_EINVAL; }
-  if (!b->ran) { al->err = "pileup needs a finished run of the batch"; return WFA_HIP_EINVAL; }
-  const int64_t n = b->n;
-  if (n > 0 && !j) { al->err = "pileup: the text indices are missing"; return WFA_HIP_EINVAL; }
-  for (int64_t q = 0; q < n; ++q) {
-    char buf[240];
-    if (j[q] < 0 || j[q] >= p->nseq) {
-      snprintf(buf, sizeof(buf), "pileup: text index out of range at position %lld of the pair list: j = %d over a set of %lld sequences",
-               (long long)q, (int)j[q], (long long)p->nseq);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
-    const int64_t ts = t_start ? t_start[q] : 0, tl = b->h_tlen[(size_t)q], have = p->h_len[(size_t)j[q]];
-    if (ts < 0) {
-      snprintf(buf, sizeof(buf), "pileup: negative text start at position %lld of the pair list: t_start = %lld", (long long)q, (long long)ts);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
-    if (ts + tl > have) {
-      snprintf(buf, sizeof(buf), "pileup: text window out of range at position %lld of the pair list: [%lld, %lld + %lld) of sequence %d (%lld bases)",
-               (long long)q, (long long)ts, (long long)ts, (long long)tl, (int)j[q], (long long)have);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
-  }
-  const int rc = wfa_hip_batch_sync(b);
-  if (rc != WFA_HIP_OK) return rc;
-  if (n == 0) return WFA_HIP_OK;
-  HIP_TRY(al, hipSetDevice(al->device));
-  CrossScratch sc{al};   // (waits for the stream before the blocks go back)
-  int32_t *d_j = nullptr, *d_ts = nullptr;
-  uint8_t* d_keep = nullptr;
-  if (sc.alloc(&d_j, (size_t)n)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipMemcpyAsync(d_j, j, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  if (t_start) {
-    if (sc.alloc(&d_ts, (size_t)n)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_ts, t_start, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  }
-  if (keep) {
-    if (sc.alloc(&d_keep, (size_t)n)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_keep, keep, (size_t)n, hipMemcpyHostToDevice, al->stream));
-  }
-  wfa::PileupArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ops = b->d_ops; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len; a.status = b->d_status;
-  a.meta = b->d_meta; a.words = b->d_words; a.bytes = b->d_bytes; a.pboff = b->d_pboff; a.flags = b->d_flags;
-  a.npairs = n; a.j = d_j; a.t_start = d_ts; a.keep = d_keep;
-  a.seq_off = p->d_off; a.seq_len = p->d_len; a.nseq = p->nseq; a.total = p->total; a.table = p->d_table;
-  {
-    ReduceTimer timer(al, "pileup", n);
-    const int lrc = wfa::launch_pileup(a, al->cu_count, al->stream);
-    timer.stop();
-    const hipError_t e = hipStreamSynchronize(al->stream);   // (the caller's arrays are read by the copies above)
-    if (lrc != 0) { al->err = "pileup kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, e);
-  }
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int32_t* counts) {
-  if (!p) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = p->al;
-  if (seq < 0 || seq >= p->nseq || start < 0 || len < 0 || start + len > p->h_len[(size_t)seq]) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "pileup: rows [%lld, %lld + %lld) of sequence %d are out of range (%lld sequences; sequence length %lld)", (long long)start,
-             (long long)start, (long long)len, (int)seq, (long long)p->nseq, (long long)((seq >= 0 && seq < p->nseq) ? p->h_len[(size_t)seq] : -1));
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
-  if (len == 0) return WFA_HIP_OK;
-  if (!counts) { al->err = "pileup: null output"; return WFA_HIP_EINVAL; }
-  HIP_TRY(al, hipSetDevice(al->device));
-  // the table is a plane per column: one copy per plane, interleaved into rows on the host
-  std::vector<int32_t> plane((size_t)len * WFA_PILEUP_COLS);
-  for (int c = 0; c < WFA_PILEUP_COLS; ++c)
-    HIP_TRY(al, hipMemcpyAsync(plane.data() + (size_t)c * (size_t)len, p->d_table + (int64_t)c * p->total + p->h_off[(size_t)seq] + start,
-                               (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  for (int c = 0; c < WFA_PILEUP_COLS; ++c) {
-    const int32_t* src = plane.data() + (size_t)c * (size_t)len;
-    for (int64_t r = 0; r < len; ++r) counts[r * WFA_PILEUP_COLS + c] = src[r];
-  }
-  return WFA_HIP_OK;
-}
-
-// ---- calls and sites of a pileup against its reference set (include/wfa_hip.h; csrc/wfa_calls.hpp, k_calls.hip) ----------------------
-static_assert(WFA_SITE_COLS == WFA_HIP_SITE_COLS, "columns of the kernels and of the ABI");
-
-// the checks the two calls share: the set is the pileup's (same aligner, same lengths), the parameters, the range.  On success
-// *g0 / *n are the run of global base indices (seq = -1, sites only: every base).
-static int calls_check(wfa_hip_pileup* p, const wfa_hip_seqset_t* T, bool sites, int32_t seq, int64_t start, int64_t len, int32_t min_depth,
-                       int32_t min_permille, int64_t cap, int64_t* g0, int64_t* n) {
-  wfa_hip_aligner* al = p->al;
-  char buf[240];
-  if (!T || T->al != al) { al->err = "sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (T->n != p->nseq) {
-    snprintf(buf, sizeof(buf), "pileup: the set holds %lld sequences, the pileup was made over %lld", (long long)T->n, (long long)p->nseq);
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
-  for (int64_t k = 0; k < p->nseq; ++k)
-    if (T->h_len[(size_t)k] != p->h_len[(size_t)k]) {
-      snprintf(buf, sizeof(buf), "pileup: sequence %lld of the set has %lld bases, the pileup was made over %lld", (long long)k,
-               (long long)T->h_len[(size_t)k], (long long)p->h_len[(size_t)k]);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
-  if (min_depth < 1) {
-    snprintf(buf, sizeof(buf), "pileup: min_depth = %d is out of range (at least 1)", (int)min_depth);
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
-  if (sites && (min_permille < 1 || min_permille > 1000)) {
-    snprintf(buf, sizeof(buf), "pileup: min_permille = %d is out of range (1 .. 1000)", (int)min_permille);
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
-  if (sites && cap < 0) {
-    snprintf(buf, sizeof(buf), "pileup: cap = %lld is negative", (long long)cap);
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
-  if (sites && seq == -1) {
-    if (start != 0 || len != -1) {
-      snprintf(buf, sizeof(buf), "pileup: seq = -1 (every sequence) goes with start = 0 and len = -1, got start = %lld, len = %lld",
-               (long long)start, (long long)len);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
-    *g0 = 0; *n = p->total;
-    return WFA_HIP_OK;
-  }
-  if (seq < 0 || seq >= p->nseq || start < 0 || len < 0 || start + len > p->h_len[(size_t)seq]) {
-    snprintf(buf, sizeof(buf), "pileup: rows [%lld, %lld + %lld) of sequence %d are out of range (%lld sequences; sequence length %lld)", (long long)start,
-             (long long)start, (long long)len, (int)seq, (long long)p->nseq, (long long)((seq >= 0 && seq < p->nseq) ? p->h_len[(size_t)seq] : -1));
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
-  *g0 = p->h_off[(size_t)seq] + start; *n = len;
-  return WFA_HIP_OK;
-}
-
-static wfa::CallsArgs calls_args(const wfa_hip_pileup* p, const wfa_hip_seqset_t* T, int64_t g0, int64_t n, int32_t min_depth, int32_t min_permille) {
-  wfa::CallsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.table = p->d_table; a.total = p->total; a.ref = T->d_bytes; a.g0 = g0; a.n = n; a.min_depth = min_depth; a.min_permille = min_permille;
-  a.seq_off = p->d_off; a.nseq = p->nseq;
-  return a;
-}
-
-extern "C" int wfa_hip_pileup_calls(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
-                                    int32_t min_depth, uint8_t* out) {
-  if (!p) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = p->al;
-  int64_t g0 = 0, n = 0;
-  const int rc = calls_check(p, texts, false, seq, start, len, min_depth, 1, 0, &g0, &n);
-  if (rc != WFA_HIP_OK) return rc;
-  if (n > 0 && !out) { al->err = "pileup: null output"; return WFA_HIP_EINVAL; }
-  HIP_TRY(al, hipSetDevice(al->device));
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  if (n == 0) return WFA_HIP_OK;
-  CrossScratch sc{al};
-  wfa::CallsArgs a = calls_args(p, texts, g0, n, min_depth, 1);
-  if (sc.alloc(&a.out, (size_t)n)) return WFA_HIP_EDEVICE;
-  {
-    ReduceTimer timer(al, "calls", n, "bases");
-    const int lrc = wfa::launch_calls(a, al->cu_count, al->stream);
-    timer.stop();
-    if (lrc != 0) { al->err = "calls kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, hipMemcpyAsync(out, a.out, (size_t)n, hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-  }
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
-                                    int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows) {
-  if (!p) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = p->al;
-  int64_t g0 = 0, n = 0;
-  const int rc = calls_check(p, texts, true, seq, start, len, min_depth, min_permille, cap, &g0, &n);
-  if (rc != WFA_HIP_OK) return rc;
-  if (!count) { al->err = "pileup: null count"; return WFA_HIP_EINVAL; }
-  if (cap > 0 && !rows) { al->err = "pileup: null rows with cap > 0"; return WFA_HIP_EINVAL; }
-  HIP_TRY(al, hipSetDevice(al->device));
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  *count = 0;
-  if (n == 0) return WFA_HIP_OK;
-  // bases per chunk: read per call, a multiple of 64 in 64 .. 2^20
-  const char* env = getenv("WFA_HIP_CALLS_CHUNK");
-  const int64_t asked = env && *env ? atoll(env) : 4096;
-  CrossScratch sc{al};
-  wfa::CallsArgs a = calls_args(p, texts, g0, n, min_depth, min_permille);
-  a.chunk = std::min<int64_t>(1 << 20, std::max<int64_t>(64, (std::min<int64_t>(asked, 1 << 20) + 63) / 64 * 64));
-  a.chunks = (n + a.chunk - 1) / a.chunk;
-  if (sc.alloc(&a.chunk_count, (size_t)a.chunks) || sc.alloc(&a.chunk_off, (size_t)a.chunks + 1)) return WFA_HIP_EDEVICE;
-  uint64_t total = 0;
-  {
-    ReduceTimer timer(al, "sites count", n, "bases");
-    const int lrc = wfa::launch_sites_count(a, al->stream);
-    timer.stop();
-    if (lrc != 0) { al->err = "sites count kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, hipMemcpyAsync(&total, a.chunk_off + a.chunks, sizeof(total), hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-  }
-  *count = (int64_t)total;
-  a.cap = std::min<int64_t>((int64_t)total, cap);
-  if (a.cap == 0) return WFA_HIP_OK;
-  if (sc.alloc(&a.rows, (size_t)a.cap * WFA_SITE_COLS)) return WFA_HIP_EDEVICE;
-  {
-    ReduceTimer timer(al, "sites scatter", n, "bases");
-    const int lrc = wfa::launch_sites_scatter(a, al->stream);
-    timer.stop();
-    if (lrc != 0) { al->err = "sites scatter kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, hipMemcpyAsync(rows, a.rows, (size_t)a.cap * WFA_SITE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-  }
-  return WFA_HIP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// placement: one row per read from the hits of any number of batches (include/wfa_hip.h; csrc/wfa_place.hpp, k_place.hip)
-// ------------------------------------------------------------------------------------------------
-static_assert(WFA_PLACE_COLS == WFA_HIP_PLACE_COLS, "columns of the kernels and of the ABI");
-
-namespace wfa {   // host_place.cpp: the checks shared with wfa_hip_place_host
-int place_check_hits(int64_t nreads, int64_t base, int64_t n, const int32_t* i, const int32_t* j, const int32_t* text_start,
-                     const int32_t* text_end, char* msg, size_t cap);
-int place_check_run(int32_t full_gap, char* msg, size_t cap);
-// host_pair.cpp: the check shared with wfa_hip_pair_host
-int pair_check(int64_t nreads, int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
-               const int32_t* mate2, char* msg, size_t cap);
-}
-static_assert(WFA_PAIR_COLS == WFA_HIP_PAIR_COLS && WFA_PAIR_MAX_PAIRINGS == WFA_HIP_PAIR_MAX_PAIRINGS, "pairing: the kernels and the ABI");
-
-struct wfa_hip_placer {
-  wfa_hip_aligner* al = nullptr;
-  int64_t nreads = 0;
-  int64_t nhits = 0, cap = 0;          // records in use, and allocated
-  wfa::PlaceHit* d_hits = nullptr;     // the records, in hit-number order
-  uint32_t* d_count = nullptr;         // [nreads + 1] (wfa_place.hpp: PlaceArgs::count)
-  uint32_t* d_bsum = nullptr;
-  uint32_t* d_order = nullptr;         // [order_cap] the grouped hit numbers
-  int64_t order_cap = 0;
-  int64_t grouped = -1;                // the number of hits d_count / d_order were made for (-1: none)
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  float last_ms = 0.f;
-};
-
-extern "C" void wfa_hip_placer_destroy(wfa_hip_placer_t* p) {
-  if (!p) return;
-  wfa_hip_aligner* al = p->al;
-  (void)hipSetDevice(al->device);
-  (void)hipStreamSynchronize(al->stream);
-  pool_release(al, p->d_hits); pool_release(al, p->d_count); pool_release(al, p->d_bsum); pool_release(al, p->d_order);
-  for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
-  delete p;
-  aligner_release_ref(al);
-}
-
-// a device block of `bytes`, or WFA_HIP_EDEVICE with the byte count in the message
-static int placer_alloc(wfa_hip_aligner* al, void** out, size_t bytes, const char* what) {
-  if (pool_alloc(al, out, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    *out = nullptr;
-    char buf[160];
-    snprintf(buf, sizeof(buf), "placement: the allocation of %zu bytes failed (%s)", bytes, what);
-    al->err = buf;
-    return WFA_HIP_EDEVICE;
-  }
-  return WFA_HIP_OK;
-}
-
-extern "C" wfa_hip_placer_t* wfa_hip_placer_create(wfa_hip_aligner_t* al, int64_t nreads) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  if (nreads < 0 || nreads >= (int64_t)INT32_MAX) {
-    char buf[120];
-    snprintf(buf, sizeof(buf), "placement: nreads = %lld is out of range (0 .. 2^31 - 2)", (long long)nreads);
-    al->err = buf; g_error = al->err; return nullptr;
-  }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
-  wfa_hip_placer* p = new wfa_hip_placer();
-  p->al = al;
-  p->nreads = nreads;
-  al->live_batches += 1;
-  const size_t chunks = (size_t)((nreads + 1 + WFA_PLACE_SCAN_CHUNK - 1) / WFA_PLACE_SCAN_CHUNK);
-  if (placer_alloc(al, (void**)&p->d_count, (size_t)(nreads + 1) * sizeof(uint32_t), "4 bytes per read") != WFA_HIP_OK ||
-      placer_alloc(al, (void**)&p->d_bsum, chunks * sizeof(uint32_t), "the scan's chunk sums") != WFA_HIP_OK) {
-    g_error = al->err; wfa_hip_placer_destroy(p); return nullptr;
-  }
-  if (hipEventCreate(&p->ev[0]) != hipSuccess || hipEventCreate(&p->ev[1]) != hipSuccess) {
-    al->err = "placement: hipEventCreate failed";
-    g_error = al->err; wfa_hip_placer_destroy(p); return nullptr;
-  }
-  return p;
-}
-
-extern "C" int64_t wfa_hip_placer_count(const wfa_hip_placer_t* p) { return p ? p->nhits : 0; }
-
-extern "C" int wfa_hip_placer_clear(wfa_hip_placer_t* p) {
-  if (!p) return WFA_HIP_EINVAL;
-  p->nhits = 0; p->grouped = -1;
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_placer_kernel_ms(const wfa_hip_placer_t* p, float* ms) {
-  if (!p || !ms) return WFA_HIP_EINVAL;
-  *ms = p->last_ms;
-  return WFA_HIP_OK;
-}
-
-// room for `more` records behind the ones in use: doubling, the records copied on the aligner's stream
-static int placer_reserve(wfa_hip_placer* p, int64_t more) {
-  wfa_hip_aligner* al = p->al;
-  if (p->nhits + more <= p->cap) return WFA_HIP_OK;
-  const int64_t want = std::max<int64_t>(p->nhits + more, std::max<int64_t>(2 * p->cap, 1024));
-  wfa::PlaceHit* d_new = nullptr;
-  const int rc = placer_alloc(al, (void**)&d_new, (size_t)want * sizeof(wfa::PlaceHit), "32 bytes per hit");
-  if (rc != WFA_HIP_OK) return rc;
-  if (p->nhits > 0) {
-    const hipError_t e = hipMemcpyAsync(d_new, p->d_hits, (size_t)p->nhits * sizeof(wfa::PlaceHit), hipMemcpyDeviceToDevice, al->stream);
-    const hipError_t e2 = hipStreamSynchronize(al->stream);
-    if (e != hipSuccess || e2 != hipSuccess) { pool_release(al, d_new); HIP_TRY(al, e); HIP_TRY(al, e2); }
-  }
-  pool_release(al, p->d_hits);
-  p->d_hits = d_new; p->cap = want;
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_placer_add(wfa_hip_placer_t* p, wfa_hip_batch_t* b, const int32_t* i, const int32_t* j, const int32_t* t_start,
-                                  const uint8_t* reverse) {
-  if (!p) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = p->al;
-  if (!b) { al->err = "placement: null batch"; return WFA_HIP_EINVAL; }
-  if (b->al != al) { al->err = "placement: batch of another aligner"; return WFA_HIP_EINVAL; }
-  if (!b->ran) { al->err = "placement needs a finished run of the batch"; return WFA_HIP_EINVAL; }
-  const int64_t n = b->n;
-  char buf[240];
-  if (wfa::place_check_hits(p->nreads, p->nhits, n, i, j, t_start, nullptr, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  int rc = wfa_hip_batch_sync(b);
-  if (rc != WFA_HIP_OK) return rc;
-  if (n == 0) return WFA_HIP_OK;
-  HIP_TRY(al, hipSetDevice(al->device));
-  rc = placer_reserve(p, n);
-  if (rc != WFA_HIP_OK) return rc;
-  CrossScratch sc{al};   // (waits for the stream before the blocks go back)
-  int32_t *d_i = nullptr, *d_j = nullptr, *d_ts = nullptr;
-  uint8_t* d_rev = nullptr;
-  if (sc.alloc(&d_i, (size_t)n) || sc.alloc(&d_j, (size_t)n)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipMemcpyAsync(d_i, i, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  HIP_TRY(al, hipMemcpyAsync(d_j, j, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  if (t_start) {
-    if (sc.alloc(&d_ts, (size_t)n)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_ts, t_start, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  }
-  if (reverse) {
-    if (sc.alloc(&d_rev, (size_t)n)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_rev, reverse, (size_t)n, hipMemcpyHostToDevice, al->stream));
-  }
-  const bool full = b->cfg.scope == WFA_SCOPE_FULL;
-  wfa::PlaceRecordArgs a;
-  memset(&a, 0, sizeof(a));
-  a.score = b->d_score; a.status = b->d_status; a.meta = b->d_meta;
-  if (full) { a.ops = b->d_ops; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len; }
-  a.npairs = n; a.i = d_i; a.j = d_j; a.t_start = d_ts; a.reverse = d_rev; a.out = p->d_hits + p->nhits;
-  {
-    ReduceTimer timer(al, "place record", n);
-    const int lrc = wfa::launch_place_record(a, full, al->cu_count, al->stream);
-    timer.stop();
-    const hipError_t e = hipStreamSynchronize(al->stream);   // (the caller's arrays are read by the copies above)
-    if (lrc != 0) { al->err = "placement: record kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, e);
-  }
-  p->nhits += n; p->grouped = -1;
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_placer_add_hits(wfa_hip_placer_t* p, int64_t n, const int32_t* i, const int32_t* j, const uint8_t* reverse,
-                                       const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end) {
-  if (!p) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = p->al;
-  if (n > 0 && (!score || !status || !text_start || !text_end)) { al->err = "placement: a missing array"; return WFA_HIP_EINVAL; }
-  char buf[240];
-  if (wfa::place_check_hits(p->nreads, p->nhits, n, i, j, text_start, text_end, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (n == 0) return WFA_HIP_OK;
-  HIP_TRY(al, hipSetDevice(al->device));
-  const int rc = placer_reserve(p, n);
-  if (rc != WFA_HIP_OK) return rc;
-  std::vector<wfa::PlaceHit> rec((size_t)n);
-  for (int64_t q = 0; q < n; ++q) {
-    wfa::PlaceHit& h = rec[(size_t)q];
-    h.i = i[q]; h.j = j[q]; h.reverse = (reverse && reverse[q]) ? 1 : 0; h.status = status[q];
-    h.score = score[q]; h.ts = text_start[q]; h.te = text_end[q]; h.spare = 0;
-  }
-  HIP_TRY(al, hipMemcpyAsync(p->d_hits + p->nhits, rec.data(), (size_t)n * sizeof(wfa::PlaceHit), hipMemcpyHostToDevice, al->stream));
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  p->nhits += n; p->grouped = -1;
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_placer_run(wfa_hip_placer_t* p, int32_t min_score, int32_t full_gap, int32_t* rows, uint8_t* flags) {
-  if (!p) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = p->al;
-  char buf[160];
-  if (wfa::place_check_run(full_gap, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (p->nreads > 0 && !rows) { al->err = "placement: null rows"; return WFA_HIP_EINVAL; }
-  if (p->nreads == 0) return WFA_HIP_OK;
-  HIP_TRY(al, hipSetDevice(al->device));
-  if (p->nhits > p->order_cap) {
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
-    const int rc = placer_alloc(al, (void**)&p->d_order, (size_t)p->cap * sizeof(uint32_t), "4 bytes per hit");
-    if (rc != WFA_HIP_OK) return rc;
-    p->order_cap = p->cap;
-  }
-  CrossScratch sc{al};
-  wfa::PlaceArgs a;
-  memset(&a, 0, sizeof(a));
-  a.hits = p->d_hits; a.nhits = p->nhits; a.nreads = p->nreads; a.count = p->d_count; a.bsum = p->d_bsum; a.order = p->d_order;
-  a.min_score = min_score; a.full_gap = full_gap;
-  if (sc.alloc(&a.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
-  if (flags && sc.alloc(&a.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
-  {
-    ReduceTimer timer(al, "place", p->nhits, "hits");
-    HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
-    int lrc = 0;
-    if (p->grouped != p->nhits) {
-      p->grouped = -1;
-      HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
-      lrc = wfa::launch_place_group(a, al->stream);
-    }
-    if (lrc == 0) lrc = wfa::launch_place(a, al->cu_count, al->stream);
-    HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
-    timer.stop();
-    if (lrc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "placement: kernel launch failed"; return WFA_HIP_EDEVICE; }
-    p->grouped = p->nhits;
-    HIP_TRY(al, hipMemcpyAsync(rows, a.rows, (size_t)p->nreads * WFA_PLACE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-    if (flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(flags, a.flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
-  }
-  return WFA_HIP_OK;
-}
-
-// group (when the hits changed), place, then the pair kernel: the single-end rows and flags stay on the device for the join
-extern "C" int wfa_hip_placer_run_pairs(wfa_hip_placer_t* p, int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert,
-                                        int32_t unpaired, int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int32_t* rows,
-                                        uint8_t* flags, int32_t* pair_rows, uint8_t* pair_flags) {
-  if (!p) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = p->al;
-  char buf[240];
-  if (wfa::place_check_run(full_gap, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (wfa::pair_check(p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (nfrag > 0 && !pair_rows) { al->err = "pairing: null pair_rows"; return WFA_HIP_EINVAL; }
-  if (p->nreads == 0) return WFA_HIP_OK;   // (no read: no fragment, no hit)
-  HIP_TRY(al, hipSetDevice(al->device));
-  if (p->nhits > p->order_cap) {
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
-    const int rc = placer_alloc(al, (void**)&p->d_order, (size_t)p->cap * sizeof(uint32_t), "4 bytes per hit");
-    if (rc != WFA_HIP_OK) return rc;
-    p->order_cap = p->cap;
-  }
-  CrossScratch sc{al};
-  wfa::PairArgs a;
-  memset(&a, 0, sizeof(a));
-  wfa::PlaceArgs& s = a.place;
-  s.hits = p->d_hits; s.nhits = p->nhits; s.nreads = p->nreads; s.count = p->d_count; s.bsum = p->d_bsum; s.order = p->d_order;
-  s.min_score = min_score; s.full_gap = full_gap;
-  a.min_insert = min_insert; a.max_insert = max_insert; a.unpaired = unpaired; a.nfrag = nfrag;
-  if (sc.alloc(&s.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
-  if (sc.alloc(&s.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
-  if (pair_flags && sc.alloc(&a.pair_flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
-  if (nfrag > 0 && sc.alloc(&a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS)) return WFA_HIP_EDEVICE;
-  if (mate1 && nfrag > 0) {
-    int32_t *d_m1 = nullptr, *d_m2 = nullptr;
-    if (sc.alloc(&d_m1, (size_t)nfrag) || sc.alloc(&d_m2, (size_t)nfrag)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_m1, mate1, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(d_m2, mate2, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    a.mate1 = d_m1; a.mate2 = d_m2;
-  }
-  {
-    ReduceTimer timer(al, "place pairs", p->nhits, "hits");
-    HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
-    int lrc = 0;
-    if (p->grouped != p->nhits) {
-      p->grouped = -1;
-      HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
-      lrc = wfa::launch_place_group(s, al->stream);
-    }
-    if (lrc == 0) lrc = wfa::launch_place(s, al->cu_count, al->stream);
-    // reads in no fragment, and fragments that are not proper, keep their single-end flags
-    if (lrc == 0 && a.pair_flags && p->nhits > 0)
-      HIP_TRY(al, hipMemcpyAsync(a.pair_flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToDevice, al->stream));
-    if (lrc == 0) lrc = wfa::launch_pair(a, al->cu_count, al->stream);
-    HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
-    timer.stop();
-    if (lrc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "pairing: kernel launch failed"; return WFA_HIP_EDEVICE; }
-    p->grouped = p->nhits;
-    if (rows) HIP_TRY(al, hipMemcpyAsync(rows, s.rows, (size_t)p->nreads * WFA_PLACE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-    if (flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
-    if (nfrag > 0) HIP_TRY(al, hipMemcpyAsync(pair_rows, a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-    if (pair_flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(pair_flags, a.pair_flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
-  }
-  return WFA_HIP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// seed finder: a k-mer index over a text set, candidate windows per read (include/wfa_hip.h; csrc/wfa_seed.hpp, k_seed.hip)
-// ------------------------------------------------------------------------------------------------
-static_assert(WFA_SEED_MAX_N == WFA_HIP_SEED_MAX_N && WFA_SEED_MAX_HITS == WFA_HIP_SEED_MAX_HITS, "bounds of the kernels and of the ABI");
-static_assert(WFA_SEED_MAX_W == WFA_HIP_MINIMIZER_MAX_W, "bounds of the minimizer kernels and of the ABI");
-static_assert(WFA_CHAIN_MAX_LOOKBACK == WFA_HIP_CHAIN_MAX_LOOKBACK && WFA_CHAIN_MAX_ANCHORS == WFA_HIP_CHAIN_MAX_ANCHORS, "bounds of the chain kernel and of the ABI");
-
-namespace wfa {   // host_seed.cpp: the parameter checks shared with wfa_hip_seeds_host
-int seed_check_index(int k, int stride, int max_occ, char* msg, size_t cap);
-int seed_check_minimizer(int k, int w, int max_occ, char* msg, size_t cap);
-int seed_check_query(int n, int min_hits, int gap, int pad, int max_hits, char* msg, size_t cap);
-// host_chain.cpp: the check shared with wfa_hip_chains_host
-int seed_check_chain(int n, int min_hits, int min_score, int lookback, int max_dist, int band, int pad, int max_anchors, char* msg, size_t cap);
-}
-
-struct wfa_hip_seed_index {
-  wfa_hip_aligner* al = nullptr;
-  int k = 0, stride = 0, max_occ = 0;
-  int w = 0;                          // 0: a stride index; 1 .. 32: a minimizer index (stride = 1)
-  int64_t nseq = 0;
-  uint32_t* d_table = nullptr;        // 4^k + 1 bucket starts (its own allocation: 4^k * 4 bytes)
-  wfa::SeedRec* d_recs = nullptr;     // {j, t} per indexed position, in bucket order (its own allocation)
-  int32_t* d_len = nullptr;           // the texts' lengths
-  int64_t positions = 0, masked = 0, table_bytes = 0;
-  float build_ms = 0.f, query_ms = 0.f;
-  int32_t* d_chain_ws = nullptr;      // the chaining workspace: a slab per workgroup of the last launch (its own allocation, grown on demand)
-  size_t chain_ws_bytes = 0;
-  float chain_ms = 0.f;
-};
-
-// The letters outside ACGT of a set as the seed kernels read them: bit b of mask[w] = base 16 (w - woff) + b of the word's sequence,
-// from the runs the set keeps on the host; uploaded on the first call, nullptr when no sequence of the set is flagged.
-static int seqset_mask(wfa_hip_aligner* al, const wfa_hip_seqset* S, const uint16_t** out) {
-  *out = S->d_mask;
-  if (S->d_mask || std::find(S->h_flag.begin(), S->h_flag.end(), (uint8_t)1) == S->h_flag.end()) return WFA_HIP_OK;
-  std::vector<uint16_t> mask((size_t)S->nwords + 4, 0);
-  uint64_t w = 0;
-  for (int64_t q = 0; q < S->n; ++q) {
-    const std::vector<int32_t>& r = S->h_runs[(size_t)q];
-    for (size_t x = 0; x + 1 < r.size(); x += 2)
-      for (int32_t p = r[x]; p < r[x + 1]; ++p) mask[(size_t)w + ((size_t)p >> 4)] |= (uint16_t)(1u << (p & 15));
-    w += (uint64_t)((S->h_len[(size_t)q] + 15) >> 4);
-  }
-  uint16_t* d = nullptr;
-  HIP_TRY(al, pool_alloc(al, (void**)&d, mask.size() * sizeof(uint16_t)));
-  const hipError_t e = hipMemcpy(d, mask.data(), mask.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { pool_release(al, d); HIP_TRY(al, e); }
-  S->d_mask = d;
-  *out = d;
-  return WFA_HIP_OK;
-}
-
-static wfa::SeedSetView seed_view(const wfa_hip_seqset* S, const uint16_t* mask) {
-  wfa::SeedSetView v;
-  v.words = S->d_words; v.mask = mask; v.woff = S->d_woff; v.len = S->d_len; v.nseq = S->n; v.nwords = S->nwords;
-  return v;
-}
-
-extern "C" void wfa_hip_seed_index_destroy(wfa_hip_seed_index_t* x) {
-  if (!x) return;
-  wfa_hip_aligner* al = x->al;
-  (void)hipSetDevice(al->device);
-  if (x->d_table) (void)hipFree(x->d_table);
-  if (x->d_recs) (void)hipFree(x->d_recs);
-  if (x->d_chain_ws) (void)hipFree(x->d_chain_ws);
-  pool_release(al, x->d_len);
-  delete x;
-  aligner_release_ref(al);
-}
-
-static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wfa_hip_seqset* T) {
-  x->nseq = T->n;
-  uint64_t cap = 0;   // the positions the stride takes of sequences without a flagged letter: at least the indexed ones
-  for (int32_t len : T->h_len)
-    if (len >= x->k) cap += (uint64_t)((len - x->k) / x->stride + 1);
-  const uint64_t buckets = 1ull << (2 * x->k);
-  const size_t table_bytes = (size_t)(buckets + 1) * sizeof(uint32_t), rec_bytes = (size_t)std::max<uint64_t>(cap, 1) * sizeof(wfa::SeedRec);
-  char buf[240];
-  if (hipMalloc((void**)&x->d_table, table_bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    x->d_table = nullptr;
-    snprintf(buf, sizeof(buf), "seed index table: hipMalloc of %zu bytes failed (4 bytes per k-mer of k = %d: 4^k buckets)", table_bytes, x->k);
-    al->err = buf;
-    return WFA_HIP_EDEVICE;
-  }
-  const auto alloc_recs = [&](size_t bytes, uint64_t positions) {
-    if (hipMalloc((void**)&x->d_recs, bytes) == hipSuccess) return true;
-    (void)hipGetLastError();
-    x->d_recs = nullptr;
-    snprintf(buf, sizeof(buf), "seed index records: hipMalloc of %zu bytes failed (8 bytes per indexed position, %llu positions)", bytes,
-             (unsigned long long)positions);
-    al->err = buf;
-    return false;
-  };
-  if (x->w == 0 && !alloc_recs(rec_bytes, cap)) return WFA_HIP_EDEVICE;   // (a minimizer index: after the counting pass, by its total)
-  x->table_bytes = (int64_t)(table_bytes + rec_bytes);
-  const uint16_t* mask = nullptr;
-  if (seqset_mask(al, T, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
-  CrossScratch sc{al};
-  uint32_t *d_bsum = nullptr, *d_masked = nullptr;
-  if (sc.alloc(&d_bsum, (size_t)((buckets + 1 + WFA_SEED_SCAN_CHUNK - 1) / WFA_SEED_SCAN_CHUNK)) || sc.alloc(&d_masked, 1)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, pool_alloc(al, (void**)&x->d_len, (size_t)T->n * sizeof(int32_t)));
-  HIP_TRY(al, hipMemcpyAsync(x->d_len, T->d_len, (size_t)T->n * sizeof(int32_t), hipMemcpyDeviceToDevice, al->stream));
-  HIP_TRY(al, hipEventCreate(&sc.ev[0]));
-  HIP_TRY(al, hipEventCreate(&sc.ev[1]));
-  wfa::SeedBuildArgs a;
-  memset(&a, 0, sizeof(a));
-  a.t = seed_view(T, mask);
-  a.k = x->k; a.stride = x->stride; a.w = x->w; a.max_occ = (uint32_t)x->max_occ;
-  a.table = x->d_table; a.recs = x->d_recs; a.bsum = d_bsum; a.masked = d_masked;
-  HIP_TRY(al, hipEventRecord(sc.ev[0], al->stream));
-  HIP_TRY(al, hipMemsetAsync(x->d_table, 0, table_bytes, al->stream));
-  HIP_TRY(al, hipMemsetAsync(d_masked, 0, sizeof(uint32_t), al->stream));
-  int lrc = wfa::launch_seed_count(a, al->stream) | wfa::launch_seed_scan(a, al->stream);
-  uint32_t total = 0, masked = 0;
-  if (x->w >= 1 && lrc == 0) {
-    // the records by the count: the scan has left the total behind the last bucket
-    HIP_TRY(al, hipMemcpyAsync(&total, x->d_table + buckets, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    cap = total;
-    const size_t bytes = (size_t)std::max<uint64_t>(cap, 1) * sizeof(wfa::SeedRec);
-    if (!alloc_recs(bytes, cap)) return WFA_HIP_EDEVICE;
-    x->table_bytes = (int64_t)(table_bytes + bytes);
-    a.recs = x->d_recs;
-  }
-  lrc |= wfa::launch_seed_fill(a, (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull), al->stream);
-  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
-  HIP_TRY(al, hipMemcpyAsync(&total, x->d_table + buckets, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
-  HIP_TRY(al, hipMemcpyAsync(&masked, d_masked, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
-  const hipError_t e = hipStreamSynchronize(al->stream);
-  if (lrc != 0) { al->err = "seed index kernel launch failed"; return WFA_HIP_EDEVICE; }
-  HIP_TRY(al, e);
-  HIP_TRY(al, hipEventElapsedTime(&x->build_ms, sc.ev[0], sc.ev[1]));
-  x->positions = total; x->masked = masked;
-  return WFA_HIP_OK;
-}
-
-// the one body of both creates; minimizer: w is the window and stride plays no part, otherwise w = 0
-static wfa_hip_seed_index_t* seed_index_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int stride, int w, int max_occ, bool minimizer) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  char buf[200];
-  if (!texts || texts->al != al) { al->err = "seed index: sequence set of another aligner"; g_error = al->err; return nullptr; }
-  const int crc = minimizer ? wfa::seed_check_minimizer(k, w, max_occ, buf, sizeof(buf)) : wfa::seed_check_index(k, stride, max_occ, buf, sizeof(buf));
-  if (crc != WFA_HIP_OK) { al->err = buf; g_error = al->err; return nullptr; }
-  if (texts->n == 0) { al->err = "seed index: texts = a set of 0 sequences is out of range (at least 1)"; g_error = al->err; return nullptr; }
-  if (texts->nbytes >= (1ll << 31)) {
-    snprintf(buf, sizeof(buf), "seed index: texts = a set of %lld bases is out of range (below 2^31: split the set)", (long long)texts->nbytes);
-    al->err = buf; g_error = al->err; return nullptr;
-  }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
-  mailbox_release(al);   // (the resident one-pair kernel: the build takes the device)
-  wfa_hip_seed_index* x = new wfa_hip_seed_index();
-  x->al = al; x->k = k; x->stride = stride; x->w = w; x->max_occ = max_occ;
-  al->live_batches += 1;
-  if (seed_index_build(al, x, texts) != WFA_HIP_OK) { g_error = al->err; wfa_hip_seed_index_destroy(x); return nullptr; }
-  return x;
-}
-
-extern "C" wfa_hip_seed_index_t* wfa_hip_seed_index_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int stride, int max_occ) {
-  return seed_index_create(al, texts, k, stride, 0, max_occ, false);
-}
-
-extern "C" wfa_hip_seed_index_t* wfa_hip_seed_index_create_minimizer(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int w, int max_occ) {
-  return seed_index_create(al, texts, k, 1, w, max_occ, true);
-}
-
-extern "C" int wfa_hip_seed_index_params(const wfa_hip_seed_index_t* x, int* k, int* stride, int* w) {
-  if (!x) return WFA_HIP_EINVAL;
-  if (k) *k = x->k;
-  if (stride) *stride = x->stride;
-  if (w) *w = x->w;
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_seed_index_query(wfa_hip_seed_index_t* x, const wfa_hip_seqset_t* P, int n, int min_hits, int gap, int pad, int max_hits,
-                                        int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow) {
-  if (!x) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = x->al;
-  char buf[200];
-  if (!P || P->al != al) { al->err = "seed query: sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (wfa::seed_check_query(n, min_hits, gap, pad, max_hits, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  const int64_t m = P->n;
-  if (m == 0) return WFA_HIP_OK;
-  if (!j || !reverse || !text_start || !text_len || !hits || !overflow) { al->err = "seed query: a result array is missing"; return WFA_HIP_EINVAL; }
-  HIP_TRY(al, hipSetDevice(al->device));
-  mailbox_release(al);
-  const uint16_t* mask = nullptr;
-  if (seqset_mask(al, P, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
-  CrossScratch sc{al};
-  const size_t cells = (size_t)m * (size_t)n;
-  int32_t* d_rows = nullptr;
-  uint8_t* d_over = nullptr;
-  if (sc.alloc(&d_rows, 5 * cells) || sc.alloc(&d_over, (size_t)m)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipEventCreate(&sc.ev[0]));
-  HIP_TRY(al, hipEventCreate(&sc.ev[1]));
-  wfa::SeedQueryArgs a;
-  memset(&a, 0, sizeof(a));
-  a.p = seed_view(P, mask);
-  a.table = x->d_table; a.recs = x->d_recs; a.t_len = x->d_len; a.t_nseq = x->nseq;
-  a.k = x->k; a.w = x->w; a.max_occ = (uint32_t)x->max_occ;
-  a.n = n; a.min_hits = min_hits; a.max_hits = max_hits; a.gap = (uint32_t)gap; a.pad = pad;
-  a.j = d_rows; a.reverse = d_rows + cells; a.text_start = d_rows + 2 * cells; a.text_len = d_rows + 3 * cells; a.hits = d_rows + 4 * cells;
-  a.overflow = d_over;
-  HIP_TRY(al, hipEventRecord(sc.ev[0], al->stream));
-  const int lrc = wfa::launch_seed_query(a, m, al->cu_count, al->stream);
-  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
-  int32_t* host[5] = {j, reverse, text_start, text_len, hits};
-  for (int c = 0; c < 5; ++c)
-    HIP_TRY(al, hipMemcpyAsync(host[c], d_rows + (size_t)c * cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-  HIP_TRY(al, hipMemcpyAsync(overflow, d_over, (size_t)m, hipMemcpyDeviceToHost, al->stream));
-  const hipError_t e = hipStreamSynchronize(al->stream);
-  if (lrc != 0) { al->err = "seed query kernel launch failed"; return WFA_HIP_EDEVICE; }
-  HIP_TRY(al, e);
-  HIP_TRY(al, hipEventElapsedTime(&x->query_ms, sc.ev[0], sc.ev[1]));
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_seed_index_stats(const wfa_hip_seed_index_t* x, int64_t* positions, int64_t* masked_kmers, int64_t* table_bytes,
-                                        float* build_ms, float* query_ms) {
-  if (!x) return WFA_HIP_EINVAL;
-  if (positions) *positions = x->positions;
-  if (masked_kmers) *masked_kmers = x->masked;
-  if (table_bytes) *table_bytes = x->table_bytes;
-  if (build_ms) *build_ms = x->build_ms;
-  if (query_ms) *query_ms = x->query_ms;
-  return WFA_HIP_OK;
-}
-
-// chains: the anchors of every read chained along the read, the best chains as windows (include/wfa_hip.h "chains"; csrc/wfa_chain.hpp)
-extern "C" int wfa_hip_seed_index_chain(wfa_hip_seed_index_t* x, const wfa_hip_seqset_t* P, int n, int min_hits, int min_score, int lookback,
-                                        int max_dist, int band, int pad, int max_anchors, int32_t* j, int32_t* reverse, int32_t* text_start,
-                                        int32_t* text_len, int32_t* hits, int32_t* score, int32_t* pattern_start, int32_t* pattern_len,
-                                        uint8_t* overflow) {
-  if (!x) return WFA_HIP_EINVAL;
-  wfa_hip_aligner* al = x->al;
-  char buf[240];
-  if (!P || P->al != al) { al->err = "seed chain: sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (wfa::seed_check_chain(n, min_hits, min_score, lookback, max_dist, band, pad, max_anchors, buf, sizeof(buf)) != WFA_HIP_OK) {
-    al->err = buf;
-    return WFA_HIP_EINVAL;
-  }
-  const int64_t m = P->n;
-  if (m == 0) return WFA_HIP_OK;
-  if (!j || !reverse || !text_start || !text_len || !hits || !score || !pattern_start || !pattern_len || !overflow) {
-    al->err = "seed chain: a result array is missing";
-    return WFA_HIP_EINVAL;
-  }
-  HIP_TRY(al, hipSetDevice(al->device));
-  mailbox_release(al);
-  const uint16_t* mask = nullptr;
-  if (seqset_mask(al, P, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
-  // the workspace: a slab of WFA_CHAIN_PLANES x max_anchors int32 per workgroup of this launch
-  const unsigned grid = wfa::chain_grid(m, al->cu_count);
-  const size_t ws_bytes = (size_t)grid * WFA_CHAIN_PLANES * (size_t)max_anchors * sizeof(int32_t);
-  if (ws_bytes > x->chain_ws_bytes) {
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    if (x->d_chain_ws) (void)hipFree(x->d_chain_ws);
-    x->d_chain_ws = nullptr;
-    x->chain_ws_bytes = 0;
-    if (hipMalloc((void**)&x->d_chain_ws, ws_bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      x->d_chain_ws = nullptr;
-      snprintf(buf, sizeof(buf), "seed chain workspace: hipMalloc of %zu bytes failed (32 bytes x max_anchors = %d per workgroup, %u workgroups)",
-               ws_bytes, max_anchors, grid);
-      al->err = buf;
-      return WFA_HIP_EDEVICE;
-    }
-    x->chain_ws_bytes = ws_bytes;
-  }
-  CrossScratch sc{al};
-  const size_t cells = (size_t)m * (size_t)n;
-  int32_t* d_rows = nullptr;
-  uint8_t* d_over = nullptr;
-  if (sc.alloc(&d_rows, 8 * cells) || sc.alloc(&d_over, (size_t)m)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipEventCreate(&sc.ev[0]));
-  HIP_TRY(al, hipEventCreate(&sc.ev[1]));
-  wfa::ChainArgs a;
-  memset(&a, 0, sizeof(a));
-  a.p = seed_view(P, mask);
-  a.table = x->d_table; a.recs = x->d_recs; a.t_len = x->d_len; a.t_nseq = x->nseq;
-  a.k = x->k; a.w = x->w; a.max_occ = (uint32_t)x->max_occ;
-  a.n = n; a.min_hits = min_hits; a.min_score = min_score; a.lookback = lookback; a.max_dist = max_dist; a.band = band; a.pad = pad;
-  a.max_anchors = (uint32_t)max_anchors;
-  a.slab = x->d_chain_ws;
-  a.j = d_rows; a.reverse = d_rows + cells; a.text_start = d_rows + 2 * cells; a.text_len = d_rows + 3 * cells; a.hits = d_rows + 4 * cells;
-  a.score = d_rows + 5 * cells; a.pattern_start = d_rows + 6 * cells; a.pattern_len = d_rows + 7 * cells;
-  a.overflow = d_over;
-  HIP_TRY(al, hipEventRecord(sc.ev[0], al->stream));
-  const int lrc = wfa::launch_chain(a, m, grid, al->stream);
-  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
-  int32_t* host[8] = {j, reverse, text_start, text_len, hits, score, pattern_start, pattern_len};
-  for (int c = 0; c < 8; ++c)
-    HIP_TRY(al, hipMemcpyAsync(host[c], d_rows + (size_t)c * cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-  HIP_TRY(al, hipMemcpyAsync(overflow, d_over, (size_t)m, hipMemcpyDeviceToHost, al->stream));
-  const hipError_t e = hipStreamSynchronize(al->stream);
-  if (lrc != 0) { al->err = "seed chain kernel launch failed"; return WFA_HIP_EDEVICE; }
-  HIP_TRY(al, e);
-  HIP_TRY(al, hipEventElapsedTime(&x->chain_ms, sc.ev[0], sc.ev[1]));
-  return WFA_HIP_OK;
-}
-
-extern "C" int wfa_hip_seed_index_chain_stats(const wfa_hip_seed_index_t* x, float* kernel_ms, int64_t* workspace_bytes) {
-  if (!x) return WFA_HIP_EINVAL;
-  if (kernel_ms) *kernel_ms = x->chain_ms;
-  if (workspace_bytes) *workspace_bytes = (int64_t)x->chain_ws_bytes;
   return WFA_HIP_OK;
 }

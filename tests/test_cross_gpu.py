@@ -215,6 +215,11 @@ def test_errors(gpu):
         blob = np.frombuffer(b"ACGTNACGTT" + b"\0" * 64, np.uint8)
         s = na.seqset(blob, np.array([0, 5], np.int64), np.array([5, 5], np.int32))
         na.cross(s).close()
+        # a refused run gives no handle back: its reason is in wfa_hip_global_error() too, whichever unit of the library raised it
+        q = na.seqset(np.frombuffer(b"ACGTTGCAACGTTGCAACGT" * 4 + b"\0" * 64, np.uint8), np.arange(4, dtype=np.int64) * 20, np.full(4, 20, np.int32))
+        assert not _native.lib().wfa_hip_cross_run_k(na._h, q._h, None, 0, 0)
+        assert _native.lib().wfa_hip_global_error().decode().startswith("want: a combination of WFA_HIP_CROSS_DENSE")
+        q.close()
         cfg.wildcard = ord("N")
         na.set_config(cfg)
         with pytest.raises(ValueError, match="wildcard"):
