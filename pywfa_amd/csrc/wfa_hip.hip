@@ -1355,7 +1355,7 @@ static int pilot_first_width(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t 
   if (!full && b->stage_pick == 16 && wfa::seg_shape(b->dcfg, &X, &OE, &E) != WFA_SHAPE_RTC) {
     HIP_TRY(al, hipMemsetAsync(pcount, 0, sizeof(uint32_t), stream));
     if (wfa::launch_lane(wfa::seg_shape(b->dcfg, &X, &OE, &E), wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1), al->cu_count,
-                         knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, b->d_words, b->d_meta, psample, nullptr, np,
+                         knob(al, K_LANE_WAVES_PER_CU, 48), wfa::lane_refill_arg(knob(al, K_LANE_REFILL_MIN, 8), knob(al, K_LANE_WINFIN, 1) != 0), b->max_len, stream, b->d_words, b->d_meta, psample, nullptr, np,
                          b->d_score, b->d_status, plist, pcount, nullptr, 0, X, OE, E, 0, nullptr, 0, 4) != 0) return pilot_launch_failed(al, b, rtc_failures);
     uint32_t handed = 0;
     HIP_TRY(al, hipMemcpyAsync(&handed, pcount, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -2567,7 +2567,9 @@ static int run_fast_stages(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t st
         lane_dyn = (uint32_t)std::max<int64_t>(64, std::min<int64_t>(lane_dyn, per_wave));
       }
       lrc = wfa::launch_lane(p.shape, affine_gcd(b->dcfg), al->cu_count,
-                             lane_dyn ? dyn_waves : knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, b->d_words, b->d_meta,
+                             lane_dyn ? dyn_waves : knob(al, K_LANE_WAVES_PER_CU, 48),
+                             // (WFA_HIP_LANE_WINFIN=0: the window pass finishes only what the refill used to, for A/B runs and tests)
+                             wfa::lane_refill_arg(knob(al, K_LANE_REFILL_MIN, 8), knob(al, K_LANE_WINFIN, 1) != 0), b->max_len, stream, b->d_words, b->d_meta,
                              c.in_list, c.in_count, c.in_n, b->d_score, b->d_status, out_list, out_count,
                              (knob(al, K_LANE_DEBUG, 0) && al->ws) ? al->ws : nullptr, knob(al, K_LANE_LDS_PAD_KB, 0), p.sh_x, p.sh_oe, p.sh_e, knob(al, K_LANE_MIN_PAIRS, 0),
                              // (slices of the list taken at run time, 192 pairs at a time, from counters zeroed with the run's others: [12] for

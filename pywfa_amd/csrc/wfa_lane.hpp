@@ -50,16 +50,27 @@
 // has to be for any shape.  A lock-step pass per unit of score for one cell (and none at all at the other scores) is replaced by a
 // walk along diagonal 0, bounded by lim of slot j0 = min(tlen, plen): a run that stops is the next cell of the chain, the one behind
 // it starts a base further on, and if that lies beyond lim the clamp of compute-next would have made it (and with it every later
-// cell) NULL.  A pair with tlen == plen whose cell i reaches tlen is finished in the refill, as termination would have found at
-// step i X: score -(i X) g, status 0, the lane idle again.
+// cell) NULL.  A pair with tlen == plen whose cell i reaches tlen is finished before the loop, as termination would have found at
+// step i X: score -(i X) g, status 0 (shapes with three or more cells: in the refill, the lane idle again; WINCH: below).
+// The Hamming finish (WINCH).  Take a pair with tlen == plen and m differences along diagonal 0.  The alignment that stays on diagonal 0
+// costs m X.  Any other alignment leaves diagonal 0 and returns to it (it starts and ends there), so it holds at least one insertion run
+// and one deletion run and costs at least 2 OE.  Hence m X <= 2 OE implies that the optimum is exactly m X (at equality both give the
+// same score, and this form returns scores only): every such pair, m <= MH = floor(2 OE / X), is finished when its window is walked —
+// score -(m X) g, status 0 — and takes no lane, no LDS load and no place in a refill.  The stage would have kept that score itself:
+// with tlen == plen its bound is Bmin / g = 2 OE + 2 E (H - 1) >= 2 OE, so no such pair was ever handed on.  Pairs with tlen != plen
+// are left alone whatever their diagonal 0 looks like (a single-gap shortcut needs a proof of its own).
 // Where the walk runs (WINCH, shapes of up to two cells: every built-in shape): once per 64-pair metadata window, at the head of the
 // refill that may first draw from it — all 64 lanes hold a pair then, a refill only the 8 - 12 that take one, and the chain does not
 // depend on when a lane takes the pair.  Diagonal 0 needs no funnel shift (the text words follow the pattern words, both
 // word-aligned), so lane i XORs its pair's words straight from global memory, 32 bases per round, and the cells are the positions of
-// the first NCH differences below lim, then lim itself.  Cell 0 travels in the ten spare bits of the window's `ln`, cell 1 waits in LDS
-// (`wch`, int16 by window position: 256 B, so that a wave's LDS at 150 bp stays within five 1 280-byte granules) for the refill that
-// takes the pair, which only writes the state down.  Pairs the stage cannot take are not walked.  Shapes with more cells keep the
-// walk inside the refill, on the words in LDS, all taking lanes together.
+// the first NCH differences below lim, then lim itself.  A pair of equal lengths goes on counting differences behind its cells, up to
+// MH + 1 or the end of the sequence — the loop is wave-wide and runs to the longest chain of 64 pairs anyway.  What the pass does not
+// finish moves to the front of the window, in order (a forward ds_permute: no memory), and the refill draws from the wn0 - wp0 pairs
+// left in window 0 and the wn1 of window 1; a window with nothing left gives way to the next one at once, so a window, a slice or a
+// whole list that finishes costs its chains and nothing else.  Cell 0 travels in the ten spare bits of the window's `ln`, cell 1 waits
+// in LDS (`wch`, int16 by position in the compacted window: 256 B, so that a wave's LDS at 150 bp stays within five 1 280-byte granules)
+// for the refill that takes the pair, which only writes the state down.  Pairs the stage cannot take are not walked (and stay in the
+// window: they are handed on).  Shapes with more cells keep the walk inside the refill, on the words in LDS, all taking lanes together.
 // The state at step K, before its extension, is then written down as the loop would hold it:
 //   Mh[d] = M at score K - 1 - d = chain[(K - 1 - d) / X] in slot j0 where that score is a multiple of X in [0, K), else NULL;
 //   Ih[0] = I_K = M_0 + 1 in slot j0 + 1, Dh[0] = D_K = M_0 in slot j0 - 1 (a slot outside the band: nothing, as the NULL
@@ -197,6 +208,12 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
   // more than two cells keep the chain inside the refill.
   constexpr bool WINCH = ENTRY && NCH <= 2;
   constexpr uint32_t LNM = WINCH ? 0x3ffu : 0xffffu;   // a length in its half of ln (WINCH: the bits above hold cell 0)
+  // the Hamming finish (header comment): an equal-length pair with at most MH = floor(2 OE / X) differences scores -(m X) g.  MH X <= 2 OE,
+  // far inside an int for every shape (2/4/1: 4 x 2, 1/2/1: 4 x 1, 6/8/3: 2 x 6).  Bit 8 of refill_arg off: only the pairs the chain itself
+  // ends (fewer than NCH differences, NCH - 1 <= MH), those the refill used to finish
+  constexpr int MH = (2 * OE) / X;
+  static_assert(NCH - 1 <= MH && MH * X <= 2 * OE, "the chain's own end cells lie within the Hamming bound");
+  const int mh = (refill_arg & 0x100) ? MH : NCH - 1;
   constexpr int NREC = LaneFull<OE, E>::NREC;     // FULL: steps a pair can take here (bounds the walk)
   extern __shared__ uint32_t lds[];               // [4 guard words][64 slots x slot_words][4 guard words]
   const int slot_words = slot_words_seq;
@@ -232,16 +249,20 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
   // differences of pattern and text on diagonal 0 below L = min(plen, tlen), straight from global memory (text words follow the
   // pattern words, both word-aligned: an XOR word by word, 32 bases per round).  Cell c is the c-th difference; the first cell
   // without one is L itself (the run reaches lim: a live cell there), the cell behind it stays NULL.  Pairs the stage cannot
-  // take and lanes beyond the slice load nothing; no load leaves the first ceil(L / 16) words of either sequence.  Returns ln
-  // with cell 0 in its spare bits (a pair that is not walked: ln as it is — the refill does not read its cells).
-  auto window_chain = [&](uint32_t wb, uint32_t pw, uint32_t ln) -> uint32_t {
+  // take and lanes beyond the slice load nothing; no load leaves the first ceil(L / 16) words of either sequence.  Finishes the
+  // pairs of the Hamming rule, moves the others to the front of the window (pid, pw and ln, with cell 0 in the spare bits of ln
+  // — a pair that is not walked: ln as it is, the refill does not read its cells — and cell 1 in wch) and returns their number.
+  auto window_chain = [&](uint32_t wb, uint32_t& pid, uint32_t& pw, uint32_t& ln) -> uint32_t {
     WFA_LANE_MARK("entry_begin");
     WFA_LANE_COUNT(8);
     const int pl = (int)(ln & 0xffffu), tl = (int)(ln >> 16);
     const int nwp = (pl + 15) >> 4, ntot = nwp + ((tl + 15) >> 4), ak = tl - pl, L = min(pl, tl);
-    const bool elig = (unsigned long long)wb + lane < end &&
-                      !(ln == 0xffffffffu || ntot + 1 > slot_words_seq || ak < 1 - 2 * H || ak > 2 * H - 1);
+    const bool inw = (unsigned long long)wb + lane < end;
+    const bool elig = inw && !(ln == 0xffffffffu || ntot + 1 > slot_words_seq || ak < 1 - 2 * H || ak > 2 * H - 1);
     bool act = elig;
+    // the Hamming finish: a pair of equal lengths goes on counting differences behind its cells, up to mh + 1 or to L
+    bool hact = elig && ak == 0, hend = false;
+    int hm = 0;
     const uint32_t* pp = a.words + pw;             // pattern word 2 r of round r; the text word lies nwp words on
     int ch[NCH];
 #pragma unroll
@@ -250,18 +271,23 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
     const int imax = slot_words_seq >> 1;          // (a slot holds no longer sequence: the loop ends there whatever the data say)
     int base = 0;                                  // first base of this round's words
 #pragma nounroll
-    for (int i = 0; i < imax && __any(act); i += 2) {
+    for (int i = 0; i < imax && __any(act || hact); i += 2) {
       WFA_LANE_MARK("entryround_begin");
       WFA_LANE_COUNT(9);
       uint32_t x0 = 0u, x1 = 0u;
-      if (act && base < L) x0 = pp[0] ^ pp[nwp];
-      if (act && base + 16 < L) x1 = pp[1] ^ pp[nwp + 1];
-      // one bit per differing base (bit 2 b of its word)
-      unsigned long long d = (unsigned long long)((x0 | (x0 >> 1)) & 0x55555555u) | ((unsigned long long)((x1 | (x1 >> 1)) & 0x55555555u) << 32);
+      const bool on = act || hact;
+      if (on && base < L) x0 = pp[0] ^ pp[nwp];
+      if (on && base + 16 < L) x1 = pp[1] ^ pp[nwp + 1];
+      // one bit per differing base (bit 2 b of its word), the bases at and beyond L left out
+      const int nb = L - base;
+      const uint32_t k0 = nb >= 16 ? 0x55555555u : nb > 0 ? (0x55555555u >> (32 - 2 * nb)) : 0u;
+      const uint32_t k1 = nb >= 32 ? 0x55555555u : nb > 16 ? (0x55555555u >> (64 - 2 * nb)) : 0u;
+      unsigned long long d = (unsigned long long)((x0 | (x0 >> 1)) & k0) | ((unsigned long long)((x1 | (x1 >> 1)) & k1) << 32);
+      hm += hact ? (int)__builtin_popcountll(d) : 0;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
-        const int pos = d ? base + ((int)__builtin_ctzll(d) >> 1) : 0x7fff;
-        const bool hit = act && pos < L;
+        const int pos = base + ((int)__builtin_ctzll(d | (1ull << 63)) >> 1);
+        const bool hit = act && d != 0ull;
 #pragma unroll
         for (int k = 0; k < NCH; ++k) ch[k] = (hit && ci == k) ? pos : ch[k];
         ci += hit ? 1 : 0;
@@ -269,17 +295,41 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
         d &= d - 1ull;
       }
       // no further difference below L in these words, and they reach L: the run ends at L, and with it the chain
-      const bool endc = act && base + 32 >= L;
+      const bool last = base + 32 >= L;
+      const bool endc = act && last;
 #pragma unroll
       for (int k = 0; k < NCH; ++k) ch[k] = (endc && ci == k) ? L : ch[k];
       act = act && !endc;
+      hend = hend || (hact && last);               // every base of the pair has been compared
+      hact = hact && !last && hm <= mh;
       pp += 2; base += 32;
       WFA_LANE_MARK("entryround_end");
     }
-    if constexpr (NCH == 2) wch[64 + lane] = (short)ch[1];   // (always window 1: a window moves down with its cells)
-    WFA_LANE_MARK("entry_end");
+    // finished here and now: such a pair takes no lane and no place in a refill
+    const bool fin = hend && hm <= mh;
+    if (fin) {
+      a.score[pid] = -__mul24(hm * X, a.g);
+      a.status[pid] = 0;
+    }
     const uint32_t c0 = (uint32_t)ch[0];           // 0 .. 512 in a pair that was walked
-    return elig ? (ln | ((c0 & 0x3fu) << 10) | ((c0 >> 6) << 26)) : ln;
+    uint32_t lnc = elig ? (ln | ((c0 & 0x3fu) << 10) | ((c0 >> 6) << 26)) : ln;
+    // the pairs that are left move to the front of the window, in order (a forward permute: every lane sends its pair to its rank
+    // among those left, a finished pair and a lane beyond the slice behind them — a permutation of the 64 lanes); cell 1 goes to the
+    // same position in LDS
+    const bool keep = inw && !fin;
+    const unsigned long long km = __ballot(keep);
+    int dst = lane;
+    if (__ballot(fin)) {
+      const int rk = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u));
+      dst = keep ? rk : (int)__builtin_popcountll(km) + lane - rk;
+      pid = (uint32_t)__builtin_amdgcn_ds_permute(dst << 2, (int)pid);
+      pw = (uint32_t)__builtin_amdgcn_ds_permute(dst << 2, (int)pw);
+      lnc = (uint32_t)__builtin_amdgcn_ds_permute(dst << 2, (int)lnc);
+    }
+    if constexpr (NCH == 2) wch[64 + dst] = (short)ch[1];   // (always window 1: a window moves down with its cells)
+    ln = lnc;
+    WFA_LANE_MARK("entry_end");
+    return (uint32_t)__builtin_popcountll(km);
   };
   auto load_window = [&](uint32_t wb, uint32_t& pid, uint32_t& pw, uint32_t& ln) {
     const unsigned long long idx = (unsigned long long)wb + lane;
@@ -291,13 +341,19 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
       ln = (m.plen > WFA_FAST_MAX_LEN || m.tlen > WFA_FAST_MAX_LEN) ? 0xffffffffu : ((uint32_t)m.plen | ((uint32_t)m.tlen << 16));
     }
   };
-  uint32_t wbase = begin, next_i = begin;
+  uint32_t wbase = begin, next_i = begin;          // (!WINCH: the windows are 64 consecutive pairs of the list each)
   // WINCH: the chains of a window are followed in ONE place, at the head of the refill that may first draw from it (the chain loop
-  // exists once, and its registers are not live across the prologue).  wneed: windows whose chains are due (2: a new slice, both
-  // windows); wmeta: the metadata of window 1 has been requested already (when window 1 moved down: its latency hides behind the
-  // steps up to the next refill)
-  uint32_t wneed = 2u;
+  // exists once, and its registers are not live across the prologue).  A window then holds only the pairs the chain did not finish,
+  // moved to its front: window 0 the positions wp0 .. wn0 - 1 (wp0: taken already), window 1 its first wn1; wnext: where in the list
+  // the next window starts (>= end: the slice has no more); wmeta: the metadata of window 1 has been requested already (when window 1
+  // moved down: its latency hides behind the steps up to the next refill)
+  uint32_t wn0 = 0u, wp0 = 0u, wn1 = 0u, wnext = begin;
   bool wmeta = false;
+  // every pair of the slice has been taken or finished
+  auto slice_done = [&]() -> bool {
+    if constexpr (WINCH) return wp0 >= wn0 && wn1 == 0u && wnext >= end;
+    else return next_i >= end;
+  };
   if constexpr (!WINCH) {
     load_window(wbase, pid0, pw0, ln0);
     load_window(wbase + 64u, pid1, pw1, ln1);
@@ -354,41 +410,46 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
     WFA_LANE_MARK("looptop_begin");   // (analysis builds: what precedes the first of these is the prologue)
     // =================== take pairs ===================
     const int nidle = __builtin_popcountll(idle);
-    if (!exhausted && next_i >= end && (nidle >= refill_min || idle == ~0ull)) {
+    if (!exhausted && slice_done() && (nidle >= refill_min || idle == ~0ull)) {
       // this slice is used up: the next chunk of the list, if any (its metadata windows replace the old ones: every pair of the old
       // slice has been taken)
       if (grab(begin, end)) {
         wbase = begin; next_i = begin;
-        if constexpr (WINCH) { wneed = 2u; wmeta = false; }
+        if constexpr (WINCH) { wn0 = wp0 = wn1 = 0u; wnext = begin; wmeta = false; }
         else { load_window(wbase, pid0, pw0, ln0); load_window(wbase + 64u, pid1, pw1, ln1); }
       } else exhausted = true;
     }
-    if (next_i < end && (nidle >= refill_min || idle == ~0ull)) {
+    if (!slice_done() && (nidle >= refill_min || idle == ~0ull)) {
       WFA_LANE_MARK("refill_begin");
       WFA_LANE_COUNT(1);
       if constexpr (WINCH) {
-        // the windows that are due, always through window 1: with two (a new slice) the first moves down before the second is fetched
+        // the windows that are due, always through window 1, until both hold pairs or the slice has no more: a window that has nothing
+        // left (the first of a new slice, or one whose pairs all finished in the chain) gives way to the next one at once.  (Only the
+        // window requested at the last move-down comes with its metadata on the way; the one behind a window that finished entirely is
+        // loaded here and waited for: one exposed global round trip per such window, on every window of all-substitution data)
 #pragma nounroll
-        for (; wneed; --wneed) {
-          const uint32_t wb = wneed == 2u ? wbase : wbase + 64u;
-          if (!wmeta) load_window(wb, pid1, pw1, ln1);
+        while (wn1 == 0u && wnext < end) {
+          if (!wmeta) load_window(wnext, pid1, pw1, ln1);
           wmeta = false;
-          ln1 = window_chain(wb, pw1, ln1);
-          if (wneed == 2u) {
+          wn1 = window_chain(wnext, pid1, pw1, ln1);
+          wnext = (end - wnext > 64u) ? wnext + 64u : end;
+          if (wp0 >= wn0) {
             pid0 = pid1; pw0 = pw1; ln0 = ln1;
             if constexpr (NCH == 2) wch[lane] = wch[64 + lane];
+            wn0 = wn1; wp0 = 0u; wn1 = 0u;
           }
         }
       }
       const bool is_idle = __builtin_amdgcn_inverse_ballot_w64(idle);
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-      const uint32_t navail = end - next_i;
+      const uint32_t navail = WINCH ? (wn0 - wp0) + wn1 : end - next_i;   // (WINCH: 0 if the rest of the slice finished in its chains)
       const bool take = is_idle && rank < navail;
-      const uint32_t src = next_i + rank - wbase;   // 0 .. 126: position in the two windows
-      const int sl = (int)(src & 63u);
+      // position in the two windows.  !WINCH: 0 .. 126, window 1 from 64 on; WINCH: window 0 up to wn0, window 1 behind it
+      const uint32_t src = WINCH ? wp0 + rank : next_i + rank - wbase;
+      const bool hi_w = src >= (WINCH ? wn0 : 64u);
+      const int sl = (int)((WINCH ? (hi_w ? src - wn0 : src) : src) & 63u);
       const uint32_t a_pid = __shfl(pid0, sl, 64), a_pw = __shfl(pw0, sl, 64), a_ln = __shfl(ln0, sl, 64);
       const uint32_t b_pid = __shfl(pid1, sl, 64), b_pw = __shfl(pw1, sl, 64), b_ln = __shfl(ln1, sl, 64);
-      const bool hi_w = src >= 64u;
       const uint32_t n_pid = hi_w ? b_pid : a_pid, n_pw = hi_w ? b_pw : a_pw, n_ln = hi_w ? b_ln : a_ln;
       const int pl = (int)(n_ln & LNM), tl = (int)((n_ln >> 16) & LNM);
       const int nwp = (pl + 15) >> 4, ntot = nwp + ((tl + 15) >> 4);
@@ -464,7 +525,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
         }
       }
       const uint32_t ntake = min((uint32_t)nidle, navail);
-      next_i += ntake;
+      if constexpr (WINCH) wp0 += ntake; else next_i += ntake;
       idle &= ~tmask;
       if constexpr (!WINCH) {
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the words are in LDS
@@ -475,17 +536,17 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
         const bool go = take && !bad;
         if (__any(go)) {
           int ch[NCH];
-          int fin_i = -1;
+          bool fin = false;   // (!WINCH only) the pair ends inside its chain: finished here, the lane idle again
           if constexpr (WINCH) {
-            // the chain was followed before this refill: cell 0 comes with the pair's ln, cell 1 waits at its window position
+            // the chain was followed before this refill: cell 0 comes with the pair's ln, cell 1 waits at its window position.  (A pair
+            // whose chain reached its end never comes here: the window pass finished it.)
             ch[0] = (int)(((n_ln >> 10) & 0x3fu) | (((n_ln >> 26) & 0xfu) << 6));
-            if constexpr (NCH == 2) ch[1] = (int)wch[src];
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) fin_i = (ak == 0 && ch[i] == tl) ? i : fin_i;   // the end cell: the pair's score is i * X
+            if constexpr (NCH == 2) ch[1] = (int)wch[(hi_w ? 64 : 0) + sl];
           } else {
             // (more cells than the windows hold: all taking lanes follow diagonal 0 together, here)
             WFA_LANE_MARK("entry_begin");
             WFA_LANE_COUNT(8);
+            int fin_i = -1;
 #pragma unroll
             for (int i = 0; i < NCH; ++i) ch[i] = WFA_LANE_NULL16;
             const int etb = go ? tb : pbase;             // (other lanes read along, inside their own slot, and advance by 0)
@@ -517,17 +578,17 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
               WFA_LANE_MARK("entryround_end");
             } while (__any(act));
             WFA_LANE_MARK("entry_end");
+            fin = go && fin_i >= 0;
+            if (fin) {
+              a.score[mypid] = -__mul24(fin_i * X, a.g);
+              a.status[mypid] = 0;
+            }
+            idle |= __ballot(fin);                     // finished before the loop: the lane is idle again
           }
-          const bool fin = go && fin_i >= 0;
-          if (fin) {
-            a.score[mypid] = -__mul24(fin_i * X, a.g);
-            a.status[mypid] = 0;
-          }
-          idle |= __ballot(fin);                       // finished before the loop: the lane is idle again
           if (go) {
             // one value in slot `slot` of a ring register set, NULL elsewhere (a slot outside the band, or a finished pair: all NULL)
             auto place = [&](uint32_t (&dst)[NR], int slot, int val) {
-              const int rr = fin ? -1 : (slot >> 1);   // (-1 and NR match no register)
+              const int rr = (!WINCH && fin) ? -1 : (slot >> 1);   // (-1 and NR match no register)
               const uint32_t w = (slot & 1) ? (((uint32_t)WFA_LANE_NULL16 & 0xffffu) | ((uint32_t)val << 16))
                                             : ((WFA_LANE_NULL2 & 0xffff0000u) | ((uint32_t)val & 0xffffu));
 #pragma unroll
@@ -547,9 +608,9 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
             for (int r = 0; r < NR; ++r) {
               const uint32_t gap = pk_max(Ih[0][r], Dh[0][r]);
               cur[r] = pk_clamp((K % X == 0) ? pk_max(gap, mm[r]) : gap, lim[r]);   // (not extended: the loop does that)
-              if (fin) lim[r] = WFA_LANE_NULL2;
+              if constexpr (!WINCH) { if (fin) lim[r] = WFA_LANE_NULL2; }
             }
-            if (fin) { deadline = NEVER; jt = 0; tend = 0xffffu; }
+            if constexpr (!WINCH) { if (fin) { deadline = NEVER; jt = 0; tend = 0xffffu; } }
           }
         }
       }
@@ -557,15 +618,20 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the words are in LDS
         asm volatile("" ::: "memory");
       }
-      if (next_i - wbase >= 64u) {           // window 0 used up: window 1 moves down (WINCH: with its chains), the one after is requested
-        pid0 = pid1; pw0 = pw1; ln0 = ln1; wbase += 64u;
-        if constexpr (WINCH) {
+      if constexpr (WINCH) {
+        if (wp0 >= wn0) {                    // window 0 used up: window 1 moves down with its chains, less what was taken from it
+          pid0 = pid1; pw0 = pw1; ln0 = ln1;
           if constexpr (NCH == 2) wch[lane] = wch[64 + lane];
-          wneed = 1u; wmeta = true;
+          wp0 -= wn0; wn0 = wn1; wn1 = 0u;
+          if (wnext < end) { load_window(wnext, pid1, pw1, ln1); wmeta = true; }   // the one after is requested
         }
+      } else if (next_i - wbase >= 64u) {    // window 0 used up: window 1 moves down, the one after is requested
+        pid0 = pid1; pw0 = pw1; ln0 = ln1; wbase += 64u;
         load_window(wbase + 64u, pid1, pw1, ln1);
       }
       WFA_LANE_MARK("refill_end");
+      // (the rest of the slice finished in its chains and no lane holds a pair: nothing to step, on to the next slice or the end)
+      if (WINCH && ntake == 0u && idle == ~0ull) continue;
     } else if (idle == ~0ull && exhausted) {
       rej_flush();
       break;                                 // nothing left
@@ -738,7 +804,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
         }
         idle |= bd;
         WFA_LANE_MARK("bd_end");
-        if (idle == ~0ull && next_i >= end && exhausted) { rej_flush(); break; }   // (a flush behind the loop costs 40 registers)
+        if (idle == ~0ull && slice_done() && exhausted) { rej_flush(); break; }   // (a flush behind the loop costs 40 registers)
       }
     }
 
@@ -911,6 +977,10 @@ inline int lane_slot_words(int max_len) {
   const int w = 2 * ((max_len + 15) >> 4) + 1;
   return w | 1;
 }
+
+// the kernel's refill_arg: the refill threshold in bits 0-7, bit 8: the Hamming finish of the window pass (plain score-only form; off:
+// the window pass finishes only the pairs whose chain reaches their end, as the refill used to)
+inline int lane_refill_arg(int refill_min, bool winfin) { return (refill_min & 0xff) | (winfin ? 0x100 : 0); }
 
 // shape_idx: index in WFA_SEG_SHAPES (seg_shape()); per_cu: slices of the work list (waves) per CU
 // records of origin codes per lane of the FULL form for a penalty shape (LaneFull<OE, E>::NREC)
