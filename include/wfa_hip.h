@@ -710,6 +710,69 @@ int wfa_hip_pair_host(int64_t nreads, int64_t nhits, const int32_t* i, const int
                       const int32_t* mate2 /* nullable */, int32_t* rows /* nreads x 8, nullable */, uint8_t* flags /* nhits, nullable */,
                       int32_t* pair_rows /* nfrag x 12 */, uint8_t* pair_flags /* nhits, nullable */, char* msg, size_t msg_cap);
 
+/* ---- rescue: the window in which a lost mate must lie, from its anchored partner ---------------------------- */
+
+/*
+ * The pairing joins the hits it is given.  A fragment whose one mate was never aligned at its true place (a repeat masked by the seed
+ * index, too many errors for the seeds, an overflowed seed list) has no proper pairing, however well the other mate is anchored.  The
+ * anchored mate, the orientation rule and the insert bounds say where the lost mate must lie; this rule turns them into a window list
+ * in the shape wfa_hip_batch_create_windows takes, made where the records lie: 32 bytes per window cross PCIe.  Integers only, 64-bit
+ * arithmetic, nothing depends on scheduling.  The terms of "placement" and "pairing" keep their meaning.
+ *
+ * Inputs: a placer's hits; the parameters of wfa_hip_placer_run_pairs (min_score, full_gap, min_insert, max_insert, unpaired, nfrag,
+ * mate1, mate2); len(r), the length of read r in a pattern set; tlen(j), the length of text j in a text set; pad >= 0, min_len >= 0
+ * and anchor_mapq in 0 .. 60.
+ * RESCUED FRAGMENT.  Fragment f whose pair row under those parameters has proper == 0 && pairings == 0 && overflow == 0.
+ * ANCHOR.  For a rescued fragment take mate m = 1, then m = 2, and let a be the single-end primary of mate m (se(m).hit).  Mate m is
+ * an anchor iff a >= 0, a's interval is non-empty (te_a > ts_a) and se(m).mapq >= anchor_mapq.  The other mate o then gets ONE window
+ * on text j_a, on the strand 1 - reverse_a:
+ *     anchor forward (reverse_a == 0; o must be the reverse hit, whose end lies in [ts_a + min_insert, ts_a + max_insert]):
+ *         lo = ts_a + min_insert - len(o) - pad,    hi = ts_a + max_insert + pad
+ *     anchor reverse (reverse_a == 1; o is the forward hit, whose start lies in [te_a - max_insert, te_a - min_insert]):
+ *         lo = te_a - max_insert - pad,             hi = te_a - min_insert + len(o) + pad
+ *     in both cases clipped, lo = max(lo, 0), hi = min(hi, tlen(j_a)); the window is made iff hi - lo >= max(min_len, 1) and is
+ *     dropped otherwise.
+ * A fragment yields 0, 1 or 2 windows: both mates may anchor, for instance when the two single-end primaries lie on different texts.
+ * LIST ORDER.  Ascending fragment number; within a fragment the window anchored by mate 1 comes before the one anchored by mate 2.
+ * PER WINDOW WFA_HIP_RESCUE_COLS int32 (32 bytes): i (the read to align, mate o), j, text_start (= lo), text_len (= hi - lo), reverse,
+ * fragment, anchor (the anchor's hit number) and a spare that is 0.  The first five are exactly the arrays
+ * wfa_hip_batch_create_windows takes; the pattern window is the whole read.
+ * WHAT RESCUE DOES NOT DO.  It does not rescue a fragment that has proper pairings but lost to its single-end primaries.  It uses no
+ * anchor other than the primary.  It does not dedupe against hits the other mate already has: the same-locus rule of the next pair run
+ * absorbs those.
+ *
+ * wfa_hip_placer_rescue runs group, place and pair on the device exactly as wfa_hip_placer_run_pairs does, downloads none of their
+ * outputs, and makes the list there (csrc/wfa_place.hpp, k_rescue.hip: a thread per (fragment, anchoring mate) decides, an exclusive
+ * scan of the 0 / 1 decisions gives every window its position, a second pass stores the rows; no atomics, the order comes from the
+ * scan: two calls give identical bytes).  *count receives the full number of windows and rows the first min(*count, cap) of them
+ * (cap x WFA_HIP_RESCUE_COLS int32, row-major; rows behind them are not touched; cap = 0 with rows = NULL is the counting call), the
+ * convention of wfa_hip_pileup_sites.  Only the count and those rows are downloaded.  wfa_hip_placer_kernel_ms then covers the rescue
+ * kernels too.  A placer keeps, on the host, the hits at which the j it was given rises above all before: the last is the greatest j, and
+ * the first with j >= the number of texts is the first hit of the list outside the text set, the one wfa_hip_rescue_host names.
+ * WFA_HIP_EINVAL, nothing launched, nothing written (wfa_hip_last_error names the first offending position and its values): what
+ * wfa_hip_placer_run_pairs refuses (pair_rows aside); a NULL set or a set of another aligner; a pattern set with fewer sequences than
+ * the placer has reads; a hit whose j is not below the number of texts; a negative pad, min_len or cap; anchor_mapq outside 0 .. 60;
+ * a NULL count; NULL rows with cap > 0.
+ */
+#define WFA_HIP_RESCUE_COLS 8   /* i, j, text_start, text_len, reverse, fragment, anchor, spare */
+int  wfa_hip_placer_rescue(wfa_hip_placer_t* placer, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int32_t min_score,
+                           int32_t full_gap, int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag,
+                           const int32_t* mate1 /* nullable */, const int32_t* mate2 /* nullable */, int32_t pad, int32_t min_len,
+                           int32_t anchor_mapq, int64_t cap, int64_t* count, int32_t* rows /* cap x 8, nullable */);
+
+/* Host only, needs no GPU: the rule above in plain C++ over the arrays wfa_hip_pair_host takes, read_len[nreads] and
+ * text_len[ntexts]: what wfa_hip_placer_add_hits + wfa_hip_placer_rescue give.  *count receives the full number of windows,
+ * min(*count, cap) rows are written.  Returns WFA_HIP_OK, or WFA_HIP_EINVAL (nothing written; msg as for wfa_hip_place_host) for
+ * whatever wfa_hip_pair_host refuses (pair_rows aside); a negative pad, min_len, cap, ntexts, read_len or text_len; anchor_mapq
+ * outside 0 .. 60; a hit whose j >= ntexts; a missing pointer (read_len with nreads > 0, text_len with ntexts > 0, count, rows with
+ * cap > 0). */
+int wfa_hip_rescue_host(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse, const int32_t* score,
+                        const int32_t* status, const int32_t* text_start, const int32_t* text_end, int32_t min_score, int32_t full_gap,
+                        int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1 /* nullable */,
+                        const int32_t* mate2 /* nullable */, const int32_t* read_len, int64_t ntexts, const int32_t* text_len,
+                        int32_t pad, int32_t min_len, int32_t anchor_mapq, int64_t cap, int64_t* count,
+                        int32_t* rows /* cap x 8, nullable */, char* msg, size_t msg_cap);
+
 /* ---- seed finder: an exact-match k-mer index over a text set, candidate windows for every read ------------ */
 
 /*

@@ -75,6 +75,7 @@ SYMBOLS = [
     "wfa_hip_placer_create", "wfa_hip_placer_add", "wfa_hip_placer_add_hits", "wfa_hip_placer_run", "wfa_hip_placer_count",
     "wfa_hip_placer_clear", "wfa_hip_placer_kernel_ms", "wfa_hip_placer_destroy", "wfa_hip_place_host",
     "wfa_hip_placer_run_pairs", "wfa_hip_pair_host",
+    "wfa_hip_placer_rescue", "wfa_hip_rescue_host",
 ]
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
@@ -92,6 +93,8 @@ PLACE_NOT_ELIGIBLE, PLACE_OTHER_LOCUS, PLACE_SAME_LOCUS, PLACE_PRIMARY = 0, 1, 2
 PAIR_COLS = 12
 PAIR_COLUMNS = ("hit1", "hit2", "proper", "score", "second", "mapq", "mapq1", "mapq2", "insert", "pairings", "ties", "overflow")
 PAIR_MAX_PAIRINGS = 65536
+RESCUE_COLS = 8
+RESCUE_COLUMNS = ("i", "j", "text_start", "text_len", "reverse", "fragment", "anchor", "spare")
 INT32_MIN = -2**31
 SEED_MAX_N, SEED_MAX_HITS = 16, 4096
 SEED_KEYS = ("j", "reverse", "text_start", "text_len", "hits")   # the int32 arrays of a seed query, and overflow (uint8)
@@ -229,6 +232,9 @@ def lib():
     L.wfa_hip_place_host.argtypes = [i64, i64] + [vp] * 7 + [i32, i32, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
     L.wfa_hip_placer_run_pairs.argtypes = [vp] + [i32] * 5 + [i64] + [vp] * 6
     L.wfa_hip_pair_host.argtypes = [i64, i64] + [vp] * 7 + [i32] * 5 + [i64] + [vp] * 6 + [ctypes.c_char_p, ctypes.c_size_t]
+    L.wfa_hip_placer_rescue.argtypes = [vp] * 3 + [i32] * 5 + [i64, vp, vp] + [i32] * 3 + [i64, ctypes.POINTER(i64), vp]
+    L.wfa_hip_rescue_host.argtypes = ([i64, i64] + [vp] * 7 + [i32] * 5 + [i64, vp, vp, vp, i64, vp] + [i32] * 3 +
+                                      [i64, ctypes.POINTER(i64), vp, ctypes.c_char_p, ctypes.c_size_t])
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
@@ -647,6 +653,37 @@ def pair_host(nreads, i, j, reverse, score, status, text_start, text_end, mates,
     return rows, flags, pair_rows, pair_flags
 
 
+def rescue_host(nreads, i, j, reverse, score, status, text_start, text_end, mates, read_len, text_len, min_score=INT32_MIN, full_gap=1,
+                min_insert=0, max_insert=1000, unpaired=0, pad=16, min_len=0, anchor_mapq=0, cap=None):
+    """wfa_hip_rescue_host (host only): ``(count, rows)`` of the rescue rule over a list of hits in hit-number order, the reads' lengths
+    ``read_len`` (one per read) and the texts' lengths ``text_len`` — rows int32 of shape (min(count, cap), 8) in the columns
+    RESCUE_COLUMNS, every window when ``cap`` is None (a counting call first); what ``Placer.add_hits`` + ``Placer.rescue`` give."""
+    a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
+    nfrag, m1, m2 = _mate_arrays(mates)
+    nreads = int(nreads)
+    read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+    text_len = np.ascontiguousarray(text_len, dtype=np.int32)
+    if read_len.shape != (max(nreads, 0),):
+        raise ValueError(f"read_len: one value per read ({nreads})")
+    if text_len.ndim != 1:
+        raise ValueError("text_len: one value per text")
+    msg = ctypes.create_string_buffer(256)
+    p = lambda v: _ptr(v) if v is not None and v.size else None   # noqa: E731
+    mp = lambda v: None if v is None else _ptr(v)                 # noqa: E731  (an empty mate array is still "given")
+    args = (nreads, n, p(a["i"]), p(a["j"]), p(a["reverse"]), p(a["score"]), p(a["status"]), p(a["text_start"]), p(a["text_end"]),
+            int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired), nfrag, mp(m1), mp(m2), p(read_len),
+            text_len.shape[0], p(text_len), int(pad), int(min_len), int(anchor_mapq))
+    count = ctypes.c_int64(0)
+    if cap is None:
+        if lib().wfa_hip_rescue_host(*args, 0, ctypes.byref(count), None, msg, 256) != OK:
+            raise ValueError(f"wfa_hip_rescue_host: {msg.value.decode()}")
+        cap = count.value
+    rows = np.zeros((max(int(cap), 0), RESCUE_COLS), np.int32)
+    if lib().wfa_hip_rescue_host(*args, int(cap), ctypes.byref(count), p(rows), msg, 256) != OK:
+        raise ValueError(f"wfa_hip_rescue_host: {msg.value.decode()}")
+    return count.value, rows[:min(count.value, rows.shape[0])]
+
+
 def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16, pad=16, max_hits=2048, w=None):
     """wfa_hip_seeds_host (host only): the row ``SeedIndex.query`` holds for ONE read (bytes) against the texts (a list of bytes, or a
     blob dict(seqs=, off=, len=) made once for many reads): dict of int32[n] ``j`` / ``reverse`` / ``text_start`` / ``text_len`` /
@@ -1020,6 +1057,25 @@ class Placer:
         if rc != OK:
             self.aligner._raise(rc, "wfa_hip_placer_run_pairs")
         return r, fl, pr, pf
+
+    def rescue(self, patterns, texts, mates, min_score=INT32_MIN, full_gap=1, min_insert=0, max_insert=1000, unpaired=0, pad=16, min_len=0,
+               anchor_mapq=0, cap=None):
+        """wfa_hip_placer_rescue over every hit added so far: ``(count, rows)`` of the windows in which the lost mates of the
+        fragments without a proper pairing must lie — rows int32 of shape (min(count, cap), 8) in the columns RESCUE_COLUMNS, list
+        order; ``cap`` None: room for every window (two per fragment).  ``patterns`` / ``texts``: the SeqSets of the reads and of the
+        texts the hits lie on; ``mates`` as for ``run_pairs``."""
+        nfrag, m1, m2 = _mate_arrays(mates)
+        if cap is None:
+            cap = 2 * max(nfrag, 0)
+        rows = np.zeros((max(int(cap), 0), RESCUE_COLS), np.int32)
+        count = ctypes.c_int64(0)
+        rc = lib().wfa_hip_placer_rescue(self._h, patterns._h, texts._h, int(min_score), int(full_gap), int(min_insert), int(max_insert),
+                                         int(unpaired), nfrag, None if m1 is None else _ptr(m1), None if m2 is None else _ptr(m2),
+                                         int(pad), int(min_len), int(anchor_mapq), int(cap), ctypes.byref(count),
+                                         _ptr(rows) if rows.size else None)
+        if rc != OK:
+            self.aligner._raise(rc, "wfa_hip_placer_rescue")
+        return count.value, rows[:min(count.value, rows.shape[0])]
 
     def kernel_ms(self):
         ms = ctypes.c_float(0)

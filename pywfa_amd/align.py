@@ -1286,7 +1286,7 @@ class WavefrontAligner:
 
     def place_pairs(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
                     text_len=None, reverse=None, mates=None, min_insert=0, max_insert=1000, unpaired=None, min_score=None,
-                    full_gap=None):
+                    full_gap=None, rescue=False, rescue_pad=16, rescue_mapq=0):
         """``place_windows`` for paired-end reads (same arguments, same checks; either scope): the listed windows are aligned, every
         read is placed on its own, and then the hits of the two mates of every fragment are joined on the GPU.  The rule is that of
         include/wfa_hip.h ("pairing"), integers only.  ``mates``: an (F, 2) integer array of indices into ``patterns``, fragment f
@@ -1306,7 +1306,24 @@ class WavefrontAligner:
         given, 3 that hit, 2 at its locus, 1 eligible elsewhere, 0 not eligible; the single-end flag for a read in no proper
         fragment) and ``pairs``, a dict of int32 arrays of length F: hit1, hit2 (list positions, -1 without one), proper, score,
         second (-2**31 when not proper or without a runner-up), mapq, mapq1, mapq2, insert, pairings (proper pairings), ties,
-        overflow.  48 bytes per fragment more come back than from ``place_windows``, and a byte per hit."""
+        overflow.  48 bytes per fragment more come back than from ``place_windows``, and a byte per hit.
+
+        ``rescue=True`` (scope full and span ends-free only): MATE RESCUE.  A fragment without any proper pairing — a mate whose true
+        place was never listed, because its seeds were masked, too few or overflowed — gets, from every mate whose single-end primary
+        has a mapq of at least ``rescue_mapq`` (0 .. 60), one more window for the OTHER mate: on the anchor's text, on the opposite
+        strand, as wide as the orientation rule and ``min_insert`` .. ``max_insert`` allow plus ``rescue_pad`` bases on either side
+        (include/wfa_hip.h, "rescue").  The window list is made on the GPU where the hits lie (32 bytes per window come back), the
+        windows are aligned under this aligner's configuration with ``text_begin_free`` and ``text_end_free`` set to
+        F = (max_insert - min_insert) + 2 * rescue_pad for these alignments only (both are restored afterwards, also when the run
+        raises; windows clipped below F bases by an end of their text are not made), their hits are added behind the n0 listed
+        ones, and all hits are paired once.  A fragment that has proper pairings but lost to its single-end primaries is not
+        rescued, only the primary anchors, and a rescue window may find a place the other mate already has a hit at: the
+        same-locus rule absorbs it.  The rescue windows are wide, so they run in the general kernels: they cost far more per pair
+        than the listed windows.  ``score``, ``status``, ``flag`` and ``pair_flag`` then cover the n0 listed hits followed by the
+        rescue hits; ``pairs`` gains ``rescued`` (int32: 1 iff the fragment is proper and one of its chosen hits is a rescue hit),
+        and ``rescue`` is added: dict(i=, j=, text_start=, text_len=, reverse=, fragment=, anchor=) of int32 arrays, possibly
+        empty, hit ``n0 + q`` being window ``q`` of it (``anchor``: the hit number of the anchor).  ``rescue=False`` returns exactly
+        the keys above."""
         for name, v in (("min_score", min_score), ("full_gap", full_gap), ("min_insert", min_insert), ("max_insert", max_insert),
                         ("unpaired", unpaired)):
             if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
@@ -1323,6 +1340,25 @@ class WavefrontAligner:
             unpaired = full_gap
         if not 0 <= int(unpaired) < 2**31:
             raise ValueError(f"unpaired = {unpaired} is out of range (at least 0)")
+        if not isinstance(rescue, (bool, np.bool_)):
+            raise ValueError(f"rescue must be True or False, got {rescue!r}")
+        for name, v in (("rescue_pad", rescue_pad), ("rescue_mapq", rescue_mapq)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+        if int(rescue_pad) < 0:
+            raise ValueError(f"rescue_pad = {rescue_pad} is out of range (at least 0)")
+        if not 0 <= int(rescue_mapq) <= 60:
+            raise ValueError(f"rescue_mapq = {rescue_mapq} is out of range (0 .. 60)")
+        # the free ends of the rescue alignments: a bound on the insert range and the pad together, which only a rescue has
+        free = (int(max_insert) - int(min_insert)) + 2 * int(rescue_pad)
+        if rescue and free >= 2**31:
+            raise ValueError(f"max_insert - min_insert = {int(max_insert) - int(min_insert)} with rescue_pad = {rescue_pad} is out of range "
+                             "for a rescue ((max_insert - min_insert) + 2 * rescue_pad below 2^31)")
+        if rescue and self._cfg.scope != 1:
+            raise ValueError("rescue needs scope='full': under scope score a hit's interval is its whole window, and a rescue window "
+                             "is as wide as the insert range")
+        if rescue and self._cfg.span != 1:
+            raise ValueError("rescue needs span='ends-free': the rescued mate lies somewhere inside its window")
         patterns, texts, arrays, wlen = self._window_lists(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
         nreads = len(patterns)
         if mates is None:
@@ -1357,13 +1393,37 @@ class WavefrontAligner:
                 placer.add(rb, ii[lo:hi], jj[lo:hi], None if ts is None else ts[lo:hi], None if rev is None else rev[lo:hi])
 
             out = self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, each=add)
-            rows, flags, pair_rows, pair_flags = placer.run_pairs(
-                mates, _native.INT32_MIN if min_score is None else int(min_score), int(full_gap), int(min_insert), int(max_insert),
-                int(unpaired))
+            how = (_native.INT32_MIN if min_score is None else int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired))
+            n0 = ii.shape[0]
+            if rescue:
+                _, found = placer.rescue(sets[0], sets[-1], mates, *how, pad=int(rescue_pad), min_len=free, anchor_mapq=int(rescue_mapq))
+                ri, rj, rts, rtl, rrev, rfrag, ranchor = (np.ascontiguousarray(found[:, c]) for c in range(7))
+                if found.shape[0]:
+                    rrev8 = rrev.astype(np.uint8)
+                    lens = [sets[0].length[ri].astype(np.int64), rtl.astype(np.int64)]
+
+                    def add_rescued(rb, lo, hi, score, status):
+                        placer.add(rb, ri[lo:hi], rj[lo:hi], rts[lo:hi], rrev8[lo:hi])
+
+                    before = (self.text_begin_free, self.text_end_free)
+                    try:
+                        self.text_begin_free = free
+                        self.text_end_free = free
+                        more = self._run_windows(sets[0], sets[-1] if texts is not None else None, (ri, rj, None, None, rts, rtl, rrev8),
+                                                 lens, each=add_rescued)
+                    finally:
+                        self.text_begin_free, self.text_end_free = before
+                    out["score"] = np.concatenate([out["score"], more["score"]])
+                    out["status"] = np.concatenate([out["status"], more["status"]])
+            rows, flags, pair_rows, pair_flags = placer.run_pairs(mates, *how)
             out["flag"] = flags
             out["reads"] = {name: np.ascontiguousarray(rows[:, c]) for c, name in enumerate(_native.PLACE_COLUMNS)}
             out["pair_flag"] = pair_flags
             out["pairs"] = {name: np.ascontiguousarray(pair_rows[:, c]) for c, name in enumerate(_native.PAIR_COLUMNS)}
+            if rescue:
+                pairs = out["pairs"]
+                pairs["rescued"] = ((pairs["proper"] == 1) & ((pairs["hit1"] >= n0) | (pairs["hit2"] >= n0))).astype(np.int32)
+                out["rescue"] = dict(i=ri, j=rj, text_start=rts, text_len=rtl, reverse=rrev, fragment=rfrag, anchor=ranchor)
             return out
         finally:
             if placer is not None:

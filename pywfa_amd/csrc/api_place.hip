@@ -14,7 +14,11 @@ int place_check_run(int32_t full_gap, char* msg, size_t cap);
 // host_pair.cpp: the check shared with wfa_hip_pair_host
 int pair_check(int64_t nreads, int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
                const int32_t* mate2, char* msg, size_t cap);
+// host_rescue.cpp: the check shared with wfa_hip_rescue_host
+int rescue_check(int32_t pad, int32_t min_len, int32_t anchor_mapq, int64_t cap, const int64_t* count, const int32_t* rows, char* msg,
+                 size_t msg_cap);
 }
+static_assert(WFA_RESCUE_COLS == WFA_HIP_RESCUE_COLS, "rescue: the kernels and the ABI");
 static_assert(WFA_PAIR_COLS == WFA_HIP_PAIR_COLS && WFA_PAIR_MAX_PAIRINGS == WFA_HIP_PAIR_MAX_PAIRINGS, "pairing: the kernels and the ABI");
 
 struct wfa_hip_placer {
@@ -27,6 +31,9 @@ struct wfa_hip_placer {
   uint32_t* d_order = nullptr;         // [order_cap] the grouped hit numbers
   int64_t order_cap = 0;
   int64_t grouped = -1;                // the number of hits d_count / d_order were made for (-1: none)
+  // (hit number, j) of every hit whose j exceeds that of all hits before it: the last one is the greatest text index among the hits,
+  // the first one with j >= n the first hit that a set of n texts does not hold (rescue checks it against its text set)
+  std::vector<std::pair<int64_t, int32_t>> j_rise;
   hipEvent_t ev[2] = {nullptr, nullptr};
   float last_ms = 0.f;
 };
@@ -83,7 +90,7 @@ extern "C" int64_t wfa_hip_placer_count(const wfa_hip_placer_t* p) { return p ? 
 
 extern "C" int wfa_hip_placer_clear(wfa_hip_placer_t* p) {
   if (!p) return WFA_HIP_EINVAL;
-  p->nhits = 0; p->grouped = -1;
+  p->nhits = 0; p->grouped = -1; p->j_rise.clear();
   return WFA_HIP_OK;
 }
 
@@ -109,6 +116,13 @@ static int placer_reserve(wfa_hip_placer* p, int64_t more) {
   pool_release(al, p->d_hits);
   p->d_hits = d_new; p->cap = want;
   return WFA_HIP_OK;
+}
+
+// the rises of j among the n hits about to be appended (the caller's host array)
+static void placer_note_texts(wfa_hip_placer* p, int64_t n, const int32_t* j) {
+  int32_t top = p->j_rise.empty() ? -1 : p->j_rise.back().second;
+  for (int64_t q = 0; q < n; ++q)
+    if (j[q] > top) { top = j[q]; p->j_rise.emplace_back(p->nhits + q, top); }
 }
 
 extern "C" int wfa_hip_placer_add(wfa_hip_placer_t* p, wfa_hip_batch_t* b, const int32_t* i, const int32_t* j, const int32_t* t_start,
@@ -155,6 +169,7 @@ extern "C" int wfa_hip_placer_add(wfa_hip_placer_t* p, wfa_hip_batch_t* b, const
     if (lrc != 0) { al->err = "placement: record kernel launch failed"; return WFA_HIP_EDEVICE; }
     HIP_TRY(al, e);
   }
+  placer_note_texts(p, n, j);
   p->nhits += n; p->grouped = -1;
   return WFA_HIP_OK;
 }
@@ -178,6 +193,7 @@ extern "C" int wfa_hip_placer_add_hits(wfa_hip_placer_t* p, int64_t n, const int
   }
   HIP_TRY(al, hipMemcpyAsync(p->d_hits + p->nhits, rec.data(), (size_t)n * sizeof(wfa::PlaceHit), hipMemcpyHostToDevice, al->stream));
   HIP_TRY(al, hipStreamSynchronize(al->stream));
+  placer_note_texts(p, n, j);
   p->nhits += n; p->grouped = -1;
   return WFA_HIP_OK;
 }
@@ -226,7 +242,54 @@ extern "C" int wfa_hip_placer_run(wfa_hip_placer_t* p, int32_t min_score, int32_
   return WFA_HIP_OK;
 }
 
-// group (when the hits changed), place, then the pair kernel: the single-end rows and flags stay on the device for the join
+// What wfa_hip_placer_run_pairs and wfa_hip_placer_rescue share, after their checks: the blocks of one pair run in `sc`, the mates
+// uploaded, ev[0] recorded, then group (when the hits changed), place and the pair kernel enqueued; the single-end rows and flags
+// stay on the device for the join.  `*launch_rc`: nonzero when a launch failed (the later ones are then left out).  The caller records
+// ev[1] and stops its timer either way, as run_pairs always did, then handles a failed launch, synchronises and reads the elapsed time.
+static int placer_enqueue_pairs(wfa_hip_placer* p, CrossScratch& sc, wfa::PairArgs& a, int32_t min_score, int32_t full_gap,
+                                int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
+                                const int32_t* mate2, bool want_pair_flags, int* launch_rc) {
+  wfa_hip_aligner* al = p->al;
+  *launch_rc = 0;
+  if (p->nhits > p->order_cap) {
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
+    const int rc = placer_alloc(al, (void**)&p->d_order, (size_t)p->cap * sizeof(uint32_t), "4 bytes per hit");
+    if (rc != WFA_HIP_OK) return rc;
+    p->order_cap = p->cap;
+  }
+  memset(&a, 0, sizeof(a));
+  wfa::PlaceArgs& s = a.place;
+  s.hits = p->d_hits; s.nhits = p->nhits; s.nreads = p->nreads; s.count = p->d_count; s.bsum = p->d_bsum; s.order = p->d_order;
+  s.min_score = min_score; s.full_gap = full_gap;
+  a.min_insert = min_insert; a.max_insert = max_insert; a.unpaired = unpaired; a.nfrag = nfrag;
+  if (sc.alloc(&s.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
+  if (sc.alloc(&s.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  if (want_pair_flags && sc.alloc(&a.pair_flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  if (nfrag > 0 && sc.alloc(&a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS)) return WFA_HIP_EDEVICE;
+  if (mate1 && nfrag > 0) {
+    int32_t *d_m1 = nullptr, *d_m2 = nullptr;
+    if (sc.alloc(&d_m1, (size_t)nfrag) || sc.alloc(&d_m2, (size_t)nfrag)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipMemcpyAsync(d_m1, mate1, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    HIP_TRY(al, hipMemcpyAsync(d_m2, mate2, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    a.mate1 = d_m1; a.mate2 = d_m2;
+  }
+  HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
+  int lrc = 0;
+  if (p->grouped != p->nhits) {
+    p->grouped = -1;
+    HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
+    lrc = wfa::launch_place_group(s, al->stream);
+  }
+  if (lrc == 0) lrc = wfa::launch_place(s, al->cu_count, al->stream);
+  // reads in no fragment, and fragments that are not proper, keep their single-end flags
+  if (lrc == 0 && a.pair_flags && p->nhits > 0)
+    HIP_TRY(al, hipMemcpyAsync(a.pair_flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToDevice, al->stream));
+  if (lrc == 0) lrc = wfa::launch_pair(a, al->cu_count, al->stream);
+  *launch_rc = lrc;
+  return WFA_HIP_OK;
+}
+
 extern "C" int wfa_hip_placer_run_pairs(wfa_hip_placer_t* p, int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert,
                                         int32_t unpaired, int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int32_t* rows,
                                         uint8_t* flags, int32_t* pair_rows, uint8_t* pair_flags) {
@@ -238,45 +301,14 @@ extern "C" int wfa_hip_placer_run_pairs(wfa_hip_placer_t* p, int32_t min_score, 
   if (nfrag > 0 && !pair_rows) { al->err = "pairing: null pair_rows"; return WFA_HIP_EINVAL; }
   if (p->nreads == 0) return WFA_HIP_OK;   // (no read: no fragment, no hit)
   HIP_TRY(al, hipSetDevice(al->device));
-  if (p->nhits > p->order_cap) {
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
-    const int rc = placer_alloc(al, (void**)&p->d_order, (size_t)p->cap * sizeof(uint32_t), "4 bytes per hit");
-    if (rc != WFA_HIP_OK) return rc;
-    p->order_cap = p->cap;
-  }
   CrossScratch sc{al};
   wfa::PairArgs a;
-  memset(&a, 0, sizeof(a));
-  wfa::PlaceArgs& s = a.place;
-  s.hits = p->d_hits; s.nhits = p->nhits; s.nreads = p->nreads; s.count = p->d_count; s.bsum = p->d_bsum; s.order = p->d_order;
-  s.min_score = min_score; s.full_gap = full_gap;
-  a.min_insert = min_insert; a.max_insert = max_insert; a.unpaired = unpaired; a.nfrag = nfrag;
-  if (sc.alloc(&s.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
-  if (sc.alloc(&s.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
-  if (pair_flags && sc.alloc(&a.pair_flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
-  if (nfrag > 0 && sc.alloc(&a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS)) return WFA_HIP_EDEVICE;
-  if (mate1 && nfrag > 0) {
-    int32_t *d_m1 = nullptr, *d_m2 = nullptr;
-    if (sc.alloc(&d_m1, (size_t)nfrag) || sc.alloc(&d_m2, (size_t)nfrag)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_m1, mate1, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(d_m2, mate2, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    a.mate1 = d_m1; a.mate2 = d_m2;
-  }
   {
     ReduceTimer timer(al, "place pairs", p->nhits, "hits");
-    HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
     int lrc = 0;
-    if (p->grouped != p->nhits) {
-      p->grouped = -1;
-      HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
-      lrc = wfa::launch_place_group(s, al->stream);
-    }
-    if (lrc == 0) lrc = wfa::launch_place(s, al->cu_count, al->stream);
-    // reads in no fragment, and fragments that are not proper, keep their single-end flags
-    if (lrc == 0 && a.pair_flags && p->nhits > 0)
-      HIP_TRY(al, hipMemcpyAsync(a.pair_flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToDevice, al->stream));
-    if (lrc == 0) lrc = wfa::launch_pair(a, al->cu_count, al->stream);
+    const int rc = placer_enqueue_pairs(p, sc, a, min_score, full_gap, min_insert, max_insert, unpaired, nfrag, mate1, mate2, pair_flags != nullptr, &lrc);
+    if (rc != WFA_HIP_OK) return rc;
+    const wfa::PlaceArgs& s = a.place;
     HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
     timer.stop();
     if (lrc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "pairing: kernel launch failed"; return WFA_HIP_EDEVICE; }
@@ -287,6 +319,67 @@ extern "C" int wfa_hip_placer_run_pairs(wfa_hip_placer_t* p, int32_t min_score, 
     if (pair_flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(pair_flags, a.pair_flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
     HIP_TRY(al, hipStreamSynchronize(al->stream));
     HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
+  }
+  return WFA_HIP_OK;
+}
+
+// group, place and pair as wfa_hip_placer_run_pairs enqueues them, none of their outputs downloaded; then decide, scan and emit
+// (k_rescue.hip).  4 bytes (the count) and 32 per returned window come back.
+extern "C" int wfa_hip_placer_rescue(wfa_hip_placer_t* p, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int32_t min_score,
+                                     int32_t full_gap, int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag,
+                                     const int32_t* mate1, const int32_t* mate2, int32_t pad, int32_t min_len, int32_t anchor_mapq,
+                                     int64_t cap, int64_t* count, int32_t* rows) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  char buf[240];
+  if (wfa::place_check_run(full_gap, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (wfa::pair_check(p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (wfa::rescue_check(pad, min_len, anchor_mapq, cap, count, rows, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (!patterns || !texts) { al->err = "rescue: a missing sequence set"; return WFA_HIP_EINVAL; }
+  if (patterns->al != al || texts->al != al) { al->err = "rescue: sequence set of another aligner"; return WFA_HIP_EINVAL; }
+  if (patterns->n < p->nreads) {
+    snprintf(buf, sizeof(buf), "rescue: the pattern set has %lld sequences, the placer %lld reads", (long long)patterns->n, (long long)p->nreads);
+    al->err = buf; return WFA_HIP_EINVAL;
+  }
+  if (!p->j_rise.empty() && (int64_t)p->j_rise.back().second >= texts->n) {
+    size_t k = 0;   // (the rises ascend in j: the first one outside the set is the first such hit of the list)
+    while ((int64_t)p->j_rise[k].second < texts->n) ++k;
+    snprintf(buf, sizeof(buf), "rescue: text index out of range at position %lld of the hit list: j = %d over %lld texts",
+             (long long)p->j_rise[k].first, (int)p->j_rise[k].second, (long long)texts->n);
+    al->err = buf; return WFA_HIP_EINVAL;
+  }
+  if (p->nreads == 0 || nfrag == 0) { *count = 0; return WFA_HIP_OK; }   // (no fragment: no window)
+  HIP_TRY(al, hipSetDevice(al->device));
+  CrossScratch sc{al};
+  wfa::RescueArgs r;
+  memset(&r, 0, sizeof(r));
+  const int64_t nslots = 2 * nfrag, out_cap = std::min<int64_t>(cap, nslots);
+  r.read_len = patterns->d_len; r.npatterns = patterns->n; r.text_len = texts->d_len; r.ntexts = texts->n;
+  r.pad = pad; r.min_len = min_len; r.anchor_mapq = anchor_mapq; r.cap = out_cap;
+  if (sc.alloc(&r.slot, (size_t)nslots + 1)) return WFA_HIP_EDEVICE;
+  if (sc.alloc(&r.bsum, (size_t)((nslots + 1 + WFA_PLACE_SCAN_CHUNK - 1) / WFA_PLACE_SCAN_CHUNK))) return WFA_HIP_EDEVICE;
+  if (out_cap > 0 && sc.alloc(&r.out, (size_t)out_cap * WFA_RESCUE_COLS)) return WFA_HIP_EDEVICE;
+  {
+    ReduceTimer timer(al, "rescue", p->nhits, "hits");
+    int pair_rc = 0, lrc = 0;
+    const int rc = placer_enqueue_pairs(p, sc, r.pair, min_score, full_gap, min_insert, max_insert, unpaired, nfrag, mate1, mate2, false, &pair_rc);
+    if (rc != WFA_HIP_OK) return rc;
+    if (pair_rc == 0) lrc = wfa::launch_rescue(r, al->cu_count, al->stream);
+    HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
+    timer.stop();
+    if (pair_rc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "pairing: kernel launch failed"; return WFA_HIP_EDEVICE; }
+    p->grouped = p->nhits;
+    if (lrc != 0) { (void)hipStreamSynchronize(al->stream); al->err = "rescue: kernel launch failed"; return WFA_HIP_EDEVICE; }
+    uint32_t n = 0;
+    HIP_TRY(al, hipMemcpyAsync(&n, r.slot + nslots, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
+    const int64_t take = std::min<int64_t>((int64_t)n, out_cap);
+    if (take > 0) {
+      HIP_TRY(al, hipMemcpyAsync(rows, r.out, (size_t)take * WFA_RESCUE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+      HIP_TRY(al, hipStreamSynchronize(al->stream));
+    }
+    *count = (int64_t)n;
   }
   return WFA_HIP_OK;
 }

@@ -72,16 +72,17 @@ __global__ void __launch_bounds__(256) wfa_place_hits_kernel(PlaceArgs a) {
   }
 }
 
+// ---- the scan of n counters, in place (launch_place_scan: the group step's nreads + 1 counters, the rescue's 2 nfrag + 1) ----
+
 // chunk sums of the counters
-__global__ void __launch_bounds__(256) wfa_place_scan_reduce_kernel(PlaceArgs a) {
+__global__ void __launch_bounds__(256) wfa_place_scan_reduce_kernel(const uint32_t* count, int64_t n, uint32_t* bsum) {
   __shared__ uint32_t s_red[4];
-  const int64_t n = a.nreads + 1;
   const int64_t base = (int64_t)blockIdx.x * WFA_PLACE_SCAN_CHUNK + (int64_t)threadIdx.x * 16;
   uint32_t sum = 0;
 #pragma unroll
-  for (int u = 0; u < 16; ++u) sum += base + u < n ? a.count[base + u] : 0u;
+  for (int u = 0; u < 16; ++u) sum += base + u < n ? count[base + u] : 0u;
   sum = seed_block_sum(sum, s_red);
-  if (threadIdx.x == 0) a.bsum[blockIdx.x] = sum;
+  if (threadIdx.x == 0) bsum[blockIdx.x] = sum;
 }
 
 // the chunk sums to their exclusive prefix, in place: one workgroup, 256 sums per round
@@ -98,21 +99,20 @@ __global__ void __launch_bounds__(256) wfa_place_scan_top_kernel(uint32_t* bsum,
   }
 }
 
-// every counter to the inclusive prefix over all of them: the END of its read's group
-__global__ void __launch_bounds__(256) wfa_place_scan_apply_kernel(PlaceArgs a) {
+// every counter to the inclusive prefix over all of them (the group step: the END of its read's group)
+__global__ void __launch_bounds__(256) wfa_place_scan_apply_kernel(uint32_t* count, int64_t n, const uint32_t* bsum) {
   __shared__ uint32_t s_red[4];
-  const int64_t n = a.nreads + 1;
   const int64_t base = (int64_t)blockIdx.x * WFA_PLACE_SCAN_CHUNK + (int64_t)threadIdx.x * 16;
   uint32_t c[16];
   uint32_t sum = 0;
 #pragma unroll
-  for (int u = 0; u < 16; ++u) { c[u] = base + u < n ? a.count[base + u] : 0u; sum += c[u]; }
+  for (int u = 0; u < 16; ++u) { c[u] = base + u < n ? count[base + u] : 0u; sum += c[u]; }
   uint32_t total;
-  uint32_t run = a.bsum[blockIdx.x] + seed_block_exclusive(sum, s_red, &total);
+  uint32_t run = bsum[blockIdx.x] + seed_block_exclusive(sum, s_red, &total);
 #pragma unroll
   for (int u = 0; u < 16; ++u) {
     run += c[u];
-    if (base + u < n) a.count[base + u] = run;
+    if (base + u < n) count[base + u] = run;
   }
 }
 
@@ -360,12 +360,19 @@ int launch_place_record(const PlaceRecordArgs& a, bool full, int cu_count, hipSt
 
 static unsigned hits_grid(int64_t nhits) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((nhits + 255) / 256, 1 << 16)); }
 
+// count[0 .. n) to its inclusive prefix sums in three passes; bsum holds ceil(n / WFA_PLACE_SCAN_CHUNK) words
+int launch_place_scan(uint32_t* count, int64_t n, uint32_t* bsum, hipStream_t stream) {
+  if (n <= 0) return 0;
+  const unsigned chunks = (unsigned)((n + WFA_PLACE_SCAN_CHUNK - 1) / WFA_PLACE_SCAN_CHUNK);
+  hipLaunchKernelGGL(wfa_place_scan_reduce_kernel, dim3(chunks), dim3(256), 0, stream, count, n, bsum);
+  hipLaunchKernelGGL(wfa_place_scan_top_kernel, dim3(1), dim3(256), 0, stream, bsum, chunks);
+  hipLaunchKernelGGL(wfa_place_scan_apply_kernel, dim3(chunks), dim3(256), 0, stream, count, n, bsum);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_place_group(const PlaceArgs& a, hipStream_t stream) {
-  const unsigned chunks = (unsigned)((a.nreads + 1 + WFA_PLACE_SCAN_CHUNK - 1) / WFA_PLACE_SCAN_CHUNK);
   if (a.nhits > 0) hipLaunchKernelGGL(wfa_place_hits_kernel<false>, dim3(hits_grid(a.nhits)), dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(wfa_place_scan_reduce_kernel, dim3(chunks), dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(wfa_place_scan_top_kernel, dim3(1), dim3(256), 0, stream, a.bsum, chunks);
-  hipLaunchKernelGGL(wfa_place_scan_apply_kernel, dim3(chunks), dim3(256), 0, stream, a);
+  if (launch_place_scan(a.count, a.nreads + 1, a.bsum, stream) != 0) return -1;
   if (a.nhits > 0) hipLaunchKernelGGL(wfa_place_hits_kernel<true>, dim3(hits_grid(a.nhits)), dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -37,6 +37,14 @@
 //            wave reductions for second, ties and the number of runner-up candidates.  Then the lanes stride each mate's group
 //            once for pair_flags (which the host entry has filled with the single-end flags beforehand, a device copy: reads in
 //            no fragment and fragments that are not proper keep them); lanes 0 .. 11 store the row.  No LDS, no atomics.
+//   rescue   (include/wfa_hip.h, "rescue"; wfa_hip_rescue_host in host_rescue.cpp is its plain statement; k_rescue.hip.)  After pair,
+//            so it reads the pair rows, the single-end rows and the records in HBM, and the length arrays of the two sequence sets.
+//            2 nfrag slots, slot s = (fragment s / 2, anchoring mate s % 2), a thread per slot, grid-stride.  decide: the pair row's
+//            proper / pairings / overflow, the anchoring mate's single-end hit and mapq, the anchor's record (two 16-byte loads),
+//            len(o) and tlen(j_a); it writes 0 / 1 at counter s + 1 (counter 0 is 0).  The scan of the group step
+//            (launch_place_scan) over the 2 nfrag + 1 counters makes counter s the EXCLUSIVE prefix of slot s and the last one the
+//            number of windows.  emit recomputes the window and stores its 32-byte row at counter s as two 16-byte stores, when
+//            that is below the caller's capacity.  The order is the scan's, never arrival order; no atomics, no LDS but the scan's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,6 +84,7 @@ struct PlaceArgs {
 };
 
 int launch_place_record(const PlaceRecordArgs& a, bool full, int cu_count, hipStream_t stream);
+int launch_place_scan(uint32_t* count, int64_t n, uint32_t* bsum, hipStream_t stream);   // count[0 .. n) to its inclusive prefix, in place
 int launch_place_group(const PlaceArgs& a, hipStream_t stream);   // count, scan, scatter (a.count zeroed by the caller)
 int launch_place(const PlaceArgs& a, int cu_count, hipStream_t stream);
 
@@ -93,5 +102,20 @@ struct PairArgs {
 };
 
 int launch_pair(const PairArgs& a, int cu_count, hipStream_t stream);
+
+#define WFA_RESCUE_COLS 8
+
+struct RescueArgs {
+  PairArgs pair;             // after launch_pair: the records, the single-end rows and the pair rows
+  const int32_t* read_len; int64_t npatterns;   // the pattern set's lengths (npatterns >= place.nreads: the host has checked)
+  const int32_t* text_len; int64_t ntexts;      // the text set's lengths (every j < ntexts: the host has checked)
+  int32_t pad, min_len, anchor_mapq;
+  uint32_t* slot;            // [2 nfrag + 1]: slot[0] = 0 and slot[s + 1] = 0 / 1 after decide; exclusive prefixes (slot[2 nfrag]: the count) after the scan
+  uint32_t* bsum;            // [ceil((2 nfrag + 1) / WFA_PLACE_SCAN_CHUNK)]
+  int64_t cap;               // rows of `out`
+  int32_t* out;              // [cap x WFA_RESCUE_COLS], 16-byte aligned
+};
+
+int launch_rescue(const RescueArgs& a, int cu_count, hipStream_t stream);   // decide, scan, emit
 
 }  // namespace wfa
