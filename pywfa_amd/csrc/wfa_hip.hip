@@ -1815,6 +1815,8 @@ struct CascadePlan {
 
 // which band windows (in chunks of 64 diagonals) the banded stages run, in order
 static void plan_band_windows(const wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePlan& p) {
+  // (gap-affine-2p, reads below 32 000 bases only: its explicit entries are always 6 x int16 — wfa_band.hpp, sat16 — and wfa_slim.hpp
+  // keeps doubled offsets in int16, so the slim kernel itself hands on every pair longer than 16 000 bases)
   if (!p.lin && !p.tiny && wfa::band_supported(b->dcfg, b->ncomp) && (b->ncomp != 5 || b->max_len < 32000) && knob(al, K_NO_BAND, 0) == 0) {
     if (b->ncomp == 5) {
       // gap-affine-2p wavefronts are wide (C4: 99 % need more than 108 diagonals, 2.6 % more than 172)
@@ -1864,7 +1866,7 @@ static void plan_band_stages(wfa_hip_aligner* al, const wfa_hip_batch* b, Cascad
     if (i > 0 || p.use_fast || p.use_laneh || p.use_segh || p.use_segfull) grid = std::min<long long>(grid, (long long)al->cu_count * knob(al, K_BAND_LEFTOVER_WAVES_PER_CU, 64));
     if (i > 0 && p.want_pipe_tail) grid = std::min<long long>(grid, (long long)al->cu_count * 8);   // (one launch's leftovers at a time: a few hundred pairs; the history slices are tens of megabytes each)
     if (full) {
-      const bool h16 = b->max_len < 32000;
+      const bool h16 = b->max_len < 32000;   // (wfa_band.hpp's range, sat16: the inputs of a valid cell never exceed 32 767 — 4 x int16 entries; as launch_band_stage's)
       const int rec = ((h16 && b->ncomp != 5) ? 2 : 4) * (p.band_nch[i] == 3 ? 256 : 64 * p.band_nch[i]);  // ints per record (2p: 16-byte entries)
       // steps of an alignment = score / g; sized for scores up to 0.9 x the read length (about 15 % divergence)
       long long records = std::max<long long>(256, (long long)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / wfa::band_gcd(b->dcfg, b->ncomp == 5) + 64);
@@ -1931,6 +1933,8 @@ static void plan_tile_stage(const wfa_hip_aligner* al, const wfa_hip_batch* b, C
   const uint32_t in_n = b->n_packed;
   const wfa::WideArgs& w0 = p.w0;
   const int64_t budget = p.budget;
+  // (wfa_tile_cell.hpp's range: int16 rows with NULL = -32768 — a dead value gains at most 1 per step and must stay negative: reads
+  // of up to 32 000 bases here, and in the kernel every pair of up to 32 000 bases for up to 32 000 steps, then handed on)
   const bool tile32 = b->max_len > WFA_TILE_MAX_LEN;
   const int tile_cb = tile32 ? 4 : 2;
   const int tile32_knob = knob(al, K_TILE32, -1);
@@ -2206,6 +2210,8 @@ static void plan_cascade(wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePla
               (b->dcfg.heuristic == WFA_HEUR_NONE || p.wide_adapt) && b->dcfg.match == 0 &&
               b->max_len > 64 && 2 * (int64_t)b->max_len <= 0x3fffff00ll && b->dcfg.e1 >= 1 && b->dcfg.x >= 1 && knob(al, K_NO_WIDE, 0) == 0;
   // reads beyond 16 kb (plen + tlen > 32 000 does not fit int16 offsets): the workspace-row form with int32 rows (round 3)
+  // (wfa_wide.hpp's range: int16 rows with NULL = -16384 — a negative value is dead, a NULL gains at most 1 per step and must stay
+  // negative: the kernel hands a pair on when plen + tlen > 32 000 and after 16 000 steps; this host test is the stricter one)
   p.wide32 = 2 * (int64_t)b->max_len > 32000;
   const bool any_pre = p.use_fast || p.use_laneh || p.use_segh || p.use_segfull || p.n_stages > 0 || p.wide_ok;
   // the general kernel's geometry is fixed first so that one workspace allocation serves every stage
@@ -2257,6 +2263,8 @@ static BilevelPlan plan_bilevel(wfa_hip_aligner* al, const wfa_hip_batch* b, boo
   //   workspace: [ring / base-history slices][window queues, leaves, per-pair words, counters][slices of the depth-first kernel]
   memset(&bp.la, 0, sizeof(bp.la));
   bp.bilevel = full && knob(al, K_BILEVEL, 1) != 0;
+  // (wfa_bilevel.hpp's range: int16 rings stored clamped to [-16384, 32767] — a negative offset is dead, none of a read of up to
+  // 32 000 bases reaches the upper clamp)
   bp.bl_i16 = b->max_len <= 32000 && knob(al, K_BILEVEL_I32, 0) == 0;
   size_t bl_bytes = 0;
   if (bp.bilevel) {
@@ -2765,7 +2773,7 @@ static int run_band_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t str
     ba.dbg = b->d_counters + CNT_DEBUG;
     (void)hipMemsetAsync(b->d_counters + CNT_DEBUG, 0, CNT_DEBUG_WORDS * sizeof(uint32_t), stream);
   }
-  ba.h16 = (b->max_len < 32000) ? 1 : 0;
+  ba.h16 = (b->max_len < 32000) ? 1 : 0;   // (wfa_band.hpp's range, sat16: the inputs of a valid cell never exceed 32 767; the same test sizes the records in plan_band_stages)
   fill_ends_free(ba, b->dcfg, true);
   ba.hist = (i > 0 && p.later_off) ? al->ws + p.later_off / 4 : al->ws; ba.hist_stride = p.band_stride[i];
   const bool split = full && c.in_count == nullptr && b->max_len > knob(al, K_BAND_SPLIT_MIN, 100) && knob(al, K_BAND_NO_SPLIT, 0) == 0;
