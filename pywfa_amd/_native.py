@@ -49,34 +49,108 @@ class NativeError(RuntimeError):
 
 _lib = None
 
-# every symbol include/wfa_hip.h declares (tests/test_abi.py checks the library exports them all)
-SYMBOLS = [
-    "wfa_hip_abi_version", "wfa_hip_device_count", "wfa_hip_global_error", "wfa_hip_config_default",
-    "wfa_hip_config_validate", "wfa_hip_create", "wfa_hip_destroy", "wfa_hip_set_config",
-    "wfa_hip_get_config", "wfa_hip_last_error", "wfa_hip_align_batch", "wfa_hip_batch_create",
-    "wfa_hip_batch_destroy", "wfa_hip_batch_run", "wfa_hip_batch_sync", "wfa_hip_batch_results",
-    "wfa_hip_batch_last_kernel_ms", "wfa_hip_batch_algorithmic_bytes", "wfa_hip_batch_fallback_pairs",
-    "wfa_hip_batch_rle_counts", "wfa_hip_batch_rle_runs",
-    "wfa_hip_plan_shards", "wfa_hip_plan_host_threads", "wfa_hip_multi_create", "wfa_hip_multi_destroy", "wfa_hip_multi_set_config",
-    "wfa_hip_multi_last_error", "wfa_hip_multi_align_batch", "wfa_hip_pack_2bit", "wfa_hip_batch_extent",
-    "wfa_hip_align_batch_packed2bits", "wfa_hip_batch_create_packed2bits", "wfa_hip_cigar_sprint_pretty",
-    "wfa_hip_batch_extent_packed2bits", "wfa_hip_align_pair", "wfa_hip_upload_info",
-    "wfa_hip_seqset_create", "wfa_hip_seqset_destroy", "wfa_hip_cross_run", "wfa_hip_cross_dense", "wfa_hip_cross_completed",
-    "wfa_hip_cross_kernel_ms", "wfa_hip_cross_destroy", "wfa_hip_plan_cross_bands", "wfa_hip_cross_run_k", "wfa_hip_cross_topk",
-    "wfa_hip_batch_create_indexed", "wfa_hip_batch_create_windows", "wfa_hip_window_2bit",
-    "wfa_hip_batch_summary", "wfa_hip_ops_summary", "wfa_hip_pileup_create", "wfa_hip_pileup_add", "wfa_hip_pileup_read",
-    "wfa_hip_pileup_clear", "wfa_hip_pileup_destroy", "wfa_hip_ops_pileup",
-    "wfa_hip_seed_index_create", "wfa_hip_seed_index_destroy", "wfa_hip_seed_index_query", "wfa_hip_seed_index_stats",
-    "wfa_hip_seeds_host",
-    "wfa_hip_seed_index_chain", "wfa_hip_seed_index_chain_stats", "wfa_hip_chains_host",
-    "wfa_hip_seed_index_create_minimizer", "wfa_hip_seed_index_params", "wfa_hip_minimizers_host", "wfa_hip_seeds_host_minimizer",
-    "wfa_hip_chains_host_minimizer",
-    "wfa_hip_pileup_calls", "wfa_hip_pileup_sites", "wfa_hip_calls_host", "wfa_hip_sites_host",
-    "wfa_hip_placer_create", "wfa_hip_placer_add", "wfa_hip_placer_add_hits", "wfa_hip_placer_run", "wfa_hip_placer_count",
-    "wfa_hip_placer_clear", "wfa_hip_placer_kernel_ms", "wfa_hip_placer_destroy", "wfa_hip_place_host",
-    "wfa_hip_placer_run_pairs", "wfa_hip_pair_host",
-    "wfa_hip_placer_rescue", "wfa_hip_rescue_host",
-]
+_int, _i32, _i64, _vp, _str, _size = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
+_cfgp, _intp, _i64p, _floatp = (ctypes.POINTER(t) for t in (Config, ctypes.c_int, ctypes.c_int64, ctypes.c_float))
+_CTYPES = object()   # a restype / argtypes that ``lib()`` leaves as ctypes has it (int; unchecked arguments)
+_ALIGN_BATCH = [_vp, _i64] + [_vp] * 11
+_BATCH_CREATE = [_vp, _i64] + [_vp] * 5
+_INDEX_CREATE = [_vp, _vp, _int, _int, _int]
+_SEEDS_HOST = [_vp, _i32, _i64, _vp, _vp, _vp] + [_int] * 8 + [_vp] * 6 + [_str, _size]
+_CHAINS_HOST = [_vp, _i32, _i64, _vp, _vp, _vp] + [_int] * 11 + [_vp] * 9 + [_str, _size]
+_HITS = [_i64, _i64] + [_vp] * 7   # nreads, the hits and their seven arrays (the host rules)
+
+# every symbol include/wfa_hip.h declares (tests/test_abi.py checks the library exports them all): name -> (restype, argtypes)
+SIGNATURES = {
+    "wfa_hip_abi_version": (_int, _CTYPES),
+    "wfa_hip_device_count": (_int, _CTYPES),
+    "wfa_hip_global_error": (_str, _CTYPES),
+    "wfa_hip_config_default": (_CTYPES, [_cfgp]),
+    "wfa_hip_config_validate": (_CTYPES, [_cfgp, _str, _size]),
+    "wfa_hip_create": (_vp, [_cfgp, _int]),
+    "wfa_hip_destroy": (None, [_vp]),
+    "wfa_hip_set_config": (_CTYPES, [_vp, _cfgp]),
+    "wfa_hip_get_config": (_CTYPES, [_vp, _cfgp]),
+    "wfa_hip_last_error": (_str, [_vp]),
+    "wfa_hip_align_batch": (_CTYPES, _ALIGN_BATCH),
+    "wfa_hip_batch_create": (_vp, _BATCH_CREATE),
+    "wfa_hip_batch_destroy": (None, [_vp]),
+    "wfa_hip_batch_run": (_CTYPES, [_vp, _vp]),
+    "wfa_hip_batch_sync": (_CTYPES, [_vp]),
+    "wfa_hip_batch_results": (_CTYPES, [_vp] * 7),
+    "wfa_hip_batch_last_kernel_ms": (_CTYPES, [_vp, _floatp, _i64p]),
+    "wfa_hip_batch_algorithmic_bytes": (_i64, [_vp]),
+    "wfa_hip_batch_fallback_pairs": (_i64, [_vp]),
+    "wfa_hip_batch_rle_counts": (_i64, [_vp, _vp, _vp]),
+    "wfa_hip_batch_rle_runs": (_CTYPES, [_vp, _vp, _vp]),
+    "wfa_hip_plan_shards": (_CTYPES, [_i64, _vp, _vp, _int, _vp]),
+    "wfa_hip_plan_host_threads": (_CTYPES, [_int, _int, _intp, _intp]),
+    "wfa_hip_multi_create": (_vp, [_cfgp, _vp, _int]),
+    "wfa_hip_multi_destroy": (None, [_vp]),
+    "wfa_hip_multi_set_config": (_CTYPES, [_vp, _cfgp]),
+    "wfa_hip_multi_last_error": (_str, [_vp]),
+    "wfa_hip_multi_align_batch": (_CTYPES, _ALIGN_BATCH),
+    "wfa_hip_pack_2bit": (_CTYPES, [_vp, _i32, _vp, _int]),
+    "wfa_hip_batch_extent": (_i64, [_i64, _vp, _vp, _vp, _vp]),
+    "wfa_hip_align_batch_packed2bits": (_CTYPES, _ALIGN_BATCH),
+    "wfa_hip_batch_create_packed2bits": (_vp, _BATCH_CREATE),
+    "wfa_hip_cigar_sprint_pretty": (_i64, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _i64]),
+    "wfa_hip_batch_extent_packed2bits": (_i64, [_i64, _vp, _vp, _vp, _vp]),
+    "wfa_hip_align_pair": (_CTYPES, [_vp, _str, _i32, _str, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "wfa_hip_upload_info": (_CTYPES, [_vp, _vp, _int]),
+    "wfa_hip_seqset_create": (_vp, [_vp, _i64, _vp, _vp, _vp]),
+    "wfa_hip_seqset_destroy": (None, [_vp]),
+    "wfa_hip_cross_run": (_vp, [_vp, _vp, _vp, _int]),
+    "wfa_hip_cross_dense": (_CTYPES, [_vp, _vp, _vp]),
+    "wfa_hip_cross_completed": (_CTYPES, [_vp, _i64p, _vp, _vp, _vp]),
+    "wfa_hip_cross_kernel_ms": (_CTYPES, [_vp, _floatp, _i64p]),
+    "wfa_hip_cross_destroy": (None, [_vp]),
+    "wfa_hip_plan_cross_bands": (_i64, [_i64, _i64, _int, _i64, _vp, _i64]),
+    "wfa_hip_cross_run_k": (_vp, [_vp, _vp, _vp, _int, _int]),
+    "wfa_hip_cross_topk": (_CTYPES, [_vp, _vp, _vp]),
+    "wfa_hip_batch_create_indexed": (_vp, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "wfa_hip_batch_create_windows": (_vp, [_vp, _vp, _vp, _i64] + [_vp] * 7),
+    "wfa_hip_window_2bit": (_CTYPES, [_vp, _i64, _i32, _int, _vp]),
+    "wfa_hip_batch_summary": (_CTYPES, [_vp, _vp]),
+    "wfa_hip_ops_summary": (_CTYPES, [_vp, _i64, _i32, _i32, _vp]),
+    "wfa_hip_pileup_create": (_vp, [_vp, _vp]),
+    "wfa_hip_pileup_add": (_CTYPES, [_vp, _vp, _vp, _vp, _vp]),
+    "wfa_hip_pileup_read": (_CTYPES, [_vp, _i32, _i64, _i64, _vp]),
+    "wfa_hip_pileup_clear": (_CTYPES, [_vp]),
+    "wfa_hip_pileup_destroy": (None, [_vp]),
+    "wfa_hip_ops_pileup": (_CTYPES, [_vp, _i64, _vp, _i32, _i32, _vp]),
+    "wfa_hip_seed_index_create": (_vp, _INDEX_CREATE),
+    "wfa_hip_seed_index_destroy": (None, [_vp]),
+    "wfa_hip_seed_index_query": (_CTYPES, [_vp, _vp] + [_int] * 5 + [_vp] * 6),
+    "wfa_hip_seed_index_stats": (_CTYPES, [_vp, _i64p, _i64p, _i64p, _floatp, _floatp]),
+    "wfa_hip_seeds_host": (_CTYPES, _SEEDS_HOST),
+    "wfa_hip_seed_index_chain": (_CTYPES, [_vp, _vp] + [_int] * 8 + [_vp] * 9),
+    "wfa_hip_seed_index_chain_stats": (_CTYPES, [_vp, _floatp, _i64p]),
+    "wfa_hip_chains_host": (_CTYPES, _CHAINS_HOST),
+    "wfa_hip_seed_index_create_minimizer": (_vp, _INDEX_CREATE),
+    "wfa_hip_seed_index_params": (_CTYPES, [_vp] + [_intp] * 3),
+    "wfa_hip_minimizers_host": (_CTYPES, [_vp, _i64, _int, _int, _vp, _str, _size]),
+    "wfa_hip_seeds_host_minimizer": (_CTYPES, _SEEDS_HOST),
+    "wfa_hip_chains_host_minimizer": (_CTYPES, _CHAINS_HOST),
+    "wfa_hip_pileup_calls": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _vp]),
+    "wfa_hip_pileup_sites": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i64, _i64p, _vp]),
+    "wfa_hip_calls_host": (_CTYPES, [_vp, _vp, _i64, _i32, _vp]),
+    "wfa_hip_sites_host": (_CTYPES, [_vp, _vp, _i64, _i32, _i64, _i32, _i32, _i64, _i64p, _vp]),
+    "wfa_hip_placer_create": (_vp, [_vp, _i64]),
+    "wfa_hip_placer_add": (_CTYPES, [_vp] * 6),
+    "wfa_hip_placer_add_hits": (_CTYPES, [_vp, _i64] + [_vp] * 7),
+    "wfa_hip_placer_run": (_CTYPES, [_vp, _i32, _i32, _vp, _vp]),
+    "wfa_hip_placer_count": (_i64, [_vp]),
+    "wfa_hip_placer_clear": (_CTYPES, [_vp]),
+    "wfa_hip_placer_kernel_ms": (_CTYPES, [_vp, _floatp]),
+    "wfa_hip_placer_destroy": (None, [_vp]),
+    "wfa_hip_place_host": (_CTYPES, _HITS + [_i32, _i32, _vp, _vp, _str, _size]),
+    "wfa_hip_placer_run_pairs": (_CTYPES, [_vp] + [_i32] * 5 + [_i64] + [_vp] * 6),
+    "wfa_hip_pair_host": (_CTYPES, _HITS + [_i32] * 5 + [_i64] + [_vp] * 6 + [_str, _size]),
+    "wfa_hip_placer_rescue": (_CTYPES, [_vp] * 3 + [_i32] * 5 + [_i64, _vp, _vp] + [_i32] * 3 + [_i64, _i64p, _vp]),
+    "wfa_hip_rescue_host": (_CTYPES, _HITS + [_i32] * 5 + [_i64, _vp, _vp, _vp, _i64, _vp] + [_i32] * 3 +
+                            [_i64, _i64p, _vp, _str, _size]),
+}
+SYMBOLS = list(SIGNATURES)
 
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
 CROSS_MAX_K = 64
@@ -113,133 +187,15 @@ def lib():
         raise NativeError(f"{LIB_PATH} is missing: build it with pywfa_amd/csrc/build.sh "
                           "(there is no CPU fallback)")
     L = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    cfgp = ctypes.POINTER(Config)
-    L.wfa_hip_abi_version.restype = ctypes.c_int
-    L.wfa_hip_device_count.restype = ctypes.c_int
-    L.wfa_hip_global_error.restype = ctypes.c_char_p
-    L.wfa_hip_config_default.argtypes = [cfgp]
-    L.wfa_hip_config_validate.argtypes = [cfgp, ctypes.c_char_p, ctypes.c_size_t]
-    L.wfa_hip_create.argtypes = [cfgp, ctypes.c_int]
-    L.wfa_hip_create.restype = vp
-    L.wfa_hip_destroy.argtypes = [vp]
-    L.wfa_hip_destroy.restype = None
-    L.wfa_hip_set_config.argtypes = [vp, cfgp]
-    L.wfa_hip_get_config.argtypes = [vp, cfgp]
-    L.wfa_hip_last_error.argtypes = [vp]
-    L.wfa_hip_last_error.restype = ctypes.c_char_p
-    L.wfa_hip_align_batch.argtypes = [vp, i64] + [vp] * 11
-    L.wfa_hip_align_pair.argtypes = [vp, ctypes.c_char_p, i32, ctypes.c_char_p, i32, vp, vp, vp, vp, vp]
-    L.wfa_hip_batch_create.argtypes = [vp, i64] + [vp] * 5
-    L.wfa_hip_batch_create.restype = vp
-    L.wfa_hip_align_batch_packed2bits.argtypes = [vp, i64] + [vp] * 11
-    L.wfa_hip_batch_create_packed2bits.argtypes = [vp, i64] + [vp] * 5
-    L.wfa_hip_batch_create_packed2bits.restype = vp
-    L.wfa_hip_cigar_sprint_pretty.argtypes = [vp, i64, vp, i32, vp, i32, vp, i64]
-    L.wfa_hip_cigar_sprint_pretty.restype = i64
-    L.wfa_hip_batch_destroy.argtypes = [vp]
-    L.wfa_hip_batch_destroy.restype = None
-    L.wfa_hip_batch_run.argtypes = [vp, vp]
-    L.wfa_hip_batch_sync.argtypes = [vp]
-    L.wfa_hip_batch_results.argtypes = [vp] * 7
-    L.wfa_hip_batch_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
-    L.wfa_hip_batch_algorithmic_bytes.argtypes = [vp]
-    L.wfa_hip_batch_algorithmic_bytes.restype = i64
-    L.wfa_hip_batch_fallback_pairs.argtypes = [vp]
-    L.wfa_hip_batch_fallback_pairs.restype = i64
-    L.wfa_hip_batch_rle_counts.argtypes = [vp, vp, vp]
-    L.wfa_hip_batch_rle_counts.restype = i64
-    L.wfa_hip_batch_rle_runs.argtypes = [vp, vp, vp]
-    L.wfa_hip_plan_shards.argtypes = [i64, vp, vp, ctypes.c_int, vp]
-    L.wfa_hip_plan_host_threads.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    L.wfa_hip_pack_2bit.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int]
-    L.wfa_hip_upload_info.argtypes = [vp, vp, ctypes.c_int]
-    L.wfa_hip_batch_extent.argtypes = [i64, vp, vp, vp, vp]
-    L.wfa_hip_batch_extent.restype = i64
-    L.wfa_hip_batch_extent_packed2bits.argtypes = [i64, vp, vp, vp, vp]
-    L.wfa_hip_batch_extent_packed2bits.restype = i64
-    L.wfa_hip_multi_create.argtypes = [cfgp, vp, ctypes.c_int]
-    L.wfa_hip_multi_create.restype = vp
-    L.wfa_hip_multi_destroy.argtypes = [vp]
-    L.wfa_hip_multi_destroy.restype = None
-    L.wfa_hip_multi_set_config.argtypes = [vp, cfgp]
-    L.wfa_hip_multi_last_error.argtypes = [vp]
-    L.wfa_hip_multi_last_error.restype = ctypes.c_char_p
-    L.wfa_hip_multi_align_batch.argtypes = [vp, i64] + [vp] * 11
-    L.wfa_hip_seqset_create.argtypes = [vp, i64, vp, vp, vp]
-    L.wfa_hip_seqset_create.restype = vp
-    L.wfa_hip_seqset_destroy.argtypes = [vp]
-    L.wfa_hip_seqset_destroy.restype = None
-    L.wfa_hip_cross_run.argtypes = [vp, vp, vp, ctypes.c_int]
-    L.wfa_hip_cross_run.restype = vp
-    L.wfa_hip_cross_run_k.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int]
-    L.wfa_hip_cross_run_k.restype = vp
-    L.wfa_hip_cross_topk.argtypes = [vp, vp, vp]
-    L.wfa_hip_cross_dense.argtypes = [vp, vp, vp]
-    L.wfa_hip_cross_completed.argtypes = [vp, ctypes.POINTER(i64), vp, vp, vp]
-    L.wfa_hip_cross_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
-    L.wfa_hip_cross_destroy.argtypes = [vp]
-    L.wfa_hip_cross_destroy.restype = None
-    L.wfa_hip_plan_cross_bands.argtypes = [i64, i64, ctypes.c_int, i64, vp, i64]
-    L.wfa_hip_plan_cross_bands.restype = i64
-    L.wfa_hip_batch_create_indexed.argtypes = [vp, vp, vp, i64, vp, vp]
-    L.wfa_hip_batch_create_indexed.restype = vp
-    L.wfa_hip_batch_create_windows.argtypes = [vp, vp, vp, i64] + [vp] * 7
-    L.wfa_hip_batch_create_windows.restype = vp
-    L.wfa_hip_window_2bit.argtypes = [vp, i64, i32, ctypes.c_int, vp]
-    L.wfa_hip_batch_summary.argtypes = [vp, vp]
-    L.wfa_hip_ops_summary.argtypes = [vp, i64, i32, i32, vp]
-    L.wfa_hip_pileup_create.argtypes = [vp, vp]
-    L.wfa_hip_pileup_create.restype = vp
-    L.wfa_hip_pileup_add.argtypes = [vp, vp, vp, vp, vp]
-    L.wfa_hip_pileup_read.argtypes = [vp, i32, i64, i64, vp]
-    L.wfa_hip_pileup_clear.argtypes = [vp]
-    L.wfa_hip_pileup_destroy.argtypes = [vp]
-    L.wfa_hip_pileup_destroy.restype = None
-    L.wfa_hip_ops_pileup.argtypes = [vp, i64, vp, i32, i32, vp]
-    L.wfa_hip_seed_index_create.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.wfa_hip_seed_index_create.restype = vp
-    L.wfa_hip_seed_index_destroy.argtypes = [vp]
-    L.wfa_hip_seed_index_destroy.restype = None
-    L.wfa_hip_seed_index_query.argtypes = [vp, vp] + [ctypes.c_int] * 5 + [vp] * 6
-    L.wfa_hip_seed_index_stats.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64),
-                                           ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
-    L.wfa_hip_seeds_host.argtypes = [vp, i32, i64, vp, vp, vp] + [ctypes.c_int] * 8 + [vp] * 6 + [ctypes.c_char_p, ctypes.c_size_t]
-    L.wfa_hip_seed_index_chain.argtypes = [vp, vp] + [ctypes.c_int] * 8 + [vp] * 9
-    L.wfa_hip_seed_index_chain_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
-    L.wfa_hip_chains_host.argtypes = [vp, i32, i64, vp, vp, vp] + [ctypes.c_int] * 11 + [vp] * 9 + [ctypes.c_char_p, ctypes.c_size_t]
-    L.wfa_hip_seed_index_create_minimizer.argtypes = L.wfa_hip_seed_index_create.argtypes
-    L.wfa_hip_seed_index_create_minimizer.restype = vp
-    L.wfa_hip_seed_index_params.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int)] * 3
-    L.wfa_hip_minimizers_host.argtypes = [vp, i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_size_t]
-    L.wfa_hip_seeds_host_minimizer.argtypes = L.wfa_hip_seeds_host.argtypes
-    L.wfa_hip_chains_host_minimizer.argtypes = L.wfa_hip_chains_host.argtypes
-    L.wfa_hip_pileup_calls.argtypes = [vp, vp, i32, i64, i64, i32, vp]
-    L.wfa_hip_pileup_sites.argtypes = [vp, vp, i32, i64, i64, i32, i32, i64, ctypes.POINTER(i64), vp]
-    L.wfa_hip_calls_host.argtypes = [vp, vp, i64, i32, vp]
-    L.wfa_hip_sites_host.argtypes = [vp, vp, i64, i32, i64, i32, i32, i64, ctypes.POINTER(i64), vp]
-    L.wfa_hip_placer_create.argtypes = [vp, i64]
-    L.wfa_hip_placer_create.restype = vp
-    L.wfa_hip_placer_add.argtypes = [vp] * 6
-    L.wfa_hip_placer_add_hits.argtypes = [vp, i64] + [vp] * 7
-    L.wfa_hip_placer_run.argtypes = [vp, i32, i32, vp, vp]
-    L.wfa_hip_placer_count.argtypes = [vp]
-    L.wfa_hip_placer_count.restype = i64
-    L.wfa_hip_placer_clear.argtypes = [vp]
-    L.wfa_hip_placer_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-    L.wfa_hip_placer_destroy.argtypes = [vp]
-    L.wfa_hip_placer_destroy.restype = None
-    L.wfa_hip_place_host.argtypes = [i64, i64] + [vp] * 7 + [i32, i32, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
-    L.wfa_hip_placer_run_pairs.argtypes = [vp] + [i32] * 5 + [i64] + [vp] * 6
-    L.wfa_hip_pair_host.argtypes = [i64, i64] + [vp] * 7 + [i32] * 5 + [i64] + [vp] * 6 + [ctypes.c_char_p, ctypes.c_size_t]
-    L.wfa_hip_placer_rescue.argtypes = [vp] * 3 + [i32] * 5 + [i64, vp, vp] + [i32] * 3 + [i64, ctypes.POINTER(i64), vp]
-    L.wfa_hip_rescue_host.argtypes = ([i64, i64] + [vp] * 7 + [i32] * 5 + [i64, vp, vp, vp, i64, vp] + [i32] * 3 +
-                                      [i64, ctypes.POINTER(i64), vp, ctypes.c_char_p, ctypes.c_size_t])
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if restype is not _CTYPES:
+            getattr(L, name).restype = restype
+        if argtypes is not _CTYPES:
+            getattr(L, name).argtypes = argtypes
     if L.wfa_hip_abi_version() != ABI_VERSION:
         raise NativeError("libwfa_hip.so ABI version mismatch: rebuild it")
     _lib = L
     return L
-
 
 
 _HOST = False   # False = not looked for yet; None = absent
@@ -276,6 +232,11 @@ def validate(cfg):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _ptr_or_null(a):
+    """``_ptr`` with NULL for an empty array too."""
+    return _ptr(a) if a is not None and a.size else None
 
 
 def _check_batch(batch):
@@ -332,22 +293,44 @@ def cigar_sprint_pretty(ops, pattern, text):
     return buf.value.decode("ascii", "replace")
 
 
-class Aligner:
+def _raise_code(rc, what, msg):
+    """The exception of a non-OK code of the library."""
+    if rc == EINVAL:
+        raise ValueError(f"{what}: {msg}")
+    if rc == ENOTSUP:
+        raise NotImplementedError(f"{what}: {msg}")
+    raise NativeError(f"{what}: {msg}")
+
+
+def _raise_config_refused(cfg, what):
+    """The exception of an aligner create that returned NULL: what the validation says of ``cfg``, else the library's global error."""
+    msg = lib().wfa_hip_global_error().decode()
+    rc, vmsg = validate(cfg)
+    if rc == EINVAL:
+        raise ValueError(vmsg)
+    if rc == ENOTSUP:
+        raise NotImplementedError(vmsg)
+    raise NativeError(f"{what} failed: {msg}")
+
+
+class _Checked:
+    """``_call``: one call of the library whose non-OK code goes to ``_raise`` under the symbol's name."""
+
+    def _call(self, symbol, *args):
+        rc = getattr(lib(), symbol)(*args)
+        if rc != OK:
+            self._raise(rc, symbol)
+
+
+class Aligner(_Checked):
     """Owns one wfa_hip_aligner_t (replaces the wavefront_aligner_t* of align.pyx:419)."""
 
     def __init__(self, cfg, device=0):
-        L = lib()
         self._pair_caller = None
         self._pair_align = None
-        self._h = L.wfa_hip_create(ctypes.byref(cfg), device)
+        self._h = lib().wfa_hip_create(ctypes.byref(cfg), device)
         if not self._h:
-            msg = L.wfa_hip_global_error().decode()
-            rc, vmsg = validate(cfg)
-            if rc == EINVAL:
-                raise ValueError(vmsg)
-            if rc == ENOTSUP:
-                raise NotImplementedError(vmsg)
-            raise NativeError(f"wfa_hip_create failed: {msg}")
+            _raise_config_refused(cfg, "wfa_hip_create")
         self.device = device
         self._batches = weakref.WeakSet()
         self._pair_state = None
@@ -381,17 +364,10 @@ class Aligner:
         return lib().wfa_hip_last_error(self._h).decode()
 
     def _raise(self, rc, what):
-        msg = self.error()
-        if rc == EINVAL:
-            raise ValueError(f"{what}: {msg}")
-        if rc == ENOTSUP:
-            raise NotImplementedError(f"{what}: {msg}")
-        raise NativeError(f"{what}: {msg}")
+        _raise_code(rc, what, self.error())
 
     def set_config(self, cfg):
-        rc = lib().wfa_hip_set_config(self._h, ctypes.byref(cfg))
-        if rc != OK:
-            self._raise(rc, "wfa_hip_set_config")
+        self._call("wfa_hip_set_config", self._h, ctypes.byref(cfg))
 
     def get_config(self):
         c = Config()
@@ -608,7 +584,7 @@ def place_host(nreads, i, j, reverse, score, status, text_start, text_end, min_s
     rows = np.zeros((max(nreads, 0), PLACE_COLS), np.int32)
     flags = np.zeros(n, np.uint8)
     msg = ctypes.create_string_buffer(256)
-    p = lambda v: _ptr(v) if v is not None and v.size else None   # noqa: E731
+    p = _ptr_or_null
     rc = lib().wfa_hip_place_host(nreads, n, p(a["i"]), p(a["j"]), p(a["reverse"]), p(a["score"]), p(a["status"]), p(a["text_start"]),
                                   p(a["text_end"]), int(min_score), int(full_gap), p(rows), p(flags), msg, 256)
     if rc != OK:
@@ -629,6 +605,13 @@ def _mate_arrays(mates):
     return m.shape[0], np.ascontiguousarray(m[:, 0], dtype=np.int32), np.ascontiguousarray(m[:, 1], dtype=np.int32)
 
 
+def _mate_ptrs(mates):
+    """``(nfrag, mate1, mate2)`` as the C entries take them: ``_mate_arrays`` as pointers (which keep their arrays alive), NULL for
+    interleaved mates only: an empty mate array is still "given"."""
+    nfrag, m1, m2 = _mate_arrays(mates)
+    return nfrag, _ptr(m1), _ptr(m2)
+
+
 def pair_host(nreads, i, j, reverse, score, status, text_start, text_end, mates, min_score=INT32_MIN, full_gap=1, min_insert=0,
               max_insert=1000, unpaired=0):
     """wfa_hip_pair_host (host only): ``(rows, flags, pair_rows, pair_flags)`` of the pairing rule over a list of hits in hit-number
@@ -636,18 +619,17 @@ def pair_host(nreads, i, j, reverse, score, status, text_start, text_end, mates,
     per hit; what ``Placer.add_hits`` + ``Placer.run_pairs`` give.  ``mates``: an (F, 2) integer array of read indices, or an int F:
     interleaved, fragment f being reads 2 f and 2 f + 1."""
     a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
-    nfrag, m1, m2 = _mate_arrays(mates)
+    nfrag, m1, m2 = _mate_ptrs(mates)
     nreads = int(nreads)
     rows = np.zeros((max(nreads, 0), PLACE_COLS), np.int32)
     flags = np.zeros(n, np.uint8)
     pair_rows = np.zeros((max(nfrag, 0), PAIR_COLS), np.int32)
     pair_flags = np.zeros(n, np.uint8)
     msg = ctypes.create_string_buffer(256)
-    p = lambda v: _ptr(v) if v is not None and v.size else None   # noqa: E731
-    mp = lambda v: None if v is None else _ptr(v)                 # noqa: E731  (an empty mate array is still "given")
+    p = _ptr_or_null
     rc = lib().wfa_hip_pair_host(nreads, n, p(a["i"]), p(a["j"]), p(a["reverse"]), p(a["score"]), p(a["status"]), p(a["text_start"]),
                                  p(a["text_end"]), int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired), nfrag,
-                                 mp(m1), mp(m2), p(rows), p(flags), p(pair_rows), p(pair_flags), msg, 256)
+                                 m1, m2, p(rows), p(flags), p(pair_rows), p(pair_flags), msg, 256)
     if rc != OK:
         raise ValueError(f"wfa_hip_pair_host: {msg.value.decode()}")
     return rows, flags, pair_rows, pair_flags
@@ -659,7 +641,7 @@ def rescue_host(nreads, i, j, reverse, score, status, text_start, text_end, mate
     ``read_len`` (one per read) and the texts' lengths ``text_len`` — rows int32 of shape (min(count, cap), 8) in the columns
     RESCUE_COLUMNS, every window when ``cap`` is None (a counting call first); what ``Placer.add_hits`` + ``Placer.rescue`` give."""
     a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
-    nfrag, m1, m2 = _mate_arrays(mates)
+    nfrag, m1, m2 = _mate_ptrs(mates)
     nreads = int(nreads)
     read_len = np.ascontiguousarray(read_len, dtype=np.int32)
     text_len = np.ascontiguousarray(text_len, dtype=np.int32)
@@ -668,10 +650,9 @@ def rescue_host(nreads, i, j, reverse, score, status, text_start, text_end, mate
     if text_len.ndim != 1:
         raise ValueError("text_len: one value per text")
     msg = ctypes.create_string_buffer(256)
-    p = lambda v: _ptr(v) if v is not None and v.size else None   # noqa: E731
-    mp = lambda v: None if v is None else _ptr(v)                 # noqa: E731  (an empty mate array is still "given")
+    p = _ptr_or_null
     args = (nreads, n, p(a["i"]), p(a["j"]), p(a["reverse"]), p(a["score"]), p(a["status"]), p(a["text_start"]), p(a["text_end"]),
-            int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired), nfrag, mp(m1), mp(m2), p(read_len),
+            int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired), nfrag, m1, m2, p(read_len),
             text_len.shape[0], p(text_len), int(pad), int(min_len), int(anchor_mapq))
     count = ctypes.c_int64(0)
     if cap is None:
@@ -783,9 +764,43 @@ def plan_cross_bands(m, n, triangle, max_pairs):
     return out
 
 
-class SeqSet:
+class _Handle(_Checked):
+    """What the resident handles share: the ``aligner`` they belong to (its ``close()`` closes them first), the native handle ``_h``,
+    and an idempotent ``close()`` through the destroy symbol the class names."""
+
+    _destroy = None              # the symbol that frees _h
+    _device_failure = "failed"   # a refused create whose message holds this is a NativeError, any other a ValueError
+    aligner = None
+    _h = None                    # (also of an object whose constructor raised: close() and __del__ then do nothing)
+
+    def _created(self, handle, what, refused=ValueError):
+        """Keep the handle a create returned and register with the aligner, or raise its last error under the symbol's name."""
+        self._h = handle
+        if not handle:
+            msg = self.aligner.error()
+            raise (NativeError if self._device_failure in msg else refused)(f"{what}: {msg}")
+        self.aligner._batches.add(self)
+
+    def _raise(self, rc, what):
+        self.aligner._raise(rc, what)
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SeqSet(_Handle):
     """A set of sequences resident in HBM, 2-bit packed once (wfa_hip_seqset_t).  ``seqs`` / ``off`` / ``len`` as a batch's blob:
     sequence k = seqs[off[k] .. +len[k])."""
+
+    _destroy = "wfa_hip_seqset_destroy"
 
     def __init__(self, aligner, seqs, off, length):
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
@@ -801,28 +816,14 @@ class SeqSet:
         self.aligner = aligner
         self.n = n
         self.length = length.copy()   # (an indexed batch sizes its op buffers from the lengths)
-        self._h = lib().wfa_hip_seqset_create(aligner._h, n, _ptr(seqs) if seqs.size else None, _ptr(off), _ptr(length))
-        if not self._h:
-            msg = aligner.error()
-            if "failed:" in msg:
-                raise NativeError(f"wfa_hip_seqset_create: {msg}")
-            raise ValueError(f"wfa_hip_seqset_create: {msg}")
-        aligner._batches.add(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().wfa_hip_seqset_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._created(lib().wfa_hip_seqset_create(aligner._h, n, _ptr(seqs) if seqs.size else None, _ptr(off), _ptr(length)),
+                      "wfa_hip_seqset_create")
 
 
-class CrossRun:
+class CrossRun(_Handle):
     """The results of one cross run, resident in HBM (wfa_hip_cross_t)."""
+
+    _destroy = "wfa_hip_cross_destroy"
 
     def __init__(self, aligner, patterns, texts=None, want=CROSS_DENSE, k=None):
         self.aligner = aligner
@@ -831,67 +832,43 @@ class CrossRun:
         self.k = 0 if k is None else int(k)
         th = None if texts is None else texts._h
         if k is None:
-            self._h = lib().wfa_hip_cross_run(aligner._h, patterns._h, th, int(want))
+            h = lib().wfa_hip_cross_run(aligner._h, patterns._h, th, int(want))
         else:
-            self._h = lib().wfa_hip_cross_run_k(aligner._h, patterns._h, th, int(want), self.k)
-        if not self._h:
-            msg = aligner.error()
-            if "failed" in msg:
-                raise NativeError(f"wfa_hip_cross_run: {msg}")
-            raise ValueError(f"wfa_hip_cross_run: {msg}")
-        aligner._batches.add(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().wfa_hip_cross_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            h = lib().wfa_hip_cross_run_k(aligner._h, patterns._h, th, int(want), self.k)
+        self._created(h, "wfa_hip_cross_run")
 
     def dense(self):
         score = np.zeros((self.m, self.n), np.int32)
         status = np.zeros((self.m, self.n), np.int32)
-        rc = lib().wfa_hip_cross_dense(self._h, _ptr(score), _ptr(status))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_cross_dense")
+        self._call("wfa_hip_cross_dense", self._h, _ptr(score), _ptr(status))
         return score, status
 
     def completed(self):
         count = ctypes.c_int64(0)
-        rc = lib().wfa_hip_cross_completed(self._h, ctypes.byref(count), None, None, None)
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_cross_completed")
+        self._call("wfa_hip_cross_completed", self._h, ctypes.byref(count), None, None, None)
         out = {k: np.zeros(count.value, np.int32) for k in ("i", "j", "score")}
         if count.value:
-            rc = lib().wfa_hip_cross_completed(self._h, ctypes.byref(count), _ptr(out["i"]), _ptr(out["j"]), _ptr(out["score"]))
-            if rc != OK:
-                self.aligner._raise(rc, "wfa_hip_cross_completed")
+            self._call("wfa_hip_cross_completed", self._h, ctypes.byref(count), _ptr(out["i"]), _ptr(out["j"]), _ptr(out["score"]))
         return out
 
     def topk(self):
         """wfa_hip_cross_topk: dict(j=, score=), int32 arrays of shape (m, k)."""
         out = {key: np.zeros((self.m, self.k), np.int32) for key in ("j", "score")}
-        rc = lib().wfa_hip_cross_topk(self._h, _ptr(out["j"]), _ptr(out["score"]))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_cross_topk")
+        self._call("wfa_hip_cross_topk", self._h, _ptr(out["j"]), _ptr(out["score"]))
         return out
 
     def kernel_ms(self):
         ms = ctypes.c_float(0)
         pairs = ctypes.c_int64(0)
-        rc = lib().wfa_hip_cross_kernel_ms(self._h, ctypes.byref(ms), ctypes.byref(pairs))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_cross_kernel_ms")
+        self._call("wfa_hip_cross_kernel_ms", self._h, ctypes.byref(ms), ctypes.byref(pairs))
         return ms.value, pairs.value
 
 
-class Pileup:
+class Pileup(_Handle):
     """Per-base counters over a text SeqSet, resident in HBM (wfa_hip_pileup_t): 32 bytes per text base, int32 counters without an
     overflow check.  Stays valid after the set is closed."""
+
+    _destroy = "wfa_hip_pileup_destroy"
 
     def __init__(self, aligner, texts):
         if not texts._h:
@@ -899,24 +876,7 @@ class Pileup:
         self.aligner = aligner
         self.n = texts.n
         self.length = texts.length
-        self._h = lib().wfa_hip_pileup_create(aligner._h, texts._h)
-        if not self._h:
-            msg = aligner.error()
-            if "failed" in msg:
-                raise NativeError(f"wfa_hip_pileup_create: {msg}")
-            raise ValueError(f"wfa_hip_pileup_create: {msg}")
-        aligner._batches.add(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().wfa_hip_pileup_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._created(lib().wfa_hip_pileup_create(aligner._h, texts._h), "wfa_hip_pileup_create")
 
     def add(self, batch, j, t_start=None, keep=None):
         """wfa_hip_pileup_add: the pairs of a ResidentBatch after its full-scope run, pair q against texts[j[q]] from t_start[q]."""
@@ -926,37 +886,30 @@ class Pileup:
         for name, a in (("j", j), ("t_start", t_start), ("keep", keep)):
             if a is not None and a.shape != (batch.n,):
                 raise ValueError(f"{name}: one value per pair of the batch ({batch.n})")
-        rc = lib().wfa_hip_pileup_add(self._h, batch._h, _ptr(j), _ptr(t_start), _ptr(keep))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_pileup_add")
+        self._call("wfa_hip_pileup_add", self._h, batch._h, _ptr(j), _ptr(t_start), _ptr(keep))
 
-    def read(self, seq, start=0, length=None):
-        """wfa_hip_pileup_read: int32[length, 8], the rows [start, start + length) of one sequence (to its end when None)."""
+    def _rows(self, seq, start, length):
+        """``(seq, start, length)`` as ints, a ``length`` of None running to the end of the sequence."""
         seq, start = int(seq), int(start)
         if length is None:
             if not 0 <= seq < self.n:
                 raise ValueError(f"sequence {seq} is out of range for a set of {self.n}")
             length = int(self.length[seq]) - start
-        length = int(length)
+        return seq, start, int(length)
+
+    def read(self, seq, start=0, length=None):
+        """wfa_hip_pileup_read: int32[length, 8], the rows [start, start + length) of one sequence (to its end when None)."""
+        seq, start, length = self._rows(seq, start, length)
         out = np.zeros((max(length, 0), PILEUP_COLS), np.int32)
-        rc = lib().wfa_hip_pileup_read(self._h, seq, start, length, _ptr(out) if out.size else None)
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_pileup_read")
+        self._call("wfa_hip_pileup_read", self._h, seq, start, length, _ptr_or_null(out))
         return out
 
     def calls(self, texts, seq, start=0, length=None, min_depth=1):
         """wfa_hip_pileup_calls: uint8[length], the call bytes of the rows [start, start + length) of one sequence (to its end when
         None) against the letters of the SeqSet ``texts``."""
-        seq, start = int(seq), int(start)
-        if length is None:
-            if not 0 <= seq < self.n:
-                raise ValueError(f"sequence {seq} is out of range for a set of {self.n}")
-            length = int(self.length[seq]) - start
-        length = int(length)
+        seq, start, length = self._rows(seq, start, length)
         out = np.zeros(max(length, 0), np.uint8)
-        rc = lib().wfa_hip_pileup_calls(self._h, texts._h, seq, start, length, int(min_depth), _ptr(out) if out.size else None)
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_pileup_calls")
+        self._call("wfa_hip_pileup_calls", self._h, texts._h, seq, start, length, int(min_depth), _ptr_or_null(out))
         return out
 
     def sites(self, texts, seq=-1, start=0, length=-1, min_depth=1, min_permille=500, cap=None):
@@ -965,48 +918,27 @@ class Pileup:
         args = (self._h, texts._h, int(seq), int(start), int(length), int(min_depth), int(min_permille))
         count = ctypes.c_int64(0)
         if cap is None:
-            rc = lib().wfa_hip_pileup_sites(*args, 0, ctypes.byref(count), None)
-            if rc != OK:
-                self.aligner._raise(rc, "wfa_hip_pileup_sites")
+            self._call("wfa_hip_pileup_sites", *args, 0, ctypes.byref(count), None)
             cap = count.value
         rows = np.zeros((max(int(cap), 0), SITE_COLS), np.int32)
         if cap != 0:
-            rc = lib().wfa_hip_pileup_sites(*args, int(cap), ctypes.byref(count), _ptr(rows) if rows.size else None)
-            if rc != OK:
-                self.aligner._raise(rc, "wfa_hip_pileup_sites")
+            self._call("wfa_hip_pileup_sites", *args, int(cap), ctypes.byref(count), _ptr_or_null(rows))
         return count.value, rows[:min(count.value, rows.shape[0])]
 
     def clear(self):
-        rc = lib().wfa_hip_pileup_clear(self._h)
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_pileup_clear")
+        self._call("wfa_hip_pileup_clear", self._h)
 
 
-class Placer:
+class Placer(_Handle):
     """The hits of any number of batches, recorded and grouped by read in HBM (wfa_hip_placer_t); ``run`` reduces every read to one
     row.  Stays valid after the batches are closed."""
+
+    _destroy = "wfa_hip_placer_destroy"
 
     def __init__(self, aligner, nreads):
         self.aligner = aligner
         self.nreads = int(nreads)
-        self._h = lib().wfa_hip_placer_create(aligner._h, self.nreads)
-        if not self._h:
-            msg = aligner.error()
-            if "failed" in msg:
-                raise NativeError(f"wfa_hip_placer_create: {msg}")
-            raise ValueError(f"wfa_hip_placer_create: {msg}")
-        aligner._batches.add(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().wfa_hip_placer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._created(lib().wfa_hip_placer_create(aligner._h, self.nreads), "wfa_hip_placer_create")
 
     def __len__(self):
         return int(lib().wfa_hip_placer_count(self._h))
@@ -1020,25 +952,20 @@ class Placer:
         for name, a in (("i", i), ("j", j), ("t_start", t_start), ("reverse", reverse)):
             if a is not None and a.shape != (batch.n,):
                 raise ValueError(f"{name}: one value per pair of the batch ({batch.n})")
-        rc = lib().wfa_hip_placer_add(self._h, batch._h, _ptr(i), _ptr(j), _ptr(t_start), _ptr(reverse))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_placer_add")
+        self._call("wfa_hip_placer_add", self._h, batch._h, _ptr(i), _ptr(j), _ptr(t_start), _ptr(reverse))
 
     def add_hits(self, i, j, reverse, score, status, text_start, text_end):
         """wfa_hip_placer_add_hits: hits from host arrays, in list order."""
         a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
-        rc = lib().wfa_hip_placer_add_hits(self._h, n, *[_ptr(a[k]) for k in ("i", "j", "reverse", "score", "status", "text_start", "text_end")])
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_placer_add_hits")
+        self._call("wfa_hip_placer_add_hits", self._h, n,
+                   *[_ptr(a[k]) for k in ("i", "j", "reverse", "score", "status", "text_start", "text_end")])
 
     def run(self, min_score=INT32_MIN, full_gap=1, flags=True):
         """wfa_hip_placer_run over every hit added so far: ``(rows, flags)``, rows int32 of shape (nreads, 8) in the columns
         PLACE_COLUMNS, flags uint8 per hit (None when ``flags`` is False)."""
         rows = np.zeros((self.nreads, PLACE_COLS), np.int32)
         fl = np.zeros(len(self), np.uint8) if flags else None
-        rc = lib().wfa_hip_placer_run(self._h, int(min_score), int(full_gap), _ptr(rows) if rows.size else None, _ptr(fl))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_placer_run")
+        self._call("wfa_hip_placer_run", self._h, int(min_score), int(full_gap), _ptr_or_null(rows), _ptr(fl))
         return rows, fl
 
     def run_pairs(self, mates, min_score=INT32_MIN, full_gap=1, min_insert=0, max_insert=1000, unpaired=0, rows=True, flags=True,
@@ -1046,16 +973,14 @@ class Placer:
         """wfa_hip_placer_run_pairs over every hit added so far: ``(rows, flags, pair_rows, pair_flags)`` — rows and flags as ``run``
         gives them, pair_rows int32 of shape (F, 12) in the columns PAIR_COLUMNS, pair_flags uint8 per hit; None for each of rows,
         flags and pair_flags that is False.  ``mates``: an (F, 2) integer array of read indices, or an int F: interleaved."""
-        nfrag, m1, m2 = _mate_arrays(mates)
+        nfrag, m1, m2 = _mate_ptrs(mates)
         r = np.zeros((self.nreads, PLACE_COLS), np.int32) if rows else None
         fl = np.zeros(len(self), np.uint8) if flags else None
         pr = np.zeros((max(nfrag, 0), PAIR_COLS), np.int32)
         pf = np.zeros(len(self), np.uint8) if pair_flags else None
-        p = lambda v: _ptr(v) if v is not None and v.size else None   # noqa: E731
-        rc = lib().wfa_hip_placer_run_pairs(self._h, int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired), nfrag,
-                                            None if m1 is None else _ptr(m1), None if m2 is None else _ptr(m2), p(r), p(fl), p(pr), p(pf))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_placer_run_pairs")
+        p = _ptr_or_null
+        self._call("wfa_hip_placer_run_pairs", self._h, int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired),
+                   nfrag, m1, m2, p(r), p(fl), p(pr), p(pf))
         return r, fl, pr, pf
 
     def rescue(self, patterns, texts, mates, min_score=INT32_MIN, full_gap=1, min_insert=0, max_insert=1000, unpaired=0, pad=16, min_len=0,
@@ -1064,35 +989,30 @@ class Placer:
         fragments without a proper pairing must lie — rows int32 of shape (min(count, cap), 8) in the columns RESCUE_COLUMNS, list
         order; ``cap`` None: room for every window (two per fragment).  ``patterns`` / ``texts``: the SeqSets of the reads and of the
         texts the hits lie on; ``mates`` as for ``run_pairs``."""
-        nfrag, m1, m2 = _mate_arrays(mates)
+        nfrag, m1, m2 = _mate_ptrs(mates)
         if cap is None:
             cap = 2 * max(nfrag, 0)
         rows = np.zeros((max(int(cap), 0), RESCUE_COLS), np.int32)
         count = ctypes.c_int64(0)
-        rc = lib().wfa_hip_placer_rescue(self._h, patterns._h, texts._h, int(min_score), int(full_gap), int(min_insert), int(max_insert),
-                                         int(unpaired), nfrag, None if m1 is None else _ptr(m1), None if m2 is None else _ptr(m2),
-                                         int(pad), int(min_len), int(anchor_mapq), int(cap), ctypes.byref(count),
-                                         _ptr(rows) if rows.size else None)
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_placer_rescue")
+        self._call("wfa_hip_placer_rescue", self._h, patterns._h, texts._h, int(min_score), int(full_gap), int(min_insert),
+                   int(max_insert), int(unpaired), nfrag, m1, m2, int(pad), int(min_len), int(anchor_mapq), int(cap),
+                   ctypes.byref(count), _ptr_or_null(rows))
         return count.value, rows[:min(count.value, rows.shape[0])]
 
     def kernel_ms(self):
         ms = ctypes.c_float(0)
-        rc = lib().wfa_hip_placer_kernel_ms(self._h, ctypes.byref(ms))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_placer_kernel_ms")
+        self._call("wfa_hip_placer_kernel_ms", self._h, ctypes.byref(ms))
         return ms.value
 
     def clear(self):
-        rc = lib().wfa_hip_placer_clear(self._h)
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_placer_clear")
+        self._call("wfa_hip_placer_clear", self._h)
 
 
-class SeedIndex:
+class SeedIndex(_Handle):
     """An exact-match k-mer index over a text SeqSet, resident in HBM (wfa_hip_seed_index_t): 4^k * 4 bytes of table plus 8 bytes per
     indexed position.  Stays valid after the set is closed."""
+
+    _destroy = "wfa_hip_seed_index_destroy"
 
     def __init__(self, aligner, texts, k=13, stride=1, max_occ=64, w=None):
         if not texts._h:
@@ -1100,38 +1020,18 @@ class SeedIndex:
         self.aligner = aligner
         self.n = texts.n
         if w is None:
-            name = "wfa_hip_seed_index_create"
-            self._h = lib().wfa_hip_seed_index_create(aligner._h, texts._h, k, stride, max_occ)
+            self._created(lib().wfa_hip_seed_index_create(aligner._h, texts._h, k, stride, max_occ), "wfa_hip_seed_index_create")
         else:
-            name = "wfa_hip_seed_index_create_minimizer"
-            self._h = lib().wfa_hip_seed_index_create_minimizer(aligner._h, texts._h, k, w, max_occ)
-        if not self._h:
-            msg = aligner.error()
-            if "failed" in msg:
-                raise NativeError(f"{name}: {msg}")
-            raise ValueError(f"{name}: {msg}")
-        aligner._batches.add(self)
+            self._created(lib().wfa_hip_seed_index_create_minimizer(aligner._h, texts._h, k, w, max_occ),
+                          "wfa_hip_seed_index_create_minimizer")
 
     def params(self):
         """wfa_hip_seed_index_params: dict(k=, stride=, w=); w = 0 for a stride index, stride = 1 for a minimizer index."""
         if not self._h:
             raise ValueError("seed index is closed")
         k, stride, w = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        rc = lib().wfa_hip_seed_index_params(self._h, ctypes.byref(k), ctypes.byref(stride), ctypes.byref(w))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_seed_index_params")
+        self._call("wfa_hip_seed_index_params", self._h, ctypes.byref(k), ctypes.byref(stride), ctypes.byref(w))
         return dict(k=k.value, stride=stride.value, w=w.value)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().wfa_hip_seed_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def query(self, patterns, n=4, min_hits=2, gap=16, pad=16, max_hits=2048):
         """wfa_hip_seed_index_query: dict of int32[M, n] ``j`` / ``reverse`` / ``text_start`` / ``text_len`` / ``hits`` and uint8[M]
@@ -1143,10 +1043,8 @@ class SeedIndex:
         cols = n if 1 <= n <= SEED_MAX_N else 1   # (out of range: the library refuses before it writes)
         out = {key: np.zeros((patterns.n, cols), np.int32) for key in SEED_KEYS}
         out["overflow"] = np.zeros(patterns.n, np.uint8)
-        rc = lib().wfa_hip_seed_index_query(self._h, patterns._h, n, min_hits, gap, pad, max_hits, *[_ptr(out[key]) for key in SEED_KEYS],
-                                            _ptr(out["overflow"]))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_seed_index_query")
+        self._call("wfa_hip_seed_index_query", self._h, patterns._h, n, min_hits, gap, pad, max_hits,
+                   *[_ptr(out[key]) for key in SEED_KEYS], _ptr(out["overflow"]))
         return out
 
     def chain(self, patterns, n=4, min_hits=3, min_score=40, lookback=32, max_dist=5000, band=500, pad=64, max_anchors=16384):
@@ -1159,10 +1057,8 @@ class SeedIndex:
         cols = n if 1 <= n <= SEED_MAX_N else 1   # (out of range: the library refuses before it writes)
         out = {key: np.zeros((patterns.n, cols), np.int32) for key in CHAIN_KEYS}
         out["overflow"] = np.zeros(patterns.n, np.uint8)
-        rc = lib().wfa_hip_seed_index_chain(self._h, patterns._h, n, min_hits, min_score, lookback, max_dist, band, pad, max_anchors,
-                                            *[_ptr(out[key]) for key in CHAIN_KEYS], _ptr(out["overflow"]))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_seed_index_chain")
+        self._call("wfa_hip_seed_index_chain", self._h, patterns._h, n, min_hits, min_score, lookback, max_dist, band, pad, max_anchors,
+                   *[_ptr(out[key]) for key in CHAIN_KEYS], _ptr(out["overflow"]))
         return out
 
     def chain_stats(self):
@@ -1170,9 +1066,7 @@ class SeedIndex:
         if not self._h:
             raise ValueError("seed index is closed")
         ms, nbytes = ctypes.c_float(0), ctypes.c_int64(0)
-        rc = lib().wfa_hip_seed_index_chain_stats(self._h, ctypes.byref(ms), ctypes.byref(nbytes))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_seed_index_chain_stats")
+        self._call("wfa_hip_seed_index_chain_stats", self._h, ctypes.byref(ms), ctypes.byref(nbytes))
         return dict(kernel_ms=ms.value, workspace_bytes=nbytes.value)
 
     def stats(self):
@@ -1181,54 +1075,29 @@ class SeedIndex:
             raise ValueError("seed index is closed")
         pos, masked, nbytes = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
         bms, qms = ctypes.c_float(0), ctypes.c_float(0)
-        rc = lib().wfa_hip_seed_index_stats(self._h, ctypes.byref(pos), ctypes.byref(masked), ctypes.byref(nbytes), ctypes.byref(bms),
-                                            ctypes.byref(qms))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_seed_index_stats")
+        self._call("wfa_hip_seed_index_stats", self._h, ctypes.byref(pos), ctypes.byref(masked), ctypes.byref(nbytes), ctypes.byref(bms),
+                   ctypes.byref(qms))
         return dict(positions=pos.value, masked_kmers=masked.value, table_bytes=nbytes.value, build_ms=bms.value, query_ms=qms.value)
 
 
-class MultiAligner:
+class MultiAligner(_Handle):
     """One aligner per device of a node (wfa_hip_multi_t): a batch is sharded over them, results land in disjoint
-    slices of one set of arrays."""
+    slices of one set of arrays.  A handle of no aligner: it is created like one and keeps its own last error."""
+
+    _destroy = "wfa_hip_multi_destroy"
 
     def __init__(self, cfg, devices):
-        L = lib()
         self.devices = [int(d) for d in devices]
         arr = (ctypes.c_int * len(self.devices))(*self.devices)
-        self._h = L.wfa_hip_multi_create(ctypes.byref(cfg), arr, len(self.devices))
+        self._h = lib().wfa_hip_multi_create(ctypes.byref(cfg), arr, len(self.devices))
         if not self._h:
-            msg = L.wfa_hip_global_error().decode()
-            rc, vmsg = validate(cfg)
-            if rc == EINVAL:
-                raise ValueError(vmsg)
-            if rc == ENOTSUP:
-                raise NotImplementedError(vmsg)
-            raise NativeError(f"wfa_hip_multi_create failed: {msg}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().wfa_hip_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            _raise_config_refused(cfg, "wfa_hip_multi_create")
 
     def _raise(self, rc, what):
-        msg = lib().wfa_hip_multi_last_error(self._h).decode()
-        if rc == EINVAL:
-            raise ValueError(f"{what}: {msg}")
-        if rc == ENOTSUP:
-            raise NotImplementedError(f"{what}: {msg}")
-        raise NativeError(f"{what}: {msg}")
+        _raise_code(rc, what, lib().wfa_hip_multi_last_error(self._h).decode())
 
     def set_config(self, cfg):
-        rc = lib().wfa_hip_multi_set_config(self._h, ctypes.byref(cfg))
-        if rc != OK:
-            self._raise(rc, "wfa_hip_multi_set_config")
+        self._call("wfa_hip_multi_set_config", self._h, ctypes.byref(cfg))
 
     def align_batch(self, batch, want_cigar):
         if "packed" in batch:   # (ADVICE r03: the multi-device entry takes ASCII; 2-bit bytes would be read as letters outside ACGT)
@@ -1244,15 +1113,16 @@ class MultiAligner:
             clen = np.zeros(n, np.int32)
         else:
             cigar_off = ops = cbeg = clen = None
-        rc = lib().wfa_hip_multi_align_batch(self._h, n, _ptr(seqs), _ptr(p_off), _ptr(p_len), _ptr(t_off), _ptr(t_len),
-                                             _ptr(score), _ptr(status), _ptr(ops), _ptr(cigar_off), _ptr(cbeg), _ptr(clen))
-        if rc != OK:
-            self._raise(rc, "wfa_hip_multi_align_batch")
+        self._call("wfa_hip_multi_align_batch", self._h, n, _ptr(seqs), _ptr(p_off), _ptr(p_len), _ptr(t_off), _ptr(t_len),
+                   _ptr(score), _ptr(status), _ptr(ops), _ptr(cigar_off), _ptr(cbeg), _ptr(clen))
         return score, status, ((ops, cbeg, clen) if want_cigar else None)
 
 
-class ResidentBatch:
+class ResidentBatch(_Handle):
     """A batch kept in HBM (wfa_hip_batch_t): upload + 2-bit pack once, run many times."""
+
+    _destroy = "wfa_hip_batch_destroy"
+    _device_failure = "failed:"   # (a batch's create tells a device failure by the HIP_TRY form only, as it always did)
 
     def __init__(self, aligner, batch):
         seqs, p_off, p_len, t_off, t_len, n = _check_batch(batch)
@@ -1260,13 +1130,7 @@ class ResidentBatch:
         self.n = n
         self._p_len, self._t_len = p_len, t_len
         create = lib().wfa_hip_batch_create_packed2bits if "packed" in batch else lib().wfa_hip_batch_create
-        self._h = create(aligner._h, n, _ptr(seqs), _ptr(p_off), _ptr(p_len), _ptr(t_off), _ptr(t_len))
-        if not self._h:
-            msg = aligner.error()
-            if "failed:" in msg:
-                raise NativeError(f"wfa_hip_batch_create: {msg}")
-            raise ValueError(f"wfa_hip_batch_create: {msg}")
-        aligner._batches.add(self)
+        self._created(create(aligner._h, n, _ptr(seqs), _ptr(p_off), _ptr(p_len), _ptr(t_off), _ptr(t_len)), "wfa_hip_batch_create")
 
     @classmethod
     def indexed(cls, aligner, patterns, texts, i, j):
@@ -1289,13 +1153,8 @@ class ResidentBatch:
         # (the pairs' lengths, which size the op buffers of results(True), are looked up when first asked for: the library has
         # checked the indices by then)
         self._lens = (patterns.length, tset.length, i, j)
-        self._h = lib().wfa_hip_batch_create_indexed(aligner._h, patterns._h, texts._h if texts is not None else None, n, _ptr(i), _ptr(j))
-        if not self._h:
-            msg = aligner.error()
-            if "failed:" in msg:
-                raise NativeError(f"wfa_hip_batch_create_indexed: {msg}")
-            raise ValueError(f"wfa_hip_batch_create_indexed: {msg}")
-        aligner._batches.add(self)
+        h = lib().wfa_hip_batch_create_indexed(aligner._h, patterns._h, texts._h if texts is not None else None, n, _ptr(i), _ptr(j))
+        self._created(h, "wfa_hip_batch_create_indexed")
         return self
 
     @classmethod
@@ -1331,11 +1190,9 @@ class ResidentBatch:
         self.aligner = aligner
         self.n = n
         self._wins = (patterns.length, tset.length, arr)   # (the windows' lengths size the op buffers of results(True): on first use)
-        self._h = lib().wfa_hip_batch_create_windows(aligner._h, patterns._h, texts._h if texts is not None else None, n,
-                                                     *[_ptr(arr[k]) for k in ("i", "j", "p_start", "p_len", "t_start", "t_len", "reverse")])
-        if not self._h:
-            raise NativeError(f"wfa_hip_batch_create_windows: {aligner.error()}")
-        aligner._batches.add(self)
+        h = lib().wfa_hip_batch_create_windows(aligner._h, patterns._h, texts._h if texts is not None else None, n,
+                                               *[_ptr(arr[k]) for k in ("i", "j", "p_start", "p_len", "t_start", "t_len", "reverse")])
+        self._created(h, "wfa_hip_batch_create_windows", refused=NativeError)
         return self
 
     def __getattr__(self, name):
@@ -1352,26 +1209,11 @@ class ResidentBatch:
             return self.__dict__[name]
         raise AttributeError(name)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().wfa_hip_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def run(self, stream=None):
-        rc = lib().wfa_hip_batch_run(self._h, stream)
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_batch_run")
+        self._call("wfa_hip_batch_run", self._h, stream)
 
     def sync(self):
-        rc = lib().wfa_hip_batch_sync(self._h)
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_batch_sync")
+        self._call("wfa_hip_batch_sync", self._h)
 
     def results(self, want_cigar):
         n = self.n
@@ -1385,18 +1227,13 @@ class ResidentBatch:
             clen = np.zeros(n, np.int32)
         else:
             cigar_off = ops = cbeg = clen = None
-        rc = lib().wfa_hip_batch_results(self._h, _ptr(score), _ptr(status), _ptr(ops), _ptr(cigar_off),
-                                         _ptr(cbeg), _ptr(clen))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_batch_results")
+        self._call("wfa_hip_batch_results", self._h, _ptr(score), _ptr(status), _ptr(ops), _ptr(cigar_off), _ptr(cbeg), _ptr(clen))
         return score, status, ((ops, cbeg, clen) if want_cigar else None)
 
     def last_kernel(self):
         ms = ctypes.c_float(0)
         pairs = ctypes.c_int64(0)
-        rc = lib().wfa_hip_batch_last_kernel_ms(self._h, ctypes.byref(ms), ctypes.byref(pairs))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_batch_last_kernel_ms")
+        self._call("wfa_hip_batch_last_kernel_ms", self._h, ctypes.byref(ms), ctypes.byref(pairs))
         return ms.value, pairs.value
 
     def rle(self):
@@ -1408,12 +1245,10 @@ class ResidentBatch:
         locs = np.zeros((n, 4), np.int32)
         total = lib().wfa_hip_batch_rle_counts(self._h, _ptr(cnt), _ptr(locs))
         if total < 0:
-            self.aligner._raise(int(total), "wfa_hip_batch_rle_counts")
+            self._raise(int(total), "wfa_hip_batch_rle_counts")
         code = np.zeros(max(int(total), 1), np.uint8)
         rlen = np.zeros(max(int(total), 1), np.int32)
-        rc = lib().wfa_hip_batch_rle_runs(self._h, _ptr(code), _ptr(rlen))
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_batch_rle_runs")
+        self._call("wfa_hip_batch_rle_runs", self._h, _ptr(code), _ptr(rlen))
         off = np.zeros(n + 1, np.int64)
         np.cumsum(cnt, out=off[1:])
         return off, code[:total], rlen[:total], locs
@@ -1422,9 +1257,7 @@ class ResidentBatch:
         """wfa_hip_batch_summary: int32[n, 10] of the last scope=full run, reduced on the GPU — per pair the numbers of M, X, I and D
         ops, of I runs and of D runs, and the four ``locations``."""
         out = np.zeros((self.n, SUMMARY_COLS), np.int32)
-        rc = lib().wfa_hip_batch_summary(self._h, _ptr(out) if self.n else None)
-        if rc != OK:
-            self.aligner._raise(rc, "wfa_hip_batch_summary")
+        self._call("wfa_hip_batch_summary", self._h, _ptr(out) if self.n else None)
         return out
 
     def algorithmic_bytes(self):

@@ -325,6 +325,11 @@ class BatchResults:
                                int(self.status[i]))
 
 
+def _columns(rows, names):
+    """The columns of an (n, len(names)) array as a dict of contiguous arrays."""
+    return {name: np.ascontiguousarray(rows[:, c]) for c, name in enumerate(names)}
+
+
 def _summary_dict(rows):
     """The (n, 10) rows of ``ResidentBatch.summary()`` as the dict the ``summary=True`` forms return."""
     out = {name: np.ascontiguousarray(rows[:, k]) for k, name in enumerate(("M", "X", "I", "D", "I_runs", "D_runs"))}
@@ -340,7 +345,26 @@ def _need_full_for_summary(cfg):
 _CALL_LETTERS = np.frombuffer(b"ACGTN-N", np.uint8)   # (CALL_CODES as letters; deleted bases are dropped before the lookup)
 
 
-class Pileup:
+class _Closing:
+    """``close()`` and the context manager of an object that owns one native handle, kept under the attribute ``_OWNS`` names."""
+
+    _OWNS = None
+
+    def close(self):
+        handle = getattr(self, self._OWNS)
+        if handle is not None:
+            handle.close()
+            setattr(self, self._OWNS, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class Pileup(_Closing):
     """Per-base counts over the text sequences, kept on the GPU (``WavefrontAligner.pileup``).  ``score`` / ``status``: the listed
     pairs' results, in list order.  ``counts(j)``: int32 rows of the columns ``COLUMNS`` for text ``j`` — reads whose aligned base is
     A, C, G, T or another letter, reads that delete the base, reads that insert in front of it, reads that mismatch (these are also
@@ -351,6 +375,7 @@ class Pileup:
     COLUMNS = _native.PILEUP_COLUMNS
     CALL_CODES = _native.CALL_CODES
     SITE_COLUMNS = _native.SITE_COLUMNS
+    _OWNS = "_pileup"
 
     def __init__(self, native_pileup, score, status, aligner=None):
         self._pileup = native_pileup
@@ -453,25 +478,15 @@ class Pileup:
             seq, start, stop = self._range(p, j, start, stop)
             length = stop - start
         _, rows = self._with_texts(p, texts, min_depth, lambda t: p.sites(t, seq, start, length, int(min_depth), permille))
-        return {name: np.ascontiguousarray(rows[:, k]) for k, name in enumerate(self.SITE_COLUMNS)}
-
-    def close(self):
-        if self._pileup is not None:
-            self._pileup.close()
-            self._pileup = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
+        return _columns(rows, self.SITE_COLUMNS)
 
 
-class SequenceSet:
+class SequenceSet(_Closing):
     """Sequences kept on the GPU, uploaded and packed once (``WavefrontAligner.sequence_set``): pass it wherever ``score_matrix``,
     ``completed_pairs``, ``nearest`` and ``align_pairs`` take a list of sequences.  ``len()`` is the number of sequences; ``close()``
     (or leaving the ``with`` block) releases the device memory.  Results already returned stay valid."""
+
+    _OWNS = "_set"
 
     def __init__(self, aligner, native_set):
         self._aligner = aligner
@@ -481,18 +496,6 @@ class SequenceSet:
         if self._set is None:
             raise ValueError("sequence set is closed")
         return self._set.n
-
-    def close(self):
-        if self._set is not None:
-            self._set.close()
-            self._set = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 def _seed_param(name, value, lo, hi=None):
@@ -505,11 +508,13 @@ def _seed_param(name, value, lo, hi=None):
     return int(value)
 
 
-class SeedIndex:
+class SeedIndex(_Closing):
     """An exact-match k-mer index over text sequences, kept on the GPU (``WavefrontAligner.seed_index``): ``seeds(patterns)`` finds
     every read's best candidate windows on both strands, in the shape ``align_windows`` and ``pileup`` take.  ``stats()``:
     dict(positions=, masked_kmers=, table_bytes=, build_ms=, query_ms=).  The index takes 4^k * 4 bytes plus 8 bytes per indexed
     position until ``close()`` (or the end of the ``with`` block) and stays valid after the texts' set is closed."""
+
+    _OWNS = "_index"
 
     def __init__(self, aligner, native_index):
         self._aligner = aligner
@@ -613,16 +618,39 @@ class SeedIndex:
         st.update(chain_ms=ch["kernel_ms"], chain_workspace_bytes=ch["workspace_bytes"])
         return st
 
-    def close(self):
-        if self._index is not None:
-            self._index.close()
-            self._index = None
+
+class _Windows:
+    """One call's window list (``WavefrontAligner._windows``).  Made: the arguments are checked (ValueError, nothing is uploaded) —
+    ``arrays`` (i, j, pattern_start, pattern_len, text_start, text_len, reverse), ``wlen``, ``nreads`` (the patterns).  Entered: the
+    wildcard is pushed and the sets are open — ``pset``, ``tset`` (None: one set), ``text_set`` (the set ``j`` points into) and
+    ``run(**how)``.  Left: the sets this call uploaded are closed, a caller's ``SequenceSet`` stays open."""
+
+    def __init__(self, aligner, *window_args):
+        self._aligner = aligner
+        self._patterns, self._texts, self.arrays, self.wlen = aligner._window_lists(*window_args)
+        self.nreads = len(self._patterns)
+        self._mine, self._attached, self._keep = [], None, False
 
     def __enter__(self):
+        self._aligner._sync_wildcard()
+        sets, self._mine = self._aligner._open_sets(self._patterns, self._texts)
+        self.pset, self.text_set = sets[0], sets[-1]
+        self.tset = sets[-1] if self._texts is not None else None
         return self
 
-    def __exit__(self, *exc):
-        self.close()
+    def attach(self, handle, keep=False):
+        """``handle`` (a table, a placer) is closed when the body is left; ``keep``: only when it raises."""
+        self._attached, self._keep = handle, keep
+        return handle
+
+    def run(self, **how):
+        return self._aligner._run_windows(self.pset, self.tset, self.arrays, self.wlen, **how)
+
+    def __exit__(self, exc_type, *exc):
+        if self._attached is not None and not (self._keep and exc_type is None):
+            self._attached.close()
+        for s in self._mine:
+            s.close()
         return False
 
 
@@ -1028,27 +1056,9 @@ class WavefrontAligner:
         full = self._cfg.scope == 1
         score = np.zeros(npairs, np.int32)
         status = np.zeros(npairs, np.int32)
-        if summary or each is not None:
-            rows = np.zeros((npairs, _native.SUMMARY_COLS), np.int32) if summary else None
-            for lo, hi in zip(cuts[:-1], cuts[1:]):
-                rb = make(lo, hi)
-                try:
-                    rb.run()
-                    rb.sync()
-                    sc, st, _ = rb.results(False)
-                    score[lo:hi] = sc
-                    status[lo:hi] = st
-                    if summary:
-                        rows[lo:hi] = rb.summary()
-                    else:
-                        each(rb, lo, hi, sc, st)
-                finally:
-                    rb.close()
-            out = {"score": score, "status": status}
-            if summary:
-                out["summary"] = _summary_dict(rows)
-            return out
-        small = full and npairs <= 1024 and len(cuts) <= 2
+        strings = not summary and each is None   # op strings are wanted: as they are for a small list, run-length encoded otherwise
+        small = strings and full and npairs <= 1024 and len(cuts) <= 2
+        rows = np.zeros((npairs, _native.SUMMARY_COLS), np.int32) if summary else None
         ops_res, runs = None, []
         for lo, hi in zip(cuts[:-1], cuts[1:]):
             rb = make(lo, hi)
@@ -1058,13 +1068,21 @@ class WavefrontAligner:
                 sc, st, cig = rb.results(small)
                 score[lo:hi] = sc
                 status[lo:hi] = st
-                if small:
+                if summary:
+                    rows[lo:hi] = rb.summary()
+                elif each is not None:
+                    each(rb, lo, hi, sc, st)
+                elif small:
                     ops_res = cig
                 elif full:
                     runs.append(rb.rle()[:3])
             finally:
                 rb.close()
         out = {"score": score, "status": status}
+        if summary:
+            out["summary"] = _summary_dict(rows)
+        if not strings:
+            return out
         if small or (full and npairs == 0):
             ops, cbeg, clen = ops_res if ops_res is not None else (np.zeros(1, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.int32))
             out["cigar_ops"] = _OpsSequence(ops, cbeg, clen, "ops")
@@ -1173,6 +1191,35 @@ class WavefrontAligner:
             pset, tset, i[lo:hi], j[lo:hi], cut(ps, lo, hi), cut(pl, lo, hi),
             cut(ts, lo, hi), cut(tl, lo, hi), cut(rev, lo, hi)), **how)
 
+    def _windows(self, *window_args):
+        """The session of one call over a window list: ``_Windows`` of (patterns, texts, i, j, pattern_start, pattern_len, text_start,
+        text_len, reverse)."""
+        return _Windows(self, *window_args)
+
+    def _placement(self, min_score, full_gap, **pair_only):
+        """``(min_score, full_gap)`` of ``place_windows`` / ``place_pairs`` as the ints the library takes, defaults filled in, after
+        the check that they (and the integers only ``place_pairs`` has) are integers at all."""
+        for name, v in dict(min_score=min_score, full_gap=full_gap, **pair_only).items():
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise ValueError(f"{name} must be an integer{'' if name.endswith('insert') else ' or None'}, got {v!r}")
+        if min_score is not None and not -2**31 <= int(min_score) < 2**31:
+            raise ValueError(f"min_score = {min_score} does not fit 32 bits")
+        if full_gap is None:
+            full_gap = 6 * int(self._cfg.mismatch) if self._cfg.distance >= 2 else 6
+        if not 1 <= int(full_gap) < 2**31:
+            raise ValueError(f"full_gap = {full_gap} is out of range (at least 1)")
+        return _native.INT32_MIN if min_score is None else int(min_score), int(full_gap)
+
+    @staticmethod
+    def _hits_into(placer, arrays):
+        """The ``each`` of ``_run_lists`` that adds every chunk's pairs to ``placer`` as hits of the listed windows."""
+        ii, jj, ts, rev = arrays[0], arrays[1], arrays[4], arrays[6]
+
+        def add(rb, lo, hi, score, status):
+            placer.add(rb, ii[lo:hi], jj[lo:hi], None if ts is None else ts[lo:hi], None if rev is None else rev[lo:hi])
+
+        return add
+
     def align_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None,
                       text_start=None, text_len=None, reverse=None, summary=False):
         """Align windows of resident sequences on the GPU: pair q is bases [pattern_start[q], + pattern_len[q]) of patterns[i[q]],
@@ -1189,14 +1236,8 @@ class WavefrontAligner:
         ``summary=True`` (scope full only): dict(score=, status=, summary=) as ``align_batch`` describes, no op strings."""
         if summary:
             _need_full_for_summary(self._cfg)
-        patterns, texts, arrays, wlen = self._window_lists(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
-        self._sync_wildcard()
-        sets, mine = self._open_sets(patterns, texts)
-        try:
-            return self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, summary=summary)
-        finally:
-            for s in mine:
-                s.close()
+        with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
+            return w.run(summary=summary)
 
     def pileup(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
                text_len=None, reverse=None, min_score=None):
@@ -1213,27 +1254,16 @@ class WavefrontAligner:
             raise ValueError("pileup needs scope='full'")
         if min_score is not None and (isinstance(min_score, bool) or not isinstance(min_score, (int, np.integer))):
             raise ValueError(f"min_score must be an integer or None, got {min_score!r}")
-        patterns, texts, arrays, wlen = self._window_lists(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
-        jj, ts = arrays[1], arrays[4]
-        self._sync_wildcard()
-        sets, mine = self._open_sets(patterns, texts)
-        table = None
-        try:
-            table = self._native.pileup(sets[-1])
+        with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
+            jj, ts = w.arrays[1], w.arrays[4]
+            table = w.attach(self._native.pileup(w.text_set), keep=True)
 
             def add(rb, lo, hi, score, status):
                 keep = None if min_score is None else (score >= int(min_score))
                 table.add(rb, jj[lo:hi], None if ts is None else ts[lo:hi], keep)
 
-            out = self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, each=add)
-            res = Pileup(table, out["score"], out["status"], self)
-            table = None
-            return res
-        finally:
-            if table is not None:
-                table.close()
-            for s in mine:
-                s.close()
+            out = w.run(each=add)
+            return Pileup(table, out["score"], out["status"], self)
 
     def place_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
                       text_len=None, reverse=None, min_score=None, full_gap=None):
@@ -1253,36 +1283,13 @@ class WavefrontAligner:
         a runner-up), mapq, hits (eligible), ties (runner-ups that equal the primary's score), text_start, text_end (the primary's
         interval on its text).  Neither scores nor locations are grouped on the host: 32 bytes per read and a byte per hit come
         back (csrc/wfa_place.hpp).  With ``devices=[...]`` the first device runs it."""
-        for name, v in (("min_score", min_score), ("full_gap", full_gap)):
-            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
-                raise ValueError(f"{name} must be an integer or None, got {v!r}")
-        if min_score is not None and not -2**31 <= int(min_score) < 2**31:
-            raise ValueError(f"min_score = {min_score} does not fit 32 bits")
-        if full_gap is None:
-            full_gap = 6 * int(self._cfg.mismatch) if self._cfg.distance >= 2 else 6
-        if not 1 <= int(full_gap) < 2**31:
-            raise ValueError(f"full_gap = {full_gap} is out of range (at least 1)")
-        patterns, texts, arrays, wlen = self._window_lists(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
-        ii, jj, ts, rev = arrays[0], arrays[1], arrays[4], arrays[6]
-        self._sync_wildcard()
-        sets, mine = self._open_sets(patterns, texts)
-        placer = None
-        try:
-            placer = self._native.placer(len(patterns))
-
-            def add(rb, lo, hi, score, status):
-                placer.add(rb, ii[lo:hi], jj[lo:hi], None if ts is None else ts[lo:hi], None if rev is None else rev[lo:hi])
-
-            out = self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, each=add)
-            rows, flags = placer.run(_native.INT32_MIN if min_score is None else int(min_score), int(full_gap))
-            out["flag"] = flags
-            out["reads"] = {name: np.ascontiguousarray(rows[:, c]) for c, name in enumerate(_native.PLACE_COLUMNS)}
+        min_score, full_gap = self._placement(min_score, full_gap)
+        with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
+            placer = w.attach(self._native.placer(w.nreads))
+            out = w.run(each=self._hits_into(placer, w.arrays))
+            rows, out["flag"] = placer.run(min_score, full_gap)
+            out["reads"] = _columns(rows, _native.PLACE_COLUMNS)
             return out
-        finally:
-            if placer is not None:
-                placer.close()
-            for s in mine:
-                s.close()
 
     def place_pairs(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
                     text_len=None, reverse=None, mates=None, min_insert=0, max_insert=1000, unpaired=None, min_score=None,
@@ -1324,16 +1331,7 @@ class WavefrontAligner:
         and ``rescue`` is added: dict(i=, j=, text_start=, text_len=, reverse=, fragment=, anchor=) of int32 arrays, possibly
         empty, hit ``n0 + q`` being window ``q`` of it (``anchor``: the hit number of the anchor).  ``rescue=False`` returns exactly
         the keys above."""
-        for name, v in (("min_score", min_score), ("full_gap", full_gap), ("min_insert", min_insert), ("max_insert", max_insert),
-                        ("unpaired", unpaired)):
-            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
-                raise ValueError(f"{name} must be an integer{'' if name.endswith('insert') else ' or None'}, got {v!r}")
-        if min_score is not None and not -2**31 <= int(min_score) < 2**31:
-            raise ValueError(f"min_score = {min_score} does not fit 32 bits")
-        if full_gap is None:
-            full_gap = 6 * int(self._cfg.mismatch) if self._cfg.distance >= 2 else 6
-        if not 1 <= int(full_gap) < 2**31:
-            raise ValueError(f"full_gap = {full_gap} is out of range (at least 1)")
+        min_score, full_gap = self._placement(min_score, full_gap, min_insert=min_insert, max_insert=max_insert, unpaired=unpaired)
         if min_insert is None or max_insert is None or not 0 <= int(min_insert) <= int(max_insert) < 2**31:
             raise ValueError(f"min_insert = {min_insert}, max_insert = {max_insert} are out of range (0 <= min_insert <= max_insert)")
         if unpaired is None:
@@ -1359,8 +1357,8 @@ class WavefrontAligner:
                              "is as wide as the insert range")
         if rescue and self._cfg.span != 1:
             raise ValueError("rescue needs span='ends-free': the rescued mate lies somewhere inside its window")
-        patterns, texts, arrays, wlen = self._window_lists(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
-        nreads = len(patterns)
+        w = self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
+        nreads = w.nreads
         if mates is None:
             if nreads % 2:
                 raise ValueError(f"mates=None takes the reads as interleaved pairs: {nreads} reads are an odd number")
@@ -1382,54 +1380,37 @@ class WavefrontAligner:
             if again.size:
                 f = int(again.min()) // 2
                 raise ValueError(f"mates[{f}] = ({m[f, 0]}, {m[f, 1]}): read {flat[again.min()]} belongs to an earlier fragment")
-        ii, jj, ts, rev = arrays[0], arrays[1], arrays[4], arrays[6]
-        self._sync_wildcard()
-        sets, mine = self._open_sets(patterns, texts)
-        placer = None
-        try:
-            placer = self._native.placer(nreads)
-
-            def add(rb, lo, hi, score, status):
-                placer.add(rb, ii[lo:hi], jj[lo:hi], None if ts is None else ts[lo:hi], None if rev is None else rev[lo:hi])
-
-            out = self._run_windows(sets[0], sets[-1] if texts is not None else None, arrays, wlen, each=add)
-            how = (_native.INT32_MIN if min_score is None else int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired))
-            n0 = ii.shape[0]
+        with w:
+            placer = w.attach(self._native.placer(nreads))
+            out = w.run(each=self._hits_into(placer, w.arrays))
+            how = (min_score, full_gap, int(min_insert), int(max_insert), int(unpaired))
+            n0 = w.arrays[0].shape[0]
             if rescue:
-                _, found = placer.rescue(sets[0], sets[-1], mates, *how, pad=int(rescue_pad), min_len=free, anchor_mapq=int(rescue_mapq))
+                _, found = placer.rescue(w.pset, w.text_set, mates, *how, pad=int(rescue_pad), min_len=free, anchor_mapq=int(rescue_mapq))
                 ri, rj, rts, rtl, rrev, rfrag, ranchor = (np.ascontiguousarray(found[:, c]) for c in range(7))
                 if found.shape[0]:
                     rrev8 = rrev.astype(np.uint8)
-                    lens = [sets[0].length[ri].astype(np.int64), rtl.astype(np.int64)]
-
-                    def add_rescued(rb, lo, hi, score, status):
-                        placer.add(rb, ri[lo:hi], rj[lo:hi], rts[lo:hi], rrev8[lo:hi])
-
+                    rescued = (ri, rj, None, None, rts, rtl, rrev8)
+                    lens = [w.pset.length[ri].astype(np.int64), rtl.astype(np.int64)]
                     before = (self.text_begin_free, self.text_end_free)
                     try:
                         self.text_begin_free = free
                         self.text_end_free = free
-                        more = self._run_windows(sets[0], sets[-1] if texts is not None else None, (ri, rj, None, None, rts, rtl, rrev8),
-                                                 lens, each=add_rescued)
+                        more = self._run_windows(w.pset, w.tset, rescued, lens, each=self._hits_into(placer, rescued))
                     finally:
                         self.text_begin_free, self.text_end_free = before
                     out["score"] = np.concatenate([out["score"], more["score"]])
                     out["status"] = np.concatenate([out["status"], more["status"]])
             rows, flags, pair_rows, pair_flags = placer.run_pairs(mates, *how)
             out["flag"] = flags
-            out["reads"] = {name: np.ascontiguousarray(rows[:, c]) for c, name in enumerate(_native.PLACE_COLUMNS)}
+            out["reads"] = _columns(rows, _native.PLACE_COLUMNS)
             out["pair_flag"] = pair_flags
-            out["pairs"] = {name: np.ascontiguousarray(pair_rows[:, c]) for c, name in enumerate(_native.PAIR_COLUMNS)}
+            out["pairs"] = _columns(pair_rows, _native.PAIR_COLUMNS)
             if rescue:
                 pairs = out["pairs"]
                 pairs["rescued"] = ((pairs["proper"] == 1) & ((pairs["hit1"] >= n0) | (pairs["hit2"] >= n0))).astype(np.int32)
                 out["rescue"] = dict(i=ri, j=rj, text_start=rts, text_len=rtl, reverse=rrev, fragment=rfrag, anchor=ranchor)
             return out
-        finally:
-            if placer is not None:
-                placer.close()
-            for s in mine:
-                s.close()
 
     def score_matrix(self, patterns, texts=None):
         """Score every pattern against every text on the GPU: returns ``(score, status)``, int32 arrays of shape (M, N).
