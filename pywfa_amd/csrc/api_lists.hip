@@ -56,29 +56,23 @@ struct IndexedPairs {
     p->bytes = all_bytes || P->h_flag[a] || T->h_flag[bq];
   }
   __attribute__((always_inline)) int check(int64_t q, bool all_bytes, ListPair* p) const { get(q, all_bytes, p); return 0; }   // (indices in range: nothing else to refuse)
-  std::string refusal(int, int64_t) const { return std::string(); }
+  int refuse(wfa_hip_aligner* al, int, int64_t) const { return fail_inval(al, "%s", ""); }
   // the sets' words and 64 zero words, only when a listed pair points into them
   uint64_t table_words(bool any_long) const { return any_long ? P->nwords + (same ? 0 : T->nwords) + 64 : 0; }
   // byte pairs: the sets' bytes, the text set's behind the pattern set's
   int byte_store(wfa_hip_aligner* al, wfa_hip_batch* b, const ListPlan&) const {
     HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)(P->nbytes + (same ? 0 : T->nbytes) + 64)));
-    HIP_TRY(al, hipMemcpyAsync(b->d_bytes, P->d_bytes, (size_t)P->nbytes + (same ? 64 : 0), hipMemcpyDeviceToDevice, al->stream));
-    if (!same) HIP_TRY(al, hipMemcpyAsync(b->d_bytes + P->nbytes, T->d_bytes, (size_t)T->nbytes + 64, hipMemcpyDeviceToDevice, al->stream));
-    return WFA_HIP_OK;
+    return copy_sets(al, b->d_bytes, P->d_bytes, (size_t)P->nbytes, T->d_bytes, (size_t)T->nbytes, same, 64);
   }
-  int generate(wfa_hip_aligner* al, wfa_hip_batch* b, CrossScratch& sc, const ListPlan& plan) const {
+  int generate(wfa_hip_aligner* al, wfa_hip_batch* b, StreamScratch& sc, const ListPlan& plan) const {
     const int64_t n = b->n;
     if (plan.any_long) {
-      HIP_TRY(al, hipMemcpyAsync(b->d_words, P->d_words, (size_t)P->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
-      if (!same) HIP_TRY(al, hipMemcpyAsync(b->d_words + P->nwords, T->d_words, (size_t)T->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
+      if (copy_sets(al, b->d_words, P->d_words, (size_t)P->nwords, T->d_words, (size_t)T->nwords, same, 0)) return WFA_HIP_EDEVICE;
       HIP_TRY(al, hipMemsetAsync(b->d_words + (plan.table_words - 64), 0, 64 * sizeof(uint32_t), al->stream));
     }
     int32_t *d_i = nullptr, *d_j = nullptr;
     uint32_t* d_chunk = nullptr;
-    if (sc.alloc(&d_i, (size_t)n) || sc.alloc(&d_j, (size_t)n) || sc.alloc(&d_chunk, plan.chunk_base.size())) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_i, i, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(d_j, j, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(d_chunk, plan.chunk_base.data(), plan.chunk_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
+    if (sc.upload(&d_i, i, (size_t)n) || sc.upload(&d_j, j, (size_t)n) || sc.upload(&d_chunk, plan.chunk_base.data(), plan.chunk_base.size())) return WFA_HIP_EDEVICE;
     wfa::PairsGenArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.p_words = P->d_words; ga.p_woff = P->d_woff; ga.p_len = P->d_len; ga.p_boff = P->d_boff; ga.p_flag = P->d_flag;
@@ -134,15 +128,13 @@ struct WindowPairs {
     const Win w = window(q, P->h_len[(size_t)i[q]], T->h_len[(size_t)j[q]]);
     fill(p, (int)w.pl, (int)w.tl, (opt[(size_t)q] & WFA_WIN_BYTES) != 0);
   }
-  std::string refusal(int err, int64_t q) const {
+  int refuse(wfa_hip_aligner* al, int err, int64_t q) const {
     const int64_t pseq = P->h_len[(size_t)i[q]], tseq = T->h_len[(size_t)j[q]];
     const Win w = window(q, pseq, tseq);
-    char buf[320];
-    snprintf(buf, sizeof(buf), "%s at position %lld of the pair list: pattern window [%lld, %lld + %lld) of sequence %d (%lld bases), "
-             "text window [%lld, %lld + %lld) of sequence %d (%lld bases)", err == 2 ? "negative start or length" : "window out of range",
-             (long long)q, (long long)w.ps, (long long)w.ps, (long long)w.pl, (int)i[q], (long long)pseq,
-             (long long)w.ts, (long long)w.ts, (long long)w.tl, (int)j[q], (long long)tseq);
-    return buf;
+    return fail_inval(al, "%s at position %lld of the pair list: pattern window [%lld, %lld + %lld) of sequence %d (%lld bases), "
+                      "text window [%lld, %lld + %lld) of sequence %d (%lld bases)", err == 2 ? "negative start or length" : "window out of range",
+                      (long long)q, (long long)w.ps, (long long)w.ps, (long long)w.pl, (int)i[q], (long long)pseq,
+                      (long long)w.ts, (long long)w.ts, (long long)w.tl, (int)j[q], (long long)tseq);
   }
   uint64_t table_words(bool) const { return 0; }
   // byte pairs: their byte slots and 64 zero bytes
@@ -151,28 +143,18 @@ struct WindowPairs {
     HIP_TRY(al, hipMemsetAsync(b->d_bytes + plan.slot_bytes, 0, 64, al->stream));
     return WFA_HIP_OK;
   }
-  int generate(wfa_hip_aligner* al, wfa_hip_batch* b, CrossScratch& sc, const ListPlan& plan) const {
+  int generate(wfa_hip_aligner* al, wfa_hip_batch* b, StreamScratch& sc, const ListPlan& plan) const {
     const int64_t n = b->n;
     int32_t* d_arr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     uint8_t* d_opt = nullptr;
     uint32_t* d_chunk = nullptr;
     int64_t* d_bchunk = nullptr;
-    if (plan.lists) {
-      if (sc.alloc(&d_bchunk, plan.chunk_bbase.size())) return WFA_HIP_EDEVICE;
-      HIP_TRY(al, hipMemcpyAsync(d_bchunk, plan.chunk_bbase.data(), plan.chunk_bbase.size() * sizeof(int64_t), hipMemcpyHostToDevice, al->stream));
-    }
+    if (plan.lists && sc.upload(&d_bchunk, plan.chunk_bbase.data(), plan.chunk_bbase.size())) return WFA_HIP_EDEVICE;
     const int32_t* h_arr[6] = {i, j, p_start, p_len, t_start, t_len};
-    for (int k = 0; k < 6; ++k) {
-      if (!h_arr[k]) continue;
-      if (sc.alloc(&d_arr[k], (size_t)n)) return WFA_HIP_EDEVICE;
-      HIP_TRY(al, hipMemcpyAsync(d_arr[k], h_arr[k], (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    }
-    if (plan.any_opt) {
-      if (sc.alloc(&d_opt, (size_t)n)) return WFA_HIP_EDEVICE;
-      HIP_TRY(al, hipMemcpyAsync(d_opt, opt.data(), (size_t)n, hipMemcpyHostToDevice, al->stream));
-    }
-    if (sc.alloc(&d_chunk, plan.chunk_base.size())) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_chunk, plan.chunk_base.data(), plan.chunk_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, al->stream));
+    for (int k = 0; k < 6; ++k)
+      if (sc.upload_opt(&d_arr[k], h_arr[k], (size_t)n)) return WFA_HIP_EDEVICE;
+    if (plan.any_opt && sc.upload(&d_opt, opt.data(), (size_t)n)) return WFA_HIP_EDEVICE;
+    if (sc.upload(&d_chunk, plan.chunk_base.data(), plan.chunk_base.size())) return WFA_HIP_EDEVICE;
     wfa::WindowsGenArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.p_words = P->d_words; ga.p_woff = P->d_woff; ga.p_len = P->d_len; ga.p_boff = P->d_boff; ga.p_bytes = P->d_bytes;
@@ -241,14 +223,11 @@ static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, De
   std::vector<int64_t> obase((size_t)nthr), bbase((size_t)nthr), sbase((size_t)nthr);
   for (int t = 0; t < nthr; ++t) {
     const Part& pt = parts[(size_t)t];
-    if (pt.err == 1) {
-      char buf[200];
-      snprintf(buf, sizeof(buf), "index out of range at position %lld of the pair list: (%d, %d) over sets of %lld and %lld sequences",
-               (long long)pt.bad, (int)D.i[pt.bad], (int)D.j[pt.bad], (long long)np_set, (long long)nt_set);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
-    if (pt.err == PART_ENDS_FREE) { al->err = part_error_message(pt.err); return WFA_HIP_EINVAL; }
-    if (pt.err) { al->err = D.refusal(pt.err, pt.bad); return WFA_HIP_EINVAL; }
+    if (pt.err == 1)
+      return fail_inval(al, "index out of range at position %lld of the pair list: (%d, %d) over sets of %lld and %lld sequences",
+                        (long long)pt.bad, (int)D.i[pt.bad], (int)D.j[pt.bad], (long long)np_set, (long long)nt_set);
+    if (pt.err == PART_ENDS_FREE) return fail_inval(al, "%s", part_error_message(pt.err));
+    if (pt.err) return D.refuse(al, pt.err, pt.bad);
     wbase[(size_t)t] = slot_words; obase[(size_t)t] = b->ops_bytes; bbase[(size_t)t] = nbytes; sbase[(size_t)t] = slot_bytes;
     slot_words += pt.words; nbytes += pt.nbytes; slot_bytes += pt.slot_bytes;
     max_gen = std::max(max_gen, pt.max_gen); any_long |= pt.any_long; any_opt |= pt.any_opt;
@@ -257,7 +236,7 @@ static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, De
   }
   // the word table: what the descriptor puts in front, the slots, 64 zero words
   const uint64_t table_words = D.table_words(any_long);
-  if (table_words + slot_words + 64 > 0xFFFFFFF0ull) { al->err = Desc::too_large; return WFA_HIP_EINVAL; }
+  if (table_words + slot_words + 64 > 0xFFFFFFF0ull) return fail_inval(al, "%s", Desc::too_large);
   const bool lists = nbytes > 0;
   const int64_t chunks = (n + WFA_PAIRS_CHUNK - 1) / WFA_PAIRS_CHUNK;
   std::vector<uint32_t> chunk_base((size_t)std::max<int64_t>(chunks, 1), (uint32_t)table_words);
@@ -289,7 +268,7 @@ static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, De
     }
   };
   run_parts(nthr, nthr, pass2);
-  CrossScratch sc{al};   // (declared behind the host tables above: it waits for the stream before they go)
+  StreamScratch sc{al};   // (declared behind the host tables above: it waits for the stream before they go)
   const size_t nn = (size_t)std::max<int64_t>(n, 1);
   { const int arc = batch_alloc_common(al, b, table_words + slot_words + 64, 64); if (arc != WFA_HIP_OK) return arc; }
   b->n_bytes = (uint32_t)nbytes;
@@ -315,25 +294,15 @@ static int batch_build_list(wfa_hip_aligner* al, wfa_hip_batch* b, int64_t n, De
 // reason in al->err and g_error.  *texts == nullptr: one set against itself.
 static wfa_hip_batch* list_batch_new(wfa_hip_aligner* al, const wfa_hip_seqset* patterns, const wfa_hip_seqset** texts,
                                      int64_t npairs, const int32_t* i, const int32_t* j) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
+  if (!al) return fail_create(al, "null aligner");
   if (!*texts) *texts = patterns;
-  if (!patterns || patterns->al != al || (*texts)->al != al) { al->err = "sequence set of another aligner"; g_error = al->err; return nullptr; }
-  if (patterns->wildcard != al->cfg.wildcard || (*texts)->wildcard != al->cfg.wildcard) {
-    al->err = "sequence set packed under another wildcard: create it again"; g_error = al->err; return nullptr;
-  }
-  if (npairs < 0 || npairs > 0x7FFFFFF0ll || (npairs > 0 && (!i || !j))) { al->err = "invalid pair list arguments"; g_error = al->err; return nullptr; }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  if (!patterns || patterns->al != al || (*texts)->al != al) return fail_create(al, "sequence set of another aligner");
+  if (patterns->wildcard != al->cfg.wildcard || (*texts)->wildcard != al->cfg.wildcard)
+    return fail_create(al, "sequence set packed under another wildcard: create it again");
+  if (npairs < 0 || npairs > 0x7FFFFFF0ll || (npairs > 0 && (!i || !j))) return fail_create(al, "invalid pair list arguments");
+  if (!create_begin(al)) return nullptr;
   mailbox_release(al);   // (the resident one-pair kernel: batches take the device)
-  wfa_hip_batch* b = batch_new(al);
-  return b;
-}
-
-// ... and what they do with the build's outcome
-static wfa_hip_batch* list_batch_done(wfa_hip_aligner* al, wfa_hip_batch* b, int rc) {
-  if (rc == WFA_HIP_OK) return b;
-  g_error = al->err;
-  batch_free(b);
-  return nullptr;
+  return batch_new(al);   // (the core's own adopt step)
 }
 
 extern "C" wfa_hip_batch_t* wfa_hip_batch_create_indexed(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts,
@@ -342,7 +311,7 @@ extern "C" wfa_hip_batch_t* wfa_hip_batch_create_indexed(wfa_hip_aligner_t* al, 
   wfa_hip_batch* b = list_batch_new(al, patterns, &texts, npairs, i, j);
   if (!b) return nullptr;
   IndexedPairs D{patterns, texts, same, i, j};
-  return list_batch_done(al, b, batch_build_list(al, b, npairs, D));
+  return create_done(al, b, batch_build_list(al, b, npairs, D), batch_free);
 }
 
 extern "C" int wfa_hip_window_2bit(const uint32_t* words, int64_t start, int32_t len, int reverse, uint32_t* out) {
@@ -365,5 +334,5 @@ extern "C" wfa_hip_batch_t* wfa_hip_batch_create_windows(wfa_hip_aligner_t* al, 
   wfa_hip_batch* b = list_batch_new(al, patterns, &texts, npairs, i, j);
   if (!b) return nullptr;
   WindowPairs D{patterns, texts, i, j, p_start, p_len, t_start, t_len, reverse, std::vector<uint8_t>((size_t)npairs, 0)};
-  return list_batch_done(al, b, batch_build_list(al, b, npairs, D));
+  return create_done(al, b, batch_build_list(al, b, npairs, D), batch_free);
 }

@@ -22,8 +22,7 @@ extern "C" void wfa_hip_pileup_destroy(wfa_hip_pileup_t* p) {
   (void)hipSetDevice(al->device);
   if (p->d_table) (void)hipFree(p->d_table);
   pool_release(al, p->d_off); pool_release(al, p->d_len);
-  delete p;
-  aligner_release_ref(al);
+  destroy_end(p);
 }
 
 static int pileup_build(wfa_hip_aligner* al, wfa_hip_pileup* p, const wfa_hip_seqset_t* T) {
@@ -33,14 +32,8 @@ static int pileup_build(wfa_hip_aligner* al, wfa_hip_pileup* p, const wfa_hip_se
   for (int64_t k = 0; k < T->n; ++k) p->h_off[(size_t)k + 1] = p->h_off[(size_t)k] + T->h_len[(size_t)k];
   p->total = p->h_off[(size_t)T->n];
   const size_t bytes = (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t);
-  if (hipMalloc((void**)&p->d_table, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    p->d_table = nullptr;
-    char buf[160];
-    snprintf(buf, sizeof(buf), "pileup table: hipMalloc of %zu bytes failed (32 bytes per text base, %lld bases)", bytes, (long long)p->total);
-    al->err = buf;
-    return WFA_HIP_EDEVICE;
-  }
+  if (hipMalloc((void**)&p->d_table, bytes) != hipSuccess)
+    return fail_alloc(al, (void**)&p->d_table, "pileup table: hipMalloc of %zu bytes failed (32 bytes per text base, %lld bases)", bytes, (long long)p->total);
   const size_t nn = (size_t)std::max<int64_t>(T->n, 1);
   HIP_TRY(al, pool_alloc(al, (void**)&p->d_off, nn * sizeof(int64_t)));
   HIP_TRY(al, pool_alloc(al, (void**)&p->d_len, nn * sizeof(int32_t)));
@@ -54,14 +47,11 @@ static int pileup_build(wfa_hip_aligner* al, wfa_hip_pileup* p, const wfa_hip_se
 }
 
 extern "C" wfa_hip_pileup_t* wfa_hip_pileup_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  if (!texts || texts->al != al) { al->err = "sequence set of another aligner"; g_error = al->err; return nullptr; }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
-  wfa_hip_pileup* p = new wfa_hip_pileup();
-  p->al = al;
-  al->live_batches += 1;
-  if (pileup_build(al, p, texts) != WFA_HIP_OK) { g_error = al->err; wfa_hip_pileup_destroy(p); return nullptr; }
-  return p;
+  if (!al) return fail_create(al, "null aligner");
+  if (!texts || texts->al != al) return fail_create(al, "sequence set of another aligner");
+  if (!create_begin(al)) return nullptr;
+  wfa_hip_pileup* p = create_adopt(al, new wfa_hip_pileup());
+  return create_done(al, p, pileup_build(al, p, texts), wfa_hip_pileup_destroy);
 }
 
 extern "C" int wfa_hip_pileup_clear(wfa_hip_pileup_t* p) {
@@ -76,75 +66,51 @@ extern "C" int wfa_hip_pileup_clear(wfa_hip_pileup_t* p) {
 extern "C" int wfa_hip_pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
-  if (!b) { al->err = "pileup: null batch"; return WFA_HIP_EINVAL; }
-  if (b->al != al) { al->err = "pileup: batch of another aligner"; return WFA_HIP_EINVAL; }
-  if (b->cfg.scope != WFA_SCOPE_FULL) { al->err = "pileup needs scope=full"; return WFA_HIP_EINVAL; }
-  if (!b->ran) { al->err = "pileup needs a finished run of the batch"; return WFA_HIP_EINVAL; }
+  int rc = batch_of(al, b, "pileup", true);
+  if (rc != WFA_HIP_OK) return rc;
   const int64_t n = b->n;
-  if (n > 0 && !j) { al->err = "pileup: the text indices are missing"; return WFA_HIP_EINVAL; }
+  if (n > 0 && !j) return fail_inval(al, "pileup: the text indices are missing");
   for (int64_t q = 0; q < n; ++q) {
-    char buf[240];
-    if (j[q] < 0 || j[q] >= p->nseq) {
-      snprintf(buf, sizeof(buf), "pileup: text index out of range at position %lld of the pair list: j = %d over a set of %lld sequences",
-               (long long)q, (int)j[q], (long long)p->nseq);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
+    if (j[q] < 0 || j[q] >= p->nseq)
+      return fail_inval(al, "pileup: text index out of range at position %lld of the pair list: j = %d over a set of %lld sequences",
+                        (long long)q, (int)j[q], (long long)p->nseq);
     const int64_t ts = t_start ? t_start[q] : 0, tl = b->h_tlen[(size_t)q], have = p->h_len[(size_t)j[q]];
-    if (ts < 0) {
-      snprintf(buf, sizeof(buf), "pileup: negative text start at position %lld of the pair list: t_start = %lld", (long long)q, (long long)ts);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
-    if (ts + tl > have) {
-      snprintf(buf, sizeof(buf), "pileup: text window out of range at position %lld of the pair list: [%lld, %lld + %lld) of sequence %d (%lld bases)",
-               (long long)q, (long long)ts, (long long)ts, (long long)tl, (int)j[q], (long long)have);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
+    if (ts < 0) return fail_inval(al, "pileup: negative text start at position %lld of the pair list: t_start = %lld", (long long)q, (long long)ts);
+    if (ts + tl > have)
+      return fail_inval(al, "pileup: text window out of range at position %lld of the pair list: [%lld, %lld + %lld) of sequence %d (%lld bases)",
+                        (long long)q, (long long)ts, (long long)ts, (long long)tl, (int)j[q], (long long)have);
   }
-  const int rc = wfa_hip_batch_sync(b);
+  rc = wfa_hip_batch_sync(b);
   if (rc != WFA_HIP_OK) return rc;
   if (n == 0) return WFA_HIP_OK;
   HIP_TRY(al, hipSetDevice(al->device));
-  CrossScratch sc{al};   // (waits for the stream before the blocks go back)
+  StreamScratch sc{al};   // (waits for the stream before the blocks go back)
   int32_t *d_j = nullptr, *d_ts = nullptr;
   uint8_t* d_keep = nullptr;
-  if (sc.alloc(&d_j, (size_t)n)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipMemcpyAsync(d_j, j, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  if (t_start) {
-    if (sc.alloc(&d_ts, (size_t)n)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_ts, t_start, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  }
-  if (keep) {
-    if (sc.alloc(&d_keep, (size_t)n)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_keep, keep, (size_t)n, hipMemcpyHostToDevice, al->stream));
-  }
+  if (sc.upload(&d_j, j, (size_t)n) || sc.upload_opt(&d_ts, t_start, (size_t)n) || sc.upload_opt(&d_keep, keep, (size_t)n)) return WFA_HIP_EDEVICE;
   wfa::PileupArgs a;
   memset(&a, 0, sizeof(a));
   a.ops = b->d_ops; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len; a.status = b->d_status;
   a.meta = b->d_meta; a.words = b->d_words; a.bytes = b->d_bytes; a.pboff = b->d_pboff; a.flags = b->d_flags;
   a.npairs = n; a.j = d_j; a.t_start = d_ts; a.keep = d_keep;
   a.seq_off = p->d_off; a.seq_len = p->d_len; a.nseq = p->nseq; a.total = p->total; a.table = p->d_table;
-  {
-    ReduceTimer timer(al, "pileup", n);
-    const int lrc = wfa::launch_pileup(a, al->cu_count, al->stream);
-    timer.stop();
-    const hipError_t e = hipStreamSynchronize(al->stream);   // (the caller's arrays are read by the copies above)
-    if (lrc != 0) { al->err = "pileup kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, e);
-  }
-  return WFA_HIP_OK;
+  ReduceTimer timer(al, "pileup", n);
+  return launch_end(al, &timer, wfa::launch_pileup(a, al->cu_count, al->stream), "pileup kernel launch failed");   // (the caller's arrays are read by the copies above)
+}
+
+// rows [start, start + len) of sequence seq are rows of the pileup, or the refusal that names them
+static int pileup_check_rows(const wfa_hip_pileup* p, int32_t seq, int64_t start, int64_t len) {
+  if (seq >= 0 && seq < p->nseq && start >= 0 && len >= 0 && start + len <= p->h_len[(size_t)seq]) return WFA_HIP_OK;
+  return fail_inval(p->al, "pileup: rows [%lld, %lld + %lld) of sequence %d are out of range (%lld sequences; sequence length %lld)", (long long)start,
+                    (long long)start, (long long)len, (int)seq, (long long)p->nseq, (long long)((seq >= 0 && seq < p->nseq) ? p->h_len[(size_t)seq] : -1));
 }
 
 extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int32_t* counts) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
-  if (seq < 0 || seq >= p->nseq || start < 0 || len < 0 || start + len > p->h_len[(size_t)seq]) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "pileup: rows [%lld, %lld + %lld) of sequence %d are out of range (%lld sequences; sequence length %lld)", (long long)start,
-             (long long)start, (long long)len, (int)seq, (long long)p->nseq, (long long)((seq >= 0 && seq < p->nseq) ? p->h_len[(size_t)seq] : -1));
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
+  if (pileup_check_rows(p, seq, start, len) != WFA_HIP_OK) return WFA_HIP_EINVAL;
   if (len == 0) return WFA_HIP_OK;
-  if (!counts) { al->err = "pileup: null output"; return WFA_HIP_EINVAL; }
+  if (!counts) return fail_inval(al, "pileup: null output");
   HIP_TRY(al, hipSetDevice(al->device));
   // the table is a plane per column: one copy per plane, interleaved into rows on the host
   std::vector<int32_t> plane((size_t)len * WFA_PILEUP_COLS);
@@ -167,45 +133,32 @@ static_assert(WFA_SITE_COLS == WFA_HIP_SITE_COLS, "columns of the kernels and of
 static int calls_check(wfa_hip_pileup* p, const wfa_hip_seqset_t* T, bool sites, int32_t seq, int64_t start, int64_t len, int32_t min_depth,
                        int32_t min_permille, int64_t cap, int64_t* g0, int64_t* n) {
   wfa_hip_aligner* al = p->al;
-  char buf[240];
-  if (!T || T->al != al) { al->err = "sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (T->n != p->nseq) {
-    snprintf(buf, sizeof(buf), "pileup: the set holds %lld sequences, the pileup was made over %lld", (long long)T->n, (long long)p->nseq);
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
+  if (!T || T->al != al) return fail_inval(al, "sequence set of another aligner");
+  if (T->n != p->nseq) return fail_inval(al, "pileup: the set holds %lld sequences, the pileup was made over %lld", (long long)T->n, (long long)p->nseq);
   for (int64_t k = 0; k < p->nseq; ++k)
-    if (T->h_len[(size_t)k] != p->h_len[(size_t)k]) {
-      snprintf(buf, sizeof(buf), "pileup: sequence %lld of the set has %lld bases, the pileup was made over %lld", (long long)k,
-               (long long)T->h_len[(size_t)k], (long long)p->h_len[(size_t)k]);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
-  if (min_depth < 1) {
-    snprintf(buf, sizeof(buf), "pileup: min_depth = %d is out of range (at least 1)", (int)min_depth);
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
-  if (sites && (min_permille < 1 || min_permille > 1000)) {
-    snprintf(buf, sizeof(buf), "pileup: min_permille = %d is out of range (1 .. 1000)", (int)min_permille);
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
-  if (sites && cap < 0) {
-    snprintf(buf, sizeof(buf), "pileup: cap = %lld is negative", (long long)cap);
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
+    if (T->h_len[(size_t)k] != p->h_len[(size_t)k])
+      return fail_inval(al, "pileup: sequence %lld of the set has %lld bases, the pileup was made over %lld", (long long)k,
+                        (long long)T->h_len[(size_t)k], (long long)p->h_len[(size_t)k]);
+  if (min_depth < 1) return fail_inval(al, "pileup: min_depth = %d is out of range (at least 1)", (int)min_depth);
+  if (sites && (min_permille < 1 || min_permille > 1000)) return fail_inval(al, "pileup: min_permille = %d is out of range (1 .. 1000)", (int)min_permille);
+  if (sites && cap < 0) return fail_inval(al, "pileup: cap = %lld is negative", (long long)cap);
   if (sites && seq == -1) {
-    if (start != 0 || len != -1) {
-      snprintf(buf, sizeof(buf), "pileup: seq = -1 (every sequence) goes with start = 0 and len = -1, got start = %lld, len = %lld",
-               (long long)start, (long long)len);
-      al->err = buf; return WFA_HIP_EINVAL;
-    }
+    if (start != 0 || len != -1)
+      return fail_inval(al, "pileup: seq = -1 (every sequence) goes with start = 0 and len = -1, got start = %lld, len = %lld", (long long)start, (long long)len);
     *g0 = 0; *n = p->total;
     return WFA_HIP_OK;
   }
-  if (seq < 0 || seq >= p->nseq || start < 0 || len < 0 || start + len > p->h_len[(size_t)seq]) {
-    snprintf(buf, sizeof(buf), "pileup: rows [%lld, %lld + %lld) of sequence %d are out of range (%lld sequences; sequence length %lld)", (long long)start,
-             (long long)start, (long long)len, (int)seq, (long long)p->nseq, (long long)((seq >= 0 && seq < p->nseq) ? p->h_len[(size_t)seq] : -1));
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
+  if (pileup_check_rows(p, seq, start, len) != WFA_HIP_OK) return WFA_HIP_EINVAL;
   *g0 = p->h_off[(size_t)seq] + start; *n = len;
+  return WFA_HIP_OK;
+}
+
+// the end of a calls / sites launch: the timer stopped, the launch's outcome, `count` results back to the caller, the stream synchronised
+template <class T> static int calls_launched(StreamScratch& sc, ReduceTimer& timer, int lrc, const char* failed, T* host, const T* dev, size_t count) {
+  timer.stop();
+  if (lrc != 0) { sc.al->err = failed; return WFA_HIP_EDEVICE; }
+  if (sc.download(host, dev, count)) return WFA_HIP_EDEVICE;
+  HIP_TRY(sc.al, hipStreamSynchronize(sc.al->stream));
   return WFA_HIP_OK;
 }
 
@@ -224,22 +177,15 @@ extern "C" int wfa_hip_pileup_calls(wfa_hip_pileup_t* p, const wfa_hip_seqset_t*
   int64_t g0 = 0, n = 0;
   const int rc = calls_check(p, texts, false, seq, start, len, min_depth, 1, 0, &g0, &n);
   if (rc != WFA_HIP_OK) return rc;
-  if (n > 0 && !out) { al->err = "pileup: null output"; return WFA_HIP_EINVAL; }
+  if (n > 0 && !out) return fail_inval(al, "pileup: null output");
   HIP_TRY(al, hipSetDevice(al->device));
   HIP_TRY(al, hipStreamSynchronize(al->stream));
   if (n == 0) return WFA_HIP_OK;
-  CrossScratch sc{al};
+  StreamScratch sc{al};
   wfa::CallsArgs a = calls_args(p, texts, g0, n, min_depth, 1);
   if (sc.alloc(&a.out, (size_t)n)) return WFA_HIP_EDEVICE;
-  {
-    ReduceTimer timer(al, "calls", n, "bases");
-    const int lrc = wfa::launch_calls(a, al->cu_count, al->stream);
-    timer.stop();
-    if (lrc != 0) { al->err = "calls kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, hipMemcpyAsync(out, a.out, (size_t)n, hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-  }
-  return WFA_HIP_OK;
+  ReduceTimer timer(al, "calls", n, "bases");
+  return calls_launched(sc, timer, wfa::launch_calls(a, al->cu_count, al->stream), "calls kernel launch failed", out, a.out, (size_t)n);
 }
 
 extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
@@ -249,8 +195,8 @@ extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t*
   int64_t g0 = 0, n = 0;
   const int rc = calls_check(p, texts, true, seq, start, len, min_depth, min_permille, cap, &g0, &n);
   if (rc != WFA_HIP_OK) return rc;
-  if (!count) { al->err = "pileup: null count"; return WFA_HIP_EINVAL; }
-  if (cap > 0 && !rows) { al->err = "pileup: null rows with cap > 0"; return WFA_HIP_EINVAL; }
+  if (!count) return fail_inval(al, "pileup: null count");
+  if (cap > 0 && !rows) return fail_inval(al, "pileup: null rows with cap > 0");
   HIP_TRY(al, hipSetDevice(al->device));
   HIP_TRY(al, hipStreamSynchronize(al->stream));
   *count = 0;
@@ -258,7 +204,7 @@ extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t*
   // bases per chunk: read per call, a multiple of 64 in 64 .. 2^20
   const char* env = getenv("WFA_HIP_CALLS_CHUNK");
   const int64_t asked = env && *env ? atoll(env) : 4096;
-  CrossScratch sc{al};
+  StreamScratch sc{al};
   wfa::CallsArgs a = calls_args(p, texts, g0, n, min_depth, min_permille);
   a.chunk = std::min<int64_t>(1 << 20, std::max<int64_t>(64, (std::min<int64_t>(asked, 1 << 20) + 63) / 64 * 64));
   a.chunks = (n + a.chunk - 1) / a.chunk;
@@ -266,23 +212,13 @@ extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t*
   uint64_t total = 0;
   {
     ReduceTimer timer(al, "sites count", n, "bases");
-    const int lrc = wfa::launch_sites_count(a, al->stream);
-    timer.stop();
-    if (lrc != 0) { al->err = "sites count kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, hipMemcpyAsync(&total, a.chunk_off + a.chunks, sizeof(total), hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    const int crc = calls_launched(sc, timer, wfa::launch_sites_count(a, al->stream), "sites count kernel launch failed", &total, a.chunk_off + a.chunks, 1);
+    if (crc != WFA_HIP_OK) return crc;
   }
   *count = (int64_t)total;
   a.cap = std::min<int64_t>((int64_t)total, cap);
   if (a.cap == 0) return WFA_HIP_OK;
   if (sc.alloc(&a.rows, (size_t)a.cap * WFA_SITE_COLS)) return WFA_HIP_EDEVICE;
-  {
-    ReduceTimer timer(al, "sites scatter", n, "bases");
-    const int lrc = wfa::launch_sites_scatter(a, al->stream);
-    timer.stop();
-    if (lrc != 0) { al->err = "sites scatter kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, hipMemcpyAsync(rows, a.rows, (size_t)a.cap * WFA_SITE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-  }
-  return WFA_HIP_OK;
+  ReduceTimer timer(al, "sites scatter", n, "bases");
+  return calls_launched(sc, timer, wfa::launch_sites_scatter(a, al->stream), "sites scatter kernel launch failed", rows, a.rows, (size_t)a.cap * WFA_SITE_COLS);
 }

@@ -45,45 +45,29 @@ extern "C" void wfa_hip_placer_destroy(wfa_hip_placer_t* p) {
   (void)hipStreamSynchronize(al->stream);
   pool_release(al, p->d_hits); pool_release(al, p->d_count); pool_release(al, p->d_bsum); pool_release(al, p->d_order);
   for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
-  delete p;
-  aligner_release_ref(al);
+  destroy_end(p);
 }
 
-// a device block of `bytes`, or WFA_HIP_EDEVICE with the byte count in the message
-static int placer_alloc(wfa_hip_aligner* al, void** out, size_t bytes, const char* what) {
-  if (pool_alloc(al, out, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    *out = nullptr;
-    char buf[160];
-    snprintf(buf, sizeof(buf), "placement: the allocation of %zu bytes failed (%s)", bytes, what);
-    al->err = buf;
-    return WFA_HIP_EDEVICE;
-  }
+// a pool block of `count` values of T, or WFA_HIP_EDEVICE with the byte count and what they are for in the message
+template <class T> static int placer_block(wfa_hip_aligner* al, T** out, size_t count, const char* what) {
+  if (pool_alloc(al, (void**)out, count * sizeof(T)) == hipSuccess) return WFA_HIP_OK;
+  return fail_alloc(al, (void**)out, "placement: the allocation of %zu bytes failed (%s)", count * sizeof(T), what);
+}
+
+static int placer_build(wfa_hip_aligner* al, wfa_hip_placer* p) {
+  const size_t chunks = (size_t)((p->nreads + 1 + WFA_PLACE_SCAN_CHUNK - 1) / WFA_PLACE_SCAN_CHUNK);
+  if (placer_block(al, &p->d_count, (size_t)(p->nreads + 1), "4 bytes per read") || placer_block(al, &p->d_bsum, chunks, "the scan's chunk sums")) return WFA_HIP_EDEVICE;
+  if (hipEventCreate(&p->ev[0]) != hipSuccess || hipEventCreate(&p->ev[1]) != hipSuccess) { al->err = "placement: hipEventCreate failed"; return WFA_HIP_EDEVICE; }
   return WFA_HIP_OK;
 }
 
 extern "C" wfa_hip_placer_t* wfa_hip_placer_create(wfa_hip_aligner_t* al, int64_t nreads) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  if (nreads < 0 || nreads >= (int64_t)INT32_MAX) {
-    char buf[120];
-    snprintf(buf, sizeof(buf), "placement: nreads = %lld is out of range (0 .. 2^31 - 2)", (long long)nreads);
-    al->err = buf; g_error = al->err; return nullptr;
-  }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
-  wfa_hip_placer* p = new wfa_hip_placer();
-  p->al = al;
+  if (!al) return fail_create(al, "null aligner");
+  if (nreads < 0 || nreads >= (int64_t)INT32_MAX) return fail_create(al, "placement: nreads = %lld is out of range (0 .. 2^31 - 2)", (long long)nreads);
+  if (!create_begin(al)) return nullptr;
+  wfa_hip_placer* p = create_adopt(al, new wfa_hip_placer());
   p->nreads = nreads;
-  al->live_batches += 1;
-  const size_t chunks = (size_t)((nreads + 1 + WFA_PLACE_SCAN_CHUNK - 1) / WFA_PLACE_SCAN_CHUNK);
-  if (placer_alloc(al, (void**)&p->d_count, (size_t)(nreads + 1) * sizeof(uint32_t), "4 bytes per read") != WFA_HIP_OK ||
-      placer_alloc(al, (void**)&p->d_bsum, chunks * sizeof(uint32_t), "the scan's chunk sums") != WFA_HIP_OK) {
-    g_error = al->err; wfa_hip_placer_destroy(p); return nullptr;
-  }
-  if (hipEventCreate(&p->ev[0]) != hipSuccess || hipEventCreate(&p->ev[1]) != hipSuccess) {
-    al->err = "placement: hipEventCreate failed";
-    g_error = al->err; wfa_hip_placer_destroy(p); return nullptr;
-  }
-  return p;
+  return create_done(al, p, placer_build(al, p), wfa_hip_placer_destroy);
 }
 
 extern "C" int64_t wfa_hip_placer_count(const wfa_hip_placer_t* p) { return p ? p->nhits : 0; }
@@ -106,8 +90,7 @@ static int placer_reserve(wfa_hip_placer* p, int64_t more) {
   if (p->nhits + more <= p->cap) return WFA_HIP_OK;
   const int64_t want = std::max<int64_t>(p->nhits + more, std::max<int64_t>(2 * p->cap, 1024));
   wfa::PlaceHit* d_new = nullptr;
-  const int rc = placer_alloc(al, (void**)&d_new, (size_t)want * sizeof(wfa::PlaceHit), "32 bytes per hit");
-  if (rc != WFA_HIP_OK) return rc;
+  if (placer_block(al, &d_new, (size_t)want, "32 bytes per hit")) return WFA_HIP_EDEVICE;
   if (p->nhits > 0) {
     const hipError_t e = hipMemcpyAsync(d_new, p->d_hits, (size_t)p->nhits * sizeof(wfa::PlaceHit), hipMemcpyDeviceToDevice, al->stream);
     const hipError_t e2 = hipStreamSynchronize(al->stream);
@@ -129,32 +112,21 @@ extern "C" int wfa_hip_placer_add(wfa_hip_placer_t* p, wfa_hip_batch_t* b, const
                                   const uint8_t* reverse) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
-  if (!b) { al->err = "placement: null batch"; return WFA_HIP_EINVAL; }
-  if (b->al != al) { al->err = "placement: batch of another aligner"; return WFA_HIP_EINVAL; }
-  if (!b->ran) { al->err = "placement needs a finished run of the batch"; return WFA_HIP_EINVAL; }
+  int rc = batch_of(al, b, "placement", false);
+  if (rc != WFA_HIP_OK) return rc;
   const int64_t n = b->n;
-  char buf[240];
-  if (wfa::place_check_hits(p->nreads, p->nhits, n, i, j, t_start, nullptr, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  int rc = wfa_hip_batch_sync(b);
+  if (check_inval(al, wfa::place_check_hits, p->nreads, p->nhits, n, i, j, t_start, nullptr)) return WFA_HIP_EINVAL;
+  rc = wfa_hip_batch_sync(b);
   if (rc != WFA_HIP_OK) return rc;
   if (n == 0) return WFA_HIP_OK;
   HIP_TRY(al, hipSetDevice(al->device));
   rc = placer_reserve(p, n);
   if (rc != WFA_HIP_OK) return rc;
-  CrossScratch sc{al};   // (waits for the stream before the blocks go back)
+  StreamScratch sc{al};   // (waits for the stream before the blocks go back)
   int32_t *d_i = nullptr, *d_j = nullptr, *d_ts = nullptr;
   uint8_t* d_rev = nullptr;
-  if (sc.alloc(&d_i, (size_t)n) || sc.alloc(&d_j, (size_t)n)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipMemcpyAsync(d_i, i, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  HIP_TRY(al, hipMemcpyAsync(d_j, j, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  if (t_start) {
-    if (sc.alloc(&d_ts, (size_t)n)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_ts, t_start, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-  }
-  if (reverse) {
-    if (sc.alloc(&d_rev, (size_t)n)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_rev, reverse, (size_t)n, hipMemcpyHostToDevice, al->stream));
-  }
+  if (sc.upload(&d_i, i, (size_t)n) || sc.upload(&d_j, j, (size_t)n) || sc.upload_opt(&d_ts, t_start, (size_t)n) || sc.upload_opt(&d_rev, reverse, (size_t)n))
+    return WFA_HIP_EDEVICE;
   const bool full = b->cfg.scope == WFA_SCOPE_FULL;
   wfa::PlaceRecordArgs a;
   memset(&a, 0, sizeof(a));
@@ -163,11 +135,8 @@ extern "C" int wfa_hip_placer_add(wfa_hip_placer_t* p, wfa_hip_batch_t* b, const
   a.npairs = n; a.i = d_i; a.j = d_j; a.t_start = d_ts; a.reverse = d_rev; a.out = p->d_hits + p->nhits;
   {
     ReduceTimer timer(al, "place record", n);
-    const int lrc = wfa::launch_place_record(a, full, al->cu_count, al->stream);
-    timer.stop();
-    const hipError_t e = hipStreamSynchronize(al->stream);   // (the caller's arrays are read by the copies above)
-    if (lrc != 0) { al->err = "placement: record kernel launch failed"; return WFA_HIP_EDEVICE; }
-    HIP_TRY(al, e);
+    rc = launch_end(al, &timer, wfa::launch_place_record(a, full, al->cu_count, al->stream), "placement: record kernel launch failed");   // (the caller's arrays are read by the copies above)
+    if (rc != WFA_HIP_OK) return rc;
   }
   placer_note_texts(p, n, j);
   p->nhits += n; p->grouped = -1;
@@ -178,9 +147,8 @@ extern "C" int wfa_hip_placer_add_hits(wfa_hip_placer_t* p, int64_t n, const int
                                        const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
-  if (n > 0 && (!score || !status || !text_start || !text_end)) { al->err = "placement: a missing array"; return WFA_HIP_EINVAL; }
-  char buf[240];
-  if (wfa::place_check_hits(p->nreads, p->nhits, n, i, j, text_start, text_end, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
+  if (n > 0 && (!score || !status || !text_start || !text_end)) return fail_inval(al, "placement: a missing array");
+  if (check_inval(al, wfa::place_check_hits, p->nreads, p->nhits, n, i, j, text_start, text_end)) return WFA_HIP_EINVAL;
   if (n == 0) return WFA_HIP_OK;
   HIP_TRY(al, hipSetDevice(al->device));
   const int rc = placer_reserve(p, n);
@@ -198,90 +166,103 @@ extern "C" int wfa_hip_placer_add_hits(wfa_hip_placer_t* p, int64_t n, const int
   return WFA_HIP_OK;
 }
 
-extern "C" int wfa_hip_placer_run(wfa_hip_placer_t* p, int32_t min_score, int32_t full_gap, int32_t* rows, uint8_t* flags) {
-  if (!p) return WFA_HIP_EINVAL;
+// ---- what the three runs (run, run_pairs, rescue) share, in the order they use it -------------------------------------------------------
+// d_order holds a hit number per record
+static int placer_ensure_order(wfa_hip_placer* p) {
   wfa_hip_aligner* al = p->al;
-  char buf[160];
-  if (wfa::place_check_run(full_gap, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (p->nreads > 0 && !rows) { al->err = "placement: null rows"; return WFA_HIP_EINVAL; }
-  if (p->nreads == 0) return WFA_HIP_OK;
-  HIP_TRY(al, hipSetDevice(al->device));
-  if (p->nhits > p->order_cap) {
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
-    const int rc = placer_alloc(al, (void**)&p->d_order, (size_t)p->cap * sizeof(uint32_t), "4 bytes per hit");
-    if (rc != WFA_HIP_OK) return rc;
-    p->order_cap = p->cap;
-  }
-  CrossScratch sc{al};
-  wfa::PlaceArgs a;
-  memset(&a, 0, sizeof(a));
-  a.hits = p->d_hits; a.nhits = p->nhits; a.nreads = p->nreads; a.count = p->d_count; a.bsum = p->d_bsum; a.order = p->d_order;
-  a.min_score = min_score; a.full_gap = full_gap;
-  if (sc.alloc(&a.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
-  if (flags && sc.alloc(&a.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
-  {
-    ReduceTimer timer(al, "place", p->nhits, "hits");
-    HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
-    int lrc = 0;
-    if (p->grouped != p->nhits) {
-      p->grouped = -1;
-      HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
-      lrc = wfa::launch_place_group(a, al->stream);
-    }
-    if (lrc == 0) lrc = wfa::launch_place(a, al->cu_count, al->stream);
-    HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
-    timer.stop();
-    if (lrc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "placement: kernel launch failed"; return WFA_HIP_EDEVICE; }
-    p->grouped = p->nhits;
-    HIP_TRY(al, hipMemcpyAsync(rows, a.rows, (size_t)p->nreads * WFA_PLACE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-    if (flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(flags, a.flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
-  }
+  if (p->nhits <= p->order_cap) return WFA_HIP_OK;
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
+  if (placer_block(al, &p->d_order, (size_t)p->cap, "4 bytes per hit")) return WFA_HIP_EDEVICE;
+  p->order_cap = p->cap;
   return WFA_HIP_OK;
 }
 
+// the placement kernels' arguments; the rows, and the flags when `want_flags`, in the run's scratch
+static int placer_args(wfa_hip_placer* p, StreamScratch& sc, wfa::PlaceArgs& s, int32_t min_score, int32_t full_gap, bool want_flags) {
+  memset(&s, 0, sizeof(s));
+  s.hits = p->d_hits; s.nhits = p->nhits; s.nreads = p->nreads; s.count = p->d_count; s.bsum = p->d_bsum; s.order = p->d_order;
+  s.min_score = min_score; s.full_gap = full_gap;
+  if (sc.alloc(&s.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
+  if (want_flags && sc.alloc(&s.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  return WFA_HIP_OK;
+}
+
+// ev[0] recorded, then group (when the hits changed since the last one) and place enqueued.  `*launch_rc`: nonzero when a launch failed
+// (the later ones are then left out; placer_launched handles it)
+static int placer_enqueue_place(wfa_hip_placer* p, const wfa::PlaceArgs& s, int* launch_rc) {
+  wfa_hip_aligner* al = p->al;
+  *launch_rc = 0;
+  HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
+  if (p->grouped != p->nhits) {
+    p->grouped = -1;
+    HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
+    *launch_rc = wfa::launch_place_group(s, al->stream);
+  }
+  if (*launch_rc == 0) *launch_rc = wfa::launch_place(s, al->cu_count, al->stream);
+  return WFA_HIP_OK;
+}
+
+// behind the run's last launch: ev[1] recorded and the timer stopped either way; a failed launch leaves the hits ungrouped
+static int placer_launched(wfa_hip_placer* p, ReduceTimer& timer, int launch_rc, const char* failed) {
+  wfa_hip_aligner* al = p->al;
+  HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
+  timer.stop();
+  if (launch_rc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = failed; return WFA_HIP_EDEVICE; }
+  p->grouped = p->nhits;
+  return WFA_HIP_OK;
+}
+
+// the run's downloads are enqueued: the stream synchronised, the kernels' time read
+static int placer_finish(wfa_hip_placer* p) {
+  HIP_TRY(p->al, hipStreamSynchronize(p->al->stream));
+  HIP_TRY(p->al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_placer_run(wfa_hip_placer_t* p, int32_t min_score, int32_t full_gap, int32_t* rows, uint8_t* flags) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (check_inval(al, wfa::place_check_run, full_gap)) return WFA_HIP_EINVAL;
+  if (p->nreads > 0 && !rows) return fail_inval(al, "placement: null rows");
+  if (p->nreads == 0) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  int rc = placer_ensure_order(p);
+  if (rc != WFA_HIP_OK) return rc;
+  StreamScratch sc{al};
+  wfa::PlaceArgs a;
+  if (placer_args(p, sc, a, min_score, full_gap, flags != nullptr)) return WFA_HIP_EDEVICE;
+  ReduceTimer timer(al, "place", p->nhits, "hits");
+  int lrc = 0;
+  if ((rc = placer_enqueue_place(p, a, &lrc)) != WFA_HIP_OK || (rc = placer_launched(p, timer, lrc, "placement: kernel launch failed")) != WFA_HIP_OK) return rc;
+  if (sc.download(rows, a.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
+  if (flags && p->nhits > 0 && sc.download(flags, a.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  return placer_finish(p);
+}
+
 // What wfa_hip_placer_run_pairs and wfa_hip_placer_rescue share, after their checks: the blocks of one pair run in `sc`, the mates
-// uploaded, ev[0] recorded, then group (when the hits changed), place and the pair kernel enqueued; the single-end rows and flags
-// stay on the device for the join.  `*launch_rc`: nonzero when a launch failed (the later ones are then left out).  The caller records
-// ev[1] and stops its timer either way, as run_pairs always did, then handles a failed launch, synchronises and reads the elapsed time.
-static int placer_enqueue_pairs(wfa_hip_placer* p, CrossScratch& sc, wfa::PairArgs& a, int32_t min_score, int32_t full_gap,
+// uploaded, then group, place (placer_enqueue_place) and the pair kernel enqueued; the single-end rows and flags stay on the device for
+// the join.  The caller goes on with placer_launched, as wfa_hip_placer_run does.
+static int placer_enqueue_pairs(wfa_hip_placer* p, StreamScratch& sc, wfa::PairArgs& a, int32_t min_score, int32_t full_gap,
                                 int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
                                 const int32_t* mate2, bool want_pair_flags, int* launch_rc) {
   wfa_hip_aligner* al = p->al;
   *launch_rc = 0;
-  if (p->nhits > p->order_cap) {
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    pool_release(al, p->d_order); p->d_order = nullptr; p->order_cap = 0;
-    const int rc = placer_alloc(al, (void**)&p->d_order, (size_t)p->cap * sizeof(uint32_t), "4 bytes per hit");
-    if (rc != WFA_HIP_OK) return rc;
-    p->order_cap = p->cap;
-  }
+  const int rc = placer_ensure_order(p);
+  if (rc != WFA_HIP_OK) return rc;
   memset(&a, 0, sizeof(a));
   wfa::PlaceArgs& s = a.place;
-  s.hits = p->d_hits; s.nhits = p->nhits; s.nreads = p->nreads; s.count = p->d_count; s.bsum = p->d_bsum; s.order = p->d_order;
-  s.min_score = min_score; s.full_gap = full_gap;
+  if (placer_args(p, sc, s, min_score, full_gap, true)) return WFA_HIP_EDEVICE;
   a.min_insert = min_insert; a.max_insert = max_insert; a.unpaired = unpaired; a.nfrag = nfrag;
-  if (sc.alloc(&s.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
-  if (sc.alloc(&s.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
   if (want_pair_flags && sc.alloc(&a.pair_flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
   if (nfrag > 0 && sc.alloc(&a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS)) return WFA_HIP_EDEVICE;
   if (mate1 && nfrag > 0) {
     int32_t *d_m1 = nullptr, *d_m2 = nullptr;
-    if (sc.alloc(&d_m1, (size_t)nfrag) || sc.alloc(&d_m2, (size_t)nfrag)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipMemcpyAsync(d_m1, mate1, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
-    HIP_TRY(al, hipMemcpyAsync(d_m2, mate2, (size_t)nfrag * sizeof(int32_t), hipMemcpyHostToDevice, al->stream));
+    if (sc.upload(&d_m1, mate1, (size_t)nfrag) || sc.upload(&d_m2, mate2, (size_t)nfrag)) return WFA_HIP_EDEVICE;
     a.mate1 = d_m1; a.mate2 = d_m2;
   }
-  HIP_TRY(al, hipEventRecord(p->ev[0], al->stream));
   int lrc = 0;
-  if (p->grouped != p->nhits) {
-    p->grouped = -1;
-    HIP_TRY(al, hipMemsetAsync(p->d_count, 0, (size_t)(p->nreads + 1) * sizeof(uint32_t), al->stream));
-    lrc = wfa::launch_place_group(s, al->stream);
-  }
-  if (lrc == 0) lrc = wfa::launch_place(s, al->cu_count, al->stream);
+  { const int erc = placer_enqueue_place(p, s, &lrc); if (erc != WFA_HIP_OK) return erc; }
   // reads in no fragment, and fragments that are not proper, keep their single-end flags
   if (lrc == 0 && a.pair_flags && p->nhits > 0)
     HIP_TRY(al, hipMemcpyAsync(a.pair_flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToDevice, al->stream));
@@ -295,32 +276,24 @@ extern "C" int wfa_hip_placer_run_pairs(wfa_hip_placer_t* p, int32_t min_score, 
                                         uint8_t* flags, int32_t* pair_rows, uint8_t* pair_flags) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
-  char buf[240];
-  if (wfa::place_check_run(full_gap, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (wfa::pair_check(p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (nfrag > 0 && !pair_rows) { al->err = "pairing: null pair_rows"; return WFA_HIP_EINVAL; }
+  if (check_inval(al, wfa::place_check_run, full_gap)) return WFA_HIP_EINVAL;
+  if (check_inval(al, wfa::pair_check, p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2)) return WFA_HIP_EINVAL;
+  if (nfrag > 0 && !pair_rows) return fail_inval(al, "pairing: null pair_rows");
   if (p->nreads == 0) return WFA_HIP_OK;   // (no read: no fragment, no hit)
   HIP_TRY(al, hipSetDevice(al->device));
-  CrossScratch sc{al};
+  StreamScratch sc{al};
   wfa::PairArgs a;
-  {
-    ReduceTimer timer(al, "place pairs", p->nhits, "hits");
-    int lrc = 0;
-    const int rc = placer_enqueue_pairs(p, sc, a, min_score, full_gap, min_insert, max_insert, unpaired, nfrag, mate1, mate2, pair_flags != nullptr, &lrc);
-    if (rc != WFA_HIP_OK) return rc;
-    const wfa::PlaceArgs& s = a.place;
-    HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
-    timer.stop();
-    if (lrc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "pairing: kernel launch failed"; return WFA_HIP_EDEVICE; }
-    p->grouped = p->nhits;
-    if (rows) HIP_TRY(al, hipMemcpyAsync(rows, s.rows, (size_t)p->nreads * WFA_PLACE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-    if (flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(flags, s.flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
-    if (nfrag > 0) HIP_TRY(al, hipMemcpyAsync(pair_rows, a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-    if (pair_flags && p->nhits > 0) HIP_TRY(al, hipMemcpyAsync(pair_flags, a.pair_flags, (size_t)p->nhits, hipMemcpyDeviceToHost, al->stream));
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-    HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
-  }
-  return WFA_HIP_OK;
+  ReduceTimer timer(al, "place pairs", p->nhits, "hits");
+  int lrc = 0, rc;
+  if ((rc = placer_enqueue_pairs(p, sc, a, min_score, full_gap, min_insert, max_insert, unpaired, nfrag, mate1, mate2, pair_flags != nullptr, &lrc)) != WFA_HIP_OK ||
+      (rc = placer_launched(p, timer, lrc, "pairing: kernel launch failed")) != WFA_HIP_OK)
+    return rc;
+  const wfa::PlaceArgs& s = a.place;
+  if (rows && sc.download(rows, s.rows, (size_t)p->nreads * WFA_PLACE_COLS)) return WFA_HIP_EDEVICE;
+  if (flags && p->nhits > 0 && sc.download(flags, s.flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  if (nfrag > 0 && sc.download(pair_rows, a.pair_rows, (size_t)nfrag * WFA_PAIR_COLS)) return WFA_HIP_EDEVICE;
+  if (pair_flags && p->nhits > 0 && sc.download(pair_flags, a.pair_flags, (size_t)p->nhits)) return WFA_HIP_EDEVICE;
+  return placer_finish(p);
 }
 
 // group, place and pair as wfa_hip_placer_run_pairs enqueues them, none of their outputs downloaded; then decide, scan and emit
@@ -331,26 +304,22 @@ extern "C" int wfa_hip_placer_rescue(wfa_hip_placer_t* p, const wfa_hip_seqset_t
                                      int64_t cap, int64_t* count, int32_t* rows) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
-  char buf[240];
-  if (wfa::place_check_run(full_gap, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (wfa::pair_check(p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (wfa::rescue_check(pad, min_len, anchor_mapq, cap, count, rows, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  if (!patterns || !texts) { al->err = "rescue: a missing sequence set"; return WFA_HIP_EINVAL; }
-  if (patterns->al != al || texts->al != al) { al->err = "rescue: sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (patterns->n < p->nreads) {
-    snprintf(buf, sizeof(buf), "rescue: the pattern set has %lld sequences, the placer %lld reads", (long long)patterns->n, (long long)p->nreads);
-    al->err = buf; return WFA_HIP_EINVAL;
-  }
+  if (check_inval(al, wfa::place_check_run, full_gap)) return WFA_HIP_EINVAL;
+  if (check_inval(al, wfa::pair_check, p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2)) return WFA_HIP_EINVAL;
+  if (check_inval(al, wfa::rescue_check, pad, min_len, anchor_mapq, cap, count, rows)) return WFA_HIP_EINVAL;
+  if (!patterns || !texts) return fail_inval(al, "rescue: a missing sequence set");
+  if (patterns->al != al || texts->al != al) return fail_inval(al, "rescue: sequence set of another aligner");
+  if (patterns->n < p->nreads)
+    return fail_inval(al, "rescue: the pattern set has %lld sequences, the placer %lld reads", (long long)patterns->n, (long long)p->nreads);
   if (!p->j_rise.empty() && (int64_t)p->j_rise.back().second >= texts->n) {
     size_t k = 0;   // (the rises ascend in j: the first one outside the set is the first such hit of the list)
     while ((int64_t)p->j_rise[k].second < texts->n) ++k;
-    snprintf(buf, sizeof(buf), "rescue: text index out of range at position %lld of the hit list: j = %d over %lld texts",
-             (long long)p->j_rise[k].first, (int)p->j_rise[k].second, (long long)texts->n);
-    al->err = buf; return WFA_HIP_EINVAL;
+    return fail_inval(al, "rescue: text index out of range at position %lld of the hit list: j = %d over %lld texts",
+                      (long long)p->j_rise[k].first, (int)p->j_rise[k].second, (long long)texts->n);
   }
   if (p->nreads == 0 || nfrag == 0) { *count = 0; return WFA_HIP_OK; }   // (no fragment: no window)
   HIP_TRY(al, hipSetDevice(al->device));
-  CrossScratch sc{al};
+  StreamScratch sc{al};
   wfa::RescueArgs r;
   memset(&r, 0, sizeof(r));
   const int64_t nslots = 2 * nfrag, out_cap = std::min<int64_t>(cap, nslots);
@@ -359,27 +328,19 @@ extern "C" int wfa_hip_placer_rescue(wfa_hip_placer_t* p, const wfa_hip_seqset_t
   if (sc.alloc(&r.slot, (size_t)nslots + 1)) return WFA_HIP_EDEVICE;
   if (sc.alloc(&r.bsum, (size_t)((nslots + 1 + WFA_PLACE_SCAN_CHUNK - 1) / WFA_PLACE_SCAN_CHUNK))) return WFA_HIP_EDEVICE;
   if (out_cap > 0 && sc.alloc(&r.out, (size_t)out_cap * WFA_RESCUE_COLS)) return WFA_HIP_EDEVICE;
-  {
-    ReduceTimer timer(al, "rescue", p->nhits, "hits");
-    int pair_rc = 0, lrc = 0;
-    const int rc = placer_enqueue_pairs(p, sc, r.pair, min_score, full_gap, min_insert, max_insert, unpaired, nfrag, mate1, mate2, false, &pair_rc);
-    if (rc != WFA_HIP_OK) return rc;
-    if (pair_rc == 0) lrc = wfa::launch_rescue(r, al->cu_count, al->stream);
-    HIP_TRY(al, hipEventRecord(p->ev[1], al->stream));
-    timer.stop();
-    if (pair_rc != 0) { (void)hipStreamSynchronize(al->stream); p->grouped = -1; al->err = "pairing: kernel launch failed"; return WFA_HIP_EDEVICE; }
-    p->grouped = p->nhits;
-    if (lrc != 0) { (void)hipStreamSynchronize(al->stream); al->err = "rescue: kernel launch failed"; return WFA_HIP_EDEVICE; }
-    uint32_t n = 0;
-    HIP_TRY(al, hipMemcpyAsync(&n, r.slot + nslots, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
+  ReduceTimer timer(al, "rescue", p->nhits, "hits");
+  int pair_rc = 0, lrc = 0, rc;
+  if ((rc = placer_enqueue_pairs(p, sc, r.pair, min_score, full_gap, min_insert, max_insert, unpaired, nfrag, mate1, mate2, false, &pair_rc)) != WFA_HIP_OK) return rc;
+  if (pair_rc == 0) lrc = wfa::launch_rescue(r, al->cu_count, al->stream);
+  if ((rc = placer_launched(p, timer, pair_rc, "pairing: kernel launch failed")) != WFA_HIP_OK) return rc;
+  if (lrc != 0) { (void)hipStreamSynchronize(al->stream); al->err = "rescue: kernel launch failed"; return WFA_HIP_EDEVICE; }
+  uint32_t n = 0;
+  if (sc.download(&n, r.slot + nslots, 1) || (rc = placer_finish(p)) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
+  const int64_t take = std::min<int64_t>((int64_t)n, out_cap);
+  if (take > 0) {
+    if (sc.download(rows, r.out, (size_t)take * WFA_RESCUE_COLS)) return WFA_HIP_EDEVICE;
     HIP_TRY(al, hipStreamSynchronize(al->stream));
-    HIP_TRY(al, hipEventElapsedTime(&p->last_ms, p->ev[0], p->ev[1]));
-    const int64_t take = std::min<int64_t>((int64_t)n, out_cap);
-    if (take > 0) {
-      HIP_TRY(al, hipMemcpyAsync(rows, r.out, (size_t)take * WFA_RESCUE_COLS * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-      HIP_TRY(al, hipStreamSynchronize(al->stream));
-    }
-    *count = (int64_t)n;
   }
+  *count = (int64_t)n;
   return WFA_HIP_OK;
 }

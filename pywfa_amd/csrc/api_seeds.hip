@@ -68,8 +68,7 @@ extern "C" void wfa_hip_seed_index_destroy(wfa_hip_seed_index_t* x) {
   if (x->d_recs) (void)hipFree(x->d_recs);
   if (x->d_chain_ws) (void)hipFree(x->d_chain_ws);
   pool_release(al, x->d_len);
-  delete x;
-  aligner_release_ref(al);
+  destroy_end(x);
 }
 
 static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wfa_hip_seqset* T) {
@@ -79,28 +78,18 @@ static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wf
     if (len >= x->k) cap += (uint64_t)((len - x->k) / x->stride + 1);
   const uint64_t buckets = 1ull << (2 * x->k);
   const size_t table_bytes = (size_t)(buckets + 1) * sizeof(uint32_t), rec_bytes = (size_t)std::max<uint64_t>(cap, 1) * sizeof(wfa::SeedRec);
-  char buf[240];
-  if (hipMalloc((void**)&x->d_table, table_bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    x->d_table = nullptr;
-    snprintf(buf, sizeof(buf), "seed index table: hipMalloc of %zu bytes failed (4 bytes per k-mer of k = %d: 4^k buckets)", table_bytes, x->k);
-    al->err = buf;
-    return WFA_HIP_EDEVICE;
-  }
+  if (hipMalloc((void**)&x->d_table, table_bytes) != hipSuccess)
+    return fail_alloc(al, (void**)&x->d_table, "seed index table: hipMalloc of %zu bytes failed (4 bytes per k-mer of k = %d: 4^k buckets)", table_bytes, x->k);
   const auto alloc_recs = [&](size_t bytes, uint64_t positions) {
-    if (hipMalloc((void**)&x->d_recs, bytes) == hipSuccess) return true;
-    (void)hipGetLastError();
-    x->d_recs = nullptr;
-    snprintf(buf, sizeof(buf), "seed index records: hipMalloc of %zu bytes failed (8 bytes per indexed position, %llu positions)", bytes,
-             (unsigned long long)positions);
-    al->err = buf;
-    return false;
+    if (hipMalloc((void**)&x->d_recs, bytes) == hipSuccess) return WFA_HIP_OK;
+    return fail_alloc(al, (void**)&x->d_recs, "seed index records: hipMalloc of %zu bytes failed (8 bytes per indexed position, %llu positions)", bytes,
+                      (unsigned long long)positions);
   };
-  if (x->w == 0 && !alloc_recs(rec_bytes, cap)) return WFA_HIP_EDEVICE;   // (a minimizer index: after the counting pass, by its total)
+  if (x->w == 0 && alloc_recs(rec_bytes, cap)) return WFA_HIP_EDEVICE;   // (a minimizer index: after the counting pass, by its total)
   x->table_bytes = (int64_t)(table_bytes + rec_bytes);
   const uint16_t* mask = nullptr;
   if (seqset_mask(al, T, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
-  CrossScratch sc{al};
+  StreamScratch sc{al};
   uint32_t *d_bsum = nullptr, *d_masked = nullptr;
   if (sc.alloc(&d_bsum, (size_t)((buckets + 1 + WFA_SEED_SCAN_CHUNK - 1) / WFA_SEED_SCAN_CHUNK)) || sc.alloc(&d_masked, 1)) return WFA_HIP_EDEVICE;
   HIP_TRY(al, pool_alloc(al, (void**)&x->d_len, (size_t)T->n * sizeof(int32_t)));
@@ -119,21 +108,18 @@ static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wf
   uint32_t total = 0, masked = 0;
   if (x->w >= 1 && lrc == 0) {
     // the records by the count: the scan has left the total behind the last bucket
-    HIP_TRY(al, hipMemcpyAsync(&total, x->d_table + buckets, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
+    if (sc.download(&total, x->d_table + buckets, 1)) return WFA_HIP_EDEVICE;
     HIP_TRY(al, hipStreamSynchronize(al->stream));
     cap = total;
     const size_t bytes = (size_t)std::max<uint64_t>(cap, 1) * sizeof(wfa::SeedRec);
-    if (!alloc_recs(bytes, cap)) return WFA_HIP_EDEVICE;
+    if (alloc_recs(bytes, cap)) return WFA_HIP_EDEVICE;
     x->table_bytes = (int64_t)(table_bytes + bytes);
     a.recs = x->d_recs;
   }
   lrc |= wfa::launch_seed_fill(a, (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull), al->stream);
   HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
-  HIP_TRY(al, hipMemcpyAsync(&total, x->d_table + buckets, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
-  HIP_TRY(al, hipMemcpyAsync(&masked, d_masked, sizeof(uint32_t), hipMemcpyDeviceToHost, al->stream));
-  const hipError_t e = hipStreamSynchronize(al->stream);
-  if (lrc != 0) { al->err = "seed index kernel launch failed"; return WFA_HIP_EDEVICE; }
-  HIP_TRY(al, e);
+  if (sc.download(&total, x->d_table + buckets, 1) || sc.download(&masked, d_masked, 1)) return WFA_HIP_EDEVICE;
+  { const int erc = launch_end(al, nullptr, lrc, "seed index kernel launch failed"); if (erc != WFA_HIP_OK) return erc; }
   HIP_TRY(al, hipEventElapsedTime(&x->build_ms, sc.ev[0], sc.ev[1]));
   x->positions = total; x->masked = masked;
   return WFA_HIP_OK;
@@ -141,23 +127,18 @@ static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wf
 
 // the one body of both creates; minimizer: w is the window and stride plays no part, otherwise w = 0
 static wfa_hip_seed_index_t* seed_index_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int stride, int w, int max_occ, bool minimizer) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  char buf[200];
-  if (!texts || texts->al != al) { al->err = "seed index: sequence set of another aligner"; g_error = al->err; return nullptr; }
-  const int crc = minimizer ? wfa::seed_check_minimizer(k, w, max_occ, buf, sizeof(buf)) : wfa::seed_check_index(k, stride, max_occ, buf, sizeof(buf));
-  if (crc != WFA_HIP_OK) { al->err = buf; g_error = al->err; return nullptr; }
-  if (texts->n == 0) { al->err = "seed index: texts = a set of 0 sequences is out of range (at least 1)"; g_error = al->err; return nullptr; }
-  if (texts->nbytes >= (1ll << 31)) {
-    snprintf(buf, sizeof(buf), "seed index: texts = a set of %lld bases is out of range (below 2^31: split the set)", (long long)texts->nbytes);
-    al->err = buf; g_error = al->err; return nullptr;
-  }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  if (!al) return fail_create(al, "null aligner");
+  if (!texts || texts->al != al) return fail_create(al, "seed index: sequence set of another aligner");
+  const int crc = minimizer ? check_inval(al, wfa::seed_check_minimizer, k, w, max_occ) : check_inval(al, wfa::seed_check_index, k, stride, max_occ);
+  if (crc != WFA_HIP_OK) { g_error = al->err; return nullptr; }
+  if (texts->n == 0) return fail_create(al, "seed index: texts = a set of 0 sequences is out of range (at least 1)");
+  if (texts->nbytes >= (1ll << 31))
+    return fail_create(al, "seed index: texts = a set of %lld bases is out of range (below 2^31: split the set)", (long long)texts->nbytes);
+  if (!create_begin(al)) return nullptr;
   mailbox_release(al);   // (the resident one-pair kernel: the build takes the device)
-  wfa_hip_seed_index* x = new wfa_hip_seed_index();
-  x->al = al; x->k = k; x->stride = stride; x->w = w; x->max_occ = max_occ;
-  al->live_batches += 1;
-  if (seed_index_build(al, x, texts) != WFA_HIP_OK) { g_error = al->err; wfa_hip_seed_index_destroy(x); return nullptr; }
-  return x;
+  wfa_hip_seed_index* x = create_adopt(al, new wfa_hip_seed_index());
+  x->k = k; x->stride = stride; x->w = w; x->max_occ = max_occ;
+  return create_done(al, x, seed_index_build(al, x, texts), wfa_hip_seed_index_destroy);
 }
 
 extern "C" wfa_hip_seed_index_t* wfa_hip_seed_index_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* texts, int k, int stride, int max_occ) {
@@ -176,47 +157,67 @@ extern "C" int wfa_hip_seed_index_params(const wfa_hip_seed_index_t* x, int* k, 
   return WFA_HIP_OK;
 }
 
+// What a query and a chain run share: the reads' mask, then a block of `ncols` int32 columns of P->n x n cells and a byte per read in the
+// scratch, two events round the launch, and the columns back to the caller's arrays.  Only the argument struct and the launch differ.
+namespace {   // (internal: none of its members is exported)
+struct SeedRows {
+  wfa_hip_seed_index* x; const wfa_hip_seqset* P; int n;
+  StreamScratch sc;
+  const uint16_t* mask = nullptr;
+  size_t cells = 0;
+  int32_t* d_rows = nullptr;
+  uint8_t* d_over = nullptr;
+  int begin() {
+    wfa_hip_aligner* al = sc.al;
+    HIP_TRY(al, hipSetDevice(al->device));
+    mailbox_release(al);
+    return seqset_mask(al, P, &mask) != WFA_HIP_OK ? WFA_HIP_EDEVICE : WFA_HIP_OK;
+  }
+  // the blocks and the events; *a zeroed, then what SeedQueryArgs and ChainArgs have in common (the first five columns among it)
+  template <class Args> int rows(int ncols, Args* a) {
+    wfa_hip_aligner* al = sc.al;
+    cells = (size_t)P->n * (size_t)n;
+    if (sc.alloc(&d_rows, (size_t)ncols * cells) || sc.alloc(&d_over, (size_t)P->n)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipEventCreate(&sc.ev[0]));
+    HIP_TRY(al, hipEventCreate(&sc.ev[1]));
+    memset(a, 0, sizeof(*a));
+    a->p = seed_view(P, mask);
+    a->table = x->d_table; a->recs = x->d_recs; a->t_len = x->d_len; a->t_nseq = x->nseq;
+    a->k = x->k; a->w = x->w; a->max_occ = (uint32_t)x->max_occ;
+    a->n = n;
+    a->j = d_rows; a->reverse = d_rows + cells; a->text_start = d_rows + 2 * cells; a->text_len = d_rows + 3 * cells; a->hits = d_rows + 4 * cells;
+    a->overflow = d_over;
+    return WFA_HIP_OK;
+  }
+  // behind the launch: the second event, the downloads, the stream synchronised, the launch's outcome, the kernel's time
+  int finish(int lrc, int ncols, int32_t* const* host, uint8_t* overflow, float* ms, const char* failed) {
+    wfa_hip_aligner* al = sc.al;
+    HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
+    if (sc.download_columns(host, ncols, d_rows, cells) || sc.download(overflow, d_over, (size_t)P->n)) return WFA_HIP_EDEVICE;
+    const int rc = launch_end(al, nullptr, lrc, failed);
+    if (rc != WFA_HIP_OK) return rc;
+    HIP_TRY(al, hipEventElapsedTime(ms, sc.ev[0], sc.ev[1]));
+    return WFA_HIP_OK;
+  }
+};
+}  // namespace
+
 extern "C" int wfa_hip_seed_index_query(wfa_hip_seed_index_t* x, const wfa_hip_seqset_t* P, int n, int min_hits, int gap, int pad, int max_hits,
                                         int32_t* j, int32_t* reverse, int32_t* text_start, int32_t* text_len, int32_t* hits, uint8_t* overflow) {
   if (!x) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = x->al;
-  char buf[200];
-  if (!P || P->al != al) { al->err = "seed query: sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (wfa::seed_check_query(n, min_hits, gap, pad, max_hits, buf, sizeof(buf)) != WFA_HIP_OK) { al->err = buf; return WFA_HIP_EINVAL; }
-  const int64_t m = P->n;
-  if (m == 0) return WFA_HIP_OK;
-  if (!j || !reverse || !text_start || !text_len || !hits || !overflow) { al->err = "seed query: a result array is missing"; return WFA_HIP_EINVAL; }
-  HIP_TRY(al, hipSetDevice(al->device));
-  mailbox_release(al);
-  const uint16_t* mask = nullptr;
-  if (seqset_mask(al, P, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
-  CrossScratch sc{al};
-  const size_t cells = (size_t)m * (size_t)n;
-  int32_t* d_rows = nullptr;
-  uint8_t* d_over = nullptr;
-  if (sc.alloc(&d_rows, 5 * cells) || sc.alloc(&d_over, (size_t)m)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipEventCreate(&sc.ev[0]));
-  HIP_TRY(al, hipEventCreate(&sc.ev[1]));
+  if (!P || P->al != al) return fail_inval(al, "seed query: sequence set of another aligner");
+  if (check_inval(al, wfa::seed_check_query, n, min_hits, gap, pad, max_hits)) return WFA_HIP_EINVAL;
+  if (P->n == 0) return WFA_HIP_OK;
+  if (!j || !reverse || !text_start || !text_len || !hits || !overflow) return fail_inval(al, "seed query: a result array is missing");
+  SeedRows r{x, P, n, StreamScratch{al}};
   wfa::SeedQueryArgs a;
-  memset(&a, 0, sizeof(a));
-  a.p = seed_view(P, mask);
-  a.table = x->d_table; a.recs = x->d_recs; a.t_len = x->d_len; a.t_nseq = x->nseq;
-  a.k = x->k; a.w = x->w; a.max_occ = (uint32_t)x->max_occ;
-  a.n = n; a.min_hits = min_hits; a.max_hits = max_hits; a.gap = (uint32_t)gap; a.pad = pad;
-  a.j = d_rows; a.reverse = d_rows + cells; a.text_start = d_rows + 2 * cells; a.text_len = d_rows + 3 * cells; a.hits = d_rows + 4 * cells;
-  a.overflow = d_over;
-  HIP_TRY(al, hipEventRecord(sc.ev[0], al->stream));
-  const int lrc = wfa::launch_seed_query(a, m, al->cu_count, al->stream);
-  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
+  if (r.begin() || r.rows(5, &a)) return WFA_HIP_EDEVICE;
+  a.min_hits = min_hits; a.max_hits = max_hits; a.gap = (uint32_t)gap; a.pad = pad;
+  HIP_TRY(al, hipEventRecord(r.sc.ev[0], al->stream));
+  const int lrc = wfa::launch_seed_query(a, P->n, al->cu_count, al->stream);
   int32_t* host[5] = {j, reverse, text_start, text_len, hits};
-  for (int c = 0; c < 5; ++c)
-    HIP_TRY(al, hipMemcpyAsync(host[c], d_rows + (size_t)c * cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-  HIP_TRY(al, hipMemcpyAsync(overflow, d_over, (size_t)m, hipMemcpyDeviceToHost, al->stream));
-  const hipError_t e = hipStreamSynchronize(al->stream);
-  if (lrc != 0) { al->err = "seed query kernel launch failed"; return WFA_HIP_EDEVICE; }
-  HIP_TRY(al, e);
-  HIP_TRY(al, hipEventElapsedTime(&x->query_ms, sc.ev[0], sc.ev[1]));
-  return WFA_HIP_OK;
+  return r.finish(lrc, 5, host, overflow, &x->query_ms, "seed query kernel launch failed");
 }
 
 extern "C" int wfa_hip_seed_index_stats(const wfa_hip_seed_index_t* x, int64_t* positions, int64_t* masked_kmers, int64_t* table_bytes,
@@ -237,22 +238,14 @@ extern "C" int wfa_hip_seed_index_chain(wfa_hip_seed_index_t* x, const wfa_hip_s
                                         uint8_t* overflow) {
   if (!x) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = x->al;
-  char buf[240];
-  if (!P || P->al != al) { al->err = "seed chain: sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (wfa::seed_check_chain(n, min_hits, min_score, lookback, max_dist, band, pad, max_anchors, buf, sizeof(buf)) != WFA_HIP_OK) {
-    al->err = buf;
-    return WFA_HIP_EINVAL;
-  }
+  if (!P || P->al != al) return fail_inval(al, "seed chain: sequence set of another aligner");
+  if (check_inval(al, wfa::seed_check_chain, n, min_hits, min_score, lookback, max_dist, band, pad, max_anchors)) return WFA_HIP_EINVAL;
   const int64_t m = P->n;
   if (m == 0) return WFA_HIP_OK;
-  if (!j || !reverse || !text_start || !text_len || !hits || !score || !pattern_start || !pattern_len || !overflow) {
-    al->err = "seed chain: a result array is missing";
-    return WFA_HIP_EINVAL;
-  }
-  HIP_TRY(al, hipSetDevice(al->device));
-  mailbox_release(al);
-  const uint16_t* mask = nullptr;
-  if (seqset_mask(al, P, &mask) != WFA_HIP_OK) return WFA_HIP_EDEVICE;
+  if (!j || !reverse || !text_start || !text_len || !hits || !score || !pattern_start || !pattern_len || !overflow)
+    return fail_inval(al, "seed chain: a result array is missing");
+  SeedRows r{x, P, n, StreamScratch{al}};
+  if (r.begin()) return WFA_HIP_EDEVICE;
   // the workspace: a slab of WFA_CHAIN_PLANES x max_anchors int32 per workgroup of this launch
   const unsigned grid = wfa::chain_grid(m, al->cu_count);
   const size_t ws_bytes = (size_t)grid * WFA_CHAIN_PLANES * (size_t)max_anchors * sizeof(int32_t);
@@ -261,46 +254,21 @@ extern "C" int wfa_hip_seed_index_chain(wfa_hip_seed_index_t* x, const wfa_hip_s
     if (x->d_chain_ws) (void)hipFree(x->d_chain_ws);
     x->d_chain_ws = nullptr;
     x->chain_ws_bytes = 0;
-    if (hipMalloc((void**)&x->d_chain_ws, ws_bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      x->d_chain_ws = nullptr;
-      snprintf(buf, sizeof(buf), "seed chain workspace: hipMalloc of %zu bytes failed (32 bytes x max_anchors = %d per workgroup, %u workgroups)",
-               ws_bytes, max_anchors, grid);
-      al->err = buf;
-      return WFA_HIP_EDEVICE;
-    }
+    if (hipMalloc((void**)&x->d_chain_ws, ws_bytes) != hipSuccess)
+      return fail_alloc(al, (void**)&x->d_chain_ws, "seed chain workspace: hipMalloc of %zu bytes failed (32 bytes x max_anchors = %d per workgroup, %u workgroups)",
+                        ws_bytes, max_anchors, grid);
     x->chain_ws_bytes = ws_bytes;
   }
-  CrossScratch sc{al};
-  const size_t cells = (size_t)m * (size_t)n;
-  int32_t* d_rows = nullptr;
-  uint8_t* d_over = nullptr;
-  if (sc.alloc(&d_rows, 8 * cells) || sc.alloc(&d_over, (size_t)m)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipEventCreate(&sc.ev[0]));
-  HIP_TRY(al, hipEventCreate(&sc.ev[1]));
   wfa::ChainArgs a;
-  memset(&a, 0, sizeof(a));
-  a.p = seed_view(P, mask);
-  a.table = x->d_table; a.recs = x->d_recs; a.t_len = x->d_len; a.t_nseq = x->nseq;
-  a.k = x->k; a.w = x->w; a.max_occ = (uint32_t)x->max_occ;
-  a.n = n; a.min_hits = min_hits; a.min_score = min_score; a.lookback = lookback; a.max_dist = max_dist; a.band = band; a.pad = pad;
+  if (r.rows(8, &a)) return WFA_HIP_EDEVICE;
+  a.min_hits = min_hits; a.min_score = min_score; a.lookback = lookback; a.max_dist = max_dist; a.band = band; a.pad = pad;
   a.max_anchors = (uint32_t)max_anchors;
   a.slab = x->d_chain_ws;
-  a.j = d_rows; a.reverse = d_rows + cells; a.text_start = d_rows + 2 * cells; a.text_len = d_rows + 3 * cells; a.hits = d_rows + 4 * cells;
-  a.score = d_rows + 5 * cells; a.pattern_start = d_rows + 6 * cells; a.pattern_len = d_rows + 7 * cells;
-  a.overflow = d_over;
-  HIP_TRY(al, hipEventRecord(sc.ev[0], al->stream));
+  a.score = r.d_rows + 5 * r.cells; a.pattern_start = r.d_rows + 6 * r.cells; a.pattern_len = r.d_rows + 7 * r.cells;
+  HIP_TRY(al, hipEventRecord(r.sc.ev[0], al->stream));
   const int lrc = wfa::launch_chain(a, m, grid, al->stream);
-  HIP_TRY(al, hipEventRecord(sc.ev[1], al->stream));
   int32_t* host[8] = {j, reverse, text_start, text_len, hits, score, pattern_start, pattern_len};
-  for (int c = 0; c < 8; ++c)
-    HIP_TRY(al, hipMemcpyAsync(host[c], d_rows + (size_t)c * cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
-  HIP_TRY(al, hipMemcpyAsync(overflow, d_over, (size_t)m, hipMemcpyDeviceToHost, al->stream));
-  const hipError_t e = hipStreamSynchronize(al->stream);
-  if (lrc != 0) { al->err = "seed chain kernel launch failed"; return WFA_HIP_EDEVICE; }
-  HIP_TRY(al, e);
-  HIP_TRY(al, hipEventElapsedTime(&x->chain_ms, sc.ev[0], sc.ev[1]));
-  return WFA_HIP_OK;
+  return r.finish(lrc, 8, host, overflow, &x->chain_ms, "seed chain kernel launch failed");
 }
 
 extern "C" int wfa_hip_seed_index_chain_stats(const wfa_hip_seed_index_t* x, float* kernel_ms, int64_t* workspace_bytes) {

@@ -28,8 +28,7 @@ extern "C" void wfa_hip_seqset_destroy(wfa_hip_seqset_t* s) {
   (void)hipSetDevice(al->device);
   void* ptrs[] = {s->d_words, s->d_bytes, s->d_woff, s->d_len, s->d_boff, s->d_flag, s->d_mask};
   for (void* p : ptrs) pool_release(al, p);
-  delete s;
-  aligner_release_ref(al);
+  destroy_end(s);
 }
 
 // the runs of letters host_pack_seq flags (anything but upper-case ACGT) in one sequence
@@ -54,11 +53,11 @@ static int seqset_build(wfa_hip_aligner* al, wfa_hip_seqset* s, int64_t n, const
   uint64_t w = 0;
   int64_t bb = 0;
   for (int64_t k = 0; k < n; ++k) {
-    if (len[k] < 0 || off[k] < 0) { al->err = "negative length or offset"; return WFA_HIP_EINVAL; }
-    if (len[k] > INT_MAX / 4 - 8) { al->err = "sequence too long"; return WFA_HIP_EINVAL; }
+    if (len[k] < 0 || off[k] < 0) return fail_inval(al, "negative length or offset");
+    if (len[k] > INT_MAX / 4 - 8) return fail_inval(al, "sequence too long");
     woff[(size_t)k] = (uint32_t)w; w += (uint64_t)((len[k] + 15) >> 4);
     boff[(size_t)k] = bb; bb += len[k];
-    if (w > 0x7FFFFFF0ull) { al->err = "sequence set too large: more than 2^31 packed words"; return WFA_HIP_EINVAL; }
+    if (w > 0x7FFFFFF0ull) return fail_inval(al, "sequence set too large: more than 2^31 packed words");
   }
   s->nwords = w; s->nbytes = bb;
   std::vector<uint32_t> words((size_t)w + 4, 0u);
@@ -95,16 +94,13 @@ static int seqset_build(wfa_hip_aligner* al, wfa_hip_seqset* s, int64_t n, const
 }
 
 extern "C" wfa_hip_seqset_t* wfa_hip_seqset_create(wfa_hip_aligner_t* al, int64_t n, const uint8_t* seqs, const int64_t* off, const int32_t* len) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  if (n < 0 || n > 0x7FFFFFF0ll || (n > 0 && (!seqs || !off || !len))) { al->err = "invalid sequence set arguments"; g_error = al->err; return nullptr; }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  if (!al) return fail_create(al, "null aligner");
+  if (n < 0 || n > 0x7FFFFFF0ll || (n > 0 && (!seqs || !off || !len))) return fail_create(al, "invalid sequence set arguments");
+  if (!create_begin(al)) return nullptr;
   mailbox_release(al);   // (the resident one-pair kernel: sets take the device)
-  wfa_hip_seqset* s = new wfa_hip_seqset();
-  s->al = al;
+  wfa_hip_seqset* s = create_adopt(al, new wfa_hip_seqset());
   s->wildcard = al->cfg.wildcard;
-  al->live_batches += 1;
-  if (seqset_build(al, s, n, seqs, off, len) != WFA_HIP_OK) { g_error = al->err; wfa_hip_seqset_destroy(s); return nullptr; }
-  return s;
+  return create_done(al, s, seqset_build(al, s, n, seqs, off, len), wfa_hip_seqset_destroy);
 }
 
 extern "C" int64_t wfa_hip_plan_cross_bands(int64_t m, int64_t n, int triangle, int64_t max_pairs, int64_t* row_begin, int64_t cap) {
@@ -134,24 +130,21 @@ extern "C" void wfa_hip_cross_destroy(wfa_hip_cross_t* x) {
   (void)hipStreamSynchronize(al->stream);
   void* ptrs[] = {x->d_score, x->d_status, x->d_ci, x->d_cj, x->d_cs, x->d_topk};
   for (void* p : ptrs) pool_release(al, p);
-  delete x;
-  aligner_release_ref(al);
+  destroy_end(x);
 }
 
 // every refusal of a cross run, in this order (T: the text set, the pattern set itself for all-vs-all)
 static int cross_check(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wfa_hip_seqset* T, int want, int top_k) {
-  if (!P || P->al != al || T->al != al) { al->err = "sequence set of another aligner"; return WFA_HIP_EINVAL; }
-  if (want <= 0 || (want & ~(WFA_HIP_CROSS_DENSE | WFA_HIP_CROSS_COMPLETED | WFA_HIP_CROSS_TOPK)) != 0) {
-    al->err = "want: a combination of WFA_HIP_CROSS_DENSE, WFA_HIP_CROSS_COMPLETED and WFA_HIP_CROSS_TOPK"; return WFA_HIP_EINVAL;
-  }
-  if ((want & WFA_HIP_CROSS_TOPK) && (top_k < 1 || top_k > WFA_HIP_CROSS_MAX_K)) { al->err = "k: 1 .. WFA_HIP_CROSS_MAX_K (64)"; return WFA_HIP_EINVAL; }
-  if (P->wildcard != al->cfg.wildcard || T->wildcard != al->cfg.wildcard) { al->err = "sequence set packed under another wildcard: create it again"; return WFA_HIP_EINVAL; }
+  if (!P || P->al != al || T->al != al) return fail_inval(al, "sequence set of another aligner");
+  if (want <= 0 || (want & ~(WFA_HIP_CROSS_DENSE | WFA_HIP_CROSS_COMPLETED | WFA_HIP_CROSS_TOPK)) != 0)
+    return fail_inval(al, "want: a combination of WFA_HIP_CROSS_DENSE, WFA_HIP_CROSS_COMPLETED and WFA_HIP_CROSS_TOPK");
+  if ((want & WFA_HIP_CROSS_TOPK) && (top_k < 1 || top_k > WFA_HIP_CROSS_MAX_K)) return fail_inval(al, "k: 1 .. WFA_HIP_CROSS_MAX_K (64)");
+  if (P->wildcard != al->cfg.wildcard || T->wildcard != al->cfg.wildcard) return fail_inval(al, "sequence set packed under another wildcard: create it again");
   const wfa_hip_config_t& c = al->cfg;
   if (c.span == WFA_SPAN_ENDSFREE && P->n > 0 && T->n > 0) {   // (wavefront_align.c:86-102, as batch_build)
     const int32_t minp = *std::min_element(P->h_len.begin(), P->h_len.end()), mint = *std::min_element(T->h_len.begin(), T->h_len.end());
-    if (c.pattern_begin_free > minp || c.pattern_end_free > minp || c.text_begin_free > mint || c.text_end_free > mint) {
-      al->err = "Ends-free parameters must be not larger than the sequences"; return WFA_HIP_EINVAL;
-    }
+    if (c.pattern_begin_free > minp || c.pattern_end_free > minp || c.text_begin_free > mint || c.text_end_free > mint)
+      return fail_inval(al, "Ends-free parameters must be not larger than the sequences");
   }
   return WFA_HIP_OK;
 }
@@ -229,7 +222,7 @@ struct CrossRun {
   wfa_hip_aligner* al; const wfa_hip_seqset *P, *T; wfa_hip_cross* x;
   bool dense, completed, topk;
   CrossPlan plan;
-  CrossScratch sc;                 // (declared in front of the view: released after it)
+  StreamScratch sc;                 // (declared in front of the view: released after it)
   ViewGuard view;                  // the batch view: one for every band, so that the pilots' picks of the first large band hold for the later ones
   uint32_t *list_packed = nullptr, *list_bytes = nullptr;        // byte pairs: a band's two work lists ...
   int64_t *d_row_bytes = nullptr, *d_col_flag = nullptr;         // ... and the plan's two prefix tables
@@ -257,16 +250,14 @@ static int cross_view_alloc(CrossRun& run) {
   if (!al->dcfg.rtc) { b->dcfg.rtc = 0; b->gcfg.rtc = 0; }   // (the run-time path failed earlier on this aligner)
   if (p.c.wildcard >= 0 && !p.all_bytes) { b->wild = p.c.wildcard; b->dcfg.wildcard = -1; b->gcfg.wildcard = -1; }   // (as batch_build)
   HIP_TRY(al, pool_alloc(al, (void**)&b->d_bytes, (size_t)(P->nbytes + (ava ? 0 : T->nbytes) + 64)));
-  HIP_TRY(al, hipMemcpyAsync(b->d_bytes, P->d_bytes, (size_t)P->nbytes + (ava ? 64 : 0), hipMemcpyDeviceToDevice, al->stream));
-  if (!ava) HIP_TRY(al, hipMemcpyAsync(b->d_bytes + P->nbytes, T->d_bytes, (size_t)T->nbytes + 64, hipMemcpyDeviceToDevice, al->stream));
+  if (copy_sets(al, b->d_bytes, P->d_bytes, (size_t)P->nbytes, T->d_bytes, (size_t)T->nbytes, ava, 64)) return WFA_HIP_EDEVICE;
   // One word table per run: the pattern set's words, the text set's (cross mode), 64 zero words, then a slot per pair of a band for the
   // pairs of up to WFA_FAST_MAX_LEN bases: the register stages (wfa_lane.hpp, wfa_seg.hpp) fetch a pair's pattern and text words in ONE
   // load, the text's words right behind the pattern's, so the generator copies both sequences of such a pair into its slot.  Longer pairs
   // point into the sets' words (every other stage reads pattern and text through their own offsets).
-  if (p.table_words + (uint64_t)p.cap * p.slot_words > 0xFFFFFFF0ull) { al->err = "sequence sets too large: more than 2^32 words of a band"; return WFA_HIP_EINVAL; }
+  if (p.table_words + (uint64_t)p.cap * p.slot_words > 0xFFFFFFF0ull) return fail_inval(al, "sequence sets too large: more than 2^32 words of a band");
   HIP_TRY(al, pool_alloc(al, (void**)&b->d_words, (size_t)(p.table_words + (uint64_t)p.cap * p.slot_words) * sizeof(uint32_t)));
-  HIP_TRY(al, hipMemcpyAsync(b->d_words, P->d_words, (size_t)P->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
-  if (!ava) HIP_TRY(al, hipMemcpyAsync(b->d_words + P->nwords, T->d_words, (size_t)T->nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, al->stream));
+  if (copy_sets(al, b->d_words, P->d_words, (size_t)P->nwords, T->d_words, (size_t)T->nwords, ava, 0)) return WFA_HIP_EDEVICE;
   HIP_TRY(al, hipMemsetAsync(b->d_words + p.table_words - 64, 0, 64 * sizeof(uint32_t), al->stream));
   const size_t ncap = (size_t)p.cap;
   HIP_TRY(al, pool_alloc(al, (void**)&b->d_meta, ncap * sizeof(WfaPairMeta)));
@@ -286,7 +277,7 @@ static int cross_view_alloc(CrossRun& run) {
 static int cross_scratch_alloc(CrossRun& run) {
   wfa_hip_aligner* al = run.al;
   const CrossPlan& p = run.plan;
-  CrossScratch& sc = run.sc;
+  StreamScratch& sc = run.sc;
   const size_t ncap = (size_t)p.cap;
   if (p.any_bytes) {
     if (sc.alloc(&run.list_packed, ncap) || sc.alloc(&run.list_bytes, ncap) || sc.alloc(&run.d_row_bytes, p.row_bytes.size()) || sc.alloc(&run.d_col_flag, p.col_flag.size()))
@@ -474,31 +465,24 @@ static int cross_run_impl(wfa_hip_aligner* al, const wfa_hip_seqset* P, const wf
 }
 
 extern "C" wfa_hip_cross_t* wfa_hip_cross_run_k(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want, int k) {
-  if (!al) { g_error = "null aligner"; return nullptr; }
-  if (hipSetDevice(al->device) != hipSuccess) { al->err = "hipSetDevice failed"; g_error = al->err; return nullptr; }
+  if (!create_begin(al)) return nullptr;
   mailbox_release(al);
-  wfa_hip_cross* x = new wfa_hip_cross();
-  x->al = al;
-  al->live_batches += 1;
-  const int rc = cross_run_impl(al, patterns, texts, want, k, x);
-  if (rc != WFA_HIP_OK) { g_error = al->err; wfa_hip_cross_destroy(x); return nullptr; }
-  return x;
+  wfa_hip_cross* x = create_adopt(al, new wfa_hip_cross());
+  return create_done(al, x, cross_run_impl(al, patterns, texts, want, k, x), wfa_hip_cross_destroy);
 }
 
 extern "C" wfa_hip_cross_t* wfa_hip_cross_run(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* patterns, const wfa_hip_seqset_t* texts, int want) {
-  if (al && (want & WFA_HIP_CROSS_TOPK)) {
-    al->err = "want: WFA_HIP_CROSS_DENSE and / or WFA_HIP_CROSS_COMPLETED (top-k: wfa_hip_cross_run_k)"; g_error = al->err; return nullptr;
-  }
+  if (al && (want & WFA_HIP_CROSS_TOPK)) return fail_create(al, "want: WFA_HIP_CROSS_DENSE and / or WFA_HIP_CROSS_COMPLETED (top-k: wfa_hip_cross_run_k)");
   return wfa_hip_cross_run_k(al, patterns, texts, want, 0);
 }
 
 extern "C" int wfa_hip_cross_topk(wfa_hip_cross_t* x, int32_t* j, int32_t* score) {
   if (!x) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = x->al;
-  if (!(x->want & WFA_HIP_CROSS_TOPK)) { al->err = "the run was made without WFA_HIP_CROSS_TOPK"; return WFA_HIP_EINVAL; }
+  if (!(x->want & WFA_HIP_CROSS_TOPK)) return fail_inval(al, "the run was made without WFA_HIP_CROSS_TOPK");
   const size_t cells = (size_t)x->m * (size_t)x->k;
   if (cells == 0) return WFA_HIP_OK;
-  if (!j || !score) { al->err = "j/score outputs are required"; return WFA_HIP_EINVAL; }
+  if (!j || !score) return fail_inval(al, "j/score outputs are required");
   std::vector<uint64_t> keys(cells, 0ull);   // (no device list: no columns, every row is padding)
   if (x->d_topk) {
     HIP_TRY(al, hipSetDevice(al->device));
@@ -514,10 +498,10 @@ extern "C" int wfa_hip_cross_topk(wfa_hip_cross_t* x, int32_t* j, int32_t* score
 extern "C" int wfa_hip_cross_dense(wfa_hip_cross_t* x, int32_t* score, int32_t* status) {
   if (!x) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = x->al;
-  if (!(x->want & WFA_HIP_CROSS_DENSE)) { al->err = "the run was made without WFA_HIP_CROSS_DENSE"; return WFA_HIP_EINVAL; }
+  if (!(x->want & WFA_HIP_CROSS_DENSE)) return fail_inval(al, "the run was made without WFA_HIP_CROSS_DENSE");
   const size_t cells = (size_t)(x->m * x->n);
   if (cells == 0) return WFA_HIP_OK;
-  if (!score || !status) { al->err = "score/status outputs are required"; return WFA_HIP_EINVAL; }
+  if (!score || !status) return fail_inval(al, "score/status outputs are required");
   HIP_TRY(al, hipSetDevice(al->device));
   HIP_TRY(al, hipMemcpy(score, x->d_score, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
   HIP_TRY(al, hipMemcpy(status, x->d_status, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -527,7 +511,7 @@ extern "C" int wfa_hip_cross_dense(wfa_hip_cross_t* x, int32_t* score, int32_t* 
 extern "C" int wfa_hip_cross_completed(wfa_hip_cross_t* x, int64_t* count, int32_t* i, int32_t* j, int32_t* score) {
   if (!x || !count) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = x->al;
-  if (!(x->want & WFA_HIP_CROSS_COMPLETED)) { al->err = "the run was made without WFA_HIP_CROSS_COMPLETED"; return WFA_HIP_EINVAL; }
+  if (!(x->want & WFA_HIP_CROSS_COMPLETED)) return fail_inval(al, "the run was made without WFA_HIP_CROSS_COMPLETED");
   *count = x->count;
   if (x->count == 0) return WFA_HIP_OK;
   HIP_TRY(al, hipSetDevice(al->device));

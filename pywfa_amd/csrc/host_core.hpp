@@ -3,6 +3,8 @@
 // (hidden visibility: none of it enters the dynamic symbol table); the definitions are in wfa_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -218,6 +220,45 @@ struct wfa_hip_batch {
     }                                                                                          \
   } while (0)
 
+// ---- refusals: one message buffer (HIP_TRY's 512 bytes), one place per error channel -------------------------------------------------
+#define WFA_FORMAT_ERR(buf, fmt) char buf[512]; do { va_list ap_; va_start(ap_, fmt); vsnprintf(buf, sizeof(buf), fmt, ap_); va_end(ap_); } while (0)
+// an int entry refuses its arguments: al->err alone
+__attribute__((format(printf, 2, 3))) static inline int fail_inval(wfa_hip_aligner* al, const char* fmt, ...) {
+  WFA_FORMAT_ERR(buf, fmt);
+  al->err = buf;
+  return WFA_HIP_EINVAL;
+}
+// a creator refuses: g_error, and al->err where there is an aligner; converts to the null handle of any type
+__attribute__((format(printf, 2, 3))) static inline decltype(nullptr) fail_create(wfa_hip_aligner* al, const char* fmt, ...) {
+  WFA_FORMAT_ERR(buf, fmt);
+  if (al) al->err = buf;
+  g_error = buf;
+  return nullptr;
+}
+// one of the checks shared with the *_host entries (host_place.cpp and its kin: their last two parameters are (msg, cap)), its refusal in al->err
+template <class Check, class... A> static int check_inval(wfa_hip_aligner* al, Check check, A... args) {
+  char buf[512];
+  if (check(args..., buf, sizeof(buf)) == WFA_HIP_OK) return WFA_HIP_OK;
+  al->err = buf;
+  return WFA_HIP_EINVAL;
+}
+// a failed allocation of *p: HIP's error cleared, the pointer nulled, the message (bytes and what they were for) in al->err
+__attribute__((format(printf, 3, 4))) static inline int fail_alloc(wfa_hip_aligner* al, void** p, const char* fmt, ...) {
+  (void)hipGetLastError();
+  *p = nullptr;
+  WFA_FORMAT_ERR(buf, fmt);
+  al->err = buf;
+  return WFA_HIP_EDEVICE;
+}
+// "a finished batch of this aligner", as the entries that reduce a batch's results ask for it; `what`: the entry's prefix
+static inline int batch_of(wfa_hip_aligner* al, const wfa_hip_batch* b, const char* what, bool need_full) {
+  if (!b) return fail_inval(al, "%s: null batch", what);
+  if (b->al != al) return fail_inval(al, "%s: batch of another aligner", what);
+  if (need_full && b->cfg.scope != WFA_SCOPE_FULL) return fail_inval(al, "%s needs scope=full", what);
+  if (!b->ran) return fail_inval(al, "%s needs a finished run of the batch", what);
+  return WFA_HIP_OK;
+}
+
 // ---- wfa_hip.hip: the aligner's pool, lifetime and configuration ------------------------------------------------------------------
 hipError_t pool_alloc(wfa_hip_aligner* al, void** p, size_t bytes);
 void pool_release(wfa_hip_aligner* al, void* p);
@@ -272,5 +313,15 @@ struct ReduceTimer {
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
   }
 };
+
+// The end of a launch whose results (or whose caller's arrays) the stream still holds: the timer stopped, the stream synchronised, then
+// the two outcomes in this order: a failed launch's message, else the synchronisation's error.
+static inline int launch_end(wfa_hip_aligner* al, ReduceTimer* timer, int launch_rc, const char* failed) {
+  if (timer) timer->stop();
+  const hipError_t e = hipStreamSynchronize(al->stream);
+  if (launch_rc != 0) { al->err = failed; return WFA_HIP_EDEVICE; }
+  HIP_TRY(al, e);
+  return WFA_HIP_OK;
+}
 
 #pragma GCC visibility pop

@@ -764,7 +764,7 @@ static int staged_pack_upload(wfa_hip_aligner* al, wfa_hip_batch* b, const std::
     HIP_TRY(al, hipEventRecord(al->up_join, al->up_stream));
     HIP_TRY(al, hipStreamWaitEvent(stream, al->up_join, 0));
   }
-  if (failed.load() == 2) { al->err = "negative length or offset"; return WFA_HIP_EINVAL; }
+  if (failed.load() == 2) return fail_inval(al, "negative length or offset");
   if (failed.load()) { al->err = "pipelined upload failed"; return WFA_HIP_EDEVICE; }
   for (auto& v : bad) flagged->insert(flagged->end(), v.begin(), v.end());
   return WFA_HIP_OK;
@@ -1026,7 +1026,7 @@ static int scan_lengths(wfa_hip_aligner* al, const wfa_hip_config_t& c, const Ba
     s->max_width = std::max(s->max_width, pt.max_width); s->max_len = std::max(s->max_len, pt.max_len);
     s->packed_bytes += pt.packed; s->ops_bytes += pt.ops; s->blob_end = std::max(s->blob_end, pt.blob_end);
   }
-  if (s->total_words > 0xFFFFFFF0ull) { al->err = "batch too large: more than 2^32 packed words (split the batch)"; return WFA_HIP_EINVAL; }
+  if (s->total_words > 0xFFFFFFF0ull) return fail_inval(al, "batch too large: more than 2^32 packed words (split the batch)");
   // the metadata of a host-packed upload as 4 B per pair (16-bit lengths; the word offsets are rebuilt on the device) when no sequence
   // is longer than 65 535 bases (WFA_HIP_LEN16=0: the 16 B records)
   if (s->form == UploadForm::HostPacked && s->max_len < 65536 && knob(al, K_LEN16, 1) != 0) s->form = UploadForm::HostPacked16;
@@ -3063,7 +3063,7 @@ extern "C" int wfa_hip_batch_results(wfa_hip_batch_t* b, int32_t* score, int32_t
   if (rc != WFA_HIP_OK) return rc;
   const int64_t n = b->n;
   if (n == 0) return WFA_HIP_OK;
-  if (!score || !status) { al->err = "score/status outputs are required"; return WFA_HIP_EINVAL; }
+  if (!score || !status) return fail_inval(al, "score/status outputs are required");
   HIP_TRY(al, hipMemcpy(score, b->d_score, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
   HIP_TRY(al, hipMemcpy(status, b->d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
   const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
@@ -3076,7 +3076,7 @@ extern "C" int wfa_hip_batch_results(wfa_hip_batch_t* b, int32_t* score, int32_t
     else memset(cigar_begin, 0, (size_t)n * sizeof(int64_t));
   }
   if (full && cigar_ops) {
-    if (!cigar_off || !cigar_begin || !cigar_len) { al->err = "cigar_off/cigar_begin/cigar_len are required with cigar_ops"; return WFA_HIP_EINVAL; }
+    if (!cigar_off || !cigar_begin || !cigar_len) return fail_inval(al, "cigar_off/cigar_begin/cigar_len are required with cigar_ops");
     // the device regions are laid out back to back in pair order (plen+tlen bytes each); the caller's
     // regions may be spaced differently: copy whole, then re-base per pair when they differ
     // (a shard of a larger batch: the caller's regions are the device layout shifted by cigar_off[0])
@@ -3126,7 +3126,7 @@ extern "C" int64_t wfa_hip_batch_algorithmic_bytes(const wfa_hip_batch_t* b) {
 extern "C" int64_t wfa_hip_batch_rle_counts(wfa_hip_batch_t* b, int32_t* run_count, int32_t* locations) {
   if (!b) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = b->al;
-  if (b->cfg.scope != WFA_SCOPE_FULL) { al->err = "run-length encoding needs scope=full"; return WFA_HIP_EINVAL; }
+  if (b->cfg.scope != WFA_SCOPE_FULL) return fail_inval(al, "run-length encoding needs scope=full");
   int rc = wfa_hip_batch_sync(b);
   if (rc != WFA_HIP_OK) return rc;
   const int64_t n = b->n;
@@ -3160,10 +3160,10 @@ extern "C" int64_t wfa_hip_batch_rle_counts(wfa_hip_batch_t* b, int32_t* run_cou
 extern "C" int wfa_hip_batch_rle_runs(wfa_hip_batch_t* b, uint8_t* run_code, int32_t* run_len) {
   if (!b) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = b->al;
-  if (b->rle_total < 0) { al->err = "call wfa_hip_batch_rle_counts first"; return WFA_HIP_EINVAL; }
+  if (b->rle_total < 0) return fail_inval(al, "call wfa_hip_batch_rle_counts first");
   const int64_t n = b->n, total = b->rle_total;
   if (n == 0 || total == 0) return WFA_HIP_OK;
-  if (!run_code || !run_len) { al->err = "null output"; return WFA_HIP_EINVAL; }
+  if (!run_code || !run_len) return fail_inval(al, "null output");
   uint8_t* d_code = nullptr; int32_t* d_start = nullptr;
   HIP_TRY(al, pool_alloc(al, (void**)&d_code, (size_t)total));
   HIP_TRY(al, pool_alloc(al, (void**)&d_start, (size_t)total * 4));
@@ -3197,11 +3197,11 @@ static_assert(WFA_SUMMARY_COLS == WFA_HIP_SUMMARY_COLS, "columns of the kernels 
 extern "C" int wfa_hip_batch_summary(wfa_hip_batch_t* b, int32_t* summary) {
   if (!b) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = b->al;
-  if (b->cfg.scope != WFA_SCOPE_FULL) { al->err = "per-pair summary needs scope=full"; return WFA_HIP_EINVAL; }
-  if (!b->ran) { al->err = "per-pair summary needs a finished run of the batch"; return WFA_HIP_EINVAL; }
+  int rc = batch_of(al, b, "per-pair summary", true);
+  if (rc != WFA_HIP_OK) return rc;
   const int64_t n = b->n;
-  if (n > 0 && !summary) { al->err = "per-pair summary: null output"; return WFA_HIP_EINVAL; }
-  const int rc = wfa_hip_batch_sync(b);
+  if (n > 0 && !summary) return fail_inval(al, "per-pair summary: null output");
+  rc = wfa_hip_batch_sync(b);
   if (rc != WFA_HIP_OK) return rc;
   if (n == 0) return WFA_HIP_OK;
   HIP_TRY(al, hipSetDevice(al->device));
