@@ -499,7 +499,8 @@ int wfa_hip_ops_summary(const uint8_t* ops, int64_t ops_len, int32_t plen, int32
  * of texts[j[q]].
  *
  * wfa_hip_pileup_read copies the rows [start, start + len) of sequence `seq` into counts (len x WFA_HIP_PILEUP_COLS, row-major);
- * WFA_HIP_EINVAL when the range leaves the sequence.  wfa_hip_pileup_clear zeroes the table.
+ * WFA_HIP_EINVAL when the range leaves the sequence.  wfa_hip_pileup_clear zeroes the table (and drops the insertion log of a pileup
+ * that tracks insertions, keeping that setting: "insertions" below).
  */
 #define WFA_HIP_PILEUP_COLS 8   /* A, C, G, T, other, deleted, insertion-before, mismatch */
 typedef struct wfa_hip_pileup wfa_hip_pileup_t;
@@ -541,8 +542,8 @@ int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uint8_t* patte
  *   j, pos, ref = r, alt (-1 when !snv), depth, ref_count = c[r], alt_count (A; 0 when !snv), ins_count = c6
  * Sites come out in ascending (j, pos), always: the order does not depend on scheduling, two calls give identical rows.
  *
- * Out of scope: the pileup does not record WHICH bases were inserted, so a site says that, and how often, reads insert in front of a
- * base, not what they insert (align those few reads with CIGARs); quality values, strand bias, genotypes and multi-base events.
+ * A site says that, and how often, reads insert in front of a base; WHAT they insert is the allele row of "insertions" below, from a
+ * pileup made to track them.  Out of scope: quality values, strand bias, genotypes and multi-base events.
  *
  * The pileup keeps no reference letters and outlives its set, so both device calls take the set: the one the pileup was made over, or
  * one made again from the same sequences.  wfa_hip_pileup_calls writes out[0 .. len) for the rows [start, start + len) of sequence
@@ -568,6 +569,86 @@ int wfa_hip_pileup_sites(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts
 int wfa_hip_calls_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t min_depth, uint8_t* out);
 int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t seq, int64_t start,
                        int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows);
+
+/* ---- insertions: what the reads insert, one allele per reported row ---------------------------------------- */
+
+/*
+ * Column 6 counts THAT reads insert in front of a base.  A pileup that tracks insertions also keeps WHAT they insert, in a log on the
+ * device, and reduces it there to one allele per row.  It is opt-in: a pileup that does not ask for it behaves, allocates and launches
+ * exactly as before.  Integers only.
+ *
+ * RECORDS.  A pair contributes under exactly the conditions of wfa_hip_pileup_add (status 0, keep, its window inside its text).  Every
+ * maximal D run of its aligned core that the add counts into column 6 is one record (g, n, letters):
+ *   g        the global row t_start + h of text j: the row whose column 6 the run increments
+ *   n        the run's length
+ *   letters  col(pattern[v .. v + n)): 0..3 = A C G T, 4 = any other byte; the batch's pattern, so on the text's strand for a
+ *            reverse window
+ * So the number of records at a row equals that row's column 6.
+ *
+ * ALLELE OF A ROW.  The alleles are the distinct (n, letters) among the row's records, count(a) the multiplicity of allele a.  The
+ * row's allele is the one with the greatest count; ties go to the smaller n, then to the lexicographically smaller column sequence.
+ * The order is total: the result never depends on the order in which records were stored, added or split over adds.
+ *
+ * REPORTED ROWS, parameters min_depth >= 1 and min_permille in 0..1000; depth as in "calls and sites".  A row is reported iff
+ * depth >= min_depth and
+ *   min_permille > 0:   c6 >= 1 && 1000 * c6 >= min_permille * depth      (exactly the `ins` condition of SITE)
+ *   min_permille == 0:  2 * c6 > depth                                    (exactly bit 3 of CALL)
+ * Its row is WFA_HIP_INSERTION_COLS int32:
+ *   j, pos, depth, ins_count (= c6), allele_count, allele_len, alleles (the number of distinct alleles), overflow
+ * Rows come out in ascending (j, pos), always.  The alleles' letters follow in one byte array in row order, as ASCII A C G T N; row
+ * r's letters start at the sum of allele_len of the rows before it.  A row whose ins_count exceeds WFA_HIP_INS_MAX_READS is still
+ * reported, with overflow = 1 and allele_count = allele_len = alleles = 0: the limit (default 4096; read per call from the environment
+ * variable of that name, as WFA_HIP_CALLS_CHUNK is; at least 1) bounds the work of the one wave that serves a row, a documented limit
+ * like max_hits.
+ *
+ * wfa_hip_pileup_track_insertions turns tracking on or off.  Allowed only while the pileup is empty: fresh, or just after
+ * wfa_hip_pileup_clear; otherwise WFA_HIP_EINVAL with a message.  wfa_hip_pileup_clear drops the log and keeps the setting.
+ * wfa_hip_pileup_add, with tracking on, also appends the batch's records to the log: a count pass gives records and inserted bases per
+ * pair, an exclusive scan places them, the two totals are downloaded, the log grows by doubling, then every pair writes its runs at
+ * its scanned offset while the table is added to — no atomics for the log.  COST: ABOUT 24 BYTES PER RECORD AND 1 BYTE PER INSERTED
+ * BASE in HBM until the pileup is cleared or destroyed, 16 bytes per pair of scratch during the add, one more pass over the op strings,
+ * and the 16-byte download.  The log grows before anything is added: a failed growth returns WFA_HIP_EDEVICE, the message names the
+ * byte count, and neither the table nor the log has changed.  wfa_hip_pileup_insertion_stats gives the records and the inserted bases
+ * of the log (either pointer may be NULL); WFA_HIP_EINVAL on a pileup that does not track.
+ *
+ * wfa_hip_pileup_insertions follows the conventions of wfa_hip_pileup_sites: seq = -1 takes every sequence (start = 0, len = -1);
+ * *count and *bases_count are always the full numbers (rows, and letters of all rows); only the first min(*count, cap) rows are
+ * written, and only the letters of those rows that fit whole in bases_cap — nothing behind them is touched; cap = 0 and bases_cap = 0
+ * with NULL rows and bases is the counting call.  Two calls give identical bytes.  Kernels: csrc/wfa_insertions.hpp, k_pileup.hip (the
+ * record side), k_insertions.hip (rows selected by the chunk count / scan / scatter of the sites; a bucket per row sized from c6 by a
+ * scan; records find their row by binary search; a wave per row picks the allele; a scan over allele_len places the letters).
+ * WFA_HIP_EINVAL, nothing launched, nothing written: whatever wfa_hip_pileup_sites refuses (`texts` is taken and checked the same way
+ * although the rule needs no letters, so the call shape matches), with min_permille in 0..1000; a pileup that does not track ("... was
+ * not made to track insertions"); bases_cap < 0; a NULL count or bases_count; NULL bases with bases_cap > 0.
+ *
+ * Out of scope: quality values, strands, genotypes, left-normalising insertions across reads (reads that place the same inserted bases
+ * at different rows of a repeat are different records at different rows), more than one allele per row.
+ */
+#define WFA_HIP_INSERTION_COLS 8   /* j, pos, depth, ins_count, allele_count, allele_len, alleles, overflow */
+#define WFA_HIP_INS_MAX_READS 4096 /* the default of the limit; the environment variable of this name replaces it per call */
+int wfa_hip_pileup_track_insertions(wfa_hip_pileup_t* pileup, int on);
+int wfa_hip_pileup_insertion_stats(wfa_hip_pileup_t* pileup, int64_t* records, int64_t* bases);
+int wfa_hip_pileup_insertions(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                              int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows /* cap x 8, nullable */,
+                              int64_t bases_cap, int64_t* bases_count, uint8_t* bases /* bases_cap, nullable */);
+
+/* Host only, needs no GPU.  wfa_hip_ops_insertions: ONE pair's records by the rule above, from its op string and its ASCII pattern
+ * bytes: recs[r] = (h, n, offset), h window-relative (the row is t_start + h), offset the first of the record's n column bytes (0..4)
+ * in cols.  *count and *cols_count are the full numbers; the first min(*count, cap) records are written, and of those the column bytes
+ * of the records that fit whole in cols_cap; nothing behind them is touched.  Refused (WFA_HIP_EINVAL, nothing written): what
+ * wfa_hip_ops_pileup refuses, a negative capacity, a NULL count, NULL recs / cols with a capacity > 0.
+ * wfa_hip_insertions_host: the allele rule on `len` rows as wfa_hip_pileup_read returns them (counts: len x 8) and the records of
+ * those rows: record r lies on row rec_row[r] (relative to the first of the len rows; records outside are skipped) and has the
+ * rec_n[r] column bytes cols[rec_off[r] ..].  Rows are numbered j = seq, pos = start + row; outputs and capacities as
+ * wfa_hip_pileup_insertions; WFA_HIP_INS_MAX_READS is read from the environment in the same way.  Refused (WFA_HIP_EINVAL, nothing
+ * written): what wfa_hip_sites_host refuses (min_permille in 0..1000), a negative count or capacity, a missing pointer, a record whose
+ * column bytes leave cols[0 .. ncols). */
+int wfa_hip_ops_insertions(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen, int64_t cap,
+                           int64_t* count, int32_t* recs /* cap x 3 */, int64_t cols_cap, int64_t* cols_count, uint8_t* cols);
+int wfa_hip_insertions_host(const int32_t* counts, int64_t len, int32_t seq, int64_t start, int32_t min_depth, int32_t min_permille,
+                            int64_t nrec, const int64_t* rec_row, const int32_t* rec_n, const int64_t* rec_off, const uint8_t* cols,
+                            int64_t ncols, int64_t cap, int64_t* count, int32_t* rows, int64_t bases_cap, int64_t* bases_count,
+                            uint8_t* bases);
 
 /* ---- placement: one row per read from the hits of any number of batches ---------------------------------- */
 

@@ -135,6 +135,11 @@ SIGNATURES = {
     "wfa_hip_pileup_sites": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i64, _i64p, _vp]),
     "wfa_hip_calls_host": (_CTYPES, [_vp, _vp, _i64, _i32, _vp]),
     "wfa_hip_sites_host": (_CTYPES, [_vp, _vp, _i64, _i32, _i64, _i32, _i32, _i64, _i64p, _vp]),
+    "wfa_hip_pileup_track_insertions": (_CTYPES, [_vp, _int]),
+    "wfa_hip_pileup_insertion_stats": (_CTYPES, [_vp, _i64p, _i64p]),
+    "wfa_hip_pileup_insertions": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i64, _i64p, _vp, _i64, _i64p, _vp]),
+    "wfa_hip_ops_insertions": (_CTYPES, [_vp, _i64, _vp, _i32, _i32, _i64, _i64p, _vp, _i64, _i64p, _vp]),
+    "wfa_hip_insertions_host": (_CTYPES, [_vp, _i64, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64p, _vp, _i64, _i64p, _vp]),
     "wfa_hip_placer_create": (_vp, [_vp, _i64]),
     "wfa_hip_placer_add": (_CTYPES, [_vp] * 6),
     "wfa_hip_placer_add_hits": (_CTYPES, [_vp, _i64] + [_vp] * 7),
@@ -161,6 +166,9 @@ CALL_CODES = ("A", "C", "G", "T", "other", "del", "no call")   # the low 3 bits 
 CALL_NONE, CALL_INS = 6, 8
 SITE_COLS = 8
 SITE_COLUMNS = ("j", "pos", "ref", "alt", "depth", "ref_count", "alt_count", "ins_count")
+INSERTION_COLS = 8
+INSERTION_COLUMNS = ("j", "pos", "depth", "ins_count", "allele_count", "allele_len", "alleles", "overflow")
+INS_MAX_READS = 4096   # the default of WFA_HIP_INS_MAX_READS
 PLACE_COLS = 8
 PLACE_COLUMNS = ("hit", "score", "second", "mapq", "hits", "ties", "text_start", "text_end")
 PLACE_NOT_ELIGIBLE, PLACE_OTHER_LOCUS, PLACE_SAME_LOCUS, PLACE_PRIMARY = 0, 1, 2, 3   # the flag byte of a hit
@@ -527,6 +535,59 @@ def ops_pileup(ops, pattern, tlen, rows=None):
     return rows
 
 
+def _letters_written(rows, bases_cap):
+    """The letters an insertions call wrote for ``rows`` into ``bases_cap`` bytes: those of the rows that fit whole."""
+    ends = np.cumsum(rows[:, 5].astype(np.int64)) if len(rows) else np.zeros(0, np.int64)
+    fit = ends[ends <= bases_cap]
+    return int(fit[-1]) if len(fit) else 0
+
+
+def ops_insertions(ops, pattern, tlen):
+    """wfa_hip_ops_insertions (host only): one pair's insertion records from its op string and its ASCII pattern:
+    ``(recs, cols)``, recs int32 of shape (records, 3) = (h, n, offset), cols the records' column bytes (0..4) back to back."""
+    ops = np.frombuffer(bytes(ops), dtype=np.uint8) if not isinstance(ops, np.ndarray) else np.ascontiguousarray(ops, dtype=np.uint8)
+    pattern = np.frombuffer(bytes(pattern), dtype=np.uint8) if not isinstance(pattern, np.ndarray) else np.ascontiguousarray(pattern, dtype=np.uint8)
+    head = (_ptr(ops) if ops.size else None, ops.size, _ptr(pattern) if pattern.size else None, pattern.size, int(tlen))
+    count, ncols = ctypes.c_int64(0), ctypes.c_int64(0)
+    if lib().wfa_hip_ops_insertions(*head, 0, ctypes.byref(count), None, 0, ctypes.byref(ncols), None) != OK:
+        raise ValueError("wfa_hip_ops_insertions: invalid arguments (an op string that outruns its pair?)")
+    recs = np.zeros((count.value, 3), np.int32)
+    cols = np.zeros(ncols.value, np.uint8)
+    if count.value:
+        lib().wfa_hip_ops_insertions(*head, count.value, ctypes.byref(count), _ptr(recs), ncols.value, ctypes.byref(ncols), _ptr_or_null(cols))
+    return recs, cols
+
+
+def insertions_host(counts, rec_row, rec_n, rec_off, cols, seq=0, start=0, min_depth=1, min_permille=500, cap=None, bases_cap=None):
+    """wfa_hip_insertions_host (host only): ``(count, rows, bases_count, bases)`` as ``Pileup.insertions`` gives them, for the rows
+    ``counts`` (int32, shape (len, 8)) and the records of those rows (row relative to the first, length, offset into ``cols``)."""
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    if counts.ndim != 2 or counts.shape[1] != PILEUP_COLS:
+        raise ValueError("counts: int32 of shape (len, 8)")
+    rec_row = np.ascontiguousarray(rec_row, dtype=np.int64)
+    rec_n = np.ascontiguousarray(rec_n, dtype=np.int32)
+    rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+    cols = np.ascontiguousarray(cols, dtype=np.uint8)
+    if not rec_row.shape == rec_n.shape == rec_off.shape or rec_row.ndim != 1:
+        raise ValueError("rec_row, rec_n and rec_off: one value per record")
+    head = (_ptr_or_null(counts), counts.shape[0], int(seq), int(start), int(min_depth), int(min_permille), rec_row.size,
+            _ptr_or_null(rec_row), _ptr_or_null(rec_n), _ptr_or_null(rec_off), _ptr_or_null(cols), cols.size)
+    what = f"wfa_hip_insertions_host: invalid arguments (min_depth = {min_depth}, min_permille = {min_permille}, cap = {cap}, bases_cap = {bases_cap})"
+    count, nbases = ctypes.c_int64(0), ctypes.c_int64(0)
+    if cap is None or bases_cap is None:
+        if lib().wfa_hip_insertions_host(*head, 0, ctypes.byref(count), None, 0, ctypes.byref(nbases), None) != OK:
+            raise ValueError(what)
+        cap = count.value if cap is None else cap
+        bases_cap = nbases.value if bases_cap is None else bases_cap
+    rows = np.zeros((max(int(cap), 0), INSERTION_COLS), np.int32)
+    bases = np.zeros(max(int(bases_cap), 0), np.uint8)
+    if lib().wfa_hip_insertions_host(*head, int(cap), ctypes.byref(count), _ptr_or_null(rows), int(bases_cap), ctypes.byref(nbases),
+                                     _ptr_or_null(bases)) != OK:
+        raise ValueError(what)
+    rows = rows[:min(count.value, rows.shape[0])]
+    return count.value, rows, nbases.value, bases[:_letters_written(rows, bases.shape[0])]
+
+
 def _calls_rows(counts, ref):
     counts = np.ascontiguousarray(counts, dtype=np.int32)
     ref = np.frombuffer(bytes(ref), dtype=np.uint8) if not isinstance(ref, np.ndarray) else np.ascontiguousarray(ref, dtype=np.uint8)
@@ -866,9 +927,10 @@ class CrossRun(_Handle):
 
 class Pileup(_Handle):
     """Per-base counters over a text SeqSet, resident in HBM (wfa_hip_pileup_t): 32 bytes per text base, int32 counters without an
-    overflow check.  Stays valid after the set is closed."""
+    overflow check.  Stays valid after the set is closed.  ``tracking``: whether it keeps the insertion log (``track_insertions``)."""
 
     _destroy = "wfa_hip_pileup_destroy"
+    tracking = False
 
     def __init__(self, aligner, texts):
         if not texts._h:
@@ -927,6 +989,35 @@ class Pileup(_Handle):
 
     def clear(self):
         self._call("wfa_hip_pileup_clear", self._h)
+
+    def track_insertions(self, on=True):
+        """wfa_hip_pileup_track_insertions: keep (or stop keeping) what the reads insert; only while the pileup is empty."""
+        self._call("wfa_hip_pileup_track_insertions", self._h, 1 if on else 0)
+        self.tracking = bool(on)
+
+    def insertion_stats(self):
+        """wfa_hip_pileup_insertion_stats: ``(records, inserted bases)`` of the log."""
+        records, bases = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._call("wfa_hip_pileup_insertion_stats", self._h, ctypes.byref(records), ctypes.byref(bases))
+        return records.value, bases.value
+
+    def insertions(self, texts, seq=-1, start=0, length=-1, min_depth=1, min_permille=500, cap=None, bases_cap=None):
+        """wfa_hip_pileup_insertions: ``(count, rows, bases_count, bases)``; rows int32 of shape (min(count, cap), 8) in ascending
+        (j, pos), bases the ASCII letters of the rows' alleles back to back (uint8, as many as were written).  A capacity of None: a
+        counting call, then one with the exact capacities.  seq = -1: every sequence; min_permille = 0: the majority rule."""
+        args = (self._h, texts._h, int(seq), int(start), int(length), int(min_depth), int(min_permille))
+        count, nbases = ctypes.c_int64(0), ctypes.c_int64(0)
+        if cap is None or bases_cap is None:
+            self._call("wfa_hip_pileup_insertions", *args, 0, ctypes.byref(count), None, 0, ctypes.byref(nbases), None)
+            cap = count.value if cap is None else cap
+            bases_cap = nbases.value if bases_cap is None else bases_cap
+        rows = np.zeros((max(int(cap), 0), INSERTION_COLS), np.int32)
+        bases = np.zeros(max(int(bases_cap), 0), np.uint8)
+        if cap != 0:
+            self._call("wfa_hip_pileup_insertions", *args, int(cap), ctypes.byref(count), _ptr_or_null(rows), int(bases_cap),
+                       ctypes.byref(nbases), _ptr_or_null(bases))
+        rows = rows[:min(count.value, rows.shape[0])]
+        return count.value, rows, nbases.value, bases[:_letters_written(rows, bases.shape[0])]
 
 
 class Placer(_Handle):

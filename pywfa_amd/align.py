@@ -370,11 +370,14 @@ class Pileup(_Closing):
     A, C, G, T or another letter, reads that delete the base, reads that insert in front of it, reads that mismatch (these are also
     under their letter).  ``depth(j)``: the reads whose aligned core covers each base.  Counters are int32 and not checked for
     overflow; the table takes 32 bytes per text base until ``close()`` (or the end of the ``with`` block).  ``calls`` / ``consensus`` /
-    ``sites`` reduce the table on the GPU against the reference letters: a byte per base or a row per variant site comes back."""
+    ``sites`` reduce the table on the GPU against the reference letters: a byte per base or a row per variant site comes back.  A
+    pileup made with ``insertions=True`` also keeps what the reads insert (about 24 bytes per insertion and 1 byte per inserted base
+    on the GPU): ``insertions`` gives one allele per insertion site, ``consensus(insertions=True)`` splices them in."""
 
     COLUMNS = _native.PILEUP_COLUMNS
     CALL_CODES = _native.CALL_CODES
     SITE_COLUMNS = _native.SITE_COLUMNS
+    INSERTION_COLUMNS = _native.INSERTION_COLUMNS
     _OWNS = "_pileup"
 
     def __init__(self, native_pileup, score, status, aligner=None):
@@ -452,11 +455,62 @@ class Pileup(_Closing):
         raw = self._with_texts(p, texts, min_depth, lambda t: p.calls(t, j, start, stop - start, int(min_depth)))
         return dict(code=raw & 7, ins=(raw & _native.CALL_INS) != 0)
 
-    def consensus(self, texts, j, start=0, stop=None, min_depth=1):
+    def _tracking(self):
+        """The open native pileup, which must have been made with ``insertions=True``."""
+        p = self._open()
+        if not p.tracking:
+            raise ValueError("this pileup was not made to track insertions: make it with pileup(..., insertions=True)")
+        return p
+
+    def consensus(self, texts, j, start=0, stop=None, min_depth=1, insertions=False):
         """The called sequence of the rows [start, stop) of text ``j`` as a ``str``: A, C, G, T; N for another letter and for no call;
-        deleted bases are left out.  The insertion flag of ``calls`` is ignored: the pileup does not record which bases were inserted."""
-        code = self.calls(texts, j, start, stop, min_depth)["code"]
-        return _CALL_LETTERS[code[code != 5]].tobytes().decode()
+        deleted bases are left out.  ``insertions=False``: the insertion flag of ``calls`` is ignored.  ``insertions=True`` (a pileup
+        made with ``insertions=True``): in front of every base of the range whose ``calls()["ins"]`` is set — the first of the range
+        and a base that is itself called deleted included — the allele most of the inserting reads carry (``insertions`` under the
+        majority rule) is spliced in; a row over ``WFA_HIP_INS_MAX_READS`` splices nothing.  The splice is made on the host from the
+        two small results."""
+        if not insertions:
+            code = self.calls(texts, j, start, stop, min_depth)["code"]
+            return _CALL_LETTERS[code[code != 5]].tobytes().decode()
+        p = self._tracking()
+        j, start, stop = self._range(p, j, start, stop)
+
+        def both(t):
+            return p.calls(t, j, start, stop - start, int(min_depth)), p.insertions(t, j, start, stop - start, int(min_depth), 0)
+
+        raw, (_, rows, _, letters) = self._with_texts(p, texts, min_depth, both)
+        code = raw & 7
+        # a row's letters go in front of its base; then the deleted bases (not the letters in front of them) are dropped
+        at = np.repeat(rows[:, 1] - start, rows[:, 5])
+        seq = np.insert(_CALL_LETTERS[code], at, letters)
+        return seq[np.insert(code != 5, at, True)].tobytes().decode()
+
+    def insertions(self, texts, j=None, start=0, stop=None, min_depth=1, min_frac=0.5):
+        """What the reads insert, reduced on the GPU to one allele per site (a pileup made with ``insertions=True``): a dict of int32
+        arrays ``INSERTION_COLUMNS`` in ascending (j, pos), plus ``seq``, a list of ``str``: per row the inserted bases (A, C, G, T, N
+        for another letter) in front of base ``pos`` of text ``j``.  Rows: the bases covered by at least ``min_depth`` reads where at
+        least ``min_frac`` of them insert (the ``ins`` condition of ``sites``; ``min_frac``, ``j``, ``start``, ``stop`` as there).  The
+        allele is the inserted sequence most of the row's inserting reads carry (``allele_count`` of ``ins_count``; ties go to the
+        shorter, then to the alphabetically smaller in the order A C G T N); ``alleles``: how many different ones they carry.  A row
+        with more than ``WFA_HIP_INS_MAX_READS`` (4096) inserting reads has ``overflow`` = 1, zeros and ``""``.  Qualities, strands,
+        genotypes, left-normalising insertions across reads and more than one allele per row are out of scope."""
+        p = self._tracking()
+        if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
+            raise ValueError(f"min_frac = {min_frac!r} is out of range (0.001 .. 1)")
+        permille = int(round(float(min_frac) * 1000))
+        if j is None:
+            if start != 0 or stop is not None:
+                raise ValueError("j = None takes every text: start and stop go with one text")
+            seq, start, length = -1, 0, -1
+        else:
+            seq, start, stop = self._range(p, j, start, stop)
+            length = stop - start
+        _, rows, _, letters = self._with_texts(p, texts, min_depth, lambda t: p.insertions(t, seq, start, length, int(min_depth), permille))
+        out = _columns(rows, self.INSERTION_COLUMNS)
+        text = letters.tobytes().decode()
+        ends = np.cumsum(rows[:, 5].astype(np.int64))
+        out["seq"] = [text[int(e - n):int(e)] for e, n in zip(ends, rows[:, 5])]
+        return out
 
     def sites(self, texts, j=None, start=0, stop=None, min_depth=1, min_frac=0.5):
         """The bases where the reads disagree with the reference, found on the GPU (only their rows come back): a dict of int32 arrays
@@ -465,7 +519,7 @@ class Pileup(_Closing):
         ``CALL_CODES``, 5 = deleted; ``alt_count``), or where at least ``min_frac`` of them insert in front of the base (``ins_count``;
         ``alt`` = -1 and ``alt_count`` = 0 when only this holds).  ``min_frac`` is rounded to permille.  ``j=None``: every text (then
         ``start`` / ``stop`` must be left alone); otherwise the rows [start, stop) of text ``j``.  What was inserted, qualities, strands
-        and genotypes are out of scope: align the few reads of a site with CIGARs."""
+        and genotypes are out of scope; what was inserted: ``insertions``, on a pileup made with ``insertions=True``."""
         p = self._open()
         if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
             raise ValueError(f"min_frac = {min_frac!r} is out of range (0.001 .. 1)")
@@ -1240,15 +1294,17 @@ class WavefrontAligner:
             return w.run(summary=summary)
 
     def pileup(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
-               text_len=None, reverse=None, min_score=None):
+               text_len=None, reverse=None, min_score=None, insertions=False):
         """Align the listed windows as ``align_windows`` does (same arguments, same checks; scope must be "full") and pile the
         alignments up over the TEXT sequences on the GPU: the patterns are reads, the texts references.  Every pair whose status is
         0 (and whose score is at least ``min_score``, when given) adds the ops of its aligned core — first M to last M — to the
         text bases they cover; neither op strings nor their run-length encoding leave the device (csrc/wfa_pileup.hpp).
-        ``texts=None`` piles up over ``patterns``.
+        ``texts=None`` piles up over ``patterns``.  ``insertions=True``: the pileup also keeps what the reads insert (a log on the
+        GPU, about 24 bytes per insertion and 1 byte per inserted base, and a second pass over the op strings), for
+        ``Pileup.insertions`` and ``Pileup.consensus(insertions=True)``.
 
         Returns a ``Pileup`` (``score``, ``status``, ``counts(j)``, ``depth(j)``, ``calls()``, ``consensus()``, ``sites()``,
-        ``close()``; a context manager), which stays
+        ``insertions()``, ``close()``; a context manager), which stays
         valid after the sets are closed.  With ``devices=[...]`` the first device runs it."""
         if self._cfg.scope != 1:
             raise ValueError("pileup needs scope='full'")
@@ -1257,6 +1313,8 @@ class WavefrontAligner:
         with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
             jj, ts = w.arrays[1], w.arrays[4]
             table = w.attach(self._native.pileup(w.text_set), keep=True)
+            if insertions:
+                table.track_insertions(True)
 
             def add(rb, lo, hi, score, status):
                 keep = None if min_score is None else (score >= int(min_score))

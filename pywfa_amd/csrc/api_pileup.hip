@@ -1,6 +1,6 @@
 // api_pileup.hip — pileups and calls of libwfa_hip.so (the C ABI declared in include/wfa_hip.h).
 #include "host_sets.hpp"
-#include "wfa_calls.hpp"
+#include "wfa_insertions.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // pileup over a text set (include/wfa_hip.h; csrc/wfa_pileup.hpp, k_pileup.hip)
@@ -14,6 +14,10 @@ struct wfa_hip_pileup {
   std::vector<int64_t> h_off;          // first base of a sequence in a plane
   int32_t* d_table = nullptr;          // WFA_PILEUP_COLS planes of `total` counters (its own allocation: up to 32 bytes x every text base)
   int64_t* d_off = nullptr; int32_t* d_len = nullptr;
+  // the insertion log (include/wfa_hip.h, "insertions"; csrc/wfa_insertions.hpp): its own allocations, grown by doubling
+  bool track = false, added = false;   // added: an add since the create or the last clear
+  wfa::InsRecord* d_rec = nullptr; uint8_t* d_ins = nullptr;
+  int64_t nrec = 0, nins = 0, cap_rec = 0, cap_ins = 0;
 };
 
 extern "C" void wfa_hip_pileup_destroy(wfa_hip_pileup_t* p) {
@@ -21,6 +25,8 @@ extern "C" void wfa_hip_pileup_destroy(wfa_hip_pileup_t* p) {
   wfa_hip_aligner* al = p->al;
   (void)hipSetDevice(al->device);
   if (p->d_table) (void)hipFree(p->d_table);
+  if (p->d_rec) (void)hipFree(p->d_rec);
+  if (p->d_ins) (void)hipFree(p->d_ins);
   pool_release(al, p->d_off); pool_release(al, p->d_len);
   destroy_end(p);
 }
@@ -60,7 +66,76 @@ extern "C" int wfa_hip_pileup_clear(wfa_hip_pileup_t* p) {
   HIP_TRY(al, hipSetDevice(al->device));
   HIP_TRY(al, hipMemsetAsync(p->d_table, 0, (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t), al->stream));
   HIP_TRY(al, hipStreamSynchronize(al->stream));
+  p->nrec = p->nins = 0;   // (the log's blocks stay for the next adds)
+  p->added = false;
   return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_track_insertions(wfa_hip_pileup_t* p, int on) {
+  if (!p) return WFA_HIP_EINVAL;
+  if (p->added) return fail_inval(p->al, "pileup: insertion tracking is chosen while the pileup is empty (fresh, or just cleared); this one has been added to");
+  p->track = on != 0;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_insertion_stats(wfa_hip_pileup_t* p, int64_t* records, int64_t* bases) {
+  if (!p) return WFA_HIP_EINVAL;
+  if (!p->track) return fail_inval(p->al, "pileup: this pileup was not made to track insertions");
+  if (records) *records = p->nrec;
+  if (bases) *bases = p->nins;
+  return WFA_HIP_OK;
+}
+
+// room for `need` elements in a block of the log that holds `have` of them: a new block of twice the size (of the exact size when that
+// fails), the old contents copied over.  A failure leaves the block as it was.
+template <class T> static int ins_log_grow(wfa_hip_aligner* al, T** block, int64_t* cap, int64_t have, int64_t need, const char* what) {
+  if (need <= *cap) return WFA_HIP_OK;
+  T* fresh = nullptr;
+  int64_t want = std::max<int64_t>({need, 2 * *cap, 1024});
+  if (hipMalloc((void**)&fresh, (size_t)want * sizeof(T)) != hipSuccess) {
+    (void)hipGetLastError();
+    want = need;
+    if (hipMalloc((void**)&fresh, (size_t)want * sizeof(T)) != hipSuccess)
+      return fail_alloc(al, (void**)&fresh, "pileup insertion log: hipMalloc of %zu bytes failed (%s, %lld of them)", (size_t)want * sizeof(T), what, (long long)want);
+  }
+  if (have > 0) {
+    const hipError_t e = hipMemcpyAsync(fresh, *block, (size_t)have * sizeof(T), hipMemcpyDeviceToDevice, al->stream);
+    const hipError_t e2 = hipStreamSynchronize(al->stream);
+    if (e != hipSuccess || e2 != hipSuccess) { (void)hipFree(fresh); HIP_TRY(al, e); HIP_TRY(al, e2); }
+  }
+  if (*block) (void)hipFree(*block);
+  *block = fresh; *cap = want;
+  return WFA_HIP_OK;
+}
+
+// An add with tracking on (csrc/wfa_insertions.hpp): count, the two scans, the 16-byte download, the growth, then the table kernel in its
+// tracking form.  Nothing is added before the log has its room.
+static int pileup_add_tracked(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a) {
+  wfa_hip_aligner* al = p->al;
+  const size_t n = (size_t)a.npairs;
+  wfa::InsLogArgs g;
+  memset(&g, 0, sizeof(g));
+  if (sc.alloc(&g.pair_count, n) || sc.alloc(&g.rec_off, n + 1) || sc.alloc(&g.base_off, n + 1)) return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipMemsetAsync(g.pair_count, 0, n * sizeof(wfa::InsPairCount), al->stream));
+  uint64_t totals[2] = {0, 0};
+  {
+    ReduceTimer timer(al, "pileup insertion count", a.npairs);
+    const int lrc = wfa::launch_pileup_count(a, g, al->cu_count, al->stream);
+    timer.stop();
+    if (lrc != 0) { al->err = "pileup insertion count kernel launch failed"; return WFA_HIP_EDEVICE; }
+    if (sc.download(&totals[0], g.rec_off + n, 1) || sc.download(&totals[1], g.base_off + n, 1)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+  }
+  int rc = ins_log_grow(al, &p->d_rec, &p->cap_rec, p->nrec, p->nrec + (int64_t)totals[0], "records of 24 bytes");
+  if (rc == WFA_HIP_OK) rc = ins_log_grow(al, &p->d_ins, &p->cap_ins, p->nins, p->nins + (int64_t)totals[1], "inserted bases of 1 byte");
+  if (rc != WFA_HIP_OK) return rc;
+  g.records = p->d_rec; g.bases = p->d_ins;
+  g.rec_base = p->nrec; g.base_base = p->nins; g.rec_cap = p->cap_rec; g.base_cap = p->cap_ins;
+  ReduceTimer timer(al, "pileup tracked", a.npairs);
+  p->added = true;
+  rc = launch_end(al, &timer, wfa::launch_pileup_track(a, g, al->cu_count, al->stream), "pileup kernel launch failed");
+  if (rc == WFA_HIP_OK) { p->nrec += (int64_t)totals[0]; p->nins += (int64_t)totals[1]; }
+  return rc;
 }
 
 extern "C" int wfa_hip_pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep) {
@@ -94,7 +169,9 @@ extern "C" int wfa_hip_pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const
   a.meta = b->d_meta; a.words = b->d_words; a.bytes = b->d_bytes; a.pboff = b->d_pboff; a.flags = b->d_flags;
   a.npairs = n; a.j = d_j; a.t_start = d_ts; a.keep = d_keep;
   a.seq_off = p->d_off; a.seq_len = p->d_len; a.nseq = p->nseq; a.total = p->total; a.table = p->d_table;
+  if (p->track) return pileup_add_tracked(p, sc, a);
   ReduceTimer timer(al, "pileup", n);
+  p->added = true;
   return launch_end(al, &timer, wfa::launch_pileup(a, al->cu_count, al->stream), "pileup kernel launch failed");   // (the caller's arrays are read by the copies above)
 }
 
@@ -131,7 +208,7 @@ static_assert(WFA_SITE_COLS == WFA_HIP_SITE_COLS, "columns of the kernels and of
 // the checks the two calls share: the set is the pileup's (same aligner, same lengths), the parameters, the range.  On success
 // *g0 / *n are the run of global base indices (seq = -1, sites only: every base).
 static int calls_check(wfa_hip_pileup* p, const wfa_hip_seqset_t* T, bool sites, int32_t seq, int64_t start, int64_t len, int32_t min_depth,
-                       int32_t min_permille, int64_t cap, int64_t* g0, int64_t* n) {
+                       int32_t min_permille, int64_t cap, int64_t* g0, int64_t* n, int32_t permille_lo = 1) {
   wfa_hip_aligner* al = p->al;
   if (!T || T->al != al) return fail_inval(al, "sequence set of another aligner");
   if (T->n != p->nseq) return fail_inval(al, "pileup: the set holds %lld sequences, the pileup was made over %lld", (long long)T->n, (long long)p->nseq);
@@ -140,7 +217,8 @@ static int calls_check(wfa_hip_pileup* p, const wfa_hip_seqset_t* T, bool sites,
       return fail_inval(al, "pileup: sequence %lld of the set has %lld bases, the pileup was made over %lld", (long long)k,
                         (long long)T->h_len[(size_t)k], (long long)p->h_len[(size_t)k]);
   if (min_depth < 1) return fail_inval(al, "pileup: min_depth = %d is out of range (at least 1)", (int)min_depth);
-  if (sites && (min_permille < 1 || min_permille > 1000)) return fail_inval(al, "pileup: min_permille = %d is out of range (1 .. 1000)", (int)min_permille);
+  if (sites && (min_permille < permille_lo || min_permille > 1000))
+    return fail_inval(al, "pileup: min_permille = %d is out of range (%d .. 1000)", (int)min_permille, (int)permille_lo);
   if (sites && cap < 0) return fail_inval(al, "pileup: cap = %lld is negative", (long long)cap);
   if (sites && seq == -1) {
     if (start != 0 || len != -1)
@@ -168,6 +246,16 @@ static wfa::CallsArgs calls_args(const wfa_hip_pileup* p, const wfa_hip_seqset_t
   a.table = p->d_table; a.total = p->total; a.ref = T->d_bytes; a.g0 = g0; a.n = n; a.min_depth = min_depth; a.min_permille = min_permille;
   a.seq_off = p->d_off; a.nseq = p->nseq;
   return a;
+}
+
+// the chunks of a run and their two arrays.  Bases per chunk: read per call, a multiple of 64 in 64 .. 2^20
+static int calls_chunks(StreamScratch& sc, wfa::CallsArgs* a) {
+  const char* env = getenv("WFA_HIP_CALLS_CHUNK");
+  const int64_t asked = env && *env ? atoll(env) : 4096;
+  a->chunk = std::min<int64_t>(1 << 20, std::max<int64_t>(64, (std::min<int64_t>(asked, 1 << 20) + 63) / 64 * 64));
+  a->chunks = (a->n + a->chunk - 1) / a->chunk;
+  if (sc.alloc(&a->chunk_count, (size_t)a->chunks) || sc.alloc(&a->chunk_off, (size_t)a->chunks + 1)) return WFA_HIP_EDEVICE;
+  return WFA_HIP_OK;
 }
 
 extern "C" int wfa_hip_pileup_calls(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
@@ -201,14 +289,9 @@ extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t*
   HIP_TRY(al, hipStreamSynchronize(al->stream));
   *count = 0;
   if (n == 0) return WFA_HIP_OK;
-  // bases per chunk: read per call, a multiple of 64 in 64 .. 2^20
-  const char* env = getenv("WFA_HIP_CALLS_CHUNK");
-  const int64_t asked = env && *env ? atoll(env) : 4096;
   StreamScratch sc{al};
   wfa::CallsArgs a = calls_args(p, texts, g0, n, min_depth, min_permille);
-  a.chunk = std::min<int64_t>(1 << 20, std::max<int64_t>(64, (std::min<int64_t>(asked, 1 << 20) + 63) / 64 * 64));
-  a.chunks = (n + a.chunk - 1) / a.chunk;
-  if (sc.alloc(&a.chunk_count, (size_t)a.chunks) || sc.alloc(&a.chunk_off, (size_t)a.chunks + 1)) return WFA_HIP_EDEVICE;
+  if (calls_chunks(sc, &a)) return WFA_HIP_EDEVICE;
   uint64_t total = 0;
   {
     ReduceTimer timer(al, "sites count", n, "bases");
@@ -221,4 +304,74 @@ extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t*
   if (sc.alloc(&a.rows, (size_t)a.cap * WFA_SITE_COLS)) return WFA_HIP_EDEVICE;
   ReduceTimer timer(al, "sites scatter", n, "bases");
   return calls_launched(sc, timer, wfa::launch_sites_scatter(a, al->stream), "sites scatter kernel launch failed", rows, a.rows, (size_t)a.cap * WFA_SITE_COLS);
+}
+
+// ---- what the reads insert: one allele per reported row (include/wfa_hip.h, "insertions"; csrc/wfa_insertions.hpp, k_insertions.hip) ------
+static_assert(WFA_INSERTION_COLS == WFA_HIP_INSERTION_COLS, "columns of the kernels and of the ABI");
+
+extern "C" int wfa_hip_pileup_insertions(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                         int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows,
+                                         int64_t bases_cap, int64_t* bases_count, uint8_t* bases) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  int64_t g0 = 0, n = 0;
+  const int rc = calls_check(p, texts, true, seq, start, len, min_depth, min_permille, cap, &g0, &n, 0);
+  if (rc != WFA_HIP_OK) return rc;
+  if (!p->track) return fail_inval(al, "pileup: this pileup was not made to track insertions");
+  if (bases_cap < 0) return fail_inval(al, "pileup: bases_cap = %lld is negative", (long long)bases_cap);
+  if (!count || !bases_count) return fail_inval(al, "pileup: null count");
+  if (cap > 0 && !rows) return fail_inval(al, "pileup: null rows with cap > 0");
+  if (bases_cap > 0 && !bases) return fail_inval(al, "pileup: null bases with bases_cap > 0");
+  HIP_TRY(al, hipSetDevice(al->device));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  *count = 0; *bases_count = 0;
+  if (n == 0) return WFA_HIP_OK;
+  // records per row one wave reduces: read per call, as the chunk is
+  const char* env = getenv("WFA_HIP_INS_MAX_READS");
+  const int64_t asked = env && *env ? atoll(env) : WFA_HIP_INS_MAX_READS;
+  StreamScratch sc{al};
+  wfa::InsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = calls_args(p, texts, g0, n, min_depth, min_permille);
+  a.max_reads = (int32_t)std::min<int64_t>(INT32_MAX, std::max<int64_t>(1, asked));
+  a.records = p->d_rec; a.bases = p->d_ins; a.nrec = p->nrec;
+  if (calls_chunks(sc, &a.c)) return WFA_HIP_EDEVICE;
+  uint64_t nsel = 0;
+  {
+    ReduceTimer timer(al, "insertions count", n, "bases");
+    const int crc = calls_launched(sc, timer, wfa::launch_ins_select_count(a, al->stream), "insertions count kernel launch failed", &nsel, a.c.chunk_off + a.c.chunks, 1);
+    if (crc != WFA_HIP_OK) return crc;
+  }
+  if (nsel == 0) return WFA_HIP_OK;
+  a.nsel = (int64_t)nsel;
+  const size_t ns = (size_t)nsel;
+  if (sc.alloc(&a.sel_g, ns) || sc.alloc(&a.bucket_size, ns) || sc.alloc(&a.bucket_off, ns + 1) || sc.alloc(&a.bucket_fill, ns) ||
+      sc.alloc(&a.bucket, (size_t)p->nrec) || sc.alloc(&a.rows, ns * WFA_INSERTION_COLS) || sc.alloc(&a.best, ns) ||
+      sc.alloc(&a.allele_len, ns) || sc.alloc(&a.letter_off, ns + 1))
+    return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipMemsetAsync(a.bucket_fill, 0, ns * sizeof(uint32_t), al->stream));
+  uint64_t nletters = 0;
+  {
+    ReduceTimer timer(al, "insertions reduce", (int64_t)nsel, "rows");
+    int lrc = wfa::launch_ins_select(a, al->stream);
+    if (lrc == 0) lrc = wfa::launch_ins_reduce(a, p->nins, al->cu_count, al->stream);
+    const int rrc = calls_launched(sc, timer, lrc, "insertions reduce kernel launch failed", &nletters, a.letter_off + ns, 1);
+    if (rrc != WFA_HIP_OK) return rrc;
+  }
+  const int64_t k = std::min<int64_t>((int64_t)nsel, cap);
+  if (k > 0) {
+    if (sc.download(rows, a.rows, (size_t)k * WFA_INSERTION_COLS)) return WFA_HIP_EDEVICE;
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+  }
+  *count = (int64_t)nsel; *bases_count = (int64_t)nletters;
+  // the letters of the rows that fit whole: a prefix of the byte array (a row's letters start where the rows before it end)
+  int64_t end = 0, fit = 0;
+  for (int64_t r = 0; r < k; ++r) {
+    end += rows[r * WFA_INSERTION_COLS + 5];
+    if (end <= bases_cap) fit = end;
+  }
+  if (fit == 0) return WFA_HIP_OK;
+  if (sc.alloc(&a.letters, (size_t)fit)) return WFA_HIP_EDEVICE;
+  ReduceTimer timer(al, "insertions letters", k, "rows");
+  return calls_launched(sc, timer, wfa::launch_ins_letters(a, k, fit, al->cu_count, al->stream), "insertions letters kernel launch failed", bases, a.letters, (size_t)fit);
 }

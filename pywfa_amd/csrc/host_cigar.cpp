@@ -2,8 +2,12 @@
 // cigar_print_pretty (align.pyx:445-459 -> alignment/cigar.c:778-863), as a string a binding can write wherever it likes.
 #include <stdint.h>
 #include <stdio.h>
+#include <algorithm>
+#include <map>
+#include <stdlib.h>
 #include <string>
 #include <string.h>
+#include <vector>
 #include "wfa_hip.h"
 
 namespace {
@@ -183,5 +187,86 @@ extern "C" int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int
     ++n;
   }
   *count = n;
+  return WFA_HIP_OK;
+}
+
+// ---- insertions: a pair's records, and the allele rule over rows and records (the kernels: wfa_insertions.hpp, k_pileup.hip, k_insertions.hip) ----
+
+extern "C" int wfa_hip_ops_insertions(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen, int64_t cap,
+                                      int64_t* count, int32_t* recs, int64_t cols_cap, int64_t* cols_count, uint8_t* cols) {
+  if (ops_len < 0 || plen < 0 || tlen < 0 || (ops_len > 0 && !ops) || (plen > 0 && !pattern) || cap < 0 || cols_cap < 0 || !count || !cols_count ||
+      (cap > 0 && !recs) || (cols_cap > 0 && !cols))
+    return WFA_HIP_EINVAL;
+  // an op string that outruns its pair is refused before anything is written (as wfa_hip_ops_pileup refuses it)
+  int64_t nv = 0, nh = 0;
+  for (int64_t i = 0; i < ops_len; ++i) { const uint8_t c = ops[i]; nv += (c == 'M' || c == 'X' || c == 'D'); nh += (c == 'M' || c == 'X' || c == 'I'); }
+  if (nv > plen || nh > tlen) return WFA_HIP_EINVAL;
+  int64_t nrec = 0, ncols = 0, first = 0, last = -1;
+  if (aligned_core(ops, ops_len, &first, &last)) {
+    int32_t v = 0, h = 0;
+    for (int64_t i = 0; i <= last;) {
+      const uint8_t c = ops[i];
+      if (c != 'D') { v += (c == 'M' || c == 'X'); h += (c == 'M' || c == 'X' || c == 'I'); ++i; continue; }
+      int64_t e = i;
+      while (ops[e] == 'D') ++e;   // (the core ends with an M)
+      const int32_t n = (int32_t)(e - i);
+      if (i > first) {             // a run of the core: one record
+        if (nrec < cap) {
+          int32_t* r = recs + 3 * nrec;
+          r[0] = h; r[1] = n; r[2] = (int32_t)ncols;
+          if (ncols + n <= cols_cap)
+            for (int32_t k = 0; k < n; ++k) cols[ncols + k] = (uint8_t)ref_col(pattern[v + k]);
+        }
+        ++nrec; ncols += n;
+      }
+      v += n; i = e;
+    }
+  }
+  *count = nrec; *cols_count = ncols;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_insertions_host(const int32_t* counts, int64_t len, int32_t seq, int64_t start, int32_t min_depth, int32_t min_permille,
+                                       int64_t nrec, const int64_t* rec_row, const int32_t* rec_n, const int64_t* rec_off, const uint8_t* cols,
+                                       int64_t ncols, int64_t cap, int64_t* count, int32_t* rows, int64_t bases_cap, int64_t* bases_count,
+                                       uint8_t* bases) {
+  if (len < 0 || min_depth < 1 || min_permille < 0 || min_permille > 1000 || nrec < 0 || ncols < 0 || cap < 0 || bases_cap < 0 || !count ||
+      !bases_count || (len > 0 && !counts) || (nrec > 0 && (!rec_row || !rec_n || !rec_off)) || (ncols > 0 && !cols) || (cap > 0 && !rows) ||
+      (bases_cap > 0 && !bases))
+    return WFA_HIP_EINVAL;
+  for (int64_t r = 0; r < nrec; ++r)
+    if (rec_n[r] < 0 || rec_off[r] < 0 || rec_off[r] + rec_n[r] > ncols) return WFA_HIP_EINVAL;
+  const char* env = getenv("WFA_HIP_INS_MAX_READS");
+  const int64_t max_reads = std::max<int64_t>(1, env && *env ? atoll(env) : WFA_HIP_INS_MAX_READS);
+  // the records of every row, in the order they were given (the rule does not depend on it)
+  std::vector<std::vector<int64_t>> at((size_t)len);
+  for (int64_t r = 0; r < nrec; ++r)
+    if (rec_row[r] >= 0 && rec_row[r] < len) at[(size_t)rec_row[r]].push_back(r);
+  int64_t n = 0, nb = 0;
+  typedef std::pair<int32_t, std::vector<uint8_t>> Allele;   // (n, letters): its natural order is the rule's tie order
+  for (int64_t g = 0; g < len; ++g) {
+    const int32_t* c = counts + g * WFA_HIP_PILEUP_COLS;
+    const int64_t depth = depth_of(c), c6 = c[6];
+    if (depth < min_depth) continue;
+    if (min_permille > 0 ? !(c6 >= 1 && 1000 * c6 >= (int64_t)min_permille * depth) : !(2 * c6 > depth)) continue;
+    const bool overflow = c6 > max_reads;
+    std::map<Allele, int64_t> alleles;
+    if (!overflow)
+      for (int64_t r : at[(size_t)g]) alleles[Allele(rec_n[r], std::vector<uint8_t>(cols + rec_off[r], cols + rec_off[r] + rec_n[r]))] += 1;
+    const Allele* best = nullptr;
+    int64_t best_count = 0;
+    for (const auto& kv : alleles)   // ascending (n, letters): the first of the greatest count
+      if (kv.second > best_count) { best = &kv.first; best_count = kv.second; }
+    const int32_t alen = best ? best->first : 0;
+    if (n < cap) {
+      int32_t* row = rows + n * WFA_HIP_INSERTION_COLS;
+      row[0] = seq; row[1] = (int32_t)(start + g); row[2] = (int32_t)depth; row[3] = c[6];
+      row[4] = (int32_t)best_count; row[5] = alen; row[6] = (int32_t)alleles.size(); row[7] = overflow ? 1 : 0;
+      if (nb + alen <= bases_cap)
+        for (int32_t k = 0; k < alen; ++k) bases[nb + k] = (uint8_t)"ACGTN"[best->second[(size_t)k] > 4 ? 4 : best->second[(size_t)k]];
+    }
+    ++n; nb += alen;
+  }
+  *count = n; *bases_count = nb;
   return WFA_HIP_OK;
 }

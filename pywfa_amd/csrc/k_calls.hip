@@ -104,6 +104,11 @@ int launch_sites_count(const CallsArgs& a, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int launch_sites_scan(const CallsArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(wfa_sites_scan_kernel, dim3(1), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_sites_scatter(const CallsArgs& a, hipStream_t stream) {
   if (a.chunks <= 0 || a.cap <= 0) return 0;
   hipLaunchKernelGGL(wfa_sites_scatter_kernel, dim3(chunk_grid(a.chunks)), dim3(256), 0, stream, a);

@@ -1,13 +1,20 @@
-// k_pileup.hip — the pileup reduction (wfa_pileup.hpp: PileupArgs; wfa_hip_pileup_add in wfa_hip.hip).
-// One wave per pair, grid-stride.  Every store is an int32 atomicAdd into the table; a lane adds only for an op of the aligned core
+// k_pileup.hip — the pileup reduction (wfa_pileup.hpp: PileupArgs; wfa_hip_pileup_add in api_pileup.hip) and the record side of the
+// insertion log (wfa_insertions.hpp: InsLogArgs).
+// One wave per pair, grid-stride.  Every store to the table is an int32 atomicAdd; a lane adds only for an op of the aligned core
 // whose text position lies inside the pair's text window, and the host has checked that the window lies inside its sequence, so an op
-// string that disagreed with its pair's lengths could lose counts but never leave the table.
+// string that disagreed with its pair's lengths could lose counts but never leave the table.  The log's stores are plain: a record
+// and a column byte have one writer, at an index below the allocated size (checked at the store).
 #include <algorithm>
-#include "wfa_pileup.hpp"
+#include "wfa_insertions.hpp"
 
 namespace wfa {
 
-__global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) {
+enum { PILEUP_TABLE = 0, PILEUP_COUNT = 1, PILEUP_TRACK = 2 };
+
+// The walk of a pair's op string.  PILEUP_TABLE: the adds to the table (g unused).  PILEUP_COUNT: no store but pair_count[q] of a
+// contributing pair (the host zeroes the array).  PILEUP_TRACK: the adds and the pair's records and column bytes.
+template <int MODE>
+__device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArgs& g) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -41,6 +48,11 @@ __global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) {
     const uint32_t* pw = a.words + m.p_woff;
     int vbase = 0, hbase = 0;
     unsigned long long carry_d = 0;
+    // the log (wave-uniform): the pair's counted runs and D ops so far; the run that is open across a round boundary
+    uint32_t nrec = 0, nbase = 0;
+    int64_t rec0 = 0, b0 = 0, open_rec = -1, open_off = 0, open_g = 0;
+    int32_t open_n = 0;
+    if (MODE == PILEUP_TRACK) { rec0 = g.rec_base + (int64_t)g.rec_off[q]; b0 = g.base_base + (int64_t)g.base_off[q]; }
     for (int base = 0; base <= last; base += 64) {
       const int i = base + lane;
       const uint32_t c = (i < len) ? p[i] : 0u;
@@ -49,7 +61,47 @@ __global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) {
       const int v = vbase + __builtin_popcountll(bv & lower);
       const int h = hbase + __builtin_popcountll(bh & lower);
       const bool d_start = ((bd & ~((bd << 1) | carry_d)) >> lane) & 1ull;
+      if (MODE != PILEUP_TABLE) {
+        // a run's D ops share its h, so a run is counted whole or not at all; the core begins and ends with an M, so no run leaves it
+        const bool inside = i >= first && i <= last && h < m.tlen;
+        const unsigned long long dv = __ballot(c == 'D' && inside), sv = __ballot(d_start && inside);
+        if (MODE == PILEUP_TRACK) {
+          if (open_rec >= 0) {   // the open run goes on: over the leading D ops of this round
+            const unsigned long long nd = ~bd;
+            const int lead = nd ? __builtin_ctzll(nd) : 64;
+            open_n += lead;
+            if (lead < 64) {
+              if (lane == 0 && open_rec < g.rec_cap) g.records[open_rec] = InsRecord{open_g, open_off, open_n, 0};
+              open_rec = -1;
+            }
+          }
+          const int64_t my_off = b0 + nbase + __builtin_popcountll(dv & lower);
+          if (c == 'D' && inside && my_off < g.base_cap)
+            g.bases[my_off] = (uint8_t)(v >= m.plen ? 4 : on_bytes ? wfa_pileup_letter_col(pb[v]) : wfa_pileup_code_col((pw[v >> 4] >> (2 * (v & 15))) & 3u));
+          const unsigned long long x = ~(bd >> lane);
+          const int nin = x ? __builtin_ctzll(x) : 64;   // the D ops of this round from this lane on
+          if (d_start && inside && lane + nin < 64) {
+            const int64_t r = rec0 + nrec + __builtin_popcountll(sv & lower);
+            if (r < g.rec_cap) g.records[r] = InsRecord{a.seq_off[jq] + ts + h, my_off, nin, 0};
+          }
+          // a counted run that starts in this round and reaches its end stays open
+          if (bd >> 63) {
+            const unsigned long long nd = ~bd;
+            const int t = nd ? __builtin_clzll(nd) : 64, s = 64 - t;
+            const int hs = __shfl(h, s & 63);
+            if ((sv >> (s & 63)) & 1ull) {
+              const unsigned long long below = (1ull << (s & 63)) - 1ull;
+              open_rec = rec0 + nrec + __builtin_popcountll(sv & below);
+              open_off = b0 + nbase + __builtin_popcountll(dv & below);
+              open_g = a.seq_off[jq] + ts + hs;
+              open_n = t;
+            }
+          }
+        }
+        nrec += (uint32_t)__builtin_popcountll(sv); nbase += (uint32_t)__builtin_popcountll(dv);
+      }
       vbase += __builtin_popcountll(bv); hbase += __builtin_popcountll(bh); carry_d = bd >> 63;
+      if (MODE == PILEUP_COUNT) continue;
       if (i < first || i > last || h >= m.tlen) continue;
       int32_t* row = row0 + h;
       if (c == 'M' || c == 'X') {
@@ -64,13 +116,37 @@ __global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) {
         atomicAdd(row + (int64_t)WFA_PILEUP_INS * a.total, 1);
       }
     }
+    if (MODE == PILEUP_COUNT && lane == 0) g.pair_count[q] = InsPairCount{nrec, nbase};
   }
+}
+
+__global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) { pileup_walk<PILEUP_TABLE>(a, InsLogArgs{}); }
+__global__ void __launch_bounds__(256) wfa_pileup_count_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_COUNT>(a, g); }
+__global__ void __launch_bounds__(256) wfa_pileup_track_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_TRACK>(a, g); }
+
+static unsigned pileup_grid(const PileupArgs& a, int cu_count) {
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.npairs + 3) / 4, (int64_t)cu_count * 16));
 }
 
 int launch_pileup(const PileupArgs& a, int cu_count, hipStream_t stream) {
   if (a.npairs <= 0) return 0;
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.npairs + 3) / 4, (int64_t)cu_count * 16));
+  const unsigned grid = pileup_grid(a, cu_count);
   hipLaunchKernelGGL(wfa_pileup_kernel, dim3(grid), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_pileup_count(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream) {
+  if (a.npairs <= 0) return 0;
+  hipLaunchKernelGGL(wfa_pileup_count_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g);
+  if (hipGetLastError() != hipSuccess) return -1;
+  const uint32_t* counts = reinterpret_cast<const uint32_t*>(g.pair_count);
+  if (launch_ins_scan(counts, 2, g.rec_off, a.npairs, stream) != 0) return -1;
+  return launch_ins_scan(counts + 1, 2, g.base_off, a.npairs, stream);
+}
+
+int launch_pileup_track(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream) {
+  if (a.npairs <= 0) return 0;
+  hipLaunchKernelGGL(wfa_pileup_track_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

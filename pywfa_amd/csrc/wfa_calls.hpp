@@ -88,5 +88,6 @@ __host__ __device__ inline bool calls_site(const CallsBase& b, int32_t min_depth
 int launch_calls(const CallsArgs& a, int cu_count, hipStream_t stream);
 int launch_sites_count(const CallsArgs& a, hipStream_t stream);     // count + scan: chunk_off[chunks] is the number of sites
 int launch_sites_scatter(const CallsArgs& a, hipStream_t stream);
+int launch_sites_scan(const CallsArgs& a, hipStream_t stream);      // the scan alone, over chunk counts another count kernel wrote (wfa_insertions.hpp)
 
 }  // namespace wfa

@@ -74,6 +74,18 @@ cdef extern from "wfa_hip.h" nogil:
     int wfa_hip_calls_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t min_depth, uint8_t* out)
     int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, int32_t seq, int64_t start, int32_t min_depth,
                             int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows)
+    # what the reads insert: the log of a tracking pileup and its alleles (include/wfa_hip.h: "insertions")
+    int wfa_hip_pileup_track_insertions(wfa_hip_pileup_t* pileup, int on)
+    int wfa_hip_pileup_insertion_stats(wfa_hip_pileup_t* pileup, int64_t* records, int64_t* bases)
+    int wfa_hip_pileup_insertions(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                  int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows,
+                                  int64_t bases_cap, int64_t* bases_count, uint8_t* bases)
+    int wfa_hip_ops_insertions(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen, int64_t cap,
+                               int64_t* count, int32_t* recs, int64_t cols_cap, int64_t* cols_count, uint8_t* cols)
+    int wfa_hip_insertions_host(const int32_t* counts, int64_t len, int32_t seq, int64_t start, int32_t min_depth, int32_t min_permille,
+                                int64_t nrec, const int64_t* rec_row, const int32_t* rec_n, const int64_t* rec_off, const uint8_t* cols,
+                                int64_t ncols, int64_t cap, int64_t* count, int32_t* rows, int64_t bases_cap, int64_t* bases_count,
+                                uint8_t* bases)
     # placement: one row per read from the hits of any number of batches (include/wfa_hip.h: "placement")
     ctypedef struct wfa_hip_batch_t
     ctypedef struct wfa_hip_placer_t
