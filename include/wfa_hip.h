@@ -621,8 +621,9 @@ int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, i
  * although the rule needs no letters, so the call shape matches), with min_permille in 0..1000; a pileup that does not track ("... was
  * not made to track insertions"); bases_cap < 0; a NULL count or bases_count; NULL bases with bases_cap > 0.
  *
- * Out of scope: quality values, strands, genotypes, left-normalising insertions across reads (reads that place the same inserted bases
- * at different rows of a repeat are different records at different rows), more than one allele per row.
+ * Out of scope: quality values, strands, genotypes, more than one allele per row.  Reads that place the same inserted bases at
+ * different rows of a repeat are different records at different rows: left-align the batch first ("left alignment" below), which puts
+ * every gap at the left end of its repeat as far as the read's own window and its own mismatches allow.
  */
 #define WFA_HIP_INSERTION_COLS 8   /* j, pos, depth, ins_count, allele_count, allele_len, alleles, overflow */
 #define WFA_HIP_INS_MAX_READS 4096 /* the default of the limit; the environment variable of this name replaces it per call */
@@ -649,6 +650,53 @@ int wfa_hip_insertions_host(const int32_t* counts, int64_t len, int32_t seq, int
                             int64_t nrec, const int64_t* rec_row, const int32_t* rec_n, const int64_t* rec_off, const uint8_t* cols,
                             int64_t ncols, int64_t cap, int64_t* count, int32_t* rows, int64_t bases_cap, int64_t* bases_count,
                             uint8_t* bases);
+
+/* ---- left alignment: gaps at the left end of their repeat, where VCF puts them ----------------------------- */
+
+/*
+ * WFA's backtrace leaves a gap at the RIGHT end of a homopolymer or tandem repeat; VCF, and every tool and truth set that follows it,
+ * puts it at the LEFT end.  Left alignment is a pure rewrite of the op string of a status-0 pair, done before the string is reduced, so
+ * that summaries, pileups, sites and insertion rows report a gap where a caller expects it, and reads that stopped at different places
+ * of one repeat agree as far as their own letters allow.
+ *
+ * INPUT.  The op string and the pair's own letters P[0 .. plen) and T[0 .. tlen): the batch's letters, so a reverse-strand window is
+ * already on the text's strand.
+ * CORE.  The aligned core: first M (index `first`) .. last M (index `last`).  Without an M nothing changes.
+ * RUNS.  The maximal gap runs (I runs and D runs) that lie wholly inside (first, last), taken in ascending op order over the string as
+ * already rewritten.
+ * SHIFT.  A run of kind c occupies ops [a, a + L); x is the position in S when the run starts, with S = T and x = h for I, S = P and
+ * x = v for D.  While a - 1 > first, ops[a - 1] == 'M' and S[x - 1] == S[x + L - 1] (byte equality; no wildcard rule):
+ *     ops[a - 1] = c, ops[a + L - 1] = 'M', then a and x decrease by one.
+ * MERGE.  If the run has moved at least once, a - 1 > first and ops[a - 1] == c, the run in front of it and this one are one run from
+ * here on: a goes to the start of that earlier run, L grows by its length, x drops by its length, and SHIFT goes on with the larger L.
+ * STOP.  Anything else in front of the run stops it: an X, a gap of the other kind, the core's first M.
+ *
+ * What follows from the rule:
+ *   - the string keeps its length, its count of every letter, its `first` and its `last`, so `locations` (and with them the interval
+ *     a placement sees) do not change;
+ *   - every M still pairs equal letters;
+ *   - applying the rule twice gives the bytes of applying it once;
+ *   - the reported score stays WFA's and is NOT recomputed: under gap-affine and gap-affine-2p a shift costs nothing; a merge (which
+ *     the one-component metrics produce) can only improve the score of the string.
+ * Out of scope: moving a gap through a mismatch; joint realignment across reads; re-scoring; normalising against anything but the
+ * pair's own window (a gap cannot move left of the window or of the core's first M).
+ *
+ * wfa_hip_batch_left_align waits for the batch's last run and rewrites the op strings of its status-0 pairs in place, in the batch's
+ * device buffer; nothing crosses PCIe but the two counters.  Everything read from the batch afterwards sees the rewritten strings:
+ * wfa_hip_batch_results, wfa_hip_batch_rle_counts / _rle_runs, wfa_hip_batch_summary, wfa_hip_pileup_add, wfa_hip_placer_add.  The
+ * run-length encoding the batch may hold is dropped (call wfa_hip_batch_rle_counts again).  A new wfa_hip_batch_run brings WFA's own
+ * strings back.  stats (nullable): [0] the runs that moved, [1] the merges, summed over the batch; a second call changes nothing and
+ * reports zeros.  Kernel: csrc/wfa_leftalign.hpp, k_leftalign.hip (a wave per pair; a pair without a gap inside its core is left
+ * without a store).  WFA_HIP_EINVAL, nothing launched: what wfa_hip_batch_summary refuses (a batch of scope score, or without a
+ * finished run).
+ */
+int wfa_hip_batch_left_align(wfa_hip_batch_t* batch, int64_t* stats /* nullable; [0] runs moved, [1] merges */);
+
+/* Host only, needs no GPU: the rule for ONE pair, in place, from its op string and its ASCII pattern and text bytes.  Returns
+ * WFA_HIP_OK, or WFA_HIP_EINVAL with nothing changed on a negative length, a missing pointer, or an op string that does not consume
+ * exactly plen pattern and tlen text bases. */
+int wfa_hip_ops_left_align(uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen,
+                           int64_t* stats /* nullable; [0] runs moved, [1] merges */);
 
 /* ---- placement: one row per read from the hits of any number of batches ---------------------------------- */
 

@@ -140,6 +140,8 @@ SIGNATURES = {
     "wfa_hip_pileup_insertions": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i64, _i64p, _vp, _i64, _i64p, _vp]),
     "wfa_hip_ops_insertions": (_CTYPES, [_vp, _i64, _vp, _i32, _i32, _i64, _i64p, _vp, _i64, _i64p, _vp]),
     "wfa_hip_insertions_host": (_CTYPES, [_vp, _i64, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64p, _vp, _i64, _i64p, _vp]),
+    "wfa_hip_batch_left_align": (_CTYPES, [_vp, _vp]),
+    "wfa_hip_ops_left_align": (_CTYPES, [_vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "wfa_hip_placer_create": (_vp, [_vp, _i64]),
     "wfa_hip_placer_add": (_CTYPES, [_vp] * 6),
     "wfa_hip_placer_add_hits": (_CTYPES, [_vp, _i64] + [_vp] * 7),
@@ -533,6 +535,19 @@ def ops_pileup(ops, pattern, tlen, rows=None):
     if rc != OK:
         raise ValueError("wfa_hip_ops_pileup: invalid arguments (an op string that outruns its pair?)")
     return rows
+
+
+def ops_left_align(ops, pattern, text):
+    """wfa_hip_ops_left_align (host only): one pair's op string (bytes or a uint8 array of M / X / I / D) left-aligned against its ASCII
+    pattern and text: (a new uint8 array, runs moved, merges).  ValueError for an op string that does not consume exactly its pair."""
+    ops = np.frombuffer(bytes(ops), dtype=np.uint8).copy() if not isinstance(ops, np.ndarray) else np.array(ops, dtype=np.uint8)
+    pattern = np.frombuffer(bytes(pattern), dtype=np.uint8) if not isinstance(pattern, np.ndarray) else np.ascontiguousarray(pattern, dtype=np.uint8)
+    text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+    stats = np.zeros(2, np.int64)
+    rc = lib().wfa_hip_ops_left_align(_ptr_or_null(ops), ops.size, _ptr_or_null(pattern), pattern.size, _ptr_or_null(text), text.size, _ptr(stats))
+    if rc != OK:
+        raise ValueError("wfa_hip_ops_left_align: invalid arguments (an op string that does not consume exactly its pair?)")
+    return ops, int(stats[0]), int(stats[1])
 
 
 def _letters_written(rows, bases_cap):
@@ -1350,6 +1365,13 @@ class ResidentBatch(_Handle):
         out = np.zeros((self.n, SUMMARY_COLS), np.int32)
         self._call("wfa_hip_batch_summary", self._h, _ptr(out) if self.n else None)
         return out
+
+    def left_align(self):
+        """wfa_hip_batch_left_align: the op strings of the status-0 pairs of the last scope=full run rewritten in place on the GPU, every
+        gap run at the left end of its repeat; everything read from the batch afterwards sees them.  Returns (runs moved, merges)."""
+        stats = np.zeros(2, np.int64)
+        self._call("wfa_hip_batch_left_align", self._h, _ptr(stats))
+        return int(stats[0]), int(stats[1])
 
     def algorithmic_bytes(self):
         return int(lib().wfa_hip_batch_algorithmic_bytes(self._h))

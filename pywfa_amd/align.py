@@ -215,6 +215,21 @@ def cigartuples_to_str(cigartuples):
     return "".join(f"{int(n)}{_OP_CHARS[op]}" for op, n in cigartuples)
 
 
+def left_align_ops(ops, pattern, text):
+    """Left-align one pair's op string on the host (no GPU): ``ops`` holds one letter per op (M X I D; a ``str``, ``bytes`` or a
+    uint8 array: what ``cigar_ops`` gives), ``pattern`` and ``text`` are the pair's own letters (of a window: the window's, a
+    reversed pattern reverse-complemented).  Inside the aligned core, first M to last M, every I or D run moves left over M ops
+    while the letter that enters it equals the letter that leaves it, and joins a run of its own kind that it meets; a mismatch, a
+    gap of the other kind and the core's first M stop it — the rule ``left_align=True`` applies on the GPU (include/wfa_hip.h,
+    "left alignment").  Returns the rewritten ops in the type they came in.  ValueError when the ops do not consume exactly the
+    pattern and the text."""
+    as_bytes = [x.encode() if isinstance(x, str) else x for x in (ops, pattern, text)]
+    out, _moved, _merges = _native.ops_left_align(*as_bytes)
+    if isinstance(ops, str):
+        return out.tobytes().decode()
+    return out if isinstance(ops, np.ndarray) else out.tobytes()
+
+
 def _rle(ops):
     """Run-length encode a uint8 array of op chars -> (chars, lengths)."""
     if ops.size == 0:
@@ -337,9 +352,9 @@ def _summary_dict(rows):
     return out
 
 
-def _need_full_for_summary(cfg):
+def _need_full_for_summary(cfg, what="summary=True"):
     if cfg.scope != 1:
-        raise ValueError("summary=True needs scope='full'")
+        raise ValueError(f"{what} needs scope='full'")
 
 
 _CALL_LETTERS = np.frombuffer(b"ACGTN-N", np.uint8)   # (CALL_CODES as letters; deleted bases are dropped before the lookup)
@@ -1057,7 +1072,7 @@ class WavefrontAligner:
             raise ValueError(f"i and j differ in length: {out[0].shape[0]} and {out[1].shape[0]}")
         return out
 
-    def align_pairs(self, patterns, texts=None, *, i=None, j=None, summary=False):
+    def align_pairs(self, patterns, texts=None, *, i=None, j=None, summary=False, left_align=False):
         """Align the listed pairs (patterns[i[q]], texts[j[q]]) on the GPU, each sequence uploaded once however many pairs name it;
         ``texts=None``: both indices into ``patterns``.  ``patterns`` / ``texts``: lists of ``str`` (uploaded and released inside
         the call) or ``SequenceSet`` handles of ``sequence_set`` (left open).  ``i`` / ``j``: integer arrays of equal length, every
@@ -1066,9 +1081,14 @@ class WavefrontAligner:
 
         Returns what ``wavefront_align_batch`` returns for those pairs under this aligner's configuration, in list order:
         dict(score=, status=) and, with scope full, cigarstrings= / cigar_ops=.  With ``devices=[...]`` the first device runs it.
-        ``summary=True`` (scope full only): dict(score=, status=, summary=) as ``align_batch`` describes, no op strings."""
+        ``summary=True`` (scope full only): dict(score=, status=, summary=) as ``align_batch`` describes, no op strings.
+        ``left_align=True`` (scope full only, else ValueError): the op strings are left-aligned on the GPU before anything is read
+        (``left_align_ops`` states the rule); ``cigarstrings``, ``cigar_ops`` and ``summary`` are then those of the rewritten
+        strings, the scores stay WFA's."""
         if summary:
             _need_full_for_summary(self._cfg)
+        if left_align:
+            _need_full_for_summary(self._cfg, "left_align=True")
         if not isinstance(patterns, (SequenceSet, list)):
             patterns = list(patterns)
         if texts is not None and not isinstance(texts, (SequenceSet, list)):
@@ -1098,15 +1118,16 @@ class WavefrontAligner:
                 hi = min(lo + budget, int(np.searchsorted(words, before + (1 << 31), side="right")))
                 cuts.append(max(hi, lo + 1))
             return self._run_lists(npairs, cuts, lambda lo, hi: self._native.batch_indexed(
-                pset, tset if texts is not None else None, i[lo:hi], j[lo:hi]), summary=summary)
+                pset, tset if texts is not None else None, i[lo:hi], j[lo:hi]), summary=summary, left_align=bool(left_align))
         finally:
             for s in mine:
                 s.close()
 
-    def _run_lists(self, npairs, cuts, make, summary=False, each=None):
+    def _run_lists(self, npairs, cuts, make, summary=False, each=None, left_align=False):
         """Run the resident batches ``make(lo, hi)`` of the consecutive chunks ``cuts`` of a pair list and join their results.
         ``summary``: the per-pair summary rows instead of op strings.  ``each(rb, lo, hi, score, status)``: called on every chunk's
-        batch after its run instead of fetching op strings (``pileup``)."""
+        batch after its run instead of fetching op strings (``pileup``).  ``left_align``: every chunk's op strings are left-aligned
+        on the GPU after its run, before anything is read from the batch."""
         full = self._cfg.scope == 1
         score = np.zeros(npairs, np.int32)
         status = np.zeros(npairs, np.int32)
@@ -1119,6 +1140,8 @@ class WavefrontAligner:
             try:
                 rb.run()
                 rb.sync()
+                if left_align:
+                    rb.left_align()
                 sc, st, cig = rb.results(small)
                 score[lo:hi] = sc
                 status[lo:hi] = st
@@ -1275,7 +1298,7 @@ class WavefrontAligner:
         return add
 
     def align_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None,
-                      text_start=None, text_len=None, reverse=None, summary=False):
+                      text_start=None, text_len=None, reverse=None, summary=False, left_align=False):
         """Align windows of resident sequences on the GPU: pair q is bases [pattern_start[q], + pattern_len[q]) of patterns[i[q]],
         reverse-complemented where ``reverse[q]``, against bases [text_start[q], + text_len[q]) of texts[j[q]] (never reversed);
         ``texts=None``: both indices into ``patterns``.  A start left out is 0 for every pair, a length left out runs to the end of
@@ -1287,21 +1310,28 @@ class WavefrontAligner:
         order, as ``align_pairs`` does: dict(score=, status=) and, with scope full, cigarstrings= / cigar_ops= (coordinates relative
         to the windows: add the starts).  ValueError, before anything is uploaded, for arrays that are not one-dimensional integer
         arrays of one length, negative values, a window that ends behind its sequence, or a ``reverse`` that is not boolean / 0-1.
-        ``summary=True`` (scope full only): dict(score=, status=, summary=) as ``align_batch`` describes, no op strings."""
+        ``summary=True`` (scope full only): dict(score=, status=, summary=) as ``align_batch`` describes, no op strings.
+        ``left_align=True`` (scope full only): as for ``align_pairs``; the letters are the windows', a reversed pattern on the
+        text's strand, and no gap moves left of its window."""
         if summary:
             _need_full_for_summary(self._cfg)
+        if left_align:
+            _need_full_for_summary(self._cfg, "left_align=True")
         with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
-            return w.run(summary=summary)
+            return w.run(summary=summary, left_align=bool(left_align))
 
     def pileup(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
-               text_len=None, reverse=None, min_score=None, insertions=False):
+               text_len=None, reverse=None, min_score=None, insertions=False, left_align=False):
         """Align the listed windows as ``align_windows`` does (same arguments, same checks; scope must be "full") and pile the
         alignments up over the TEXT sequences on the GPU: the patterns are reads, the texts references.  Every pair whose status is
         0 (and whose score is at least ``min_score``, when given) adds the ops of its aligned core — first M to last M — to the
         text bases they cover; neither op strings nor their run-length encoding leave the device (csrc/wfa_pileup.hpp).
         ``texts=None`` piles up over ``patterns``.  ``insertions=True``: the pileup also keeps what the reads insert (a log on the
         GPU, about 24 bytes per insertion and 1 byte per inserted base, and a second pass over the op strings), for
-        ``Pileup.insertions`` and ``Pileup.consensus(insertions=True)``.
+        ``Pileup.insertions`` and ``Pileup.consensus(insertions=True)``.  ``left_align=True``: every op string is left-aligned on
+        the GPU before it is piled up (``left_align_ops`` states the rule), so a gap inside a homopolymer or tandem repeat is
+        counted at the left end of the repeat, where VCF puts it, and reads that stopped at different places of one repeat agree
+        as far as their own letters allow; tables, ``sites``, ``insertions`` and ``consensus(insertions=True)`` follow.
 
         Returns a ``Pileup`` (``score``, ``status``, ``counts(j)``, ``depth(j)``, ``calls()``, ``consensus()``, ``sites()``,
         ``insertions()``, ``close()``; a context manager), which stays
@@ -1320,7 +1350,7 @@ class WavefrontAligner:
                 keep = None if min_score is None else (score >= int(min_score))
                 table.add(rb, jj[lo:hi], None if ts is None else ts[lo:hi], keep)
 
-            out = w.run(each=add)
+            out = w.run(each=add, left_align=bool(left_align))
             return Pileup(table, out["score"], out["status"], self)
 
     def place_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,

@@ -1,6 +1,39 @@
 // api_pileup.hip — pileups and calls of libwfa_hip.so (the C ABI declared in include/wfa_hip.h).
 #include "host_sets.hpp"
 #include "wfa_insertions.hpp"
+#include "wfa_leftalign.hpp"
+
+// ------------------------------------------------------------------------------------------------
+// left alignment of a batch's op strings (include/wfa_hip.h, "left alignment"; csrc/wfa_leftalign.hpp, k_leftalign.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int wfa_hip_batch_left_align(wfa_hip_batch_t* b, int64_t* stats) {
+  if (!b) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = b->al;
+  int rc = batch_of(al, b, "left alignment", true);
+  if (rc != WFA_HIP_OK) return rc;
+  rc = wfa_hip_batch_sync(b);
+  if (rc != WFA_HIP_OK) return rc;
+  if (stats) stats[0] = stats[1] = 0;
+  if (b->n == 0) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  b->rle_total = -1;   // the run-length encoding of the strings as they were
+  StreamScratch sc{al};
+  wfa::LeftAlignArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ops = b->d_ops; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len; a.status = b->d_status;
+  a.meta = b->d_meta; a.words = b->d_words; a.bytes = b->d_bytes; a.pboff = b->d_pboff; a.tboff = b->d_tboff; a.flags = b->d_flags;
+  a.npairs = b->n;
+  if (sc.alloc(&a.stats, 2)) return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipMemsetAsync(a.stats, 0, 2 * sizeof(unsigned long long), al->stream));
+  unsigned long long got[2] = {0, 0};
+  ReduceTimer timer(al, "left align", b->n);
+  const int lrc = wfa::launch_left_align(a, al->cu_count, al->stream);
+  timer.stop();
+  if (lrc == 0 && sc.download(got, a.stats, 2)) return WFA_HIP_EDEVICE;
+  rc = launch_end(al, nullptr, lrc, "left alignment kernel launch failed");
+  if (rc == WFA_HIP_OK && stats) { stats[0] = (int64_t)got[0]; stats[1] = (int64_t)got[1]; }
+  return rc;
+}
 
 // ------------------------------------------------------------------------------------------------
 // pileup over a text set (include/wfa_hip.h; csrc/wfa_pileup.hpp, k_pileup.hip)

@@ -136,6 +136,46 @@ extern "C" int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uin
   return WFA_HIP_OK;
 }
 
+// ---- left alignment: the rewrite of one pair's op string, stated in plain C (the kernel: wfa_leftalign.hpp, k_leftalign.hip) --------
+
+extern "C" int wfa_hip_ops_left_align(uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen,
+                                      int64_t* stats) {
+  if (ops_len < 0 || plen < 0 || tlen < 0 || (ops_len > 0 && !ops) || (plen > 0 && !pattern) || (tlen > 0 && !text)) return WFA_HIP_EINVAL;
+  // an op string that does not consume exactly its pair is refused before anything is rewritten
+  int64_t nv = 0, nh = 0;
+  for (int64_t i = 0; i < ops_len; ++i) { const uint8_t c = ops[i]; nv += (c == 'M' || c == 'X' || c == 'D'); nh += (c == 'M' || c == 'X' || c == 'I'); }
+  if (nv != plen || nh != tlen) return WFA_HIP_EINVAL;
+  int64_t moved_runs = 0, merges = 0, first = 0, last = -1;
+  if (aligned_core(ops, ops_len, &first, &last)) {
+    int64_t v = 0, h = 0;   // the positions in front of op i
+    for (int64_t i = 0; i < last;) {
+      const uint8_t c = ops[i];
+      if (i <= first || (c != 'I' && c != 'D')) { v += (c == 'M' || c == 'X' || c == 'D'); h += (c == 'M' || c == 'X' || c == 'I'); ++i; continue; }
+      int64_t a = i, L = 0;
+      while (ops[a + L] == c) ++L;   // (the core ends with an M)
+      const int64_t end = a + L;     // the ops in front of `end` keep their letter counts: v and h there do not depend on the rewrite
+      const uint8_t* S = (c == 'I') ? text : pattern;
+      int64_t x = (c == 'I') ? h : v;
+      bool moved = false;
+      for (;;) {
+        while (a - 1 > first && ops[a - 1] == 'M' && S[x - 1] == S[x + L - 1]) {
+          ops[a - 1] = c; ops[a + L - 1] = 'M';
+          --a; --x; moved = true;
+        }
+        if (!(moved && a - 1 > first && ops[a - 1] == c)) break;
+        int64_t n = 0;               // the run in front has become a part of this one
+        while (ops[a - 1 - n] == c) ++n;   // (the core begins with an M)
+        a -= n; x -= n; L += n; ++merges;
+      }
+      moved_runs += moved;
+      if (c == 'I') h += end - i; else v += end - i;
+      i = end;
+    }
+  }
+  if (stats) { stats[0] = moved_runs; stats[1] = merges; }
+  return WFA_HIP_OK;
+}
+
 // ---- calls and sites: the two reductions of pileup rows against their reference bytes (the kernels: wfa_calls.hpp, k_calls.hip) ----
 
 namespace {
