@@ -19,6 +19,7 @@
 #ifndef __HIPCC_RTC__
 #include <string>
 #include "wfa_rtc.hpp"
+#include "wfa_shapes.hpp"
 #endif
 #include "wfa_hip.h"
 #include "wfa_common.hpp"
@@ -27,9 +28,6 @@
 namespace wfa {
 
 template <int N> struct band_int { static constexpr int value = N; };   // (a compile-time chunk count passed to the step lambdas)
-
-// penalty shapes (x, o + e, e) / gcd the banded kernel is instantiated for: pywfa's 4/6/2 and the presets 4/4/2, 4/6/1, 3/4/1
-#define WFA_BAND_SHAPES(F) F(0, 2, 4, 1) F(1, 2, 3, 1) F(2, 4, 7, 1) F(3, 3, 5, 1)
 
 struct BandArgs {
   const uint32_t* words;
@@ -1281,15 +1279,26 @@ inline int launch_band_bt_impl(const BandArgs& a, int nch, hipStream_t stream) {
 
 #endif  // WFA_BAND_WALK_KERNELS
 
-#ifndef __HIPCC_RTC__   // ---- host side (launch code, shape tables) ----
+#ifndef __HIPCC_RTC__   // ---- host side (launch code) ----
+// The form of a launch of the banded kernel: which of wfa_band_kernel (0), wfa_band_kernel_w3 (3) and wfa_band_kernel_w4 (4) it is and
+// the kernel's PB and SPLIT arguments.  The built-in instantiations (launch_band_t / launch_band_k) and the name of a run-time one
+// (band_rtc_name) both come from here.
+struct BandForm { int kernel; bool pb, split; };
+// (the piggy-back forms need a few more registers: compiled without the occupancy cap rather than with spills)
+constexpr int band_kernel(bool two, int nch, bool pb) { return (two && nch == 3) ? 4 : (two && nch == 4 && !pb) ? 3 : 0; }
+// split: history slot per pair, walk in its own kernel; piggy-back history on request
+constexpr BandForm band_form(bool two, int nch, bool full, bool a_split, bool a_pb) {
+  return BandForm{band_kernel(two, nch, full && a_split && a_pb), full && a_split && a_pb, full && a_split};
+}
+
 template <int NCH, bool FULL, bool ADAPT, bool PB, bool SPLIT, int X, int OE, int E, int OE2, int E2>
 static int launch_band_k(const BandArgs& a, bool seqlds, long long grid, hipStream_t stream) {
   const size_t smem = seqlds ? (size_t)a.lds_words * 2 * sizeof(uint32_t) : 0;
-  // (the piggy-back forms need a few more registers: compiled without the occupancy cap rather than with spills)
-  if constexpr (OE2 > 0 && NCH == 3) {
+  constexpr int K = band_kernel(OE2 > 0, NCH, PB);
+  if constexpr (K == 4) {
     if (seqlds) hipLaunchKernelGGL((wfa_band_kernel_w4<NCH, FULL, ADAPT, true, PB, SPLIT, X, OE, E, OE2, E2>), dim3((unsigned)grid), dim3(64), smem, stream, a);
     else hipLaunchKernelGGL((wfa_band_kernel_w4<NCH, FULL, ADAPT, false, PB, SPLIT, X, OE, E, OE2, E2>), dim3((unsigned)grid), dim3(64), 0, stream, a);
-  } else if constexpr (OE2 > 0 && NCH == 4 && !PB) {
+  } else if constexpr (K == 3) {
     if (seqlds) hipLaunchKernelGGL((wfa_band_kernel_w3<NCH, FULL, ADAPT, true, PB, SPLIT, X, OE, E, OE2, E2>), dim3((unsigned)grid), dim3(64), smem, stream, a);
     else hipLaunchKernelGGL((wfa_band_kernel_w3<NCH, FULL, ADAPT, false, PB, SPLIT, X, OE, E, OE2, E2>), dim3((unsigned)grid), dim3(64), 0, stream, a);
   } else {
@@ -1301,8 +1310,9 @@ static int launch_band_k(const BandArgs& a, bool seqlds, long long grid, hipStre
 template <int NCH, bool FULL, bool ADAPT, int X, int OE, int E, int OE2, int E2>
 static int launch_band_t(const BandArgs& a, bool seqlds, long long grid, hipStream_t stream) {
   constexpr bool CAN_PB = FULL;
-  if (FULL && a.split) {  // history slot per pair, walk in its own kernel; piggy-back history on request
-    if (CAN_PB && a.pb) return launch_band_k<NCH, FULL, ADAPT, CAN_PB, FULL, X, OE, E, OE2, E2>(a, seqlds, grid, stream);
+  const BandForm f = band_form(OE2 > 0, NCH, FULL, a.split != 0, a.pb != 0);
+  if (f.split) {
+    if (f.pb) return launch_band_k<NCH, FULL, ADAPT, CAN_PB, FULL, X, OE, E, OE2, E2>(a, seqlds, grid, stream);
     return launch_band_k<NCH, FULL, ADAPT, false, FULL, X, OE, E, OE2, E2>(a, seqlds, grid, stream);
   }
   return launch_band_k<NCH, FULL, ADAPT, false, false, X, OE, E, OE2, E2>(a, seqlds, grid, stream);
@@ -1325,20 +1335,15 @@ static int launch_band_shape(const BandArgs& a, int nch, bool full, bool adapt, 
   return -1;
 }
 
-// ---- host entry points.  Every penalty shape is compiled in its own translation unit (csrc/k_band.hip, once per
-// index; index 4 = gap-affine-2p, index 5 = the walks / expansion kernels) so that the library builds in parallel.
+// ---- host entry points.  Every unit (band_unit_shape(), wfa_shapes.hpp: the leading gap-affine shapes, then gap-affine-2p) is compiled in
+// its own translation unit (csrc/k_band.hip and csrc/k_slim.hip, once per index; k_band.hip's index band_unit_count = the walks /
+// expansion kernels) so that the library builds in parallel.
 int launch_band_bt(const BandArgs& a, int nch, hipStream_t stream);
 int launch_lane_expand(const BandArgs& a, hipStream_t walk_stream, hipStream_t expand_stream);   // walk the codes of wfa_lane_kernel<.., FULL> into run records / run records into op bytes (either stream may be null: that half is skipped)
-#define WFA_BAND_DECL(i, x, oe, e) int launch_band_s##i(const BandArgs& a, int nch, bool full, bool adapt, bool seqlds, long long grid, hipStream_t stream);
-WFA_BAND_SHAPES(WFA_BAND_DECL)
-#undef WFA_BAND_DECL
-int launch_band_s4(const BandArgs& a, int nch, bool full, bool adapt, bool seqlds, long long grid, hipStream_t stream);  // 2p
-// the slim form (wfa_slim.hpp, csrc/k_slim.hip): one translation unit per gap-affine shape
-#define WFA_SLIM_DECL(i, x, oe, e) int launch_slim_s##i(const BandArgs& a, int nch, bool full, long long grid, hipStream_t stream); \
-  int launch_slim_mailbox_s##i(const BandArgs& a, bool full, hipStream_t stream, SlimMailbox* mb);
-WFA_BAND_SHAPES(WFA_SLIM_DECL)
-#undef WFA_SLIM_DECL
-int launch_slim_s4(const BandArgs& a, int nch, bool full, long long grid, hipStream_t stream);  // 2p
+template <int I> int launch_band_unit(const BandArgs& a, int nch, bool full, bool adapt, bool seqlds, long long grid, hipStream_t stream);
+// the slim form (wfa_slim.hpp); the mailbox kernel exists for the gap-affine units only (-1 from the others)
+template <int I> int launch_slim_unit(const BandArgs& a, int nch, bool full, long long grid, hipStream_t stream);
+template <int I> int launch_slim_mailbox_unit(const BandArgs& a, bool full, hipStream_t stream, SlimMailbox* mb);
 // launches the slim form covers: the wf-adaptive long-read cascade — its first window (128 diagonals, gap-affine-2p: 192; score-only
 // or the piggy-back history of a split launch) and the 256-diagonal stage behind it (score-only or the explicit int16 history, walked
 // in-kernel)
@@ -1351,46 +1356,13 @@ inline bool slim_takes(const BandArgs& a, int nch, bool full, bool adapt, bool s
   return false;
 }
 
-// configurations the band kernel covers: gap-affine / gap-affine-2p with an instantiated penalty shape
-// (x, o1 + e1, e1 [, o2 + e2, e2]) / gcd; 2p: pywfa's default 4/6/2/24/1
-#define WFA_BAND_SHAPES_2P(F) F(4, 8, 2, 25, 1)
-inline int band_gcd(const WfaDevConfig& c, bool two) {
-  int g = gcd_int(gcd_int(c.x, c.o1 + c.e1), c.e1);
-  if (two) g = gcd_int(gcd_int(g, c.o2 + c.e2), c.e2);
-  return g;
-}
+// configurations the band kernel covers: gap-affine / gap-affine-2p with a built-in penalty shape or one the run-time path takes;
 // none / wf-adaptive / X-drop, with or without a step limit
 inline bool band_supported(const WfaDevConfig& c, int ncomp) {
   if ((ncomp != 3 && ncomp != 5) || c.match != 0 || c.wildcard >= 0) return false;
   if (c.heuristic < 0 || c.heuristic > 2) return false;
-  const bool two = ncomp == 5;
-  const int g = band_gcd(c, two);
-  const int X = c.x / g, OE = (c.o1 + c.e1) / g, E = c.e1 / g;
-  if (two) {
-    const int OE2 = (c.o2 + c.e2) / g, E2 = c.e2 / g;
-#define WFA_BAND_MATCH2(x, oe, e, oe2, e2) if (X == x && OE == oe && E == e && OE2 == oe2 && E2 == e2) return true;
-    WFA_BAND_SHAPES_2P(WFA_BAND_MATCH2)
-#undef WFA_BAND_MATCH2
-    return c.rtc && rtc_shape_ok(X, OE, E, OE2, E2) && rtc_available();
-  }
-#define WFA_BAND_MATCH(i, x, oe, e) if (X == x && OE == oe && E == e) return true;
-  WFA_BAND_SHAPES(WFA_BAND_MATCH)
-#undef WFA_BAND_MATCH
-  return c.rtc && rtc_shape_ok(X, OE, E) && rtc_available();
-}
-
-// the banded kernel of a shape without an instantiation, compiled at run time (csrc/wfa_rtc.cpp): the same choice of kernel and
-// template arguments launch_band_shape / _t / _k make at compile time
-inline int launch_band_rtc(const BandArgs& a, int nch, bool full, bool adapt, bool seqlds, long long grid, hipStream_t stream) {
-  const int g = a.g, X = a.x / g, OE = a.oe / g, E = a.e / g, OE2 = a.oe2 > 0 ? a.oe2 / g : 0, E2 = a.oe2 > 0 ? a.e2 / g : 0;
-  if (!(nch == 1 || nch == 2 || nch == 4 || (nch == 3 && OE2 > 0))) return -1;
-  const bool split = full && a.split, pb = split && a.pb;
-  const char* kernel = (OE2 > 0 && nch == 3) ? "wfa_band_kernel_w4" : (OE2 > 0 && nch == 4 && !pb) ? "wfa_band_kernel_w3" : "wfa_band_kernel";
-  const std::string name = std::string("wfa::") + kernel + "<" + std::to_string(nch) + ", " + rtc_bool(full) + ", " + rtc_bool(adapt) + ", " + rtc_bool(seqlds) + ", " +
-                           rtc_bool(pb) + ", " + rtc_bool(split) + ", " + std::to_string(X) + ", " + std::to_string(OE) + ", " + std::to_string(E) + ", " +
-                           std::to_string(OE2) + ", " + std::to_string(E2) + ">";
-  const size_t smem = seqlds ? (size_t)a.lds_words * 2 * sizeof(uint32_t) : 0;
-  return rtc_launch("wfa_band.hpp", name, (unsigned)grid, 64, smem, stream, &a, sizeof(a));
+  const PenaltyShape sh = penalty_shape(c, ncomp == 5);
+  return band_unit(sh) >= 0 || (c.rtc && rtc_shape_ok(sh.X, sh.OE, sh.E, sh.OE2, sh.E2) && rtc_available());
 }
 
 // shapes without an instantiation whose slim form is compiled at run time: gap-affine with rings of up to twelve steps (round 5) and,
@@ -1400,67 +1372,79 @@ inline bool slim_rtc_shape_ok(int X, int OE, int E, int OE2, int E2 = 0) {
   if (OE2 == 0) return (X > OE ? X : OE) <= 12 && E <= 3;
   return X < OE && OE < OE2 && X <= 8 && E <= 3 && E2 >= 1 && E2 <= 2 && OE2 - X <= 40;
 }
-inline int launch_slim_rtc(const BandArgs& a, int nch, bool full, long long grid, hipStream_t stream) {
-  const int g = a.g, X = a.x / g, OE = a.oe / g, E = a.e / g, OE2 = a.oe2 / g, E2 = a.e2 / g;
-  const int hist = (full && a.split) ? 1 : full ? 2 : 0;
-  size_t smem = (size_t)a.lds_words * 2 * sizeof(uint32_t);
-  std::string name;
-  if (OE2 > 0) {
-    name = std::string("wfa::") + (nch == 4 ? "wfa_slim_kernel_tail<4, " : "wfa_slim_kernel_2p<3, ") + std::to_string(hist) + ", " + std::to_string(X) + ", " +
-           std::to_string(OE) + ", " + std::to_string(E) + ", " + std::to_string(OE2) + ", " + std::to_string(E2) + ">";
-    smem += (size_t)(OE2 - X) * (size_t)(64 * (nch == 4 ? 4 : 3) + 2) * sizeof(short);   // the LDS ring of the deep M history (wfa_slim.hpp)
-  } else {
-    name = std::string("wfa::") + (nch == 4 ? "wfa_slim_kernel_tail<4, " : "wfa_slim_kernel<2, ") + std::to_string(hist) + ", " + std::to_string(X) + ", " +
-           std::to_string(OE) + ", " + std::to_string(E) + (a.win ? ", 0, 0, true>" : ", 0, 0>");
-  }
-  return rtc_launch("wfa_slim.hpp", name, (unsigned)grid, 64, smem, stream, &a, sizeof(a));
+
+// Where a launch of the banded stage goes: a built-in unit of the banded or of the slim kernel, or the run-time instantiation of either.
+// launch_band() follows it, and slim_launches() — from which the host tells the walk which kernel wrote the codes — reads the same answer.
+struct BandRoute {
+  enum Kind { BAND_UNIT, SLIM_UNIT, SLIM_RTC, BAND_RTC } kind;
+  int unit;             // BAND_UNIT / SLIM_UNIT: band_unit(shape)
+  PenaltyShape shape;
+  BandForm form;        // BAND_UNIT / BAND_RTC: the kernel and its PB / SPLIT arguments
+};
+inline BandRoute band_route(const BandArgs& a, int nch, bool full, bool adapt, bool seqlds) {
+  BandRoute r;
+  r.shape = penalty_shape_of_args(a);
+  r.form = band_form(a.oe2 > 0, nch, full, a.split != 0, a.pb != 0);
+  r.unit = band_unit(r.shape);
+  const bool takes = slim_takes(a, nch, full, adapt, seqlds);
+  if (rtc_force_all() && rtc_available()) r.kind = BandRoute::BAND_RTC;   // (first: tests send the built-in shapes through the run-time path)
+  else if (r.unit >= 0) r.kind = takes ? BandRoute::SLIM_UNIT : BandRoute::BAND_UNIT;
+  else r.kind = (takes && slim_rtc_shape_ok(r.shape.X, r.shape.OE, r.shape.E, r.shape.OE2, r.shape.E2)) ? BandRoute::SLIM_RTC : BandRoute::BAND_RTC;
+  return r;
 }
 
-// true when launch_band() sends this launch to wfa_slim_kernel: slim_takes() and a shape the library has an instantiation of or
-// compiles the slim form of (the host sets BandArgs::pb_raw from it before the launch: the walk must know which kernel wrote the codes)
+// the banded kernel of a shape without an instantiation, compiled at run time (csrc/wfa_rtc.cpp)
+inline std::string band_rtc_name(const PenaltyShape& sh, const BandForm& f, int nch, bool full, bool adapt, bool seqlds) {
+  const char* kernel = f.kernel == 4 ? "wfa_band_kernel_w4" : f.kernel == 3 ? "wfa_band_kernel_w3" : "wfa_band_kernel";
+  return std::string("wfa::") + kernel + "<" + std::to_string(nch) + ", " + rtc_bool(full) + ", " + rtc_bool(adapt) + ", " + rtc_bool(seqlds) + ", " +
+         rtc_bool(f.pb) + ", " + rtc_bool(f.split) + ", " + std::to_string(sh.X) + ", " + std::to_string(sh.OE) + ", " + std::to_string(sh.E) + ", " +
+         std::to_string(sh.OE2) + ", " + std::to_string(sh.E2) + ">";
+}
+inline int launch_band_rtc(const BandArgs& a, const BandRoute& r, int nch, bool full, bool adapt, bool seqlds, long long grid, hipStream_t stream) {
+  if (!(nch == 1 || nch == 2 || nch == 4 || (nch == 3 && r.shape.OE2 > 0))) return -1;
+  const size_t smem = seqlds ? (size_t)a.lds_words * 2 * sizeof(uint32_t) : 0;
+  return rtc_launch("wfa_band.hpp", band_rtc_name(r.shape, r.form, nch, full, adapt, seqlds), (unsigned)grid, 64, smem, stream, &a, sizeof(a));
+}
+
+// the slim kernel of a shape without an instantiation (hist: 0 score only, 1 the piggy-back history of a split launch, 2 the explicit one)
+inline std::string slim_rtc_name(const PenaltyShape& sh, int nch, int hist, bool win) {
+  const std::string head = std::string("wfa::") + (nch == 4 ? "wfa_slim_kernel_tail<4, " : sh.OE2 > 0 ? "wfa_slim_kernel_2p<3, " : "wfa_slim_kernel<2, ") +
+                           std::to_string(hist) + ", " + std::to_string(sh.X) + ", " + std::to_string(sh.OE) + ", " + std::to_string(sh.E);
+  if (sh.OE2 > 0) return head + ", " + std::to_string(sh.OE2) + ", " + std::to_string(sh.E2) + ">";
+  return head + (win ? ", 0, 0, true>" : ", 0, 0>");
+}
+inline int launch_slim_rtc(const BandArgs& a, const PenaltyShape& sh, int nch, bool full, long long grid, hipStream_t stream) {
+  size_t smem = (size_t)a.lds_words * 2 * sizeof(uint32_t);
+  if (sh.OE2 > 0) smem += (size_t)(sh.OE2 - sh.X) * (size_t)(64 * (nch == 4 ? 4 : 3) + 2) * sizeof(short);   // the LDS ring of the deep M history (wfa_slim.hpp)
+  return rtc_launch("wfa_slim.hpp", slim_rtc_name(sh, nch, (full && a.split) ? 1 : full ? 2 : 0, a.win != 0), (unsigned)grid, 64, smem, stream, &a, sizeof(a));
+}
+
+// true when launch_band() sends this launch to wfa_slim_kernel (the host sets BandArgs::pb_raw from it before the launch: the walk must
+// know which kernel wrote the codes).  A run-time slim kernel counts only where hipRTC works.  launch_band() itself does not ask: a
+// shape without a unit reaches it only after band_supported() has said yes, which for such a shape includes rtc_available() — so the
+// two agree on every launch that is made.
 inline bool slim_launches(const BandArgs& a, int nch, bool full, bool adapt, bool seqlds) {
-  if (!slim_takes(a, nch, full, adapt, seqlds) || (rtc_force_all() && rtc_available())) return false;
-  const int g = a.g, X = a.x / g, OE = a.oe / g, E = a.e / g;
-  if (a.oe2 > 0) {
-    const int OE2 = a.oe2 / g, E2 = a.e2 / g;
-#define WFA_SLIM_MATCH2(x_, oe_, e_, oe2_, e2_) if (X == x_ && OE == oe_ && E == e_ && OE2 == oe2_ && E2 == e2_) return true;
-    WFA_BAND_SHAPES_2P(WFA_SLIM_MATCH2)
-#undef WFA_SLIM_MATCH2
-    return slim_rtc_shape_ok(X, OE, E, OE2, E2) && rtc_available();
-  }
-#define WFA_SLIM_MATCH(i, x, oe, e) if (X == x && OE == oe && E == e) return true;
-  WFA_BAND_SHAPES(WFA_SLIM_MATCH)
-#undef WFA_SLIM_MATCH
-  return slim_rtc_shape_ok(X, OE, E, 0) && rtc_available();
+  const BandRoute r = band_route(a, nch, full, adapt, seqlds);
+  return r.kind == BandRoute::SLIM_UNIT || (r.kind == BandRoute::SLIM_RTC && rtc_available());
 }
 
 // an instance of the resident one-pair kernel (wfa_slim.hpp) for this configuration; -1: none (gap-affine-2p, a shape without an
 // instantiation, a launch the slim form does not take)
 inline int launch_slim_mailbox(const BandArgs& a, bool full, bool adapt, hipStream_t stream, SlimMailbox* mb) {
-  if (a.oe2 > 0 || a.split || !slim_takes(a, 2, full, adapt, true) || (rtc_force_all() && rtc_available())) return -1;
-  const int g = a.g, X = a.x / g, OE = a.oe / g, E = a.e / g;
-#define WFA_SLIM_MB(i, x, oe, e) if (X == x && OE == oe && E == e) return launch_slim_mailbox_s##i(a, full, stream, mb);
-  WFA_BAND_SHAPES(WFA_SLIM_MB)
-#undef WFA_SLIM_MB
-  return -1;
+  if (a.oe2 > 0 || a.split) return -1;
+  const BandRoute r = band_route(a, 2, full, adapt, true);
+  if (r.kind != BandRoute::SLIM_UNIT) return -1;
+  return with_shape_index<band_unit_count>(r.unit, [&](auto i) { return launch_slim_mailbox_unit<decltype(i)::value>(a, full, stream, mb); });
 }
 
 inline int launch_band(const BandArgs& a, int nch, bool full, bool adapt, bool seqlds, long long grid, hipStream_t stream) {
-  const int g = a.g, X = a.x / g, OE = a.oe / g, E = a.e / g;
-  if (rtc_force_all() && rtc_available()) return launch_band_rtc(a, nch, full, adapt, seqlds, grid, stream);
-  if (a.oe2 > 0) {
-    const int OE2 = a.oe2 / g, E2 = a.e2 / g;
-#define WFA_BAND_LAUNCH2(x_, oe_, e_, oe2_, e2_) if (X == x_ && OE == oe_ && E == e_ && OE2 == oe2_ && E2 == e2_) return slim_takes(a, nch, full, adapt, seqlds) ? launch_slim_s4(a, nch, full, grid, stream) : launch_band_s4(a, nch, full, adapt, seqlds, grid, stream);
-    WFA_BAND_SHAPES_2P(WFA_BAND_LAUNCH2)
-#undef WFA_BAND_LAUNCH2
-    if (slim_takes(a, nch, full, adapt, seqlds) && slim_rtc_shape_ok(X, OE, E, OE2, E2)) return launch_slim_rtc(a, nch, full, grid, stream);
-    return launch_band_rtc(a, nch, full, adapt, seqlds, grid, stream);
+  const BandRoute r = band_route(a, nch, full, adapt, seqlds);
+  switch (r.kind) {
+    case BandRoute::SLIM_UNIT: return with_shape_index<band_unit_count>(r.unit, [&](auto i) { return launch_slim_unit<decltype(i)::value>(a, nch, full, grid, stream); });
+    case BandRoute::BAND_UNIT: return with_shape_index<band_unit_count>(r.unit, [&](auto i) { return launch_band_unit<decltype(i)::value>(a, nch, full, adapt, seqlds, grid, stream); });
+    case BandRoute::SLIM_RTC: return launch_slim_rtc(a, r.shape, nch, full, grid, stream);
+    default: return launch_band_rtc(a, r, nch, full, adapt, seqlds, grid, stream);
   }
-#define WFA_BAND_LAUNCH(i, x, oe, e) if (X == x && OE == oe && E == e) return slim_takes(a, nch, full, adapt, seqlds) ? launch_slim_s##i(a, nch, full, grid, stream) : launch_band_s##i(a, nch, full, adapt, seqlds, grid, stream);
-  WFA_BAND_SHAPES(WFA_BAND_LAUNCH)
-#undef WFA_BAND_LAUNCH
-  if (slim_takes(a, nch, full, adapt, seqlds) && slim_rtc_shape_ok(X, OE, E, 0)) return launch_slim_rtc(a, nch, full, grid, stream);
-  return launch_band_rtc(a, nch, full, adapt, seqlds, grid, stream);
 }
 
 #endif  // __HIPCC_RTC__

@@ -784,10 +784,9 @@ template <class Args> static void fill_heuristic(Args& a, const WfaDevConfig& d)
   a.heur = d.heuristic; a.min_wf_len = d.min_wf_len; a.max_dist_thr = d.max_dist_thr;
   a.steps_between = d.steps_between; a.max_steps = d.max_steps;
 }
-static int affine_gcd(const WfaDevConfig& d) { return wfa::gcd_int(wfa::gcd_int(d.x, d.o1 + d.e1), d.e1); }
 // (BandArgs: the penalties, and the gcd the kernels divide scores by; two: gap-affine-2p)
 static void fill_band_penalties(wfa::BandArgs& a, const WfaDevConfig& d, bool two) {
-  a.g = wfa::band_gcd(d, two);
+  a.g = wfa::penalty_shape(d, two).g;
   a.x = d.x; a.oe = d.o1 + d.e1; a.e = d.e1;
   if (two) { a.oe2 = d.o2 + d.e2; a.e2 = d.e2; }
 }
@@ -1351,12 +1350,13 @@ static int pilot_first_width(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t 
   }
   // Score only, 16 diagonals first: the 8-diagonal lane form (wfa_lane.hpp, NRP = 4) in front of it pays while it proves most pairs —
   // what it hands on starts over in the 16-diagonal form.  Its own pass over the same sample decides (b->narrow_pick).
-  int X, OE, E;
-  if (!full && b->stage_pick == 16 && wfa::seg_shape(b->dcfg, &X, &OE, &E) != WFA_SHAPE_RTC) {
+  wfa::PenaltyShape sh;
+  const int shape = wfa::seg_shape(b->dcfg, &sh);
+  if (!full && b->stage_pick == 16 && shape != WFA_SHAPE_RTC) {
     HIP_TRY(al, hipMemsetAsync(pcount, 0, sizeof(uint32_t), stream));
-    if (wfa::launch_lane(wfa::seg_shape(b->dcfg, &X, &OE, &E), wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1), al->cu_count,
+    if (wfa::launch_lane(shape, sh, al->cu_count,
                          knob(al, K_LANE_WAVES_PER_CU, 48), wfa::lane_refill_arg(knob(al, K_LANE_REFILL_MIN, 8), knob(al, K_LANE_WINFIN, 1) != 0), b->max_len, stream, b->d_words, b->d_meta, psample, nullptr, np,
-                         b->d_score, b->d_status, plist, pcount, nullptr, 0, X, OE, E, 0, nullptr, 0, 4) != 0) return pilot_launch_failed(al, b, rtc_failures);
+                         b->d_score, b->d_status, plist, pcount, nullptr, 0, 0, nullptr, 0, 4) != 0) return pilot_launch_failed(al, b, rtc_failures);
     uint32_t handed = 0;
     HIP_TRY(al, hipMemcpyAsync(&handed, pcount, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(al, hipStreamSynchronize(stream));
@@ -1416,15 +1416,16 @@ static int pilot_lane_heur(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t st
   if (b->laneh_pick != 0 || b->cfg.scope == WFA_SCOPE_FULL) return WFA_HIP_OK;
   const unsigned rtc_failures = wfa::rtc_failure_count();
   b->laneh_pick = 2; b->segh_pick = 2;
-  int X, OE, E;
   const bool lane_ok = wfa::lane_heur_config(b->dcfg, b->ncomp);
   const bool seg_ok = wfa::seg_heur_config(b->dcfg, b->ncomp);
-  if ((!lane_ok && !seg_ok) || wfa::seg_supported(b->dcfg, b->ncomp, false) ||
-      wfa::seg_shape(b->dcfg, &X, &OE, &E) < 0 || b->max_len > WFA_FAST_MAX_LEN || knob(al, K_NO_FAST, 0) != 0) return WFA_HIP_OK;
+  if ((!lane_ok && !seg_ok) || wfa::seg_supported(b->dcfg, b->ncomp, false)) return WFA_HIP_OK;
+  wfa::PenaltyShape sh;
+  const int shape = wfa::seg_shape(b->dcfg, &sh);
+  if (shape < 0 || b->max_len > WFA_FAST_MAX_LEN || knob(al, K_NO_FAST, 0) != 0) return WFA_HIP_OK;
   const bool free_begins = b->dcfg.endsfree && (b->dcfg.pbf | b->dcfg.tbf) != 0;
   int forced = knob(al, K_LANE_HEUR, -1);       // (WFA_HIP_LANE_HEUR = 1 / 0: always / never, whatever the batch)
   if (!lane_ok) forced = 0;                     // (X-drop: the segmented form only)
-  if (wfa::seg_shape(b->dcfg, &X, &OE, &E) == WFA_SHAPE_RTC && !wfa::rtc_lane_shape_ok(X, OE, E)) forced = 0;   // (a run-time shape whose rings outgrow the lane kernel's registers)
+  if (shape == WFA_SHAPE_RTC && !wfa::rtc_lane_shape_ok(sh.X, sh.OE, sh.E)) forced = 0;   // (a run-time shape whose rings outgrow the lane kernel's registers)
   const int forced_seg = knob(al, K_SEG_HEUR, -1);    // (WFA_HIP_SEG_HEUR likewise)
   if (forced >= 0) b->laneh_pick = forced == 2 ? 3 : forced ? 1 : 2;   // (2: the 32-diagonal form)
   if (forced_seg >= 0) b->segh_pick = (forced_seg && seg_ok) ? 1 : 2;
@@ -1441,20 +1442,20 @@ static int pilot_lane_heur(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t st
   memset(&fa, 0, sizeof(fa));
   fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = psample; fa.nwork = np;
   fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = plist; fa.fb_count = pcount;
-  fa.g = wfa::gcd_int(wfa::gcd_int(b->dcfg.x, b->dcfg.o1 + b->dcfg.e1), b->dcfg.e1);
+  fa.g = sh.g;
   fa.ef = (b->dcfg.endsfree && (b->dcfg.pbf | b->dcfg.pef | b->dcfg.tbf | b->dcfg.tef)) ? 1 : 0;
   fa.pbf = b->dcfg.pbf; fa.pef = b->dcfg.pef; fa.tbf = b->dcfg.tbf; fa.tef = b->dcfg.tef;
   fa.heur = b->dcfg.heuristic; fa.min_wf_len = b->dcfg.min_wf_len; fa.max_dist_thr = b->dcfg.max_dist_thr;
   fa.steps_between = b->dcfg.steps_between; fa.max_steps = b->dcfg.max_steps; fa.xdrop = b->dcfg.xdrop; fa.scope = b->dcfg.scope;
   if (forced < 0 &&
-      wfa::launch_lane_args(wfa::seg_shape(b->dcfg, &X, &OE, &E), OE, E, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8),
-                            b->max_len, stream, fa, false, 0, 256, 1, X) != 0) return pilot_launch_failed(al, b, rtc_failures);
+      wfa::launch_lane_args(shape, sh, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8),
+                            b->max_len, stream, fa, false, 0, 256, 1) != 0) return pilot_launch_failed(al, b, rtc_failures);
   // (round 6) ... and through the 32-diagonal form of the same kernel (rings of 16 registers: shallow shapes only)
-  const bool lane32_ok = std::max(X, OE) <= 8 && E <= 3 && knob(al, K_LANE_HEUR32, 1) != 0;
+  const bool lane32_ok = std::max(sh.X, sh.OE) <= 8 && sh.E <= 3 && knob(al, K_LANE_HEUR32, 1) != 0;
   if (forced < 0 && lane32_ok) {
     fa.fb_count = pcount + 2;
-    if (wfa::launch_lane_args(wfa::seg_shape(b->dcfg, &X, &OE, &E), OE, E, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8),
-                              b->max_len, stream, fa, false, 0, 256, 2, X) != 0) return pilot_launch_failed(al, b, rtc_failures);
+    if (wfa::launch_lane_args(shape, sh, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8),
+                              b->max_len, stream, fa, false, 0, 256, 2) != 0) return pilot_launch_failed(al, b, rtc_failures);
   }
   if (forced_seg < 0 && seg_ok) {   // (the same sample through the 32-lane form; its list is not read, only its count)
     fa.fb_count = pcount + 1;
@@ -1778,7 +1779,8 @@ struct CascadePlan {
   bool tiny = false, lin = false, adapt = false;
   bool use_fast = false, use_segfull = false, use_laneh = false, use_segh = false, use_lanefull = false;
   int laneh_form = 1;                       // (2: 32 diagonals per pair)
-  int shape = -1, sh_x = 0, sh_oe = 0, sh_e = 0;   // wfa::seg_shape of the run's penalties, and the penalties over their gcd
+  int shape = -1;                           // wfa::seg_shape of the run's penalties ...
+  wfa::PenaltyShape sh = {};                // ... and their gap-affine shape
   bool lane_shape_fits = false;             // a built-in shape, or a run-time one whose rings fit the lane kernel's registers
   int64_t budget = 0;                       // free_budget at the top of the plan (nothing in it allocates)
   bool wide_adapt = false, wide_ok = false, wide32 = false, wide_two = false;
@@ -1869,7 +1871,7 @@ static void plan_band_stages(wfa_hip_aligner* al, const wfa_hip_batch* b, Cascad
       const bool h16 = b->max_len < 32000;   // (wfa_band.hpp's range, sat16: the inputs of a valid cell never exceed 32 767 — 4 x int16 entries; as launch_band_stage's)
       const int rec = ((h16 && b->ncomp != 5) ? 2 : 4) * (p.band_nch[i] == 3 ? 256 : 64 * p.band_nch[i]);  // ints per record (2p: 16-byte entries)
       // steps of an alignment = score / g; sized for scores up to 0.9 x the read length (about 15 % divergence)
-      long long records = std::max<long long>(256, (long long)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / wfa::band_gcd(b->dcfg, b->ncomp == 5) + 64);
+      long long records = std::max<long long>(256, (long long)(b->max_len * 0.9 * penalty_scale(b->dcfg)) / wfa::penalty_shape(b->dcfg, b->ncomp == 5).g + 64);
       records = knob(al, K_BAND_RECORDS, (int)records);
       p.band_stride[i] = ((int64_t)records * rec + 63) & ~63ll;
       const int64_t budget = p.budget;
@@ -2151,7 +2153,7 @@ static void plan_lanefull(const wfa_hip_aligner* al, const wfa_hip_batch* b, Cas
     // a wave's life: 65 536 pairs with CIGAR 397 -> 289 us; 1 M pairs in two launches: 1.07 ms with 256, 1.15 with 64).  One value for the
     // geometry and every launch of the stage: a shorter last launch must not have more waves than the record lists were sized for
     p.lf_min_pairs = knob(al, K_LANE_MIN_PAIRS, p.lanefull_cap <= 262144 ? 64 : 256);
-    wfa::lane_full_geometry((uint32_t)p.lanefull_cap, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), p.lf_min_pairs, p.sh_oe, p.sh_e,
+    wfa::lane_full_geometry((uint32_t)p.lanefull_cap, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), p.lf_min_pairs, p.sh.OE, p.sh.E,
                             &p.lanefull_grid, &p.lanefull_recs);
     p.lanefull_codes_off = p.lanefull_off + (((size_t)(p.lanefull_cap * p.lanefull_split * p.lanefull_slot_bytes) + 255) & ~(size_t)255);
     p.lanefull_codes_bytes = ((size_t)p.lanefull_grid * (size_t)p.lanefull_recs * 512 + 255) & ~(size_t)255;
@@ -2166,8 +2168,8 @@ static void plan_cascade(wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePla
   const bool full = (b->cfg.scope == WFA_SCOPE_FULL);
   const uint32_t in_n = b->n_packed;
   p.budget = free_budget(al);
-  p.shape = wfa::seg_shape(b->dcfg, &p.sh_x, &p.sh_oe, &p.sh_e);
-  p.lane_shape_fits = p.shape != WFA_SHAPE_RTC || wfa::rtc_lane_shape_ok(p.sh_x, p.sh_oe, p.sh_e);
+  p.shape = wfa::seg_shape(b->dcfg, &p.sh);
+  p.lane_shape_fits = p.shape != WFA_SHAPE_RTC || wfa::rtc_lane_shape_ok(p.sh.X, p.sh.OE, p.sh.E);
   p.adapt = (b->dcfg.heuristic != WFA_HEUR_NONE);  // the heuristic instantiations of the banded kernel (wf-adaptive / X-drop)
   // a handful of short pairs: one launch of the general kernel beats six nearly empty stages (single-pair calls of a
   // pywfa-style loop).  Long reads take the stages whatever the count: an alignment of milliseconds dwarfs the launches, and
@@ -2222,9 +2224,8 @@ static void plan_cascade(wfa_hip_aligner* al, const wfa_hip_batch* b, CascadePla
   if (p.wide_ok) {
     wfa::WideArgs& w0 = p.w0;
     memset(&w0, 0, sizeof(w0));
-    w0.g = p.wide_two ? wfa::band_gcd(b->dcfg, true) : affine_gcd(b->dcfg);
-    w0.X = b->dcfg.x / w0.g; w0.OE = (b->dcfg.o1 + b->dcfg.e1) / w0.g; w0.E = b->dcfg.e1 / w0.g;
-    if (p.wide_two) { w0.OE2 = (b->dcfg.o2 + b->dcfg.e2) / w0.g; w0.E2 = b->dcfg.e2 / w0.g; }
+    const wfa::PenaltyShape ws = wfa::penalty_shape(b->dcfg, p.wide_two);
+    w0.g = ws.g; w0.X = ws.X; w0.OE = ws.OE; w0.E = ws.E; w0.OE2 = ws.OE2; w0.E2 = ws.E2;
     w0.seq_words = ((b->max_len + 15) >> 4) + 4;
     p.full_range = (2 * b->max_len + 8 + b->dcfg.pbf + b->dcfg.tbf) & ~1;
     plan_tile_stage(al, b, p);
@@ -2361,7 +2362,7 @@ static int run_biwfa(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, 
       // sub-sequences outgrow the buffers) moves to the level's second launch, the workspace form: rows in HBM / L2, the pair's
       // sequences in LDS when they fit, four chunks of loads in flight per thread.
       const bool lds_form = kind == 0 && bp.bl_i16 && b->ncomp <= 3 && knob(al, K_BILEVEL_LDS, 0) != 0;   // (off: measured slower than the workspace form at every level of 1 kb and 10 kb reads — per-step overheads, not the rows' latency, are what a narrow window pays)
-      const int gsc = std::max(1, wfa::band_gcd(b->dcfg, false));
+      const int gsc = std::max(1, wfa::penalty_shape(b->dcfg, false).g);
       bp.la.lds_slots = (b->dcfg.scope - 1) / gsc + 1;
       const int full_seq_words = (b->max_len + 15) / 16 + 4;
       const bool seql = kind == 0 && (size_t)2 * full_seq_words * 4 <= (size_t)48 * 1024 && knob(al, K_BILEVEL_NO_SEQL, 0) == 0;
@@ -2443,7 +2444,7 @@ static int run_lanefull_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t
   fa.lin = b->dcfg.lin;
   fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = c.in_list; fa.nwork_dev = nullptr;
   fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
-  fa.g = affine_gcd(b->dcfg);
+  fa.g = p.sh.g;
   const int64_t lf_slots = p.lanefull_cap * p.lanefull_split;   // slots in the region (split: slot = work item; otherwise one launch's worth, reused)
   int32_t* const lf_runs = al->ws + p.lanefull_off / 4;
   int4* const lf_ends = reinterpret_cast<int4*>(reinterpret_cast<char*>(al->ws) + p.lanefull_off + (size_t)lf_slots * WFA_LANE_RUN_SLOT * 4);
@@ -2471,7 +2472,7 @@ static int run_lanefull_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t
       ba.hist = fa.hist; ba.end_state = fa.end_state; ba.lane_codes = fa.codes;
     }
     // (a shorter last launch has fewer waves and needs fewer records than the lists were sized for)
-    if (wfa::launch_lane_args(p.shape, p.sh_oe, p.sh_e, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, fa, true, 0, p.lf_min_pairs, false, p.sh_x) != 0) {
+    if (wfa::launch_lane_args(p.shape, p.sh, al->cu_count, knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, fa, true, 0, p.lf_min_pairs) != 0) {
       al->err = "lane kernel launch failed"; return WFA_HIP_EDEVICE;
     }
     ba.work_begin = (uint32_t)w0; ba.nwork = cnt;
@@ -2574,12 +2575,12 @@ static int run_fast_stages(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t st
         const int64_t per_wave = expect / std::max<int64_t>(1, (int64_t)al->cu_count * dyn_waves * 2);
         lane_dyn = (uint32_t)std::max<int64_t>(64, std::min<int64_t>(lane_dyn, per_wave));
       }
-      lrc = wfa::launch_lane(p.shape, affine_gcd(b->dcfg), al->cu_count,
+      lrc = wfa::launch_lane(p.shape, p.sh, al->cu_count,
                              lane_dyn ? dyn_waves : knob(al, K_LANE_WAVES_PER_CU, 48),
                              // (WFA_HIP_LANE_WINFIN=0: the window pass finishes only what the refill used to, for A/B runs and tests)
                              wfa::lane_refill_arg(knob(al, K_LANE_REFILL_MIN, 8), knob(al, K_LANE_WINFIN, 1) != 0), b->max_len, stream, b->d_words, b->d_meta,
                              c.in_list, c.in_count, c.in_n, b->d_score, b->d_status, out_list, out_count,
-                             (knob(al, K_LANE_DEBUG, 0) && al->ws) ? al->ws : nullptr, knob(al, K_LANE_LDS_PAD_KB, 0), p.sh_x, p.sh_oe, p.sh_e, knob(al, K_LANE_MIN_PAIRS, 0),
+                             (knob(al, K_LANE_DEBUG, 0) && al->ws) ? al->ws : nullptr, knob(al, K_LANE_LDS_PAD_KB, 0), knob(al, K_LANE_MIN_PAIRS, 0),
                              // (slices of the list taken at run time, 192 pairs at a time, from counters zeroed with the run's others: [12] for
                              // the first lane stage, [14] for the one behind it; WFA_HIP_LANE_DYN=0: fixed slices)
                              b->d_counters + (lane_k == 0 ? CNT_LANE_DYN0 : CNT_LANE_DYN1), lane_dyn, narrow ? 4 : 8);
@@ -2611,13 +2612,13 @@ static int run_laneh_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t st
   memset(&fa, 0, sizeof(fa));
   fa.words = b->d_words; fa.meta = b->d_meta; fa.worklist = c.in_list; fa.nwork_dev = c.in_count; fa.nwork = c.in_n;
   fa.score = b->d_score; fa.status = b->d_status; fa.fb_list = out_list; fa.fb_count = out_count;
-  fa.g = affine_gcd(b->dcfg);
+  fa.g = p.sh.g;
   fill_ends_free(fa, b->dcfg, true);
   fill_heuristic(fa, b->dcfg);
   // (slices of the list taken at run time, as the plain score-only form)
   const uint32_t laneh_dyn = (c.in_count == nullptr && c.in_n >= 65536u) ? (uint32_t)std::max(0, knob(al, K_LANE_DYN, 192)) : 0u;
   if (laneh_dyn) { fa.dyn_next = b->d_counters + CNT_LANEH_DYN; fa.dyn_chunk = laneh_dyn; }
-  if (wfa::launch_lane_args(p.shape, p.sh_oe, p.sh_e, al->cu_count, laneh_dyn ? knob(al, K_LANE_DYN_WAVES, 16) : knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, fa, false, 0, knob(al, K_LANE_MIN_PAIRS, 0), p.laneh_form, p.sh_x) != 0) {   // (pairs per wave by the size of the batch, as the plain form)
+  if (wfa::launch_lane_args(p.shape, p.sh, al->cu_count, laneh_dyn ? knob(al, K_LANE_DYN_WAVES, 16) : knob(al, K_LANE_WAVES_PER_CU, 48), knob(al, K_LANE_REFILL_MIN, 8), b->max_len, stream, fa, false, 0, knob(al, K_LANE_MIN_PAIRS, 0), p.laneh_form) != 0) {   // (pairs per wave by the size of the batch, as the plain form)
     al->err = "lane kernel launch failed"; return WFA_HIP_EDEVICE;
   }
   c.advance(b, out_list, out_count);

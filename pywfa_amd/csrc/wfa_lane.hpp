@@ -90,6 +90,7 @@
 #include "wfa_hip.h"
 #ifndef __HIPCC_RTC__
 #include "wfa_rtc.hpp"
+#include "wfa_shapes.hpp"
 #endif
 
 namespace wfa {
@@ -946,13 +947,8 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
 }
 
 #ifndef __HIPCC_RTC__   // ---- host side (launch code) ----
-// per-shape entry points (csrc/k_lane.hip compiled once per shape index of WFA_SEG_SHAPES)
-#define WFA_LANE_DECL(i, x, oe, e) \
-  int launch_lane_s##i(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur, int nrp);
-// (the shape list is wfa_seg.hpp's; declared here without including it)
-WFA_LANE_DECL(0, 2, 4, 1) WFA_LANE_DECL(1, 2, 3, 1) WFA_LANE_DECL(2, 4, 7, 1) WFA_LANE_DECL(3, 3, 5, 1)
-WFA_LANE_DECL(4, 6, 8, 3) WFA_LANE_DECL(5, 5, 3, 3) WFA_LANE_DECL(6, 1, 2, 1)
-#undef WFA_LANE_DECL
+// per-shape entry point (csrc/k_lane.hip, compiled once per index of affine_shapes, wfa_shapes.hpp)
+template <int I> int launch_lane_unit(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur, int nrp);
 
 template <int X, int OE, int E>
 inline int launch_lane_shape(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur, int nrp) {
@@ -966,7 +962,7 @@ inline int launch_lane_shape(unsigned grid, size_t smem, hipStream_t stream, con
 }
 
 // configurations of the general score-only form (HEUR): gap-affine with an instantiated shape, match 0, no wildcard; no heuristic or
-// wf-adaptive (X-drop stays in the banded kernel), any free ends, any step limit (the shape list is wfa_seg.hpp's: seg_shape())
+// wf-adaptive (X-drop stays in the banded kernel), any free ends, any step limit (the shape: seg_shape(), wfa_seg.hpp)
 inline bool lane_heur_config(const WfaDevConfig& c, int ncomp) {
   return ncomp == 3 && c.match == 0 && c.wildcard < 0 && (c.heuristic == 0 || c.heuristic == 1);
 }
@@ -982,7 +978,7 @@ inline int lane_slot_words(int max_len) {
 // the window pass finishes only the pairs whose chain reaches their end, as the refill used to)
 inline int lane_refill_arg(int refill_min, bool winfin) { return (refill_min & 0xff) | (winfin ? 0x100 : 0); }
 
-// shape_idx: index in WFA_SEG_SHAPES (seg_shape()); per_cu: slices of the work list (waves) per CU
+// shape_idx: index in affine_shapes (seg_shape()); per_cu: slices of the work list (waves) per CU
 // records of origin codes per lane of the FULL form for a penalty shape (LaneFull<OE, E>::NREC)
 inline int lane_full_records(int OE, int E) { return 2 * (OE - E) + E * 17 + 1; }
 // FULL form: waves of a launch over `nwork` pairs and the records a wave's list needs.  A wave of `per` pairs makes at most
@@ -1003,29 +999,20 @@ inline void lane_full_geometry(uint32_t nwork, int cu_count, int per_cu, int min
 // run records per pair of the FULL form (ints of a slot): an alignment inside the band has at most Bmin / g edits
 #define WFA_LANE_RUN_SLOT 32
 
-// full = the FULL form: a.hist = run-record slots (a.hist_stride ints each, slot = work item - a.work_begin), a.end_state per slot
-// (shape_idx WFA_SHAPE_RTC: no instantiation in the library — the kernel of (X, OE, E) is compiled at run time, csrc/wfa_rtc.cpp)
-inline int launch_lane_args(int shape_idx, int OE, int E, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, FastArgs a, bool full, int lds_pad_kb = 0, int min_pairs = 0, int heur = 0, int X = 0, int nrp = 8);   // heur: 0 no, 1 the general form (16 diagonals), 2 its 32-diagonal form; nrp: 8 (16 diagonals) or 4 (8 diagonals: plain score-only form, instantiated shapes only)
-
-inline int launch_lane(int shape_idx, int g, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, const uint32_t* words,
-                       const WfaPairMeta* meta, const uint32_t* worklist, const uint32_t* nwork_dev, uint32_t nwork,
-                       int32_t* score, int32_t* status, uint32_t* fb_list, uint32_t* fb_count, int32_t* debug_counters = nullptr, int lds_pad_kb = 0,
-                       int X = 0, int OE = 0, int E = 0, int min_pairs = 0, uint32_t* dyn_next = nullptr, uint32_t dyn_chunk = 0, int nrp = 8) {
-  FastArgs a = FastArgs();
-  a.dyn_next = dyn_chunk ? dyn_next : nullptr; a.dyn_chunk = dyn_chunk;
-  a.words = words; a.meta = meta; a.worklist = worklist; a.nwork_dev = nwork_dev; a.nwork = nwork;
-  a.score = score; a.status = status; a.fb_list = fb_list; a.fb_count = fb_count;
-  a.g = g;
-  a.hist = debug_counters; a.hist_stride = 0; a.end_state = nullptr; a.work_begin = 0;
-  a.ef = a.pbf = a.pef = a.tbf = a.tef = 0; a.heur = 0; a.min_wf_len = a.max_dist_thr = a.steps_between = 0; a.max_steps = INT_MAX;
-  return launch_lane_args(shape_idx, OE, E, cu_count, per_cu, refill_min, max_len, stream, a, false, lds_pad_kb, min_pairs, 0, X, nrp);
+// the lane kernel of a run-time shape: wfa_lane_kernel<X, OE, E, FULL, HEUR [, LIN [, NRP]]>
+inline std::string lane_rtc_name(const PenaltyShape& sh, bool full, int heur, int lin) {
+  return "wfa::wfa_lane_kernel<" + std::to_string(sh.X) + ", " + std::to_string(sh.OE) + ", " + std::to_string(sh.E) + ", " +
+         rtc_bool(full && !heur) + ", " + rtc_bool(heur != 0) + (heur == 2 ? std::string(", 0, 16>") : lin ? ", " + std::to_string(lin) + ">" : std::string(">"));
 }
 
-inline int launch_lane_args(int shape_idx, int OE, int E, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, FastArgs a, bool full, int lds_pad_kb, int min_pairs, int heur, int X, int nrp) {
+// full = the FULL form: a.hist = run-record slots (a.hist_stride ints each, slot = work item - a.work_begin), a.end_state per slot
+// (shape_idx WFA_SHAPE_RTC: no instantiation in the library — the kernel of `sh` is compiled at run time, csrc/wfa_rtc.cpp)
+// heur: 0 no, 1 the general form (16 diagonals), 2 its 32-diagonal form; nrp: 8 (16 diagonals) or 4 (8 diagonals: plain score-only form, instantiated shapes only)
+inline int launch_lane_args(int shape_idx, const PenaltyShape& sh, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, FastArgs a, bool full, int lds_pad_kb = 0, int min_pairs = 0, int heur = 0, int nrp = 8) {
   const uint32_t nwork = a.nwork;
   const uint32_t* nwork_dev = a.nwork_dev;
   const int slot_words = lane_slot_words(std::min(max_len, WFA_FAST_MAX_LEN));
-  const size_t smem = ((size_t)64 * slot_words + 8) * sizeof(uint32_t) + (size_t)lds_pad_kb * 1024;   // (lds_pad_kb: occupancy experiments)   // (lds_pad_kb: occupancy experiments)
+  const size_t smem = ((size_t)64 * slot_words + 8) * sizeof(uint32_t) + (size_t)lds_pad_kb * 1024;   // (lds_pad_kb: occupancy experiments)
   // every wave should see several hundred pairs (64 lanes x a few refills), and there should be several waves per SIMD
   long long grid = (long long)cu_count * per_cu;
   // a wave should see a few refills' worth of pairs (256) — when the batch is large enough to give every SIMD four such waves.  A smaller
@@ -1040,22 +1027,28 @@ inline int launch_lane_args(int shape_idx, int OE, int E, int cu_count, int per_
   if (a.lin) shape_idx = WFA_SHAPE_RTC;      // (the one-component form: instantiated at run time whatever the shape)
   if (nrp != 8 && nrp != 4) return -1;
   if (nrp == 4 && (shape_idx == WFA_SHAPE_RTC || full || heur)) return -1;   // (the 8-diagonal form: built-in shapes, plain score-only form)
-  switch (shape_idx) {
-    case 0: return launch_lane_s0((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
-    case 1: return launch_lane_s1((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
-    case 2: return launch_lane_s2((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
-    case 3: return launch_lane_s3((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
-    case 4: return launch_lane_s4((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
-    case 5: return launch_lane_s5((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
-    case 6: return launch_lane_s6((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
-    case WFA_SHAPE_RTC: {
-      struct { FastArgs a; int slot_words; int refill_min; } args = {a, slot_words, refill_min};   // (the kernel's argument list)
-      const std::string name = "wfa::wfa_lane_kernel<" + std::to_string(X) + ", " + std::to_string(OE) + ", " + std::to_string(E) + ", " +
-                               rtc_bool(full && !heur) + ", " + rtc_bool(heur != 0) + (heur == 2 ? std::string(", 0, 16>") : a.lin ? ", " + std::to_string(a.lin) + ">" : std::string(">"));
-      return rtc_launch("wfa_lane.hpp", name, (unsigned)grid, 64, smem, stream, &args, sizeof(args));
-    }
-    default: return -1;
+  if (shape_idx == WFA_SHAPE_RTC) {
+    struct { FastArgs a; int slot_words; int refill_min; } args = {a, slot_words, refill_min};   // (the kernel's argument list)
+    return rtc_launch("wfa_lane.hpp", lane_rtc_name(sh, full, heur, a.lin), (unsigned)grid, 64, smem, stream, &args, sizeof(args));
   }
+  return with_shape_index<affine_shape_count>(shape_idx, [&](auto i) {
+    return launch_lane_unit<decltype(i)::value>((unsigned)grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
+  });
+}
+
+// the plain score-only form
+inline int launch_lane(int shape_idx, const PenaltyShape& sh, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, const uint32_t* words,
+                       const WfaPairMeta* meta, const uint32_t* worklist, const uint32_t* nwork_dev, uint32_t nwork,
+                       int32_t* score, int32_t* status, uint32_t* fb_list, uint32_t* fb_count, int32_t* debug_counters = nullptr, int lds_pad_kb = 0,
+                       int min_pairs = 0, uint32_t* dyn_next = nullptr, uint32_t dyn_chunk = 0, int nrp = 8) {
+  FastArgs a = FastArgs();
+  a.dyn_next = dyn_chunk ? dyn_next : nullptr; a.dyn_chunk = dyn_chunk;
+  a.words = words; a.meta = meta; a.worklist = worklist; a.nwork_dev = nwork_dev; a.nwork = nwork;
+  a.score = score; a.status = status; a.fb_list = fb_list; a.fb_count = fb_count;
+  a.g = sh.g;
+  a.hist = debug_counters; a.hist_stride = 0; a.end_state = nullptr; a.work_begin = 0;
+  a.ef = a.pbf = a.pef = a.tbf = a.tef = 0; a.heur = 0; a.min_wf_len = a.max_dist_thr = a.steps_between = 0; a.max_steps = INT_MAX;
+  return launch_lane_args(shape_idx, sh, cu_count, per_cu, refill_min, max_len, stream, a, false, lds_pad_kb, min_pairs, 0, nrp);
 }
 
 #endif  // __HIPCC_RTC__

@@ -36,6 +36,7 @@
 #ifndef __HIPCC_RTC__
 #include <string>
 #include "wfa_rtc.hpp"
+#include "wfa_shapes.hpp"
 #endif
 
 namespace wfa {
@@ -504,36 +505,29 @@ wfa_seg_kernel(const FastArgs a) {
 }
 
 #ifndef __HIPCC_RTC__   // ---- host side (shape table, launch code) ----
-// Penalty shapes (index, x, o + e, e) / gcd with an instantiation of the segmented kernel.  The first is pywfa's default
-// 4/6/2 (also 2/3/1, 8/12/4, ...); the others are the usual short-read / long-read presets: 4/4/2, 4/6/1, 3/4/1,
-// 6/5/3, 5/0/3 and unit costs 1/1/1.  Each shape is compiled in its own translation unit (csrc/k_seg.hip, once per
-// index) so that the library builds in parallel; the entry points below are what the host side links against.
-#define WFA_SEG_SHAPES(F) F(0, 2, 4, 1) F(1, 2, 3, 1) F(2, 4, 7, 1) F(3, 3, 5, 1) F(4, 6, 8, 3) F(5, 5, 3, 3) F(6, 1, 2, 1)
+// Per-shape entry points: each shape of affine_shapes (wfa_shapes.hpp) is compiled in its own translation unit (csrc/k_seg.hip, once
+// per index) so that the library builds in parallel; these are what the host side links against.
+template <int I> int launch_seg_unit(int w, bool lazy, unsigned grid, hipStream_t stream, const FastArgs& a);
+template <int I> int launch_seg_full_unit(int w, unsigned grid, hipStream_t stream, const FastArgs& a);
+template <int I> int launch_seg_heur_unit(unsigned grid, hipStream_t stream, const FastArgs& a);
 
-#define WFA_SEG_DECL(i, x, oe, e)                                                                        \
-  int launch_seg_s##i(int w, bool lazy, unsigned grid, hipStream_t stream, const FastArgs& a);           \
-  int launch_seg_full_s##i(int w, unsigned grid, hipStream_t stream, const FastArgs& a);                 \
-  int launch_seg_heur_s##i(unsigned grid, hipStream_t stream, const FastArgs& a);
-WFA_SEG_SHAPES(WFA_SEG_DECL)
-#undef WFA_SEG_DECL
-
-// index of the instantiated shape of these penalties; WFA_SHAPE_RTC for a shape the run-time path takes (c.rtc: hipRTC works here,
-// csrc/wfa_rtc.cpp); -1 if none
-inline int seg_shape(const WfaDevConfig& c, int* X, int* OE, int* E) {
-  const int g = gcd_int(gcd_int(c.x, c.o1 + c.e1), c.e1);
-  *X = c.x / g; *OE = (c.o1 + c.e1) / g; *E = c.e1 / g;
-#define WFA_SEG_MATCH(i, x, oe, e) if (*X == x && *OE == oe && *E == e && !(c.rtc && rtc_force_all())) return i;
-  WFA_SEG_SHAPES(WFA_SEG_MATCH)
-#undef WFA_SEG_MATCH
-  if (c.rtc && rtc_shape_ok(*X, *OE, *E) && rtc_available()) return WFA_SHAPE_RTC;
+// *sh: the gap-affine shape of these penalties.  Returns its index in affine_shapes; WFA_SHAPE_RTC for a shape the run-time path takes
+// (c.rtc: hipRTC works here, csrc/wfa_rtc.cpp); -1 if none
+inline int seg_shape(const WfaDevConfig& c, PenaltyShape* sh) {
+  *sh = penalty_shape(c, false);
+  const int i = builtin_shape(*sh);
+  if (i >= 0 && !(c.rtc && rtc_force_all())) return i;
+  if (c.rtc && rtc_shape_ok(sh->X, sh->OE, sh->E) && rtc_available()) return WFA_SHAPE_RTC;
   return -1;
 }
 // the segmented kernel of a run-time shape: wfa_seg_kernel<X, OE, E, W, LAZY, FULL, HEUR>
-inline int launch_seg_rtc(int X, int OE, int E, int w, bool lazy, bool full, bool heur, unsigned grid, hipStream_t stream, const FastArgs& a) {
-  if (lazy && (X < 2 || OE < 2)) lazy = false;   // (the two-round extension: M must not be read one step after it is made)
-  const std::string name = "wfa::wfa_seg_kernel<" + std::to_string(X) + ", " + std::to_string(OE) + ", " + std::to_string(E) + ", " + std::to_string(w) + ", " +
-                           rtc_bool(lazy) + ", " + rtc_bool(full) + ", " + rtc_bool(heur) + (a.lin ? ", " + std::to_string(a.lin) + ">" : std::string(">"));
-  return rtc_launch("wfa_seg.hpp", name, grid, 64, 0, stream, &a, sizeof(a));
+inline std::string seg_rtc_name(const PenaltyShape& sh, int w, bool lazy, bool full, bool heur, int lin) {
+  return "wfa::wfa_seg_kernel<" + std::to_string(sh.X) + ", " + std::to_string(sh.OE) + ", " + std::to_string(sh.E) + ", " + std::to_string(w) + ", " +
+         rtc_bool(lazy) + ", " + rtc_bool(full) + ", " + rtc_bool(heur) + (lin ? ", " + std::to_string(lin) + ">" : std::string(">"));
+}
+inline int launch_seg_rtc(const PenaltyShape& sh, int w, bool lazy, bool full, bool heur, unsigned grid, hipStream_t stream, const FastArgs& a) {
+  if (lazy && (sh.X < 2 || sh.OE < 2)) lazy = false;   // (the two-round extension: M must not be read one step after it is made)
+  return rtc_launch("wfa_seg.hpp", seg_rtc_name(sh, w, lazy, full, heur, a.lin), grid, 64, 0, stream, &a, sizeof(a));
 }
 
 // which configurations the segmented kernels cover (score only, gap-affine, end-to-end or ends-free without free ends)
@@ -541,8 +535,8 @@ inline bool seg_supported(const WfaDevConfig& c, int ncomp, bool full) {
   if (full || ncomp != 3 || c.match != 0 || c.heuristic != 0 || c.wildcard >= 0) return false;
   if (c.endsfree && (c.pbf | c.pef | c.tbf | c.tef)) return false;
   if (c.max_steps != INT_MAX) return false;
-  int X, OE, E;
-  return seg_shape(c, &X, &OE, &E) >= 0;
+  PenaltyShape sh;
+  return seg_shape(c, &sh) >= 0;
 }
 
 template <int X, int OE, int E>
@@ -586,51 +580,44 @@ inline int launch_seg_full_shape(int w, unsigned grid, hipStream_t stream, const
 // issues oldest-first, so resident waves finish one after the other and a lone last wave cannot fill the VALU; with
 // short slices the dispatcher refills the CU as waves retire (C2: 5.10 -> 4.42 ms).
 inline int launch_seg_full(const WfaDevConfig& c, int cu_count, int per_cu, hipStream_t stream, FastArgs a, int w) {
-  int X, OE, E;
-  const int idx = seg_shape(c, &X, &OE, &E);
+  PenaltyShape sh;
+  const int idx = seg_shape(c, &sh);
   if (idx < 0) return -1;
-  a.g = gcd_int(gcd_int(c.x, c.o1 + c.e1), c.e1);
+  a.g = sh.g;
   long long grid = std::min<long long>((long long)cu_count * per_cu, (long long)a.nwork);
   if (grid < 1) grid = 1;
-  if (a.lin) return launch_seg_rtc(X, OE, E, (w == 32 || w == 64) ? w : 16, false, true, false, (unsigned)grid, stream, a);   // (run-time instantiation only)
-#define WFA_SEG_LAUNCH_FULL(i, x, oe, e) if (idx == i) return launch_seg_full_s##i(w, (unsigned)grid, stream, a);
-  WFA_SEG_SHAPES(WFA_SEG_LAUNCH_FULL)
-#undef WFA_SEG_LAUNCH_FULL
-  if (idx == WFA_SHAPE_RTC) return launch_seg_rtc(X, OE, E, (w == 32 || w == 64) ? w : 16, false, true, false, (unsigned)grid, stream, a);
-  return -1;
+  if (a.lin || idx == WFA_SHAPE_RTC) return launch_seg_rtc(sh, (w == 32 || w == 64) ? w : 16, false, true, false, (unsigned)grid, stream, a);   // (a.lin: run-time instantiation only)
+  return with_shape_index<affine_shape_count>(idx, [&](auto i) { return launch_seg_full_unit<decltype(i)::value>(w, (unsigned)grid, stream, a); });
 }
 
 // configurations of the general form of the 32-lane segments: what the lane kernel's general form takes (wfa_lane.hpp,
 // lane_heur_config), without a step limit (the banded kernel reports the limit's status)
 inline bool seg_heur_config(const WfaDevConfig& c, int ncomp) {
-  int X, OE, E;
+  PenaltyShape sh;
   return ncomp == 3 && c.match == 0 && c.wildcard < 0 && (c.heuristic == 0 || c.heuristic == 1 || c.heuristic == 2) && c.max_steps == INT_MAX &&
-         seg_shape(c, &X, &OE, &E) >= 0;
+         seg_shape(c, &sh) >= 0;
 }
 // a.ef / a.pbf .. / a.heur .. set by the caller (FastArgs, wfa_common.hpp); the work list is a.worklist / a.nwork_dev / a.nwork
 inline int launch_seg_heur(const WfaDevConfig& c, int cu_count, int per_cu, hipStream_t stream, FastArgs a) {
-  int X, OE, E;
-  const int idx = seg_shape(c, &X, &OE, &E);
+  PenaltyShape sh;
+  const int idx = seg_shape(c, &sh);
   if (idx < 0) return -1;
-  a.g = gcd_int(gcd_int(c.x, c.o1 + c.e1), c.e1);
+  a.g = sh.g;
   a.hist = nullptr; a.hist_stride = 0; a.end_state = nullptr; a.work_begin = 0;
   long long grid = (long long)cu_count * per_cu;
   if (!a.nwork_dev && grid > (long long)a.nwork) grid = a.nwork;
   if (grid < 1) grid = 1;
-#define WFA_SEG_LAUNCH_HEUR(i, x, oe, e) if (idx == i) return launch_seg_heur_s##i((unsigned)grid, stream, a);
-  WFA_SEG_SHAPES(WFA_SEG_LAUNCH_HEUR)
-#undef WFA_SEG_LAUNCH_HEUR
-  if (idx == WFA_SHAPE_RTC) return launch_seg_rtc(X, OE, E, 32, false, false, true, (unsigned)grid, stream, a);
-  return -1;
+  if (idx == WFA_SHAPE_RTC) return launch_seg_rtc(sh, 32, false, false, true, (unsigned)grid, stream, a);
+  return with_shape_index<affine_shape_count>(idx, [&](auto i) { return launch_seg_heur_unit<decltype(i)::value>((unsigned)grid, stream, a); });
 }
 
 // steps a w-lane segment can take before it hands its pair on (+ 1), i.e. the records a history slot needs
 // ints of a pair's history slot of the FULL form: the code records (w bytes each), the walk's event bytes, its run records
 inline void seg_full_slot(const WfaDevConfig& c, int w, int max_len, long long* code_ints, long long* event_ints, long long* slot_ints);
 inline int seg_full_records(const WfaDevConfig& c, int w) {
-  int X, OE, E;
-  if (seg_shape(c, &X, &OE, &E) < 0) return 0;
-  return 2 * (OE - E) + E * (w + 1) + 3;
+  PenaltyShape sh;
+  if (seg_shape(c, &sh) < 0) return 0;
+  return 2 * (sh.OE - sh.E) + sh.E * (w + 1) + 3;
 }
 
 inline void seg_full_slot(const WfaDevConfig& c, int w, int max_len, long long* code_ints, long long* event_ints, long long* slot_ints) {
@@ -647,21 +634,18 @@ inline int launch_seg(const WfaDevConfig& c, int cu_count, int per_cu, hipStream
   FastArgs a = FastArgs();   // (value-initialised: lin = 0 and every field no launch path sets)
   a.words = words; a.meta = meta; a.worklist = worklist; a.nwork_dev = nwork_dev; a.nwork = nwork;
   a.score = score; a.status = status; a.fb_list = fb_list; a.fb_count = fb_count;
-  a.g = gcd_int(gcd_int(c.x, c.o1 + c.e1), c.e1);
   a.hist = nullptr; a.hist_stride = 0; a.end_state = nullptr; a.work_begin = 0;
-  int X, OE, E;
-  const int idx = seg_shape(c, &X, &OE, &E);
+  PenaltyShape sh;
+  const int idx = seg_shape(c, &sh);
   if (idx < 0) return -1;
+  a.g = sh.g;
   long long grid = (long long)cu_count * per_cu;
   if (!nwork_dev && grid > (long long)nwork) grid = nwork;
   if (grid < 1) grid = 1;
   const bool lazy = variant >= 6;
   const int w = (variant == 3 || variant == 7) ? 8 : (variant == 4 || variant == 8) ? 32 : (variant == 5 || variant == 9) ? 64 : 16;
-#define WFA_SEG_LAUNCH(i, x, oe, e) if (idx == i) return launch_seg_s##i(w, lazy, (unsigned)grid, stream, a);
-  WFA_SEG_SHAPES(WFA_SEG_LAUNCH)
-#undef WFA_SEG_LAUNCH
-  if (idx == WFA_SHAPE_RTC) return launch_seg_rtc(X, OE, E, w, lazy, false, false, (unsigned)grid, stream, a);
-  return -1;
+  if (idx == WFA_SHAPE_RTC) return launch_seg_rtc(sh, w, lazy, false, false, (unsigned)grid, stream, a);
+  return with_shape_index<affine_shape_count>(idx, [&](auto i) { return launch_seg_unit<decltype(i)::value>(w, lazy, (unsigned)grid, stream, a); });
 }
 
 #endif  // __HIPCC_RTC__

@@ -16,7 +16,7 @@ from pywfa_amd import datagen
 pytestmark = pytest.mark.gpu
 
 # (mismatch, gap_opening, gap_extension) -> the lane kernel's shape (X, OE, E) in units of g: the seven built-in shapes in the
-# order of WFA_SEG_SHAPES, then one that is instantiated at run time
+# order of affine_shapes (csrc/wfa_shapes.hpp), then one that is instantiated at run time
 SHAPES = {
     "s0_2_4_1": (4, 6, 2),
     "s1_2_3_1": (2, 2, 1),
