@@ -114,6 +114,11 @@ typedef unsigned short lane_u2 __attribute__((ext_vector_type(2)));
 #else
 #define WFA_LANE_MARK(name)
 #endif
+// The plain score-only form skips the extension probes of a register that is dead in all 64 lanes (1) or probes unconditionally (0), by
+// the packed registers of the form (probe blocks per wave-step on C2)
+#ifndef WFA_LANE_PROBE_LIVE_TEST
+#define WFA_LANE_PROBE_LIVE_TEST(nrp) 1
+#endif
 #define WFA_LANE_COUNT(i) do { if (WFA_LANE_DEBUG_COUNTERS && !FULL && a.hist) { if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.hist) + (i), 1ull); } } while (0)
 
 __device__ __forceinline__ uint32_t lane_ffbl(uint32_t x) {  // index of the lowest set bit, ~0u for 0
@@ -136,6 +141,20 @@ __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) {
 __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) {
   lane_s2 r = __builtin_bit_cast(lane_s2, a) + __builtin_bit_cast(lane_s2, b);
   return __builtin_bit_cast(uint32_t, r);
+}
+// The extension probes of the plain score-only form address the packed words by DOUBLED base coordinates that include the LDS address of
+// the word array (8 x the byte address: a byte holds four bases): c2 = 2 (base coordinate) + 8 (address of lds[]).  v_alignbit reads only
+// the low five bits of its shift operand, so c2 itself is the funnel-shift count (2 bits per base, 32 per word), and the byte address of
+// the word that holds the base is (c2 >> 3) & ~3: no separate shift count and no base address to add.
+typedef const __attribute__((address_space(3))) uint32_t* lane_ldsw;
+__device__ __forceinline__ lane_ldsw lane_word(uint32_t c2) { return (lane_ldsw)(__UINTPTR_TYPE__)((c2 >> 3) & ~3u); }
+// 2 x (half Q of a packed register, unsigned) + base: the doubled coordinate of an offset straight from its half, one instruction
+template <int Q>
+__device__ __forceinline__ uint32_t lane_half2_plus(uint32_t packed, uint32_t base) {
+  uint32_t r;
+  if (Q) asm("v_mad_u32_u16 %0, %1, 2, %2 op_sel:[1,0,0,0]" : "=v"(r) : "v"(packed), "v"(base));
+  else asm("v_mad_u32_u16 %0, %1, 2, %2" : "=v"(r) : "v"(packed), "v"(base));
+  return r;
 }
 // per half: nm > lim ? NULL : nm   (only M is clamped, R/wavefront_compute_affine.c:80-84; negative values are dead anyway).
 // Built-in shapes: three instructions per register — packed difference, its sign spread over each half, one bit-select.  Written in C
@@ -376,6 +395,9 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
     for (int d = 0; d < E; ++d) { Ih[d][r] = WFA_LANE_NULL2; Dh[d][r] = WFA_LANE_NULL2; }
   }
   int kb0 = pbase, tb = pbase;   // pattern coordinate of offset x on slot j is x + kb0 - j; text coordinate is x + tb
+  // ENTRY: the same two as doubled coordinates with the address of lds[] folded in (lane_word), for the extension probes
+  const uint32_t lds8 = 8u * (uint32_t)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) uint32_t*)lds;
+  uint32_t kbd = 2u * (uint32_t)pbase + lds8, tbd = kbd;
   int jt = 0;                    // slot of the end diagonal tlen - plen
   uint32_t tend = 0xffffu;       // tlen: the offset that ends the alignment on slot jt (0xffff: no pair)
   int s0 = 0, deadline = NEVER;
@@ -482,6 +504,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
         mypid = n_pid; s0 = gstep - K;                // (ENTRY: the pair enters the loop at its score K)
         if (FULL) myslot = next_i + rank;   // (slot = index of the work item in this launch)
         kb0 = pbase - k0; tb = pbase + nwp * 16;
+        if constexpr (ENTRY) { kbd = 2u * (uint32_t)kb0 + lds8; tbd = 2u * (uint32_t)tb + lds8; }
         jt = bad ? 0 : ak - k0;
         tend = bad ? 0xffffu : (uint32_t)tl;
         // Bmin / g in units of g (o / g = OE - E, e / g = E), see wfa_seg.hpp
@@ -645,6 +668,117 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
     // run {slot, offset, bases left}; all lanes' pending runs are then continued together, 32 bases per round, so the
     // longest run of the 64 pairs is waited for once per step and not once per slot.  (A second run of the same
     // lane in the same step — rare — is finished on the spot.)
+    if constexpr (ENTRY) {
+      // The plain score-only form: the same probes with less bookkeeping around the comparison.
+      //  * addresses and shift counts from doubled coordinates (lane_word): 2 x + kbd - 2 j and 2 x + tbd, each one v_mad_u32_u16 from
+      //    the packed half;
+      //  * what is left of a slot's run, packed: lim - cur where the cell lives, 0 where it is dead (the sign of cur spread over its
+      //    half); a dead cell then advances by 0, so the probe ADDS the run lengths to cur (one v_pk_add) and needs no unpacking of
+      //    cur, no select of the old value for dead cells and no repacking.  The same makes the probe of a register that is dead in
+      //    all 64 lanes a no-op: every `left` is 0, every m is 0, nothing is parked and cur + 0 is written back; the words it reads
+      //    are those at offset 0 of the lane's own slot;
+      //  * the run: f = ffbl >> 1 is 0 .. 15 or 0x7fffffff (all 16 equal), so with t = min(f, left): m = min(t, 16), and the run goes
+      //    on (all 16 equal and more than 16 left) exactly if t > 16;
+      //  * the parked run is remembered as its register (the new cur and lim of the register and its index: one select each per
+      //    register, the half in a lane mask) and unpacked once behind the probes.
+      // LIVE_TEST: a register dead in all lanes is skipped (the test: some packed `left` is not 0).  Measured on C2 (2 M pairs, the
+      // counting build): DESIGN §3.1.
+      constexpr bool LIVE_TEST = WFA_LANE_PROBE_LIVE_TEST(NRP);
+      // (lane masks as wave-wide scalars: the park rule is scalar arithmetic, a lane's bit is read back where a select needs it)
+      unsigned long long free_m = ~0ull, hot_qm = 0ull;   // lanes without a parked run yet; lanes whose parked run is in the high half of its register
+      int hot_r = -1;                         // register of the parked run
+      uint32_t hot_c = 0u, hot_l = 0u;        // that register's cur (behind its first probes) and lim
+      // one 32-base round of a run that goes on, in doubled units: the coordinates advance by the run, `left2` shrinks by it
+      auto run32 = [&](uint32_t& v2, uint32_t& h2, uint32_t& left2) -> bool {
+        const lane_ldsw pp = lane_word(v2), tp = lane_word(h2);
+        const uint32_t p0 = pp[0], p1 = pp[1], p2 = pp[2], t0 = tp[0], t1 = tp[1], t2 = tp[2];
+        const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, v2) ^ __builtin_amdgcn_alignbit(t1, t0, h2);
+        const uint32_t xh = __builtin_amdgcn_alignbit(p2, p1, v2) ^ __builtin_amdgcn_alignbit(t2, t1, h2);
+        const uint32_t fb2 = min(lane_ffbl(xl), lane_ffbl(xh) | 32u) & ~1u;   // 2 x equal bases: 0 .. 62, or 0xfffffffe: all 32
+        const uint32_t t = min(fb2, left2);
+        const uint32_t m2 = min(t, 64u);
+        v2 += m2; h2 += m2; left2 -= m2;
+        return t > 64u;                       // all 32 equal and more than 32 left
+      };
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const uint32_t dead = __builtin_bit_cast(uint32_t, __builtin_bit_cast(lane_s2, cur[r]) >> (short)15);   // 0xffff per dead half
+        const uint32_t xc = cur[r] & ~dead;                       // max(offset, 0)
+        const uint32_t lf = pk_sub(lim[r], cur[r]) & ~dead;       // longest possible run; in-bounds cells have 0 <= off <= lim
+        if (!LIVE_TEST || __builtin_amdgcn_ballot_w64(lf != 0u)) {
+          WFA_LANE_MARK("probe_begin");
+          WFA_LANE_COUNT(4);
+          uint32_t v2[2], h2[2], m[2];
+          bool more[2];
+          v2[0] = lane_half2_plus<0>(xc, kbd - (uint32_t)(4 * r)); h2[0] = lane_half2_plus<0>(xc, tbd);
+          v2[1] = lane_half2_plus<1>(xc, kbd - (uint32_t)(4 * r + 2)); h2[1] = lane_half2_plus<1>(xc, tbd);
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const lane_ldsw pp = lane_word(v2[q]), tp = lane_word(h2[q]);
+            const uint32_t p0 = pp[0], p1 = pp[1], t0 = tp[0], t1 = tp[1];
+            const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, v2[q]) ^ __builtin_amdgcn_alignbit(t1, t0, h2[q]);
+            const uint32_t t = min(lane_ffbl(xl) >> 1, q ? (lf >> 16) : (lf & 0xffffu));   // (ffbl of 0 is ~0: all 16 equal)
+            m[q] = min(t, 16u);
+            more[q] = t > 16u;
+          }
+          // the first run that goes on is parked; a lane that already has one finishes this one now
+          const unsigned long long more0 = __builtin_amdgcn_ballot_w64(more[0]), more1 = __builtin_amdgcn_ballot_w64(more[1]);
+          const unsigned long long park0 = more0 & free_m, park1 = more1 & free_m & ~more0, parks_m = park0 | park1;
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const unsigned long long now_m = q ? (more1 & ~park1) : (more0 & ~park0);
+            if (now_m) {
+              const bool now = __builtin_amdgcn_inverse_ballot_w64(now_m);
+              WFA_LANE_MARK("nowfix_begin");
+              WFA_LANE_COUNT(7);
+              // (from the cell itself once more, 32 bases per round; other lanes advance by 0)
+              uint32_t vv = v2[q], hh = h2[q];
+              uint32_t l2 = now ? 2u * (q ? (lf >> 16) : (lf & 0xffffu)) : 0u;
+              bool mo;
+              do {
+                WFA_LANE_MARK("now_begin");
+                WFA_LANE_COUNT(5);
+                mo = run32(vv, hh, l2);
+                WFA_LANE_MARK("now_end");
+              } while (__builtin_amdgcn_ballot_w64(mo));
+              m[q] = now ? (vv - v2[q]) >> 1 : m[q];
+              WFA_LANE_MARK("nowfix_end");
+            }
+          }
+          cur[r] = pk_add(cur[r], m[0] | (m[1] << 16));
+          const bool parks = __builtin_amdgcn_inverse_ballot_w64(parks_m);
+          hot_c = parks ? cur[r] : hot_c; hot_l = parks ? lim[r] : hot_l; hot_r = parks ? r : hot_r;
+          hot_qm |= park1;
+          free_m &= ~parks_m;
+          WFA_LANE_MARK("probe_end");
+        }
+      }
+      if (~free_m) {
+        // the parked runs, all lanes together
+        const bool hot_q = __builtin_amdgcn_inverse_ballot_w64(hot_qm);
+        WFA_LANE_COUNT(2);
+        WFA_LANE_MARK("parkfix_begin");
+        // (a live cell: 0 <= x0 <= l0.  Lanes without a parked run: hot_c = hot_l = 0, hot_r = -1 — they read along at offset 0, two
+        // slots below slot 0, and advance by 0)
+        const uint32_t x0 = hot_q ? (hot_c >> 16) : (hot_c & 0xffffu), l0 = hot_q ? (hot_l >> 16) : (hot_l & 0xffffu);
+        uint32_t l2 = 2u * (l0 - x0);
+        uint32_t vv = 2u * x0 + kbd - (uint32_t)(4 * hot_r + (hot_q ? 2 : 0)), hh = 2u * x0 + tbd;
+        const uint32_t v0 = vv;
+        bool mo;
+        do {
+          WFA_LANE_MARK("parked_begin");
+          mo = run32(vv, hh, l2);
+          WFA_LANE_COUNT(3);
+          WFA_LANE_MARK("parked_end");
+        } while (__builtin_amdgcn_ballot_w64(mo));
+        // the run's length onto its half register (lanes without a parked run: hot_r = -1 matches no register)
+        const uint32_t adv = (vv - v0) >> 1;
+        const uint32_t inc = hot_q ? (adv << 16) : adv;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) cur[r] = pk_add(cur[r], (hot_r == r) ? inc : 0u);
+        WFA_LANE_MARK("parkfix_end");
+      }
+    } else {
     int hot_j = -1, hot_x = 0, hot_left = 0;
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
@@ -748,9 +882,11 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
       }
       WFA_LANE_MARK("parkfix_end");
     }
+    }   // (!ENTRY)
 
     // =================== termination / hand-over ===================
     {
+      WFA_LANE_MARK("term_begin");
       // R/wavefront_termination.c:37-61: the cell of the end diagonal (slot jt) has reached offset tlen
       uint32_t endv = 0;
       bool hit = false;
@@ -807,6 +943,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
         WFA_LANE_MARK("bd_end");
         if (idle == ~0ull && slice_done() && exhausted) { rej_flush(); break; }   // (a flush behind the loop costs 40 registers)
       }
+      WFA_LANE_MARK("term_end");
     }
 
     // =================== wf-adaptive cut-off (R/wavefront_heuristic.c:257-293, dispatcher :509-567) ===================
@@ -877,6 +1014,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
 
     // =================== compute-next (R/wavefront_compute_affine.c:44-86) ===================
     {
+      WFA_LANE_MARK("next_begin");
       uint32_t gi[NR], gd[NR];
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
@@ -940,6 +1078,7 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
         // a cell of an outermost slot is alive (an offset or a gap value >= 0): the next steps could reach beyond the band
         edge_live = (((nm[0] & ni[0] & nd[0]) & 0x00008000u) == 0u) || (((nm[NR - 1] & ni[NR - 1] & nd[NR - 1]) & 0x80000000u) == 0u);
       }
+      WFA_LANE_MARK("next_end");
     }
     ++gstep;
   }

@@ -2,7 +2,7 @@
 """Dynamic instruction mix of wfa_lane_kernel<2,4,1,false,false> (the C2 hot loop): which share of its vector instructions runs at
 the full issue rate (development aid).
 
-    python tools/lane_mix.py [--width 16|8 | --kernel SYMBOL] [--static] [counts-file]
+    python tools/lane_mix.py [--width 16|8 | --kernel SYMBOL] [--static] [--asm FILE] [counts-file]
 
    --width 8 counts the 8-diagonal form (NRP = 4, the first stage of the score-only cascade), --kernel any instantiation of k_lane.hip's
    shape 0 by its mangled name; --static prints the static counts per region and instruction and stops (no counts file needed).
@@ -11,7 +11,8 @@ the full issue rate (development aid).
    the entry chains of a 64-pair window and a round of them (`entry` / `entryround`: inside `refill`, at its head, once per
    window; the part of the refill that reads the cells and writes the state of step K down is priced under `refill`; shapes with
    more than two cells below K run the chain in every refill that takes a pair instead), the first-probe block of a register, a round of a second run, the
-   parked-run loop and its write-back, the hand-over block),
+   parked-run loop and its write-back, termination (`term`, with the hand-over block `bd` inside it) and compute-next (`next`), so that
+   `step` is only what is left of the loop: the refill test and the parked-run test),
    and the vector instructions of every region are counted by class: "full rate" = v_add_u32 / v_and / v_or / v_xor (0.91-0.93 ns
    per wave64 instruction and SIMD, profiles/r02_issue_rate.txt), everything else "half rate" (min / max / alignbit / cndmask /
    shifts / sub / add3 / pk / dpp / ffbl / cmp / mov-with-dpp: 1.64-1.83 ns); v_mov_b32 and v_readlane etc. are listed apart.
@@ -51,12 +52,16 @@ def compile_marks():
     subprocess.run(cmd, check=True, capture_output=True)
 
 
-def static_counts():
+def static_counts(asm=None):
     regions = collections.defaultdict(lambda: collections.Counter())
     copies = collections.Counter()
     inside, stack, loop_seen = False, [], False
-    first_loop_label = None
-    for line in open(ASM):
+    # what lies outside every begin / end pair belongs to the section of the loop body it stands in, in layout order (the scheduler moves
+    # plain arithmetic across the marks: the liveness test and the unpacking in front of a probe block, the write-back behind it):
+    # behind the refill the probes, behind the parked runs termination, behind termination compute-next
+    section = {"refill": "probe", "parkfix": "term", "term": "next"}
+    outside = "step"
+    for line in open(asm or ASM):
         t = line.strip()
         if t.startswith(KERNEL + ":"):
             inside = True
@@ -70,16 +75,22 @@ def static_counts():
             name, kind = m.group(1), m.group(2)
             if name == "looptop":
                 loop_seen = True
+                outside = "step"
                 continue
             if kind == "begin":
                 stack.append(name); copies[name] += 1
-            elif stack and stack[-1] == name:
-                stack.pop()
+            elif name in stack:
+                # (a loop's blocks may be laid out rotated, its end mark in front of its begin mark: an end closes whatever was opened
+                # inside its region too, and an end without a begin closes nothing)
+                while stack.pop() != name:
+                    pass
+                if not stack and name in section:
+                    outside = section[name]
             continue
         m = re.match(r"(v_[a-z0-9_]+)\s", t)
         if not m:
             continue
-        region = stack[-1] if stack else ("step" if loop_seen else "prologue")
+        region = stack[-1] if stack else (outside if loop_seen else "prologue")
         regions[region][classify(m.group(1))] += 1
         regions[region]["ops:" + m.group(1)] += 1
     return regions, copies
@@ -92,15 +103,30 @@ def main():
     ap.add_argument("--width", type=int, choices=sorted(KERNELS), default=16, help="diagonals of the band (the kernel's NRP x 2)")
     ap.add_argument("--kernel", help="mangled kernel symbol (overrides --width)")
     ap.add_argument("--static", action="store_true", help="print the static counts per region and stop")
+    ap.add_argument("--asm", help="count this assembly file (a marks build made earlier, e.g. of another commit) instead of compiling")
     ap.add_argument("counts_file", nargs="?")
     args = ap.parse_args()
     KERNEL = args.kernel or KERNELS[args.width]
-    compile_marks()
-    regions, copies = static_counts()
+    if not args.asm:
+        compile_marks()
+    regions, copies = static_counts(args.asm)
     if args.static:
         for name, cnt in sorted(regions.items()):
             n_copies = max(copies.get(name, 1), 1)
             print(f"{name} ({n_copies} copies): " + ", ".join(f"{k[4:]} {v}" for k, v in sorted(cnt.items()) if k.startswith("ops:")))
+        # the first-probe block of one packed register (two slots): vector instructions of all copies and per copy, by instruction
+        # (the _e32 / _e64 / _sdwa encodings of an instruction together)
+        probe, n = regions.get("probe", {}), max(copies.get("probe", 1), 1)
+        ops = collections.Counter()
+        for k, v in probe.items():
+            if k.startswith("ops:"):
+                ops[re.sub(r"_(e32|e64|sdwa|dpp)$", "", k[4:])] += v
+        total = sum(ops.values())
+        print(f"\nprobe blocks: {n}; VALU in all probe blocks: {total}; per block: {total / n:.1f} "
+              f"(full rate {probe.get('full', 0) / n:.1f}, half rate {probe.get('half', 0) / n:.1f}, mov {probe.get('mov', 0) / n:.1f})")
+        print("| instruction | all blocks | per block |\n|---|---|---|")
+        for k, v in sorted(ops.items(), key=lambda kv: (-kv[1], kv[0])):
+            print(f"| {k} | {v} | {v / n:.2f} |")
         return
     TAG = os.environ.get("WFA_PROFILE_TAG", "r05")
     counts_file = args.counts_file or os.path.join(ROOT, "profiles", TAG + "_lane_regions.txt")
@@ -109,7 +135,7 @@ def main():
     steps, refills, parked, prounds, probes, now_rounds, bd, now_runs, entries, erounds = [int(x or 0) for x in m.groups()]
     # executions of ONE copy of each region (the unrolled copies of a region are equal: their static counts are averaged)
     execs = {"step": steps, "refill": refills, "probe": probes, "nowfix": now_runs, "now": now_rounds, "parkfix": parked, "parked": prounds, "bd": bd,
-             "entry": entries, "entryround": erounds}
+             "entry": entries, "entryround": erounds, "term": steps, "next": steps}
     dyn = collections.Counter()
     per_region = {}
     for name, cnt in regions.items():
