@@ -543,7 +543,9 @@ int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uint8_t* patte
  * Sites come out in ascending (j, pos), always: the order does not depend on scheduling, two calls give identical rows.
  *
  * A site says that, and how often, reads insert in front of a base; WHAT they insert is the allele row of "insertions" below, from a
- * pileup made to track them.  Out of scope: quality values, strand bias, genotypes and multi-base events.
+ * pileup made to track them; per-strand counts and a diploid genotype per site: "strands and genotypes" below.  Out of scope: quality
+ * values and multi-base events; more than one alternate allele per site, ploidy other than 2, a Fisher or other strand statistic (the
+ * four counts are returned; the test is the caller's).
  *
  * The pileup keeps no reference letters and outlives its set, so both device calls take the set: the one the pileup was made over, or
  * one made again from the same sequences.  wfa_hip_pileup_calls writes out[0 .. len) for the rows [start, start + len) of sequence
@@ -621,7 +623,9 @@ int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, i
  * although the rule needs no letters, so the call shape matches), with min_permille in 0..1000; a pileup that does not track ("... was
  * not made to track insertions"); bases_cap < 0; a NULL count or bases_count; NULL bases with bases_cap > 0.
  *
- * Out of scope: quality values, strands, genotypes, more than one allele per row.  Reads that place the same inserted bases at
+ * Out of scope: quality values and multi-base events; more than one alternate allele per site (here: per row), ploidy other than 2, a
+ * Fisher or other strand statistic (the four counts are returned; the test is the caller's).  The log keeps no strand per record
+ * ("strands and genotypes" below counts strands per base).  Reads that place the same inserted bases at
  * different rows of a repeat are different records at different rows: left-align the batch first ("left alignment" below), which puts
  * every gap at the left end of its repeat as far as the read's own window and its own mismatches allow.
  */
@@ -650,6 +654,83 @@ int wfa_hip_insertions_host(const int32_t* counts, int64_t len, int32_t seq, int
                             int64_t nrec, const int64_t* rec_row, const int32_t* rec_n, const int64_t* rec_off, const uint8_t* cols,
                             int64_t ncols, int64_t cap, int64_t* count, int32_t* rows, int64_t bases_cap, int64_t* bases_count,
                             uint8_t* bases);
+
+/* ---- strands and genotypes: per-strand counts, and a diploid genotype per variant site ---------------------- */
+
+/*
+ * A site seen on one strand only is the classic artefact every caller filters, and "0/1 or 1/1, and how sure" is the first thing a
+ * caller asks of a site.  Both are integer reductions of data already resident.  Strand tracking is opt-in: a pileup that does not ask
+ * for it behaves, allocates and launches exactly as before.  Integers only, 64-bit products.
+ *
+ * STRANDS.  wfa_hip_pileup_track_strands turns tracking on or off.  Allowed only while the pileup is empty: fresh, or just after
+ * wfa_hip_pileup_clear; otherwise WFA_HIP_EINVAL with a message.  Turning it on allocates a second zeroed table, the FORWARD TABLE: the
+ * same 8 planes, plane stride and layout (csrc/wfa_pileup.hpp), 32 MORE BYTES PER TEXT BASE; a failed allocation returns
+ * WFA_HIP_EDEVICE, the message names the byte count, and the pileup is unchanged and not tracking.  Turning it off frees that table.
+ * wfa_hip_pileup_clear keeps the setting and zeroes both tables.  Strand tracking and insertion tracking are independent; both may be
+ * on, and the insertion log is the same either way (no strand per record).
+ *
+ * wfa_hip_pileup_add_strands does exactly what wfa_hip_pileup_add does to the table; in addition a pair with reverse[q] == 0 makes the
+ * same adds to the same rows and columns of the forward table (reverse NULL: every pair is forward).  reverse is the strand array given
+ * to wfa_hip_batch_create_windows; the letters counted are the batch's either way, i.e. on the text's strand.  Reverse counts are
+ * total - forward and are never stored.  10 bytes per pair uploaded.  Its refusals are those of wfa_hip_pileup_add, and a pileup that
+ * does not track strands.  wfa_hip_pileup_add on a pileup that tracks strands is refused, the message names this call.  Kernel:
+ * k_pileup.hip, the table kernel (and its insertion-tracking form) compiled with a STRANDS flag: the strand is uniform over the wave
+ * that serves a pair, a forward pair issues each atomicAdd twice.
+ *
+ * wfa_hip_pileup_read_strand is wfa_hip_pileup_read for one strand (0 forward, 1 reverse = total - forward, subtracted on the host):
+ * the same checks, plus WFA_HIP_EINVAL for a strand outside {0, 1} and for a pileup that does not track strands.
+ *
+ * GENOTYPED SITES.  For base g take c0..c7, r, depth, alt, A = c[alt], snv and ins exactly as SITE ("calls and sites") defines them
+ * and, on a tracking pileup, f0..f7 from the forward table and depth_fwd = f0 + ... + f5.  Parameters: min_depth >= 1, min_permille in
+ * 1..1000, err_q in 1..60, min_alt_strand >= 0 (a value above 0 needs a tracking pileup).
+ *   snv' = snv && f[alt] >= min_alt_strand && A - f[alt] >= min_alt_strand
+ *   ins' = ins && f6 >= min_alt_strand && c6 - f6 >= min_alt_strand
+ * (min_alt_strand == 0: snv' = snv, ins' = ins.)  A base of depth >= min_depth is reported iff snv' || ins'.
+ *
+ * GENOTYPE of an event with R reference reads and A alternate reads:
+ *   L0 = err_q * A  (genotype 0/0)      L1 = 3 * (R + A)  (0/1)      L2 = err_q * R  (1/1)
+ *   gt = the index of the smallest L, the smaller index on a tie;  gq = min(99, second smallest L - smallest L)
+ * The 3 is 10 log10 2 rounded: under 0/1 every read had an even chance of showing either allele.  err_q is the phred-scaled cost of a
+ * read that contradicts the genotype.  gq is a documented confidence, NOT a calibrated likelihood, as mapq is in "placement": no base
+ * qualities, no mapping qualities, no prior enter it.  SNV event: R = c[r], A = c[alt].  Insertion event: A = c6,
+ * R = max(0, depth - c6).
+ *
+ * Row, WFA_HIP_GENOTYPE_COLS int32:
+ *   0..7    the site row: j, pos, ref, alt, depth, ref_count, alt_count, ins_count — with snv' in place of snv
+ *   8..11   gt, gq (-1, -1 when !snv'), ins_gt, ins_gq (-1, -1 when !ins')
+ *   12..15  depth_fwd (its low 32 bits), ref_fwd = f[r], alt_fwd (f[alt]; 0 when !snv'), ins_fwd = f6; all four -1 on a pileup that
+ *           does not track strands
+ * Rows come out in ascending (j, pos), always; two calls give identical bytes.  With min_alt_strand == 0, columns 0..7 of the rows are
+ * byte for byte the rows of wfa_hip_pileup_sites with the same min_depth and min_permille.
+ *
+ * wfa_hip_pileup_genotypes follows the conventions of wfa_hip_pileup_sites: seq = -1 takes every sequence (start = 0, len = -1);
+ * *count is always the full number; the first min(*count, cap) rows are written (cap x 16 int32; rows behind them are not touched);
+ * cap = 0 with rows = NULL is the counting call.  Kernels: csrc/wfa_calls.hpp, k_calls.hip — the sites' chunk count / scan / scatter
+ * (WFA_HIP_CALLS_CHUNK applies), no atomics; the forward planes are read only at bases that pass SITE; a row is four 16-byte stores.
+ * WFA_HIP_EINVAL, nothing launched, nothing written (wfa_hip_last_error names the values): whatever wfa_hip_pileup_sites refuses;
+ * err_q outside 1..60; min_alt_strand < 0; min_alt_strand > 0 on a pileup that does not track strands.
+ *
+ * Out of scope: quality values and multi-base events; more than one alternate allele per site, ploidy other than 2, a Fisher or other
+ * strand statistic (the four counts are returned; the test is the caller's).
+ */
+#define WFA_HIP_GENOTYPE_COLS 16  /* the 8 of a site, gt, gq, ins_gt, ins_gq, depth_fwd, ref_fwd, alt_fwd, ins_fwd */
+int wfa_hip_pileup_track_strands(wfa_hip_pileup_t* pileup, int on);
+int wfa_hip_pileup_add_strands(wfa_hip_pileup_t* pileup, wfa_hip_batch_t* batch, const int32_t* j, const int32_t* t_start /* nullable: 0 */,
+                               const uint8_t* keep /* nullable: all */, const uint8_t* reverse /* nullable: all forward */);
+int wfa_hip_pileup_read_strand(wfa_hip_pileup_t* pileup, int32_t seq, int64_t start, int64_t len, int strand /* 0 forward, 1 reverse */,
+                               int32_t* counts /* len x 8 */);
+int wfa_hip_pileup_genotypes(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                             int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap, int64_t* count,
+                             int32_t* rows /* cap x 16, nullable */);
+
+/* Host only, needs no GPU: the rule of the genotyped sites on `len` rows as wfa_hip_pileup_read returns them (counts: len x 8) and,
+ * for a tracking pileup, as wfa_hip_pileup_read_strand returns them for strand 0 (counts_fwd: len x 8; NULL: not tracking, columns
+ * 12..15 are -1), over the reference bytes ref[0 .. len).  Rows are numbered j = seq, pos = start + row; count, cap and rows as
+ * wfa_hip_sites_host.  Refused (WFA_HIP_EINVAL, nothing written): what wfa_hip_sites_host refuses, err_q outside 1..60,
+ * min_alt_strand < 0, min_alt_strand > 0 with counts_fwd NULL. */
+int wfa_hip_genotypes_host(const int32_t* counts, const int32_t* counts_fwd /* nullable */, const uint8_t* ref, int64_t len, int32_t seq,
+                           int64_t start, int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
+                           int64_t* count, int32_t* rows);
 
 /* ---- left alignment: gaps at the left end of their repeat, where VCF puts them ----------------------------- */
 

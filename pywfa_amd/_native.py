@@ -140,6 +140,11 @@ SIGNATURES = {
     "wfa_hip_pileup_insertions": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i64, _i64p, _vp, _i64, _i64p, _vp]),
     "wfa_hip_ops_insertions": (_CTYPES, [_vp, _i64, _vp, _i32, _i32, _i64, _i64p, _vp, _i64, _i64p, _vp]),
     "wfa_hip_insertions_host": (_CTYPES, [_vp, _i64, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64p, _vp, _i64, _i64p, _vp]),
+    "wfa_hip_pileup_track_strands": (_CTYPES, [_vp, _int]),
+    "wfa_hip_pileup_add_strands": (_CTYPES, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "wfa_hip_pileup_read_strand": (_CTYPES, [_vp, _i32, _i64, _i64, _int, _vp]),
+    "wfa_hip_pileup_genotypes": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64p, _vp]),
+    "wfa_hip_genotypes_host": (_CTYPES, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _i64, _i64p, _vp]),
     "wfa_hip_batch_left_align": (_CTYPES, [_vp, _vp]),
     "wfa_hip_ops_left_align": (_CTYPES, [_vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "wfa_hip_placer_create": (_vp, [_vp, _i64]),
@@ -171,6 +176,8 @@ SITE_COLUMNS = ("j", "pos", "ref", "alt", "depth", "ref_count", "alt_count", "in
 INSERTION_COLS = 8
 INSERTION_COLUMNS = ("j", "pos", "depth", "ins_count", "allele_count", "allele_len", "alleles", "overflow")
 INS_MAX_READS = 4096   # the default of WFA_HIP_INS_MAX_READS
+GENOTYPE_COLS = 16
+GENOTYPE_COLUMNS = SITE_COLUMNS + ("gt", "gq", "ins_gt", "ins_gq", "depth_fwd", "ref_fwd", "alt_fwd", "ins_fwd")
 PLACE_COLS = 8
 PLACE_COLUMNS = ("hit", "score", "second", "mapq", "hits", "ties", "text_start", "text_end")
 PLACE_NOT_ELIGIBLE, PLACE_OTHER_LOCUS, PLACE_SAME_LOCUS, PLACE_PRIMARY = 0, 1, 2, 3   # the flag byte of a hit
@@ -640,6 +647,33 @@ def sites_host(counts, ref, seq=0, start=0, min_depth=1, min_permille=500, cap=N
     return count.value, rows[:min(count.value, rows.shape[0])]
 
 
+def genotypes_host(counts, ref, counts_fwd=None, seq=0, start=0, min_depth=1, min_permille=500, err_q=20, min_alt_strand=0, cap=None):
+    """wfa_hip_genotypes_host (host only): ``(count, rows)`` of the genotyped sites among the rows ``counts`` over the reference bytes
+    ``ref``; ``counts_fwd``: the forward rows of a pileup that tracks strands (``Pileup.read(strand=0)``), None: not tracking (the
+    last four columns are -1).  Rows: int32 of shape (min(count, cap), 16), every one when ``cap`` is None (a counting call first)."""
+    counts, ref = _calls_rows(counts, ref)
+    if counts_fwd is not None:
+        counts_fwd = np.ascontiguousarray(counts_fwd, dtype=np.int32)
+        if counts_fwd.shape != counts.shape:
+            raise ValueError("counts_fwd: int32 of the shape of counts")
+        if not counts_fwd.size:
+            counts_fwd = np.zeros((1, PILEUP_COLS), np.int32)   # (tracking is told from a non-NULL pointer, even over no rows)
+    n = counts.shape[0]
+    args = (_ptr(counts) if counts.size else None, None if counts_fwd is None else _ptr(counts_fwd),
+            _ptr(ref) if ref.size else None, n, int(seq), int(start), int(min_depth), int(min_permille), int(err_q), int(min_alt_strand))
+    what = (f"wfa_hip_genotypes_host: invalid arguments (min_depth = {min_depth}, min_permille = {min_permille}, err_q = {err_q}, "
+            f"min_alt_strand = {min_alt_strand}, cap = {cap})")
+    count = ctypes.c_int64(0)
+    if cap is None:
+        if lib().wfa_hip_genotypes_host(*args, 0, ctypes.byref(count), None) != OK:
+            raise ValueError(what)
+        cap = count.value
+    rows = np.zeros((max(int(cap), 0), GENOTYPE_COLS), np.int32)
+    if lib().wfa_hip_genotypes_host(*args, int(cap), ctypes.byref(count), _ptr(rows) if rows.size else None) != OK:
+        raise ValueError(what)
+    return count.value, rows[:min(count.value, rows.shape[0])]
+
+
 def _hit_arrays(i, j, reverse, score, status, text_start, text_end):
     """The arrays of a hit list as the C entries take them: int32 each, ``reverse`` uint8 0 / 1 or None; one length."""
     a = {k: np.ascontiguousarray(v, dtype=np.int32) for k, v in
@@ -942,10 +976,12 @@ class CrossRun(_Handle):
 
 class Pileup(_Handle):
     """Per-base counters over a text SeqSet, resident in HBM (wfa_hip_pileup_t): 32 bytes per text base, int32 counters without an
-    overflow check.  Stays valid after the set is closed.  ``tracking``: whether it keeps the insertion log (``track_insertions``)."""
+    overflow check.  Stays valid after the set is closed.  ``tracking``: whether it keeps the insertion log (``track_insertions``);
+    ``strands``: whether it keeps the forward table (``track_strands``: 32 more bytes per text base)."""
 
     _destroy = "wfa_hip_pileup_destroy"
     tracking = False
+    strands = False
 
     def __init__(self, aligner, texts):
         if not texts._h:
@@ -955,15 +991,21 @@ class Pileup(_Handle):
         self.length = texts.length
         self._created(lib().wfa_hip_pileup_create(aligner._h, texts._h), "wfa_hip_pileup_create")
 
-    def add(self, batch, j, t_start=None, keep=None):
-        """wfa_hip_pileup_add: the pairs of a ResidentBatch after its full-scope run, pair q against texts[j[q]] from t_start[q]."""
+    def add(self, batch, j, t_start=None, keep=None, reverse=None):
+        """wfa_hip_pileup_add: the pairs of a ResidentBatch after its full-scope run, pair q against texts[j[q]] from t_start[q].  On a
+        pileup that tracks strands, wfa_hip_pileup_add_strands: ``reverse[q]`` != 0 is a reverse pair, None: every pair is forward
+        (a ``reverse`` on a pileup that does not track goes to that call too, which refuses it)."""
         j = np.ascontiguousarray(j, dtype=np.int32)
         t_start = None if t_start is None else np.ascontiguousarray(t_start, dtype=np.int32)
         keep = None if keep is None else np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
-        for name, a in (("j", j), ("t_start", t_start), ("keep", keep)):
+        reverse = None if reverse is None else np.ascontiguousarray(np.asarray(reverse) != 0, dtype=np.uint8)
+        for name, a in (("j", j), ("t_start", t_start), ("keep", keep), ("reverse", reverse)):
             if a is not None and a.shape != (batch.n,):
                 raise ValueError(f"{name}: one value per pair of the batch ({batch.n})")
-        self._call("wfa_hip_pileup_add", self._h, batch._h, _ptr(j), _ptr(t_start), _ptr(keep))
+        if self.strands or reverse is not None:
+            self._call("wfa_hip_pileup_add_strands", self._h, batch._h, _ptr(j), _ptr(t_start), _ptr(keep), _ptr(reverse))
+        else:
+            self._call("wfa_hip_pileup_add", self._h, batch._h, _ptr(j), _ptr(t_start), _ptr(keep))
 
     def _rows(self, seq, start, length):
         """``(seq, start, length)`` as ints, a ``length`` of None running to the end of the sequence."""
@@ -974,11 +1016,15 @@ class Pileup(_Handle):
             length = int(self.length[seq]) - start
         return seq, start, int(length)
 
-    def read(self, seq, start=0, length=None):
-        """wfa_hip_pileup_read: int32[length, 8], the rows [start, start + length) of one sequence (to its end when None)."""
+    def read(self, seq, start=0, length=None, strand=None):
+        """wfa_hip_pileup_read: int32[length, 8], the rows [start, start + length) of one sequence (to its end when None).  ``strand``
+        0 or 1: wfa_hip_pileup_read_strand, the forward or the reverse counts of a pileup that tracks strands."""
         seq, start, length = self._rows(seq, start, length)
         out = np.zeros((max(length, 0), PILEUP_COLS), np.int32)
-        self._call("wfa_hip_pileup_read", self._h, seq, start, length, _ptr_or_null(out))
+        if strand is None:
+            self._call("wfa_hip_pileup_read", self._h, seq, start, length, _ptr_or_null(out))
+        else:
+            self._call("wfa_hip_pileup_read_strand", self._h, seq, start, length, int(strand), _ptr_or_null(out))
         return out
 
     def calls(self, texts, seq, start=0, length=None, min_depth=1):
@@ -1002,8 +1048,26 @@ class Pileup(_Handle):
             self._call("wfa_hip_pileup_sites", *args, int(cap), ctypes.byref(count), _ptr_or_null(rows))
         return count.value, rows[:min(count.value, rows.shape[0])]
 
+    def genotypes(self, texts, seq=-1, start=0, length=-1, min_depth=1, min_permille=500, err_q=20, min_alt_strand=0, cap=None):
+        """wfa_hip_pileup_genotypes: ``(count, rows)``, rows int32 of shape (min(count, cap), 16) in ascending (j, pos); ``cap`` None: a
+        counting call, then one with the exact capacity.  seq = -1: every sequence."""
+        args = (self._h, texts._h, int(seq), int(start), int(length), int(min_depth), int(min_permille), int(err_q), int(min_alt_strand))
+        count = ctypes.c_int64(0)
+        if cap is None:
+            self._call("wfa_hip_pileup_genotypes", *args, 0, ctypes.byref(count), None)
+            cap = count.value
+        rows = np.zeros((max(int(cap), 0), GENOTYPE_COLS), np.int32)
+        if cap != 0:
+            self._call("wfa_hip_pileup_genotypes", *args, int(cap), ctypes.byref(count), _ptr_or_null(rows))
+        return count.value, rows[:min(count.value, rows.shape[0])]
+
     def clear(self):
         self._call("wfa_hip_pileup_clear", self._h)
+
+    def track_strands(self, on=True):
+        """wfa_hip_pileup_track_strands: keep (or stop keeping) the forward table; only while the pileup is empty."""
+        self._call("wfa_hip_pileup_track_strands", self._h, 1 if on else 0)
+        self.strands = bool(on)
 
     def track_insertions(self, on=True):
         """wfa_hip_pileup_track_insertions: keep (or stop keeping) what the reads insert; only while the pileup is empty."""

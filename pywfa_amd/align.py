@@ -387,9 +387,12 @@ class Pileup(_Closing):
     overflow; the table takes 32 bytes per text base until ``close()`` (or the end of the ``with`` block).  ``calls`` / ``consensus`` /
     ``sites`` reduce the table on the GPU against the reference letters: a byte per base or a row per variant site comes back.  A
     pileup made with ``insertions=True`` also keeps what the reads insert (about 24 bytes per insertion and 1 byte per inserted base
-    on the GPU): ``insertions`` gives one allele per insertion site, ``consensus(insertions=True)`` splices them in."""
+    on the GPU): ``insertions`` gives one allele per insertion site, ``consensus(insertions=True)`` splices them in.  A pileup made
+    with ``strands=True`` also counts the forward reads on their own (32 more bytes per text base): ``counts`` / ``depth`` take
+    ``strand="+"`` / ``"-"``, ``genotypes`` reports the forward counts and can ask for both strands (``min_alt_strand``)."""
 
     COLUMNS = _native.PILEUP_COLUMNS
+    GENOTYPE_COLUMNS = _native.GENOTYPE_COLUMNS
     CALL_CODES = _native.CALL_CODES
     SITE_COLUMNS = _native.SITE_COLUMNS
     INSERTION_COLUMNS = _native.INSERTION_COLUMNS
@@ -409,9 +412,16 @@ class Pileup(_Closing):
     def __len__(self):
         return self._open().n
 
-    def counts(self, j, start=0, stop=None):
-        """int32 array of shape (stop - start, 8): the rows [start, stop) of text ``j`` (to its end when ``stop`` is None)."""
+    def counts(self, j, start=0, stop=None, strand=None):
+        """int32 array of shape (stop - start, 8): the rows [start, stop) of text ``j`` (to its end when ``stop`` is None).
+        ``strand``: None, every read; ``"+"`` / ``"-"``, the forward / the reverse reads only (a pileup made with ``strands=True``,
+        else ValueError; the reverse counts are the total minus the forward ones)."""
         p = self._open()
+        if strand is not None:
+            if strand not in ("+", "-"):
+                raise ValueError(f"strand = {strand!r}: \"+\", \"-\" or None")
+            if not p.strands:
+                raise ValueError("this pileup was not made to track strands: make it with pileup(..., strands=True)")
         if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= int(j) < p.n:
             raise ValueError(f"j = {j!r} is out of range for {p.n} text sequences")
         have = int(p.length[int(j)])
@@ -419,11 +429,12 @@ class Pileup(_Closing):
         stop = have if stop is None else int(stop)
         if not 0 <= start <= stop <= have:
             raise ValueError(f"rows [{start}, {stop}) are out of range for text sequence {int(j)} ({have} bases)")
-        return p.read(int(j), start, stop - start)
+        return p.read(int(j), start, stop - start, None if strand is None else int(strand == "-"))
 
-    def depth(self, j, start=0, stop=None):
-        """The sum of the columns A, C, G, T, other and del: the contributing reads whose aligned core covers each base."""
-        return self.counts(j, start, stop)[:, :6].sum(axis=1, dtype=np.int32)
+    def depth(self, j, start=0, stop=None, strand=None):
+        """The sum of the columns A, C, G, T, other and del: the contributing reads whose aligned core covers each base (``strand``
+        as for ``counts``)."""
+        return self.counts(j, start, stop, strand)[:, :6].sum(axis=1, dtype=np.int32)
 
     def _range(self, p, j, start, stop):
         """The checked rows [start, stop) of text ``j`` (the wording of ``counts``)."""
@@ -507,8 +518,8 @@ class Pileup(_Closing):
         least ``min_frac`` of them insert (the ``ins`` condition of ``sites``; ``min_frac``, ``j``, ``start``, ``stop`` as there).  The
         allele is the inserted sequence most of the row's inserting reads carry (``allele_count`` of ``ins_count``; ties go to the
         shorter, then to the alphabetically smaller in the order A C G T N); ``alleles``: how many different ones they carry.  A row
-        with more than ``WFA_HIP_INS_MAX_READS`` (4096) inserting reads has ``overflow`` = 1, zeros and ``""``.  Qualities, strands,
-        genotypes, left-normalising insertions across reads and more than one allele per row are out of scope."""
+        with more than ``WFA_HIP_INS_MAX_READS`` (4096) inserting reads has ``overflow`` = 1, zeros and ``""``.  Qualities, multi-base
+        events, a strand per inserting read and more than one allele per row are out of scope."""
         p = self._tracking()
         if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
             raise ValueError(f"min_frac = {min_frac!r} is out of range (0.001 .. 1)")
@@ -533,8 +544,9 @@ class Pileup(_Closing):
         column other than the reference's letter holds at least ``min_frac`` of the covering reads (``alt`` its column in
         ``CALL_CODES``, 5 = deleted; ``alt_count``), or where at least ``min_frac`` of them insert in front of the base (``ins_count``;
         ``alt`` = -1 and ``alt_count`` = 0 when only this holds).  ``min_frac`` is rounded to permille.  ``j=None``: every text (then
-        ``start`` / ``stop`` must be left alone); otherwise the rows [start, stop) of text ``j``.  What was inserted, qualities, strands
-        and genotypes are out of scope; what was inserted: ``insertions``, on a pileup made with ``insertions=True``."""
+        ``start`` / ``stop`` must be left alone); otherwise the rows [start, stop) of text ``j``.  Qualities and multi-base events are
+        out of scope; what was inserted: ``insertions``, on a pileup made with ``insertions=True``; strands and genotypes:
+        ``genotypes``."""
         p = self._open()
         if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
             raise ValueError(f"min_frac = {min_frac!r} is out of range (0.001 .. 1)")
@@ -548,6 +560,39 @@ class Pileup(_Closing):
             length = stop - start
         _, rows = self._with_texts(p, texts, min_depth, lambda t: p.sites(t, seq, start, length, int(min_depth), permille))
         return _columns(rows, self.SITE_COLUMNS)
+
+    def genotypes(self, texts, j=None, start=0, stop=None, min_depth=8, min_frac=0.2, err_q=20, min_alt_strand=0):
+        """The sites with a diploid genotype each, made on the GPU: a dict of int32 arrays ``GENOTYPE_COLUMNS`` in ascending (j, pos).
+        The first eight are the columns of ``sites`` (same ``texts``, ``j``, ``start``, ``stop``, ``min_depth``, ``min_frac``).
+        ``gt`` / ``gq``: 0, 1 or 2 copies of ``alt`` and a confidence 0..99, from ``ref_count`` and ``alt_count`` alone — the
+        smallest of err_q * alt_count (0/0), 3 * (ref_count + alt_count) (0/1) and err_q * ref_count (1/1), and its distance to the
+        next; a documented confidence, not a calibrated likelihood (no qualities enter it).  ``ins_gt`` / ``ins_gq``: the same for
+        the insertion in front of the base, from ``ins_count`` and the reads that cover the base without one.  A pair is -1, -1 where
+        the site has no such event.  ``depth_fwd``, ``ref_fwd``, ``alt_fwd``, ``ins_fwd``: the forward reads among ``depth``,
+        ``ref_count``, ``alt_count``, ``ins_count`` (a pileup made with ``strands=True``; -1 otherwise) — the reverse ones are the
+        difference, the strand test is the caller's.  ``min_alt_strand`` > 0 (needs ``strands=True``): an event counts only when at
+        least that many reads of EACH strand carry it.  More than one alternate allele per site and ploidy other than 2 are out of
+        scope."""
+        p = self._open()
+        if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
+            raise ValueError(f"min_frac = {min_frac!r} is out of range (0.001 .. 1)")
+        permille = int(round(float(min_frac) * 1000))
+        if isinstance(err_q, bool) or not isinstance(err_q, (int, np.integer)) or not 1 <= int(err_q) <= 60:
+            raise ValueError(f"err_q = {err_q!r} is out of range (an integer, 1 .. 60)")
+        if isinstance(min_alt_strand, bool) or not isinstance(min_alt_strand, (int, np.integer)) or not 0 <= int(min_alt_strand) < 2**31:
+            raise ValueError(f"min_alt_strand = {min_alt_strand!r} is out of range (an integer, at least 0)")
+        if int(min_alt_strand) > 0 and not p.strands:
+            raise ValueError("min_alt_strand > 0 needs a pileup made to track strands: make it with pileup(..., strands=True)")
+        if j is None:
+            if start != 0 or stop is not None:
+                raise ValueError("j = None takes every text: start and stop go with one text")
+            seq, start, length = -1, 0, -1
+        else:
+            seq, start, stop = self._range(p, j, start, stop)
+            length = stop - start
+        _, rows = self._with_texts(p, texts, min_depth,
+                                   lambda t: p.genotypes(t, seq, start, length, int(min_depth), permille, int(err_q), int(min_alt_strand)))
+        return _columns(rows, self.GENOTYPE_COLUMNS)
 
 
 class SequenceSet(_Closing):
@@ -1321,7 +1366,7 @@ class WavefrontAligner:
             return w.run(summary=summary, left_align=bool(left_align))
 
     def pileup(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
-               text_len=None, reverse=None, min_score=None, insertions=False, left_align=False):
+               text_len=None, reverse=None, min_score=None, insertions=False, left_align=False, strands=False):
         """Align the listed windows as ``align_windows`` does (same arguments, same checks; scope must be "full") and pile the
         alignments up over the TEXT sequences on the GPU: the patterns are reads, the texts references.  Every pair whose status is
         0 (and whose score is at least ``min_score``, when given) adds the ops of its aligned core — first M to last M — to the
@@ -1332,9 +1377,12 @@ class WavefrontAligner:
         the GPU before it is piled up (``left_align_ops`` states the rule), so a gap inside a homopolymer or tandem repeat is
         counted at the left end of the repeat, where VCF puts it, and reads that stopped at different places of one repeat agree
         as far as their own letters allow; tables, ``sites``, ``insertions`` and ``consensus(insertions=True)`` follow.
+        ``strands=True``: the pileup also counts the forward reads (``reverse[q]`` == 0; every read when ``reverse`` is None) in a
+        second table of 32 more bytes per text base, for ``counts(strand=...)`` and the strand columns and filter of
+        ``Pileup.genotypes``; without it nothing more is allocated or launched.
 
         Returns a ``Pileup`` (``score``, ``status``, ``counts(j)``, ``depth(j)``, ``calls()``, ``consensus()``, ``sites()``,
-        ``insertions()``, ``close()``; a context manager), which stays
+        ``genotypes()``, ``insertions()``, ``close()``; a context manager), which stays
         valid after the sets are closed.  With ``devices=[...]`` the first device runs it."""
         if self._cfg.scope != 1:
             raise ValueError("pileup needs scope='full'")
@@ -1343,12 +1391,18 @@ class WavefrontAligner:
         with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
             jj, ts = w.arrays[1], w.arrays[4]
             table = w.attach(self._native.pileup(w.text_set), keep=True)
+            rev = w.arrays[6]
             if insertions:
                 table.track_insertions(True)
+            if strands:
+                table.track_strands(True)
 
             def add(rb, lo, hi, score, status):
                 keep = None if min_score is None else (score >= int(min_score))
-                table.add(rb, jj[lo:hi], None if ts is None else ts[lo:hi], keep)
+                if strands:
+                    table.add(rb, jj[lo:hi], None if ts is None else ts[lo:hi], keep, None if rev is None else rev[lo:hi])
+                else:
+                    table.add(rb, jj[lo:hi], None if ts is None else ts[lo:hi], keep)
 
             out = w.run(each=add, left_align=bool(left_align))
             return Pileup(table, out["score"], out["status"], self)

@@ -51,13 +51,19 @@ struct wfa_hip_pileup {
   bool track = false, added = false;   // added: an add since the create or the last clear
   wfa::InsRecord* d_rec = nullptr; uint8_t* d_ins = nullptr;
   int64_t nrec = 0, nins = 0, cap_rec = 0, cap_ins = 0;
+  // strands (include/wfa_hip.h, "strands and genotypes"): the forward table, of the table's size and layout, while tracking is on
+  bool strands = false;
+  int32_t* d_fwd = nullptr;
 };
+
+static size_t pileup_table_bytes(const wfa_hip_pileup* p) { return (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t); }
 
 extern "C" void wfa_hip_pileup_destroy(wfa_hip_pileup_t* p) {
   if (!p) return;
   wfa_hip_aligner* al = p->al;
   (void)hipSetDevice(al->device);
   if (p->d_table) (void)hipFree(p->d_table);
+  if (p->d_fwd) (void)hipFree(p->d_fwd);
   if (p->d_rec) (void)hipFree(p->d_rec);
   if (p->d_ins) (void)hipFree(p->d_ins);
   pool_release(al, p->d_off); pool_release(al, p->d_len);
@@ -97,7 +103,8 @@ extern "C" int wfa_hip_pileup_clear(wfa_hip_pileup_t* p) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
   HIP_TRY(al, hipSetDevice(al->device));
-  HIP_TRY(al, hipMemsetAsync(p->d_table, 0, (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t), al->stream));
+  HIP_TRY(al, hipMemsetAsync(p->d_table, 0, pileup_table_bytes(p), al->stream));
+  if (p->d_fwd) HIP_TRY(al, hipMemsetAsync(p->d_fwd, 0, pileup_table_bytes(p), al->stream));
   HIP_TRY(al, hipStreamSynchronize(al->stream));
   p->nrec = p->nins = 0;   // (the log's blocks stay for the next adds)
   p->added = false;
@@ -108,6 +115,29 @@ extern "C" int wfa_hip_pileup_track_insertions(wfa_hip_pileup_t* p, int on) {
   if (!p) return WFA_HIP_EINVAL;
   if (p->added) return fail_inval(p->al, "pileup: insertion tracking is chosen while the pileup is empty (fresh, or just cleared); this one has been added to");
   p->track = on != 0;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_track_strands(wfa_hip_pileup_t* p, int on) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (p->added) return fail_inval(al, "pileup: strand tracking is chosen while the pileup is empty (fresh, or just cleared); this one has been added to");
+  if ((on != 0) == p->strands) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  if (!on) {
+    HIP_TRY(al, hipStreamSynchronize(al->stream));
+    (void)hipFree(p->d_fwd);
+    p->d_fwd = nullptr; p->strands = false;
+    return WFA_HIP_OK;
+  }
+  const size_t bytes = pileup_table_bytes(p);
+  int32_t* fwd = nullptr;
+  if (hipMalloc((void**)&fwd, bytes) != hipSuccess)
+    return fail_alloc(al, (void**)&fwd, "pileup forward table: hipMalloc of %zu bytes failed (32 more bytes per text base, %lld bases)", bytes, (long long)p->total);
+  const hipError_t e = hipMemsetAsync(fwd, 0, bytes, al->stream);
+  const hipError_t e2 = hipStreamSynchronize(al->stream);
+  if (e != hipSuccess || e2 != hipSuccess) { (void)hipFree(fwd); HIP_TRY(al, e); HIP_TRY(al, e2); }
+  p->d_fwd = fwd; p->strands = true;
   return WFA_HIP_OK;
 }
 
@@ -143,7 +173,7 @@ template <class T> static int ins_log_grow(wfa_hip_aligner* al, T** block, int64
 
 // An add with tracking on (csrc/wfa_insertions.hpp): count, the two scans, the 16-byte download, the growth, then the table kernel in its
 // tracking form.  Nothing is added before the log has its room.
-static int pileup_add_tracked(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a) {
+static int pileup_add_tracked(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a, const wfa::PileupStrandArgs* s) {
   wfa_hip_aligner* al = p->al;
   const size_t n = (size_t)a.npairs;
   wfa::InsLogArgs g;
@@ -166,16 +196,21 @@ static int pileup_add_tracked(wfa_hip_pileup* p, StreamScratch& sc, const wfa::P
   g.rec_base = p->nrec; g.base_base = p->nins; g.rec_cap = p->cap_rec; g.base_cap = p->cap_ins;
   ReduceTimer timer(al, "pileup tracked", a.npairs);
   p->added = true;
-  rc = launch_end(al, &timer, wfa::launch_pileup_track(a, g, al->cu_count, al->stream), "pileup kernel launch failed");
+  rc = launch_end(al, &timer, s ? wfa::launch_pileup_track_strands(a, g, *s, al->cu_count, al->stream) : wfa::launch_pileup_track(a, g, al->cu_count, al->stream),
+                  "pileup kernel launch failed");
   if (rc == WFA_HIP_OK) { p->nrec += (int64_t)totals[0]; p->nins += (int64_t)totals[1]; }
   return rc;
 }
 
-extern "C" int wfa_hip_pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep) {
+// the two adds: `stranded` is the entry (wfa_hip_pileup_add_strands), which must match the pileup's setting
+static int pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep, const uint8_t* reverse,
+                      bool stranded) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
   int rc = batch_of(al, b, "pileup", true);
   if (rc != WFA_HIP_OK) return rc;
+  if (stranded && !p->strands) return fail_inval(al, "pileup: this pileup was not made to track strands (wfa_hip_pileup_track_strands); add to it with wfa_hip_pileup_add");
+  if (!stranded && p->strands) return fail_inval(al, "pileup: this pileup tracks strands; add to it with wfa_hip_pileup_add_strands, which takes the pairs' strands");
   const int64_t n = b->n;
   if (n > 0 && !j) return fail_inval(al, "pileup: the text indices are missing");
   for (int64_t q = 0; q < n; ++q) {
@@ -194,18 +229,34 @@ extern "C" int wfa_hip_pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const
   HIP_TRY(al, hipSetDevice(al->device));
   StreamScratch sc{al};   // (waits for the stream before the blocks go back)
   int32_t *d_j = nullptr, *d_ts = nullptr;
-  uint8_t* d_keep = nullptr;
+  uint8_t *d_keep = nullptr, *d_rev = nullptr;
   if (sc.upload(&d_j, j, (size_t)n) || sc.upload_opt(&d_ts, t_start, (size_t)n) || sc.upload_opt(&d_keep, keep, (size_t)n)) return WFA_HIP_EDEVICE;
+  if (stranded && sc.upload_opt(&d_rev, reverse, (size_t)n)) return WFA_HIP_EDEVICE;
   wfa::PileupArgs a;
   memset(&a, 0, sizeof(a));
   a.ops = b->d_ops; a.cigar_begin = b->d_cigar_begin; a.cigar_len = b->d_cigar_len; a.status = b->d_status;
   a.meta = b->d_meta; a.words = b->d_words; a.bytes = b->d_bytes; a.pboff = b->d_pboff; a.flags = b->d_flags;
   a.npairs = n; a.j = d_j; a.t_start = d_ts; a.keep = d_keep;
   a.seq_off = p->d_off; a.seq_len = p->d_len; a.nseq = p->nseq; a.total = p->total; a.table = p->d_table;
-  if (p->track) return pileup_add_tracked(p, sc, a);
+  const wfa::PileupStrandArgs s{d_rev, p->d_fwd};
+  if (p->track) return pileup_add_tracked(p, sc, a, stranded ? &s : nullptr);
+  if (stranded) {
+    ReduceTimer timer(al, "pileup stranded", n);
+    p->added = true;
+    return launch_end(al, &timer, wfa::launch_pileup_strands(a, s, al->cu_count, al->stream), "pileup kernel launch failed");
+  }
   ReduceTimer timer(al, "pileup", n);
   p->added = true;
   return launch_end(al, &timer, wfa::launch_pileup(a, al->cu_count, al->stream), "pileup kernel launch failed");   // (the caller's arrays are read by the copies above)
+}
+
+extern "C" int wfa_hip_pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep) {
+  return pileup_add(p, b, j, t_start, keep, nullptr, false);
+}
+
+extern "C" int wfa_hip_pileup_add_strands(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep,
+                                          const uint8_t* reverse) {
+  return pileup_add(p, b, j, t_start, keep, reverse, true);
 }
 
 // rows [start, start + len) of sequence seq are rows of the pileup, or the refusal that names them
@@ -213,6 +264,14 @@ static int pileup_check_rows(const wfa_hip_pileup* p, int32_t seq, int64_t start
   if (seq >= 0 && seq < p->nseq && start >= 0 && len >= 0 && start + len <= p->h_len[(size_t)seq]) return WFA_HIP_OK;
   return fail_inval(p->al, "pileup: rows [%lld, %lld + %lld) of sequence %d are out of range (%lld sequences; sequence length %lld)", (long long)start,
                     (long long)start, (long long)len, (int)seq, (long long)p->nseq, (long long)((seq >= 0 && seq < p->nseq) ? p->h_len[(size_t)seq] : -1));
+}
+
+// the rows of one table (the total or the forward one) into `plane`, a stretch of len counters per column; the stream is not waited for
+static int pileup_fetch_planes(const wfa_hip_pileup* p, const int32_t* table, int32_t seq, int64_t start, int64_t len, int32_t* plane) {
+  for (int c = 0; c < WFA_PILEUP_COLS; ++c)
+    HIP_TRY(p->al, hipMemcpyAsync(plane + (size_t)c * (size_t)len, table + (int64_t)c * p->total + p->h_off[(size_t)seq] + start,
+                                  (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost, p->al->stream));
+  return WFA_HIP_OK;
 }
 
 extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int32_t* counts) {
@@ -224,13 +283,35 @@ extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t sta
   HIP_TRY(al, hipSetDevice(al->device));
   // the table is a plane per column: one copy per plane, interleaved into rows on the host
   std::vector<int32_t> plane((size_t)len * WFA_PILEUP_COLS);
-  for (int c = 0; c < WFA_PILEUP_COLS; ++c)
-    HIP_TRY(al, hipMemcpyAsync(plane.data() + (size_t)c * (size_t)len, p->d_table + (int64_t)c * p->total + p->h_off[(size_t)seq] + start,
-                               (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+  const int rc = pileup_fetch_planes(p, p->d_table, seq, start, len, plane.data());
+  if (rc != WFA_HIP_OK) return rc;
   HIP_TRY(al, hipStreamSynchronize(al->stream));
   for (int c = 0; c < WFA_PILEUP_COLS; ++c) {
     const int32_t* src = plane.data() + (size_t)c * (size_t)len;
     for (int64_t r = 0; r < len; ++r) counts[r * WFA_PILEUP_COLS + c] = src[r];
+  }
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_read_strand(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int strand, int32_t* counts) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (pileup_check_rows(p, seq, start, len) != WFA_HIP_OK) return WFA_HIP_EINVAL;
+  if (strand != 0 && strand != 1) return fail_inval(al, "pileup: strand = %d is out of range (0 forward, 1 reverse)", strand);
+  if (!p->strands) return fail_inval(al, "pileup: this pileup was not made to track strands");
+  if (len == 0) return WFA_HIP_OK;
+  if (!counts) return fail_inval(al, "pileup: null output");
+  HIP_TRY(al, hipSetDevice(al->device));
+  // forward: the forward table's rows; reverse: the table's rows minus those
+  const size_t cells = (size_t)len * WFA_PILEUP_COLS;
+  std::vector<int32_t> plane(cells * (strand ? 2 : 1));
+  int rc = pileup_fetch_planes(p, p->d_fwd, seq, start, len, plane.data());
+  if (rc == WFA_HIP_OK && strand) rc = pileup_fetch_planes(p, p->d_table, seq, start, len, plane.data() + cells);
+  if (rc != WFA_HIP_OK) return rc;
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  for (int c = 0; c < WFA_PILEUP_COLS; ++c) {
+    const int32_t* f = plane.data() + (size_t)c * (size_t)len;
+    for (int64_t r = 0; r < len; ++r) counts[r * WFA_PILEUP_COLS + c] = strand ? f[cells + (size_t)r] - f[r] : f[r];
   }
   return WFA_HIP_OK;
 }
@@ -337,6 +418,48 @@ extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t*
   if (sc.alloc(&a.rows, (size_t)a.cap * WFA_SITE_COLS)) return WFA_HIP_EDEVICE;
   ReduceTimer timer(al, "sites scatter", n, "bases");
   return calls_launched(sc, timer, wfa::launch_sites_scatter(a, al->stream), "sites scatter kernel launch failed", rows, a.rows, (size_t)a.cap * WFA_SITE_COLS);
+}
+
+// ---- genotyped sites (include/wfa_hip.h, "strands and genotypes"; csrc/wfa_calls.hpp, k_calls.hip) -----------------------------------
+static_assert(WFA_GENOTYPE_COLS == WFA_HIP_GENOTYPE_COLS, "columns of the kernels and of the ABI");
+
+extern "C" int wfa_hip_pileup_genotypes(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                        int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
+                                        int64_t* count, int32_t* rows) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  int64_t g0 = 0, n = 0;
+  const int rc = calls_check(p, texts, true, seq, start, len, min_depth, min_permille, cap, &g0, &n);
+  if (rc != WFA_HIP_OK) return rc;
+  if (err_q < 1 || err_q > 60) return fail_inval(al, "pileup: err_q = %d is out of range (1 .. 60)", (int)err_q);
+  if (min_alt_strand < 0) return fail_inval(al, "pileup: min_alt_strand = %d is negative", (int)min_alt_strand);
+  if (min_alt_strand > 0 && !p->strands)
+    return fail_inval(al, "pileup: min_alt_strand = %d needs a pileup made to track strands (wfa_hip_pileup_track_strands)", (int)min_alt_strand);
+  if (!count) return fail_inval(al, "pileup: null count");
+  if (cap > 0 && !rows) return fail_inval(al, "pileup: null rows with cap > 0");
+  HIP_TRY(al, hipSetDevice(al->device));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  *count = 0;
+  if (n == 0) return WFA_HIP_OK;
+  StreamScratch sc{al};
+  wfa::GenoArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = calls_args(p, texts, g0, n, min_depth, min_permille);
+  a.fwd = p->strands ? p->d_fwd : nullptr; a.err_q = err_q; a.min_alt_strand = min_alt_strand;
+  if (calls_chunks(sc, &a.c)) return WFA_HIP_EDEVICE;
+  uint64_t total = 0;
+  {
+    ReduceTimer timer(al, "genotypes count", n, "bases");
+    const int crc = calls_launched(sc, timer, wfa::launch_genotypes_count(a, al->stream), "genotypes count kernel launch failed", &total, a.c.chunk_off + a.c.chunks, 1);
+    if (crc != WFA_HIP_OK) return crc;
+  }
+  *count = (int64_t)total;
+  a.c.cap = std::min<int64_t>((int64_t)total, cap);
+  if (a.c.cap == 0) return WFA_HIP_OK;
+  if (sc.alloc(&a.c.rows, (size_t)a.c.cap * WFA_GENOTYPE_COLS)) return WFA_HIP_EDEVICE;
+  ReduceTimer timer(al, "genotypes scatter", n, "bases");
+  return calls_launched(sc, timer, wfa::launch_genotypes_scatter(a, al->stream), "genotypes scatter kernel launch failed", rows, a.c.rows,
+                        (size_t)a.c.cap * WFA_GENOTYPE_COLS);
 }
 
 // ---- what the reads insert: one allele per reported row (include/wfa_hip.h, "insertions"; csrc/wfa_insertions.hpp, k_insertions.hip) ------

@@ -230,6 +230,59 @@ extern "C" int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int
   return WFA_HIP_OK;
 }
 
+// ---- genotyped sites: the sites under the strand filter, a diploid genotype per event (the kernels: wfa_calls.hpp, k_calls.hip) ----
+
+namespace {
+// GENOTYPE: the index of the smallest of L0, L1, L2 (the smaller index on a tie) and min(99, second smallest - smallest)
+void genotype_of(int64_t R, int64_t A, int32_t err_q, int32_t* gt, int32_t* gq) {
+  const int64_t L[3] = {(int64_t)err_q * A, 3 * (R + A), (int64_t)err_q * R};
+  int best = 0;
+  for (int k = 1; k < 3; ++k) if (L[k] < L[best]) best = k;
+  const int64_t second = std::min(L[(best + 1) % 3], L[(best + 2) % 3]);
+  *gt = best;
+  *gq = (int32_t)std::min<int64_t>(99, second - L[best]);
+}
+}  // namespace
+
+extern "C" int wfa_hip_genotypes_host(const int32_t* counts, const int32_t* counts_fwd, const uint8_t* ref, int64_t len, int32_t seq, int64_t start,
+                                      int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap, int64_t* count,
+                                      int32_t* rows) {
+  if (len < 0 || min_depth < 1 || min_permille < 1 || min_permille > 1000 || err_q < 1 || err_q > 60 || min_alt_strand < 0 ||
+      (min_alt_strand > 0 && !counts_fwd) || cap < 0 || !count || (len > 0 && (!counts || !ref)) || (cap > 0 && !rows))
+    return WFA_HIP_EINVAL;
+  int64_t n = 0;
+  for (int64_t g = 0; g < len; ++g) {
+    const int32_t* c = counts + g * WFA_HIP_PILEUP_COLS;
+    const int32_t* f = counts_fwd ? counts_fwd + g * WFA_HIP_PILEUP_COLS : nullptr;
+    const int64_t depth = depth_of(c);
+    if (depth < min_depth) continue;
+    const int r = ref_col(ref[g]);
+    int alt = -1;
+    for (int x = 0; x < 6; ++x) if (x != r && (alt < 0 || c[x] > c[alt])) alt = x;
+    const int64_t A = c[alt], ins = c[6];
+    bool snv = A >= 1 && 1000 * A >= (int64_t)min_permille * depth;
+    bool has_ins = ins >= 1 && 1000 * ins >= (int64_t)min_permille * depth;
+    if (min_alt_strand > 0) {
+      snv = snv && f[alt] >= min_alt_strand && A - f[alt] >= min_alt_strand;
+      has_ins = has_ins && f[6] >= min_alt_strand && ins - f[6] >= min_alt_strand;
+    }
+    if (!snv && !has_ins) continue;
+    if (n < cap) {
+      int32_t* row = rows + n * WFA_HIP_GENOTYPE_COLS;
+      row[0] = seq; row[1] = (int32_t)(start + g); row[2] = r; row[3] = snv ? alt : -1; row[4] = (int32_t)depth;
+      row[5] = c[r]; row[6] = snv ? c[alt] : 0; row[7] = c[6];
+      row[8] = row[9] = row[10] = row[11] = -1;
+      if (snv) genotype_of(c[r], A, err_q, &row[8], &row[9]);
+      if (has_ins) genotype_of(std::max<int64_t>(0, depth - ins), ins, err_q, &row[10], &row[11]);
+      row[12] = row[13] = row[14] = row[15] = -1;
+      if (f) { row[12] = (int32_t)depth_of(f); row[13] = f[r]; row[14] = snv ? f[alt] : 0; row[15] = f[6]; }
+    }
+    ++n;
+  }
+  *count = n;
+  return WFA_HIP_OK;
+}
+
 // ---- insertions: a pair's records, and the allele rule over rows and records (the kernels: wfa_insertions.hpp, k_pileup.hip, k_insertions.hip) ----
 
 extern "C" int wfa_hip_ops_insertions(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen, int64_t cap,

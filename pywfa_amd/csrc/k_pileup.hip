@@ -2,7 +2,8 @@
 // insertion log (wfa_insertions.hpp: InsLogArgs).
 // One wave per pair, grid-stride.  Every store to the table is an int32 atomicAdd; a lane adds only for an op of the aligned core
 // whose text position lies inside the pair's text window, and the host has checked that the window lies inside its sequence, so an op
-// string that disagreed with its pair's lengths could lose counts but never leave the table.  The log's stores are plain: a record
+// string that disagreed with its pair's lengths could lose counts but never leave the table.  The stranded forms add a second time at
+// the same offset of the forward table, an allocation of the table's size.  The log's stores are plain: a record
 // and a column byte have one writer, at an index below the allocated size (checked at the store).
 #include <algorithm>
 #include "wfa_insertions.hpp"
@@ -13,8 +14,10 @@ enum { PILEUP_TABLE = 0, PILEUP_COUNT = 1, PILEUP_TRACK = 2 };
 
 // The walk of a pair's op string.  PILEUP_TABLE: the adds to the table (g unused).  PILEUP_COUNT: no store but pair_count[q] of a
 // contributing pair (the host zeroes the array).  PILEUP_TRACK: the adds and the pair's records and column bytes.
-template <int MODE>
-__device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArgs& g) {
+// STRANDS (TABLE and TRACK; wfa_pileup.hpp: PileupStrandArgs): a forward pair repeats every add at the same row and column of the
+// forward table.  The strand is the pair's, so it is uniform over the wave; without STRANDS `s` is not read.
+template <int MODE, bool STRANDS>
+__device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs& s) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -43,6 +46,9 @@ __device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArg
     // (checked on the host; here so that nothing a caller passes can move a store out of the table)
     if (jq < 0 || jq >= a.nseq || ts < 0 || ts + m.tlen > a.seq_len[jq]) continue;
     int32_t* row0 = a.table + a.seq_off[jq] + ts;
+    // the forward table has the table's size and layout: the same offsets stay inside it
+    const bool fwd = STRANDS && (s.reverse == nullptr || s.reverse[q] == 0);
+    int32_t* frow0 = STRANDS ? s.fwd + a.seq_off[jq] + ts : nullptr;
     const bool on_bytes = a.bytes != nullptr && a.flags[q] != 0;
     const uint8_t* pb = on_bytes ? a.bytes + a.pboff[q] : nullptr;
     const uint32_t* pw = a.words + m.p_woff;
@@ -104,25 +110,37 @@ __device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArg
       if (MODE == PILEUP_COUNT) continue;
       if (i < first || i > last || h >= m.tlen) continue;
       int32_t* row = row0 + h;
+      int32_t* frow = frow0 + h;
       if (c == 'M' || c == 'X') {
         if (v < m.plen) {
           const int col = on_bytes ? wfa_pileup_letter_col(pb[v]) : wfa_pileup_code_col((pw[v >> 4] >> (2 * (v & 15))) & 3u);
           atomicAdd(row + (int64_t)col * a.total, 1);
-          if (c == 'X') atomicAdd(row + (int64_t)WFA_PILEUP_MISMATCH * a.total, 1);
+          if (STRANDS && fwd) atomicAdd(frow + (int64_t)col * a.total, 1);
+          if (c == 'X') {
+            atomicAdd(row + (int64_t)WFA_PILEUP_MISMATCH * a.total, 1);
+            if (STRANDS && fwd) atomicAdd(frow + (int64_t)WFA_PILEUP_MISMATCH * a.total, 1);
+          }
         }
       } else if (c == 'I') {
         atomicAdd(row + (int64_t)WFA_PILEUP_DEL * a.total, 1);
+        if (STRANDS && fwd) atomicAdd(frow + (int64_t)WFA_PILEUP_DEL * a.total, 1);
       } else if (d_start) {
         atomicAdd(row + (int64_t)WFA_PILEUP_INS * a.total, 1);
+        if (STRANDS && fwd) atomicAdd(frow + (int64_t)WFA_PILEUP_INS * a.total, 1);
       }
     }
     if (MODE == PILEUP_COUNT && lane == 0) g.pair_count[q] = InsPairCount{nrec, nbase};
   }
 }
 
-__global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) { pileup_walk<PILEUP_TABLE>(a, InsLogArgs{}); }
-__global__ void __launch_bounds__(256) wfa_pileup_count_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_COUNT>(a, g); }
-__global__ void __launch_bounds__(256) wfa_pileup_track_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_TRACK>(a, g); }
+__global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) { pileup_walk<PILEUP_TABLE, false>(a, InsLogArgs{}, PileupStrandArgs{}); }
+__global__ void __launch_bounds__(256) wfa_pileup_count_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_COUNT, false>(a, g, PileupStrandArgs{}); }
+__global__ void __launch_bounds__(256) wfa_pileup_track_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_TRACK, false>(a, g, PileupStrandArgs{}); }
+// the stranded forms (COUNT stores nothing to a table and has none)
+__global__ void __launch_bounds__(256) wfa_pileup_strands_kernel(PileupArgs a, PileupStrandArgs s) { pileup_walk<PILEUP_TABLE, true>(a, InsLogArgs{}, s); }
+__global__ void __launch_bounds__(256) wfa_pileup_track_strands_kernel(PileupArgs a, InsLogArgs g, PileupStrandArgs s) {
+  pileup_walk<PILEUP_TRACK, true>(a, g, s);
+}
 
 static unsigned pileup_grid(const PileupArgs& a, int cu_count) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.npairs + 3) / 4, (int64_t)cu_count * 16));
@@ -132,6 +150,13 @@ int launch_pileup(const PileupArgs& a, int cu_count, hipStream_t stream) {
   if (a.npairs <= 0) return 0;
   const unsigned grid = pileup_grid(a, cu_count);
   hipLaunchKernelGGL(wfa_pileup_kernel, dim3(grid), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_pileup_strands(const PileupArgs& a, const PileupStrandArgs& s, int cu_count, hipStream_t stream) {
+  if (a.npairs <= 0) return 0;
+  if (!s.fwd) return -1;
+  hipLaunchKernelGGL(wfa_pileup_strands_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, s);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -147,6 +172,13 @@ int launch_pileup_count(const PileupArgs& a, const InsLogArgs& g, int cu_count, 
 int launch_pileup_track(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream) {
   if (a.npairs <= 0) return 0;
   hipLaunchKernelGGL(wfa_pileup_track_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_pileup_track_strands(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs& s, int cu_count, hipStream_t stream) {
+  if (a.npairs <= 0) return 0;
+  if (!s.fwd) return -1;
+  hipLaunchKernelGGL(wfa_pileup_track_strands_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g, s);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

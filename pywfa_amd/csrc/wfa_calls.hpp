@@ -85,6 +85,40 @@ __host__ __device__ inline bool calls_site(const CallsBase& b, int32_t min_depth
   return b.depth >= min_depth && (*snv || ins);
 }
 
+// ---- genotyped sites (include/wfa_hip.h, "strands and genotypes"; wfa_hip_genotypes_host in host_cigar.cpp is the plain statement) ----
+// The sites' three passes under a predicate with a strand filter, and rows of 16 columns: the site row, a diploid genotype and its
+// confidence for the SNV and for the insertion event, and the forward counts.  The forward table (the pileup's second table, same
+// planes and stride; nullptr on a pileup that does not track strands) is read only at bases that pass the sites' own predicate: in
+// the count pass only when min_alt_strand > 0, in the scatter pass for the row's last four columns.  A row is four int4 stores.
+#define WFA_GENOTYPE_COLS 16
+
+struct GenoArgs {
+  CallsArgs c;               // the run, the parameters of SITE, the chunks; rows: [cap x WFA_GENOTYPE_COLS]
+  const int32_t* fwd;        // the forward table or nullptr
+  int32_t err_q, min_alt_strand;
+};
+
+// the `ins` condition of SITE
+__host__ __device__ inline bool calls_ins(const CallsBase& b, int32_t min_permille) {
+  return b.c[6] >= 1 && 1000 * (int64_t)b.c[6] >= (int64_t)min_permille * b.depth;
+}
+
+// GENOTYPE of an event with R reference and A alternate reads: the smallest of L0 = err_q A, L1 = 3 (R + A), L2 = err_q R, the
+// smaller index on a tie; gq = min(99, second smallest - smallest)
+__host__ __device__ inline void calls_genotype(int64_t R, int64_t A, int32_t err_q, int32_t* gt, int32_t* gq) {
+  const int64_t L0 = (int64_t)err_q * A, L1 = 3 * (R + A), L2 = (int64_t)err_q * R;
+  int best = 0;
+  int64_t lo = L0, next = L1 < L2 ? L1 : L2;
+  if (L1 < lo) { best = 1; lo = L1; next = L0 < L2 ? L0 : L2; }
+  if (L2 < lo) { best = 2; lo = L2; next = L0 < L1 ? L0 : L1; }
+  const int64_t d = next - lo;
+  *gt = best;
+  *gq = (int32_t)(d < 99 ? d : 99);
+}
+
+int launch_genotypes_count(const GenoArgs& a, hipStream_t stream);     // count + scan, as launch_sites_count
+int launch_genotypes_scatter(const GenoArgs& a, hipStream_t stream);
+
 int launch_calls(const CallsArgs& a, int cu_count, hipStream_t stream);
 int launch_sites_count(const CallsArgs& a, hipStream_t stream);     // count + scan: chunk_off[chunks] is the number of sites
 int launch_sites_scatter(const CallsArgs& a, hipStream_t stream);

@@ -57,6 +57,16 @@ struct PileupArgs {
   int32_t* table;            // WFA_PILEUP_COLS planes
 };
 
+// Strands (include/wfa_hip.h, "strands and genotypes"; opt-in): a pileup that tracks them keeps a second table of the same 8 planes,
+// plane stride and layout, the FORWARD table: a pair with reverse[q] == 0 makes every add a second time, at the same row and column
+// of that table.  Reverse counts are total - forward and are never stored.  A pair's strand is uniform over its wave, so the second
+// atomicAdd brings no divergence; a kernel compiled without the flag never reads this struct.
+struct PileupStrandArgs {
+  const uint8_t* reverse;    // [npairs] or nullptr: every pair is forward
+  int32_t* fwd;              // WFA_PILEUP_COLS planes of PileupArgs::total counters
+};
+
 int launch_pileup(const PileupArgs& a, int cu_count, hipStream_t stream);
+int launch_pileup_strands(const PileupArgs& a, const PileupStrandArgs& s, int cu_count, hipStream_t stream);
 
 }  // namespace wfa

@@ -102,6 +102,17 @@ cdef extern from "wfa_hip.h" nogil:
     int wfa_hip_place_host(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse, const int32_t* score,
                             const int32_t* status, const int32_t* text_start, const int32_t* text_end, int32_t min_score,
                             int32_t full_gap, int32_t* rows, uint8_t* flags, char* msg, size_t msg_cap)
+    # per-strand counts and genotyped sites of a pileup (include/wfa_hip.h: "strands and genotypes")
+    int wfa_hip_pileup_track_strands(wfa_hip_pileup_t* pileup, int on)
+    int wfa_hip_pileup_add_strands(wfa_hip_pileup_t* pileup, wfa_hip_batch_t* batch, const int32_t* j, const int32_t* t_start,
+                                   const uint8_t* keep, const uint8_t* reverse)
+    int wfa_hip_pileup_read_strand(wfa_hip_pileup_t* pileup, int32_t seq, int64_t start, int64_t len, int strand, int32_t* counts)
+    int wfa_hip_pileup_genotypes(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                 int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
+                                 int64_t* count, int32_t* rows)
+    int wfa_hip_genotypes_host(const int32_t* counts, const int32_t* counts_fwd, const uint8_t* ref, int64_t len, int32_t seq,
+                               int64_t start, int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
+                               int64_t* count, int32_t* rows)
     # pairing: one row per fragment of two reads (include/wfa_hip.h: "pairing")
     int wfa_hip_placer_run_pairs(wfa_hip_placer_t* placer, int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert,
                             int32_t unpaired, int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int32_t* rows, uint8_t* flags,
