@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import common
+import corpus_common
 from oracle import loader
 from pywfa_amd import datagen
 
@@ -81,14 +82,7 @@ def corpora():
     out["special"] = vo.corpus_special(seed=99)   # empty / length-1 / N / repeats / long gaps / windows
     # (every configuration meets the edge cases whatever the sampling below skips — 64 pairs of the special corpus: the
     # empty / length-1 / identical / unrelated block, then homopolymers, two-letter reads, reads with N, long gaps, windows)
-    sp = out["special"]
-    n_sp = len(sp["p_len"])
-    pick = list(range(27)) + [27 + 30 * i for i in range(10)] + [327 + 33 * i for i in range(6)] + [527 + 12 * i for i in range(8)] + \
-           [627 + 25 * i for i in range(8)] + [827 + 40 * i for i in range(5)]
-    pick = [i for i in pick if i < n_sp]
-    pats = [bytes(sp["seqs"][sp["p_off"][i]:sp["p_off"][i] + sp["p_len"][i]]).decode() for i in pick]
-    txts = [bytes(sp["seqs"][sp["t_off"][i]:sp["t_off"][i] + sp["t_len"][i]]).decode() for i in pick]
-    out["special_mini"] = datagen.from_strings(pats, txts)
+    out["special_mini"] = corpus_common.special_mini(out["special"])
     return out
 
 

@@ -8,26 +8,11 @@ import numpy as np
 import pytest
 
 import common
+from corpus_common import ragged_batch
 from oracle import loader
 from pywfa_amd import _native, datagen
 
 pytestmark = pytest.mark.gpu
-
-
-def ragged_batch(n, length, error, seed):
-    """`n` pairs of about `length` bases with length differences, a few short / empty ones mixed in."""
-    rng = np.random.default_rng(seed)
-    b = datagen.generate(n, length, error, seed)
-    pats, txts = [], []
-    for i in range(n):
-        p, t = datagen.pair_strings(b, i)
-        k = i % 9
-        if k == 1: p = p[:len(p) - int(rng.integers(1, 200))]
-        if k == 2: t = t[int(rng.integers(1, 200)):]
-        if k == 3: p = p[:int(rng.integers(0, 40))]
-        if k == 4 and i % 36 == 4: p, t = "", t[:17]
-        pats.append(p); txts.append(t)
-    return datagen.from_strings(pats, txts)
 
 
 CASES = [
