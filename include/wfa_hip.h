@@ -543,8 +543,8 @@ int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uint8_t* patte
  * Sites come out in ascending (j, pos), always: the order does not depend on scheduling, two calls give identical rows.
  *
  * A site says that, and how often, reads insert in front of a base; WHAT they insert is the allele row of "insertions" below, from a
- * pileup made to track them; per-strand counts and a diploid genotype per site: "strands and genotypes" below.  Out of scope: quality
- * values and multi-base events; more than one alternate allele per site, ploidy other than 2, a Fisher or other strand statistic (the
+ * pileup made to track them; per-strand counts and a diploid genotype per site: "strands and genotypes" below; base
+ * qualities: "base qualities" below.  Out of scope: multi-base events; more than one alternate allele per site, ploidy other than 2, a Fisher or other strand statistic (the
  * four counts are returned; the test is the caller's).
  *
  * The pileup keeps no reference letters and outlives its set, so both device calls take the set: the one the pileup was made over, or
@@ -623,7 +623,7 @@ int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, i
  * although the rule needs no letters, so the call shape matches), with min_permille in 0..1000; a pileup that does not track ("... was
  * not made to track insertions"); bases_cap < 0; a NULL count or bases_count; NULL bases with bases_cap > 0.
  *
- * Out of scope: quality values and multi-base events; more than one alternate allele per site (here: per row), ploidy other than 2, a
+ * Out of scope: multi-base events; more than one alternate allele per site (here: per row), ploidy other than 2, a
  * Fisher or other strand statistic (the four counts are returned; the test is the caller's).  The log keeps no strand per record
  * ("strands and genotypes" below counts strands per base).  Reads that place the same inserted bases at
  * different rows of a repeat are different records at different rows: left-align the batch first ("left alignment" below), which puts
@@ -710,8 +710,8 @@ int wfa_hip_insertions_host(const int32_t* counts, int64_t len, int32_t seq, int
  * WFA_HIP_EINVAL, nothing launched, nothing written (wfa_hip_last_error names the values): whatever wfa_hip_pileup_sites refuses;
  * err_q outside 1..60; min_alt_strand < 0; min_alt_strand > 0 on a pileup that does not track strands.
  *
- * Out of scope: quality values and multi-base events; more than one alternate allele per site, ploidy other than 2, a Fisher or other
- * strand statistic (the four counts are returned; the test is the caller's).
+ * Out of scope: multi-base events; more than one alternate allele per site, ploidy other than 2, a Fisher or other strand statistic
+ * (the four counts are returned; the test is the caller's).  Base qualities in the costs: "base qualities" below.
  */
 #define WFA_HIP_GENOTYPE_COLS 16  /* the 8 of a site, gt, gq, ins_gt, ins_gq, depth_fwd, ref_fwd, alt_fwd, ins_fwd */
 int wfa_hip_pileup_track_strands(wfa_hip_pileup_t* pileup, int on);
@@ -731,6 +731,90 @@ int wfa_hip_pileup_genotypes(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* t
 int wfa_hip_genotypes_host(const int32_t* counts, const int32_t* counts_fwd /* nullable */, const uint8_t* ref, int64_t len, int32_t seq,
                            int64_t start, int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
                            int64_t* count, int32_t* rows);
+
+/* ---- base qualities: a quality filter, quality sums per base, quality-weighted genotypes ------------------- */
+
+/*
+ * A FASTQ record's fourth line says how far each base is to be trusted.  A pileup that tracks qualities leaves bases under a threshold
+ * out and sums the qualities of those it counts, and the genotype of a site is then charged what its contradicting reads really
+ * cost.  Everything here is opt-in: a pileup that does not ask for it behaves, allocates and launches exactly as before.
+ *
+ * QUALITY SET.  wfa_hip_qualset_create uploads one byte per base of the sequences of `reads`, RAW PHRED (0 .. WFA_HIP_MAX_QUALITY;
+ * not phred + 33), once: entry k is quals[off[k] .. off[k] + len[k]) and belongs to sequence k of `reads`.  Refused (NULL,
+ * WFA_HIP_EINVAL as far as an error code goes, nothing allocated; wfa_hip_last_error names the first offending entry): a set of
+ * another aligner; a missing pointer; a negative offset; len[k] other than the length of sequence k; a value above 93.  The set keeps
+ * the lengths and outlives `reads`.
+ *
+ * RULE.  The quality of pattern position v of pair q is the stored read's, seen through the pair's window: with r = i[q],
+ * s = p_start[q] (NULL: 0) and n the pair's pattern length,
+ *   Q(v)  = quals[r][reverse[q] ? s + n - 1 - v : s + v]            (the arrays given to wfa_hip_batch_create_windows are exactly these)
+ *   Qc(v) = min(Q(v), quality_cap)
+ * with the parameters min_base_quality in 0 .. 93 and quality_cap in 1 .. 93 of the add.  The walk is that of wfa_hip_pileup_add: the
+ * same core, the same v, h and g.  ONE THING CHANGES: an M or X with Q(v) < min_base_quality adds NOTHING, no letter and no mismatch,
+ * to any table.  I ops and D runs count as they do there, whatever the qualities.  So the sum of columns 0..5 is the number of
+ * contributing reads whose aligned core covers the base WITH A BASE THAT PASSED THE FILTER OR WITH A DELETION, which is the depth the
+ * calls, sites and genotypes then see.  ONE TABLE IS ADDED, the QUALITY TABLE: the same 8 planes, plane stride and layout, 32 MORE
+ * BYTES PER TEXT BASE, int32 and not checked for overflow, as the counts are:
+ *   M that passes   +Qc(v) to the letter's column
+ *   X that passes   +Qc(v) to the letter's column and to column 7
+ *   I               +min(Qc(v - 1), Qc(v)) to column 5: the read bases on either side of the text base the read lacks (an index outside
+ *                   [0, n) is left out of the min; the core's first and last M make at least one exist)
+ *   D run           +Qc(v) of its first inserted base to column 6, at the row where the run is counted
+ * With min_base_quality = 0 the count table is byte for byte that of wfa_hip_pileup_add on the same list.
+ *
+ * wfa_hip_pileup_track_qualities turns tracking on or off, only while the pileup is empty, as wfa_hip_pileup_track_strands; on
+ * allocates the zeroed quality table (a failed allocation: WFA_HIP_EDEVICE, the message names the byte count, the pileup unchanged),
+ * off frees it.  wfa_hip_pileup_clear keeps the setting and zeroes the table.  Quality, strand and insertion tracking are independent.
+ *
+ * wfa_hip_pileup_add_quals is the add of a pileup that tracks qualities, with or without strands: `reverse` is the strand array in
+ * both (it orients the qualities, and with strand tracking a pair with reverse[q] == 0 repeats its count adds, filter included, in
+ * the forward table; there is no forward quality table).  The insertion log is unaffected: records are written whatever the
+ * qualities.  WFA_HIP_EINVAL, nothing launched (the message names the first offending list position): whatever wfa_hip_pileup_add
+ * refuses; a pileup that does not track qualities; a quality set of another aligner; a missing i; i[q] outside the set; a negative
+ * p_start[q]; p_start[q] + plen[q] behind the read's end; min_base_quality outside 0..93; quality_cap outside 1..93.
+ * wfa_hip_pileup_add and wfa_hip_pileup_add_strands on a pileup that tracks qualities are refused, the message names this call.
+ * Kernel: k_pileup.hip, the table kernel compiled with a QUALS flag: one byte load per lane (two on an I), ascending over the wave
+ * for a forward pair, descending for a reverse one, and one more atomicAdd per add.  18 bytes per pair uploaded.
+ *
+ * wfa_hip_pileup_read_quality is wfa_hip_pileup_read for the quality table (the same checks, and a pileup that does not track).
+ *
+ * QUALITY-WEIGHTED GENOTYPES.  wfa_hip_pileup_genotypes_quals takes the arguments of wfa_hip_pileup_genotypes and has its SITE
+ * selection, min_alt_strand filter, row layout, count / scan / scatter and order.  Only the three costs of an event change, qsum being
+ * the base's row of the quality table:
+ *   SNV or deletion event:  L0 = qsum[alt]      L1 = 3 * (R + A)      L2 = qsum[r]
+ *   insertion event:        L0 = qsum[6]        L1 = 3 * (R + A)      L2 = err_q * R
+ * (R, A as in GENOTYPE.)  A read that does not insert has no base to take a quality from, so the insertion's L2 keeps the constant.
+ * 64-bit arithmetic, gq capped at 99.  The quality planes are read only at bases that are reported.  Refused as
+ * wfa_hip_pileup_genotypes, and on a pileup that does not track qualities.
+ *
+ * Out of scope: mapping qualities in the costs, a prior, recalibration; multi-base events.
+ */
+#define WFA_HIP_MAX_QUALITY 93
+typedef struct wfa_hip_qualset wfa_hip_qualset_t;  /* the base qualities of a sequence set, resident in HBM */
+wfa_hip_qualset_t* wfa_hip_qualset_create(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* reads, const uint8_t* quals, const int64_t* off,
+                                          const int32_t* len);
+void wfa_hip_qualset_destroy(wfa_hip_qualset_t* quals);
+int wfa_hip_pileup_track_qualities(wfa_hip_pileup_t* pileup, int on);
+int wfa_hip_pileup_add_quals(wfa_hip_pileup_t* pileup, wfa_hip_batch_t* batch, const int32_t* j, const int32_t* t_start /* nullable: 0 */,
+                             const uint8_t* keep /* nullable: all */, const uint8_t* reverse /* nullable: all forward */,
+                             const wfa_hip_qualset_t* quals, const int32_t* i, const int32_t* p_start /* nullable: 0 */,
+                             int32_t min_base_quality, int32_t quality_cap);
+int wfa_hip_pileup_read_quality(wfa_hip_pileup_t* pileup, int32_t seq, int64_t start, int64_t len, int32_t* qsums /* len x 8 */);
+int wfa_hip_pileup_genotypes_quals(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                   int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
+                                   int64_t* count, int32_t* rows /* cap x 16, nullable */);
+
+/* Host only, needs no GPU: ONE pair's contribution by the rule above, as wfa_hip_ops_pileup: quals[0 .. plen) are the qualities of
+ * pattern[0 .. plen) in the window's order (already reversed for a reverse pair); rows and qrows (tlen x 8 each) are added to.
+ * WFA_HIP_EINVAL, nothing added: what wfa_hip_ops_pileup refuses, a quality above 93, a parameter out of range. */
+int wfa_hip_ops_pileup_quals(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen, const uint8_t* quals,
+                             int32_t min_base_quality, int32_t quality_cap, int32_t* rows /* tlen x 8, added to */,
+                             int32_t* qrows /* tlen x 8, added to */);
+
+/* Host only: wfa_hip_genotypes_host with the costs above; qsums: len x 8, the rows wfa_hip_pileup_read_quality returns. */
+int wfa_hip_genotypes_quals_host(const int32_t* counts, const int32_t* qsums, const int32_t* counts_fwd /* nullable */, const uint8_t* ref,
+                                 int64_t len, int32_t seq, int64_t start, int32_t min_depth, int32_t min_permille, int32_t err_q,
+                                 int32_t min_alt_strand, int64_t cap, int64_t* count, int32_t* rows);
 
 /* ---- left alignment: gaps at the left end of their repeat, where VCF puts them ----------------------------- */
 

@@ -145,6 +145,14 @@ SIGNATURES = {
     "wfa_hip_pileup_read_strand": (_CTYPES, [_vp, _i32, _i64, _i64, _int, _vp]),
     "wfa_hip_pileup_genotypes": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64p, _vp]),
     "wfa_hip_genotypes_host": (_CTYPES, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _i64, _i64p, _vp]),
+    "wfa_hip_qualset_create": (_vp, [_vp, _vp, _vp, _vp, _vp]),
+    "wfa_hip_qualset_destroy": (None, [_vp]),
+    "wfa_hip_pileup_track_qualities": (_CTYPES, [_vp, _int]),
+    "wfa_hip_pileup_add_quals": (_CTYPES, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32]),
+    "wfa_hip_pileup_read_quality": (_CTYPES, [_vp, _i32, _i64, _i64, _vp]),
+    "wfa_hip_pileup_genotypes_quals": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64p, _vp]),
+    "wfa_hip_ops_pileup_quals": (_CTYPES, [_vp, _i64, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "wfa_hip_genotypes_quals_host": (_CTYPES, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _i64, _i64p, _vp]),
     "wfa_hip_batch_left_align": (_CTYPES, [_vp, _vp]),
     "wfa_hip_ops_left_align": (_CTYPES, [_vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "wfa_hip_placer_create": (_vp, [_vp, _i64]),
@@ -177,6 +185,7 @@ INSERTION_COLS = 8
 INSERTION_COLUMNS = ("j", "pos", "depth", "ins_count", "allele_count", "allele_len", "alleles", "overflow")
 INS_MAX_READS = 4096   # the default of WFA_HIP_INS_MAX_READS
 GENOTYPE_COLS = 16
+MAX_QUALITY = 93   # WFA_HIP_MAX_QUALITY: raw phred, the printable range of FASTQ
 GENOTYPE_COLUMNS = SITE_COLUMNS + ("gt", "gq", "ins_gt", "ins_gq", "depth_fwd", "ref_fwd", "alt_fwd", "ins_fwd")
 PLACE_COLS = 8
 PLACE_COLUMNS = ("hit", "score", "second", "mapq", "hits", "ties", "text_start", "text_end")
@@ -478,6 +487,10 @@ class Aligner(_Checked):
         """wfa_hip_pileup_create: a zeroed Pileup over the bases of a SeqSet."""
         return Pileup(self, texts)
 
+    def qualset(self, reads, quals, off, length):
+        """wfa_hip_qualset_create: the base qualities (raw phred) of the sequences of a SeqSet."""
+        return QualSet(self, reads, quals, off, length)
+
     def placer(self, nreads):
         """wfa_hip_placer_create: a Placer over reads 0 .. nreads - 1, without hits."""
         return Placer(self, nreads)
@@ -542,6 +555,31 @@ def ops_pileup(ops, pattern, tlen, rows=None):
     if rc != OK:
         raise ValueError("wfa_hip_ops_pileup: invalid arguments (an op string that outruns its pair?)")
     return rows
+
+
+def ops_pileup_quals(ops, pattern, tlen, quals, min_base_quality=0, quality_cap=40, rows=None, qrows=None):
+    """wfa_hip_ops_pileup_quals (host only): one pair's contribution to a pileup that tracks qualities; ``quals``: a raw phred value
+    per pattern base, in the window's order.  ``(rows, qrows)``, both int32 of shape (tlen, 8), added to when given."""
+    ops = np.frombuffer(bytes(ops), dtype=np.uint8) if not isinstance(ops, np.ndarray) else np.ascontiguousarray(ops, dtype=np.uint8)
+    pattern = np.frombuffer(bytes(pattern), dtype=np.uint8) if not isinstance(pattern, np.ndarray) else np.ascontiguousarray(pattern, dtype=np.uint8)
+    quals = np.ascontiguousarray(quals, dtype=np.uint8)
+    tlen = int(tlen)
+    if quals.shape != pattern.shape:
+        raise ValueError("quals: one value per pattern base")
+    out = []
+    for name, a in (("rows", rows), ("qrows", qrows)):
+        if a is None:
+            a = np.zeros((max(tlen, 0), PILEUP_COLS), np.int32)
+        if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.shape == (tlen, PILEUP_COLS) and a.flags.c_contiguous):
+            raise ValueError(f"{name}: a contiguous int32 array of shape (tlen, 8)")
+        out.append(a)
+    rc = lib().wfa_hip_ops_pileup_quals(_ptr(ops) if ops.size else None, ops.size, _ptr(pattern) if pattern.size else None, pattern.size, tlen,
+                                        _ptr(quals) if quals.size else None, int(min_base_quality), int(quality_cap),
+                                        _ptr(out[0]) if out[0].size else None, _ptr(out[1]) if out[1].size else None)
+    if rc != OK:
+        raise ValueError("wfa_hip_ops_pileup_quals: invalid arguments (an op string that outruns its pair, a quality above 93, "
+                         f"min_base_quality = {min_base_quality} outside 0 .. 93 or quality_cap = {quality_cap} outside 1 .. 93?)")
+    return out[0], out[1]
 
 
 def ops_left_align(ops, pattern, text):
@@ -670,6 +708,36 @@ def genotypes_host(counts, ref, counts_fwd=None, seq=0, start=0, min_depth=1, mi
         cap = count.value
     rows = np.zeros((max(int(cap), 0), GENOTYPE_COLS), np.int32)
     if lib().wfa_hip_genotypes_host(*args, int(cap), ctypes.byref(count), _ptr(rows) if rows.size else None) != OK:
+        raise ValueError(what)
+    return count.value, rows[:min(count.value, rows.shape[0])]
+
+
+def genotypes_quals_host(counts, qsums, ref, counts_fwd=None, seq=0, start=0, min_depth=1, min_permille=500, err_q=20, min_alt_strand=0,
+                         cap=None):
+    """wfa_hip_genotypes_quals_host (host only): ``genotypes_host`` with the costs of "base qualities"; ``qsums``: the rows of the
+    quality table (``Pileup.read_quality``), int32 of the shape of ``counts``."""
+    counts, ref = _calls_rows(counts, ref)
+    qsums = np.ascontiguousarray(qsums, dtype=np.int32)
+    if qsums.shape != counts.shape:
+        raise ValueError("qsums: int32 of the shape of counts")
+    if counts_fwd is not None:
+        counts_fwd = np.ascontiguousarray(counts_fwd, dtype=np.int32)
+        if counts_fwd.shape != counts.shape:
+            raise ValueError("counts_fwd: int32 of the shape of counts")
+        if not counts_fwd.size:
+            counts_fwd = np.zeros((1, PILEUP_COLS), np.int32)   # (tracking is told from a non-NULL pointer, even over no rows)
+    n = counts.shape[0]
+    args = (_ptr(counts) if counts.size else None, _ptr(qsums) if qsums.size else None, None if counts_fwd is None else _ptr(counts_fwd),
+            _ptr(ref) if ref.size else None, n, int(seq), int(start), int(min_depth), int(min_permille), int(err_q), int(min_alt_strand))
+    what = (f"wfa_hip_genotypes_quals_host: invalid arguments (min_depth = {min_depth}, min_permille = {min_permille}, err_q = {err_q}, "
+            f"min_alt_strand = {min_alt_strand}, cap = {cap})")
+    count = ctypes.c_int64(0)
+    if cap is None:
+        if lib().wfa_hip_genotypes_quals_host(*args, 0, ctypes.byref(count), None) != OK:
+            raise ValueError(what)
+        cap = count.value
+    rows = np.zeros((max(int(cap), 0), GENOTYPE_COLS), np.int32)
+    if lib().wfa_hip_genotypes_quals_host(*args, int(cap), ctypes.byref(count), _ptr(rows) if rows.size else None) != OK:
         raise ValueError(what)
     return count.value, rows[:min(count.value, rows.shape[0])]
 
@@ -930,6 +998,32 @@ class SeqSet(_Handle):
                       "wfa_hip_seqset_create")
 
 
+class QualSet(_Handle):
+    """The base qualities of the sequences of a SeqSet, resident in HBM (wfa_hip_qualset_t): a byte per base, raw phred 0 .. 93;
+    entry k = quals[off[k] .. +len[k]), len[k] the length of sequence k of ``reads``.  Stays valid after ``reads`` is closed."""
+
+    _destroy = "wfa_hip_qualset_destroy"
+
+    def __init__(self, aligner, reads, quals, off, length):
+        if not reads._h:
+            raise ValueError("the sequence set is closed")
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        n = length.shape[0]
+        if off.shape[0] != n or n != reads.n:
+            raise ValueError(f"quality set: one entry per sequence of the set ({reads.n})")
+        if n and (int(off.min()) < 0 or int(length.min()) < 0):
+            raise ValueError("negative length or offset")
+        if n and int((off + length).max()) > quals.size:
+            raise ValueError("quality offsets run past the blob")
+        self.aligner = aligner
+        self.n = n
+        self.length = length.copy()
+        self._created(lib().wfa_hip_qualset_create(aligner._h, reads._h, _ptr(quals) if quals.size else None, _ptr(off), _ptr(length)),
+                      "wfa_hip_qualset_create")
+
+
 class CrossRun(_Handle):
     """The results of one cross run, resident in HBM (wfa_hip_cross_t)."""
 
@@ -977,11 +1071,13 @@ class CrossRun(_Handle):
 class Pileup(_Handle):
     """Per-base counters over a text SeqSet, resident in HBM (wfa_hip_pileup_t): 32 bytes per text base, int32 counters without an
     overflow check.  Stays valid after the set is closed.  ``tracking``: whether it keeps the insertion log (``track_insertions``);
-    ``strands``: whether it keeps the forward table (``track_strands``: 32 more bytes per text base)."""
+    ``strands``: whether it keeps the forward table (``track_strands``: 32 more bytes per text base); ``qualities``: whether it keeps
+    the quality table (``track_qualities``: 32 more bytes per text base)."""
 
     _destroy = "wfa_hip_pileup_destroy"
     tracking = False
     strands = False
+    qualities = False
 
     def __init__(self, aligner, texts):
         if not texts._h:
@@ -1007,6 +1103,23 @@ class Pileup(_Handle):
         else:
             self._call("wfa_hip_pileup_add", self._h, batch._h, _ptr(j), _ptr(t_start), _ptr(keep))
 
+    def add_quals(self, batch, j, quals, i, t_start=None, keep=None, reverse=None, p_start=None, min_base_quality=0, quality_cap=40):
+        """wfa_hip_pileup_add_quals: ``add`` on a pileup that tracks qualities (with or without strands): pair q is the window from
+        ``p_start[q]`` of read ``i[q]`` of the QualSet ``quals``, reversed where ``reverse[q]``."""
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        i = np.ascontiguousarray(i, dtype=np.int32)
+        t_start = None if t_start is None else np.ascontiguousarray(t_start, dtype=np.int32)
+        p_start = None if p_start is None else np.ascontiguousarray(p_start, dtype=np.int32)
+        keep = None if keep is None else np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        reverse = None if reverse is None else np.ascontiguousarray(np.asarray(reverse) != 0, dtype=np.uint8)
+        for name, a in (("j", j), ("i", i), ("t_start", t_start), ("p_start", p_start), ("keep", keep), ("reverse", reverse)):
+            if a is not None and a.shape != (batch.n,):
+                raise ValueError(f"{name}: one value per pair of the batch ({batch.n})")
+        if not quals._h:
+            raise ValueError("the quality set is closed")
+        self._call("wfa_hip_pileup_add_quals", self._h, batch._h, _ptr(j), _ptr(t_start), _ptr(keep), _ptr(reverse), quals._h, _ptr(i),
+                   _ptr(p_start), int(min_base_quality), int(quality_cap))
+
     def _rows(self, seq, start, length):
         """``(seq, start, length)`` as ints, a ``length`` of None running to the end of the sequence."""
         seq, start = int(seq), int(start)
@@ -1025,6 +1138,13 @@ class Pileup(_Handle):
             self._call("wfa_hip_pileup_read", self._h, seq, start, length, _ptr_or_null(out))
         else:
             self._call("wfa_hip_pileup_read_strand", self._h, seq, start, length, int(strand), _ptr_or_null(out))
+        return out
+
+    def read_quality(self, seq, start=0, length=None):
+        """wfa_hip_pileup_read_quality: int32[length, 8], the rows of the quality table of a pileup that tracks qualities."""
+        seq, start, length = self._rows(seq, start, length)
+        out = np.zeros((max(length, 0), PILEUP_COLS), np.int32)
+        self._call("wfa_hip_pileup_read_quality", self._h, seq, start, length, _ptr_or_null(out))
         return out
 
     def calls(self, texts, seq, start=0, length=None, min_depth=1):
@@ -1048,17 +1168,20 @@ class Pileup(_Handle):
             self._call("wfa_hip_pileup_sites", *args, int(cap), ctypes.byref(count), _ptr_or_null(rows))
         return count.value, rows[:min(count.value, rows.shape[0])]
 
-    def genotypes(self, texts, seq=-1, start=0, length=-1, min_depth=1, min_permille=500, err_q=20, min_alt_strand=0, cap=None):
+    def genotypes(self, texts, seq=-1, start=0, length=-1, min_depth=1, min_permille=500, err_q=20, min_alt_strand=0, cap=None,
+                  qualities=False):
         """wfa_hip_pileup_genotypes: ``(count, rows)``, rows int32 of shape (min(count, cap), 16) in ascending (j, pos); ``cap`` None: a
-        counting call, then one with the exact capacity.  seq = -1: every sequence."""
+        counting call, then one with the exact capacity.  seq = -1: every sequence.  ``qualities``: wfa_hip_pileup_genotypes_quals,
+        the costs from the quality table of a pileup that tracks qualities."""
+        symbol = "wfa_hip_pileup_genotypes_quals" if qualities else "wfa_hip_pileup_genotypes"
         args = (self._h, texts._h, int(seq), int(start), int(length), int(min_depth), int(min_permille), int(err_q), int(min_alt_strand))
         count = ctypes.c_int64(0)
         if cap is None:
-            self._call("wfa_hip_pileup_genotypes", *args, 0, ctypes.byref(count), None)
+            self._call(symbol, *args, 0, ctypes.byref(count), None)
             cap = count.value
         rows = np.zeros((max(int(cap), 0), GENOTYPE_COLS), np.int32)
         if cap != 0:
-            self._call("wfa_hip_pileup_genotypes", *args, int(cap), ctypes.byref(count), _ptr_or_null(rows))
+            self._call(symbol, *args, int(cap), ctypes.byref(count), _ptr_or_null(rows))
         return count.value, rows[:min(count.value, rows.shape[0])]
 
     def clear(self):
@@ -1068,6 +1191,11 @@ class Pileup(_Handle):
         """wfa_hip_pileup_track_strands: keep (or stop keeping) the forward table; only while the pileup is empty."""
         self._call("wfa_hip_pileup_track_strands", self._h, 1 if on else 0)
         self.strands = bool(on)
+
+    def track_qualities(self, on=True):
+        """wfa_hip_pileup_track_qualities: keep (or stop keeping) the quality table; only while the pileup is empty."""
+        self._call("wfa_hip_pileup_track_qualities", self._h, 1 if on else 0)
+        self.qualities = bool(on)
 
     def track_insertions(self, on=True):
         """wfa_hip_pileup_track_insertions: keep (or stop keeping) what the reads insert; only while the pileup is empty."""

@@ -436,6 +436,17 @@ class Pileup(_Closing):
         as for ``counts``)."""
         return self.counts(j, start, stop, strand)[:, :6].sum(axis=1, dtype=np.int32)
 
+    def quality_sums(self, j, start=0, stop=None):
+        """int32 array of shape (stop - start, 8): the rows [start, stop) of text ``j`` of the QUALITY table of a pileup made with
+        ``qualities=`` (else ValueError).  The columns are those of ``counts``; a cell is the sum of min(quality, ``quality_cap``)
+        over the reads ``counts`` holds there: the base's own quality under a letter and under ``mismatch``, the smaller of the two
+        neighbouring bases' under ``del``, the first inserted base's under ``ins``."""
+        p = self._open()
+        if not p.qualities:
+            raise ValueError("this pileup was not made to track qualities: make it with pileup(..., qualities=...)")
+        seq, start, stop = self._range(p, j, start, stop)
+        return p.read_quality(seq, start, stop - start)
+
     def _range(self, p, j, start, stop):
         """The checked rows [start, stop) of text ``j`` (the wording of ``counts``)."""
         if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= int(j) < p.n:
@@ -518,7 +529,7 @@ class Pileup(_Closing):
         least ``min_frac`` of them insert (the ``ins`` condition of ``sites``; ``min_frac``, ``j``, ``start``, ``stop`` as there).  The
         allele is the inserted sequence most of the row's inserting reads carry (``allele_count`` of ``ins_count``; ties go to the
         shorter, then to the alphabetically smaller in the order A C G T N); ``alleles``: how many different ones they carry.  A row
-        with more than ``WFA_HIP_INS_MAX_READS`` (4096) inserting reads has ``overflow`` = 1, zeros and ``""``.  Qualities, multi-base
+        with more than ``WFA_HIP_INS_MAX_READS`` (4096) inserting reads has ``overflow`` = 1, zeros and ``""``.  Multi-base
         events, a strand per inserting read and more than one allele per row are out of scope."""
         p = self._tracking()
         if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
@@ -544,8 +555,8 @@ class Pileup(_Closing):
         column other than the reference's letter holds at least ``min_frac`` of the covering reads (``alt`` its column in
         ``CALL_CODES``, 5 = deleted; ``alt_count``), or where at least ``min_frac`` of them insert in front of the base (``ins_count``;
         ``alt`` = -1 and ``alt_count`` = 0 when only this holds).  ``min_frac`` is rounded to permille.  ``j=None``: every text (then
-        ``start`` / ``stop`` must be left alone); otherwise the rows [start, stop) of text ``j``.  Qualities and multi-base events are
-        out of scope; what was inserted: ``insertions``, on a pileup made with ``insertions=True``; strands and genotypes:
+        ``start`` / ``stop`` must be left alone); otherwise the rows [start, stop) of text ``j``.  Multi-base events are
+        out of scope; base qualities: ``pileup(..., qualities=)``; what was inserted: ``insertions``, on a pileup made with ``insertions=True``; strands and genotypes:
         ``genotypes``."""
         p = self._open()
         if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
@@ -561,7 +572,7 @@ class Pileup(_Closing):
         _, rows = self._with_texts(p, texts, min_depth, lambda t: p.sites(t, seq, start, length, int(min_depth), permille))
         return _columns(rows, self.SITE_COLUMNS)
 
-    def genotypes(self, texts, j=None, start=0, stop=None, min_depth=8, min_frac=0.2, err_q=20, min_alt_strand=0):
+    def genotypes(self, texts, j=None, start=0, stop=None, min_depth=8, min_frac=0.2, err_q=20, min_alt_strand=0, qualities=False):
         """The sites with a diploid genotype each, made on the GPU: a dict of int32 arrays ``GENOTYPE_COLUMNS`` in ascending (j, pos).
         The first eight are the columns of ``sites`` (same ``texts``, ``j``, ``start``, ``stop``, ``min_depth``, ``min_frac``).
         ``gt`` / ``gq``: 0, 1 or 2 copies of ``alt`` and a confidence 0..99, from ``ref_count`` and ``alt_count`` alone — the
@@ -571,9 +582,13 @@ class Pileup(_Closing):
         the site has no such event.  ``depth_fwd``, ``ref_fwd``, ``alt_fwd``, ``ins_fwd``: the forward reads among ``depth``,
         ``ref_count``, ``alt_count``, ``ins_count`` (a pileup made with ``strands=True``; -1 otherwise) — the reverse ones are the
         difference, the strand test is the caller's.  ``min_alt_strand`` > 0 (needs ``strands=True``): an event counts only when at
-        least that many reads of EACH strand carry it.  More than one alternate allele per site and ploidy other than 2 are out of
-        scope."""
+        least that many reads of EACH strand carry it.  ``qualities=True`` (a pileup made with ``qualities=``, else ValueError): the
+        costs come from ``quality_sums`` instead of ``err_q`` — the summed qualities of the alt reads (0/0) and of the ref reads
+        (1/1); for the insertion those of the inserting reads (0/0), while reads that do not insert keep ``err_q`` each (1/1).
+        More than one alternate allele per site and ploidy other than 2 are out of scope."""
         p = self._open()
+        if qualities and not p.qualities:
+            raise ValueError("qualities=True needs a pileup made to track qualities: make it with pileup(..., qualities=...)")
         if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
             raise ValueError(f"min_frac = {min_frac!r} is out of range (0.001 .. 1)")
         permille = int(round(float(min_frac) * 1000))
@@ -591,7 +606,8 @@ class Pileup(_Closing):
             seq, start, stop = self._range(p, j, start, stop)
             length = stop - start
         _, rows = self._with_texts(p, texts, min_depth,
-                                   lambda t: p.genotypes(t, seq, start, length, int(min_depth), permille, int(err_q), int(min_alt_strand)))
+                                   lambda t: p.genotypes(t, seq, start, length, int(min_depth), permille, int(err_q), int(min_alt_strand),
+                                                         qualities=bool(qualities)))
         return _columns(rows, self.GENOTYPE_COLUMNS)
 
 
@@ -610,6 +626,68 @@ class SequenceSet(_Closing):
         if self._set is None:
             raise ValueError("sequence set is closed")
         return self._set.n
+
+
+class QualitySet(_Closing):
+    """The base qualities of a set of reads kept on the GPU, a byte per base, uploaded once (``WavefrontAligner.quality_set``): pass
+    it as ``pileup(..., qualities=)`` with the reads it was made for.  ``len()`` is the number of reads; ``close()`` (or leaving the
+    ``with`` block) releases the device memory."""
+
+    _OWNS = "_set"
+
+    def __init__(self, aligner, native_set):
+        self._aligner = aligner
+        self._set = native_set
+
+    def __len__(self):
+        if self._set is None:
+            raise ValueError("quality set is closed")
+        return self._set.n
+
+
+def _quality_blob(quals, lengths, offset):
+    """The qualities of ``len(lengths)`` reads as the library takes them, (uint8 blob of raw phred, int64 offsets, int32 lengths), or
+    ValueError naming the first offending entry.  An entry: ``str`` / ``bytes`` of phred + ``offset`` (the fourth line of a FASTQ
+    record), or a uint8 array of raw phred (``offset`` plays no part)."""
+    if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or not 0 <= int(offset) <= 255 - _native.MAX_QUALITY:
+        raise ValueError(f"offset = {offset!r} is out of range (an integer, 0 .. {255 - _native.MAX_QUALITY})")
+    if isinstance(quals, (str, bytes, np.ndarray)) or not hasattr(quals, "__len__"):
+        raise ValueError("qualities must be a list with one entry per read (str, bytes or a uint8 array each)")
+    n = len(lengths)
+    if len(quals) != n:
+        raise ValueError(f"qualities has {len(quals)} entries, the reads are {n}")
+    parts = []
+    for k, q in enumerate(quals):
+        if isinstance(q, str):
+            try:
+                q = q.encode("ascii")
+            except UnicodeEncodeError:
+                raise ValueError(f"qualities[{k}] holds a character outside ASCII") from None
+        if isinstance(q, (bytes, bytearray)):
+            a = np.frombuffer(bytes(q), np.uint8).astype(np.int32) - int(offset)
+        elif isinstance(q, np.ndarray) and q.dtype == np.uint8 and q.ndim == 1:
+            a = q.astype(np.int32)
+        else:
+            raise ValueError(f"qualities[{k}] must be a str, bytes or a one-dimensional uint8 array, got {type(q).__name__}")
+        if a.shape[0] != int(lengths[k]):
+            raise ValueError(f"qualities[{k}] has {a.shape[0]} values, read {k} has {int(lengths[k])} bases")
+        bad = np.flatnonzero((a < 0) | (a > _native.MAX_QUALITY))
+        if len(bad):
+            x = int(bad[0])
+            raise ValueError(f"qualities[{k}][{x}] = {int(a[x])} is out of range (phred 0 .. {_native.MAX_QUALITY})")
+        parts.append(a.astype(np.uint8))
+    length = np.asarray(lengths, dtype=np.int32)
+    off = np.zeros(n, np.int64)
+    if n:
+        off[1:] = np.cumsum(length[:-1], dtype=np.int64)
+    blob = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    return blob, off, length
+
+
+def _quality_param(name, value, lo):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= _native.MAX_QUALITY:
+        raise ValueError(f"{name} = {value!r} is out of range (an integer, {lo} .. {_native.MAX_QUALITY})")
+    return int(value)
 
 
 def _seed_param(name, value, lo, hi=None):
@@ -1023,6 +1101,31 @@ class WavefrontAligner:
         self._sync_wildcard()
         return SequenceSet(self, self._seqset(seqs))
 
+    def _read_lengths(self, patterns):
+        """The lengths of ``patterns`` (a list of ``str`` or a ``SequenceSet`` of this aligner, open)."""
+        if isinstance(patterns, SequenceSet):
+            if patterns._aligner is not self:
+                raise ValueError("sequence set of another aligner")
+            if patterns._set is None or not patterns._set._h:
+                raise ValueError("sequence set is closed")
+            return patterns._set.length
+        return np.fromiter((len(s) for s in patterns), np.int32, len(patterns))
+
+    def quality_set(self, patterns, quals, offset=33):
+        """Upload the base qualities of the reads ``patterns`` (a ``SequenceSet`` or a list of ``str``) once and keep them on the
+        GPU: a ``QualitySet`` (``len()``, ``close()``, context manager) for ``pileup(..., qualities=)``.  ``quals``: one entry per
+        read, a ``str`` or ``bytes`` of phred + ``offset`` as in FASTQ, or a uint8 array of raw phred (``offset`` ignored); one
+        value per base, phred 0 .. 93.  ValueError, before anything is uploaded, names the first offending entry."""
+        if not isinstance(patterns, (SequenceSet, list)):
+            patterns = list(patterns)
+        blob, off, length = _quality_blob(quals, self._read_lengths(patterns), offset)
+        sets, mine = self._open_sets(patterns, None)
+        try:
+            return QualitySet(self, self._native.qualset(sets[0], blob, off, length))
+        finally:
+            for s in mine:
+                s.close()
+
     def seed_index(self, texts, k=13, stride=1, max_occ=64, w=None):
         """Index the k-mers of ``texts`` (a list of ``str`` or a ``SequenceSet``) on the GPU: a ``SeedIndex`` (``seeds()``,
         ``stats()``, ``close()``, context manager), the seed source of ``align_windows`` / ``pileup`` for reads without an index of
@@ -1366,7 +1469,8 @@ class WavefrontAligner:
             return w.run(summary=summary, left_align=bool(left_align))
 
     def pileup(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
-               text_len=None, reverse=None, min_score=None, insertions=False, left_align=False, strands=False):
+               text_len=None, reverse=None, min_score=None, insertions=False, left_align=False, strands=False, qualities=None,
+               min_base_quality=0, quality_cap=40):
         """Align the listed windows as ``align_windows`` does (same arguments, same checks; scope must be "full") and pile the
         alignments up over the TEXT sequences on the GPU: the patterns are reads, the texts references.  Every pair whose status is
         0 (and whose score is at least ``min_score``, when given) adds the ops of its aligned core — first M to last M — to the
@@ -1380,26 +1484,66 @@ class WavefrontAligner:
         ``strands=True``: the pileup also counts the forward reads (``reverse[q]`` == 0; every read when ``reverse`` is None) in a
         second table of 32 more bytes per text base, for ``counts(strand=...)`` and the strand columns and filter of
         ``Pileup.genotypes``; without it nothing more is allocated or launched.
+        ``qualities``: the reads' base qualities, a ``QualitySet`` made for ``patterns`` or what ``quality_set`` takes (a list of
+        FASTQ-style ``str`` / ``bytes`` at offset 33, or of uint8 arrays of raw phred).  A read base whose quality is under
+        ``min_base_quality`` (0 .. 93) is not counted at all, neither under its letter nor as a mismatch; deletions and insertions
+        count whatever the qualities.  A third table of 32 more bytes per text base sums min(quality, ``quality_cap``) (1 .. 93)
+        of what is counted, for ``Pileup.quality_sums`` and ``Pileup.genotypes(qualities=True)``.  It combines freely with
+        ``insertions``, ``strands``, ``left_align`` and ``min_score``; ``min_base_quality`` / ``quality_cap`` without
+        ``qualities`` are a ValueError.
 
         Returns a ``Pileup`` (``score``, ``status``, ``counts(j)``, ``depth(j)``, ``calls()``, ``consensus()``, ``sites()``,
-        ``genotypes()``, ``insertions()``, ``close()``; a context manager), which stays
+        ``genotypes()``, ``insertions()``, ``quality_sums(j)``, ``close()``; a context manager), which stays
         valid after the sets are closed.  With ``devices=[...]`` the first device runs it."""
         if self._cfg.scope != 1:
             raise ValueError("pileup needs scope='full'")
         if min_score is not None and (isinstance(min_score, bool) or not isinstance(min_score, (int, np.integer))):
             raise ValueError(f"min_score must be an integer or None, got {min_score!r}")
-        with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
-            jj, ts = w.arrays[1], w.arrays[4]
+        if qualities is None:
+            if min_base_quality != 0 or quality_cap != 40:
+                raise ValueError("min_base_quality and quality_cap go with qualities=: this pileup was asked for without base qualities")
+        else:
+            min_base_quality = _quality_param("min_base_quality", min_base_quality, 0)
+            quality_cap = _quality_param("quality_cap", quality_cap, 1)
+        w = self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
+        qblob = None
+        if isinstance(qualities, QualitySet):
+            if qualities._aligner is not self:
+                raise ValueError("quality set of another aligner")
+            if qualities._set is None or not qualities._set._h:
+                raise ValueError("quality set is closed")
+            have = self._read_lengths(w._patterns)
+            if qualities._set.n != len(have) or not np.array_equal(qualities._set.length, have):
+                raise ValueError(f"the quality set was made for other reads: {qualities._set.n} entries for {len(have)} patterns, or "
+                                 "lengths that differ")
+        elif qualities is not None:
+            qblob = _quality_blob(qualities, self._read_lengths(w._patterns), 33)
+        with w:
+            ii, jj, ps, ts = w.arrays[0], w.arrays[1], w.arrays[2], w.arrays[4]
             table = w.attach(self._native.pileup(w.text_set), keep=True)
             rev = w.arrays[6]
             if insertions:
                 table.track_insertions(True)
             if strands:
                 table.track_strands(True)
+            qset = None
+            if qualities is not None:
+                table.track_qualities(True)
+                if qblob is None:
+                    qset = qualities._set
+                else:
+                    qset = self._native.qualset(w.pset, *qblob)
+                    w._mine.append(qset)   # (this call's upload: closed with the sets when the body is left)
+
+            def cut(a, lo, hi):
+                return None if a is None else a[lo:hi]
 
             def add(rb, lo, hi, score, status):
                 keep = None if min_score is None else (score >= int(min_score))
-                if strands:
+                if qset is not None:
+                    table.add_quals(rb, jj[lo:hi], qset, ii[lo:hi], cut(ts, lo, hi), keep, cut(rev, lo, hi), cut(ps, lo, hi),
+                                    min_base_quality, quality_cap)
+                elif strands:
                     table.add(rb, jj[lo:hi], None if ts is None else ts[lo:hi], keep, None if rev is None else rev[lo:hi])
                 else:
                     table.add(rb, jj[lo:hi], None if ts is None else ts[lo:hi], keep)

@@ -54,6 +54,9 @@ struct wfa_hip_pileup {
   // strands (include/wfa_hip.h, "strands and genotypes"): the forward table, of the table's size and layout, while tracking is on
   bool strands = false;
   int32_t* d_fwd = nullptr;
+  // base qualities (include/wfa_hip.h, "base qualities"): the quality table, of the table's size and layout, while tracking is on
+  bool quals = false;
+  int32_t* d_qtab = nullptr;
 };
 
 static size_t pileup_table_bytes(const wfa_hip_pileup* p) { return (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t); }
@@ -64,6 +67,7 @@ extern "C" void wfa_hip_pileup_destroy(wfa_hip_pileup_t* p) {
   (void)hipSetDevice(al->device);
   if (p->d_table) (void)hipFree(p->d_table);
   if (p->d_fwd) (void)hipFree(p->d_fwd);
+  if (p->d_qtab) (void)hipFree(p->d_qtab);
   if (p->d_rec) (void)hipFree(p->d_rec);
   if (p->d_ins) (void)hipFree(p->d_ins);
   pool_release(al, p->d_off); pool_release(al, p->d_len);
@@ -105,6 +109,7 @@ extern "C" int wfa_hip_pileup_clear(wfa_hip_pileup_t* p) {
   HIP_TRY(al, hipSetDevice(al->device));
   HIP_TRY(al, hipMemsetAsync(p->d_table, 0, pileup_table_bytes(p), al->stream));
   if (p->d_fwd) HIP_TRY(al, hipMemsetAsync(p->d_fwd, 0, pileup_table_bytes(p), al->stream));
+  if (p->d_qtab) HIP_TRY(al, hipMemsetAsync(p->d_qtab, 0, pileup_table_bytes(p), al->stream));
   HIP_TRY(al, hipStreamSynchronize(al->stream));
   p->nrec = p->nins = 0;   // (the log's blocks stay for the next adds)
   p->added = false;
@@ -118,27 +123,38 @@ extern "C" int wfa_hip_pileup_track_insertions(wfa_hip_pileup_t* p, int on) {
   return WFA_HIP_OK;
 }
 
-extern "C" int wfa_hip_pileup_track_strands(wfa_hip_pileup_t* p, int on) {
-  if (!p) return WFA_HIP_EINVAL;
+// a second table of the table's size and layout (`what`: "forward" or "quality"; `kind`: "strand" or "quality") kept or dropped, only
+// while the pileup is empty; a failure leaves the pileup as it was
+static int pileup_track_table(wfa_hip_pileup* p, int on, int32_t** table, bool* tracking, const char* what, const char* kind) {
   wfa_hip_aligner* al = p->al;
-  if (p->added) return fail_inval(al, "pileup: strand tracking is chosen while the pileup is empty (fresh, or just cleared); this one has been added to");
-  if ((on != 0) == p->strands) return WFA_HIP_OK;
+  if (p->added) return fail_inval(al, "pileup: %s tracking is chosen while the pileup is empty (fresh, or just cleared); this one has been added to", kind);
+  if ((on != 0) == *tracking) return WFA_HIP_OK;
   HIP_TRY(al, hipSetDevice(al->device));
   if (!on) {
     HIP_TRY(al, hipStreamSynchronize(al->stream));
-    (void)hipFree(p->d_fwd);
-    p->d_fwd = nullptr; p->strands = false;
+    (void)hipFree(*table);
+    *table = nullptr; *tracking = false;
     return WFA_HIP_OK;
   }
   const size_t bytes = pileup_table_bytes(p);
-  int32_t* fwd = nullptr;
-  if (hipMalloc((void**)&fwd, bytes) != hipSuccess)
-    return fail_alloc(al, (void**)&fwd, "pileup forward table: hipMalloc of %zu bytes failed (32 more bytes per text base, %lld bases)", bytes, (long long)p->total);
-  const hipError_t e = hipMemsetAsync(fwd, 0, bytes, al->stream);
+  int32_t* fresh = nullptr;
+  if (hipMalloc((void**)&fresh, bytes) != hipSuccess)
+    return fail_alloc(al, (void**)&fresh, "pileup %s table: hipMalloc of %zu bytes failed (32 more bytes per text base, %lld bases)", what, bytes, (long long)p->total);
+  const hipError_t e = hipMemsetAsync(fresh, 0, bytes, al->stream);
   const hipError_t e2 = hipStreamSynchronize(al->stream);
-  if (e != hipSuccess || e2 != hipSuccess) { (void)hipFree(fwd); HIP_TRY(al, e); HIP_TRY(al, e2); }
-  p->d_fwd = fwd; p->strands = true;
+  if (e != hipSuccess || e2 != hipSuccess) { (void)hipFree(fresh); HIP_TRY(al, e); HIP_TRY(al, e2); }
+  *table = fresh; *tracking = true;
   return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_track_strands(wfa_hip_pileup_t* p, int on) {
+  if (!p) return WFA_HIP_EINVAL;
+  return pileup_track_table(p, on, &p->d_fwd, &p->strands, "forward", "strand");
+}
+
+extern "C" int wfa_hip_pileup_track_qualities(wfa_hip_pileup_t* p, int on) {
+  if (!p) return WFA_HIP_EINVAL;
+  return pileup_track_table(p, on, &p->d_qtab, &p->quals, "quality", "quality");
 }
 
 extern "C" int wfa_hip_pileup_insertion_stats(wfa_hip_pileup_t* p, int64_t* records, int64_t* bases) {
@@ -173,7 +189,8 @@ template <class T> static int ins_log_grow(wfa_hip_aligner* al, T** block, int64
 
 // An add with tracking on (csrc/wfa_insertions.hpp): count, the two scans, the 16-byte download, the growth, then the table kernel in its
 // tracking form.  Nothing is added before the log has its room.
-static int pileup_add_tracked(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a, const wfa::PileupStrandArgs* s) {
+static int pileup_add_tracked(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a, const wfa::PileupStrandArgs* s,
+                              const wfa::PileupQualArgs* u = nullptr) {
   wfa_hip_aligner* al = p->al;
   const size_t n = (size_t)a.npairs;
   wfa::InsLogArgs g;
@@ -196,19 +213,40 @@ static int pileup_add_tracked(wfa_hip_pileup* p, StreamScratch& sc, const wfa::P
   g.rec_base = p->nrec; g.base_base = p->nins; g.rec_cap = p->cap_rec; g.base_cap = p->cap_ins;
   ReduceTimer timer(al, "pileup tracked", a.npairs);
   p->added = true;
-  rc = launch_end(al, &timer, s ? wfa::launch_pileup_track_strands(a, g, *s, al->cu_count, al->stream) : wfa::launch_pileup_track(a, g, al->cu_count, al->stream),
+  rc = launch_end(al, &timer,
+                  u   ? wfa::launch_pileup_track_quals(a, g, s, *u, al->cu_count, al->stream)
+                  : s ? wfa::launch_pileup_track_strands(a, g, *s, al->cu_count, al->stream)
+                      : wfa::launch_pileup_track(a, g, al->cu_count, al->stream),
                   "pileup kernel launch failed");
   if (rc == WFA_HIP_OK) { p->nrec += (int64_t)totals[0]; p->nins += (int64_t)totals[1]; }
   return rc;
 }
 
-// the two adds: `stranded` is the entry (wfa_hip_pileup_add_strands), which must match the pileup's setting
+// what an add with qualities takes on top of the strands' (wfa_hip_pileup_add_quals)
+struct PileupQualList {
+  const wfa_hip_qualset_t* set; const int32_t* i; const int32_t* p_start;
+  int32_t min_base_quality, quality_cap;
+};
+
+// the three adds: `stranded` is the entry (wfa_hip_pileup_add_strands), which must match the pileup's setting; `ql` that of
+// wfa_hip_pileup_add_quals, which serves a pileup that tracks qualities with and without strands
 static int pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep, const uint8_t* reverse,
-                      bool stranded) {
+                      bool stranded, const PileupQualList* ql = nullptr) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
   int rc = batch_of(al, b, "pileup", true);
   if (rc != WFA_HIP_OK) return rc;
+  if (ql && !p->quals) return fail_inval(al, "pileup: this pileup was not made to track qualities (wfa_hip_pileup_track_qualities)");
+  if (!ql && p->quals)
+    return fail_inval(al, "pileup: this pileup tracks qualities; add to it with wfa_hip_pileup_add_quals, which takes the quality set and the pairs' reads");
+  if (ql) {
+    stranded = p->strands;
+    if (!ql->set || ql->set->al != al) return fail_inval(al, "quality set of another aligner");
+    if (ql->min_base_quality < 0 || ql->min_base_quality > WFA_HIP_MAX_QUALITY)
+      return fail_inval(al, "pileup: min_base_quality = %d is out of range (0 .. %d)", (int)ql->min_base_quality, WFA_HIP_MAX_QUALITY);
+    if (ql->quality_cap < 1 || ql->quality_cap > WFA_HIP_MAX_QUALITY)
+      return fail_inval(al, "pileup: quality_cap = %d is out of range (1 .. %d)", (int)ql->quality_cap, WFA_HIP_MAX_QUALITY);
+  }
   if (stranded && !p->strands) return fail_inval(al, "pileup: this pileup was not made to track strands (wfa_hip_pileup_track_strands); add to it with wfa_hip_pileup_add");
   if (!stranded && p->strands) return fail_inval(al, "pileup: this pileup tracks strands; add to it with wfa_hip_pileup_add_strands, which takes the pairs' strands");
   const int64_t n = b->n;
@@ -222,6 +260,18 @@ static int pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j,
     if (ts + tl > have)
       return fail_inval(al, "pileup: text window out of range at position %lld of the pair list: [%lld, %lld + %lld) of sequence %d (%lld bases)",
                         (long long)q, (long long)ts, (long long)ts, (long long)tl, (int)j[q], (long long)have);
+  }
+  if (ql && n > 0 && !ql->i) return fail_inval(al, "pileup: the read indices are missing");
+  for (int64_t q = 0; ql && q < n; ++q) {
+    const int32_t r = ql->i[q];
+    if (r < 0 || r >= ql->set->n)
+      return fail_inval(al, "pileup: read index out of range at position %lld of the pair list: i = %d over a quality set of %lld reads",
+                        (long long)q, (int)r, (long long)ql->set->n);
+    const int64_t ps = ql->p_start ? ql->p_start[q] : 0, pl = b->h_plen[(size_t)q], have = ql->set->h_len[(size_t)r];
+    if (ps < 0) return fail_inval(al, "pileup: negative pattern start at position %lld of the pair list: p_start = %lld", (long long)q, (long long)ps);
+    if (ps + pl > have)
+      return fail_inval(al, "pileup: pattern window out of range at position %lld of the pair list: [%lld, %lld + %lld) of read %d (%lld qualities)",
+                        (long long)q, (long long)ps, (long long)ps, (long long)pl, (int)r, (long long)have);
   }
   rc = wfa_hip_batch_sync(b);
   if (rc != WFA_HIP_OK) return rc;
@@ -239,6 +289,18 @@ static int pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j,
   a.npairs = n; a.j = d_j; a.t_start = d_ts; a.keep = d_keep;
   a.seq_off = p->d_off; a.seq_len = p->d_len; a.nseq = p->nseq; a.total = p->total; a.table = p->d_table;
   const wfa::PileupStrandArgs s{d_rev, p->d_fwd};
+  if (ql) {
+    int32_t *d_i = nullptr, *d_ps = nullptr;
+    if (!stranded && sc.upload_opt(&d_rev, reverse, (size_t)n)) return WFA_HIP_EDEVICE;
+    if (sc.upload(&d_i, ql->i, (size_t)n) || sc.upload_opt(&d_ps, ql->p_start, (size_t)n)) return WFA_HIP_EDEVICE;
+    const wfa::PileupStrandArgs sq{d_rev, p->d_fwd};
+    const wfa::PileupQualArgs u{ql->set->d_quals, ql->set->d_off, ql->set->d_len, ql->set->n, d_i, d_ps, d_rev,
+                                ql->min_base_quality, ql->quality_cap, p->d_qtab};
+    if (p->track) return pileup_add_tracked(p, sc, a, stranded ? &sq : nullptr, &u);
+    ReduceTimer timer(al, "pileup qualities", n);
+    p->added = true;
+    return launch_end(al, &timer, wfa::launch_pileup_quals(a, stranded ? &sq : nullptr, u, al->cu_count, al->stream), "pileup kernel launch failed");
+  }
   if (p->track) return pileup_add_tracked(p, sc, a, stranded ? &s : nullptr);
   if (stranded) {
     ReduceTimer timer(al, "pileup stranded", n);
@@ -259,6 +321,13 @@ extern "C" int wfa_hip_pileup_add_strands(wfa_hip_pileup_t* p, wfa_hip_batch_t* 
   return pileup_add(p, b, j, t_start, keep, reverse, true);
 }
 
+extern "C" int wfa_hip_pileup_add_quals(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep,
+                                        const uint8_t* reverse, const wfa_hip_qualset_t* quals, const int32_t* i, const int32_t* p_start,
+                                        int32_t min_base_quality, int32_t quality_cap) {
+  const PileupQualList ql{quals, i, p_start, min_base_quality, quality_cap};
+  return pileup_add(p, b, j, t_start, keep, reverse, false, &ql);
+}
+
 // rows [start, start + len) of sequence seq are rows of the pileup, or the refusal that names them
 static int pileup_check_rows(const wfa_hip_pileup* p, int32_t seq, int64_t start, int64_t len) {
   if (seq >= 0 && seq < p->nseq && start >= 0 && len >= 0 && start + len <= p->h_len[(size_t)seq]) return WFA_HIP_OK;
@@ -274,16 +343,17 @@ static int pileup_fetch_planes(const wfa_hip_pileup* p, const int32_t* table, in
   return WFA_HIP_OK;
 }
 
-extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int32_t* counts) {
-  if (!p) return WFA_HIP_EINVAL;
+// the rows of one table, interleaved; `table` null: `missing` is the refusal
+static int pileup_read_table(wfa_hip_pileup_t* p, const int32_t* table, const char* missing, int32_t seq, int64_t start, int64_t len, int32_t* counts) {
   wfa_hip_aligner* al = p->al;
   if (pileup_check_rows(p, seq, start, len) != WFA_HIP_OK) return WFA_HIP_EINVAL;
+  if (!table) return fail_inval(al, "%s", missing);
   if (len == 0) return WFA_HIP_OK;
   if (!counts) return fail_inval(al, "pileup: null output");
   HIP_TRY(al, hipSetDevice(al->device));
   // the table is a plane per column: one copy per plane, interleaved into rows on the host
   std::vector<int32_t> plane((size_t)len * WFA_PILEUP_COLS);
-  const int rc = pileup_fetch_planes(p, p->d_table, seq, start, len, plane.data());
+  const int rc = pileup_fetch_planes(p, table, seq, start, len, plane.data());
   if (rc != WFA_HIP_OK) return rc;
   HIP_TRY(al, hipStreamSynchronize(al->stream));
   for (int c = 0; c < WFA_PILEUP_COLS; ++c) {
@@ -291,6 +361,16 @@ extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t sta
     for (int64_t r = 0; r < len; ++r) counts[r * WFA_PILEUP_COLS + c] = src[r];
   }
   return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_read(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int32_t* counts) {
+  if (!p) return WFA_HIP_EINVAL;
+  return pileup_read_table(p, p->d_table, "pileup: no table", seq, start, len, counts);
+}
+
+extern "C" int wfa_hip_pileup_read_quality(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int32_t* qsums) {
+  if (!p) return WFA_HIP_EINVAL;
+  return pileup_read_table(p, p->quals ? p->d_qtab : nullptr, "pileup: this pileup was not made to track qualities", seq, start, len, qsums);
 }
 
 extern "C" int wfa_hip_pileup_read_strand(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int strand, int32_t* counts) {
@@ -423,14 +503,15 @@ extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t*
 // ---- genotyped sites (include/wfa_hip.h, "strands and genotypes"; csrc/wfa_calls.hpp, k_calls.hip) -----------------------------------
 static_assert(WFA_GENOTYPE_COLS == WFA_HIP_GENOTYPE_COLS, "columns of the kernels and of the ABI");
 
-extern "C" int wfa_hip_pileup_genotypes(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
-                                        int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
-                                        int64_t* count, int32_t* rows) {
+// the two genotype calls: `quals` is the entry (wfa_hip_pileup_genotypes_quals), whose scatter pass takes the costs from the quality table
+static int pileup_genotypes(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len, int32_t min_depth,
+                            int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap, int64_t* count, int32_t* rows, bool quals) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
   int64_t g0 = 0, n = 0;
   const int rc = calls_check(p, texts, true, seq, start, len, min_depth, min_permille, cap, &g0, &n);
   if (rc != WFA_HIP_OK) return rc;
+  if (quals && !p->quals) return fail_inval(al, "pileup: quality-weighted genotypes need a pileup made to track qualities (wfa_hip_pileup_track_qualities)");
   if (err_q < 1 || err_q > 60) return fail_inval(al, "pileup: err_q = %d is out of range (1 .. 60)", (int)err_q);
   if (min_alt_strand < 0) return fail_inval(al, "pileup: min_alt_strand = %d is negative", (int)min_alt_strand);
   if (min_alt_strand > 0 && !p->strands)
@@ -458,8 +539,20 @@ extern "C" int wfa_hip_pileup_genotypes(wfa_hip_pileup_t* p, const wfa_hip_seqse
   if (a.c.cap == 0) return WFA_HIP_OK;
   if (sc.alloc(&a.c.rows, (size_t)a.c.cap * WFA_GENOTYPE_COLS)) return WFA_HIP_EDEVICE;
   ReduceTimer timer(al, "genotypes scatter", n, "bases");
-  return calls_launched(sc, timer, wfa::launch_genotypes_scatter(a, al->stream), "genotypes scatter kernel launch failed", rows, a.c.rows,
-                        (size_t)a.c.cap * WFA_GENOTYPE_COLS);
+  return calls_launched(sc, timer, quals ? wfa::launch_genotypes_quals_scatter(a, p->d_qtab, al->stream) : wfa::launch_genotypes_scatter(a, al->stream),
+                        "genotypes scatter kernel launch failed", rows, a.c.rows, (size_t)a.c.cap * WFA_GENOTYPE_COLS);
+}
+
+extern "C" int wfa_hip_pileup_genotypes(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                        int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
+                                        int64_t* count, int32_t* rows) {
+  return pileup_genotypes(p, texts, seq, start, len, min_depth, min_permille, err_q, min_alt_strand, cap, count, rows, false);
+}
+
+extern "C" int wfa_hip_pileup_genotypes_quals(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                              int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
+                                              int64_t* count, int32_t* rows) {
+  return pileup_genotypes(p, texts, seq, start, len, min_depth, min_permille, err_q, min_alt_strand, cap, count, rows, true);
 }
 
 // ---- what the reads insert: one allele per reported row (include/wfa_hip.h, "insertions"; csrc/wfa_insertions.hpp, k_insertions.hip) ------

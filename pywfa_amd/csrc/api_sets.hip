@@ -103,6 +103,60 @@ extern "C" wfa_hip_seqset_t* wfa_hip_seqset_create(wfa_hip_aligner_t* al, int64_
   return create_done(al, s, seqset_build(al, s, n, seqs, off, len), wfa_hip_seqset_destroy);
 }
 
+// ---- the base qualities of a set's sequences (include/wfa_hip.h, "base qualities") ---------------------------------------------------
+extern "C" void wfa_hip_qualset_destroy(wfa_hip_qualset_t* s) {
+  if (!s) return;
+  wfa_hip_aligner* al = s->al;
+  (void)hipSetDevice(al->device);
+  void* ptrs[] = {s->d_quals, s->d_off, s->d_len};
+  for (void* p : ptrs) pool_release(al, p);
+  destroy_end(s);
+}
+
+// the bytes packed read after read (the caller's offsets need not be), uploaded once
+static int qualset_build(wfa_hip_aligner* al, wfa_hip_qualset* s, const wfa_hip_seqset_t* reads, const uint8_t* quals, const int64_t* off) {
+  s->n = reads->n;
+  s->h_len = reads->h_len;
+  std::vector<int64_t> boff((size_t)s->n);
+  int64_t bb = 0;
+  for (int64_t k = 0; k < s->n; ++k) { boff[(size_t)k] = bb; bb += s->h_len[(size_t)k]; }
+  s->nbytes = bb;
+  std::vector<uint8_t> bytes((size_t)bb + 64, 0u);
+  for (int64_t k = 0; k < s->n; ++k)
+    if (s->h_len[(size_t)k] > 0) memcpy(bytes.data() + boff[(size_t)k], quals + off[k], (size_t)s->h_len[(size_t)k]);
+  const size_t nn = (size_t)std::max<int64_t>(s->n, 1);
+  HIP_TRY(al, pool_alloc(al, (void**)&s->d_quals, bytes.size()));
+  HIP_TRY(al, pool_alloc(al, (void**)&s->d_off, nn * sizeof(int64_t)));
+  HIP_TRY(al, pool_alloc(al, (void**)&s->d_len, nn * sizeof(int32_t)));
+  HIP_TRY(al, hipMemcpy(s->d_quals, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+  if (s->n > 0) {
+    HIP_TRY(al, hipMemcpy(s->d_off, boff.data(), (size_t)s->n * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIP_TRY(al, hipMemcpy(s->d_len, s->h_len.data(), (size_t)s->n * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  return WFA_HIP_OK;
+}
+
+extern "C" wfa_hip_qualset_t* wfa_hip_qualset_create(wfa_hip_aligner_t* al, const wfa_hip_seqset_t* reads, const uint8_t* quals, const int64_t* off,
+                                                     const int32_t* len) {
+  if (!al) return fail_create(al, "null aligner");
+  if (!reads || reads->al != al) return fail_create(al, "sequence set of another aligner");
+  const int64_t n = reads->n;
+  if (n > 0 && (!quals || !off || !len)) return fail_create(al, "quality set: the qualities, their offsets or their lengths are missing");
+  for (int64_t k = 0; k < n; ++k) {
+    if (off[k] < 0) return fail_create(al, "quality set: negative offset at entry %lld: off = %lld", (long long)k, (long long)off[k]);
+    if (len[k] != reads->h_len[(size_t)k])
+      return fail_create(al, "quality set: entry %lld has %d qualities, read %lld of the set has %d bases", (long long)k, (int)len[k], (long long)k,
+                         (int)reads->h_len[(size_t)k]);
+    for (int32_t x = 0; x < len[k]; ++x)
+      if (quals[off[k] + x] > WFA_HIP_MAX_QUALITY)
+        return fail_create(al, "quality set: quality %d at position %d of entry %lld is out of range (raw phred, 0 .. %d)", (int)quals[off[k] + x],
+                           (int)x, (long long)k, WFA_HIP_MAX_QUALITY);
+  }
+  if (!create_begin(al)) return nullptr;
+  wfa_hip_qualset* s = create_adopt(al, new wfa_hip_qualset());
+  return create_done(al, s, qualset_build(al, s, reads, quals, off), wfa_hip_qualset_destroy);
+}
+
 extern "C" int64_t wfa_hip_plan_cross_bands(int64_t m, int64_t n, int triangle, int64_t max_pairs, int64_t* row_begin, int64_t cap) {
   if (m < 0 || n < 0 || max_pairs < 1 || (triangle != 0 && triangle != 1)) return WFA_HIP_EINVAL;
   const int64_t rows = (n == 0) ? 0 : (triangle ? n : m);

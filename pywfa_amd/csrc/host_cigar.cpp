@@ -136,6 +136,50 @@ extern "C" int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uin
   return WFA_HIP_OK;
 }
 
+// the pileup with base qualities (include/wfa_hip.h, "base qualities"): quals[v] is the quality of pattern[v]
+extern "C" int wfa_hip_ops_pileup_quals(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen, const uint8_t* quals,
+                                        int32_t min_base_quality, int32_t quality_cap, int32_t* rows, int32_t* qrows) {
+  if (ops_len < 0 || plen < 0 || tlen < 0 || (ops_len > 0 && !ops) || (plen > 0 && (!pattern || !quals)) || (tlen > 0 && (!rows || !qrows)) ||
+      min_base_quality < 0 || min_base_quality > WFA_HIP_MAX_QUALITY || quality_cap < 1 || quality_cap > WFA_HIP_MAX_QUALITY)
+    return WFA_HIP_EINVAL;
+  for (int32_t v = 0; v < plen; ++v) if (quals[v] > WFA_HIP_MAX_QUALITY) return WFA_HIP_EINVAL;
+  int64_t nv = 0, nh = 0;
+  for (int64_t i = 0; i < ops_len; ++i) { const uint8_t c = ops[i]; nv += (c == 'M' || c == 'X' || c == 'D'); nh += (c == 'M' || c == 'X' || c == 'I'); }
+  if (nv > plen || nh > tlen) return WFA_HIP_EINVAL;
+  int64_t first = 0, last = -1;
+  if (!aligned_core(ops, ops_len, &first, &last)) return WFA_HIP_OK;
+  const auto capped = [&](int32_t x) { return std::min<int32_t>(quals[x], quality_cap); };
+  int32_t v = 0, h = 0;
+  for (int64_t i = 0; i <= last; ++i) {
+    const uint8_t c = ops[i];
+    const bool in = i >= first;
+    int32_t* row = rows + (int64_t)WFA_HIP_PILEUP_COLS * h;
+    int32_t* qrow = qrows + (int64_t)WFA_HIP_PILEUP_COLS * h;
+    if (c == 'M' || c == 'X') {
+      if (in && quals[v] >= min_base_quality) {
+        const uint8_t l = pattern[v];
+        const int col = l == 'A' ? 0 : l == 'C' ? 1 : l == 'G' ? 2 : l == 'T' ? 3 : 4;
+        row[col] += 1; qrow[col] += capped(v);
+        if (c == 'X') { row[7] += 1; qrow[7] += capped(v); }
+      }
+      ++v; ++h;
+    } else if (c == 'I') {
+      if (in) {
+        // the read bases on either side of the text base it lacks; one outside the pattern is left out
+        int32_t qq = -1;
+        if (v - 1 >= 0 && v - 1 < plen) qq = capped(v - 1);
+        if (v < plen) qq = qq < 0 ? capped(v) : std::min(qq, capped(v));
+        row[5] += 1; qrow[5] += std::max(qq, 0);
+      }
+      ++h;
+    } else if (c == 'D') {
+      if (in && ops[i - 1] != 'D') { row[6] += 1; qrow[6] += capped(v); }   // (inside the core a D has an op in front of it)
+      ++v;
+    }
+  }
+  return WFA_HIP_OK;
+}
+
 // ---- left alignment: the rewrite of one pair's op string, stated in plain C (the kernel: wfa_leftalign.hpp, k_leftalign.hip) --------
 
 extern "C" int wfa_hip_ops_left_align(uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen,
@@ -274,6 +318,62 @@ extern "C" int wfa_hip_genotypes_host(const int32_t* counts, const int32_t* coun
       row[8] = row[9] = row[10] = row[11] = -1;
       if (snv) genotype_of(c[r], A, err_q, &row[8], &row[9]);
       if (has_ins) genotype_of(std::max<int64_t>(0, depth - ins), ins, err_q, &row[10], &row[11]);
+      row[12] = row[13] = row[14] = row[15] = -1;
+      if (f) { row[12] = (int32_t)depth_of(f); row[13] = f[r]; row[14] = snv ? f[alt] : 0; row[15] = f[6]; }
+    }
+    ++n;
+  }
+  *count = n;
+  return WFA_HIP_OK;
+}
+
+namespace {
+// GENOTYPE over three given costs
+void genotype_of_costs(int64_t L0, int64_t L1, int64_t L2, int32_t* gt, int32_t* gq) {
+  const int64_t L[3] = {L0, L1, L2};
+  int best = 0;
+  for (int k = 1; k < 3; ++k) if (L[k] < L[best]) best = k;
+  const int64_t second = std::min(L[(best + 1) % 3], L[(best + 2) % 3]);
+  *gt = best;
+  *gq = (int32_t)std::min<int64_t>(99, second - L[best]);
+}
+}  // namespace
+
+// the genotyped sites with the costs of "base qualities": the selection, the filter and the rows of wfa_hip_genotypes_host
+extern "C" int wfa_hip_genotypes_quals_host(const int32_t* counts, const int32_t* qsums, const int32_t* counts_fwd, const uint8_t* ref, int64_t len,
+                                            int32_t seq, int64_t start, int32_t min_depth, int32_t min_permille, int32_t err_q,
+                                            int32_t min_alt_strand, int64_t cap, int64_t* count, int32_t* rows) {
+  if (len < 0 || min_depth < 1 || min_permille < 1 || min_permille > 1000 || err_q < 1 || err_q > 60 || min_alt_strand < 0 ||
+      (min_alt_strand > 0 && !counts_fwd) || cap < 0 || !count || (len > 0 && (!counts || !qsums || !ref)) || (cap > 0 && !rows))
+    return WFA_HIP_EINVAL;
+  int64_t n = 0;
+  for (int64_t g = 0; g < len; ++g) {
+    const int32_t* c = counts + g * WFA_HIP_PILEUP_COLS;
+    const int32_t* qs = qsums + g * WFA_HIP_PILEUP_COLS;
+    const int32_t* f = counts_fwd ? counts_fwd + g * WFA_HIP_PILEUP_COLS : nullptr;
+    const int64_t depth = depth_of(c);
+    if (depth < min_depth) continue;
+    const int r = ref_col(ref[g]);
+    int alt = -1;
+    for (int x = 0; x < 6; ++x) if (x != r && (alt < 0 || c[x] > c[alt])) alt = x;
+    const int64_t A = c[alt], ins = c[6];
+    bool snv = A >= 1 && 1000 * A >= (int64_t)min_permille * depth;
+    bool has_ins = ins >= 1 && 1000 * ins >= (int64_t)min_permille * depth;
+    if (min_alt_strand > 0) {
+      snv = snv && f[alt] >= min_alt_strand && A - f[alt] >= min_alt_strand;
+      has_ins = has_ins && f[6] >= min_alt_strand && ins - f[6] >= min_alt_strand;
+    }
+    if (!snv && !has_ins) continue;
+    if (n < cap) {
+      int32_t* row = rows + n * WFA_HIP_GENOTYPE_COLS;
+      row[0] = seq; row[1] = (int32_t)(start + g); row[2] = r; row[3] = snv ? alt : -1; row[4] = (int32_t)depth;
+      row[5] = c[r]; row[6] = snv ? c[alt] : 0; row[7] = c[6];
+      row[8] = row[9] = row[10] = row[11] = -1;
+      if (snv) genotype_of_costs(qs[alt], 3 * ((int64_t)c[r] + A), qs[r], &row[8], &row[9]);
+      if (has_ins) {
+        const int64_t R = std::max<int64_t>(0, depth - ins);
+        genotype_of_costs(qs[6], 3 * (R + ins), (int64_t)err_q * R, &row[10], &row[11]);
+      }
       row[12] = row[13] = row[14] = row[15] = -1;
       if (f) { row[12] = (int32_t)depth_of(f); row[13] = f[r]; row[14] = snv ? f[alt] : 0; row[15] = f[6]; }
     }

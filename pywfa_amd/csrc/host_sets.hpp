@@ -20,6 +20,15 @@ struct wfa_hip_seqset {
   mutable uint16_t* d_mask = nullptr;   // the seed finder's view of h_runs: one bit per base, 16 per word (seqset_mask: built on first use)
 };
 
+// the base qualities of a set's sequences (include/wfa_hip.h, "base qualities"): a byte per base, raw phred, read after read
+struct wfa_hip_qualset {
+  wfa_hip_aligner* al = nullptr;
+  int64_t n = 0;
+  int64_t nbytes = 0;
+  std::vector<int32_t> h_len;      // the lengths of the reads it was made over
+  uint8_t* d_quals = nullptr; int64_t* d_off = nullptr; int32_t* d_len = nullptr;
+};
+
 // ---- a resident handle's life: create_begin, the creator's own checks and `new`, create_adopt, its build, create_done; its destroy
 // releases what it owns and ends in destroy_end.  Handles count as the aligner's live batches: the last one to go frees an aligner
 // whose destroy is pending.

@@ -182,6 +182,63 @@ __global__ void __launch_bounds__(256) wfa_genotypes_scatter_kernel(GenoArgs a) 
   }
 }
 
+// The scatter pass with the costs of "base qualities" (include/wfa_hip.h): the ranks, the rows and the stores of the kernel above; the
+// costs of an event are sums of the quality table qtab, loaded at this base only, in the planes of the event's columns (0..6, at
+// global indices in [g0, g0 + n), as the table's).  A kernel of its own, so that the one above compiles to the code it had.
+__global__ void __launch_bounds__(256) wfa_genotypes_quals_scatter_kernel(GenoArgs a, const int32_t* qtab) {
+  __shared__ uint32_t s_red[4];
+  const CallsArgs& c = a.c;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long lower = (1ull << lane) - 1ull;
+  for (int64_t ch = blockIdx.x; ch < c.chunks; ch += gridDim.x) {
+    uint64_t run = c.chunk_off[ch];
+    if (run >= (uint64_t)c.cap || c.chunk_off[ch + 1] == run) continue;   // (uniform over the workgroup)
+    const int64_t i0 = ch * c.chunk;
+    for (int64_t t0 = 0; t0 < c.chunk; t0 += 256) {
+      const int64_t i = i0 + t0 + threadIdx.x;
+      CallsBase b; int alt; bool snv, ins;
+      const bool site = t0 + threadIdx.x < c.chunk && geno_flag(a, i, &b, &alt, &snv, &ins);
+      const unsigned long long m = __ballot(site);
+      if (lane == 0) s_red[wave] = (uint32_t)__builtin_popcountll(m);
+      __syncthreads();
+      uint32_t before = 0;
+      for (int w = 0; w < wave; ++w) before += s_red[w];
+      const uint32_t total = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+      __syncthreads();
+      const uint64_t rank = run + before + (uint32_t)__builtin_popcountll(m & lower);
+      run += total;
+      if (!site || rank >= (uint64_t)c.cap) continue;
+      const int64_t g = c.g0 + i;
+      int64_t lo = 0, hi = c.nseq;   // the first sequence that starts behind g; its predecessor owns g
+      while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (c.seq_off[mid] > g) hi = mid; else lo = mid + 1; }
+      const int64_t j = lo - 1;
+      const int32_t ref_count = geno_pick(b.c, b.r), alt_count = geno_pick(b.c, alt);
+      int32_t gt = -1, gq = -1, ins_gt = -1, ins_gq = -1;
+      if (snv)
+        calls_genotype_costs(qtab[(int64_t)alt * c.total + g], 3 * ((int64_t)ref_count + alt_count), qtab[(int64_t)b.r * c.total + g], &gt, &gq);
+      if (ins) {
+        const int64_t R = b.depth > b.c[6] ? b.depth - b.c[6] : 0;
+        calls_genotype_costs(qtab[(int64_t)WFA_PILEUP_INS * c.total + g], 3 * (R + b.c[6]), (int64_t)a.err_q * R, &ins_gt, &ins_gq);
+      }
+      int4 strands = make_int4(-1, -1, -1, -1);
+      if (a.fwd) {
+        int32_t f[7];
+        int64_t depth_fwd = 0;
+#pragma unroll
+        for (int x = 0; x < 7; ++x) f[x] = a.fwd[(int64_t)x * c.total + g];
+#pragma unroll
+        for (int x = 0; x < 6; ++x) depth_fwd += f[x];
+        strands = make_int4((int32_t)depth_fwd, geno_pick(f, b.r), snv ? geno_pick(f, alt) : 0, f[6]);
+      }
+      int4* row = reinterpret_cast<int4*>(c.rows + rank * WFA_GENOTYPE_COLS);
+      row[0] = make_int4((int32_t)j, (int32_t)(g - c.seq_off[j]), b.r, snv ? alt : -1);
+      row[1] = make_int4((int32_t)b.depth, ref_count, snv ? alt_count : 0, b.c[6]);
+      row[2] = make_int4(gt, gq, ins_gt, ins_gq);
+      row[3] = strands;
+    }
+  }
+}
+
 int launch_calls(const CallsArgs& a, int cu_count, hipStream_t stream) {
   if (a.n <= 0) return 0;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.n + 255) / 256, (int64_t)cu_count * 32));
@@ -218,6 +275,13 @@ int launch_genotypes_scatter(const GenoArgs& a, hipStream_t stream) {
   if (a.c.chunks <= 0 || a.c.cap <= 0) return 0;
   if (a.min_alt_strand > 0 && !a.fwd) return -1;
   hipLaunchKernelGGL(wfa_genotypes_scatter_kernel, dim3(chunk_grid(a.c.chunks)), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_genotypes_quals_scatter(const GenoArgs& a, const int32_t* qtab, hipStream_t stream) {
+  if (a.c.chunks <= 0 || a.c.cap <= 0) return 0;
+  if (!qtab || (a.min_alt_strand > 0 && !a.fwd)) return -1;
+  hipLaunchKernelGGL(wfa_genotypes_quals_scatter_kernel, dim3(chunk_grid(a.c.chunks)), dim3(256), 0, stream, a, qtab);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -3,7 +3,8 @@
 // One wave per pair, grid-stride.  Every store to the table is an int32 atomicAdd; a lane adds only for an op of the aligned core
 // whose text position lies inside the pair's text window, and the host has checked that the window lies inside its sequence, so an op
 // string that disagreed with its pair's lengths could lose counts but never leave the table.  The stranded forms add a second time at
-// the same offset of the forward table, an allocation of the table's size.  The log's stores are plain: a record
+// the same offset of the forward table, the forms with qualities once more at the same offset of the quality table, each an allocation
+// of the table's size.  The log's stores are plain: a record
 // and a column byte have one writer, at an index below the allocated size (checked at the store).
 #include <algorithm>
 #include "wfa_insertions.hpp"
@@ -16,8 +17,13 @@ enum { PILEUP_TABLE = 0, PILEUP_COUNT = 1, PILEUP_TRACK = 2 };
 // contributing pair (the host zeroes the array).  PILEUP_TRACK: the adds and the pair's records and column bytes.
 // STRANDS (TABLE and TRACK; wfa_pileup.hpp: PileupStrandArgs): a forward pair repeats every add at the same row and column of the
 // forward table.  The strand is the pair's, so it is uniform over the wave; without STRANDS `s` is not read.
-template <int MODE, bool STRANDS>
-__device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs& s) {
+// QUALS (TABLE and TRACK; wfa_pileup.hpp: PileupQualArgs): every add of a count comes with an add of a capped quality at the same row
+// and column of the quality table, an allocation of the table's size; an M or X under min_base_quality adds nothing to any table.
+// The log's records do not depend on the qualities.  Every quality load is at an index in [0, qn) behind the window's first byte, and
+// qn is the pair's pattern length only where the window lies inside its read of the set (else 0: nothing is loaded).  Without QUALS
+// `u` is not read.
+template <int MODE, bool STRANDS, bool QUALS>
+__device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs& s, const PileupQualArgs& u) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -52,6 +58,18 @@ __device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArg
     const bool on_bytes = a.bytes != nullptr && a.flags[q] != 0;
     const uint8_t* pb = on_bytes ? a.bytes + a.pboff[q] : nullptr;
     const uint32_t* pw = a.words + m.p_woff;
+    // the window's quality bytes: position x of the pattern is byte x of them, byte qn - 1 - x on the reverse strand
+    const uint8_t* qb = nullptr;
+    int qn = 0;
+    bool qrev = false;
+    int32_t* qrow0 = QUALS ? u.qtab + a.seq_off[jq] + ts : nullptr;
+    if (QUALS) {
+      const int rq = u.i[q];
+      const int64_t ps = u.p_start ? u.p_start[q] : 0;
+      // (checked on the host; here so that nothing a caller passes can move a load out of the quality bytes)
+      if (rq >= 0 && rq < u.nreads && ps >= 0 && m.plen > 0 && ps + m.plen <= u.qlen[rq]) { qb = u.quals + u.qoff[rq] + ps; qn = m.plen; }
+      qrev = u.reverse != nullptr && u.reverse[q] != 0;
+    }
     int vbase = 0, hbase = 0;
     unsigned long long carry_d = 0;
     // the log (wave-uniform): the pair's counted runs and D ops so far; the run that is open across a round boundary
@@ -111,35 +129,65 @@ __device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArg
       if (i < first || i > last || h >= m.tlen) continue;
       int32_t* row = row0 + h;
       int32_t* frow = frow0 + h;
+      int32_t* qrow = qrow0 + h;
+      // this lane's quality: of position v (an M or X, and a D run's first base), or the smaller of positions v - 1 and v (an I)
+      int qv = 0;
+      bool pass = true;
+      if (QUALS) {
+        const int x0 = c == 'I' ? v - 1 : v;
+        int q0 = -1, q1 = -1;
+        if (x0 >= 0 && x0 < qn) q0 = qb[qrev ? qn - 1 - x0 : x0];
+        if (c == 'I' && v < qn) q1 = qb[qrev ? qn - 1 - v : v];
+        pass = q0 >= u.min_base_quality;   // (asked of an M or X only; a position without a byte never passes)
+        qv = q0 < 0 ? q1 : (q1 < 0 || q0 < q1) ? q0 : q1;
+        qv = qv < 0 ? 0 : qv < u.quality_cap ? qv : u.quality_cap;
+      }
       if (c == 'M' || c == 'X') {
-        if (v < m.plen) {
+        if (v < m.plen && (!QUALS || pass)) {
           const int col = on_bytes ? wfa_pileup_letter_col(pb[v]) : wfa_pileup_code_col((pw[v >> 4] >> (2 * (v & 15))) & 3u);
           atomicAdd(row + (int64_t)col * a.total, 1);
           if (STRANDS && fwd) atomicAdd(frow + (int64_t)col * a.total, 1);
+          if (QUALS) atomicAdd(qrow + (int64_t)col * a.total, qv);
           if (c == 'X') {
             atomicAdd(row + (int64_t)WFA_PILEUP_MISMATCH * a.total, 1);
             if (STRANDS && fwd) atomicAdd(frow + (int64_t)WFA_PILEUP_MISMATCH * a.total, 1);
+            if (QUALS) atomicAdd(qrow + (int64_t)WFA_PILEUP_MISMATCH * a.total, qv);
           }
         }
       } else if (c == 'I') {
         atomicAdd(row + (int64_t)WFA_PILEUP_DEL * a.total, 1);
         if (STRANDS && fwd) atomicAdd(frow + (int64_t)WFA_PILEUP_DEL * a.total, 1);
+        if (QUALS) atomicAdd(qrow + (int64_t)WFA_PILEUP_DEL * a.total, qv);
       } else if (d_start) {
         atomicAdd(row + (int64_t)WFA_PILEUP_INS * a.total, 1);
         if (STRANDS && fwd) atomicAdd(frow + (int64_t)WFA_PILEUP_INS * a.total, 1);
+        if (QUALS) atomicAdd(qrow + (int64_t)WFA_PILEUP_INS * a.total, qv);
       }
     }
     if (MODE == PILEUP_COUNT && lane == 0) g.pair_count[q] = InsPairCount{nrec, nbase};
   }
 }
 
-__global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) { pileup_walk<PILEUP_TABLE, false>(a, InsLogArgs{}, PileupStrandArgs{}); }
-__global__ void __launch_bounds__(256) wfa_pileup_count_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_COUNT, false>(a, g, PileupStrandArgs{}); }
-__global__ void __launch_bounds__(256) wfa_pileup_track_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_TRACK, false>(a, g, PileupStrandArgs{}); }
+__global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) { pileup_walk<PILEUP_TABLE, false, false>(a, InsLogArgs{}, PileupStrandArgs{}, PileupQualArgs{}); }
+__global__ void __launch_bounds__(256) wfa_pileup_count_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_COUNT, false, false>(a, g, PileupStrandArgs{}, PileupQualArgs{}); }
+__global__ void __launch_bounds__(256) wfa_pileup_track_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_TRACK, false, false>(a, g, PileupStrandArgs{}, PileupQualArgs{}); }
 // the stranded forms (COUNT stores nothing to a table and has none)
-__global__ void __launch_bounds__(256) wfa_pileup_strands_kernel(PileupArgs a, PileupStrandArgs s) { pileup_walk<PILEUP_TABLE, true>(a, InsLogArgs{}, s); }
+__global__ void __launch_bounds__(256) wfa_pileup_strands_kernel(PileupArgs a, PileupStrandArgs s) { pileup_walk<PILEUP_TABLE, true, false>(a, InsLogArgs{}, s, PileupQualArgs{}); }
 __global__ void __launch_bounds__(256) wfa_pileup_track_strands_kernel(PileupArgs a, InsLogArgs g, PileupStrandArgs s) {
-  pileup_walk<PILEUP_TRACK, true>(a, g, s);
+  pileup_walk<PILEUP_TRACK, true, false>(a, g, s, PileupQualArgs{});
+}
+// the forms with qualities, each with and without strands
+__global__ void __launch_bounds__(256) wfa_pileup_quals_kernel(PileupArgs a, PileupQualArgs u) {
+  pileup_walk<PILEUP_TABLE, false, true>(a, InsLogArgs{}, PileupStrandArgs{}, u);
+}
+__global__ void __launch_bounds__(256) wfa_pileup_quals_strands_kernel(PileupArgs a, PileupStrandArgs s, PileupQualArgs u) {
+  pileup_walk<PILEUP_TABLE, true, true>(a, InsLogArgs{}, s, u);
+}
+__global__ void __launch_bounds__(256) wfa_pileup_track_quals_kernel(PileupArgs a, InsLogArgs g, PileupQualArgs u) {
+  pileup_walk<PILEUP_TRACK, false, true>(a, g, PileupStrandArgs{}, u);
+}
+__global__ void __launch_bounds__(256) wfa_pileup_track_quals_strands_kernel(PileupArgs a, InsLogArgs g, PileupStrandArgs s, PileupQualArgs u) {
+  pileup_walk<PILEUP_TRACK, true, true>(a, g, s, u);
 }
 
 static unsigned pileup_grid(const PileupArgs& a, int cu_count) {
@@ -179,6 +227,25 @@ int launch_pileup_track_strands(const PileupArgs& a, const InsLogArgs& g, const 
   if (a.npairs <= 0) return 0;
   if (!s.fwd) return -1;
   hipLaunchKernelGGL(wfa_pileup_track_strands_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g, s);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+static bool pileup_quals_ok(const PileupQualArgs& u) { return u.quals && u.qoff && u.qlen && u.i && u.qtab; }
+
+int launch_pileup_quals(const PileupArgs& a, const PileupStrandArgs* s, const PileupQualArgs& u, int cu_count, hipStream_t stream) {
+  if (a.npairs <= 0) return 0;
+  if (!pileup_quals_ok(u) || (s && !s->fwd)) return -1;
+  if (s) hipLaunchKernelGGL(wfa_pileup_quals_strands_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, *s, u);
+  else hipLaunchKernelGGL(wfa_pileup_quals_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, u);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_pileup_track_quals(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs* s, const PileupQualArgs& u, int cu_count,
+                              hipStream_t stream) {
+  if (a.npairs <= 0) return 0;
+  if (!pileup_quals_ok(u) || (s && !s->fwd)) return -1;
+  if (s) hipLaunchKernelGGL(wfa_pileup_track_quals_strands_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g, *s, u);
+  else hipLaunchKernelGGL(wfa_pileup_track_quals_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g, u);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

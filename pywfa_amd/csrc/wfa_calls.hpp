@@ -116,8 +116,22 @@ __host__ __device__ inline void calls_genotype(int64_t R, int64_t A, int32_t err
   *gq = (int32_t)(d < 99 ? d : 99);
 }
 
+// GENOTYPE over three given costs (include/wfa_hip.h, "base qualities": the costs are sums of capped qualities)
+__host__ __device__ inline void calls_genotype_costs(int64_t L0, int64_t L1, int64_t L2, int32_t* gt, int32_t* gq) {
+  int best = 0;
+  int64_t lo = L0, next = L1 < L2 ? L1 : L2;
+  if (L1 < lo) { best = 1; lo = L1; next = L0 < L2 ? L0 : L2; }
+  if (L2 < lo) { best = 2; lo = L2; next = L0 < L1 ? L0 : L1; }
+  const int64_t d = next - lo;
+  *gt = best;
+  *gq = (int32_t)(d < 99 ? d : 99);
+}
+
 int launch_genotypes_count(const GenoArgs& a, hipStream_t stream);     // count + scan, as launch_sites_count
 int launch_genotypes_scatter(const GenoArgs& a, hipStream_t stream);
+// the scatter pass with the costs of "base qualities": qtab is the pileup's quality table (the table's planes and stride), read only
+// at bases that are reported, in the planes of the events' columns.  The count pass is launch_genotypes_count: the selection is the same.
+int launch_genotypes_quals_scatter(const GenoArgs& a, const int32_t* qtab, hipStream_t stream);
 
 int launch_calls(const CallsArgs& a, int cu_count, hipStream_t stream);
 int launch_sites_count(const CallsArgs& a, hipStream_t stream);     // count + scan: chunk_off[chunks] is the number of sites

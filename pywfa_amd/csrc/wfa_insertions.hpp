@@ -90,6 +90,8 @@ __host__ __device__ inline bool ins_selected(int64_t depth, int32_t c6, int32_t 
 int launch_pileup_count(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream);   // count + the two scans
 int launch_pileup_track(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream);   // table + scatter
 int launch_pileup_track_strands(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs& s, int cu_count, hipStream_t stream);   // and the forward table
+int launch_pileup_track_quals(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs* s, const PileupQualArgs& u, int cu_count,
+                              hipStream_t stream);   // and the quality table (s: nullptr without strands)
 // out[0 .. n] = the exclusive 64-bit prefix of `n` 32-bit values read with a stride of `stride` words, out[n] the total
 int launch_ins_scan(const uint32_t* in, int stride, uint64_t* out, int64_t n, hipStream_t stream);
 

@@ -66,7 +66,27 @@ struct PileupStrandArgs {
   int32_t* fwd;              // WFA_PILEUP_COLS planes of PileupArgs::total counters
 };
 
+// Base qualities (include/wfa_hip.h, "base qualities"; opt-in): a pileup that tracks them keeps one more table of the same 8 planes,
+// plane stride and layout, the QUALITY table, and every op that adds a count adds a capped phred value at the same row and column of
+// it.  The quality of pattern position v of pair q is that of the stored read i[q], seen through the window [s, s + plen) with
+// s = p_start[q]: byte s + v of a forward pair, s + plen - 1 - v of a reverse one.  An M or X whose quality lies under
+// min_base_quality adds nothing to any table.  One byte load per lane (two on an I op), contiguous over the wave; the strand is the
+// pair's, so the direction is uniform over the wave.  A kernel compiled without the flag never reads this struct.
+struct PileupQualArgs {
+  const uint8_t* quals;      // the quality set's bytes, raw phred, read after read
+  const int64_t* qoff;       // [nreads] first byte of a read
+  const int32_t* qlen;       // [nreads]
+  int64_t nreads;
+  const int32_t* i;          // [npairs] read of pair q
+  const int32_t* p_start;    // [npairs] or nullptr: 0
+  const uint8_t* reverse;    // [npairs] or nullptr: every pair is forward
+  int32_t min_base_quality, quality_cap;
+  int32_t* qtab;             // WFA_PILEUP_COLS planes of PileupArgs::total sums
+};
+
 int launch_pileup(const PileupArgs& a, int cu_count, hipStream_t stream);
 int launch_pileup_strands(const PileupArgs& a, const PileupStrandArgs& s, int cu_count, hipStream_t stream);
+// the table kernel with qualities; s: the strand arguments of a pileup that tracks strands too, or nullptr
+int launch_pileup_quals(const PileupArgs& a, const PileupStrandArgs* s, const PileupQualArgs& u, int cu_count, hipStream_t stream);
 
 }  // namespace wfa

@@ -113,6 +113,24 @@ cdef extern from "wfa_hip.h" nogil:
     int wfa_hip_genotypes_host(const int32_t* counts, const int32_t* counts_fwd, const uint8_t* ref, int64_t len, int32_t seq,
                                int64_t start, int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
                                int64_t* count, int32_t* rows)
+    # base qualities of a pileup (include/wfa_hip.h: "base qualities")
+    ctypedef struct wfa_hip_qualset_t
+    wfa_hip_qualset_t* wfa_hip_qualset_create(wfa_hip_aligner_t* aligner, const wfa_hip_seqset_t* reads, const uint8_t* quals,
+                                              const int64_t* off, const int32_t* len)
+    void wfa_hip_qualset_destroy(wfa_hip_qualset_t* quals)
+    int wfa_hip_pileup_track_qualities(wfa_hip_pileup_t* pileup, int on)
+    int wfa_hip_pileup_add_quals(wfa_hip_pileup_t* pileup, wfa_hip_batch_t* batch, const int32_t* j, const int32_t* t_start,
+                                 const uint8_t* keep, const uint8_t* reverse, const wfa_hip_qualset_t* quals, const int32_t* i,
+                                 const int32_t* p_start, int32_t min_base_quality, int32_t quality_cap)
+    int wfa_hip_pileup_read_quality(wfa_hip_pileup_t* pileup, int32_t seq, int64_t start, int64_t len, int32_t* qsums)
+    int wfa_hip_pileup_genotypes_quals(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                       int32_t min_depth, int32_t min_permille, int32_t err_q, int32_t min_alt_strand, int64_t cap,
+                                       int64_t* count, int32_t* rows)
+    int wfa_hip_ops_pileup_quals(const uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, int32_t tlen,
+                                 const uint8_t* quals, int32_t min_base_quality, int32_t quality_cap, int32_t* rows, int32_t* qrows)
+    int wfa_hip_genotypes_quals_host(const int32_t* counts, const int32_t* qsums, const int32_t* counts_fwd, const uint8_t* ref,
+                                     int64_t len, int32_t seq, int64_t start, int32_t min_depth, int32_t min_permille, int32_t err_q,
+                                     int32_t min_alt_strand, int64_t cap, int64_t* count, int32_t* rows)
     # pairing: one row per fragment of two reads (include/wfa_hip.h: "pairing")
     int wfa_hip_placer_run_pairs(wfa_hip_placer_t* placer, int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert,
                             int32_t unpaired, int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int32_t* rows, uint8_t* flags,
