@@ -83,6 +83,7 @@ static int pileup_build(wfa_hip_aligner* al, wfa_hip_pileup* p, const wfa_hip_se
   const size_t bytes = (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t);
   if (hipMalloc((void**)&p->d_table, bytes) != hipSuccess)
     return fail_alloc(al, (void**)&p->d_table, "pileup table: hipMalloc of %zu bytes failed (32 bytes per text base, %lld bases)", bytes, (long long)p->total);
+  HIP_TRY(al, poison_fill(al, p->d_table, bytes, al->stream));
   const size_t nn = (size_t)std::max<int64_t>(T->n, 1);
   HIP_TRY(al, pool_alloc(al, (void**)&p->d_off, nn * sizeof(int64_t)));
   HIP_TRY(al, pool_alloc(al, (void**)&p->d_len, nn * sizeof(int32_t)));
@@ -140,7 +141,8 @@ static int pileup_track_table(wfa_hip_pileup* p, int on, int32_t** table, bool* 
   int32_t* fresh = nullptr;
   if (hipMalloc((void**)&fresh, bytes) != hipSuccess)
     return fail_alloc(al, (void**)&fresh, "pileup %s table: hipMalloc of %zu bytes failed (32 more bytes per text base, %lld bases)", what, bytes, (long long)p->total);
-  const hipError_t e = hipMemsetAsync(fresh, 0, bytes, al->stream);
+  hipError_t e = poison_fill(al, fresh, bytes, al->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(fresh, 0, bytes, al->stream);
   const hipError_t e2 = hipStreamSynchronize(al->stream);
   if (e != hipSuccess || e2 != hipSuccess) { (void)hipFree(fresh); HIP_TRY(al, e); HIP_TRY(al, e2); }
   *table = fresh; *tracking = true;
@@ -177,6 +179,8 @@ template <class T> static int ins_log_grow(wfa_hip_aligner* al, T** block, int64
     if (hipMalloc((void**)&fresh, (size_t)want * sizeof(T)) != hipSuccess)
       return fail_alloc(al, (void**)&fresh, "pileup insertion log: hipMalloc of %zu bytes failed (%s, %lld of them)", (size_t)want * sizeof(T), what, (long long)want);
   }
+  // (WFA_HIP_POISON: the fill first, the old contents over it — the grown tail stays filled until an add writes it)
+  { const hipError_t e = poison_fill(al, fresh, (size_t)want * sizeof(T), al->stream); if (e != hipSuccess) { (void)hipFree(fresh); HIP_TRY(al, e); } }
   if (have > 0) {
     const hipError_t e = hipMemcpyAsync(fresh, *block, (size_t)have * sizeof(T), hipMemcpyDeviceToDevice, al->stream);
     const hipError_t e2 = hipStreamSynchronize(al->stream);

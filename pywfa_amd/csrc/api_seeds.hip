@@ -81,10 +81,11 @@ static int seed_index_build(wfa_hip_aligner* al, wfa_hip_seed_index* x, const wf
   if (hipMalloc((void**)&x->d_table, table_bytes) != hipSuccess)
     return fail_alloc(al, (void**)&x->d_table, "seed index table: hipMalloc of %zu bytes failed (4 bytes per k-mer of k = %d: 4^k buckets)", table_bytes, x->k);
   const auto alloc_recs = [&](size_t bytes, uint64_t positions) {
-    if (hipMalloc((void**)&x->d_recs, bytes) == hipSuccess) return WFA_HIP_OK;
+    if (hipMalloc((void**)&x->d_recs, bytes) == hipSuccess) { HIP_TRY(al, poison_fill(al, x->d_recs, bytes, al->stream)); return WFA_HIP_OK; }
     return fail_alloc(al, (void**)&x->d_recs, "seed index records: hipMalloc of %zu bytes failed (8 bytes per indexed position, %llu positions)", bytes,
                       (unsigned long long)positions);
   };
+  HIP_TRY(al, poison_fill(al, x->d_table, table_bytes, al->stream));
   if (x->w == 0 && alloc_recs(rec_bytes, cap)) return WFA_HIP_EDEVICE;   // (a minimizer index: after the counting pass, by its total)
   x->table_bytes = (int64_t)(table_bytes + rec_bytes);
   const uint16_t* mask = nullptr;
@@ -258,6 +259,7 @@ extern "C" int wfa_hip_seed_index_chain(wfa_hip_seed_index_t* x, const wfa_hip_s
       return fail_alloc(al, (void**)&x->d_chain_ws, "seed chain workspace: hipMalloc of %zu bytes failed (32 bytes x max_anchors = %d per workgroup, %u workgroups)",
                         ws_bytes, max_anchors, grid);
     x->chain_ws_bytes = ws_bytes;
+    HIP_TRY(al, poison_fill(al, x->d_chain_ws, ws_bytes, al->stream));
   }
   wfa::ChainArgs a;
   if (r.rows(8, &a)) return WFA_HIP_EDEVICE;

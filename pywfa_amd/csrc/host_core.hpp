@@ -37,7 +37,7 @@ extern thread_local std::string g_error;   // what wfa_hip_global_error() return
   F(ARENA_KB) F(BAND_DEBUG) F(BAND_SLIM) F(BAND_LDS_MAX) F(BAND_NO_WIN) F(BAND_SPLIT_MIN) F(NO_TINY_INLINE) F(BILEVEL) F(BILEVEL_WIDE_LEVELS) F(BILEVEL_PER_CU) F(BILEVEL_I32) F(BILEVEL_QCAP) F(BILEVEL_LEVELS) F(BILEVEL_LDS) F(BILEVEL_NO_1024) F(BILEVEL_HUGE_MIN) F(BILEVEL_LDS_W) F(BILEVEL_NO_SEQL) F(LANE_DYN) F(LANE_DYN_WAVES) F(BAND_LEFTOVER_WAVES_PER_CU) F(BAND_NCH) F(BAND_NO_LDS) F(BAND_NO_SPLIT) F(BAND_PB) F(PIPE_TAIL) F(LEN16) F(MAILBOX) F(MAILBOX_IDLE_US) F(TILE32)     \
   F(BAND_RECORDS) F(BAND_SPLIT_ROUNDS) F(BAND_WAVES_PER_CU) F(NO_BAND) F(NO_FAST) F(NO_SEGFULL) F(SEGFULL_PAIRS)     \
   F(SEGFULL_STAGES) F(STAGE_TIMING) F(LANE_HEUR32) F(THREADS) F(TINY_BATCH) F(WAVES_PER_CU) F(FAST_WAVES_PER_CU) F(TIMING)          \
-  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_WINFIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT) F(CROSS_BAND) F(CROSS_TOPK_CHUNK) F(REDUCE_TIMING)
+  F(LANE_FULL) F(LANE_FULL_SPLIT) F(LANE_HEUR) F(SEG_HEUR) F(LANE_LDS_PAD_KB) F(LANE_MIN_PAIRS) F(PIPE_CHUNK) F(PIPE_THREADS) F(PACK_THREADS) F(NO_TINY_BAND) F(NO_TINY_POLL) F(UP_STREAMS) F(NO_DUAL) F(NO_WIDE) F(WIDE_ADAPT) F(WIDE_GROWS) F(WIDE_LDS_KB) F(WIDE_THREADS) F(TILE) F(TILE_T) F(TILE_WT) F(TILE_THREADS) F(TILE_PER_CU) F(NO_PIPE) F(HOST_PACK) F(GENERAL_PB) F(LANE_WAVES_PER_CU) F(LANE_REFILL_MIN) F(LANE_WINFIN) F(LANE_DEBUG) F(NO_TINY) F(PILOT_PCT) F(WIDE_ADAPT_LDS) F(LANE_NARROW_WAVES) F(PILOT_NARROW_PCT) F(CROSS_BAND) F(CROSS_TOPK_CHUNK) F(REDUCE_TIMING) F(POISON)
 enum WfaKnob {
 #define WFA_KNOB_ENUM(n) K_##n,
   WFA_KNOBS(WFA_KNOB_ENUM)
@@ -138,6 +138,21 @@ struct wfa_hip_aligner {
 
 static inline int knob(const wfa_hip_aligner* al, WfaKnob k, int dflt) {
   return al->knobs.set[k] ? al->knobs.value[k] : dflt;
+}
+
+// WFA_HIP_POISON=1..255 (a development knob for the tests; synchronises): device memory that is handed out without its contents being
+// defined — a block of the pool (fresh or recycled, over its whole size class), a direct allocation, the aligner's workspace at the start
+// of a run — is filled with that byte first, so that a kernel reading a byte nothing wrote sees 0x7f7f.. or 0xffff.. and not the zero page
+// of a fresh allocation or the previous batch's data.  The fill goes to `stream` and the call waits for that stream alone (never the
+// device: the resident one-pair kernel may be running on its own stream).  A batch run has told that kernel to leave before its fill
+// (mailbox_release); the single-call path (tiny_band) has NOT: the instance is idle between calls, its history is written per pair
+// before its walk reads it, and it leaves by itself after its idle time.  A workspace that has just grown is filled twice on that path
+// (ensure_ws, then wait_for_workspace): harmless.  Off (unset or 0): one array read.
+static inline hipError_t poison_fill(const wfa_hip_aligner* al, void* p, size_t bytes, hipStream_t stream) {
+  const int v = al->knobs.value[K_POISON];
+  if (v < 1 || v > 255 || !p || bytes == 0) return hipSuccess;
+  const hipError_t e = hipMemsetAsync(p, v, bytes, stream);
+  return e != hipSuccess ? e : hipStreamSynchronize(stream);
 }
 
 struct wfa_hip_batch {

@@ -63,7 +63,7 @@ hipError_t pool_alloc(wfa_hip_aligner* al, void** p, size_t bytes) {
     auto it = al->pool_free.find(want);
     if (it != al->pool_free.end()) {
       *p = it->second; al->pool_cached -= want; al->pool_free.erase(it);
-      return hipSuccess;
+      return poison_fill(al, *p, want, al->stream);   // (WFA_HIP_POISON: a recycled block does not carry the last batch's data)
     }
   }
   hipError_t e = hipMalloc(p, want);
@@ -73,7 +73,7 @@ hipError_t pool_alloc(wfa_hip_aligner* al, void** p, size_t bytes) {
     pool_drain_cached(al);
     e = hipMalloc(p, want);
   }
-  if (e == hipSuccess) al->pool_size[*p] = want;
+  if (e == hipSuccess) { al->pool_size[*p] = want; e = poison_fill(al, *p, want, al->stream); }
   return e;
 }
 
@@ -1576,7 +1576,8 @@ struct DualStream {
 
 // ---- launch geometry -------------------------------------------------------------------------------
 
-static int ensure_ws(wfa_hip_aligner* al, size_t bytes) {
+// (`stream`: the run's; WFA_HIP_POISON fills a grown workspace there)
+static int ensure_ws(wfa_hip_aligner* al, size_t bytes, hipStream_t stream) {
   if (bytes <= al->ws_bytes) return WFA_HIP_OK;
   if (al->ws) { (void)hipFree(al->ws); al->ws = nullptr; al->ws_bytes = 0; }
   hipError_t e = hipMalloc((void**)&al->ws, bytes);
@@ -1587,6 +1588,7 @@ static int ensure_ws(wfa_hip_aligner* al, size_t bytes) {
   }
   HIP_TRY(al, e);
   al->ws_bytes = bytes;
+  HIP_TRY(al, poison_fill(al, al->ws, al->ws_bytes, stream));
   return WFA_HIP_OK;
 }
 
@@ -1629,8 +1631,10 @@ static int launch_general_dyn(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t
 struct Geometry { int threads; int grid; int64_t ws_stride; };
 
 // every run of an aligner uses the one workspace (al->ws): order `stream` after the previous run when that was enqueued on another stream
+// (WFA_HIP_POISON: the run then starts on a filled workspace, not on the previous run's rows and lists)
 static int wait_for_workspace(wfa_hip_aligner* al, hipStream_t stream) {
   if (al->ws_event_recorded && al->ws_last_stream != stream) HIP_TRY(al, hipStreamWaitEvent(stream, al->ws_event, 0));
+  HIP_TRY(al, poison_fill(al, al->ws, al->ws_bytes, stream));
   return WFA_HIP_OK;
 }
 
@@ -2314,7 +2318,7 @@ static int run_biwfa(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream, 
   b->dcfg.biwfa_top = full ? 1 : 0;
   b->gcfg.biwfa_top = b->dcfg.biwfa_top;   // (the general kernel's copy of the configuration)
   BilevelPlan bp = plan_bilevel(al, b, biwfa_score);
-  int rc = ensure_ws(al, std::max((size_t)bp.dfs_off + (size_t)bp.grid * bp.stride * 4, full ? (size_t)bp.g.grid * bp.g.ws_stride * 4 : (size_t)0));
+  int rc = ensure_ws(al, std::max((size_t)bp.dfs_off + (size_t)bp.grid * bp.stride * 4, full ? (size_t)bp.g.grid * bp.g.ws_stride * 4 : (size_t)0), stream);
   if (rc != WFA_HIP_OK) return rc;
   WfaKernelArgs& a = bp.ba.k;
   a.words = b->d_words; a.bytes = b->d_bytes; a.meta = b->d_meta; a.p_boff = b->d_pboff; a.t_boff = b->d_tboff;
@@ -2866,7 +2870,7 @@ static int run_wide_stage(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t str
 static int run_cascade(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t stream) {
   CascadePlan p;
   plan_cascade(al, b, p);
-  int rc = ensure_ws(al, p.need);
+  int rc = ensure_ws(al, p.need, stream);
   if (rc != WFA_HIP_OK) return rc;
   Chain c;
   c.in_list = b->d_list_packed; c.in_n = b->n_packed;
@@ -2956,7 +2960,7 @@ static int batch_run_once(wfa_hip_batch_t* b, void* stream_) {
     // 3) 8-bit pairs (non-ACGT letters, wildcard matching)
     if (b->n_bytes > 0) {
       Geometry g = plan_general(al, b, b->n_bytes, b->arena_fixed + b->arena_ints);
-      int rc = ensure_ws(al, (size_t)g.grid * g.ws_stride * 4);
+      int rc = ensure_ws(al, (size_t)g.grid * g.ws_stride * 4, stream);
       if (rc != WFA_HIP_OK) return rc;
       rc = launch_general_dyn(al, b, stream, false, b->d_list_bytes, nullptr, b->n_bytes, g.ws_stride, g.grid, g.threads,
                               b->d_ovf_list[0], b->d_counters + CNT_OVF);
@@ -3013,7 +3017,7 @@ static int retry_overflows(wfa_hip_batch* b) {
       uint32_t* d_l = b->d_fb_list2[0];  // free to reuse: the first pass is complete
       HIP_TRY(al, hipMemcpy(d_l, l.data(), l.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
       Geometry g = plan_general(al, b, (uint32_t)l.size(), b->arena_fixed + b->arena_ints);
-      int rc = ensure_ws(al, (size_t)g.grid * g.ws_stride * 4);
+      int rc = ensure_ws(al, (size_t)g.grid * g.ws_stride * 4, stream);
       if (rc != WFA_HIP_OK) return rc;
       rc = launch_general_dyn(al, b, stream, kind == 0, d_l, nullptr, (uint32_t)l.size(), g.ws_stride, g.grid, g.threads,
                               b->d_ovf_list[nxt], b->d_counters + 1 + nxt);
@@ -3457,7 +3461,7 @@ static int tiny_band_args(wfa_hip_aligner* al, const TinyCall& k, const TinyLayo
     // whose slices exceed 256 MB or the free memory take the batch path, and so does a call whose workspace cannot be had)
     const size_t hist_bytes = (size_t)k.n * (size_t)ba.hist_stride * 4;
     if (hist_bytes > ((size_t)256 << 20) || (int64_t)hist_bytes > free_budget(al)) return 0;
-    if (ensure_ws(al, hist_bytes) != WFA_HIP_OK) return 0;
+    if (ensure_ws(al, hist_bytes, al->stream) != WFA_HIP_OK) return 0;
     ba.hist = al->ws;
   }
   return 1;
@@ -3587,7 +3591,7 @@ static int tiny_general(wfa_hip_aligner* al, const TinyCall& k, const TinyLayout
     stride = (int64_t)al->dcfg.scope * al->ncomp * L.max_width;
   }
   stride = (stride + 63) & ~63ll;
-  int rc = ensure_ws(al, (size_t)n * stride * 4);
+  int rc = ensure_ws(al, (size_t)n * stride * 4, al->stream);
   if (rc != WFA_HIP_OK) return rc;
   hipStream_t stream = al->stream;
   { const int wrc = wait_for_workspace(al, stream); if (wrc != WFA_HIP_OK) return wrc; }
@@ -3627,6 +3631,7 @@ static int align_tiny(wfa_hip_aligner* al, int64_t n, const uint8_t* seqs, const
   if (!al->tiny_h) {
     HIP_TRY(al, hipHostMalloc((void**)&al->tiny_h, TINY_BLOCK_BYTES, hipHostMallocMapped));
     HIP_TRY(al, hipMalloc((void**)&al->tiny_d, TINY_IN_BYTES));
+    HIP_TRY(al, poison_fill(al, al->tiny_d, TINY_IN_BYTES, al->stream));
   }
   if (!al->tiny_hd) HIP_TRY(al, hipHostGetDevicePointer((void**)&al->tiny_hd, al->tiny_h, 0));   // the pinned block as the device sees it
   if (L.band_form) { const int brc = tiny_band(al, k, L); if (brc != TINY_TO_GENERAL) return brc; }
