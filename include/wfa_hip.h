@@ -500,7 +500,7 @@ int wfa_hip_ops_summary(const uint8_t* ops, int64_t ops_len, int32_t plen, int32
  *
  * wfa_hip_pileup_read copies the rows [start, start + len) of sequence `seq` into counts (len x WFA_HIP_PILEUP_COLS, row-major);
  * WFA_HIP_EINVAL when the range leaves the sequence.  wfa_hip_pileup_clear zeroes the table (and drops the insertion log of a pileup
- * that tracks insertions, keeping that setting: "insertions" below).
+ * that tracks insertions, keeping that setting: "insertions" below; likewise the deletion log and the starts plane: "deletions" below).
  */
 #define WFA_HIP_PILEUP_COLS 8   /* A, C, G, T, other, deleted, insertion-before, mismatch */
 typedef struct wfa_hip_pileup wfa_hip_pileup_t;
@@ -544,8 +544,9 @@ int wfa_hip_ops_pileup(const uint8_t* ops, int64_t ops_len, const uint8_t* patte
  *
  * A site says that, and how often, reads insert in front of a base; WHAT they insert is the allele row of "insertions" below, from a
  * pileup made to track them; per-strand counts and a diploid genotype per site: "strands and genotypes" below; base
- * qualities: "base qualities" below.  Out of scope: multi-base events; more than one alternate allele per site, ploidy other than 2, a Fisher or other strand statistic (the
- * four counts are returned; the test is the caller's).
+ * qualities: "base qualities" below; a deletion of several bases as one event with its start and length: "deletions" below.
+ * Out of scope: multi-base substitutions, genotypes and strand counts per deletion allele; more than one alternate allele per site,
+ * ploidy other than 2, a Fisher or other strand statistic (the four counts are returned; the test is the caller's).
  *
  * The pileup keeps no reference letters and outlives its set, so both device calls take the set: the one the pileup was made over, or
  * one made again from the same sequences.  wfa_hip_pileup_calls writes out[0 .. len) for the rows [start, start + len) of sequence
@@ -623,7 +624,8 @@ int wfa_hip_sites_host(const int32_t* counts, const uint8_t* ref, int64_t len, i
  * although the rule needs no letters, so the call shape matches), with min_permille in 0..1000; a pileup that does not track ("... was
  * not made to track insertions"); bases_cap < 0; a NULL count or bases_count; NULL bases with bases_cap > 0.
  *
- * Out of scope: multi-base events; more than one alternate allele per site (here: per row), ploidy other than 2, a
+ * Out of scope: multi-base substitutions, genotypes and strand counts per deletion allele ("deletions" below records deletion runs);
+ * more than one alternate allele per site (here: per row), ploidy other than 2, a
  * Fisher or other strand statistic (the four counts are returned; the test is the caller's).  The log keeps no strand per record
  * ("strands and genotypes" below counts strands per base).  Reads that place the same inserted bases at
  * different rows of a repeat are different records at different rows: left-align the batch first ("left alignment" below), which puts
@@ -654,6 +656,96 @@ int wfa_hip_insertions_host(const int32_t* counts, int64_t len, int32_t seq, int
                             int64_t nrec, const int64_t* rec_row, const int32_t* rec_n, const int64_t* rec_off, const uint8_t* cols,
                             int64_t ncols, int64_t cap, int64_t* count, int32_t* rows, int64_t bases_cap, int64_t* bases_count,
                             uint8_t* bases);
+
+/* ---- deletions: what the reads delete, one deletion length per reported row -------------------------------- */
+
+/*
+ * Column 5 counts, per reference base, the reads that delete that base.  A pileup that tracks deletions also keeps every deletion as
+ * ONE event with a start and a length, in a log on the device, and reduces it there to one length per row.  It is opt-in: a pileup
+ * that does not ask for it behaves, allocates and launches exactly as before.  Integers only.  Op letters are WFA's: I is a text
+ * base the read lacks.
+ *
+ * RECORDS.  A pair contributes under exactly the conditions of wfa_hip_pileup_add (status 0, keep, its window inside its text).  Every
+ * maximal I run inside its aligned core (first M to last M) is one record (g, n):
+ *   g        the global row t_start + h of text j of the run's first deleted base
+ *   n        the run's length
+ * A D run next to an I run neither breaks nor joins the I run.  Two facts follow:
+ *   the number of records that COVER a row (g <= row < g + n) equals that row's column 5;
+ *   the number of records that START at a row is at most that row's column 5.
+ *
+ * STARTS PLANE.  A pileup that tracks deletions keeps one more int32 plane next to the table: starts[g] is the number of records
+ * that start at row g.  It is added to with integer adds, as the table is, so it does not depend on how a list is split or ordered.
+ *
+ * ALLELE OF A ROW.  The alleles are the distinct n among the records that start at the row, count(n) the multiplicity of n.  The
+ * row's allele is the n with the greatest count; ties go to the smaller n.  The order is total: the result never depends on the order
+ * in which records were stored, added or split over adds.
+ *
+ * REPORTED ROWS, parameters min_depth >= 1 and min_permille in 0..1000; depth as in "calls and sites", taken at row g; S = starts[g].
+ * A row is reported iff depth >= min_depth and
+ *   min_permille > 0:   S >= 1 && 1000 * S >= min_permille * depth      (64-bit products)
+ *   min_permille == 0:  2 * S > depth
+ * Its row is WFA_HIP_DELETION_COLS int32:
+ *   j, pos, depth, del_count (= S), allele_count, allele_len, alleles (the number of distinct lengths), overflow
+ * pos is the FIRST DELETED BASE, 0-based; VCF anchors a deletion one base earlier (POS = pos in VCF's 1-based numbering, REF = the
+ * base in front of the deletion plus the allele_len deleted bases; the reference has the letters, the log keeps none).  Rows come out
+ * in ascending (j, pos), always.  A row is selected by where it starts, so its deleted bases may reach past the queried range.  A row
+ * with S > WFA_HIP_DEL_MAX_READS is still reported, with overflow = 1 and allele_count = allele_len = alleles = 0: the limit (default
+ * 4096; read per call from the environment variable of that name, exactly as WFA_HIP_INS_MAX_READS is; at least 1) bounds the work of
+ * the one wave that serves a row.
+ *
+ * wfa_hip_pileup_track_deletions turns tracking on or off.  Allowed only while the pileup is empty: fresh, or just after
+ * wfa_hip_pileup_clear; otherwise WFA_HIP_EINVAL with a message.  Turning it on allocates the zeroed starts plane, 4 MORE BYTES PER TEXT
+ * BASE; a failed allocation returns WFA_HIP_EDEVICE, the message names the byte count, and the pileup is unchanged and not tracking.
+ * Turning it off frees the plane.  wfa_hip_pileup_clear drops the log, zeroes the plane and keeps the setting.  Tracking deletions does
+ * not depend on insertions, strands or qualities, and goes with every form of the add: wfa_hip_pileup_add, _add_strands and _add_quals
+ * make exactly their own adds to their tables — the table kernels are the ones a pileup without the log runs — and the deletion log
+ * gets a pass of its own: a count pass gives records and deleted bases per pair, an exclusive scan places the records, the two totals
+ * are downloaded, the log grows by doubling, the tables are added to, then every pair writes its records at its scanned offset and adds
+ * 1 to starts[g] per record.  COST: 16 BYTES PER RECORD in HBM until the pileup is cleared or destroyed, the 4 bytes per text base of
+ * the plane, 8 bytes of counts per pair (and the two 64-bit prefixes of the scans) of scratch during the add, one more pass over the op
+ * strings, and the 16-byte download.  The log grows before anything is written: a failed growth returns WFA_HIP_EDEVICE, the message
+ * names the byte count, and neither a table nor the log nor the plane has changed.  wfa_hip_pileup_deletion_stats gives the records
+ * of the log and the sum of their lengths (either pointer may be NULL); wfa_hip_pileup_read_deletion_starts copies starts[] of the
+ * rows [start, start + len) of sequence seq, as wfa_hip_pileup_read copies the table's; both WFA_HIP_EINVAL on a pileup that does not
+ * track.
+ *
+ * wfa_hip_pileup_deletions follows the conventions of wfa_hip_pileup_insertions: seq = -1 takes every sequence (start = 0, len = -1);
+ * *count is always the full number; only the first min(*count, cap) rows are written, and nothing behind them is touched; cap = 0
+ * with rows = NULL is the counting call.  Two calls give identical bytes.  Kernels: csrc/wfa_deletions.hpp, k_deletions.hip (the record
+ * side: a wave per pair, 64 ops per round, run starts from the I ballot and the last op of the round before, a run that crosses a
+ * round boundary carried wave-uniformly; rows selected by the chunk count / scan / scatter of the sites; a bucket per row sized from S
+ * by a scan; records find their row by binary search; a wave per row picks the length).  WFA_HIP_EINVAL, nothing launched, nothing
+ * written: whatever wfa_hip_pileup_insertions refuses of these arguments (min_permille in 0..1000), and a pileup that does not track
+ * ("... was not made to track deletions").
+ *
+ * Out of scope: multi-base substitutions; genotypes and strand counts per deletion allele; more than one allele per row.  Reads that
+ * place the same deleted bases at different rows of a repeat are different records at different rows: left-align the batch first
+ * ("left alignment" below), which puts every gap at the left end of its repeat as far as the read's own window and its own
+ * mismatches allow.
+ */
+#define WFA_HIP_DELETION_COLS 8    /* j, pos, depth, del_count, allele_count, allele_len, alleles, overflow */
+#define WFA_HIP_DEL_MAX_READS 4096 /* the default of the limit; the environment variable of this name replaces it per call */
+int wfa_hip_pileup_track_deletions(wfa_hip_pileup_t* pileup, int on);
+int wfa_hip_pileup_deletion_stats(wfa_hip_pileup_t* pileup, int64_t* records, int64_t* bases);
+int wfa_hip_pileup_read_deletion_starts(wfa_hip_pileup_t* pileup, int32_t seq, int64_t start, int64_t len, int32_t* out /* len */);
+int wfa_hip_pileup_deletions(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                             int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows /* cap x 8, nullable */);
+
+/* Host only, needs no GPU.  wfa_hip_ops_deletions: ONE pair's records by the rule above, from its op string: recs[r] = (h, n), h
+ * window-relative (the row is t_start + h).  *count is the full number; the first min(*count, cap) records are written, nothing behind
+ * them is touched.  Refused (WFA_HIP_EINVAL, nothing written): a negative length or capacity, a missing pointer, an op string that
+ * consumes more than plen pattern or tlen text bases.
+ * wfa_hip_deletions_host: the allele rule on `len` rows as wfa_hip_pileup_read returns them (counts: len x 8), their starts as
+ * wfa_hip_pileup_read_deletion_starts returns them (starts: len) and the records that start at those rows: record r starts at row
+ * rec_row[r] (relative to the first of the len rows; records outside are skipped) and has length rec_n[r].  Rows are numbered j = seq,
+ * pos = start + row; count, cap and rows as wfa_hip_pileup_deletions; WFA_HIP_DEL_MAX_READS is read from the environment in the same
+ * way.  Refused (WFA_HIP_EINVAL, nothing written): what wfa_hip_sites_host refuses (min_permille in 0..1000), a negative count or
+ * capacity, a missing pointer, a record of length below 1. */
+int wfa_hip_ops_deletions(const uint8_t* ops, int64_t ops_len, int32_t plen, int32_t tlen, int64_t cap, int64_t* count,
+                          int32_t* recs /* cap x 2: h, n */);
+int wfa_hip_deletions_host(const int32_t* counts, const int32_t* starts, int64_t len, int32_t seq, int64_t start, int32_t min_depth,
+                           int32_t min_permille, int64_t nrec, const int64_t* rec_row, const int32_t* rec_n, int64_t cap,
+                           int64_t* count, int32_t* rows);
 
 /* ---- strands and genotypes: per-strand counts, and a diploid genotype per variant site ---------------------- */
 
@@ -710,7 +802,8 @@ int wfa_hip_insertions_host(const int32_t* counts, int64_t len, int32_t seq, int
  * WFA_HIP_EINVAL, nothing launched, nothing written (wfa_hip_last_error names the values): whatever wfa_hip_pileup_sites refuses;
  * err_q outside 1..60; min_alt_strand < 0; min_alt_strand > 0 on a pileup that does not track strands.
  *
- * Out of scope: multi-base events; more than one alternate allele per site, ploidy other than 2, a Fisher or other strand statistic
+ * Out of scope: multi-base substitutions, genotypes and strand counts per deletion allele ("deletions" above records deletion runs,
+ * without a genotype); more than one alternate allele per site, ploidy other than 2, a Fisher or other strand statistic
  * (the four counts are returned; the test is the caller's).  Base qualities in the costs: "base qualities" below.
  */
 #define WFA_HIP_GENOTYPE_COLS 16  /* the 8 of a site, gt, gq, ins_gt, ins_gq, depth_fwd, ref_fwd, alt_fwd, ins_fwd */
@@ -787,7 +880,8 @@ int wfa_hip_genotypes_host(const int32_t* counts, const int32_t* counts_fwd /* n
  * 64-bit arithmetic, gq capped at 99.  The quality planes are read only at bases that are reported.  Refused as
  * wfa_hip_pileup_genotypes, and on a pileup that does not track qualities.
  *
- * Out of scope: mapping qualities in the costs, a prior, recalibration; multi-base events.
+ * Out of scope: mapping qualities in the costs, a prior, recalibration; of the multi-base events, substitutions and
+ * a genotype or strand counts per deletion allele (deletion runs themselves: "deletions" above).
  */
 #define WFA_HIP_MAX_QUALITY 93
 typedef struct wfa_hip_qualset wfa_hip_qualset_t;  /* the base qualities of a sequence set, resident in HBM */

@@ -140,6 +140,12 @@ SIGNATURES = {
     "wfa_hip_pileup_insertions": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i64, _i64p, _vp, _i64, _i64p, _vp]),
     "wfa_hip_ops_insertions": (_CTYPES, [_vp, _i64, _vp, _i32, _i32, _i64, _i64p, _vp, _i64, _i64p, _vp]),
     "wfa_hip_insertions_host": (_CTYPES, [_vp, _i64, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64p, _vp, _i64, _i64p, _vp]),
+    "wfa_hip_pileup_track_deletions": (_CTYPES, [_vp, _int]),
+    "wfa_hip_pileup_deletion_stats": (_CTYPES, [_vp, _i64p, _i64p]),
+    "wfa_hip_pileup_read_deletion_starts": (_CTYPES, [_vp, _i32, _i64, _i64, _vp]),
+    "wfa_hip_pileup_deletions": (_CTYPES, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i64, _i64p, _vp]),
+    "wfa_hip_ops_deletions": (_CTYPES, [_vp, _i64, _i32, _i32, _i64, _i64p, _vp]),
+    "wfa_hip_deletions_host": (_CTYPES, [_vp, _vp, _i64, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _i64, _i64p, _vp]),
     "wfa_hip_pileup_track_strands": (_CTYPES, [_vp, _int]),
     "wfa_hip_pileup_add_strands": (_CTYPES, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "wfa_hip_pileup_read_strand": (_CTYPES, [_vp, _i32, _i64, _i64, _int, _vp]),
@@ -184,6 +190,9 @@ SITE_COLUMNS = ("j", "pos", "ref", "alt", "depth", "ref_count", "alt_count", "in
 INSERTION_COLS = 8
 INSERTION_COLUMNS = ("j", "pos", "depth", "ins_count", "allele_count", "allele_len", "alleles", "overflow")
 INS_MAX_READS = 4096   # the default of WFA_HIP_INS_MAX_READS
+DELETION_COLS = 8
+DELETION_COLUMNS = ("j", "pos", "depth", "del_count", "allele_count", "allele_len", "alleles", "overflow")
+DEL_MAX_READS = 4096   # the default of WFA_HIP_DEL_MAX_READS
 GENOTYPE_COLS = 16
 MAX_QUALITY = 93   # WFA_HIP_MAX_QUALITY: raw phred, the printable range of FASTQ
 GENOTYPE_COLUMNS = SITE_COLUMNS + ("gt", "gq", "ins_gt", "ins_gq", "depth_fwd", "ref_fwd", "alt_fwd", "ins_fwd")
@@ -648,6 +657,45 @@ def insertions_host(counts, rec_row, rec_n, rec_off, cols, seq=0, start=0, min_d
     return count.value, rows, nbases.value, bases[:_letters_written(rows, bases.shape[0])]
 
 
+def ops_deletions(ops, plen, tlen):
+    """wfa_hip_ops_deletions (host only): one pair's deletion records from its op string: int32 of shape (records, 2) = (h, n), h
+    the window-relative row of the first deleted base."""
+    ops = np.frombuffer(bytes(ops), dtype=np.uint8) if not isinstance(ops, np.ndarray) else np.ascontiguousarray(ops, dtype=np.uint8)
+    head = (_ptr(ops) if ops.size else None, ops.size, int(plen), int(tlen))
+    count = ctypes.c_int64(0)
+    if lib().wfa_hip_ops_deletions(*head, 0, ctypes.byref(count), None) != OK:
+        raise ValueError("wfa_hip_ops_deletions: invalid arguments (an op string that outruns its pair?)")
+    recs = np.zeros((count.value, 2), np.int32)
+    if count.value:
+        lib().wfa_hip_ops_deletions(*head, count.value, ctypes.byref(count), _ptr(recs))
+    return recs
+
+
+def deletions_host(counts, starts, rec_row, rec_n, seq=0, start=0, min_depth=1, min_permille=500, cap=None):
+    """wfa_hip_deletions_host (host only): ``(count, rows)`` as ``Pileup.deletions`` gives them, for the rows ``counts`` (int32,
+    shape (len, 8)), their ``starts`` (int32, len) and the records that start at those rows (row relative to the first, length)."""
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    starts = np.ascontiguousarray(starts, dtype=np.int32)
+    if counts.ndim != 2 or counts.shape[1] != PILEUP_COLS or starts.shape != (counts.shape[0],):
+        raise ValueError("counts: int32 of shape (len, 8); starts: one value per row")
+    rec_row = np.ascontiguousarray(rec_row, dtype=np.int64)
+    rec_n = np.ascontiguousarray(rec_n, dtype=np.int32)
+    if rec_row.shape != rec_n.shape or rec_row.ndim != 1:
+        raise ValueError("rec_row and rec_n: one value per record")
+    head = (_ptr_or_null(counts), _ptr_or_null(starts), counts.shape[0], int(seq), int(start), int(min_depth), int(min_permille), rec_row.size,
+            _ptr_or_null(rec_row), _ptr_or_null(rec_n))
+    what = f"wfa_hip_deletions_host: invalid arguments (min_depth = {min_depth}, min_permille = {min_permille}, cap = {cap})"
+    count = ctypes.c_int64(0)
+    if cap is None:
+        if lib().wfa_hip_deletions_host(*head, 0, ctypes.byref(count), None) != OK:
+            raise ValueError(what)
+        cap = count.value
+    rows = np.zeros((max(int(cap), 0), DELETION_COLS), np.int32)
+    if lib().wfa_hip_deletions_host(*head, int(cap), ctypes.byref(count), _ptr_or_null(rows)) != OK:
+        raise ValueError(what)
+    return count.value, rows[:min(count.value, rows.shape[0])]
+
+
 def _calls_rows(counts, ref):
     counts = np.ascontiguousarray(counts, dtype=np.int32)
     ref = np.frombuffer(bytes(ref), dtype=np.uint8) if not isinstance(ref, np.ndarray) else np.ascontiguousarray(ref, dtype=np.uint8)
@@ -1071,11 +1119,13 @@ class CrossRun(_Handle):
 class Pileup(_Handle):
     """Per-base counters over a text SeqSet, resident in HBM (wfa_hip_pileup_t): 32 bytes per text base, int32 counters without an
     overflow check.  Stays valid after the set is closed.  ``tracking``: whether it keeps the insertion log (``track_insertions``);
+    ``deletions_tracked``: whether it keeps the deletion log and the starts plane (``track_deletions``: 4 more bytes per text base);
     ``strands``: whether it keeps the forward table (``track_strands``: 32 more bytes per text base); ``qualities``: whether it keeps
     the quality table (``track_qualities``: 32 more bytes per text base)."""
 
     _destroy = "wfa_hip_pileup_destroy"
     tracking = False
+    deletions_tracked = False
     strands = False
     qualities = False
 
@@ -1225,6 +1275,39 @@ class Pileup(_Handle):
                        ctypes.byref(nbases), _ptr_or_null(bases))
         rows = rows[:min(count.value, rows.shape[0])]
         return count.value, rows, nbases.value, bases[:_letters_written(rows, bases.shape[0])]
+
+
+    def track_deletions(self, on=True):
+        """wfa_hip_pileup_track_deletions: keep (or stop keeping) what the reads delete as runs; only while the pileup is empty."""
+        self._call("wfa_hip_pileup_track_deletions", self._h, 1 if on else 0)
+        self.deletions_tracked = bool(on)
+
+    def deletion_stats(self):
+        """wfa_hip_pileup_deletion_stats: ``(records, deleted bases)`` of the log."""
+        records, bases = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._call("wfa_hip_pileup_deletion_stats", self._h, ctypes.byref(records), ctypes.byref(bases))
+        return records.value, bases.value
+
+    def deletion_starts(self, seq, start=0, length=None):
+        """wfa_hip_pileup_read_deletion_starts: int32[length], the deletion records that start at each of the rows
+        [start, start + length) of one sequence (to its end when None)."""
+        seq, start, length = self._rows(seq, start, length)
+        out = np.zeros(max(length, 0), np.int32)
+        self._call("wfa_hip_pileup_read_deletion_starts", self._h, seq, start, length, _ptr_or_null(out))
+        return out
+
+    def deletions(self, texts, seq=-1, start=0, length=-1, min_depth=1, min_permille=500, cap=None):
+        """wfa_hip_pileup_deletions: ``(count, rows)``, rows int32 of shape (min(count, cap), 8) in ascending (j, pos); ``cap`` None: a
+        counting call, then one with the exact capacity.  seq = -1: every sequence; min_permille = 0: the majority rule."""
+        args = (self._h, texts._h, int(seq), int(start), int(length), int(min_depth), int(min_permille))
+        count = ctypes.c_int64(0)
+        if cap is None:
+            self._call("wfa_hip_pileup_deletions", *args, 0, ctypes.byref(count), None)
+            cap = count.value
+        rows = np.zeros((max(int(cap), 0), DELETION_COLS), np.int32)
+        if cap != 0:
+            self._call("wfa_hip_pileup_deletions", *args, int(cap), ctypes.byref(count), _ptr_or_null(rows))
+        return count.value, rows[:min(count.value, rows.shape[0])]
 
 
 class Placer(_Handle):

@@ -388,6 +388,8 @@ class Pileup(_Closing):
     ``sites`` reduce the table on the GPU against the reference letters: a byte per base or a row per variant site comes back.  A
     pileup made with ``insertions=True`` also keeps what the reads insert (about 24 bytes per insertion and 1 byte per inserted base
     on the GPU): ``insertions`` gives one allele per insertion site, ``consensus(insertions=True)`` splices them in.  A pileup made
+    with ``deletions=True`` also keeps every deletion as one event (16 bytes per deletion and 4 bytes per text base on the GPU):
+    ``deletions`` gives one deletion length per site where deletions start, ``deletion_starts(j)`` how many start at each base.  A pileup made
     with ``strands=True`` also counts the forward reads on their own (32 more bytes per text base): ``counts`` / ``depth`` take
     ``strand="+"`` / ``"-"``, ``genotypes`` reports the forward counts and can ask for both strands (``min_alt_strand``)."""
 
@@ -396,6 +398,7 @@ class Pileup(_Closing):
     CALL_CODES = _native.CALL_CODES
     SITE_COLUMNS = _native.SITE_COLUMNS
     INSERTION_COLUMNS = _native.INSERTION_COLUMNS
+    DELETION_COLUMNS = _native.DELETION_COLUMNS
     _OWNS = "_pileup"
 
     def __init__(self, native_pileup, score, status, aligner=None):
@@ -530,7 +533,7 @@ class Pileup(_Closing):
         allele is the inserted sequence most of the row's inserting reads carry (``allele_count`` of ``ins_count``; ties go to the
         shorter, then to the alphabetically smaller in the order A C G T N); ``alleles``: how many different ones they carry.  A row
         with more than ``WFA_HIP_INS_MAX_READS`` (4096) inserting reads has ``overflow`` = 1, zeros and ``""``.  Multi-base
-        events, a strand per inserting read and more than one allele per row are out of scope."""
+        substitutions, a strand per inserting read and more than one allele per row are out of scope."""
         p = self._tracking()
         if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 1 <= round(float(min_frac) * 1000) <= 1000:
             raise ValueError(f"min_frac = {min_frac!r} is out of range (0.001 .. 1)")
@@ -549,13 +552,52 @@ class Pileup(_Closing):
         out["seq"] = [text[int(e - n):int(e)] for e, n in zip(ends, rows[:, 5])]
         return out
 
+    def _tracking_deletions(self):
+        """The open native pileup, which must have been made with ``deletions=True``."""
+        p = self._open()
+        if not p.deletions_tracked:
+            raise ValueError("this pileup was not made to track deletions: make it with pileup(..., deletions=True)")
+        return p
+
+    def deletions(self, texts, j=None, start=0, stop=None, min_depth=1, min_frac=0.5):
+        """What the reads delete, reduced on the GPU to one deletion per site (a pileup made with ``deletions=True``): a dict of int32
+        arrays ``DELETION_COLUMNS`` in ascending (j, pos).  ``pos`` is the first deleted base of text ``j``, 0-based (VCF anchors the
+        event one base earlier); ``del_count`` the reads whose deletion starts there.  Rows: the bases covered by at least
+        ``min_depth`` reads where at least ``min_frac`` of them start a deletion (``min_frac``, rounded to permille, ``j``, ``start``,
+        ``stop`` as for ``sites``; ``min_frac=0``: more than half of them).  A row is selected by where it starts, so its deleted bases
+        may reach past ``stop``.  ``allele_len`` is the length most of those reads delete (``allele_count`` of ``del_count``; ties go
+        to the shorter); ``alleles``: how many different lengths they delete.  A row with more than ``WFA_HIP_DEL_MAX_READS`` (4096)
+        such reads has ``overflow`` = 1 and zeros.  The deleted letters are the reference's: ``texts[j][pos:pos + allele_len]``.
+        Multi-base substitutions, genotypes and strand counts per deletion allele and more than one allele per row are out of scope."""
+        p = self._tracking_deletions()
+        if isinstance(min_frac, bool) or not isinstance(min_frac, (int, float, np.integer, np.floating)) or not 0 <= round(float(min_frac) * 1000) <= 1000:
+            raise ValueError(f"min_frac = {min_frac!r} is out of range (0 .. 1)")
+        permille = int(round(float(min_frac) * 1000))
+        if j is None:
+            if start != 0 or stop is not None:
+                raise ValueError("j = None takes every text: start and stop go with one text")
+            seq, start, length = -1, 0, -1
+        else:
+            seq, start, stop = self._range(p, j, start, stop)
+            length = stop - start
+        _, rows = self._with_texts(p, texts, min_depth, lambda t: p.deletions(t, seq, start, length, int(min_depth), permille))
+        return _columns(rows, self.DELETION_COLUMNS)
+
+    def deletion_starts(self, j, start=0, stop=None):
+        """int32 array of length stop - start: how many reads' deletions START at each of the rows [start, stop) of text ``j`` (a
+        pileup made with ``deletions=True``, else ValueError).  The reads that delete a base at all are ``counts(j)[:, 5]``."""
+        p = self._tracking_deletions()
+        seq, start, stop = self._range(p, j, start, stop)
+        return p.deletion_starts(seq, start, stop - start)
+
     def sites(self, texts, j=None, start=0, stop=None, min_depth=1, min_frac=0.5):
         """The bases where the reads disagree with the reference, found on the GPU (only their rows come back): a dict of int32 arrays
         ``SITE_COLUMNS`` in ascending (j, pos).  Among bases covered by at least ``min_depth`` reads, a site is one whose strongest
         column other than the reference's letter holds at least ``min_frac`` of the covering reads (``alt`` its column in
         ``CALL_CODES``, 5 = deleted; ``alt_count``), or where at least ``min_frac`` of them insert in front of the base (``ins_count``;
         ``alt`` = -1 and ``alt_count`` = 0 when only this holds).  ``min_frac`` is rounded to permille.  ``j=None``: every text (then
-        ``start`` / ``stop`` must be left alone); otherwise the rows [start, stop) of text ``j``.  Multi-base events are
+        ``start`` / ``stop`` must be left alone); otherwise the rows [start, stop) of text ``j``.  A deletion of several
+        bases is a site per base here and one event in ``deletions``, on a pileup made with ``deletions=True``; multi-base substitutions are
         out of scope; base qualities: ``pileup(..., qualities=)``; what was inserted: ``insertions``, on a pileup made with ``insertions=True``; strands and genotypes:
         ``genotypes``."""
         p = self._open()
@@ -1470,17 +1512,20 @@ class WavefrontAligner:
 
     def pileup(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
                text_len=None, reverse=None, min_score=None, insertions=False, left_align=False, strands=False, qualities=None,
-               min_base_quality=0, quality_cap=40):
+               min_base_quality=0, quality_cap=40, deletions=False):
         """Align the listed windows as ``align_windows`` does (same arguments, same checks; scope must be "full") and pile the
         alignments up over the TEXT sequences on the GPU: the patterns are reads, the texts references.  Every pair whose status is
         0 (and whose score is at least ``min_score``, when given) adds the ops of its aligned core — first M to last M — to the
         text bases they cover; neither op strings nor their run-length encoding leave the device (csrc/wfa_pileup.hpp).
         ``texts=None`` piles up over ``patterns``.  ``insertions=True``: the pileup also keeps what the reads insert (a log on the
         GPU, about 24 bytes per insertion and 1 byte per inserted base, and a second pass over the op strings), for
-        ``Pileup.insertions`` and ``Pileup.consensus(insertions=True)``.  ``left_align=True``: every op string is left-aligned on
+        ``Pileup.insertions`` and ``Pileup.consensus(insertions=True)``.  ``deletions=True``: the pileup also keeps every deletion
+        as one event with its start and length (a log on the GPU, 16 bytes per deletion and 4 bytes per text base, and one more pass
+        over the op strings), for ``Pileup.deletions`` and ``Pileup.deletion_starts``; it combines freely with the other options.
+        ``left_align=True``: every op string is left-aligned on
         the GPU before it is piled up (``left_align_ops`` states the rule), so a gap inside a homopolymer or tandem repeat is
         counted at the left end of the repeat, where VCF puts it, and reads that stopped at different places of one repeat agree
-        as far as their own letters allow; tables, ``sites``, ``insertions`` and ``consensus(insertions=True)`` follow.
+        as far as their own letters allow; tables, ``sites``, ``insertions``, ``deletions`` and ``consensus(insertions=True)`` follow.
         ``strands=True``: the pileup also counts the forward reads (``reverse[q]`` == 0; every read when ``reverse`` is None) in a
         second table of 32 more bytes per text base, for ``counts(strand=...)`` and the strand columns and filter of
         ``Pileup.genotypes``; without it nothing more is allocated or launched.
@@ -1493,7 +1538,7 @@ class WavefrontAligner:
         ``qualities`` are a ValueError.
 
         Returns a ``Pileup`` (``score``, ``status``, ``counts(j)``, ``depth(j)``, ``calls()``, ``consensus()``, ``sites()``,
-        ``genotypes()``, ``insertions()``, ``quality_sums(j)``, ``close()``; a context manager), which stays
+        ``genotypes()``, ``insertions()``, ``deletions()``, ``quality_sums(j)``, ``close()``; a context manager), which stays
         valid after the sets are closed.  With ``devices=[...]`` the first device runs it."""
         if self._cfg.scope != 1:
             raise ValueError("pileup needs scope='full'")
@@ -1524,6 +1569,8 @@ class WavefrontAligner:
             rev = w.arrays[6]
             if insertions:
                 table.track_insertions(True)
+            if deletions:
+                table.track_deletions(True)
             if strands:
                 table.track_strands(True)
             qset = None

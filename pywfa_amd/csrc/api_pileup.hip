@@ -1,5 +1,6 @@
 // api_pileup.hip — pileups and calls of libwfa_hip.so (the C ABI declared in include/wfa_hip.h).
 #include "host_sets.hpp"
+#include "wfa_deletions.hpp"
 #include "wfa_insertions.hpp"
 #include "wfa_leftalign.hpp"
 
@@ -57,7 +58,15 @@ struct wfa_hip_pileup {
   // base qualities (include/wfa_hip.h, "base qualities"): the quality table, of the table's size and layout, while tracking is on
   bool quals = false;
   int32_t* d_qtab = nullptr;
+  // the deletion log and the starts plane (include/wfa_hip.h, "deletions"; csrc/wfa_deletions.hpp): the log grown by doubling, the
+  // plane one counter per text base while tracking is on
+  bool dels = false;
+  wfa::DelRecord* d_del = nullptr;
+  int32_t* d_starts = nullptr;
+  int64_t ndel = 0, ndel_bases = 0, cap_del = 0;
 };
+
+static size_t pileup_plane_bytes(const wfa_hip_pileup* p) { return (size_t)std::max<int64_t>(p->total, 1) * sizeof(int32_t); }
 
 static size_t pileup_table_bytes(const wfa_hip_pileup* p) { return (size_t)std::max<int64_t>(p->total, 1) * WFA_PILEUP_COLS * sizeof(int32_t); }
 
@@ -70,6 +79,8 @@ extern "C" void wfa_hip_pileup_destroy(wfa_hip_pileup_t* p) {
   if (p->d_qtab) (void)hipFree(p->d_qtab);
   if (p->d_rec) (void)hipFree(p->d_rec);
   if (p->d_ins) (void)hipFree(p->d_ins);
+  if (p->d_del) (void)hipFree(p->d_del);
+  if (p->d_starts) (void)hipFree(p->d_starts);
   pool_release(al, p->d_off); pool_release(al, p->d_len);
   destroy_end(p);
 }
@@ -111,8 +122,10 @@ extern "C" int wfa_hip_pileup_clear(wfa_hip_pileup_t* p) {
   HIP_TRY(al, hipMemsetAsync(p->d_table, 0, pileup_table_bytes(p), al->stream));
   if (p->d_fwd) HIP_TRY(al, hipMemsetAsync(p->d_fwd, 0, pileup_table_bytes(p), al->stream));
   if (p->d_qtab) HIP_TRY(al, hipMemsetAsync(p->d_qtab, 0, pileup_table_bytes(p), al->stream));
+  if (p->d_starts) HIP_TRY(al, hipMemsetAsync(p->d_starts, 0, pileup_plane_bytes(p), al->stream));
   HIP_TRY(al, hipStreamSynchronize(al->stream));
   p->nrec = p->nins = 0;   // (the log's blocks stay for the next adds)
+  p->ndel = p->ndel_bases = 0;
   p->added = false;
   return WFA_HIP_OK;
 }
@@ -124,9 +137,9 @@ extern "C" int wfa_hip_pileup_track_insertions(wfa_hip_pileup_t* p, int on) {
   return WFA_HIP_OK;
 }
 
-// a second table of the table's size and layout (`what`: "forward" or "quality"; `kind`: "strand" or "quality") kept or dropped, only
-// while the pileup is empty; a failure leaves the pileup as it was
-static int pileup_track_table(wfa_hip_pileup* p, int on, int32_t** table, bool* tracking, const char* what, const char* kind) {
+// a second table of the table's size and layout (`what`: "forward" or "quality"; `kind`: "strand" or "quality"), or with `plane` one
+// plane of it (the deletion starts), kept or dropped, only while the pileup is empty; a failure leaves the pileup as it was
+static int pileup_track_table(wfa_hip_pileup* p, int on, int32_t** table, bool* tracking, const char* what, const char* kind, bool plane = false) {
   wfa_hip_aligner* al = p->al;
   if (p->added) return fail_inval(al, "pileup: %s tracking is chosen while the pileup is empty (fresh, or just cleared); this one has been added to", kind);
   if ((on != 0) == *tracking) return WFA_HIP_OK;
@@ -137,10 +150,11 @@ static int pileup_track_table(wfa_hip_pileup* p, int on, int32_t** table, bool* 
     *table = nullptr; *tracking = false;
     return WFA_HIP_OK;
   }
-  const size_t bytes = pileup_table_bytes(p);
+  const size_t bytes = plane ? pileup_plane_bytes(p) : pileup_table_bytes(p);
   int32_t* fresh = nullptr;
   if (hipMalloc((void**)&fresh, bytes) != hipSuccess)
-    return fail_alloc(al, (void**)&fresh, "pileup %s table: hipMalloc of %zu bytes failed (32 more bytes per text base, %lld bases)", what, bytes, (long long)p->total);
+    return fail_alloc(al, (void**)&fresh, "pileup %s %s: hipMalloc of %zu bytes failed (%d more bytes per text base, %lld bases)", what,
+                      plane ? "plane" : "table", bytes, plane ? 4 : 32, (long long)p->total);
   hipError_t e = poison_fill(al, fresh, bytes, al->stream);
   if (e == hipSuccess) e = hipMemsetAsync(fresh, 0, bytes, al->stream);
   const hipError_t e2 = hipStreamSynchronize(al->stream);
@@ -159,6 +173,19 @@ extern "C" int wfa_hip_pileup_track_qualities(wfa_hip_pileup_t* p, int on) {
   return pileup_track_table(p, on, &p->d_qtab, &p->quals, "quality", "quality");
 }
 
+extern "C" int wfa_hip_pileup_track_deletions(wfa_hip_pileup_t* p, int on) {
+  if (!p) return WFA_HIP_EINVAL;
+  return pileup_track_table(p, on, &p->d_starts, &p->dels, "deletion starts", "deletion", true);
+}
+
+extern "C" int wfa_hip_pileup_deletion_stats(wfa_hip_pileup_t* p, int64_t* records, int64_t* bases) {
+  if (!p) return WFA_HIP_EINVAL;
+  if (!p->dels) return fail_inval(p->al, "pileup: this pileup was not made to track deletions");
+  if (records) *records = p->ndel;
+  if (bases) *bases = p->ndel_bases;
+  return WFA_HIP_OK;
+}
+
 extern "C" int wfa_hip_pileup_insertion_stats(wfa_hip_pileup_t* p, int64_t* records, int64_t* bases) {
   if (!p) return WFA_HIP_EINVAL;
   if (!p->track) return fail_inval(p->al, "pileup: this pileup was not made to track insertions");
@@ -169,7 +196,8 @@ extern "C" int wfa_hip_pileup_insertion_stats(wfa_hip_pileup_t* p, int64_t* reco
 
 // room for `need` elements in a block of the log that holds `have` of them: a new block of twice the size (of the exact size when that
 // fails), the old contents copied over.  A failure leaves the block as it was.
-template <class T> static int ins_log_grow(wfa_hip_aligner* al, T** block, int64_t* cap, int64_t have, int64_t need, const char* what) {
+template <class T> static int ins_log_grow(wfa_hip_aligner* al, T** block, int64_t* cap, int64_t have, int64_t need, const char* what,
+                                           const char* log = "insertion") {
   if (need <= *cap) return WFA_HIP_OK;
   T* fresh = nullptr;
   int64_t want = std::max<int64_t>({need, 2 * *cap, 1024});
@@ -177,7 +205,7 @@ template <class T> static int ins_log_grow(wfa_hip_aligner* al, T** block, int64
     (void)hipGetLastError();
     want = need;
     if (hipMalloc((void**)&fresh, (size_t)want * sizeof(T)) != hipSuccess)
-      return fail_alloc(al, (void**)&fresh, "pileup insertion log: hipMalloc of %zu bytes failed (%s, %lld of them)", (size_t)want * sizeof(T), what, (long long)want);
+      return fail_alloc(al, (void**)&fresh, "pileup %s log: hipMalloc of %zu bytes failed (%s, %lld of them)", log, (size_t)want * sizeof(T), what, (long long)want);
   }
   // (WFA_HIP_POISON: the fill first, the old contents over it — the grown tail stays filled until an add writes it)
   { const hipError_t e = poison_fill(al, fresh, (size_t)want * sizeof(T), al->stream); if (e != hipSuccess) { (void)hipFree(fresh); HIP_TRY(al, e); } }
@@ -223,6 +251,36 @@ static int pileup_add_tracked(wfa_hip_pileup* p, StreamScratch& sc, const wfa::P
                       : wfa::launch_pileup_track(a, g, al->cu_count, al->stream),
                   "pileup kernel launch failed");
   if (rc == WFA_HIP_OK) { p->nrec += (int64_t)totals[0]; p->nins += (int64_t)totals[1]; }
+  return rc;
+}
+
+// The deletion log's pass of an add (csrc/wfa_deletions.hpp), before the table kernel of whatever form: count, the two scans, the
+// 16-byte download, the growth; *totals = {records, deleted bases} of the batch.  Nothing has been written when it fails.
+static int pileup_deletions_count(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a, wfa::DelLogArgs* g, uint64_t* totals) {
+  wfa_hip_aligner* al = p->al;
+  const size_t n = (size_t)a.npairs;
+  memset(g, 0, sizeof(*g));
+  if (sc.alloc(&g->pair_count, n) || sc.alloc(&g->rec_off, n + 1) || sc.alloc(&g->base_off, n + 1)) return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipMemsetAsync(g->pair_count, 0, n * sizeof(wfa::DelPairCount), al->stream));
+  totals[0] = totals[1] = 0;
+  ReduceTimer timer(al, "pileup deletion count", a.npairs);
+  const int lrc = wfa::launch_del_count(a, *g, al->cu_count, al->stream);
+  timer.stop();
+  if (lrc != 0) { al->err = "pileup deletion count kernel launch failed"; return WFA_HIP_EDEVICE; }
+  if (sc.download(&totals[0], g->rec_off + n, 1) || sc.download(&totals[1], g->base_off + n, 1)) return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  const int rc = ins_log_grow(al, &p->d_del, &p->cap_del, p->ndel, p->ndel + (int64_t)totals[0], "records of 16 bytes", "deletion");
+  if (rc != WFA_HIP_OK) return rc;
+  g->records = p->d_del; g->rec_base = p->ndel; g->rec_cap = p->cap_del; g->starts = p->d_starts;
+  return WFA_HIP_OK;
+}
+
+// ... and behind the table kernel: the records at their scanned offsets, the starts plane
+static int pileup_deletions_scatter(wfa_hip_pileup* p, const wfa::PileupArgs& a, const wfa::DelLogArgs& g, const uint64_t* totals) {
+  wfa_hip_aligner* al = p->al;
+  ReduceTimer timer(al, "pileup deletion scatter", a.npairs);
+  const int rc = launch_end(al, &timer, wfa::launch_del_scatter(a, g, al->cu_count, al->stream), "pileup deletion scatter kernel launch failed");
+  if (rc == WFA_HIP_OK) { p->ndel += (int64_t)totals[0]; p->ndel_bases += (int64_t)totals[1]; }
   return rc;
 }
 
@@ -293,27 +351,38 @@ static int pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j,
   a.npairs = n; a.j = d_j; a.t_start = d_ts; a.keep = d_keep;
   a.seq_off = p->d_off; a.seq_len = p->d_len; a.nseq = p->nseq; a.total = p->total; a.table = p->d_table;
   const wfa::PileupStrandArgs s{d_rev, p->d_fwd};
-  if (ql) {
-    int32_t *d_i = nullptr, *d_ps = nullptr;
-    if (!stranded && sc.upload_opt(&d_rev, reverse, (size_t)n)) return WFA_HIP_EDEVICE;
-    if (sc.upload(&d_i, ql->i, (size_t)n) || sc.upload_opt(&d_ps, ql->p_start, (size_t)n)) return WFA_HIP_EDEVICE;
-    const wfa::PileupStrandArgs sq{d_rev, p->d_fwd};
-    const wfa::PileupQualArgs u{ql->set->d_quals, ql->set->d_off, ql->set->d_len, ql->set->n, d_i, d_ps, d_rev,
-                                ql->min_base_quality, ql->quality_cap, p->d_qtab};
-    if (p->track) return pileup_add_tracked(p, sc, a, stranded ? &sq : nullptr, &u);
-    ReduceTimer timer(al, "pileup qualities", n);
+  // the table kernel of the pileup's form (and the insertion log's passes)
+  const auto table_add = [&]() -> int {
+    if (ql) {
+      int32_t *d_i = nullptr, *d_ps = nullptr;
+      if (!stranded && sc.upload_opt(&d_rev, reverse, (size_t)n)) return WFA_HIP_EDEVICE;
+      if (sc.upload(&d_i, ql->i, (size_t)n) || sc.upload_opt(&d_ps, ql->p_start, (size_t)n)) return WFA_HIP_EDEVICE;
+      const wfa::PileupStrandArgs sq{d_rev, p->d_fwd};
+      const wfa::PileupQualArgs u{ql->set->d_quals, ql->set->d_off, ql->set->d_len, ql->set->n, d_i, d_ps, d_rev,
+                                  ql->min_base_quality, ql->quality_cap, p->d_qtab};
+      if (p->track) return pileup_add_tracked(p, sc, a, stranded ? &sq : nullptr, &u);
+      ReduceTimer timer(al, "pileup qualities", n);
+      p->added = true;
+      return launch_end(al, &timer, wfa::launch_pileup_quals(a, stranded ? &sq : nullptr, u, al->cu_count, al->stream), "pileup kernel launch failed");
+    }
+    if (p->track) return pileup_add_tracked(p, sc, a, stranded ? &s : nullptr);
+    if (stranded) {
+      ReduceTimer timer(al, "pileup stranded", n);
+      p->added = true;
+      return launch_end(al, &timer, wfa::launch_pileup_strands(a, s, al->cu_count, al->stream), "pileup kernel launch failed");
+    }
+    ReduceTimer timer(al, "pileup", n);
     p->added = true;
-    return launch_end(al, &timer, wfa::launch_pileup_quals(a, stranded ? &sq : nullptr, u, al->cu_count, al->stream), "pileup kernel launch failed");
-  }
-  if (p->track) return pileup_add_tracked(p, sc, a, stranded ? &s : nullptr);
-  if (stranded) {
-    ReduceTimer timer(al, "pileup stranded", n);
-    p->added = true;
-    return launch_end(al, &timer, wfa::launch_pileup_strands(a, s, al->cu_count, al->stream), "pileup kernel launch failed");
-  }
-  ReduceTimer timer(al, "pileup", n);
-  p->added = true;
-  return launch_end(al, &timer, wfa::launch_pileup(a, al->cu_count, al->stream), "pileup kernel launch failed");   // (the caller's arrays are read by the copies above)
+    return launch_end(al, &timer, wfa::launch_pileup(a, al->cu_count, al->stream), "pileup kernel launch failed");   // (the caller's arrays are read by the copies above)
+  };
+  if (!p->dels) return table_add();
+  // the deletion log (csrc/wfa_deletions.hpp): its room first, so that a failed growth changes nothing; its records behind the table kernel
+  wfa::DelLogArgs dg;
+  uint64_t dtotals[2];
+  rc = pileup_deletions_count(p, sc, a, &dg, dtotals);
+  if (rc == WFA_HIP_OK) rc = table_add();
+  if (rc == WFA_HIP_OK) rc = pileup_deletions_scatter(p, a, dg, dtotals);
+  return rc;
 }
 
 extern "C" int wfa_hip_pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j, const int32_t* t_start, const uint8_t* keep) {
@@ -627,4 +696,66 @@ extern "C" int wfa_hip_pileup_insertions(wfa_hip_pileup_t* p, const wfa_hip_seqs
   if (sc.alloc(&a.letters, (size_t)fit)) return WFA_HIP_EDEVICE;
   ReduceTimer timer(al, "insertions letters", k, "rows");
   return calls_launched(sc, timer, wfa::launch_ins_letters(a, k, fit, al->cu_count, al->stream), "insertions letters kernel launch failed", bases, a.letters, (size_t)fit);
+}
+
+// ---- what the reads delete: one length per reported row (include/wfa_hip.h, "deletions"; csrc/wfa_deletions.hpp, k_deletions.hip) ---------
+static_assert(WFA_DELETION_COLS == WFA_HIP_DELETION_COLS, "columns of the kernels and of the ABI");
+
+extern "C" int wfa_hip_pileup_read_deletion_starts(wfa_hip_pileup_t* p, int32_t seq, int64_t start, int64_t len, int32_t* out) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (pileup_check_rows(p, seq, start, len) != WFA_HIP_OK) return WFA_HIP_EINVAL;
+  if (!p->dels) return fail_inval(al, "pileup: this pileup was not made to track deletions");
+  if (len == 0) return WFA_HIP_OK;
+  if (!out) return fail_inval(al, "pileup: null output");
+  HIP_TRY(al, hipSetDevice(al->device));
+  HIP_TRY(al, hipMemcpyAsync(out, p->d_starts + p->h_off[(size_t)seq] + start, (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost, al->stream));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_pileup_deletions(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                        int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  int64_t g0 = 0, n = 0;
+  const int rc = calls_check(p, texts, true, seq, start, len, min_depth, min_permille, cap, &g0, &n, 0);
+  if (rc != WFA_HIP_OK) return rc;
+  if (!p->dels) return fail_inval(al, "pileup: this pileup was not made to track deletions");
+  if (!count) return fail_inval(al, "pileup: null count");
+  if (cap > 0 && !rows) return fail_inval(al, "pileup: null rows with cap > 0");
+  HIP_TRY(al, hipSetDevice(al->device));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  *count = 0;
+  if (n == 0) return WFA_HIP_OK;
+  // records per row one wave reduces: read per call, as the chunk is
+  const char* env = getenv("WFA_HIP_DEL_MAX_READS");
+  const int64_t asked = env && *env ? atoll(env) : WFA_HIP_DEL_MAX_READS;
+  StreamScratch sc{al};
+  wfa::DelArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = calls_args(p, texts, g0, n, min_depth, min_permille);
+  a.starts = p->d_starts;
+  a.max_reads = (int32_t)std::min<int64_t>(INT32_MAX, std::max<int64_t>(1, asked));
+  a.records = p->d_del; a.nrec = p->ndel;
+  if (calls_chunks(sc, &a.c)) return WFA_HIP_EDEVICE;
+  uint64_t nsel = 0;
+  {
+    ReduceTimer timer(al, "deletions count", n, "bases");
+    const int crc = calls_launched(sc, timer, wfa::launch_del_select_count(a, al->stream), "deletions count kernel launch failed", &nsel, a.c.chunk_off + a.c.chunks, 1);
+    if (crc != WFA_HIP_OK) return crc;
+  }
+  *count = (int64_t)nsel;
+  const int64_t k = std::min<int64_t>((int64_t)nsel, cap);
+  if (k == 0) return WFA_HIP_OK;
+  a.nsel = (int64_t)nsel;
+  const size_t ns = (size_t)nsel;
+  if (sc.alloc(&a.sel_g, ns) || sc.alloc(&a.bucket_size, ns) || sc.alloc(&a.bucket_off, ns + 1) || sc.alloc(&a.bucket_fill, ns) ||
+      sc.alloc(&a.bucket, (size_t)p->ndel) || sc.alloc(&a.rows, ns * WFA_DELETION_COLS))
+    return WFA_HIP_EDEVICE;
+  HIP_TRY(al, hipMemsetAsync(a.bucket_fill, 0, ns * sizeof(uint32_t), al->stream));
+  ReduceTimer timer(al, "deletions reduce", (int64_t)nsel, "rows");
+  int lrc = wfa::launch_del_select(a, al->stream);
+  if (lrc == 0) lrc = wfa::launch_del_reduce(a, al->cu_count, al->stream);
+  return calls_launched(sc, timer, lrc, "deletions reduce kernel launch failed", rows, a.rows, (size_t)k * WFA_DELETION_COLS);
 }

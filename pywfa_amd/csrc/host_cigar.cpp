@@ -463,3 +463,70 @@ extern "C" int wfa_hip_insertions_host(const int32_t* counts, int64_t len, int32
   *count = n; *bases_count = nb;
   return WFA_HIP_OK;
 }
+
+// ---- deletions: a pair's records, and the allele rule over rows, starts and records (the kernels: wfa_deletions.hpp, k_deletions.hip) ----
+
+extern "C" int wfa_hip_ops_deletions(const uint8_t* ops, int64_t ops_len, int32_t plen, int32_t tlen, int64_t cap, int64_t* count, int32_t* recs) {
+  if (ops_len < 0 || plen < 0 || tlen < 0 || (ops_len > 0 && !ops) || cap < 0 || !count || (cap > 0 && !recs)) return WFA_HIP_EINVAL;
+  // an op string that outruns its pair is refused before anything is written (as wfa_hip_ops_pileup refuses it)
+  int64_t nv = 0, nh = 0;
+  for (int64_t i = 0; i < ops_len; ++i) { const uint8_t c = ops[i]; nv += (c == 'M' || c == 'X' || c == 'D'); nh += (c == 'M' || c == 'X' || c == 'I'); }
+  if (nv > plen || nh > tlen) return WFA_HIP_EINVAL;
+  int64_t nrec = 0, first = 0, last = -1;
+  if (aligned_core(ops, ops_len, &first, &last)) {
+    int32_t h = 0;
+    for (int64_t i = 0; i <= last;) {
+      const uint8_t c = ops[i];
+      if (c != 'I') { h += (c == 'M' || c == 'X'); ++i; continue; }
+      int64_t e = i;
+      while (ops[e] == 'I') ++e;   // (the core ends with an M)
+      const int32_t n = (int32_t)(e - i);
+      if (i > first) {             // a run of the core: one record, whatever stands beside it (a D run neither breaks nor joins it)
+        if (nrec < cap) { recs[2 * nrec] = h; recs[2 * nrec + 1] = n; }
+        ++nrec;
+      }
+      h += n; i = e;
+    }
+  }
+  *count = nrec;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_deletions_host(const int32_t* counts, const int32_t* starts, int64_t len, int32_t seq, int64_t start, int32_t min_depth,
+                                      int32_t min_permille, int64_t nrec, const int64_t* rec_row, const int32_t* rec_n, int64_t cap,
+                                      int64_t* count, int32_t* rows) {
+  if (len < 0 || min_depth < 1 || min_permille < 0 || min_permille > 1000 || nrec < 0 || cap < 0 || !count || (len > 0 && (!counts || !starts)) ||
+      (nrec > 0 && (!rec_row || !rec_n)) || (cap > 0 && !rows))
+    return WFA_HIP_EINVAL;
+  for (int64_t r = 0; r < nrec; ++r)
+    if (rec_n[r] < 1) return WFA_HIP_EINVAL;
+  const char* env = getenv("WFA_HIP_DEL_MAX_READS");
+  const int64_t max_reads = std::max<int64_t>(1, env && *env ? atoll(env) : WFA_HIP_DEL_MAX_READS);
+  // the lengths of the records that start at every row, in the order they were given (the rule does not depend on it)
+  std::vector<std::vector<int32_t>> at((size_t)len);
+  for (int64_t r = 0; r < nrec; ++r)
+    if (rec_row[r] >= 0 && rec_row[r] < len) at[(size_t)rec_row[r]].push_back(rec_n[r]);
+  int64_t n = 0;
+  for (int64_t g = 0; g < len; ++g) {
+    const int32_t* c = counts + g * WFA_HIP_PILEUP_COLS;
+    const int64_t depth = depth_of(c), S = starts[g];
+    if (depth < min_depth) continue;
+    if (min_permille > 0 ? !(S >= 1 && 1000 * S >= (int64_t)min_permille * depth) : !(2 * S > depth)) continue;
+    const bool overflow = S > max_reads;
+    std::map<int32_t, int64_t> alleles;
+    if (!overflow)
+      for (int32_t m : at[(size_t)g]) alleles[m] += 1;
+    int32_t best = 0;
+    int64_t best_count = 0;
+    for (const auto& kv : alleles)   // ascending n: the first of the greatest count
+      if (kv.second > best_count) { best = kv.first; best_count = kv.second; }
+    if (n < cap) {
+      int32_t* row = rows + n * WFA_HIP_DELETION_COLS;
+      row[0] = seq; row[1] = (int32_t)(start + g); row[2] = (int32_t)depth; row[3] = starts[g];
+      row[4] = (int32_t)best_count; row[5] = best; row[6] = (int32_t)alleles.size(); row[7] = overflow ? 1 : 0;
+    }
+    ++n;
+  }
+  *count = n;
+  return WFA_HIP_OK;
+}

@@ -86,6 +86,17 @@ cdef extern from "wfa_hip.h" nogil:
                                 int64_t nrec, const int64_t* rec_row, const int32_t* rec_n, const int64_t* rec_off, const uint8_t* cols,
                                 int64_t ncols, int64_t cap, int64_t* count, int32_t* rows, int64_t bases_cap, int64_t* bases_count,
                                 uint8_t* bases)
+    # what the reads delete: the log of a tracking pileup, its starts plane and its rows (include/wfa_hip.h: "deletions")
+    int wfa_hip_pileup_track_deletions(wfa_hip_pileup_t* pileup, int on)
+    int wfa_hip_pileup_deletion_stats(wfa_hip_pileup_t* pileup, int64_t* records, int64_t* bases)
+    int wfa_hip_pileup_read_deletion_starts(wfa_hip_pileup_t* pileup, int32_t seq, int64_t start, int64_t len, int32_t* out)
+    int wfa_hip_pileup_deletions(wfa_hip_pileup_t* pileup, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
+                                 int32_t min_depth, int32_t min_permille, int64_t cap, int64_t* count, int32_t* rows)
+    int wfa_hip_ops_deletions(const uint8_t* ops, int64_t ops_len, int32_t plen, int32_t tlen, int64_t cap, int64_t* count,
+                              int32_t* recs)
+    int wfa_hip_deletions_host(const int32_t* counts, const int32_t* starts, int64_t len, int32_t seq, int64_t start,
+                               int32_t min_depth, int32_t min_permille, int64_t nrec, const int64_t* rec_row, const int32_t* rec_n,
+                               int64_t cap, int64_t* count, int32_t* rows)
     # placement: one row per read from the hits of any number of batches (include/wfa_hip.h: "placement")
     ctypedef struct wfa_hip_batch_t
     ctypedef struct wfa_hip_placer_t
