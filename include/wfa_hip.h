@@ -1161,6 +1161,74 @@ int wfa_hip_rescue_host(int64_t nreads, int64_t nhits, const int32_t* i, const i
                         int32_t pad, int32_t min_len, int32_t anchor_mapq, int64_t cap, int64_t* count,
                         int32_t* rows /* cap x 8, nullable */, char* msg, size_t msg_cap);
 
+/* ---- duplicates: the fragments and reads that lie at one place with the same ends, one representative each --- */
+
+/*
+ * PCR copies of one fragment land at the same place with the same ends, and every copy adds to a pileup's counts as if it were an
+ * independent read: a polymerase error copied ten times looks like ten observations.  This rule groups the placed fragments and reads
+ * by (text, strand, ends) where the records lie and names one representative per group; 16 bytes per read and per fragment cross
+ * PCIe.  Integers only, 64-bit where sums occur, nothing depends on scheduling.  The terms of "placement" and "pairing" keep their
+ * meaning.
+ *
+ * Inputs: a placer's hits; the parameters of wfa_hip_placer_run_pairs (min_score, full_gap, min_insert, max_insert, unpaired, nfrag,
+ * mate1, mate2); tlen(j), the length of text j in a text set.
+ * UNITS.  After group, place and pair under those parameters:
+ *     PAIR UNIT f: fragment f whose pair row has proper == 1.  h and g are its chosen hits, F the one with reverse == 0 and R the
+ *         other.  Key = (j, ts_F, te_R, first), `first` being 1 when F is mate 1's hit and 2 otherwise: F1R2 and F2R1 fragments with
+ *         the same ends are different molecules.  Score = the pair row's score (the saturated int32).  Bucket position b = ts_F.
+ *     READ UNIT r: a read that is in no fragment, or a mate of a fragment with proper == 0, whose single-end row has hit >= 0 and a
+ *         non-empty primary interval (te > ts).  Key = (j, reverse, p5), p5 = ts for a forward primary and te - 1 for a reverse one:
+ *         the 5' end, so reverse reads of different lengths that end at the same base are one group.  Score = the single-end score.
+ *         b = p5.
+ *     Everything else is no unit: a read without an eligible hit, a read whose primary interval is empty, a fragment that is not
+ *     proper.  The mates of a pair unit are not read units.  A pair unit and a read unit are never in one group.
+ * GROUP.  The units of one kind with equal keys.  Its REPRESENTATIVE is the unit of greatest score, on a tie the one with the smallest
+ * unit number (fragment number or read number).
+ * BUCKET.  All units, of either kind, with the same (j, b).
+ * OVERFLOW.  A bucket with more than WFA_HIP_DUP_MAX_BUCKET units is not resolved: each of its units is alone and carries
+ * overflow = 1 (the convention of WFA_HIP_INS_MAX_READS).  A unit whose b lies outside [0, tlen(j)) is alone with overflow = 0; only
+ * hits added through wfa_hip_placer_add_hits with invented intervals can have one.
+ * ROWS.  WFA_HIP_DUP_COLS int32 (16 bytes) each: rep, size, dup, overflow.  For a unit, rep is its group's representative's unit
+ * number (its own for the representative and for a unit that is alone), size the number of units in the group, dup = 1 iff rep is not
+ * its own number.  A fragment that is not a pair unit gets -1, 0, 0, 0.  A read that is not a read unit gets -1, 0, d, o, with d and o
+ * the dup and overflow of its fragment's pair row when it is a mate of a pair unit, and both 0 otherwise: the read rows' dup column
+ * alone filters a read list for a pileup.
+ * WHAT IT DOES NOT DO.  No unclipped coordinates: under scope full the interval is the aligned core, so a read whose first base
+ * mismatches starts one base later and misses its group.  No matching of a lone read against an end of a pair unit.  No optical
+ * duplicates, no UMIs, no library or read-group split.  The representative is chosen by alignment score, not by summed base quality.
+ *
+ * wfa_hip_placer_duplicates runs group, place and pair on the device exactly as wfa_hip_placer_rescue does, downloads none of their
+ * outputs, and marks the duplicates there (csrc/wfa_dup.hpp, k_dup.hip: every unit is one 32-byte record with a 64-bit bucket number,
+ * counted into a plane that is direct-addressed by the text set's base offsets; a scan and a scatter bring the records into bucket
+ * order; a thread per record walks its bucket for the group's size and the maximum of (score, ~unit number), both order-free: two
+ * calls give identical bytes).  read_rows receives nreads x WFA_HIP_DUP_COLS int32, pair_rows nfrag x WFA_HIP_DUP_COLS.  nfrag == 0
+ * with both mate arrays NULL is the single-end form: every read is a candidate read unit, pair_rows may be NULL.  It may be called
+ * before, after or between the placer's other runs and adds; wfa_hip_placer_kernel_ms then covers the new kernels too.
+ * DEVICE MEMORY, allocated by the first call and kept on the placer (nothing of it without one): 4 BYTES PER BASE OF THE TEXT SET for
+ * the plane plus the scan's chunk sums, 64 bytes per read for the unit records and their bucket-ordered copy, 1 byte per read.  The
+ * plane's cost grows with the text set, not with the reads; a hashed plane is not built.
+ * WFA_HIP_EINVAL, nothing launched, nothing written (wfa_hip_last_error names the first offending position and its values): what
+ * wfa_hip_placer_run_pairs refuses (pair_rows aside); a NULL set or a set of another aligner; a hit whose j is not below the number of
+ * texts; NULL read_rows with nreads > 0; NULL pair_rows with nfrag > 0.  A failed allocation: WFA_HIP_EDEVICE with the byte count.
+ */
+#define WFA_HIP_DUP_COLS 4          /* rep, size, dup, overflow */
+#define WFA_HIP_DUP_MAX_BUCKET 4096
+int  wfa_hip_placer_duplicates(wfa_hip_placer_t* placer, const wfa_hip_seqset_t* texts, int32_t min_score, int32_t full_gap,
+                               int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag,
+                               const int32_t* mate1 /* nullable */, const int32_t* mate2 /* nullable */,
+                               int32_t* read_rows /* nreads x 4 */, int32_t* pair_rows /* nfrag x 4, nullable when nfrag == 0 */);
+
+/* Host only, needs no GPU: the rule above in plain C++ over the arrays wfa_hip_pair_host takes and text_len[ntexts]: what
+ * wfa_hip_placer_add_hits + wfa_hip_placer_duplicates give.  Returns WFA_HIP_OK, or WFA_HIP_EINVAL (nothing written; msg as for
+ * wfa_hip_place_host) for whatever wfa_hip_pair_host refuses (pair_rows aside); a negative ntexts or text_len; a hit whose
+ * j >= ntexts; a missing pointer (text_len with ntexts > 0, read_rows with nreads > 0, pair_rows with nfrag > 0). */
+int wfa_hip_duplicates_host(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse, const int32_t* score,
+                            const int32_t* status, const int32_t* text_start, const int32_t* text_end, int32_t min_score,
+                            int32_t full_gap, int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag,
+                            const int32_t* mate1 /* nullable */, const int32_t* mate2 /* nullable */, int64_t ntexts,
+                            const int32_t* text_len, int32_t* read_rows /* nreads x 4 */, int32_t* pair_rows /* nfrag x 4 */,
+                            char* msg, size_t msg_cap);
+
 /* ---- seed finder: an exact-match k-mer index over a text set, candidate windows for every read ------------ */
 
 /*

@@ -175,6 +175,8 @@ SIGNATURES = {
     "wfa_hip_placer_rescue": (_CTYPES, [_vp] * 3 + [_i32] * 5 + [_i64, _vp, _vp] + [_i32] * 3 + [_i64, _i64p, _vp]),
     "wfa_hip_rescue_host": (_CTYPES, _HITS + [_i32] * 5 + [_i64, _vp, _vp, _vp, _i64, _vp] + [_i32] * 3 +
                             [_i64, _i64p, _vp, _str, _size]),
+    "wfa_hip_placer_duplicates": (_CTYPES, [_vp] * 2 + [_i32] * 5 + [_i64] + [_vp] * 4),
+    "wfa_hip_duplicates_host": (_CTYPES, _HITS + [_i32] * 5 + [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _str, _size]),
 }
 SYMBOLS = list(SIGNATURES)
 
@@ -204,6 +206,9 @@ PAIR_COLUMNS = ("hit1", "hit2", "proper", "score", "second", "mapq", "mapq1", "m
 PAIR_MAX_PAIRINGS = 65536
 RESCUE_COLS = 8
 RESCUE_COLUMNS = ("i", "j", "text_start", "text_len", "reverse", "fragment", "anchor", "spare")
+DUP_COLS = 4
+DUP_COLUMNS = ("rep", "size", "dup", "overflow")
+DUP_MAX_BUCKET = 4096   # WFA_HIP_DUP_MAX_BUCKET
 INT32_MIN = -2**31
 SEED_MAX_N, SEED_MAX_HITS = 16, 4096
 SEED_KEYS = ("j", "reverse", "text_start", "text_len", "hits")   # the int32 arrays of a seed query, and overflow (uint8)
@@ -891,6 +896,29 @@ def rescue_host(nreads, i, j, reverse, score, status, text_start, text_end, mate
     return count.value, rows[:min(count.value, rows.shape[0])]
 
 
+def duplicates_host(nreads, i, j, reverse, score, status, text_start, text_end, mates, text_len, min_score=INT32_MIN, full_gap=1,
+                    min_insert=0, max_insert=1000, unpaired=0):
+    """wfa_hip_duplicates_host (host only): ``(read_rows, pair_rows)`` of the duplicate rule over a list of hits in hit-number order and
+    the texts' lengths ``text_len`` — int32 of shape (nreads, 4) and (F, 4) in the columns DUP_COLUMNS; what ``Placer.add_hits`` +
+    ``Placer.duplicates`` give.  ``mates`` as for ``pair_host``; 0: the single-end form."""
+    a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
+    nfrag, m1, m2 = _mate_ptrs(mates)
+    nreads = int(nreads)
+    text_len = np.ascontiguousarray(text_len, dtype=np.int32)
+    if text_len.ndim != 1:
+        raise ValueError("text_len: one value per text")
+    read_rows = np.zeros((max(nreads, 0), DUP_COLS), np.int32)
+    pair_rows = np.zeros((max(nfrag, 0), DUP_COLS), np.int32)
+    msg = ctypes.create_string_buffer(256)
+    p = _ptr_or_null
+    rc = lib().wfa_hip_duplicates_host(nreads, n, p(a["i"]), p(a["j"]), p(a["reverse"]), p(a["score"]), p(a["status"]), p(a["text_start"]),
+                                       p(a["text_end"]), int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired),
+                                       nfrag, m1, m2, text_len.shape[0], p(text_len), p(read_rows), p(pair_rows), msg, 256)
+    if rc != OK:
+        raise ValueError(f"wfa_hip_duplicates_host: {msg.value.decode()}")
+    return read_rows, pair_rows
+
+
 def seeds_host(read, texts, k=13, stride=1, max_occ=64, n=4, min_hits=2, gap=16, pad=16, max_hits=2048, w=None):
     """wfa_hip_seeds_host (host only): the row ``SeedIndex.query`` holds for ONE read (bytes) against the texts (a list of bytes, or a
     blob dict(seqs=, off=, len=) made once for many reads): dict of int32[n] ``j`` / ``reverse`` / ``text_start`` / ``text_len`` /
@@ -1379,6 +1407,17 @@ class Placer(_Handle):
                    int(max_insert), int(unpaired), nfrag, m1, m2, int(pad), int(min_len), int(anchor_mapq), int(cap),
                    ctypes.byref(count), _ptr_or_null(rows))
         return count.value, rows[:min(count.value, rows.shape[0])]
+
+    def duplicates(self, texts, mates, min_score=INT32_MIN, full_gap=1, min_insert=0, max_insert=1000, unpaired=0):
+        """wfa_hip_placer_duplicates over every hit added so far: ``(read_rows, pair_rows)``, int32 of shape (nreads, 4) and (F, 4)
+        in the columns DUP_COLUMNS — the representative's number, the group's size, 1 for a duplicate, 1 for a bucket too full to
+        resolve.  ``texts``: the SeqSet the hits lie on; ``mates`` as for ``run_pairs``, 0: the single-end form."""
+        nfrag, m1, m2 = _mate_ptrs(mates)
+        read_rows = np.zeros((self.nreads, DUP_COLS), np.int32)
+        pair_rows = np.zeros((max(nfrag, 0), DUP_COLS), np.int32)
+        self._call("wfa_hip_placer_duplicates", self._h, texts._h, int(min_score), int(full_gap), int(min_insert), int(max_insert),
+                   int(unpaired), nfrag, m1, m2, _ptr_or_null(read_rows), _ptr_or_null(pair_rows))
+        return read_rows, pair_rows
 
     def kernel_ms(self):
         ms = ctypes.c_float(0)

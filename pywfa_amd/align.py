@@ -345,6 +345,12 @@ def _columns(rows, names):
     return {name: np.ascontiguousarray(rows[:, c]) for c, name in enumerate(names)}
 
 
+def _dup_columns(rows):
+    """The four int32 arrays that ``duplicates=True`` adds to ``reads`` / ``pairs``, from rows in the columns DUP_COLUMNS."""
+    rep, size, dup, overflow = (np.ascontiguousarray(rows[:, c]) for c in range(_native.DUP_COLS))
+    return dict(dup=dup, dup_rep=rep, dup_size=size, dup_overflow=overflow)
+
+
 def _summary_dict(rows):
     """The (n, 10) rows of ``ResidentBatch.summary()`` as the dict the ``summary=True`` forms return."""
     out = {name: np.ascontiguousarray(rows[:, k]) for k, name in enumerate(("M", "X", "I", "D", "I_runs", "D_runs"))}
@@ -1599,7 +1605,7 @@ class WavefrontAligner:
             return Pileup(table, out["score"], out["status"], self)
 
     def place_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
-                      text_len=None, reverse=None, min_score=None, full_gap=None):
+                      text_len=None, reverse=None, min_score=None, full_gap=None, duplicates=False):
         """Align the listed windows as ``align_windows`` does (same arguments, same checks; either scope) and decide on the GPU where
         every PATTERN sequence goes: the patterns are reads, each window one candidate hit of read ``i[q]``.  The rule is that of
         include/wfa_hip.h ("placement"), integers only.  A hit is eligible when its status is 0 and its score at least ``min_score``
@@ -1615,18 +1621,28 @@ class WavefrontAligner:
         ``len(patterns)``: hit (the primary's list position, -1 for a read without an eligible hit), score, second (-2**31 without
         a runner-up), mapq, hits (eligible), ties (runner-ups that equal the primary's score), text_start, text_end (the primary's
         interval on its text).  Neither scores nor locations are grouped on the host: 32 bytes per read and a byte per hit come
-        back (csrc/wfa_place.hpp).  With ``devices=[...]`` the first device runs it."""
+        back (csrc/wfa_place.hpp).  With ``devices=[...]`` the first device runs it.
+
+        ``duplicates=True``: DUPLICATE MARKING, single-end (include/wfa_hip.h, "duplicates"; ``place_pairs`` describes it).  Every
+        read whose primary has a non-empty interval is a unit with the key (text, strand, 5' end); ``reads`` gains the int32 arrays
+        ``dup``, ``dup_rep``, ``dup_size`` and ``dup_overflow``.  ``duplicates=False`` returns exactly the keys above and neither
+        allocates nor launches anything more."""
         min_score, full_gap = self._placement(min_score, full_gap)
+        if not isinstance(duplicates, (bool, np.bool_)):
+            raise ValueError(f"duplicates must be True or False, got {duplicates!r}")
         with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
             placer = w.attach(self._native.placer(w.nreads))
             out = w.run(each=self._hits_into(placer, w.arrays))
             rows, out["flag"] = placer.run(min_score, full_gap)
             out["reads"] = _columns(rows, _native.PLACE_COLUMNS)
+            if duplicates:
+                read_rows, _ = placer.duplicates(w.text_set, 0, min_score, full_gap)
+                out["reads"].update(_dup_columns(read_rows))
             return out
 
     def place_pairs(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
                     text_len=None, reverse=None, mates=None, min_insert=0, max_insert=1000, unpaired=None, min_score=None,
-                    full_gap=None, rescue=False, rescue_pad=16, rescue_mapq=0):
+                    full_gap=None, rescue=False, rescue_pad=16, rescue_mapq=0, duplicates=False):
         """``place_windows`` for paired-end reads (same arguments, same checks; either scope): the listed windows are aligned, every
         read is placed on its own, and then the hits of the two mates of every fragment are joined on the GPU.  The rule is that of
         include/wfa_hip.h ("pairing"), integers only.  ``mates``: an (F, 2) integer array of indices into ``patterns``, fragment f
@@ -1663,7 +1679,23 @@ class WavefrontAligner:
         rescue hits; ``pairs`` gains ``rescued`` (int32: 1 iff the fragment is proper and one of its chosen hits is a rescue hit),
         and ``rescue`` is added: dict(i=, j=, text_start=, text_len=, reverse=, fragment=, anchor=) of int32 arrays, possibly
         empty, hit ``n0 + q`` being window ``q`` of it (``anchor``: the hit number of the anchor).  ``rescue=False`` returns exactly
-        the keys above."""
+        the keys above.
+
+        ``duplicates=True``: DUPLICATE MARKING (include/wfa_hip.h, "duplicates"), on the GPU after the final pairing, so after a
+        rescue too.  A proper fragment is a unit with the key (text, start of its forward hit, end of its reverse hit, which mate is
+        the forward one); a read in no proper fragment whose primary has a non-empty interval is a unit with the key (text, strand,
+        5' end: the start of a forward primary, the last base of a reverse one).  Units of one kind with equal keys are a group; its
+        representative is the unit of greatest score (pair score or single-end score), the smallest fragment / read number on a
+        tie, and every other member is a duplicate.  ``pairs`` and ``reads`` each gain four int32 arrays: ``dup_rep`` (the
+        representative's fragment / read number; -1 for what is no unit), ``dup_size`` (units in the group, 0 for no unit),
+        ``dup`` (1: a duplicate) and ``dup_overflow`` (1: more than 4 096 units start at that base, none of them was resolved).
+        The mates of a proper fragment are no units of their own, but their ``dup`` and ``dup_overflow`` repeat the fragment's:
+        ``reads["dup"] == 0`` alone selects the reads to pile up.  16 bytes per read and per fragment come back; the device keeps
+        4 bytes per base of the TEXT SET (a direct-addressed plane: its cost grows with the references, not with the reads) and
+        65 per read.  Not done: unclipped coordinates (the interval is the aligned core, so a read whose first base mismatches
+        starts a base later and misses its group), matching a lone read against an end of a proper fragment, optical duplicates,
+        UMIs, a library or read-group split; the representative is chosen by alignment score, not by summed base quality.
+        ``duplicates=False`` returns exactly the keys above and neither allocates nor launches anything more."""
         min_score, full_gap = self._placement(min_score, full_gap, min_insert=min_insert, max_insert=max_insert, unpaired=unpaired)
         if min_insert is None or max_insert is None or not 0 <= int(min_insert) <= int(max_insert) < 2**31:
             raise ValueError(f"min_insert = {min_insert}, max_insert = {max_insert} are out of range (0 <= min_insert <= max_insert)")
@@ -1673,6 +1705,8 @@ class WavefrontAligner:
             raise ValueError(f"unpaired = {unpaired} is out of range (at least 0)")
         if not isinstance(rescue, (bool, np.bool_)):
             raise ValueError(f"rescue must be True or False, got {rescue!r}")
+        if not isinstance(duplicates, (bool, np.bool_)):
+            raise ValueError(f"duplicates must be True or False, got {duplicates!r}")
         for name, v in (("rescue_pad", rescue_pad), ("rescue_mapq", rescue_mapq)):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{name} must be an integer, got {v!r}")
@@ -1743,6 +1777,10 @@ class WavefrontAligner:
                 pairs = out["pairs"]
                 pairs["rescued"] = ((pairs["proper"] == 1) & ((pairs["hit1"] >= n0) | (pairs["hit2"] >= n0))).astype(np.int32)
                 out["rescue"] = dict(i=ri, j=rj, text_start=rts, text_len=rtl, reverse=rrev, fragment=rfrag, anchor=ranchor)
+            if duplicates:
+                read_rows, frag_rows = placer.duplicates(w.text_set, mates, *how)
+                out["reads"].update(_dup_columns(read_rows))
+                out["pairs"].update(_dup_columns(frag_rows))
             return out
 
     def score_matrix(self, patterns, texts=None):

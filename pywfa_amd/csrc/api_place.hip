@@ -1,6 +1,7 @@
 // api_place.hip — the placer of libwfa_hip.so (the C ABI declared in include/wfa_hip.h).
 #include "host_sets.hpp"
 #include "wfa_place.hpp"
+#include "wfa_dup.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // placement: one row per read from the hits of any number of batches (include/wfa_hip.h; csrc/wfa_place.hpp, k_place.hip)
@@ -17,8 +18,12 @@ int pair_check(int64_t nreads, int32_t min_insert, int32_t max_insert, int32_t u
 // host_rescue.cpp: the check shared with wfa_hip_rescue_host
 int rescue_check(int32_t pad, int32_t min_len, int32_t anchor_mapq, int64_t cap, const int64_t* count, const int32_t* rows, char* msg,
                  size_t msg_cap);
+// host_dup.cpp: the check shared with wfa_hip_duplicates_host
+int dup_check(int64_t nreads, int64_t nfrag, const int32_t* read_rows, const int32_t* pair_rows, char* msg, size_t cap);
 }
 static_assert(WFA_RESCUE_COLS == WFA_HIP_RESCUE_COLS, "rescue: the kernels and the ABI");
+static_assert(WFA_DUP_COLS == WFA_HIP_DUP_COLS && WFA_DUP_MAX_BUCKET == WFA_HIP_DUP_MAX_BUCKET, "duplicates: the kernels and the ABI");
+static_assert(sizeof(wfa::DupUnit) == 32, "duplicates: a unit record is two 16-byte words");
 static_assert(WFA_PAIR_COLS == WFA_HIP_PAIR_COLS && WFA_PAIR_MAX_PAIRINGS == WFA_HIP_PAIR_MAX_PAIRINGS, "pairing: the kernels and the ABI");
 
 struct wfa_hip_placer {
@@ -34,6 +39,14 @@ struct wfa_hip_placer {
   // (hit number, j) of every hit whose j exceeds that of all hits before it: the last one is the greatest text index among the hits,
   // the first one with j >= n the first hit that a set of n texts does not hold (rescue checks it against its text set)
   std::vector<std::pair<int64_t, int32_t>> j_rise;
+  // duplicates (wfa_dup.hpp), nothing of it before the first wfa_hip_placer_duplicates: the plane over the bases of a text set with
+  // its chunk sums (grown when a larger set comes), the unit records and their bucket-ordered copy, the owner bytes
+  uint32_t* d_dup_plane = nullptr;
+  uint32_t* d_dup_bsum = nullptr;
+  int64_t dup_bases = -1;              // the plane holds dup_bases + 1 counters (-1: none)
+  wfa::DupUnit* d_dup_rec = nullptr;
+  wfa::DupUnit* d_dup_sorted = nullptr;
+  uint8_t* d_dup_owned = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
   float last_ms = 0.f;
 };
@@ -44,6 +57,11 @@ extern "C" void wfa_hip_placer_destroy(wfa_hip_placer_t* p) {
   (void)hipSetDevice(al->device);
   (void)hipStreamSynchronize(al->stream);
   pool_release(al, p->d_hits); pool_release(al, p->d_count); pool_release(al, p->d_bsum); pool_release(al, p->d_order);
+  if (p->d_dup_plane) pool_release(al, p->d_dup_plane);
+  if (p->d_dup_bsum) pool_release(al, p->d_dup_bsum);
+  if (p->d_dup_rec) pool_release(al, p->d_dup_rec);
+  if (p->d_dup_sorted) pool_release(al, p->d_dup_sorted);
+  if (p->d_dup_owned) pool_release(al, p->d_dup_owned);
   for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
   destroy_end(p);
 }
@@ -343,4 +361,69 @@ extern "C" int wfa_hip_placer_rescue(wfa_hip_placer_t* p, const wfa_hip_seqset_t
   }
   *count = (int64_t)n;
   return WFA_HIP_OK;
+}
+
+// ---- duplicates (include/wfa_hip.h, "duplicates"; wfa_dup.hpp, k_dup.hip) ---------------------------------------------------------------
+// the blocks the placer keeps for it: the per-read ones once, the plane again when a text set has more bases than any before
+static int placer_ensure_dup(wfa_hip_placer* p, int64_t nbases) {
+  wfa_hip_aligner* al = p->al;
+  const size_t nreads = (size_t)p->nreads;
+  if (!p->d_dup_rec && placer_block(al, &p->d_dup_rec, nreads, "32 bytes per read, the unit records")) return WFA_HIP_EDEVICE;
+  if (!p->d_dup_sorted && placer_block(al, &p->d_dup_sorted, nreads, "32 bytes per read, the units in bucket order")) return WFA_HIP_EDEVICE;
+  if (!p->d_dup_owned && placer_block(al, &p->d_dup_owned, nreads, "1 byte per read")) return WFA_HIP_EDEVICE;
+  if (nbases <= p->dup_bases) return WFA_HIP_OK;
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  if (p->d_dup_plane) pool_release(al, p->d_dup_plane);
+  if (p->d_dup_bsum) pool_release(al, p->d_dup_bsum);
+  p->d_dup_plane = nullptr; p->d_dup_bsum = nullptr; p->dup_bases = -1;
+  const size_t counters = (size_t)nbases + 1, chunks = (counters + WFA_PLACE_SCAN_CHUNK - 1) / WFA_PLACE_SCAN_CHUNK;
+  if (placer_block(al, &p->d_dup_plane, counters, "4 bytes per text base, the bucket plane") ||
+      placer_block(al, &p->d_dup_bsum, chunks, "the plane scan's chunk sums"))
+    return WFA_HIP_EDEVICE;
+  p->dup_bases = nbases;
+  return WFA_HIP_OK;
+}
+
+// group, place and pair as wfa_hip_placer_run_pairs enqueues them, none of their outputs downloaded; then key, scan, scatter and resolve
+// (k_dup.hip).  16 bytes per read and per fragment come back.
+extern "C" int wfa_hip_placer_duplicates(wfa_hip_placer_t* p, const wfa_hip_seqset_t* texts, int32_t min_score, int32_t full_gap,
+                                         int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
+                                         const int32_t* mate2, int32_t* read_rows, int32_t* pair_rows) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (check_inval(al, wfa::place_check_run, full_gap)) return WFA_HIP_EINVAL;
+  if (check_inval(al, wfa::pair_check, p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2)) return WFA_HIP_EINVAL;
+  if (!texts) return fail_inval(al, "duplicates: a missing sequence set");
+  if (texts->al != al) return fail_inval(al, "duplicates: sequence set of another aligner");
+  if (!p->j_rise.empty() && (int64_t)p->j_rise.back().second >= texts->n) {
+    size_t k = 0;   // (the rises ascend in j: the first one outside the set is the first such hit of the list)
+    while ((int64_t)p->j_rise[k].second < texts->n) ++k;
+    return fail_inval(al, "duplicates: text index out of range at position %lld of the hit list: j = %d over %lld texts",
+                      (long long)p->j_rise[k].first, (int)p->j_rise[k].second, (long long)texts->n);
+  }
+  if (check_inval(al, wfa::dup_check, p->nreads, nfrag, read_rows, pair_rows)) return WFA_HIP_EINVAL;
+  if (p->nreads == 0) return WFA_HIP_OK;   // (no read: no fragment, no unit)
+  HIP_TRY(al, hipSetDevice(al->device));
+  int rc = placer_ensure_dup(p, texts->nbytes);
+  if (rc != WFA_HIP_OK) return rc;
+  StreamScratch sc{al};
+  wfa::DupArgs d;
+  memset(&d, 0, sizeof(d));
+  d.boff = texts->d_boff; d.text_len = texts->d_len; d.ntexts = texts->n; d.nbases = texts->nbytes;
+  d.plane = p->d_dup_plane; d.bsum = p->d_dup_bsum; d.rec = p->d_dup_rec; d.sorted = p->d_dup_sorted; d.owned = p->d_dup_owned;
+  if (sc.alloc(&d.read_rows, (size_t)p->nreads * WFA_DUP_COLS)) return WFA_HIP_EDEVICE;
+  if (nfrag > 0 && sc.alloc(&d.frag_rows, (size_t)nfrag * WFA_DUP_COLS)) return WFA_HIP_EDEVICE;
+  ReduceTimer timer(al, "duplicates", p->nhits, "hits");
+  int pair_rc = 0, lrc = 0;
+  if ((rc = placer_enqueue_pairs(p, sc, d.pair, min_score, full_gap, min_insert, max_insert, unpaired, nfrag, mate1, mate2, false, &pair_rc)) != WFA_HIP_OK) return rc;
+  if (pair_rc == 0) {
+    HIP_TRY(al, hipMemsetAsync(d.plane, 0, ((size_t)d.nbases + 1) * sizeof(uint32_t), al->stream));
+    HIP_TRY(al, hipMemsetAsync(d.owned, 0, (size_t)p->nreads, al->stream));
+    lrc = wfa::launch_dup(d, al->cu_count, al->stream);
+  }
+  if ((rc = placer_launched(p, timer, pair_rc, "pairing: kernel launch failed")) != WFA_HIP_OK) return rc;
+  if (lrc != 0) { (void)hipStreamSynchronize(al->stream); al->err = "duplicates: kernel launch failed"; return WFA_HIP_EDEVICE; }
+  if (sc.download(read_rows, d.read_rows, (size_t)p->nreads * WFA_DUP_COLS)) return WFA_HIP_EDEVICE;
+  if (nfrag > 0 && sc.download(pair_rows, d.frag_rows, (size_t)nfrag * WFA_DUP_COLS)) return WFA_HIP_EDEVICE;
+  return placer_finish(p);
 }

@@ -162,3 +162,12 @@ cdef extern from "wfa_hip.h" nogil:
                             const int32_t* mate1, const int32_t* mate2, const int32_t* read_len, int64_t ntexts, const int32_t* text_len,
                             int32_t pad, int32_t min_len, int32_t anchor_mapq, int64_t cap, int64_t* count, int32_t* rows, char* msg,
                             size_t msg_cap)
+    # duplicates: one representative per group of fragments / reads with the same ends (include/wfa_hip.h: "duplicates")
+    int wfa_hip_placer_duplicates(wfa_hip_placer_t* placer, const wfa_hip_seqset_t* texts, int32_t min_score, int32_t full_gap,
+                            int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
+                            const int32_t* mate2, int32_t* read_rows, int32_t* pair_rows)
+    int wfa_hip_duplicates_host(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse,
+                            const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end,
+                            int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert, int32_t unpaired,
+                            int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int64_t ntexts, const int32_t* text_len,
+                            int32_t* read_rows, int32_t* pair_rows, char* msg, size_t msg_cap)
