@@ -9,6 +9,6 @@ constexpr PenaltyShape S = affine_shapes[WFA_TU_INDEX];
 
 template <>
 int launch_lane_unit<WFA_TU_INDEX>(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur, int nrp) {
-  return launch_lane_shape<S.X, S.OE, S.E>(grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
+  return launch_lane_shape<S.X, S.OE, S.E, lane_shape_widths[WFA_TU_INDEX]>(grid, smem, stream, a, slot_words, refill_min, full, heur, nrp);
 }
 }  // namespace wfa

@@ -1307,6 +1307,46 @@ __global__ void __launch_bounds__(256) wfa_pilot_sample_kernel(const uint32_t* _
   if (i < np) out[i] = list ? list[i * stride] : i * stride;
 }
 
+// What a first lane stage of 2 H diagonals (wfa_lane.hpp, NRP = H = 4, 5, 6) would hand on of the pilot's sample, from the scores the
+// 16-diagonal pilot left: the keep rule is closed-form in the score and ak = tlen - plen — |ak| <= 2 H - 1 and score / g <= Bmin(H) — so
+// the three widths cost one pass over 8 192 scores and no launch of their kernels.  A pair the 16-diagonal pilot handed on counts as
+// handed on; a score exactly at Bmin counts as kept (the kernel hands on the few of them whose every optimal alignment leaves the
+// band: this is a cost estimate, tests/test_lane_width_model.py prints the difference).  out[H - 4] += pairs handed on.
+__global__ void __launch_bounds__(256) wfa_pilot_width_kernel(const uint32_t* __restrict__ sample, uint32_t np, const WfaPairMeta* __restrict__ meta,
+                                                              const int32_t* __restrict__ score, const int32_t* __restrict__ status,
+                                                              int g, int OE, int E, uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool handed[3] = {false, false, false};
+  if (i < np) {
+    const uint32_t pid = sample[i];
+    const WfaPairMeta m = meta[pid];
+    const int ak = (int)m.tlen - (int)m.plen, c = (ak + 1) >> 1;
+    const bool kept16 = status[pid] == 0;
+    const int steps = kept16 ? -score[pid] / g : 0;
+#pragma unroll
+    for (int H = 4; H <= 6; ++H) {
+      const int dl = min(2 * (OE - E) + E * (2 * c + 2 * H - ak), 2 * (OE - E) + E * (2 * H + 2 - 2 * c + ak));
+      handed[H - 4] = !kept16 || ak < 1 - 2 * H || ak > 2 * H - 1 || steps > dl;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const unsigned long long bm = __ballot(handed[k]);
+    if ((threadIdx.x & 63u) == 0u && bm) atomicAdd(out + k, (uint32_t)__builtin_popcountll(bm));
+  }
+}
+
+// The pilot's cost model of the first lane stage's width: time per input pair c1(H) + r(H) c2, r(H) the share of the sample a
+// stage of 2 H diagonals hands on, c1(H) what that stage costs per pair it is given and c2 what the 16-diagonal stage behind it costs per
+// pair it receives.  In picoseconds per pair on MI355X, from the kernel times of the C2 benchmark (10 M x 150 bp at 2 %, penalties 0/4/6/2)
+// under a kernel trace with each width forced (DESIGN §3.1 has the table): the narrow stage took 1 222 / 1 376 / 1 510 us at H = 4 / 5 / 6,
+// the 16-diagonal stage behind it 775 / 526 / 372 us for the 1 764 941 / 1 082 247 / 645 037 pairs it received — a line, 140 us + 360 ps
+// per pair, whose constant part is paid once a narrow stage exists and is counted with c1: c1(H) = (t1(H) + 140 us) / 10 M.
+// LANE_COST_NONE: the 16-diagonal stage as the first stage, 1 883 us for the 10 M.
+static const int LANE_COST_C1[3] = {136, 152, 165};   // H = 4, 5, 6
+static const int LANE_COST_C2 = 360;
+static const int LANE_COST_NONE = 188;
+
 // A pilot's launch failed.  If the run-time path failed under it (wfa::rtc_failure_count moved since `failures`), the batch and its
 // aligner go on without run-time shapes and the pilot's stage is left out (WFA_HIP_OK); any other failure is the device's.
 static int pilot_launch_failed(wfa_hip_aligner* al, wfa_hip_batch* b, unsigned failures) {
@@ -1352,21 +1392,37 @@ static int pilot_first_width(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t 
   // what it hands on starts over in the 16-diagonal form.  Its own pass over the same sample decides (b->narrow_pick).
   wfa::PenaltyShape sh;
   const int shape = wfa::seg_shape(b->dcfg, &sh);
+  // The width — 8, 10 or 12 diagonals, or no narrow stage — is the one with the lowest modelled time per input pair, c1(H) + r(H) c2
+  // (LANE_COST_*), among the widths the shape is built with that hand on at most WFA_HIP_PILOT_NARROW_PCT of the sample.  r(H) is counted
+  // from the scores the 16-diagonal pilot just left (wfa_pilot_width_kernel): one small kernel where the 8-diagonal form used to run over
+  // the sample itself.  WFA_HIP_LANE_NARROW_NRP names the width instead (the upper bound on r still holds).
   if (!full && b->stage_pick == 16 && shape != WFA_SHAPE_RTC) {
-    HIP_TRY(al, hipMemsetAsync(pcount, 0, sizeof(uint32_t), stream));
-    if (wfa::launch_lane(shape, sh, al->cu_count,
-                         knob(al, K_LANE_WAVES_PER_CU, 48), wfa::lane_refill_arg(knob(al, K_LANE_REFILL_MIN, 8), knob(al, K_LANE_WINFIN, 1) != 0), b->max_len, stream, b->d_words, b->d_meta, psample, nullptr, np,
-                         b->d_score, b->d_status, plist, pcount, nullptr, 0, 0, nullptr, 0, 4) != 0) return pilot_launch_failed(al, b, rtc_failures);
-    uint32_t handed = 0;
-    HIP_TRY(al, hipMemcpyAsync(&handed, pcount, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(al, hipMemsetAsync(pcount, 0, 3 * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(wfa_pilot_width_kernel, dim3((np + 255u) / 256u), dim3(256), 0, stream, psample, np, b->d_meta, b->d_score, b->d_status,
+                       sh.g, sh.OE, sh.E, pcount);
+    HIP_TRY(al, hipGetLastError());
+    uint32_t handed[3] = {0, 0, 0};
+    HIP_TRY(al, hipMemcpyAsync(handed, pcount, sizeof(handed), hipMemcpyDeviceToHost, stream));
     HIP_TRY(al, hipStreamSynchronize(stream));
-    // (150 bp, 2 M - 10 M pairs: 1 % and 2 % divergence, where it hands on 5 % / 18 %, 2-23 % faster; 3 % slower by 9 %)
+    // (150 bp, 2 M - 10 M pairs, 8 diagonals: 1 % and 2 % divergence, where it hands on 5 % / 18 %, 2-23 % faster; 3 % slower by 9 %)
     const uint32_t pct = (uint32_t)knob(al, K_PILOT_NARROW_PCT, 20);
-    if (knob(al, K_STAGE_TIMING, 0)) fprintf(stderr, "[wfa_hip] pilot: 8 diagonals (lane form) hand on %u of %u\n", handed, np);
-    b->narrow_pick = (handed * 100u <= np * pct) ? 1 : 2;
-    b->narrow_permille = (int)((uint64_t)handed * 1000u / np);
+    const int forced = knob(al, K_LANE_NARROW_NRP, 0);
+    int best = 0;
+    int64_t best_cost = (int64_t)LANE_COST_NONE * np;
+    for (int H = 4; H <= 6; ++H) {
+      if (!wfa::lane_shape_has_width(shape, H) || handed[H - 4] * 100u > np * pct) continue;
+      if (forced != 0 && forced != H) continue;
+      const int64_t cost = (int64_t)LANE_COST_C1[H - 4] * np + (int64_t)LANE_COST_C2 * handed[H - 4];
+      if (forced == H || cost < best_cost) { best = H; best_cost = cost; }
+    }
+    if (knob(al, K_STAGE_TIMING, 0))
+      fprintf(stderr, "[wfa_hip] pilot: 8 / 10 / 12 diagonals (lane form) hand on %u / %u / %u of %u; first lane stage: %d diagonals\n",
+              handed[0], handed[1], handed[2], np, best ? 2 * best : 16);
+    b->narrow_pick = best ? 1 : 2;
+    b->narrow_nrp = best;
+    b->narrow_permille = (int)((uint64_t)handed[best ? best - 4 : 0] * 1000u / np);
   }
-  HIP_TRY(al, hipMemsetAsync(pcount, 0, sizeof(uint32_t), stream));
+  HIP_TRY(al, hipMemsetAsync(pcount, 0, 3 * sizeof(uint32_t), stream));
   return WFA_HIP_OK;
 }
 
@@ -2570,7 +2626,14 @@ static int run_fast_stages(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t st
       // for the chip, not for a count the host does not know)
       uint32_t lane_dyn = (c.in_n >= 65536u && lane_k < 2) ? (uint32_t)std::max(0, knob(al, K_LANE_DYN, 192)) : 0u;
       // (waves per CU: the 16-diagonal form holds 4 per SIMD, the 8-diagonal one 6)
-      const int dyn_waves = narrow ? knob(al, K_LANE_NARROW_WAVES, 24) : knob(al, K_LANE_DYN_WAVES, 16);
+      // the narrow form's width in packed registers (4, 5, 6: 8, 10, 12 diagonals): WFA_HIP_LANE_NARROW_NRP where the shape is built with
+      // it, else the pilot's pick, else 8 diagonals; its waves per CU: what that width's registers and LDS hold
+      int nrp = 8;
+      if (narrow) {
+        const int forced = knob(al, K_LANE_NARROW_NRP, 0);
+        nrp = (forced != 0 && wfa::lane_shape_has_width(p.shape, forced)) ? forced : (b->narrow_pick == 1 && b->narrow_nrp != 0) ? b->narrow_nrp : 4;
+      }
+      const int dyn_waves = narrow ? knob(al, K_LANE_NARROW_WAVES, wfa::lane_narrow_waves_per_cu(p.sh, nrp)) : knob(al, K_LANE_DYN_WAVES, 16);
       if (lane_dyn && c.in_count != nullptr) {
         // behind another stage: slices sized for the pairs it is expected to receive (the first stage's pilot, else 64), so that
         // every wave gets at least two — a wave with one slice of 192 runs as long as its slowest lane's three pairs (2 M pairs at
@@ -2587,7 +2650,7 @@ static int run_fast_stages(wfa_hip_aligner* al, wfa_hip_batch* b, hipStream_t st
                              (knob(al, K_LANE_DEBUG, 0) && al->ws) ? al->ws : nullptr, knob(al, K_LANE_LDS_PAD_KB, 0), knob(al, K_LANE_MIN_PAIRS, 0),
                              // (slices of the list taken at run time, 192 pairs at a time, from counters zeroed with the run's others: [12] for
                              // the first lane stage, [14] for the one behind it; WFA_HIP_LANE_DYN=0: fixed slices)
-                             b->d_counters + (lane_k == 0 ? CNT_LANE_DYN0 : CNT_LANE_DYN1), lane_dyn, narrow ? 4 : 8);
+                             b->d_counters + (lane_k == 0 ? CNT_LANE_DYN0 : CNT_LANE_DYN1), lane_dyn, nrp);
       if (knob(al, K_LANE_DEBUG, 0) && al->ws) {  // development aid (build with -DWFA_LANE_DEBUG_COUNTERS=1)
         unsigned long long c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         hipStreamSynchronize(stream); hipMemcpy(c, al->ws, sizeof(c), hipMemcpyDeviceToHost); hipMemset(al->ws, 0, sizeof(c));

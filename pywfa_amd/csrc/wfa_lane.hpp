@@ -179,9 +179,6 @@ __device__ __forceinline__ uint32_t pk_clamp(uint32_t nm, uint32_t lim) {
 #ifndef WFA_LANE_WAVES_PER_EU
 #define WFA_LANE_WAVES_PER_EU 0   // > 0: cap the registers for that many waves per SIMD (the 4/6/2 shape needs 109 VGPRs: 4 waves)
 #endif
-#if WFA_LANE_WAVES_PER_EU > 0
-#define WFA_LANE_OCCUPANCY __attribute__((amdgpu_waves_per_eu(WFA_LANE_WAVES_PER_EU, WFA_LANE_WAVES_PER_EU)))
-#else
 // The 8-diagonal form is built for occupancy: 6 waves per SIMD (at most 80 VGPRs) for the 2/4/1 shape of C2.  Left to itself the allocator
 // ends a few registers above the step the form stood on — in the extension probes — once the window-time chain shares the loop with them, so
 // the form asks for the waves its rings allow (R = M depth + 2 E + cur and lim, four registers each): every built-in shape then compiles
@@ -190,7 +187,18 @@ constexpr int lane_narrow_waves(int X, int OE, int E) {
   const int R = ((X > OE) ? X : OE) + 2 * E + 2;
   return R <= 6 ? 7 : R <= 8 ? 6 : R <= 11 ? 5 : 4;
 }
-#define WFA_LANE_OCCUPANCY __attribute__((amdgpu_waves_per_eu((NRP == 4) ? lane_narrow_waves(X, OE, E) : 1)))
+// The 10- and 12-diagonal forms (NRP = 5, 6) ask for what their rings allow in the same way: R registers per packed register of the band and
+// about 48 for everything else, in allocation steps of 8, out of 512 per SIMD.  (NRP = 4 gives the table above.)
+constexpr int lane_width_waves(int X, int OE, int E, int NRP) {
+  if (NRP == 4) return lane_narrow_waves(X, OE, E);
+  const int R = ((X > OE) ? X : OE) + 2 * E + 2;
+  const int w = 512 / ((R * NRP + 48 + 7) & ~7);
+  return w > 7 ? 7 : w < 3 ? 3 : w;
+}
+#if WFA_LANE_WAVES_PER_EU > 0
+#define WFA_LANE_OCCUPANCY __attribute__((amdgpu_waves_per_eu(WFA_LANE_WAVES_PER_EU, WFA_LANE_WAVES_PER_EU)))
+#else
+#define WFA_LANE_OCCUPANCY __attribute__((amdgpu_waves_per_eu((NRP == 4) ? lane_narrow_waves(X, OE, E) : (NRP == 5 || NRP == 6) ? lane_width_waves(X, OE, E, NRP) : 1)))
 #endif
 
 // records of origin codes a lane can need: steps 0 .. Bmin / g - 1 (wfa_seg.hpp: Bmin / g <= 2 (OE - E) + E (2 H + 1))
@@ -210,12 +218,17 @@ struct LaneFull { static constexpr int NREC = 2 * (OE - E) + E * 17 + 1; };
 // pairs it mostly proves (150 bp at 2 %: 82 % of the pairs within its Bmin; 16 diagonals: 98 %).  The rings take half the registers
 // (4/6/2: 79 VGPRs, 6 waves per SIMD instead of 4) and the step half the probe blocks; what it cannot prove is handed on and starts
 // over in the 16-diagonal form (its state is exact only up to the narrow deadline).  Every use of NR / H below is generic in the width.
+// NRP = 5, 6 (plain score-only form only): the same first stage with 10 or 12 diagonals, k in [c - NRP, c + NRP): Bmin grows by 2 E per
+// unit of H, so on 150 bp at 2 % they keep 89.2 % and 93.6 % of the pairs where 8 diagonals keep 82.4 % (tests/test_lane_width_model.py),
+// for one or two more probe blocks and ring registers per step.  Nothing below needs a power of two or an even NR: slots are found by
+// comparing slot >> 1 with the register index (`place`, the end-slot select, the parked run), the band centre and j0 are plain
+// arithmetic in H, and the neighbour of the outermost registers is the NULL shifted in by alignbit.
 template <int X, int OE, int E, bool FULL, bool HEUR = false, int LIN = 0, int NRP = 8>
 __global__ void __launch_bounds__(64) WFA_LANE_OCCUPANCY
 wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg) {
   static_assert(!(FULL && HEUR), "the general form is score only");
-  static_assert(NRP == 8 || (HEUR && NRP == 16) || (NRP == 4 && !FULL && !HEUR && LIN == 0),
-                "the wider band exists in the general form only, the narrow one in the plain score-only form only");
+  static_assert(NRP == 8 || (HEUR && NRP == 16) || (NRP >= 4 && NRP <= 6 && !FULL && !HEUR && LIN == 0),
+                "the wider band exists in the general form only, the narrow ones (8, 10, 12 diagonals) in the plain score-only form only");
   const int refill_min = refill_arg & 0xff;
   constexpr int NR = NRP, W = 2 * NR, H = NR;     // band of 16 diagonals = 8 packed registers (NRP = 16: 32 diagonals, NRP = 4: 8)
   constexpr int DM = (X > OE) ? X : OE;           // depth of the M ring
@@ -1089,10 +1102,15 @@ wfa_lane_kernel(const FastArgs a, const int slot_words_seq, const int refill_arg
 // per-shape entry point (csrc/k_lane.hip, compiled once per index of affine_shapes, wfa_shapes.hpp)
 template <int I> int launch_lane_unit(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur, int nrp);
 
-template <int X, int OE, int E>
+// WIDTHS: the narrow widths the shape is built with beyond 8 diagonals (bit NRP; lane_shape_widths, wfa_shapes.hpp)
+template <int X, int OE, int E, unsigned WIDTHS = 0u>
 inline int launch_lane_shape(unsigned grid, size_t smem, hipStream_t stream, const FastArgs& a, int slot_words, int refill_min, bool full, int heur, int nrp) {
-  if (nrp == 4 && (full || heur)) return -1;   // (the 8-diagonal band exists in the plain score-only form only)
-  if (nrp == 4) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, false, 0, 4>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
+  if (nrp < 8 && (full || heur)) return -1;   // (the narrow bands exist in the plain score-only form only)
+  if (nrp == 5 || nrp == 6) {
+    if constexpr ((WIDTHS & (1u << 5)) != 0u) { if (nrp == 5) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, false, 0, 5>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min); }
+    if constexpr ((WIDTHS & (1u << 6)) != 0u) { if (nrp == 6) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, false, 0, 6>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min); }
+    if ((WIDTHS & (1u << nrp)) == 0u) return -1;
+  } else if (nrp == 4) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, false, 0, 4>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
   else if (heur == 2) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, true, 0, 16>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
   else if (heur) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, false, true>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
   else if (full) hipLaunchKernelGGL((wfa_lane_kernel<X, OE, E, true>), dim3(grid), dim3(64), smem, stream, a, slot_words, refill_min);
@@ -1111,6 +1129,12 @@ inline bool lane_heur_config(const WfaDevConfig& c, int ncomp) {
 inline int lane_slot_words(int max_len) {
   const int w = 2 * ((max_len + 15) >> 4) + 1;
   return w | 1;
+}
+
+// waves per CU of a narrow first stage's run-time slices: what the registers hold (lane_width_waves per SIMD, four SIMDs), and no more than
+// the 24 whose LDS fits a CU at 150 bp (five 1 280-byte granules per wave of 160 KB).  8 diagonals: 24 for every shape, as before.
+inline int lane_narrow_waves_per_cu(const PenaltyShape& sh, int nrp) {
+  return nrp == 4 ? 24 : std::min(24, 4 * lane_width_waves(sh.X, sh.OE, sh.E, nrp));
 }
 
 // the kernel's refill_arg: the refill threshold in bits 0-7, bit 8: the Hamming finish of the window pass (plain score-only form; off:
@@ -1146,7 +1170,7 @@ inline std::string lane_rtc_name(const PenaltyShape& sh, bool full, int heur, in
 
 // full = the FULL form: a.hist = run-record slots (a.hist_stride ints each, slot = work item - a.work_begin), a.end_state per slot
 // (shape_idx WFA_SHAPE_RTC: no instantiation in the library — the kernel of `sh` is compiled at run time, csrc/wfa_rtc.cpp)
-// heur: 0 no, 1 the general form (16 diagonals), 2 its 32-diagonal form; nrp: 8 (16 diagonals) or 4 (8 diagonals: plain score-only form, instantiated shapes only)
+// heur: 0 no, 1 the general form (16 diagonals), 2 its 32-diagonal form; nrp: 8 (16 diagonals) or 4, 5, 6 (8, 10, 12 diagonals: plain score-only form, instantiated shapes only)
 inline int launch_lane_args(int shape_idx, const PenaltyShape& sh, int cu_count, int per_cu, int refill_min, int max_len, hipStream_t stream, FastArgs a, bool full, int lds_pad_kb = 0, int min_pairs = 0, int heur = 0, int nrp = 8) {
   const uint32_t nwork = a.nwork;
   const uint32_t* nwork_dev = a.nwork_dev;
@@ -1164,8 +1188,8 @@ inline int launch_lane_args(int shape_idx, const PenaltyShape& sh, int cu_count,
   if (grid < 1) grid = 1;
   if (full && a.codes_cap <= 0) return -1;   // (the caller sizes the record lists with lane_full_geometry)
   if (a.lin) shape_idx = WFA_SHAPE_RTC;      // (the one-component form: instantiated at run time whatever the shape)
-  if (nrp != 8 && nrp != 4) return -1;
-  if (nrp == 4 && (shape_idx == WFA_SHAPE_RTC || full || heur)) return -1;   // (the 8-diagonal form: built-in shapes, plain score-only form)
+  if (nrp != 8 && !(nrp >= 4 && nrp <= 6)) return -1;
+  if (nrp != 8 && (shape_idx == WFA_SHAPE_RTC || full || heur || !lane_shape_has_width(shape_idx, nrp))) return -1;   // (the narrow forms: built-in shapes, plain score-only form)
   if (shape_idx == WFA_SHAPE_RTC) {
     struct { FastArgs a; int slot_words; int refill_min; } args = {a, slot_words, refill_min};   // (the kernel's argument list)
     return rtc_launch("wfa_lane.hpp", lane_rtc_name(sh, full, heur, a.lin), (unsigned)grid, 64, smem, stream, &args, sizeof(args));

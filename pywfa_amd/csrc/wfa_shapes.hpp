@@ -26,6 +26,23 @@ constexpr PenaltyShape affine_shapes[] = {
   {1, 1, 2, 1, 0, 0},
 };
 constexpr int affine_shape_count = (int)(sizeof(affine_shapes) / sizeof(affine_shapes[0]));
+// The narrow first stage of the lane kernel (wfa_lane.hpp, NRP = 4: 8 diagonals) is built for every entry; these are the further widths
+// an entry gets, one bit per NRP (5: 10 diagonals, 6: 12) — a width is listed only where the kernel compiles without scratch at the
+// waves per SIMD its rings allow.
+constexpr unsigned LW5 = 1u << 5, LW6 = 1u << 6;
+constexpr unsigned lane_shape_widths[] = {
+  LW5 | LW6,
+  LW5 | LW6,
+  LW5 | LW6,
+  LW5 | LW6,
+  LW5 | LW6,
+  LW5 | LW6,
+  LW5 | LW6,
+};
+static_assert(sizeof(lane_shape_widths) / sizeof(lane_shape_widths[0]) == affine_shape_count, "one entry per shape of affine_shapes");
+constexpr bool lane_shape_has_width(int shape_idx, int nrp) {
+  return shape_idx >= 0 && shape_idx < affine_shape_count && (nrp == 4 || ((nrp == 5 || nrp == 6) && (lane_shape_widths[shape_idx] & (1u << nrp)) != 0u));
+}
 // The lane and the segmented kernels are built for all of them, the banded and the slim kernels for this many leading entries.
 constexpr int band_shape_count = 4;
 // Gap-affine-2p (banded and slim kernels only): pywfa's default 4/6/2/24/1.
