@@ -497,7 +497,7 @@ static inline int64_t bt_cand(oracle_ws_t* ws, int c, int s, int k, int add, int
   const wf_t* w = wf_slot(ws, c, s);
   if (!w->exists || k < w->lo || k > w->hi) return OFFSET_NULL;
   const int32_t o = ws->arena[w->idx + (k - w->base)];
-  return (((int64_t)(o + add)) << 4) | type;
+  return ((int64_t)(o + add)) * 16 + type; /* (the reference's (offset << 4) | type; a NULL offset is negative) */
 }
 
 typedef struct {

@@ -132,8 +132,11 @@ def test_biwfa_matches_golden_vectors(gpu, run_idx):
         assert [common.rle(c) for c in cigars] == run["cigar"]
 
 
-@pytest.mark.parametrize("kw", [dict(match=-1, span="end-to-end"), dict(mismatch=6, gap_opening=2, gap_extension=3), dict(distance="affine2p", match=-2),
-                                dict(match=-1, max_steps=600), dict(distance="linear", match=-1, mismatch=5, gap_extension=4)])
+SHORT_DIVERGENT = [dict(match=-1, span="end-to-end"), dict(mismatch=6, gap_opening=2, gap_extension=3), dict(distance="affine2p", match=-2),
+                   dict(match=-1, max_steps=600), dict(distance="linear", match=-1, mismatch=5, gap_extension=4)]
+
+
+@pytest.mark.parametrize("kw", SHORT_DIVERGENT)
 def test_biwfa_short_divergent_reads_under_large_penalties(gpu, kw):
     """the top-level base case of reads <= 100 bases has no score bound (two unrelated 100-mers under match=-1 score
     ~1000): what outgrows the BiWFA kernel's base-case history is aligned by the general kernel — same op strings, the unset
@@ -149,7 +152,11 @@ def test_biwfa_short_divergent_reads_under_large_penalties(gpu, kw):
         common.assert_same(o, score, status, cigars, batch, f"biwfa short divergent {kw}")
 
 
-@pytest.mark.parametrize("kw0", [dict(span="end-to-end"), dict(distance="affine2p"), dict(distance="levenshtein", span="end-to-end"), dict(match=-1, span="end-to-end")])
+STEP_KW0 = [dict(span="end-to-end"), dict(distance="affine2p"), dict(distance="levenshtein", span="end-to-end"), dict(match=-1, span="end-to-end")]
+STEP_LIMITS = (5, 60, 300, 1200)
+
+
+@pytest.mark.parametrize("kw0", STEP_KW0)
 @pytest.mark.parametrize("scope", ["full", "score"])
 def test_biwfa_step_limit_matches_oracle(gpu, kw0, scope):
     # (the suite's time budget: with CIGARs gap-affine-2p only under -m gpu, 10 s a case; WFA_TEST_FULL=1 runs the four)
@@ -160,7 +167,7 @@ def test_biwfa_step_limit_matches_oracle(gpu, kw0, scope):
     corpora = [datagen.generate(500, 150, 0.05, 21), datagen.generate(200, 150, 0.2, 22), datagen.generate(300, 60, 0.1, 23),
                datagen.generate(40, 1500, 0.08, 24), datagen.generate(3, 10000, 0.08, 25), vo.corpus_special(seed=6)]
     # (with CIGARs two of the four limits under -m gpu: one that cuts most alignments short and one that few reach)
-    for ms in ((5, 60, 300, 1200) if scope == "score" or os.environ.get("WFA_TEST_FULL") == "1" else (60, 1200)):
+    for ms in (STEP_LIMITS if scope == "score" or os.environ.get("WFA_TEST_FULL") == "1" else (60, 1200)):
         oc, nc = common.configs_pair(**dict(kw0, scope=scope, memory_mode="biwfa", max_steps=ms))
         for i, batch in enumerate(corpora):
             o = loader.run(loader.oracle(), oc, batch)

@@ -114,10 +114,13 @@ def test_wildcard_reads(gpu):
         assert np.array_equal(status, et) and np.array_equal(score, es), kw
 
 
+ORACLE_KWS = [dict(scope="score", span="end-to-end"), dict(scope="score", distance="affine2p"), dict(scope="score", max_steps=30)]
+
+
 @pytest.mark.gpu
 def test_against_oracle(gpu):
     reads = families(21, 8, 6, 0, 200)[:48]
-    for kw in (dict(scope="score", span="end-to-end"), dict(scope="score", distance="affine2p"), dict(scope="score", max_steps=30)):
+    for kw in ORACLE_KWS:
         oc, nc = configs_pair(**kw)
         al = WavefrontAligner(**kw)
         score, status = al.score_matrix(reads)

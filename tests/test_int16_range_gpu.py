@@ -17,6 +17,16 @@ from pywfa_amd import _native
 pytestmark = pytest.mark.gpu
 
 
+# every configuration of this module (the tests add the scope where they run both)
+KWS = {
+    "exact": dict(span="end-to-end"),
+    "adaptive": dict(span="end-to-end", scope="full", heuristic="adaptive"),
+    "adaptive-ends-free": dict(span="ends-free", scope="full", heuristic="adaptive", text_end_free=40),
+    "adaptive-2p": dict(distance="affine2p", span="end-to-end", scope="full", heuristic="adaptive"),
+    "biwfa": dict(span="end-to-end", scope="full", memory_mode="biwfa"),
+}
+
+
 def _checker():
     return loader.reference() if loader.have_reference() else loader.oracle()
 
@@ -71,7 +81,7 @@ def test_exact_reads_at_the_tiled_rows_limit(gpu, L, tile32, scope, monkeypatch)
     (WFA_HIP_TILE32=1) or the wide kernel's int32 rows (0).  The host picks by the longest read, the kernel checks every pair against
     the same limit: nothing may be left to the general kernel."""
     monkeypatch.setenv("WFA_HIP_TILE32", tile32)
-    kw = dict(span="end-to-end", scope=scope)
+    kw = dict(KWS["exact"], scope=scope)
     check(("len", L), _length_batch(L, 3100 + L % 100), kw, f"exact L={L} tile32={tile32} {scope}")
 
 
@@ -81,7 +91,7 @@ def test_exact_reads_at_the_wide_rows_limit(gpu, plen, tlen, scope, monkeypatch)
     """WFA_HIP_TILE=0: the step-by-step wide kernel's own forms.  int16 rows (NULL = -16384) while twice the longest read of the
     batch is at most 32 000, int32 rows beyond — so (16 001, 15 999), whose sum the kernel's own per-pair test would accept, gets int32."""
     monkeypatch.setenv("WFA_HIP_TILE", "0")
-    kw = dict(span="end-to-end", scope=scope)
+    kw = dict(KWS["exact"], scope=scope)
     check(("shape", plen, tlen), _shape_batch(plen, tlen, 3300 + plen % 10 + tlen % 10), kw, f"wide ({plen}, {tlen}) {scope}")
 
 
@@ -92,9 +102,7 @@ def test_adaptive_reads_at_the_history_limit(gpu, L, variant, monkeypatch):
     4 x int16 below 32 000 bases, 4 x int32 at 32 000), and one ends-free run that may leave up to 40 bases of the text."""
     if variant == "explicit":
         monkeypatch.setenv("WFA_HIP_BAND_PB", "0")
-    kw = dict(span="end-to-end", scope="full", heuristic="adaptive")
-    if variant == "ends-free":
-        kw = dict(span="ends-free", scope="full", heuristic="adaptive", text_end_free=40)
+    kw = KWS["adaptive-ends-free"] if variant == "ends-free" else KWS["adaptive"]
     check(("len", L), _length_batch(L, 3100 + L % 100), kw, f"adaptive L={L} {variant}")
 
 
@@ -102,7 +110,7 @@ def test_adaptive_reads_at_the_history_limit(gpu, L, variant, monkeypatch):
 def test_adaptive_2p_reads_at_the_doubled_offset_limits(gpu, L):
     """gap-affine-2p under wf-adaptive: the slim kernel keeps doubled offsets in int16 for pairs of up to 16 000 bases and hands longer
     ones on (16 001); the banded kernel takes batches whose longest read is below 32 000 (31 999), the stages behind it the rest."""
-    kw = dict(distance="affine2p", span="end-to-end", scope="full", heuristic="adaptive")
+    kw = KWS["adaptive-2p"]
     check(("len", L), _length_batch(L, 3100 + L % 100), kw, f"adaptive 2p L={L}", staged=False)
 
 
@@ -112,7 +120,7 @@ def test_biwfa_reads_at_the_ring_limit(gpu, L, bilevel, monkeypatch):
     """BiWFA with CIGARs: the level kernels' rings are int16 (stores clamped to [-16384, 32767]) up to 32 000 bases, int32 beyond;
     WFA_HIP_BILEVEL=0 is the depth-first kernel."""
     monkeypatch.setenv("WFA_HIP_BILEVEL", bilevel)
-    kw = dict(span="end-to-end", scope="full", memory_mode="biwfa")
+    kw = KWS["biwfa"]
     check(("len", L), _length_batch(L, 3100 + L % 100), kw, f"biwfa L={L} bilevel={bilevel}", staged=False)
 
 
@@ -124,7 +132,7 @@ def test_wide_int16_rows_beyond_16384_steps(gpu, scope, monkeypatch):
     2.4 GB for the two op strings on one core, the plain oracle 6 s; score only 1.3 s / 5 s.)"""
     monkeypatch.setenv("WFA_HIP_TILE", "0")
     batch = _step_batch(8200)
-    kw = dict(span="end-to-end", scope=scope)
+    kw = dict(KWS["exact"], scope=scope)
     o = expected(("steps", 8200), batch, kw)
     assert list(o["score"]) == [-32800, -32800]
     check(("steps", 8200), batch, kw, f"16 400 steps, wide rows, {scope}", staged=False)
@@ -137,7 +145,7 @@ def test_tiled_int16_rows_beyond_32000_steps(gpu):
     10 GB) nor a test's time.  The plain oracle needs 20 s for the two pairs on one core, so the real library (5 s) is used where it
     was built."""
     batch = _step_batch(16001)
-    kw = dict(span="end-to-end", scope="score")
+    kw = dict(KWS["exact"], scope="score")
     o = expected(("steps", 16001), batch, kw)
     assert list(o["score"]) == [-64004, -64004]
     check(("steps", 16001), batch, kw, "32 002 steps, default route", staged=False)

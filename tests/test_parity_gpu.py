@@ -117,9 +117,12 @@ def test_hip_matches_oracle(gpu, corpora, corpus, cfg_idx, monkeypatch):
     common.assert_same(o, score, status, cigars, batch, f"{corpus} {kw}")
 
 
-@pytest.mark.parametrize("kw", [dict(span="end-to-end", scope="full", heuristic="adaptive"),
-                                dict(span="end-to-end", scope="score"),
-                                dict(distance="affine2p", span="ends-free", pattern_end_free=100, text_end_free=100, heuristic="adaptive")])
+TENKB = [dict(span="end-to-end", scope="full", heuristic="adaptive"),
+         dict(span="end-to-end", scope="score"),
+         dict(distance="affine2p", span="ends-free", pattern_end_free=100, text_end_free=100, heuristic="adaptive")]
+
+
+@pytest.mark.parametrize("kw", TENKB)
 def test_hip_matches_oracle_10kb(gpu, kw):
     batch = datagen.generate(24, 10000, 0.08, 1003)
     oc, nc = common.configs_pair(**kw)
@@ -349,7 +352,10 @@ def test_segmented_stages_accept_only_proven_scores(gpu, stages, monkeypatch):
     assert np.array_equal(score, o["score"][perm]) and np.array_equal(status, o["status"][perm])
 
 
-@pytest.mark.parametrize("pen", [(4, 4, 2), (4, 6, 1), (3, 4, 1), (6, 5, 3), (5, 0, 3), (1, 1, 1), (8, 12, 4), (2, 3, 1), (7, 11, 3)])
+SEG_PENS = [(4, 4, 2), (4, 6, 1), (3, 4, 1), (6, 5, 3), (5, 0, 3), (1, 1, 1), (8, 12, 4), (2, 3, 1), (7, 11, 3)]
+
+
+@pytest.mark.parametrize("pen", SEG_PENS)
 def test_segmented_kernel_penalty_shapes(gpu, pen):
     """Score-only end-to-end batches under the penalty shapes the segmented kernel is instantiated for (and one it is
     not: 7/11/3 runs in the general kernel) against the oracle, short and long slices, low and high divergence."""
@@ -394,9 +400,12 @@ def test_segmented_full_cigar_in_several_launches(gpu, span, monkeypatch):
         common.assert_same(o, score, status, cigars, parts[0], f"segmented full {span} {env}")
 
 
-@pytest.mark.parametrize("kw", [dict(span="end-to-end", memory_mode="medium"), dict(span="end-to-end", memory_mode="low", heuristic="adaptive"),
-                                dict(memory_mode="medium"), dict(memory_mode="low", span="ends-free", pattern_begin_free=40, pattern_end_free=30,
-                                                                 text_begin_free=25, text_end_free=35, heuristic="adaptive")])
+PIGGYBACK = [dict(span="end-to-end", memory_mode="medium"), dict(span="end-to-end", memory_mode="low", heuristic="adaptive"),
+             dict(memory_mode="medium"), dict(memory_mode="low", span="ends-free", pattern_begin_free=40, pattern_end_free=30,
+                                              text_begin_free=25, text_end_free=35, heuristic="adaptive")]
+
+
+@pytest.mark.parametrize("kw", PIGGYBACK)
 @pytest.mark.parametrize("band_pb", ["default", "0"])
 def test_piggyback_history_gives_the_same_cigars(gpu, kw, band_pb, monkeypatch):
     """Long reads keep one byte of origin codes per (step, diagonal) instead of the offsets and the op string is unpacked by
@@ -416,10 +425,13 @@ def test_piggyback_history_gives_the_same_cigars(gpu, kw, band_pb, monkeypatch):
         common.assert_same(o, score, status, cigars, batch, f"piggy-back {kw2} L={L}")
 
 
-@pytest.mark.parametrize("kw", [dict(heuristic="adaptive", memory_mode="medium"), dict(span="end-to-end", heuristic="adaptive", memory_mode="low"),
-                                dict(memory_mode="low", span="ends-free", pattern_begin_free=40, pattern_end_free=30, text_begin_free=25,
-                                     text_end_free=35, heuristic="adaptive"),
-                                dict(memory_mode="medium", span="end-to-end")])
+PIGGYBACK_2P = [dict(heuristic="adaptive", memory_mode="medium"), dict(span="end-to-end", heuristic="adaptive", memory_mode="low"),
+                dict(memory_mode="low", span="ends-free", pattern_begin_free=40, pattern_end_free=30, text_begin_free=25,
+                     text_end_free=35, heuristic="adaptive"),
+                dict(memory_mode="medium", span="end-to-end")]
+
+
+@pytest.mark.parametrize("kw", PIGGYBACK_2P)
 @pytest.mark.parametrize("band_pb", ["default", "0"])
 def test_piggyback_history_gap_affine_2p(gpu, kw, band_pb, monkeypatch):
     """(band_pb = "0": the same inputs with the explicit 16-byte history entries.)
@@ -451,15 +463,19 @@ def test_piggyback_history_gap_affine_2p(gpu, kw, band_pb, monkeypatch):
         common.assert_same(o, score, status, cigars, batch, f"piggy-back 2p {kw2} L={L}")
 
 
-@pytest.mark.parametrize("pen", [(4, 4, 2), (4, 6, 1), (3, 4, 1), (2, 3, 1)])
+BANDED_PENS = [(4, 4, 2), (4, 6, 1), (3, 4, 1), (2, 3, 1)]
+BANDED_KWS = [dict(span="end-to-end", scope="full", heuristic="adaptive"), dict(scope="full", memory_mode="medium"),
+              dict(span="end-to-end", scope="score", heuristic="adaptive"),
+              dict(scope="full", span="ends-free", pattern_begin_free=20, text_end_free=15, heuristic="adaptive", memory_mode="low")]
+
+
+@pytest.mark.parametrize("pen", BANDED_PENS)
 def test_banded_kernel_penalty_shapes(gpu, pen):
     """Long reads and full CIGARs under the penalty shapes the banded kernel is instantiated for: exact and wf-adaptive,
     explicit and piggy-back history, ends-free with free ends."""
     x, o, e = pen
     base = dict(mismatch=x, gap_opening=o, gap_extension=e)
-    for i, kw in enumerate([dict(span="end-to-end", scope="full", heuristic="adaptive"), dict(scope="full", memory_mode="medium"),
-                            dict(span="end-to-end", scope="score", heuristic="adaptive"),
-                            dict(scope="full", span="ends-free", pattern_begin_free=20, text_end_free=15, heuristic="adaptive", memory_mode="low")]):
+    for i, kw in enumerate(BANDED_KWS):
         for j, (n, L, err) in enumerate([(300, 1500, 0.05), (100, 3000, 0.08), (1500, 200, 0.1)]):
             batch = datagen.generate(n, L, err, 9500 + 10 * i + j)
             kw2 = common.clamp_free(dict(base, **kw), batch)
@@ -505,13 +521,16 @@ def test_pilot_choice_never_changes_results(gpu, scope, order):
     rb.close(); al.close()
 
 
-@pytest.mark.parametrize("kw", [dict(span="end-to-end", scope="score"), dict(scope="full"),
-                                dict(scope="full", span="ends-free", pattern_begin_free=6, pattern_end_free=9, text_begin_free=4, text_end_free=3),
-                                dict(scope="full", heuristic="adaptive"), dict(scope="score", heuristic="X-drop", xdrop=30),
-                                dict(scope="full", distance="affine2p"), dict(scope="full", max_steps=14),
-                                dict(scope="full", mismatch=4, gap_opening=4, gap_extension=2),
-                                dict(scope="full", mismatch=7, gap_opening=3, gap_extension=2),      # no banded shape: the general kernel
-                                dict(scope="full", distance="levenshtein")])
+SINGLE_CALLS = [dict(span="end-to-end", scope="score"), dict(scope="full"),
+                dict(scope="full", span="ends-free", pattern_begin_free=6, pattern_end_free=9, text_begin_free=4, text_end_free=3),
+                dict(scope="full", heuristic="adaptive"), dict(scope="score", heuristic="X-drop", xdrop=30),
+                dict(scope="full", distance="affine2p"), dict(scope="full", max_steps=14),
+                dict(scope="full", mismatch=4, gap_opening=4, gap_extension=2),
+                dict(scope="full", mismatch=7, gap_opening=3, gap_extension=2),      # no banded shape: the general kernel
+                dict(scope="full", distance="levenshtein")]
+
+
+@pytest.mark.parametrize("kw", SINGLE_CALLS)
 def test_single_calls_match_oracle(gpu, kw, monkeypatch):
     """Calls of 1 .. 4 096 short pairs (pywfa's usual loop, and small batches) take the single-call path: one launch of the banded kernel reading the
     host-packed pairs from the pinned block, completion polled by the host; pairs it cannot hold (unrelated sequences: the
@@ -555,8 +574,11 @@ def test_single_calls_match_oracle(gpu, kw, monkeypatch):
         for k_ in env: monkeypatch.delenv(k_)
 
 
-@pytest.mark.parametrize("kw", [dict(scope="score", span="end-to-end"), dict(scope="full"), dict(scope="full", mismatch=5),
-                                dict(scope="full", distance="affine2p"), dict(scope="score", distance="levenshtein"), dict(scope="full", match=-1)])
+ALIGN_PAIR = [dict(scope="score", span="end-to-end"), dict(scope="full"), dict(scope="full", mismatch=5),
+              dict(scope="full", distance="affine2p"), dict(scope="score", distance="levenshtein"), dict(scope="full", match=-1)]
+
+
+@pytest.mark.parametrize("kw", ALIGN_PAIR)
 def test_align_pair_entry_matches_the_batch_entry_and_the_oracle(gpu, kw):
     """wfa_hip_align_pair (round 4: pywfa's one-pair-per-call pattern without arrays on the way) against the oracle: ragged pairs,
     an empty pattern, a letter outside ACGT, sequences in either order in memory."""

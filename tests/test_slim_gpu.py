@@ -82,11 +82,15 @@ def test_slim_kernel_matches_oracle_and_band_kernel(gpu, cfg_idx, scope, monkeyp
         assert np.array_equal(score, score0) and np.array_equal(status, status0) and cigars == cigars0
 
 
+OVERFLOW = {d: dict(distance=d, span="end-to-end", heuristic="adaptive", min_wavefront_length=10, max_distance_threshold=400, scope="full")
+            for d in ("affine", "affine2p")}
+
+
 @pytest.mark.parametrize("distance", ["affine", "affine2p"])
 def test_slim_kernel_window_overflow_is_handed_on(gpu, distance):
     """Reads whose wavefront outgrows the window (a cut-off that keeps everything) go on to the 256-diagonal stage."""
     batch = datagen.generate(40, 6000, 0.12, 515)
-    kw = dict(distance=distance, span="end-to-end", heuristic="adaptive", min_wavefront_length=10, max_distance_threshold=400, scope="full")
+    kw = OVERFLOW[distance]
     oc, nc = common.configs_pair(**kw)
     o = loader.run(loader.oracle(), oc, batch)
     score, status, cigars = common.gpu_run(nc, batch, True, resident=True)
@@ -136,9 +140,12 @@ def test_slim_kernel_without_a_heuristic(gpu, cfg_idx, scope, monkeypatch):
             assert bytes(a._ops) == o["cigars"][i]
 
 
-@pytest.mark.parametrize("kw", [dict(span="end-to-end", heuristic="adaptive"),
-                                dict(span="ends-free", heuristic="adaptive", pattern_begin_free=30, text_end_free=50),
-                                dict(span="end-to-end", heuristic="adaptive", mismatch=5, gap_opening=6, gap_extension=2)])
+WINDOWED = [dict(span="end-to-end", heuristic="adaptive"),
+            dict(span="ends-free", heuristic="adaptive", pattern_begin_free=30, text_end_free=50),
+            dict(span="end-to-end", heuristic="adaptive", mismatch=5, gap_opening=6, gap_extension=2)]
+
+
+@pytest.mark.parametrize("kw", WINDOWED)
 @pytest.mark.parametrize("scope", ["full", "score"])
 def test_slim_kernel_on_windows_of_long_reads(gpu, kw, scope, monkeypatch):
     """Reads whose sequences do not fit LDS (over 26 kb): the 256-diagonal slim kernel stages WINDOWS of the two sequences and moves them

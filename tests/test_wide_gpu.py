@@ -78,9 +78,12 @@ def test_tile_kernel_geometries(gpu, idx, geo, monkeypatch):
     common.assert_same(o, score, status, cigars, batch, f"tile {kw} {TILE_GEOMETRIES[geo]}")
 
 
-@pytest.mark.parametrize("kw", [dict(span="end-to-end", scope="full"), dict(span="end-to-end", scope="score", mismatch=1, gap_opening=1, gap_extension=1),
-                                dict(distance="affine2p", span="end-to-end", scope="full"),
-                                dict(span="ends-free", scope="full", pattern_begin_free=20, pattern_end_free=20, text_begin_free=10, text_end_free=10)])
+HANDS_ON = [dict(span="end-to-end", scope="full"), dict(span="end-to-end", scope="score", mismatch=1, gap_opening=1, gap_extension=1),
+            dict(distance="affine2p", span="end-to-end", scope="full"),
+            dict(span="ends-free", scope="full", pattern_begin_free=20, pattern_end_free=20, text_begin_free=10, text_end_free=10)]
+
+
+@pytest.mark.parametrize("kw", HANDS_ON)
 def test_tile_kernel_hands_on_what_trimming_would_change(gpu, kw, monkeypatch):
     """Unrelated sequences, prefixes and overhangs of 65-260 bases: wavefronts run into the ends of the diagonal range and gap cells
     past a sequence end lie outside their row's in-bounds cells — where the reference's per-step trimming changes values.  The
@@ -171,8 +174,11 @@ def test_wide_kernel_10kb_exact_sample(gpu):
         else: assert np.array_equal(s_score, score)
 
 
-@pytest.mark.parametrize("kw", [dict(span="end-to-end", scope="score"), dict(span="end-to-end", scope="full"),
-                                dict(distance="affine2p", span="ends-free", pattern_end_free=50, text_end_free=50, scope="score")])
+BEYOND_16KB = [dict(span="end-to-end", scope="score"), dict(span="end-to-end", scope="full"),
+               dict(distance="affine2p", span="ends-free", pattern_end_free=50, text_end_free=50, scope="score")]
+
+
+@pytest.mark.parametrize("kw", BEYOND_16KB)
 @pytest.mark.parametrize("tile32", ["0", "1"])
 def test_exact_reads_beyond_16kb_take_the_int32_rows(gpu, kw, tile32, monkeypatch):
     if tile32 == "1" and kw.get("scope") != "full" and os.environ.get("WFA_TEST_FULL") != "1":
@@ -264,7 +270,10 @@ def test_wide_kernel_takes_wf_adaptive_leftovers_of_the_banded_stages(gpu):
     common.assert_same(o, score, status, cigars, batch, "wide takes the banded stages' wf-adaptive leftovers")
 
 
-@pytest.mark.parametrize("L,e,dist", [(600, 0.10, "affine"), (900, 0.01, "affine"), (300, 0.08, "affine2p"), (500, 0.01, "affine2p")])
+MIDLENGTH = [(600, 0.10, "affine"), (900, 0.01, "affine"), (300, 0.08, "affine2p"), (500, 0.01, "affine2p")]
+
+
+@pytest.mark.parametrize("L,e,dist", MIDLENGTH)
 def test_exact_midlength_batches_with_the_band_pilot(gpu, L, e, dist):
     """Round 5: exact reads of 300 - 1 200 bases in batches of >= 32 768 pairs — a pilot on 4 096 sampled pairs decides whether the
     256-diagonal register window runs before the tiled rows (csrc/wfa_hip.hip: pilot_band; 600 bp at 10 %: it does not, 900 bp at
