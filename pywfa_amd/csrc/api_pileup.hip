@@ -196,8 +196,8 @@ extern "C" int wfa_hip_pileup_insertion_stats(wfa_hip_pileup_t* p, int64_t* reco
 
 // room for `need` elements in a block of the log that holds `have` of them: a new block of twice the size (of the exact size when that
 // fails), the old contents copied over.  A failure leaves the block as it was.
-template <class T> static int ins_log_grow(wfa_hip_aligner* al, T** block, int64_t* cap, int64_t have, int64_t need, const char* what,
-                                           const char* log = "insertion") {
+template <class T> static int pileup_log_grow(wfa_hip_aligner* al, T** block, int64_t* cap, int64_t have, int64_t need, const char* log,
+                                              const char* what) {
   if (need <= *cap) return WFA_HIP_OK;
   T* fresh = nullptr;
   int64_t want = std::max<int64_t>({need, 2 * *cap, 1024});
@@ -219,57 +219,47 @@ template <class T> static int ins_log_grow(wfa_hip_aligner* al, T** block, int64
   return WFA_HIP_OK;
 }
 
-// An add with tracking on (csrc/wfa_insertions.hpp): count, the two scans, the 16-byte download, the growth, then the table kernel in its
-// tracking form.  Nothing is added before the log has its room.
-static int pileup_add_tracked(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a, const wfa::PileupStrandArgs* s,
-                              const wfa::PileupQualArgs* u = nullptr) {
-  wfa_hip_aligner* al = p->al;
-  const size_t n = (size_t)a.npairs;
-  wfa::InsLogArgs g;
-  memset(&g, 0, sizeof(g));
-  if (sc.alloc(&g.pair_count, n) || sc.alloc(&g.rec_off, n + 1) || sc.alloc(&g.base_off, n + 1)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipMemsetAsync(g.pair_count, 0, n * sizeof(wfa::InsPairCount), al->stream));
-  uint64_t totals[2] = {0, 0};
-  {
-    ReduceTimer timer(al, "pileup insertion count", a.npairs);
-    const int lrc = wfa::launch_pileup_count(a, g, al->cu_count, al->stream);
-    timer.stop();
-    if (lrc != 0) { al->err = "pileup insertion count kernel launch failed"; return WFA_HIP_EDEVICE; }
-    if (sc.download(&totals[0], g.rec_off + n, 1) || sc.download(&totals[1], g.base_off + n, 1)) return WFA_HIP_EDEVICE;
-    HIP_TRY(al, hipStreamSynchronize(al->stream));
-  }
-  int rc = ins_log_grow(al, &p->d_rec, &p->cap_rec, p->nrec, p->nrec + (int64_t)totals[0], "records of 24 bytes");
-  if (rc == WFA_HIP_OK) rc = ins_log_grow(al, &p->d_ins, &p->cap_ins, p->nins, p->nins + (int64_t)totals[1], "inserted bases of 1 byte");
-  if (rc != WFA_HIP_OK) return rc;
-  g.records = p->d_rec; g.bases = p->d_ins;
-  g.rec_base = p->nrec; g.base_base = p->nins; g.rec_cap = p->cap_rec; g.base_cap = p->cap_ins;
-  ReduceTimer timer(al, "pileup tracked", a.npairs);
-  p->added = true;
-  rc = launch_end(al, &timer,
-                  u   ? wfa::launch_pileup_track_quals(a, g, s, *u, al->cu_count, al->stream)
-                  : s ? wfa::launch_pileup_track_strands(a, g, *s, al->cu_count, al->stream)
-                      : wfa::launch_pileup_track(a, g, al->cu_count, al->stream),
-                  "pileup kernel launch failed");
-  if (rc == WFA_HIP_OK) { p->nrec += (int64_t)totals[0]; p->nins += (int64_t)totals[1]; }
-  return rc;
-}
-
-// The deletion log's pass of an add (csrc/wfa_deletions.hpp), before the table kernel of whatever form: count, the two scans, the
-// 16-byte download, the growth; *totals = {records, deleted bases} of the batch.  Nothing has been written when it fails.
-static int pileup_deletions_count(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a, wfa::DelLogArgs* g, uint64_t* totals) {
-  wfa_hip_aligner* al = p->al;
-  const size_t n = (size_t)a.npairs;
+// The count pass of a log of an add (csrc/wfa_insertions.hpp, wfa_deletions.hpp; g: InsLogArgs or DelLogArgs, zeroed): the scratch of
+// the pass, the zeroed pair counts, launch() = count + the two scans, the 16-byte download of totals = {records, bases} of the batch.
+// The caller grows its log by them before anything is written to it.
+template <class LogArgs, class Launch>
+static int pileup_log_count(wfa_hip_aligner* al, StreamScratch& sc, int64_t npairs, LogArgs* g, uint64_t* totals, const char* label, const char* failed,
+                            Launch launch) {
+  const size_t n = (size_t)npairs;
   memset(g, 0, sizeof(*g));
   if (sc.alloc(&g->pair_count, n) || sc.alloc(&g->rec_off, n + 1) || sc.alloc(&g->base_off, n + 1)) return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipMemsetAsync(g->pair_count, 0, n * sizeof(wfa::DelPairCount), al->stream));
+  HIP_TRY(al, hipMemsetAsync(g->pair_count, 0, n * sizeof(*g->pair_count), al->stream));
   totals[0] = totals[1] = 0;
-  ReduceTimer timer(al, "pileup deletion count", a.npairs);
-  const int lrc = wfa::launch_del_count(a, *g, al->cu_count, al->stream);
+  ReduceTimer timer(al, label, npairs);
+  const int lrc = launch();
   timer.stop();
-  if (lrc != 0) { al->err = "pileup deletion count kernel launch failed"; return WFA_HIP_EDEVICE; }
+  if (lrc != 0) { al->err = failed; return WFA_HIP_EDEVICE; }
   if (sc.download(&totals[0], g->rec_off + n, 1) || sc.download(&totals[1], g->base_off + n, 1)) return WFA_HIP_EDEVICE;
   HIP_TRY(al, hipStreamSynchronize(al->stream));
-  const int rc = ins_log_grow(al, &p->d_del, &p->cap_del, p->ndel, p->ndel + (int64_t)totals[0], "records of 16 bytes", "deletion");
+  return WFA_HIP_OK;
+}
+
+// The insertion log's pass of an add with tracking on, before the table kernel in its tracking form: the count pass and the growth of
+// the two blocks.  Nothing is added before the log has its room.
+static int pileup_insertions_count(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a, wfa::InsLogArgs* g, uint64_t* totals) {
+  wfa_hip_aligner* al = p->al;
+  int rc = pileup_log_count(al, sc, a.npairs, g, totals, "pileup insertion count", "pileup insertion count kernel launch failed",
+                            [&] { return wfa::launch_pileup_count(a, *g, al->cu_count, al->stream); });
+  if (rc == WFA_HIP_OK) rc = pileup_log_grow(al, &p->d_rec, &p->cap_rec, p->nrec, p->nrec + (int64_t)totals[0], "insertion", "records of 24 bytes");
+  if (rc == WFA_HIP_OK) rc = pileup_log_grow(al, &p->d_ins, &p->cap_ins, p->nins, p->nins + (int64_t)totals[1], "insertion", "inserted bases of 1 byte");
+  if (rc != WFA_HIP_OK) return rc;
+  g->records = p->d_rec; g->bases = p->d_ins;
+  g->rec_base = p->nrec; g->base_base = p->nins; g->rec_cap = p->cap_rec; g->base_cap = p->cap_ins;
+  return WFA_HIP_OK;
+}
+
+// The deletion log's pass of an add (csrc/wfa_deletions.hpp), before the table kernel of whatever form: the count pass and the growth.
+// Nothing has been written when it fails.
+static int pileup_deletions_count(wfa_hip_pileup* p, StreamScratch& sc, const wfa::PileupArgs& a, wfa::DelLogArgs* g, uint64_t* totals) {
+  wfa_hip_aligner* al = p->al;
+  int rc = pileup_log_count(al, sc, a.npairs, g, totals, "pileup deletion count", "pileup deletion count kernel launch failed",
+                            [&] { return wfa::launch_del_count(a, *g, al->cu_count, al->stream); });
+  if (rc == WFA_HIP_OK) rc = pileup_log_grow(al, &p->d_del, &p->cap_del, p->ndel, p->ndel + (int64_t)totals[0], "deletion", "records of 16 bytes");
   if (rc != WFA_HIP_OK) return rc;
   g->records = p->d_del; g->rec_base = p->ndel; g->rec_cap = p->cap_del; g->starts = p->d_starts;
   return WFA_HIP_OK;
@@ -350,30 +340,29 @@ static int pileup_add(wfa_hip_pileup_t* p, wfa_hip_batch_t* b, const int32_t* j,
   a.meta = b->d_meta; a.words = b->d_words; a.bytes = b->d_bytes; a.pboff = b->d_pboff; a.flags = b->d_flags;
   a.npairs = n; a.j = d_j; a.t_start = d_ts; a.keep = d_keep;
   a.seq_off = p->d_off; a.seq_len = p->d_len; a.nseq = p->nseq; a.total = p->total; a.table = p->d_table;
-  const wfa::PileupStrandArgs s{d_rev, p->d_fwd};
-  // the table kernel of the pileup's form (and the insertion log's passes)
+  // the table kernel of the pileup's form (and the insertion log's count pass before it)
   const auto table_add = [&]() -> int {
+    int32_t *d_i = nullptr, *d_ps = nullptr;
     if (ql) {
-      int32_t *d_i = nullptr, *d_ps = nullptr;
       if (!stranded && sc.upload_opt(&d_rev, reverse, (size_t)n)) return WFA_HIP_EDEVICE;
       if (sc.upload(&d_i, ql->i, (size_t)n) || sc.upload_opt(&d_ps, ql->p_start, (size_t)n)) return WFA_HIP_EDEVICE;
-      const wfa::PileupStrandArgs sq{d_rev, p->d_fwd};
-      const wfa::PileupQualArgs u{ql->set->d_quals, ql->set->d_off, ql->set->d_len, ql->set->n, d_i, d_ps, d_rev,
-                                  ql->min_base_quality, ql->quality_cap, p->d_qtab};
-      if (p->track) return pileup_add_tracked(p, sc, a, stranded ? &sq : nullptr, &u);
-      ReduceTimer timer(al, "pileup qualities", n);
-      p->added = true;
-      return launch_end(al, &timer, wfa::launch_pileup_quals(a, stranded ? &sq : nullptr, u, al->cu_count, al->stream), "pileup kernel launch failed");
     }
-    if (p->track) return pileup_add_tracked(p, sc, a, stranded ? &s : nullptr);
-    if (stranded) {
-      ReduceTimer timer(al, "pileup stranded", n);
-      p->added = true;
-      return launch_end(al, &timer, wfa::launch_pileup_strands(a, s, al->cu_count, al->stream), "pileup kernel launch failed");
+    const wfa::PileupStrandArgs s{d_rev, p->d_fwd};
+    const wfa::PileupQualArgs u = ql ? wfa::PileupQualArgs{ql->set->d_quals, ql->set->d_off, ql->set->d_len, ql->set->n, d_i, d_ps, d_rev,
+                                                           ql->min_base_quality, ql->quality_cap, p->d_qtab}
+                                     : wfa::PileupQualArgs{};
+    wfa::InsLogArgs g;
+    uint64_t totals[2] = {0, 0};
+    if (p->track) {
+      const int crc = pileup_insertions_count(p, sc, a, &g, totals);
+      if (crc != WFA_HIP_OK) return crc;
     }
-    ReduceTimer timer(al, "pileup", n);
+    ReduceTimer timer(al, p->track ? "pileup tracked" : ql ? "pileup qualities" : stranded ? "pileup stranded" : "pileup", n);
     p->added = true;
-    return launch_end(al, &timer, wfa::launch_pileup(a, al->cu_count, al->stream), "pileup kernel launch failed");   // (the caller's arrays are read by the copies above)
+    const int arc = launch_end(al, &timer, wfa::launch_pileup(a, p->track ? &g : nullptr, stranded ? &s : nullptr, ql ? &u : nullptr, al->cu_count, al->stream),
+                               "pileup kernel launch failed");   // (the caller's arrays are read by the copies above)
+    if (arc == WFA_HIP_OK) { p->nrec += (int64_t)totals[0]; p->nins += (int64_t)totals[1]; }
+    return arc;
   };
   if (!p->dels) return table_add();
   // the deletion log (csrc/wfa_deletions.hpp): its room first, so that a failed growth changes nothing; its records behind the table kernel
@@ -515,13 +504,49 @@ static wfa::CallsArgs calls_args(const wfa_hip_pileup* p, const wfa_hip_seqset_t
   return a;
 }
 
-// the chunks of a run and their two arrays.  Bases per chunk: read per call, a multiple of 64 in 64 .. 2^20
+// a limit that is read per call from the environment; unset or empty: `preset`
+static int64_t env_limit(const char* name, int64_t preset) {
+  const char* env = getenv(name);
+  return env && *env ? atoll(env) : preset;
+}
+
+// the chunks of a run and their two arrays.  Bases per chunk: a multiple of 64 in 64 .. 2^20
 static int calls_chunks(StreamScratch& sc, wfa::CallsArgs* a) {
-  const char* env = getenv("WFA_HIP_CALLS_CHUNK");
-  const int64_t asked = env && *env ? atoll(env) : 4096;
+  const int64_t asked = env_limit("WFA_HIP_CALLS_CHUNK", 4096);
   a->chunk = std::min<int64_t>(1 << 20, std::max<int64_t>(64, (std::min<int64_t>(asked, 1 << 20) + 63) / 64 * 64));
   a->chunks = (a->n + a->chunk - 1) / a->chunk;
   if (sc.alloc(&a->chunk_count, (size_t)a->chunks) || sc.alloc(&a->chunk_off, (size_t)a->chunks + 1)) return WFA_HIP_EDEVICE;
+  return WFA_HIP_OK;
+}
+
+// What the reports of ordered rows (sites, genotypes, insertions, deletions) do alike behind their own checks: the refusals of a null
+// count and of null rows, then `also`, a report's own refusal that stands behind those two (nullptr: none); the device, the stream
+// waited for, *count = 0.
+static int report_begin(wfa_hip_aligner* al, int64_t cap, int64_t* count, const int32_t* rows, const char* also = nullptr) {
+  if (!count) return fail_inval(al, "pileup: null count");
+  if (cap > 0 && !rows) return fail_inval(al, "pileup: null rows with cap > 0");
+  if (also) return fail_inval(al, "%s", also);
+  HIP_TRY(al, hipSetDevice(al->device));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  *count = 0;
+  return WFA_HIP_OK;
+}
+
+// the count pass of a report over the chunks of c: launch() = count + scan under the timer `label`, *total = chunk_off[chunks] downloaded
+template <class Launch>
+static int report_total(StreamScratch& sc, const wfa::CallsArgs& c, const char* label, const char* failed, Launch launch, uint64_t* total) {
+  ReduceTimer timer(sc.al, label, c.n, "bases");
+  return calls_launched(sc, timer, launch(), failed, total, c.chunk_off + c.chunks, 1);
+}
+
+// the scratch of the select that the two logs' reports share (a: InsArgs or DelArgs, nsel set): the selected rows, their buckets over
+// the log's nrec records, the rows; the fill counters zeroed
+template <class Args> static int report_select_scratch(StreamScratch& sc, Args* a, int64_t nrec) {
+  const size_t ns = (size_t)a->nsel;
+  if (sc.alloc(&a->sel_g, ns) || sc.alloc(&a->bucket_size, ns) || sc.alloc(&a->bucket_off, ns + 1) || sc.alloc(&a->bucket_fill, ns) ||
+      sc.alloc(&a->bucket, (size_t)nrec) || sc.alloc(&a->rows, ns * 8))   // (WFA_INSERTION_COLS, WFA_DELETION_COLS)
+    return WFA_HIP_EDEVICE;
+  HIP_TRY(sc.al, hipMemsetAsync(a->bucket_fill, 0, ns * sizeof(uint32_t), sc.al->stream));
   return WFA_HIP_OK;
 }
 
@@ -550,21 +575,15 @@ extern "C" int wfa_hip_pileup_sites(wfa_hip_pileup_t* p, const wfa_hip_seqset_t*
   int64_t g0 = 0, n = 0;
   const int rc = calls_check(p, texts, true, seq, start, len, min_depth, min_permille, cap, &g0, &n);
   if (rc != WFA_HIP_OK) return rc;
-  if (!count) return fail_inval(al, "pileup: null count");
-  if (cap > 0 && !rows) return fail_inval(al, "pileup: null rows with cap > 0");
-  HIP_TRY(al, hipSetDevice(al->device));
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  *count = 0;
+  const int brc = report_begin(al, cap, count, rows);
+  if (brc != WFA_HIP_OK) return brc;
   if (n == 0) return WFA_HIP_OK;
   StreamScratch sc{al};
   wfa::CallsArgs a = calls_args(p, texts, g0, n, min_depth, min_permille);
   if (calls_chunks(sc, &a)) return WFA_HIP_EDEVICE;
   uint64_t total = 0;
-  {
-    ReduceTimer timer(al, "sites count", n, "bases");
-    const int crc = calls_launched(sc, timer, wfa::launch_sites_count(a, al->stream), "sites count kernel launch failed", &total, a.chunk_off + a.chunks, 1);
-    if (crc != WFA_HIP_OK) return crc;
-  }
+  const int crc = report_total(sc, a, "sites count", "sites count kernel launch failed", [&] { return wfa::launch_sites_count(a, al->stream); }, &total);
+  if (crc != WFA_HIP_OK) return crc;
   *count = (int64_t)total;
   a.cap = std::min<int64_t>((int64_t)total, cap);
   if (a.cap == 0) return WFA_HIP_OK;
@@ -589,11 +608,8 @@ static int pileup_genotypes(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, 
   if (min_alt_strand < 0) return fail_inval(al, "pileup: min_alt_strand = %d is negative", (int)min_alt_strand);
   if (min_alt_strand > 0 && !p->strands)
     return fail_inval(al, "pileup: min_alt_strand = %d needs a pileup made to track strands (wfa_hip_pileup_track_strands)", (int)min_alt_strand);
-  if (!count) return fail_inval(al, "pileup: null count");
-  if (cap > 0 && !rows) return fail_inval(al, "pileup: null rows with cap > 0");
-  HIP_TRY(al, hipSetDevice(al->device));
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  *count = 0;
+  const int brc = report_begin(al, cap, count, rows);
+  if (brc != WFA_HIP_OK) return brc;
   if (n == 0) return WFA_HIP_OK;
   StreamScratch sc{al};
   wfa::GenoArgs a;
@@ -602,18 +618,14 @@ static int pileup_genotypes(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, 
   a.fwd = p->strands ? p->d_fwd : nullptr; a.err_q = err_q; a.min_alt_strand = min_alt_strand;
   if (calls_chunks(sc, &a.c)) return WFA_HIP_EDEVICE;
   uint64_t total = 0;
-  {
-    ReduceTimer timer(al, "genotypes count", n, "bases");
-    const int crc = calls_launched(sc, timer, wfa::launch_genotypes_count(a, al->stream), "genotypes count kernel launch failed", &total, a.c.chunk_off + a.c.chunks, 1);
-    if (crc != WFA_HIP_OK) return crc;
-  }
+  const int crc = report_total(sc, a.c, "genotypes count", "genotypes count kernel launch failed", [&] { return wfa::launch_genotypes_count(a, al->stream); }, &total);
+  if (crc != WFA_HIP_OK) return crc;
   *count = (int64_t)total;
   a.c.cap = std::min<int64_t>((int64_t)total, cap);
   if (a.c.cap == 0) return WFA_HIP_OK;
   if (sc.alloc(&a.c.rows, (size_t)a.c.cap * WFA_GENOTYPE_COLS)) return WFA_HIP_EDEVICE;
   ReduceTimer timer(al, "genotypes scatter", n, "bases");
-  return calls_launched(sc, timer, quals ? wfa::launch_genotypes_quals_scatter(a, p->d_qtab, al->stream) : wfa::launch_genotypes_scatter(a, al->stream),
-                        "genotypes scatter kernel launch failed", rows, a.c.rows, (size_t)a.c.cap * WFA_GENOTYPE_COLS);
+  return calls_launched(sc, timer, wfa::launch_genotypes_scatter(a, quals, p->d_qtab, al->stream), "genotypes scatter kernel launch failed", rows, a.c.rows, (size_t)a.c.cap * WFA_GENOTYPE_COLS);
 }
 
 extern "C" int wfa_hip_pileup_genotypes(wfa_hip_pileup_t* p, const wfa_hip_seqset_t* texts, int32_t seq, int64_t start, int64_t len,
@@ -641,37 +653,25 @@ extern "C" int wfa_hip_pileup_insertions(wfa_hip_pileup_t* p, const wfa_hip_seqs
   if (rc != WFA_HIP_OK) return rc;
   if (!p->track) return fail_inval(al, "pileup: this pileup was not made to track insertions");
   if (bases_cap < 0) return fail_inval(al, "pileup: bases_cap = %lld is negative", (long long)bases_cap);
-  if (!count || !bases_count) return fail_inval(al, "pileup: null count");
-  if (cap > 0 && !rows) return fail_inval(al, "pileup: null rows with cap > 0");
-  if (bases_cap > 0 && !bases) return fail_inval(al, "pileup: null bases with bases_cap > 0");
-  HIP_TRY(al, hipSetDevice(al->device));
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  *count = 0; *bases_count = 0;
+  if (!bases_count) return fail_inval(al, "pileup: null count");
+  const int brc = report_begin(al, cap, count, rows, bases_cap > 0 && !bases ? "pileup: null bases with bases_cap > 0" : nullptr);
+  if (brc != WFA_HIP_OK) return brc;
+  *bases_count = 0;
   if (n == 0) return WFA_HIP_OK;
-  // records per row one wave reduces: read per call, as the chunk is
-  const char* env = getenv("WFA_HIP_INS_MAX_READS");
-  const int64_t asked = env && *env ? atoll(env) : WFA_HIP_INS_MAX_READS;
   StreamScratch sc{al};
   wfa::InsArgs a;
   memset(&a, 0, sizeof(a));
   a.c = calls_args(p, texts, g0, n, min_depth, min_permille);
-  a.max_reads = (int32_t)std::min<int64_t>(INT32_MAX, std::max<int64_t>(1, asked));
+  a.max_reads = (int32_t)std::min<int64_t>(INT32_MAX, std::max<int64_t>(1, env_limit("WFA_HIP_INS_MAX_READS", WFA_HIP_INS_MAX_READS)));   // records per row one wave reduces
   a.records = p->d_rec; a.bases = p->d_ins; a.nrec = p->nrec;
   if (calls_chunks(sc, &a.c)) return WFA_HIP_EDEVICE;
   uint64_t nsel = 0;
-  {
-    ReduceTimer timer(al, "insertions count", n, "bases");
-    const int crc = calls_launched(sc, timer, wfa::launch_ins_select_count(a, al->stream), "insertions count kernel launch failed", &nsel, a.c.chunk_off + a.c.chunks, 1);
-    if (crc != WFA_HIP_OK) return crc;
-  }
+  const int crc = report_total(sc, a.c, "insertions count", "insertions count kernel launch failed", [&] { return wfa::launch_ins_select_count(a, al->stream); }, &nsel);
+  if (crc != WFA_HIP_OK) return crc;
   if (nsel == 0) return WFA_HIP_OK;
   a.nsel = (int64_t)nsel;
   const size_t ns = (size_t)nsel;
-  if (sc.alloc(&a.sel_g, ns) || sc.alloc(&a.bucket_size, ns) || sc.alloc(&a.bucket_off, ns + 1) || sc.alloc(&a.bucket_fill, ns) ||
-      sc.alloc(&a.bucket, (size_t)p->nrec) || sc.alloc(&a.rows, ns * WFA_INSERTION_COLS) || sc.alloc(&a.best, ns) ||
-      sc.alloc(&a.allele_len, ns) || sc.alloc(&a.letter_off, ns + 1))
-    return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipMemsetAsync(a.bucket_fill, 0, ns * sizeof(uint32_t), al->stream));
+  if (report_select_scratch(sc, &a, p->nrec) || sc.alloc(&a.best, ns) || sc.alloc(&a.allele_len, ns) || sc.alloc(&a.letter_off, ns + 1)) return WFA_HIP_EDEVICE;
   uint64_t nletters = 0;
   {
     ReduceTimer timer(al, "insertions reduce", (int64_t)nsel, "rows");
@@ -722,38 +722,25 @@ extern "C" int wfa_hip_pileup_deletions(wfa_hip_pileup_t* p, const wfa_hip_seqse
   const int rc = calls_check(p, texts, true, seq, start, len, min_depth, min_permille, cap, &g0, &n, 0);
   if (rc != WFA_HIP_OK) return rc;
   if (!p->dels) return fail_inval(al, "pileup: this pileup was not made to track deletions");
-  if (!count) return fail_inval(al, "pileup: null count");
-  if (cap > 0 && !rows) return fail_inval(al, "pileup: null rows with cap > 0");
-  HIP_TRY(al, hipSetDevice(al->device));
-  HIP_TRY(al, hipStreamSynchronize(al->stream));
-  *count = 0;
+  const int brc = report_begin(al, cap, count, rows);
+  if (brc != WFA_HIP_OK) return brc;
   if (n == 0) return WFA_HIP_OK;
-  // records per row one wave reduces: read per call, as the chunk is
-  const char* env = getenv("WFA_HIP_DEL_MAX_READS");
-  const int64_t asked = env && *env ? atoll(env) : WFA_HIP_DEL_MAX_READS;
   StreamScratch sc{al};
   wfa::DelArgs a;
   memset(&a, 0, sizeof(a));
   a.c = calls_args(p, texts, g0, n, min_depth, min_permille);
   a.starts = p->d_starts;
-  a.max_reads = (int32_t)std::min<int64_t>(INT32_MAX, std::max<int64_t>(1, asked));
+  a.max_reads = (int32_t)std::min<int64_t>(INT32_MAX, std::max<int64_t>(1, env_limit("WFA_HIP_DEL_MAX_READS", WFA_HIP_DEL_MAX_READS)));   // records per row one wave reduces
   a.records = p->d_del; a.nrec = p->ndel;
   if (calls_chunks(sc, &a.c)) return WFA_HIP_EDEVICE;
   uint64_t nsel = 0;
-  {
-    ReduceTimer timer(al, "deletions count", n, "bases");
-    const int crc = calls_launched(sc, timer, wfa::launch_del_select_count(a, al->stream), "deletions count kernel launch failed", &nsel, a.c.chunk_off + a.c.chunks, 1);
-    if (crc != WFA_HIP_OK) return crc;
-  }
+  const int crc = report_total(sc, a.c, "deletions count", "deletions count kernel launch failed", [&] { return wfa::launch_del_select_count(a, al->stream); }, &nsel);
+  if (crc != WFA_HIP_OK) return crc;
   *count = (int64_t)nsel;
   const int64_t k = std::min<int64_t>((int64_t)nsel, cap);
   if (k == 0) return WFA_HIP_OK;
   a.nsel = (int64_t)nsel;
-  const size_t ns = (size_t)nsel;
-  if (sc.alloc(&a.sel_g, ns) || sc.alloc(&a.bucket_size, ns) || sc.alloc(&a.bucket_off, ns + 1) || sc.alloc(&a.bucket_fill, ns) ||
-      sc.alloc(&a.bucket, (size_t)p->ndel) || sc.alloc(&a.rows, ns * WFA_DELETION_COLS))
-    return WFA_HIP_EDEVICE;
-  HIP_TRY(al, hipMemsetAsync(a.bucket_fill, 0, ns * sizeof(uint32_t), al->stream));
+  if (report_select_scratch(sc, &a, p->ndel)) return WFA_HIP_EDEVICE;
   ReduceTimer timer(al, "deletions reduce", (int64_t)nsel, "rows");
   int lrc = wfa::launch_del_select(a, al->stream);
   if (lrc == 0) lrc = wfa::launch_del_reduce(a, al->cu_count, al->stream);

@@ -1,19 +1,19 @@
 // k_deletions.hip — the record side of a pileup's deletion log and its reduction to one deletion length per reported row
-// (wfa_deletions.hpp: the rule, the layout and the kernels' outline; pileup_add_deletions and wfa_hip_pileup_deletions in api_pileup.hip).
+// (wfa_deletions.hpp: the rule, the layout and the kernels' outline; k_select.hpp: the select's passes and the fill; pileup_deletions_count / _scatter and wfa_hip_pileup_deletions in api_pileup.hip).
 // Stores: count pair_count[q] for q < npairs; scatter a record at an index below rec_cap and one atomicAdd on starts[g], g inside the
 // pair's text window, which the kernel checks to lie inside its sequence as the table kernel does; the select kernels
 // chunk_count[ch] / row `rank` of sel_g, bucket_size and rows for rank < nsel; fill a slot below its row's bucket size and below
 // nrec; reduce row `row` < nsel.  Every index read from the log is checked against the selected rows before it is used.
-#include <algorithm>
-#include "k_seed.hpp"   // (the workgroup sum of the seed kernels)
+#include "k_select.hpp"
 #include "wfa_deletions.hpp"
-#include "wfa_insertions.hpp"   // (launch_ins_scan)
 
 namespace wfa {
 
 // ---- the record side: a wave per pair, 64 ops per round --------------------------------------------------------------------------------
 // SCATTER false: pair_count[q] of a contributing pair (the host zeroes the array).  SCATTER true: the pair's records from its scanned
-// offset, and starts[g] += 1 per record.
+// offset, and starts[g] += 1 per record.  The lines up to the window check are pileup_walk's (k_pileup.hip), written out in both:
+// behind a shared function the scatter kernel here ran 4 % longer and the table kernel took 6 more VGPRs.  The carry of an open run
+// reads like pileup_walk's too but closes on another ballot: here on dv, the COUNTED I ops, there on every D op of the round.
 template <bool SCATTER>
 __device__ __forceinline__ void del_walk(const PileupArgs& a, const DelLogArgs& g) {
   const int lane = threadIdx.x & 63;
@@ -104,106 +104,32 @@ __device__ __forceinline__ void del_walk(const PileupArgs& a, const DelLogArgs& 
 __global__ void __launch_bounds__(256) wfa_del_count_kernel(PileupArgs a, DelLogArgs g) { del_walk<false>(a, g); }
 __global__ void __launch_bounds__(256) wfa_del_scatter_kernel(PileupArgs a, DelLogArgs g) { del_walk<true>(a, g); }
 
-static unsigned pair_grid(const PileupArgs& a, int cu_count) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.npairs + 3) / 4, (int64_t)cu_count * 16));
-}
-
 int launch_del_count(const PileupArgs& a, const DelLogArgs& g, int cu_count, hipStream_t stream) {
   if (a.npairs <= 0) return 0;
-  hipLaunchKernelGGL(wfa_del_count_kernel, dim3(pair_grid(a, cu_count)), dim3(256), 0, stream, a, g);
+  hipLaunchKernelGGL(wfa_del_count_kernel, dim3(wave_grid(a.npairs, cu_count)), dim3(256), 0, stream, a, g);
   if (hipGetLastError() != hipSuccess) return -1;
   const uint32_t* counts = reinterpret_cast<const uint32_t*>(g.pair_count);
-  if (launch_ins_scan(counts, 2, g.rec_off, a.npairs, stream) != 0) return -1;
-  return launch_ins_scan(counts + 1, 2, g.base_off, a.npairs, stream);
+  if (launch_scan64(counts, 2, g.rec_off, a.npairs, stream) != 0) return -1;
+  return launch_scan64(counts + 1, 2, g.base_off, a.npairs, stream);
 }
 
 int launch_del_scatter(const PileupArgs& a, const DelLogArgs& g, int cu_count, hipStream_t stream) {
   if (a.npairs <= 0) return 0;
   if (!g.starts) return -1;
-  hipLaunchKernelGGL(wfa_del_scatter_kernel, dim3(pair_grid(a, cu_count)), dim3(256), 0, stream, a, g);
+  hipLaunchKernelGGL(wfa_del_scatter_kernel, dim3(wave_grid(a.npairs, cu_count)), dim3(256), 0, stream, a, g);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// ---- select: the reported rows, in ascending global index ---------------------------------------------------------------------------------
-// whether base i of the run is a reported row (false behind the run's end); its depth and S
-__device__ inline bool del_flag(const DelArgs& a, int64_t i, int64_t* depth, int32_t* S) {
-  const CallsArgs& c = a.c;
-  if (i >= c.n) return false;
-  const int64_t g = c.g0 + i;
-  int64_t d = 0;
-#pragma unroll
-  for (int x = 0; x < 6; ++x) d += c.table[(int64_t)x * c.total + g];
-  *depth = d;
-  *S = a.starts[g];
-  return del_selected(d, *S, c.min_depth, c.min_permille);
-}
-
+// ---- select: the reported rows, in ascending global index; fill: the length of every record of the log into the bucket of its row
+// (k_select.hpp) ----------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) wfa_del_select_count_kernel(DelArgs a) {
-  __shared__ uint32_t s_red[4];
-  const CallsArgs& c = a.c;
-  for (int64_t ch = blockIdx.x; ch < c.chunks; ch += gridDim.x) {
-    const int64_t i0 = ch * c.chunk;
-    uint32_t mine = 0;   // the rows of this wave's rounds (the same in every lane)
-    for (int64_t t = threadIdx.x; t < c.chunk; t += 256) {
-      int64_t depth; int32_t S;
-      mine += (uint32_t)__builtin_popcountll(__ballot(del_flag(a, i0 + t, &depth, &S)));
-    }
-    const uint32_t sum = seed_block_sum((threadIdx.x & 63) == 0 ? mine : 0u, s_red);
-    if (threadIdx.x == 0) c.chunk_count[ch] = sum;
-  }
+  select_count(a.c, [&](int64_t i) { int64_t depth; int32_t E; return event_flag(a.c, a.starts, i, &depth, &E); });
 }
 
-__global__ void __launch_bounds__(256) wfa_del_select_kernel(DelArgs a) {
-  __shared__ uint32_t s_red[4];
-  const CallsArgs& c = a.c;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long lower = (1ull << lane) - 1ull;
-  for (int64_t ch = blockIdx.x; ch < c.chunks; ch += gridDim.x) {
-    uint64_t run = c.chunk_off[ch];
-    if (c.chunk_off[ch + 1] == run) continue;   // (uniform over the workgroup)
-    const int64_t i0 = ch * c.chunk;
-    for (int64_t t0 = 0; t0 < c.chunk; t0 += 256) {
-      const int64_t i = i0 + t0 + threadIdx.x;
-      int64_t depth = 0; int32_t S = 0;
-      const bool sel = t0 + threadIdx.x < c.chunk && del_flag(a, i, &depth, &S);
-      const unsigned long long m = __ballot(sel);
-      if (lane == 0) s_red[wave] = (uint32_t)__builtin_popcountll(m);
-      __syncthreads();
-      uint32_t before = 0;
-      for (int w = 0; w < wave; ++w) before += s_red[w];
-      const uint32_t total = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-      __syncthreads();
-      const uint64_t rank = run + before + (uint32_t)__builtin_popcountll(m & lower);
-      run += total;
-      if (!sel || rank >= (uint64_t)a.nsel) continue;
-      const int64_t g = c.g0 + i;
-      int64_t lo = 0, hi = c.nseq;   // the first sequence that starts behind g; its predecessor owns g
-      while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (c.seq_off[mid] > g) hi = mid; else lo = mid + 1; }
-      const int64_t j = lo - 1;
-      const bool overflow = S > a.max_reads;
-      a.sel_g[rank] = g;
-      a.bucket_size[rank] = overflow ? 0u : (uint32_t)S;
-      int4* row = reinterpret_cast<int4*>(a.rows + rank * WFA_DELETION_COLS);
-      row[0] = make_int4((int32_t)j, (int32_t)(g - c.seq_off[j]), (int32_t)depth, S);
-      row[1] = make_int4(0, 0, 0, overflow ? 1 : 0);
-    }
-  }
-}
+__global__ void __launch_bounds__(256) wfa_del_select_kernel(DelArgs a) { event_select(a, a.starts); }
 
-// ---- fill: the length of every record of the log into the bucket of its row -----------------------------------------------------------------
 __global__ void __launch_bounds__(256) wfa_del_fill_kernel(DelArgs a) {
-  const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.nrec; r += nthreads) {
-    const DelRecord rec = a.records[r];
-    if (rec.g < a.c.g0 || rec.g >= a.c.g0 + a.c.n) continue;
-    int64_t lo = 0, hi = a.nsel;   // the first selected row at or behind g
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.sel_g[mid] < rec.g) lo = mid + 1; else hi = mid; }
-    if (lo >= a.nsel || a.sel_g[lo] != rec.g) continue;
-    const uint32_t size = a.bucket_size[lo];
-    if (size == 0) continue;
-    const uint32_t slot = atomicAdd(a.bucket_fill + lo, 1u);
-    if (slot < size && a.bucket_off[lo] + slot < (uint64_t)a.nrec) a.bucket[a.bucket_off[lo] + slot] = rec.n;   // (the buckets are sized from the plane, the array from the log)
-  }
+  event_fill(a, [](int64_t, const DelRecord& rec) { return rec.n; });
 }
 
 // ---- reduce: a wave per row ----------------------------------------------------------------------------------------------------------------
@@ -240,9 +166,6 @@ __global__ void __launch_bounds__(256) wfa_del_reduce_kernel(DelArgs a) {
   }
 }
 
-static unsigned chunk_grid(int64_t chunks) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(chunks, 1 << 16)); }
-static unsigned wave_grid(int64_t waves, int cu_count) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)cu_count * 16)); }
-
 int launch_del_select_count(const DelArgs& a, hipStream_t stream) {
   if (a.c.chunks > 0) hipLaunchKernelGGL(wfa_del_select_count_kernel, dim3(chunk_grid(a.c.chunks)), dim3(256), 0, stream, a);
   if (hipGetLastError() != hipSuccess) return -1;
@@ -253,15 +176,12 @@ int launch_del_select(const DelArgs& a, hipStream_t stream) {
   if (a.c.chunks <= 0 || a.nsel <= 0) return 0;
   hipLaunchKernelGGL(wfa_del_select_kernel, dim3(chunk_grid(a.c.chunks)), dim3(256), 0, stream, a);
   if (hipGetLastError() != hipSuccess) return -1;
-  return launch_ins_scan(a.bucket_size, 1, a.bucket_off, a.nsel, stream);
+  return launch_scan64(a.bucket_size, 1, a.bucket_off, a.nsel, stream);
 }
 
 int launch_del_reduce(const DelArgs& a, int cu_count, hipStream_t stream) {
   if (a.nsel <= 0) return 0;
-  if (a.nrec > 0) {
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.nrec + 255) / 256, (int64_t)cu_count * 32));
-    hipLaunchKernelGGL(wfa_del_fill_kernel, dim3(grid), dim3(256), 0, stream, a);
-  }
+  if (a.nrec > 0) hipLaunchKernelGGL(wfa_del_fill_kernel, dim3(thread_grid(a.nrec, cu_count)), dim3(256), 0, stream, a);
   hipLaunchKernelGGL(wfa_del_reduce_kernel, dim3(wave_grid(a.nsel, cu_count)), dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -1,12 +1,13 @@
 // k_pileup.hip — the pileup reduction (wfa_pileup.hpp: PileupArgs; wfa_hip_pileup_add in api_pileup.hip) and the record side of the
 // insertion log (wfa_insertions.hpp: InsLogArgs).
 // One wave per pair, grid-stride.  Every store to the table is an int32 atomicAdd; a lane adds only for an op of the aligned core
-// whose text position lies inside the pair's text window, and the host has checked that the window lies inside its sequence, so an op
-// string that disagreed with its pair's lengths could lose counts but never leave the table.  The stranded forms add a second time at
-// the same offset of the forward table, the forms with qualities once more at the same offset of the quality table, each an allocation
-// of the table's size.  The log's stores are plain: a record
-// and a column byte have one writer, at an index below the allocated size (checked at the store).
-#include <algorithm>
+// whose text position lies inside the pair's text window, and the host and the kernel have checked that the window lies
+// inside its sequence, so an op string that disagreed with its pair's lengths could lose counts but never leave the table.  The
+// stranded forms add a second time at the same offset of the forward table, the forms with qualities once more at the same offset of
+// the quality table, each an allocation of the table's size.  The log's stores are plain: a record and a column byte have one writer,
+// at an index below the allocated size (checked at the store); the count form stores pair_count[q], q < npairs, and nothing else.
+// The forms are the instantiations of one kernel template, picked by the one launcher from the argument structs it is given.
+#include "k_select.hpp"   // (the wave grid, the 64-bit scan)
 #include "wfa_insertions.hpp"
 
 namespace wfa {
@@ -168,84 +169,33 @@ __device__ __forceinline__ void pileup_walk(const PileupArgs& a, const InsLogArg
   }
 }
 
-__global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a) { pileup_walk<PILEUP_TABLE, false, false>(a, InsLogArgs{}, PileupStrandArgs{}, PileupQualArgs{}); }
-__global__ void __launch_bounds__(256) wfa_pileup_count_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_COUNT, false, false>(a, g, PileupStrandArgs{}, PileupQualArgs{}); }
-__global__ void __launch_bounds__(256) wfa_pileup_track_kernel(PileupArgs a, InsLogArgs g) { pileup_walk<PILEUP_TRACK, false, false>(a, g, PileupStrandArgs{}, PileupQualArgs{}); }
-// the stranded forms (COUNT stores nothing to a table and has none)
-__global__ void __launch_bounds__(256) wfa_pileup_strands_kernel(PileupArgs a, PileupStrandArgs s) { pileup_walk<PILEUP_TABLE, true, false>(a, InsLogArgs{}, s, PileupQualArgs{}); }
-__global__ void __launch_bounds__(256) wfa_pileup_track_strands_kernel(PileupArgs a, InsLogArgs g, PileupStrandArgs s) {
-  pileup_walk<PILEUP_TRACK, true, false>(a, g, s, PileupQualArgs{});
-}
-// the forms with qualities, each with and without strands
-__global__ void __launch_bounds__(256) wfa_pileup_quals_kernel(PileupArgs a, PileupQualArgs u) {
-  pileup_walk<PILEUP_TABLE, false, true>(a, InsLogArgs{}, PileupStrandArgs{}, u);
-}
-__global__ void __launch_bounds__(256) wfa_pileup_quals_strands_kernel(PileupArgs a, PileupStrandArgs s, PileupQualArgs u) {
-  pileup_walk<PILEUP_TABLE, true, true>(a, InsLogArgs{}, s, u);
-}
-__global__ void __launch_bounds__(256) wfa_pileup_track_quals_kernel(PileupArgs a, InsLogArgs g, PileupQualArgs u) {
-  pileup_walk<PILEUP_TRACK, false, true>(a, g, PileupStrandArgs{}, u);
-}
-__global__ void __launch_bounds__(256) wfa_pileup_track_quals_strands_kernel(PileupArgs a, InsLogArgs g, PileupStrandArgs s, PileupQualArgs u) {
-  pileup_walk<PILEUP_TRACK, true, true>(a, g, s, u);
-}
-
-static unsigned pileup_grid(const PileupArgs& a, int cu_count) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.npairs + 3) / 4, (int64_t)cu_count * 16));
-}
-
-int launch_pileup(const PileupArgs& a, int cu_count, hipStream_t stream) {
-  if (a.npairs <= 0) return 0;
-  const unsigned grid = pileup_grid(a, cu_count);
-  hipLaunchKernelGGL(wfa_pileup_kernel, dim3(grid), dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_pileup_strands(const PileupArgs& a, const PileupStrandArgs& s, int cu_count, hipStream_t stream) {
-  if (a.npairs <= 0) return 0;
-  if (!s.fwd) return -1;
-  hipLaunchKernelGGL(wfa_pileup_strands_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, s);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+// one kernel per form; a form reads only the argument structs its flags name
+template <int MODE, bool STRANDS, bool QUALS>
+__global__ void __launch_bounds__(256) wfa_pileup_kernel(PileupArgs a, InsLogArgs g, PileupStrandArgs s, PileupQualArgs u) {
+  pileup_walk<MODE, STRANDS, QUALS>(a, g, s, u);
 }
 
 int launch_pileup_count(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream) {
   if (a.npairs <= 0) return 0;
-  hipLaunchKernelGGL(wfa_pileup_count_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g);
+  hipLaunchKernelGGL((wfa_pileup_kernel<PILEUP_COUNT, false, false>), dim3(wave_grid(a.npairs, cu_count)), dim3(256), 0, stream, a, g,
+                     PileupStrandArgs{}, PileupQualArgs{});
   if (hipGetLastError() != hipSuccess) return -1;
   const uint32_t* counts = reinterpret_cast<const uint32_t*>(g.pair_count);
-  if (launch_ins_scan(counts, 2, g.rec_off, a.npairs, stream) != 0) return -1;
-  return launch_ins_scan(counts + 1, 2, g.base_off, a.npairs, stream);
+  if (launch_scan64(counts, 2, g.rec_off, a.npairs, stream) != 0) return -1;
+  return launch_scan64(counts + 1, 2, g.base_off, a.npairs, stream);
 }
 
-int launch_pileup_track(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream) {
+int launch_pileup(const PileupArgs& a, const InsLogArgs* g, const PileupStrandArgs* s, const PileupQualArgs* u, int cu_count, hipStream_t stream) {
   if (a.npairs <= 0) return 0;
-  hipLaunchKernelGGL(wfa_pileup_track_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_pileup_track_strands(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs& s, int cu_count, hipStream_t stream) {
-  if (a.npairs <= 0) return 0;
-  if (!s.fwd) return -1;
-  hipLaunchKernelGGL(wfa_pileup_track_strands_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g, s);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-static bool pileup_quals_ok(const PileupQualArgs& u) { return u.quals && u.qoff && u.qlen && u.i && u.qtab; }
-
-int launch_pileup_quals(const PileupArgs& a, const PileupStrandArgs* s, const PileupQualArgs& u, int cu_count, hipStream_t stream) {
-  if (a.npairs <= 0) return 0;
-  if (!pileup_quals_ok(u) || (s && !s->fwd)) return -1;
-  if (s) hipLaunchKernelGGL(wfa_pileup_quals_strands_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, *s, u);
-  else hipLaunchKernelGGL(wfa_pileup_quals_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, u);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_pileup_track_quals(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs* s, const PileupQualArgs& u, int cu_count,
-                              hipStream_t stream) {
-  if (a.npairs <= 0) return 0;
-  if (!pileup_quals_ok(u) || (s && !s->fwd)) return -1;
-  if (s) hipLaunchKernelGGL(wfa_pileup_track_quals_strands_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g, *s, u);
-  else hipLaunchKernelGGL(wfa_pileup_track_quals_kernel, dim3(pileup_grid(a, cu_count)), dim3(256), 0, stream, a, g, u);
+  if ((s && !s->fwd) || (u && !(u->quals && u->qoff && u->qlen && u->i && u->qtab))) return -1;
+  using Kernel = void (*)(PileupArgs, InsLogArgs, PileupStrandArgs, PileupQualArgs);
+  static const Kernel forms[2][2][2] = {   // [g][s][u]
+      {{wfa_pileup_kernel<PILEUP_TABLE, false, false>, wfa_pileup_kernel<PILEUP_TABLE, false, true>},
+       {wfa_pileup_kernel<PILEUP_TABLE, true, false>, wfa_pileup_kernel<PILEUP_TABLE, true, true>}},
+      {{wfa_pileup_kernel<PILEUP_TRACK, false, false>, wfa_pileup_kernel<PILEUP_TRACK, false, true>},
+       {wfa_pileup_kernel<PILEUP_TRACK, true, false>, wfa_pileup_kernel<PILEUP_TRACK, true, true>}}};
+  hipLaunchKernelGGL(forms[g != nullptr][s != nullptr][u != nullptr], dim3(wave_grid(a.npairs, cu_count)), dim3(256), 0, stream, a,
+                     g ? *g : InsLogArgs{}, s ? *s : PileupStrandArgs{}, u ? *u : PileupQualArgs{});
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

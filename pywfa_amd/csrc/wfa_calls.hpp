@@ -11,7 +11,8 @@
 // sequence, and every sequence (seq = -1), are both one run [g0, g0 + n) of global indices, and ascending global index is ascending
 // (j, pos).  Neighbouring lanes take neighbouring bases: seven coalesced int32 reads and one byte per base, 29 bytes.
 //
-// Kernels (k_calls.hip):
+// Kernels (k_calls.hip; the count and the scatter pass are the templates of k_select.hpp, which the genotypes and the two logs'
+// reports instantiate under predicates of their own):
 //   calls    a thread per base, grid-stride; one byte stored per base.
 //   sites    three passes over chunks of `chunk` bases (a multiple of 64; WFA_HIP_CALLS_CHUNK), no atomics, no waiting on other
 //            workgroups:
@@ -103,20 +104,8 @@ __host__ __device__ inline bool calls_ins(const CallsBase& b, int32_t min_permil
   return b.c[6] >= 1 && 1000 * (int64_t)b.c[6] >= (int64_t)min_permille * b.depth;
 }
 
-// GENOTYPE of an event with R reference and A alternate reads: the smallest of L0 = err_q A, L1 = 3 (R + A), L2 = err_q R, the
-// smaller index on a tie; gq = min(99, second smallest - smallest)
-__host__ __device__ inline void calls_genotype(int64_t R, int64_t A, int32_t err_q, int32_t* gt, int32_t* gq) {
-  const int64_t L0 = (int64_t)err_q * A, L1 = 3 * (R + A), L2 = (int64_t)err_q * R;
-  int best = 0;
-  int64_t lo = L0, next = L1 < L2 ? L1 : L2;
-  if (L1 < lo) { best = 1; lo = L1; next = L0 < L2 ? L0 : L2; }
-  if (L2 < lo) { best = 2; lo = L2; next = L0 < L1 ? L0 : L1; }
-  const int64_t d = next - lo;
-  *gt = best;
-  *gq = (int32_t)(d < 99 ? d : 99);
-}
-
-// GENOTYPE over three given costs (include/wfa_hip.h, "base qualities": the costs are sums of capped qualities)
+// GENOTYPE over three given costs L0, L1, L2 (homozygous reference, heterozygous, homozygous alternate): the smallest, the smaller
+// index on a tie; gq = min(99, second smallest - smallest)
 __host__ __device__ inline void calls_genotype_costs(int64_t L0, int64_t L1, int64_t L2, int32_t* gt, int32_t* gq) {
   int best = 0;
   int64_t lo = L0, next = L1 < L2 ? L1 : L2;
@@ -127,15 +116,27 @@ __host__ __device__ inline void calls_genotype_costs(int64_t L0, int64_t L1, int
   *gq = (int32_t)(d < 99 ? d : 99);
 }
 
-int launch_genotypes_count(const GenoArgs& a, hipStream_t stream);     // count + scan, as launch_sites_count
-int launch_genotypes_scatter(const GenoArgs& a, hipStream_t stream);
-// the scatter pass with the costs of "base qualities": qtab is the pileup's quality table (the table's planes and stride), read only
-// at bases that are reported, in the planes of the events' columns.  The count pass is launch_genotypes_count: the selection is the same.
-int launch_genotypes_quals_scatter(const GenoArgs& a, const int32_t* qtab, hipStream_t stream);
+// GENOTYPE of an event with R reference and A alternate reads: the costs L0 = err_q A, L1 = 3 (R + A), L2 = err_q R.  (Under "base
+// qualities", include/wfa_hip.h, the costs are sums of capped qualities instead.)
+__host__ __device__ inline void calls_genotype(int64_t R, int64_t A, int32_t err_q, int32_t* gt, int32_t* gq) {
+  calls_genotype_costs((int64_t)err_q * A, 3 * (R + A), (int64_t)err_q * R, gt, gq);
+}
+
+// whether a base with E events of a log (c6 of the insertions, starts[g] of the deletions) is a reported row of that log's report
+// (include/wfa_hip.h, "insertions" / "deletions": the ins condition of SITE on E, or bit 3 of CALL on E under min_permille 0)
+__host__ __device__ inline bool event_selected(int64_t depth, int32_t E, int32_t min_depth, int32_t min_permille) {
+  if (depth < min_depth) return false;
+  if (min_permille > 0) return E >= 1 && 1000 * (int64_t)E >= (int64_t)min_permille * depth;
+  return 2 * (int64_t)E > depth;
+}
 
 int launch_calls(const CallsArgs& a, int cu_count, hipStream_t stream);
 int launch_sites_count(const CallsArgs& a, hipStream_t stream);     // count + scan: chunk_off[chunks] is the number of sites
 int launch_sites_scatter(const CallsArgs& a, hipStream_t stream);
-int launch_sites_scan(const CallsArgs& a, hipStream_t stream);      // the scan alone, over chunk counts another count kernel wrote (wfa_insertions.hpp)
+int launch_sites_scan(const CallsArgs& a, hipStream_t stream);      // the scan alone, over chunk counts another count kernel wrote (the two logs' selects)
+int launch_genotypes_count(const GenoArgs& a, hipStream_t stream);  // count + scan, as launch_sites_count
+// the scatter pass; quals: with the costs of "base qualities" from qtab, the pileup's quality table (the table's planes and stride), read
+// only at bases that are reported, in the planes of the events' columns.  The count pass is the same for both: the selection is.
+int launch_genotypes_scatter(const GenoArgs& a, bool quals, const int32_t* qtab, hipStream_t stream);
 
 }  // namespace wfa

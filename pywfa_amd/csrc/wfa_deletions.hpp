@@ -13,8 +13,8 @@
 //            popcount of the text-consuming ballot below the lane); pair_count[q] = {records, deleted bases} of pair q (zero for a
 //            pair that does not contribute).  A run's start is an I whose predecessor — the lane below, or the last op of the previous
 //            round — is not a counted I.
-//   scan     wfa_ins_scan_kernel twice (wfa_insertions.hpp): the exclusive 64-bit prefixes, the two totals behind them (downloaded:
-//            16 bytes; the log grows before anything is written)
+//   scan     wfa_scan64_kernel twice (k_select.hpp, k_calls.hip): the exclusive 64-bit prefixes, the two totals behind them
+//            (downloaded: 16 bytes; the log grows before anything is written)
 //   scatter  wfa_del_scatter_kernel: the same walk; the lane at a run's start writes (g, n) at the pair's scanned offset + the starts
 //            in front of it when the run ends inside the 64-op round, otherwise the run stays OPEN (the scheme wfa_insertions.hpp
 //            describes for D runs): its row, its slot and its length so far are carried wave-uniformly into the next rounds, and lane 0
@@ -24,13 +24,13 @@
 // outran its pair is cut where column 5 stops counting it, and g always lies inside the pair's text, hence inside the plane.
 //
 // Reduction (k_deletions.hip), wfa_hip_pileup_deletions:
-//   select   the chunk count / scan / scatter of the sites (wfa_calls.hpp) under the deletion predicate on (depth, S = starts[g]):
+//   select   the chunk count / scan / scatter of the sites (wfa_calls.hpp, k_select.hpp) under event_selected(depth, S = starts[g]):
 //            the selected rows' global indices in ascending order, their columns j, pos, depth, del_count, overflow, and a bucket size
 //            per row (S; 0 for an overflow row)
 //   scan     the bucket sizes -> bucket offsets
-//   fill     a thread per record of the log: a binary search of its row among the selected ones; a record on a selected row puts
-//            its length into the next free slot of that row's bucket (an atomic counter per row: the order inside a bucket is
-//            whatever scheduling gives, and nothing that is written out depends on it)
+//   fill     (k_select.hpp, shared with the insertions) a thread per record of the log: a binary search of its row among the selected
+//            ones; a record on a selected row puts its length into the next free slot of that row's bucket (an atomic counter per
+//            row: the order inside a bucket is whatever scheduling gives, and nothing that is written out depends on it)
 //   reduce   a wave per row: every length's multiplicity among the bucket's lengths, the best under (count descending, n ascending),
 //            and the number of distinct lengths (the slots without an equal one in a lower slot)
 // The work of the one wave that serves a row is bounded by WFA_HIP_DEL_MAX_READS (records per row; more: an overflow row).
@@ -78,13 +78,6 @@ struct DelArgs {
   // the log
   const DelRecord* records; int64_t nrec;
 };
-
-// whether a base is a reported row (include/wfa_hip.h, "deletions")
-__host__ __device__ inline bool del_selected(int64_t depth, int32_t S, int32_t min_depth, int32_t min_permille) {
-  if (depth < min_depth) return false;
-  if (min_permille > 0) return S >= 1 && 1000 * (int64_t)S >= (int64_t)min_permille * depth;
-  return 2 * (int64_t)S > depth;
-}
 
 int launch_del_count(const PileupArgs& a, const DelLogArgs& g, int cu_count, hipStream_t stream);     // count + the two scans
 int launch_del_scatter(const PileupArgs& a, const DelLogArgs& g, int cu_count, hipStream_t stream);   // the records and the starts plane

@@ -8,24 +8,24 @@
 //
 // Record side (k_pileup.hip): the log is two arrays that grow by doubling, InsRecord[records] and one column byte per inserted
 // base.  An add with tracking on is count -> exclusive scan -> scatter, no atomics for the log:
-//   count    wfa_pileup_count_kernel (pileup_walk<PILEUP_COUNT>): a wave per pair, the walk of the table kernel without a store to the table;
+//   count    wfa_pileup_kernel<PILEUP_COUNT>: a wave per pair, the walk of the table kernel without a store to the table;
 //            pair_count[q] = {records, inserted bases} of pair q (zero for a pair that does not contribute)
-//   scan     wfa_ins_scan_kernel twice: the exclusive 64-bit prefixes, the two totals behind them (downloaded: 16 bytes; the log
-//            grows before anything is added)
-//   scatter  wfa_pileup_track_kernel (pileup_walk<PILEUP_TRACK>): the table kernel, which also writes pair q's records from its scanned record offset and
+//   scan     wfa_scan64_kernel twice (k_select.hpp, k_calls.hip): the exclusive 64-bit prefixes, the two totals behind them
+//            (downloaded: 16 bytes; the log grows before anything is added)
+//   scatter  wfa_pileup_kernel<PILEUP_TRACK>: the table kernel, which also writes pair q's records from its scanned record offset and
 //            its column bytes from its scanned base offset.  Every D op of a counted run writes its own column byte (its place: the
 //            pair's base offset + the counted D ops in front of it); the lane at a run's start writes the record when the run ends
 //            inside the 64-op round, otherwise the run stays OPEN: its row, its place in the two arrays and its length so far are
 //            carried wave-uniformly into the next rounds, and lane 0 writes the record in the round where the run ends.
 //
 // Reduction (k_insertions.hip), wfa_hip_pileup_insertions:
-//   select   the chunk count / scan / scatter of the sites (wfa_calls.hpp) under the insertion predicate: the selected rows' global
-//            indices in ascending order, their row columns j, pos, depth, ins_count, overflow, and a bucket size per row (c6; 0 for
-//            an overflow row)
+//   select   the chunk count / scan / scatter of the sites (wfa_calls.hpp, k_select.hpp) under event_selected(depth, c6): the selected
+//            rows' global indices in ascending order, their row columns j, pos, depth, ins_count, overflow, and a bucket size per
+//            row (c6; 0 for an overflow row)
 //   scan     the bucket sizes -> bucket offsets
-//   fill     a thread per record of the log: a binary search of its row among the selected ones; a record on a selected row takes
-//            the next free slot of that row's bucket (an atomic counter per row: the order inside a bucket is whatever scheduling
-//            gives, and nothing that is written out depends on it)
+//   fill     (k_select.hpp, shared with the deletions) a thread per record of the log: a binary search of its row among the selected
+//            ones; a record on a selected row takes the next free slot of that row's bucket (an atomic counter per row: the order
+//            inside a bucket is whatever scheduling gives, and nothing that is written out depends on it)
 //   reduce   a wave per row: every record's multiplicity among the bucket's records, the best under the total order above, and the
 //            number of distinct alleles (the records without an equal one in a lower slot) -> allele_count, allele_len, alleles
 //   scan     allele_len -> the letters' offsets, the last one the total
@@ -80,20 +80,8 @@ struct InsArgs {
   const InsRecord* records; const uint8_t* bases; int64_t nrec;
 };
 
-// whether a base is a reported row (include/wfa_hip.h, "insertions": the ins condition of SITE, or bit 3 of CALL under min_permille 0)
-__host__ __device__ inline bool ins_selected(int64_t depth, int32_t c6, int32_t min_depth, int32_t min_permille) {
-  if (depth < min_depth) return false;
-  if (min_permille > 0) return c6 >= 1 && 1000 * (int64_t)c6 >= (int64_t)min_permille * depth;
-  return 2 * (int64_t)c6 > depth;
-}
-
-int launch_pileup_count(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream);   // count + the two scans
-int launch_pileup_track(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream);   // table + scatter
-int launch_pileup_track_strands(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs& s, int cu_count, hipStream_t stream);   // and the forward table
-int launch_pileup_track_quals(const PileupArgs& a, const InsLogArgs& g, const PileupStrandArgs* s, const PileupQualArgs& u, int cu_count,
-                              hipStream_t stream);   // and the quality table (s: nullptr without strands)
-// out[0 .. n] = the exclusive 64-bit prefix of `n` 32-bit values read with a stride of `stride` words, out[n] the total
-int launch_ins_scan(const uint32_t* in, int stride, uint64_t* out, int64_t n, hipStream_t stream);
+// the record side (k_pileup.hip): the count form of the table kernel + the two scans; the tracking form is launch_pileup's (wfa_pileup.hpp)
+int launch_pileup_count(const PileupArgs& a, const InsLogArgs& g, int cu_count, hipStream_t stream);
 
 int launch_ins_select_count(const InsArgs& a, hipStream_t stream);   // count + scan: c.chunk_off[c.chunks] is the number of rows
 int launch_ins_select(const InsArgs& a, hipStream_t stream);         // scatter of the rows + the scan of the bucket sizes

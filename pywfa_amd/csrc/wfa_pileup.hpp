@@ -15,9 +15,10 @@
 // this layout the atomics of a wave's M ops on one letter fall into one or two 256-byte stretches of that letter's plane, where a
 // row-major table (8 counters per base) would spread them over 64 rows of 32 bytes each (the one-lane-per-row shape).
 //
-// Kernel (k_pileup.hip): one wave per pair, grid-stride; a first pass finds the first and the last M with ballots (as the location
-// pass of wfa_rle.hpp), a second pass takes 64 ops per round: v and h of a lane are the running bases plus the popcounts of the
-// pattern- / text-consuming ballots below the lane; at most two no-return int32 atomicAdds per op.
+// Kernel (k_pileup.hip; wfa_pileup_kernel<MODE, STRANDS, QUALS>, one launcher, launch_pileup): one wave per pair, grid-stride; a first
+// pass finds the first and the last M with ballots (as the location pass of wfa_rle.hpp), a second pass takes 64 ops per round: v and
+// h of a lane are the running bases plus the popcounts of the pattern- / text-consuming ballots below the lane; at most two no-return
+// int32 atomicAdds per op.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,9 +85,9 @@ struct PileupQualArgs {
   int32_t* qtab;             // WFA_PILEUP_COLS planes of PileupArgs::total sums
 };
 
-int launch_pileup(const PileupArgs& a, int cu_count, hipStream_t stream);
-int launch_pileup_strands(const PileupArgs& a, const PileupStrandArgs& s, int cu_count, hipStream_t stream);
-// the table kernel with qualities; s: the strand arguments of a pileup that tracks strands too, or nullptr
-int launch_pileup_quals(const PileupArgs& a, const PileupStrandArgs* s, const PileupQualArgs& u, int cu_count, hipStream_t stream);
+// The table kernel in the form its arguments ask for (k_pileup.hip): g: with the insertion log's records and column bytes (the count
+// pass before it: launch_pileup_count, wfa_insertions.hpp); s: and the forward table; u: and the quality table.  nullptr: without.
+struct InsLogArgs;
+int launch_pileup(const PileupArgs& a, const InsLogArgs* g, const PileupStrandArgs* s, const PileupQualArgs* u, int cu_count, hipStream_t stream);
 
 }  // namespace wfa
