@@ -957,6 +957,73 @@ int wfa_hip_batch_left_align(wfa_hip_batch_t* batch, int64_t* stats /* nullable;
 int wfa_hip_ops_left_align(uint8_t* ops, int64_t ops_len, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen,
                            int64_t* stats /* nullable; [0] runs moved, [1] merges */);
 
+/* ---- SAM fields: POS, soft clips, a SAM CIGAR, NM and MD per pair ---------------------------------------- */
+
+/*
+ * What a batch returns about an alignment is in WFA's vocabulary: op letters M X I D with D meaning "the read inserts" and I meaning
+ * "the read deletes" (the opposite of SAM), coordinates relative to a window, free ends as leading or trailing gap ops, no NM and no
+ * MD.  These entries turn the op string and the text letters the batch holds into the per-read fields a SAM record wants.
+ *
+ * INPUT.  One pair gives its op string, its status, plen and tlen, and its own text letters T[0 .. tlen): the batch's letters, so a
+ * reverse-strand window is already on the text's strand, which is SAM's convention for SEQ.  Op letters are the library's: M and X
+ * consume a pattern base and a text base, D a pattern base only, I a text base only.
+ * FLAGS.  WFA_HIP_SAM_EQX writes = and X instead of folding both into M.  WFA_HIP_SAM_CORE makes the anchors M only; without it the
+ * anchors are M and X.
+ * SPAN.  f is the first anchor op, l the last.  A pair whose status is not 0, whose op string is empty, or that has no anchor op is
+ * UNMAPPED: its row is {-1, 0, 0, 0, 0, 0, 0, 0} and both of its strings are empty.  Without WFA_HIP_SAM_CORE the span runs from the
+ * first to the last op that pairs two bases, as whole-read aligners write it; with it the span is the aligned core of `locations`,
+ * pos is `locations`' text_start, and the clips take the outer mismatches.
+ * ROW.  WFA_HIP_SAM_COLS int32:
+ *   0  pos         the X and I ops before f: 0-based and window-relative (a SAM writer adds the window's start and 1)
+ *   1  ref_len     the M, X and I ops in [f, l]
+ *   2  clip_left   the X and D ops before f
+ *   3  clip_right  the X and D ops after l
+ *   4  nm          the X, I and D ops in [f, l]
+ *   5  cigar_len   the byte length of the CIGAR string
+ *   6  md_len      the byte length of the MD string
+ *   7  query_len   the M, X and D ops in [f, l]
+ * so that clip_left + query_len + clip_right == plen and pos + ref_len <= tlen.
+ * CIGAR.  clip_left and S when clip_left is not zero; then the maximal runs of the span after the mapping M -> M (= under EQX),
+ * X -> M (X under EQX), D -> I, I -> D, each as its decimal length and its letter (a run is maximal AFTER the mapping: without EQX,
+ * MMXM is 4M); then clip_right and S when clip_right is not zero.  Text ops outside the span only move pos.
+ * MD.  The form of samtools calmd, [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*: walk the span with `run`, the M ops since the last event.  An X at
+ * text offset h emits run and the letter T[h], and run = 0.  The first op of a maximal I run (maximal in the op string) emits run, ^
+ * and its letter, and run = 0; every further I of that run emits its letter.  D ops emit nothing and do not break run.  The end emits
+ * run.  A zero run is therefore always written.  Letters are the bytes the batch holds for the text base: ACGT from the 2-bit words,
+ * the stored byte for a pair on the byte path.  There is no wildcard rule: an M is a match whatever the letters are.
+ * Examples (ops, T, flags: CIGAR, MD):
+ *   MMXMIIMDM    ACGTACGT  none  4M2D1M1I1M      2G1^AC2       row 0, 8, 0, 0, 4, 10, 7, 7
+ *   MMXMIIMDM    ACGTACGT  EQX   2=1X1=2D1=1I1=  2G1^AC2
+ *   DDIIIMMMXMD  ACGTACGT  none  2S5M1S          3G1           pos 3, ref_len 5, nm 1
+ *   XMMMX        ACGTA     none  5M              0A3A0         nm 2
+ *   XMMMX        ACGTA     CORE  1S3M1S          3             pos 1, nm 0
+ *   MIIDIIXM     ACGTACG   none  1M2D1I2D2M      1^CG0^TA0C1
+ * Out of scope: FLAG, RNEXT, PNEXT and TLEN (integer arithmetic on the rows of a placement plus these columns); writing SAM or BAM;
+ * hard clips; these fields on placements, pileups and host-buffer batches; feeding unclipped ends to the duplicate marker; lower-case
+ * or wildcard letters in MD beyond "the stored byte".
+ *
+ * Two steps, like wfa_hip_batch_rle_counts / _rle_runs, over the last run of a resident batch (after a wfa_hip_batch_left_align: over
+ * the rewritten strings):
+ *   step 1  wfa_hip_batch_sam_counts: rows[n x 8], and the bytes of all CIGAR and of all MD strings
+ *   step 2  wfa_hip_batch_sam_strings: the two blobs; pair q's strings start at the prefix sums of columns 5 and 6 of the rows
+ * The offsets are made on the device and stay there; the flags of step 1 hold for step 2.  WFA_HIP_EINVAL, nothing launched: what
+ * wfa_hip_batch_summary refuses (a batch of scope score, or without a finished run), unknown flag bits, a missing output, and step 2
+ * without a step 1 since the batch's last run or left alignment.  n = 0 is fine.  Kernels: csrc/wfa_sam.hpp, k_sam.hip (a wave per
+ * pair, two passes around a 64-bit scan).  wfa_hip_batch_sam_kernel_ms: the HIP-event time of both passes of the last two calls.
+ */
+#define WFA_HIP_SAM_COLS 8
+#define WFA_HIP_SAM_EQX  1
+#define WFA_HIP_SAM_CORE 2
+int wfa_hip_batch_sam_counts(wfa_hip_batch_t* batch, int flags, int32_t* rows /* n x 8 */, int64_t* cigar_bytes, int64_t* md_bytes);
+int wfa_hip_batch_sam_strings(wfa_hip_batch_t* batch, uint8_t* cigar /* cigar_bytes */, uint8_t* md /* md_bytes */);
+int wfa_hip_batch_sam_kernel_ms(wfa_hip_batch_t* batch, float* ms);
+
+/* Host only, needs no GPU: the rule for ONE pair, from its op string and its ASCII text: row8, and cigar[0 .. row8[5]) and
+ * md[0 .. row8[6]).  Returns WFA_HIP_OK, or WFA_HIP_EINVAL with nothing written when a buffer is too small, a pointer is missing, a
+ * flag bit is unknown, or the op string does not consume exactly plen pattern and tlen text bases. */
+int wfa_hip_ops_sam(const uint8_t* ops, int64_t ops_len, const uint8_t* text, int32_t tlen, int32_t plen, int flags,
+                    int32_t* row8, uint8_t* cigar, int64_t cigar_cap, uint8_t* md, int64_t md_cap);
+
 /* ---- placement: one row per read from the hits of any number of batches ---------------------------------- */
 
 /*

@@ -161,6 +161,10 @@ SIGNATURES = {
     "wfa_hip_genotypes_quals_host": (_CTYPES, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _i64, _i64p, _vp]),
     "wfa_hip_batch_left_align": (_CTYPES, [_vp, _vp]),
     "wfa_hip_ops_left_align": (_CTYPES, [_vp, _i64, _vp, _i32, _vp, _i32, _vp]),
+    "wfa_hip_batch_sam_counts": (_CTYPES, [_vp, _int, _vp, _i64p, _i64p]),
+    "wfa_hip_batch_sam_strings": (_CTYPES, [_vp, _vp, _vp]),
+    "wfa_hip_batch_sam_kernel_ms": (_CTYPES, [_vp, _floatp]),
+    "wfa_hip_ops_sam": (_CTYPES, [_vp, _i64, _vp, _i32, _i32, _int, _vp, _vp, _i64, _vp, _i64]),
     "wfa_hip_placer_create": (_vp, [_vp, _i64]),
     "wfa_hip_placer_add": (_CTYPES, [_vp] * 6),
     "wfa_hip_placer_add_hits": (_CTYPES, [_vp, _i64] + [_vp] * 7),
@@ -183,6 +187,9 @@ SYMBOLS = list(SIGNATURES)
 CROSS_DENSE, CROSS_COMPLETED, CROSS_TOPK = 1, 2, 4
 CROSS_MAX_K = 64
 SUMMARY_COLS = 10   # M, X, I, D, I runs, D runs, pattern_start, pattern_end, text_start, text_end
+SAM_COLS = 8
+SAM_COLUMNS = ("pos", "ref_len", "clip_left", "clip_right", "nm", "cigar_len", "md_len", "query_len")
+SAM_EQX, SAM_CORE = 1, 2   # WFA_HIP_SAM_EQX: = and X instead of M; WFA_HIP_SAM_CORE: the anchors are M only
 PILEUP_COLS = 8
 PILEUP_COLUMNS = ("A", "C", "G", "T", "other", "del", "ins", "mismatch")
 CALL_CODES = ("A", "C", "G", "T", "other", "del", "no call")   # the low 3 bits of a call byte; CALL_INS: its insertion flag
@@ -607,6 +614,23 @@ def ops_left_align(ops, pattern, text):
     if rc != OK:
         raise ValueError("wfa_hip_ops_left_align: invalid arguments (an op string that does not consume exactly its pair?)")
     return ops, int(stats[0]), int(stats[1])
+
+
+def ops_sam(ops, text, plen, flags=0):
+    """wfa_hip_ops_sam (host only): the SAM fields of one pair from its op string (bytes or a uint8 array of M / X / I / D), its ASCII
+    text and the length of its pattern: (row int32[8] in the columns SAM_COLUMNS, the CIGAR as bytes, the MD string as bytes).
+    ValueError for unknown flag bits or an op string that does not consume exactly its pair."""
+    ops = np.frombuffer(bytes(ops), dtype=np.uint8) if not isinstance(ops, np.ndarray) else np.ascontiguousarray(ops, dtype=np.uint8)
+    text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+    row = np.zeros(SAM_COLS, np.int32)
+    # a token is at most 11 bytes an op (CIGAR) or 12 (MD), the clips and the last number 11 each
+    cigar = np.zeros(11 * ops.size + 22, np.uint8)
+    md = np.zeros(12 * ops.size + 11, np.uint8)
+    rc = lib().wfa_hip_ops_sam(_ptr_or_null(ops), ops.size, _ptr_or_null(text), text.size, int(plen), int(flags), _ptr(row),
+                               _ptr(cigar), cigar.size, _ptr(md), md.size)
+    if rc != OK:
+        raise ValueError("wfa_hip_ops_sam: invalid arguments (unknown flags, or an op string that does not consume exactly its pair?)")
+    return row, cigar[:row[5]].tobytes(), md[:row[6]].tobytes()
 
 
 def _letters_written(rows, bases_cap):
@@ -1686,6 +1710,23 @@ class ResidentBatch(_Handle):
         stats = np.zeros(2, np.int64)
         self._call("wfa_hip_batch_left_align", self._h, _ptr(stats))
         return int(stats[0]), int(stats[1])
+
+    def sam(self, flags=0):
+        """wfa_hip_batch_sam_counts and _sam_strings: the SAM fields of the last scope=full run, made on the GPU (after a
+        ``left_align()``: of the rewritten strings).  Returns (rows int32[n, 8] in the columns SAM_COLUMNS, the CIGAR strings and the MD
+        strings as two uint8 blobs): pair q's strings start at the prefix sums of columns 5 and 6.  ``flags``: SAM_EQX | SAM_CORE."""
+        rows = np.zeros((self.n, SAM_COLS), np.int32)
+        nc, nm = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._call("wfa_hip_batch_sam_counts", self._h, int(flags), _ptr(rows) if self.n else None, ctypes.byref(nc), ctypes.byref(nm))
+        cigar, md = np.zeros(max(nc.value, 1), np.uint8), np.zeros(max(nm.value, 1), np.uint8)
+        self._call("wfa_hip_batch_sam_strings", self._h, _ptr(cigar), _ptr(md))
+        return rows, cigar[:nc.value], md[:nm.value]
+
+    def sam_kernel_ms(self):
+        """wfa_hip_batch_sam_kernel_ms: the HIP-event time of the two passes of the last ``sam()``."""
+        ms = ctypes.c_float(0)
+        self._call("wfa_hip_batch_sam_kernel_ms", self._h, ctypes.byref(ms))
+        return ms.value
 
     def algorithmic_bytes(self):
         return int(lib().wfa_hip_batch_algorithmic_bytes(self._h))

@@ -311,6 +311,33 @@ class _OpsSequence:
         return (self._item(i) for i in range(len(self)))
 
 
+class _TextSequence:
+    """Read-only sequence of ``str`` over a blob of strings laid end to end (``blob`` uint8, ``off`` int64[n + 1]): the CIGAR or MD
+    strings of ``sam=True``, built on access like the items of ``_OpsSequence``."""
+
+    def __init__(self, blob, off):
+        self._blob, self._off = blob, off
+
+    def __len__(self):
+        return len(self._off) - 1
+
+    def _item(self, i):
+        return self._blob[int(self._off[i]):int(self._off[i + 1])].tobytes().decode("latin-1")
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self._item(j) for j in range(*i.indices(len(self)))]
+        n = len(self)
+        if i < 0:
+            i += n
+        if not 0 <= i < n:
+            raise IndexError(i)
+        return self._item(i)
+
+    def __iter__(self):
+        return (self._item(i) for i in range(len(self)))
+
+
 class BatchResults:
     """Results of a whole batch with the Python-side surface pre-computed on the device: ``score``,
     ``status``, run-length encoded CIGARs (``run_off``, ``run_code``, ``run_len``) and ``locations``
@@ -361,6 +388,27 @@ def _summary_dict(rows):
 def _need_full_for_summary(cfg, what="summary=True"):
     if cfg.scope != 1:
         raise ValueError(f"{what} needs scope='full'")
+
+
+def _sam_flags(cfg, sam, eqx, clip_mismatches):
+    """The flags of ``sam=True`` (None without it) after the checks of the three keywords."""
+    if not sam:
+        if eqx or clip_mismatches:
+            raise ValueError(f"{'eqx' if eqx else 'clip_mismatches'}=True needs sam=True")
+        return None
+    _need_full_for_summary(cfg, "sam=True")
+    return (_native.SAM_EQX if eqx else 0) | (_native.SAM_CORE if clip_mismatches else 0)
+
+
+def _sam_dict(rows, cigar, md):
+    """The rows and the two blobs of ``ResidentBatch.sam()`` (chunks joined end to end) as the dict ``sam=True`` returns."""
+    out = {name: np.ascontiguousarray(rows[:, _native.SAM_COLUMNS.index(name)])
+           for name in ("pos", "ref_len", "clip_left", "clip_right", "nm", "query_len")}
+    for name, col, blob in (("cigar", 5, cigar), ("md", 6, md)):
+        off = np.zeros(len(rows) + 1, np.int64)
+        np.cumsum(rows[:, col], out=off[1:])
+        out[name] = _TextSequence(blob, off)
+    return out
 
 
 _CALL_LETTERS = np.frombuffer(b"ACGTN-N", np.uint8)   # (CALL_CODES as letters; deleted bases are dropped before the lookup)
@@ -1268,7 +1316,8 @@ class WavefrontAligner:
             raise ValueError(f"i and j differ in length: {out[0].shape[0]} and {out[1].shape[0]}")
         return out
 
-    def align_pairs(self, patterns, texts=None, *, i=None, j=None, summary=False, left_align=False):
+    def align_pairs(self, patterns, texts=None, *, i=None, j=None, summary=False, left_align=False, sam=False, eqx=False,
+                    clip_mismatches=False):
         """Align the listed pairs (patterns[i[q]], texts[j[q]]) on the GPU, each sequence uploaded once however many pairs name it;
         ``texts=None``: both indices into ``patterns``.  ``patterns`` / ``texts``: lists of ``str`` (uploaded and released inside
         the call) or ``SequenceSet`` handles of ``sequence_set`` (left open).  ``i`` / ``j``: integer arrays of equal length, every
@@ -1280,11 +1329,19 @@ class WavefrontAligner:
         ``summary=True`` (scope full only): dict(score=, status=, summary=) as ``align_batch`` describes, no op strings.
         ``left_align=True`` (scope full only, else ValueError): the op strings are left-aligned on the GPU before anything is read
         (``left_align_ops`` states the rule); ``cigarstrings``, ``cigar_ops`` and ``summary`` are then those of the rewritten
-        strings, the scores stay WFA's."""
+        strings, the scores stay WFA's.
+        ``sam=True`` (scope full only): the SAM fields of every pair are made on the GPU (after the left alignment, when both are
+        asked for) and no op string is returned: dict(score=, status=, sam=dict(pos=, ref_len=, clip_left=, clip_right=, nm=,
+        query_len=, cigar=, md=)), with ``summary=True`` also summary=.  The six numbers are int32 arrays, ``cigar`` and ``md`` lazy
+        sequences of ``str``.  The CIGAR is SAM's: the library's ``D`` (the read inserts) reads ``I`` and its ``I`` reads ``D``;
+        free ends and, with ``clip_mismatches=True``, the mismatches outside the aligned core are soft clips; ``eqx=True`` writes
+        ``=`` and ``X`` for ``M``.  ``pos`` is 0-based in the text of the pair, -1 for a pair without an alignment (its strings are
+        empty).  ``eqx`` or ``clip_mismatches`` without ``sam=True``: ValueError.  (include/wfa_hip.h, "SAM fields", has the rule.)"""
         if summary:
             _need_full_for_summary(self._cfg)
         if left_align:
             _need_full_for_summary(self._cfg, "left_align=True")
+        sam_flags = _sam_flags(self._cfg, sam, eqx, clip_mismatches) if sam or eqx or clip_mismatches else None
         if not isinstance(patterns, (SequenceSet, list)):
             patterns = list(patterns)
         if texts is not None and not isinstance(texts, (SequenceSet, list)):
@@ -1314,23 +1371,24 @@ class WavefrontAligner:
                 hi = min(lo + budget, int(np.searchsorted(words, before + (1 << 31), side="right")))
                 cuts.append(max(hi, lo + 1))
             return self._run_lists(npairs, cuts, lambda lo, hi: self._native.batch_indexed(
-                pset, tset if texts is not None else None, i[lo:hi], j[lo:hi]), summary=summary, left_align=bool(left_align))
+                pset, tset if texts is not None else None, i[lo:hi], j[lo:hi]), summary=summary, left_align=bool(left_align), sam=sam_flags)
         finally:
             for s in mine:
                 s.close()
 
-    def _run_lists(self, npairs, cuts, make, summary=False, each=None, left_align=False):
+    def _run_lists(self, npairs, cuts, make, summary=False, each=None, left_align=False, sam=None):
         """Run the resident batches ``make(lo, hi)`` of the consecutive chunks ``cuts`` of a pair list and join their results.
         ``summary``: the per-pair summary rows instead of op strings.  ``each(rb, lo, hi, score, status)``: called on every chunk's
         batch after its run instead of fetching op strings (``pileup``).  ``left_align``: every chunk's op strings are left-aligned
-        on the GPU after its run, before anything is read from the batch."""
+        on the GPU after its run, before anything is read from the batch.  ``sam``: the flags of ``sam=True`` — the SAM fields of
+        every chunk instead of op strings (beside the summary rows, when both are asked for) — or None."""
         full = self._cfg.scope == 1
         score = np.zeros(npairs, np.int32)
         status = np.zeros(npairs, np.int32)
-        strings = not summary and each is None   # op strings are wanted: as they are for a small list, run-length encoded otherwise
+        strings = not summary and each is None and sam is None   # op strings are wanted: as they are for a small list, run-length encoded otherwise
         small = strings and full and npairs <= 1024 and len(cuts) <= 2
         rows = np.zeros((npairs, _native.SUMMARY_COLS), np.int32) if summary else None
-        ops_res, runs = None, []
+        ops_res, runs, sams = None, [], []
         for lo, hi in zip(cuts[:-1], cuts[1:]):
             rb = make(lo, hi)
             try:
@@ -1343,17 +1401,22 @@ class WavefrontAligner:
                 status[lo:hi] = st
                 if summary:
                     rows[lo:hi] = rb.summary()
-                elif each is not None:
+                if sam is not None:
+                    sams.append(rb.sam(sam))
+                if each is not None:
                     each(rb, lo, hi, sc, st)
                 elif small:
                     ops_res = cig
-                elif full:
+                elif strings and full:
                     runs.append(rb.rle()[:3])
             finally:
                 rb.close()
         out = {"score": score, "status": status}
         if summary:
             out["summary"] = _summary_dict(rows)
+        if sam is not None:
+            parts = list(zip(*sams)) if sams else [[np.zeros((0, _native.SAM_COLS), np.int32)], [np.zeros(0, np.uint8)], [np.zeros(0, np.uint8)]]
+            out["sam"] = _sam_dict(*(np.concatenate(p) for p in parts))
         if not strings:
             return out
         if small or (full and npairs == 0):
@@ -1494,7 +1557,8 @@ class WavefrontAligner:
         return add
 
     def align_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None,
-                      text_start=None, text_len=None, reverse=None, summary=False, left_align=False):
+                      text_start=None, text_len=None, reverse=None, summary=False, left_align=False, sam=False, eqx=False,
+                      clip_mismatches=False):
         """Align windows of resident sequences on the GPU: pair q is bases [pattern_start[q], + pattern_len[q]) of patterns[i[q]],
         reverse-complemented where ``reverse[q]``, against bases [text_start[q], + text_len[q]) of texts[j[q]] (never reversed);
         ``texts=None``: both indices into ``patterns``.  A start left out is 0 for every pair, a length left out runs to the end of
@@ -1508,13 +1572,21 @@ class WavefrontAligner:
         arrays of one length, negative values, a window that ends behind its sequence, or a ``reverse`` that is not boolean / 0-1.
         ``summary=True`` (scope full only): dict(score=, status=, summary=) as ``align_batch`` describes, no op strings.
         ``left_align=True`` (scope full only): as for ``align_pairs``; the letters are the windows', a reversed pattern on the
-        text's strand, and no gap moves left of its window."""
+        text's strand, and no gap moves left of its window.
+        ``sam=True``, ``eqx``, ``clip_mismatches`` (scope full only): as for ``align_pairs``; ``pos`` is in the coordinates of the
+        text SEQUENCE (the window's start is added; -1 stays -1), the read is the window on the text's strand, and the MD letters are
+        the window's."""
         if summary:
             _need_full_for_summary(self._cfg)
         if left_align:
             _need_full_for_summary(self._cfg, "left_align=True")
+        sam_flags = _sam_flags(self._cfg, sam, eqx, clip_mismatches) if sam or eqx or clip_mismatches else None
         with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
-            return w.run(summary=summary, left_align=bool(left_align))
+            out = w.run(summary=summary, left_align=bool(left_align), sam=sam_flags)
+            if sam_flags is not None and w.arrays[4] is not None:
+                pos = out["sam"]["pos"]
+                out["sam"]["pos"] = np.where(pos >= 0, pos + w.arrays[4], pos).astype(np.int32)
+            return out
 
     def pileup(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
                text_len=None, reverse=None, min_score=None, insertions=False, left_align=False, strands=False, qualities=None,

@@ -18,6 +18,7 @@ extern "C" int wfa_hip_batch_left_align(wfa_hip_batch_t* b, int64_t* stats) {
   if (b->n == 0) return WFA_HIP_OK;
   HIP_TRY(al, hipSetDevice(al->device));
   b->rle_total = -1;   // the run-length encoding of the strings as they were
+  b->sam_serial = -1;  // ... and their SAM fields
   StreamScratch sc{al};
   wfa::LeftAlignArgs a;
   memset(&a, 0, sizeof(a));

@@ -222,6 +222,14 @@ struct wfa_hip_batch {
   // device-side result surface (RLE)
   int32_t* d_plen = nullptr; int32_t* d_tlen = nullptr; int32_t* d_run_count = nullptr; int32_t* d_locs = nullptr;
   int64_t* d_run_off = nullptr; int64_t rle_total = -1;
+  // SAM fields (api_sam.hip): the rows of wfa_hip_batch_sam_counts and the two scans of their length columns stay here for
+  // wfa_hip_batch_sam_strings; they hold for the run and the op strings they were made from (run_serial; a left alignment drops them)
+  int64_t run_serial = 0;      // counts the runs of the batch
+  int32_t* d_sam_rows = nullptr; uint64_t* d_sam_off = nullptr;   // n x 8; two arrays of n + 1
+  int64_t sam_serial = -1;     // the run the rows belong to, -1: none
+  int sam_flags = 0;
+  int64_t sam_bytes[2] = {0, 0};   // the CIGAR and MD bytes of all pairs
+  float sam_ms[2] = {0.f, 0.f};    // HIP-event times of the two passes
 };
 
 #define HIP_TRY(al, expr)                                                                      \

@@ -414,7 +414,7 @@ void batch_free(wfa_hip_batch* b) {
   void* ptrs[] = {b->d_bytes, b->d_pboff, b->d_tboff, b->d_meta, b->d_words, b->d_flags, b->d_score, b->d_status,
                   b->d_ops, b->d_cigar_off, b->d_cigar_begin, b->d_cigar_len, b->d_list_packed, b->d_list_bytes,
                   b->d_fb_list2[0], b->d_fb_list2[1], b->d_ovf_list[0], b->d_ovf_list[1], b->d_counters,
-                  b->d_plen, b->d_tlen, b->d_run_count, b->d_locs, b->d_run_off, b->d_len16, b->d_pieces};
+                  b->d_plen, b->d_tlen, b->d_run_count, b->d_locs, b->d_run_off, b->d_len16, b->d_pieces, b->d_sam_rows, b->d_sam_off};
   // blocks go back to the aligner's pool: nothing of this batch may still be running
   const bool timing = b->al->knobs.set[K_TIMING];
   const double t0 = timing ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0.0;
@@ -2997,6 +2997,7 @@ static int batch_run_once(wfa_hip_batch_t* b, void* stream_) {
   } side_guard{al};
   b->last_stream = stream;
   b->ran = true; b->synced = false;
+  b->run_serial += 1;
   b->last_fallback = 0;
   b->last_kernel_pairs = 0;
   if (b->n == 0) { b->synced = true; side_guard.ok = true; return WFA_HIP_OK; }
