@@ -1054,6 +1054,21 @@ int wfa_hip_ops_sam(const uint8_t* ops, int64_t ops_len, const uint8_t* text, in
  * loc_te being exactly columns 8 and 9 of wfa_hip_batch_summary for the pair: the aligned core; for an op string without an M
  * loc_te <= loc_ts, an empty interval.  Scope score: the whole window [t0, t0 + tlen[q]), tlen[q] the batch's own text length.
  *
+ * CLIPS.  Every hit also carries two integers, lead and trail: the bases of the read that the aligned core leaves out on either side.
+ * For a pair whose op string has an M, lead is the number of pattern-consuming ops (X and D) in front of the first M and trail the
+ * number behind the last M, each saturated at WFA_HIP_CLIP_MAX = 65 535.  A pair with no M, an empty op string, plen == 0 or
+ * tlen == 0 has lead = trail = 0, and so has every pair under scope score.  The UNCLIPPED INTERVAL of a hit is
+ *     us = ts - lead,   ue = te + trail                                                                  (64-bit)
+ * where the read's first and last base would land if the clipped ends were laid down without gaps; us may be negative and ue beyond
+ * its text for a read that hangs over an end.  For a mapped pair under wfa_hip_batch_sam_counts with WFA_HIP_SAM_CORE (Python:
+ * sam=True, clip_mismatches=True), whose pos is relative to the window's start t0, lead == clip_left and trail == clip_right below
+ * the cap, so us == t0 + pos - clip_left and ue == t0 + pos + ref_len + clip_right.  The clips share the record's last word: a hit
+ * stays 37 bytes.  wfa_hip_placer_add fills them on the device from the walk that gives the interval; wfa_hip_placer_add_hits_clips
+ * takes them from host arrays (either NULL: 0; a negative value is refused, one above the cap saturated), wfa_hip_placer_add_hits
+ * gives 0.  wfa_hip_placer_read_clips downloads lead and trail of all hits so far (wfa_hip_placer_count int32 each, 32 bytes per
+ * hit cross PCIe): for tests, and for a SAM writer that wants the chosen hit's soft clips.  wfa_hip_ops_clips (host only, no GPU)
+ * states the rule for one op string.  Placement, pairing and rescue never read them; "duplicates" may.
+ *
  * wfa_hip_placer_create: a placer over reads 0 .. nreads - 1 (nreads >= 0), without hits.  37 BYTES PER HIT AND 36 PER READ in HBM
  * (csrc/wfa_place.hpp), the records grown by doubling; a failed allocation: WFA_HIP_EDEVICE, the message names the byte count.
  * wfa_hip_placer_add waits for the batch's last run, as wfa_hip_pileup_add does, and appends its pairs as hits: pair q is a hit of
@@ -1079,6 +1094,15 @@ int  wfa_hip_placer_add(wfa_hip_placer_t* placer, wfa_hip_batch_t* batch, const 
                         const int32_t* t_start /* nullable: 0 */, const uint8_t* reverse /* nullable: forward */);
 int  wfa_hip_placer_add_hits(wfa_hip_placer_t* placer, int64_t n, const int32_t* i, const int32_t* j, const uint8_t* reverse /* nullable */,
                              const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end);
+#define WFA_HIP_CLIP_MAX 65535   /* lead and trail saturate here */
+int  wfa_hip_placer_add_hits_clips(wfa_hip_placer_t* placer, int64_t n, const int32_t* i, const int32_t* j,
+                                   const uint8_t* reverse /* nullable */, const int32_t* score, const int32_t* status,
+                                   const int32_t* text_start, const int32_t* text_end, const int32_t* lead /* nullable: 0 */,
+                                   const int32_t* trail /* nullable: 0 */);
+int  wfa_hip_placer_read_clips(wfa_hip_placer_t* placer, int32_t* lead /* nhits */, int32_t* trail /* nhits */);
+/* Host only, needs no GPU: lead and trail of one op string (ops_len bytes of M, X, I, D) of a pair of plen pattern and tlen text
+ * bases.  WFA_HIP_EINVAL for a NULL output, a negative length or NULL ops with ops_len > 0. */
+int  wfa_hip_ops_clips(const uint8_t* ops, int64_t ops_len, int32_t plen, int32_t tlen, int32_t* lead, int32_t* trail);
 int  wfa_hip_placer_run(wfa_hip_placer_t* placer, int32_t min_score, int32_t full_gap, int32_t* rows /* nreads x 8 */,
                         uint8_t* flags /* nhits, nullable */);
 int64_t wfa_hip_placer_count(const wfa_hip_placer_t* placer);
@@ -1253,16 +1277,29 @@ int wfa_hip_rescue_host(int64_t nreads, int64_t nhits, const int32_t* i, const i
  * unit number (fragment number or read number).
  * BUCKET.  All units, of either kind, with the same (j, b).
  * OVERFLOW.  A bucket with more than WFA_HIP_DUP_MAX_BUCKET units is not resolved: each of its units is alone and carries
- * overflow = 1 (the convention of WFA_HIP_INS_MAX_READS).  A unit whose b lies outside [0, tlen(j)) is alone with overflow = 0; only
- * hits added through wfa_hip_placer_add_hits with invented intervals can have one.
+ * overflow = 1 (the convention of WFA_HIP_INS_MAX_READS).  A unit whose b lies outside [0, tlen(j)) is alone with overflow = 0: on
+ * core coordinates only hits added through wfa_hip_placer_add_hits with invented intervals can have one; on unclipped coordinates
+ * (below) a real read that hangs over an end of its text has one.  A unit whose key coordinate does not fit int32 is alone with
+ * overflow = 0 too; only invented intervals can have one.
  * ROWS.  WFA_HIP_DUP_COLS int32 (16 bytes) each: rep, size, dup, overflow.  For a unit, rep is its group's representative's unit
  * number (its own for the representative and for a unit that is alone), size the number of units in the group, dup = 1 iff rep is not
  * its own number.  A fragment that is not a pair unit gets -1, 0, 0, 0.  A read that is not a read unit gets -1, 0, d, o, with d and o
  * the dup and overflow of its fragment's pair row when it is a mate of a pair unit, and both 0 otherwise: the read rows' dup column
  * alone filters a read list for a pileup.
- * WHAT IT DOES NOT DO.  No unclipped coordinates: under scope full the interval is the aligned core, so a read whose first base
- * mismatches starts one base later and misses its group.  No matching of a lone read against an end of a pair unit.  No optical
- * duplicates, no UMIs, no library or read-group split.  The representative is chosen by alignment score, not by summed base quality.
+ * UNCLIPPED ENDS (wfa_hip_placer_duplicates_ex, WFA_HIP_DUP_UNCLIPPED).  On core coordinates a PCR copy whose first base carries a
+ * substitution, or that starts with a small insertion, begins a base later and misses its group.  Under this flag the rule is the
+ * same except for the coordinates in keys and buckets, which are the unclipped ones of "placement" (CLIPS): a pair unit's key is
+ * (j, us_F, ue_R, first) with b = us_F; a read unit's key is (j, reverse, p5) with p5 = us forward and ue - 1 reverse, b = p5.
+ * Group, place and pair — eligibility, same locus, properness and `insert` — keep the core intervals.  Under scope score the clips
+ * are 0 and the flag changes nothing.
+ * REPRESENTATIVE BY BASE QUALITY (WFA_HIP_DUP_BY_QUALITY).  As short-read pipelines do: qsum(r) is the sum of q over all stored
+ * bases of read r in a quality set with q >= min_quality (0 .. WFA_HIP_MAX_QUALITY; 15 is customary), in 64 bits, saturated to
+ * INT32_MAX.  A read unit's score is qsum(r), a pair unit's qsum(m1) + qsum(m2), saturated the same way; ties still go to the
+ * smallest unit number.  The qualities are those of the whole read, not of a pattern window.
+ * WHAT IT DOES NOT DO.  Without the flags: no unclipped coordinates and the representative by alignment score.  With or without:
+ * no matching of a lone read against an end of a pair unit; no optical duplicates, no UMIs, no library or read-group split; no
+ * hashed plane; clips wider than WFA_HIP_CLIP_MAX saturate.  NOT MEASURED HERE: how many planted copies either rule marks, and what
+ * the flags cost; DESIGN.md section 6.4 holds what tools/probes/dup_ends_index.py gave, or says that it was not run.
  *
  * wfa_hip_placer_duplicates runs group, place and pair on the device exactly as wfa_hip_placer_rescue does, downloads none of their
  * outputs, and marks the duplicates there (csrc/wfa_dup.hpp, k_dup.hip: every unit is one 32-byte record with a 64-bit bucket number,
@@ -1277,7 +1314,25 @@ int wfa_hip_rescue_host(int64_t nreads, int64_t nhits, const int32_t* i, const i
  * WFA_HIP_EINVAL, nothing launched, nothing written (wfa_hip_last_error names the first offending position and its values): what
  * wfa_hip_placer_run_pairs refuses (pair_rows aside); a NULL set or a set of another aligner; a hit whose j is not below the number of
  * texts; NULL read_rows with nreads > 0; NULL pair_rows with nfrag > 0.  A failed allocation: WFA_HIP_EDEVICE with the byte count.
+ *
+ * wfa_hip_placer_duplicates_ex takes the same arguments and flags, quals, min_quality.  flags == 0 with quals == NULL is
+ * wfa_hip_placer_duplicates byte for byte, with its allocations and launches.  WFA_HIP_DUP_UNCLIPPED: the key kernels read the clip
+ * word of the records they load anyway; nothing more is allocated or launched.  WFA_HIP_DUP_BY_QUALITY: `quals` is a quality set of
+ * this aligner over at least nreads reads, read r of the placer being entry r; one more kernel in front of the key kernels (a wave
+ * per read, 16-byte loads of the quality bytes inside the read, byte loads at its unaligned ends, no byte outside the read is
+ * loaded; a wave reduction; no LDS, no atomics) writes qsum, 4 BYTES PER READ kept on the placer from the first such call; the key
+ * kernels take the score from it.  Two calls give identical bytes.  WFA_HIP_EINVAL, nothing launched, in addition: an unknown flag
+ * bit; the quality flag without quals or quals without the flag; min_quality outside 0 .. WFA_HIP_MAX_QUALITY under the flag; a
+ * quality set of another aligner or over fewer than nreads reads.
  */
+#define WFA_HIP_DUP_UNCLIPPED 1
+#define WFA_HIP_DUP_BY_QUALITY 2
+int  wfa_hip_placer_duplicates_ex(wfa_hip_placer_t* placer, const wfa_hip_seqset_t* texts, int32_t min_score, int32_t full_gap,
+                                  int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag,
+                                  const int32_t* mate1 /* nullable */, const int32_t* mate2 /* nullable */,
+                                  int32_t* read_rows /* nreads x 4 */, int32_t* pair_rows /* nfrag x 4, nullable when nfrag == 0 */,
+                                  int flags, const wfa_hip_qualset_t* quals /* NULL without WFA_HIP_DUP_BY_QUALITY */,
+                                  int32_t min_quality);
 #define WFA_HIP_DUP_COLS 4          /* rep, size, dup, overflow */
 #define WFA_HIP_DUP_MAX_BUCKET 4096
 int  wfa_hip_placer_duplicates(wfa_hip_placer_t* placer, const wfa_hip_seqset_t* texts, int32_t min_score, int32_t full_gap,
@@ -1295,6 +1350,20 @@ int wfa_hip_duplicates_host(int64_t nreads, int64_t nhits, const int32_t* i, con
                             const int32_t* mate1 /* nullable */, const int32_t* mate2 /* nullable */, int64_t ntexts,
                             const int32_t* text_len, int32_t* read_rows /* nreads x 4 */, int32_t* pair_rows /* nfrag x 4 */,
                             char* msg, size_t msg_cap);
+/* wfa_hip_duplicates_host plus lead and trail per hit (either nullable: 0; negative: refused; above WFA_HIP_CLIP_MAX: saturated),
+ * flags, and qsum[nreads], the summed base quality of every read (required, and not negative, under WFA_HIP_DUP_BY_QUALITY; NULL
+ * without it): what wfa_hip_placer_add_hits_clips + wfa_hip_placer_duplicates_ex give over a quality set with those sums.
+ * wfa_hip_duplicates_host is this with NULL, NULL, 0, NULL. */
+int wfa_hip_duplicates_host_ex(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse,
+                               const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end,
+                               int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert, int32_t unpaired,
+                               int64_t nfrag, const int32_t* mate1 /* nullable */, const int32_t* mate2 /* nullable */, int64_t ntexts,
+                               const int32_t* text_len, int32_t* read_rows /* nreads x 4 */, int32_t* pair_rows /* nfrag x 4 */,
+                               const int32_t* lead /* nullable */, const int32_t* trail /* nullable */, int flags,
+                               const int32_t* qsum /* nreads, NULL without the quality flag */, char* msg, size_t msg_cap);
+/* Host only: qsum of one read, the sum of quals[k] >= min_quality over its len bytes, 64-bit, saturated to INT32_MAX.  WFA_HIP_EINVAL
+ * for a NULL output, a negative len, NULL quals with len > 0 or min_quality outside 0 .. WFA_HIP_MAX_QUALITY. */
+int wfa_hip_qsum_host(const uint8_t* quals, int64_t len, int32_t min_quality, int32_t* out);
 
 /* ---- seed finder: an exact-match k-mer index over a text set, candidate windows for every read ------------ */
 

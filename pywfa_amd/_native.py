@@ -181,6 +181,12 @@ SIGNATURES = {
                             [_i64, _i64p, _vp, _str, _size]),
     "wfa_hip_placer_duplicates": (_CTYPES, [_vp] * 2 + [_i32] * 5 + [_i64] + [_vp] * 4),
     "wfa_hip_duplicates_host": (_CTYPES, _HITS + [_i32] * 5 + [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _str, _size]),
+    "wfa_hip_placer_add_hits_clips": (_CTYPES, [_vp, _i64] + [_vp] * 9),
+    "wfa_hip_placer_read_clips": (_CTYPES, [_vp] * 3),
+    "wfa_hip_ops_clips": (_CTYPES, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "wfa_hip_placer_duplicates_ex": (_CTYPES, [_vp] * 2 + [_i32] * 5 + [_i64] + [_vp] * 4 + [_int, _vp, _i32]),
+    "wfa_hip_duplicates_host_ex": (_CTYPES, _HITS + [_i32] * 5 + [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _int, _vp, _str, _size]),
+    "wfa_hip_qsum_host": (_CTYPES, [_vp, _i64, _i32, _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 
@@ -216,6 +222,8 @@ RESCUE_COLUMNS = ("i", "j", "text_start", "text_len", "reverse", "fragment", "an
 DUP_COLS = 4
 DUP_COLUMNS = ("rep", "size", "dup", "overflow")
 DUP_MAX_BUCKET = 4096   # WFA_HIP_DUP_MAX_BUCKET
+DUP_UNCLIPPED, DUP_BY_QUALITY = 1, 2   # WFA_HIP_DUP_UNCLIPPED: keys on the unclipped ends; WFA_HIP_DUP_BY_QUALITY: scores from base qualities
+CLIP_MAX = 65535        # WFA_HIP_CLIP_MAX
 INT32_MIN = -2**31
 SEED_MAX_N, SEED_MAX_HITS = 16, 4096
 SEED_KEYS = ("j", "reverse", "text_start", "text_len", "hits")   # the int32 arrays of a seed query, and overflow (uint8)
@@ -920,12 +928,52 @@ def rescue_host(nreads, i, j, reverse, score, status, text_start, text_end, mate
     return count.value, rows[:min(count.value, rows.shape[0])]
 
 
+def _clip_arrays(lead, trail, n):
+    """``lead`` and ``trail`` of n hits as the C entries take them: int32 each, or None."""
+    out = []
+    for name, c in (("lead", lead), ("trail", trail)):
+        c = None if c is None else np.ascontiguousarray(c, dtype=np.int32)
+        if c is not None and c.shape != (n,):
+            raise ValueError(f"{name}: one value per hit ({n})")
+        out.append(c)
+    return out
+
+
+def ops_clips(ops, plen, tlen):
+    """wfa_hip_ops_clips (host only): ``(lead, trail)`` of one pair, the pattern bases (X and D ops) in front of the first and behind
+    the last M of its op string, each saturated at CLIP_MAX; (0, 0) without an M or for an empty pair."""
+    ops = np.frombuffer(bytes(ops), dtype=np.uint8) if not isinstance(ops, np.ndarray) else np.ascontiguousarray(ops, dtype=np.uint8)
+    lead, trail = ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = lib().wfa_hip_ops_clips(_ptr(ops) if ops.size else None, ops.size, int(plen), int(tlen), ctypes.byref(lead), ctypes.byref(trail))
+    if rc != OK:
+        raise ValueError("wfa_hip_ops_clips: invalid arguments")
+    return lead.value, trail.value
+
+
+def qsum_host(quals, min_quality=15):
+    """wfa_hip_qsum_host (host only): the sum of the raw phred values of one read (a uint8 array) that are at least ``min_quality``
+    (0 .. 93), saturated to 2^31 - 1."""
+    quals = np.ascontiguousarray(quals, dtype=np.uint8)
+    out = ctypes.c_int32(0)
+    if quals.ndim != 1 or lib().wfa_hip_qsum_host(_ptr(quals) if quals.size else None, quals.size, int(min_quality), ctypes.byref(out)) != OK:
+        raise ValueError(f"wfa_hip_qsum_host: invalid arguments (min_quality = {min_quality}: 0 .. {MAX_QUALITY})")
+    return out.value
+
+
 def duplicates_host(nreads, i, j, reverse, score, status, text_start, text_end, mates, text_len, min_score=INT32_MIN, full_gap=1,
-                    min_insert=0, max_insert=1000, unpaired=0):
+                    min_insert=0, max_insert=1000, unpaired=0, lead=None, trail=None, flags=None, qsum=None):
     """wfa_hip_duplicates_host (host only): ``(read_rows, pair_rows)`` of the duplicate rule over a list of hits in hit-number order and
     the texts' lengths ``text_len`` — int32 of shape (nreads, 4) and (F, 4) in the columns DUP_COLUMNS; what ``Placer.add_hits`` +
-    ``Placer.duplicates`` give.  ``mates`` as for ``pair_host``; 0: the single-end form."""
+    ``Placer.duplicates`` give.  ``mates`` as for ``pair_host``; 0: the single-end form.  With any of ``lead`` / ``trail`` (the clips
+    per hit), ``flags`` (DUP_UNCLIPPED | DUP_BY_QUALITY) or ``qsum`` (int32 per read, for DUP_BY_QUALITY):
+    wfa_hip_duplicates_host_ex."""
     a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
+    ex = not (lead is None and trail is None and flags is None and qsum is None)
+    lead, trail = _clip_arrays(lead, trail, n)
+    if qsum is not None:
+        qsum = np.ascontiguousarray(qsum, dtype=np.int32)
+        if qsum.shape != (max(int(nreads), 0),):
+            raise ValueError(f"qsum: one value per read ({nreads})")
     nfrag, m1, m2 = _mate_ptrs(mates)
     nreads = int(nreads)
     text_len = np.ascontiguousarray(text_len, dtype=np.int32)
@@ -935,11 +983,15 @@ def duplicates_host(nreads, i, j, reverse, score, status, text_start, text_end, 
     pair_rows = np.zeros((max(nfrag, 0), DUP_COLS), np.int32)
     msg = ctypes.create_string_buffer(256)
     p = _ptr_or_null
-    rc = lib().wfa_hip_duplicates_host(nreads, n, p(a["i"]), p(a["j"]), p(a["reverse"]), p(a["score"]), p(a["status"]), p(a["text_start"]),
-                                       p(a["text_end"]), int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired),
-                                       nfrag, m1, m2, text_len.shape[0], p(text_len), p(read_rows), p(pair_rows), msg, 256)
+    head = (nreads, n, p(a["i"]), p(a["j"]), p(a["reverse"]), p(a["score"]), p(a["status"]), p(a["text_start"]), p(a["text_end"]),
+            int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired), nfrag, m1, m2, text_len.shape[0], p(text_len),
+            p(read_rows), p(pair_rows))
+    if ex:   # (qsum: _ptr, so that an empty array is still "given")
+        rc = lib().wfa_hip_duplicates_host_ex(*head, p(lead), p(trail), int(flags or 0), _ptr(qsum), msg, 256)
+    else:
+        rc = lib().wfa_hip_duplicates_host(*head, msg, 256)
     if rc != OK:
-        raise ValueError(f"wfa_hip_duplicates_host: {msg.value.decode()}")
+        raise ValueError(f"wfa_hip_duplicates_host{'_ex' if ex else ''}: {msg.value.decode()}")
     return read_rows, pair_rows
 
 
@@ -1387,11 +1439,23 @@ class Placer(_Handle):
                 raise ValueError(f"{name}: one value per pair of the batch ({batch.n})")
         self._call("wfa_hip_placer_add", self._h, batch._h, _ptr(i), _ptr(j), _ptr(t_start), _ptr(reverse))
 
-    def add_hits(self, i, j, reverse, score, status, text_start, text_end):
-        """wfa_hip_placer_add_hits: hits from host arrays, in list order."""
+    def add_hits(self, i, j, reverse, score, status, text_start, text_end, lead=None, trail=None):
+        """wfa_hip_placer_add_hits: hits from host arrays, in list order.  ``lead`` / ``trail`` (int per hit, either None: 0):
+        wfa_hip_placer_add_hits_clips, the hits' clips (not negative; saturated at CLIP_MAX)."""
         a, n = _hit_arrays(i, j, reverse, score, status, text_start, text_end)
-        self._call("wfa_hip_placer_add_hits", self._h, n,
-                   *[_ptr(a[k]) for k in ("i", "j", "reverse", "score", "status", "text_start", "text_end")])
+        ptrs = [_ptr(a[k]) for k in ("i", "j", "reverse", "score", "status", "text_start", "text_end")]
+        if lead is None and trail is None:
+            self._call("wfa_hip_placer_add_hits", self._h, n, *ptrs)
+        else:
+            lead, trail = _clip_arrays(lead, trail, n)
+            self._call("wfa_hip_placer_add_hits_clips", self._h, n, *ptrs, _ptr(lead), _ptr(trail))
+
+    def clips(self):
+        """wfa_hip_placer_read_clips: ``(lead, trail)``, int32 per hit added so far — the pattern bases in front of the first and behind
+        the last M of each hit's alignment (0 under scope score)."""
+        lead, trail = np.zeros(len(self), np.int32), np.zeros(len(self), np.int32)
+        self._call("wfa_hip_placer_read_clips", self._h, _ptr_or_null(lead), _ptr_or_null(trail))
+        return lead, trail
 
     def run(self, min_score=INT32_MIN, full_gap=1, flags=True):
         """wfa_hip_placer_run over every hit added so far: ``(rows, flags)``, rows int32 of shape (nreads, 8) in the columns
@@ -1432,15 +1496,26 @@ class Placer(_Handle):
                    ctypes.byref(count), _ptr_or_null(rows))
         return count.value, rows[:min(count.value, rows.shape[0])]
 
-    def duplicates(self, texts, mates, min_score=INT32_MIN, full_gap=1, min_insert=0, max_insert=1000, unpaired=0):
+    def duplicates(self, texts, mates, min_score=INT32_MIN, full_gap=1, min_insert=0, max_insert=1000, unpaired=0, unclipped=False,
+                   qualities=None, min_quality=15):
         """wfa_hip_placer_duplicates over every hit added so far: ``(read_rows, pair_rows)``, int32 of shape (nreads, 4) and (F, 4)
         in the columns DUP_COLUMNS — the representative's number, the group's size, 1 for a duplicate, 1 for a bucket too full to
-        resolve.  ``texts``: the SeqSet the hits lie on; ``mates`` as for ``run_pairs``, 0: the single-end form."""
+        resolve.  ``texts``: the SeqSet the hits lie on; ``mates`` as for ``run_pairs``, 0: the single-end form.  ``unclipped=True``
+        (DUP_UNCLIPPED): keys and buckets on the hits' unclipped ends; ``qualities``, a QualSet over the placer's reads
+        (DUP_BY_QUALITY): the representative is the unit with the greatest sum of base qualities of at least ``min_quality``.
+        Either one: wfa_hip_placer_duplicates_ex."""
         nfrag, m1, m2 = _mate_ptrs(mates)
         read_rows = np.zeros((self.nreads, DUP_COLS), np.int32)
         pair_rows = np.zeros((max(nfrag, 0), DUP_COLS), np.int32)
-        self._call("wfa_hip_placer_duplicates", self._h, texts._h, int(min_score), int(full_gap), int(min_insert), int(max_insert),
-                   int(unpaired), nfrag, m1, m2, _ptr_or_null(read_rows), _ptr_or_null(pair_rows))
+        args = (self._h, texts._h, int(min_score), int(full_gap), int(min_insert), int(max_insert), int(unpaired), nfrag, m1, m2,
+                _ptr_or_null(read_rows), _ptr_or_null(pair_rows))
+        if not unclipped and qualities is None:
+            self._call("wfa_hip_placer_duplicates", *args)
+        else:
+            if qualities is not None and not qualities._h:
+                raise ValueError("the quality set is closed")
+            flags = (DUP_UNCLIPPED if unclipped else 0) | (DUP_BY_QUALITY if qualities is not None else 0)
+            self._call("wfa_hip_placer_duplicates_ex", *args, flags, None if qualities is None else qualities._h, int(min_quality))
         return read_rows, pair_rows
 
     def kernel_ms(self):

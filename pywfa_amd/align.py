@@ -1676,8 +1676,58 @@ class WavefrontAligner:
             out = w.run(each=add, left_align=bool(left_align))
             return Pileup(table, out["score"], out["status"], self)
 
+    def _dup_options(self, duplicates, dup_ends, dup_qualities, dup_min_quality):
+        """The duplicate options of ``place_windows`` / ``place_pairs``, checked before anything is uploaded: (unclipped,
+        min_quality)."""
+        if not isinstance(duplicates, (bool, np.bool_)):
+            raise ValueError(f"duplicates must be True or False, got {duplicates!r}")
+        if dup_ends not in ("core", "unclipped"):
+            raise ValueError(f"dup_ends must be 'core' or 'unclipped', got {dup_ends!r}")
+        if not duplicates:
+            for name, given in (("dup_ends", dup_ends != "core"), ("dup_qualities", dup_qualities is not None),
+                                ("dup_min_quality", isinstance(dup_min_quality, (bool, np.bool_)) or dup_min_quality != 15)):
+                if given:
+                    raise ValueError(f"{name} goes with duplicates=True")
+            return False, 15
+        if dup_ends == "unclipped" and self._cfg.scope != 1:
+            raise ValueError("dup_ends='unclipped' needs scope='full': under scope score a hit's interval is its whole window and has no clips")
+        if dup_qualities is None:
+            if isinstance(dup_min_quality, (bool, np.bool_)) or dup_min_quality != 15:
+                raise ValueError("dup_min_quality goes with dup_qualities=: the representative was asked for by alignment score")
+            return dup_ends == "unclipped", 15
+        return dup_ends == "unclipped", _quality_param("dup_min_quality", dup_min_quality, 0)
+
+    def _dup_quality_blob(self, w, dup_qualities):
+        """``dup_qualities`` against the reads of the window list ``w``, before anything is uploaded: None for a ``QualitySet`` (or no
+        qualities), else the blob of ``_quality_blob``."""
+        if dup_qualities is None:
+            return None
+        if isinstance(dup_qualities, QualitySet):
+            if dup_qualities._aligner is not self:
+                raise ValueError("quality set of another aligner")
+            if dup_qualities._set is None or not dup_qualities._set._h:
+                raise ValueError("quality set is closed")
+            have = self._read_lengths(w._patterns)
+            if dup_qualities._set.n != len(have) or not np.array_equal(dup_qualities._set.length, have):
+                raise ValueError(f"the quality set was made for other reads: {dup_qualities._set.n} entries for {len(have)} patterns, or "
+                                 "lengths that differ")
+            return None
+        return _quality_blob(dup_qualities, self._read_lengths(w._patterns), 33)
+
+    def _mark_duplicates(self, w, placer, mates, how, unclipped, dup_qualities, qblob, min_quality):
+        """``placer.duplicates`` inside the entered window list ``w``; a blob of this call is uploaded and closed with the sets."""
+        qset = None
+        if dup_qualities is not None:
+            if qblob is None:
+                qset = dup_qualities._set
+            else:
+                qset = self._native.qualset(w.pset, *qblob)
+                w._mine.append(qset)
+        return placer.duplicates(w.text_set, mates, *how, unclipped=unclipped, qualities=qset, min_quality=min_quality)
+
     def place_windows(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
-                      text_len=None, reverse=None, min_score=None, full_gap=None, duplicates=False):
+                      text_len=None, reverse=None, min_score=None, full_gap=None, duplicates=False, dup_ends="core",
+                      dup_qualities=None, dup_min_quality=15):
         """Align the listed windows as ``align_windows`` does (same arguments, same checks; either scope) and decide on the GPU where
         every PATTERN sequence goes: the patterns are reads, each window one candidate hit of read ``i[q]``.  The rule is that of
         include/wfa_hip.h ("placement"), integers only.  A hit is eligible when its status is 0 and its score at least ``min_score``
@@ -1697,24 +1747,26 @@ class WavefrontAligner:
 
         ``duplicates=True``: DUPLICATE MARKING, single-end (include/wfa_hip.h, "duplicates"; ``place_pairs`` describes it).  Every
         read whose primary has a non-empty interval is a unit with the key (text, strand, 5' end); ``reads`` gains the int32 arrays
-        ``dup``, ``dup_rep``, ``dup_size`` and ``dup_overflow``.  ``duplicates=False`` returns exactly the keys above and neither
-        allocates nor launches anything more."""
+        ``dup``, ``dup_rep``, ``dup_size`` and ``dup_overflow``.  ``dup_ends``, ``dup_qualities`` and ``dup_min_quality`` are those of
+        ``place_pairs``.  ``duplicates=False`` returns exactly the keys above and neither allocates nor launches anything more."""
         min_score, full_gap = self._placement(min_score, full_gap)
-        if not isinstance(duplicates, (bool, np.bool_)):
-            raise ValueError(f"duplicates must be True or False, got {duplicates!r}")
-        with self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse) as w:
+        unclipped, min_quality = self._dup_options(duplicates, dup_ends, dup_qualities, dup_min_quality)
+        w = self._windows(patterns, texts, i, j, pattern_start, pattern_len, text_start, text_len, reverse)
+        qblob = self._dup_quality_blob(w, dup_qualities)
+        with w:
             placer = w.attach(self._native.placer(w.nreads))
             out = w.run(each=self._hits_into(placer, w.arrays))
             rows, out["flag"] = placer.run(min_score, full_gap)
             out["reads"] = _columns(rows, _native.PLACE_COLUMNS)
             if duplicates:
-                read_rows, _ = placer.duplicates(w.text_set, 0, min_score, full_gap)
+                read_rows, _ = self._mark_duplicates(w, placer, 0, (min_score, full_gap), unclipped, dup_qualities, qblob, min_quality)
                 out["reads"].update(_dup_columns(read_rows))
             return out
 
     def place_pairs(self, patterns, texts=None, *, i=None, j=None, pattern_start=None, pattern_len=None, text_start=None,
                     text_len=None, reverse=None, mates=None, min_insert=0, max_insert=1000, unpaired=None, min_score=None,
-                    full_gap=None, rescue=False, rescue_pad=16, rescue_mapq=0, duplicates=False):
+                    full_gap=None, rescue=False, rescue_pad=16, rescue_mapq=0, duplicates=False, dup_ends="core", dup_qualities=None,
+                    dup_min_quality=15):
         """``place_windows`` for paired-end reads (same arguments, same checks; either scope): the listed windows are aligned, every
         read is placed on its own, and then the hits of the two mates of every fragment are joined on the GPU.  The rule is that of
         include/wfa_hip.h ("pairing"), integers only.  ``mates``: an (F, 2) integer array of indices into ``patterns``, fragment f
@@ -1764,9 +1816,17 @@ class WavefrontAligner:
         The mates of a proper fragment are no units of their own, but their ``dup`` and ``dup_overflow`` repeat the fragment's:
         ``reads["dup"] == 0`` alone selects the reads to pile up.  16 bytes per read and per fragment come back; the device keeps
         4 bytes per base of the TEXT SET (a direct-addressed plane: its cost grows with the references, not with the reads) and
-        65 per read.  Not done: unclipped coordinates (the interval is the aligned core, so a read whose first base mismatches
-        starts a base later and misses its group), matching a lone read against an end of a proper fragment, optical duplicates,
-        UMIs, a library or read-group split; the representative is chosen by alignment score, not by summed base quality.
+        65 per read.  ``dup_ends="core"`` keys a unit on the ends of the aligned core, so a copy whose first base mismatches, or
+        that starts with a small insertion, starts a base later and misses its group; ``dup_ends="unclipped"`` (scope full only)
+        keys it on the UNCLIPPED ends instead — where the read's first and last base would land if the bases in front of the
+        first and behind the last match were laid down without gaps (include/wfa_hip.h, "placement": CLIPS).  A unit whose
+        unclipped start hangs over an end of its text is alone.  Placement, pairing and ``insert`` keep the core either way.
+        ``dup_qualities`` (a ``QualitySet`` made for ``patterns``, or what ``quality_set`` takes with offset 33): the
+        representative is the unit with the greatest sum of base qualities of at least ``dup_min_quality`` (0 .. 93; 15 as in
+        Picard and samtools markdup) over its read, or its two reads, instead of the greatest alignment score; one more kernel
+        and 4 bytes per read.  The returned keys are the same under every option.  Any of the three without ``duplicates=True``
+        is a ValueError.  Not done: matching a lone read against an end of a proper fragment, optical duplicates, UMIs, a library
+        or read-group split, clips wider than 65 535 bases, qualities of a pattern window rather than of the whole read.
         ``duplicates=False`` returns exactly the keys above and neither allocates nor launches anything more."""
         min_score, full_gap = self._placement(min_score, full_gap, min_insert=min_insert, max_insert=max_insert, unpaired=unpaired)
         if min_insert is None or max_insert is None or not 0 <= int(min_insert) <= int(max_insert) < 2**31:
@@ -1777,8 +1837,7 @@ class WavefrontAligner:
             raise ValueError(f"unpaired = {unpaired} is out of range (at least 0)")
         if not isinstance(rescue, (bool, np.bool_)):
             raise ValueError(f"rescue must be True or False, got {rescue!r}")
-        if not isinstance(duplicates, (bool, np.bool_)):
-            raise ValueError(f"duplicates must be True or False, got {duplicates!r}")
+        unclipped, min_quality = self._dup_options(duplicates, dup_ends, dup_qualities, dup_min_quality)
         for name, v in (("rescue_pad", rescue_pad), ("rescue_mapq", rescue_mapq)):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{name} must be an integer, got {v!r}")
@@ -1819,6 +1878,7 @@ class WavefrontAligner:
             if again.size:
                 f = int(again.min()) // 2
                 raise ValueError(f"mates[{f}] = ({m[f, 0]}, {m[f, 1]}): read {flat[again.min()]} belongs to an earlier fragment")
+        qblob = self._dup_quality_blob(w, dup_qualities)
         with w:
             placer = w.attach(self._native.placer(nreads))
             out = w.run(each=self._hits_into(placer, w.arrays))
@@ -1850,7 +1910,7 @@ class WavefrontAligner:
                 pairs["rescued"] = ((pairs["proper"] == 1) & ((pairs["hit1"] >= n0) | (pairs["hit2"] >= n0))).astype(np.int32)
                 out["rescue"] = dict(i=ri, j=rj, text_start=rts, text_len=rtl, reverse=rrev, fragment=rfrag, anchor=ranchor)
             if duplicates:
-                read_rows, frag_rows = placer.duplicates(w.text_set, mates, *how)
+                read_rows, frag_rows = self._mark_duplicates(w, placer, mates, how, unclipped, dup_qualities, qblob, min_quality)
                 out["reads"].update(_dup_columns(read_rows))
                 out["pairs"].update(_dup_columns(frag_rows))
             return out

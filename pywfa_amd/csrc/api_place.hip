@@ -20,7 +20,11 @@ int rescue_check(int32_t pad, int32_t min_len, int32_t anchor_mapq, int64_t cap,
                  size_t msg_cap);
 // host_dup.cpp: the check shared with wfa_hip_duplicates_host
 int dup_check(int64_t nreads, int64_t nfrag, const int32_t* read_rows, const int32_t* pair_rows, char* msg, size_t cap);
+int dup_check_flags(int flags, bool have_quals, int32_t min_quality, char* msg, size_t cap);
+int dup_check_clips(int64_t base, int64_t n, const int32_t* lead, const int32_t* trail, char* msg, size_t cap);
 }
+static_assert(WFA_PLACE_CLIP_MAX == WFA_HIP_CLIP_MAX, "clips: the kernels and the ABI");
+static_assert(WFA_DUP_UNCLIPPED == WFA_HIP_DUP_UNCLIPPED && WFA_DUP_BY_QUALITY == WFA_HIP_DUP_BY_QUALITY, "duplicates: the flags of the kernels and of the ABI");
 static_assert(WFA_RESCUE_COLS == WFA_HIP_RESCUE_COLS, "rescue: the kernels and the ABI");
 static_assert(WFA_DUP_COLS == WFA_HIP_DUP_COLS && WFA_DUP_MAX_BUCKET == WFA_HIP_DUP_MAX_BUCKET, "duplicates: the kernels and the ABI");
 static_assert(sizeof(wfa::DupUnit) == 32, "duplicates: a unit record is two 16-byte words");
@@ -47,6 +51,7 @@ struct wfa_hip_placer {
   wfa::DupUnit* d_dup_rec = nullptr;
   wfa::DupUnit* d_dup_sorted = nullptr;
   uint8_t* d_dup_owned = nullptr;
+  int32_t* d_dup_qsum = nullptr;       // [nreads], from the first call under WFA_HIP_DUP_BY_QUALITY on
   hipEvent_t ev[2] = {nullptr, nullptr};
   float last_ms = 0.f;
 };
@@ -62,6 +67,7 @@ extern "C" void wfa_hip_placer_destroy(wfa_hip_placer_t* p) {
   if (p->d_dup_rec) pool_release(al, p->d_dup_rec);
   if (p->d_dup_sorted) pool_release(al, p->d_dup_sorted);
   if (p->d_dup_owned) pool_release(al, p->d_dup_owned);
+  if (p->d_dup_qsum) pool_release(al, p->d_dup_qsum);
   for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
   destroy_end(p);
 }
@@ -161,12 +167,14 @@ extern "C" int wfa_hip_placer_add(wfa_hip_placer_t* p, wfa_hip_batch_t* b, const
   return WFA_HIP_OK;
 }
 
-extern "C" int wfa_hip_placer_add_hits(wfa_hip_placer_t* p, int64_t n, const int32_t* i, const int32_t* j, const uint8_t* reverse,
-                                       const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end) {
+extern "C" int wfa_hip_placer_add_hits_clips(wfa_hip_placer_t* p, int64_t n, const int32_t* i, const int32_t* j, const uint8_t* reverse,
+                                             const int32_t* score, const int32_t* status, const int32_t* text_start,
+                                             const int32_t* text_end, const int32_t* lead, const int32_t* trail) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
   if (n > 0 && (!score || !status || !text_start || !text_end)) return fail_inval(al, "placement: a missing array");
   if (check_inval(al, wfa::place_check_hits, p->nreads, p->nhits, n, i, j, text_start, text_end)) return WFA_HIP_EINVAL;
+  if (check_inval(al, wfa::dup_check_clips, p->nhits, n, lead, trail)) return WFA_HIP_EINVAL;
   if (n == 0) return WFA_HIP_OK;
   HIP_TRY(al, hipSetDevice(al->device));
   const int rc = placer_reserve(p, n);
@@ -175,12 +183,35 @@ extern "C" int wfa_hip_placer_add_hits(wfa_hip_placer_t* p, int64_t n, const int
   for (int64_t q = 0; q < n; ++q) {
     wfa::PlaceHit& h = rec[(size_t)q];
     h.i = i[q]; h.j = j[q]; h.reverse = (reverse && reverse[q]) ? 1 : 0; h.status = status[q];
-    h.score = score[q]; h.ts = text_start[q]; h.te = text_end[q]; h.spare = 0;
+    h.score = score[q]; h.ts = text_start[q]; h.te = text_end[q];
+    h.clips = wfa::place_clip_word(lead ? lead[q] : 0, trail ? trail[q] : 0);
   }
   HIP_TRY(al, hipMemcpyAsync(p->d_hits + p->nhits, rec.data(), (size_t)n * sizeof(wfa::PlaceHit), hipMemcpyHostToDevice, al->stream));
   HIP_TRY(al, hipStreamSynchronize(al->stream));
   placer_note_texts(p, n, j);
   p->nhits += n; p->grouped = -1;
+  return WFA_HIP_OK;
+}
+
+extern "C" int wfa_hip_placer_add_hits(wfa_hip_placer_t* p, int64_t n, const int32_t* i, const int32_t* j, const uint8_t* reverse,
+                                       const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end) {
+  return wfa_hip_placer_add_hits_clips(p, n, i, j, reverse, score, status, text_start, text_end, nullptr, nullptr);
+}
+
+// the clip words of all records, downloaded and split
+extern "C" int wfa_hip_placer_read_clips(wfa_hip_placer_t* p, int32_t* lead, int32_t* trail) {
+  if (!p) return WFA_HIP_EINVAL;
+  wfa_hip_aligner* al = p->al;
+  if (p->nhits > 0 && (!lead || !trail)) return fail_inval(al, "clips: a missing array (%s)", !lead ? "lead" : "trail");
+  if (p->nhits == 0) return WFA_HIP_OK;
+  HIP_TRY(al, hipSetDevice(al->device));
+  std::vector<wfa::PlaceHit> rec((size_t)p->nhits);
+  HIP_TRY(al, hipMemcpyAsync(rec.data(), p->d_hits, (size_t)p->nhits * sizeof(wfa::PlaceHit), hipMemcpyDeviceToHost, al->stream));
+  HIP_TRY(al, hipStreamSynchronize(al->stream));
+  for (int64_t q = 0; q < p->nhits; ++q) {
+    lead[q] = wfa::place_clip_lead(rec[(size_t)q].clips);
+    trail[q] = wfa::place_clip_trail(rec[(size_t)q].clips);
+  }
   return WFA_HIP_OK;
 }
 
@@ -386,11 +417,18 @@ static int placer_ensure_dup(wfa_hip_placer* p, int64_t nbases) {
 
 // group, place and pair as wfa_hip_placer_run_pairs enqueues them, none of their outputs downloaded; then key, scan, scatter and resolve
 // (k_dup.hip).  16 bytes per read and per fragment come back.
-extern "C" int wfa_hip_placer_duplicates(wfa_hip_placer_t* p, const wfa_hip_seqset_t* texts, int32_t min_score, int32_t full_gap,
-                                         int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
-                                         const int32_t* mate2, int32_t* read_rows, int32_t* pair_rows) {
+// Under WFA_HIP_DUP_BY_QUALITY the qsum kernel runs in front of the key kernels; under WFA_HIP_DUP_UNCLIPPED the key kernels take the
+// clip words of the records they load.  flags == 0: the launches and allocations of wfa_hip_placer_duplicates before there were flags.
+extern "C" int wfa_hip_placer_duplicates_ex(wfa_hip_placer_t* p, const wfa_hip_seqset_t* texts, int32_t min_score, int32_t full_gap,
+                                            int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
+                                            const int32_t* mate2, int32_t* read_rows, int32_t* pair_rows, int flags,
+                                            const wfa_hip_qualset_t* quals, int32_t min_quality) {
   if (!p) return WFA_HIP_EINVAL;
   wfa_hip_aligner* al = p->al;
+  if (check_inval(al, wfa::dup_check_flags, flags, quals != nullptr, min_quality)) return WFA_HIP_EINVAL;
+  if (quals && quals->al != al) return fail_inval(al, "duplicates: quality set of another aligner");
+  if (quals && quals->n < p->nreads)
+    return fail_inval(al, "duplicates: the quality set has %lld reads, the placer %lld", (long long)quals->n, (long long)p->nreads);
   if (check_inval(al, wfa::place_check_run, full_gap)) return WFA_HIP_EINVAL;
   if (check_inval(al, wfa::pair_check, p->nreads, min_insert, max_insert, unpaired, nfrag, mate1, mate2)) return WFA_HIP_EINVAL;
   if (!texts) return fail_inval(al, "duplicates: a missing sequence set");
@@ -413,17 +451,35 @@ extern "C" int wfa_hip_placer_duplicates(wfa_hip_placer_t* p, const wfa_hip_seqs
   d.plane = p->d_dup_plane; d.bsum = p->d_dup_bsum; d.rec = p->d_dup_rec; d.sorted = p->d_dup_sorted; d.owned = p->d_dup_owned;
   if (sc.alloc(&d.read_rows, (size_t)p->nreads * WFA_DUP_COLS)) return WFA_HIP_EDEVICE;
   if (nfrag > 0 && sc.alloc(&d.frag_rows, (size_t)nfrag * WFA_DUP_COLS)) return WFA_HIP_EDEVICE;
+  d.flags = flags;
+  if (flags & WFA_DUP_BY_QUALITY) {
+    if (!p->d_dup_qsum && placer_block(al, &p->d_dup_qsum, (size_t)p->nreads, "4 bytes per read, the summed base qualities")) return WFA_HIP_EDEVICE;
+    d.qsum = p->d_dup_qsum;
+  }
   ReduceTimer timer(al, "duplicates", p->nhits, "hits");
   int pair_rc = 0, lrc = 0;
   if ((rc = placer_enqueue_pairs(p, sc, d.pair, min_score, full_gap, min_insert, max_insert, unpaired, nfrag, mate1, mate2, false, &pair_rc)) != WFA_HIP_OK) return rc;
   if (pair_rc == 0) {
     HIP_TRY(al, hipMemsetAsync(d.plane, 0, ((size_t)d.nbases + 1) * sizeof(uint32_t), al->stream));
     HIP_TRY(al, hipMemsetAsync(d.owned, 0, (size_t)p->nreads, al->stream));
-    lrc = wfa::launch_dup(d, al->cu_count, al->stream);
+    if (flags & WFA_DUP_BY_QUALITY) {
+      wfa::DupQsumArgs q;
+      q.quals = quals->d_quals; q.off = quals->d_off; q.len = quals->d_len; q.nreads = p->nreads; q.min_quality = min_quality;
+      q.qsum = p->d_dup_qsum;
+      lrc = wfa::launch_dup_qsum(q, al->cu_count, al->stream);
+    }
+    if (lrc == 0) lrc = wfa::launch_dup(d, al->cu_count, al->stream);
   }
   if ((rc = placer_launched(p, timer, pair_rc, "pairing: kernel launch failed")) != WFA_HIP_OK) return rc;
   if (lrc != 0) { (void)hipStreamSynchronize(al->stream); al->err = "duplicates: kernel launch failed"; return WFA_HIP_EDEVICE; }
   if (sc.download(read_rows, d.read_rows, (size_t)p->nreads * WFA_DUP_COLS)) return WFA_HIP_EDEVICE;
   if (nfrag > 0 && sc.download(pair_rows, d.frag_rows, (size_t)nfrag * WFA_DUP_COLS)) return WFA_HIP_EDEVICE;
   return placer_finish(p);
+}
+
+extern "C" int wfa_hip_placer_duplicates(wfa_hip_placer_t* p, const wfa_hip_seqset_t* texts, int32_t min_score, int32_t full_gap,
+                                         int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
+                                         const int32_t* mate2, int32_t* read_rows, int32_t* pair_rows) {
+  return wfa_hip_placer_duplicates_ex(p, texts, min_score, full_gap, min_insert, max_insert, unpaired, nfrag, mate1, mate2, read_rows, pair_rows,
+                                      0, nullptr, 0);
 }

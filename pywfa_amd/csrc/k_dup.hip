@@ -1,6 +1,7 @@
 // k_dup.hip — duplicate marking after placement (wfa_dup.hpp: rule, layout and the kernels' outline; wfa_hip_placer_duplicates in
 // api_place.hip).
-// Stores: key writes owned[r], rec[r] and read_rows row r only for r < nreads, frag_rows row f for f < nfrag, and adds to plane[bucket]
+// Stores: qsum writes qsum[r] only for r < nreads, and loads the bytes [off[r], off[r] + len[r]) of the quality set and no other (the host
+// has checked that the set covers the reads); key writes owned[r], rec[r] and read_rows row r only for r < nreads, frag_rows row f for f < nfrag, and adds to plane[bucket]
 // only for 0 <= bucket < nbases; the scan writes plane[0 .. nbases] and bsum[chunk]; scatter subtracts from plane[bucket] under the same
 // guard and writes sorted[slot] only for slot < nreads; resolve writes the rows of units and mates inside [0, nfrag) and [0, nreads).
 // Loads are guarded the way the pair and rescue kernels guard them: a mate outside [0, nreads), a hit number outside [0, nhits) or a
@@ -43,6 +44,14 @@ __device__ inline int64_t dup_bucket(const DupArgs& a, int32_t j, int64_t b) {
   return at >= 0 && at < a.nbases ? at : -1;
 }
 
+// the unclipped start and end of a record (its clip word: wfa_place.hpp), 64-bit
+__device__ inline int64_t dup_start(const DupArgs& a, const int4& h1) {
+  return (int64_t)h1.y - ((a.flags & WFA_DUP_UNCLIPPED) ? place_clip_lead(h1.w) : 0);
+}
+__device__ inline int64_t dup_end(const DupArgs& a, const int4& h1) {
+  return (int64_t)h1.z + ((a.flags & WFA_DUP_UNCLIPPED) ? place_clip_trail(h1.w) : 0);
+}
+
 __global__ void __launch_bounds__(256) wfa_dup_key_fragments_kernel(DupArgs a) {
   const PairArgs& A = a.pair;
   const PlaceArgs& P = A.place;
@@ -58,18 +67,24 @@ __global__ void __launch_bounds__(256) wfa_dup_key_fragments_kernel(DupArgs a) {
     a.owned[r1] = 1; a.owned[r2] = 2;
     const int4* h = reinterpret_cast<const int4*>(P.hits + pr.x);
     const int4* g = reinterpret_cast<const int4*>(P.hits + pr.y);
-    const int4 h0 = h[0], h1 = h[1], g1 = g[1];   // i, j, reverse, status | score, ts, te, spare
+    const int4 h0 = h[0], h1 = h[1], g1 = g[1];   // i, j, reverse, status | score, ts, te, clips
     const bool h_fwd = h0.z == 0;
     DupUnit u;
-    u.kind = h_fwd ? 1 : 2; u.end = h_fwd ? g1.z : h1.z; u.score = pr.w; u.unit = (int32_t)f; u.m1 = (int32_t)r1; u.m2 = (int32_t)r2;
-    u.bucket = dup_bucket(a, h0.y, h_fwd ? h1.y : g1.y);
-    if (u.bucket < 0) {   // b outside the text: alone, and its mates follow it
+    const int64_t end = dup_end(a, h_fwd ? g1 : h1);   // te_R, or ue_R
+    u.kind = h_fwd ? 1 : 2; u.end = 0; u.score = pr.w; u.unit = (int32_t)f; u.m1 = (int32_t)r1; u.m2 = (int32_t)r2;
+    if (a.flags & WFA_DUP_BY_QUALITY) {
+      const int64_t q = (int64_t)a.qsum[r1] + a.qsum[r2];
+      u.score = (int32_t)(q > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : q);
+    }
+    u.bucket = end > (int64_t)INT32_MAX ? -1 : dup_bucket(a, h0.y, dup_start(a, h_fwd ? h1 : g1));
+    if (u.bucket < 0) {   // b outside the text (or an end beyond int32): alone, and its mates follow it
       dup_store_row(a.frag_rows, f, (int32_t)f, 1, 0, 0);
       dup_store_row(a.read_rows, r1, -1, 0, 0, 0);
       dup_store_row(a.read_rows, r2, -1, 0, 0, 0);
       dup_store_unit(a.rec + r1, dup_no_unit());
       continue;
     }
+    u.end = (int32_t)end;   // (it fits: the test above)
     dup_store_unit(a.rec + r1, u);
     atomicAdd(&a.plane[u.bucket], 1u);
   }
@@ -89,11 +104,17 @@ __global__ void __launch_bounds__(256) wfa_dup_key_reads_kernel(DupArgs a) {
       dup_store_unit(a.rec + r, dup_no_unit());
       continue;
     }
-    const int4 h0 = *reinterpret_cast<const int4*>(P.hits + s0.x);   // i, j, reverse, status
+    const int4* hp = reinterpret_cast<const int4*>(P.hits + s0.x);
+    const int4 h0 = hp[0];   // i, j, reverse, status
     const bool rev = h0.z != 0;
     DupUnit u;
-    u.kind = rev ? 4 : 3; u.end = 0; u.score = s0.y; u.unit = (int32_t)r; u.m1 = -1; u.m2 = -1;
-    u.bucket = dup_bucket(a, h0.y, rev ? (int64_t)s1.w - 1 : (int64_t)s1.z);
+    u.kind = rev ? 4 : 3; u.end = 0; u.score = (a.flags & WFA_DUP_BY_QUALITY) ? a.qsum[r] : s0.y; u.unit = (int32_t)r; u.m1 = -1; u.m2 = -1;
+    int64_t p5 = rev ? (int64_t)s1.w - 1 : (int64_t)s1.z;
+    if (a.flags & WFA_DUP_UNCLIPPED) {   // (the row's interval is the primary's: the clip word comes from its record)
+      const int4 h1 = hp[1];             // score, ts, te, clips
+      p5 = rev ? dup_end(a, h1) - 1 : dup_start(a, h1);
+    }
+    u.bucket = dup_bucket(a, h0.y, p5);
     if (u.bucket < 0) {
       dup_store_row(a.read_rows, r, (int32_t)r, 1, 0, 0);
       dup_store_unit(a.rec + r, dup_no_unit());
@@ -149,6 +170,55 @@ __global__ void __launch_bounds__(256) wfa_dup_resolve_kernel(DupArgs a) {
       if (u.m2 >= 0 && u.m2 < nreads) dup_store_row(a.read_rows, u.m2, -1, 0, dup, overflow);
     }
   }
+}
+
+// ---- qsum (wfa_dup.hpp) ----
+
+// the bytes of a word that are at least minq, summed
+__device__ inline uint32_t dup_qsum_word(uint32_t w, uint32_t minq) {
+  uint32_t s = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t q = (w >> (8 * k)) & 0xffu;
+    s += q >= minq ? q : 0u;
+  }
+  return s;
+}
+
+__global__ void __launch_bounds__(256) wfa_dup_qsum_kernel(DupQsumArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const uint32_t minq = (uint32_t)a.min_quality;
+  for (int64_t r = wave; r < a.nreads; r += nwaves) {
+    const int64_t len = a.len[r] > 0 ? a.len[r] : 0;
+    const uint8_t* p = a.quals + a.off[r];
+    // [0, head) and [head + 16 * chunks, len) by bytes, the chunks between them 16-byte aligned: all of it inside [0, len)
+    const int64_t to_edge = (int64_t)((16u - (uint32_t)((uintptr_t)p & 15u)) & 15u);
+    const int64_t head = to_edge < len ? to_edge : len;
+    const int64_t chunks = (len - head) >> 4, tail_at = head + (chunks << 4), tail = len - tail_at;
+    unsigned long long sum = 0;
+    if (lane < head) { const uint32_t q = p[lane]; sum += q >= minq ? q : 0u; }
+    if (lane >= 16 && lane - 16 < tail) { const uint32_t q = p[tail_at + lane - 16]; sum += q >= minq ? q : 0u; }
+    const uint4* c = reinterpret_cast<const uint4*>(p + head);
+    for (int64_t k = lane; k < chunks; k += 64) {
+      const uint4 v = c[k];
+      sum += dup_qsum_word(v.x, minq) + dup_qsum_word(v.y, minq) + dup_qsum_word(v.z, minq) + dup_qsum_word(v.w, minq);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint32_t lo = __shfl_xor((uint32_t)sum, off), hi = __shfl_xor((uint32_t)(sum >> 32), off);
+      sum += ((unsigned long long)hi << 32) | lo;
+    }
+    if (lane == 0) a.qsum[r] = (int32_t)(sum > (unsigned long long)INT32_MAX ? (unsigned long long)INT32_MAX : sum);
+  }
+}
+
+int launch_dup_qsum(const DupQsumArgs& a, int cu_count, hipStream_t stream) {
+  if (a.nreads <= 0) return 0;
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.nreads + 3) / 4, (int64_t)cu_count * 16));
+  hipLaunchKernelGGL(wfa_dup_qsum_kernel, dim3(grid), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_dup(const DupArgs& a, int cu_count, hipStream_t stream) {

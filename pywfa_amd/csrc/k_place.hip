@@ -12,28 +12,28 @@
 
 namespace wfa {
 
-__device__ inline PlaceHit place_hit_of(const PlaceRecordArgs& a, int64_t q, int32_t ts, int32_t te) {
+__device__ inline PlaceHit place_hit_of(const PlaceRecordArgs& a, int64_t q, int32_t ts, int32_t te, int32_t clips) {
   PlaceHit h;
   h.i = a.i[q]; h.j = a.j[q]; h.reverse = (a.reverse && a.reverse[q]) ? 1 : 0; h.status = a.status[q];
-  h.score = a.score[q]; h.ts = ts; h.te = te; h.spare = 0;
+  h.score = a.score[q]; h.ts = ts; h.te = te; h.clips = clips;
   return h;
 }
 
 __device__ inline void place_store(PlaceHit* dst, const PlaceHit& h) {
   int4* d = reinterpret_cast<int4*>(dst);
   d[0] = make_int4(h.i, h.j, h.reverse, h.status);
-  d[1] = make_int4(h.score, h.ts, h.te, h.spare);
+  d[1] = make_int4(h.score, h.ts, h.te, h.clips);
 }
 
 __device__ inline PlaceHit place_load(const PlaceHit* src) {
   const int4* s = reinterpret_cast<const int4*>(src);
   const int4 a = s[0], b = s[1];
   PlaceHit h;
-  h.i = a.x; h.j = a.y; h.reverse = a.z; h.status = a.w; h.score = b.x; h.ts = b.y; h.te = b.z; h.spare = b.w;
+  h.i = a.x; h.j = a.y; h.reverse = a.z; h.status = a.w; h.score = b.x; h.ts = b.y; h.te = b.z; h.clips = b.w;
   return h;
 }
 
-// scope full: the aligned core of the pair's op string, in text coordinates
+// scope full: the aligned core of the pair's op string, in text coordinates, and the pattern bases on either side of it
 __global__ void __launch_bounds__(256) wfa_place_record_full_kernel(PlaceRecordArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -44,7 +44,8 @@ __global__ void __launch_bounds__(256) wfa_place_record_full_kernel(PlaceRecordA
     const SummaryScan s = summary_scan(a.ops + a.cigar_begin[q], len, lane);
     const bool zero = (len == 0) || plen == 0 || tlen == 0;
     const int32_t t0 = a.t_start ? a.t_start[q] : 0;
-    if (lane == 0) place_store(a.out + q, place_hit_of(a, q, t0 + (zero ? 0 : s.head_t), t0 + (zero ? 0 : tlen - s.tail_t)));
+    const int32_t clips = zero || s.nm == 0 ? 0 : place_clip_word(s.head_p, s.tail_p);
+    if (lane == 0) place_store(a.out + q, place_hit_of(a, q, t0 + (zero ? 0 : s.head_t), t0 + (zero ? 0 : tlen - s.tail_t), clips));
   }
 }
 
@@ -53,7 +54,7 @@ __global__ void __launch_bounds__(256) wfa_place_record_score_kernel(PlaceRecord
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < a.npairs; q += nthreads) {
     const int32_t t0 = a.t_start ? a.t_start[q] : 0;
-    place_store(a.out + q, place_hit_of(a, q, t0, t0 + a.meta[q].tlen));
+    place_store(a.out + q, place_hit_of(a, q, t0, t0 + a.meta[q].tlen, 0));
   }
 }
 

@@ -26,7 +26,7 @@ __device__ inline bool rescue_slot(const RescueArgs& a, int64_t s, RescueRow* w)
   const int32_t hit = se[0], mapq = se[3];
   if (hit < 0 || (int64_t)hit >= P.nhits || mapq < a.anchor_mapq) return false;
   const int4* rec = reinterpret_cast<const int4*>(P.hits + hit);
-  const int4 x = rec[0], y = rec[1];   // i, j, reverse, status | score, ts, te, spare
+  const int4 x = rec[0], y = rec[1];   // i, j, reverse, status | score, ts, te, clips
   const int32_t j = x.y, rev = x.z, ts = y.y, te = y.z;
   if (te <= ts || j < 0 || (int64_t)j >= a.ntexts) return false;
   const int64_t len_o = a.read_len[ro], tlen = a.text_len[j];

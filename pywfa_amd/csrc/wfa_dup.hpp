@@ -7,6 +7,9 @@
 // te - 1 reverse, score the single-end one's, bucket position p5.  A group is the units of one kind with equal keys, its representative
 // the unit of greatest score, then of smallest number.  A bucket — all units of one (j, b) — above WFA_DUP_MAX_BUCKET units is not
 // resolved: each of its units is alone with overflow = 1.  A unit whose b is outside its text is alone with overflow = 0.
+// Under WFA_DUP_UNCLIPPED the coordinates of keys and buckets are the unclipped ones (ts - lead, te + trail, from the clip word of the
+// records the key kernels load anyway); `end` then carries ue_R and the bucket us_F, so the record stays 32 bytes and scan, scatter
+// and resolve are the same.  Under WFA_DUP_BY_QUALITY a unit's score is the summed base quality of its read(s), from qsum[].
 //
 // Layout on the device, kept on the placer from the first call on: a plane of one 4-byte counter per base of the text set and one
 // more, direct-addressed by the set's resident base offsets (bucket = boff[j] + b), with the scan's chunk sums; 32 bytes per read for
@@ -15,6 +18,10 @@
 // (a read unit) or of its mate 1 (a pair unit): a read is in at most one fragment, so no two units share a slot.
 //
 // Kernels (k_dup.hip), after the pair kernel, so they read the pair rows, the single-end rows and the records in HBM:
+//   qsum     (WFA_DUP_BY_QUALITY only, before key.)  A wave per read, grid-stride.  The read's bytes between its first and last 16-byte
+//            boundary are taken as 16-byte loads, a lane a chunk; the up to 15 bytes in front and behind by one predicated byte load
+//            a lane: NO LOAD TOUCHES A BYTE OUTSIDE THE READ.  Per byte a compare with min_quality and an add, 64-bit lane sums, a
+//            wave reduction by shuffles, lane 0 stores the sum saturated to INT32_MAX.  No LDS, no atomics.
 //   key      two launches.  fragments: a thread per fragment, grid-stride.  A proper fragment marks its mates in the owner plane (1 for
 //            mate 1, whose slot holds the record, 2 for mate 2), loads its two chosen records and, with b inside the text, stores the
 //            unit record and does one atomicAdd on plane[bucket]; with b outside it stores its final row (alone) and an empty record.
@@ -37,6 +44,8 @@ namespace wfa {
 
 #define WFA_DUP_COLS 4
 #define WFA_DUP_MAX_BUCKET 4096
+#define WFA_DUP_UNCLIPPED 1     // DupArgs::flags: keys and buckets on the unclipped ends
+#define WFA_DUP_BY_QUALITY 2    // DupArgs::flags: scores from qsum
 
 struct alignas(16) DupUnit {
   int64_t bucket;            // boff[j] + b, inside [0, nbases)
@@ -57,7 +66,20 @@ struct DupArgs {
   uint8_t* owned;            // [nreads]: zero before key
   int32_t* read_rows;        // [nreads x WFA_DUP_COLS], 16-byte aligned
   int32_t* frag_rows;        // [nfrag x WFA_DUP_COLS], 16-byte aligned (pair.pair_rows are the pairing's)
+  int flags;                 // WFA_DUP_UNCLIPPED: keys and buckets on the unclipped ends; WFA_DUP_BY_QUALITY: scores from qsum
+  const int32_t* qsum;       // [nreads] after launch_dup_qsum, under WFA_DUP_BY_QUALITY (else nullptr)
 };
+
+// the summed base qualities of every read (k_dup.hip: a wave per read)
+struct DupQsumArgs {
+  const uint8_t* quals;      // the quality set's bytes, read r at off[r], len[r] of them
+  const int64_t* off; const int32_t* len;
+  int64_t nreads;
+  int32_t min_quality;
+  int32_t* qsum;             // [nreads]
+};
+
+int launch_dup_qsum(const DupQsumArgs& a, int cu_count, hipStream_t stream);
 
 int launch_dup(const DupArgs& a, int cu_count, hipStream_t stream);   // key, scan, scatter, resolve (plane and owned zeroed by the caller)
 

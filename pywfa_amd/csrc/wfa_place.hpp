@@ -15,7 +15,9 @@
 // Kernels (k_place.hip):
 //   record   per pair of a batch after its run, one PlaceHit.  Scope full: a wave per pair, the walk of wfa_summary.hpp
 //            (summary_scan: 64 ops per round, ballots) for the text bases in front of the first and behind the last M, so that the
-//            interval is columns 8 and 9 of the summary.  Scope score: a thread per pair, the whole window.
+//            interval is columns 8 and 9 of the summary; the same walk's pattern bases in front of the first and behind the last M,
+//            each saturated at WFA_PLACE_CLIP_MAX, go into the record's clip word (the record stays 32 bytes).  Scope score: a
+//            thread per pair, the whole window, clips 0.
 //   group    count (a thread per hit, one atomicAdd on its read's counter), an inclusive scan of the nreads + 1 counters in the
 //            three passes of the seed index's table (chunk sums, their prefix in one workgroup, apply: a counter becomes the END of
 //            its group), scatter (a thread per hit: atomicSub on the counter gives its slot, the counter ends as the group's BEGIN,
@@ -54,10 +56,12 @@ namespace wfa {
 
 #define WFA_PLACE_COLS 8
 #define WFA_PLACE_SCAN_CHUNK 4096   // counters per workgroup of the scan: 256 threads x 16
+#define WFA_PLACE_CLIP_MAX 65535    // a clip saturates here: two of them share the record's last word
 
 struct alignas(16) PlaceHit {
   int32_t i, j, reverse, status;   // read, text, strand (0 / 1), the pair's status
-  int32_t score, ts, te, spare;    // its score, the text interval [ts, te) in coordinates of text j; spare: 0
+  int32_t score, ts, te, clips;    // its score, the text interval [ts, te) in coordinates of text j; clips: lead | trail << 16
+                                   // (include/wfa_hip.h, "clips": the pattern bases in front of the first and behind the last M)
 };
 
 struct PlaceRecordArgs {
@@ -82,6 +86,15 @@ struct PlaceArgs {
   int32_t* rows;             // [nreads x WFA_PLACE_COLS]
   uint8_t* flags;            // [nhits]
 };
+
+// the clip word of a record, and its halves
+__host__ __device__ inline int32_t place_clip_word(int64_t lead, int64_t trail) {
+  const uint32_t l = (uint32_t)(lead < 0 ? 0 : lead > WFA_PLACE_CLIP_MAX ? WFA_PLACE_CLIP_MAX : lead);
+  const uint32_t t = (uint32_t)(trail < 0 ? 0 : trail > WFA_PLACE_CLIP_MAX ? WFA_PLACE_CLIP_MAX : trail);
+  return (int32_t)(l | (t << 16));
+}
+__host__ __device__ inline int32_t place_clip_lead(int32_t word) { return (int32_t)((uint32_t)word & 0xffffu); }
+__host__ __device__ inline int32_t place_clip_trail(int32_t word) { return (int32_t)((uint32_t)word >> 16); }
 
 int launch_place_record(const PlaceRecordArgs& a, bool full, int cu_count, hipStream_t stream);
 int launch_place_scan(uint32_t* count, int64_t n, uint32_t* bsum, hipStream_t stream);   // count[0 .. n) to its inclusive prefix, in place

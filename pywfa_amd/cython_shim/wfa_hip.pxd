@@ -171,3 +171,21 @@ cdef extern from "wfa_hip.h" nogil:
                             int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert, int32_t unpaired,
                             int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int64_t ntexts, const int32_t* text_len,
                             int32_t* read_rows, int32_t* pair_rows, char* msg, size_t msg_cap)
+    # clips of every hit, duplicates on unclipped ends, the representative by summed base quality (include/wfa_hip.h: "placement" CLIPS,
+    # "duplicates")
+    int wfa_hip_placer_add_hits_clips(wfa_hip_placer_t* placer, int64_t n, const int32_t* i, const int32_t* j, const uint8_t* reverse,
+                            const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end,
+                            const int32_t* lead, const int32_t* trail)
+    int wfa_hip_placer_read_clips(wfa_hip_placer_t* placer, int32_t* lead, int32_t* trail)
+    int wfa_hip_ops_clips(const uint8_t* ops, int64_t ops_len, int32_t plen, int32_t tlen, int32_t* lead, int32_t* trail)
+    int wfa_hip_placer_duplicates_ex(wfa_hip_placer_t* placer, const wfa_hip_seqset_t* texts, int32_t min_score, int32_t full_gap,
+                            int32_t min_insert, int32_t max_insert, int32_t unpaired, int64_t nfrag, const int32_t* mate1,
+                            const int32_t* mate2, int32_t* read_rows, int32_t* pair_rows, int flags, const wfa_hip_qualset_t* quals,
+                            int32_t min_quality)
+    int wfa_hip_duplicates_host_ex(int64_t nreads, int64_t nhits, const int32_t* i, const int32_t* j, const uint8_t* reverse,
+                            const int32_t* score, const int32_t* status, const int32_t* text_start, const int32_t* text_end,
+                            int32_t min_score, int32_t full_gap, int32_t min_insert, int32_t max_insert, int32_t unpaired,
+                            int64_t nfrag, const int32_t* mate1, const int32_t* mate2, int64_t ntexts, const int32_t* text_len,
+                            int32_t* read_rows, int32_t* pair_rows, const int32_t* lead, const int32_t* trail, int flags,
+                            const int32_t* qsum, char* msg, size_t msg_cap)
+    int wfa_hip_qsum_host(const uint8_t* quals, int64_t len, int32_t min_quality, int32_t* out)
