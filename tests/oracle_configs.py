@@ -28,7 +28,7 @@ FIELDS = tuple(n for n, _ in loader.Config._fields_)
 
 MODULES = ("test_parity_gpu", "test_slim_gpu", "test_wide_gpu", "test_biwfa_gpu", "test_cross_gpu", "test_cross_topk_gpu",
            "test_windows_gpu", "test_summary_gpu", "test_reconfigure_gpu", "test_lane_entry_gpu", "test_lane_window_entry_gpu",
-           "test_lane_winfin_gpu", "test_int16_range_gpu", "test_optimality_gpu")
+           "test_lane_winfin_gpu", "test_int16_range_gpu", "test_optimality_gpu", "test_pipeline_gpu")
 # further GPU modules that hand the oracle configurations written inside their functions: no list of theirs is collected, but the
 # literals in their source are checked against the registry (literal_configs below)
 SCANNED_ONLY = ("test_lane_widths_gpu", "test_lane_probe_gpu", "test_lane_narrow_gpu", "test_baseline_configs_gpu", "test_mailbox_gpu",
@@ -174,6 +174,16 @@ def build_shape(shape):
     if kind == "int16_len":    # tests/int16_common.py: four pairs of exactly L bases with the work at their end
         import int16_common
         return int16_common.length_batch(shape[1], 3100 + shape[1] % 100)
+    if kind == "pipeline":     # tests/pipeline_common.py: 300 listed windows, the rescue windows, the long reads' chain windows
+        import pipeline_common as pc
+        from test_windows_gpu import materialise
+        if shape[1] == 2:
+            reads, W = pc.long_reads()[0], pc.as_rig_list(pc.expected_long()["w"], [len(r) for r in pc.long_reads()[0]])
+        else:
+            reads, e = pc.corpus()[0], pc.expected_placement()
+            lens = [len(r) for r in reads]
+            W = pc.as_rig_list({k: v[:300] for k, v in e["w"].items()}, lens) if shape[1] == 0 else pc.as_rig_list(dict(e["rescue"], text_start=e["rescue"]["text_start"], text_len=e["rescue"]["text_len"]), lens)
+        return _pairs(*materialise(reads, pc.genome()[0], W))
     if kind == "biwfa_levels": # tests/test_biwfa_gpu.py, the level-queue test: 3 kb, 700 and 90 bases
         return _pairs(*zip(*[datagen.pair_strings(b, i) for b in (datagen.generate(3, 3000, 0.10, 99), datagen.generate(20, 700, 0.15, 98),
                                                                    datagen.generate(20, 90, 0.1, 97)) for i in range(len(b["p_len"]))]))
@@ -290,6 +300,7 @@ SOURCES = [
     ("test_int16_range_gpu", "KWS", lambda i, item: [dict(item[1], scope=s) for s in ("score", "full")] if "scope" not in item[1] else [item[1]],
      lambda i, r, kw: [("int16_len", 32000)] + ([("int16_len", 16000)] if kw.get("distance") == "affine2p" else [])),
     ("test_optimality_gpu", "HEUR", lambda i, item: [dict(item[1], scope="full")], lambda i, r, kw: [("optimality", r[0])]),
+    ("test_pipeline_gpu", "ORACLE_KWS", _same, lambda i, r, kw: [("pipeline", i)]),
 ]
 
 # configuration lists of MODULES that never reach the oracle

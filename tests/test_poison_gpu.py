@@ -251,6 +251,35 @@ def module_case(module, name, *args):
     return step
 
 
+def first_aligner_shared(step):
+    """`step` with only the FIRST aligner its body creates being the shared one: a body that holds two aligners of different
+    configurations at once (a scope-score one beside the one under test) gets a fresh aligner for every further one, and closes it
+    itself."""
+    def wrapped(gpu, monkeypatch):
+        same, made = _native.Aligner, []
+
+        def once(cfg, device=0):
+            made.append(cfg)
+            return same(cfg, device) if len(made) == 1 else SharedAligner.__bases__[0](cfg, device)
+
+        monkeypatch.setattr(_native, "Aligner", once)
+        step(gpu, monkeypatch)
+    wrapped.__doc__ = step.__doc__
+    return wrapped
+
+
+def step_pipeline(gpu, monkeypatch):
+    """The whole paired-read pipeline with its handles held open (tests/test_pipeline_gpu.py, case 1), every call against the composed
+    reference of pipeline_common."""
+    import pipeline_common as pc
+    import test_pipeline_gpu as pipeline
+    wa = pywfa_amd.WavefrontAligner(**pc.KW)
+    try:
+        pipeline.test_handles_held_open_and_the_three_hand_off_traps(wa)
+    finally:
+        wa.close()
+
+
 MP = object()
 STEPS = [
     ("cross", step_cross),
@@ -266,8 +295,15 @@ STEPS = [
     ("placer-run", module_case("test_place_gpu", "test_add_hits_and_run_equal_the_host_statement")),
     ("placer-pairs", module_case("test_pair_gpu", "test_run_pairs_equals_the_host_statement_on_random_lists_and_edges")),
     ("rescue", module_case("test_rescue_gpu", "test_rescue_equals_the_host_statement_on_random_cases")),
+    ("sam", first_aligner_shared(module_case("test_sam_gpu", "test_c_abi_two_steps_refusals_and_a_new_run"))),
+    ("sam-leftalign", module_case("test_sam_gpu", "test_left_align_then_sam_and_summary_beside_sam", MP)),
+    ("deletions", module_case("test_deletions_gpu", "test_pieces_orders_stats_and_a_clear", MP, 3, (2, 1, 0))),
+    ("duplicates", module_case("test_dup_gpu", "test_duplicates_between_the_placers_other_runs_and_adds")),
+    ("dup-ends-clips", first_aligner_shared(module_case("test_dup_ends_gpu", "test_record_kernel_stores_the_clips", MP, "edge"))),
+    ("dup-ends-qsum", module_case("test_dup_ends_gpu", "test_quality_sums_at_every_offset_and_length")),
     ("seeds", step_seeds),
     ("cross-again", step_cross),
+    ("pipeline", step_pipeline),
 ]
 
 
@@ -275,7 +311,9 @@ STEPS = [
 def test_resident_set_apis_in_sequence_on_one_aligner(gpu, shared, step, monkeypatch):
     """Score matrix, top-k and pair lists; windows on both strands with summaries, RLE and left-aligned gaps; pileup add / read / calls /
     sites / genotypes with the strand, quality and insertion tracks, a clear and adds that grow the tables; placer run / run_pairs /
-    rescue; the k-mer and minimizer seed indexes with query and chain; the score matrix again — one step per test (a few seconds each),
+    rescue; SAM fields (their rows and offsets are pool blocks kept across the runs of a batch), deletions, duplicates by core and by
+    unclipped ends with the quality sums; the k-mer and minimizer seed indexes with query and chain; the score matrix again; the whole
+    paired-read pipeline — one step per test (a few seconds each),
     in this order on the one aligner of the poison value (pytest keeps the tests of a module-scoped parameter together)."""
     def same_aligner(cfg, device=0):
         shared.set_config(cfg)
